@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json metric on MI355X: 64-bit range proofs verified / second (batch).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--no-extra] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full [--no-extra] [--no-cpu-baseline] [--no-traffic]] [--dump-outputs DIR]
 
 Headline (value): BASELINE.json configs[1].  A step = one engine call = one pass of the hot path (RangeProof::verify:
 transcript replay, decompression, scalar block, weight chain, final MSM) over one resident input of --batches-per-step
@@ -12,10 +12,12 @@ value = steps x batches-per-step x 1024 x N / elapsed.  All 64 batches of a step
 on the box by the engine's own batch prover with the recipe of benches/range_proof.rs:206-262 (the prover's bytes are
 pinned against the oracle in tests/test_gpu_prove.py); every slot holds the same 64 batches in another order.
 
-The same JSON line carries, under "extra", the other BASELINE configs as their own timed legs, each with the roofline of
+With --full the same JSON line carries, under "extra", the other BASELINE configs as their own timed legs, each with the roofline of
 its dominant kernel: configs[2] (256 x aggregation-8), one 4096-proof reference batch on one GPU (north_star's target
 sentence), single-call latency at 1 and 256 proofs (configs[0]'s shape, benches/range_proof.rs:115-119), the batch
-prover on configs[4]; "cpu_baseline" times the oracle/c port on one host core AND on all host cores.
+prover on configs[4]; "cpu_baseline" times the oracle/c port on one host core AND on all host cores.  These legs, the CPU
+baselines and the rocprofv3 traffic passes take about a minute whatever --steps says, so a run without --full times the
+headline alone and lasts about as long as its steps (plus start-up, input generation and the pre-heat).
 
 N > 1: `python bench.py --gpus N` starts `python -m torch.distributed.run` as a CHILD process (before anything touches
 the GPU) and relays its JSON line; under torchrun it runs as one rank per GPU.  value = weak scaling, every rank runs
@@ -69,6 +71,9 @@ def parse_args():
                          "reach the clock it then sustains (tools/clock_ramp.py), and 0.3-0.4 s after a load starts from idle the chip "
                          "holds back for ~40 ms (tools/rate_ramp.py: one 100 ms window at 17 M proofs/s and 2.15 GHz among windows at "
                          "27.5 M and 2.29 GHz) -- the timed region starts behind both; a service under load sees neither")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs, every leg's cpu_baseline and the rocprofv3 traffic passes (the --no-* flags below "
+                         "leave out parts of them); without it only the headline is timed")
     ap.add_argument("--no-extra", action="store_true", help="skip the extra legs (cfg3, 4096-wide, latency, prover)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=5.0, help="CPU work per part (one thread / all cores) of the headline's cpu_baseline")
@@ -91,7 +96,13 @@ def parse_args():
     ap.add_argument("--one-device", action="store_true", default=os.environ.get("BPP_BENCH_ONE_DEVICE", "0") == "1",
                     help="every local rank on device 0 (a rehearsal of the multi-rank code as PROCESSES on a one-GPU box; RCCL refuses "
                          "two ranks on one device, so this implies --transport gloo); the line says so")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the headline's timed steps, write what its last step computed as DIR/<name>.npy (see dump_outputs); "
+                         "the inputs are seeded, so two builds run with the same arguments can be compared output for output")
+    args = ap.parse_args()
+    if not args.full:
+        args.no_extra = args.no_cpu_baseline = args.no_traffic = True
+    return args
 
 
 def usable_cpus():
@@ -416,7 +427,9 @@ class Leg:
             raise RuntimeError("forced failure of step %d (BPP_BENCH_FAIL_STEP)" % FAIL_STEP)
         t0 = time.perf_counter()
         self._call(rb)
-        return time.perf_counter() - t0, eng.last_profile()
+        dt = time.perf_counter() - t0
+        self.last_slot = slot  # the slot whose step finished last: its batch's traces are what dump_outputs() reads
+        return dt, eng.last_profile()
 
     def run_steps(self, count):
         """`count` complete steps, at most len(slots) in flight; returns (latencies, stage profiles).  A step that raises
@@ -461,6 +474,43 @@ class Leg:
             rb.close()
             params.close()
             eng.close()
+
+
+TRACE_CHALLENGES, TRACE_WEIGHTS, TRACE_MSM_RESULT = 1, 3, 6  # bpp_batch_trace selectors (include/bpp.h)
+DUMP_ROWS, DUMP_CHALLENGE_ROWS = 65536, 4096  # proofs whose weights / Fiat-Shamir challenges are written (a seeded sample beyond)
+
+
+def dump_outputs(leg, out_dir):
+    """--dump-outputs: what the leg's last step computed, read back from that step's resident batch, as .npy files in `out_dir`.
+    A VerifyOnly call hands its caller one verdict; under it lie the final MSM point of every reference batch (the identity
+    when the batch verifies), the batch weight of every proof and the Fiat-Shamir challenges of a seeded sample of 4096
+    proofs (*_rows.npy: which input rows).  Rows follow the
+    proofs' order in the inputs (every slot holds them in another order) and bytes are stored as float32, so that the files
+    of two builds compare element for element.  At 65 536 proofs per step the files hold ~13 MB."""
+    import numpy as np
+    slot = leg.last_slot
+    rb, idx, chunk = leg.slots[slot][3], leg.data_idx[slot], leg.chunk
+    n = len(idx)
+    pick = np.random.default_rng(20240601)
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(pick.choice(n, DUMP_ROWS, replace=False))
+    chal_rows = np.sort(pick.choice(n, min(n, DUMP_CHALLENGE_ROWS), replace=False))
+    canon = np.empty(n, dtype=np.int64)
+    canon[idx] = np.arange(n)  # input row -> row of the resident batch
+    weights = np.frombuffer(rb.trace(TRACE_WEIGHTS), dtype=np.uint8).reshape(n, 32)
+    chal = np.frombuffer(rb.trace(TRACE_CHALLENGES), dtype=np.uint8).reshape(n, -1, 32)
+    groups = n // chunk if chunk else 1
+    msm = np.frombuffer(rb.trace(TRACE_MSM_RESULT), dtype=np.uint8).reshape(groups, 32)
+    batch_of_group = idx[::chunk] // chunk if chunk else np.zeros(1, dtype=np.int64)
+    msm_canon = np.empty_like(msm)
+    msm_canon[batch_of_group] = msm
+    out = {"verified": np.ones(groups, dtype=np.float64),  # the call returned Ok: every reference batch of the step verified
+           "msm_result": msm_canon.astype(np.float32),
+           "weights": weights[canon[rows]].astype(np.float32), "weight_rows": rows.astype(np.float64),
+           "challenges": chal[canon[chal_rows]].astype(np.float32), "challenge_rows": chal_rows.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(out)
 
 
 def kernel_roofline(profs, alone_ms=None):
@@ -1100,6 +1150,8 @@ def main():
         if use_dist:
             dist.destroy_process_group()
         raise SystemExit(3)
+    if args.dump_outputs and rank == 0:  # before the calibration steps below run on slot 0
+        dump_outputs(leg, args.dump_outputs)
     if args.only == "headline":
         print(json.dumps({"only": "headline", "proofs_per_s": 1024 * R * args.steps / elapsed}))
         leg.close()

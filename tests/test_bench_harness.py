@@ -92,6 +92,88 @@ def test_forced_failing_step_makes_bench_exit_nonzero():
     assert line["steps_completed"] == 16 and line["all_steps_verified"] is True and line["value"] > 0
 
 
+def test_only_full_runs_the_fixed_length_legs(monkeypatch):
+    """CPU: the extra legs, the CPU baselines and the rocprofv3 passes last about a minute whatever --steps says; a run without
+    --full times the headline alone, so that its length follows --steps"""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"])
+    a = bench.parse_args()
+    assert a.steps == 20 and a.warmup == 5 and a.no_extra and a.no_cpu_baseline and a.no_traffic
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-traffic"])
+    a = bench.parse_args()
+    assert not a.no_extra and not a.no_cpu_baseline and a.no_traffic
+
+
+def test_dump_outputs_rows_follow_the_inputs(tmp_path):
+    """CPU: --dump-outputs reads the traces of the slot that ran the last step, whose resident batch holds the input proofs in
+    its own order; the files hold them in the inputs' order (per proof: weights, challenges; per reference batch: MSM point)"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class FakeBatch:
+        def __init__(self, idx):
+            self.idx = idx
+
+        def trace(self, what):
+            cs = 3  # challenge slots per proof
+            if what == bench.TRACE_WEIGHTS:
+                return bytes(int(i) for i in self.idx for _ in range(32))
+            if what == bench.TRACE_CHALLENGES:
+                return bytes((int(i) * cs + k) % 256 for i in self.idx for k in range(cs) for _ in range(32))
+            assert what == bench.TRACE_MSM_RESULT
+            return bytes(100 + int(i) // 4 for i in self.idx[::4] for _ in range(32))
+    idx = [np.arange(8), np.array([4, 5, 6, 7, 0, 1, 2, 3])]
+    leg = bench.Leg.__new__(bench.Leg)
+    leg.chunk, leg.data_idx, leg.last_slot = 4, idx, 1
+    leg.slots = [(None, None, None, FakeBatch(i)) for i in idx]
+    names = bench.dump_outputs(leg, str(tmp_path / "out"))
+    got = {n: np.load(tmp_path / "out" / (n + ".npy")) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert (got["verified"] == 1.0).all() and got["verified"].shape == (2,)
+    assert (got["weights"] == np.arange(8, dtype=np.float32)[:, None]).all() and got["weights"].shape == (8, 32)
+    assert (got["weight_rows"] == np.arange(8)).all() and (got["challenge_rows"] == np.arange(8)).all()
+    assert (got["challenges"][:, :, 0] == np.arange(24, dtype=np.float32).reshape(8, 3)).all()
+    assert (got["msm_result"][:, 0] == [100, 101]).all() and got["msm_result"].shape == (2, 32)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_what_the_timed_step_computed(tmp_path):
+    """GPU: bench.py --dump-outputs writes the last timed step's outputs of the headline: every reference batch verified, its final
+    MSM point the identity, and per proof the weights and challenges that a verification of the same seeded inputs, made again in
+    this process, computes"""
+    import importlib
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-extra", "--no-cpu-baseline", "--no-traffic", "--steps", "6",
+           "--warmup", "2", "--batches-per-step", "2", "--preheat-ms", "0", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-800:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == line["steps_completed"] == 6 and line["ms_per_step"] > 0
+    got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert sorted(got) == ["challenge_rows", "challenges", "msm_result", "verified", "weight_rows", "weights"]
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert (got["verified"] == 1.0).all() and got["verified"].shape == (2,) and (got["msm_result"] == 0).all()
+    bpp = importlib.import_module("bulletproofs-plus_amd")
+    packed = importlib.import_module("bulletproofs-plus_amd.packed")
+    eng = bpp.Engine(0)
+    params = bpp.RangeParameters.init(64, 1, bpp.create_pedersen_gens_with_extension_degree(1), engine=eng)
+    d = bench.make_inputs(np, packed, params, 2048, seed=8675309)  # the headline's inputs on rank 0
+    rb = packed.ResidentBatch(params, d["proofs"], d["commitments"], d["min_values"], d["min_present"], None, bench.LABEL)
+    rb.verify_only(1024)
+    weights = np.frombuffer(rb.trace(bench.TRACE_WEIGHTS), dtype=np.uint8).reshape(2048, 32)
+    chal = np.frombuffer(rb.trace(bench.TRACE_CHALLENGES), dtype=np.uint8).reshape(2048, -1, 32)
+    rb.close()
+    params.close()
+    eng.close()
+    assert (got["weight_rows"] == np.arange(2048)).all() and (got["weights"] == weights).all()
+    assert (got["challenges"] == chal[got["challenge_rows"].astype(np.int64)]).all()
+
+
 def _oracle_inputs(np, n_bits, m, t, count, seed_nonces):
     """a make_inputs()-shaped data set made by the oracle's prover (CPU): what the engine's prover hands the legs on the box"""
     from oracle import cport

@@ -11,7 +11,7 @@ if [ "$PART" != "b" ]; then
 (cd tools/microbench && (test -x fetch_calib || hipcc -O3 --offload-arch=gfx950 fetch_calib.hip -o fetch_calib))
 timeout -k 10 700 bash tools/profile_round.sh $TAG > $O/${TAG}_profile.log 2>&1
 echo "profile set done"
-timeout -k 10 700 python3 bench.py > $O/${TAG}_bench_full.json 2> $O/${TAG}_bench.err
+timeout -k 10 700 python3 bench.py --full > $O/${TAG}_bench_full.json 2> $O/${TAG}_bench.err
 echo "full bench done"
 timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --no-extra --no-cpu-baseline --no-traffic > $O/${TAG}_bench_steps20.json 2>> $O/${TAG}_bench.err
 timeout -k 10 400 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29512 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra > $O/${TAG}_bench_torchrun1.json 2>> $O/${TAG}_bench.err

@@ -103,7 +103,7 @@ def main():
     ap.add_argument("arms", nargs="+")
     a = ap.parse_args()
     base = {"headline": [sys.executable, "bench.py", "--no-extra", "--no-cpu-baseline", "--no-traffic"],
-            "headline-again": [sys.executable, "bench.py", "--no-cpu-baseline", "--no-traffic"],
+            "headline-again": [sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-traffic"],
             "prover": [sys.executable, "tools/bench_prover_leg.py"], "prover-inflight": [sys.executable, "tools/bench_prove_concurrent.py"],
             "latency": [sys.executable, "tools/bench_latency.py", "--no-cpu"], "cmd": shlex.split(a.cmd)}[a.leg]
     if not base:
