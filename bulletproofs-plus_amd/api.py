@@ -530,6 +530,54 @@ class RangeProof:
         return [RangeProof.from_bytes(raw[i * stride:i * stride + plen.value]) for i in range(n)]
 
     @staticmethod
+    def prove_batch_mixed(transcripts, statements, witnesses, rng_bytes):
+        """n x RangeProof::prove_with_rng of ANY aggregation factors (powers of two up to the parameters' maximum) in one engine
+        call (bpp_prove_batch_mixed).  Returns one entry per item: its RangeProof, or the ProofError that prove_batch on that item
+        alone would raise.  An item that fails never stops the others."""
+        if not statements or len(statements) != len(witnesses) or len(transcripts) != len(statements) or \
+                len(rng_bytes) != len(statements):
+            raise ProofError(ProofErrorKind.InvalidArgument, "Range statements, witnesses, transcripts length mismatch")
+        params = statements[0].generators
+        res = [None] * len(statements)
+        keep = []  # the items that pass this layer's own checks (_prove_marshal's, item by item)
+        for i, (tr, st, w, rb) in enumerate(zip(transcripts, statements, witnesses, rng_bytes)):
+            try:
+                RangeProof._prove_marshal([tr], [st], [w], [rb])
+                keep.append(i)
+            except ProofError as e:
+                res[i] = e
+        if keep:
+            raw, codes, msgs = RangeProof._prove_mixed_call(RangeProof._prove_marshal(
+                [transcripts[i] for i in keep], [statements[i] for i in keep], [witnesses[i] for i in keep],
+                [rng_bytes[i] for i in keep]))
+            for k, i in enumerate(keep):
+                res[i] = RangeProof.from_bytes(raw[k]) if codes[k] == 0 else ProofError(codes[k], msgs[k])
+        return res
+
+    @staticmethod
+    def _prove_mixed_call(marshalled):
+        """bpp_prove_batch_mixed over marshalled items -> (proof bytes per item, codes, messages); an engine fault (a negative code)
+        raises EngineError"""
+        params, items, n, _keep = marshalled
+        eng = params.engine
+        stride = 1 + 32 * (6 + 5 + 2 * 12)
+        out = (ctypes.c_uint8 * (stride * n))()
+        lens = (c_size_t * n)()
+        status = (ctypes.c_int * n)()
+        err = ctypes.create_string_buffer(256)
+        rc = eng.lib.bpp_prove_batch_mixed(eng.ctx, params.handle, items, n, out, stride, lens, status, err, 256)
+        codes = [status[i] for i in range(n)]
+        if rc < 0 or any(c < 0 for c in codes):
+            _check(min([rc] + codes), eng.ctx, err)
+        raw = bytes(out)
+        msgs = [""] * n
+        for i in range(n):
+            if codes[i]:
+                eng.lib.bpp_prove_item_message(eng.ctx, params.handle, ctypes.byref(items[i]), stride, codes[i], err, 256)
+                msgs[i] = err.value.decode(errors="replace")
+        return [raw[i * stride:i * stride + lens[i]] for i in range(n)], codes, msgs
+
+    @staticmethod
     def prove_with_rng(transcript, statement, witness, rng):
         """RangeProof::prove_with_rng; `rng` = object with fill_bytes(n) (the external RNG) or the bytes themselves"""
         need = 32 * (RangeProof.rounds_for(statement) + 3)

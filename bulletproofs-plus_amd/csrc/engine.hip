@@ -3075,3 +3075,4 @@ int bpp_profile_get(bpp_ctx *ctx, bpp_profile *out) {
 #include "engine_batcher.h"
 
 #include "engine_prove.h"
+#include "engine_prove_pool.h"

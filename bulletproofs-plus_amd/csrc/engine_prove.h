@@ -5,9 +5,16 @@
 #pragma once
 
 // ================================================================= batch prover
-extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
-                               size_t proof_stride, size_t *proof_len, char *errbuf, size_t errbuf_len) {
-  BPP_ENTRY(ctx);
+namespace {
+// The body of bpp_prove_batch (the context's lock held, its device current).  dev_status == nullptr: bpp_prove_batch itself, which
+// turns the first device-side status word into the call's error.  Otherwise (bpp_prove_batch_mixed) the status words go to
+// dev_status[i] and every proof is copied out at proof_stride (*proof_len: the longest): whoever called sorts the items out.
+// mixed: the items may have different aggregation factors, sorted largest first (bpp_prove_batch_mixed has checked each one).
+// They run as ragged launches aligned at the end: R = items[0]'s rounds global steps, proof i joins at step R - rounds_i
+// (ProveDesc::roff), and as the proofs are sorted, those active at a step are a prefix of every sub-batch: each round's kernels
+// and fixed-base MSM cover only that prefix.  Every proof reaches the final step in the same launch.
+int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
+                  size_t proof_stride, size_t *proof_len, char *errbuf, size_t errbuf_len, uint32_t *dev_status, bool mixed = false) {
   try {
     const std::shared_ptr<Params> Pp = params_registry().get(params);
     if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
@@ -48,6 +55,14 @@ extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_it
         (void)hipStreamSynchronize(ctx->stream);                                           // call's streams do not wait for the null stream)
       }
     }};
+    auto rounds_of = [&](uint32_t mi) {
+      uint32_t r = 0;
+      while ((1u << r) < mi * n) r++;
+      return r;
+    };
+    uint32_t rounds_min = rounds;  // (the smallest class's rounds: "ct" = 2's ex_back is clamped to it)
+    std::vector<uint32_t> roff(B, 0);
+    std::vector<uint32_t> state_m;  // the aggregation factor each distinct transcript state is for (its "M" append)
     std::vector<uint64_t> minvals((size_t)B * m);
     std::vector<uint8_t> minpres((size_t)B * m);
     std::map<std::string, uint32_t> state_ids;
@@ -55,15 +70,21 @@ extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_it
     for (uint32_t i = 0; i < B; i++) {
       const bpp_prove_item &it = items[i];
       ProveDesc &d = desc[i];
-      if (it.m != m) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "all items of one prove batch must share the aggregation factor"};
+      if (!mixed && it.m != m) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "all items of one prove batch must share the aggregation factor"};
+      if (mixed && (it.m == 0 || (it.m & (it.m - 1)) || it.m > m || (i && it.m > items[i - 1].m)))
+        throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "mixed prove batch: items must be sorted by aggregation factor"};
+      const uint32_t mi = mixed ? it.m : m, rounds_i = mixed ? rounds_of(mi) : rounds, ext_len_i = 32 * (rounds_i + 3);
       if (!it.values || !it.blindings32 || !it.commitments32 || !it.rng_bytes || (!it.min_values && it.min_present))
         throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "null witness / statement field"};
-      if (it.seed_nonce32 && m > 1)
+      if (it.seed_nonce32 && mi > 1)
         throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Mask recovery is not supported with an aggregated statement"};
-      if (it.rng_len < ext_len) throw ProofErr{BPP_ERR_INVALID_LENGTH, "not enough external randomness: need (rounds + 3) * 32 bytes"};
-      d.m = m;
+      if (it.rng_len < ext_len_i) throw ProofErr{BPP_ERR_INVALID_LENGTH, "not enough external randomness: need (rounds + 3) * 32 bytes"};
+      d.m = mi;
+      d.mslot = m;
+      d.roff = roff[i] = rounds - rounds_i;
+      rounds_min = std::min(rounds_min, rounds_i);
       d.minval_idx = i * m;
-      for (uint32_t j = 0; j < m; j++) {
+      for (uint32_t j = 0; j < mi; j++) {
         // :264-271
         if (n < 64 && (it.values[j] >> n) > 0) throw ProofErr{BPP_ERR_INVALID_LENGTH, "Value exceeds bit vector capacity!"};
         const bool present = it.min_present ? it.min_present[j] != 0 : false;
@@ -73,27 +94,27 @@ extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_it
         minvals[(size_t)i * m + j] = mv;
         minpres[(size_t)i * m + j] = present ? 1 : 0;
       }
-      for (uint32_t q = 0; q < m * t; q++)
+      for (uint32_t q = 0; q < mi * t; q++)
         if (!sc_is_canonical(it.blindings32 + 32 * (size_t)q)) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "blinding factor is not canonical"};
       if (it.seed_nonce32 && !sc_is_canonical(it.seed_nonce32)) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "seed nonce is not canonical"};
       d.wit_off = (uint32_t)bytes.size();
-      for (uint32_t j = 0; j < m; j++) {
+      for (uint32_t j = 0; j < mi; j++) {
         uint8_t v8[8];
         for (int k = 0; k < 8; k++) v8[k] = (uint8_t)(it.values[j] >> (8 * k));
         bytes.insert(bytes.end(), v8, v8 + 8);
         bytes.insert(bytes.end(), it.blindings32 + (size_t)j * t * 32, it.blindings32 + (size_t)(j + 1) * t * 32);
       }
       d.commit_off = (uint32_t)bytes.size();
-      bytes.insert(bytes.end(), it.commitments32, it.commitments32 + (size_t)m * 32);
+      bytes.insert(bytes.end(), it.commitments32, it.commitments32 + (size_t)mi * 32);
       d.ext_off = (uint32_t)bytes.size();
-      bytes.insert(bytes.end(), it.rng_bytes, it.rng_bytes + ext_len);
+      bytes.insert(bytes.end(), it.rng_bytes, it.rng_bytes + ext_len_i);
       d.seed_off = (uint32_t)bytes.size();
       d.flags = it.seed_nonce32 ? 1u : 0u;
       if (it.seed_nonce32) bytes.insert(bytes.end(), it.seed_nonce32, it.seed_nonce32 + 32);
       else bytes.insert(bytes.end(), 32, 0);
       // the same transcript source as the previous item (the common case: one label for the whole call): same id, no key, no lookup
       if (i && items[i - 1].transcript_state == it.transcript_state && items[i - 1].transcript_label == it.transcript_label &&
-          items[i - 1].label_len == it.label_len) {
+          items[i - 1].label_len == it.label_len && items[i - 1].m == it.m) {
         d.state_idx = desc[i - 1].state_idx;
         continue;
       }
@@ -105,10 +126,12 @@ extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_it
         key.assign((const char *)it.transcript_label, it.transcript_label ? it.label_len : 0);
         key.push_back('L');
       }
+      key.append((const char *)&mi, sizeof(mi));  // (the state continues with "M" = this proof's aggregation factor)
       auto sit = state_ids.find(key);
       if (sit == state_ids.end()) {
         uint32_t id = (uint32_t)(states.size() / 203);
         states.resize(states.size() + 203);
+        state_m.push_back(mi);
         if (it.transcript_state) {
           memcpy(&states[(size_t)id * 203], it.transcript_state, 203);
           if (states[(size_t)id * 203 + 200] >= BPP_STROBE_R) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "transcript state has pos >= rate"};
@@ -134,7 +157,7 @@ extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_it
       for (uint32_t k = 0; k < t; k++) merlin_append_message(st, (const uint8_t *)"G", 1, &P.hg32[(size_t)(k + 1) * 32], 32);
       merlin_append_u64(st, (const uint8_t *)"N", 1, n);
       merlin_append_u64(st, (const uint8_t *)"T", 1, t);
-      merlin_append_u64(st, (const uint8_t *)"M", 1, m);
+      merlin_append_u64(st, (const uint8_t *)"M", 1, state_m[id]);
       strobe_to_bytes(&states[id * 203], st);
     }
 
@@ -255,7 +278,9 @@ extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_it
     // call's own chain.  2^ex_back points per side and proof; ex_parts slices of <= 128 terms per point.  One round back is the
     // rule ("ct_back" = 2, 3 for the A/B): earlier, the points' MSM doubles the load of a round whose own MSM the chain waits for,
     // and the time the final step no longer spends in an MSM is not given back (profiles/r06_ct_back_ab.txt).
-    const uint32_t ex_back = std::min<uint32_t>(rounds, ctx->opt.ct_back > 0 ? std::min(3, ctx->opt.ct_back) : 1u);
+    // (mixed calls: at most the smallest class's rounds, so that every proof is active at step R - ex_back; the bytes do not depend
+    // on ex_back)
+    const uint32_t ex_back = std::min<uint32_t>(rounds_min, ctx->opt.ct_back > 0 ? std::min(3, ctx->opt.ct_back) : 1u);
     const uint32_t ex_nc = 1u << ex_back, ex_nt = 2 * ex_nc, ex_terms = mn >> ex_back, ex_parts = cdiv(ex_terms, 128u);
     struct Sub {
       uint32_t lo, nb;
@@ -426,9 +451,19 @@ extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_it
         hipStream_t s = lane_stream(q), sm = msm_stream(q);
         const uint32_t nb = u.nb;
         uint8_t *lr_prev = j ? u.d_lr + (size_t)(j - 1) * nb * 64 : nullptr;
+        // the proofs of this sub-batch that take part in step j (all of them in a uniform call): a prefix, roff ascending
+        uint32_t na = nb;
+        while (na && roff[u.lo + na - 1] > j) na--;
+        if (na == 0) {
+          if (j == 0) {  // (the witness check joins all the same: see below)
+            HIP_CHECK(hipStreamWaitEvent(s, ctx->prove_aux_events[4 * q + 1], 0));
+            hipLaunchKernelGGL(kp_check_commitments, dim3(cdiv(nb, 64)), b64, 0, s, u.d_bytes, u.d_desc, u.d_commit32, nb, u.d_ps);
+          }
+          continue;
+        }
         if (fused) {  // the previous round's L / R are encoded by the same launch (kernels_prove.h: kp_round)
           auto launch_round = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(nb), dim3(64 * kp_waves), 0, s, u.d_bytes, u.d_desc, u.d_minvals, u.d_minpres, n, t, n_gen, nb, j, rounds,
+            hipLaunchKernelGGL(kernel, dim3(na), dim3(64 * kp_waves), 0, s, u.d_bytes, u.d_desc, u.d_minvals, u.d_minpres, n, t, n_gen, na, j, rounds,
                                stride, u.d_a32, j ? (parts ? u.d_part : u.d_ge) : (const ge *)nullptr, parts, lr_prev, u.d_ps, u.d_vec, u.d_ts, u.d_tg,
                                u.d_tc, ct ? u.d_fts : (sc *)nullptr, u.d_ftg, u.d_ftc, ct ? u.d_exs : (sc *)nullptr, u.d_exg, u.d_exc, ex_back);
           };
@@ -436,8 +471,8 @@ extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_it
           else if (kp_waves == 2) launch_round(kp_round<2>);
           else launch_round(kp_round<4>);
         } else {
-          hipLaunchKernelGGL(kp_lane, dim3(nb), b64, 0, s, u.d_bytes, u.d_desc, n, t, nb, j, rounds, u.d_a32, lr_prev, u.d_ps);
-          hipLaunchKernelGGL(kp_wave, dim3(nb), b64, 0, s, u.d_bytes, u.d_desc, u.d_minvals, u.d_minpres, n, t, n_gen, j, rounds,
+          hipLaunchKernelGGL(kp_lane, dim3(na), b64, 0, s, u.d_bytes, u.d_desc, n, t, na, j, rounds, u.d_a32, lr_prev, u.d_ps);
+          hipLaunchKernelGGL(kp_wave, dim3(na), b64, 0, s, u.d_bytes, u.d_desc, u.d_minvals, u.d_minpres, n, t, n_gen, j, rounds,
                              stride, u.d_ps, u.d_vec, u.d_ts, u.d_tg, u.d_tc, ct ? u.d_fts : (sc *)nullptr, u.d_ftg, u.d_ftc,
                              ct ? u.d_exs : (sc *)nullptr, u.d_exg, u.d_exc, ex_back);
         }
@@ -460,7 +495,7 @@ extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_it
         fb_mark(sm);
         // (the last launch: three outputs per proof in rows of mn + t + 1 terms, see kp_wave_body)
         const bool three = j == rounds;
-        const uint32_t n_out = (three ? 3 : 2) * nb, row = three ? mn + t + 1 : stride;
+        const uint32_t n_out = (three ? 3 : 2) * na, row = three ? mn + t + 1 : stride;  // (na = nb in the last launch)
         if (parts) {
           hipLaunchKernelGGL(k_fb_part, dim3(n_out * parts), b64, 0, sm, u.d_ts, u.d_tg, u.d_tc, row, parts, P.fb_table.p, P.fb_geo, u.d_part, 1u);
           // a plain point per output where the consumer is not the fused round kernel: the last launch, the unfused form
@@ -495,7 +530,7 @@ extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_it
         if (j == rounds) {  // A1 = A1g + A1h and B
           hipLaunchKernelGGL(kp_final_points, dim3(cdiv(2 * nb, 64)), b64, 0, s, u.d_ge, nb, out);
         } else if (!fused) {
-          hipLaunchKernelGGL(k_compress_ge, dim3(cdiv(2 * nb, 64)), b64, 0, s, u.d_ge, 2 * nb, out);
+          hipLaunchKernelGGL(k_compress_ge, dim3(cdiv(2 * na, 64)), b64, 0, s, u.d_ge, 2 * na, out);
         }
       }
     for (uint32_t q = 0; q < n_sub; q++) {
@@ -547,15 +582,165 @@ extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_it
       pp.fb_windows = P.fb_geo.items;  // additions per term
       pp.sub_batches = n_sub;
     }
-    for (uint32_t i = 0; i < B; i++) {
-      if (pin_status[i] & PV_STATUS_COMMIT_MISMATCH) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Witness opening is invalid!"};
-      if (pin_status[i] & PV_STATUS_TRANSCRIPT)
-        throw ProofErr{BPP_ERR_VERIFICATION_FAILED, "Identity element cannot be added to the transcript / zero challenge"};
+    if (dev_status) {
+      memcpy(dev_status, pin_status, (size_t)B * sizeof(uint32_t));
+    } else {
+      for (uint32_t i = 0; i < B; i++) {
+        if (pin_status[i] & PV_STATUS_COMMIT_MISMATCH) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Witness opening is invalid!"};
+        if (pin_status[i] & PV_STATUS_TRANSCRIPT)
+          throw ProofErr{BPP_ERR_VERIFICATION_FAILED, "Identity element cannot be added to the transcript / zero challenge"};
+      }
     }
     for (uint32_t i = 0; i < B; i++) memcpy(proofs_out + (size_t)i * proof_stride, &pin_proofs[(size_t)i * plen], plen);
     return BPP_OK;
   }
   BPP_CATCH(ctx, errbuf, errbuf_len)
+}
+}  // namespace
+
+extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
+                               size_t proof_stride, size_t *proof_len, char *errbuf, size_t errbuf_len) {
+  BPP_ENTRY(ctx);
+  return prove_uniform(ctx, params, items, n_items, proofs_out, proof_stride, proof_len, errbuf, errbuf_len, nullptr);
+}
+
+// ================================================================= mixed aggregation factors
+// bpp_prove_batch_mixed: items of any power-of-two m up to P.m_max in one call.  Every item is checked on its own, in the order a
+// one-item bpp_prove_batch checks it (the first finding is its status and message); the items that pass are proved as ONE call of
+// ragged launches (prove_uniform with mixed = true, largest m first), whose device-side status words are read item by item.
+// A proof's bytes depend on nothing but its own item (its transcript, its witness, its randomness, and the parameters' N, T and
+// its own M), so every proof equals the one a bpp_prove_batch of its class would make.  DESIGN.md 4.2 has the choice of this form.
+namespace {
+
+struct MixedOutcome {
+  std::vector<int> code;
+  std::vector<std::string> msg;
+};
+
+// the proof length of an item whose m passes RangeStatement::init, 0 otherwise
+size_t prove_item_len(const Params &P, uint32_t m) {
+  if (m == 0 || (m & (m - 1)) || P.m_max < m || m * P.n_bits < 2) return 0;
+  uint32_t rounds = 0;
+  while ((1u << rounds) < m * P.n_bits) rounds++;
+  return 1 + 32 * (size_t)(P.t + 5 + 2 * rounds);
+}
+
+// the host-side checks of a one-item bpp_prove_batch on `it`, in the same order and with the same codes and messages
+void prove_item_check(const Params &P, const bpp_prove_item &it, size_t proof_stride) {
+  const uint32_t n = P.n_bits, t = P.t, m = it.m;
+  if (m == 0 || (m & (m - 1))) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Number of commitments must be a power of two"};
+  if (P.m_max < m) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Not enough generators for this statement"};
+  if (m * n < 2) throw ProofErr{BPP_ERR_INVALID_LENGTH, "bit_length * aggregation factor must be at least 2"};
+  uint32_t rounds = 0;
+  while ((1u << rounds) < m * n) rounds++;
+  if (proof_stride < prove_item_len(P, m)) throw ProofErr{BPP_ERR_INVALID_LENGTH, "proof_stride too small"};
+  if (!it.values || !it.blindings32 || !it.commitments32 || !it.rng_bytes || (!it.min_values && it.min_present))
+    throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "null witness / statement field"};
+  if (it.seed_nonce32 && m > 1) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Mask recovery is not supported with an aggregated statement"};
+  if (it.rng_len < 32 * (size_t)(rounds + 3))
+    throw ProofErr{BPP_ERR_INVALID_LENGTH, "not enough external randomness: need (rounds + 3) * 32 bytes"};
+  for (uint32_t j = 0; j < m; j++) {
+    if (n < 64 && (it.values[j] >> n) > 0) throw ProofErr{BPP_ERR_INVALID_LENGTH, "Value exceeds bit vector capacity!"};
+    const bool present = it.min_present ? it.min_present[j] != 0 : false;
+    if (present && it.values[j] < it.min_values[j]) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Minimum value is larger than value"};
+  }
+  for (uint32_t q = 0; q < m * t; q++)
+    if (!sc_is_canonical(it.blindings32 + 32 * (size_t)q)) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "blinding factor is not canonical"};
+  if (it.seed_nonce32 && !sc_is_canonical(it.seed_nonce32)) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "seed nonce is not canonical"};
+  if (it.transcript_state && it.transcript_state[200] >= BPP_STROBE_R)
+    throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "transcript state has pos >= rate"};
+}
+
+// The mixed call (the context's lock held, its device current): proof i at proofs_out + i * proof_stride, its length in
+// proof_lens[i] (0 for an m that no statement can have), its outcome in out.code[i] / out.msg[i].  A failed item's slot is zeroed.
+// Throws only what concerns the whole call (an unknown params handle, a null argument).
+void prove_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out, size_t proof_stride,
+                 size_t *proof_lens, MixedOutcome &out) {
+  const std::shared_ptr<Params> Pp = params_registry().get(params);
+  if (!Pp || Pp->device != ctx->device) throw ProofErr{BPP_ERR_BAD_HANDLE, "unknown params handle"};
+  const Params &P = *Pp;
+  if (!items || n_items == 0 || !proofs_out || !proof_lens) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "null argument"};
+  out.code.assign(n_items, BPP_OK);
+  out.msg.assign(n_items, std::string());
+  std::map<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> classes;  // m -> the items that passed the host checks
+  for (size_t i = 0; i < n_items; i++) {
+    proof_lens[i] = prove_item_len(P, items[i].m);
+    try {
+      prove_item_check(P, items[i], proof_stride);
+      classes[items[i].m].push_back((uint32_t)i);
+    } catch (const ProofErr &e) {
+      out.code[i] = e.code;
+      out.msg[i] = e.msg;
+    }
+  }
+  // ONE ragged call over every class, largest aggregation factor first (prove_uniform with mixed = true)
+  std::vector<uint32_t> idx;
+  for (auto &kv : classes) idx.insert(idx.end(), kv.second.begin(), kv.second.end());
+  if (idx.empty()) return;
+  std::vector<bpp_prove_item> sub(idx.size());
+  for (size_t k = 0; k < idx.size(); k++) sub[k] = items[idx[k]];
+  const size_t plen = prove_item_len(P, sub[0].m);
+  std::vector<uint8_t> buf(idx.size() * plen, 0);
+  std::vector<uint32_t> status(idx.size(), 0);
+  char err[256];
+  err[0] = 0;
+  size_t len = 0;
+  const int rc = prove_uniform(ctx, params, sub.data(), sub.size(), buf.data(), plen, &len, err, sizeof(err), status.data(), true);
+  {
+    for (size_t k = 0; k < idx.size(); k++) {
+      const uint32_t i = idx[k];
+      if (rc != BPP_OK) {  // (an engine fault: every item of the call shares it)
+        out.code[i] = rc;
+        out.msg[i] = err;
+      } else if (status[k] & PV_STATUS_COMMIT_MISMATCH) {
+        out.code[i] = BPP_ERR_INVALID_ARGUMENT;
+        out.msg[i] = "Witness opening is invalid!";
+      } else if (status[k] & PV_STATUS_TRANSCRIPT) {
+        out.code[i] = BPP_ERR_VERIFICATION_FAILED;
+        out.msg[i] = "Identity element cannot be added to the transcript / zero challenge";
+      } else {
+        memcpy(proofs_out + (size_t)i * proof_stride, &buf[k * plen], proof_lens[i]);
+      }
+    }
+  }
+  for (size_t i = 0; i < n_items; i++)
+    if (out.code[i] != BPP_OK && proof_lens[i] && proof_stride >= proof_lens[i]) memset(proofs_out + i * proof_stride, 0, proof_lens[i]);
+}
+
+}  // namespace
+
+extern "C" int bpp_prove_batch_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
+                                     size_t proof_stride, size_t *proof_lens, int *item_status, char *errbuf, size_t errbuf_len) {
+  BPP_ENTRY(ctx);
+  try {
+    MixedOutcome out;
+    prove_mixed(ctx, params, items, n_items, proofs_out, proof_stride, proof_lens, out);
+    if (item_status) memcpy(item_status, out.code.data(), n_items * sizeof(int));
+    for (size_t i = 0; i < n_items; i++)
+      if (out.code[i] != BPP_OK) return fail(ctx, out.code[i], out.msg[i], errbuf, errbuf_len);
+    set_err(errbuf, errbuf_len, "");
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, errbuf, errbuf_len)
+}
+
+// The message that goes with item_status of bpp_prove_batch_mixed: the item's host-side checks run again (no device work), and an
+// item that passes them failed on the device, whose two findings have one message each.  Keeps no state: any thread, any time.
+extern "C" int bpp_prove_item_message(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item, size_t proof_stride, int status,
+                                      char *errbuf, size_t errbuf_len) {
+  if (!ctx || !item) return BPP_ERR_BAD_HANDLE;
+  const std::shared_ptr<Params> Pp = params_registry().get(params);
+  if (!Pp || Pp->device != ctx->device) return BPP_ERR_BAD_HANDLE;
+  try {
+    prove_item_check(*Pp, *item, proof_stride);
+  } catch (const ProofErr &e) {
+    set_err(errbuf, errbuf_len, e.msg);
+    return e.code;
+  }
+  set_err(errbuf, errbuf_len, status == BPP_ERR_INVALID_ARGUMENT ? "Witness opening is invalid!"
+                              : status == BPP_ERR_VERIFICATION_FAILED ? "Identity element cannot be added to the transcript / zero challenge"
+                              : "");
+  return status;
 }
 
 #ifdef BPP_KP_PHASES

@@ -1,0 +1,294 @@
+// bpp_prove_pool: pools the small prove calls of many host threads (a wallet service or an exchange making outputs) into
+// mixed-aggregation engine calls.
+//
+// Why: a call of one proof is a chain of latency-bound launches (kp_init, kp_A, a round kernel and a fixed-base MSM per round,
+// the final step) that the chip runs in about the time a call of a few hundred proofs takes.  The pool gives separate callers
+// the second form, the way bpp_batcher does for verify_batch: every caller hands over its items (any aggregation factors;
+// bpp_prove_pool_prove blocks until its proofs are there); whichever caller finds a lane free leads the next pooled call, takes
+// what queued up while the previous pooled calls ran (plus what arrives within max_wait_us), proves everybody's items as ONE
+// bpp_prove_batch_mixed on the lane's context and hands every caller its own proofs and outcome.  No thread of its own.
+// Each caller gets exactly what bpp_prove_batch_mixed(ctx, params, its items, ...) would have returned: a proof depends on its
+// own item alone and every item carries its own outcome, so nobody else's items change a caller's bytes, status or message.
+// The lanes keep copies of the callers' item DESCRIPTORS only (pointers into the callers' buffers); the witness bytes, nonces
+// and the page-locked staging that held them are wiped by the prover itself before the engine call returns.
+// Part of engine.hip's translation unit.
+#pragma once
+
+struct bpp_prove_pool {
+  struct Req {
+    const bpp_prove_item *items = nullptr;
+    size_t n_items = 0;
+    uint8_t *proofs_out = nullptr;
+    size_t proof_stride = 0;
+    size_t *proof_lens = nullptr;
+    int code = BPP_OK;
+    std::string msg;
+    bool taken = false;  // a leader has it in its pooled call
+    bool done = false;
+  };
+  struct Lane {
+    bpp_ctx *ctx = nullptr;  // a context of its own (streams, arena, staging)
+    bool own = false;
+    bool busy = false;
+    std::vector<bpp_prove_item> items;
+    std::vector<uint8_t> proofs;
+    std::vector<size_t> lens;
+  };
+  uint64_t params = 0;
+  std::shared_ptr<Params> P;
+  size_t plen_max = 0;  // the longest proof these parameters can make (m = m_max): the lanes' output stride
+  uint32_t max_wait_us = 0, max_calls = 64, max_proofs = 4096;
+  std::mutex mu;
+  std::condition_variable cv;
+  std::deque<Req *> pending;
+  std::vector<Lane> lanes;
+  uint64_t pooled_calls = 0, engine_calls = 0, solo_calls = 0;  // statistics
+  uint32_t largest_pool_calls = 0, largest_pool_proofs = 0;
+};
+
+namespace {
+
+// A call of more than max_proofs items is a large call by itself, and one whose stride is too short for one of its proofs, or
+// whose arguments are missing, gets its answer from a call of its own: all go through bpp_prove_batch_mixed directly.
+bool prove_pool_poolable(const bpp_prove_pool *p, const bpp_prove_pool::Req *r) {
+  if (!r->items || r->n_items == 0 || !r->proofs_out || !r->proof_lens || r->n_items > p->max_proofs) return false;
+  for (size_t i = 0; i < r->n_items; i++)
+    if (r->proof_stride < prove_item_len(*p->P, r->items[i].m)) return false;
+  return true;
+}
+
+void prove_pool_solo(bpp_prove_pool *p, bpp_prove_pool::Lane &L, bpp_prove_pool::Req *r) {
+  char err[256];
+  err[0] = 0;
+  r->code = bpp_prove_batch_mixed(L.ctx, p->params, r->items, r->n_items, r->proofs_out, r->proof_stride, r->proof_lens, nullptr, err,
+                                  sizeof(err));
+  r->msg = err;
+}
+
+// one pooled engine call on `lane` over `reqs`; fills every request's code / msg (nothing may escape: callers are waiting)
+void prove_pool_run(bpp_prove_pool *p, bpp_prove_pool::Lane &L, const std::vector<bpp_prove_pool::Req *> &reqs) {
+  ScopeExit clear_lane{[&] { L.items.clear(); }};
+  if (reqs.size() == 1) {
+    prove_pool_solo(p, L, reqs[0]);
+    return;
+  }
+  try {
+    size_t n = 0;
+    for (auto *r : reqs) n += r->n_items;
+    L.items.resize(n);
+    L.lens.assign(n, 0);
+    L.proofs.resize(n * p->plen_max);
+    size_t at = 0;
+    for (auto *r : reqs) {
+      std::copy(r->items, r->items + r->n_items, L.items.begin() + (ptrdiff_t)at);
+      at += r->n_items;
+    }
+    MixedOutcome out;
+    {
+      std::lock_guard<std::mutex> lk(L.ctx->mu);
+      if (hipSetDevice(L.ctx->device) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
+      prove_mixed(L.ctx, p->params, L.items.data(), n, L.proofs.data(), p->plen_max, L.lens.data(), out);
+    }
+    // fan out: a caller's outcome is its first failing item's (bpp_prove_batch_mixed's return value and message).  An engine fault
+    // (a negative code: an allocation the pooled call needed, a HIP error) is nobody's input: the callers it hit get a call of their own.
+    at = 0;
+    for (auto *r : reqs) {
+      bool fault = false;
+      for (size_t i = 0; i < r->n_items; i++) fault = fault || out.code[at + i] < 0;
+      if (fault) {
+        prove_pool_solo(p, L, r);
+        at += r->n_items;
+        continue;
+      }
+      r->code = BPP_OK;
+      r->msg.clear();
+      for (size_t i = 0; i < r->n_items; i++) {
+        const size_t g = at + i, len = L.lens[g];
+        r->proof_lens[i] = len;
+        if (len) memcpy(r->proofs_out + i * r->proof_stride, &L.proofs[g * p->plen_max], len);
+        if (out.code[g] != BPP_OK && r->code == BPP_OK) {
+          r->code = out.code[g];
+          r->msg = out.msg[g];
+        }
+      }
+      at += r->n_items;
+    }
+  } catch (const EngineError &e) {  // an engine fault should not be pinned on all of them: everybody gets a call of their own
+    for (auto *r : reqs) prove_pool_solo(p, L, r);
+  } catch (const ProofErr &e) {
+    for (auto *r : reqs) prove_pool_solo(p, L, r);
+  } catch (const std::exception &e) {
+    for (auto *r : reqs) {
+      r->code = BPP_ERR_ENGINE;
+      r->msg = std::string("prove pool: ") + e.what();
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int bpp_prove_pool_create(bpp_ctx *ctx, uint64_t params, uint32_t lanes, uint32_t max_wait_us, uint32_t max_calls, bpp_prove_pool **out) {
+  if (!ctx || !out) return BPP_ERR_INVALID_ARGUMENT;
+  *out = nullptr;
+  const std::shared_ptr<Params> Pp = params_registry().get(params);
+  if (!Pp || Pp->device != ctx->device) return BPP_ERR_BAD_HANDLE;
+  if (lanes == 0) lanes = 2;
+  if (lanes > 8) lanes = 8;
+  auto p = std::make_unique<bpp_prove_pool>();
+  p->params = params;
+  p->P = Pp;
+  p->plen_max = prove_item_len(*Pp, Pp->m_max);
+  p->max_wait_us = max_wait_us;
+  if (max_calls) p->max_calls = max_calls;
+  p->lanes.resize(lanes);
+  for (uint32_t i = 0; i < lanes; i++) {
+    if (i == 0) {
+      p->lanes[i].ctx = ctx;
+    } else {
+      bpp_ctx *c = nullptr;
+      int rc = bpp_ctx_create(&c, ctx->device);
+      if (rc == BPP_OK) rc = bpp_params_retain(c, params);
+      if (rc != BPP_OK) {
+        if (c) bpp_ctx_destroy(c);
+        for (uint32_t j = 1; j < i; j++) bpp_ctx_destroy(p->lanes[j].ctx);
+        return rc;
+      }
+      {  // the knobs of the caller's context, as they are when the pool is made, hold on every lane
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        c->opt = ctx->opt;
+      }
+      p->lanes[i].ctx = c;
+      p->lanes[i].own = true;
+    }
+  }
+  *out = p.release();
+  return BPP_OK;
+}
+
+int bpp_prove_pool_set_limits(bpp_prove_pool *p, uint32_t max_calls, uint32_t max_proofs) {
+  if (!p) return BPP_ERR_BAD_HANDLE;
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (max_calls) p->max_calls = max_calls;
+  if (max_proofs) p->max_proofs = max_proofs;
+  return BPP_OK;
+}
+
+int bpp_prove_pool_stats(bpp_prove_pool *p, uint64_t *pooled_calls, uint64_t *engine_calls, uint64_t *solo_calls, uint32_t *largest_calls,
+                         uint32_t *largest_proofs) {
+  if (!p) return BPP_ERR_BAD_HANDLE;
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (pooled_calls) *pooled_calls = p->pooled_calls;
+  if (engine_calls) *engine_calls = p->engine_calls;
+  if (solo_calls) *solo_calls = p->solo_calls;
+  if (largest_calls) *largest_calls = p->largest_pool_calls;
+  if (largest_proofs) *largest_proofs = p->largest_pool_proofs;
+  return BPP_OK;
+}
+
+void bpp_prove_pool_destroy(bpp_prove_pool *p) {
+  if (!p) return;
+  {
+    std::unique_lock<std::mutex> lk(p->mu);
+    p->cv.wait(lk, [&] {
+      for (auto &L : p->lanes)
+        if (L.busy) return false;
+      return p->pending.empty();
+    });
+  }
+  for (auto &L : p->lanes)
+    if (L.own) bpp_ctx_destroy(L.ctx);
+  delete p;
+}
+
+int bpp_prove_pool_prove(bpp_prove_pool *p, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out, size_t proof_stride,
+                         size_t *proof_lens, char *errbuf, size_t errbuf_len) {
+  if (!p) return BPP_ERR_BAD_HANDLE;
+  bpp_prove_pool::Req me;
+  me.items = items;
+  me.n_items = n_items;
+  me.proofs_out = proofs_out;
+  me.proof_stride = proof_stride;
+  me.proof_lens = proof_lens;
+  std::vector<bpp_prove_pool::Req *> mine;
+  bpp_prove_pool::Lane *lane = nullptr;
+  {
+    std::unique_lock<std::mutex> lk(p->mu);
+    const bool poolable = prove_pool_poolable(p, &me);
+    if (poolable) {
+      p->pending.push_back(&me);
+      p->cv.notify_all();  // (a leader waiting for company counts the queue)
+    }
+    auto free_lane = [&]() -> bpp_prove_pool::Lane * {
+      for (auto &L : p->lanes)
+        if (!L.busy) return &L;
+      return nullptr;
+    };
+    // wait until somebody else has dealt with this request, or -- as long as nobody has taken it -- a lane is free and this
+    // thread leads the next pooled call
+    p->cv.wait(lk, [&] { return me.done || (!me.taken && free_lane() != nullptr); });
+    if (me.done) {
+      set_err(errbuf, errbuf_len, me.msg);
+      return me.code;
+    }
+    lane = free_lane();
+    lane->busy = true;
+    if (poolable) {
+      if (p->max_wait_us && p->pending.size() < p->max_calls)
+        p->cv.wait_for(lk, std::chrono::microseconds(p->max_wait_us), [&] { return me.taken || p->pending.size() >= p->max_calls; });
+      if (me.taken) {  // another leader took this thread's request while it waited for company: let that one finish it
+        lane->busy = false;
+        p->cv.notify_all();
+        p->cv.wait(lk, [&] { return me.done; });
+        set_err(errbuf, errbuf_len, me.msg);
+        return me.code;
+      }
+      // the leader's own request first, then whatever is queued, oldest first, within max_calls requests and max_proofs proofs;
+      // requests that do not fit stay where they are, for the next leader
+      for (auto it = p->pending.begin(); it != p->pending.end(); ++it)
+        if (*it == &me) {
+          p->pending.erase(it);
+          break;
+        }
+      me.taken = true;
+      mine.push_back(&me);
+      size_t proofs = n_items;
+      for (auto it = p->pending.begin(); it != p->pending.end() && mine.size() < p->max_calls;) {
+        bpp_prove_pool::Req *r = *it;
+        if (proofs + r->n_items > p->max_proofs) {
+          ++it;
+          continue;
+        }
+        proofs += r->n_items;
+        r->taken = true;
+        mine.push_back(r);
+        it = p->pending.erase(it);
+      }
+    } else {
+      mine.push_back(&me);
+    }
+    p->engine_calls++;
+    if (mine.size() > 1) {
+      p->pooled_calls += mine.size();
+      size_t proofs = 0;
+      for (auto *r : mine) proofs += r->n_items;
+      p->largest_pool_calls = std::max(p->largest_pool_calls, (uint32_t)mine.size());
+      p->largest_pool_proofs = std::max(p->largest_pool_proofs, (uint32_t)proofs);
+    } else {
+      p->solo_calls++;
+    }
+  }
+  prove_pool_run(p, *lane, mine);
+  {
+    std::lock_guard<std::mutex> lk(p->mu);
+    for (auto *r : mine)
+      if (r != &me) r->done = true;  // (`me` lives on this stack and is always part of `mine`)
+    lane->busy = false;
+  }
+  p->cv.notify_all();
+  set_err(errbuf, errbuf_len, me.msg);
+  return me.code;
+}
+
+}  // extern "C"

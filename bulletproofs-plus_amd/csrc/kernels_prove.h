@@ -364,7 +364,7 @@ __device__ __forceinline__ void fb_reduce_one(ge *red /* LDS, this wavefront's 6
 
 // ---------------------------------------------------------------- per-proof prover state
 struct ProveDesc {
-  uint32_t m;           // aggregation factor (uniform over a prove batch)
+  uint32_t m;           // aggregation factor of this proof
   uint32_t wit_off;     // byte offset of the witness bytes (v LE64 || r[0..t) per opening) in bytes[]
   uint32_t commit_off;  // m compressed commitments
   uint32_t ext_off;     // (rounds+3) x 32 bytes of external randomness
@@ -372,6 +372,12 @@ struct ProveDesc {
   uint32_t state_idx;
   uint32_t flags;       // bit0: seed nonce present
   uint32_t seed_off;    // byte offset of the 32-byte seed nonce (if any)
+  // Mixed aggregation factors (bpp_prove_batch_mixed): the call runs R = the largest proof's rounds as global steps; this proof
+  // takes part from step roff = R - its own rounds on (its local step is j - roff), so that every proof reaches the final step in
+  // the same launch.  Per-proof slots of the call's buffers (vectors, term rows) are sized for mslot, the call's largest m.
+  // A uniform call: roff = 0, mslot = m.
+  uint32_t roff;
+  uint32_t mslot;
 };
 
 struct ProveState {
@@ -901,7 +907,8 @@ __device__ __forceinline__ void kp_wave_body(const uint8_t *__restrict__ bytes, 
   const ProveDesc d = desc[p];
   ProveState &st = ps[p];
   const uint32_t mn = d.m * n_bits;
-  sc *a = vec + (size_t)p * KP_VEC_LEN(mn), *b = a + mn, *cG = b + mn, *cH = cG + mn, *ypow = cH + mn;
+  const uint32_t mn_slot = d.mslot * n_bits;
+  sc *a = vec + (size_t)p * KP_VEC_LEN(mn_slot), *b = a + mn, *cG = b + mn, *cH = cG + mn, *ypow = cH + mn;
   sc *fG = ypow + mn + 2, *fH = fG + KP_EX_CLASSES;  // ("ct" = 2, see below)
   sc one;
   sc_mont_one(one);
@@ -1110,15 +1117,16 @@ __device__ __forceinline__ void kp_wave_body(const uint8_t *__restrict__ bytes, 
       // points are more outputs of this round's fixed-base MSM (mn / 2^ex_back terms each: as much work as a round's L and R);
       // their multiples by 16^w are made while the remaining rounds run (ct.h: k_ct_pow16), so that the secret scalars r fG[c],
       // s fH[c] find everything they need when they exist (k_ct_var).
-      const uint32_t nc = 1u << ex_back, hn = mn >> ex_back;
-      sc *es = ex_scal + (size_t)p * 2 * mn;
-      uint32_t *eg = ex_gidx + (size_t)p * 2 * mn;
+      // (rows of hs = mn_slot / 2^ex_back terms, hn of them used: the row the host's launch reads)
+      const uint32_t nc = 1u << ex_back, hn = mn >> ex_back, hs = mn_slot >> ex_back;
+      sc *es = ex_scal + (size_t)p * 2 * mn_slot;
+      uint32_t *eg = ex_gidx + (size_t)p * 2 * mn_slot;
       for (uint32_t u = lane; u < mn; u += nthr) {
         const uint32_t c = u & (nc - 1), r2 = u >> ex_back;
-        es[c * hn + r2] = cG[u];  // (Montgomery form, as every fixed-base term list)
-        eg[c * hn + r2] = 2 * u;
-        es[(nc + c) * hn + r2] = cH[u];
-        eg[(nc + c) * hn + r2] = 2 * u + 1;
+        es[c * hs + r2] = cG[u];  // (Montgomery form, as every fixed-base term list)
+        eg[c * hs + r2] = 2 * u;
+        es[(nc + c) * hs + r2] = cH[u];
+        eg[(nc + c) * hs + r2] = 2 * u + 1;
       }
       if (lane < 2 * nc) ex_count[2 * nc * p + lane] = hn;
       if (lane < nc) {
@@ -1189,7 +1197,7 @@ __device__ __forceinline__ void kp_wave_body(const uint8_t *__restrict__ bytes, 
     // ~300 us of a round with as many additions (profiles/r04_v6_prover_launches.txt), on the call's last stretch.  The rows
     // (FINAL_ROW(mn, t) = mn + t + 1 terms each) are packed from the start of the term arrays -- 3 (mn + t + 1) <= 2 (2 mn + t + 1)
     // per proof -- which is safe because no workgroup reads a term row in this step; kp_final_points adds the halves.
-    const uint32_t fstride = mn + t + 1;
+    const uint32_t fstride = mn_slot + t + 1;  // (the host's row; mn + t + 1 of it used)
     sc *f_s = term_scal + (size_t)3 * p * fstride;
     uint32_t *f_g = term_gidx + (size_t)3 * p * fstride;
     for (uint32_t u = lane; u < mn; u += nthr) {
@@ -1235,7 +1243,9 @@ __global__ void __launch_bounds__(64) kp_lane(const uint8_t *__restrict__ bytes,
                                               uint32_t t, uint32_t B, uint32_t j, uint32_t rounds, const uint8_t *__restrict__ a32,
                                               const uint8_t *lr32, ProveState *ps) {
   __shared__ ProveLds L;
-  kp_lane_body(bytes, desc, n_bits, t, B, j, rounds, a32, lr32, ps, L);
+  if (blockIdx.x >= B) return;
+  const uint32_t ro = desc[blockIdx.x].roff;  // (this proof's local step and rounds)
+  kp_lane_body(bytes, desc, n_bits, t, B, j - ro, rounds - ro, a32, lr32, ps, L);
   lds_wipe(L);
 }
 __global__ void __launch_bounds__(64) kp_wave(const uint8_t *__restrict__ bytes, const ProveDesc *__restrict__ desc,
@@ -1246,8 +1256,9 @@ __global__ void __launch_bounds__(64) kp_wave(const uint8_t *__restrict__ bytes,
                                               uint32_t *__restrict__ ct_count, sc *__restrict__ ex_scal, uint32_t *__restrict__ ex_gidx,
                                               uint32_t *__restrict__ ex_count, uint32_t ex_back) {
   __shared__ sc red[64];
-  kp_wave_body(bytes, desc, minvals, min_present, n_bits, t, n_gen, j, rounds, stride, ps, vec, term_scal, term_gidx, term_count, ct_scal,
-               ct_idx, ct_count, ex_scal, ex_gidx, ex_count, ex_back, red);
+  const uint32_t ro = desc[blockIdx.x].roff;  // (this proof's local step and rounds; the grid covers the active proofs only)
+  kp_wave_body(bytes, desc, minvals, min_present, n_bits, t, n_gen, j - ro, rounds - ro, stride, ps, vec, term_scal, term_gidx, term_count,
+               ct_scal, ct_idx, ct_count, ex_scal, ex_gidx, ex_count, ex_back, red);
   lds_wipe(red);
 }
 // ... and as ONE launch per round (round 4): the encoding of the previous round's L and R (two lanes, ristretto_compress), the
@@ -1273,6 +1284,11 @@ __global__ void __launch_bounds__(64 * W) kp_round(const uint8_t *__restrict__ b
   const uint32_t p = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
   constexpr bool multi = W >= 2;  // (an instantiation per form: each carries only its own Fiat-Shamir step)
   if (p >= B) return;
+  // this proof's local step and rounds (mixed calls: a proof that joins at this step has no previous L and R to sum and encode)
+  const uint32_t ro = desc[p].roff;
+  j -= ro;
+  rounds -= ro;
+  if (j == 0) ge_prev = nullptr;
   // The three phases use LDS one after the other -- the points being summed (10 or 20 KB), the sponges of the Fiat-Shamir step,
   // the vector step's reduction buffer -- and SHARE it: what this workgroup holds decides how many of them fit on a compute unit
   // beside the other sub-batch's fixed-base MSM (a dozen 9 KB workgroups per CU): at 32 KB it was one, and the 512 workgroups of a
@@ -1339,8 +1355,8 @@ __global__ void __launch_bounds__(64) kp_finish(const ProveDesc *__restrict__ de
   __shared__ ProveLds L;
   const KeccakLanes K = keccak_lanes(L.wk[0]);
   ProveState &st = ps[p];
-  const uint32_t mn = desc[p].m * n_bits;
-  const sc *a = vec + (size_t)p * KP_VEC_LEN(mn), *b = a + mn;
+  const uint32_t mn = desc[p].m * n_bits, ro = desc[p].roff;
+  const sc *a = vec + (size_t)p * KP_VEC_LEN(desc[p].mslot * n_bits), *b = a + mn;
   WStrobe tr;
   ws_load(tr, L.tr, st.tr);
   const uint8_t *pa1 = a1b32 + (size_t)p * 64;
@@ -1376,7 +1392,8 @@ __global__ void __launch_bounds__(64) kp_finish(const ProveDesc *__restrict__ de
   for (uint32_t i = lane; i < 96; i += 64)  // A | A1 | B
     o[1 + 32 * t + i] = i < 32 ? a32[(size_t)p * 32 + i] : a1b32[(size_t)p * 64 + (i - 32)];
   uint8_t *olr = o + 1 + 32 * t + 96 + 64;
-  for (uint32_t i = lane; i < 64 * rounds; i += 64) olr[i] = lr_all[((size_t)(i >> 6) * B + p) * 64 + (i & 63u)];
+  // (L_j, R_j of this proof's local round j: global step j + roff)
+  for (uint32_t i = lane; i < 64 * (rounds - ro); i += 64) olr[i] = lr_all[((size_t)((i >> 6) + ro) * B + p) * 64 + (i & 63u)];
   if (!ok && lane == 0) st.status |= PV_STATUS_TRANSCRIPT;
   lds_wipe(L);
 }
@@ -1406,7 +1423,7 @@ __global__ void kp_check_commitments(const uint8_t *__restrict__ bytes, const Pr
   if (p >= B) return;
   const ProveDesc d = desc[p];
   uint32_t diff = 0;
-  for (uint32_t i = 0; i < 32 * d.m; i++) diff |= (uint32_t)(bytes[d.commit_off + i] ^ computed32[(size_t)p * 32 * d.m + i]);
+  for (uint32_t i = 0; i < 32 * d.m; i++) diff |= (uint32_t)(bytes[d.commit_off + i] ^ computed32[(size_t)p * 32 * d.mslot + i]);
   if (diff) ps[p].status |= PV_STATUS_COMMIT_MISMATCH;
 }
 
@@ -1416,7 +1433,11 @@ __global__ void kp_commit_terms(const uint8_t *__restrict__ bytes, const ProveDe
                                 uint32_t *__restrict__ tc) {
   const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
   if (o >= B * m) return;
-  const uint32_t p = o / m, j = o % m;
+  const uint32_t p = o / m, j = o % m;  // (m = the call's mslot: a proof of fewer openings leaves its further outputs empty)
+  if (j >= desc[p].m) {
+    tc[o] = 0;
+    return;
+  }
   const uint8_t *w = bytes + desc[p].wit_off + j * (8 + 32 * t);
   sc v;
   sc_0(v);

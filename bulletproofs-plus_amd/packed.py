@@ -176,6 +176,52 @@ class Batcher:
             self.handle = ctypes.c_void_p()
 
 
+class ProvePool:
+    """bpp_prove_pool: many host threads, each calling prove(...) with a few proofs of any aggregation factors; the calls that are
+    waiting are proved as ONE bpp_prove_batch_mixed on one of `lanes` contexts, every caller gets what a bpp_prove_batch_mixed
+    of its own items would have returned.  The engine's prover options at creation hold on every lane."""
+
+    STRIDE = 1 + 32 * (6 + 5 + 2 * 12)  # the longest proof any parameters make
+
+    def __init__(self, params, lanes=0, max_wait_us=0, max_calls=64):
+        self.params, self.engine = params, params.engine
+        self.handle = ctypes.c_void_p()
+        api._check(self.engine.lib.bpp_prove_pool_create(self.engine.ctx, params.handle, lanes, max_wait_us, max_calls,
+                                                         byref(self.handle)), self.engine.ctx)
+
+    @staticmethod
+    def marshal(transcripts, statements, witnesses, rng_bytes):
+        """the bpp_prove_item array of a call (api.RangeProof's marshalling: its host checks raise here), reusable"""
+        return api.RangeProof._prove_marshal(transcripts, statements, witnesses, rng_bytes)
+
+    def prove_marshalled(self, marshalled):
+        """blocks; returns the proofs' bytes, or raises the ProofError of the call's first failing item"""
+        _params, items, n, _keep = marshalled
+        out = (ctypes.c_uint8 * (self.STRIDE * n))()
+        lens = (c_size_t * n)()
+        err = ctypes.create_string_buffer(256)
+        api._check(self.engine.lib.bpp_prove_pool_prove(self.handle, items, n, out, self.STRIDE, lens, err, 256), None, err)
+        raw = bytes(out)
+        return [raw[i * self.STRIDE:i * self.STRIDE + lens[i]] for i in range(n)]
+
+    def prove(self, transcripts, statements, witnesses, rng_bytes):
+        """n x RangeProof::prove_with_rng (any aggregation factors) through the pool -> list of proof bytes"""
+        return self.prove_marshalled(self.marshal(transcripts, statements, witnesses, rng_bytes))
+
+    def set_limits(self, max_calls=0, max_proofs=0):
+        api._check(self.engine.lib.bpp_prove_pool_set_limits(self.handle, max_calls, max_proofs), None)
+
+    def stats(self):
+        v = [c_uint64() for _ in range(3)] + [ctypes.c_uint32() for _ in range(2)]
+        self.engine.lib.bpp_prove_pool_stats(self.handle, *[byref(x) for x in v])
+        return dict(zip(("pooled_calls", "engine_calls", "solo_calls", "largest_calls", "largest_proofs"), [x.value for x in v]))
+
+    def close(self):
+        if self.handle:
+            self.engine.lib.bpp_prove_pool_destroy(self.handle)
+            self.handle = ctypes.c_void_p()
+
+
 def verify_groups_actions(rb, bounds, actions):
     """bpp_verify_resident_groups_actions: one VerifyAction per group -> (result dicts, masks [n, t, 32], present [n])"""
     G = len(bounds) - 1

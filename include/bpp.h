@@ -435,6 +435,36 @@ typedef struct {
 } bpp_prove_item;
 int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
                     size_t proof_stride, size_t *proof_len, char *errbuf, size_t errbuf_len);
+/* The same for items of DIFFERENT aggregation factors: each item's m is any power of two up to the parameters' m_max
+ * (RangeProof::prove_with_rng takes any such statement).  Proof i is written at proofs_out + i * proof_stride; its length,
+ * 1 + 32*(t + 5 + 2*rounds_i), goes to proof_lens[i] (0 for an m no statement can have).  item_status[i] (may be NULL) receives
+ * the code a one-item bpp_prove_batch on that item would return; a failed item's slot is zeroed and never stops the others.
+ * Returns 0 when every item succeeds, else the first failing item's code, with its message in errbuf.  Every proof equals, byte
+ * for byte, the one bpp_prove_batch makes of the same item.  bpp_prove_batch itself still takes one m per call. */
+int bpp_prove_batch_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
+                          size_t proof_stride, size_t *proof_lens, int *item_status, char *errbuf, size_t errbuf_len);
+/* the message that goes with item_status[i] = `status` of a bpp_prove_batch_mixed call on `item` (same params and proof_stride):
+ * what a one-item bpp_prove_batch would have written to errbuf.  Host-side work only, no state kept; returns the item's code. */
+int bpp_prove_item_message(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item, size_t proof_stride, int status, char *errbuf,
+                           size_t errbuf_len);
+/* bpp_prove_pool: many host threads, each with a few proofs per call (one output of a wallet service, say).  A call of one proof
+ * is a chain of latency-bound launches; the pool hands the calls that are waiting to ONE bpp_prove_batch_mixed on one of `lanes`
+ * contexts (the first is ctx; the others are made here with ctx's options as they are now).  No thread of its own: whichever
+ * caller finds a lane free leads the next pooled call for everybody queued (plus whatever arrives within max_wait_us), up to
+ * max_calls calls and max_proofs proofs (bpp_prove_pool_set_limits; 0 keeps a limit).  bpp_prove_pool_prove blocks and returns
+ * exactly what bpp_prove_batch_mixed(ctx, params, its items, ..., NULL, ...) would: the same bytes, lengths, code and message.
+ * Calls of more than max_proofs items, or whose stride is too short, go through a call of their own.  Secrets: witness bytes are
+ * read where the caller keeps them and wiped from the engine's staging before the lane is handed on.  Stats: callers served in
+ * pooled calls, engine calls, calls that ran alone, and the largest pool so far.  destroy waits for the calls in flight. */
+typedef struct bpp_prove_pool bpp_prove_pool;
+int bpp_prove_pool_create(bpp_ctx *ctx, uint64_t params, uint32_t lanes, uint32_t max_wait_us, uint32_t max_calls,
+                          bpp_prove_pool **out);
+int bpp_prove_pool_prove(bpp_prove_pool *p, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
+                         size_t proof_stride, size_t *proof_lens, char *errbuf, size_t errbuf_len);
+int bpp_prove_pool_set_limits(bpp_prove_pool *p, uint32_t max_calls, uint32_t max_proofs);
+int bpp_prove_pool_stats(bpp_prove_pool *p, uint64_t *pooled_calls, uint64_t *engine_calls, uint64_t *solo_calls,
+                         uint32_t *largest_calls, uint32_t *largest_proofs);
+void bpp_prove_pool_destroy(bpp_prove_pool *p);
 
 /* ---- parity / diagnostics: intermediates of the last verify on `batch`, for differential tests ---- */
 #define BPP_TRACE_CHALLENGES 1     /* per proof (rmax+3) x 32: y, z, e_0.., e_final (canonical), rmax = bpp_batch_shape's max_rounds

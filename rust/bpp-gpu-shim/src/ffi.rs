@@ -88,6 +88,10 @@ pub struct bpp_comm {
 pub struct bpp_batcher {
     _p: [u8; 0],
 }
+#[repr(C)]
+pub struct bpp_prove_pool {
+    _p: [u8; 0],
+}
 
 /// outcome of one batch of a sharded wave (bpp_verify_sharded_wave)
 #[repr(C)]
@@ -262,6 +266,19 @@ extern "C" {
     // B2: RangeProof::prove_with_rng (src/range_proof.rs:232-608)
     pub fn bpp_prove_batch(ctx: *mut bpp_ctx, params: u64, items: *const bpp_prove_item, n_items: usize, proofs_out: *mut u8,
                            proof_stride: usize, proof_len: *mut usize, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_batch_mixed(ctx: *mut bpp_ctx, params: u64, items: *const bpp_prove_item, n_items: usize, proofs_out: *mut u8,
+                                 proof_stride: usize, proof_lens: *mut usize, item_status: *mut c_int, errbuf: *mut c_char,
+                                 errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_item_message(ctx: *mut bpp_ctx, params: u64, item: *const bpp_prove_item, proof_stride: usize, status: c_int,
+                                  errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_pool_create(ctx: *mut bpp_ctx, params: u64, lanes: u32, max_wait_us: u32, max_calls: u32,
+                                 out: *mut *mut bpp_prove_pool) -> c_int;
+    pub fn bpp_prove_pool_prove(p: *mut bpp_prove_pool, items: *const bpp_prove_item, n_items: usize, proofs_out: *mut u8,
+                                proof_stride: usize, proof_lens: *mut usize, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_pool_set_limits(p: *mut bpp_prove_pool, max_calls: u32, max_proofs: u32) -> c_int;
+    pub fn bpp_prove_pool_stats(p: *mut bpp_prove_pool, pooled_calls: *mut u64, engine_calls: *mut u64, solo_calls: *mut u64,
+                                largest_calls: *mut u32, largest_proofs: *mut u32) -> c_int;
+    pub fn bpp_prove_pool_destroy(p: *mut bpp_prove_pool);
     // diagnostics
     pub fn bpp_batch_trace(ctx: *mut bpp_ctx, batch: u64, what: c_int, out: *mut u8, out_len: usize, written: *mut usize) -> c_int;
     pub fn bpp_batch_shape(ctx: *mut bpp_ctx, batch: u64, n_items: *mut u32, max_rounds: *mut u32, max_mn: *mut u32, total_dyn: *mut u32,

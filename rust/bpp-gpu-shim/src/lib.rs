@@ -291,22 +291,8 @@ impl Engine {
 
     /// n x `RangeProof::prove_with_rng` in one call; all items share the aggregation factor.  Returns `to_bytes()` of each proof.
     pub fn prove_batch(&self, params: &Params, items: &[ProveItem<'_>]) -> Result<Vec<Vec<u8>>, GpuError> {
-        let present_in: Vec<Vec<u8>> = items.iter().map(|i| i.min_values.iter().map(|v| v.is_some() as u8).collect()).collect();
-        let mins: Vec<Vec<u64>> = items.iter().map(|i| i.min_values.iter().map(|v| v.unwrap_or(0)).collect()).collect();
-        let raw: Vec<ffi::bpp_prove_item> = items.iter().enumerate().map(|(k, i)| ffi::bpp_prove_item {
-            values: i.values.as_ptr(),
-            blindings32: i.blindings.as_ptr(),
-            commitments32: i.commitments.as_ptr(),
-            m: i.values.len() as u32,
-            min_values: mins[k].as_ptr(),
-            min_present: present_in[k].as_ptr(),
-            seed_nonce32: i.seed_nonce.map_or(ptr::null(), |s| s.as_ptr()),
-            transcript_state: i.transcript_state.map_or(ptr::null(), |s| s.as_ptr()),
-            transcript_label: i.transcript_label.as_ptr(),
-            label_len: i.transcript_label.len(),
-            rng_bytes: i.rng_bytes.as_ptr(),
-            rng_len: i.rng_bytes.len(),
-        }).collect();
+        let keep = RawProveItems::new(items);
+        let raw = &keep.raw;
         let stride = 1 + 32 * (6 + 5 + 2 * 12);
         let mut out = vec![0u8; stride * items.len()];
         let mut plen = 0usize;
@@ -316,6 +302,33 @@ impl Engine {
         };
         map_rc(rc, unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned())?;
         Ok((0..items.len()).map(|k| out[k * stride..k * stride + plen].to_vec()).collect())
+    }
+
+    /// n x `RangeProof::prove_with_rng` of any aggregation factors (powers of two up to the parameters' maximum) in one call
+    /// (bpp_prove_batch_mixed).  One entry per item: its `to_bytes()`, or the error `prove_batch` on that item alone returns.
+    pub fn prove_batch_mixed(&self, params: &Params, items: &[ProveItem<'_>]) -> Result<Vec<Result<Vec<u8>, GpuError>>, GpuError> {
+        let keep = RawProveItems::new(items);
+        let stride = 1 + 32 * (6 + 5 + 2 * 12);
+        let mut out = vec![0u8; stride * items.len()];
+        let mut lens = vec![0usize; items.len()];
+        let mut status = vec![0 as c_int; items.len()];
+        let mut err = [0 as core::ffi::c_char; 256];
+        let rc = unsafe {
+            ffi::bpp_prove_batch_mixed(self.ctx, params.handle, keep.raw.as_ptr(), keep.raw.len(), out.as_mut_ptr(), stride, lens.as_mut_ptr(),
+                                       status.as_mut_ptr(), err.as_mut_ptr(), err.len())
+        };
+        if rc < 0 {
+            map_rc(rc, unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned())?;
+        }
+        Ok((0..items.len()).map(|k| {
+            if status[k] == 0 {
+                return Ok(out[k * stride..k * stride + lens[k]].to_vec());
+            }
+            // the failed item's own message (host-side work only)
+            let mut e1 = [0 as core::ffi::c_char; 256];
+            unsafe { ffi::bpp_prove_item_message(self.ctx, params.handle, &keep.raw[k], stride, status[k], e1.as_mut_ptr(), e1.len()) };
+            map_rc(status[k], unsafe { CStr::from_ptr(e1.as_ptr()) }.to_string_lossy().into_owned()).map(|_| Vec::new())
+        }).collect())
     }
 
     /// Arc::clone of a parameter set created on another context of the same device
@@ -349,6 +362,10 @@ unsafe impl Sync for Params {}
 impl Params {
     pub fn extension_degree(&self) -> usize {
         self.extension_degree
+    }
+    /// the library's handle of this parameter set (a key for per-parameter caches such as a process-wide prove pool)
+    pub fn handle(&self) -> u64 {
+        self.handle
     }
 }
 impl Drop for Params {
@@ -594,6 +611,88 @@ impl Batcher {
         let mut err = [0 as core::ffi::c_char; 256];
         let rc = unsafe { ffi::bpp_batcher_verify(self.raw, &raw_in, err.as_mut_ptr(), err.len()) };
         map_rc(rc, unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned())
+    }
+}
+
+/// `bpp_prove_item`s of borrowed `ProveItem`s, with the promise arrays they point into
+struct RawProveItems {
+    raw: Vec<ffi::bpp_prove_item>,
+    _mins: Vec<Vec<u64>>,
+    _present: Vec<Vec<u8>>,
+}
+impl RawProveItems {
+    fn new(items: &[ProveItem<'_>]) -> RawProveItems {
+        let present: Vec<Vec<u8>> = items.iter().map(|i| i.min_values.iter().map(|v| v.is_some() as u8).collect()).collect();
+        let mins: Vec<Vec<u64>> = items.iter().map(|i| i.min_values.iter().map(|v| v.unwrap_or(0)).collect()).collect();
+        let raw = items.iter().enumerate().map(|(k, i)| ffi::bpp_prove_item {
+            values: i.values.as_ptr(),
+            blindings32: i.blindings.as_ptr(),
+            commitments32: i.commitments.as_ptr(),
+            m: i.values.len() as u32,
+            min_values: mins[k].as_ptr(),
+            min_present: present[k].as_ptr(),
+            seed_nonce32: i.seed_nonce.map_or(ptr::null(), |s| s.as_ptr()),
+            transcript_state: i.transcript_state.map_or(ptr::null(), |s| s.as_ptr()),
+            transcript_label: i.transcript_label.as_ptr(),
+            label_len: i.transcript_label.len(),
+            rng_bytes: i.rng_bytes.as_ptr(),
+            rng_len: i.rng_bytes.len(),
+        }).collect();
+        RawProveItems { raw, _mins: mins, _present: present }
+    }
+}
+
+/// `bpp_prove_pool`: many threads, each with a few proofs (of any aggregation factors) per call; the library proves the calls
+/// that are waiting as ONE mixed-aggregation engine call.  `prove` blocks and returns what `Engine::prove_batch_mixed` on this
+/// call's items would, as the call's first error or all of its proofs.  Shareable between threads (`&self`).
+pub struct ProvePool {
+    raw: *mut ffi::bpp_prove_pool,
+    _engine: Option<Engine>,  // the context of the first lane, when the pool owns it (dropped after the pool itself)
+}
+unsafe impl Send for ProvePool {}
+unsafe impl Sync for ProvePool {}
+
+impl ProvePool {
+    pub fn new(engine: &Engine, params: &Params, lanes: u32, max_wait_us: u32, max_calls: u32) -> Result<ProvePool, GpuError> {
+        let mut raw = core::ptr::null_mut();
+        let rc = unsafe { ffi::bpp_prove_pool_create(engine.ctx, params.handle, lanes, max_wait_us, max_calls, &mut raw) };
+        map_rc(rc, String::from("bpp_prove_pool_create"))?;
+        Ok(ProvePool { raw, _engine: None })
+    }
+    /// the same, taking ownership of `engine` (a context that exists for this pool only); `params` is retained on it first
+    pub fn new_owning(engine: Engine, params: &Params, lanes: u32, max_wait_us: u32, max_calls: u32) -> Result<ProvePool, GpuError> {
+        map_rc(unsafe { ffi::bpp_params_retain(engine.ctx, params.handle) }, String::from("bpp_params_retain"))?;
+        let mut p = ProvePool::new(&engine, params, lanes, max_wait_us, max_calls)?;
+        p._engine = Some(engine);
+        Ok(p)
+    }
+    pub fn prove(&self, items: &[ProveItem<'_>]) -> Result<Vec<Vec<u8>>, GpuError> {
+        let keep = RawProveItems::new(items);
+        let stride = 1 + 32 * (6 + 5 + 2 * 12);
+        let mut out = vec![0u8; stride * items.len()];
+        let mut lens = vec![0usize; items.len()];
+        let mut err = [0 as core::ffi::c_char; 256];
+        let rc = unsafe {
+            ffi::bpp_prove_pool_prove(self.raw, keep.raw.as_ptr(), keep.raw.len(), out.as_mut_ptr(), stride, lens.as_mut_ptr(), err.as_mut_ptr(),
+                                      err.len())
+        };
+        map_rc(rc, unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned())?;
+        Ok((0..items.len()).map(|k| out[k * stride..k * stride + lens[k]].to_vec()).collect())
+    }
+    pub fn set_limits(&self, max_calls: u32, max_proofs: u32) -> Result<(), GpuError> {
+        map_rc(unsafe { ffi::bpp_prove_pool_set_limits(self.raw, max_calls, max_proofs) }, String::from("bpp_prove_pool_set_limits"))
+    }
+    /// (callers served in pooled calls, engine calls, calls that ran alone, largest pool in calls, in proofs)
+    pub fn stats(&self) -> (u64, u64, u64, u32, u32) {
+        let (mut a, mut b, mut c, mut d, mut e) = (0u64, 0u64, 0u64, 0u32, 0u32);
+        unsafe { ffi::bpp_prove_pool_stats(self.raw, &mut a, &mut b, &mut c, &mut d, &mut e) };
+        (a, b, c, d, e)
+    }
+}
+
+impl Drop for ProvePool {
+    fn drop(&mut self) {
+        unsafe { ffi::bpp_prove_pool_destroy(self.raw) }  // (fields drop afterwards: the owned engine outlives the pool)
     }
 }
 
