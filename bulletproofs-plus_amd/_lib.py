@@ -56,6 +56,11 @@ class ProveProfile(Structure):
                 ("fb_window_bits", c_uint32), ("fb_windows", c_uint32), ("sub_batches", c_uint32)]
 
 
+class ProveCheckStats(Structure):
+    """struct bpp_prove_check_stats: what the prover's self-check ("prove_check" = 1) of a context has done"""
+    _fields_ = [(n, c_uint64) for n in ("calls", "proofs", "batch_failures", "remade", "failed")]
+
+
 class RuntimeInfo(Structure):
     """bpp_runtime_info: what the library sees of its runtime preconditions (hardware queues, contexts, the small-call gate)"""
     _fields_ = [("device", c_int), ("contexts", c_uint32), ("contexts_peak", c_uint32), ("hw_queues", c_uint32),
@@ -147,6 +152,8 @@ SYMBOLS = [
     ("bpp_prove_pool_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint32),
                                      POINTER(c_uint32)]),
     ("bpp_prove_pool_destroy", None, [c_void_p]),
+    ("bpp_prove_check_stats", c_int, [c_void_p, POINTER(ProveCheckStats)]),
+    ("bpp_prove_pool_check_stats", c_int, [c_void_p, POINTER(ProveCheckStats)]),
     ("bpp_batch_trace", c_int, [c_void_p, c_uint64, c_int, c_void_p, c_size_t, POINTER(c_size_t)]),
     ("bpp_batch_shape", c_int, [c_void_p, c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32),
                                 POINTER(c_uint32), POINTER(c_uint32)]),

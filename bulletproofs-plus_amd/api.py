@@ -42,7 +42,14 @@ class ProofError(Exception):
 
 
 class EngineError(RuntimeError):
-    """negative return codes of the C ABI: HIP failures, no gfx950 device, bad handles"""
+    """negative return codes of the C ABI: HIP failures, no gfx950 device, bad handles, a proof that failed the prover's self-check
+    (SELF_CHECK); `code` is the C code where one is known"""
+
+    SELF_CHECK = -5  # BPP_ERR_SELF_CHECK
+
+    def __init__(self, msg="", code=None):
+        super().__init__(msg)
+        self.code = code
 
 
 class VerifyAction(enum.IntEnum):
@@ -87,7 +94,7 @@ def _check(rc, ctx=None, errbuf=None):
         msg = m.decode(errors="replace") if m else ""
     if rc > 0:
         raise ProofError(rc, msg)
-    raise EngineError("bpp engine error %d: %s" % (rc, msg))
+    raise EngineError("bpp engine error %d: %s" % (rc, msg), rc)
 
 
 class Engine:
@@ -151,6 +158,13 @@ class Engine:
         calls, redraws = c_uint64(), c_uint64()
         _check(self.lib.bpp_device_chain_stats(self.ctx, byref(calls), byref(redraws)), self.ctx)
         return int(calls.value), int(redraws.value)
+
+    def prove_check_stats(self):
+        """bpp_prove_check_stats: what the prover's self-check ("prove_check" = 1) of this context has done -- prove calls and proofs
+        checked, calls whose checking batch was rejected, proofs made again, proofs that failed with EngineError.SELF_CHECK"""
+        s = _lib.ProveCheckStats()
+        _check(self.lib.bpp_prove_check_stats(self.ctx, byref(s)), self.ctx)
+        return {n: int(getattr(s, n)) for n, _ in _lib.ProveCheckStats._fields_}
 
     def last_profile(self):
         p = _lib.Profile()
@@ -533,7 +547,8 @@ class RangeProof:
     def prove_batch_mixed(transcripts, statements, witnesses, rng_bytes):
         """n x RangeProof::prove_with_rng of ANY aggregation factors (powers of two up to the parameters' maximum) in one engine
         call (bpp_prove_batch_mixed).  Returns one entry per item: its RangeProof, or the ProofError that prove_batch on that item
-        alone would raise.  An item that fails never stops the others."""
+        alone would raise, or -- "prove_check" = 1 -- an EngineError with code EngineError.SELF_CHECK for a proof that failed the
+        self-check.  An item that fails never stops the others."""
         if not statements or len(statements) != len(witnesses) or len(transcripts) != len(statements) or \
                 len(rng_bytes) != len(statements):
             raise ProofError(ProofErrorKind.InvalidArgument, "Range statements, witnesses, transcripts length mismatch")
@@ -551,13 +566,16 @@ class RangeProof:
                 [transcripts[i] for i in keep], [statements[i] for i in keep], [witnesses[i] for i in keep],
                 [rng_bytes[i] for i in keep]))
             for k, i in enumerate(keep):
-                res[i] = RangeProof.from_bytes(raw[k]) if codes[k] == 0 else ProofError(codes[k], msgs[k])
+                if codes[k] == EngineError.SELF_CHECK:
+                    res[i] = EngineError("bpp engine error %d: %s" % (codes[k], msgs[k]), codes[k])
+                else:
+                    res[i] = RangeProof.from_bytes(raw[k]) if codes[k] == 0 else ProofError(codes[k], msgs[k])
         return res
 
     @staticmethod
     def _prove_mixed_call(marshalled):
-        """bpp_prove_batch_mixed over marshalled items -> (proof bytes per item, codes, messages); an engine fault (a negative code)
-        raises EngineError"""
+        """bpp_prove_batch_mixed over marshalled items -> (proof bytes per item, codes, messages); an engine fault (a negative code
+        other than EngineError.SELF_CHECK, which is an item's own outcome) raises EngineError"""
         params, items, n, _keep = marshalled
         eng = params.engine
         stride = 1 + 32 * (6 + 5 + 2 * 12)
@@ -567,8 +585,9 @@ class RangeProof:
         err = ctypes.create_string_buffer(256)
         rc = eng.lib.bpp_prove_batch_mixed(eng.ctx, params.handle, items, n, out, stride, lens, status, err, 256)
         codes = [status[i] for i in range(n)]
-        if rc < 0 or any(c < 0 for c in codes):
-            _check(min([rc] + codes), eng.ctx, err)
+        faults = [c for c in [rc] + codes if c < 0 and c != EngineError.SELF_CHECK]
+        if faults:
+            _check(min(faults), eng.ctx, err)
         raw = bytes(out)
         msgs = [""] * n
         for i in range(n):

@@ -570,8 +570,21 @@ struct bpp_ctx {
   // would race with it); bpp_ctx_set_option changes them afterwards.
   struct Options {
     int transcripts_wave = -1, tables_wave = -1, side_decompress = -1, msm_c_bias = -1, msm_c_max = -1, msm_c_add = -1, msm_rc2 = -1, msm_quad = -1, msm_final_quad = -1,
-        fb_threads = -1, prove_subs = -1, msm_split = -1, fused_columns = -1, prove_prio = -1, prove_fused = -1, static_gemm = -1, lazy_columns = -1, ct = -1, prove_parts = -1, prove_waves = -1, prove_fifo = -1, chain = -1, chain_test_zero = 0, wait = -1, ct_back = -1, chain_inline = -1, wide_in_lanes = -1;
+        fb_threads = -1, prove_subs = -1, msm_split = -1, fused_columns = -1, prove_prio = -1, prove_fused = -1, static_gemm = -1, lazy_columns = -1, ct = -1, prove_parts = -1, prove_waves = -1, prove_fifo = -1, chain = -1, chain_test_zero = 0, wait = -1, ct_back = -1, chain_inline = -1, wide_in_lanes = -1,
+        prove_check = -1;
   } opt;
+  // the prover's self-check ("prove_check" = 1, engine_prove.h: prove_self_check): the verification batch it keeps between calls
+  // (the next check's upload adopts its buffers, as the next upload adopts spare_batch's), the remembered waits of ITS
+  // verifications (the prover's and the caller's verifications keep theirs), its counters
+  std::unique_ptr<Batch> check_spare;
+  WaitHint check_hint_rng, check_hint_end;
+  struct bpp_prove_check_stats check_stats{};
+  // test knobs of the self-check (bpp_ctx_set_option only, no environment variable, not copied to a prove pool's lanes): XOR
+  // `mask` into byte `byte` of proof `proof` - 1 in the page-locked host copy of the NEXT checked prove call, before the check; `times`
+  // = 2 alters the remake of that proof as well.  The call's entry point takes them and puts the defaults back.
+  struct CheckTamper {
+    int proof = 0, byte = 1, mask = 1, times = 1;
+  } tamper;
   std::unique_ptr<Pipeline> pipe;  // bpp_verify_submit_packed / bpp_verify_collect: lanes, tickets (built on first submit)
   std::mutex pipe_init_mu;
   uint32_t pipe_depth = 3;
@@ -629,6 +642,19 @@ const OptionName kOptions[] = {
     {"chain_inline", "BPP_CHAIN_INLINE", &bpp_ctx::Options::chain_inline},
     // chain = 2: the reduction mod l of the host sponges' bytes in k_scalars_lanes' prologue (1, the rule) or as a launch of its own (0)
     {"wide_in_lanes", "BPP_WIDE_IN_LANES", &bpp_ctx::Options::wide_in_lanes},
+    // 1: every proof of bpp_prove_batch / bpp_prove_batch_mixed (and of a prove pool made from this context) is verified on this
+    // context before it is returned, a rejected one made again once (engine_prove.h: prove_self_check); 0 / -1: off
+    {"prove_check", "BPP_PROVE_CHECK", &bpp_ctx::Options::prove_check},
+};
+struct TamperName {
+  const char *name;
+  int bpp_ctx::CheckTamper::*field;
+};
+const TamperName kTamperKnobs[] = {
+    {"prove_check_tamper", &bpp_ctx::CheckTamper::proof},
+    {"prove_check_tamper_byte", &bpp_ctx::CheckTamper::byte},
+    {"prove_check_tamper_xor", &bpp_ctx::CheckTamper::mask},
+    {"prove_check_tamper_times", &bpp_ctx::CheckTamper::times},
 };
 void options_from_env(bpp_ctx *c) {
   for (const OptionName &o : kOptions)
@@ -1018,6 +1044,7 @@ void bpp_ctx_destroy(bpp_ctx *ctx) {
   (void)hipStreamSynchronize(ctx->stream);
   ctx->batches.clear();
   ctx->spare_batch.reset();
+  ctx->check_spare.reset();
   for (uint64_t h : ctx->held_precomps) (void)precomp_registry().release(h);
   for (uint64_t h : ctx->held_params) (void)params_registry().release(h);
   if (ctx->ev_ready)
@@ -1118,6 +1145,11 @@ int bpp_ctx_set_option(bpp_ctx *ctx, const char *name, int value) {
   for (const OptionName &o : kOptions)
     if (strcmp(name, o.name) == 0) {
       ctx->opt.*(o.field) = value;
+      return BPP_OK;
+    }
+  for (const TamperName &o : kTamperKnobs)
+    if (strcmp(name, o.name) == 0) {  // (-1: the knob's default)
+      ctx->tamper.*(o.field) = value >= 0 ? value : bpp_ctx::CheckTamper{}.*(o.field);
       return BPP_OK;
     }
   return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string("unknown option: ") + name);
@@ -3054,6 +3086,13 @@ int bpp_profile_enable(bpp_ctx *ctx, int on) {
   if (!ctx) return BPP_ERR_BAD_HANDLE;
   ctx->profile = on != 0;
   ctx->profile_light = on == 2;
+  return BPP_OK;
+}
+
+int bpp_prove_check_stats(bpp_ctx *ctx, struct bpp_prove_check_stats *out) {
+  if (!ctx || !out) return BPP_ERR_BAD_HANDLE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  *out = ctx->check_stats;
   return BPP_OK;
 }
 

@@ -6,6 +6,13 @@
 
 // ================================================================= batch prover
 namespace {
+size_t prove_item_len(const Params &P, uint32_t m);
+void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_prove_item *items, uint32_t B, size_t plen, uint8_t *&proofs,
+                      uint32_t *&status, const bpp_ctx::CheckTamper &tamper, bool remake, std::vector<uint8_t> &kept_proofs,
+                      std::vector<uint32_t> &kept_status);
+// (a host-side flag next to the device's PV_STATUS_* bits: the proof failed the self-check, after its remake if there was one)
+#define PV_STATUS_SELF_CHECK 0x100u
+
 // The body of bpp_prove_batch (the context's lock held, its device current).  dev_status == nullptr: bpp_prove_batch itself, which
 // turns the first device-side status word into the call's error.  Otherwise (bpp_prove_batch_mixed) the status words go to
 // dev_status[i] and every proof is copied out at proof_stride (*proof_len: the longest): whoever called sorts the items out.
@@ -13,8 +20,11 @@ namespace {
 // They run as ragged launches aligned at the end: R = items[0]'s rounds global steps, proof i joins at step R - rounds_i
 // (ProveDesc::roff), and as the proofs are sorted, those active at a step are a prefix of every sub-batch: each round's kernels
 // and fixed-base MSM cover only that prefix.  Every proof reaches the final step in the same launch.
+// "prove_check" = 1: the proofs are verified before any of them is copied out (prove_self_check; `tamper`: the test knobs taken by
+// the call's entry point, proof = index + 1 in `items`; remake = false: the call IS a remake, whose failure is final).
 int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
-                  size_t proof_stride, size_t *proof_len, char *errbuf, size_t errbuf_len, uint32_t *dev_status, bool mixed = false) {
+                  size_t proof_stride, size_t *proof_len, char *errbuf, size_t errbuf_len, uint32_t *dev_status, bool mixed = false,
+                  const bpp_ctx::CheckTamper &tamper = bpp_ctx::CheckTamper{}, bool remake = true) {
   try {
     const std::shared_ptr<Params> Pp = params_registry().get(params);
     if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
@@ -582,26 +592,201 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
       pp.fb_windows = P.fb_geo.items;  // additions per term
       pp.sub_batches = n_sub;
     }
-    if (dev_status) {
-      memcpy(dev_status, pin_status, (size_t)B * sizeof(uint32_t));
-    } else {
+    if (!dev_status) {
       for (uint32_t i = 0; i < B; i++) {
         if (pin_status[i] & PV_STATUS_COMMIT_MISMATCH) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Witness opening is invalid!"};
         if (pin_status[i] & PV_STATUS_TRANSCRIPT)
           throw ProofErr{BPP_ERR_VERIFICATION_FAILED, "Identity element cannot be added to the transcript / zero challenge"};
       }
     }
+    std::vector<uint8_t> kept_proofs;  // (where the proofs and status words move when a remake needs the staging)
+    std::vector<uint32_t> kept_status;
+    if (ctx->opt.prove_check > 0)
+      prove_self_check(ctx, params, P, items, B, plen, pin_proofs, pin_status, tamper, remake, kept_proofs, kept_status);
+    if (dev_status) {
+      memcpy(dev_status, pin_status, (size_t)B * sizeof(uint32_t));
+    } else {
+      for (uint32_t i = 0; i < B; i++)
+        if (pin_status[i] & PV_STATUS_SELF_CHECK) {
+          char msg[160];
+          snprintf(msg, sizeof(msg), "proof %u failed the engine's self-check: the verifier rejected it and its remake", i);
+          throw ProofErr{BPP_ERR_SELF_CHECK, msg, BPP_TIER_ENGINE, i};
+        }
+    }
     for (uint32_t i = 0; i < B; i++) memcpy(proofs_out + (size_t)i * proof_stride, &pin_proofs[(size_t)i * plen], plen);
     return BPP_OK;
   }
   BPP_CATCH(ctx, errbuf, errbuf_len)
+}
+
+// ================================================================= self-check ("prove_check" = 1)
+// The proofs a prove call made are verified on the same context before any byte of them leaves the engine: the verifier's own
+// upload (upload_host.h) and resident path (verify_resident_locked), no parser or kernel of its own.  Only public inputs are
+// looked at -- the proof bytes and the item's statement and transcript -- and nothing is written but status words.
+//
+// Locks: the context's lock is held (the prove call's).  The check does NOT pass the device's small-call gate (GateHold): the gate
+// is always taken BEFORE a context's lock, and a thread that holds a context's lock and then waits for the gate deadlocks against
+// small verify calls that hold the gate and wait for this context's lock.  A prove call never passes the gate either; its check is
+// part of it.
+
+// The test knobs of the context's NEXT prove call (bpp_ctx_set_option), reset as they are taken
+bpp_ctx::CheckTamper take_tamper(bpp_ctx *ctx) {
+  const bpp_ctx::CheckTamper t = ctx->tamper;
+  ctx->tamper = bpp_ctx::CheckTamper{};
+  return t;
+}
+
+// One verification of the check as ONE reference batch (chunk 0, VerifyOnly), or -- with `single` -- every proof as a group of its
+// own (bpp_verify_resident_groups' path: group_first = 0, 1, ..., n), its code in codes[k].  The batch is the check's own: its
+// buffers come from ctx->check_spare and go back there, the caller's resident batches and the spare batch that the caller's next
+// upload adopts are left as they were.  Returns 0, or the upload's code when it refuses the batch (a proof of the wrong length, a
+// non-canonical scalar: nothing was verified, `codes` untouched), or the verification's finding; an engine fault throws.
+int check_verify(bpp_ctx *ctx, uint64_t params, const std::vector<bpp_verify_item> &vi, bool single, std::vector<int> *codes) {
+  char err[256];
+  err[0] = 0;
+  uint64_t h = 0;
+  std::swap(ctx->spare_batch, ctx->check_spare);  // (the upload adopts the check's buffers; the caller's spare waits in check_spare)
+  ScopeExit give_back{[&] {
+    std::unique_ptr<Batch> mine;
+    auto it = h ? ctx->batches.find(h) : ctx->batches.end();
+    if (it != ctx->batches.end()) {
+      (void)hipStreamSynchronize(ctx->stream);
+      wipe_batch_secrets(*it->second, ctx->stream);  // (none: no seed nonce, VerifyOnly)
+      (void)hipStreamSynchronize(ctx->stream);
+      mine = std::move(it->second);
+      ctx->batches.erase(it);
+    } else {
+      mine = std::move(ctx->spare_batch);  // (the upload refused the batch before it adopted anything)
+    }
+    ctx->spare_batch = std::move(ctx->check_spare);
+    ctx->check_spare = std::move(mine);
+  }};
+  int rc = upload_impl(ctx, params, vi.data(), vi.size(), nullptr, &h, nullptr, nullptr, err, sizeof(err));
+  if (rc < 0) throw ProofErr{rc, err, BPP_TIER_ENGINE};
+  if (rc != BPP_OK) return rc;
+  if (!single) {
+    rc = verify_resident_locked(ctx, h, BPP_VERIFY_ONLY, 0, nullptr, nullptr, err, sizeof(err), true);
+    if (rc == BPP_REDRAW_ON_HOST) rc = verify_resident_locked(ctx, h, BPP_VERIFY_ONLY, 0, nullptr, nullptr, err, sizeof(err), false);
+    if (rc < 0) throw ProofErr{rc, err, BPP_TIER_ENGINE};
+    return rc;
+  }
+  std::vector<uint32_t> first(vi.size() + 1);
+  for (size_t k = 0; k <= vi.size(); k++) first[k] = (uint32_t)k;
+  std::vector<bpp_shard_result> res(vi.size());
+  rc = verify_groups_core(ctx, h, first.data(), vi.size(), nullptr, res.data(), nullptr, nullptr);
+  if (rc != BPP_OK) throw ProofErr{rc < 0 ? rc : BPP_ERR_ENGINE, ctx->err, BPP_TIER_ENGINE};
+  for (size_t k = 0; k < vi.size(); k++) (*codes)[k] = res[k].code;
+  return BPP_OK;
+}
+
+// The check of one prove_uniform call.  The proofs whose status word is 0 -- at proofs + i * plen, each of its own item's length --
+// are verified as ONE reference batch.  When that batch is rejected (the upload refuses it, a PASS-1 finding, a point that does not
+// decode, the final MSM), the proofs that fail on their own are located: every proof as a group of its own, or, where the upload
+// refused the batch, as one-item verifications.  Each of them is made again, alone, by a one-item prove_uniform with the check on
+// (remake = false there): its bytes depend on its item alone, so a device that computes correctly gives the same bytes.  A remake
+// that passes replaces the proof; one that fails sets PV_STATUS_SELF_CHECK in the item's status word.  A remake reuses the call's
+// staging: the proofs and status words move to kept_* first, and `proofs` / `status` point there afterwards.
+void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_prove_item *items, uint32_t B, size_t plen, uint8_t *&proofs,
+                      uint32_t *&status, const bpp_ctx::CheckTamper &tamper, bool remake, std::vector<uint8_t> &kept_proofs,
+                      std::vector<uint32_t> &kept_status) {
+  std::vector<uint32_t> which;  // the items the device made a proof for
+  for (uint32_t i = 0; i < B; i++)
+    if (status[i] == 0) which.push_back(i);
+  if (which.empty()) return;
+  if (tamper.proof > 0 && (uint32_t)tamper.proof <= B) {  // (test knob: a byte of the host copy, never the device's work)
+    const uint32_t i = (uint32_t)tamper.proof - 1;
+    if ((size_t)tamper.byte < prove_item_len(P, items[i].m)) proofs[(size_t)i * plen + tamper.byte] ^= (uint8_t)tamper.mask;
+  }
+  std::vector<bpp_verify_item> vi(which.size());
+  for (size_t k = 0; k < which.size(); k++) {
+    const bpp_prove_item &it = items[which[k]];
+    bpp_verify_item &v = vi[k];
+    memset(&v, 0, sizeof(v));
+    v.proof = proofs + (size_t)which[k] * plen;
+    v.proof_len = prove_item_len(P, it.m);
+    v.commitments32 = it.commitments32;
+    v.m = it.m;
+    v.min_values = it.min_values;
+    v.min_present = it.min_present;
+    v.seed_nonce32 = nullptr;  // (the blinding factors are the prover's secret; mask recovery is not what is checked)
+    v.transcript_state = it.transcript_state;
+    v.transcript_label = it.transcript_label;
+    v.label_len = it.transcript_label ? it.label_len : 0;
+  }
+  std::vector<uint32_t> bad;  // the proofs that fail on their own
+  {
+    // the check leaves no trace on what the context remembers: its own waits (not the prover's nor the caller's verifications'), the
+    // caller's last profile and last error
+    std::swap(ctx->wait_hint_rng, ctx->check_hint_rng);
+    std::swap(ctx->wait_hint_end, ctx->check_hint_end);
+    const bpp_profile prof = ctx->prof;
+    const std::string err_before = ctx->err;
+    ScopeExit restore{[&] {
+      std::swap(ctx->wait_hint_rng, ctx->check_hint_rng);
+      std::swap(ctx->wait_hint_end, ctx->check_hint_end);
+      ctx->prof = prof;
+      ctx->err = err_before;
+    }};
+    if (remake) {
+      ctx->check_stats.calls++;
+      ctx->check_stats.proofs += which.size();
+    }
+    if (check_verify(ctx, params, vi, false, nullptr) == BPP_OK) return;
+    if (remake) ctx->check_stats.batch_failures++;
+    std::vector<int> codes(vi.size(), BPP_OK);
+    if (check_verify(ctx, params, vi, true, &codes) != BPP_OK) {  // the upload refused the batch: one-item verifications
+      for (size_t k = 0; k < vi.size(); k++) codes[k] = check_verify(ctx, params, std::vector<bpp_verify_item>(1, vi[k]), false, nullptr);
+    }
+    for (size_t k = 0; k < vi.size(); k++)
+      if (codes[k] != BPP_OK) bad.push_back(which[k]);
+  }
+  // (a batch rejected while every proof passes on its own: each proof has then passed a complete verification of its own, and
+  // none is made again)
+  if (bad.empty()) return;
+  if (!remake) {
+    for (uint32_t i : bad) status[i] |= PV_STATUS_SELF_CHECK;
+    return;
+  }
+  kept_proofs.assign(proofs, proofs + (size_t)B * plen);
+  kept_status.assign(status, status + B);
+  proofs = kept_proofs.data();
+  status = kept_status.data();
+  const WaitHint hint = ctx->wait_hint_prove;  // (a remake must not teach the call's wait the time of a one-proof call)
+  const bpp_prove_profile pprof = ctx->pprof;
+  ScopeExit restore_prove{[&] {
+    ctx->wait_hint_prove = hint;
+    ctx->pprof = pprof;
+  }};
+  for (uint32_t i : bad) {
+    const size_t len = prove_item_len(P, items[i].m);
+    std::vector<uint8_t> one(len, 0);
+    uint32_t st = 0;
+    size_t got = 0;
+    char err[256];
+    err[0] = 0;
+    bpp_ctx::CheckTamper again{};
+    if (tamper.proof == (int)i + 1 && tamper.times >= 2) {
+      again = tamper;
+      again.proof = 1;
+    }
+    ctx->check_stats.remade++;
+    const int rc = prove_uniform(ctx, params, &items[i], 1, one.data(), len, &got, err, sizeof(err), &st, false, again, false);
+    if (rc != BPP_OK) throw ProofErr{rc, err, rc < 0 ? BPP_TIER_ENGINE : BPP_TIER_CONSTRUCTION};
+    if (st != 0 || got != len) {
+      status[i] |= PV_STATUS_SELF_CHECK;
+      ctx->check_stats.failed++;
+    } else {
+      memcpy(proofs + (size_t)i * plen, one.data(), len);
+    }
+  }
 }
 }  // namespace
 
 extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
                                size_t proof_stride, size_t *proof_len, char *errbuf, size_t errbuf_len) {
   BPP_ENTRY(ctx);
-  return prove_uniform(ctx, params, items, n_items, proofs_out, proof_stride, proof_len, errbuf, errbuf_len, nullptr);
+  const bpp_ctx::CheckTamper tamper = take_tamper(ctx);
+  return prove_uniform(ctx, params, items, n_items, proofs_out, proof_stride, proof_len, errbuf, errbuf_len, nullptr, false, tamper);
 }
 
 // ================================================================= mixed aggregation factors
@@ -611,6 +796,8 @@ extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_it
 // A proof's bytes depend on nothing but its own item (its transcript, its witness, its randomness, and the parameters' N, T and
 // its own M), so every proof equals the one a bpp_prove_batch of its class would make.  DESIGN.md 4.2 has the choice of this form.
 namespace {
+
+const char *const kSelfCheckMsg = "the proof failed the engine's self-check: the verifier rejected it and its remake";
 
 struct MixedOutcome {
   std::vector<int> code;
@@ -679,13 +866,18 @@ void prove_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, siz
   if (idx.empty()) return;
   std::vector<bpp_prove_item> sub(idx.size());
   for (size_t k = 0; k < idx.size(); k++) sub[k] = items[idx[k]];
+  bpp_ctx::CheckTamper tamper = take_tamper(ctx);  // (the knob names the caller's item: here, its place in the sorted call)
+  const int tampered = tamper.proof;
+  tamper.proof = 0;
+  for (size_t k = 0; k < idx.size(); k++)
+    if ((int)idx[k] + 1 == tampered) tamper.proof = (int)k + 1;
   const size_t plen = prove_item_len(P, sub[0].m);
   std::vector<uint8_t> buf(idx.size() * plen, 0);
   std::vector<uint32_t> status(idx.size(), 0);
   char err[256];
   err[0] = 0;
   size_t len = 0;
-  const int rc = prove_uniform(ctx, params, sub.data(), sub.size(), buf.data(), plen, &len, err, sizeof(err), status.data(), true);
+  const int rc = prove_uniform(ctx, params, sub.data(), sub.size(), buf.data(), plen, &len, err, sizeof(err), status.data(), true, tamper);
   {
     for (size_t k = 0; k < idx.size(); k++) {
       const uint32_t i = idx[k];
@@ -698,6 +890,9 @@ void prove_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, siz
       } else if (status[k] & PV_STATUS_TRANSCRIPT) {
         out.code[i] = BPP_ERR_VERIFICATION_FAILED;
         out.msg[i] = "Identity element cannot be added to the transcript / zero challenge";
+      } else if (status[k] & PV_STATUS_SELF_CHECK) {
+        out.code[i] = BPP_ERR_SELF_CHECK;
+        out.msg[i] = kSelfCheckMsg;
       } else {
         memcpy(proofs_out + (size_t)i * proof_stride, &buf[k * plen], proof_lens[i]);
       }
@@ -725,7 +920,7 @@ extern "C" int bpp_prove_batch_mixed(bpp_ctx *ctx, uint64_t params, const bpp_pr
 }
 
 // The message that goes with item_status of bpp_prove_batch_mixed: the item's host-side checks run again (no device work), and an
-// item that passes them failed on the device, whose two findings have one message each.  Keeps no state: any thread, any time.
+// item that passes them failed on the device, whose two findings have one message each, or the self-check (BPP_ERR_SELF_CHECK).  Keeps no state: any thread, any time.
 extern "C" int bpp_prove_item_message(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item, size_t proof_stride, int status,
                                       char *errbuf, size_t errbuf_len) {
   if (!ctx || !item) return BPP_ERR_BAD_HANDLE;
@@ -739,6 +934,7 @@ extern "C" int bpp_prove_item_message(bpp_ctx *ctx, uint64_t params, const bpp_p
   }
   set_err(errbuf, errbuf_len, status == BPP_ERR_INVALID_ARGUMENT ? "Witness opening is invalid!"
                               : status == BPP_ERR_VERIFICATION_FAILED ? "Identity element cannot be added to the transcript / zero challenge"
+                              : status == BPP_ERR_SELF_CHECK ? kSelfCheckMsg
                               : "");
   return status;
 }

@@ -91,10 +91,11 @@ void prove_pool_run(bpp_prove_pool *p, bpp_prove_pool::Lane &L, const std::vecto
     }
     // fan out: a caller's outcome is its first failing item's (bpp_prove_batch_mixed's return value and message).  An engine fault
     // (a negative code: an allocation the pooled call needed, a HIP error) is nobody's input: the callers it hit get a call of their own.
+    // BPP_ERR_SELF_CHECK is an item's own outcome, after its one remake: it is handed on like a finding.
     at = 0;
     for (auto *r : reqs) {
       bool fault = false;
-      for (size_t i = 0; i < r->n_items; i++) fault = fault || out.code[at + i] < 0;
+      for (size_t i = 0; i < r->n_items; i++) fault = fault || (out.code[at + i] < 0 && out.code[at + i] != BPP_ERR_SELF_CHECK);
       if (fault) {
         prove_pool_solo(p, L, r);
         at += r->n_items;
@@ -184,6 +185,22 @@ int bpp_prove_pool_stats(bpp_prove_pool *p, uint64_t *pooled_calls, uint64_t *en
   if (solo_calls) *solo_calls = p->solo_calls;
   if (largest_calls) *largest_calls = p->largest_pool_calls;
   if (largest_proofs) *largest_proofs = p->largest_pool_proofs;
+  return BPP_OK;
+}
+
+int bpp_prove_pool_check_stats(bpp_prove_pool *p, struct bpp_prove_check_stats *out) {
+  if (!p || !out) return BPP_ERR_BAD_HANDLE;
+  memset(out, 0, sizeof(*out));
+  for (auto &L : p->lanes) {  // (the lanes are fixed once the pool exists)
+    struct bpp_prove_check_stats s;
+    const int rc = bpp_prove_check_stats(L.ctx, &s);
+    if (rc != BPP_OK) return rc;
+    out->calls += s.calls;
+    out->proofs += s.proofs;
+    out->batch_failures += s.batch_failures;
+    out->remade += s.remade;
+    out->failed += s.failed;
+  }
   return BPP_OK;
 }
 

@@ -216,6 +216,13 @@ class ProvePool:
         self.engine.lib.bpp_prove_pool_stats(self.handle, *[byref(x) for x in v])
         return dict(zip(("pooled_calls", "engine_calls", "solo_calls", "largest_calls", "largest_proofs"), [x.value for x in v]))
 
+    def check_stats(self):
+        """bpp_prove_pool_check_stats: the self-check counters of every lane, summed (Engine.prove_check_stats); the first lane is
+        the engine the pool was made from"""
+        s = _lib.ProveCheckStats()
+        api._check(self.engine.lib.bpp_prove_pool_check_stats(self.handle, byref(s)), None)
+        return {n: int(getattr(s, n)) for n, _ in _lib.ProveCheckStats._fields_}
+
     def close(self):
         if self.handle:
             self.engine.lib.bpp_prove_pool_destroy(self.handle)

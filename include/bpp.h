@@ -40,6 +40,7 @@ extern "C" {
 #define BPP_ERR_NO_DEVICE (-2) /* no usable gfx950 device */
 #define BPP_ERR_BAD_HANDLE (-3)
 #define BPP_ERR_COMM (-4)      /* RCCL failure (library missing, communicator error): sharded entry points only */
+#define BPP_ERR_SELF_CHECK (-5) /* "prove_check" = 1: a proof the verifier rejected, made again once and rejected again */
 
 /* Where inside RangeProof::verify (src/range_proof.rs:756-1065) a check failed.  Lower = earlier in the reference's order
  * of checks; shards of one reference batch combine their findings by (tier, rank) -- see bpp_verify_sharded. */
@@ -89,8 +90,16 @@ const char *bpp_ctx_last_error(bpp_ctx *ctx);
  * chains once more, which redraw as the reference does), 2 = the sponges on host cores, Scalar::from_bytes_mod_order_wide and the
  * look for a zero weight on the device (half the host time of 0), -1 = the engine's rule: 2 for calls of 4096 proofs and more, else
  * 0), "wait" (how the calling thread waits for the device: 0 = hipStreamSynchronize, which spins on a core; 1 = naps of 50 us between
- * looks at an event, 1-2 % of a core; -1 = the engine's rule: naps for calls of 4096 proofs and more).  The environment variables BPP_<NAME> give
- * the initial values and are read ONCE, when the context is created: no verification path calls getenv. */
+ * looks at an event, 1-2 % of a core; -1 = the engine's rule: naps for calls of 4096 proofs and more), "prove_check" (1: every proof
+ * bpp_prove_batch / bpp_prove_batch_mixed make on this context -- and a prove pool made from it -- is verified on this context before
+ * any byte of it is returned; a rejected proof is made again once, and one rejected again fails with BPP_ERR_SELF_CHECK; see
+ * bpp_prove_check_stats.  0 and -1 = off, the engine's rule).  The environment variables BPP_<NAME> give
+ * the initial values and are read ONCE, when the context is created: no verification path calls getenv.
+ * Test knobs of "prove_check", settable here only (no environment variable, not copied to a prove pool's lanes), acting on the NEXT
+ * prove call of the context and then reset: "prove_check_tamper" = i + 1 XORs "prove_check_tamper_xor" (default 0x01) into byte
+ * "prove_check_tamper_byte" (default 1) of proof i in the page-locked host copy of the call's proofs, after the device wrote them and
+ * before they are checked (i counts the call's items as the caller passed them); "prove_check_tamper_times" = 1 (default) alters the
+ * first attempt only, 2 the remake of that proof as well.  Checked calls only. */
 int bpp_ctx_set_option(bpp_ctx *ctx, const char *name, int value);
 /* verifications of this context whose weights were made on the device ("chain" 1 or 2), and how many of those ran once more
  * with everything on the host because a weight came out zero */
@@ -465,6 +474,16 @@ int bpp_prove_pool_set_limits(bpp_prove_pool *p, uint32_t max_calls, uint32_t ma
 int bpp_prove_pool_stats(bpp_prove_pool *p, uint64_t *pooled_calls, uint64_t *engine_calls, uint64_t *solo_calls,
                          uint32_t *largest_calls, uint32_t *largest_proofs);
 void bpp_prove_pool_destroy(bpp_prove_pool *p);
+/* What the self-check ("prove_check" = 1) of a context has done: prove calls checked, proofs checked (those the device made without
+ * a finding of its own), calls whose checking batch was rejected, proofs made again, proofs that failed with BPP_ERR_SELF_CHECK.
+ * The remake's own check is counted in `remade` / `failed` only.  A struct tag, like POSIX's struct stat and stat(): a typedef
+ * cannot share the function's name.  bpp_prove_pool_check_stats sums the pool's lanes (its first lane is the context it was made
+ * from, whose other calls count as well). */
+struct bpp_prove_check_stats {
+  uint64_t calls, proofs, batch_failures, remade, failed;
+};
+int bpp_prove_check_stats(bpp_ctx *ctx, struct bpp_prove_check_stats *out);
+int bpp_prove_pool_check_stats(bpp_prove_pool *p, struct bpp_prove_check_stats *out);
 
 /* ---- parity / diagnostics: intermediates of the last verify on `batch`, for differential tests ---- */
 #define BPP_TRACE_CHALLENGES 1     /* per proof (rmax+3) x 32: y, z, e_0.., e_final (canonical), rmax = bpp_batch_shape's max_rounds

@@ -17,6 +17,7 @@ pub const BPP_ERR_ENGINE: c_int = -1;
 pub const BPP_ERR_NO_DEVICE: c_int = -2;
 pub const BPP_ERR_BAD_HANDLE: c_int = -3;
 pub const BPP_ERR_COMM: c_int = -4;
+pub const BPP_ERR_SELF_CHECK: c_int = -5;
 // where inside RangeProof::verify a check failed (src/range_proof.rs:756-1065): orders findings across shards
 pub const BPP_TIER_NONE: c_int = 0;
 pub const BPP_TIER_CONSTRUCTION: c_int = 1;
@@ -167,6 +168,17 @@ pub struct bpp_prove_profile {
     pub sub_batches: u32,
 }
 
+/// `struct bpp_prove_check_stats`: what the prover's self-check ("prove_check" = 1) of a context (or a prove pool's lanes) has done
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_prove_check_stats {
+    pub calls: u64,
+    pub proofs: u64,
+    pub batch_failures: u64,
+    pub remade: u64,
+    pub failed: u64,
+}
+
 /// `int (*bpp_all_gather_fn)(void *user, const void *send, void *recv, size_t bytes_per_rank)` (include/bpp.h)
 pub type bpp_all_gather_fn = Option<unsafe extern "C" fn(user: *mut c_void, send: *const c_void, recv: *mut c_void, bytes_per_rank: usize) -> c_int>;
 
@@ -279,6 +291,8 @@ extern "C" {
     pub fn bpp_prove_pool_stats(p: *mut bpp_prove_pool, pooled_calls: *mut u64, engine_calls: *mut u64, solo_calls: *mut u64,
                                 largest_calls: *mut u32, largest_proofs: *mut u32) -> c_int;
     pub fn bpp_prove_pool_destroy(p: *mut bpp_prove_pool);
+    pub fn bpp_prove_check_stats(ctx: *mut bpp_ctx, out: *mut bpp_prove_check_stats) -> c_int;
+    pub fn bpp_prove_pool_check_stats(p: *mut bpp_prove_pool, out: *mut bpp_prove_check_stats) -> c_int;
     // diagnostics
     pub fn bpp_batch_trace(ctx: *mut bpp_ctx, batch: u64, what: c_int, out: *mut u8, out_len: usize, written: *mut usize) -> c_int;
     pub fn bpp_batch_shape(ctx: *mut bpp_ctx, batch: u64, n_items: *mut u32, max_rounds: *mut u32, max_mn: *mut u32, total_dyn: *mut u32,

@@ -7,7 +7,7 @@
 pub mod ffi;
 
 use core::ffi::c_int;
-use std::{collections::HashMap, ffi::CStr, ptr, sync::{Arc, Mutex, OnceLock}};
+use std::{collections::HashMap, ffi::{CStr, CString}, ptr, sync::{Arc, Mutex, OnceLock}};
 
 /// Mirror of `tari_bulletproofs_plus::errors::ProofError` (src/errors.rs:11-28) plus engine faults.
 #[derive(Debug, Clone, PartialEq, Eq)]
@@ -17,7 +17,8 @@ pub enum GpuError {
     InvalidLength(String),
     InvalidBlake2b,
     SizeOverflow,
-    /// HIP failure, no gfx950 device, bad handle: no reference analogue
+    /// HIP failure, no gfx950 device, bad handle, a proof that failed the prover's self-check (`ffi::BPP_ERR_SELF_CHECK`): no
+    /// reference analogue
     Engine(i32, String),
 }
 
@@ -29,6 +30,7 @@ fn map_rc(rc: c_int, msg: String) -> Result<(), GpuError> {
         ffi::BPP_ERR_INVALID_LENGTH => Err(GpuError::InvalidLength(msg)),
         ffi::BPP_ERR_INVALID_BLAKE2B => Err(GpuError::InvalidBlake2b),
         ffi::BPP_ERR_SIZE_OVERFLOW => Err(GpuError::SizeOverflow),
+        ffi::BPP_ERR_SELF_CHECK => Err(GpuError::Engine(ffi::BPP_ERR_SELF_CHECK, msg)),
         other => Err(GpuError::Engine(other, msg)),
     }
 }
@@ -58,6 +60,12 @@ impl Engine {
 
     fn last_error(&self) -> String {
         unsafe { CStr::from_ptr(ffi::bpp_ctx_last_error(self.ctx)).to_string_lossy().into_owned() }
+    }
+
+    /// `bpp_ctx_set_option`: a per-context knob (include/bpp.h lists them; -1 restores the engine's rule), e.g. "prove_check" = 1
+    pub fn set_option(&self, name: &str, value: i32) -> Result<(), GpuError> {
+        let c = CString::new(name).map_err(|_| GpuError::InvalidArgument(String::from("option name holds a NUL byte")))?;
+        map_rc(unsafe { ffi::bpp_ctx_set_option(self.ctx, c.as_ptr(), value) }, self.last_error())
     }
 
     /// RangeParameters::init (src/range_parameters.rs:32-58); `h_base` / `g_bases` = None: the reference's defaults.
@@ -257,6 +265,13 @@ impl Engine {
         info
     }
 
+    /// what the prover's self-check ("prove_check" = 1, `bpp_ctx_set_option` or BPP_PROVE_CHECK) of this context has done
+    pub fn prove_check_stats(&self) -> Result<ffi::bpp_prove_check_stats, GpuError> {
+        let mut s = ffi::bpp_prove_check_stats::default();
+        map_rc(unsafe { ffi::bpp_prove_check_stats(self.ctx, &mut s) }, String::from("bpp_prove_check_stats"))?;
+        Ok(s)
+    }
+
     /// `RangeProof::verify_batch`: every `chunk` consecutive items are one reference batch (256 = MAX_RANGE_PROOF_BATCH_SIZE,
     /// 0 = the whole input).  Returns per item `Some(mask blindings, t x 32 bytes)` or `None`.
     pub fn verify_batch(&self, params: &Params, items: &[VerifyItem<'_>], action: Action, chunk: usize)
@@ -305,7 +320,8 @@ impl Engine {
     }
 
     /// n x `RangeProof::prove_with_rng` of any aggregation factors (powers of two up to the parameters' maximum) in one call
-    /// (bpp_prove_batch_mixed).  One entry per item: its `to_bytes()`, or the error `prove_batch` on that item alone returns.
+    /// (bpp_prove_batch_mixed).  One entry per item: its `to_bytes()`, or the error `prove_batch` on that item alone returns, or
+    /// (self-check on) `GpuError::Engine(ffi::BPP_ERR_SELF_CHECK, ..)` for a proof the verifier rejected twice.
     pub fn prove_batch_mixed(&self, params: &Params, items: &[ProveItem<'_>]) -> Result<Vec<Result<Vec<u8>, GpuError>>, GpuError> {
         let keep = RawProveItems::new(items);
         let stride = 1 + 32 * (6 + 5 + 2 * 12);
@@ -317,7 +333,7 @@ impl Engine {
             ffi::bpp_prove_batch_mixed(self.ctx, params.handle, keep.raw.as_ptr(), keep.raw.len(), out.as_mut_ptr(), stride, lens.as_mut_ptr(),
                                        status.as_mut_ptr(), err.as_mut_ptr(), err.len())
         };
-        if rc < 0 {
+        if rc < 0 && rc != ffi::BPP_ERR_SELF_CHECK {  // (an engine fault of the call; a self-check failure is an item's own outcome)
             map_rc(rc, unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned())?;
         }
         Ok((0..items.len()).map(|k| {
@@ -681,6 +697,12 @@ impl ProvePool {
     }
     pub fn set_limits(&self, max_calls: u32, max_proofs: u32) -> Result<(), GpuError> {
         map_rc(unsafe { ffi::bpp_prove_pool_set_limits(self.raw, max_calls, max_proofs) }, String::from("bpp_prove_pool_set_limits"))
+    }
+    /// the self-check counters of every lane, summed (`Engine::prove_check_stats`; the first lane is the engine the pool was made from)
+    pub fn check_stats(&self) -> Result<ffi::bpp_prove_check_stats, GpuError> {
+        let mut s = ffi::bpp_prove_check_stats::default();
+        map_rc(unsafe { ffi::bpp_prove_pool_check_stats(self.raw, &mut s) }, String::from("bpp_prove_pool_check_stats"))?;
+        Ok(s)
     }
     /// (callers served in pooled calls, engine calls, calls that ran alone, largest pool in calls, in proofs)
     pub fn stats(&self) -> (u64, u64, u64, u32, u32) {

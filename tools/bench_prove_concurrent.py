@@ -19,6 +19,7 @@ def main():
     ap.add_argument("--calls", type=int, default=8)
     ap.add_argument("--m", type=int, default=4)
     ap.add_argument("--t", type=int, default=3)
+    ap.add_argument("--check", action="store_true", help='"prove_check" = 1 on every context')
     args = ap.parse_args()
     import numpy as np
     bpp = importlib.import_module("bulletproofs-plus_amd")
@@ -29,6 +30,8 @@ def main():
     d = bench.make_inputs(np, packed, p0, 1024, seed=99)  # also builds the fixed-base table
     for S in [int(x) for x in args.threads.split(",")]:
         engs = [bpp.Engine(0) for _ in range(S)]
+        for e in engs if args.check else ():
+            e.set_option("prove_check", 1)
         ps = [p0.share(e) for e in engs]
 
         def worker(k):
@@ -50,7 +53,7 @@ def main():
         el = time.perf_counter() - t0
         print(json.dumps({"metric": "range proofs created/sec (batch), calls in flight", "contexts": S, "aggregation": args.m,
                           "extension_degree": args.t, "proofs_per_call": 1024, "proofs_per_s": 1024 * args.calls * S / el,
-                          "ms_per_call": 1e3 * el / args.calls}))
+                          "ms_per_call": 1e3 * el / args.calls, "prove_check": 1 if args.check else 0}))
         for p in ps:
             p.close()
         for e in engs:

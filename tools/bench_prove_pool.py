@@ -7,6 +7,8 @@ One JSON line per (setup, S, t): proofs/s and p50 / p99 call latency.
 
   --mixed-ab   instead: one mixed call of 512 x m1 + 256 x m2 + 256 x m4 against the same proofs as one bpp_prove_batch per
                class, one after the other (median of --reps calls each, t = 1 and 3)
+  --check      every context (the solo ones, the pool's lanes) verifies each proof before returning it ("prove_check" = 1); the
+               pooled lines add the lanes' check counters
   --soak SEC   instead: SEC seconds of 16 threads through the pool, about 5 % of the calls invalid (one item short of external
                randomness); every proof is compared with the bytes of a one-item bpp_prove_batch of the same item on the same GPU
                (not with the CPU oracle: the tests pin both paths to it), every error with that of a call of its own
@@ -86,6 +88,8 @@ def run_threads(S, fn):
 def bench_rates(bpp, packed, args):
     for t in args.t:
         eng0 = bpp.Engine(0)
+        if args.check:
+            eng0.set_option("prove_check", 1)  # (before the pools are made: their lanes copy it)
         p0 = bpp.RangeParameters.init(64, 4, bpp.create_pedersen_gens_with_extension_degree(t), engine=eng0)
         items = [marshal(bpp, [x]) for x in corpus(bpp, p0, 64, t, 48, t)]
         solo_call(eng0, p0, items[0])  # fixed-base table, arena
@@ -93,6 +97,8 @@ def bench_rates(bpp, packed, args):
             for setup in ("solo", "pooled"):
                 if setup == "solo":
                     engs = [bpp.Engine(0) for _ in range(S)]
+                    for e in engs if args.check else ():
+                        e.set_option("prove_check", 1)
                     ps = [p0.share(e) for e in engs]
                     for k in range(S):
                         solo_call(engs[k], ps[k], items[k % len(items)])
@@ -115,7 +121,7 @@ def bench_rates(bpp, packed, args):
                 el, lat = run_threads(S, fn)
                 rec = {"metric": "one-proof prove calls, m in {1,2,4}", "setup": setup, "threads": S, "calls_per_thread": args.calls,
                        "bit_length": 64, "extension_degree": t, "proofs_per_s": S * args.calls / el,
-                       "p50_ms": 1e3 * pct(lat, 0.5), "p99_ms": 1e3 * pct(lat, 0.99)}
+                       "p50_ms": 1e3 * pct(lat, 0.5), "p99_ms": 1e3 * pct(lat, 0.99), "prove_check": 1 if args.check else 0}
                 if setup == "solo":
                     for p in ps:
                         p.close()
@@ -123,6 +129,8 @@ def bench_rates(bpp, packed, args):
                         e.close()
                 else:
                     rec.update(pool.stats(), lanes=args.lanes, max_wait_us=args.max_wait_us)
+                    if args.check:
+                        rec["check"] = pool.check_stats()
                     pool.close()
                 print(json.dumps(rec), flush=True)
         p0.close()
@@ -238,6 +246,7 @@ def main():
     ap.add_argument("--mixed-ab", action="store_true")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--soak", type=float, default=0)
+    ap.add_argument("--check", action="store_true", help='"prove_check" = 1 on every context of the rate runs')
     args = ap.parse_args()
     args.threads = [int(x) for x in args.threads.split(",")]
     args.t = [int(x) for x in args.t.split(",")]

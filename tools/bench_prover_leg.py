@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """The prover leg of bench.py alone (configs[4]: 1024 x aggregation-4, extension degree 3): proofs/s one call at a time over 8
-calls, k_fb_msm's summed event time and rate per call.  One line."""
+calls, k_fb_msm's summed event time and rate per call.  One line.
+
+  --check   every proof verified before it is returned (the context's "prove_check" = 1); the line adds the check's counters"""
+import argparse
 import importlib
 import json
 import os
@@ -13,12 +16,17 @@ sys.path.insert(0, ROOT)
 
 
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--check", action="store_true", help='"prove_check" = 1 on the context')
+    args = ap.parse_args()
     import numpy as np
     import bench
     bpp = importlib.import_module("bulletproofs-plus_amd")
     packed = importlib.import_module("bulletproofs-plus_amd.packed")
     eng = bpp.Engine(0)
     eng.profile(True)
+    if args.check:
+        eng.set_option("prove_check", 1)
     p5 = bpp.RangeParameters.init(64, 4, bpp.create_pedersen_gens_with_extension_degree(3), engine=eng)
     d5 = bench.make_inputs(np, packed, p5, 1024, seed=8675309 + 5)
     iters = int(os.environ.get("PROVER_ITERS", "8"))
@@ -29,8 +37,11 @@ def main():
         out = packed.prove(p5, d5["values"], d5["blindings"], d5["commitments"], d5["min_values"], d5["min_present"], None, bench.LABEL, d5["ext"])
     el = time.perf_counter() - t0
     pp = eng.last_prove_profile()
-    print(json.dumps({"proofs_per_s": round(1024 * iters / el), "ms_per_call": round(1e3 * el / iters, 3), "fb_msm_ms": round(pp["fb_msm_ms"], 3),
-                      "fb_G_adds_per_s": round(pp["fb_terms"] * pp["fb_windows"] / (pp["fb_msm_ms"] * 1e-3) / 1e9, 2), "engine_total_ms": round(pp["total_ms"], 3)}))
+    rec = {"proofs_per_s": round(1024 * iters / el), "ms_per_call": round(1e3 * el / iters, 3), "fb_msm_ms": round(pp["fb_msm_ms"], 3),
+           "fb_G_adds_per_s": round(pp["fb_terms"] * pp["fb_windows"] / (pp["fb_msm_ms"] * 1e-3) / 1e9, 2), "engine_total_ms": round(pp["total_ms"], 3)}
+    if args.check:
+        rec["check"] = eng.prove_check_stats()
+    print(json.dumps(rec))
     p5.close()
     eng.close()
 
