@@ -1759,6 +1759,13 @@ namespace {
 // ev_rng is recorded there; nothing comes to the host and the function does not wait
 void plan_lanes(bpp_ctx *ctx, Batch &b, bool for_phase2 = false);
 
+// ev_rng marks the transcript-RNG bytes of a context's PASS 1; made when a context first needs it
+void ensure_ev_rng(bpp_ctx *ctx) {
+  if (ctx->ev_rng_ready) return;
+  HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_rng, hipEventDisableTiming));
+  ctx->ev_rng_ready = true;
+}
+
 // Where a call's weight chains run (option "chain" / BPP_CHAIN: 0 host, 1 device, -1 this rule).  The host runs a chain five
 // to eight times faster than a wavefront does (chain_host.h: 0.27 us per proof, chain_dev.h: ~2), so a call that WAITS for its
 // chains -- one call at a time, few groups -- keeps them on the host.  The device form is for callers that keep several
@@ -1810,10 +1817,7 @@ void enqueue_phase1(bpp_ctx *ctx, Batch &b, StageTimer &tm, bool pass1_only, uin
   Params &P = *b.params;
   hipStream_t s = ctx->stream;
   if (!pass1_only) plan_lanes(ctx, b);  // (an option may have changed since the layout was built: k_scalars_shared writes what PASS 2 will read)
-  if (!ctx->ev_rng_ready) {
-    HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_rng, hipEventDisableTiming));
-    ctx->ev_rng_ready = true;
-  }
+  ensure_ev_rng(ctx);
   // status[] starts as status0[]: the previous verification's last kernel left it so (k_results_out), unless that call died
   // half way
   if (!b.status_clean) HIP_CHECK(hipMemcpyAsync(b.status.p, b.status0.p, (size_t)b.B * 4, hipMemcpyDeviceToDevice, s));
@@ -2404,10 +2408,7 @@ int bpp_batch_prepare(bpp_ctx *ctx, uint64_t batch, size_t chunk) {
     auto it = ctx->batches.find(batch);
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
     StageTimer tm(ctx);  // creates the profiling events when profiling is on
-    if (!ctx->ev_rng_ready) {
-      HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_rng, hipEventDisableTiming));
-      ctx->ev_rng_ready = true;
-    }
+    ensure_ev_rng(ctx);
     layout_groups(ctx, *it->second, chunk);  // group layout, MSM plan and every work buffer of that plan
     it->second->h_ident.resize(it->second->G);
     return BPP_OK;
@@ -2415,99 +2416,225 @@ int bpp_batch_prepare(bpp_ctx *ctx, uint64_t batch, size_t chunk) {
   BPP_CATCH(ctx, nullptr, 0)
 }
 
+}  // extern "C"
+
+namespace {
+
 // proofs of a resident batch (0: unknown handle), read under the context's lock: the gate is always taken BEFORE that lock
-static uint32_t batch_size_peek(bpp_ctx *ctx, uint64_t batch) {
+uint32_t batch_size_peek(bpp_ctx *ctx, uint64_t batch) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   auto it = ctx->batches.find(batch);
   return it == ctx->batches.end() ? 0u : it->second->B;
 }
 
+void shard_result_set(bpp_shard_result &r, int code, int tier, int rank, uint32_t index, const std::string &msg) {
+  r.code = code;
+  r.tier = tier;
+  r.rank = rank;
+  r.index = index;
+  snprintf(r.msg, sizeof(r.msg), "%s", msg.c_str());
+}
+
+// What one verification of a resident batch leaves behind: per group of its layout the finding of the reference's verify() on
+// that group alone (tier NONE: it returned Ok; `index` counts inside the group, `rank` is not used), and the recovered masks
+// in b.h_masks where some group asked for them.
+struct ResidentRun {
+  Batch &b;
+  std::vector<ShardFinding> found;
+  bool have_masks = false;
+  explicit ResidentRun(Batch &batch) : b(batch) {}
+  // recovered masks on their way to the caller (page-locked, written by k_results_out): wiped on every exit (src/extended_mask.rs:14)
+  void wipe_masks() {
+    if (have_masks) wipe(b.h_masks.data(), std::min(b.h_masks.n, (size_t)b.B * b.params->t * 32));
+    have_masks = false;
+  }
+  ~ResidentRun() { wipe_masks(); }
+};
+
 // (the context's lock is held.)  BPP_REDRAW_ON_HOST: the device chain drew a zero weight (probability 2^-252 per proof): the
 // caller runs the call again with the chains on the host, which redraw as the reference does (scalar_protocol.rs:23-30)
 #define BPP_REDRAW_ON_HOST (-0x7fff0001)
-static int verify_resident_locked(bpp_ctx *ctx, uint64_t batch, int action, size_t chunk, uint8_t *masks_out, uint8_t *mask_present,
-                                  char *errbuf, size_t errbuf_len, bool allow_dev_chain) {
+// One pass over a resident batch: the group layout (equal chunks, or explicit `bounds`: layout_groups), group g under
+// actions[g] (actions == nullptr: `action_all` for every group), every group verified as its own verify() call by the same
+// kernel launches.  A RecoverOnly group never looks at the final check (:1040-1043); when EVERY group is RecoverOnly the weight
+// chains and PASS 2 are not run at all.  Engine faults throw.
+int verify_flow_once(bpp_ctx *ctx, ResidentRun &run, size_t chunk, const std::vector<uint32_t> *bounds, const int *actions, int action_all,
+                     bool allow_dev_chain) {
+  Batch &b = run.b;
+  Params &P = *b.params;
+  auto t_begin = std::chrono::steady_clock::now();
+  StageTimer tm(ctx);
+  hipStream_t s = ctx->stream;
+  layout_groups(ctx, b, chunk, bounds);
+  auto action_of = [&](uint32_t g) { return actions ? actions[g] : action_all; };
+  run.found.assign(b.G, ShardFinding{});
+  auto find = [&](uint32_t g, auto &&checks) {
+    try {
+      checks();
+    } catch (const ProofErr &e) {
+      ShardFinding &f = run.found[g];
+      f.code = e.code;
+      f.tier = e.tier;
+      f.index = e.index - b.h_group_first[g];  // position inside the group's own batch
+      f.msg = e.msg;
+    }
+  };
+  // verify()'s own consistency loops (:637-682) come before anything else of the call: with one group nothing needs to run
+  if (b.any_defer && b.G == 1) {
+    find(0, [&] { check_deferred(b.defer, 0, b.B); });
+    if (run.found[0].tier != BPP_TIER_NONE) return BPP_OK;
+  }
+  bool any_msm = false, any_masks = false;
+  for (uint32_t g = 0; g < b.G; g++) {
+    any_msm = any_msm || action_of(g) != BPP_RECOVER_ONLY;
+    any_masks = any_masks || action_of(g) != BPP_VERIFY_ONLY;
+  }
+  // a proof whose L/R count does not fit its statement makes the call fail (src/range_proof.rs:875-888).  With a
+  // single group only the precedence against PASS-1 / decompression errors is still open, so PASS 2 is skipped;
+  // with several groups the earlier groups' MSM verdicts still matter (the kernels tolerate the odd shapes and run on every
+  // item; findings are raised per group afterwards, in the reference's order).
+  const bool pass1_only = b.any_rounds_bad && b.G == 1;
+  const bool want_msm = !pass1_only && any_msm;
+  const bool want_masks = !pass1_only && any_masks && b.any_seed;
+  const ChainMode cmode = want_msm ? chain_mode(ctx, b, allow_dev_chain) : CHAIN_HOST;
+  enqueue_phase1(ctx, b, tm, !want_msm, nullptr, 0, 0, cmode == CHAIN_DEVICE);
+
+  b.h_ident.resize(b.G);
+  for (uint32_t g = 0; g < b.G; g++) b.h_ident[g] = 1;
+  float chain_ms = 0;
+  if (want_msm && cmode != CHAIN_DEVICE) {
+    // weight chains: one per chunk (src/range_proof.rs:811,849,853,894); the device keeps working meanwhile
+    auto c0 = std::chrono::steady_clock::now();
+    if (cmode == CHAIN_HOST_WIDE) run_weight_chains_wide(b);
+    else run_weight_chains(b);
+    chain_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - c0).count();
+  }
+  if (want_masks) {  // masks (:941-969)
+    tm.mark(M_MASKS0);
+    hipLaunchKernelGGL(k_masks, dim3(cdiv(b.B, 64)), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.chal.p, b.seeds.p,
+                       P.n_bits, P.t, b.cs, b.B, b.masks.p);
+    tm.mark(M_MASKS);
+    b.masks_dirty = true;
+    run.have_masks = true;
+  }
+  if (want_msm) {
+    enqueue_phase2(ctx, b, tm, cmode != CHAIN_HOST, cmode == CHAIN_HOST_WIDE);
+    b.have_trace = true;
+  }
+  fetch_results(ctx, b, want_msm, want_masks);
+  // (the remembered wait belongs to the batch's size and group count and to what actually ran: equal work shares it)
+  gpu_wait_stream(ctx, s, wait_naps(ctx, b.B), &ctx->wait_hint_end,
+                  ((uint64_t)b.B << 32) | ((uint64_t)b.G << 2) | (uint64_t)((want_msm ? 1 : 0) | (want_masks ? 2 : 0)));
+  if (want_msm && cmode != CHAIN_HOST && ctx->h_chain_zero[0]) {
+    ctx->device_chain_redraws++;
+    return BPP_REDRAW_ON_HOST;
+  }
+  collect_profile(ctx, b, tm, chain_ms, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+
+  // errors surface chunk by chunk, in the reference's order; a chunk's MSM verdict precedes later chunks' errors
+  for (uint32_t g = 0; g < b.G; g++) {
+    const uint32_t p0 = b.h_group_first[g], p1 = b.h_group_first[g + 1];
+    find(g, [&] {
+      if (b.any_defer) check_deferred(b.defer, p0, p1);  // :637-682
+      check_chunk_errors(b, p0, p1);
+      if (want_msm && action_of(g) != BPP_RECOVER_ONLY && !b.h_ident[g])
+        throw ProofErr{BPP_ERR_VERIFICATION_FAILED, "Range proof batch not valid", BPP_TIER_MSM, p0};
+    });
+  }
+  return BPP_OK;
+}
+
+// first with the device's share of the weight chains, and on a zero weight once more without
+void verify_flow(bpp_ctx *ctx, ResidentRun &run, size_t chunk, const std::vector<uint32_t> *bounds, const int *actions, int action_all) {
+  if (verify_flow_once(ctx, run, chunk, bounds, actions, action_all, true) != BPP_REDRAW_ON_HOST) return;
+  run.wipe_masks();
+  (void)verify_flow_once(ctx, run, chunk, bounds, actions, action_all, false);
+}
+
+// outputs: Vec<Option<ExtendedMask>> for the proofs [p0, p1): with `give`, the masks of the items that carry a seed nonce; every
+// other item's slot is zero / absent
+void give_masks(const ResidentRun &run, uint32_t p0, uint32_t p1, bool give, uint8_t *masks_out, uint8_t *mask_present) {
+  const Batch &b = run.b;
+  const size_t row = (size_t)b.params->t * 32;
+  for (uint32_t p = p0; p < p1; p++) {
+    const bool present = give && (b.desc[p].flags & 1u);
+    if (mask_present) mask_present[p] = present ? 1 : 0;
+    if (masks_out) {
+      if (present) memcpy(masks_out + p * row, b.h_masks.data() + p * row, row);
+      else memset(masks_out + p * row, 0, row);
+    }
+  }
+}
+
+// (the context's lock is held.)  The chunked form: equal chunks under one action; the first chunk with a finding ends the call
+// with that finding, and masks are handed out only when no chunk had one.
+int verify_chunked_locked(bpp_ctx *ctx, uint64_t batch, int action, size_t chunk, uint8_t *masks_out, uint8_t *mask_present, char *errbuf,
+                          size_t errbuf_len) {
   try {
     auto it = ctx->batches.find(batch);
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle", errbuf, errbuf_len);
     if (action < 0 || action > 2) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "unknown verify action", errbuf, errbuf_len);
-    Batch &b = *it->second;
-    Params &P = *b.params;
-    auto t_begin = std::chrono::steady_clock::now();
-    StageTimer tm(ctx);
-    hipStream_t s = ctx->stream;
-    layout_groups(ctx, b, chunk);
-    // verify()'s own consistency loops (:637-682) come before anything else of the call: with one group nothing needs to run
-    if (b.any_defer && b.G == 1) check_deferred(b.defer, 0, b.B);
-    // a proof whose L/R count does not fit its statement makes the call fail (src/range_proof.rs:875-888).  With a
-    // single group only the precedence against PASS-1 / decompression errors is still open, so PASS 2 is skipped;
-    // with several groups the earlier groups' MSM verdicts still matter (the kernels tolerate the odd shapes).
-    const bool pass1_only = b.any_rounds_bad && b.G == 1;
-    const bool want_msm = !pass1_only && action != BPP_RECOVER_ONLY;
-    const ChainMode cmode = want_msm ? chain_mode(ctx, b, allow_dev_chain) : CHAIN_HOST;
-    const bool dev_chain = cmode == CHAIN_DEVICE;
-    enqueue_phase1(ctx, b, tm, pass1_only || action == BPP_RECOVER_ONLY, nullptr, 0, 0, dev_chain);
-
-    float chain_ms = 0;
-    // recovered masks on their way to the caller (page-locked, written by k_results_out): wiped on every exit (src/extended_mask.rs:14)
-    bool have_masks = false;
-    ScopeExit wipe_masks{[&] {
-      if (have_masks) wipe(b.h_masks.data(), std::min(b.h_masks.n, (size_t)b.B * P.t * 32));
-    }};
-    b.h_ident.resize(b.G);
-    for (uint32_t g = 0; g < b.G; g++) b.h_ident[g] = 1;
-    auto &h_ident = b.h_ident;
-    const uint8_t *h_masks = nullptr;
-    if (!pass1_only) {
-      // weight chains: one per chunk (src/range_proof.rs:811,849,853,894); the device keeps working meanwhile
-      auto c0 = std::chrono::steady_clock::now();
-      if (want_msm && cmode == CHAIN_HOST) run_weight_chains(b);
-      if (want_msm && cmode == CHAIN_HOST_WIDE) run_weight_chains_wide(b);
-      chain_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - c0).count();
-      if (action != BPP_VERIFY_ONLY && b.any_seed) {  // masks (:941-969)
-        tm.mark(M_MASKS0);
-        hipLaunchKernelGGL(k_masks, dim3(cdiv(b.B, 64)), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.chal.p, b.seeds.p,
-                           P.n_bits, P.t, b.cs, b.B, b.masks.p);
-        tm.mark(M_MASKS);
-        b.masks_dirty = true;
-        have_masks = true;
-      }
-      if (want_msm) {
-        enqueue_phase2(ctx, b, tm, cmode != CHAIN_HOST, cmode == CHAIN_HOST_WIDE);
-        b.have_trace = true;
-      }
-    }
-    fetch_results(ctx, b, want_msm, have_masks);
-    gpu_wait_stream(ctx, s, wait_naps(ctx, b.B), &ctx->wait_hint_end, ((uint64_t)b.B << 32) | ((uint64_t)b.G << 2) | (uint64_t)action);
-    if (want_msm && cmode != CHAIN_HOST && ctx->h_chain_zero[0]) {
-      ctx->device_chain_redraws++;
-      return BPP_REDRAW_ON_HOST;
-    }
-    if (have_masks) h_masks = b.h_masks.data();
-    auto t_end = std::chrono::steady_clock::now();
-    collect_profile(ctx, b, tm, chain_ms, std::chrono::duration<float, std::milli>(t_end - t_begin).count());
-
-    // errors surface chunk by chunk, in the reference's order; a chunk's MSM verdict precedes later chunks' errors
-    for (uint32_t g = 0; g < b.G; g++) {
-      if (b.any_defer) check_deferred(b.defer, b.h_group_first[g], b.h_group_first[g + 1]);  // :637-682
-      check_chunk_errors(b, b.h_group_first[g], b.h_group_first[g + 1]);
-      if (want_msm && !h_ident[g]) throw ProofErr{BPP_ERR_VERIFICATION_FAILED, "Range proof batch not valid", BPP_TIER_MSM, b.h_group_first[g]};
-    }
-    // outputs: Vec<Option<ExtendedMask>>
-    for (uint32_t p = 0; p < b.B; p++) {
-      bool present = (action != BPP_VERIFY_ONLY) && (b.desc[p].flags & 1u);
-      if (mask_present) mask_present[p] = present ? 1 : 0;
-      if (masks_out) {
-        if (present)
-          memcpy(masks_out + (size_t)p * P.t * 32, &h_masks[(size_t)p * P.t * 32], (size_t)P.t * 32);
-        else
-          memset(masks_out + (size_t)p * P.t * 32, 0, (size_t)P.t * 32);
-      }
-    }
+    ResidentRun run(*it->second);
+    verify_flow(ctx, run, chunk, nullptr, nullptr, action);
+    for (const ShardFinding &f : run.found)
+      if (f.tier != BPP_TIER_NONE) return fail(ctx, f.code, f.msg, errbuf, errbuf_len);
+    give_masks(run, 0, run.b.B, action != BPP_VERIFY_ONLY, masks_out, mask_present);
     return BPP_OK;
   }
   BPP_CATCH(ctx, errbuf, errbuf_len)
 }
+
+// (the context's lock is held.)  Reference batches of DIFFERENT sizes in one call: group g = proofs [group_first[g],
+// group_first[g + 1]) of the resident batch, every group with its own outcome and its own VerifyAction
+// (src/range_proof.rs:46-54) -- where the chunked form cuts equal chunks and stops at the first failing one.
+// What a pool of small calls needs (bpp_batcher below).  actions == nullptr: VerifyOnly for every group.
+// Masks (:941-969): a group whose action recovers them and whose verify() would have returned Ok gets the masks of its items
+// that carry a seed nonce (an Err returns no masks).
+int verify_groups_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first, size_t n_groups, const int *actions,
+                         bpp_shard_result *results, uint8_t *masks_out, uint8_t *mask_present) {
+  try {
+    auto it = ctx->batches.find(batch);
+    if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
+    if (!group_first || !results || n_groups == 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+    Batch &b = *it->second;
+    std::vector<uint32_t> bounds(group_first, group_first + n_groups + 1);
+    if (bounds.front() != 0 || bounds.back() != b.B) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "group boundaries must run from 0 to the batch size");
+    for (size_t g = 0; g < n_groups; g++)
+      if (bounds[g] >= bounds[g + 1]) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "empty or unordered group");
+    for (size_t g = 0; actions && g < n_groups; g++)
+      if (actions[g] < 0 || actions[g] > 2) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "unknown verify action");
+    ResidentRun run(b);
+    verify_flow(ctx, run, 0, &bounds, actions, BPP_VERIFY_ONLY);
+    for (uint32_t g = 0; g < b.G; g++) {
+      const ShardFinding &f = run.found[g];
+      memset(&results[g], 0, sizeof(results[g]));
+      shard_result_set(results[g], f.code, f.tier, -1, f.index, f.msg);
+      const bool give = (actions ? actions[g] : BPP_VERIFY_ONLY) != BPP_VERIFY_ONLY && f.tier == BPP_TIER_NONE;
+      give_masks(run, bounds[g], bounds[g + 1], give, masks_out, mask_present);
+    }
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, nullptr, 0)
+}
+
+// The host-buffers-in forms: `upload` makes the batch resident, then bpp_verify_resident and the release.  The small-call gate
+// is held across all three and taken here, BEFORE any of them takes the context's lock.
+template <class Upload>
+int verify_uploaded(bpp_ctx *ctx, size_t n_items, Upload upload, int action, size_t chunk, uint8_t *masks_out, uint8_t *mask_present,
+                    char *errbuf, size_t errbuf_len) {
+  if (!ctx) return BPP_ERR_BAD_HANDLE;
+  GateHold gate(ctx->device, n_items <= BPP_GATE_SMALL_PROOFS);  // held across upload and verification of a small call
+  uint64_t h = 0;
+  int rc = upload(&h);
+  if (rc != BPP_OK) return rc;
+  rc = bpp_verify_resident(ctx, h, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
+  (void)bpp_batch_destroy(ctx, h);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" {
 
 int bpp_verify_resident(bpp_ctx *ctx, uint64_t batch, int action, size_t chunk, uint8_t *masks_out, uint8_t *mask_present,
                         char *errbuf, size_t errbuf_len) {
@@ -2515,115 +2642,8 @@ int bpp_verify_resident(bpp_ctx *ctx, uint64_t batch, int action, size_t chunk, 
   const uint32_t n_peek = batch_size_peek(ctx, batch);
   GateHold gate(ctx->device, n_peek && n_peek <= BPP_GATE_SMALL_PROOFS);  // small calls queue for the device (DeviceState)
   BPP_ENTRY(ctx);
-  int rc = verify_resident_locked(ctx, batch, action, chunk, masks_out, mask_present, errbuf, errbuf_len, true);
-  if (rc == BPP_REDRAW_ON_HOST) rc = verify_resident_locked(ctx, batch, action, chunk, masks_out, mask_present, errbuf, errbuf_len, false);
-  return rc;
+  return verify_chunked_locked(ctx, batch, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
 }
-
-// Reference batches of DIFFERENT sizes in one call: group g = proofs [group_first[g], group_first[g + 1]) of the resident
-// batch, every group verified as its own verify() call by the same kernel launches, with its own outcome and its own
-// VerifyAction (src/range_proof.rs:46-54) -- where bpp_verify_resident cuts equal chunks and stops at the first failing one.
-// What a pool of small calls needs (bpp_batcher below).  actions == nullptr: VerifyOnly for every group.
-// Masks (:941-969): a group whose action recovers them and whose verify() would have returned Ok gets the masks of its items
-// that carry a seed nonce; every other item's slot is zero / absent (an Err returns no masks).  A RecoverOnly group never
-// looks at the final check (:1040-1043); when EVERY group is RecoverOnly the weight chains and PASS 2 are not run at all.
-}  // extern "C"
-namespace {
-int verify_groups_core_once(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first, size_t n_groups, const int *actions,
-                            bpp_shard_result *results, uint8_t *masks_out, uint8_t *mask_present, bool allow_dev_chain) {
-  try {
-    auto it = ctx->batches.find(batch);
-    if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
-    if (!group_first || !results || n_groups == 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
-    Batch &b = *it->second;
-    Params &P = *b.params;
-    std::vector<uint32_t> bounds(group_first, group_first + n_groups + 1);
-    if (bounds.front() != 0 || bounds.back() != b.B) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "group boundaries must run from 0 to the batch size");
-    for (size_t g = 0; g < n_groups; g++)
-      if (bounds[g] >= bounds[g + 1]) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "empty or unordered group");
-    bool want_msm = false, want_masks = false;
-    for (size_t g = 0; g < n_groups; g++) {
-      const int a = actions ? actions[g] : BPP_VERIFY_ONLY;
-      if (a < 0 || a > 2) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "unknown verify action");
-      want_msm = want_msm || a != BPP_RECOVER_ONLY;
-      want_masks = want_masks || a != BPP_VERIFY_ONLY;
-    }
-    want_masks = want_masks && b.any_seed;
-    auto t_begin = std::chrono::steady_clock::now();
-    StageTimer tm(ctx);
-    hipStream_t s = ctx->stream;
-    layout_groups(ctx, b, 0, &bounds);
-    // the kernels tolerate odd shapes and run on every item (as bpp_verify_resident does with several chunks); findings are
-    // raised per group afterwards, in the reference's order
-    const ChainMode cmode = want_msm ? chain_mode(ctx, b, allow_dev_chain) : CHAIN_HOST;
-    const bool dev_chain = cmode == CHAIN_DEVICE;
-    enqueue_phase1(ctx, b, tm, !want_msm, nullptr, 0, 0, dev_chain);
-    b.h_ident.resize(b.G);
-    for (uint32_t g = 0; g < b.G; g++) b.h_ident[g] = 1;
-    ScopeExit wipe_masks{[&] {
-      if (want_masks) wipe(b.h_masks.data(), std::min(b.h_masks.n, (size_t)b.B * P.t * 32));
-    }};
-    float chain_ms = 0;
-    if (want_msm && !dev_chain) {
-      auto c0 = std::chrono::steady_clock::now();
-      if (cmode == CHAIN_HOST_WIDE) run_weight_chains_wide(b);
-      else run_weight_chains(b);
-      chain_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - c0).count();
-    }
-    if (want_masks) {
-      hipLaunchKernelGGL(k_masks, dim3(cdiv(b.B, 64)), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.chal.p, b.seeds.p, P.n_bits, P.t, b.cs, b.B,
-                         b.masks.p);
-      b.masks_dirty = true;
-    }
-    if (want_msm) {
-      enqueue_phase2(ctx, b, tm, cmode != CHAIN_HOST, cmode == CHAIN_HOST_WIDE);
-      b.have_trace = true;
-    }
-    fetch_results(ctx, b, want_msm, want_masks);
-    gpu_wait_stream(ctx, s, wait_naps(ctx, b.B), &ctx->wait_hint_end, ((uint64_t)b.B << 32) | ((uint64_t)b.G << 2) | (uint64_t)((want_msm ? 1 : 0) | (want_masks ? 2 : 0)));
-    if (want_msm && cmode != CHAIN_HOST && ctx->h_chain_zero[0]) {
-      ctx->device_chain_redraws++;
-      return BPP_REDRAW_ON_HOST;
-    }
-    collect_profile(ctx, b, tm, chain_ms, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
-    for (uint32_t g = 0; g < b.G; g++) {
-      bpp_shard_result &r = results[g];
-      memset(&r, 0, sizeof(r));
-      r.rank = -1;
-      const int a = actions ? actions[g] : BPP_VERIFY_ONLY;
-      const uint32_t p0 = b.h_group_first[g], p1 = b.h_group_first[g + 1];
-      try {
-        if (b.any_defer) check_deferred(b.defer, p0, p1);
-        check_chunk_errors(b, p0, p1);
-        if (a != BPP_RECOVER_ONLY && !b.h_ident[g]) throw ProofErr{BPP_ERR_VERIFICATION_FAILED, "Range proof batch not valid", BPP_TIER_MSM, p0};
-      } catch (const ProofErr &e) {
-        r.code = e.code;
-        r.tier = e.tier;
-        r.index = e.index - p0;  // position inside the group's own batch
-        snprintf(r.msg, sizeof(r.msg), "%s", e.msg.c_str());
-      }
-      const bool give = a != BPP_VERIFY_ONLY && r.code == BPP_OK;
-      for (uint32_t p = p0; p < p1; p++) {
-        const bool present = give && (b.desc[p].flags & 1u);
-        if (mask_present) mask_present[p] = present ? 1 : 0;
-        if (masks_out) {
-          if (present) memcpy(masks_out + (size_t)p * P.t * 32, b.h_masks.data() + (size_t)p * P.t * 32, (size_t)P.t * 32);
-          else memset(masks_out + (size_t)p * P.t * 32, 0, (size_t)P.t * 32);
-        }
-      }
-    }
-    return BPP_OK;
-  }
-  BPP_CATCH(ctx, nullptr, 0)
-}
-int verify_groups_core(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first, size_t n_groups, const int *actions,
-                       bpp_shard_result *results, uint8_t *masks_out, uint8_t *mask_present) {
-  int rc = verify_groups_core_once(ctx, batch, group_first, n_groups, actions, results, masks_out, mask_present, true);
-  if (rc == BPP_REDRAW_ON_HOST) rc = verify_groups_core_once(ctx, batch, group_first, n_groups, actions, results, masks_out, mask_present, false);
-  return rc;
-}
-}  // namespace
-extern "C" {
 
 int bpp_verify_resident_groups_actions(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first, size_t n_groups, const int *actions,
                                        bpp_shard_result *results, uint8_t *masks_out, uint8_t *mask_present) {
@@ -2631,7 +2651,7 @@ int bpp_verify_resident_groups_actions(bpp_ctx *ctx, uint64_t batch, const uint3
   const uint32_t n_peek = batch_size_peek(ctx, batch);
   GateHold gate(ctx->device, n_peek && n_peek <= BPP_GATE_SMALL_PROOFS);  // small calls queue for the device (DeviceState)
   BPP_ENTRY(ctx);
-  return verify_groups_core(ctx, batch, group_first, n_groups, actions, results, masks_out, mask_present);
+  return verify_groups_locked(ctx, batch, group_first, n_groups, actions, results, masks_out, mask_present);
 }
 
 int bpp_verify_resident_groups(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first, size_t n_groups, bpp_shard_result *results) {
@@ -2641,43 +2661,24 @@ int bpp_verify_resident_groups(bpp_ctx *ctx, uint64_t batch, const uint32_t *gro
 int bpp_verify_batch_with_challenges(bpp_ctx *ctx, uint64_t params, const bpp_verify_item *items, size_t n_items,
                                      const uint8_t *const *challenges32, const uint8_t *rng_out32, int action, size_t chunk,
                                      uint8_t *masks_out, uint8_t *mask_present, char *errbuf, size_t errbuf_len) {
-  if (!ctx) return BPP_ERR_BAD_HANDLE;
-  GateHold gate(ctx->device, n_items <= BPP_GATE_SMALL_PROOFS);  // held across upload and verification of a small call
-  uint64_t h = 0;
-  int rc;
-  {
+  auto upload = [&](uint64_t *h) -> int {
     BPP_ENTRY(ctx);
     if (!challenges32 || !rng_out32) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
-    rc = upload_impl(ctx, params, items, n_items, nullptr, &h, challenges32, rng_out32, errbuf, errbuf_len);
-  }
-  if (rc != BPP_OK) return rc;
-  rc = bpp_verify_resident(ctx, h, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
-  (void)bpp_batch_destroy(ctx, h);
-  return rc;
+    return upload_impl(ctx, params, items, n_items, nullptr, h, challenges32, rng_out32, errbuf, errbuf_len);
+  };
+  return verify_uploaded(ctx, n_items, upload, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
 }
 
 int bpp_verify_batch(bpp_ctx *ctx, uint64_t params, const bpp_verify_item *items, size_t n_items, int action,
                      size_t chunk, uint8_t *masks_out, uint8_t *mask_present, char *errbuf, size_t errbuf_len) {
-  if (!ctx) return BPP_ERR_BAD_HANDLE;
-  GateHold gate(ctx->device, n_items <= BPP_GATE_SMALL_PROOFS);
-  uint64_t h = 0;
-  int rc = bpp_batch_upload(ctx, params, items, n_items, &h, errbuf, errbuf_len);
-  if (rc != BPP_OK) return rc;
-  rc = bpp_verify_resident(ctx, h, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
-  (void)bpp_batch_destroy(ctx, h);
-  return rc;
+  auto upload = [&](uint64_t *h) -> int { return bpp_batch_upload(ctx, params, items, n_items, h, errbuf, errbuf_len); };
+  return verify_uploaded(ctx, n_items, upload, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
 }
 
 int bpp_verify_batch_packed(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, int action, size_t chunk,
                             uint8_t *masks_out, uint8_t *mask_present, char *errbuf, size_t errbuf_len) {
-  if (!ctx) return BPP_ERR_BAD_HANDLE;
-  GateHold gate(ctx->device, in && in->n_items <= BPP_GATE_SMALL_PROOFS);
-  uint64_t h = 0;
-  int rc = bpp_batch_upload_packed(ctx, params, in, &h, errbuf, errbuf_len);
-  if (rc != BPP_OK) return rc;
-  rc = bpp_verify_resident(ctx, h, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
-  (void)bpp_batch_destroy(ctx, h);
-  return rc;
+  auto upload = [&](uint64_t *h) -> int { return bpp_batch_upload_packed(ctx, params, in, h, errbuf, errbuf_len); };
+  return verify_uploaded(ctx, in ? in->n_items : SIZE_MAX, upload, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
 }
 
 }  // extern "C"

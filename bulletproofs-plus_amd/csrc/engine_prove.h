@@ -621,7 +621,7 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
 
 // ================================================================= self-check ("prove_check" = 1)
 // The proofs a prove call made are verified on the same context before any byte of them leaves the engine: the verifier's own
-// upload (upload_host.h) and resident path (verify_resident_locked), no parser or kernel of its own.  Only public inputs are
+// upload (upload_host.h) and resident path (verify_chunked_locked / verify_groups_locked), no parser or kernel of its own.  Only public inputs are
 // looked at -- the proof bytes and the item's statement and transcript -- and nothing is written but status words.
 //
 // Locks: the context's lock is held (the prove call's).  The check does NOT pass the device's small-call gate (GateHold): the gate
@@ -665,15 +665,14 @@ int check_verify(bpp_ctx *ctx, uint64_t params, const std::vector<bpp_verify_ite
   if (rc < 0) throw ProofErr{rc, err, BPP_TIER_ENGINE};
   if (rc != BPP_OK) return rc;
   if (!single) {
-    rc = verify_resident_locked(ctx, h, BPP_VERIFY_ONLY, 0, nullptr, nullptr, err, sizeof(err), true);
-    if (rc == BPP_REDRAW_ON_HOST) rc = verify_resident_locked(ctx, h, BPP_VERIFY_ONLY, 0, nullptr, nullptr, err, sizeof(err), false);
+    rc = verify_chunked_locked(ctx, h, BPP_VERIFY_ONLY, 0, nullptr, nullptr, err, sizeof(err));
     if (rc < 0) throw ProofErr{rc, err, BPP_TIER_ENGINE};
     return rc;
   }
   std::vector<uint32_t> first(vi.size() + 1);
   for (size_t k = 0; k <= vi.size(); k++) first[k] = (uint32_t)k;
   std::vector<bpp_shard_result> res(vi.size());
-  rc = verify_groups_core(ctx, h, first.data(), vi.size(), nullptr, res.data(), nullptr, nullptr);
+  rc = verify_groups_locked(ctx, h, first.data(), vi.size(), nullptr, res.data(), nullptr, nullptr);
   if (rc != BPP_OK) throw ProofErr{rc < 0 ? rc : BPP_ERR_ENGINE, ctx->err, BPP_TIER_ENGINE};
   for (size_t k = 0; k < vi.size(); k++) (*codes)[k] = res[k].code;
   return BPP_OK;

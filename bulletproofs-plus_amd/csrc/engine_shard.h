@@ -158,19 +158,28 @@ struct bpp_comm {
   hipStream_t stream = nullptr;  // collectives and their staging copies
   hipEvent_t ev_wait = nullptr;  // comm_wait's marker (an EVENT is polled, not the stream: a stream query on a busy stream leaves a
                                  // helper thread of the runtime spinning, tools/microbench/wait_modes.hip)
-  DevBuf<uint8_t> send1, recv1, send2, recv2;
-  struct GroupSlot {  // exchange buffers of one batch of bpp_verify_sharded_groups_wave's pipeline
+  // exchange buffers of one batch of bpp_verify_sharded_groups_wave's pipeline; bpp_verify_sharded_wave, which exchanges once for
+  // all of its batches, uses slot 0
+  struct GroupSlot {
     DevBuf<uint8_t> send1, recv1, send2, recv2, send3, recv3;
     DevBuf<uint32_t> d_flags;
     PinnedBuf<uint8_t> h_tr, h_recv1, h_recv2;
     PinnedBuf<uint32_t> h_flags;
     std::vector<uint8_t> rng_all, weights_all;
+    // first exchange: per1 bytes per rank; second: per2 bytes per rank = n accumulators + n findings (trailers)
+    void reserve(size_t per1, size_t per2, uint32_t n, uint32_t world) {
+      send1.alloc(per1);
+      recv1.alloc(per1 * world);
+      send2.alloc(per2);
+      recv2.alloc(per2 * world);
+      d_flags.alloc(n);
+      h_tr.resize((size_t)n * BPP_SHARD_TRAILER_BYTES);
+      h_recv1.resize(per1 * world);
+      h_recv2.resize(per2 * world);
+      h_flags.resize(n);
+    }
   };
   std::vector<std::unique_ptr<GroupSlot>> slots;
-  DevBuf<uint32_t> d_flags;
-  PinnedBuf<uint8_t> h_tr, h_recv1, h_recv2;
-  PinnedBuf<uint32_t> h_flags;
-  std::vector<uint8_t> rng_all, weights_all;
   std::mutex mu;
   std::string err;
   bpp_shard_timing timing{};  // host wall-clock split of the last wave
@@ -316,13 +325,89 @@ void comm_allgather(bpp_comm *c, const uint8_t *send, uint8_t *recv, size_t byte
 std::mutex g_local_groups_mu;
 std::map<uint64_t, std::weak_ptr<LocalGroup>> g_local_groups;
 
-void shard_result_set(bpp_shard_result &r, int code, int tier, int rank, uint32_t index, const std::string &msg) {
-  r.code = code;
-  r.tier = tier;
-  r.rank = rank;
-  r.index = index;
-  snprintf(r.msg, sizeof(r.msg), "%s", msg.c_str());
+bpp_comm::GroupSlot &comm_slot(bpp_comm *c, uint32_t i) {
+  while (c->slots.size() <= i) c->slots.emplace_back(new bpp_comm::GroupSlot());
+  return *c->slots[i];
 }
+
+// ---- what bpp_verify_sharded_wave and bpp_verify_sharded_groups_wave share (their collectives they do not)
+// The locks of a sharded call and where this rank's shard lies in the reference batch
+struct ShardCall {
+  std::unique_lock<std::mutex> comm_lock;
+  std::vector<std::unique_lock<std::mutex>> ctx_locks;
+  uint32_t world = 1, rank = 0, maxc = 0, first_index = 0;
+  uint64_t n_total = 0;
+};
+int shard_call_begin(bpp_comm *comm, bpp_ctx *const *ctxs, uint32_t K, const uint32_t *counts, ShardCall &call) {
+  if (hipSetDevice(comm->device) != hipSuccess) return BPP_ERR_NO_DEVICE;
+  call.world = (uint32_t)comm->world;
+  call.rank = (uint32_t)comm->rank;
+  call.comm_lock = std::unique_lock<std::mutex>(comm->mu);
+  if (comm->dead) return comm_fail(comm, BPP_ERR_COMM, "this communicator was aborted after a collective timed out: destroy it");
+  for (uint32_t i = 0; i < K; i++) {
+    if (!ctxs[i] || ctxs[i]->device != comm->device) return comm_fail(comm, BPP_ERR_BAD_HANDLE, "context of another device (or null)");
+    for (uint32_t j = 0; j < i; j++)
+      if (ctxs[j] == ctxs[i]) return comm_fail(comm, BPP_ERR_INVALID_ARGUMENT, "every batch of a wave needs its own context (stream)");
+    call.ctx_locks.emplace_back(ctxs[i]->mu);
+  }
+  for (uint32_t r = 0; r < call.world; r++) {
+    call.maxc = std::max(call.maxc, counts[r]);
+    if (r < call.rank) call.first_index += counts[r];
+    call.n_total += counts[r];
+  }
+  if (call.n_total == 0 || call.n_total > (1u << 24)) return comm_fail(comm, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty");
+  return BPP_OK;
+}
+
+// host wall-clock split of a sharded call (bpp_comm_last_timing): lap(field) adds the time since the previous lap
+struct LapTimer {
+  bpp_shard_timing &tmg;
+  std::chrono::steady_clock::time_point t_mark = std::chrono::steady_clock::now();
+  LapTimer(bpp_comm *comm, uint32_t batches) : tmg(comm->timing) {
+    memset(&tmg, 0, sizeof(tmg));
+    tmg.batches = batches;
+  }
+  void lap(float &slot_ms) {
+    const auto now = std::chrono::steady_clock::now();
+    slot_ms += std::chrono::duration<float, std::milli>(now - t_mark).count();
+    t_mark = now;
+  }
+};
+
+// chain input of ONE reference batch: every rank's row of a gathered first exchange (rank r's block at h_recv1 + r * per1, the
+// batch's row `row_off` bytes into it, counts[r] proofs long), in rank order
+void shard_gather_rng(const uint8_t *h_recv1, size_t per1, size_t row_off, const uint32_t *counts, uint32_t world, uint8_t *dst) {
+  for (uint32_t r = 0; r < world; r++) {
+    memcpy(dst, h_recv1 + (size_t)r * per1 + row_off, (size_t)counts[r] * 32);
+    dst += (size_t)counts[r] * 32;
+  }
+}
+
+// this rank's trailer for one batch or group: its engine fault if there was one, else the first finding of its proofs [o, o + n)
+void shard_own_trailer(uint8_t *tr, int fault, const std::string &fault_msg, const Batch *b, size_t o, uint32_t n, uint32_t first_index) {
+  if (fault)
+    shard_trailer_encode(tr, BPP_TIER_ENGINE, fault, first_index, fault_msg.c_str());
+  else
+    shard_local_trailer(b->any_defer ? b->defer.data() + o : nullptr, b->h_status.data() + o, b->rounds_bad.data() + o, n, first_index, tr);
+}
+
+// every rank reads the same findings and decides alike: a finding of any rank (lowest tier, then lowest rank) comes
+// before the final check, exactly as in the single-process verify(); an engine fault only counts when nothing was found
+void shard_verdict(bpp_shard_result &out, const uint8_t *trailers, size_t stride, uint32_t world, bool identity) {
+  const ShardFinding f = shard_resolve(trailers, stride, (int)world);
+  if (f.tier != BPP_TIER_NONE)
+    shard_result_set(out, f.code > 0 || f.code < 0 ? f.code : BPP_ERR_ENGINE, f.tier, f.rank, f.index, f.msg + " (rank " + std::to_string(f.rank) + ")");
+  else if (!identity)
+    shard_result_set(out, BPP_ERR_VERIFICATION_FAILED, BPP_TIER_MSM, -1, 0, "Range proof batch not valid");
+  else
+    shard_result_set(out, BPP_OK, BPP_TIER_NONE, -1, 0, "");
+}
+
+// (an EngineError out here is a HIP failure around the collectives themselves: this rank cannot promise to reach the next collective)
+#define BPP_SHARD_CATCH(comm)                                                               \
+  catch (const CommError &e) { return comm_fail(comm, BPP_ERR_COMM, e.msg); }               \
+  catch (const EngineError &e) { return comm_fail(comm, e.code, e.msg); }                   \
+  catch (const std::exception &e) { return comm_fail(comm, BPP_ERR_ENGINE, e.what()); }
 
 }  // namespace
 
@@ -468,50 +553,23 @@ int bpp_verify_sharded_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const uint64_t
                             bpp_shard_result *results) {
   if (!comm) return BPP_ERR_BAD_HANDLE;
   if (!ctxs || !batches || !counts || !results || k_in == 0 || k_in > 64) return comm_fail(comm, BPP_ERR_INVALID_ARGUMENT, "bad wave arguments");
-  if (hipSetDevice(comm->device) != hipSuccess) return BPP_ERR_NO_DEVICE;
-  const uint32_t K = (uint32_t)k_in, world = (uint32_t)comm->world, rank = (uint32_t)comm->rank;
-  std::lock_guard<std::mutex> comm_lock(comm->mu);
-  if (comm->dead) return comm_fail(comm, BPP_ERR_COMM, "this communicator was aborted after a collective timed out: destroy it");
-  std::vector<std::unique_lock<std::mutex>> ctx_locks;
-  for (uint32_t i = 0; i < K; i++) {
-    if (!ctxs[i] || ctxs[i]->device != comm->device) return comm_fail(comm, BPP_ERR_BAD_HANDLE, "context of another device (or null) in the wave");
-    for (uint32_t j = 0; j < i; j++)
-      if (ctxs[j] == ctxs[i]) return comm_fail(comm, BPP_ERR_INVALID_ARGUMENT, "every batch of a wave needs its own context (stream)");
-    ctx_locks.emplace_back(ctxs[i]->mu);
-  }
-  uint32_t maxc = 0, first_index = 0;
-  uint64_t n_total = 0;
-  for (uint32_t r = 0; r < world; r++) {
-    maxc = std::max(maxc, counts[r]);
-    if (r < rank) first_index += counts[r];
-    n_total += counts[r];
-  }
-  if (n_total == 0 || n_total > (1u << 24)) return comm_fail(comm, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty");
+  const uint32_t K = (uint32_t)k_in;
+  ShardCall call;
+  const int rc_begin = shard_call_begin(comm, ctxs, K, counts, call);
+  if (rc_begin != BPP_OK) return rc_begin;
+  const uint32_t world = call.world, rank = call.rank, maxc = call.maxc, first_index = call.first_index;
+  const uint64_t n_total = call.n_total;
   // buffers: first exchange per rank = K slots of maxc x 32 RNG bytes; second = K accumulators + K findings (trailers)
   const size_t slot = (size_t)maxc * 32, per1 = K * slot, per2 = (size_t)K * 128 + (size_t)K * BPP_SHARD_TRAILER_BYTES;
   std::vector<Batch *> B(K, nullptr);
   std::vector<int> fault(K, 0);           // engine fault on THIS rank, per batch
   std::vector<std::string> fault_msg(K);
   std::vector<uint8_t> skip(K, 0);        // batch decided by the first exchange: no phase 2
-  auto t_mark = std::chrono::steady_clock::now();
-  bpp_shard_timing &tmg = comm->timing;
-  memset(&tmg, 0, sizeof(tmg));
-  tmg.batches = K;
-  auto lap = [&](float &slot) {
-    const auto now = std::chrono::steady_clock::now();
-    slot += std::chrono::duration<float, std::milli>(now - t_mark).count();
-    t_mark = now;
-  };
+  LapTimer laps(comm, K);
+  bpp_shard_timing &tmg = laps.tmg;
   try {
-    comm->send1.alloc(per1);
-    comm->recv1.alloc(per1 * world);
-    comm->send2.alloc(per2);
-    comm->recv2.alloc(per2 * world);
-    comm->d_flags.alloc(K);
-    comm->h_tr.resize((size_t)K * BPP_SHARD_TRAILER_BYTES);
-    comm->h_recv1.resize(per1 * world);
-    comm->h_recv2.resize(per2 * world);
-    comm->h_flags.resize(K);
+    bpp_comm::GroupSlot &S = comm_slot(comm, 0);
+    S.reserve(per1, per2, K, world);
     // ---------------------------------------------------------------- phase 1 on every context's own stream
     // Only the transcript-RNG bytes cross before the weights exist: they leave PASS 1, the first kernel of the phase, so the
     // exchange (and the weight chains behind it) overlap the decompression and the weight-free scalars of the same wave.
@@ -527,11 +585,8 @@ int bpp_verify_sharded_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const uint64_t
         B[i] = &b;
         StageTimer tm(ctxs[i]);
         hipStream_t s = ctxs[i]->stream;
-        uint8_t *dst = comm->send1.p + (size_t)i * slot;
-        if (!ctxs[i]->ev_rng_ready) {
-          HIP_CHECK(hipEventCreateWithFlags(&ctxs[i]->ev_rng, hipEventDisableTiming));
-          ctxs[i]->ev_rng_ready = true;
-        }
+        uint8_t *dst = S.send1.p + (size_t)i * slot;
+        ensure_ev_rng(ctxs[i]);
         if (b.any_defer) {
           // verify()'s consistency loops (:637-682) fail this batch before anything is computed: nothing runs on items
           // whose layout differs from the parameters'; the rank still sends a (zero) payload and, later, its finding
@@ -547,30 +602,26 @@ int bpp_verify_sharded_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const uint64_t
       } catch (const EngineError &e) {
         fault[i] = e.code;
         fault_msg[i] = e.msg;
-        (void)hipMemsetAsync(comm->send1.p + (size_t)i * slot, 0, slot, cs);  // this rank's slot still has defined bytes
+        (void)hipMemsetAsync(S.send1.p + (size_t)i * slot, 0, slot, cs);  // this rank's slot still has defined bytes
       }
     }
-    lap(tmg.enqueue1_ms);
-    comm_allgather(comm, comm->send1.p, comm->recv1.p, per1, cs);
-    HIP_CHECK(hipMemcpyAsync(comm->h_recv1.data(), comm->recv1.p, per1 * world, hipMemcpyDeviceToHost, cs));
+    laps.lap(tmg.enqueue1_ms);
+    comm_allgather(comm, S.send1.p, S.recv1.p, per1, cs);
+    HIP_CHECK(hipMemcpyAsync(S.h_recv1.data(), S.recv1.p, per1 * world, hipMemcpyDeviceToHost, cs));
     comm_wait(comm, cs);
-    lap(tmg.gather1_ms);
+    laps.lap(tmg.gather1_ms);
     // ---------------------------------------------------------------- weight transcripts over ALL proofs of each batch
     {
-      comm->rng_all.resize((size_t)K * n_total * 32);
-      comm->weights_all.resize((size_t)K * n_total * 32);
+      S.rng_all.resize((size_t)K * n_total * 32);
+      S.weights_all.resize((size_t)K * n_total * 32);
       std::vector<uint32_t> gfirst(K + 1);
       for (uint32_t i = 0; i < K; i++) {
         gfirst[i] = (uint32_t)(i * n_total);
-        uint8_t *dst = comm->rng_all.data() + (size_t)i * n_total * 32;
-        for (uint32_t r = 0; r < world; r++) {
-          memcpy(dst, comm->h_recv1.data() + (size_t)r * per1 + (size_t)i * slot, (size_t)counts[r] * 32);
-          dst += (size_t)counts[r] * 32;
-        }
+        shard_gather_rng(S.h_recv1.data(), per1, (size_t)i * slot, counts, world, S.rng_all.data() + (size_t)i * n_total * 32);
       }
       gfirst[K] = (uint32_t)(K * n_total);
-      run_weight_chains_generic(comm->rng_all.data(), comm->weights_all.data(), gfirst.data(), K);
-      lap(tmg.chains_ms);
+      run_weight_chains_generic(S.rng_all.data(), S.weights_all.data(), gfirst.data(), K);
+      laps.lap(tmg.chains_ms);
       // PASS 2 + this rank's share of the MSM wherever the kernels ran and the shapes allow it (a batch with an L/R count
       // that does not fit its statement has a PASS-2 finding coming and no scalars to run on)
       for (uint32_t i = 0; i < K; i++) {
@@ -581,12 +632,12 @@ int bpp_verify_sharded_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const uint64_t
           hipStream_t s = ctxs[i]->stream;
           if (no_kernels[i] || b.any_rounds_bad) {
             skip[i] = 1;
-            HIP_CHECK(hipMemsetAsync(comm->send2.p + (size_t)i * 128, 0, 128, s));
+            HIP_CHECK(hipMemsetAsync(S.send2.p + (size_t)i * 128, 0, 128, s));
             if (no_kernels[i]) HIP_CHECK(hipMemsetAsync(b.status.p, 0, (size_t)b.B * 4, s));
           } else {
-            memcpy(b.h_weights.data(), comm->weights_all.data() + ((size_t)i * n_total + first_index) * 32, (size_t)b.B * 32);
+            memcpy(b.h_weights.data(), S.weights_all.data() + ((size_t)i * n_total + first_index) * 32, (size_t)b.B * 32);
             enqueue_phase2(ctxs[i], b, tm);
-            hipLaunchKernelGGL(k_ge_to_bytes, dim3(1), dim3(64), 0, s, b.msm.R.p, 1u, comm->send2.p + (size_t)i * 128);
+            hipLaunchKernelGGL(k_ge_to_bytes, dim3(1), dim3(64), 0, s, b.msm.R.p, 1u, S.send2.p + (size_t)i * 128);
             HIP_CHECK(hipGetLastError());
             b.have_trace = true;
           }
@@ -597,51 +648,31 @@ int bpp_verify_sharded_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const uint64_t
         }
       }
     }
-    lap(tmg.enqueue2_ms);
+    laps.lap(tmg.enqueue2_ms);
     // ---------------------------------------------------------------- findings: one trailer per batch, next to the accumulator
     for (uint32_t i = 0; i < K; i++) {
-      uint8_t *tr = comm->h_tr.data() + (size_t)i * BPP_SHARD_TRAILER_BYTES;
+      uint8_t *tr = S.h_tr.data() + (size_t)i * BPP_SHARD_TRAILER_BYTES;
       if (!fault[i] && !gpu_wait_stream_ok(ctxs[i], ctxs[i]->stream, true)) {
         fault[i] = BPP_ERR_ENGINE;
         fault_msg[i] = "a kernel of this rank failed on the device";
       }
-      if (fault[i]) {
-        shard_trailer_encode(tr, BPP_TIER_ENGINE, fault[i], first_index, fault_msg[i].c_str());
-      } else {
-        Batch &b = *B[i];
-        settle_status(b);
-        shard_local_trailer(b.any_defer ? b.defer.data() : nullptr, b.h_status.data(), b.rounds_bad.data(), b.B, first_index, tr);
-      }
+      if (!fault[i]) settle_status(*B[i]);
+      shard_own_trailer(tr, fault[i], fault_msg[i], B[i], 0, counts[rank], first_index);
     }
-    lap(tmg.wait2_ms);
-    HIP_CHECK(hipMemcpyAsync(comm->send2.p + (size_t)K * 128, comm->h_tr.data(), (size_t)K * BPP_SHARD_TRAILER_BYTES, hipMemcpyHostToDevice, cs));
-    comm_allgather(comm, comm->send2.p, comm->recv2.p, per2, cs);
-    hipLaunchKernelGGL(k_sum_accumulators_wave, dim3(cdiv(K, 64)), dim3(64), 0, cs, comm->recv2.p, world, (uint32_t)per2, K, comm->d_flags.p);
+    laps.lap(tmg.wait2_ms);
+    HIP_CHECK(hipMemcpyAsync(S.send2.p + (size_t)K * 128, S.h_tr.data(), (size_t)K * BPP_SHARD_TRAILER_BYTES, hipMemcpyHostToDevice, cs));
+    comm_allgather(comm, S.send2.p, S.recv2.p, per2, cs);
+    hipLaunchKernelGGL(k_sum_accumulators_wave, dim3(cdiv(K, 64)), dim3(64), 0, cs, S.recv2.p, world, (uint32_t)per2, K, S.d_flags.p);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(comm->h_flags.data(), comm->d_flags.p, (size_t)K * 4, hipMemcpyDeviceToHost, cs));
-    HIP_CHECK(hipMemcpyAsync(comm->h_recv2.data(), comm->recv2.p, per2 * world, hipMemcpyDeviceToHost, cs));
+    HIP_CHECK(hipMemcpyAsync(S.h_flags.data(), S.d_flags.p, (size_t)K * 4, hipMemcpyDeviceToHost, cs));
+    HIP_CHECK(hipMemcpyAsync(S.h_recv2.data(), S.recv2.p, per2 * world, hipMemcpyDeviceToHost, cs));
     comm_wait(comm, cs);
-    lap(tmg.gather2_ms);
-    // every rank reads the same findings and decides alike: a finding of any rank (lowest tier, then lowest rank) comes
-    // before the final check, exactly as in the single-process verify(); an engine fault only counts when nothing was found
-    for (uint32_t i = 0; i < K; i++) {
-      const ShardFinding f = shard_resolve(comm->h_recv2.data() + (size_t)K * 128 + (size_t)i * BPP_SHARD_TRAILER_BYTES, per2, (int)world);
-      if (f.tier != BPP_TIER_NONE)
-        shard_result_set(results[i], f.code > 0 || f.code < 0 ? f.code : BPP_ERR_ENGINE, f.tier, f.rank, f.index, f.msg + " (rank " + std::to_string(f.rank) + ")");
-      else if (!comm->h_flags[i])
-        shard_result_set(results[i], BPP_ERR_VERIFICATION_FAILED, BPP_TIER_MSM, -1, 0, "Range proof batch not valid");
-      else
-        shard_result_set(results[i], BPP_OK, BPP_TIER_NONE, -1, 0, "");
-    }
+    laps.lap(tmg.gather2_ms);
+    for (uint32_t i = 0; i < K; i++)
+      shard_verdict(results[i], S.h_recv2.data() + (size_t)K * 128 + (size_t)i * BPP_SHARD_TRAILER_BYTES, per2, world, S.h_flags[i] != 0);
     return BPP_OK;
-  } catch (const CommError &e) {
-    return comm_fail(comm, BPP_ERR_COMM, e.msg);
-  } catch (const EngineError &e) {
-    // a HIP failure around the collectives themselves: this rank cannot promise to reach the next collective
-    return comm_fail(comm, e.code, e.msg);
-  } catch (const std::exception &e) {
-    return comm_fail(comm, BPP_ERR_ENGINE, e.what());
   }
+  BPP_SHARD_CATCH(comm)
 }
 
 // The grouped form: this rank's shards of `n_groups` reference batches live in ONE resident batch (group g = proofs
@@ -661,26 +692,13 @@ int bpp_verify_sharded_groups_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const u
   if (!comm) return BPP_ERR_BAD_HANDLE;
   if (!ctxs || !batches || !counts || !results || k_in == 0 || k_in > 16 || n_groups == 0 || n_groups > 4096)
     return comm_fail(comm, BPP_ERR_INVALID_ARGUMENT, "bad group arguments");
-  if (hipSetDevice(comm->device) != hipSuccess) return BPP_ERR_NO_DEVICE;
-  const uint32_t K = (uint32_t)k_in, G = (uint32_t)n_groups, world = (uint32_t)comm->world, rank = (uint32_t)comm->rank;
-  std::lock_guard<std::mutex> comm_lock(comm->mu);
-  if (comm->dead) return comm_fail(comm, BPP_ERR_COMM, "this communicator was aborted after a collective timed out: destroy it");
-  std::vector<std::unique_lock<std::mutex>> ctx_locks;
-  for (uint32_t i = 0; i < K; i++) {
-    if (!ctxs[i] || ctxs[i]->device != comm->device) return comm_fail(comm, BPP_ERR_BAD_HANDLE, "context of another device (or null)");
-    for (uint32_t j = 0; j < i; j++)
-      if (ctxs[j] == ctxs[i]) return comm_fail(comm, BPP_ERR_INVALID_ARGUMENT, "every batch of a wave needs its own context (stream)");
-    ctx_locks.emplace_back(ctxs[i]->mu);
-  }
-  uint32_t maxc = 0, first_index = 0;
-  uint64_t n_total = 0;
-  for (uint32_t r = 0; r < world; r++) {
-    maxc = std::max(maxc, counts[r]);
-    if (r < rank) first_index += counts[r];
-    n_total += counts[r];
-  }
+  const uint32_t K = (uint32_t)k_in, G = (uint32_t)n_groups;
+  ShardCall call;
+  const int rc_begin = shard_call_begin(comm, ctxs, K, counts, call);
+  if (rc_begin != BPP_OK) return rc_begin;
+  const uint32_t world = call.world, rank = call.rank, maxc = call.maxc, first_index = call.first_index;
+  const uint64_t n_total = call.n_total;
   const uint32_t c = counts[rank];
-  if (n_total == 0 || n_total > (1u << 24)) return comm_fail(comm, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty");
   if (c == 0) return comm_fail(comm, BPP_ERR_INVALID_ARGUMENT, "the grouped form needs a non-empty shard on every rank");
   const size_t slot = (size_t)maxc * 32, per1 = G * slot, per2 = (size_t)G * 128 + (size_t)G * BPP_SHARD_TRAILER_BYTES;
   // Weight transcripts over ALL proofs of each reference batch.  One rank replays all of them.  Several ranks share them out:
@@ -695,29 +713,13 @@ int bpp_verify_sharded_groups_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const u
   std::vector<int> fault(K, 0);  // engine fault on THIS rank: it still reaches every collective, with zero payloads and an ENGINE finding
   std::vector<std::string> fault_msg(K);
   std::vector<Batch *> B(K, nullptr);
-  auto t_mark = std::chrono::steady_clock::now();
-  bpp_shard_timing &tmg = comm->timing;
-  memset(&tmg, 0, sizeof(tmg));
-  tmg.batches = K * G;
-  auto lap = [&](float &slot_ms) {
-    const auto now = std::chrono::steady_clock::now();
-    slot_ms += std::chrono::duration<float, std::milli>(now - t_mark).count();
-    t_mark = now;
-  };
+  LapTimer laps(comm, K * G);
+  bpp_shard_timing &tmg = laps.tmg;
   try {
-    while (comm->slots.size() < K) comm->slots.emplace_back(new bpp_comm::GroupSlot());
     hipStream_t cs = comm->stream;
     for (uint32_t i = 0; i < K; i++) {
-      bpp_comm::GroupSlot &S = *comm->slots[i];
-      S.send1.alloc(per1);
-      S.recv1.alloc(per1 * world);
-      S.send2.alloc(per2);
-      S.recv2.alloc(per2 * world);
-      S.d_flags.alloc(G);
-      S.h_tr.resize((size_t)G * BPP_SHARD_TRAILER_BYTES);
-      S.h_recv1.resize(per1 * world);
-      S.h_recv2.resize(per2 * world);
-      S.h_flags.resize(G);
+      bpp_comm::GroupSlot &S = comm_slot(comm, i);
+      S.reserve(per1, per2, G, world);
       if (share_chains) {
         S.send3.alloc(per3);
         S.recv3.alloc(per3 * world);
@@ -735,10 +737,7 @@ int bpp_verify_sharded_groups_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const u
         if ((uint64_t)b.B != (uint64_t)G * c) throw EngineError{BPP_ERR_ENGINE, "the resident batch does not hold n_groups x counts[rank] proofs"};
         B[i] = &b;
         StageTimer tm(ctx);
-        if (!ctx->ev_rng_ready) {
-          HIP_CHECK(hipEventCreateWithFlags(&ctx->ev_rng, hipEventDisableTiming));
-          ctx->ev_rng_ready = true;
-        }
+        ensure_ev_rng(ctx);
         layout_groups(ctx, b, G == 1 ? 0 : c);
         if (b.G != G) throw EngineError{BPP_ERR_ENGINE, "group layout differs from n_groups"};
         if (c < maxc) HIP_CHECK(hipMemsetAsync(S.send1.p, 0, per1, s));
@@ -757,7 +756,7 @@ int bpp_verify_sharded_groups_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const u
         (void)hipMemsetAsync(S.send1.p, 0, per1, cs);
       }
     }
-    lap(tmg.enqueue1_ms);
+    laps.lap(tmg.enqueue1_ms);
     // ---------------------------------------------------------------- per slot: first exchange, chains, phase 2
     for (uint32_t i = 0; i < K; i++) {
       bpp_comm::GroupSlot &S = *comm->slots[i];
@@ -766,7 +765,7 @@ int bpp_verify_sharded_groups_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const u
       comm_allgather(comm, S.send1.p, S.recv1.p, per1, cs);
       HIP_CHECK(hipMemcpyAsync(S.h_recv1.data(), S.recv1.p, per1 * world, hipMemcpyDeviceToHost, cs));
       comm_wait(comm, cs);
-      lap(tmg.gather1_ms);
+      laps.lap(tmg.gather1_ms);
       S.rng_all.resize((size_t)std::max(n_own, 1u) * n_total * 32);
       S.weights_all.resize((size_t)std::max(n_own, 1u) * n_total * 32);
       {
@@ -774,22 +773,18 @@ int bpp_verify_sharded_groups_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const u
         for (uint32_t j = 0; j < n_own; j++) {
           const uint32_t g = share_chains ? rank + j * world : j;
           gfirst[j] = (uint32_t)(j * n_total);
-          uint8_t *dst = S.rng_all.data() + (size_t)j * n_total * 32;
-          for (uint32_t r = 0; r < world; r++) {
-            memcpy(dst, S.h_recv1.data() + (size_t)r * per1 + (size_t)g * slot, (size_t)counts[r] * 32);
-            dst += (size_t)counts[r] * 32;
-          }
+          shard_gather_rng(S.h_recv1.data(), per1, (size_t)g * slot, counts, world, S.rng_all.data() + (size_t)j * n_total * 32);
         }
         gfirst[n_own] = (uint32_t)(n_own * n_total);
         if (n_own) run_weight_chains_generic(S.rng_all.data(), S.weights_all.data(), gfirst.data(), n_own);
       }
-      lap(tmg.chains_ms);
+      laps.lap(tmg.chains_ms);
       if (share_chains) {
         if (n_own < slots3) HIP_CHECK(hipMemsetAsync(S.send3.p, 0, per3, cs));
         if (n_own) HIP_CHECK(hipMemcpyAsync(S.send3.p, S.weights_all.data(), (size_t)n_own * n_total * 32, hipMemcpyHostToDevice, cs));
         comm_allgather(comm, S.send3.p, S.recv3.p, per3, cs);
         comm_wait(comm, cs);
-        lap(tmg.gather1_ms);  // (counted with the first exchange: the timing struct is part of the ABI)
+        laps.lap(tmg.gather1_ms);  // (counted with the first exchange: the timing struct is part of the ABI)
       }
       if (!fault[i]) {
         Batch &b = *B[i];
@@ -822,7 +817,7 @@ int bpp_verify_sharded_groups_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const u
           fault_msg[i] = e.msg;
         }
       }
-      lap(tmg.enqueue2_ms);
+      laps.lap(tmg.enqueue2_ms);
     }
     // ---------------------------------------------------------------- per slot: findings, second exchange, verdicts
     for (uint32_t i = 0; i < K; i++) {
@@ -834,17 +829,9 @@ int bpp_verify_sharded_groups_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const u
       }
       if (fault[i]) (void)hipMemsetAsync(S.send2.p, 0, (size_t)G * 128, cs);
       else settle_status(*B[i]);
-      for (uint32_t g = 0; g < G; g++) {
-        uint8_t *tr = S.h_tr.data() + (size_t)g * BPP_SHARD_TRAILER_BYTES;
-        if (fault[i]) {
-          shard_trailer_encode(tr, BPP_TIER_ENGINE, fault[i], first_index, fault_msg[i].c_str());
-        } else {
-          Batch &b = *B[i];
-          const size_t o = (size_t)g * c;
-          shard_local_trailer(b.any_defer ? b.defer.data() + o : nullptr, b.h_status.data() + o, b.rounds_bad.data() + o, c, first_index, tr);
-        }
-      }
-      lap(tmg.wait2_ms);
+      for (uint32_t g = 0; g < G; g++)
+        shard_own_trailer(S.h_tr.data() + (size_t)g * BPP_SHARD_TRAILER_BYTES, fault[i], fault_msg[i], B[i], (size_t)g * c, c, first_index);
+      laps.lap(tmg.wait2_ms);
       HIP_CHECK(hipMemcpyAsync(S.send2.p + (size_t)G * 128, S.h_tr.data(), (size_t)G * BPP_SHARD_TRAILER_BYTES, hipMemcpyHostToDevice, cs));
       comm_allgather(comm, S.send2.p, S.recv2.p, per2, cs);
       hipLaunchKernelGGL(k_sum_accumulators_wave, dim3(cdiv(G, 64)), dim3(64), 0, cs, S.recv2.p, world, (uint32_t)per2, G, S.d_flags.p);
@@ -852,26 +839,13 @@ int bpp_verify_sharded_groups_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const u
       HIP_CHECK(hipMemcpyAsync(S.h_flags.data(), S.d_flags.p, (size_t)G * 4, hipMemcpyDeviceToHost, cs));
       HIP_CHECK(hipMemcpyAsync(S.h_recv2.data(), S.recv2.p, per2 * world, hipMemcpyDeviceToHost, cs));
       comm_wait(comm, cs);
-      lap(tmg.gather2_ms);
-      for (uint32_t g = 0; g < G; g++) {
-        bpp_shard_result &out = results[(size_t)i * G + g];
-        const ShardFinding f = shard_resolve(S.h_recv2.data() + (size_t)G * 128 + (size_t)g * BPP_SHARD_TRAILER_BYTES, per2, (int)world);
-        if (f.tier != BPP_TIER_NONE)
-          shard_result_set(out, f.code > 0 || f.code < 0 ? f.code : BPP_ERR_ENGINE, f.tier, f.rank, f.index, f.msg + " (rank " + std::to_string(f.rank) + ")");
-        else if (!S.h_flags[g])
-          shard_result_set(out, BPP_ERR_VERIFICATION_FAILED, BPP_TIER_MSM, -1, 0, "Range proof batch not valid");
-        else
-          shard_result_set(out, BPP_OK, BPP_TIER_NONE, -1, 0, "");
-      }
+      laps.lap(tmg.gather2_ms);
+      for (uint32_t g = 0; g < G; g++)
+        shard_verdict(results[(size_t)i * G + g], S.h_recv2.data() + (size_t)G * 128 + (size_t)g * BPP_SHARD_TRAILER_BYTES, per2, world, S.h_flags[g] != 0);
     }
     return BPP_OK;
-  } catch (const CommError &e) {
-    return comm_fail(comm, BPP_ERR_COMM, e.msg);
-  } catch (const EngineError &e) {
-    return comm_fail(comm, e.code, e.msg);
-  } catch (const std::exception &e) {
-    return comm_fail(comm, BPP_ERR_ENGINE, e.what());
   }
+  BPP_SHARD_CATCH(comm)
 }
 
 int bpp_verify_sharded_groups(bpp_comm *comm, bpp_ctx *ctx, uint64_t batch, size_t n_groups, const uint32_t *counts,

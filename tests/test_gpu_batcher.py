@@ -44,12 +44,23 @@ def test_ragged_groups_equal_calls_of_their_own(bpp, packed, engine):
     pr[100, 1 + 32:1 + 64] = np.frombuffer(b"\x01" + bytes(31), dtype=np.uint8)       # group 3 (72..271): non-canonical A at in-group index 28
     pr[273, 1 + 32:1 + 64] = 0                                                      # group 4 (272..274): identity A at in-group index 1
     pr[274, 1 + 32:1 + 64] = np.frombuffer(b"\x01" + bytes(31), dtype=np.uint8)       # ... and a later-tier finding after it
-    for proofs in (d["proofs"], pr):
+    # ONE group over the whole batch, where a call of its own stops early: every proof an (L, R) pair short (PASS 1 only), and a
+    # proof that parses under another extension degree (t = 3, five pairs: nothing runs at all)
+    cut = d["proofs"][:, :-64]
+    deg = d["proofs"].copy()
+    deg[5, 0] = 3
+    deg[5, 1 + 32:1 + 96] = 0
+    deg[5, 1 + 192:1 + 256] = 0
+    for proofs, cuts in ((d["proofs"], bounds), (pr, bounds), (cut, [0, 600]), (deg, [0, 600])):
         rb = packed.ResidentBatch(params, proofs, d["commitments"], d["min_values"], d["min_present"], None, LABEL)
-        res = packed.verify_groups(rb, bounds)
+        res = packed.verify_groups(rb, cuts)
         rb.close()
-        want = [_direct(bpp, packed, params, d, proofs, slice(bounds[g], bounds[g + 1])) for g in range(len(bounds) - 1)]
+        want = [_direct(bpp, packed, params, d, proofs, slice(cuts[g], cuts[g + 1])) for g in range(len(cuts) - 1)]
         assert [r["code"] for r in res] == want
+        if proofs is cut:
+            assert want == [int(K.InvalidLength)] and (res[0]["tier"], res[0]["index"]) == (6, 0)
+        if proofs is deg:
+            assert want == [int(K.InvalidArgument)] and (res[0]["tier"], res[0]["index"]) == (2, 5)
         if proofs is pr:
             assert want == [int(K.VerificationFailed), 0, 0, int(K.InvalidArgument), int(K.VerificationFailed), 0]
             assert (res[0]["tier"], res[3]["tier"], res[3]["index"], res[4]["tier"], res[4]["index"]) == (7, 6, 28, 5, 1)
