@@ -154,6 +154,8 @@ SYMBOLS = [
     ("bpp_prove_pool_destroy", None, [c_void_p]),
     ("bpp_prove_check_stats", c_int, [c_void_p, POINTER(ProveCheckStats)]),
     ("bpp_prove_pool_check_stats", c_int, [c_void_p, POINTER(ProveCheckStats)]),
+    ("bpp_prove_check_recovery_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    ("bpp_prove_pool_check_recovery_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     ("bpp_batch_trace", c_int, [c_void_p, c_uint64, c_int, c_void_p, c_size_t, POINTER(c_size_t)]),
     ("bpp_batch_shape", c_int, [c_void_p, c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32),
                                 POINTER(c_uint32), POINTER(c_uint32)]),

@@ -166,6 +166,13 @@ class Engine:
         _check(self.lib.bpp_prove_check_stats(self.ctx, byref(s)), self.ctx)
         return {n: int(getattr(s, n)) for n, _ in _lib.ProveCheckStats._fields_}
 
+    def prove_check_recovery_stats(self):
+        """bpp_prove_check_recovery_stats ("prove_check" = 1 and "prove_check_recovery" = 1): proofs with a seed nonce whose mask
+        recovery the self-check replayed, and how many of them did not return the witness's blinding factors"""
+        replayed, mismatched = c_uint64(), c_uint64()
+        _check(self.lib.bpp_prove_check_recovery_stats(self.ctx, byref(replayed), byref(mismatched)), self.ctx)
+        return {"replayed": int(replayed.value), "mismatched": int(mismatched.value)}
+
     def last_profile(self):
         p = _lib.Profile()
         self.lib.bpp_profile_get(self.ctx, byref(p))

@@ -15,6 +15,7 @@
 #include <time.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -571,7 +572,7 @@ struct bpp_ctx {
   struct Options {
     int transcripts_wave = -1, tables_wave = -1, side_decompress = -1, msm_c_bias = -1, msm_c_max = -1, msm_c_add = -1, msm_rc2 = -1, msm_quad = -1, msm_final_quad = -1,
         fb_threads = -1, prove_subs = -1, msm_split = -1, fused_columns = -1, prove_prio = -1, prove_fused = -1, static_gemm = -1, lazy_columns = -1, ct = -1, prove_parts = -1, prove_waves = -1, prove_fifo = -1, chain = -1, chain_test_zero = 0, wait = -1, ct_back = -1, chain_inline = -1, wide_in_lanes = -1,
-        prove_check = -1;
+        prove_check = -1, prove_check_recovery = -1;
   } opt;
   // the prover's self-check ("prove_check" = 1, engine_prove.h: prove_self_check): the verification batch it keeps between calls
   // (the next check's upload adopts its buffers, as the next upload adopts spare_batch's), the remembered waits of ITS
@@ -579,11 +580,28 @@ struct bpp_ctx {
   std::unique_ptr<Batch> check_spare;
   WaitHint check_hint_rng, check_hint_end;
   struct bpp_prove_check_stats check_stats{};
+  // the check's replay of mask recovery ("prove_check_recovery" = 1, engine_prove.h: check_verify): the witness's blinding factors of
+  // the nonce-bearing items and their places in the checking batch, page-locked and on the device (both the check's own, wiped
+  // before the prove call returns), the one word per compared proof that comes back, the counters
+  PinnedBuf<uint8_t> check_pin;
+  DevBuf<uint8_t> check_dev;
+  PinnedBuf<uint32_t> check_words;
+  uint64_t check_replayed = 0, check_mismatched = 0;
+  // the seed-nonce and mask buffers of the check's batch as they were last seen zeroed (give_back in check_verify zeroes a fresh
+  // allocation once: bpp_prove_secret_bytes reads them, and what hipMalloc hands out is not zero)
+  const void *check_zeroed_seeds = nullptr, *check_zeroed_masks = nullptr;
+  size_t check_zeroed_seeds_n = 0, check_zeroed_masks_n = 0;
+  // the statements (first commitment: public) of the context's last mixed prove call whose self-check failed on mask recovery and
+  // not on the verifier's verdict: bpp_prove_item_message, which is given an item and a code, tells the two apart by it
+  std::mutex check_note_mu;
+  std::vector<std::array<uint8_t, 32>> check_recovery_failed;
   // test knobs of the self-check (bpp_ctx_set_option only, no environment variable, not copied to a prove pool's lanes): XOR
   // `mask` into byte `byte` of proof `proof` - 1 in the page-locked host copy of the NEXT checked prove call, before the check; `times`
-  // = 2 alters the remake of that proof as well.  The call's entry point takes them and puts the defaults back.
+  // = 2 alters the remake of that proof as well.  `nonce` = 1: the byte is altered in the check's own copy of that item's seed
+  // nonce instead (byte 0..31; "prove_check_recovery" = 1: the replayed recovery then disagrees with a proof that is right).  The
+  // call's entry point takes them and puts the defaults back.
   struct CheckTamper {
-    int proof = 0, byte = 1, mask = 1, times = 1;
+    int proof = 0, byte = 1, mask = 1, times = 1, nonce = 0;
   } tamper;
   std::unique_ptr<Pipeline> pipe;  // bpp_verify_submit_packed / bpp_verify_collect: lanes, tickets (built on first submit)
   std::mutex pipe_init_mu;
@@ -645,6 +663,10 @@ const OptionName kOptions[] = {
     // 1: every proof of bpp_prove_batch / bpp_prove_batch_mixed (and of a prove pool made from this context) is verified on this
     // context before it is returned, a rejected one made again once (engine_prove.h: prove_self_check); 0 / -1: off
     {"prove_check", "BPP_PROVE_CHECK", &bpp_ctx::Options::prove_check},
+    // 1: a checked call ("prove_check" = 1) also replays mask recovery for its items that carry a seed nonce and compares the
+    // recovered masks with the witness's blinding factors on the device (engine_prove.h: check_verify); 0 / -1: off.  Without
+    // "prove_check" it does nothing
+    {"prove_check_recovery", "BPP_PROVE_CHECK_RECOVERY", &bpp_ctx::Options::prove_check_recovery},
 };
 struct TamperName {
   const char *name;
@@ -655,6 +677,7 @@ const TamperName kTamperKnobs[] = {
     {"prove_check_tamper_byte", &bpp_ctx::CheckTamper::byte},
     {"prove_check_tamper_xor", &bpp_ctx::CheckTamper::mask},
     {"prove_check_tamper_times", &bpp_ctx::CheckTamper::times},
+    {"prove_check_tamper_nonce", &bpp_ctx::CheckTamper::nonce},
 };
 void options_from_env(bpp_ctx *c) {
   for (const OptionName &o : kOptions)
@@ -3076,6 +3099,24 @@ int bpp_prove_secret_bytes(bpp_ctx *ctx, uint64_t *examined, uint64_t *nonzero) 
       for (size_t i = 0; i < ctx->prove_pin_in.n; i++) cnt += ctx->prove_pin_in.p[i] != 0;
       seen += ctx->prove_pin_in.n;
     }
+    // the self-check's replay of mask recovery: its staging of blinding factors (page-locked and on the device) and the seed
+    // nonces and recovered masks of its own verification batch, which waits in check_spare between calls
+    if (ctx->check_pin.p && ctx->check_pin.n) {
+      for (size_t i = 0; i < ctx->check_pin.n; i++) cnt += ctx->check_pin.p[i] != 0;
+      seen += ctx->check_pin.n;
+    }
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    std::vector<const DevBuf<uint8_t> *> dev{&ctx->check_dev};
+    if (ctx->check_spare && ctx->check_spare->seeds.p == ctx->check_zeroed_seeds) dev.push_back(&ctx->check_spare->seeds);
+    if (ctx->check_spare && ctx->check_spare->masks.p == ctx->check_zeroed_masks) dev.push_back(&ctx->check_spare->masks);
+    for (const DevBuf<uint8_t> *buf : dev) {
+      if (!buf->p || !buf->n) continue;
+      std::vector<uint8_t> h(buf->n);
+      HIP_CHECK(hipMemcpy(h.data(), buf->p, buf->n, hipMemcpyDeviceToHost));
+      for (uint8_t v : h) cnt += v != 0;
+      seen += h.size();
+      wipe(h.data(), h.size());
+    }
     *examined = seen;
     *nonzero = cnt;
     return BPP_OK;
@@ -3094,6 +3135,14 @@ int bpp_prove_check_stats(bpp_ctx *ctx, struct bpp_prove_check_stats *out) {
   if (!ctx || !out) return BPP_ERR_BAD_HANDLE;
   std::lock_guard<std::mutex> lk(ctx->mu);
   *out = ctx->check_stats;
+  return BPP_OK;
+}
+
+int bpp_prove_check_recovery_stats(bpp_ctx *ctx, uint64_t *replayed, uint64_t *mismatched) {
+  if (!ctx) return BPP_ERR_BAD_HANDLE;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (replayed) *replayed = ctx->check_replayed;
+  if (mismatched) *mismatched = ctx->check_mismatched;
   return BPP_OK;
 }
 

@@ -10,8 +10,14 @@ size_t prove_item_len(const Params &P, uint32_t m);
 void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_prove_item *items, uint32_t B, size_t plen, uint8_t *&proofs,
                       uint32_t *&status, const bpp_ctx::CheckTamper &tamper, bool remake, std::vector<uint8_t> &kept_proofs,
                       std::vector<uint32_t> &kept_status);
+// what follows "proof %u failed the engine's self-check: " / "the proof failed the engine's self-check: "
+const char *const kSelfCheckRejectedWhy = "the verifier rejected it and its remake";
+const char *const kSelfCheckRecoveryWhy =
+    "mask recovery under its seed nonce does not return the witness's blinding factors, for it and for its remake";
 // (a host-side flag next to the device's PV_STATUS_* bits: the proof failed the self-check, after its remake if there was one)
 #define PV_STATUS_SELF_CHECK 0x100u
+// (with it: what failed was the replay of mask recovery, not the verifier's verdict -- "prove_check_recovery" = 1)
+#define PV_STATUS_SELF_CHECK_RECOVERY 0x200u
 
 // The body of bpp_prove_batch (the context's lock held, its device current).  dev_status == nullptr: bpp_prove_batch itself, which
 // turns the first device-side status word into the call's error.  Otherwise (bpp_prove_batch_mixed) the status words go to
@@ -608,8 +614,9 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
     } else {
       for (uint32_t i = 0; i < B; i++)
         if (pin_status[i] & PV_STATUS_SELF_CHECK) {
-          char msg[160];
-          snprintf(msg, sizeof(msg), "proof %u failed the engine's self-check: the verifier rejected it and its remake", i);
+          char msg[224];
+          snprintf(msg, sizeof(msg), "proof %u failed the engine's self-check: %s", i,
+                   (pin_status[i] & PV_STATUS_SELF_CHECK_RECOVERY) ? kSelfCheckRecoveryWhy : kSelfCheckRejectedWhy);
           throw ProofErr{BPP_ERR_SELF_CHECK, msg, BPP_TIER_ENGINE, i};
         }
     }
@@ -622,7 +629,9 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
 // ================================================================= self-check ("prove_check" = 1)
 // The proofs a prove call made are verified on the same context before any byte of them leaves the engine: the verifier's own
 // upload (upload_host.h) and resident path (verify_chunked_locked / verify_groups_locked), no parser or kernel of its own.  Only public inputs are
-// looked at -- the proof bytes and the item's statement and transcript -- and nothing is written but status words.
+// looked at -- the proof bytes and the item's statement and transcript -- and nothing is written but status words.  With
+// "prove_check_recovery" = 1 the items that carry a seed nonce take it along and their blinding factors are compared with the masks
+// the verifier recovers (check_verify): two secrets the check then holds, in buffers of its own that it wipes before it returns.
 //
 // Locks: the context's lock is held (the prove call's).  The check does NOT pass the device's small-call gate (GateHold): the gate
 // is always taken BEFORE a context's lock, and a thread that holds a context's lock and then waits for the gate deadlocks against
@@ -636,23 +645,43 @@ bpp_ctx::CheckTamper take_tamper(bpp_ctx *ctx) {
   return t;
 }
 
-// One verification of the check as ONE reference batch (chunk 0, VerifyOnly), or -- with `single` -- every proof as a group of its
-// own (bpp_verify_resident_groups' path: group_first = 0, 1, ..., n), its code in codes[k].  The batch is the check's own: its
+// One verification of the check as ONE reference batch (chunk 0), or -- with `single` -- every proof as a group of its own
+// (bpp_verify_resident_groups' path: group_first = 0, 1, ..., n), its code in codes[k].  The batch is the check's own: its
 // buffers come from ctx->check_spare and go back there, the caller's resident batches and the spare batch that the caller's next
 // upload adopts are left as they were.  Returns 0, or the upload's code when it refuses the batch (a proof of the wrong length, a
 // non-canonical scalar: nothing was verified, `codes` untouched), or the verification's finding; an engine fault throws.
-int check_verify(bpp_ctx *ctx, uint64_t params, const std::vector<bpp_verify_item> &vi, bool single, std::vector<int> *codes) {
+//
+// blind == nullptr: VerifyOnly, no item carries a seed nonce.  Otherwise ("prove_check_recovery" = 1 and some item of `vi` carries
+// one) the verification runs under RecoverAndVerify: k_masks derives the nonces on its own from the uploaded seed nonce and the
+// proof's challenges and leaves the recovered masks in the batch's device buffer.  (*blind)[k] != nullptr: the t blinding factors
+// of item k's opening; they go through the check's page-locked staging into its device buffer, kp_check_recovery compares them
+// with the masks there and one word per such item comes back: (*mismatch)[k] = 1 where they differ (meaningful for the items
+// whose verification passed; without `single`, when the whole batch passed).  The recovered masks also pass through the
+// verification flow's page-locked mask bytes, which its outcome object wipes; nothing of them is copied anywhere else.
+// Wiped before this returns, on every way out: the batch's seed nonces and masks (give_back), the staging of blinding factors.
+int check_verify(bpp_ctx *ctx, uint64_t params, const std::vector<bpp_verify_item> &vi, bool single, std::vector<int> *codes,
+                 const std::vector<const uint8_t *> *blind = nullptr, std::vector<uint8_t> *mismatch = nullptr) {
   char err[256];
   err[0] = 0;
   uint64_t h = 0;
+  hipStream_t s = ctx->stream;
+  const int action = blind ? BPP_RECOVER_AND_VERIFY : BPP_VERIFY_ONLY;
   std::swap(ctx->spare_batch, ctx->check_spare);  // (the upload adopts the check's buffers; the caller's spare waits in check_spare)
   ScopeExit give_back{[&] {
     std::unique_ptr<Batch> mine;
     auto it = h ? ctx->batches.find(h) : ctx->batches.end();
     if (it != ctx->batches.end()) {
-      (void)hipStreamSynchronize(ctx->stream);
-      wipe_batch_secrets(*it->second, ctx->stream);  // (none: no seed nonce, VerifyOnly)
-      (void)hipStreamSynchronize(ctx->stream);
+      (void)hipStreamSynchronize(s);
+      Batch &b = *it->second;
+      // (a fresh allocation is zeroed once, whether or not this check wrote to it: bpp_prove_secret_bytes reads these buffers)
+      if (b.seeds.p != ctx->check_zeroed_seeds || b.seeds.n != ctx->check_zeroed_seeds_n) b.seeds_dirty = true;
+      if (b.masks.p != ctx->check_zeroed_masks || b.masks.n != ctx->check_zeroed_masks_n) b.masks_dirty = true;
+      wipe_batch_secrets(b, s);  // the items' seed nonces, the recovered masks
+      (void)hipStreamSynchronize(s);
+      ctx->check_zeroed_seeds = b.seeds.p;
+      ctx->check_zeroed_seeds_n = b.seeds.n;
+      ctx->check_zeroed_masks = b.masks.p;
+      ctx->check_zeroed_masks_n = b.masks.n;
       mine = std::move(it->second);
       ctx->batches.erase(it);
     } else {
@@ -661,20 +690,55 @@ int check_verify(bpp_ctx *ctx, uint64_t params, const std::vector<bpp_verify_ite
     ctx->spare_batch = std::move(ctx->check_spare);
     ctx->check_spare = std::move(mine);
   }};
+  bool staged = false;
+  ScopeExit wipe_staging{[&] {  // (runs before give_back: the batch is still resident, the stream may still be reading the staging)
+    if (!staged) return;
+    if (ctx->check_dev.p) (void)hipMemsetAsync(ctx->check_dev.p, 0, ctx->check_dev.n, s);
+    (void)hipStreamSynchronize(s);
+    wipe(ctx->check_pin.p, ctx->check_pin.n);
+  }};
+  auto compare = [&] {
+    Batch &b = *ctx->batches.at(h);
+    if (!b.masks_dirty) throw EngineError{BPP_ERR_ENGINE, "self-check: the verification recovered no masks"};
+    std::vector<uint32_t> idx;
+    for (size_t k = 0; k < vi.size(); k++)
+      if ((*blind)[k]) idx.push_back((uint32_t)k);
+    const size_t n = idx.size(), row = (size_t)b.params->t * 32;
+    mismatch->assign(vi.size(), 0);
+    if (n == 0) return;
+    ctx->check_pin.resize(n * row + n * 4);
+    ctx->check_dev.alloc(n * row + n * 4);
+    ctx->check_words.resize(n);
+    staged = true;
+    for (size_t q = 0; q < n; q++) {
+      memcpy(ctx->check_pin.p + q * row, (*blind)[idx[q]], row);
+      ctx->check_words[q] = 0xffffffffu;  // (a word the kernel did not write is a difference)
+    }
+    memcpy(ctx->check_pin.p + n * row, idx.data(), n * 4);
+    HIP_CHECK(hipMemcpyAsync(ctx->check_dev.p, ctx->check_pin.p, n * row + n * 4, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(kp_check_recovery, dim3(cdiv((uint32_t)n, 64)), dim3(64), 0, s, b.masks.p, ctx->check_dev.p,
+                       (const uint32_t *)(ctx->check_dev.p + n * row), (uint32_t)n, b.params->t, b.B, ctx->check_words.dev());
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipStreamSynchronize(s));
+    for (size_t q = 0; q < n; q++) (*mismatch)[idx[q]] = ctx->check_words[q] != 0 ? 1 : 0;
+  };
   int rc = upload_impl(ctx, params, vi.data(), vi.size(), nullptr, &h, nullptr, nullptr, err, sizeof(err));
   if (rc < 0) throw ProofErr{rc, err, BPP_TIER_ENGINE};
   if (rc != BPP_OK) return rc;
   if (!single) {
-    rc = verify_chunked_locked(ctx, h, BPP_VERIFY_ONLY, 0, nullptr, nullptr, err, sizeof(err));
+    rc = verify_chunked_locked(ctx, h, action, 0, nullptr, nullptr, err, sizeof(err));
     if (rc < 0) throw ProofErr{rc, err, BPP_TIER_ENGINE};
+    if (rc == BPP_OK && blind) compare();
     return rc;
   }
   std::vector<uint32_t> first(vi.size() + 1);
   for (size_t k = 0; k <= vi.size(); k++) first[k] = (uint32_t)k;
   std::vector<bpp_shard_result> res(vi.size());
-  rc = verify_groups_locked(ctx, h, first.data(), vi.size(), nullptr, res.data(), nullptr, nullptr);
+  const std::vector<int> actions(vi.size(), action);
+  rc = verify_groups_locked(ctx, h, first.data(), vi.size(), blind ? actions.data() : nullptr, res.data(), nullptr, nullptr);
   if (rc != BPP_OK) throw ProofErr{rc < 0 ? rc : BPP_ERR_ENGINE, ctx->err, BPP_TIER_ENGINE};
   for (size_t k = 0; k < vi.size(); k++) (*codes)[k] = res[k].code;
+  if (blind) compare();
   return BPP_OK;
 }
 
@@ -683,7 +747,10 @@ int check_verify(bpp_ctx *ctx, uint64_t params, const std::vector<bpp_verify_ite
 // decode, the final MSM), the proofs that fail on their own are located: every proof as a group of its own, or, where the upload
 // refused the batch, as one-item verifications.  Each of them is made again, alone, by a one-item prove_uniform with the check on
 // (remake = false there): its bytes depend on its item alone, so a device that computes correctly gives the same bytes.  A remake
-// that passes replaces the proof; one that fails sets PV_STATUS_SELF_CHECK in the item's status word.  A remake reuses the call's
+// that passes replaces the proof; one that fails sets PV_STATUS_SELF_CHECK in the item's status word.  With "prove_check_recovery"
+// = 1 a proof the verifier accepts whose replayed mask recovery (check_verify) does not return the witness's blinding factors is a
+// finding of the same kind: made again once from the same inputs (nothing is drawn again), failed if its remake's replay differs
+// too (PV_STATUS_SELF_CHECK_RECOVERY says which of the two the failure was).  A remake reuses the call's
 // staging: the proofs and status words move to kept_* first, and `proofs` / `status` point there afterwards.
 void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_prove_item *items, uint32_t B, size_t plen, uint8_t *&proofs,
                       uint32_t *&status, const bpp_ctx::CheckTamper &tamper, bool remake, std::vector<uint8_t> &kept_proofs,
@@ -692,11 +759,19 @@ void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_
   for (uint32_t i = 0; i < B; i++)
     if (status[i] == 0) which.push_back(i);
   if (which.empty()) return;
-  if (tamper.proof > 0 && (uint32_t)tamper.proof <= B) {  // (test knob: a byte of the host copy, never the device's work)
+  // (test knob: a byte of the host copy, never the device's work; with `nonce` a byte of the check's copy of the seed nonce, below)
+  if (tamper.proof > 0 && (uint32_t)tamper.proof <= B && tamper.nonce <= 0) {
     const uint32_t i = (uint32_t)tamper.proof - 1;
     if ((size_t)tamper.byte < prove_item_len(P, items[i].m)) proofs[(size_t)i * plen + tamper.byte] ^= (uint8_t)tamper.mask;
   }
+  // "prove_check_recovery" = 1: an item's seed nonce travels with it, and its blinding factors are what the recovered masks are
+  // compared with (check_verify).  A call none of whose items carries a nonce is checked exactly as without the option.
+  const bool recovery = ctx->opt.prove_check_recovery > 0;
+  uint8_t nonce_copy[32];  // (test knob "prove_check_tamper_nonce": the check's own copy of one item's nonce, one byte altered)
+  ScopeExit wipe_nonce{[&] { wipe(nonce_copy, sizeof(nonce_copy)); }};
   std::vector<bpp_verify_item> vi(which.size());
+  std::vector<const uint8_t *> blind(which.size(), nullptr);
+  size_t n_nonce = 0;
   for (size_t k = 0; k < which.size(); k++) {
     const bpp_prove_item &it = items[which[k]];
     bpp_verify_item &v = vi[k];
@@ -707,12 +782,24 @@ void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_
     v.m = it.m;
     v.min_values = it.min_values;
     v.min_present = it.min_present;
-    v.seed_nonce32 = nullptr;  // (the blinding factors are the prover's secret; mask recovery is not what is checked)
+    // (without the replay the blinding factors stay the prover's secret and mask recovery is not what is checked)
+    v.seed_nonce32 = recovery ? it.seed_nonce32 : nullptr;
+    if (v.seed_nonce32) {
+      blind[k] = it.blindings32;  // (m = 1: one opening, t blinding factors)
+      n_nonce++;
+      if (tamper.nonce > 0 && tamper.proof == (int)which[k] + 1 && tamper.byte >= 0 && tamper.byte < 32) {
+        memcpy(nonce_copy, it.seed_nonce32, 32);
+        nonce_copy[tamper.byte] ^= (uint8_t)tamper.mask;
+        v.seed_nonce32 = nonce_copy;
+      }
+    }
     v.transcript_state = it.transcript_state;
     v.transcript_label = it.transcript_label;
     v.label_len = it.transcript_label ? it.label_len : 0;
   }
-  std::vector<uint32_t> bad;  // the proofs that fail on their own
+  const std::vector<const uint8_t *> *replay = n_nonce ? &blind : nullptr;
+  std::vector<uint32_t> bad;          // the proofs that fail on their own
+  std::vector<uint8_t> bad_recovery;  // ... on the replay of mask recovery (the verifier accepted them)
   {
     // the check leaves no trace on what the context remembers: its own waits (not the prover's nor the caller's verifications'), the
     // caller's last profile and last error
@@ -730,20 +817,50 @@ void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_
       ctx->check_stats.calls++;
       ctx->check_stats.proofs += which.size();
     }
-    if (check_verify(ctx, params, vi, false, nullptr) == BPP_OK) return;
-    if (remake) ctx->check_stats.batch_failures++;
-    std::vector<int> codes(vi.size(), BPP_OK);
-    if (check_verify(ctx, params, vi, true, &codes) != BPP_OK) {  // the upload refused the batch: one-item verifications
-      for (size_t k = 0; k < vi.size(); k++) codes[k] = check_verify(ctx, params, std::vector<bpp_verify_item>(1, vi[k]), false, nullptr);
+    // (a remake's own replay is counted no more than its proof is)
+    auto replayed = [&](size_t k, bool differs) {
+      if (remake) {
+        ctx->check_replayed++;
+        if (differs) ctx->check_mismatched++;
+      }
+      if (differs) {
+        bad.push_back(which[k]);
+        bad_recovery.push_back(1);
+      }
+    };
+    std::vector<uint8_t> mismatch(vi.size(), 0);
+    if (check_verify(ctx, params, vi, false, nullptr, replay, &mismatch) == BPP_OK) {
+      for (size_t k = 0; replay && k < vi.size(); k++)
+        if (blind[k]) replayed(k, mismatch[k] != 0);
+      if (bad.empty()) return;
+      if (remake) ctx->check_stats.batch_failures++;  // (a recovery that differs is a finding of the checking batch like a rejection)
+    } else {
+      if (remake) ctx->check_stats.batch_failures++;
+      std::vector<int> codes(vi.size(), BPP_OK);
+      if (check_verify(ctx, params, vi, true, &codes, replay, &mismatch) != BPP_OK) {  // the upload refused the batch: one-item verifications
+        for (size_t k = 0; k < vi.size(); k++) {
+          const std::vector<const uint8_t *> one_blind(1, blind[k]);
+          std::vector<uint8_t> one_mismatch(1, 0);
+          codes[k] = check_verify(ctx, params, std::vector<bpp_verify_item>(1, vi[k]), false, nullptr, blind[k] ? &one_blind : nullptr,
+                                  &one_mismatch);
+          mismatch[k] = one_mismatch[0];
+        }
+      }
+      for (size_t k = 0; k < vi.size(); k++) {
+        if (codes[k] != BPP_OK) {
+          bad.push_back(which[k]);
+          bad_recovery.push_back(0);
+        } else if (blind[k]) {  // (a located proof that passes on its own still has its recovery compared)
+          replayed(k, mismatch[k] != 0);
+        }
+      }
     }
-    for (size_t k = 0; k < vi.size(); k++)
-      if (codes[k] != BPP_OK) bad.push_back(which[k]);
   }
   // (a batch rejected while every proof passes on its own: each proof has then passed a complete verification of its own, and
   // none is made again)
   if (bad.empty()) return;
   if (!remake) {
-    for (uint32_t i : bad) status[i] |= PV_STATUS_SELF_CHECK;
+    for (size_t q = 0; q < bad.size(); q++) status[bad[q]] |= PV_STATUS_SELF_CHECK | (bad_recovery[q] ? PV_STATUS_SELF_CHECK_RECOVERY : 0u);
     return;
   }
   kept_proofs.assign(proofs, proofs + (size_t)B * plen);
@@ -771,8 +888,8 @@ void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_
     ctx->check_stats.remade++;
     const int rc = prove_uniform(ctx, params, &items[i], 1, one.data(), len, &got, err, sizeof(err), &st, false, again, false);
     if (rc != BPP_OK) throw ProofErr{rc, err, rc < 0 ? BPP_TIER_ENGINE : BPP_TIER_CONSTRUCTION};
-    if (st != 0 || got != len) {
-      status[i] |= PV_STATUS_SELF_CHECK;
+    if (st != 0 || got != len) {  // (which of the two the remake failed on: its own check says)
+      status[i] |= PV_STATUS_SELF_CHECK | (st & PV_STATUS_SELF_CHECK_RECOVERY);
       ctx->check_stats.failed++;
     } else {
       memcpy(proofs + (size_t)i * plen, one.data(), len);
@@ -796,7 +913,8 @@ extern "C" int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_it
 // its own M), so every proof equals the one a bpp_prove_batch of its class would make.  DESIGN.md 4.2 has the choice of this form.
 namespace {
 
-const char *const kSelfCheckMsg = "the proof failed the engine's self-check: the verifier rejected it and its remake";
+const std::string kSelfCheckMsg = std::string("the proof failed the engine's self-check: ") + kSelfCheckRejectedWhy;
+const std::string kSelfCheckRecoveryMsg = std::string("the proof failed the engine's self-check: ") + kSelfCheckRecoveryWhy;
 
 struct MixedOutcome {
   std::vector<int> code;
@@ -848,6 +966,12 @@ void prove_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, siz
   if (!items || n_items == 0 || !proofs_out || !proof_lens) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "null argument"};
   out.code.assign(n_items, BPP_OK);
   out.msg.assign(n_items, std::string());
+  // (what bpp_prove_item_message looks up: left behind by every mixed call, empty where no self-check failed on mask recovery)
+  std::vector<std::array<uint8_t, 32>> recovery_failed;
+  ScopeExit note{[&] {
+    std::lock_guard<std::mutex> lk(ctx->check_note_mu);
+    ctx->check_recovery_failed.swap(recovery_failed);
+  }};
   std::map<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> classes;  // m -> the items that passed the host checks
   for (size_t i = 0; i < n_items; i++) {
     proof_lens[i] = prove_item_len(P, items[i].m);
@@ -891,7 +1015,12 @@ void prove_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, siz
         out.msg[i] = "Identity element cannot be added to the transcript / zero challenge";
       } else if (status[k] & PV_STATUS_SELF_CHECK) {
         out.code[i] = BPP_ERR_SELF_CHECK;
-        out.msg[i] = kSelfCheckMsg;
+        out.msg[i] = (status[k] & PV_STATUS_SELF_CHECK_RECOVERY) ? kSelfCheckRecoveryMsg : kSelfCheckMsg;
+        if (status[k] & PV_STATUS_SELF_CHECK_RECOVERY) {  // (for bpp_prove_item_message: the item's first commitment, public)
+          std::array<uint8_t, 32> c;
+          memcpy(c.data(), items[i].commitments32, 32);
+          recovery_failed.push_back(c);
+        }
       } else {
         memcpy(proofs_out + (size_t)i * proof_stride, &buf[k * plen], proof_lens[i]);
       }
@@ -919,7 +1048,9 @@ extern "C" int bpp_prove_batch_mixed(bpp_ctx *ctx, uint64_t params, const bpp_pr
 }
 
 // The message that goes with item_status of bpp_prove_batch_mixed: the item's host-side checks run again (no device work), and an
-// item that passes them failed on the device, whose two findings have one message each, or the self-check (BPP_ERR_SELF_CHECK).  Keeps no state: any thread, any time.
+// item that passes them failed on the device, whose two findings have one message each, or the self-check (BPP_ERR_SELF_CHECK).
+// Any thread, any time.  The one thing it looks up: whether the item (by its first commitment) is among those of the context's
+// last mixed call whose self-check failed on the replay of mask recovery -- the code alone does not say which of the two it was.
 extern "C" int bpp_prove_item_message(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item, size_t proof_stride, int status,
                                       char *errbuf, size_t errbuf_len) {
   if (!ctx || !item) return BPP_ERR_BAD_HANDLE;
@@ -931,9 +1062,14 @@ extern "C" int bpp_prove_item_message(bpp_ctx *ctx, uint64_t params, const bpp_p
     set_err(errbuf, errbuf_len, e.msg);
     return e.code;
   }
+  bool recovery = false;
+  if (status == BPP_ERR_SELF_CHECK && item->seed_nonce32) {
+    std::lock_guard<std::mutex> lk(ctx->check_note_mu);
+    for (const auto &c : ctx->check_recovery_failed) recovery = recovery || memcmp(c.data(), item->commitments32, 32) == 0;
+  }
   set_err(errbuf, errbuf_len, status == BPP_ERR_INVALID_ARGUMENT ? "Witness opening is invalid!"
                               : status == BPP_ERR_VERIFICATION_FAILED ? "Identity element cannot be added to the transcript / zero challenge"
-                              : status == BPP_ERR_SELF_CHECK ? kSelfCheckMsg
+                              : status == BPP_ERR_SELF_CHECK ? (recovery ? kSelfCheckRecoveryMsg : kSelfCheckMsg)
                               : "");
   return status;
 }

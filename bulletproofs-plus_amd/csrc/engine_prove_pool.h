@@ -204,6 +204,21 @@ int bpp_prove_pool_check_stats(bpp_prove_pool *p, struct bpp_prove_check_stats *
   return BPP_OK;
 }
 
+int bpp_prove_pool_check_recovery_stats(bpp_prove_pool *p, uint64_t *replayed, uint64_t *mismatched) {
+  if (!p) return BPP_ERR_BAD_HANDLE;
+  uint64_t r = 0, m = 0;
+  for (auto &L : p->lanes) {
+    uint64_t lr = 0, lm = 0;
+    const int rc = bpp_prove_check_recovery_stats(L.ctx, &lr, &lm);
+    if (rc != BPP_OK) return rc;
+    r += lr;
+    m += lm;
+  }
+  if (replayed) *replayed = r;
+  if (mismatched) *mismatched = m;
+  return BPP_OK;
+}
+
 void bpp_prove_pool_destroy(bpp_prove_pool *p) {
   if (!p) return;
   {

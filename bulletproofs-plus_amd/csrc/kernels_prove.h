@@ -1427,6 +1427,26 @@ __global__ void kp_check_commitments(const uint8_t *__restrict__ bytes, const Pr
   if (diff) ps[p].status |= PV_STATUS_COMMIT_MISMATCH;
 }
 
+// The self-check's replay of mask recovery ("prove_check_recovery" = 1, engine_prove.h: check_verify): the t masks the verifier
+// recovered for proof idx[q] of its batch (k_masks: masks[B][t][32], canonical bytes) against the t blinding factors of that item's
+// one opening (blind[n][t][32], canonical as the prover's host checks left them).  One word per compared proof, 0 = equal: all
+// 8 t words are XORed and ORed together, no exit and no branch depends on them.  A place outside the batch reads nothing and
+// reports a difference.
+__global__ void kp_check_recovery(const uint8_t *__restrict__ masks, const uint8_t *__restrict__ blind, const uint32_t *__restrict__ idx,
+                                  uint32_t n, uint32_t t, uint32_t B, uint32_t *__restrict__ words) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n) return;
+  const uint32_t p = idx[q];
+  if (p >= B) {
+    words[q] = 0xffffffffu;
+    return;
+  }
+  const uint32_t *a = (const uint32_t *)(masks + (size_t)p * t * 32), *b = (const uint32_t *)(blind + (size_t)q * t * 32);
+  uint32_t diff = 0;
+  for (uint32_t i = 0; i < 8 * t; i++) diff |= a[i] ^ b[i];
+  words[q] = diff;
+}
+
 // term lists for the commitment check: output (p, j) = v_j H + sum_k r_{j,k} G_k
 __global__ void kp_commit_terms(const uint8_t *__restrict__ bytes, const ProveDesc *__restrict__ desc, uint32_t t, uint32_t n_gen,
                                 uint32_t B, uint32_t m, uint32_t stride, sc *__restrict__ ts, uint32_t *__restrict__ tg,

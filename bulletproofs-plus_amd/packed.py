@@ -223,6 +223,12 @@ class ProvePool:
         api._check(self.engine.lib.bpp_prove_pool_check_stats(self.handle, byref(s)), None)
         return {n: int(getattr(s, n)) for n, _ in _lib.ProveCheckStats._fields_}
 
+    def check_recovery_stats(self):
+        """bpp_prove_pool_check_recovery_stats: Engine.prove_check_recovery_stats summed over the lanes"""
+        replayed, mismatched = c_uint64(), c_uint64()
+        api._check(self.engine.lib.bpp_prove_pool_check_recovery_stats(self.handle, byref(replayed), byref(mismatched)), None)
+        return {"replayed": int(replayed.value), "mismatched": int(mismatched.value)}
+
     def close(self):
         if self.handle:
             self.engine.lib.bpp_prove_pool_destroy(self.handle)

@@ -93,13 +93,20 @@ const char *bpp_ctx_last_error(bpp_ctx *ctx);
  * looks at an event, 1-2 % of a core; -1 = the engine's rule: naps for calls of 4096 proofs and more), "prove_check" (1: every proof
  * bpp_prove_batch / bpp_prove_batch_mixed make on this context -- and a prove pool made from it -- is verified on this context before
  * any byte of it is returned; a rejected proof is made again once, and one rejected again fails with BPP_ERR_SELF_CHECK; see
- * bpp_prove_check_stats.  0 and -1 = off, the engine's rule).  The environment variables BPP_<NAME> give
+ * bpp_prove_check_stats.  0 and -1 = off, the engine's rule), "prove_check_recovery" (1: a checked call also replays mask
+ * recovery -- RecoverAndVerify, src/range_proof.rs:941-969 -- for its items that carry a seed nonce and compares the recovered
+ * masks with the witness's blinding factors on the device: a proof that verifies but whose mask its owner could not get back is
+ * made again once and then fails with BPP_ERR_SELF_CHECK like a rejected one; see bpp_prove_check_recovery_stats.  Acts only
+ * where "prove_check" = 1; a call none of whose items carries a nonce is checked exactly as without it.  0 and -1 = off).
+ * The environment variables BPP_<NAME> give
  * the initial values and are read ONCE, when the context is created: no verification path calls getenv.
  * Test knobs of "prove_check", settable here only (no environment variable, not copied to a prove pool's lanes), acting on the NEXT
  * prove call of the context and then reset: "prove_check_tamper" = i + 1 XORs "prove_check_tamper_xor" (default 0x01) into byte
  * "prove_check_tamper_byte" (default 1) of proof i in the page-locked host copy of the call's proofs, after the device wrote them and
  * before they are checked (i counts the call's items as the caller passed them); "prove_check_tamper_times" = 1 (default) alters the
- * first attempt only, 2 the remake of that proof as well.  Checked calls only. */
+ * first attempt only, 2 the remake of that proof as well.  "prove_check_tamper_nonce" = 1: the byte ("prove_check_tamper_byte"
+ * 0..31) is altered in the check's own copy of item i's seed nonce instead of in the proof ("prove_check_recovery" = 1: the replay
+ * then disagrees with a proof that is right; an item without a nonce is left alone).  Checked calls only. */
 int bpp_ctx_set_option(bpp_ctx *ctx, const char *name, int value);
 /* verifications of this context whose weights were made on the device ("chain" 1 or 2), and how many of those ran once more
  * with everything on the host because a weight came out zero */
@@ -453,7 +460,10 @@ int bpp_prove_batch(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, 
 int bpp_prove_batch_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
                           size_t proof_stride, size_t *proof_lens, int *item_status, char *errbuf, size_t errbuf_len);
 /* the message that goes with item_status[i] = `status` of a bpp_prove_batch_mixed call on `item` (same params and proof_stride):
- * what a one-item bpp_prove_batch would have written to errbuf.  Host-side work only, no state kept; returns the item's code. */
+ * what a one-item bpp_prove_batch would have written to errbuf.  Host-side work only; returns the item's code.  For
+ * BPP_ERR_SELF_CHECK the text says whether the verifier rejected the proof or mask recovery did not return the witness's blinding
+ * factors ("prove_check_recovery"): that is looked up in what ctx's LAST bpp_prove_batch_mixed left behind (the item is known by its
+ * first commitment), so ask before the next mixed call on that context. */
 int bpp_prove_item_message(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item, size_t proof_stride, int status, char *errbuf,
                            size_t errbuf_len);
 /* bpp_prove_pool: many host threads, each with a few proofs per call (one output of a wallet service, say).  A call of one proof
@@ -484,6 +494,12 @@ struct bpp_prove_check_stats {
 };
 int bpp_prove_check_stats(bpp_ctx *ctx, struct bpp_prove_check_stats *out);
 int bpp_prove_pool_check_stats(bpp_prove_pool *p, struct bpp_prove_check_stats *out);
+/* "prove_check_recovery" = 1: proofs with a seed nonce whose mask recovery a call's first check replayed (those the verifier
+ * accepted), and how many of them did not return the witness's blinding factors.  A call whose only finding is such a mismatch
+ * counts in batch_failures above, its proof in remade and, if its remake's replay differs again, in failed; a remake's own replay
+ * is not counted here.  Either pointer may be NULL.  The pool's form sums its lanes. */
+int bpp_prove_check_recovery_stats(bpp_ctx *ctx, uint64_t *replayed, uint64_t *mismatched);
+int bpp_prove_pool_check_recovery_stats(bpp_prove_pool *p, uint64_t *replayed, uint64_t *mismatched);
 
 /* ---- parity / diagnostics: intermediates of the last verify on `batch`, for differential tests ---- */
 #define BPP_TRACE_CHALLENGES 1     /* per proof (rmax+3) x 32: y, z, e_0.., e_final (canonical), rmax = bpp_batch_shape's max_rounds
@@ -547,7 +563,9 @@ int bpp_batch_secret_bytes(bpp_ctx *ctx, uint64_t batch, uint64_t *nonzero);
  * blinding-factor accumulators, the transcript-RNG states keyed with the witness -- and its page-locked staging on the way IN
  * (the witness bytes; on the way out only proofs and status words travel), which bpp_prove_batch wipes on EVERY exit path (the reference
  * keeps all of it in Zeroizing<>: src/range_proof.rs:300-301,325,438-464,542-571).  *examined = bytes looked at (0 before the
- * first prove call), *nonzero = how many of them are not zero: must read 0 between calls.  Not reachable from the host and
+ * first prove call), *nonzero = how many of them are not zero: must read 0 between calls.  The self-check's own buffers are
+ * looked at as well ("prove_check_recovery"): its staging of blinding factors, page-locked and on the device, and the seed
+ * nonces and recovered masks of its verification batch.  Not reachable from the host and
  * therefore not counted here: the LDS of the prover's kernels (generator states keyed with the witness, raw draws, digits of
  * witness-derived scalars) -- every such kernel clears its LDS as its last statement (kernels_prove.h: lds_wipe; ct.h). */
 int bpp_prove_secret_bytes(bpp_ctx *ctx, uint64_t *examined, uint64_t *nonzero);

@@ -293,6 +293,8 @@ extern "C" {
     pub fn bpp_prove_pool_destroy(p: *mut bpp_prove_pool);
     pub fn bpp_prove_check_stats(ctx: *mut bpp_ctx, out: *mut bpp_prove_check_stats) -> c_int;
     pub fn bpp_prove_pool_check_stats(p: *mut bpp_prove_pool, out: *mut bpp_prove_check_stats) -> c_int;
+    pub fn bpp_prove_check_recovery_stats(ctx: *mut bpp_ctx, replayed: *mut u64, mismatched: *mut u64) -> c_int;
+    pub fn bpp_prove_pool_check_recovery_stats(p: *mut bpp_prove_pool, replayed: *mut u64, mismatched: *mut u64) -> c_int;
     // diagnostics
     pub fn bpp_batch_trace(ctx: *mut bpp_ctx, batch: u64, what: c_int, out: *mut u8, out_len: usize, written: *mut usize) -> c_int;
     pub fn bpp_batch_shape(ctx: *mut bpp_ctx, batch: u64, n_items: *mut u32, max_rounds: *mut u32, max_mn: *mut u32, total_dyn: *mut u32,

@@ -272,6 +272,15 @@ impl Engine {
         Ok(s)
     }
 
+    /// "prove_check_recovery" = 1 (with "prove_check" = 1): (proofs with a seed nonce whose mask recovery the self-check replayed,
+    /// those whose recovered masks were not the witness's blinding factors)
+    pub fn prove_check_recovery_stats(&self) -> Result<(u64, u64), GpuError> {
+        let (mut replayed, mut mismatched) = (0u64, 0u64);
+        map_rc(unsafe { ffi::bpp_prove_check_recovery_stats(self.ctx, &mut replayed, &mut mismatched) },
+               String::from("bpp_prove_check_recovery_stats"))?;
+        Ok((replayed, mismatched))
+    }
+
     /// `RangeProof::verify_batch`: every `chunk` consecutive items are one reference batch (256 = MAX_RANGE_PROOF_BATCH_SIZE,
     /// 0 = the whole input).  Returns per item `Some(mask blindings, t x 32 bytes)` or `None`.
     pub fn verify_batch(&self, params: &Params, items: &[VerifyItem<'_>], action: Action, chunk: usize)
@@ -703,6 +712,13 @@ impl ProvePool {
         let mut s = ffi::bpp_prove_check_stats::default();
         map_rc(unsafe { ffi::bpp_prove_pool_check_stats(self.raw, &mut s) }, String::from("bpp_prove_pool_check_stats"))?;
         Ok(s)
+    }
+    /// `Engine::prove_check_recovery_stats` summed over the lanes: (replayed, mismatched)
+    pub fn check_recovery_stats(&self) -> Result<(u64, u64), GpuError> {
+        let (mut replayed, mut mismatched) = (0u64, 0u64);
+        map_rc(unsafe { ffi::bpp_prove_pool_check_recovery_stats(self.raw, &mut replayed, &mut mismatched) },
+               String::from("bpp_prove_pool_check_recovery_stats"))?;
+        Ok((replayed, mismatched))
     }
     /// (callers served in pooled calls, engine calls, calls that ran alone, largest pool in calls, in proofs)
     pub fn stats(&self) -> (u64, u64, u64, u32, u32) {

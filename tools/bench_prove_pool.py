@@ -9,6 +9,8 @@ One JSON line per (setup, S, t): proofs/s and p50 / p99 call latency.
                class, one after the other (median of --reps calls each, t = 1 and 3)
   --check      every context (the solo ones, the pool's lanes) verifies each proof before returning it ("prove_check" = 1); the
                pooled lines add the lanes' check counters
+  --check-recovery   with --check: mask recovery replayed for the proofs that carry a seed nonce ("prove_check_recovery" = 1)
+  --nonces     the rate runs' one-proof calls are all m = 1 with a seed nonce each (otherwise only every third is)
   --soak SEC   instead: SEC seconds of 16 threads through the pool, about 5 % of the calls invalid (one item short of external
                randomness); every proof is compared with the bytes of a one-item bpp_prove_batch of the same item on the same GPU
                (not with the CPU oracle: the tests pin both paths to it), every error with that of a call of its own
@@ -28,12 +30,12 @@ sys.path.insert(0, ROOT)
 LABEL = b"bench_prove_pool"
 
 
-def corpus(bpp, params, n, t, count, seed):
-    """count (transcript, statement, witness, rng) of m = 1, 2, 4 in turn, seed nonces on the m = 1 ones"""
+def corpus(bpp, params, n, t, count, seed, nonces=False):
+    """count (transcript, statement, witness, rng) of m = 1, 2, 4 in turn, seed nonces on the m = 1 ones (nonces: all m = 1)"""
     r = random.Random(seed)
     out = []
     for i in range(count):
-        m = (1, 2, 4)[i % 3]
+        m = 1 if nonces else (1, 2, 4)[i % 3]
         rounds = (n * m).bit_length() - 1
         vals = [r.getrandbits(n - 1) for _ in range(m)]
         blinds = [[(r.getrandbits(250) + 1).to_bytes(32, "little") for _ in range(t)] for _ in range(m)]
@@ -90,8 +92,10 @@ def bench_rates(bpp, packed, args):
         eng0 = bpp.Engine(0)
         if args.check:
             eng0.set_option("prove_check", 1)  # (before the pools are made: their lanes copy it)
+        if args.check_recovery:
+            eng0.set_option("prove_check_recovery", 1)
         p0 = bpp.RangeParameters.init(64, 4, bpp.create_pedersen_gens_with_extension_degree(t), engine=eng0)
-        items = [marshal(bpp, [x]) for x in corpus(bpp, p0, 64, t, 48, t)]
+        items = [marshal(bpp, [x]) for x in corpus(bpp, p0, 64, t, 48, t, args.nonces)]
         solo_call(eng0, p0, items[0])  # fixed-base table, arena
         for S in args.threads:
             for setup in ("solo", "pooled"):
@@ -99,6 +103,8 @@ def bench_rates(bpp, packed, args):
                     engs = [bpp.Engine(0) for _ in range(S)]
                     for e in engs if args.check else ():
                         e.set_option("prove_check", 1)
+                    for e in engs if args.check_recovery else ():
+                        e.set_option("prove_check_recovery", 1)
                     ps = [p0.share(e) for e in engs]
                     for k in range(S):
                         solo_call(engs[k], ps[k], items[k % len(items)])
@@ -119,9 +125,10 @@ def bench_rates(bpp, packed, args):
                             pool.prove_marshalled(items[(k * 7 + c) % len(items)])
                             lat.append(time.perf_counter() - a)
                 el, lat = run_threads(S, fn)
-                rec = {"metric": "one-proof prove calls, m in {1,2,4}", "setup": setup, "threads": S, "calls_per_thread": args.calls,
+                rec = {"metric": "one-proof prove calls, " + ("m = 1 with seed nonces" if args.nonces else "m in {1,2,4}"), "setup": setup, "threads": S, "calls_per_thread": args.calls,
                        "bit_length": 64, "extension_degree": t, "proofs_per_s": S * args.calls / el,
-                       "p50_ms": 1e3 * pct(lat, 0.5), "p99_ms": 1e3 * pct(lat, 0.99), "prove_check": 1 if args.check else 0}
+                       "p50_ms": 1e3 * pct(lat, 0.5), "p99_ms": 1e3 * pct(lat, 0.99), "prove_check": 1 if args.check else 0,
+                       "prove_check_recovery": 1 if args.check_recovery else 0}
                 if setup == "solo":
                     for p in ps:
                         p.close()
@@ -131,6 +138,8 @@ def bench_rates(bpp, packed, args):
                     rec.update(pool.stats(), lanes=args.lanes, max_wait_us=args.max_wait_us)
                     if args.check:
                         rec["check"] = pool.check_stats()
+                    if args.check_recovery:
+                        rec["check_recovery"] = pool.check_recovery_stats()
                     pool.close()
                 print(json.dumps(rec), flush=True)
         p0.close()
@@ -247,6 +256,8 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--soak", type=float, default=0)
     ap.add_argument("--check", action="store_true", help='"prove_check" = 1 on every context of the rate runs')
+    ap.add_argument("--check-recovery", action="store_true", help='"prove_check_recovery" = 1 on every context of the rate runs')
+    ap.add_argument("--nonces", action="store_true", help="rate runs: every call one m = 1 proof with a seed nonce")
     args = ap.parse_args()
     args.threads = [int(x) for x in args.threads.split(",")]
     args.t = [int(x) for x in args.t.split(",")]

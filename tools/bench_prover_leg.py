@@ -2,7 +2,10 @@
 """The prover leg of bench.py alone (configs[4]: 1024 x aggregation-4, extension degree 3): proofs/s one call at a time over 8
 calls, k_fb_msm's summed event time and rate per call.  One line.
 
-  --check   every proof verified before it is returned (the context's "prove_check" = 1); the line adds the check's counters"""
+  --check            every proof verified before it is returned (the context's "prove_check" = 1); the line adds the check's counters
+  --check-recovery   with --check: mask recovery replayed for the proofs that carry a seed nonce ("prove_check_recovery" = 1)
+  --nonces           instead of configs[4]: 1024 proofs of n = 64, m = 1, extension degree --t (default 3), a seeded nonce on each
+                     (an aggregated statement cannot carry one)"""
 import argparse
 import importlib
 import json
@@ -18,6 +21,9 @@ sys.path.insert(0, ROOT)
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--check", action="store_true", help='"prove_check" = 1 on the context')
+    ap.add_argument("--check-recovery", action="store_true", help='"prove_check_recovery" = 1 on the context')
+    ap.add_argument("--nonces", action="store_true", help="1024 x (n = 64, m = 1) with a seed nonce each instead of configs[4]")
+    ap.add_argument("--t", type=int, default=3, help="extension degree of the --nonces proofs")
     args = ap.parse_args()
     import numpy as np
     import bench
@@ -27,20 +33,29 @@ def main():
     eng.profile(True)
     if args.check:
         eng.set_option("prove_check", 1)
-    p5 = bpp.RangeParameters.init(64, 4, bpp.create_pedersen_gens_with_extension_degree(3), engine=eng)
-    d5 = bench.make_inputs(np, packed, p5, 1024, seed=8675309 + 5)
+    if args.check_recovery:
+        eng.set_option("prove_check_recovery", 1)
+    if args.nonces:
+        p5 = bpp.RangeParameters.init(64, 1, bpp.create_pedersen_gens_with_extension_degree(args.t), engine=eng)
+    else:
+        p5 = bpp.RangeParameters.init(64, 4, bpp.create_pedersen_gens_with_extension_degree(3), engine=eng)
+    d5 = bench.make_inputs(np, packed, p5, 1024, seed=8675309 + 5)  # (seed nonces iff m = 1)
     iters = int(os.environ.get("PROVER_ITERS", "8"))
     for _ in range(2):
-        packed.prove(p5, d5["values"], d5["blindings"], d5["commitments"], d5["min_values"], d5["min_present"], None, bench.LABEL, d5["ext"])
+        packed.prove(p5, d5["values"], d5["blindings"], d5["commitments"], d5["min_values"], d5["min_present"], d5["seeds"], bench.LABEL, d5["ext"])
     t0 = time.perf_counter()
     for _ in range(iters):
-        out = packed.prove(p5, d5["values"], d5["blindings"], d5["commitments"], d5["min_values"], d5["min_present"], None, bench.LABEL, d5["ext"])
+        out = packed.prove(p5, d5["values"], d5["blindings"], d5["commitments"], d5["min_values"], d5["min_present"], d5["seeds"], bench.LABEL, d5["ext"])
     el = time.perf_counter() - t0
     pp = eng.last_prove_profile()
     rec = {"proofs_per_s": round(1024 * iters / el), "ms_per_call": round(1e3 * el / iters, 3), "fb_msm_ms": round(pp["fb_msm_ms"], 3),
            "fb_G_adds_per_s": round(pp["fb_terms"] * pp["fb_windows"] / (pp["fb_msm_ms"] * 1e-3) / 1e9, 2), "engine_total_ms": round(pp["total_ms"], 3)}
     if args.check:
         rec["check"] = eng.prove_check_stats()
+    if args.check_recovery:
+        rec["check_recovery"] = eng.prove_check_recovery_stats()
+    if args.nonces:
+        rec.update(nonces=1, extension_degree=args.t)
     print(json.dumps(rec))
     p5.close()
     eng.close()

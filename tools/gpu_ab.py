@@ -128,6 +128,8 @@ def main():
                 print(text, flush=True)
                 f.write(text + "\n")
                 f.flush()
+                if r.returncode in (124, 134, 137, 139, -6, -9, -11):  # an abort, a fault or a time limit: nothing further is started
+                    raise SystemExit(1)
 
 
 if __name__ == "__main__":
