@@ -146,6 +146,13 @@ SYMBOLS = [
     ("bpp_prove_batch_mixed", c_int, [c_void_p, c_uint64, POINTER(ProveItem), c_size_t, c_void_p, c_size_t, POINTER(c_size_t),
                                       POINTER(c_int), c_void_p, c_size_t]),
     ("bpp_prove_item_message", c_int, [c_void_p, c_uint64, POINTER(ProveItem), c_size_t, c_int, c_void_p, c_size_t]),
+    ("bpp_prove_openings", c_int, [c_void_p, c_uint64, POINTER(ProveItem), c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
+                                   POINTER(c_size_t), POINTER(c_int), c_void_p, c_size_t]),
+    ("bpp_prove_openings_item_message", c_int, [c_void_p, c_uint64, POINTER(ProveItem), c_void_p, c_size_t, c_size_t, c_int, c_void_p,
+                                                c_size_t]),
+    ("bpp_prove_pool_openings", c_int, [c_void_p, POINTER(ProveItem), c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
+                                        POINTER(c_size_t), c_void_p, c_size_t]),
+    ("bpp_prove_pool_openings_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     ("bpp_prove_pool_create", c_int, [c_void_p, c_uint64, c_uint32, c_uint32, c_uint32, POINTER(c_void_p)]),
     ("bpp_prove_pool_prove", c_int, [c_void_p, POINTER(ProveItem), c_size_t, c_void_p, c_size_t, POINTER(c_size_t), c_void_p, c_size_t]),
     ("bpp_prove_pool_set_limits", c_int, [c_void_p, c_uint32, c_uint32]),

@@ -604,6 +604,76 @@ class RangeProof:
         return [raw[i * stride:i * stride + lens[i]] for i in range(n)], codes, msgs
 
     @staticmethod
+    def _openings_marshal(transcripts, witnesses, minimum_value_promises, seed_nonces, rng_bytes, params):
+        """the bpp_prove_item array of a prove_openings call: _prove_marshal's, every item without commitments (commitments32 NULL)"""
+        if not witnesses or not (len(transcripts) == len(witnesses) == len(minimum_value_promises) == len(seed_nonces) == len(rng_bytes)):
+            raise ProofError(ProofErrorKind.InvalidArgument, "Range statements, witnesses, transcripts length mismatch")
+        # (placeholder statements carry the promises and the nonce through RangeStatement.init's own checks; their commitments are
+        # never read: the pointer is cleared below)
+        sts = [RangeStatement.init(params, [bytes(32)] * len(w.openings), list(mins), sn)
+               for w, mins, sn in zip(witnesses, minimum_value_promises, seed_nonces)]
+        params, items, n, keep = RangeProof._prove_marshal(transcripts, sts, witnesses, rng_bytes)
+        for i in range(n):
+            items[i].commitments32 = None
+        return params, items, n, keep
+
+    @staticmethod
+    def prove_openings(transcripts, witnesses, minimum_value_promises, seed_nonces, rng_bytes, params):
+        """Prove from the openings alone (bpp_prove_openings): n x (commit every opening, RangeStatement::init over the commitments,
+        RangeProof::prove_with_rng) of any aggregation factors in ONE engine call, the commitments made where the prover's witness
+        check computes them anyway.  minimum_value_promises[i]: one Option<u64> per opening of witnesses[i]; seed_nonces[i]: 32
+        bytes or None (only with one opening).  Returns (statements, proofs), one entry each per item: the RangeStatement built
+        from the commitments the engine returned and its RangeProof, or -- in both lists -- the ProofError / EngineError
+        (EngineError.SELF_CHECK) of an item that failed, which never stops the others."""
+        n = len(witnesses)
+        sts, res = [None] * n, [None] * n
+        keep = []
+        for i in range(n):
+            try:
+                RangeProof._openings_marshal([transcripts[i]], [witnesses[i]], [minimum_value_promises[i]], [seed_nonces[i]], [rng_bytes[i]],
+                                             params)
+                keep.append(i)
+            except ProofError as e:
+                sts[i] = res[i] = e
+        if not keep:
+            return sts, res
+        pick = lambda a: [a[i] for i in keep]  # noqa: E731
+        _p, items, cnt, _keep = RangeProof._openings_marshal(pick(transcripts), pick(witnesses), pick(minimum_value_promises), pick(seed_nonces),
+                                                            pick(rng_bytes), params)
+        eng = params.engine
+        stride = 1 + 32 * (6 + 5 + 2 * 12)
+        cstride = 32 * max(len(witnesses[i].openings) for i in keep)
+        out = (ctypes.c_uint8 * (stride * cnt))()
+        comms = (ctypes.c_uint8 * (cstride * cnt))()
+        lens = (c_size_t * cnt)()
+        status = (ctypes.c_int * cnt)()
+        err = ctypes.create_string_buffer(256)
+        rc = eng.lib.bpp_prove_openings(eng.ctx, params.handle, items, cnt, comms, cstride, out, stride, lens, status, err, 256)
+        codes = [status[k] for k in range(cnt)]
+        faults = [c for c in [rc] + codes if c < 0 and c != EngineError.SELF_CHECK]
+        if faults:
+            _check(min(faults), eng.ctx, err)
+        raw, craw = bytes(out), bytes(comms)
+        for k, i in enumerate(keep):
+            m = len(witnesses[i].openings)
+            if codes[k] == 0:
+                cs = [craw[k * cstride + 32 * j:k * cstride + 32 * j + 32] for j in range(m)]
+                sts[i] = RangeStatement.init(params, cs, list(minimum_value_promises[i]), seed_nonces[i])
+                res[i] = RangeProof.from_bytes(raw[k * stride:k * stride + lens[k]])
+                continue
+            first = None
+            if codes[k] == EngineError.SELF_CHECK and seed_nonces[i] is not None:
+                # (what the engine's note of a failed mask-recovery replay knows the item by: the commitment it made for it)
+                first = _buf(params.commit(witnesses[i].openings[0].v, witnesses[i].openings[0].r))
+            eng.lib.bpp_prove_openings_item_message(eng.ctx, params.handle, ctypes.byref(items[k]), first, cstride, stride, codes[k], err, 256)
+            msg = err.value.decode(errors="replace")
+            if codes[k] == EngineError.SELF_CHECK:
+                sts[i] = res[i] = EngineError("bpp engine error %d: %s" % (codes[k], msg), codes[k])
+            else:
+                sts[i] = res[i] = ProofError(codes[k], msg)
+        return sts, res
+
+    @staticmethod
     def prove_with_rng(transcript, statement, witness, rng):
         """RangeProof::prove_with_rng; `rng` = object with fill_bytes(n) (the external RNG) or the bytes themselves"""
         need = 32 * (RangeProof.rounds_for(statement) + 3)

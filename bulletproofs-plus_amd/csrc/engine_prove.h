@@ -9,7 +9,7 @@ namespace {
 size_t prove_item_len(const Params &P, uint32_t m);
 void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_prove_item *items, uint32_t B, size_t plen, uint8_t *&proofs,
                       uint32_t *&status, const bpp_ctx::CheckTamper &tamper, bool remake, std::vector<uint8_t> &kept_proofs,
-                      std::vector<uint32_t> &kept_status);
+                      std::vector<uint32_t> &kept_status, uint8_t *made32, size_t made_stride);
 // what follows "proof %u failed the engine's self-check: " / "the proof failed the engine's self-check: "
 const char *const kSelfCheckRejectedWhy = "the verifier rejected it and its remake";
 const char *const kSelfCheckRecoveryWhy =
@@ -28,9 +28,14 @@ const char *const kSelfCheckRecoveryWhy =
 // and fixed-base MSM cover only that prefix.  Every proof reaches the final step in the same launch.
 // "prove_check" = 1: the proofs are verified before any of them is copied out (prove_self_check; `tamper`: the test knobs taken by
 // the call's entry point, proof = index + 1 in `items`; remake = false: the call IS a remake, whose failure is final).
+// made32 != nullptr (bpp_prove_openings): an item may come without commitments (commitments32 == NULL); the ones the witness check
+// computes are then its statement's (ProveDesc::flags bit 1, kp_adopt_commitments in front of kp_init).  What the check computed
+// for EVERY item of the call comes back at made32 + i * 32 * items[0].m: for an item whose status word is 0 those are its
+// statement's commitments, made or brought.  A sub-batch without such an item -- every call with made32 == nullptr -- is enqueued
+// exactly as before.
 int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
                   size_t proof_stride, size_t *proof_len, char *errbuf, size_t errbuf_len, uint32_t *dev_status, bool mixed = false,
-                  const bpp_ctx::CheckTamper &tamper = bpp_ctx::CheckTamper{}, bool remake = true) {
+                  const bpp_ctx::CheckTamper &tamper = bpp_ctx::CheckTamper{}, bool remake = true, uint8_t *made32 = nullptr) {
   try {
     const std::shared_ptr<Params> Pp = params_registry().get(params);
     if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
@@ -90,7 +95,7 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
       if (mixed && (it.m == 0 || (it.m & (it.m - 1)) || it.m > m || (i && it.m > items[i - 1].m)))
         throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "mixed prove batch: items must be sorted by aggregation factor"};
       const uint32_t mi = mixed ? it.m : m, rounds_i = mixed ? rounds_of(mi) : rounds, ext_len_i = 32 * (rounds_i + 3);
-      if (!it.values || !it.blindings32 || !it.commitments32 || !it.rng_bytes || (!it.min_values && it.min_present))
+      if (!it.values || !it.blindings32 || (!it.commitments32 && !made32) || !it.rng_bytes || (!it.min_values && it.min_present))
         throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "null witness / statement field"};
       if (it.seed_nonce32 && mi > 1)
         throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Mask recovery is not supported with an aggregated statement"};
@@ -121,11 +126,12 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
         bytes.insert(bytes.end(), it.blindings32 + (size_t)j * t * 32, it.blindings32 + (size_t)(j + 1) * t * 32);
       }
       d.commit_off = (uint32_t)bytes.size();
-      bytes.insert(bytes.end(), it.commitments32, it.commitments32 + (size_t)mi * 32);
+      if (it.commitments32) bytes.insert(bytes.end(), it.commitments32, it.commitments32 + (size_t)mi * 32);
+      else bytes.insert(bytes.end(), (size_t)mi * 32, 0);  // (to be made: kp_adopt_commitments writes them here)
       d.ext_off = (uint32_t)bytes.size();
       bytes.insert(bytes.end(), it.rng_bytes, it.rng_bytes + ext_len_i);
       d.seed_off = (uint32_t)bytes.size();
-      d.flags = it.seed_nonce32 ? 1u : 0u;
+      d.flags = (it.seed_nonce32 ? 1u : 0u) | (it.commitments32 ? 0u : PV_FLAG_MAKE_COMMITMENTS);
       if (it.seed_nonce32) bytes.insert(bytes.end(), it.seed_nonce32, it.seed_nonce32 + 32);
       else bytes.insert(bytes.end(), 32, 0);
       // the same transcript source as the previous item (the common case: one label for the whole call): same id, no key, no lookup
@@ -370,6 +376,10 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
       }
     };
     carve();
+    // the sub-batches that hold an item whose commitments are to be made: their kp_init waits for the witness check (below)
+    std::vector<uint8_t> adopts(n_sub, 0);
+    for (uint32_t q = 0; q < n_sub; q++)
+      for (uint32_t i = 0; i < subs[q].nb; i++) adopts[q] |= (desc[subs[q].lo + i].flags & PV_FLAG_MAKE_COMMITMENTS) ? 1 : 0;
     {
       // a fresh arena starts out zero as a whole: the alignment gaps between the sub-batches' ranges and the slack at its end
       // are written by nothing and wiped by nothing, and what hipMalloc hands out is not zero -- bpp_prove_secret_bytes (and
@@ -396,7 +406,8 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
     // page-locked staging so that no copy stalls the enqueue of the next sub-batch
     const size_t in_need = bytes.size() + states.size() + minpres.size() + minvals.size() * 8 + (size_t)B * sizeof(ProveDesc) + 64;
     ctx->prove_pin_in.resize(in_need);
-    ctx->prove_pin_out.resize((size_t)B * plen + (size_t)B * sizeof(uint32_t) + 64);
+    // (on the way out: proofs, status words and -- made32 -- the commitments the witness check computed: nothing secret)
+    ctx->prove_pin_out.resize((size_t)B * plen + (size_t)B * sizeof(uint32_t) + 64 + (made32 ? (size_t)B * m * 32 : 0));
     uint8_t *pin = ctx->prove_pin_in.p;
     uint8_t *pin_bytes = pin;
     memcpy(pin_bytes, bytes.data(), bytes.size());
@@ -410,6 +421,7 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
     memcpy(pin_desc, desc.data(), (size_t)B * sizeof(ProveDesc));
     uint8_t *pin_proofs = ctx->prove_pin_out.p;
     uint32_t *pin_status = (uint32_t *)(pin_proofs + (((size_t)B * plen + 15) & ~(size_t)15));
+    uint8_t *pin_made = (uint8_t *)pin_status + (((size_t)B * sizeof(uint32_t) + 15) & ~(size_t)15);
 
     const dim3 b64(64);
     // profiling: an event pair around every k_fb_msm launch (the prover's dominant kernel), summed after the call
@@ -457,6 +469,13 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
       }
       hipLaunchKernelGGL(k_compress_ge, dim3(cdiv(nb * m, 64)), b64, 0, sx, u.d_ge, nb * m, u.d_commit32);
       HIP_CHECK(hipEventRecord(ctx->prove_aux_events[4 * q + 1], sx));
+      if (adopts[q]) {
+        // bpp_prove_openings: the transcript starts with the statement's commitments, and for a flagged proof those are what the
+        // check has just computed: here kp_init waits for the check instead of running beside it.  (The first round's MSM waits for
+        // the same event again, as in every call: a wait for an event that has fired.)
+        HIP_CHECK(hipStreamWaitEvent(s, ctx->prove_aux_events[4 * q + 1], 0));
+        hipLaunchKernelGGL(kp_adopt_commitments, dim3(cdiv(nb * m, 64)), b64, 0, s, u.d_bytes, u.d_desc, u.d_commit32, nb, m);
+      }
       hipLaunchKernelGGL(kp_init, dim3(nb), b64, 0, s, u.d_bytes, u.d_desc, u.d_minvals, u.d_states, P.d_hg32.p, n, t, nb, u.d_ps);
       hipLaunchKernelGGL(kp_A, dim3(nb), b64, 0, s, u.d_bytes, u.d_desc, u.d_minvals, u.d_minpres, P.table.p, P.fb_table.p, P.fb_geo, n_gen, n,
                          t, u.d_ps, u.d_a32);
@@ -560,6 +579,8 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
       // only the status word of each (secret-bearing) ProveState leaves the device
       HIP_CHECK(hipMemcpy2DAsync(pin_status + u.lo, sizeof(uint32_t), &u.d_ps[0].status, sizeof(ProveState), sizeof(uint32_t), nb,
                                  hipMemcpyDeviceToHost, s));
+      if (made32)
+        HIP_CHECK(hipMemcpyAsync(pin_made + (size_t)u.lo * m * 32, u.d_commit32, (size_t)nb * m * 32, hipMemcpyDeviceToHost, s));
       // zeroize the device copies of witness-derived data (the reference uses Zeroizing<> for these)
       HIP_CHECK(hipMemsetAsync(arena_base + u.arena_lo, 0, u.arena_len, s));
     }
@@ -605,10 +626,13 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
           throw ProofErr{BPP_ERR_VERIFICATION_FAILED, "Identity element cannot be added to the transcript / zero challenge"};
       }
     }
+    // (out of the staging before the self-check, whose remakes reuse it)
+    if (made32) memcpy(made32, pin_made, (size_t)B * m * 32);
     std::vector<uint8_t> kept_proofs;  // (where the proofs and status words move when a remake needs the staging)
     std::vector<uint32_t> kept_status;
     if (ctx->opt.prove_check > 0)
-      prove_self_check(ctx, params, P, items, B, plen, pin_proofs, pin_status, tamper, remake, kept_proofs, kept_status);
+      prove_self_check(ctx, params, P, items, B, plen, pin_proofs, pin_status, tamper, remake, kept_proofs, kept_status, made32,
+                       (size_t)m * 32);
     if (dev_status) {
       memcpy(dev_status, pin_status, (size_t)B * sizeof(uint32_t));
     } else {
@@ -752,9 +776,11 @@ int check_verify(bpp_ctx *ctx, uint64_t params, const std::vector<bpp_verify_ite
 // finding of the same kind: made again once from the same inputs (nothing is drawn again), failed if its remake's replay differs
 // too (PV_STATUS_SELF_CHECK_RECOVERY says which of the two the failure was).  A remake reuses the call's
 // staging: the proofs and status words move to kept_* first, and `proofs` / `status` point there afterwards.
+// made32 (bpp_prove_openings, else nullptr): the commitments the call computed, item i's at made32 + i * made_stride.  An item that
+// brought none is checked against those -- the checking batch never sees a NULL statement -- and its remake makes them again.
 void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_prove_item *items, uint32_t B, size_t plen, uint8_t *&proofs,
                       uint32_t *&status, const bpp_ctx::CheckTamper &tamper, bool remake, std::vector<uint8_t> &kept_proofs,
-                      std::vector<uint32_t> &kept_status) {
+                      std::vector<uint32_t> &kept_status, uint8_t *made32, size_t made_stride) {
   std::vector<uint32_t> which;  // the items the device made a proof for
   for (uint32_t i = 0; i < B; i++)
     if (status[i] == 0) which.push_back(i);
@@ -778,7 +804,7 @@ void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_
     memset(&v, 0, sizeof(v));
     v.proof = proofs + (size_t)which[k] * plen;
     v.proof_len = prove_item_len(P, it.m);
-    v.commitments32 = it.commitments32;
+    v.commitments32 = it.commitments32 ? it.commitments32 : made32 + (size_t)which[k] * made_stride;
     v.m = it.m;
     v.min_values = it.min_values;
     v.min_present = it.min_present;
@@ -886,13 +912,16 @@ void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_
       again.proof = 1;
     }
     ctx->check_stats.remade++;
-    const int rc = prove_uniform(ctx, params, &items[i], 1, one.data(), len, &got, err, sizeof(err), &st, false, again, false);
+    std::vector<uint8_t> made_one((size_t)32 * items[i].m, 0);
+    const int rc = prove_uniform(ctx, params, &items[i], 1, one.data(), len, &got, err, sizeof(err), &st, false, again, false,
+                                 made32 ? made_one.data() : nullptr);
     if (rc != BPP_OK) throw ProofErr{rc, err, rc < 0 ? BPP_TIER_ENGINE : BPP_TIER_CONSTRUCTION};
     if (st != 0 || got != len) {  // (which of the two the remake failed on: its own check says)
       status[i] |= PV_STATUS_SELF_CHECK | (st & PV_STATUS_SELF_CHECK_RECOVERY);
       ctx->check_stats.failed++;
     } else {
       memcpy(proofs + (size_t)i * plen, one.data(), len);
+      if (made32) memcpy(made32 + (size_t)i * made_stride, made_one.data(), made_one.size());  // (the remake's proof is over the remake's commitments)
     }
   }
 }
@@ -929,8 +958,10 @@ size_t prove_item_len(const Params &P, uint32_t m) {
   return 1 + 32 * (size_t)(P.t + 5 + 2 * rounds);
 }
 
-// the host-side checks of a one-item bpp_prove_batch on `it`, in the same order and with the same codes and messages
-void prove_item_check(const Params &P, const bpp_prove_item &it, size_t proof_stride) {
+// the host-side checks of a one-item bpp_prove_batch on `it`, in the same order and with the same codes and messages.
+// openings: an item of bpp_prove_openings / bpp_prove_pool_openings, which may come without commitments and whose commitments go
+// to a slot of commit_stride bytes.
+void prove_item_check(const Params &P, const bpp_prove_item &it, size_t proof_stride, bool openings = false, size_t commit_stride = 0) {
   const uint32_t n = P.n_bits, t = P.t, m = it.m;
   if (m == 0 || (m & (m - 1))) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Number of commitments must be a power of two"};
   if (P.m_max < m) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Not enough generators for this statement"};
@@ -938,7 +969,8 @@ void prove_item_check(const Params &P, const bpp_prove_item &it, size_t proof_st
   uint32_t rounds = 0;
   while ((1u << rounds) < m * n) rounds++;
   if (proof_stride < prove_item_len(P, m)) throw ProofErr{BPP_ERR_INVALID_LENGTH, "proof_stride too small"};
-  if (!it.values || !it.blindings32 || !it.commitments32 || !it.rng_bytes || (!it.min_values && it.min_present))
+  if (openings && commit_stride < (size_t)32 * m) throw ProofErr{BPP_ERR_INVALID_LENGTH, "commit_stride too small"};
+  if (!it.values || !it.blindings32 || (!it.commitments32 && !openings) || !it.rng_bytes || (!it.min_values && it.min_present))
     throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "null witness / statement field"};
   if (it.seed_nonce32 && m > 1) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Mask recovery is not supported with an aggregated statement"};
   if (it.rng_len < 32 * (size_t)(rounds + 3))
@@ -958,8 +990,12 @@ void prove_item_check(const Params &P, const bpp_prove_item &it, size_t proof_st
 // The mixed call (the context's lock held, its device current): proof i at proofs_out + i * proof_stride, its length in
 // proof_lens[i] (0 for an m that no statement can have), its outcome in out.code[i] / out.msg[i].  A failed item's slot is zeroed.
 // Throws only what concerns the whole call (an unknown params handle, a null argument).
+// commit_slots (bpp_prove_openings and the pool; nullptr: none of the items is of that kind): (*commit_slots)[i] != nullptr marks
+// item i as one of bpp_prove_openings -- it may come without commitments -- and is where its 32 m_i commitment bytes go, a slot of
+// (*commit_caps)[i] bytes; an item with a null slot is one of the existing entry points (a pooled call may hold both kinds).
 void prove_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out, size_t proof_stride,
-                 size_t *proof_lens, MixedOutcome &out) {
+                 size_t *proof_lens, MixedOutcome &out, const std::vector<uint8_t *> *commit_slots = nullptr,
+                 const std::vector<size_t> *commit_caps = nullptr) {
   const std::shared_ptr<Params> Pp = params_registry().get(params);
   if (!Pp || Pp->device != ctx->device) throw ProofErr{BPP_ERR_BAD_HANDLE, "unknown params handle"};
   const Params &P = *Pp;
@@ -973,11 +1009,14 @@ void prove_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, siz
     ctx->check_recovery_failed.swap(recovery_failed);
   }};
   std::map<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> classes;  // m -> the items that passed the host checks
+  auto slot = [&](size_t i) -> uint8_t * { return commit_slots ? (*commit_slots)[i] : nullptr; };
+  bool any_openings = false;  // (among the items that reach the device)
   for (size_t i = 0; i < n_items; i++) {
     proof_lens[i] = prove_item_len(P, items[i].m);
     try {
-      prove_item_check(P, items[i], proof_stride);
+      prove_item_check(P, items[i], proof_stride, slot(i) != nullptr, slot(i) ? (*commit_caps)[i] : 0);
       classes[items[i].m].push_back((uint32_t)i);
+      any_openings = any_openings || slot(i) != nullptr;
     } catch (const ProofErr &e) {
       out.code[i] = e.code;
       out.msg[i] = e.msg;
@@ -997,10 +1036,15 @@ void prove_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, siz
   const size_t plen = prove_item_len(P, sub[0].m);
   std::vector<uint8_t> buf(idx.size() * plen, 0);
   std::vector<uint32_t> status(idx.size(), 0);
+  // what the witness check computed for every item of the sorted call, in rows of the largest m (a call without an item of the
+  // new kind asks for nothing and runs exactly as before)
+  const size_t made_stride = (size_t)32 * sub[0].m;
+  std::vector<uint8_t> made(any_openings ? idx.size() * made_stride : 0, 0);
   char err[256];
   err[0] = 0;
   size_t len = 0;
-  const int rc = prove_uniform(ctx, params, sub.data(), sub.size(), buf.data(), plen, &len, err, sizeof(err), status.data(), true, tamper);
+  const int rc = prove_uniform(ctx, params, sub.data(), sub.size(), buf.data(), plen, &len, err, sizeof(err), status.data(), true, tamper,
+                               true, any_openings ? made.data() : nullptr);
   {
     for (size_t k = 0; k < idx.size(); k++) {
       const uint32_t i = idx[k];
@@ -1018,16 +1062,21 @@ void prove_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, siz
         out.msg[i] = (status[k] & PV_STATUS_SELF_CHECK_RECOVERY) ? kSelfCheckRecoveryMsg : kSelfCheckMsg;
         if (status[k] & PV_STATUS_SELF_CHECK_RECOVERY) {  // (for bpp_prove_item_message: the item's first commitment, public)
           std::array<uint8_t, 32> c;
-          memcpy(c.data(), items[i].commitments32, 32);
+          memcpy(c.data(), items[i].commitments32 ? items[i].commitments32 : &made[k * made_stride], 32);  // (or the one made for it)
           recovery_failed.push_back(c);
         }
       } else {
         memcpy(proofs_out + (size_t)i * proof_stride, &buf[k * plen], proof_lens[i]);
+        // (status 0: what the check computed IS what the item brought, where it brought any)
+        if (slot(i)) memcpy(slot(i), &made[k * made_stride], (size_t)32 * items[i].m);
       }
     }
   }
   for (size_t i = 0; i < n_items; i++)
     if (out.code[i] != BPP_OK && proof_lens[i] && proof_stride >= proof_lens[i]) memset(proofs_out + i * proof_stride, 0, proof_lens[i]);
+  for (size_t i = 0; i < n_items; i++)
+    if (out.code[i] != BPP_OK && slot(i) && proof_lens[i] && (*commit_caps)[i] >= (size_t)32 * items[i].m)
+      memset(slot(i), 0, (size_t)32 * items[i].m);
 }
 
 }  // namespace
@@ -1047,31 +1096,73 @@ extern "C" int bpp_prove_batch_mixed(bpp_ctx *ctx, uint64_t params, const bpp_pr
   BPP_CATCH(ctx, errbuf, errbuf_len)
 }
 
+// bpp_prove_openings: bpp_prove_batch_mixed whose items may come as openings alone.  An item with commitments32 == NULL has its
+// commitments made by the engine -- the witness check computes commit(v_j, r_j) for every opening anyway -- and they are its
+// statement's for the transcript, the proof and the self-check; an item that brings commitments is checked against them as ever.
+// Every successful item's commitments are written at commitments_out + i * commit_stride.
+extern "C" int bpp_prove_openings(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *commitments_out,
+                                  size_t commit_stride, uint8_t *proofs_out, size_t proof_stride, size_t *proof_lens, int *item_status,
+                                  char *errbuf, size_t errbuf_len) {
+  BPP_ENTRY(ctx);
+  try {
+    if (!commitments_out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
+    std::vector<uint8_t *> slots(n_items);
+    for (size_t i = 0; i < n_items; i++) slots[i] = commitments_out + i * commit_stride;
+    const std::vector<size_t> caps(n_items, commit_stride);
+    MixedOutcome out;
+    prove_mixed(ctx, params, items, n_items, proofs_out, proof_stride, proof_lens, out, &slots, &caps);
+    if (item_status) memcpy(item_status, out.code.data(), n_items * sizeof(int));
+    for (size_t i = 0; i < n_items; i++)
+      if (out.code[i] != BPP_OK) return fail(ctx, out.code[i], out.msg[i], errbuf, errbuf_len);
+    set_err(errbuf, errbuf_len, "");
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, errbuf, errbuf_len)
+}
+
 // The message that goes with item_status of bpp_prove_batch_mixed: the item's host-side checks run again (no device work), and an
 // item that passes them failed on the device, whose two findings have one message each, or the self-check (BPP_ERR_SELF_CHECK).
 // Any thread, any time.  The one thing it looks up: whether the item (by its first commitment) is among those of the context's
 // last mixed call whose self-check failed on the replay of mask recovery -- the code alone does not say which of the two it was.
-extern "C" int bpp_prove_item_message(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item, size_t proof_stride, int status,
-                                      char *errbuf, size_t errbuf_len) {
+namespace {
+// openings: an item of bpp_prove_openings (commit_stride: its call's); first_commitment32: what an item that brought no commitments
+// is known by -- the first commitment the engine made for it (nullptr for an item that brought its own)
+int prove_item_message(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item, size_t proof_stride, int status, char *errbuf,
+                       size_t errbuf_len, bool openings, size_t commit_stride, const uint8_t *first_commitment32) {
   if (!ctx || !item) return BPP_ERR_BAD_HANDLE;
   const std::shared_ptr<Params> Pp = params_registry().get(params);
   if (!Pp || Pp->device != ctx->device) return BPP_ERR_BAD_HANDLE;
   try {
-    prove_item_check(*Pp, *item, proof_stride);
+    prove_item_check(*Pp, *item, proof_stride, openings, commit_stride);
   } catch (const ProofErr &e) {
     set_err(errbuf, errbuf_len, e.msg);
     return e.code;
   }
+  const uint8_t *key = item->commitments32 ? item->commitments32 : first_commitment32;
   bool recovery = false;
-  if (status == BPP_ERR_SELF_CHECK && item->seed_nonce32) {
+  if (status == BPP_ERR_SELF_CHECK && item->seed_nonce32 && key) {
     std::lock_guard<std::mutex> lk(ctx->check_note_mu);
-    for (const auto &c : ctx->check_recovery_failed) recovery = recovery || memcmp(c.data(), item->commitments32, 32) == 0;
+    for (const auto &c : ctx->check_recovery_failed) recovery = recovery || memcmp(c.data(), key, 32) == 0;
   }
   set_err(errbuf, errbuf_len, status == BPP_ERR_INVALID_ARGUMENT ? "Witness opening is invalid!"
                               : status == BPP_ERR_VERIFICATION_FAILED ? "Identity element cannot be added to the transcript / zero challenge"
                               : status == BPP_ERR_SELF_CHECK ? (recovery ? kSelfCheckRecoveryMsg : kSelfCheckMsg)
                               : "");
   return status;
+}
+}  // namespace
+
+extern "C" int bpp_prove_item_message(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item, size_t proof_stride, int status,
+                                      char *errbuf, size_t errbuf_len) {
+  return prove_item_message(ctx, params, item, proof_stride, status, errbuf, errbuf_len, false, 0, nullptr);
+}
+
+// The same for an item of a bpp_prove_openings call.  An item that brought no commitments is known to the lookup by the first
+// commitment the engine made for it: the caller passes it (a failed item's slot of commitments_out is zero; commit(v, r) of its
+// first opening, bpp_pedersen_commit, is that commitment).  NULL there, or for an item that brought its own: the item's own first.
+extern "C" int bpp_prove_openings_item_message(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item, const uint8_t *first_commitment32,
+                                               size_t commit_stride, size_t proof_stride, int status, char *errbuf, size_t errbuf_len) {
+  return prove_item_message(ctx, params, item, proof_stride, status, errbuf, errbuf_len, true, commit_stride, first_commitment32);
 }
 
 #ifdef BPP_KP_PHASES

@@ -21,6 +21,11 @@ struct bpp_prove_pool {
     uint8_t *proofs_out = nullptr;
     size_t proof_stride = 0;
     size_t *proof_lens = nullptr;
+    // bpp_prove_pool_openings: the request's items may come without commitments, and every successful item's go to
+    // commitments_out + i * commit_stride (bpp_prove_openings).  Requests of both kinds share pooled calls.
+    bool openings = false;
+    uint8_t *commitments_out = nullptr;
+    size_t commit_stride = 0;
     int code = BPP_OK;
     std::string msg;
     bool taken = false;  // a leader has it in its pooled call
@@ -33,6 +38,8 @@ struct bpp_prove_pool {
     std::vector<bpp_prove_item> items;
     std::vector<uint8_t> proofs;
     std::vector<size_t> lens;
+    std::vector<uint8_t *> commit_slots;  // per item of the pooled call: into its caller's commitments_out, or null (prove_mixed)
+    std::vector<size_t> commit_caps;
   };
   uint64_t params = 0;
   std::shared_ptr<Params> P;
@@ -44,13 +51,16 @@ struct bpp_prove_pool {
   std::vector<Lane> lanes;
   uint64_t pooled_calls = 0, engine_calls = 0, solo_calls = 0;  // statistics
   uint32_t largest_pool_calls = 0, largest_pool_proofs = 0;
+  uint64_t openings_calls = 0, both_kinds_calls = 0;  // requests of bpp_prove_pool_openings; pooled engine calls that held both kinds
 };
 
 namespace {
 
 // A call of more than max_proofs items is a large call by itself, and one whose stride is too short for one of its proofs, or
-// whose arguments are missing, gets its answer from a call of its own: all go through bpp_prove_batch_mixed directly.
+// whose arguments are missing, gets its answer from a call of its own: all go through bpp_prove_batch_mixed (bpp_prove_openings
+// for a request of that kind) directly.
 bool prove_pool_poolable(const bpp_prove_pool *p, const bpp_prove_pool::Req *r) {
+  if (r->openings && !r->commitments_out) return false;
   if (!r->items || r->n_items == 0 || !r->proofs_out || !r->proof_lens || r->n_items > p->max_proofs) return false;
   for (size_t i = 0; i < r->n_items; i++)
     if (r->proof_stride < prove_item_len(*p->P, r->items[i].m)) return false;
@@ -60,8 +70,12 @@ bool prove_pool_poolable(const bpp_prove_pool *p, const bpp_prove_pool::Req *r) 
 void prove_pool_solo(bpp_prove_pool *p, bpp_prove_pool::Lane &L, bpp_prove_pool::Req *r) {
   char err[256];
   err[0] = 0;
-  r->code = bpp_prove_batch_mixed(L.ctx, p->params, r->items, r->n_items, r->proofs_out, r->proof_stride, r->proof_lens, nullptr, err,
-                                  sizeof(err));
+  if (r->openings)
+    r->code = bpp_prove_openings(L.ctx, p->params, r->items, r->n_items, r->commitments_out, r->commit_stride, r->proofs_out,
+                                 r->proof_stride, r->proof_lens, nullptr, err, sizeof(err));
+  else
+    r->code = bpp_prove_batch_mixed(L.ctx, p->params, r->items, r->n_items, r->proofs_out, r->proof_stride, r->proof_lens, nullptr, err,
+                                    sizeof(err));
   r->msg = err;
 }
 
@@ -78,16 +92,25 @@ void prove_pool_run(bpp_prove_pool *p, bpp_prove_pool::Lane &L, const std::vecto
     L.items.resize(n);
     L.lens.assign(n, 0);
     L.proofs.resize(n * p->plen_max);
+    L.commit_slots.assign(n, nullptr);
+    L.commit_caps.assign(n, 0);
     size_t at = 0;
+    bool any_openings = false;
     for (auto *r : reqs) {
       std::copy(r->items, r->items + r->n_items, L.items.begin() + (ptrdiff_t)at);
+      for (size_t i = 0; r->openings && i < r->n_items; i++) {
+        L.commit_slots[at + i] = r->commitments_out + i * r->commit_stride;
+        L.commit_caps[at + i] = r->commit_stride;
+        any_openings = true;
+      }
       at += r->n_items;
     }
     MixedOutcome out;
     {
       std::lock_guard<std::mutex> lk(L.ctx->mu);
       if (hipSetDevice(L.ctx->device) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
-      prove_mixed(L.ctx, p->params, L.items.data(), n, L.proofs.data(), p->plen_max, L.lens.data(), out);
+      prove_mixed(L.ctx, p->params, L.items.data(), n, L.proofs.data(), p->plen_max, L.lens.data(), out,
+                  any_openings ? &L.commit_slots : nullptr, any_openings ? &L.commit_caps : nullptr);
     }
     // fan out: a caller's outcome is its first failing item's (bpp_prove_batch_mixed's return value and message).  An engine fault
     // (a negative code: an allocation the pooled call needed, a HIP error) is nobody's input: the callers it hit get a call of their own.
@@ -234,20 +257,18 @@ void bpp_prove_pool_destroy(bpp_prove_pool *p) {
   delete p;
 }
 
-int bpp_prove_pool_prove(bpp_prove_pool *p, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out, size_t proof_stride,
-                         size_t *proof_lens, char *errbuf, size_t errbuf_len) {
-  if (!p) return BPP_ERR_BAD_HANDLE;
-  bpp_prove_pool::Req me;
-  me.items = items;
-  me.n_items = n_items;
-  me.proofs_out = proofs_out;
-  me.proof_stride = proof_stride;
-  me.proof_lens = proof_lens;
+}  // extern "C"
+
+namespace {
+// one request through the pool (bpp_prove_pool_prove, bpp_prove_pool_openings): blocks until its outcome is there
+int prove_pool_submit(bpp_prove_pool *p, bpp_prove_pool::Req &me, char *errbuf, size_t errbuf_len) {
+  const size_t n_items = me.n_items;
   std::vector<bpp_prove_pool::Req *> mine;
   bpp_prove_pool::Lane *lane = nullptr;
   {
     std::unique_lock<std::mutex> lk(p->mu);
     const bool poolable = prove_pool_poolable(p, &me);
+    if (me.openings) p->openings_calls++;
     if (poolable) {
       p->pending.push_back(&me);
       p->cv.notify_all();  // (a leader waiting for company counts the queue)
@@ -307,6 +328,9 @@ int bpp_prove_pool_prove(bpp_prove_pool *p, const bpp_prove_item *items, size_t 
       for (auto *r : mine) proofs += r->n_items;
       p->largest_pool_calls = std::max(p->largest_pool_calls, (uint32_t)mine.size());
       p->largest_pool_proofs = std::max(p->largest_pool_proofs, (uint32_t)proofs);
+      bool with = false, without = false;
+      for (auto *r : mine) (r->openings ? with : without) = true;
+      if (with && without) p->both_kinds_calls++;
     } else {
       p->solo_calls++;
     }
@@ -321,6 +345,44 @@ int bpp_prove_pool_prove(bpp_prove_pool *p, const bpp_prove_item *items, size_t 
   p->cv.notify_all();
   set_err(errbuf, errbuf_len, me.msg);
   return me.code;
+}
+}  // namespace
+
+extern "C" {
+
+int bpp_prove_pool_prove(bpp_prove_pool *p, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out, size_t proof_stride,
+                         size_t *proof_lens, char *errbuf, size_t errbuf_len) {
+  if (!p) return BPP_ERR_BAD_HANDLE;
+  bpp_prove_pool::Req me;
+  me.items = items;
+  me.n_items = n_items;
+  me.proofs_out = proofs_out;
+  me.proof_stride = proof_stride;
+  me.proof_lens = proof_lens;
+  return prove_pool_submit(p, me, errbuf, errbuf_len);
+}
+
+int bpp_prove_pool_openings(bpp_prove_pool *p, const bpp_prove_item *items, size_t n_items, uint8_t *commitments_out, size_t commit_stride,
+                            uint8_t *proofs_out, size_t proof_stride, size_t *proof_lens, char *errbuf, size_t errbuf_len) {
+  if (!p) return BPP_ERR_BAD_HANDLE;
+  bpp_prove_pool::Req me;
+  me.items = items;
+  me.n_items = n_items;
+  me.proofs_out = proofs_out;
+  me.proof_stride = proof_stride;
+  me.proof_lens = proof_lens;
+  me.openings = true;
+  me.commitments_out = commitments_out;
+  me.commit_stride = commit_stride;
+  return prove_pool_submit(p, me, errbuf, errbuf_len);
+}
+
+int bpp_prove_pool_openings_stats(bpp_prove_pool *p, uint64_t *openings_calls, uint64_t *both_kinds_calls) {
+  if (!p) return BPP_ERR_BAD_HANDLE;
+  std::lock_guard<std::mutex> lk(p->mu);
+  if (openings_calls) *openings_calls = p->openings_calls;
+  if (both_kinds_calls) *both_kinds_calls = p->both_kinds_calls;
+  return BPP_OK;
 }
 
 }  // extern "C"

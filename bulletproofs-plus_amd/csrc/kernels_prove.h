@@ -370,7 +370,7 @@ struct ProveDesc {
   uint32_t ext_off;     // (rounds+3) x 32 bytes of external randomness
   uint32_t minval_idx;  // m minimum values / presence flags
   uint32_t state_idx;
-  uint32_t flags;       // bit0: seed nonce present
+  uint32_t flags;       // bit0: seed nonce present; bit1: the commitments are to be made (kp_adopt_commitments)
   uint32_t seed_off;    // byte offset of the 32-byte seed nonce (if any)
   // Mixed aggregation factors (bpp_prove_batch_mixed): the call runs R = the largest proof's rounds as global steps; this proof
   // takes part from step roff = R - its own rounds on (its local step is j - roff), so that every proof reaches the final step in
@@ -390,6 +390,7 @@ struct ProveState {
 
 #define PV_STATUS_COMMIT_MISMATCH 2u  // InvalidArgument: "Witness opening is invalid!" (:275-284)
 #define PV_STATUS_TRANSCRIPT 1u       // VerificationFailed: identity point / zero challenge
+#define PV_FLAG_MAKE_COMMITMENTS 2u   // ProveDesc::flags: the statement's commitments are the ones the witness check computes
 
 // build_rng (src/transcripts.rs:185-194): clone, rekey with the witness bytes, finalize with 32 external bytes
 __device__ __forceinline__ void pv_build_rng(Strobe &rng, const Strobe &tr, const uint8_t *wit, uint32_t wit_len,
@@ -1425,6 +1426,26 @@ __global__ void kp_check_commitments(const uint8_t *__restrict__ bytes, const Pr
   uint32_t diff = 0;
   for (uint32_t i = 0; i < 32 * d.m; i++) diff |= (uint32_t)(bytes[d.commit_off + i] ^ computed32[(size_t)p * 32 * d.mslot + i]);
   if (diff) ps[p].status |= PV_STATUS_COMMIT_MISMATCH;
+}
+
+// bpp_prove_openings: a proof whose statement brings no commitments (ProveDesc::flags bit 1; the host left its 32 m bytes at commit_off
+// zero) takes the ones the witness check has just computed -- computed32[p][0..m), rows of mslot as kp_check_commitments reads them --
+// as its statement's.  Runs in front of kp_init, so every later reader of bytes + commit_off (the transcript's "Ci" appends, the round
+// kernels, kp_check_commitments, which then compares the bytes with themselves) sees them.  One lane per (proof, opening), eight
+// dword stores each: commit_off is a multiple of 8 (every field of the packed bytes is) and the rows of computed32 of 32.  Public
+// bytes, no LDS: nothing to wipe.  Proofs of fewer than mslot openings leave their further rows alone; unflagged proofs are not touched.
+__global__ void __launch_bounds__(64) kp_adopt_commitments(uint8_t *__restrict__ bytes, const ProveDesc *__restrict__ desc,
+                                                           const uint8_t *__restrict__ computed32 /* [B][mslot][32] */, uint32_t B,
+                                                           uint32_t mslot) {
+  const uint32_t o = blockIdx.x * blockDim.x + threadIdx.x;
+  if (o >= B * mslot) return;
+  const uint32_t p = o / mslot, j = o % mslot;
+  const ProveDesc d = desc[p];
+  if (!(d.flags & PV_FLAG_MAKE_COMMITMENTS) || j >= d.m) return;
+  const uint32_t *src = (const uint32_t *)(computed32 + ((size_t)p * d.mslot + j) * 32);
+  uint32_t *dst = (uint32_t *)(bytes + d.commit_off + 32 * j);
+#pragma unroll
+  for (int k = 0; k < 8; k++) dst[k] = src[k];
 }
 
 // The self-check's replay of mask recovery ("prove_check_recovery" = 1, engine_prove.h: check_verify): the t masks the verifier

@@ -57,13 +57,17 @@ def commit(params, values, blindings):
 
 
 def prove(params, values, blindings, commitments, min_values, min_present, seed_nonces, label, rng_bytes):
-    """n x RangeProof::prove_with_rng in one bpp_prove_batch call -> uint8 [n, proof_len]"""
+    """n x RangeProof::prove_with_rng in one bpp_prove_batch call -> uint8 [n, proof_len]
+
+    commitments=None: prove from the openings alone (bpp_prove_openings: the engine makes commit(v, r) for every opening and uses
+    them as the statements' commitments) -> (commitments uint8 [n, m, 32], proofs uint8 [n, proof_len])"""
     n_bits, t = params.bit_length(), int(params.extension_degree())
     values = np.ascontiguousarray(values, dtype=np.uint64)
     n, m = values.shape
     rounds = max((n_bits * m).bit_length() - 1, 0)
     blindings = _c(blindings, np.uint8, (n, m, t, 32))
-    commitments = _c(commitments, np.uint8, (n, m, 32))
+    if commitments is not None:
+        commitments = _c(commitments, np.uint8, (n, m, 32))
     min_values = _c(min_values, np.uint64, (n, m))
     min_present = _c(min_present, np.uint8, (n, m))
     rng_bytes = _c(rng_bytes, np.uint8, (n, 32 * (rounds + 3)))
@@ -71,7 +75,8 @@ def prove(params, values, blindings, commitments, min_values, min_present, seed_
     items = np.zeros(n, dtype=_PROVE_ITEM)
     items["values"] = _rows(values)
     items["blindings32"] = _rows(blindings)
-    items["commitments32"] = _rows(commitments)
+    if commitments is not None:
+        items["commitments32"] = _rows(commitments)
     items["m"] = m
     items["min_values"] = _rows(min_values)
     items["min_present"] = _rows(min_present)
@@ -87,6 +92,13 @@ def prove(params, values, blindings, commitments, min_values, min_present, seed_
     got = c_size_t()
     err = ctypes.create_string_buffer(256)
     eng = params.engine
+    if commitments is None:
+        made = np.empty((n, m, 32), dtype=np.uint8)
+        lens = (c_size_t * n)()
+        rc = eng.lib.bpp_prove_openings(eng.ctx, params.handle, items.ctypes.data_as(POINTER(_lib.ProveItem)), n, made.ctypes.data, 32 * m,
+                                        out.ctypes.data, plen, lens, None, err, 256)
+        api._check(rc, eng.ctx, err)
+        return made, out
     rc = eng.lib.bpp_prove_batch(eng.ctx, params.handle, items.ctypes.data_as(POINTER(_lib.ProveItem)), n, out.ctypes.data, plen,
                                  byref(got), err, 256)
     api._check(rc, eng.ctx, err)
@@ -207,6 +219,33 @@ class ProvePool:
     def prove(self, transcripts, statements, witnesses, rng_bytes):
         """n x RangeProof::prove_with_rng (any aggregation factors) through the pool -> list of proof bytes"""
         return self.prove_marshalled(self.marshal(transcripts, statements, witnesses, rng_bytes))
+
+    def prove_openings_marshalled(self, marshalled):
+        """bpp_prove_pool_openings over api.RangeProof._openings_marshal's items; blocks; returns (commitments per item, proof
+        bytes per item), or raises the ProofError of the call's first failing item"""
+        _params, items, n, _keep = marshalled
+        cstride = 32 * max(items[i].m for i in range(n))
+        comms = (ctypes.c_uint8 * (cstride * n))()
+        out = (ctypes.c_uint8 * (self.STRIDE * n))()
+        lens = (c_size_t * n)()
+        err = ctypes.create_string_buffer(256)
+        api._check(self.engine.lib.bpp_prove_pool_openings(self.handle, items, n, comms, cstride, out, self.STRIDE, lens, err, 256), None, err)
+        raw, craw = bytes(out), bytes(comms)
+        return ([[craw[i * cstride + 32 * j:i * cstride + 32 * j + 32] for j in range(items[i].m)] for i in range(n)],
+                [raw[i * self.STRIDE:i * self.STRIDE + lens[i]] for i in range(n)])
+
+    def prove_openings(self, transcripts, witnesses, minimum_value_promises, seed_nonces, rng_bytes):
+        """api.RangeProof.prove_openings through the pool -> (statements, list of proof bytes); raises the first failing item's error"""
+        comms, proofs = self.prove_openings_marshalled(api.RangeProof._openings_marshal(transcripts, witnesses, minimum_value_promises,
+                                                                                       seed_nonces, rng_bytes, self.params))
+        sts = [api.RangeStatement.init(self.params, c, list(mins), sn) for c, mins, sn in zip(comms, minimum_value_promises, seed_nonces)]
+        return sts, proofs
+
+    def openings_stats(self):
+        """bpp_prove_pool_openings_stats: requests of the openings kind, pooled engine calls that held requests of both kinds"""
+        a, b = c_uint64(), c_uint64()
+        api._check(self.engine.lib.bpp_prove_pool_openings_stats(self.handle, byref(a), byref(b)), None)
+        return {"openings_calls": int(a.value), "both_kinds_calls": int(b.value)}
 
     def set_limits(self, max_calls=0, max_proofs=0):
         api._check(self.engine.lib.bpp_prove_pool_set_limits(self.handle, max_calls, max_proofs), None)

@@ -466,6 +466,26 @@ int bpp_prove_batch_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *i
  * first commitment), so ask before the next mixed call on that context. */
 int bpp_prove_item_message(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item, size_t proof_stride, int status, char *errbuf,
                            size_t errbuf_len);
+/* Prove from the openings alone: bpp_prove_batch_mixed -- mixed aggregation factors, per-item status, a failed item never stops the
+ * others -- with one rule added.  An item with commitments32 == NULL has its m_i commitments commit(v_j, r_j) made by the engine (the
+ * witness check computes them anyway, through the uniform-access lines under "ct" >= 1), and they are the statement's commitments
+ * for everything that follows: the transcript, the proof, the self-check.  An item that brings commitments32 is handled as by
+ * bpp_prove_batch_mixed (its witness check can fail with "Witness opening is invalid!").  For every item that succeeds its m_i x 32
+ * commitment bytes are written at commitments_out + i * commit_stride: the made ones, or the brought ones.  A failed item's slot is
+ * zeroed in commitments_out and in proofs_out.  commitments_out == NULL fails the call with BPP_ERR_INVALID_ARGUMENT;
+ * commit_stride < 32 * m_i fails that item with BPP_ERR_INVALID_LENGTH ("commit_stride too small", checked after proof_stride).
+ * For an item without commitments, the commitment bytes and the proof bytes equal what bpp_pedersen_commit followed by a one-item
+ * bpp_prove_batch on that item give.  The existing entry points still refuse an item without commitments. */
+int bpp_prove_openings(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *commitments_out,
+                       size_t commit_stride, uint8_t *proofs_out, size_t proof_stride, size_t *proof_lens, int *item_status,
+                       char *errbuf, size_t errbuf_len);
+/* bpp_prove_item_message for an item of a bpp_prove_openings call (same params, commit_stride and proof_stride).  The lookup behind
+ * BPP_ERR_SELF_CHECK knows an item by its first commitment; for an item that brought none that is the one the engine made, which
+ * the caller passes as first_commitment32 (a failed item's slot of commitments_out is zero: bpp_pedersen_commit of its first
+ * opening gives it).  NULL for an item that brought its own; NULL for one that did not: the text then names the verifier's
+ * rejection.  Looks at what ctx's LAST bpp_prove_openings or bpp_prove_batch_mixed left behind. */
+int bpp_prove_openings_item_message(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item, const uint8_t *first_commitment32,
+                                    size_t commit_stride, size_t proof_stride, int status, char *errbuf, size_t errbuf_len);
 /* bpp_prove_pool: many host threads, each with a few proofs per call (one output of a wallet service, say).  A call of one proof
  * is a chain of latency-bound launches; the pool hands the calls that are waiting to ONE bpp_prove_batch_mixed on one of `lanes`
  * contexts (the first is ctx; the others are made here with ctx's options as they are now).  No thread of its own: whichever
@@ -484,6 +504,13 @@ int bpp_prove_pool_set_limits(bpp_prove_pool *p, uint32_t max_calls, uint32_t ma
 int bpp_prove_pool_stats(bpp_prove_pool *p, uint64_t *pooled_calls, uint64_t *engine_calls, uint64_t *solo_calls,
                          uint32_t *largest_calls, uint32_t *largest_proofs);
 void bpp_prove_pool_destroy(bpp_prove_pool *p);
+/* bpp_prove_openings through the pool: to it what bpp_prove_pool_prove is to bpp_prove_batch_mixed (the same bytes, lengths, code and
+ * message).  Requests of both kinds share pooled calls.  Stats: requests of this kind so far, and pooled engine calls that held
+ * requests of both kinds (either pointer may be NULL). */
+int bpp_prove_pool_openings(bpp_prove_pool *p, const bpp_prove_item *items, size_t n_items, uint8_t *commitments_out,
+                            size_t commit_stride, uint8_t *proofs_out, size_t proof_stride, size_t *proof_lens, char *errbuf,
+                            size_t errbuf_len);
+int bpp_prove_pool_openings_stats(bpp_prove_pool *p, uint64_t *openings_calls, uint64_t *both_kinds_calls);
 /* What the self-check ("prove_check" = 1) of a context has done: prove calls checked, proofs checked (those the device made without
  * a finding of its own), calls whose checking batch was rejected, proofs made again, proofs that failed with BPP_ERR_SELF_CHECK.
  * The remake's own check is counted in `remade` / `failed` only.  A struct tag, like POSIX's struct stat and stat(): a typedef

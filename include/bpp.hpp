@@ -14,6 +14,7 @@
 //
 // Scalars and points are 32-byte arrays (canonical little-endian scalar / ristretto255 encoding).
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <cstring>
@@ -21,6 +22,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "bpp.h"
@@ -252,6 +254,63 @@ class RangeProof {
   static RangeProof prove_with_rng(const Transcript &transcript, const RangeStatement &statement, const RangeWitness &witness,
                                    const std::vector<uint8_t> &rng_bytes) {
     return prove_batch({transcript}, {statement}, {witness}, {rng_bytes})[0];
+  }
+
+  // Prove from the openings alone (bpp_prove_openings): the engine makes commit(v, r) for every opening, in the same call, and the
+  // statements are built from what it returns.  Any aggregation factors (powers of two up to the parameters' maximum) in one call;
+  // minimum_value_promises[i] has one entry per opening of witnesses[i], seed_nonces[i] only with one opening.  Throws the first
+  // failing item's error.
+  static std::pair<std::vector<RangeStatement>, std::vector<RangeProof>> prove_openings(
+      const std::vector<Transcript> &transcripts, const std::vector<RangeWitness> &witnesses,
+      const std::vector<std::vector<std::optional<uint64_t>>> &minimum_value_promises, const std::vector<std::optional<Bytes32>> &seed_nonces,
+      const std::vector<std::vector<uint8_t>> &rng_bytes, const std::shared_ptr<RangeParameters> &generators) {
+    const size_t n = witnesses.size();
+    if (n == 0 || transcripts.size() != n || minimum_value_promises.size() != n || seed_nonces.size() != n || rng_bytes.size() != n)
+      throw ProofError(ProofErrorKind::InvalidArgument, "Range statements, witnesses, transcripts length mismatch");
+    auto &params = *generators;
+    std::vector<bpp_prove_item> items(n);
+    std::vector<std::vector<uint64_t>> vals(n), mins(n);
+    std::vector<std::vector<uint8_t>> blind(n), pres(n);
+    size_t m_max = 1;
+    for (size_t i = 0; i < n; i++) {
+      const auto &w = witnesses[i];
+      const size_t m = w.openings.size();
+      m_max = std::max(m_max, m);
+      if (minimum_value_promises[i].size() != m) throw ProofError(ProofErrorKind::InvalidArgument, "Incorrect number of minimum value promises");
+      if (w.extension_degree != static_cast<uint32_t>(params.extension_degree()))
+        throw ProofError(ProofErrorKind::InvalidLength, "Witness and statement extension degrees do not match!");
+      for (size_t j = 0; j < m; j++) {
+        vals[i].push_back(w.openings[j].v);
+        for (const auto &r : w.openings[j].r) blind[i].insert(blind[i].end(), r.begin(), r.end());
+        mins[i].push_back(minimum_value_promises[i][j].value_or(0));
+        pres[i].push_back(minimum_value_promises[i][j] ? 1 : 0);
+      }
+      bpp_prove_item &it = items[i];
+      memset(&it, 0, sizeof(it));  // (commitments32 stays NULL: to be made)
+      it.values = vals[i].data();
+      it.blindings32 = blind[i].data();
+      it.m = static_cast<uint32_t>(m);
+      it.min_values = mins[i].data();
+      it.min_present = pres[i].data();
+      it.seed_nonce32 = seed_nonces[i] ? seed_nonces[i]->data() : nullptr;
+      fill_transcript(transcripts[i], it.transcript_state, it.transcript_label, it.label_len);
+      it.rng_bytes = rng_bytes[i].data();
+      it.rng_len = rng_bytes[i].size();
+    }
+    const size_t stride = 1 + 32 * (6 + 5 + 2 * 12), cstride = 32 * m_max;
+    std::vector<uint8_t> out(stride * n), comm(cstride * n);
+    std::vector<size_t> lens(n, 0);
+    char err[256] = {0};
+    check(bpp_prove_openings(params.engine().ctx(), params.handle(), items.data(), n, comm.data(), cstride, out.data(), stride, lens.data(),
+                             nullptr, err, sizeof(err)), err);
+    std::pair<std::vector<RangeStatement>, std::vector<RangeProof>> res;
+    for (size_t i = 0; i < n; i++) {
+      std::vector<Bytes32> cs(items[i].m);
+      for (size_t j = 0; j < cs.size(); j++) std::copy_n(comm.begin() + i * cstride + 32 * j, 32, cs[j].begin());
+      res.first.push_back(RangeStatement::init(generators, std::move(cs), minimum_value_promises[i], seed_nonces[i]));
+      res.second.push_back(from_bytes(std::vector<uint8_t>(out.begin() + i * stride, out.begin() + i * stride + lens[i])));
+    }
+    return res;
   }
 
   // src/range_proof.rs:712-752; every `chunk` proofs are one reference batch (all chunks are verified)

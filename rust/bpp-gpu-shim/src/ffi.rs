@@ -283,6 +283,16 @@ extern "C" {
                                  errbuf_len: usize) -> c_int;
     pub fn bpp_prove_item_message(ctx: *mut bpp_ctx, params: u64, item: *const bpp_prove_item, proof_stride: usize, status: c_int,
                                   errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_openings(ctx: *mut bpp_ctx, params: u64, items: *const bpp_prove_item, n_items: usize, commitments_out: *mut u8,
+                              commit_stride: usize, proofs_out: *mut u8, proof_stride: usize, proof_lens: *mut usize,
+                              item_status: *mut c_int, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_openings_item_message(ctx: *mut bpp_ctx, params: u64, item: *const bpp_prove_item, first_commitment32: *const u8,
+                                           commit_stride: usize, proof_stride: usize, status: c_int, errbuf: *mut c_char,
+                                           errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_pool_openings(p: *mut bpp_prove_pool, items: *const bpp_prove_item, n_items: usize, commitments_out: *mut u8,
+                                   commit_stride: usize, proofs_out: *mut u8, proof_stride: usize, proof_lens: *mut usize,
+                                   errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_pool_openings_stats(p: *mut bpp_prove_pool, openings_calls: *mut u64, both_kinds_calls: *mut u64) -> c_int;
     pub fn bpp_prove_pool_create(ctx: *mut bpp_ctx, params: u64, lanes: u32, max_wait_us: u32, max_calls: u32,
                                  out: *mut *mut bpp_prove_pool) -> c_int;
     pub fn bpp_prove_pool_prove(p: *mut bpp_prove_pool, items: *const bpp_prove_item, n_items: usize, proofs_out: *mut u8,

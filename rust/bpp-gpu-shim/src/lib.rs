@@ -356,6 +356,41 @@ impl Engine {
         }).collect())
     }
 
+    /// Prove from the openings alone (bpp_prove_openings): `prove_batch_mixed` whose items may come with an EMPTY `commitments`
+    /// slice; the engine then makes commit(v_j, r_j) for every opening of that item -- in the same call, where the prover's witness
+    /// check computes them anyway -- and proves over them.  One entry per item: (its m x 32 commitment bytes, made or brought, its
+    /// `to_bytes()`), or the item's error.
+    #[allow(clippy::type_complexity)]
+    pub fn prove_openings(&self, params: &Params, items: &[ProveItem<'_>]) -> Result<Vec<Result<(Vec<u8>, Vec<u8>), GpuError>>, GpuError> {
+        let keep = RawProveItems::new_openings(items);
+        let stride = 1 + 32 * (6 + 5 + 2 * 12);
+        let cstride = 32 * items.iter().map(|i| i.values.len()).max().unwrap_or(1);
+        let mut out = vec![0u8; stride * items.len()];
+        let mut comms = vec![0u8; cstride * items.len()];
+        let mut lens = vec![0usize; items.len()];
+        let mut status = vec![0 as c_int; items.len()];
+        let mut err = [0 as core::ffi::c_char; 256];
+        let rc = unsafe {
+            ffi::bpp_prove_openings(self.ctx, params.handle, keep.raw.as_ptr(), keep.raw.len(), comms.as_mut_ptr(), cstride, out.as_mut_ptr(),
+                                    stride, lens.as_mut_ptr(), status.as_mut_ptr(), err.as_mut_ptr(), err.len())
+        };
+        if rc < 0 && rc != ffi::BPP_ERR_SELF_CHECK {
+            map_rc(rc, unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned())?;
+        }
+        Ok((0..items.len()).map(|k| {
+            if status[k] == 0 {
+                return Ok((comms[k * cstride..k * cstride + 32 * items[k].values.len()].to_vec(), out[k * stride..k * stride + lens[k]].to_vec()));
+            }
+            // (first_commitment32 = NULL: a self-check failure's text names the verifier's rejection unless the item brought its own)
+            let mut e1 = [0 as core::ffi::c_char; 256];
+            unsafe {
+                ffi::bpp_prove_openings_item_message(self.ctx, params.handle, &keep.raw[k], ptr::null(), cstride, stride, status[k], e1.as_mut_ptr(),
+                                                     e1.len())
+            };
+            map_rc(status[k], unsafe { CStr::from_ptr(e1.as_ptr()) }.to_string_lossy().into_owned()).map(|_| (Vec::new(), Vec::new()))
+        }).collect())
+    }
+
     /// Arc::clone of a parameter set created on another context of the same device
     pub fn retain(&self, params: &Params) -> Result<Params, GpuError> {
         map_rc(unsafe { ffi::bpp_params_retain(self.ctx, params.handle) }, self.last_error())?;
@@ -647,12 +682,19 @@ struct RawProveItems {
 }
 impl RawProveItems {
     fn new(items: &[ProveItem<'_>]) -> RawProveItems {
+        RawProveItems::build(items, false)
+    }
+    /// for bpp_prove_openings / bpp_prove_pool_openings: an empty `commitments` slice becomes NULL ("to be made")
+    fn new_openings(items: &[ProveItem<'_>]) -> RawProveItems {
+        RawProveItems::build(items, true)
+    }
+    fn build(items: &[ProveItem<'_>], openings: bool) -> RawProveItems {
         let present: Vec<Vec<u8>> = items.iter().map(|i| i.min_values.iter().map(|v| v.is_some() as u8).collect()).collect();
         let mins: Vec<Vec<u64>> = items.iter().map(|i| i.min_values.iter().map(|v| v.unwrap_or(0)).collect()).collect();
         let raw = items.iter().enumerate().map(|(k, i)| ffi::bpp_prove_item {
             values: i.values.as_ptr(),
             blindings32: i.blindings.as_ptr(),
-            commitments32: i.commitments.as_ptr(),
+            commitments32: if openings && i.commitments.is_empty() { ptr::null() } else { i.commitments.as_ptr() },
             m: i.values.len() as u32,
             min_values: mins[k].as_ptr(),
             min_present: present[k].as_ptr(),
@@ -703,6 +745,30 @@ impl ProvePool {
         };
         map_rc(rc, unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned())?;
         Ok((0..items.len()).map(|k| out[k * stride..k * stride + lens[k]].to_vec()).collect())
+    }
+    /// `Engine::prove_openings` through the pool (bpp_prove_pool_openings): per item (commitment bytes, proof bytes), or the call's
+    /// first error.  Calls of this kind and `prove` calls share pooled engine calls.
+    pub fn prove_openings(&self, items: &[ProveItem<'_>]) -> Result<Vec<(Vec<u8>, Vec<u8>)>, GpuError> {
+        let keep = RawProveItems::new_openings(items);
+        let stride = 1 + 32 * (6 + 5 + 2 * 12);
+        let cstride = 32 * items.iter().map(|i| i.values.len()).max().unwrap_or(1);
+        let mut out = vec![0u8; stride * items.len()];
+        let mut comms = vec![0u8; cstride * items.len()];
+        let mut lens = vec![0usize; items.len()];
+        let mut err = [0 as core::ffi::c_char; 256];
+        let rc = unsafe {
+            ffi::bpp_prove_pool_openings(self.raw, keep.raw.as_ptr(), keep.raw.len(), comms.as_mut_ptr(), cstride, out.as_mut_ptr(), stride,
+                                         lens.as_mut_ptr(), err.as_mut_ptr(), err.len())
+        };
+        map_rc(rc, unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned())?;
+        Ok((0..items.len()).map(|k| (comms[k * cstride..k * cstride + 32 * items[k].values.len()].to_vec(),
+                                     out[k * stride..k * stride + lens[k]].to_vec())).collect())
+    }
+    /// (requests of `prove_openings` so far, pooled engine calls that held requests of both kinds)
+    pub fn openings_stats(&self) -> (u64, u64) {
+        let (mut a, mut b) = (0u64, 0u64);
+        unsafe { ffi::bpp_prove_pool_openings_stats(self.raw, &mut a, &mut b) };
+        (a, b)
     }
     pub fn set_limits(&self, max_calls: u32, max_proofs: u32) -> Result<(), GpuError> {
         map_rc(unsafe { ffi::bpp_prove_pool_set_limits(self.raw, max_calls, max_proofs) }, String::from("bpp_prove_pool_set_limits"))

@@ -11,6 +11,11 @@ One JSON line per (setup, S, t): proofs/s and p50 / p99 call latency.
                pooled lines add the lanes' check counters
   --check-recovery   with --check: mask recovery replayed for the proofs that carry a seed nonce ("prove_check_recovery" = 1)
   --nonces     the rate runs' one-proof calls are all m = 1 with a seed nonce each (otherwise only every third is)
+  --openings   the rate runs' calls prove from the openings alone: one bpp_prove_openings (solo) / bpp_prove_pool_openings (pooled)
+               per call, the commitments made by the engine
+  --openings-two-call   the same output the way it took two calls: bpp_pedersen_commit for the item's openings, then the existing
+               prove call, timed together (pooled: the commit call goes to the context the pool was made from, the one context a
+               pool's callers share)
   --soak SEC   instead: SEC seconds of 16 threads through the pool, about 5 % of the calls invalid (one item short of external
                randomness); every proof is compared with the bytes of a one-item bpp_prove_batch of the same item on the same GPU
                (not with the CPU oracle: the tests pin both paths to it), every error with that of a call of its own
@@ -65,6 +70,19 @@ def solo_call(eng, params, mar):
     return [raw[i * STRIDE:i * STRIDE + plen.value] for i in range(n)]
 
 
+def openings_call(eng, params, mar):
+    """one bpp_prove_openings over items marshalled without commitments -> proof bytes"""
+    _p, arr, n, _k = mar
+    out = (ctypes.c_uint8 * (STRIDE * n))()
+    comms = (ctypes.c_uint8 * (128 * n))()
+    lens = (ctypes.c_size_t * n)()
+    err = ctypes.create_string_buffer(256)
+    rc = eng.lib.bpp_prove_openings(eng.ctx, params.handle, arr, n, comms, 128, out, STRIDE, lens, None, err, 256)
+    assert rc == 0, err.value
+    raw = bytes(out)
+    return [raw[i * STRIDE:i * STRIDE + lens[i]] for i in range(n)]
+
+
 def pct(xs, q):
     xs = sorted(xs)
     return xs[min(len(xs) - 1, int(q * len(xs)))]
@@ -95,7 +113,11 @@ def bench_rates(bpp, packed, args):
         if args.check_recovery:
             eng0.set_option("prove_check_recovery", 1)
         p0 = bpp.RangeParameters.init(64, 4, bpp.create_pedersen_gens_with_extension_degree(t), engine=eng0)
-        items = [marshal(bpp, [x]) for x in corpus(bpp, p0, 64, t, 48, t, args.nonces)]
+        raw = corpus(bpp, p0, 64, t, 48, t, args.nonces)
+        items = [marshal(bpp, [x]) for x in raw]
+        # the same items without commitments, and their openings for the two-call form's bpp_pedersen_commit
+        bare = [bpp.RangeProof._openings_marshal([x[0]], [x[2]], [x[1].minimum_value_promises], [x[1].seed_nonce], [x[3]], p0) for x in raw]
+        opened = [([o.v for o in x[2].openings], [o.r for o in x[2].openings]) for x in raw]
         solo_call(eng0, p0, items[0])  # fixed-base table, arena
         for S in args.threads:
             for setup in ("solo", "pooled"):
@@ -111,8 +133,14 @@ def bench_rates(bpp, packed, args):
 
                     def fn(k, lat):
                         for c in range(args.calls):
+                            i = (k * 7 + c) % len(items)
                             a = time.perf_counter()
-                            solo_call(engs[k], ps[k], items[(k * 7 + c) % len(items)])
+                            if args.openings:
+                                openings_call(engs[k], ps[k], bare[i])
+                            else:
+                                if args.openings_two_call:
+                                    ps[k].commit_many(*opened[i])
+                                solo_call(engs[k], ps[k], items[i])
                             lat.append(time.perf_counter() - a)
                 else:
                     pool = packed.ProvePool(p0, lanes=args.lanes, max_wait_us=args.max_wait_us)
@@ -121,14 +149,21 @@ def bench_rates(bpp, packed, args):
 
                     def fn(k, lat):
                         for c in range(args.calls):
+                            i = (k * 7 + c) % len(items)
                             a = time.perf_counter()
-                            pool.prove_marshalled(items[(k * 7 + c) % len(items)])
+                            if args.openings:
+                                pool.prove_openings_marshalled(bare[i])
+                            else:
+                                if args.openings_two_call:
+                                    p0.commit_many(*opened[i])
+                                pool.prove_marshalled(items[i])
                             lat.append(time.perf_counter() - a)
                 el, lat = run_threads(S, fn)
                 rec = {"metric": "one-proof prove calls, " + ("m = 1 with seed nonces" if args.nonces else "m in {1,2,4}"), "setup": setup, "threads": S, "calls_per_thread": args.calls,
                        "bit_length": 64, "extension_degree": t, "proofs_per_s": S * args.calls / el,
                        "p50_ms": 1e3 * pct(lat, 0.5), "p99_ms": 1e3 * pct(lat, 0.99), "prove_check": 1 if args.check else 0,
-                       "prove_check_recovery": 1 if args.check_recovery else 0}
+                       "prove_check_recovery": 1 if args.check_recovery else 0,
+                       "form": "openings" if args.openings else ("openings-two-call" if args.openings_two_call else "commitments brought")}
                 if setup == "solo":
                     for p in ps:
                         p.close()
@@ -257,6 +292,8 @@ def main():
     ap.add_argument("--soak", type=float, default=0)
     ap.add_argument("--check", action="store_true", help='"prove_check" = 1 on every context of the rate runs')
     ap.add_argument("--check-recovery", action="store_true", help='"prove_check_recovery" = 1 on every context of the rate runs')
+    ap.add_argument("--openings", action="store_true", help="rate runs: one call from the openings alone (bpp_prove_openings)")
+    ap.add_argument("--openings-two-call", action="store_true", help="rate runs: bpp_pedersen_commit + the existing prove call, timed together")
     ap.add_argument("--nonces", action="store_true", help="rate runs: every call one m = 1 proof with a seed nonce")
     args = ap.parse_args()
     args.threads = [int(x) for x in args.threads.split(",")]
