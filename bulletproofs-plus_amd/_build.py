@@ -91,6 +91,21 @@ def build_sanitizer_harness(force=False):
     return SANITIZER_BIN
 
 
+PROVE_JOB_SANITIZER_BIN = os.path.join(HERE, "hosttest_prove_job_asan")
+
+
+def build_prove_job_harness(force=False):
+    """hosttest_prove_job.cpp (the job copy bpp_prove_submit takes of its caller's items: per-item check, deep copy, wipe) under
+    ASan + UBSan: an executable, run by tests/test_prove_pipeline_host.py."""
+    src = os.path.join(CSRC, "hosttest_prove_job.cpp")
+    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
+    if not force and not _stale(PROVE_JOB_SANITIZER_BIN, deps):
+        return PROVE_JOB_SANITIZER_BIN
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-fno-omit-frame-pointer", "-o", PROVE_JOB_SANITIZER_BIN, src], check=True, cwd=CSRC)
+    return PROVE_JOB_SANITIZER_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     build_hosttest(force="--force" in sys.argv)

@@ -163,6 +163,11 @@ SYMBOLS = [
     ("bpp_prove_pool_check_stats", c_int, [c_void_p, POINTER(ProveCheckStats)]),
     ("bpp_prove_check_recovery_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     ("bpp_prove_pool_check_recovery_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    ("bpp_prove_pipeline_depth", c_int, [c_void_p, c_uint32]),
+    ("bpp_prove_submit", c_int, [c_void_p, c_uint64, POINTER(ProveItem), c_size_t, c_size_t, c_int, c_size_t, POINTER(c_uint64),
+                                 c_void_p, c_size_t]),
+    ("bpp_prove_collect", c_int, [c_void_p, c_uint64, c_void_p, c_void_p, POINTER(c_size_t), POINTER(c_int), c_void_p, c_size_t]),
+    ("bpp_prove_ticket_done", c_int, [c_void_p, c_uint64, POINTER(c_int)]),
     ("bpp_batch_trace", c_int, [c_void_p, c_uint64, c_int, c_void_p, c_size_t, POINTER(c_size_t)]),
     ("bpp_batch_shape", c_int, [c_void_p, c_uint64, POINTER(c_uint32), POINTER(c_uint32), POINTER(c_uint32),
                                 POINTER(c_uint32), POINTER(c_uint32)]),

@@ -36,6 +36,7 @@
 #include "kernels_prove.h"
 #include "kernels_verify.h"
 #include "msm.h"
+#include "prove_job_host.h"
 #include "upload_host.h"
 
 using namespace bpp;
@@ -507,6 +508,15 @@ struct Pipeline {
 
 void pipeline_shutdown(bpp_ctx *ctx);
 
+// the same for prove calls (bpp_prove_submit / bpp_prove_collect, engine_prove_pipe.h): lanes and tickets of their own
+struct ProvePipeline;
+void prove_pipeline_shutdown(bpp_ctx *ctx);
+// what the lanes add to the context's own answers (bpp_prove_check_stats, bpp_prove_check_recovery_stats, bpp_prove_secret_bytes);
+// nothing for a context that never used the prove pipeline
+int prove_pipeline_check_stats(bpp_ctx *ctx, struct bpp_prove_check_stats *sum);
+int prove_pipeline_recovery_stats(bpp_ctx *ctx, uint64_t *replayed, uint64_t *mismatched);
+int prove_pipeline_secret_bytes(bpp_ctx *ctx, uint64_t *examined, uint64_t *nonzero);
+
 // What a waiting site remembers: how long its wait took the last times (microseconds, a running mean) and for WHICH work -- a key the
 // caller makes from the call's size.  A remembered time is only used for a call with the same key: a context that proved 8192
 // proofs per call and then proves 1024 must not sleep through the shorter call on the longer one's memory (it did, for one
@@ -606,6 +616,9 @@ struct bpp_ctx {
   std::unique_ptr<Pipeline> pipe;  // bpp_verify_submit_packed / bpp_verify_collect: lanes, tickets (built on first submit)
   std::mutex pipe_init_mu;
   uint32_t pipe_depth = 3;
+  std::shared_ptr<ProvePipeline> prove_pipe;  // bpp_prove_submit / bpp_prove_collect: lanes, tickets (built on first submit)
+  std::mutex prove_pipe_init_mu;
+  uint32_t prove_pipe_depth = 3;
 };
 
 namespace {
@@ -1059,6 +1072,7 @@ void bpp_ctx_destroy(bpp_ctx *ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   pipeline_shutdown(ctx);  // waits for the calls in flight on the lanes, joins their threads, destroys their contexts
+  prove_pipeline_shutdown(ctx);  // the same for the prove pipeline; results never collected are dropped, what it still holds is wiped
   // a call of another thread that is still inside this context (it holds the context's lock while it waits for the device) ends
   // first: destroying a context under a running call is the caller's bug, but it must not become a use of freed events
   { std::lock_guard<std::mutex> lk(ctx->mu); }
@@ -3081,7 +3095,8 @@ int bpp_batch_secret_bytes(bpp_ctx *ctx, uint64_t batch, uint64_t *nonzero) {
   BPP_CATCH(ctx, nullptr, 0)
 }
 
-int bpp_prove_secret_bytes(bpp_ctx *ctx, uint64_t *examined, uint64_t *nonzero) {
+// the context's own buffers (its lock held); the lanes of its prove pipeline are looked at afterwards, without it
+static int prove_secret_bytes_own(bpp_ctx *ctx, uint64_t *examined, uint64_t *nonzero) {
   BPP_ENTRY(ctx);
   try {
     if (!examined || !nonzero) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
@@ -3124,6 +3139,19 @@ int bpp_prove_secret_bytes(bpp_ctx *ctx, uint64_t *examined, uint64_t *nonzero) 
   BPP_CATCH(ctx, nullptr, 0)
 }
 
+int bpp_prove_secret_bytes(bpp_ctx *ctx, uint64_t *examined, uint64_t *nonzero) {
+  uint64_t seen = 0, cnt = 0;
+  int rc = prove_secret_bytes_own(ctx, examined ? &seen : nullptr, nonzero ? &cnt : nullptr);
+  if (rc != BPP_OK) return rc;
+  // the prove pipeline's lanes, their arenas and staging: each under its own lock (a lane's running call is waited for), the
+  // parent's released, so that nothing ever holds a context's lock while it asks for the pipeline's
+  rc = prove_pipeline_secret_bytes(ctx, &seen, &cnt);
+  if (rc != BPP_OK) return rc;
+  *examined = seen;
+  *nonzero = cnt;
+  return BPP_OK;
+}
+
 int bpp_profile_enable(bpp_ctx *ctx, int on) {
   if (!ctx) return BPP_ERR_BAD_HANDLE;
   ctx->profile = on != 0;
@@ -3133,16 +3161,25 @@ int bpp_profile_enable(bpp_ctx *ctx, int on) {
 
 int bpp_prove_check_stats(bpp_ctx *ctx, struct bpp_prove_check_stats *out) {
   if (!ctx || !out) return BPP_ERR_BAD_HANDLE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  *out = ctx->check_stats;
-  return BPP_OK;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    *out = ctx->check_stats;
+  }
+  return prove_pipeline_check_stats(ctx, out);
 }
 
 int bpp_prove_check_recovery_stats(bpp_ctx *ctx, uint64_t *replayed, uint64_t *mismatched) {
   if (!ctx) return BPP_ERR_BAD_HANDLE;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (replayed) *replayed = ctx->check_replayed;
-  if (mismatched) *mismatched = ctx->check_mismatched;
+  uint64_t r, m;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    r = ctx->check_replayed;
+    m = ctx->check_mismatched;
+  }
+  const int rc = prove_pipeline_recovery_stats(ctx, &r, &m);
+  if (rc != BPP_OK) return rc;
+  if (replayed) *replayed = r;
+  if (mismatched) *mismatched = m;
   return BPP_OK;
 }
 
@@ -3165,3 +3202,4 @@ int bpp_profile_get(bpp_ctx *ctx, bpp_profile *out) {
 
 #include "engine_prove.h"
 #include "engine_prove_pool.h"
+#include "engine_prove_pipe.h"

@@ -384,9 +384,11 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
       // a fresh arena starts out zero as a whole: the alignment gaps between the sub-batches' ranges and the slack at its end
       // are written by nothing and wiped by nothing, and what hipMalloc hands out is not zero -- bpp_prove_secret_bytes (and
       // anyone reading the arena) must see zeros there, not somebody's left-overs
+      // (a regrown arena may come back at the address the freed one had: the size tells, not the pointer alone)
       const uint8_t *before = ctx->prove_arena.p;
+      const size_t before_n = ctx->prove_arena.n;
       ctx->prove_arena.alloc(arena_need + 256);
-      if (ctx->prove_arena.p != before) {  // (on a stream of ours and waited for: the sub-batch streams do not wait for the null stream)
+      if (ctx->prove_arena.p != before || ctx->prove_arena.n != before_n) {  // (on a stream of ours and waited for: the sub-batch streams do not wait for the null stream)
         HIP_CHECK(hipMemsetAsync(ctx->prove_arena.p, 0, ctx->prove_arena.n, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
       }
@@ -951,40 +953,14 @@ struct MixedOutcome {
 };
 
 // the proof length of an item whose m passes RangeStatement::init, 0 otherwise
-size_t prove_item_len(const Params &P, uint32_t m) {
-  if (m == 0 || (m & (m - 1)) || P.m_max < m || m * P.n_bits < 2) return 0;
-  uint32_t rounds = 0;
-  while ((1u << rounds) < m * P.n_bits) rounds++;
-  return 1 + 32 * (size_t)(P.t + 5 + 2 * rounds);
-}
+size_t prove_item_len(const Params &P, uint32_t m) { return prove_item_len_host(ParamShape{P.n_bits, P.m_max, P.t}, m); }
 
-// the host-side checks of a one-item bpp_prove_batch on `it`, in the same order and with the same codes and messages.
+// the host-side checks of a one-item bpp_prove_batch on `it`, in the same order and with the same codes and messages
+// (prove_job_host.h has them: bpp_prove_submit runs the same routine before it copies an item).
 // openings: an item of bpp_prove_openings / bpp_prove_pool_openings, which may come without commitments and whose commitments go
 // to a slot of commit_stride bytes.
 void prove_item_check(const Params &P, const bpp_prove_item &it, size_t proof_stride, bool openings = false, size_t commit_stride = 0) {
-  const uint32_t n = P.n_bits, t = P.t, m = it.m;
-  if (m == 0 || (m & (m - 1))) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Number of commitments must be a power of two"};
-  if (P.m_max < m) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Not enough generators for this statement"};
-  if (m * n < 2) throw ProofErr{BPP_ERR_INVALID_LENGTH, "bit_length * aggregation factor must be at least 2"};
-  uint32_t rounds = 0;
-  while ((1u << rounds) < m * n) rounds++;
-  if (proof_stride < prove_item_len(P, m)) throw ProofErr{BPP_ERR_INVALID_LENGTH, "proof_stride too small"};
-  if (openings && commit_stride < (size_t)32 * m) throw ProofErr{BPP_ERR_INVALID_LENGTH, "commit_stride too small"};
-  if (!it.values || !it.blindings32 || (!it.commitments32 && !openings) || !it.rng_bytes || (!it.min_values && it.min_present))
-    throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "null witness / statement field"};
-  if (it.seed_nonce32 && m > 1) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Mask recovery is not supported with an aggregated statement"};
-  if (it.rng_len < 32 * (size_t)(rounds + 3))
-    throw ProofErr{BPP_ERR_INVALID_LENGTH, "not enough external randomness: need (rounds + 3) * 32 bytes"};
-  for (uint32_t j = 0; j < m; j++) {
-    if (n < 64 && (it.values[j] >> n) > 0) throw ProofErr{BPP_ERR_INVALID_LENGTH, "Value exceeds bit vector capacity!"};
-    const bool present = it.min_present ? it.min_present[j] != 0 : false;
-    if (present && it.values[j] < it.min_values[j]) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Minimum value is larger than value"};
-  }
-  for (uint32_t q = 0; q < m * t; q++)
-    if (!sc_is_canonical(it.blindings32 + 32 * (size_t)q)) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "blinding factor is not canonical"};
-  if (it.seed_nonce32 && !sc_is_canonical(it.seed_nonce32)) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "seed nonce is not canonical"};
-  if (it.transcript_state && it.transcript_state[200] >= BPP_STROBE_R)
-    throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "transcript state has pos >= rate"};
+  prove_item_check_host(ParamShape{P.n_bits, P.m_max, P.t}, it, proof_stride, openings, commit_stride);
 }
 
 // The mixed call (the context's lock held, its device current): proof i at proofs_out + i * proof_stride, its length in

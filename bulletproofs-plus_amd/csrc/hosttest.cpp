@@ -8,6 +8,7 @@
 #include "wkeccak.h"
 #include "recode.h"
 #include "upload_host.h"
+#include "prove_job_host.h"
 // the uniform-access scalar multiplication (ct.h) with its table reads RECORDED: BPP_CT_TOUCH(entry) appends the entry index
 #include <vector>
 static thread_local std::vector<uint8_t> *g_ct_trace = nullptr;
@@ -201,4 +202,25 @@ int ht_fb_recode(const uint8_t a[32], uint32_t n_gens, int16_t *digits /* 32 */,
   fb_recode(digits, x, g);
   *wbits = g.wbits;
   return (int)g.items; }
+// the job copy bpp_prove_submit takes of its caller's items (prove_job_host.h: the per-item check, the deep copy, the wipe):
+// codes_out[i] = what the check found for item i; *copy_bytes = the size of the copy; returns the number of items copied, or -1
+// when the copy does not equal its source byte for byte or does not read zero after the wipe
+int ht_prove_job_copy(uint32_t n_bits, uint32_t m_max, uint32_t t, const bpp_prove_item *items, size_t n, size_t proof_stride, int openings,
+                      size_t commit_stride, int *codes_out, size_t *copy_bytes) {
+  const ParamShape P{n_bits, m_max, t};
+  ProveJobCopy c;
+  c.take(P, items, n, proof_stride, openings != 0, commit_stride);
+  for (size_t i = 0; i < n; i++) codes_out[i] = c.code[i];
+  if (copy_bytes) *copy_bytes = c.store_bytes;
+  bool same = true;
+  for (size_t k = 0; k < c.items.size(); k++) {
+    const bpp_prove_item &a = items[c.index[k]], &b = c.items[k];
+    same = same && a.m == b.m && memcmp(a.values, b.values, 8 * (size_t)a.m) == 0 &&
+           memcmp(a.blindings32, b.blindings32, 32 * (size_t)a.m * t) == 0 && memcmp(a.rng_bytes, b.rng_bytes, b.rng_len) == 0 &&
+           (a.seed_nonce32 != nullptr) == (b.seed_nonce32 != nullptr) && (!a.seed_nonce32 || memcmp(a.seed_nonce32, b.seed_nonce32, 32) == 0);
+  }
+  const int copied = (int)c.items.size();
+  c.wipe();
+  for (size_t i = 0; i < c.store_bytes; i++) same = same && c.bytes()[i] == 0;
+  return same ? copied : -1; }
 }

@@ -274,6 +274,140 @@ class ProvePool:
             self.handle = ctypes.c_void_p()
 
 
+class ProvePipeline:
+    """bpp_prove_submit / bpp_prove_collect on one engine: prove calls in flight from ONE thread.  submit(...) /
+    submit_openings(...) take what RangeProof.prove_batch_mixed / RangeProof.prove_openings take and return a ticket at once (the
+    engine has its own copy of the items by then); collect(ticket) blocks and returns what those calls return -- one RangeProof or
+    ProofError per item -- and raises what they raise.  Tickets may be collected in any order.  `depth` lanes (1..8), each a
+    context with the engine's prover options as they are at the first submit; the depth can only be set before the first submit
+    of the engine (depth=None keeps what the engine has)."""
+
+    STRIDE = ProvePool.STRIDE
+
+    def __init__(self, params, depth=3):
+        self.params, self.engine = params, params.engine
+        if depth is not None:
+            api._check(self.engine.lib.bpp_prove_pipeline_depth(self.engine.ctx, int(depth)), self.engine.ctx)
+        self._jobs = {}  # ticket -> what collect needs: the engine's ticket (None: no item reached the engine), the marshalled items, ...
+        self._next = 1
+
+    def _submit(self, marshalled, openings, cstride):
+        _p, items, n, _keep = marshalled
+        ticket = c_uint64()
+        err = ctypes.create_string_buffer(256)
+        api._check(self.engine.lib.bpp_prove_submit(self.engine.ctx, self.params.handle, items, n, self.STRIDE, 1 if openings else 0, cstride,
+                                                    byref(ticket), err, 256), None, err)
+        return ticket.value
+
+    def _ticket(self, job):
+        t = self._next
+        self._next += 1
+        self._jobs[t] = job
+        return t
+
+    def submit(self, transcripts, statements, witnesses, rng_bytes):
+        """RangeProof.prove_batch_mixed, submitted: returns a ticket"""
+        if not statements or len(statements) != len(witnesses) or len(transcripts) != len(statements) or \
+                len(rng_bytes) != len(statements):
+            raise api.ProofError(api.ProofErrorKind.InvalidArgument, "Range statements, witnesses, transcripts length mismatch")
+        res, keep = [None] * len(statements), []
+        for i, (tr, st, w, rb) in enumerate(zip(transcripts, statements, witnesses, rng_bytes)):
+            try:
+                api.RangeProof._prove_marshal([tr], [st], [w], [rb])
+                keep.append(i)
+            except api.ProofError as e:
+                res[i] = e
+        job = {"openings": False, "res": res, "keep": keep, "engine_ticket": None}
+        if keep:
+            pick = lambda a: [a[i] for i in keep]  # noqa: E731
+            job["marshalled"] = api.RangeProof._prove_marshal(pick(transcripts), pick(statements), pick(witnesses), pick(rng_bytes))
+            job["engine_ticket"] = self._submit(job["marshalled"], False, 0)
+        return self._ticket(job)
+
+    def submit_openings(self, transcripts, witnesses, minimum_value_promises, seed_nonces, rng_bytes):
+        """RangeProof.prove_openings (on this pipeline's parameters), submitted: returns a ticket"""
+        n = len(witnesses)
+        res, keep = [None] * n, []
+        for i in range(n):
+            try:
+                api.RangeProof._openings_marshal([transcripts[i]], [witnesses[i]], [minimum_value_promises[i]], [seed_nonces[i]],
+                                                 [rng_bytes[i]], self.params)
+                keep.append(i)
+            except api.ProofError as e:
+                res[i] = e
+        job = {"openings": True, "res": res, "keep": keep, "engine_ticket": None, "witnesses": [witnesses[i] for i in keep],
+               "promises": [list(minimum_value_promises[i]) for i in keep], "nonces": [seed_nonces[i] for i in keep]}
+        if keep:
+            pick = lambda a: [a[i] for i in keep]  # noqa: E731
+            job["marshalled"] = api.RangeProof._openings_marshal(pick(transcripts), pick(witnesses), pick(minimum_value_promises),
+                                                                 pick(seed_nonces), pick(rng_bytes), self.params)
+            job["cstride"] = 32 * max(len(w.openings) for w in job["witnesses"])
+            job["engine_ticket"] = self._submit(job["marshalled"], True, job["cstride"])
+        return self._ticket(job)
+
+    def done(self, ticket):
+        """True once collect(ticket) would not wait; never blocks"""
+        job = self._jobs[ticket]
+        if job["engine_ticket"] is None:
+            return True
+        d = ctypes.c_int()
+        api._check(self.engine.lib.bpp_prove_ticket_done(self.engine.ctx, job["engine_ticket"], byref(d)), None)
+        return bool(d.value)
+
+    def collect(self, ticket):
+        """blocks until the ticket's call is done: the list RangeProof.prove_batch_mixed returns, or for a ticket of
+        submit_openings the (statements, proofs) pair RangeProof.prove_openings returns"""
+        job = self._jobs.pop(ticket)
+        res, keep, openings = job["res"], job["keep"], job["openings"]
+        sts = list(res)
+        if not keep:
+            return (sts, res) if openings else res
+        eng, params = self.engine, self.params
+        _p, items, n, _keep = job["marshalled"]
+        stride, cstride = self.STRIDE, job.get("cstride", 0)
+        out = (ctypes.c_uint8 * (stride * n))()
+        comms = (ctypes.c_uint8 * (cstride * n))() if openings else None
+        lens = (c_size_t * n)()
+        status = (ctypes.c_int * n)()
+        err = ctypes.create_string_buffer(256)
+        rc = eng.lib.bpp_prove_collect(eng.ctx, job["engine_ticket"], comms, out, lens, status, err, 256)
+        codes = [status[k] for k in range(n)]
+        faults = [c for c in [rc] + codes if c < 0 and c != api.EngineError.SELF_CHECK]
+        if faults:
+            api._check(min(faults), None, err)
+        raw, craw = bytes(out), bytes(comms) if openings else b""
+        for k, i in enumerate(keep):
+            if codes[k] == 0:
+                res[i] = api.RangeProof.from_bytes(raw[k * stride:k * stride + lens[k]])
+                if openings:
+                    cs = [craw[k * cstride + 32 * j:k * cstride + 32 * j + 32] for j in range(items[k].m)]
+                    sts[i] = api.RangeStatement.init(params, cs, job["promises"][k], job["nonces"][k])
+                continue
+            # (the parent context holds this ticket's note of failed mask-recovery replays since the collect)
+            if openings:
+                first = None
+                if codes[k] == api.EngineError.SELF_CHECK and job["nonces"][k] is not None:
+                    o = job["witnesses"][k].openings[0]
+                    first = api._buf(params.commit(o.v, o.r))
+                eng.lib.bpp_prove_openings_item_message(eng.ctx, params.handle, byref(items[k]), first, cstride, stride, codes[k], err, 256)
+            else:
+                eng.lib.bpp_prove_item_message(eng.ctx, params.handle, byref(items[k]), stride, codes[k], err, 256)
+            msg = err.value.decode(errors="replace")
+            if codes[k] == api.EngineError.SELF_CHECK:
+                res[i] = sts[i] = api.EngineError("bpp engine error %d: %s" % (codes[k], msg), codes[k])
+            else:
+                res[i] = sts[i] = api.ProofError(codes[k], msg)
+        return (sts, res) if openings else res
+
+    def close(self):
+        """collects and drops whatever is still outstanding (the lanes live as long as the engine does)"""
+        for t in list(self._jobs):
+            try:
+                self.collect(t)
+            except (api.ProofError, api.EngineError):
+                pass
+
+
 def verify_groups_actions(rb, bounds, actions):
     """bpp_verify_resident_groups_actions: one VerifyAction per group -> (result dicts, masks [n, t, 32], present [n])"""
     G = len(bounds) - 1

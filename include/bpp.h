@@ -527,6 +527,44 @@ int bpp_prove_pool_check_stats(bpp_prove_pool *p, struct bpp_prove_check_stats *
  * is not counted here.  Either pointer may be NULL.  The pool's form sums its lanes. */
 int bpp_prove_check_recovery_stats(bpp_ctx *ctx, uint64_t *replayed, uint64_t *mismatched);
 int bpp_prove_pool_check_recovery_stats(bpp_prove_pool *p, uint64_t *replayed, uint64_t *mismatched);
+/* Prove calls in flight from ONE thread and ONE context: the prover's form of bpp_verify_submit_packed / bpp_verify_collect.
+ * bpp_prove_submit hands a whole prove call to one of `depth` lanes and returns a ticket; bpp_prove_collect blocks until that call
+ * is done and returns EXACTLY what the blocking call over the same items returns -- bpp_prove_batch_mixed(ctx, params, items,
+ * n_items, proofs_out, proof_stride, proof_lens, item_status, ...) for a ticket submitted with openings == 0 (every item brings
+ * commitments32; commit_stride is ignored), bpp_prove_openings(..., commitments_out, commit_stride, proofs_out, proof_stride, ...) for
+ * one submitted with openings != 0 (an item with commitments32 == NULL has them made by the engine): the proof and commitment
+ * bytes, proof_lens, item_status, the zeroed slots of failed items, the return code and the message in errbuf.  A failed item
+ * never stops the others.  The output buffers given to collect have the geometry declared at submit.
+ * The caller's buffers are free when bpp_prove_submit returns: the items array and everything it points to (values, blinding
+ * factors, commitments, promises, seed nonce, transcript state or label, rng bytes).  submit checks every item on the calling
+ * thread and takes its own copy of the ones that pass; the copy's witness bytes are wiped as soon as the lane's call has returned,
+ * on every path, and at bpp_ctx_destroy at the latest.
+ * A lane is a context of its own (the prover's streams, arena and staging: count each against the hardware queues) with a worker
+ * thread, made on the first submit with ctx's options AS THEY ARE THEN: bpp_ctx_set_option after the first submit does not reach
+ * the lanes, and the self-check's tamper knobs are never copied.  With "prove_check" (and "prove_check_recovery") set before the
+ * first submit every lane checks its calls as a context does; bpp_prove_check_stats, bpp_prove_check_recovery_stats and
+ * bpp_prove_secret_bytes of ctx then include its lanes, and bpp_prove_collect copies the lane's note for that ticket into ctx, so that
+ * bpp_prove_item_message / bpp_prove_openings_item_message on ctx right after the collect answer for that ticket.
+ * Lanes are claimed round-robin in ticket order; submit blocks only while the lane whose turn it is still runs its previous job (a
+ * lane is free once its job is done, collected or not).  Tickets may be collected in any order and from any thread; they are a
+ * number space of their own, unknown to bpp_verify_collect.  Blocking prove and verify calls on ctx, and a bpp_prove_pool made from
+ * it, keep working beside the pipeline.  bpp_ctx_destroy waits for the jobs in flight and drops results never collected.
+ * bpp_prove_submit itself fails (no ticket, *ticket untouched) only for what needs no look at an item: ctx == NULL or an unknown
+ * params handle -> BPP_ERR_BAD_HANDLE, no usable device -> BPP_ERR_NO_DEVICE, items == NULL, n_items == 0 or ticket == NULL ->
+ * BPP_ERR_INVALID_ARGUMENT "null argument".  Everything else, per-item failures included, is reported by collect.
+ * bpp_prove_collect with proofs_out == NULL or proof_lens == NULL (or commitments_out == NULL for an openings ticket) returns
+ * BPP_ERR_INVALID_ARGUMENT and leaves the ticket collectable; an unknown ticket, one already collected or a ticket of the verify
+ * pipeline -> BPP_ERR_BAD_HANDLE "unknown ticket", from bpp_prove_ticket_done as well.
+ * Messages of bpp_prove_submit and bpp_prove_collect go to errbuf alone, as those of the verify pipeline do: they may run on any
+ * thread beside a blocking call that holds the context, so they leave bpp_ctx_last_error to that call.
+ * bpp_prove_pipeline_depth: lanes of the prove pipeline, 1..8, default 3; only before the first bpp_prove_submit of the context.
+ * bpp_prove_ticket_done never blocks: *done = 1 once bpp_prove_collect would not wait. */
+int bpp_prove_pipeline_depth(bpp_ctx *ctx, uint32_t depth);
+int bpp_prove_submit(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, size_t proof_stride, int openings,
+                     size_t commit_stride, uint64_t *ticket, char *errbuf, size_t errbuf_len);
+int bpp_prove_collect(bpp_ctx *ctx, uint64_t ticket, uint8_t *commitments_out, uint8_t *proofs_out, size_t *proof_lens,
+                      int *item_status, char *errbuf, size_t errbuf_len);
+int bpp_prove_ticket_done(bpp_ctx *ctx, uint64_t ticket, int *done);
 
 /* ---- parity / diagnostics: intermediates of the last verify on `batch`, for differential tests ---- */
 #define BPP_TRACE_CHALLENGES 1     /* per proof (rmax+3) x 32: y, z, e_0.., e_final (canonical), rmax = bpp_batch_shape's max_rounds

@@ -63,6 +63,57 @@ class Engine {
   Engine &operator=(const Engine &) = delete;
   bpp_ctx *ctx() const { return ctx_; }
 
+  // Prove calls in flight from ONE thread (bpp_prove_submit / bpp_prove_collect).  prove_submit hands a whole call -- the items of
+  // a bpp_prove_batch_mixed, or with openings = true of a bpp_prove_openings (an item may come without commitments) -- to a lane of
+  // this engine and returns at once; the items and everything they point to are free again then.  prove_collect blocks and gives
+  // what the blocking call over the same items gives, item by item; an item that fails never stops the others.
+  struct ProveTicket {
+    uint64_t id = 0;
+    size_t n_items = 0, commit_stride = 0;
+    bool openings = false;
+  };
+  struct ProveResult {
+    std::vector<std::vector<uint8_t>> proofs;       // per item; empty for an item that failed
+    std::vector<std::vector<uint8_t>> commitments;  // openings tickets: per item 32 bytes per opening, as the call returned them
+    std::vector<int> status;                        // per item: 0, a ProofErrorKind, or a negative engine code
+    int code = 0;                                   // the call's return value: the first failing item's
+    std::string message;
+  };
+  static constexpr size_t kProofStride = 1 + 32 * (6 + 5 + 2 * 12);  // the longest proof any parameters make
+  void prove_pipeline_depth(uint32_t depth) { check(bpp_prove_pipeline_depth(ctx_, depth), bpp_ctx_last_error(ctx_)); }
+  ProveTicket prove_submit(uint64_t params, const bpp_prove_item *items, size_t n_items, bool openings = false, size_t commit_stride = 0) {
+    ProveTicket t;
+    t.n_items = n_items;
+    t.openings = openings;
+    t.commit_stride = openings ? commit_stride : 0;
+    char err[256] = {0};
+    check(bpp_prove_submit(ctx_, params, items, n_items, kProofStride, openings ? 1 : 0, commit_stride, &t.id, err, sizeof(err)), err);
+    return t;
+  }
+  bool prove_ticket_done(const ProveTicket &t) {
+    int done = 0;
+    check(bpp_prove_ticket_done(ctx_, t.id, &done), "unknown ticket");
+    return done != 0;
+  }
+  ProveResult prove_collect(const ProveTicket &t) {
+    std::vector<uint8_t> out(kProofStride * t.n_items), comm(t.openings ? t.commit_stride * t.n_items : 0);
+    std::vector<size_t> lens(t.n_items, 0);
+    ProveResult r;
+    r.status.assign(t.n_items, 0);
+    char err[256] = {0};
+    r.code = bpp_prove_collect(ctx_, t.id, t.openings ? comm.data() : nullptr, out.data(), lens.data(), r.status.data(), err, sizeof(err));
+    r.message = err;
+    bool any_status = false;
+    for (int s : r.status) any_status = any_status || s != 0;
+    if (r.code != 0 && !any_status) check(r.code, err);  // (a finding of the call itself: an unknown ticket, an engine fault)
+    for (size_t i = 0; i < t.n_items; i++) {
+      const bool ok = r.status[i] == 0;
+      r.proofs.emplace_back(out.begin() + i * kProofStride, out.begin() + i * kProofStride + (ok ? lens[i] : 0));
+      if (t.openings) r.commitments.emplace_back(comm.begin() + i * t.commit_stride, comm.begin() + (i + 1) * t.commit_stride);
+    }
+    return r;
+  }
+
  private:
   bpp_ctx *ctx_ = nullptr;
 };

@@ -305,6 +305,13 @@ extern "C" {
     pub fn bpp_prove_pool_check_stats(p: *mut bpp_prove_pool, out: *mut bpp_prove_check_stats) -> c_int;
     pub fn bpp_prove_check_recovery_stats(ctx: *mut bpp_ctx, replayed: *mut u64, mismatched: *mut u64) -> c_int;
     pub fn bpp_prove_pool_check_recovery_stats(p: *mut bpp_prove_pool, replayed: *mut u64, mismatched: *mut u64) -> c_int;
+    // prove calls in flight from one thread: lanes inside one context, tickets, results equal to the blocking calls'
+    pub fn bpp_prove_pipeline_depth(ctx: *mut bpp_ctx, depth: u32) -> c_int;
+    pub fn bpp_prove_submit(ctx: *mut bpp_ctx, params: u64, items: *const bpp_prove_item, n_items: usize, proof_stride: usize,
+                            openings: c_int, commit_stride: usize, ticket: *mut u64, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_collect(ctx: *mut bpp_ctx, ticket: u64, commitments_out: *mut u8, proofs_out: *mut u8, proof_lens: *mut usize,
+                             item_status: *mut c_int, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_ticket_done(ctx: *mut bpp_ctx, ticket: u64, done: *mut c_int) -> c_int;
     // diagnostics
     pub fn bpp_batch_trace(ctx: *mut bpp_ctx, batch: u64, what: c_int, out: *mut u8, out_len: usize, written: *mut usize) -> c_int;
     pub fn bpp_batch_shape(ctx: *mut bpp_ctx, batch: u64, n_items: *mut u32, max_rounds: *mut u32, max_mn: *mut u32, total_dyn: *mut u32,

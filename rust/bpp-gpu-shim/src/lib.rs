@@ -391,6 +391,68 @@ impl Engine {
         }).collect())
     }
 
+    /// lanes of the prove pipeline (1..8, default 3); only before the first `prove_submit` of this engine
+    pub fn prove_pipeline_depth(&self, depth: u32) -> Result<(), GpuError> {
+        map_rc(unsafe { ffi::bpp_prove_pipeline_depth(self.ctx, depth) }, self.last_error())
+    }
+
+    /// A whole prove call handed to a lane of this engine (bpp_prove_submit): returns at once with a ticket, and `items` -- and
+    /// everything they borrow -- are free again then (the engine has checked every item and keeps its own copy of the ones that
+    /// pass, wiped as soon as the lane's call has returned).  `openings`: the ticket is a `prove_openings` call (an item may come
+    /// with an empty `commitments` slice), else a `prove_batch_mixed` call.  Several tickets may be outstanding: with as many as
+    /// lanes, one thread keeps the device as busy as several threads with an engine each.
+    pub fn prove_submit(&self, params: &Params, items: &[ProveItem<'_>], openings: bool) -> Result<ProveTicket, GpuError> {
+        let keep = if openings { RawProveItems::new_openings(items) } else { RawProveItems::new(items) };
+        let stride = 1 + 32 * (6 + 5 + 2 * 12);
+        let cstride = if openings { 32 * items.iter().map(|i| i.values.len()).max().unwrap_or(1) } else { 0 };
+        let mut id = 0u64;
+        let mut err = [0 as core::ffi::c_char; 256];
+        let rc = unsafe {
+            ffi::bpp_prove_submit(self.ctx, params.handle, keep.raw.as_ptr(), keep.raw.len(), stride, openings as c_int, cstride, &mut id,
+                                  err.as_mut_ptr(), err.len())
+        };
+        map_rc(rc, unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned())?;
+        Ok(ProveTicket { id, openings, stride, cstride, m: items.iter().map(|i| i.values.len()).collect() })
+    }
+
+    /// true once `prove_collect` on this ticket would not wait; never blocks
+    pub fn prove_ticket_done(&self, ticket: &ProveTicket) -> Result<bool, GpuError> {
+        let mut done: c_int = 0;
+        map_rc(unsafe { ffi::bpp_prove_ticket_done(self.ctx, ticket.id, &mut done) }, String::from("unknown ticket"))?;
+        Ok(done != 0)
+    }
+
+    /// Blocks until the ticket's call is done (bpp_prove_collect) and returns what `prove_openings` / `prove_batch_mixed` over the
+    /// same items return: per item (its m x 32 commitment bytes -- empty for a ticket without `openings` --, its `to_bytes()`), or
+    /// the item's error.  The items are gone by now, so only the call's first failing item carries its message; the others carry
+    /// their code.  Any order, any thread.
+    #[allow(clippy::type_complexity)]
+    pub fn prove_collect(&self, ticket: ProveTicket) -> Result<Vec<Result<(Vec<u8>, Vec<u8>), GpuError>>, GpuError> {
+        let n = ticket.m.len();
+        let (stride, cstride) = (ticket.stride, ticket.cstride);
+        let mut out = vec![0u8; stride * n];
+        let mut comms = vec![0u8; cstride * n];
+        let mut lens = vec![0usize; n];
+        let mut status = vec![0 as c_int; n];
+        let mut err = [0 as core::ffi::c_char; 256];
+        let rc = unsafe {
+            ffi::bpp_prove_collect(self.ctx, ticket.id, if ticket.openings { comms.as_mut_ptr() } else { ptr::null_mut() }, out.as_mut_ptr(),
+                                   lens.as_mut_ptr(), status.as_mut_ptr(), err.as_mut_ptr(), err.len())
+        };
+        let msg = unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned();
+        if rc != 0 && status.iter().all(|&s| s == 0) {  // (a finding of the call itself: an unknown ticket, an engine fault)
+            map_rc(rc, msg.clone())?;
+        }
+        let first = status.iter().position(|&s| s != 0);
+        Ok((0..n).map(|k| {
+            if status[k] == 0 {
+                let c = if ticket.openings { comms[k * cstride..k * cstride + 32 * ticket.m[k]].to_vec() } else { Vec::new() };
+                return Ok((c, out[k * stride..k * stride + lens[k]].to_vec()));
+            }
+            map_rc(status[k], if Some(k) == first { msg.clone() } else { String::new() }).map(|_| (Vec::new(), Vec::new()))
+        }).collect())
+    }
+
     /// Arc::clone of a parameter set created on another context of the same device
     pub fn retain(&self, params: &Params) -> Result<Params, GpuError> {
         map_rc(unsafe { ffi::bpp_params_retain(self.ctx, params.handle) }, self.last_error())?;
@@ -672,6 +734,15 @@ impl Batcher {
         let rc = unsafe { ffi::bpp_batcher_verify(self.raw, &raw_in, err.as_mut_ptr(), err.len()) };
         map_rc(rc, unsafe { CStr::from_ptr(err.as_ptr()) }.to_string_lossy().into_owned())
     }
+}
+
+/// a prove call in flight (`Engine::prove_submit`); collect it on the engine that issued it
+pub struct ProveTicket {
+    id: u64,
+    openings: bool,
+    stride: usize,
+    cstride: usize,
+    m: Vec<usize>,  // per item: its aggregation factor
 }
 
 /// `bpp_prove_item`s of borrowed `ProveItem`s, with the promise arrays they point into
