@@ -61,6 +61,11 @@ class ProveCheckStats(Structure):
     _fields_ = [(n, c_uint64) for n in ("calls", "proofs", "batch_failures", "remade", "failed")]
 
 
+class VerifyCheckStats(Structure):
+    """struct bpp_verify_check_stats: what the rechecks of rejections ("verify_check" = 1) of a context have done"""
+    _fields_ = [(n, c_uint64) for n in ("calls", "rechecked_groups", "confirmed", "overturned", "tie_breaks", "undecided")]
+
+
 class RuntimeInfo(Structure):
     """bpp_runtime_info: what the library sees of its runtime preconditions (hardware queues, contexts, the small-call gate)"""
     _fields_ = [("device", c_int), ("contexts", c_uint32), ("contexts_peak", c_uint32), ("hw_queues", c_uint32),
@@ -163,6 +168,9 @@ SYMBOLS = [
     ("bpp_prove_pool_check_stats", c_int, [c_void_p, POINTER(ProveCheckStats)]),
     ("bpp_prove_check_recovery_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     ("bpp_prove_pool_check_recovery_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
+    ("bpp_verify_check_resolve", c_int, [POINTER(ShardResult), c_int, POINTER(ShardResult), POINTER(c_int)]),
+    ("bpp_verify_check_stats", c_int, [c_void_p, POINTER(VerifyCheckStats)]),
+    ("bpp_batcher_verify_check_stats", c_int, [c_void_p, POINTER(VerifyCheckStats)]),
     ("bpp_prove_pipeline_depth", c_int, [c_void_p, c_uint32]),
     ("bpp_prove_submit", c_int, [c_void_p, c_uint64, POINTER(ProveItem), c_size_t, c_size_t, c_int, c_size_t, POINTER(c_uint64),
                                  c_void_p, c_size_t]),

@@ -166,6 +166,14 @@ class Engine:
         _check(self.lib.bpp_prove_check_stats(self.ctx, byref(s)), self.ctx)
         return {n: int(getattr(s, n)) for n, _ in _lib.ProveCheckStats._fields_}
 
+    def verify_check_stats(self):
+        """bpp_verify_check_stats: what the rechecks of rejections ("verify_check" = 1) of this context and its pipeline lanes have
+        done -- verifications with the option on, groups rejected on the device in pass 1, those whose returned outcome is pass 1's,
+        those whose outcome is not, groups that needed the third pass, groups with three different outcomes"""
+        s = _lib.VerifyCheckStats()
+        _check(self.lib.bpp_verify_check_stats(self.ctx, byref(s)), self.ctx)
+        return {n: int(getattr(s, n)) for n, _ in _lib.VerifyCheckStats._fields_}
+
     def prove_check_recovery_stats(self):
         """bpp_prove_check_recovery_stats ("prove_check" = 1 and "prove_check_recovery" = 1): proofs with a seed nonce whose mask
         recovery the self-check replayed, and how many of them did not return the witness's blinding factors"""

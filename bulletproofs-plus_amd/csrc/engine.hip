@@ -36,6 +36,7 @@
 #include "kernels_prove.h"
 #include "kernels_verify.h"
 #include "msm.h"
+#include "msm_plain.h"
 #include "prove_job_host.h"
 #include "upload_host.h"
 
@@ -380,6 +381,11 @@ struct MsmWork {
   MsmPlan plan{};
   uint32_t max_group_terms = 0;
   bool split = false;  // half-scalar plan (small verifier calls): every term twice, 127-bit windows
+  // the plain MSM (msm_plain.h: "msm_plain" = 1, pass 2 of "verify_check"): the group offsets as the host made them, one partial
+  // sum per wavefront, the ids of the groups to evaluate (mapped: the kernels read them where the host wrote them)
+  std::vector<uint32_t> h_goff;
+  DevBuf<ge> plain_part;
+  PinnedBuf<uint32_t> plain_list;
 };
 
 struct Batch {
@@ -432,6 +438,7 @@ struct Batch {
   uint32_t G = 0;
   std::vector<uint32_t> h_group_first;
   PinnedBuf<uint8_t> h_rng, h_weights, h_masks;  // mapped: written / read by the kernels directly (PinnedBuf)
+  PinnedBuf<uint8_t> h_masks_check;  // "verify_check": where passes 2 and 3 leave their masks (verify_flow wipes it before it returns)
   PinnedBuf<uint8_t> h_wide;  // chain mode 2: the host sponges' 64 bytes per proof, reduced on the device
   PinnedBuf<uint32_t> h_status, h_ident;
   // k_results_out writes one summary word per BPP_STATUS_BLOCK proofs and a block's words only when there is something in them;
@@ -582,8 +589,20 @@ struct bpp_ctx {
   struct Options {
     int transcripts_wave = -1, tables_wave = -1, side_decompress = -1, msm_c_bias = -1, msm_c_max = -1, msm_c_add = -1, msm_rc2 = -1, msm_quad = -1, msm_final_quad = -1,
         fb_threads = -1, prove_subs = -1, msm_split = -1, fused_columns = -1, prove_prio = -1, prove_fused = -1, static_gemm = -1, lazy_columns = -1, ct = -1, prove_parts = -1, prove_waves = -1, prove_fifo = -1, chain = -1, chain_test_zero = 0, wait = -1, ct_back = -1, chain_inline = -1, wide_in_lanes = -1,
-        prove_check = -1, prove_check_recovery = -1;
+        prove_check = -1, prove_check_recovery = -1, msm_plain = -1, verify_check = -1;
   } opt;
+  // "verify_check" = 1 (verify_flow): what the rechecks of this context's verifications have done; the prover's self-check runs
+  // its verifications with the recheck off (verify_check_off > 0) -- a rejection there is already answered by a remake
+  struct bpp_verify_check_stats vcheck_stats{};
+  int verify_check_off = 0;
+  // test knobs of the recheck (bpp_ctx_set_option only, never copied to a lane): on the context's NEXT verification, in the passes
+  // of the bit mask `passes` (1, 2, 4), the host copy of the results of group `group` is altered after the wait and before findings
+  // are raised -- kind 1: identity flag 0; 2: identity flag 1 and the device bits of the group's status words cleared; 3 / 4:
+  // BPP_ST_TRANSCRIPT_FAIL / BPP_ST_DECOMPRESS_FAIL set in the status word of the group's first proof.  A kind above 15 holds one
+  // kind per pass, four bits each, pass 1 in the lowest (three different outcomes need two different alterations)
+  struct VerifyTamper {
+    int passes = 0, group = 0, kind = 0;
+  } vtamper;
   // the prover's self-check ("prove_check" = 1, engine_prove.h: prove_self_check): the verification batch it keeps between calls
   // (the next check's upload adopts its buffers, as the next upload adopts spare_batch's), the remembered waits of ITS
   // verifications (the prover's and the caller's verifications keep theirs), its counters
@@ -680,6 +699,12 @@ const OptionName kOptions[] = {
     // recovered masks with the witness's blinding factors on the device (engine_prove.h: check_verify); 0 / -1: off.  Without
     // "prove_check" it does nothing
     {"prove_check_recovery", "BPP_PROVE_CHECK_RECOVERY", &bpp_ctx::Options::prove_check_recovery},
+    // 1: bpp_msm_vartime, bpp_msm_vartime_batched and bpp_msm_mixed through the plain double-and-add kernels (msm_plain.h) instead
+    // of the bucket method; 0 / -1: off
+    {"msm_plain", "BPP_MSM_PLAIN", &bpp_ctx::Options::msm_plain},
+    // 1: a group that a verification rejects on the device (tiers PASS1, PASS2, MSM) is verified once more under the complementary
+    // kernel forms with the plain MSM, and a third time when the two disagree (verify_flow); 0 / -1: off
+    {"verify_check", "BPP_VERIFY_CHECK", &bpp_ctx::Options::verify_check},
 };
 struct TamperName {
   const char *name;
@@ -691,6 +716,15 @@ const TamperName kTamperKnobs[] = {
     {"prove_check_tamper_xor", &bpp_ctx::CheckTamper::mask},
     {"prove_check_tamper_times", &bpp_ctx::CheckTamper::times},
     {"prove_check_tamper_nonce", &bpp_ctx::CheckTamper::nonce},
+};
+struct VerifyTamperName {
+  const char *name;
+  int bpp_ctx::VerifyTamper::*field;
+};
+const VerifyTamperName kVerifyTamperKnobs[] = {
+    {"verify_check_tamper", &bpp_ctx::VerifyTamper::passes},
+    {"verify_check_tamper_group", &bpp_ctx::VerifyTamper::group},
+    {"verify_check_tamper_kind", &bpp_ctx::VerifyTamper::kind},
 };
 void options_from_env(bpp_ctx *c) {
   for (const OptionName &o : kOptions)
@@ -875,6 +909,7 @@ void msm_plan_alloc(bpp_ctx *ctx, MsmWork &w, const std::vector<uint32_t> &goff,
   w.plan = plan;
   w.split = split;
   w.max_group_terms = maxg;
+  w.h_goff = goff;
   const size_t nbk = (size_t)G * plan.K * plan.nb;
   w.counts.alloc(nbk);
   w.starts.alloc(nbk);
@@ -961,6 +996,56 @@ void msm_run(bpp_ctx *ctx, MsmWork &w, const sc *scalars, PointTables tabs, Stag
   HIP_CHECK(hipGetLastError());
 }
 
+// The plain MSM (msm_plain.h) over the groups `groups` of term lists that are already on the device (w.term_sidx, w.term_pidx,
+// w.group_off, unsplit; goff = the same offsets on the host): R[g] and is_identity[g] of those groups, every other group's
+// entries untouched.  Nothing of msm.h's plan is looked at.
+void msm_plain_run(bpp_ctx *ctx, MsmWork &w, const std::vector<uint32_t> &goff, const sc *scalars, const niels *tab_a, const niels *tab_b,
+                   uint32_t n_a, const std::vector<uint32_t> &groups) {
+  if (groups.empty()) return;
+  uint32_t maxg = 0;
+  for (uint32_t g : groups) {
+    if ((size_t)g + 1 >= goff.size()) throw EngineError{BPP_ERR_ENGINE, "plain MSM: group out of range"};
+    maxg = std::max(maxg, goff[g + 1] - goff[g]);
+  }
+  const uint32_t waves = std::max<uint32_t>(1, cdiv(maxg, 64)), n = (uint32_t)groups.size();
+  w.plain_part.alloc((size_t)n * waves);
+  w.plain_list.resize(n);
+  memcpy(w.plain_list.data(), groups.data(), (size_t)n * 4);
+  hipStream_t s = ctx->stream;
+  for (uint32_t lo = 0; lo < n; lo += 65535u) {  // (grid.y)
+    const uint32_t ny = std::min<uint32_t>(65535u, n - lo);
+    ge *part = w.plain_part.p + (size_t)lo * waves;
+    hipLaunchKernelGGL(k_msm_plain, dim3(waves, ny), dim3(64), 0, s, (const uint32_t *)scalars, w.term_sidx.p, w.term_pidx.p, w.group_off.p, tab_a,
+                       tab_b, n_a, w.plain_list.dev() + lo, waves, part);
+    hipLaunchKernelGGL(k_msm_plain_sum, dim3(ny), dim3(64), 0, s, part, w.group_off.p, w.plain_list.dev() + lo, waves, w.R.p, w.is_identity.p);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
+// term lists and result buffers of a plain MSM from host vectors: what msm_prepare does for the bucket method, without a plan
+void msm_plain_prepare(bpp_ctx *ctx, MsmWork &w, const std::vector<uint32_t> &sidx, const std::vector<uint32_t> &pidx,
+                       const std::vector<uint32_t> &goff) {
+  const uint32_t n = (uint32_t)sidx.size(), G1 = (uint32_t)goff.size();
+  w.split = false;
+  w.h_goff = goff;
+  w.term_sidx.alloc(n);
+  w.term_pidx.alloc(n);
+  w.group_off.alloc(G1);
+  w.R.alloc(G1 - 1);
+  w.comp32.alloc((size_t)(G1 - 1) * 32);
+  w.is_identity.alloc(G1 - 1);
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));  // pin_small may still feed an earlier copy / kernel
+  ctx->pin_small.resize((size_t)G1 + 2 * (size_t)n);
+  uint32_t *pin = ctx->pin_small.data();
+  memcpy(pin, goff.data(), (size_t)G1 * 4);
+  memcpy(pin + G1, sidx.data(), (size_t)n * 4);
+  memcpy(pin + G1 + n, pidx.data(), (size_t)n * 4);
+  HIP_CHECK(hipMemcpyAsync(w.group_off.p, pin, (size_t)G1 * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIP_CHECK(hipMemcpyAsync(w.term_sidx.p, pin + G1, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIP_CHECK(hipMemcpyAsync(w.term_pidx.p, pin + G1 + n, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+}
+
 // decompress `n` host points into a device niels table; returns number of bad encodings
 uint32_t decompress_to_device(bpp_ctx *ctx, const uint8_t *pts32, size_t n, niels *out) {
   DevBuf<uint8_t> d_in;
@@ -1012,10 +1097,18 @@ int msm_host_entry(bpp_ctx *ctx, const niels *tab_a, uint32_t n_a, const uint8_t
     goff = {0u, (uint32_t)n};
   }
   MsmWork w;
-  msm_prepare(ctx, w, sidx, pidx, goff);
-  PointTables tabs{tab_a, d_dyn.p, n_a, nullptr, nullptr};
-  msm_run(ctx, w, d_sc.p, tabs, nullptr);
-  hipLaunchKernelGGL(k_compress_ge, dim3(cdiv(w.plan.G, 64)), dim3(64), 0, ctx->stream, w.R.p, w.plan.G, w.comp32.p);
+  const uint32_t G = (uint32_t)goff.size() - 1;
+  if (ctx->opt.msm_plain == 1) {  // every group through the double-and-add kernels (msm_plain.h)
+    msm_plain_prepare(ctx, w, sidx, pidx, goff);
+    std::vector<uint32_t> all(G);
+    for (uint32_t g = 0; g < G; g++) all[g] = g;
+    msm_plain_run(ctx, w, goff, d_sc.p, tab_a, d_dyn.p, n_a, all);
+  } else {
+    msm_prepare(ctx, w, sidx, pidx, goff);
+    PointTables tabs{tab_a, d_dyn.p, n_a, nullptr, nullptr};
+    msm_run(ctx, w, d_sc.p, tabs, nullptr);
+  }
+  hipLaunchKernelGGL(k_compress_ge, dim3(cdiv(G, 64)), dim3(64), 0, ctx->stream, w.R.p, G, w.comp32.p);
   HIP_CHECK(hipMemcpyAsync(out32, w.comp32.p, 32 * (goff.size() - 1), hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return BPP_OK;
@@ -1187,6 +1280,11 @@ int bpp_ctx_set_option(bpp_ctx *ctx, const char *name, int value) {
   for (const TamperName &o : kTamperKnobs)
     if (strcmp(name, o.name) == 0) {  // (-1: the knob's default)
       ctx->tamper.*(o.field) = value >= 0 ? value : bpp_ctx::CheckTamper{}.*(o.field);
+      return BPP_OK;
+    }
+  for (const VerifyTamperName &o : kVerifyTamperKnobs)
+    if (strcmp(name, o.name) == 0) {
+      ctx->vtamper.*(o.field) = value >= 0 ? value : 0;
       return BPP_OK;
     }
   return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string("unknown option: ") + name);
@@ -2358,7 +2456,10 @@ void layout_groups(bpp_ctx *ctx, Batch &b, size_t chunk, const std::vector<uint3
 // rule: one launch fewer on the step's latency chain -- between two synchronisations the steps in flight run in step and every
 // launch of the chain counts: the driver's 20-step form + 1-2 %, profiles/r06_wait_ahead_ab.txt); the matrix-product form of the
 // generator columns keeps k_chain_finish_bytes in front
-void enqueue_phase2(bpp_ctx *ctx, Batch &b, StageTimer &tm, bool weights_resident = false, bool wide = false) {
+// plain_groups (pass 2 of "verify_check"): the final MSM of those groups alone, through the plain kernels (msm_plain.h); the layout is
+// then an unsplit one
+void enqueue_phase2(bpp_ctx *ctx, Batch &b, StageTimer &tm, bool weights_resident = false, bool wide = false,
+                    const std::vector<uint32_t> *plain_groups = nullptr) {
   Params &P = *b.params;
   hipStream_t s = ctx->stream;
   // (weights_resident: the grouped sharded form has put them into b.weights device -> device already)
@@ -2407,6 +2508,11 @@ void enqueue_phase2(bpp_ctx *ctx, Batch &b, StageTimer &tm, bool weights_residen
     hipLaunchKernelGGL(k_reduce_static, dim3(cdiv(b.cols, BPP_REDUCE_TILE), b.G), dim3(64), 0, s, b.rows.p, b.group_first.p, b.cols,
                        b.scal.p);
   tm.mark(M_REDUCE);
+  if (plain_groups) {
+    if (b.msm.split) throw EngineError{BPP_ERR_ENGINE, "plain MSM over a half-scalar layout"};
+    msm_plain_run(ctx, b.msm, b.msm.h_goff, b.scal.p, P.table.p, b.dynpts.p, P.table_len, *plain_groups);
+    return;
+  }
   PointTables tabs{P.table.p, b.dynpts.p, P.table_len, P.table_hi.p, b.dyn_hi.p};
   msm_run(ctx, b.msm, b.scal.p, tabs, &tm);
   HIP_CHECK(hipGetLastError());
@@ -2479,6 +2585,11 @@ struct ResidentRun {
   Batch &b;
   std::vector<ShardFinding> found;
   bool have_masks = false;
+  // "verify_check" (verify_flow): the groups whose final MSM this pass takes through the plain kernels -- the others' is not run
+  // and their identity flag is not looked at -- and the test knob that alters this pass's results on the host
+  const std::vector<uint32_t> *plain_groups = nullptr;
+  const bpp_ctx::VerifyTamper *tamper = nullptr;
+  int tamper_kind = 0;
   explicit ResidentRun(Batch &batch) : b(batch) {}
   // recovered masks on their way to the caller (page-locked, written by k_results_out): wiped on every exit (src/extended_mask.rs:14)
   void wipe_masks() {
@@ -2555,18 +2666,43 @@ int verify_flow_once(bpp_ctx *ctx, ResidentRun &run, size_t chunk, const std::ve
     run.have_masks = true;
   }
   if (want_msm) {
-    enqueue_phase2(ctx, b, tm, cmode != CHAIN_HOST, cmode == CHAIN_HOST_WIDE);
+    enqueue_phase2(ctx, b, tm, cmode != CHAIN_HOST, cmode == CHAIN_HOST_WIDE, run.plain_groups);
     b.have_trace = true;
   }
   fetch_results(ctx, b, want_msm, want_masks);
   // (the remembered wait belongs to the batch's size and group count and to what actually ran: equal work shares it)
   gpu_wait_stream(ctx, s, wait_naps(ctx, b.B), &ctx->wait_hint_end,
-                  ((uint64_t)b.B << 32) | ((uint64_t)b.G << 2) | (uint64_t)((want_msm ? 1 : 0) | (want_masks ? 2 : 0)));
+                  ((uint64_t)b.B << 32) | ((uint64_t)b.G << 2) | (uint64_t)((want_msm ? 1 : 0) | (want_masks ? 2 : 0)) |
+                      (run.plain_groups ? 1ull << 63 : 0ull));  // (a recheck's pass 2 is other work: it does not teach the next call how long to nap)
   if (want_msm && cmode != CHAIN_HOST && ctx->h_chain_zero[0]) {
     ctx->device_chain_redraws++;
     return BPP_REDRAW_ON_HOST;
   }
   collect_profile(ctx, b, tm, chain_ms, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
+  if (run.plain_groups) {  // groups whose MSM this pass did not run: nothing is claimed about them
+    std::vector<uint8_t> ran(b.G, 0);
+    for (uint32_t g : *run.plain_groups) ran[g] = 1;
+    for (uint32_t g = 0; g < b.G; g++)
+      if (!ran[g]) b.h_ident[g] = 1;
+  }
+  if (run.tamper && run.tamper_kind && (uint32_t)run.tamper->group < b.G) {  // test knob: bytes of page-locked host memory only
+    const uint32_t g = (uint32_t)run.tamper->group, p0 = b.h_group_first[g], p1 = b.h_group_first[g + 1];
+    settle_status(b);
+    auto dirty = [&](uint32_t p) { b.h_status_dirty[p / BPP_STATUS_BLOCK] = 1; };
+    switch (run.tamper_kind) {
+      case 1: b.h_ident[g] = 0; break;
+      case 2:
+        b.h_ident[g] = 1;
+        for (uint32_t p = p0; p < p1; p++) {
+          b.h_status[p] &= ~(BPP_ST_TRANSCRIPT_FAIL | BPP_ST_DECOMPRESS_FAIL);
+          dirty(p);
+        }
+        break;
+      case 3: b.h_status[p0] |= BPP_ST_TRANSCRIPT_FAIL; dirty(p0); break;
+      case 4: b.h_status[p0] |= BPP_ST_DECOMPRESS_FAIL; dirty(p0); break;
+      default: break;
+    }
+  }
 
   // errors surface chunk by chunk, in the reference's order; a chunk's MSM verdict precedes later chunks' errors
   for (uint32_t g = 0; g < b.G; g++) {
@@ -2582,10 +2718,143 @@ int verify_flow_once(bpp_ctx *ctx, ResidentRun &run, size_t chunk, const std::ve
 }
 
 // first with the device's share of the weight chains, and on a zero weight once more without
-void verify_flow(bpp_ctx *ctx, ResidentRun &run, size_t chunk, const std::vector<uint32_t> *bounds, const int *actions, int action_all) {
+void verify_flow_pass(bpp_ctx *ctx, ResidentRun &run, size_t chunk, const std::vector<uint32_t> *bounds, const int *actions, int action_all) {
   if (verify_flow_once(ctx, run, chunk, bounds, actions, action_all, true) != BPP_REDRAW_ON_HOST) return;
   run.wipe_masks();
   (void)verify_flow_once(ctx, run, chunk, bounds, actions, action_all, false);
+}
+
+inline bool device_tier(int tier) { return tier == BPP_TIER_PASS1 || tier == BPP_TIER_PASS2 || tier == BPP_TIER_MSM; }
+
+// The agreement rule of "verify_check" over one group's outcomes in pass order (bpp.h: bpp_verify_check_resolve).  Two outcomes
+// agree when code, tier and index are the same.  Returns the BPP_VCHECK_* kind; `out` is set unless the answer is PENDING.
+int verify_check_resolve(const ShardFinding *passes, int n_passes, ShardFinding &out) {
+  auto same = [](const ShardFinding &a, const ShardFinding &c) { return a.code == c.code && a.tier == c.tier && a.index == c.index; };
+  if (!device_tier(passes[0].tier)) {
+    out = passes[0];
+    return BPP_VCHECK_NOT_RECHECKED;
+  }
+  if (n_passes < 2) return BPP_VCHECK_PENDING;
+  if (same(passes[0], passes[1])) {
+    out = passes[0];
+    return BPP_VCHECK_CONFIRMED;
+  }
+  if (n_passes < 3) return BPP_VCHECK_PENDING;
+  if (same(passes[0], passes[2])) {
+    out = passes[0];
+    return BPP_VCHECK_UPHELD;
+  }
+  if (same(passes[1], passes[2])) {
+    out = passes[2];
+    return BPP_VCHECK_OVERTURNED;
+  }
+  char m[160];
+  snprintf(m, sizeof(m), "verify_check: three passes, three outcomes (code/tier/index): %d/%d/%u, %d/%d/%u, %d/%d/%u", passes[0].code,
+           passes[0].tier, passes[0].index, passes[1].code, passes[1].tier, passes[1].index, passes[2].code, passes[2].tier, passes[2].index);
+  out = ShardFinding{};
+  out.code = BPP_ERR_SELF_CHECK;
+  out.tier = BPP_TIER_ENGINE;
+  out.rank = passes[0].rank;
+  out.index = passes[0].index;
+  out.msg = m;
+  return BPP_VCHECK_UNDECIDED;
+}
+
+// The other form of every verifier stage that has one, given the forms pass 1 took for this batch (DESIGN.md 4.1 has the table).
+// Where the shape permits no other form the engine's own rules quietly keep the one there is (plan_lanes, chain_mode).  The
+// layout is an unsplit one: the plain MSM reads the term lists as they are before any half-scalar split.
+void complementary_forms(bpp_ctx::Options &o, const Batch &b) {
+  auto on = [](int opt, bool rule) { return opt >= 0 ? opt != 0 : rule; };
+  o.transcripts_wave = on(o.transcripts_wave, b.B <= BPP_TRANSCRIPTS_WAVE_MAX) ? 0 : 1;
+  o.tables_wave = on(o.tables_wave, b.B <= BPP_TABLES_WAVE_MAX) ? 0 : 1;
+  o.side_decompress = on(o.side_decompress, b.B <= BPP_SIDE_DECOMPRESS_MAX) ? 0 : 1;
+  o.fused_columns = b.fused_columns ? 0 : 1;
+  o.static_gemm = b.static_gemm ? 0 : 1;
+  const int chain = (o.chain >= 0 && o.chain <= 2) ? o.chain : (b.B >= BPP_WAIT_NAP_MIN_PROOFS ? 2 : 0);
+  o.chain = chain == 0 ? 2 : 0;  // host sponges either way; the reduction mod l changes sides (a pass that runs the device chain: 0)
+  o.msm_split = 0;
+}
+
+// One verification of a resident batch.  "verify_check" = 1: pass 1 is the run below, launch for launch; when it leaves a group
+// with a device-tier finding, that group is verified again under the complementary forms with the plain MSM (pass 2), a third time
+// under pass 1's forms when the two disagree, and the outcome two passes share is the group's (bpp.h, "Rechecked rejections").
+void verify_flow(bpp_ctx *ctx, ResidentRun &run, size_t chunk, const std::vector<uint32_t> *bounds, const int *actions, int action_all) {
+  const bpp_ctx::VerifyTamper tam = ctx->vtamper;  // acts on this call, checked or not, and is reset
+  ctx->vtamper = bpp_ctx::VerifyTamper{};
+  auto pass = [&](int k) {
+    run.tamper = (tam.passes >> (k - 1)) & 1 ? &tam : nullptr;
+    run.tamper_kind = tam.kind > 15 ? (tam.kind >> (4 * (k - 1))) & 15 : tam.kind;  // (above 15: a kind per pass, four bits each)
+    verify_flow_pass(ctx, run, chunk, bounds, actions, action_all);
+    run.tamper = nullptr;
+  };
+  pass(1);
+  if (ctx->opt.verify_check != 1 || ctx->verify_check_off > 0) return;
+  Batch &b = run.b;
+  struct bpp_verify_check_stats &st = ctx->vcheck_stats;
+  st.calls++;
+  std::vector<uint32_t> re;
+  for (uint32_t g = 0; g < b.G; g++)
+    if (device_tier(run.found[g].tier)) re.push_back(g);
+  if (re.empty()) return;
+  st.rechecked_groups += re.size();
+
+  const std::vector<ShardFinding> p1 = run.found;
+  std::vector<ShardFinding> p2, p3;
+  const bpp_ctx::Options saved = ctx->opt;
+  const bool had_masks = run.have_masks;
+  // passes 2 and 3 leave their masks in a buffer of their own: pass 1's stay where the accepted groups' callers get them from
+  b.h_masks.swap(b.h_masks_check);
+  bool swapped = true;
+  auto unswap = [&] {
+    if (!swapped) return;
+    swapped = false;
+    b.h_masks.swap(b.h_masks_check);
+  };
+  ScopeExit restore{[&] {  // every exit: the options as they were, no mask byte left in the check's buffer
+    ctx->opt = saved;
+    run.plain_groups = nullptr;
+    unswap();
+    if (b.h_masks_check.p) wipe(b.h_masks_check.data(), b.h_masks_check.n);
+    run.have_masks = had_masks;
+  }};
+  complementary_forms(ctx->opt, b);
+  b.G = 0;  // (the layout is built again: unsplit term lists, the lanes' shape under the other forms)
+  run.plain_groups = &re;
+  pass(2);
+  p2 = run.found;
+  run.plain_groups = nullptr;
+  ctx->opt = saved;
+  b.G = 0;  // and once more as pass 1 had it, whether a pass follows or not: the batch's cached plan is as before
+  bool need3 = false;
+  for (uint32_t g : re) {
+    const ShardFinding two[2] = {p1[g], p2[g]};
+    ShardFinding o;
+    need3 = need3 || verify_check_resolve(two, 2, o) == BPP_VCHECK_PENDING;
+  }
+  if (need3) {
+    pass(3);
+    p3 = run.found;
+  } else {
+    layout_groups(ctx, b, chunk, bounds);
+  }
+  unswap();
+  run.found = p1;
+  const size_t row = (size_t)b.params->t * 32;
+  for (uint32_t g : re) {
+    const ShardFinding three[3] = {p1[g], p2[g], need3 ? p3[g] : ShardFinding{}};
+    ShardFinding o;
+    const int kind = verify_check_resolve(three, need3 ? 3 : 2, o);
+    run.found[g] = o;
+    if (kind != BPP_VCHECK_CONFIRMED) st.tie_breaks++;
+    if (kind == BPP_VCHECK_CONFIRMED || kind == BPP_VCHECK_UPHELD) st.confirmed++;
+    else if (kind == BPP_VCHECK_OVERTURNED) st.overturned++;
+    else st.undecided++;
+    // an overturned group that is Ok after all takes the masks of the pass that said so last (pass 3), through page-locked bytes only
+    if (kind == BPP_VCHECK_OVERTURNED && o.tier == BPP_TIER_NONE && had_masks && b.h_masks_check.p && b.h_masks.p) {
+      const size_t lo = (size_t)b.h_group_first[g] * row, hi = (size_t)b.h_group_first[g + 1] * row;
+      if (hi <= b.h_masks.n && hi <= b.h_masks_check.n) memcpy(b.h_masks.data() + lo, b.h_masks_check.data() + lo, hi - lo);
+    }
+  }
 }
 
 // outputs: Vec<Option<ExtendedMask>> for the proofs [p0, p1): with `give`, the masks of the items that carry a seed nonce; every
@@ -3156,6 +3425,50 @@ int bpp_profile_enable(bpp_ctx *ctx, int on) {
   if (!ctx) return BPP_ERR_BAD_HANDLE;
   ctx->profile = on != 0;
   ctx->profile_light = on == 2;
+  return BPP_OK;
+}
+
+int bpp_verify_check_resolve(const bpp_shard_result *passes, int n_passes, bpp_shard_result *out, int *kind) {
+  if (!passes || !out || !kind || n_passes < 1 || n_passes > 3) return BPP_ERR_INVALID_ARGUMENT;
+  ShardFinding f[3], o;
+  for (int k = 0; k < n_passes; k++) {
+    f[k].code = passes[k].code;
+    f[k].tier = passes[k].tier;
+    f[k].rank = passes[k].rank;
+    f[k].index = passes[k].index;
+    f[k].msg.assign(passes[k].msg, strnlen(passes[k].msg, sizeof(passes[k].msg)));
+  }
+  *kind = verify_check_resolve(f, n_passes, o);
+  if (*kind == BPP_VCHECK_PENDING) return 1;
+  memset(out, 0, sizeof(*out));
+  shard_result_set(*out, o.code, o.tier, o.rank, o.index, o.msg);
+  return 0;
+}
+
+int bpp_verify_check_stats(bpp_ctx *ctx, struct bpp_verify_check_stats *out) {
+  if (!ctx || !out) return BPP_ERR_BAD_HANDLE;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    *out = ctx->vcheck_stats;
+  }
+  std::vector<bpp_ctx *> lanes;  // the packed pipeline's lanes: contexts of their own, made on the first submit
+  {
+    std::lock_guard<std::mutex> lk(ctx->pipe_init_mu);
+    if (ctx->pipe) {
+      std::lock_guard<std::mutex> lk2(ctx->pipe->mu);
+      for (auto &l : ctx->pipe->lanes)
+        if (l->child) lanes.push_back(l->child);
+    }
+  }
+  for (bpp_ctx *c : lanes) {
+    std::lock_guard<std::mutex> lk(c->mu);
+    out->calls += c->vcheck_stats.calls;
+    out->rechecked_groups += c->vcheck_stats.rechecked_groups;
+    out->confirmed += c->vcheck_stats.confirmed;
+    out->overturned += c->vcheck_stats.overturned;
+    out->tie_breaks += c->vcheck_stats.tie_breaks;
+    out->undecided += c->vcheck_stats.undecided;
+  }
   return BPP_OK;
 }
 

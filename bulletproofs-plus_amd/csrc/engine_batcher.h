@@ -203,6 +203,10 @@ int bpp_batcher_create(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *sh
         for (uint32_t j = 1; j < i; j++) bpp_ctx_destroy(b->lanes[j].ctx);
         return rc;
       }
+      {  // a lane rechecks its rejections when the context it was made from does ("verify_check", read as it is now)
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        c->opt.verify_check = ctx->opt.verify_check;
+      }
       b->lanes[i].ctx = c;
       b->lanes[i].own = true;
     }
@@ -240,6 +244,23 @@ int bpp_batcher_stats(bpp_batcher *b, uint64_t *pooled_calls, uint64_t *engine_c
   if (pooled_calls) *pooled_calls = b->pooled_calls;
   if (engine_calls) *engine_calls = b->engine_calls;
   if (solo_calls) *solo_calls = b->solo_calls;
+  return BPP_OK;
+}
+
+int bpp_batcher_verify_check_stats(bpp_batcher *b, struct bpp_verify_check_stats *out) {
+  if (!b || !out) return BPP_ERR_BAD_HANDLE;
+  memset(out, 0, sizeof(*out));
+  for (auto &L : b->lanes) {  // (the first lane is the caller's context: bpp_verify_check_stats adds its pipeline's lanes)
+    struct bpp_verify_check_stats one;
+    const int rc = bpp_verify_check_stats(L.ctx, &one);
+    if (rc != BPP_OK) return rc;
+    out->calls += one.calls;
+    out->rechecked_groups += one.rechecked_groups;
+    out->confirmed += one.confirmed;
+    out->overturned += one.overturned;
+    out->tie_breaks += one.tie_breaks;
+    out->undecided += one.undecided;
+  }
   return BPP_OK;
 }
 

@@ -40,7 +40,8 @@ extern "C" {
 #define BPP_ERR_NO_DEVICE (-2) /* no usable gfx950 device */
 #define BPP_ERR_BAD_HANDLE (-3)
 #define BPP_ERR_COMM (-4)      /* RCCL failure (library missing, communicator error): sharded entry points only */
-#define BPP_ERR_SELF_CHECK (-5) /* "prove_check" = 1: a proof the verifier rejected, made again once and rejected again */
+#define BPP_ERR_SELF_CHECK (-5) /* "prove_check" = 1: a proof the verifier rejected, made again once and rejected again;
+                                   "verify_check" = 1: a group whose three verification passes gave three different outcomes */
 
 /* Where inside RangeProof::verify (src/range_proof.rs:756-1065) a check failed.  Lower = earlier in the reference's order
  * of checks; shards of one reference batch combine their findings by (tier, rank) -- see bpp_verify_sharded. */
@@ -106,7 +107,19 @@ const char *bpp_ctx_last_error(bpp_ctx *ctx);
  * before they are checked (i counts the call's items as the caller passed them); "prove_check_tamper_times" = 1 (default) alters the
  * first attempt only, 2 the remake of that proof as well.  "prove_check_tamper_nonce" = 1: the byte ("prove_check_tamper_byte"
  * 0..31) is altered in the check's own copy of item i's seed nonce instead of in the proof ("prove_check_recovery" = 1: the replay
- * then disagrees with a proof that is right; an item without a nonce is left alone).  Checked calls only. */
+ * then disagrees with a proof that is right; an item without a nonce is left alone).  Checked calls only.
+ * "msm_plain" (1: bpp_msm_vartime, bpp_msm_vartime_batched and bpp_msm_mixed run through the plain double-and-add kernels of
+ * csrc/msm_plain.h, which share nothing with the bucket method but the field and point arithmetic: a second opinion for B1
+ * callers, ~30 times the work per term; 0 and -1 = off).
+ * "verify_check" (1: every rejection a verification finds ON THE DEVICE is confirmed on an independent path before it is
+ * returned -- see "Rechecked rejections" below, bpp_verify_check_stats; 0 and -1 = off: every call enqueues what it always did).
+ * Test knobs of "verify_check", settable here only (no environment variable, never copied to a lane), acting on the NEXT verification
+ * of the context -- checked or not -- and then reset: "verify_check_tamper" = bit mask of the passes to alter (1, 2, 4 = pass 1, 2, 3),
+ * "verify_check_tamper_group" = the group (chunk) of the call's layout, "verify_check_tamper_kind" = 1: the group's identity flag
+ * reads 0 (a false MSM rejection); 2: it reads 1 and the device bits of the group's status words are cleared (a false acceptance);
+ * 3 / 4: the PASS-1 / decompression failure bit is set in the status word of the group's first proof; a value above 15 holds one
+ * kind per pass, four bits each, pass 1 in the lowest.  The knobs alter bytes of
+ * page-locked host memory after the wait and before findings are raised; nothing on the device is touched. */
 int bpp_ctx_set_option(bpp_ctx *ctx, const char *name, int value);
 /* verifications of this context whose weights were made on the device ("chain" 1 or 2), and how many of those ran once more
  * with everything on the host because a weight came out zero */
@@ -527,6 +540,49 @@ int bpp_prove_pool_check_stats(bpp_prove_pool *p, struct bpp_prove_check_stats *
  * is not counted here.  Either pointer may be NULL.  The pool's form sums its lanes. */
 int bpp_prove_check_recovery_stats(bpp_ctx *ctx, uint64_t *replayed, uint64_t *mismatched);
 int bpp_prove_pool_check_recovery_stats(bpp_prove_pool *p, uint64_t *replayed, uint64_t *mismatched);
+/* ---- Rechecked rejections ("verify_check" = 1) ----
+ * A VerificationFailed or InvalidArgument found on the device rests on one run through one set of kernel forms and one MSM
+ * plan; a node that rejects a valid block because of a slip in one form has forked itself off the chain.  With the option on,
+ * the one verification flow behind bpp_verify_batch(_packed), bpp_verify_batch_with_challenges, bpp_verify_resident,
+ * bpp_verify_resident_groups(_actions), the packed pipeline's lanes and bpp_batcher does this:
+ *   pass 1  today's run, launch for launch.  No group with a device-tier finding (BPP_TIER_PASS1, BPP_TIER_PASS2, BPP_TIER_MSM):
+ *           the call ends here and has enqueued nothing extra.
+ *   pass 2  the same layout once more under the complementary form of every stage that has one (DESIGN.md 4.1 has the table);
+ *           the final MSM of the rechecked groups -- those with a device-tier finding in pass 1 -- runs through the plain
+ *           double-and-add kernels (csrc/msm_plain.h); the other groups' MSM is not run, their pass-1 Ok stands.
+ *   A group is CONFIRMED when pass 2 gives the same code, tier and index.  Otherwise
+ *   pass 3  under pass 1's forms breaks the tie: the outcome two passes share is returned -- it may be Ok, with that pass's masks --
+ *           and a group whose three outcomes all differ gets BPP_ERR_SELF_CHECK with a message naming them.
+ * A confirmed rejection returns byte for byte what the unchecked call returns: code, tier, index, message, zeroed mask slots.
+ * The batch's cached plan and the context's options are as before when the call returns.  The zero-weight redraw rule applies
+ * to each pass.  Lanes (pipeline, batcher) copy the option when they are made.
+ * LEFT ALONE: host-tier findings (tiers 1-4: nothing ran on the device), accepted groups (re-verifying them costs a second MSM
+ * per call), the sharded entry points, and the prover's self-check ("prove_check"), whose verifications always run with the
+ * recheck off: a proof it rejects is made again anyway, and its counters keep their meaning.
+ * Both paths share field.h / point.h, the decompression and the host sponge code: a systematic error there is wrong twice.
+ *
+ * bpp_verify_check_resolve is the agreement rule as pure host code, usable without a device (like bpp_shard_resolve):
+ * passes[0 .. n_passes) are one group's outcomes in pass order (tier BPP_TIER_NONE = Ok; rank and msg are carried along).
+ * Returns 0 when the group is decided -- *out is what to return, *kind says how -- 1 when one more pass is needed (*kind =
+ * BPP_VCHECK_PENDING, *out untouched), BPP_ERR_INVALID_ARGUMENT for null arguments or n_passes outside 1..3. */
+#define BPP_VCHECK_NOT_RECHECKED 0 /* pass 1 has no device-tier finding: it stands */
+#define BPP_VCHECK_CONFIRMED 1     /* pass 2 agrees with pass 1 */
+#define BPP_VCHECK_UPHELD 2        /* pass 2 differed, pass 3 agrees with pass 1: pass 1's outcome */
+#define BPP_VCHECK_OVERTURNED 3    /* passes 2 and 3 agree with each other and not with pass 1: their outcome */
+#define BPP_VCHECK_UNDECIDED 4     /* three different outcomes: BPP_ERR_SELF_CHECK, tier BPP_TIER_ENGINE */
+#define BPP_VCHECK_PENDING 5
+int bpp_verify_check_resolve(const bpp_shard_result *passes, int n_passes, bpp_shard_result *out, int *kind);
+/* What the rechecks of a context have done: verifications that ran with the option on, groups with a device-tier finding in
+ * pass 1, those whose returned outcome is pass 1's (confirmed by pass 2, or upheld by pass 3), those whose returned outcome is
+ * NOT pass 1's, groups that needed pass 3, groups with three different outcomes.  bpp_verify_check_stats adds the counts of
+ * the context's pipeline lanes, bpp_batcher_verify_check_stats those of a batcher's lanes (its first lane is the context it was
+ * made from, whose other calls count as well). */
+struct bpp_verify_check_stats {
+  uint64_t calls, rechecked_groups, confirmed, overturned, tie_breaks, undecided;
+};
+int bpp_verify_check_stats(bpp_ctx *ctx, struct bpp_verify_check_stats *out);
+int bpp_batcher_verify_check_stats(bpp_batcher *b, struct bpp_verify_check_stats *out);
+
 /* Prove calls in flight from ONE thread and ONE context: the prover's form of bpp_verify_submit_packed / bpp_verify_collect.
  * bpp_prove_submit hands a whole prove call to one of `depth` lanes and returns a ticket; bpp_prove_collect blocks until that call
  * is done and returns EXACTLY what the blocking call over the same items returns -- bpp_prove_batch_mixed(ctx, params, items,

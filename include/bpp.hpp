@@ -63,6 +63,15 @@ class Engine {
   Engine &operator=(const Engine &) = delete;
   bpp_ctx *ctx() const { return ctx_; }
 
+  // "verify_check" = 1 (bpp.h, "Rechecked rejections"): every rejection this engine's verifications find on the device is
+  // confirmed on an independent path -- the complementary kernel forms and the plain MSM -- before it is returned
+  void verify_check(bool on) { check(bpp_ctx_set_option(ctx_, "verify_check", on ? 1 : 0), bpp_ctx_last_error(ctx_)); }
+  struct bpp_verify_check_stats verify_check_stats() const {
+    struct bpp_verify_check_stats s{};
+    check(::bpp_verify_check_stats(ctx_, &s), bpp_ctx_last_error(ctx_));
+    return s;
+  }
+
   // Prove calls in flight from ONE thread (bpp_prove_submit / bpp_prove_collect).  prove_submit hands a whole call -- the items of
   // a bpp_prove_batch_mixed, or with openings = true of a bpp_prove_openings (an item may come without commitments) -- to a lane of
   // this engine and returns at once; the items and everything they point to are free again then.  prove_collect blocks and gives
