@@ -145,6 +145,15 @@ class Engine:
     def precomputation(self, static_points):
         return Precomputation(self, static_points)
 
+    def msm_last_plan(self):
+        """bpp_msm_last_plan: the plan and the kernel forms of this context's last multiscalar multiplication"""
+        w = (c_uint32 * 8)()
+        _check(self.lib.bpp_msm_last_plan(self.ctx, w), self.ctx)
+        form = int(w[6])
+        return {"c": int(w[0]), "K": int(w[1]), "K_wide": int(w[2]), "nb": int(w[3]), "G": int(w[4]), "terms": int(w[5]),
+                "quad": bool(form & 1), "reduce": ("rc_quad", "rc2", "rc", "bitsum")[(form >> 1) & 3], "final_quad": bool(form & 8),
+                "narrow_prelude": bool(form & 16), "plain": bool(form & 32), "form": form, "dig_cap": int(w[7])}
+
     def profile(self, on=True):
         """bpp_profile_enable: False / 0 off, True / 1 an event at every stage boundary, 2 the roofline kernel's two events only"""
         self.lib.bpp_profile_enable(self.ctx, int(on))

@@ -533,8 +533,23 @@ struct WaitHint {
   uint64_t key = 0;
 };
 
+// The kernel forms the last bucket MSM of a context took (msm_run decides them once and launches by them; msm_plain_run
+// records the plain kernels): bpp_msm_last_plan reads this, so that a test can tell WHICH kernels gave it its bytes
+enum MsmReduce : uint32_t { MSM_RC_QUAD = 0, MSM_RC2 = 1, MSM_RC = 2, MSM_BITSUM = 3 };
+struct MsmForm {
+  bool valid = false;       // a B1 call or a verification has run an MSM on this context
+  bool plain = false;       // msm_plain.h; nothing below applies
+  bool quad = false;        // k_msm_accumulate_quad, else k_msm_accumulate
+  MsmReduce reduce = MSM_RC_QUAD;
+  bool final_quad = false;  // k_msm_final_quad, else k_msm_final
+  bool narrow = false;      // 256-lane prelude and order kernels, else 1024
+  uint32_t dig_cap = 0;     // terms per group whose digits k_msm_prelude keeps in LDS
+  uint32_t c = 0, K = 0, K_wide = 0, nb = 0, G = 0, terms = 0;
+};
+
 struct bpp_ctx {
   int device = 0;
+  MsmForm msm_form;
   hipStream_t stream = nullptr;
   bool own_stream = false;
   std::string err;
@@ -953,45 +968,62 @@ void msm_run(bpp_ctx *ctx, MsmWork &w, const sc *scalars, PointTables tabs, Stag
   const uint32_t per_group = plan.K * plan.nb;
   // many small groups of a throughput call: four-wavefront workgroups (msm.h); a small call (latency) and large groups: sixteen
   // few buckets on an idle chip (one batch per call): quad forms, ~3x shorter dependency chains (tests force either form)
-  const bool small = w.split || (ctx->opt.msm_quad >= 0 ? ctx->opt.msm_quad != 0 : (size_t)plan.G * per_group <= 100000);
-  const bool narrow = !small && w.max_group_terms <= BPP_SORT_SMALL_GROUP_TERMS;
-  if (narrow) {
-    const uint32_t dig_cap = msm_prelude_dig_cap(plan, w.max_group_terms, BPP_SORT_THREADS_SMALL);
+  // The selection is made once, here, and kept in the context (bpp_msm_last_plan); the launches below switch on it.
+  MsmForm f;
+  f.valid = true;
+  f.quad = w.split || (ctx->opt.msm_quad >= 0 ? ctx->opt.msm_quad != 0 : (size_t)plan.G * per_group <= 100000);
+  f.narrow = !f.quad && w.max_group_terms <= BPP_SORT_SMALL_GROUP_TERMS;
+  f.dig_cap = f.narrow ? msm_prelude_dig_cap(plan, w.max_group_terms, BPP_SORT_THREADS_SMALL) : msm_prelude_dig_cap(plan, w.max_group_terms);
+  if (plan.c <= 11 && f.quad)
+    f.reduce = MSM_RC_QUAD;
+  else if (plan.nb <= 256 && ctx->opt.msm_rc2 != 0)  // two windows per wavefront (msm.h)
+    f.reduce = MSM_RC2;
+  else if (plan.c <= 11)
+    f.reduce = MSM_RC;
+  else
+    f.reduce = MSM_BITSUM;
+  f.final_quad = ctx->opt.msm_final_quad != 0;  // (tests force either kernel)
+  f.c = plan.c, f.K = plan.K, f.K_wide = plan.K_wide, f.nb = plan.nb, f.G = plan.G, f.terms = plan.n_terms;
+  ctx->msm_form = f;
+  const uint32_t dig_cap = f.dig_cap;
+  if (f.narrow) {
     hipLaunchKernelGGL(k_msm_prelude<BPP_SORT_THREADS_SMALL>, dim3(8 * cdiv(plan.G, 8) * plan.K), dim3(BPP_SORT_THREADS_SMALL), msm_prelude_lds(plan, dig_cap), s,
                        scalars, w.term_sidx.p, w.term_pidx.p, w.group_off.p, plan, dig_cap, w.counts.p, w.starts.p, w.sorted.p, w.order_win.p, w.cls_hist.p);
     hipLaunchKernelGGL(k_msm_order<BPP_SORT_THREADS_SMALL>, dim3(plan.G), dim3(BPP_SORT_THREADS_SMALL), 0, s, w.counts.p, w.order_win.p, w.cls_hist.p, plan,
                        w.order.p);
   } else {
-    const uint32_t dig_cap = msm_prelude_dig_cap(plan, w.max_group_terms);
     hipLaunchKernelGGL(k_msm_prelude<BPP_SORT_THREADS>, dim3(8 * cdiv(plan.G, 8) * plan.K), dim3(BPP_SORT_THREADS), msm_prelude_lds(plan, dig_cap), s, scalars,
                        w.term_sidx.p, w.term_pidx.p, w.group_off.p, plan, dig_cap, w.counts.p, w.starts.p, w.sorted.p, w.order_win.p, w.cls_hist.p);
     hipLaunchKernelGGL(k_msm_order<BPP_SORT_THREADS>, dim3(plan.G), dim3(BPP_SORT_THREADS), 0, s, w.counts.p, w.order_win.p, w.cls_hist.p, plan, w.order.p);
   }
   if (tm) tm->mark(M_ORDER);  // msm_accumulate_ms brackets k_msm_accumulate alone (the roofline kernel)
-  if (small)
+  if (f.quad)
     hipLaunchKernelGGL(k_msm_accumulate_quad, dim3(cdiv(plan.G * per_group, 16)), dim3(64), 0, s, w.sorted.p, w.starts.p,
                        w.counts.p, w.order.p, tabs, plan.G * per_group, w.buckets.p);
   else
     hipLaunchKernelGGL(k_msm_accumulate, dim3(8 * cdiv(plan.G, 8) * cdiv(per_group, 64)), dim3(64), 0, s, w.sorted.p, w.starts.p,
                        w.counts.p, w.order.p, tabs, per_group, plan.G, w.buckets.p);
   if (tm) tm->mark(M_ACC);
-  if (plan.c <= 11 && small) {
-    hipLaunchKernelGGL(k_msm_window_rc_quad, dim3(plan.G * plan.K), dim3(1024), 0, s, w.buckets.p, w.counts.p, plan, w.W.p);
-  } else if (plan.nb <= 256 && ctx->opt.msm_rc2 != 0) {  // two windows per wavefront (msm.h)
-    hipLaunchKernelGGL(k_msm_window_rc2, dim3(cdiv(plan.G * plan.K, 2)), dim3(64), 0, s, w.buckets.p, w.counts.p, plan, plan.G * plan.K, w.W.p);
-  } else if (plan.c <= 11) {
-    hipLaunchKernelGGL(k_msm_window_rc, dim3(plan.G * plan.K), dim3(64), 0, s, w.buckets.p, w.counts.p, plan, w.W.p);
-  } else {
-    hipLaunchKernelGGL(k_msm_bitsum, dim3(plan.c, plan.K, plan.G), dim3(64), 0, s, w.buckets.p, w.counts.p, plan, w.Q.p);
-    hipLaunchKernelGGL(k_msm_window, dim3(cdiv(plan.G * plan.K, 64)), dim3(64), 0, s, w.Q.p, plan, w.W.p);
+  switch (f.reduce) {
+    case MSM_RC_QUAD:
+      hipLaunchKernelGGL(k_msm_window_rc_quad, dim3(plan.G * plan.K), dim3(1024), 0, s, w.buckets.p, w.counts.p, plan, w.W.p);
+      break;
+    case MSM_RC2:
+      hipLaunchKernelGGL(k_msm_window_rc2, dim3(cdiv(plan.G * plan.K, 2)), dim3(64), 0, s, w.buckets.p, w.counts.p, plan, plan.G * plan.K, w.W.p);
+      break;
+    case MSM_RC:
+      hipLaunchKernelGGL(k_msm_window_rc, dim3(plan.G * plan.K), dim3(64), 0, s, w.buckets.p, w.counts.p, plan, w.W.p);
+      break;
+    case MSM_BITSUM:
+      hipLaunchKernelGGL(k_msm_bitsum, dim3(plan.c, plan.K, plan.G), dim3(64), 0, s, w.buckets.p, w.counts.p, plan, w.Q.p);
+      hipLaunchKernelGGL(k_msm_window, dim3(cdiv(plan.G * plan.K, 64)), dim3(64), 0, s, w.Q.p, plan, w.W.p);
+      break;
   }
   if (tm) tm->mark(M_BUCKET);
-  {
-    if (ctx->opt.msm_final_quad != 0)  // (tests force either kernel)
-      hipLaunchKernelGGL(k_msm_final_quad, dim3(cdiv(plan.G, 16)), dim3(64), 0, s, w.W.p, plan, w.R.p, w.is_identity.p);
-    else
-      hipLaunchKernelGGL(k_msm_final, dim3(cdiv(plan.G, 64)), dim3(64), 0, s, w.W.p, plan, w.R.p, w.is_identity.p);
-  }
+  if (f.final_quad)
+    hipLaunchKernelGGL(k_msm_final_quad, dim3(cdiv(plan.G, 16)), dim3(64), 0, s, w.W.p, plan, w.R.p, w.is_identity.p);
+  else
+    hipLaunchKernelGGL(k_msm_final, dim3(cdiv(plan.G, 64)), dim3(64), 0, s, w.W.p, plan, w.R.p, w.is_identity.p);
   if (tm) tm->mark(M_FINAL);
   HIP_CHECK(hipGetLastError());
 }
@@ -1008,6 +1040,12 @@ void msm_plain_run(bpp_ctx *ctx, MsmWork &w, const std::vector<uint32_t> &goff, 
     maxg = std::max(maxg, goff[g + 1] - goff[g]);
   }
   const uint32_t waves = std::max<uint32_t>(1, cdiv(maxg, 64)), n = (uint32_t)groups.size();
+  {
+    MsmForm f;
+    f.valid = f.plain = true;
+    f.G = n, f.terms = goff.back();
+    ctx->msm_form = f;
+  }
   w.plain_part.alloc((size_t)n * waves);
   w.plain_list.resize(n);
   memcpy(w.plain_list.data(), groups.data(), (size_t)n * 4);
@@ -1362,6 +1400,17 @@ int bpp_msm_vartime_batched(bpp_ctx *ctx, const uint8_t *scalars32, const uint8_
                           out_points32);
   }
   BPP_CATCH(ctx, nullptr, 0)
+}
+
+int bpp_msm_last_plan(bpp_ctx *ctx, uint32_t out[8]) {
+  BPP_ENTRY(ctx);
+  if (!out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+  const MsmForm &f = ctx->msm_form;
+  if (!f.valid) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "no MSM has run on this context");
+  const uint32_t bits = f.plain ? 32u : (f.quad ? 1u : 0u) | ((uint32_t)f.reduce << 1) | (f.final_quad ? 8u : 0u) | (f.narrow ? 16u : 0u);
+  const uint32_t v[8] = {f.c, f.K, f.K_wide, f.nb, f.G, f.terms, bits, f.dig_cap};
+  memcpy(out, v, sizeof v);
+  return BPP_OK;
 }
 
 // ---------------------------------------------------------------- B2: parameters

@@ -167,6 +167,13 @@ int bpp_msm_vartime(bpp_ctx *ctx, const uint8_t *scalars32, const uint8_t *point
 /* many independent MSMs in one launch: group g covers terms [group_off[g], group_off[g+1]) */
 int bpp_msm_vartime_batched(bpp_ctx *ctx, const uint8_t *scalars32, const uint8_t *points32,
                             const uint32_t *group_off, size_t n_groups, uint8_t *out_points32 /* n_groups x 32 */);
+/* diagnostics: the kernel forms the LAST multiscalar multiplication of this context took (a B1 call above, or a verification's
+ * final one): out = { c (window bits), K (windows), K_wide (windows of c bits, the others have c - 1), nb (buckets per window),
+ * G (groups), terms, form, dig_cap (terms per group whose digits the prelude keeps in LDS) }.  form: bit 0 = quad accumulation
+ * (else one lane per bucket); bits 1-2 = the reduction, 0 rc_quad, 1 rc2, 2 rc, 3 bitsum + window; bit 3 = final_quad (else final);
+ * bit 4 = 256-lane prelude (else 1024); bit 5 = the plain kernels ("msm_plain" = 1: only G, terms and this bit are set).
+ * BPP_ERR_INVALID_ARGUMENT before the first one (an empty sum launches nothing and records nothing). */
+int bpp_msm_last_plan(bpp_ctx *ctx, uint32_t out[8]);
 
 /* ---- B2: parameters = RangeParameters::init + BulletproofGens::new + PedersenGens ----
  * (src/range_parameters.rs:32-58, src/generators/bulletproof_gens.rs:83-112, src/ristretto.rs:67-112)

@@ -109,3 +109,177 @@ def trace_challenge_bytes(trace, max_rounds):
         row += [0] * (max_rounds + 3 - len(row))
         out += b"".join(sb(x) for x in row)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Structured inputs of the bucket MSM (tests/test_gpu_msm_structured.py runs them on the device, tests/test_host_arith.py checks
+# that each family still has the property it exists for).  A case is n terms: scalar i goes with bases[pidx[i]].  Few distinct
+# bases, so that the oracle's answer is one short multiscalar multiplication over the scalars folded per base.
+class MsmCase:
+    def __init__(self, name, scalars, pidx, bases):
+        assert len(scalars) == len(pidx) and all(0 <= s < C.L for s in scalars)
+        self.name, self.scalars, self.pidx, self.bases = name, scalars, pidx, bases
+
+    def __len__(self):
+        return len(self.scalars)
+
+    def folded(self):
+        """one scalar per base: the sum of its terms' scalars mod l"""
+        acc = [0] * len(self.bases)
+        for s, p in zip(self.scalars, self.pidx):
+            acc[p] += s
+        return [a % C.L for a in acc]
+
+    def expected(self):
+        return C.multiscalar_mul(self.folded(), self.bases).compress()
+
+
+_MSM_BASES = []
+
+
+def msm_bases():
+    """D = 7 distinct points, then their negatives (7..13), then the identity (14)"""
+    if not _MSM_BASES:
+        pts = [C.from_uniform_bytes(hashlib.shake_256(b"structured-p-%d" % i).digest(64)) for i in range(7)]
+        _MSM_BASES.extend(pts + [-p for p in pts] + [C.Point.identity()])
+    return _MSM_BASES
+
+
+MSM_NEG, MSM_IDENT = 7, 14
+
+
+def msm_hashed(tag, i, bits=253):
+    """a hashed scalar below 2^bits, canonical"""
+    return (int.from_bytes(hashlib.shake_256(b"structured-s-%s-%d" % (tag, i)).digest(32), "little") & ((1 << bits) - 1)) % C.L
+
+
+MSM_CONSTANTS = [("hashed", msm_hashed(b"const", 0)), ("one", 1), ("l-1", C.L - 1), ("2^252", 1 << 252)]
+MSM_TOP = [C.L - 1, C.L - 2, 1 << 252, (1 << 252) - 1, (1 << 252) + 1]
+# low four bits 0011: window 0 of this scalar is never the bucket of digit +-1, whatever the window width
+MSM_NOT_ONE = (msm_hashed(b"not-one", 0) & ~15) | 3
+
+
+def _case(name, scalars, pidx=None):
+    n = len(scalars)
+    return MsmCase(name, list(scalars), list(pidx) if pidx is not None else [i % 7 for i in range(n)], msm_bases())
+
+
+def msm_constant(n, s, name="constant"):
+    """one scalar for every term: every window holds ONE bucket, of n terms"""
+    return _case("%s-%d" % (name, n), [s] * n)
+
+
+def msm_prefix(n, m, s, name):
+    """m terms of one scalar, the other n - m terms zero (a zero has no digit: it lands in no bucket): bucket lists of exactly m"""
+    assert m <= n
+    return _case("%s-%d-of-%d" % (name, m, n), [s] * m + [0] * (n - m))
+
+
+def msm_cancel(n, s, m=None):
+    """P, -P alternating IN THE CALL as two encodings under one scalar (m terms, the rest zero): the identity for even m, sP for odd
+    m.  The order inside a bucket's list is not the call's: k_msm_prelude scatters with atomics.  Whatever it is, every list holds
+    as many P as -P (or one more P), so some prefix sum of it is the identity and, for m >= 4, some addition a doubling or a
+    cancellation; WHERE in the list is not fixed."""
+    m = n if m is None else m
+    return _case("cancel-pm-%d-of-%d" % (m, n), [s] * m + [0] * (n - m), [(0, MSM_NEG)[i & 1] for i in range(n)])
+
+
+def msm_cancel3(n, s):
+    """P, P, -P repeating"""
+    return _case("cancel-ppm-%d" % n, [s] * n, [(0, 0, MSM_NEG)[i % 3] for i in range(n)])
+
+
+def msm_same_point(n, s):
+    """D = 1: the second addition of every bucket is a doubling"""
+    return _case("same-point-%d" % n, [s] * n, [0] * n)
+
+
+def msm_identity_terms(n, where):
+    """the encoding bytes(32) as a term: "first" / "middle" (its place IN THE CALL), "alone" (the only term of its bucket in window 0)
+    or "all".  "first" and "middle" do not fix its place in the bucket's list -- k_msm_prelude scatters with atomics, the order
+    inside a bucket is not the call's -- so the identity as the start of an accumulator (ge_from_niels_first) is likely there, not
+    certain; "alone" and "all" guarantee it."""
+    if where == "all":
+        return _case("identity-all-%d" % n, [msm_hashed(b"ident", i) for i in range(n)], [MSM_IDENT] * n)
+    at = {"first": 0, "middle": n // 2, "alone": n // 2}[where]
+    scalars = [MSM_NOT_ONE] * n
+    pidx = [i % 7 for i in range(n)]
+    pidx[at] = MSM_IDENT
+    if where == "alone":
+        scalars[at] = 1
+    return _case("identity-%s-%d" % (where, n), scalars, pidx)
+
+
+def msm_small(n, bits):
+    """every scalar below 2^bits: the windows above are empty"""
+    return _case("small-%d-%d" % (bits, n), [msm_hashed(b"small%d" % bits, i, bits) for i in range(n)])
+
+
+def msm_sparse(n, at):
+    """all zero except term `at`"""
+    scalars = [0] * n
+    scalars[at] = msm_hashed(b"sparse", at) | 1
+    return _case("sparse-%d-of-%d" % (at, n), scalars)
+
+
+def msm_zero(n):
+    return _case("zero-%d" % n, [0] * n)
+
+
+def msm_ramp(n, shift=0):
+    """s_i = (i + 1) << shift: shift 0 hits every bucket of the low window in turn, shift 120 a window that straddles a word"""
+    return _case("ramp-%d-%d" % (shift, n), [(i + 1) << shift for i in range(n)])
+
+
+def msm_window_widths(c):
+    """the MSM's windows for width c (recode.h: msm_make_plan): K = ceil(253 / c) windows, the first K_wide of c bits, the others c - 1"""
+    K = -(-253 // c)
+    K_wide = 253 - K * (c - 1)
+    return [c] * K_wide + [c - 1] * (K - K_wide)
+
+
+def msm_half_chains(c):
+    """the chain constructions of test_host_arith.py::test_scalar_recodings for window width c: nine windows whose raw value is
+    exactly half their range -- alone (digits +half), with a carry coming in at the bottom, and starting one and two windows up.
+    Built on the plan's own window boundaries (at c = 14 only six windows have 14 bits), which for c <= 13 are multiples of c."""
+    wid = msm_window_widths(c)
+    top = [sum(wid[:k + 1]) - 1 for k in range(len(wid))]  # the top bit of every window
+
+    def chain(first):
+        return sum(1 << top[k] for k in range(first, first + 9))
+    return [x % C.L for x in (chain(0), chain(0) + (1 << (c - 1)) - 1, chain(1) + (1 << (c - 1)) + 1, chain(2) + (1 << c) - 1)]
+
+
+def msm_chains(n, c):
+    """the half-digit chains of width c first, hashed scalars after them"""
+    ch = msm_half_chains(c)[:n]
+    return _case("chains-c%d-%d" % (c, n), ch + [msm_hashed(b"chain-fill", i) for i in range(n - len(ch))])
+
+
+def msm_top(n):
+    return _case("top-%d" % n, [MSM_TOP[i % 5] for i in range(n)])
+
+
+def msm_skew(n):
+    """nine terms of ten share one scalar, the tenth is hashed: one huge bucket per window beside buckets of a few terms"""
+    s = MSM_CONSTANTS[0][1]
+    return _case("skew-%d" % n, [msm_hashed(b"skew", i) if i % 10 == 9 else s for i in range(n)])
+
+
+# where the digit cache of k_msm_prelude ends at c = 13, 12, 11 (csrc/msm.h: msm_prelude_dig_cap; at c = 14 nothing is cached)
+MSM_DIG_CAPS = {11: 24576, 12: 20480, 13: 12288, 14: 0}
+
+
+def msm_structured_cases(n, c):
+    """every family at n terms (families with a size of their own are padded with zero scalars, which reach no bucket)"""
+    s = MSM_CONSTANTS[0][1]
+    out = [msm_constant(n, v, "constant-" + tag) for tag, v in MSM_CONSTANTS]
+    out += [msm_prefix(n, m, s, "clamp") for m in (254, 255, 256, 257) if m <= n]
+    out += [msm_prefix(n, m, s, "pipeline") for m in range(1, 10) if m <= n]
+    out += [msm_cancel(n, s), msm_cancel(n, s, n - 1), msm_cancel3(n, s), msm_same_point(n, s)]
+    out += [msm_identity_terms(n, w) for w in ("first", "middle", "alone", "all")]
+    out += [msm_small(n, 16), msm_small(n, 64)]
+    out += [msm_sparse(n, at) for at in sorted({0, n - 1} | {e for cap in MSM_DIG_CAPS.values() for e in (cap - 1, cap) if 0 < e < n - 1})]
+    out += [msm_zero(n), msm_ramp(n), msm_ramp(n, 120), msm_chains(n, c), msm_top(n), msm_skew(n)]
+    assert all(len(x) == n for x in out)
+    return out

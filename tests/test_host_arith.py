@@ -1,5 +1,6 @@
 """CPU suite: the product's shared host/device arithmetic headers (csrc/*.h), host-compiled, vs the oracle.
 The same headers are what hipcc compiles for gfx950; the -m gpu tests then cover the device build."""
+import collections
 import ctypes
 import hashlib
 import importlib
@@ -9,6 +10,7 @@ import pytest
 from oracle.pyref import curve as C
 from oracle.pyref import merlin as M
 from oracle.pyref import protocol as O
+from tests import helpers as H
 
 P, L = C.P, C.L
 
@@ -297,6 +299,98 @@ def test_scalar_recodings(ht, monkeypatch):
             assert all(-(1 << (w - 1)) < dig[k] <= (1 << (w - 1)) for k in range(W - 1 if merged else W))
             assert not merged or 0 <= dig[W - 1] <= (1 << w)  # entries 1 .. 2^w: its own slot and the spare one after it
             assert sum(dig[k] << (w * k) for k in range(W)) == a
+
+
+def _msm_digits(ht, a, c):
+    """digits and widths of the MSM's windows for scalar a (recode.h through ht_msm_recode), and the carry INTO every window"""
+    dig, wid = (ctypes.c_int16 * 64)(), (ctypes.c_uint32 * 64)()
+    K = ht.ht_msm_recode(a.to_bytes(32, "little"), c, dig, wid)
+    assert K == -(-253 // c)
+    carries, carry, off = [], 0, 0
+    for k in range(K):
+        carries.append(carry)
+        v = ((a >> off) & ((1 << wid[k]) - 1)) + carry
+        carry = 1 if v > (1 << (wid[k] - 1)) else 0
+        assert dig[k] == v - (carry << wid[k])
+        off += wid[k]
+    return list(dig[:K]), list(wid[:K]), carries
+
+
+def _msm_bucket_sizes(ht, scalars, c):
+    """per window: {bucket (|digit|): its number of terms} -- what k_msm_prelude's histogram holds"""
+    seen, sizes = {}, [collections.Counter() for _ in range(-(-253 // c))]
+    for a in scalars:
+        if a not in seen:
+            seen[a] = _msm_digits(ht, a, c)[0]
+        for k, d in enumerate(seen[a]):
+            if d:
+                sizes[k][abs(d)] += 1
+    return sizes
+
+
+def test_structured_msm_families_are_what_they_claim(ht):
+    """The scalar families of tests/helpers.py that tests/test_gpu_msm_structured.py feeds to the bucket MSM exist for one property
+    each of the bucket lists they make.  Checked here, through the engine's own recoding, for every window width: an edit of a
+    builder must not turn an edge case into a random one unnoticed."""
+    n = 300
+    for c in range(4, 15):
+        nb = 1 << (c - 1)
+        # constant: every window whose digit is not zero holds ONE bucket, with all n >= 256 terms (size class 255)
+        for tag, s in H.MSM_CONSTANTS:
+            sizes = _msm_bucket_sizes(ht, H.msm_constant(n, s).scalars, c)
+            assert any(sizes) and all(list(w.values()) == [n] for w in sizes if w), (c, tag)
+        # class-clamp edge and pipeline edge: bucket lists of exactly m terms, the zero padding reaches no bucket
+        for name, ms in (("clamp", (254, 255, 256, 257)), ("pipeline", range(1, 10))):
+            for m in ms:
+                sizes = _msm_bucket_sizes(ht, H.msm_prefix(n, m, H.MSM_CONSTANTS[0][1], name).scalars, c)
+                assert 2 * sum(1 for w in sizes if w) > len(sizes) and all(list(w.values()) == [m] for w in sizes if w), (c, name, m)
+        # small scalars: a carry may reach the first window that starts at or above bit `bits` (as digit +1); all above are empty
+        for bits in (16, 64):
+            case = H.msm_small(n, bits)
+            assert max(case.scalars) < 1 << bits and max(case.scalars) >> (bits - 4)
+            wid = _msm_digits(ht, 1, c)[1]
+            k0 = next(k for k in range(len(wid)) if sum(wid[:k]) >= bits)
+            sizes = _msm_bucket_sizes(ht, case.scalars, c)
+            assert all(sizes[k] for k in range(k0)) and set(sizes[k0]) <= {1} and not any(sizes[k0 + 1:]), (c, bits)
+        # half-digit chains: digits of exactly +2^(w-1), and a carry that walks up at least eight windows in a row
+        chains = H.msm_half_chains(c)
+        assert H.msm_window_widths(c) == _msm_digits(ht, 1, c)[1]
+        if c <= 13:  # the constructions of test_scalar_recodings, whose windows all have c bits
+            half_chain = sum(1 << (c * k + c - 1) for k in range(9))
+            assert chains == [half_chain, half_chain + (1 << (c - 1)) - 1, (half_chain << c) + (1 << (c - 1)) + 1, (half_chain << (2 * c)) + (1 << c) - 1]
+        assert H.msm_chains(n, c).scalars[:4] == chains and len(set(H.msm_chains(n, c).scalars)) == n
+        for a in (chains[0], chains[3]):  # no carry reaches the chain: nine digits of +half
+            dig, wid, carries = _msm_digits(ht, a, c)
+            assert sum(1 for d, w in zip(dig, wid) if d == 1 << (w - 1)) >= 9 and sum(carries) <= 1, (c, hex(a))
+        for a in (chains[1], chains[2]):  # a carry comes in at the bottom and every half window passes it on
+            dig, wid, carries = _msm_digits(ht, a, c)
+            run = best = 0
+            for cy in carries:
+                run = run + 1 if cy else 0
+                best = max(best, run)
+            assert best >= 8, (c, hex(a), carries)
+        # ramp: every bucket of window 0 is hit once there are nb terms; shifted by 120 bits, a window that straddles bit 128
+        sizes = _msm_bucket_sizes(ht, H.msm_ramp(max(n, nb)).scalars, c)
+        assert set(sizes[0]) == set(range(1, nb + 1)), c
+        if 128 % c:  # (for c = 4 and 8 a window ends at bit 127)
+            wid = _msm_digits(ht, 1, c)[1]
+            k = next(k for k in range(len(wid)) if sum(wid[:k]) < 128 < sum(wid[:k + 1]))
+            assert len(_msm_bucket_sizes(ht, H.msm_ramp(n, 120).scalars, c)[k]) > 1, c
+        # skew: a bucket of size class 255 and one of class <= 4 in the same window
+        sizes = _msm_bucket_sizes(ht, H.msm_skew(n).scalars, c)
+        assert any(max(w.values()) >= 255 and min(w.values()) <= 4 for w in sizes if w), c
+        # identity "alone": the identity's term is the only one in bucket 1 of window 0
+        case = H.msm_identity_terms(n, "alone")
+        assert _msm_bucket_sizes(ht, case.scalars, c)[0][1] == 1 and case.pidx[case.scalars.index(1)] == H.MSM_IDENT, c
+        # sparse and all zero: one term's buckets, no bucket at all
+        assert all(sum(w.values()) <= 1 for w in _msm_bucket_sizes(ht, H.msm_sparse(n, n - 1).scalars, c))
+        assert not any(_msm_bucket_sizes(ht, H.msm_zero(n).scalars, c))
+    # the sizes the device test runs: every family has n terms, and the large size puts single terms on both sides of every digit-cache end
+    for size, c in ((100, 4), (300, 5), (25000, 11)):
+        names = [x.name for x in H.msm_structured_cases(size, c)]
+        assert len(set(names)) == len(names)
+    assert {"sparse-%d-of-25000" % (e - d) for e in (12288, 20480, 24576) for d in (0, 1)} <= set(names)
+    assert H.msm_bases()[H.MSM_NEG + 3] == -H.msm_bases()[3] and H.msm_bases()[H.MSM_IDENT].is_identity()
 
 
 def test_weight_chain_single_forms(ht):
