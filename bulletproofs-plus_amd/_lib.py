@@ -189,6 +189,17 @@ SYMBOLS = [
     ("bpp_device_chain_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     ("bpp_shader_clock", c_int, [c_void_p, c_uint32, POINTER(c_double)]),
     ("bpp_transcript_new", c_int, [c_void_p, c_size_t, c_void_p]),
+    ("bpp_transcript_append_message", c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
+    ("bpp_transcript_challenge_bytes", c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
+    ("bpp_verify_batch_states", c_int, [c_void_p, c_uint64, POINTER(VerifyItem), c_size_t, c_int, c_size_t, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_size_t]),
+    ("bpp_verify_batch_packed_states", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_int, c_size_t, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_size_t]),
+    ("bpp_verify_resident_states", c_int, [c_void_p, c_uint64, c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t]),
+    ("bpp_prove_batch_mixed_states", c_int, [c_void_p, c_uint64, POINTER(ProveItem), c_size_t, c_void_p, c_size_t, POINTER(c_size_t),
+                                             POINTER(c_int), c_void_p, c_void_p, c_size_t]),
+    ("bpp_prove_openings_states", c_int, [c_void_p, c_uint64, POINTER(ProveItem), c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
+                                          POINTER(c_size_t), POINTER(c_int), c_void_p, c_void_p, c_size_t]),
     ("bpp_batch_secret_bytes", c_int, [c_void_p, c_uint64, POINTER(c_uint64)]),
     ("bpp_prove_secret_bytes", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
 ]
@@ -205,7 +216,10 @@ def load():
         raise RuntimeError("libbpp_hip.so is missing (%s): run __graft_entry__.build(); there is no CPU fallback"
                            % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
+    other_build = bool(os.environ.get("BPP_LIB_PATH"))
     for name, res, args in SYMBOLS:
+        if other_build and not hasattr(lib, name):
+            continue  # an OLDER build named by BPP_LIB_PATH (the parent arm of an A/B) lacks the newest entry points: calling one raises
         fn = getattr(lib, name)  # AttributeError if the library does not export it
         fn.restype = res
         fn.argtypes = args

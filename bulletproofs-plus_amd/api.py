@@ -250,6 +250,44 @@ class Transcript:
         _lib.load().bpp_transcript_new(_buf(self.label), len(self.label), out)
         return bytes(out)
 
+    # ---- merlin's own operations, on the state (host only: bpp_transcript_append_message / bpp_transcript_challenge_bytes).
+    # A label-only transcript becomes a state-carrying one first; from then on `state` is what the engine is given.
+    def _materialise(self):
+        if self.state is None:
+            self.state = self.strobe_state()
+            self.label = None
+        return (ctypes.c_uint8 * 203).from_buffer_copy(self.state)
+
+    def append_message(self, label, message):
+        """Transcript::append_message"""
+        label, message = bytes(label), bytes(message)
+        st = self._materialise()
+        _check(_lib.load().bpp_transcript_append_message(st, _buf(label), len(label), _buf(message), len(message)))
+        self.state = bytes(st)
+
+    def append_u64(self, label, x):
+        """Transcript::append_u64: the eight little-endian bytes of x"""
+        self.append_message(label, int(x).to_bytes(8, "little"))
+
+    def challenge_bytes(self, label, n):
+        """Transcript::challenge_bytes -> n bytes"""
+        label = bytes(label)
+        st = self._materialise()
+        out = (ctypes.c_uint8 * max(int(n), 1))()
+        _check(_lib.load().bpp_transcript_challenge_bytes(st, _buf(label), len(label), out, int(n)))
+        self.state = bytes(st)
+        return bytes(out)[:int(n)]
+
+    def _advance_to(self, state203):
+        self.state = bytes(state203)
+        self.label = None
+
+
+def _check_advance(transcripts):
+    """advance=True writes one state into each transcript object: an object passed for several items would end up with the last one's"""
+    if len({id(t) for t in transcripts}) != len(transcripts):
+        raise ProofError(ProofErrorKind.InvalidArgument, "advance=True needs one Transcript object per item")
+
 
 class PedersenGens:
     """src/generators/pedersen_gens.rs:25-36; base points are fixed by the extension degree (src/ristretto.rs:67-76)."""
@@ -568,11 +606,16 @@ class RangeProof:
         return [RangeProof.from_bytes(raw[i * stride:i * stride + plen.value]) for i in range(n)]
 
     @staticmethod
-    def prove_batch_mixed(transcripts, statements, witnesses, rng_bytes):
+    def prove_batch_mixed(transcripts, statements, witnesses, rng_bytes, advance=False):
         """n x RangeProof::prove_with_rng of ANY aggregation factors (powers of two up to the parameters' maximum) in one engine
         call (bpp_prove_batch_mixed).  Returns one entry per item: its RangeProof, or the ProofError that prove_batch on that item
         alone would raise, or -- "prove_check" = 1 -- an EngineError with code EngineError.SELF_CHECK for a proof that failed the
-        self-check.  An item that fails never stops the others."""
+        self-check.  An item that fails never stops the others.
+
+        advance=True (bpp_prove_batch_mixed_states): as `&mut Transcript` in the reference, transcripts[i] of every item that
+        succeeds becomes the transcript as the prover left it (after the last challenge); a failed item's object is untouched."""
+        if advance:
+            _check_advance(transcripts)
         if not statements or len(statements) != len(witnesses) or len(transcripts) != len(statements) or \
                 len(rng_bytes) != len(statements):
             raise ProofError(ProofErrorKind.InvalidArgument, "Range statements, witnesses, transcripts length mismatch")
@@ -586,10 +629,13 @@ class RangeProof:
             except ProofError as e:
                 res[i] = e
         if keep:
+            states = [] if advance else None
             raw, codes, msgs = RangeProof._prove_mixed_call(RangeProof._prove_marshal(
                 [transcripts[i] for i in keep], [statements[i] for i in keep], [witnesses[i] for i in keep],
-                [rng_bytes[i] for i in keep]))
+                [rng_bytes[i] for i in keep]), states)
             for k, i in enumerate(keep):
+                if advance and codes[k] == 0:
+                    transcripts[i]._advance_to(states[k])
                 if codes[k] == EngineError.SELF_CHECK:
                     res[i] = EngineError("bpp engine error %d: %s" % (codes[k], msgs[k]), codes[k])
                 else:
@@ -597,9 +643,10 @@ class RangeProof:
         return res
 
     @staticmethod
-    def _prove_mixed_call(marshalled):
+    def _prove_mixed_call(marshalled, states=None):
         """bpp_prove_batch_mixed over marshalled items -> (proof bytes per item, codes, messages); an engine fault (a negative code
-        other than EngineError.SELF_CHECK, which is an item's own outcome) raises EngineError"""
+        other than EngineError.SELF_CHECK, which is an item's own outcome) raises EngineError.  states: a list that receives the
+        203-byte advanced transcript of every item (bpp_prove_batch_mixed_states; meaningful where the item's code is 0)"""
         params, items, n, _keep = marshalled
         eng = params.engine
         stride = 1 + 32 * (6 + 5 + 2 * 12)
@@ -607,7 +654,13 @@ class RangeProof:
         lens = (c_size_t * n)()
         status = (ctypes.c_int * n)()
         err = ctypes.create_string_buffer(256)
-        rc = eng.lib.bpp_prove_batch_mixed(eng.ctx, params.handle, items, n, out, stride, lens, status, err, 256)
+        if states is not None:
+            sbuf = (ctypes.c_uint8 * (203 * n))()
+            rc = eng.lib.bpp_prove_batch_mixed_states(eng.ctx, params.handle, items, n, out, stride, lens, status, sbuf, err, 256)
+            sraw = bytes(sbuf)
+            states.extend(sraw[203 * i:203 * i + 203] for i in range(n))
+        else:
+            rc = eng.lib.bpp_prove_batch_mixed(eng.ctx, params.handle, items, n, out, stride, lens, status, err, 256)
         codes = [status[i] for i in range(n)]
         faults = [c for c in [rc] + codes if c < 0 and c != EngineError.SELF_CHECK]
         if faults:
@@ -635,13 +688,16 @@ class RangeProof:
         return params, items, n, keep
 
     @staticmethod
-    def prove_openings(transcripts, witnesses, minimum_value_promises, seed_nonces, rng_bytes, params):
+    def prove_openings(transcripts, witnesses, minimum_value_promises, seed_nonces, rng_bytes, params, advance=False):
         """Prove from the openings alone (bpp_prove_openings): n x (commit every opening, RangeStatement::init over the commitments,
         RangeProof::prove_with_rng) of any aggregation factors in ONE engine call, the commitments made where the prover's witness
         check computes them anyway.  minimum_value_promises[i]: one Option<u64> per opening of witnesses[i]; seed_nonces[i]: 32
         bytes or None (only with one opening).  Returns (statements, proofs), one entry each per item: the RangeStatement built
         from the commitments the engine returned and its RangeProof, or -- in both lists -- the ProofError / EngineError
-        (EngineError.SELF_CHECK) of an item that failed, which never stops the others."""
+        (EngineError.SELF_CHECK) of an item that failed, which never stops the others.
+        advance=True (bpp_prove_openings_states): transcripts[i] of every item that succeeds becomes the prover's final transcript."""
+        if advance:
+            _check_advance(transcripts)
         n = len(witnesses)
         sts, res = [None] * n, [None] * n
         keep = []
@@ -665,7 +721,12 @@ class RangeProof:
         lens = (c_size_t * cnt)()
         status = (ctypes.c_int * cnt)()
         err = ctypes.create_string_buffer(256)
-        rc = eng.lib.bpp_prove_openings(eng.ctx, params.handle, items, cnt, comms, cstride, out, stride, lens, status, err, 256)
+        if advance:
+            sbuf = (ctypes.c_uint8 * (203 * cnt))()
+            rc = eng.lib.bpp_prove_openings_states(eng.ctx, params.handle, items, cnt, comms, cstride, out, stride, lens, status, sbuf, err, 256)
+            sraw = bytes(sbuf)
+        else:
+            rc = eng.lib.bpp_prove_openings(eng.ctx, params.handle, items, cnt, comms, cstride, out, stride, lens, status, err, 256)
         codes = [status[k] for k in range(cnt)]
         faults = [c for c in [rc] + codes if c < 0 and c != EngineError.SELF_CHECK]
         if faults:
@@ -677,6 +738,8 @@ class RangeProof:
                 cs = [craw[k * cstride + 32 * j:k * cstride + 32 * j + 32] for j in range(m)]
                 sts[i] = RangeStatement.init(params, cs, list(minimum_value_promises[i]), seed_nonces[i])
                 res[i] = RangeProof.from_bytes(raw[k * stride:k * stride + lens[k]])
+                if advance:
+                    transcripts[i]._advance_to(sraw[203 * k:203 * k + 203])
                 continue
             first = None
             if codes[k] == EngineError.SELF_CHECK and seed_nonces[i] is not None:
@@ -691,11 +754,17 @@ class RangeProof:
         return sts, res
 
     @staticmethod
-    def prove_with_rng(transcript, statement, witness, rng):
-        """RangeProof::prove_with_rng; `rng` = object with fill_bytes(n) (the external RNG) or the bytes themselves"""
+    def prove_with_rng(transcript, statement, witness, rng, advance=False):
+        """RangeProof::prove_with_rng; `rng` = object with fill_bytes(n) (the external RNG) or the bytes themselves.
+        advance=True: `transcript` is advanced as the reference's `&mut Transcript` is (on success; an error leaves it untouched)."""
         need = 32 * (RangeProof.rounds_for(statement) + 3)
         rb = rng if isinstance(rng, (bytes, bytearray)) else b"".join(rng.fill_bytes(32) for _ in range(need // 32))
-        return RangeProof.prove_batch([transcript], [statement], [witness], [bytes(rb)])[0]
+        if not advance:
+            return RangeProof.prove_batch([transcript], [statement], [witness], [bytes(rb)])[0]
+        res = RangeProof.prove_batch_mixed([transcript], [statement], [witness], [bytes(rb)], advance=True)[0]
+        if isinstance(res, Exception):
+            raise res
+        return res
 
     @staticmethod
     def prove(transcript, statement, witness):
@@ -768,12 +837,17 @@ class RangeProof:
         return max((st.generators for st in statements), key=lambda g: g.max_aggregation_factor())
 
     @staticmethod
-    def verify_batch(transcripts, statements, proofs, action, chunk=MAX_RANGE_PROOF_BATCH_SIZE):
+    def verify_batch(transcripts, statements, proofs, action, chunk=MAX_RANGE_PROOF_BATCH_SIZE, advance=False):
         """RangeProof::verify_batch (src/range_proof.rs:712-752) -> list[ExtendedMask | None].
 
         `chunk` proofs form one reference batch (own weight transcript, own final MSM); unlike the reference's
-        wrapper every chunk is verified.  chunk=0: the whole input is one batch (the private `verify`)."""
+        wrapper every chunk is verified.  chunk=0: the whole input is one batch (the private `verify`).
+
+        advance=True (bpp_verify_batch_states): as `&mut [Transcript]` in the reference, every transcripts[i] becomes the transcript
+        as the verifier left it (r1, s1 and every d1 appended) when the call succeeds; an error leaves every object untouched."""
         RangeProof._check_batch_args(transcripts, statements, proofs)
+        if advance:
+            _check_advance(transcripts)
         params = RangeProof._largest_params(statements)
         eng = params.engine
         items, keep = RangeProof._items(transcripts, statements, proofs)
@@ -781,8 +855,16 @@ class RangeProof:
         masks = (ctypes.c_uint8 * (n * t * 32))()
         present = (ctypes.c_uint8 * n)()
         err = ctypes.create_string_buffer(256)
-        rc = eng.lib.bpp_verify_batch(eng.ctx, params.handle, items, n, int(action), chunk, masks, present, err, 256)
+        if advance:
+            sbuf = (ctypes.c_uint8 * (203 * n))()
+            rc = eng.lib.bpp_verify_batch_states(eng.ctx, params.handle, items, n, int(action), chunk, masks, present, sbuf, err, 256)
+        else:
+            rc = eng.lib.bpp_verify_batch(eng.ctx, params.handle, items, n, int(action), chunk, masks, present, err, 256)
         _check(rc, eng.ctx, err)
+        if advance:
+            sraw = bytes(sbuf)
+            for i, tr in enumerate(transcripts):
+                tr._advance_to(sraw[203 * i:203 * i + 203])
         raw = bytes(masks)
         out = []
         for i in range(n):
@@ -836,17 +918,27 @@ class ResidentBatch:
         # ctypes marshalling (Python only) / the C-ABI call: host buffers -> parsed, packed, resident in HBM
         self.marshal_seconds, self.upload_seconds = t1 - t0, _time.perf_counter() - t1
 
-    def verify(self, action=VerifyAction.VerifyOnly, chunk=0):
+    def verify(self, action=VerifyAction.VerifyOnly, chunk=0, states=False):
+        """states=True (bpp_verify_resident_states): returns (masks, [the 203-byte advanced transcript of every proof])"""
         masks = (ctypes.c_uint8 * (self.n * self.t * 32))()
         present = (ctypes.c_uint8 * self.n)()
         err = ctypes.create_string_buffer(256)
-        rc = self.engine.lib.bpp_verify_resident(self.engine.ctx, self.handle, int(action), chunk, masks, present, err,
-                                                 256)
+        if states:
+            sbuf = (ctypes.c_uint8 * (203 * self.n))()
+            rc = self.engine.lib.bpp_verify_resident_states(self.engine.ctx, self.handle, int(action), chunk, masks, present, sbuf,
+                                                            err, 256)
+        else:
+            rc = self.engine.lib.bpp_verify_resident(self.engine.ctx, self.handle, int(action), chunk, masks, present, err,
+                                                     256)
         _check(rc, self.engine.ctx, err)
         raw = bytes(masks)
         t = self.t
-        return [ExtendedMask.assign(t, [raw[(i * t + k) * 32:(i * t + k) * 32 + 32] for k in range(t)])
-                if present[i] else None for i in range(self.n)]
+        out = [ExtendedMask.assign(t, [raw[(i * t + k) * 32:(i * t + k) * 32 + 32] for k in range(t)])
+               if present[i] else None for i in range(self.n)]
+        if states:
+            sraw = bytes(sbuf)
+            return out, [sraw[203 * i:203 * i + 203] for i in range(self.n)]
+        return out
 
     def verify_only(self, chunk=0):
         """VerifyAction::VerifyOnly without the mask vector (all None by definition): no per-item work on the host"""

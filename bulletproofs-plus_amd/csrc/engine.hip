@@ -137,6 +137,14 @@ inline void wipe(void *p, size_t n) {
   if (p && n) explicit_bzero(p, n);
 }
 
+// a row of BPP_STATE_ROW_WORDS words as the kernels write an advanced transcript (kernels_verify.h) -> the ABI's 203 bytes
+inline void state_row_to_bytes(uint8_t *out203, const uint32_t *row) {
+  memcpy(out203, row, 200);  // little-endian host, as everywhere in this file
+  out203[200] = (uint8_t)row[50];
+  out203[201] = (uint8_t)(row[50] >> 8);
+  out203[202] = (uint8_t)(row[50] >> 16);
+}
+
 void set_err(char *errbuf, size_t len, const std::string &m) {
   if (errbuf && len) {
     snprintf(errbuf, len, "%s", m.c_str());
@@ -441,6 +449,10 @@ struct Batch {
   PinnedBuf<uint8_t> h_masks_check;  // "verify_check": where passes 2 and 3 leave their masks (verify_flow wipes it before it returns)
   PinnedBuf<uint8_t> h_wide;  // chain mode 2: the host sponges' 64 bytes per proof, reduced on the device
   PinnedBuf<uint32_t> h_status, h_ident;
+  // bpp_verify_*_states: the advanced transcripts as PASS 1 writes them, rows of BPP_STATE_ROW_WORDS words (mapped, public data);
+  // allocated by the first call that asks for them, written only while want_states is set (verify_chunked_locked)
+  PinnedBuf<uint32_t> h_states;
+  bool want_states = false;
   // k_results_out writes one summary word per BPP_STATUS_BLOCK proofs and a block's words only when there is something in them;
   // settle_status() makes h_status whole again on the host (a block the kernel skipped is all zero: cleared here if it was not)
   PinnedBuf<uint32_t> h_status_any;
@@ -466,7 +478,7 @@ void adopt_buffers(Batch &dst, Batch &src) {
   BPP_ADOPT(msm.cls_hist);
   BPP_ADOPT(msm.buckets); BPP_ADOPT(msm.Q); BPP_ADOPT(msm.W); BPP_ADOPT(msm.R); BPP_ADOPT(msm.comp32);
   BPP_ADOPT(msm.is_identity); BPP_ADOPT(msm.term_sidx); BPP_ADOPT(msm.term_pidx); BPP_ADOPT(msm.group_off);
-  BPP_ADOPT(h_rng); BPP_ADOPT(h_weights); BPP_ADOPT(h_wide); BPP_ADOPT(h_status); BPP_ADOPT(h_status_any); BPP_ADOPT(h_ident); BPP_ADOPT(h_masks);
+  BPP_ADOPT(h_rng); BPP_ADOPT(h_weights); BPP_ADOPT(h_wide); BPP_ADOPT(h_status); BPP_ADOPT(h_status_any); BPP_ADOPT(h_ident); BPP_ADOPT(h_masks); BPP_ADOPT(h_states);
 #undef BPP_ADOPT
   // what is known about the adopted status words travels with them (settle_status clears only the blocks that may hold something);
   // a verification whose results were never looked at leaves them unknown
@@ -1641,6 +1653,30 @@ int bpp_transcript_new(const uint8_t *label, size_t label_len, uint8_t state203[
   return BPP_OK;
 }
 
+// Transcript::append_message / challenge_bytes on a 203-byte state, in place (host only: merlin.h).  A state whose position is not
+// inside the block is refused, as the upload refuses it.
+int bpp_transcript_append_message(uint8_t state203[203], const uint8_t *label, size_t label_len, const uint8_t *msg, size_t msg_len) {
+  if (!state203 || (!label && label_len) || (!msg && msg_len)) return BPP_ERR_INVALID_ARGUMENT;
+  if (label_len > 0xffffffffu || msg_len > 0xffffffffu) return BPP_ERR_INVALID_LENGTH;
+  if (state203[200] >= BPP_STROBE_R) return BPP_ERR_INVALID_ARGUMENT;
+  Strobe s;
+  strobe_from_bytes(s, state203);
+  merlin_append_message(s, label, (uint32_t)label_len, msg, (uint32_t)msg_len);
+  strobe_to_bytes(state203, s);
+  return BPP_OK;
+}
+
+int bpp_transcript_challenge_bytes(uint8_t state203[203], const uint8_t *label, size_t label_len, uint8_t *out, size_t out_len) {
+  if (!state203 || (!label && label_len) || (!out && out_len)) return BPP_ERR_INVALID_ARGUMENT;
+  if (label_len > 0xffffffffu || out_len > 0xffffffffu) return BPP_ERR_INVALID_LENGTH;
+  if (state203[200] >= BPP_STROBE_R) return BPP_ERR_INVALID_ARGUMENT;
+  Strobe s;
+  strobe_from_bytes(s, state203);
+  merlin_challenge_bytes(s, label, (uint32_t)label_len, out, (uint32_t)out_len);
+  strobe_to_bytes(state203, s);
+  return BPP_OK;
+}
+
 int bpp_weights_from_chains(const uint8_t *rng32_all, size_t n_groups, size_t n_per_group, uint8_t *weights32_out) {
   if ((!rng32_all || !weights32_out) && n_groups * n_per_group) return BPP_ERR_INVALID_ARGUMENT;
   if (n_groups == 0 || n_per_group == 0) return BPP_OK;
@@ -2041,12 +2077,20 @@ void enqueue_phase1(bpp_ctx *ctx, Batch &b, StageTimer &tm, bool pass1_only, uin
     const int force_wave = ctx->opt.transcripts_wave;  // (tests force either kernel)
     const bool wave = force_wave >= 0 ? force_wave != 0 : b.B <= BPP_TRANSCRIPTS_WAVE_MAX;
     uint8_t *rng_host = fetch_rng ? b.h_rng.dev() : nullptr;  // mapped page-locked memory: no device-to-host copy behind PASS 1
-    if (wave)
-      hipLaunchKernelGGL(k_transcripts_wave, dim3(b.B), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.minvals.p, b.states.p,
-                         P.d_hg32.p, P.n_bits, P.t, b.B, b.cs, b.chal.p, b.rng_out.p, b.status.p, rng_host);
+    if (b.want_states) {  // the kernels' other instantiation: every proof's advanced transcript into b.h_states as well
+      b.h_states.resize((size_t)b.B * BPP_STATE_ROW_WORDS);
+      if (wave)
+        hipLaunchKernelGGL(k_transcripts_wave<true>, dim3(b.B), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.minvals.p, b.states.p,
+                           P.d_hg32.p, P.n_bits, P.t, b.B, b.cs, b.chal.p, b.rng_out.p, b.status.p, rng_host, b.h_states.dev());
+      else
+        hipLaunchKernelGGL(k_transcripts<true>, dim3(cdiv(b.B, 64)), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.minvals.p, b.states.p,
+                           P.d_hg32.p, P.n_bits, P.t, b.B, b.cs, b.chal.p, b.rng_out.p, b.status.p, rng_host, b.h_states.dev());
+    } else if (wave)
+      hipLaunchKernelGGL(k_transcripts_wave<false>, dim3(b.B), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.minvals.p, b.states.p,
+                         P.d_hg32.p, P.n_bits, P.t, b.B, b.cs, b.chal.p, b.rng_out.p, b.status.p, rng_host, (uint32_t *)nullptr);
     else
-      hipLaunchKernelGGL(k_transcripts, dim3(cdiv(b.B, 64)), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.minvals.p, b.states.p,
-                         P.d_hg32.p, P.n_bits, P.t, b.B, b.cs, b.chal.p, b.rng_out.p, b.status.p, rng_host);
+      hipLaunchKernelGGL(k_transcripts<false>, dim3(cdiv(b.B, 64)), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.minvals.p, b.states.p,
+                         P.d_hg32.p, P.n_bits, P.t, b.B, b.cs, b.chal.p, b.rng_out.p, b.status.p, rng_host, (uint32_t *)nullptr);
   }
   tm.mark(M_TRANSCRIPTS);
   if (dev_chain) {
@@ -2923,17 +2967,28 @@ void give_masks(const ResidentRun &run, uint32_t p0, uint32_t p1, bool give, uin
 
 // (the context's lock is held.)  The chunked form: equal chunks under one action; the first chunk with a finding ends the call
 // with that finding, and masks are handed out only when no chunk had one.
+// states_out203 != nullptr (bpp_verify_*_states): PASS 1 also writes every proof's advanced transcript (b.h_states), and a call that
+// returns BPP_OK hands them out as rows of 203 bytes; any other outcome leaves the caller's buffer alone.
 int verify_chunked_locked(bpp_ctx *ctx, uint64_t batch, int action, size_t chunk, uint8_t *masks_out, uint8_t *mask_present, char *errbuf,
-                          size_t errbuf_len) {
+                          size_t errbuf_len, uint8_t *states_out203 = nullptr) {
   try {
     auto it = ctx->batches.find(batch);
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle", errbuf, errbuf_len);
     if (action < 0 || action > 2) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "unknown verify action", errbuf, errbuf_len);
-    ResidentRun run(*it->second);
+    Batch &b = *it->second;
+    if (states_out203 && b.ext_challenges)
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "no transcript states: the caller replayed PASS 1 of this batch", errbuf, errbuf_len);
+    b.want_states = states_out203 != nullptr;
+    ScopeExit states_off{[&] { b.want_states = false; }};
+    ResidentRun run(b);
     verify_flow(ctx, run, chunk, nullptr, nullptr, action);
     for (const ShardFinding &f : run.found)
       if (f.tier != BPP_TIER_NONE) return fail(ctx, f.code, f.msg, errbuf, errbuf_len);
     give_masks(run, 0, run.b.B, action != BPP_VERIFY_ONLY, masks_out, mask_present);
+    if (states_out203) {
+      if (!b.h_states.p || b.h_states.n < (size_t)b.B * BPP_STATE_ROW_WORDS) throw EngineError{BPP_ERR_ENGINE, "transcript states were not written"};
+      for (uint32_t p = 0; p < b.B; p++) state_row_to_bytes(states_out203 + (size_t)p * 203, b.h_states.data() + (size_t)p * BPP_STATE_ROW_WORDS);
+    }
     return BPP_OK;
   }
   BPP_CATCH(ctx, errbuf, errbuf_len)
@@ -2976,13 +3031,14 @@ int verify_groups_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fir
 // is held across all three and taken here, BEFORE any of them takes the context's lock.
 template <class Upload>
 int verify_uploaded(bpp_ctx *ctx, size_t n_items, Upload upload, int action, size_t chunk, uint8_t *masks_out, uint8_t *mask_present,
-                    char *errbuf, size_t errbuf_len) {
+                    char *errbuf, size_t errbuf_len, uint8_t *states_out203 = nullptr) {
   if (!ctx) return BPP_ERR_BAD_HANDLE;
   GateHold gate(ctx->device, n_items <= BPP_GATE_SMALL_PROOFS);  // held across upload and verification of a small call
   uint64_t h = 0;
   int rc = upload(&h);
   if (rc != BPP_OK) return rc;
-  rc = bpp_verify_resident(ctx, h, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
+  rc = states_out203 ? bpp_verify_resident_states(ctx, h, action, chunk, masks_out, mask_present, states_out203, errbuf, errbuf_len)
+                     : bpp_verify_resident(ctx, h, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
   (void)bpp_batch_destroy(ctx, h);
   return rc;
 }
@@ -2998,6 +3054,16 @@ int bpp_verify_resident(bpp_ctx *ctx, uint64_t batch, int action, size_t chunk, 
   GateHold gate(ctx->device, n_peek && n_peek <= BPP_GATE_SMALL_PROOFS);  // small calls queue for the device (DeviceState)
   BPP_ENTRY(ctx);
   return verify_chunked_locked(ctx, batch, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
+}
+
+int bpp_verify_resident_states(bpp_ctx *ctx, uint64_t batch, int action, size_t chunk, uint8_t *masks_out, uint8_t *mask_present,
+                               uint8_t *states_out203, char *errbuf, size_t errbuf_len) {
+  if (!ctx) return BPP_ERR_BAD_HANDLE;
+  const uint32_t n_peek = batch_size_peek(ctx, batch);
+  GateHold gate(ctx->device, n_peek && n_peek <= BPP_GATE_SMALL_PROOFS);
+  BPP_ENTRY(ctx);
+  if (!states_out203) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
+  return verify_chunked_locked(ctx, batch, action, chunk, masks_out, mask_present, errbuf, errbuf_len, states_out203);
 }
 
 int bpp_verify_resident_groups_actions(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first, size_t n_groups, const int *actions,
@@ -3034,6 +3100,29 @@ int bpp_verify_batch_packed(bpp_ctx *ctx, uint64_t params, const bpp_packed_batc
                             uint8_t *masks_out, uint8_t *mask_present, char *errbuf, size_t errbuf_len) {
   auto upload = [&](uint64_t *h) -> int { return bpp_batch_upload_packed(ctx, params, in, h, errbuf, errbuf_len); };
   return verify_uploaded(ctx, in ? in->n_items : SIZE_MAX, upload, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
+}
+
+// the same calls with the advanced transcripts handed back (bpp.h, "Advanced transcripts")
+int bpp_verify_batch_states(bpp_ctx *ctx, uint64_t params, const bpp_verify_item *items, size_t n_items, int action, size_t chunk,
+                            uint8_t *masks_out, uint8_t *mask_present, uint8_t *states_out203, char *errbuf, size_t errbuf_len) {
+  if (!ctx) return BPP_ERR_BAD_HANDLE;
+  if (!states_out203) {
+    BPP_ENTRY(ctx);
+    return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
+  }
+  auto upload = [&](uint64_t *h) -> int { return bpp_batch_upload(ctx, params, items, n_items, h, errbuf, errbuf_len); };
+  return verify_uploaded(ctx, n_items, upload, action, chunk, masks_out, mask_present, errbuf, errbuf_len, states_out203);
+}
+
+int bpp_verify_batch_packed_states(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, int action, size_t chunk,
+                                   uint8_t *masks_out, uint8_t *mask_present, uint8_t *states_out203, char *errbuf, size_t errbuf_len) {
+  if (!ctx) return BPP_ERR_BAD_HANDLE;
+  if (!states_out203) {
+    BPP_ENTRY(ctx);
+    return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
+  }
+  auto upload = [&](uint64_t *h) -> int { return bpp_batch_upload_packed(ctx, params, in, h, errbuf, errbuf_len); };
+  return verify_uploaded(ctx, in ? in->n_items : SIZE_MAX, upload, action, chunk, masks_out, mask_present, errbuf, errbuf_len, states_out203);
 }
 
 }  // extern "C"

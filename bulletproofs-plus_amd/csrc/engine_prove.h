@@ -9,7 +9,7 @@ namespace {
 size_t prove_item_len(const Params &P, uint32_t m);
 void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_prove_item *items, uint32_t B, size_t plen, uint8_t *&proofs,
                       uint32_t *&status, const bpp_ctx::CheckTamper &tamper, bool remake, std::vector<uint8_t> &kept_proofs,
-                      std::vector<uint32_t> &kept_status, uint8_t *made32, size_t made_stride);
+                      std::vector<uint32_t> &kept_status, uint8_t *made32, size_t made_stride, uint8_t *tstates203);
 // what follows "proof %u failed the engine's self-check: " / "the proof failed the engine's self-check: "
 const char *const kSelfCheckRejectedWhy = "the verifier rejected it and its remake";
 const char *const kSelfCheckRecoveryWhy =
@@ -33,9 +33,14 @@ const char *const kSelfCheckRecoveryWhy =
 // for EVERY item of the call comes back at made32 + i * 32 * items[0].m: for an item whose status word is 0 those are its
 // statement's commitments, made or brought.  A sub-batch without such an item -- every call with made32 == nullptr -- is enqueued
 // exactly as before.
+// states203 != nullptr (bpp_prove_*_states): kp_finish's other instantiation also writes every proof's transcript as
+// challenge_final_e leaves it; row i of states203 (203 bytes, call order) is written for every item whose status word ends as 0 --
+// after the self-check, whose remake of a proof brings its own row -- and left alone for every other item.  A call without it
+// carves, enqueues and copies exactly what it did.
 int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
                   size_t proof_stride, size_t *proof_len, char *errbuf, size_t errbuf_len, uint32_t *dev_status, bool mixed = false,
-                  const bpp_ctx::CheckTamper &tamper = bpp_ctx::CheckTamper{}, bool remake = true, uint8_t *made32 = nullptr) {
+                  const bpp_ctx::CheckTamper &tamper = bpp_ctx::CheckTamper{}, bool remake = true, uint8_t *made32 = nullptr,
+                  uint8_t *states203 = nullptr) {
   try {
     const std::shared_ptr<Params> Pp = params_registry().get(params);
     if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
@@ -308,6 +313,7 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
       uint32_t lo, nb;
       size_t bytes_lo, bytes_len, arena_lo, arena_len;
       uint8_t *d_bytes, *d_states, *d_minpres, *d_a32, *d_lr, *d_a1b, *d_proofs, *d_commit32;
+      uint32_t *d_tstates;  // the advanced transcripts, rows of BPP_STATE_ROW_WORDS words (states203 only)
       ProveDesc *d_desc;
       uint64_t *d_minvals;
       ProveState *d_ps;
@@ -372,6 +378,7 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
         u.d_expts = (ge *)take(ct ? (size_t)ex_nt * nb * sizeof(ge) : 16);
         u.d_pow = (ge *)take(ct ? (size_t)ex_nt * nb * BPP_CT_DIGITS * sizeof(ge) : 16);
         u.d_ctprod = (ge *)take(ct ? (size_t)ex_nt * nb * sizeof(ge) : 16);
+        u.d_tstates = states203 ? (uint32_t *)take(nb * BPP_STATE_ROW_WORDS * 4) : nullptr;  // (last, and only when asked for: the arena of every other call is laid out as before)
         u.arena_len = arena_need - u.arena_lo;
       }
     };
@@ -409,7 +416,8 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
     const size_t in_need = bytes.size() + states.size() + minpres.size() + minvals.size() * 8 + (size_t)B * sizeof(ProveDesc) + 64;
     ctx->prove_pin_in.resize(in_need);
     // (on the way out: proofs, status words and -- made32 -- the commitments the witness check computed: nothing secret)
-    ctx->prove_pin_out.resize((size_t)B * plen + (size_t)B * sizeof(uint32_t) + 64 + (made32 ? (size_t)B * m * 32 : 0));
+    ctx->prove_pin_out.resize((size_t)B * plen + (size_t)B * sizeof(uint32_t) + 64 + (made32 ? (size_t)B * m * 32 : 0) +
+                              (states203 ? (size_t)B * BPP_STATE_ROW_WORDS * 4 + 16 : 0));
     uint8_t *pin = ctx->prove_pin_in.p;
     uint8_t *pin_bytes = pin;
     memcpy(pin_bytes, bytes.data(), bytes.size());
@@ -424,6 +432,7 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
     uint8_t *pin_proofs = ctx->prove_pin_out.p;
     uint32_t *pin_status = (uint32_t *)(pin_proofs + (((size_t)B * plen + 15) & ~(size_t)15));
     uint8_t *pin_made = (uint8_t *)pin_status + (((size_t)B * sizeof(uint32_t) + 15) & ~(size_t)15);
+    uint32_t *pin_tstates = (uint32_t *)(pin_made + (made32 ? (((size_t)B * m * 32 + 15) & ~(size_t)15) : 0));  // (public data)
 
     const dim3 b64(64);
     // profiling: an event pair around every k_fb_msm launch (the prover's dominant kernel), summed after the call
@@ -574,9 +583,16 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
       Sub &u = subs[q];
       hipStream_t s = lane_stream(q);
       const uint32_t nb = u.nb;
-      hipLaunchKernelGGL(kp_finish, dim3(nb), b64, 0, s, u.d_desc, n, t, nb, rounds, u.d_a32, u.d_lr, u.d_a1b, u.d_vec, u.d_ps,
-                         u.d_proofs, (uint32_t)plen);
+      if (states203)
+        hipLaunchKernelGGL(kp_finish<true>, dim3(nb), b64, 0, s, u.d_desc, n, t, nb, rounds, u.d_a32, u.d_lr, u.d_a1b, u.d_vec, u.d_ps,
+                           u.d_proofs, (uint32_t)plen, u.d_tstates);
+      else
+        hipLaunchKernelGGL(kp_finish<false>, dim3(nb), b64, 0, s, u.d_desc, n, t, nb, rounds, u.d_a32, u.d_lr, u.d_a1b, u.d_vec, u.d_ps,
+                           u.d_proofs, (uint32_t)plen, (uint32_t *)nullptr);
       HIP_CHECK(hipGetLastError());
+      if (states203)
+        HIP_CHECK(hipMemcpyAsync(pin_tstates + (size_t)u.lo * BPP_STATE_ROW_WORDS, u.d_tstates, (size_t)nb * BPP_STATE_ROW_WORDS * 4,
+                                 hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipMemcpyAsync(pin_proofs + (size_t)u.lo * plen, u.d_proofs, (size_t)nb * plen, hipMemcpyDeviceToHost, s));
       // only the status word of each (secret-bearing) ProveState leaves the device
       HIP_CHECK(hipMemcpy2DAsync(pin_status + u.lo, sizeof(uint32_t), &u.d_ps[0].status, sizeof(ProveState), sizeof(uint32_t), nb,
@@ -630,11 +646,15 @@ int prove_uniform(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, si
     }
     // (out of the staging before the self-check, whose remakes reuse it)
     if (made32) memcpy(made32, pin_made, (size_t)B * m * 32);
+    std::vector<uint8_t> tstates(states203 ? (size_t)B * 203 : 0);
+    for (uint32_t i = 0; states203 && i < B; i++) state_row_to_bytes(&tstates[(size_t)i * 203], pin_tstates + (size_t)i * BPP_STATE_ROW_WORDS);
     std::vector<uint8_t> kept_proofs;  // (where the proofs and status words move when a remake needs the staging)
     std::vector<uint32_t> kept_status;
     if (ctx->opt.prove_check > 0)
       prove_self_check(ctx, params, P, items, B, plen, pin_proofs, pin_status, tamper, remake, kept_proofs, kept_status, made32,
-                       (size_t)m * 32);
+                       (size_t)m * 32, states203 ? tstates.data() : nullptr);
+    for (uint32_t i = 0; states203 && i < B; i++)
+      if (pin_status[i] == 0) memcpy(states203 + (size_t)i * 203, &tstates[(size_t)i * 203], 203);
     if (dev_status) {
       memcpy(dev_status, pin_status, (size_t)B * sizeof(uint32_t));
     } else {
@@ -785,7 +805,9 @@ int check_verify(bpp_ctx *ctx, uint64_t params, const std::vector<bpp_verify_ite
 // brought none is checked against those -- the checking batch never sees a NULL statement -- and its remake makes them again.
 void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_prove_item *items, uint32_t B, size_t plen, uint8_t *&proofs,
                       uint32_t *&status, const bpp_ctx::CheckTamper &tamper, bool remake, std::vector<uint8_t> &kept_proofs,
-                      std::vector<uint32_t> &kept_status, uint8_t *made32, size_t made_stride) {
+                      std::vector<uint32_t> &kept_status, uint8_t *made32, size_t made_stride, uint8_t *tstates203) {
+  // (tstates203, else nullptr: the call's advanced transcripts, 203 bytes per item; a remake that passes brings the row of the
+  // proof that replaces the first one)
   std::vector<uint32_t> which;  // the items the device made a proof for
   for (uint32_t i = 0; i < B; i++)
     if (status[i] == 0) which.push_back(i);
@@ -919,7 +941,7 @@ void prove_self_check(bpp_ctx *ctx, uint64_t params, const Params &P, const bpp_
     ctx->check_stats.remade++;
     std::vector<uint8_t> made_one((size_t)32 * items[i].m, 0);
     const int rc = prove_uniform(ctx, params, &items[i], 1, one.data(), len, &got, err, sizeof(err), &st, false, again, false,
-                                 made32 ? made_one.data() : nullptr);
+                                 made32 ? made_one.data() : nullptr, tstates203 ? tstates203 + (size_t)i * 203 : nullptr);
     if (rc != BPP_OK) throw ProofErr{rc, err, rc < 0 ? BPP_TIER_ENGINE : BPP_TIER_CONSTRUCTION};
     if (st != 0 || got != len) {  // (which of the two the remake failed on: its own check says)
       status[i] |= PV_STATUS_SELF_CHECK | (st & PV_STATUS_SELF_CHECK_RECOVERY);
@@ -974,7 +996,8 @@ void prove_item_check(const Params &P, const bpp_prove_item &it, size_t proof_st
 // (*commit_caps)[i] bytes; an item with a null slot is one of the existing entry points (a pooled call may hold both kinds).
 void prove_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out, size_t proof_stride,
                  size_t *proof_lens, MixedOutcome &out, const std::vector<uint8_t *> *commit_slots = nullptr,
-                 const std::vector<size_t> *commit_caps = nullptr) {
+                 const std::vector<size_t> *commit_caps = nullptr, uint8_t *states_out203 = nullptr) {
+  // states_out203 (bpp_prove_*_states, else nullptr): row i receives item i's advanced transcript when the item succeeds
   const std::shared_ptr<Params> Pp = params_registry().get(params);
   if (!Pp || Pp->device != ctx->device) throw ProofErr{BPP_ERR_BAD_HANDLE, "unknown params handle"};
   const Params &P = *Pp;
@@ -1022,8 +1045,9 @@ void prove_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, siz
   char err[256];
   err[0] = 0;
   size_t len = 0;
+  std::vector<uint8_t> tstates(states_out203 ? idx.size() * 203 : 0);
   const int rc = prove_uniform(ctx, params, sub.data(), sub.size(), buf.data(), plen, &len, err, sizeof(err), status.data(), true, tamper,
-                               true, any_openings ? made.data() : nullptr);
+                               true, any_openings ? made.data() : nullptr, states_out203 ? tstates.data() : nullptr);
   {
     for (size_t k = 0; k < idx.size(); k++) {
       const uint32_t i = idx[k];
@@ -1048,6 +1072,7 @@ void prove_mixed(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, siz
         memcpy(proofs_out + (size_t)i * proof_stride, &buf[k * plen], proof_lens[i]);
         // (status 0: what the check computed IS what the item brought, where it brought any)
         if (slot(i)) memcpy(slot(i), &made[k * made_stride], (size_t)32 * items[i].m);
+        if (states_out203) memcpy(states_out203 + (size_t)i * 203, &tstates[k * 203], 203);
       }
     }
   }
@@ -1075,6 +1100,23 @@ extern "C" int bpp_prove_batch_mixed(bpp_ctx *ctx, uint64_t params, const bpp_pr
   BPP_CATCH(ctx, errbuf, errbuf_len)
 }
 
+extern "C" int bpp_prove_batch_mixed_states(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
+                                            size_t proof_stride, size_t *proof_lens, int *item_status, uint8_t *states_out203,
+                                            char *errbuf, size_t errbuf_len) {
+  BPP_ENTRY(ctx);
+  try {
+    if (!states_out203) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
+    MixedOutcome out;
+    prove_mixed(ctx, params, items, n_items, proofs_out, proof_stride, proof_lens, out, nullptr, nullptr, states_out203);
+    if (item_status) memcpy(item_status, out.code.data(), n_items * sizeof(int));
+    for (size_t i = 0; i < n_items; i++)
+      if (out.code[i] != BPP_OK) return fail(ctx, out.code[i], out.msg[i], errbuf, errbuf_len);
+    set_err(errbuf, errbuf_len, "");
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, errbuf, errbuf_len)
+}
+
 // bpp_prove_openings: bpp_prove_batch_mixed whose items may come as openings alone.  An item with commitments32 == NULL has its
 // commitments made by the engine -- the witness check computes commit(v_j, r_j) for every opening anyway -- and they are its
 // statement's for the transcript, the proof and the self-check; an item that brings commitments is checked against them as ever.
@@ -1090,6 +1132,26 @@ extern "C" int bpp_prove_openings(bpp_ctx *ctx, uint64_t params, const bpp_prove
     const std::vector<size_t> caps(n_items, commit_stride);
     MixedOutcome out;
     prove_mixed(ctx, params, items, n_items, proofs_out, proof_stride, proof_lens, out, &slots, &caps);
+    if (item_status) memcpy(item_status, out.code.data(), n_items * sizeof(int));
+    for (size_t i = 0; i < n_items; i++)
+      if (out.code[i] != BPP_OK) return fail(ctx, out.code[i], out.msg[i], errbuf, errbuf_len);
+    set_err(errbuf, errbuf_len, "");
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, errbuf, errbuf_len)
+}
+
+extern "C" int bpp_prove_openings_states(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *commitments_out,
+                                         size_t commit_stride, uint8_t *proofs_out, size_t proof_stride, size_t *proof_lens,
+                                         int *item_status, uint8_t *states_out203, char *errbuf, size_t errbuf_len) {
+  BPP_ENTRY(ctx);
+  try {
+    if (!commitments_out || !states_out203) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
+    std::vector<uint8_t *> slots(n_items);
+    for (size_t i = 0; i < n_items; i++) slots[i] = commitments_out + i * commit_stride;
+    const std::vector<size_t> caps(n_items, commit_stride);
+    MixedOutcome out;
+    prove_mixed(ctx, params, items, n_items, proofs_out, proof_stride, proof_lens, out, &slots, &caps, states_out203);
     if (item_status) memcpy(item_status, out.code.data(), n_items * sizeof(int));
     for (size_t i = 0; i < n_items; i++)
       if (out.code[i] != BPP_OK) return fail(ctx, out.code[i], out.msg[i], errbuf, errbuf_len);

@@ -1343,11 +1343,16 @@ __global__ void __launch_bounds__(64 * W) kp_round(const uint8_t *__restrict__ b
 
 // ---- final lane kernel: challenge_final_e, responses, wire bytes (:587-607, to_bytes :1120-1150) ----
 // proof layout: [t] d1[t] A A1 B r1 s1 (L_j R_j)...
+// STATES (bpp_prove_*_states): the transcript as challenge_final_e leaves it (src/transcripts.rs:152-161) goes out as the row of
+// 52 words the verifier's kernels write (kernels_verify.h: 50 state words, pos | pos_begin << 8 | cur_flags << 16, a zero word),
+// one word per lane.  The prover appends neither r1, s1 nor d1: this is not the state a verifier of the same proof ends with.
+template <bool STATES>
 __global__ void __launch_bounds__(64) kp_finish(const ProveDesc *__restrict__ desc, uint32_t n_bits, uint32_t t, uint32_t B,
                                                 uint32_t rounds, const uint8_t *__restrict__ a32,
                                                 const uint8_t *__restrict__ lr_all /* [rounds][B][2][32] */,
                                                 const uint8_t *__restrict__ a1b32 /* [B][2][32] */, const sc *__restrict__ vec,
-                                                ProveState *__restrict__ ps, uint8_t *__restrict__ proofs, uint32_t proof_stride) {
+                                                ProveState *__restrict__ ps, uint8_t *__restrict__ proofs, uint32_t proof_stride,
+                                                uint32_t *__restrict__ states_out) {
   // one wavefront per proof (round 4; before: one lane per proof on the one-lane sponge, three Keccak-f of ~26 us each on the
   // call's last stretch with nothing beside them): the transcript's last three operations on the cooperative sponge of the
   // Fiat-Shamir steps, then lane k < t makes d1_k, lanes t and t + 1 make r1 and s1, and the wire bytes are written by all lanes
@@ -1365,6 +1370,10 @@ __global__ void __launch_bounds__(64) kp_finish(const ProveDesc *__restrict__ de
   ok = pw_validate_append(tr, K, "B", 1, pa1 + 32) && ok;
   sc e;
   ok = pw_challenge(tr, L, K, "e", 1, e) && ok;
+  if constexpr (STATES) {  // (the squeeze ended with a barrier: L.tr is whole; public bytes, written before the LDS is wiped)
+    const uint32_t meta = tr.pos | (tr.pos_begin << 8) | (tr.cur_flags << 16);
+    if (lane < 52u) states_out[(size_t)p * 52u + lane] = lane < 50u ? reinterpret_cast<const uint32_t *>(L.tr)[lane] : (lane == 50u ? meta : 0u);
+  }
   uint8_t *o = proofs + (size_t)p * proof_stride;
   // wire format (src/range_proof.rs:1120-1150): [t] d1[t] A A1 B r1 s1 (L_j R_j)_j
   if (lane < t + 2) {

@@ -48,13 +48,21 @@ __device__ __forceinline__ bool lm_challenge_scalar(LStrobe &s, uint64_t label, 
   sc_mont_from_wide_words(out, w);
   return !sc_iszero(out);
 }
+// STATES (bpp_verify_*_states): every proof's transcript as to_verifier_rng leaves it (src/transcripts.rs:166-172: r1, s1 and every d1
+// appended, build_rng not yet run -- that works on a clone) goes out as one row of BPP_STATE_ROW_WORDS words: the 50 state words,
+// then pos | pos_begin << 8 | cur_flags << 16, then a zero word.  Rows lie back to back, 208 bytes each, so the 64 rows of a
+// wavefront are 13 KB of whole 64-byte lines.  The default instantiation holds none of this: same code, registers and LDS as before.
+#define BPP_STATE_ROW_WORDS 52u
+template <bool STATES>
 __global__ void __launch_bounds__(64, BPP_TRANSCRIPTS_WAVES) k_transcripts(const uint8_t *__restrict__ bytes, const ProofDesc *__restrict__ desc,
                                                     const uint64_t *__restrict__ minvals,
                                                     const uint8_t *__restrict__ states, const uint8_t *__restrict__ hg32,
                                                     uint32_t n_bits, uint32_t t, uint32_t B, uint32_t cs,
                                                     sc *__restrict__ chal, uint8_t *__restrict__ rng_out,
-                                                    uint32_t *__restrict__ status, uint8_t *__restrict__ rng_host) {
-  __shared__ uint32_t sponge[BPP_LS_WORDS * BPP_LS_STRIDE];  // word w of lane l at [w * 64 + l] (lstrobe.h)
+                                                    uint32_t *__restrict__ status, uint8_t *__restrict__ rng_host,
+                                                    uint32_t *__restrict__ states_out) {
+  // word w of lane l at [w * 64 + l] (lstrobe.h); STATES: two more words per lane, the room of 64 rows of BPP_STATE_ROW_WORDS
+  __shared__ uint32_t sponge[(STATES ? BPP_STATE_ROW_WORDS : BPP_LS_WORDS) * BPP_LS_STRIDE];
   uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
   // The lanes past the end of the input replay the LAST proof once more (the same values to the same places) instead of
   // leaving: the host's copy at the end is stored by lane q for piece q of the wavefront's rows, so with B % 64 != 0 the
@@ -106,6 +114,34 @@ __global__ void __launch_bounds__(64, BPP_TRANSCRIPTS_WAVES) k_transcripts(const
   lm_append_mem(s, lm_label("r1", 2), 2, pr1, 32);
   lm_append_mem(s, lm_label("s1", 2), 2, ps1, 32);
   for (uint32_t k = 0; k < t; k++) lm_append_mem(s, lm_label("d1", 2), 2, pd1 + 32 * k, 32);
+  if constexpr (STATES) {
+    // The finalize below keys the sponge in place, so the state leaves now.  A lane's 50 words are 256 bytes apart in LDS (word-
+    // major) and its row in memory is 208 bytes: stored by the lane itself it would cross the bus as 64 x 13 partial pieces.  As
+    // for rng_host below, the wavefront's rows are turned row-major inside the sponge's own LDS -- out through registers, back in
+    // as rows -- and leave as 13 stores of 1 KB each, lane q with piece q; then the words go back where the sponge keeps them.
+    // The lanes past the end (they replay the last proof) take part in the exchange and store nothing: `live` ends at row B - 1.
+    uint32_t w[BPP_LS_WORDS];
+#pragma unroll
+    for (uint32_t i = 0; i < BPP_LS_WORDS; i++) w[i] = s.st[i * BPP_LS_STRIDE];
+    ws_sync();
+    uint32_t *row = sponge + threadIdx.x * BPP_STATE_ROW_WORDS;
+#pragma unroll
+    for (uint32_t i = 0; i < BPP_LS_WORDS; i++) row[i] = w[i];
+    row[BPP_LS_WORDS] = s.pos | (s.pos_begin << 8) | (BPP_FLAG_A << 16);  // (the last operation was the AD of an append_message)
+    row[BPP_LS_WORDS + 1] = 0;
+    ws_sync();
+    const uint32_t p0 = blockIdx.x * blockDim.x, live = min(B - p0, 64u) * (BPP_STATE_ROW_WORDS / 4u);  // 16-byte pieces of this wavefront's rows
+#pragma unroll 1
+    for (uint32_t k = 0; k < BPP_STATE_ROW_WORDS / 4u; k++) {
+      const uint32_t q = k * 64u + threadIdx.x;
+      if (q < live)
+        reinterpret_cast<uint4 *>(states_out)[(size_t)p0 * (BPP_STATE_ROW_WORDS / 4u) + q] = *reinterpret_cast<const uint4 *>(&sponge[q * 4u]);
+    }
+    ws_sync();
+#pragma unroll
+    for (uint32_t i = 0; i < BPP_LS_WORDS; i++) s.st[i * BPP_LS_STRIDE] = w[i];
+    ws_sync();
+  }
   lm_rng_finalize_zero(s);
   uint32_t out[8];
   lm_rng_fill32(s, out);
@@ -153,12 +189,14 @@ __device__ __forceinline__ bool wave_challenge(WStrobe &s, TranscriptLds &L, con
 __device__ __forceinline__ bool wave_nonzero32(const uint8_t *p32) {
   return __ballot(threadIdx.x < 32 && p32[threadIdx.x & 31u] != 0) != 0;
 }
+template <bool STATES>  // (the same rows as k_transcripts<true> writes)
 __global__ void __launch_bounds__(64) k_transcripts_wave(const uint8_t *__restrict__ bytes, const ProofDesc *__restrict__ desc,
                                                          const uint64_t *__restrict__ minvals,
                                                          const uint8_t *__restrict__ states, const uint8_t *__restrict__ hg32,
                                                          uint32_t n_bits, uint32_t t, uint32_t B, uint32_t cs,
                                                          sc *__restrict__ chal, uint8_t *__restrict__ rng_out,
-                                                         uint32_t *__restrict__ status, uint8_t *__restrict__ rng_host) {
+                                                         uint32_t *__restrict__ status, uint8_t *__restrict__ rng_host,
+                                                         uint32_t *__restrict__ states_out) {
   const uint32_t p = blockIdx.x, lane = threadIdx.x;
   if (p >= B) return;
   __shared__ TranscriptLds L;
@@ -211,6 +249,14 @@ __global__ void __launch_bounds__(64) k_transcripts_wave(const uint8_t *__restri
   wm_append_message(s, K, "r1", 2, BytesAt{pr1}, 32);
   wm_append_message(s, K, "s1", 2, BytesAt{ps1}, 32);
   for (uint32_t k = 0; k < t; k++) wm_append_message(s, K, "d1", 2, BytesAt{pd1 + 32 * k}, 32);
+  if constexpr (STATES) {  // the proof's row, one word per lane: 208 contiguous bytes, before the finalize keys the state in place
+    ws_sync();
+    const uint32_t meta = s.pos | (s.pos_begin << 8) | (s.cur_flags << 16);
+    if (lane < BPP_STATE_ROW_WORDS)
+      states_out[(size_t)p * BPP_STATE_ROW_WORDS + lane] =
+          lane < BPP_LS_WORDS ? reinterpret_cast<const uint32_t *>(L.st)[lane] : (lane == BPP_LS_WORDS ? meta : 0u);
+    ws_sync();
+  }
   wm_rng_finalize(s, K, ZeroAt{});
   wm_rng_fill(s, K, L.buf, 32);
   if (lane < 32) rng_out[(size_t)p * 32 + lane] = L.buf[lane];

@@ -129,13 +129,20 @@ class PackedInput:
                                        ptr(self.seed_present), ptr(self.state), ptr(self.label), len(label))
 
 
-def verify_batch(params, inp, action=api.VerifyAction.VerifyOnly, chunk=api.MAX_RANGE_PROOF_BATCH_SIZE):
+def verify_batch(params, inp, action=api.VerifyAction.VerifyOnly, chunk=api.MAX_RANGE_PROOF_BATCH_SIZE, states=False):
     """RangeProof::verify_batch over a PackedInput in ONE C call (bpp_verify_batch_packed: upload, verify, release).
-    Returns (masks uint8 [n, t, 32], present uint8 [n])."""
+    Returns (masks uint8 [n, t, 32], present uint8 [n]); with states=True (bpp_verify_batch_packed_states) a third array,
+    uint8 [n, 203]: every proof's transcript as the verifier left it."""
     eng, t = params.engine, int(params.extension_degree())
     masks = np.zeros((inp.n, t, 32), dtype=np.uint8)
     present = np.zeros(inp.n, dtype=np.uint8)
     err = ctypes.create_string_buffer(256)
+    if states:
+        st = np.zeros((inp.n, 203), dtype=np.uint8)
+        rc = eng.lib.bpp_verify_batch_packed_states(eng.ctx, params.handle, byref(inp.struct), int(action), chunk, masks.ctypes.data,
+                                                    present.ctypes.data, st.ctypes.data, err, 256)
+        api._check(rc, eng.ctx, err)
+        return masks, present, st
     rc = eng.lib.bpp_verify_batch_packed(eng.ctx, params.handle, byref(inp.struct), int(action), chunk, masks.ctypes.data,
                                          present.ctypes.data, err, 256)
     api._check(rc, eng.ctx, err)

@@ -701,6 +701,44 @@ int bpp_prove_secret_bytes(bpp_ctx *ctx, uint64_t *examined, uint64_t *nonzero);
 /* Transcript::new(label) -> 203-byte STROBE state (host helper for callers that keep merlin on their side) */
 int bpp_transcript_new(const uint8_t *label, size_t label_len, uint8_t state203[203]);
 
+/* Transcript::append_message / Transcript::challenge_bytes on a 203-byte state, IN PLACE (host only, no device, no context): what a
+ * caller without a merlin of its own needs to bind context before a call and to go on with the transcript a *_states call handed
+ * back.  A state with pos (byte 200) >= 166, the STROBE rate, is refused with BPP_ERR_INVALID_ARGUMENT, as the upload refuses it. */
+int bpp_transcript_append_message(uint8_t state203[203], const uint8_t *label, size_t label_len, const uint8_t *msg, size_t msg_len);
+int bpp_transcript_challenge_bytes(uint8_t state203[203], const uint8_t *label, size_t label_len, uint8_t *out, size_t out_len);
+
+/* ---- Advanced transcripts: `&mut Transcript` on the device paths ----
+ * The reference's prove_with_rng and verify_batch take `&mut Transcript` (src/range_proof.rs:222-237, :712-717, :757) and leave
+ * it advanced by everything the proof appended and drew, so that the caller can go on with it.  The calls below are the named
+ * existing calls plus states_out203, n_items x 203 packed bytes (st[200], pos, pos_begin, cur_flags: bpp_transcript_new's form),
+ * which must not be NULL; everything else they do and return is what the call without the buffer does and returns.
+ *   verifier: row i = proof i's transcript after to_verifier_rng has appended r1, s1 and every d1 (src/transcripts.rs:166-172) and
+ *             before build_rng, which works on a clone.  It depends on the proof, its statement and the transcript that came in --
+ *             not on the VerifyAction, on `chunk`, on the kernel forms or on whether the transcript came as a label or as a state.
+ *   prover:   row i = item i's transcript after the challenge_scalar(b"e") of challenge_final_e (src/transcripts.rs:152-161).  The
+ *             prover never appends r1, s1, d1: its final state and a verifier's for the same proof differ, as in the reference.
+ *             Under "prove_check" = 1 the row belongs to the proof that is returned (a remade proof has the same bytes and state).
+ *   failures: NARROWER than the reference, which leaves a transcript partly advanced when it returns an error.  A verify call that
+ *             returns anything but BPP_OK writes NOTHING to states_out203.  A prove item whose status is not 0 -- BPP_ERR_SELF_CHECK
+ *             included -- leaves its own row untouched while the other items' rows are written.
+ * The rows leave the device through page-locked memory (written by PASS 1 itself / copied behind the prover's last kernel); they
+ * are public data.  The calls without the buffer run the kernels' default instantiations and allocate nothing for this.
+ * A batch uploaded by bpp_verify_batch_with_challenges' path has no device-side transcript: BPP_ERR_INVALID_ARGUMENT.
+ * NOT covered (they hand nothing back, as before): bpp_verify_submit_packed / bpp_verify_collect, bpp_batcher, bpp_prove_pool,
+ * bpp_prove_submit / bpp_prove_collect, the sharded forms, the grouped resident forms, and bpp_prove_batch (all-or-nothing). */
+int bpp_verify_batch_states(bpp_ctx *ctx, uint64_t params, const bpp_verify_item *items, size_t n_items, int action, size_t chunk,
+                            uint8_t *masks_out, uint8_t *mask_present, uint8_t *states_out203, char *errbuf, size_t errbuf_len);
+int bpp_verify_batch_packed_states(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, int action, size_t chunk,
+                                   uint8_t *masks_out, uint8_t *mask_present, uint8_t *states_out203, char *errbuf, size_t errbuf_len);
+int bpp_verify_resident_states(bpp_ctx *ctx, uint64_t batch, int action, size_t chunk, uint8_t *masks_out, uint8_t *mask_present,
+                               uint8_t *states_out203, char *errbuf, size_t errbuf_len);
+int bpp_prove_batch_mixed_states(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out,
+                                 size_t proof_stride, size_t *proof_lens, int *item_status, uint8_t *states_out203, char *errbuf,
+                                 size_t errbuf_len);
+int bpp_prove_openings_states(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items, size_t n_items, uint8_t *commitments_out,
+                              size_t commit_stride, uint8_t *proofs_out, size_t proof_stride, size_t *proof_lens, int *item_status,
+                              uint8_t *states_out203, char *errbuf, size_t errbuf_len);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,8 @@
 //   RangeProof::{prove_with_rng, verify_batch, to_bytes, from_bytes}   same (src/range_proof.rs:232,712,1120,1155)
 //   VerifyAction, ExtendedMask, ProofError{VerificationFailed,...}     same (ProofError is an exception)
 //   merlin::Transcript::new(label)                               Transcript::create(label)
+//   Transcript::{append_message, append_u64, challenge_bytes}    same (on the 203-byte state, host only)
+//   `&mut Transcript` of prove_with_rng / verify_batch           the overloads that take the transcript(s) by pointer
 //
 // Scalars and points are 32-byte arrays (canonical little-endian scalar / ristretto255 encoding).
 #pragma once
@@ -22,6 +24,7 @@
 #include <optional>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -147,7 +150,39 @@ class Transcript {
   const std::string &label() const { return label_; }
   const std::vector<uint8_t> &state() const { return state_; }
 
+  // merlin's own operations, on the 203-byte state (host only: bpp_transcript_append_message / bpp_transcript_challenge_bytes).  A
+  // label-only transcript becomes a state-carrying one first.
+  void append_message(const std::string &label, const uint8_t *message, size_t len) {
+    materialise();
+    check(bpp_transcript_append_message(state_.data(), reinterpret_cast<const uint8_t *>(label.data()), label.size(), message, len),
+          "transcript state has pos >= rate");
+  }
+  void append_message(const std::string &label, const std::vector<uint8_t> &message) { append_message(label, message.data(), message.size()); }
+  void append_u64(const std::string &label, uint64_t x) {
+    uint8_t b[8];
+    for (int k = 0; k < 8; k++) b[k] = static_cast<uint8_t>(x >> (8 * k));
+    append_message(label, b, 8);
+  }
+  std::vector<uint8_t> challenge_bytes(const std::string &label, size_t n) {
+    materialise();
+    std::vector<uint8_t> out(n);
+    check(bpp_transcript_challenge_bytes(state_.data(), reinterpret_cast<const uint8_t *>(label.data()), label.size(), out.data(), n),
+          "transcript state has pos >= rate");
+    return out;
+  }
+  // what an advancing call (RangeProof::verify_batch / prove_batch / prove_with_rng with a transcript POINTER) leaves behind
+  void advance_to(const uint8_t state203[203]) {
+    state_.assign(state203, state203 + 203);
+    label_.clear();
+  }
+
  private:
+  void materialise() {
+    if (!state_.empty()) return;
+    state_.resize(203);
+    check(bpp_transcript_new(reinterpret_cast<const uint8_t *>(label_.data()), label_.size(), state_.data()), "bpp_transcript_new");
+    label_.clear();
+  }
   std::string label_;
   std::vector<uint8_t> state_;
 };
@@ -268,6 +303,36 @@ class RangeProof {
   // n x prove_with_rng in one engine call; rng_bytes[i] = (rounds + 3) x 32 bytes from the caller's RNG
   static std::vector<RangeProof> prove_batch(const std::vector<Transcript> &transcripts, const std::vector<RangeStatement> &statements,
                                              const std::vector<RangeWitness> &witnesses, const std::vector<std::vector<uint8_t>> &rng_bytes) {
+    return prove_batch_impl(transcripts, statements, witnesses, rng_bytes, nullptr);
+  }
+  // The reference's `&mut Transcript` (src/range_proof.rs:222-237): the forms that take their transcripts by POINTER advance them --
+  // on success every transcript is left as the prover left it (after the last challenge), on an error all are untouched.  A pointer
+  // and not a non-const reference: callers of the const forms above hold ordinary, non-const objects, and an overload on constness
+  // would silently start advancing theirs.  (A template, so that a braced `{}` for the transcripts still means the const form's empty
+  // vector and never a null pointer.)  One call of bpp_prove_batch_mixed_states; throws the first failing item's error.
+  template <class T, class = std::enable_if_t<std::is_same<T, Transcript>::value>>
+  static std::vector<RangeProof> prove_batch(std::vector<T> *transcripts, const std::vector<RangeStatement> &statements,
+                                             const std::vector<RangeWitness> &witnesses, const std::vector<std::vector<uint8_t>> &rng_bytes) {
+    if (!transcripts) throw ProofError(ProofErrorKind::InvalidArgument, "null transcripts");
+    std::vector<uint8_t> states;
+    auto proofs = prove_batch_impl(*transcripts, statements, witnesses, rng_bytes, &states);
+    for (size_t i = 0; i < transcripts->size(); i++) (*transcripts)[i].advance_to(&states[203 * i]);
+    return proofs;
+  }
+  static RangeProof prove_with_rng(Transcript *transcript, const RangeStatement &statement, const RangeWitness &witness,
+                                   const std::vector<uint8_t> &rng_bytes) {
+    if (!transcript) throw ProofError(ProofErrorKind::InvalidArgument, "null transcript");
+    std::vector<uint8_t> states;
+    auto proofs = prove_batch_impl({*transcript}, {statement}, {witness}, {rng_bytes}, &states);
+    transcript->advance_to(states.data());
+    return proofs[0];
+  }
+
+ private:
+  // states != nullptr: bpp_prove_batch_mixed_states, 203 bytes per item into *states
+  static std::vector<RangeProof> prove_batch_impl(const std::vector<Transcript> &transcripts, const std::vector<RangeStatement> &statements,
+                                                  const std::vector<RangeWitness> &witnesses, const std::vector<std::vector<uint8_t>> &rng_bytes,
+                                                  std::vector<uint8_t> *states) {
     const size_t n = statements.size();
     if (n == 0 || witnesses.size() != n || transcripts.size() != n || rng_bytes.size() != n)
       throw ProofError(ProofErrorKind::InvalidArgument, "Range statements, witnesses, transcripts length mismatch");
@@ -306,11 +371,21 @@ class RangeProof {
     std::vector<uint8_t> out(stride * n);
     size_t plen = 0;
     char err[256] = {0};
-    check(bpp_prove_batch(params.engine().ctx(), params.handle(), items.data(), n, out.data(), stride, &plen, err, sizeof(err)), err);
     std::vector<RangeProof> proofs;
+    if (states) {
+      states->assign(203 * n, 0);
+      std::vector<size_t> lens(n, 0);
+      check(bpp_prove_batch_mixed_states(params.engine().ctx(), params.handle(), items.data(), n, out.data(), stride, lens.data(), nullptr,
+                                         states->data(), err, sizeof(err)), err);
+      for (size_t i = 0; i < n; i++) proofs.push_back(from_bytes(std::vector<uint8_t>(out.begin() + i * stride, out.begin() + i * stride + lens[i])));
+      return proofs;
+    }
+    check(bpp_prove_batch(params.engine().ctx(), params.handle(), items.data(), n, out.data(), stride, &plen, err, sizeof(err)), err);
     for (size_t i = 0; i < n; i++) proofs.push_back(from_bytes(std::vector<uint8_t>(out.begin() + i * stride, out.begin() + i * stride + plen)));
     return proofs;
   }
+
+ public:
   static RangeProof prove_with_rng(const Transcript &transcript, const RangeStatement &statement, const RangeWitness &witness,
                                    const std::vector<uint8_t> &rng_bytes) {
     return prove_batch({transcript}, {statement}, {witness}, {rng_bytes})[0];
@@ -378,6 +453,27 @@ class RangeProof {
                                                                 const std::vector<RangeStatement> &statements,
                                                                 const std::vector<RangeProof> &proofs, VerifyAction action,
                                                                 size_t chunk = BPP_REFERENCE_CHUNK) {
+    return verify_batch_impl(transcripts, statements, proofs, action, chunk, nullptr);
+  }
+  // `&mut [Transcript]` (src/range_proof.rs:712-717): with the transcripts by POINTER (see prove_batch) a call that succeeds leaves
+  // every transcript as the verifier left it -- r1, s1 and every d1 appended (src/transcripts.rs:166-172); an error leaves all untouched
+  template <class T, class = std::enable_if_t<std::is_same<T, Transcript>::value>>
+  static std::vector<std::optional<ExtendedMask>> verify_batch(std::vector<T> *transcripts,
+                                                                const std::vector<RangeStatement> &statements,
+                                                                const std::vector<RangeProof> &proofs, VerifyAction action,
+                                                                size_t chunk = BPP_REFERENCE_CHUNK) {
+    if (!transcripts) throw ProofError(ProofErrorKind::InvalidArgument, "null transcripts");
+    std::vector<uint8_t> states;
+    auto masks = verify_batch_impl(*transcripts, statements, proofs, action, chunk, &states);
+    for (size_t i = 0; i < transcripts->size(); i++) (*transcripts)[i].advance_to(&states[203 * i]);
+    return masks;
+  }
+
+ private:
+  static std::vector<std::optional<ExtendedMask>> verify_batch_impl(const std::vector<Transcript> &transcripts,
+                                                                     const std::vector<RangeStatement> &statements,
+                                                                     const std::vector<RangeProof> &proofs, VerifyAction action, size_t chunk,
+                                                                     std::vector<uint8_t> *states) {
     if (statements.empty() || proofs.empty() || transcripts.empty())
       throw ProofError(ProofErrorKind::InvalidArgument, "Range statements or proofs length empty");
     if (statements.size() != proofs.size()) throw ProofError(ProofErrorKind::InvalidArgument, "Range statements and proofs length mismatch");
@@ -418,8 +514,14 @@ class RangeProof {
     }
     std::vector<uint8_t> masks(n * t * 32), present(n);
     char err[256] = {0};
-    check(bpp_verify_batch(params.engine().ctx(), params.handle(), items.data(), n, static_cast<int>(action), chunk, masks.data(),
-                           present.data(), err, sizeof(err)), err);
+    if (states) {
+      states->assign(203 * n, 0);
+      check(bpp_verify_batch_states(params.engine().ctx(), params.handle(), items.data(), n, static_cast<int>(action), chunk, masks.data(),
+                                    present.data(), states->data(), err, sizeof(err)), err);
+    } else {
+      check(bpp_verify_batch(params.engine().ctx(), params.handle(), items.data(), n, static_cast<int>(action), chunk, masks.data(),
+                             present.data(), err, sizeof(err)), err);
+    }
     std::vector<std::optional<ExtendedMask>> out(n);
     for (size_t i = 0; i < n; i++) {
       if (!present[i]) continue;
@@ -434,7 +536,6 @@ class RangeProof {
     return out;
   }
 
- private:
   static void fill_transcript(const Transcript &tr, const uint8_t *&state, const uint8_t *&label, size_t &len) {
     if (!tr.state().empty()) {
       state = tr.state().data();

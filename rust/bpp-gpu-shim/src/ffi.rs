@@ -339,6 +339,22 @@ extern "C" {
     pub fn bpp_host_pool_cpu_ns() -> u64;
     pub fn bpp_device_chain_stats(ctx: *mut bpp_ctx, calls: *mut u64, redraws: *mut u64) -> c_int;
     pub fn bpp_transcript_new(label: *const u8, label_len: usize, state203: *mut u8) -> c_int;
+    pub fn bpp_transcript_append_message(state203: *mut u8, label: *const u8, label_len: usize, msg: *const u8, msg_len: usize) -> c_int;
+    pub fn bpp_transcript_challenge_bytes(state203: *mut u8, label: *const u8, label_len: usize, out: *mut u8, out_len: usize) -> c_int;
+    pub fn bpp_verify_batch_states(ctx: *mut bpp_ctx, params: u64, items: *const bpp_verify_item, n_items: usize, action: c_int, chunk: usize,
+                                   masks_out: *mut u8, mask_present: *mut u8, states_out203: *mut u8, errbuf: *mut c_char,
+                                   errbuf_len: usize) -> c_int;
+    pub fn bpp_verify_batch_packed_states(ctx: *mut bpp_ctx, params: u64, input: *const bpp_packed_batch, action: c_int, chunk: usize,
+                                          masks_out: *mut u8, mask_present: *mut u8, states_out203: *mut u8, errbuf: *mut c_char,
+                                          errbuf_len: usize) -> c_int;
+    pub fn bpp_verify_resident_states(ctx: *mut bpp_ctx, batch: u64, action: c_int, chunk: usize, masks_out: *mut u8, mask_present: *mut u8,
+                                      states_out203: *mut u8, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_batch_mixed_states(ctx: *mut bpp_ctx, params: u64, items: *const bpp_prove_item, n_items: usize, proofs_out: *mut u8,
+                                        proof_stride: usize, proof_lens: *mut usize, item_status: *mut c_int, states_out203: *mut u8,
+                                        errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_openings_states(ctx: *mut bpp_ctx, params: u64, items: *const bpp_prove_item, n_items: usize, commitments_out: *mut u8,
+                                     commit_stride: usize, proofs_out: *mut u8, proof_stride: usize, proof_lens: *mut usize,
+                                     item_status: *mut c_int, states_out203: *mut u8, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
     pub fn bpp_batch_secret_bytes(ctx: *mut bpp_ctx, batch: u64, nonzero: *mut u64) -> c_int;
     pub fn bpp_prove_secret_bytes(ctx: *mut bpp_ctx, examined: *mut u64, nonzero: *mut u64) -> c_int;
     pub fn bpp_shader_clock(ctx: *mut bpp_ctx, window_us: u32, ghz: *mut f64) -> c_int;
