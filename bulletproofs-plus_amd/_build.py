@@ -106,6 +106,21 @@ def build_prove_job_harness(force=False):
     return PROVE_JOB_SANITIZER_BIN
 
 
+LANES_BINS = {"tsan": os.path.join(HERE, "hosttest_lanes_tsan"), "asan": os.path.join(HERE, "hosttest_lanes_asan")}
+LANES_FLAGS = {"tsan": ["-fsanitize=thread"], "asan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]}
+
+
+def build_lanes_harness(kind, force=False):
+    """hosttest_lanes.cpp (lanes_host.h: the submit/collect and the leader protocol behind the pipelines, the batcher and the prove
+    pool) under ThreadSanitizer (kind "tsan") or ASan + UBSan ("asan"): an executable, run by tests/test_lanes_host.py."""
+    src = os.path.join(CSRC, "hosttest_lanes.cpp")
+    exe = LANES_BINS[kind]
+    if not force and not _stale(exe, [src, os.path.join(CSRC, "lanes_host.h")]):
+        return exe
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-pthread"] + LANES_FLAGS[kind] + ["-o", exe, src], check=True, cwd=CSRC)
+    return exe
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     build_hosttest(force="--force" in sys.argv)

@@ -35,6 +35,7 @@
 #include "ct.h"
 #include "kernels_prove.h"
 #include "kernels_verify.h"
+#include "lanes_host.h"
 #include "msm.h"
 #include "msm_plain.h"
 #include "prove_job_host.h"
@@ -143,6 +144,37 @@ inline void state_row_to_bytes(uint8_t *out203, const uint32_t *row) {
   out203[200] = (uint8_t)row[50];
   out203[201] = (uint8_t)(row[50] >> 8);
   out203[202] = (uint8_t)(row[50] >> 16);
+}
+
+// a lane's counters into a sum over lanes (contexts' own, a pipeline's, a pool's)
+inline void add_stats(struct bpp_prove_check_stats &sum, const struct bpp_prove_check_stats &s) {
+  sum.calls += s.calls;
+  sum.proofs += s.proofs;
+  sum.batch_failures += s.batch_failures;
+  sum.remade += s.remade;
+  sum.failed += s.failed;
+}
+inline void add_stats(struct bpp_verify_check_stats &sum, const struct bpp_verify_check_stats &s) {
+  sum.calls += s.calls;
+  sum.rechecked_groups += s.rechecked_groups;
+  sum.confirmed += s.confirmed;
+  sum.overturned += s.overturned;
+  sum.tie_breaks += s.tie_breaks;
+  sum.undecided += s.undecided;
+}
+// a context's self-check counters added to a sum over lanes (the prove pool's, the prove pipeline's); the context's code
+inline int add_check_stats(bpp_ctx *c, struct bpp_prove_check_stats &sum) {
+  struct bpp_prove_check_stats s;
+  const int rc = bpp_prove_check_stats(c, &s);
+  if (rc == BPP_OK) add_stats(sum, s);
+  return rc;
+}
+inline int add_recovery_stats(bpp_ctx *c, uint64_t &replayed, uint64_t &mismatched) {
+  uint64_t r = 0, m = 0;
+  const int rc = bpp_prove_check_recovery_stats(c, &r, &m);
+  replayed += rc == BPP_OK ? r : 0;
+  mismatched += rc == BPP_OK ? m : 0;
+  return rc;
 }
 
 void set_err(char *errbuf, size_t len, const std::string &m) {
@@ -514,11 +546,13 @@ struct PipeLane {
   bool busy = false;             // from the moment submit claims the lane until its job is done
 };
 
+// (the ticket protocol of lanes_host.h written out: the depth-1 submit/collect cycle measured 9 % slower through TicketLanes and
+// the cause was not found, profiles/lanes_refactor_ab.txt; the prove pipeline, which measured no slower, runs on it)
 struct Pipeline {
   std::mutex mu;                  // lanes' state, tickets
   std::condition_variable cv;
   std::mutex submit_mu;           // one submit at a time: lanes are claimed in ticket order
-  std::vector<std::unique_ptr<PipeLane>> lanes;
+  std::vector<std::unique_ptr<PipeLane>> lanes;  // fixed once the pipeline exists
   std::map<uint64_t, std::shared_ptr<PipeJob>> tickets;
   uint64_t next_ticket = 1;
   uint32_t next_lane = 0;
@@ -528,7 +562,8 @@ struct Pipeline {
 void pipeline_shutdown(bpp_ctx *ctx);
 
 // the same for prove calls (bpp_prove_submit / bpp_prove_collect, engine_prove_pipe.h): lanes and tickets of their own
-struct ProvePipeline;
+struct ProveJob;
+using ProvePipeline = lanes::TicketLanes<bpp_ctx *, ProveJob>;
 void prove_pipeline_shutdown(bpp_ctx *ctx);
 // what the lanes add to the context's own answers (bpp_prove_check_stats, bpp_prove_check_recovery_stats, bpp_prove_secret_bytes);
 // nothing for a context that never used the prove pipeline
@@ -659,7 +694,7 @@ struct bpp_ctx {
   struct CheckTamper {
     int proof = 0, byte = 1, mask = 1, times = 1, nonce = 0;
   } tamper;
-  std::unique_ptr<Pipeline> pipe;  // bpp_verify_submit_packed / bpp_verify_collect: lanes, tickets (built on first submit)
+  std::shared_ptr<Pipeline> pipe;  // bpp_verify_submit_packed / bpp_verify_collect: lanes, tickets (built on first submit)
   std::mutex pipe_init_mu;
   uint32_t pipe_depth = 3;
   std::shared_ptr<ProvePipeline> prove_pipe;  // bpp_prove_submit / bpp_prove_collect: lanes, tickets (built on first submit)
@@ -3129,10 +3164,96 @@ int bpp_verify_batch_packed_states(bpp_ctx *ctx, uint64_t params, const bpp_pack
 
 // ---------------------------------------------------------------- pipelined host-buffers-in form
 // One context, `depth` lanes.  A lane is a private child context (own stream, page-locked staging, recycled work buffers)
-// plus a worker thread.  submit packs the caller's buffers into the next lane's staging ON THE CALLING THREAD -- the lanes
-// of earlier tickets are busy with DMA, kernels and weight chains meanwhile -- and hands the plan to the lane's worker,
-// which runs the device half of the upload, the verification and the release exactly as bpp_verify_batch_packed does.
+// plus a worker thread (lanes::TicketLanes).  submit packs the caller's buffers into the next lane's staging ON THE CALLING
+// THREAD -- the lanes of earlier tickets are busy with DMA, kernels and weight chains meanwhile -- and hands the plan to the
+// lane's worker, which runs the device half of the upload, the verification and the release exactly as bpp_verify_batch_packed does.
 namespace {
+
+// ---- what the lanes of the two pipelines (this one, engine_prove_pipe.h) and of the two pools (engine_batcher.h,
+// engine_prove_pool.h) are made of.  Lock order: ctx->mu is never taken while a pipeline's or a pool's mutex is held.
+bpp_ctx::Options ctx_options(bpp_ctx *ctx) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  return ctx->opt;
+}
+
+// n new contexts on `device`, each retaining `params` if given and then handed to `adopt`.  All or nothing: the ones already
+// made are destroyed when one fails.
+template <class Adopt>
+int make_lane_contexts(int device, uint32_t n, const uint64_t *params, Adopt adopt, std::vector<bpp_ctx *> &out) {
+  for (uint32_t i = 0; i < n; i++) {
+    bpp_ctx *c = nullptr;
+    int rc = bpp_ctx_create(&c, device);
+    if (rc == BPP_OK && params) rc = bpp_params_retain(c, *params);
+    if (rc != BPP_OK) {
+      if (c) bpp_ctx_destroy(c);
+      for (bpp_ctx *made : out) bpp_ctx_destroy(made);
+      out.clear();
+      return rc;
+    }
+    adopt(c);
+    out.push_back(c);
+  }
+  return BPP_OK;
+}
+
+// the contexts of a pool's lanes: the caller's own first, then lanes - 1 that the pool owns
+template <class Lane, class Adopt>
+int make_pool_lanes(bpp_ctx *ctx, uint64_t params, uint32_t lanes, Adopt adopt, std::vector<Lane> &out) {
+  const bpp_ctx::Options opt = ctx_options(ctx);
+  std::vector<bpp_ctx *> own;
+  const int rc = make_lane_contexts(ctx->device, lanes - 1, &params, [&](bpp_ctx *c) { adopt(c, opt); }, own);
+  if (rc != BPP_OK) return rc;
+  out.resize(lanes);
+  out[0].ctx = ctx;
+  for (uint32_t i = 1; i < lanes; i++) {
+    out[i].ctx = own[i - 1];
+    out[i].own = true;
+  }
+  return BPP_OK;
+}
+
+// a context's pipeline (`slot`, guarded by `init_mu`), made on the first submit: `depth` child contexts with the knobs of the
+// caller's context as they are now (the tamper knobs stay behind), read BEFORE the pipeline's own lock is taken
+template <class P, class Make>
+std::shared_ptr<P> pipeline_get(bpp_ctx *ctx, std::mutex &init_mu, std::shared_ptr<P> &slot, const uint32_t &depth, const char *what, Make make) {
+  {
+    std::lock_guard<std::mutex> lk(init_mu);
+    if (slot) return slot;
+  }
+  const bpp_ctx::Options opt = ctx_options(ctx);
+  std::lock_guard<std::mutex> lk(init_mu);
+  if (slot) return slot;  // (another thread's first submit was quicker)
+  std::vector<bpp_ctx *> children;
+  if (make_lane_contexts(ctx->device, depth, nullptr, [&](bpp_ctx *c) { c->opt = opt; }, children) != BPP_OK) throw EngineError{BPP_ERR_ENGINE, what};
+  try {
+    slot = make(children);
+  } catch (...) {  // (an allocation, a worker thread that could not be started: the children go with it)
+    for (bpp_ctx *c : children) bpp_ctx_destroy(c);
+    throw;
+  }
+  return slot;
+}
+
+// every reader's reference: the pipeline outlives a context destroyed meanwhile
+template <class P>
+std::shared_ptr<P> pipeline_peek(std::mutex &init_mu, const std::shared_ptr<P> &slot) {
+  std::lock_guard<std::mutex> lk(init_mu);
+  return slot;
+}
+
+// waits for the calls in flight on the lanes, joins their threads, hands what nobody collected to `on_uncollected`, destroys the lanes
+template <class P, class F>
+void pipeline_end(std::mutex &init_mu, std::shared_ptr<P> &slot, F on_uncollected) {
+  std::shared_ptr<P> pp;
+  {
+    std::lock_guard<std::mutex> lk(init_mu);
+    pp = std::move(slot);
+    slot.reset();
+  }
+  if (!pp) return;
+  pp->shutdown(on_uncollected);
+  pp->for_each_lane([](bpp_ctx *c) { bpp_ctx_destroy(c); });
+}
 
 void pipe_worker(bpp_ctx *owner, Pipeline *pp, PipeLane *lane) {
   (void)hipSetDevice(owner->device);
@@ -3184,28 +3305,35 @@ void pipe_worker(bpp_ctx *owner, Pipeline *pp, PipeLane *lane) {
   }
 }
 
-Pipeline *pipeline_get(bpp_ctx *ctx) {
-  std::lock_guard<std::mutex> lk(ctx->pipe_init_mu);
-  if (ctx->pipe) return ctx->pipe.get();
-  auto pp = std::make_unique<Pipeline>();
-  for (uint32_t i = 0; i < ctx->pipe_depth; i++) {
-    auto lane = std::make_unique<PipeLane>();
-    if (bpp_ctx_create(&lane->child, ctx->device) != BPP_OK) throw EngineError{BPP_ERR_ENGINE, "pipeline lane: context creation failed"};
-    lane->child->opt = ctx->opt;
-    pp->lanes.push_back(std::move(lane));
+std::shared_ptr<Pipeline> make_pipeline(bpp_ctx *owner, const std::vector<bpp_ctx *> &children) {
+  auto pp = std::make_shared<Pipeline>();
+  for (bpp_ctx *c : children) {
+    pp->lanes.push_back(std::make_unique<PipeLane>());
+    pp->lanes.back()->child = c;
   }
-  for (auto &lane : pp->lanes) lane->th = std::thread(pipe_worker, ctx, pp.get(), lane.get());
-  ctx->pipe = std::move(pp);
-  return ctx->pipe.get();
+  try {
+    for (auto &lane : pp->lanes) lane->th = std::thread(pipe_worker, owner, pp.get(), lane.get());
+  } catch (...) {  // a thread that could not be started: the ones that were are ended, not abandoned while joinable
+    {
+      std::lock_guard<std::mutex> lk(pp->mu);
+      pp->quit = true;
+    }
+    pp->cv.notify_all();
+    for (auto &lane : pp->lanes)
+      if (lane->th.joinable()) lane->th.join();
+    throw;
+  }
+  return pp;
 }
 
 }  // namespace
 
 void pipeline_shutdown(bpp_ctx *ctx) {
-  std::unique_ptr<Pipeline> pp;
+  std::shared_ptr<Pipeline> pp;
   {
     std::lock_guard<std::mutex> lk(ctx->pipe_init_mu);
     pp = std::move(ctx->pipe);
+    ctx->pipe.reset();
   }
   if (!pp) return;
   {
@@ -3222,7 +3350,9 @@ void pipeline_shutdown(bpp_ctx *ctx) {
     if (l->th.joinable()) l->th.join();
     bpp_ctx_destroy(l->child);
   }
+  std::lock_guard<std::mutex> lk(pp->mu);
   for (auto &kv : pp->tickets) wipe(kv.second->masks.data(), kv.second->masks.size());
+  pp->tickets.clear();
 }
 
 extern "C" {
@@ -3247,7 +3377,8 @@ int bpp_verify_submit_packed(bpp_ctx *ctx, uint64_t params, const bpp_packed_bat
     if (in->n_items > (1u << 24)) return fail(nullptr, BPP_ERR_SIZE_OVERFLOW, "batch too large", errbuf, errbuf_len);
     const std::shared_ptr<Params> Pp = params_registry().get(params);
     if (!Pp || Pp->device != ctx->device) return fail(nullptr, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
-    Pipeline *pp = pipeline_get(ctx);
+    const std::shared_ptr<Pipeline> pp = pipeline_get(ctx, ctx->pipe_init_mu, ctx->pipe, ctx->pipe_depth, "pipeline lane: context creation failed",
+                                                      [&](const std::vector<bpp_ctx *> &children) { return make_pipeline(ctx, children); });
     std::lock_guard<std::mutex> submit_lock(pp->submit_mu);
     PipeLane *lane;
     {
@@ -3291,11 +3422,7 @@ int bpp_verify_submit_packed(bpp_ctx *ctx, uint64_t params, const bpp_packed_bat
 int bpp_verify_collect(bpp_ctx *ctx, uint64_t ticket, uint8_t *masks_out, uint8_t *mask_present, char *errbuf,
                        size_t errbuf_len) {
   if (!ctx) return BPP_ERR_BAD_HANDLE;
-  Pipeline *pp;
-  {
-    std::lock_guard<std::mutex> lk(ctx->pipe_init_mu);
-    pp = ctx->pipe.get();
-  }
+  const std::shared_ptr<Pipeline> pp = pipeline_peek(ctx->pipe_init_mu, ctx->pipe);
   if (!pp) return fail(nullptr, BPP_ERR_BAD_HANDLE, "unknown ticket", errbuf, errbuf_len);
   std::shared_ptr<PipeJob> job;
   {
@@ -3303,8 +3430,8 @@ int bpp_verify_collect(bpp_ctx *ctx, uint64_t ticket, uint8_t *masks_out, uint8_
     auto it = pp->tickets.find(ticket);
     if (it == pp->tickets.end()) return fail(nullptr, BPP_ERR_BAD_HANDLE, "unknown ticket", errbuf, errbuf_len);
     job = it->second;
-    pp->cv.wait(lk, [&] { return job->done; });
-    pp->tickets.erase(it);
+    pp->cv.wait(lk, [&] { return job->done; });  // (the lock is released in the wait: `it` is not used again)
+    if (!pp->tickets.erase(ticket)) return fail(nullptr, BPP_ERR_BAD_HANDLE, "unknown ticket", errbuf, errbuf_len);  // (another thread was first)
   }
   ScopeExit wipe_masks{[&] { wipe(job->masks.data(), job->masks.size()); }};
   if (job->rc != BPP_OK) {
@@ -3589,24 +3716,12 @@ int bpp_verify_check_stats(bpp_ctx *ctx, struct bpp_verify_check_stats *out) {
     std::lock_guard<std::mutex> lk(ctx->mu);
     *out = ctx->vcheck_stats;
   }
-  std::vector<bpp_ctx *> lanes;  // the packed pipeline's lanes: contexts of their own, made on the first submit
-  {
-    std::lock_guard<std::mutex> lk(ctx->pipe_init_mu);
-    if (ctx->pipe) {
-      std::lock_guard<std::mutex> lk2(ctx->pipe->mu);
-      for (auto &l : ctx->pipe->lanes)
-        if (l->child) lanes.push_back(l->child);
+  // the packed pipeline's lanes: contexts of their own, made on the first submit
+  if (const std::shared_ptr<Pipeline> pp = pipeline_peek(ctx->pipe_init_mu, ctx->pipe))
+    for (auto &l : pp->lanes) {
+      std::lock_guard<std::mutex> lk(l->child->mu);
+      add_stats(*out, l->child->vcheck_stats);
     }
-  }
-  for (bpp_ctx *c : lanes) {
-    std::lock_guard<std::mutex> lk(c->mu);
-    out->calls += c->vcheck_stats.calls;
-    out->rechecked_groups += c->vcheck_stats.rechecked_groups;
-    out->confirmed += c->vcheck_stats.confirmed;
-    out->overturned += c->vcheck_stats.overturned;
-    out->tie_breaks += c->vcheck_stats.tie_breaks;
-    out->undecided += c->vcheck_stats.undecided;
-  }
   return BPP_OK;
 }
 

@@ -19,19 +19,16 @@
 #pragma once
 
 struct bpp_batcher {
-  struct Req {
+  struct Req : lanes::PoolReq {
     const bpp_packed_batch *in = nullptr;
     int action = BPP_VERIFY_ONLY;
     uint8_t *masks_out = nullptr, *mask_present = nullptr;
     int code = BPP_OK;
     std::string msg;
-    bool taken = false;  // a leader has it in its pooled call
-    bool done = false;
   };
   struct Lane {
     bpp_ctx *ctx = nullptr;  // a context of its own (stream, staging, recycled work buffers)
     bool own = false;
-    bool busy = false;
     std::vector<bpp_verify_item> items;
     std::vector<uint32_t> bounds;
     std::vector<int> actions;
@@ -40,40 +37,37 @@ struct bpp_batcher {
   };
   uint64_t params = 0;
   uint32_t t = 1;
-  uint32_t max_wait_us = 0, max_calls = 64, max_proofs = 16384;
-  std::mutex mu;
-  std::condition_variable cv;
-  std::deque<Req *> pending;
-  std::vector<Lane> lanes;
-  uint64_t pooled_calls = 0, engine_calls = 0, solo_calls = 0;  // statistics
-  uint32_t largest_pool_calls = 0, largest_pool_proofs = 0;
+  lanes::LeaderPool<Lane, Req> pool;  // the leader protocol (lanes_host.h); a request's weight is its number of proofs
+  bpp_batcher(std::vector<Lane> lanes, uint32_t max_wait_us, uint32_t max_calls) : pool(std::move(lanes), max_wait_us, max_calls, 16384) {}
 };
 
 namespace {
 
 // A proof of more than this many bytes cannot belong to any statement (64 (L, R) pairs is the wire cap, layout.h) and an input
 // of more than max_proofs items is a large call by itself: both go through a call of their own.
-bool batcher_poolable(const bpp_batcher *b, const bpp_packed_batch *in) {
-  return in->n_items <= b->max_proofs && in->proof_len <= 1 + 32 * (size_t)(6 + 5 + 2 * 64) && in->proof_stride >= in->proof_len;
+bool batcher_poolable(uint32_t max_proofs, const bpp_packed_batch *in) {
+  return in->n_items <= max_proofs && in->proof_len <= 1 + 32 * (size_t)(6 + 5 + 2 * 64) && in->proof_stride >= in->proof_len;
 }
 // requests of one pool either all need the final check or none does (a RecoverOnly pool skips the weight chains and PASS 2)
-inline bool batcher_wants_msm(const bpp_batcher::Req *r) { return r->action != BPP_RECOVER_ONLY; }
+inline bool batcher_wants_msm(const bpp_batcher::Req &r) { return r.action != BPP_RECOVER_ONLY; }
 
 void batcher_run_unchecked(bpp_batcher *b, bpp_batcher::Lane &L, std::vector<bpp_batcher::Req *> reqs);
+// a failure of a pooled call that is nobody's finding (the batcher's and the prove pool's)
+template <class Req>
+void fail_requests(const std::vector<Req *> &reqs, const std::string &msg) {
+  for (auto *r : reqs) {
+    r->code = BPP_ERR_ENGINE;
+    r->msg = msg;
+  }
+}
 // one pooled engine call on `lane` over `reqs`; fills every request's code / msg (nothing may escape: callers are waiting)
 void batcher_run(bpp_batcher *b, bpp_batcher::Lane &L, const std::vector<bpp_batcher::Req *> &reqs) {
   try {
     batcher_run_unchecked(b, L, reqs);
   } catch (const std::exception &e) {
-    for (auto *r : reqs) {
-      r->code = BPP_ERR_ENGINE;
-      r->msg = std::string("batcher: ") + e.what();
-    }
+    fail_requests(reqs, std::string("batcher: ") + e.what());
   } catch (...) {
-    for (auto *r : reqs) {
-      r->code = BPP_ERR_ENGINE;
-      r->msg = "batcher: unexpected failure";
-    }
+    fail_requests(reqs, "batcher: unexpected failure");
   }
 }
 
@@ -185,90 +179,57 @@ int bpp_batcher_create(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *sh
   if (!Pp || Pp->device != ctx->device) return BPP_ERR_BAD_HANDLE;
   if (lanes == 0) lanes = 2;  // (two pooled calls in flight keep the pools large; three are within run-to-run noise of two, four and six lose)
   if (lanes > 8) lanes = 8;
-  auto b = std::make_unique<bpp_batcher>();
+  std::vector<bpp_batcher::Lane> made;
+  // a lane rechecks its rejections when the context it was made from does ("verify_check", read as it is now)
+  const int rc = make_pool_lanes(ctx, params, lanes, [](bpp_ctx *c, const bpp_ctx::Options &opt) { c->opt.verify_check = opt.verify_check; }, made);
+  if (rc != BPP_OK) return rc;
+  auto b = std::make_unique<bpp_batcher>(std::move(made), max_wait_us, max_calls ? max_calls : 64);
   b->params = params;
   b->t = Pp->t;
-  b->max_wait_us = max_wait_us;
-  if (max_calls) b->max_calls = max_calls;
-  b->lanes.resize(lanes);
-  for (uint32_t i = 0; i < lanes; i++) {
-    if (i == 0) {
-      b->lanes[i].ctx = ctx;
-    } else {
-      bpp_ctx *c = nullptr;
-      int rc = bpp_ctx_create(&c, ctx->device);
-      if (rc == BPP_OK) rc = bpp_params_retain(c, params);
-      if (rc != BPP_OK) {
-        if (c) bpp_ctx_destroy(c);
-        for (uint32_t j = 1; j < i; j++) bpp_ctx_destroy(b->lanes[j].ctx);
-        return rc;
-      }
-      {  // a lane rechecks its rejections when the context it was made from does ("verify_check", read as it is now)
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        c->opt.verify_check = ctx->opt.verify_check;
-      }
-      b->lanes[i].ctx = c;
-      b->lanes[i].own = true;
-    }
-  }
   *out = b.release();
   return BPP_OK;
 }
 
 int bpp_batcher_set_limits(bpp_batcher *b, uint32_t max_calls, uint32_t max_proofs) {
   if (!b) return BPP_ERR_BAD_HANDLE;
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (max_calls) b->max_calls = max_calls;
-  if (max_proofs) b->max_proofs = max_proofs;
+  b->pool.set_limits(max_calls, max_proofs);
   return BPP_OK;
 }
 
 void bpp_batcher_destroy(bpp_batcher *b) {
   if (!b) return;
-  {
-    std::unique_lock<std::mutex> lk(b->mu);
-    b->cv.wait(lk, [&] {
-      for (auto &L : b->lanes)
-        if (L.busy) return false;
-      return b->pending.empty();
-    });
-  }
-  for (auto &L : b->lanes)
+  b->pool.drain();
+  b->pool.for_each_lane([](bpp_batcher::Lane &L) {
     if (L.own) bpp_ctx_destroy(L.ctx);
+  });
   delete b;
 }
 
 int bpp_batcher_stats(bpp_batcher *b, uint64_t *pooled_calls, uint64_t *engine_calls, uint64_t *solo_calls) {
   if (!b) return BPP_ERR_BAD_HANDLE;
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (pooled_calls) *pooled_calls = b->pooled_calls;
-  if (engine_calls) *engine_calls = b->engine_calls;
-  if (solo_calls) *solo_calls = b->solo_calls;
+  const lanes::PoolStats s = b->pool.stats();
+  if (pooled_calls) *pooled_calls = s.pooled_calls;
+  if (engine_calls) *engine_calls = s.engine_calls;
+  if (solo_calls) *solo_calls = s.solo_calls;
   return BPP_OK;
 }
 
 int bpp_batcher_verify_check_stats(bpp_batcher *b, struct bpp_verify_check_stats *out) {
   if (!b || !out) return BPP_ERR_BAD_HANDLE;
   memset(out, 0, sizeof(*out));
-  for (auto &L : b->lanes) {  // (the first lane is the caller's context: bpp_verify_check_stats adds its pipeline's lanes)
+  int rc = BPP_OK;
+  b->pool.for_each_lane([&](bpp_batcher::Lane &L) {  // (the first lane is the caller's context: bpp_verify_check_stats adds its pipeline's lanes)
     struct bpp_verify_check_stats one;
-    const int rc = bpp_verify_check_stats(L.ctx, &one);
-    if (rc != BPP_OK) return rc;
-    out->calls += one.calls;
-    out->rechecked_groups += one.rechecked_groups;
-    out->confirmed += one.confirmed;
-    out->overturned += one.overturned;
-    out->tie_breaks += one.tie_breaks;
-    out->undecided += one.undecided;
-  }
-  return BPP_OK;
+    if (rc == BPP_OK && (rc = bpp_verify_check_stats(L.ctx, &one)) == BPP_OK) add_stats(*out, one);
+  });
+  return rc;
 }
 
 int bpp_batcher_largest_pool(bpp_batcher *b, uint32_t *calls, uint32_t *proofs) {
   if (!b) return BPP_ERR_BAD_HANDLE;
-  std::lock_guard<std::mutex> lk(b->mu);
-  if (calls) *calls = b->largest_pool_calls;
-  if (proofs) *proofs = b->largest_pool_proofs;
+  const lanes::PoolStats s = b->pool.stats();
+  if (calls) *calls = s.largest_pool_calls;
+  if (proofs) *proofs = s.largest_pool_weight;
   return BPP_OK;
 }
 
@@ -288,81 +249,11 @@ int bpp_batcher_verify_action(bpp_batcher *b, const bpp_packed_batch *in, int ac
   me.action = action;
   me.masks_out = masks_out;
   me.mask_present = mask_present;
-  const bool poolable = batcher_poolable(b, in);
-  std::vector<bpp_batcher::Req *> mine;
-  bpp_batcher::Lane *lane = nullptr;
-  {
-    std::unique_lock<std::mutex> lk(b->mu);
-    if (poolable) b->pending.push_back(&me);
-    auto free_lane = [&]() -> bpp_batcher::Lane * {
-      for (auto &L : b->lanes)
-        if (!L.busy) return &L;
-      return nullptr;
-    };
-    // wait until somebody else has dealt with this request, or -- as long as nobody has taken it -- a lane is free and this
-    // thread leads the next pooled call
-    b->cv.wait(lk, [&] { return me.done || (!me.taken && free_lane() != nullptr); });
-    if (me.done) {
-      set_err(errbuf, errbuf_len, me.msg);
-      return me.code;
-    }
-    lane = free_lane();
-    lane->busy = true;
-    if (poolable) {
-      if (b->max_wait_us && b->pending.size() < b->max_calls)
-        b->cv.wait_for(lk, std::chrono::microseconds(b->max_wait_us), [&] { return me.taken || b->pending.size() >= b->max_calls; });
-      if (me.taken) {  // another leader took this thread's request while it waited for company: let that one finish it
-        lane->busy = false;
-        b->cv.notify_all();
-        b->cv.wait(lk, [&] { return me.done; });
-        set_err(errbuf, errbuf_len, me.msg);
-        return me.code;
-      }
-      // The leader's own request goes first (it fits by itself: poolable), then whatever is queued, oldest first, as long as the
-      // pool stays within max_calls requests and max_proofs proofs and is of one kind (with or without the final check).
-      // Requests that do not fit stay where they are, for the next leader.
-      for (auto it = b->pending.begin(); it != b->pending.end(); ++it)
-        if (*it == &me) {
-          b->pending.erase(it);
-          break;
-        }
-      me.taken = true;
-      mine.push_back(&me);
-      size_t proofs = in->n_items;
-      const bool msm = batcher_wants_msm(&me);
-      for (auto it = b->pending.begin(); it != b->pending.end() && mine.size() < b->max_calls;) {
-        bpp_batcher::Req *r = *it;
-        if (batcher_wants_msm(r) != msm || proofs + r->in->n_items > b->max_proofs) {
-          ++it;
-          continue;
-        }
-        proofs += r->in->n_items;
-        r->taken = true;
-        mine.push_back(r);
-        it = b->pending.erase(it);
-      }
-    } else {
-      mine.push_back(&me);
-    }
-    b->engine_calls++;
-    if (mine.size() > 1) {
-      b->pooled_calls += mine.size();
-      size_t proofs = 0;
-      for (auto *r : mine) proofs += r->in->n_items;
-      b->largest_pool_calls = std::max(b->largest_pool_calls, (uint32_t)mine.size());
-      b->largest_pool_proofs = std::max(b->largest_pool_proofs, (uint32_t)proofs);
-    } else {
-      b->solo_calls++;
-    }
-  }
-  batcher_run(b, *lane, mine);
-  {
-    std::lock_guard<std::mutex> lk(b->mu);
-    for (auto *r : mine)
-      if (r != &me) r->done = true;  // (`me` lives on this stack and is always part of `mine`)
-    lane->busy = false;
-  }
-  b->cv.notify_all();
+  // a pool is of one kind: with or without the final check
+  b->pool.serve(
+      me, [&](uint32_t max_proofs) { return batcher_poolable(max_proofs, in); }, [](const bpp_batcher::Req &r) { return r.in->n_items; },
+      [](const bpp_batcher::Req &a, const bpp_batcher::Req &r) { return batcher_wants_msm(a) == batcher_wants_msm(r); },
+      [&](bpp_batcher::Lane &L, const std::vector<bpp_batcher::Req *> &reqs) { batcher_run(b, L, reqs); });
   set_err(errbuf, errbuf_len, me.msg);
   return me.code;
 }

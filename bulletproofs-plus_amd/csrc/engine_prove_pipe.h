@@ -1,5 +1,5 @@
 // bpp_prove_submit / bpp_prove_collect: prove calls in flight from ONE thread and ONE context, the prover's form of
-// bpp_verify_submit_packed / bpp_verify_collect (Pipeline / PipeLane / pipe_worker in engine.hip).
+// bpp_verify_submit_packed / bpp_verify_collect (engine.hip), over the same tickets-and-lanes protocol (lanes::TicketLanes).
 //
 // One context, `depth` lanes.  A lane is a private child context (the prover's streams, arena and page-locked staging of its own)
 // plus a worker thread.  submit checks every item ON THE CALLING THREAD (prove_item_check, as prove_mixed does), takes a copy of
@@ -25,36 +25,19 @@ struct ProveJob {
   int call_rc = BPP_OK;  // a finding of the whole call (an exception of the lane's prove_mixed): collect returns it and writes nothing
   std::string call_msg;
   std::vector<std::array<uint8_t, 32>> note;  // what the lane's call left for bpp_prove_item_message (check_recovery_failed)
-  bool done = false, collected = false;
+  bool done = false;
 };
 
-struct ProveLane {
-  bpp_ctx *child = nullptr;
-  std::thread th;
-  std::shared_ptr<ProveJob> job;  // posted by submit, taken by the worker
-  bool busy = false;              // from the moment submit claims the lane until its job is done (not: collected)
-};
-
-struct ProvePipeline {
-  std::mutex mu;  // lanes' state, tickets
-  std::condition_variable cv;
-  std::mutex submit_mu;  // one submit at a time: lanes are claimed in ticket order
-  std::vector<std::unique_ptr<ProveLane>> lanes;
-  std::map<uint64_t, std::shared_ptr<ProveJob>> tickets;
-  // a number space of its own: bpp_verify_collect counts from 1 and never gets here, and a verify ticket is none of these
-  uint64_t next_ticket = (1ull << 48) + 1;
-  uint32_t next_lane = 0;
-  bool quit = false;
-};
+// (tickets in a number space of its own: bpp_verify_collect counts from 1 and never gets here, and a verify ticket is none of these)
+static const uint64_t PROVE_FIRST_TICKET = (1ull << 48) + 1;
 
 namespace {
 
 // the lane's call over the job's copy: what bpp_prove_batch_mixed / bpp_prove_openings do between BPP_ENTRY and the return
-void prove_pipe_run(ProveLane *lane, ProveJob &job) {
+void prove_pipe_run(bpp_ctx *&c, ProveJob &job) {
   ScopeExit wipe_copy{[&] { job.copy.wipe(); }};  // on every way out: the witness bytes are not needed once the call has returned
   const size_t n = job.copy.items.size();
   if (n == 0) return;  // (nothing passed the check: the blocking call returns before any device work as well)
-  bpp_ctx *c = lane->child;
   std::vector<uint8_t> proofs(n * job.row, 0), commits(job.openings ? n * job.crow : 0, 0);
   std::vector<size_t> lens(n, 0);
   std::vector<uint8_t *> slots(job.openings ? n : 0);
@@ -91,135 +74,60 @@ void prove_pipe_run(ProveLane *lane, ProveJob &job) {
   }
 }
 
-void prove_pipe_worker(bpp_ctx *owner, ProvePipeline *pp, ProveLane *lane) {
-  (void)hipSetDevice(owner->device);
-  for (;;) {
-    std::shared_ptr<ProveJob> job;
-    {
-      std::unique_lock<std::mutex> lk(pp->mu);
-      pp->cv.wait(lk, [&] { return pp->quit || lane->job; });
-      if (!lane->job) return;  // quit with nothing posted
-      job = std::move(lane->job);
-      lane->job.reset();
-    }
-    try {
-      prove_pipe_run(lane, *job);
-    } catch (const std::exception &e) {  // (an allocation of the merge itself: nothing may escape a worker)
-      job->call_rc = BPP_ERR_ENGINE;
-      job->call_msg = std::string("prove pipeline: ") + e.what();
-    }
-    {
-      std::lock_guard<std::mutex> lk(pp->mu);
-      job->done = true;
-      lane->busy = false;  // the lane is free now: the results wait in the job
-    }
-    pp->cv.notify_all();
-  }
+void prove_pipe_threw(ProveJob &job, const char *what) {  // (an allocation of the merge itself: nothing escapes a worker)
+  job.call_rc = BPP_ERR_ENGINE;
+  job.call_msg = std::string("prove pipeline: ") + (what ? what : "unexpected failure");
 }
 
-ProvePipeline *prove_pipeline_get(bpp_ctx *ctx) {
-  {
-    std::lock_guard<std::mutex> lk(ctx->prove_pipe_init_mu);
-    if (ctx->prove_pipe) return ctx->prove_pipe.get();
-  }
-  // the knobs of the caller's context as they are now hold on every lane (the self-check's tamper knobs stay behind).  Read
-  // BEFORE the pipeline's own lock is taken: nothing takes the context's lock while it holds the pipeline's
-  bpp_ctx::Options opt;
-  {
-    std::lock_guard<std::mutex> ck(ctx->mu);
-    opt = ctx->opt;
-  }
-  std::lock_guard<std::mutex> lk(ctx->prove_pipe_init_mu);
-  if (ctx->prove_pipe) return ctx->prove_pipe.get();  // (another thread's first submit was quicker)
-  auto pp = std::make_shared<ProvePipeline>();
-  for (uint32_t i = 0; i < ctx->prove_pipe_depth; i++) {
-    auto lane = std::make_unique<ProveLane>();
-    if (bpp_ctx_create(&lane->child, ctx->device) != BPP_OK) {
-      for (auto &l : pp->lanes) bpp_ctx_destroy(l->child);
-      throw EngineError{BPP_ERR_ENGINE, "prove pipeline lane: context creation failed"};
-    }
-    lane->child->opt = opt;
-    pp->lanes.push_back(std::move(lane));
-  }
-  for (auto &lane : pp->lanes) lane->th = std::thread(prove_pipe_worker, ctx, pp.get(), lane.get());
-  ctx->prove_pipe = std::move(pp);
-  return ctx->prove_pipe.get();
+std::shared_ptr<ProvePipeline> prove_pipeline_get(bpp_ctx *ctx) {
+  return pipeline_get(ctx, ctx->prove_pipe_init_mu, ctx->prove_pipe, ctx->prove_pipe_depth, "prove pipeline lane: context creation failed",
+                      [](std::vector<bpp_ctx *> children) {
+                        return std::make_shared<ProvePipeline>(std::move(children), PROVE_FIRST_TICKET, prove_pipe_run, prove_pipe_threw);
+                      });
 }
 
-std::shared_ptr<ProvePipeline> prove_pipeline_peek(bpp_ctx *ctx) {
-  std::lock_guard<std::mutex> lk(ctx->prove_pipe_init_mu);
-  return ctx->prove_pipe;
+std::shared_ptr<ProvePipeline> prove_pipeline_peek(bpp_ctx *ctx) { return pipeline_peek(ctx->prove_pipe_init_mu, ctx->prove_pipe); }
+
+// the sum over the lanes of what `one(lane's context)` answers; the first code that is not BPP_OK ends it
+template <class F>
+int prove_pipeline_sum(bpp_ctx *ctx, F one) {
+  const std::shared_ptr<ProvePipeline> pp = prove_pipeline_peek(ctx);
+  int rc = BPP_OK;
+  if (pp)
+    pp->for_each_lane([&](bpp_ctx *c) {
+      if (rc == BPP_OK) rc = one(c);
+    });
+  return rc;
 }
 
 }  // namespace
 
 void prove_pipeline_shutdown(bpp_ctx *ctx) {
-  std::shared_ptr<ProvePipeline> pp;
-  {
-    std::lock_guard<std::mutex> lk(ctx->prove_pipe_init_mu);
-    pp = std::move(ctx->prove_pipe);
-    ctx->prove_pipe.reset();
-  }
-  if (!pp) return;
-  {
-    std::unique_lock<std::mutex> lk(pp->mu);
-    pp->cv.wait(lk, [&] {  // jobs in flight finish first (every posted job runs, and its worker wipes its copy)
-      for (auto &l : pp->lanes)
-        if (l->busy) return false;
-      return true;
-    });
-    pp->quit = true;
-  }
-  pp->cv.notify_all();
-  for (auto &l : pp->lanes) {
-    if (l->th.joinable()) l->th.join();
-    bpp_ctx_destroy(l->child);
-  }
-  for (auto &kv : pp->tickets) kv.second->copy.wipe();  // results never collected are public; a copy still held is not
-  pp->tickets.clear();
+  // (every posted job has run, and its worker has wiped its copy; results never collected are public, a copy still held is not)
+  pipeline_end(ctx->prove_pipe_init_mu, ctx->prove_pipe, [](ProveJob &job) { job.copy.wipe(); });
 }
 
 int prove_pipeline_check_stats(bpp_ctx *ctx, struct bpp_prove_check_stats *sum) {
-  const std::shared_ptr<ProvePipeline> pp = prove_pipeline_peek(ctx);
-  if (!pp) return BPP_OK;
-  for (auto &l : pp->lanes) {  // (the lanes are fixed once the pipeline exists)
-    struct bpp_prove_check_stats s;
-    const int rc = bpp_prove_check_stats(l->child, &s);
-    if (rc != BPP_OK) return rc;
-    sum->calls += s.calls;
-    sum->proofs += s.proofs;
-    sum->batch_failures += s.batch_failures;
-    sum->remade += s.remade;
-    sum->failed += s.failed;
-  }
-  return BPP_OK;
+  return prove_pipeline_sum(ctx, [&](bpp_ctx *c) { return add_check_stats(c, *sum); });
 }
 
 int prove_pipeline_recovery_stats(bpp_ctx *ctx, uint64_t *replayed, uint64_t *mismatched) {
-  const std::shared_ptr<ProvePipeline> pp = prove_pipeline_peek(ctx);
-  if (!pp) return BPP_OK;
-  for (auto &l : pp->lanes) {
-    uint64_t r = 0, m = 0;
-    const int rc = bpp_prove_check_recovery_stats(l->child, &r, &m);
-    if (rc != BPP_OK) return rc;
-    *replayed += r;
-    *mismatched += m;
-  }
-  return BPP_OK;
+  return prove_pipeline_sum(ctx, [&](bpp_ctx *c) { return add_recovery_stats(c, *replayed, *mismatched); });
 }
 
 int prove_pipeline_secret_bytes(bpp_ctx *ctx, uint64_t *examined, uint64_t *nonzero) {
-  const std::shared_ptr<ProvePipeline> pp = prove_pipeline_peek(ctx);
-  if (!pp) return BPP_OK;
-  for (auto &l : pp->lanes) {  // (waits for a lane's running call: its staging is looked at between calls)
+  // (waits for a lane's running call: its staging is looked at between calls)
+  const int rc = prove_pipeline_sum(ctx, [&](bpp_ctx *c) {
     uint64_t seen = 0, cnt = 0;
-    const int rc = bpp_prove_secret_bytes(l->child, &seen, &cnt);
-    if (rc != BPP_OK) return rc;
-    *examined += seen;
-    *nonzero += cnt;
-  }
-  (void)hipSetDevice(ctx->device);
-  return BPP_OK;
+    const int one = bpp_prove_secret_bytes(c, &seen, &cnt);
+    if (one == BPP_OK) {
+      *examined += seen;
+      *nonzero += cnt;
+    }
+    return one;
+  });
+  if (rc == BPP_OK) (void)hipSetDevice(ctx->device);
+  return rc;
 }
 
 extern "C" {
@@ -255,36 +163,14 @@ int bpp_prove_submit(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *items,
     job->crow = (size_t)32 * Pp->m_max;
     job->proofs.assign(n_items * job->row, 0);
     if (job->openings) job->commits.assign(n_items * job->crow, 0);
-    ProvePipeline *pp = prove_pipeline_get(ctx);
-    std::lock_guard<std::mutex> submit_lock(pp->submit_mu);
-    ProveLane *lane;
-    {
-      std::unique_lock<std::mutex> lk(pp->mu);
-      lane = pp->lanes[pp->next_lane].get();
-      pp->cv.wait(lk, [&] { return !lane->busy; });  // its previous job is done (collected or not): arena and staging are free
-      lane->busy = true;
-      pp->next_lane = (pp->next_lane + 1) % (uint32_t)pp->lanes.size();
-    }
+    const std::shared_ptr<ProvePipeline> pp = prove_pipeline_get(ctx);
+    ProvePipeline::Claim lane = pp->claim();  // its previous job is done (collected or not): arena and staging are free
     // the lane keeps the parameters alive for as long as it lives, whatever the caller does with its own reference
     int held = BPP_OK;
-    if (!lane->child->held_params.count(params)) held = bpp_params_retain(lane->child, params);
+    if (!lane.lane()->held_params.count(params)) held = bpp_params_retain(lane.lane(), params);
     (void)hipSetDevice(ctx->device);
-    if (held != BPP_OK) {
-      {
-        std::lock_guard<std::mutex> lk(pp->mu);
-        lane->busy = false;
-      }
-      pp->cv.notify_all();
-      return fail(nullptr, held, "unknown params handle", errbuf, errbuf_len);
-    }
-    {
-      std::lock_guard<std::mutex> lk(pp->mu);
-      job->ticket = pp->next_ticket++;
-      pp->tickets[job->ticket] = job;
-      lane->job = job;
-      *ticket = job->ticket;
-    }
-    pp->cv.notify_all();
+    if (held != BPP_OK) return fail(nullptr, held, "unknown params handle", errbuf, errbuf_len);  // (the claim gives the lane back)
+    *ticket = pp->post(lane, job);
     set_err(errbuf, errbuf_len, "");
     return BPP_OK;
   }
@@ -296,10 +182,9 @@ int bpp_prove_ticket_done(bpp_ctx *ctx, uint64_t ticket, int *done) {
   if (!done) return BPP_ERR_INVALID_ARGUMENT;
   const std::shared_ptr<ProvePipeline> pp = prove_pipeline_peek(ctx);
   if (!pp) return fail(nullptr, BPP_ERR_BAD_HANDLE, "unknown ticket");
-  std::lock_guard<std::mutex> lk(pp->mu);
-  auto it = pp->tickets.find(ticket);
-  if (it == pp->tickets.end()) return fail(nullptr, BPP_ERR_BAD_HANDLE, "unknown ticket");
-  *done = it->second->done ? 1 : 0;
+  const lanes::TicketState st = pp->done(ticket);
+  if (st == lanes::TicketState::unknown) return fail(nullptr, BPP_ERR_BAD_HANDLE, "unknown ticket");
+  *done = st == lanes::TicketState::done ? 1 : 0;
   return BPP_OK;
 }
 
@@ -308,20 +193,13 @@ int bpp_prove_collect(bpp_ctx *ctx, uint64_t ticket, uint8_t *commitments_out, u
   if (!ctx) return BPP_ERR_BAD_HANDLE;
   const std::shared_ptr<ProvePipeline> pp = prove_pipeline_peek(ctx);
   if (!pp) return fail(nullptr, BPP_ERR_BAD_HANDLE, "unknown ticket", errbuf, errbuf_len);
-  std::shared_ptr<ProveJob> job;
-  {
-    std::unique_lock<std::mutex> lk(pp->mu);
-    auto it = pp->tickets.find(ticket);
-    if (it == pp->tickets.end()) return fail(nullptr, BPP_ERR_BAD_HANDLE, "unknown ticket", errbuf, errbuf_len);
-    job = it->second;
-    // (the blocking calls' "null argument": the ticket stays collectable)
-    if (!proofs_out || !proof_lens || (job->openings && !commitments_out))
-      return fail(nullptr, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
-    pp->cv.wait(lk, [&] { return job->done; });
-    if (job->collected) return fail(nullptr, BPP_ERR_BAD_HANDLE, "unknown ticket", errbuf, errbuf_len);  // (another thread was first)
-    job->collected = true;
-    pp->tickets.erase(ticket);
-  }
+  std::shared_ptr<ProveJob> job = pp->peek(ticket);
+  if (!job) return fail(nullptr, BPP_ERR_BAD_HANDLE, "unknown ticket", errbuf, errbuf_len);
+  // (the blocking calls' "null argument": the ticket stays collectable)
+  if (!proofs_out || !proof_lens || (job->openings && !commitments_out))
+    return fail(nullptr, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
+  job = pp->take(ticket);
+  if (!job) return fail(nullptr, BPP_ERR_BAD_HANDLE, "unknown ticket", errbuf, errbuf_len);  // (another thread was first)
   {  // asking this context about an item right after the collect answers for this ticket (bpp_prove_item_message)
     std::lock_guard<std::mutex> lk(ctx->check_note_mu);
     ctx->check_recovery_failed = job->note;

@@ -15,7 +15,7 @@
 #pragma once
 
 struct bpp_prove_pool {
-  struct Req {
+  struct Req : lanes::PoolReq {
     const bpp_prove_item *items = nullptr;
     size_t n_items = 0;
     uint8_t *proofs_out = nullptr;
@@ -28,13 +28,10 @@ struct bpp_prove_pool {
     size_t commit_stride = 0;
     int code = BPP_OK;
     std::string msg;
-    bool taken = false;  // a leader has it in its pooled call
-    bool done = false;
   };
   struct Lane {
     bpp_ctx *ctx = nullptr;  // a context of its own (streams, arena, staging)
     bool own = false;
-    bool busy = false;
     std::vector<bpp_prove_item> items;
     std::vector<uint8_t> proofs;
     std::vector<size_t> lens;
@@ -44,14 +41,9 @@ struct bpp_prove_pool {
   uint64_t params = 0;
   std::shared_ptr<Params> P;
   size_t plen_max = 0;  // the longest proof these parameters can make (m = m_max): the lanes' output stride
-  uint32_t max_wait_us = 0, max_calls = 64, max_proofs = 4096;
-  std::mutex mu;
-  std::condition_variable cv;
-  std::deque<Req *> pending;
-  std::vector<Lane> lanes;
-  uint64_t pooled_calls = 0, engine_calls = 0, solo_calls = 0;  // statistics
-  uint32_t largest_pool_calls = 0, largest_pool_proofs = 0;
-  uint64_t openings_calls = 0, both_kinds_calls = 0;  // requests of bpp_prove_pool_openings; pooled engine calls that held both kinds
+  lanes::LeaderPool<Lane, Req> pool;  // the leader protocol (lanes_host.h); a request's weight is its number of proofs
+  std::atomic<uint64_t> openings_calls{0}, both_kinds_calls{0};  // requests of bpp_prove_pool_openings; pooled engine calls that held both kinds
+  bpp_prove_pool(std::vector<Lane> lanes, uint32_t max_wait_us, uint32_t max_calls) : pool(std::move(lanes), max_wait_us, max_calls, 4096) {}
 };
 
 namespace {
@@ -59,9 +51,9 @@ namespace {
 // A call of more than max_proofs items is a large call by itself, and one whose stride is too short for one of its proofs, or
 // whose arguments are missing, gets its answer from a call of its own: all go through bpp_prove_batch_mixed (bpp_prove_openings
 // for a request of that kind) directly.
-bool prove_pool_poolable(const bpp_prove_pool *p, const bpp_prove_pool::Req *r) {
+bool prove_pool_poolable(const bpp_prove_pool *p, uint32_t max_proofs, const bpp_prove_pool::Req *r) {
   if (r->openings && !r->commitments_out) return false;
-  if (!r->items || r->n_items == 0 || !r->proofs_out || !r->proof_lens || r->n_items > p->max_proofs) return false;
+  if (!r->items || r->n_items == 0 || !r->proofs_out || !r->proof_lens || r->n_items > max_proofs) return false;
   for (size_t i = 0; i < r->n_items; i++)
     if (r->proof_stride < prove_item_len(*p->P, r->items[i].m)) return false;
   return true;
@@ -95,8 +87,9 @@ void prove_pool_run(bpp_prove_pool *p, bpp_prove_pool::Lane &L, const std::vecto
     L.commit_slots.assign(n, nullptr);
     L.commit_caps.assign(n, 0);
     size_t at = 0;
-    bool any_openings = false;
+    bool any_openings = false, any_without = false;
     for (auto *r : reqs) {
+      any_without = any_without || !r->openings;
       std::copy(r->items, r->items + r->n_items, L.items.begin() + (ptrdiff_t)at);
       for (size_t i = 0; r->openings && i < r->n_items; i++) {
         L.commit_slots[at + i] = r->commitments_out + i * r->commit_stride;
@@ -105,6 +98,7 @@ void prove_pool_run(bpp_prove_pool *p, bpp_prove_pool::Lane &L, const std::vecto
       }
       at += r->n_items;
     }
+    if (any_openings && any_without) p->both_kinds_calls++;
     MixedOutcome out;
     {
       std::lock_guard<std::mutex> lk(L.ctx->mu);
@@ -142,10 +136,9 @@ void prove_pool_run(bpp_prove_pool *p, bpp_prove_pool::Lane &L, const std::vecto
   } catch (const ProofErr &e) {
     for (auto *r : reqs) prove_pool_solo(p, L, r);
   } catch (const std::exception &e) {
-    for (auto *r : reqs) {
-      r->code = BPP_ERR_ENGINE;
-      r->msg = std::string("prove pool: ") + e.what();
-    }
+    fail_requests(reqs, std::string("prove pool: ") + e.what());
+  } catch (...) {
+    fail_requests(reqs, "prove pool: unexpected failure");
   }
 }
 
@@ -160,83 +153,50 @@ int bpp_prove_pool_create(bpp_ctx *ctx, uint64_t params, uint32_t lanes, uint32_
   if (!Pp || Pp->device != ctx->device) return BPP_ERR_BAD_HANDLE;
   if (lanes == 0) lanes = 2;
   if (lanes > 8) lanes = 8;
-  auto p = std::make_unique<bpp_prove_pool>();
+  std::vector<bpp_prove_pool::Lane> made;
+  // the knobs of the caller's context, as they are when the pool is made, hold on every lane
+  const int rc = make_pool_lanes(ctx, params, lanes, [](bpp_ctx *c, const bpp_ctx::Options &opt) { c->opt = opt; }, made);
+  if (rc != BPP_OK) return rc;
+  auto p = std::make_unique<bpp_prove_pool>(std::move(made), max_wait_us, max_calls ? max_calls : 64);
   p->params = params;
   p->P = Pp;
   p->plen_max = prove_item_len(*Pp, Pp->m_max);
-  p->max_wait_us = max_wait_us;
-  if (max_calls) p->max_calls = max_calls;
-  p->lanes.resize(lanes);
-  for (uint32_t i = 0; i < lanes; i++) {
-    if (i == 0) {
-      p->lanes[i].ctx = ctx;
-    } else {
-      bpp_ctx *c = nullptr;
-      int rc = bpp_ctx_create(&c, ctx->device);
-      if (rc == BPP_OK) rc = bpp_params_retain(c, params);
-      if (rc != BPP_OK) {
-        if (c) bpp_ctx_destroy(c);
-        for (uint32_t j = 1; j < i; j++) bpp_ctx_destroy(p->lanes[j].ctx);
-        return rc;
-      }
-      {  // the knobs of the caller's context, as they are when the pool is made, hold on every lane
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        c->opt = ctx->opt;
-      }
-      p->lanes[i].ctx = c;
-      p->lanes[i].own = true;
-    }
-  }
   *out = p.release();
   return BPP_OK;
 }
 
 int bpp_prove_pool_set_limits(bpp_prove_pool *p, uint32_t max_calls, uint32_t max_proofs) {
   if (!p) return BPP_ERR_BAD_HANDLE;
-  std::lock_guard<std::mutex> lk(p->mu);
-  if (max_calls) p->max_calls = max_calls;
-  if (max_proofs) p->max_proofs = max_proofs;
+  p->pool.set_limits(max_calls, max_proofs);
   return BPP_OK;
 }
 
 int bpp_prove_pool_stats(bpp_prove_pool *p, uint64_t *pooled_calls, uint64_t *engine_calls, uint64_t *solo_calls, uint32_t *largest_calls,
                          uint32_t *largest_proofs) {
   if (!p) return BPP_ERR_BAD_HANDLE;
-  std::lock_guard<std::mutex> lk(p->mu);
-  if (pooled_calls) *pooled_calls = p->pooled_calls;
-  if (engine_calls) *engine_calls = p->engine_calls;
-  if (solo_calls) *solo_calls = p->solo_calls;
-  if (largest_calls) *largest_calls = p->largest_pool_calls;
-  if (largest_proofs) *largest_proofs = p->largest_pool_proofs;
+  const lanes::PoolStats s = p->pool.stats();
+  if (pooled_calls) *pooled_calls = s.pooled_calls;
+  if (engine_calls) *engine_calls = s.engine_calls;
+  if (solo_calls) *solo_calls = s.solo_calls;
+  if (largest_calls) *largest_calls = s.largest_pool_calls;
+  if (largest_proofs) *largest_proofs = s.largest_pool_weight;
   return BPP_OK;
 }
 
 int bpp_prove_pool_check_stats(bpp_prove_pool *p, struct bpp_prove_check_stats *out) {
   if (!p || !out) return BPP_ERR_BAD_HANDLE;
   memset(out, 0, sizeof(*out));
-  for (auto &L : p->lanes) {  // (the lanes are fixed once the pool exists)
-    struct bpp_prove_check_stats s;
-    const int rc = bpp_prove_check_stats(L.ctx, &s);
-    if (rc != BPP_OK) return rc;
-    out->calls += s.calls;
-    out->proofs += s.proofs;
-    out->batch_failures += s.batch_failures;
-    out->remade += s.remade;
-    out->failed += s.failed;
-  }
-  return BPP_OK;
+  int rc = BPP_OK;
+  p->pool.for_each_lane([&](bpp_prove_pool::Lane &L) { rc = rc == BPP_OK ? add_check_stats(L.ctx, *out) : rc; });
+  return rc;
 }
 
 int bpp_prove_pool_check_recovery_stats(bpp_prove_pool *p, uint64_t *replayed, uint64_t *mismatched) {
   if (!p) return BPP_ERR_BAD_HANDLE;
   uint64_t r = 0, m = 0;
-  for (auto &L : p->lanes) {
-    uint64_t lr = 0, lm = 0;
-    const int rc = bpp_prove_check_recovery_stats(L.ctx, &lr, &lm);
-    if (rc != BPP_OK) return rc;
-    r += lr;
-    m += lm;
-  }
+  int rc = BPP_OK;
+  p->pool.for_each_lane([&](bpp_prove_pool::Lane &L) { rc = rc == BPP_OK ? add_recovery_stats(L.ctx, r, m) : rc; });
+  if (rc != BPP_OK) return rc;
   if (replayed) *replayed = r;
   if (mismatched) *mismatched = m;
   return BPP_OK;
@@ -244,105 +204,34 @@ int bpp_prove_pool_check_recovery_stats(bpp_prove_pool *p, uint64_t *replayed, u
 
 void bpp_prove_pool_destroy(bpp_prove_pool *p) {
   if (!p) return;
-  {
-    std::unique_lock<std::mutex> lk(p->mu);
-    p->cv.wait(lk, [&] {
-      for (auto &L : p->lanes)
-        if (L.busy) return false;
-      return p->pending.empty();
-    });
-  }
-  for (auto &L : p->lanes)
+  p->pool.drain();
+  p->pool.for_each_lane([](bpp_prove_pool::Lane &L) {
     if (L.own) bpp_ctx_destroy(L.ctx);
+  });
   delete p;
 }
 
 }  // extern "C"
 
 namespace {
-// one request through the pool (bpp_prove_pool_prove, bpp_prove_pool_openings): blocks until its outcome is there
-int prove_pool_submit(bpp_prove_pool *p, bpp_prove_pool::Req &me, char *errbuf, size_t errbuf_len) {
-  const size_t n_items = me.n_items;
-  std::vector<bpp_prove_pool::Req *> mine;
-  bpp_prove_pool::Lane *lane = nullptr;
-  {
-    std::unique_lock<std::mutex> lk(p->mu);
-    const bool poolable = prove_pool_poolable(p, &me);
-    if (me.openings) p->openings_calls++;
-    if (poolable) {
-      p->pending.push_back(&me);
-      p->cv.notify_all();  // (a leader waiting for company counts the queue)
-    }
-    auto free_lane = [&]() -> bpp_prove_pool::Lane * {
-      for (auto &L : p->lanes)
-        if (!L.busy) return &L;
-      return nullptr;
-    };
-    // wait until somebody else has dealt with this request, or -- as long as nobody has taken it -- a lane is free and this
-    // thread leads the next pooled call
-    p->cv.wait(lk, [&] { return me.done || (!me.taken && free_lane() != nullptr); });
-    if (me.done) {
-      set_err(errbuf, errbuf_len, me.msg);
-      return me.code;
-    }
-    lane = free_lane();
-    lane->busy = true;
-    if (poolable) {
-      if (p->max_wait_us && p->pending.size() < p->max_calls)
-        p->cv.wait_for(lk, std::chrono::microseconds(p->max_wait_us), [&] { return me.taken || p->pending.size() >= p->max_calls; });
-      if (me.taken) {  // another leader took this thread's request while it waited for company: let that one finish it
-        lane->busy = false;
-        p->cv.notify_all();
-        p->cv.wait(lk, [&] { return me.done; });
-        set_err(errbuf, errbuf_len, me.msg);
-        return me.code;
-      }
-      // the leader's own request first, then whatever is queued, oldest first, within max_calls requests and max_proofs proofs;
-      // requests that do not fit stay where they are, for the next leader
-      for (auto it = p->pending.begin(); it != p->pending.end(); ++it)
-        if (*it == &me) {
-          p->pending.erase(it);
-          break;
-        }
-      me.taken = true;
-      mine.push_back(&me);
-      size_t proofs = n_items;
-      for (auto it = p->pending.begin(); it != p->pending.end() && mine.size() < p->max_calls;) {
-        bpp_prove_pool::Req *r = *it;
-        if (proofs + r->n_items > p->max_proofs) {
-          ++it;
-          continue;
-        }
-        proofs += r->n_items;
-        r->taken = true;
-        mine.push_back(r);
-        it = p->pending.erase(it);
-      }
-    } else {
-      mine.push_back(&me);
-    }
-    p->engine_calls++;
-    if (mine.size() > 1) {
-      p->pooled_calls += mine.size();
-      size_t proofs = 0;
-      for (auto *r : mine) proofs += r->n_items;
-      p->largest_pool_calls = std::max(p->largest_pool_calls, (uint32_t)mine.size());
-      p->largest_pool_proofs = std::max(p->largest_pool_proofs, (uint32_t)proofs);
-      bool with = false, without = false;
-      for (auto *r : mine) (r->openings ? with : without) = true;
-      if (with && without) p->both_kinds_calls++;
-    } else {
-      p->solo_calls++;
-    }
-  }
-  prove_pool_run(p, *lane, mine);
-  {
-    std::lock_guard<std::mutex> lk(p->mu);
-    for (auto *r : mine)
-      if (r != &me) r->done = true;  // (`me` lives on this stack and is always part of `mine`)
-    lane->busy = false;
-  }
-  p->cv.notify_all();
+// one request through the pool: blocks until its outcome is there.  `openings`: the request's items may come without commitments
+int prove_pool_submit(bpp_prove_pool *p, bool openings, const bpp_prove_item *items, size_t n_items, uint8_t *commitments_out, size_t commit_stride,
+                      uint8_t *proofs_out, size_t proof_stride, size_t *proof_lens, char *errbuf, size_t errbuf_len) {
+  if (!p) return BPP_ERR_BAD_HANDLE;
+  bpp_prove_pool::Req me;
+  me.items = items;
+  me.n_items = n_items;
+  me.proofs_out = proofs_out;
+  me.proof_stride = proof_stride;
+  me.proof_lens = proof_lens;
+  me.openings = openings;
+  me.commitments_out = commitments_out;
+  me.commit_stride = commit_stride;
+  if (openings) p->openings_calls++;
+  p->pool.serve(
+      me, [&](uint32_t max_proofs) { return prove_pool_poolable(p, max_proofs, &me); }, [](const bpp_prove_pool::Req &r) { return r.n_items; },
+      [](const bpp_prove_pool::Req &, const bpp_prove_pool::Req &) { return true; },
+      [&](bpp_prove_pool::Lane &L, const std::vector<bpp_prove_pool::Req *> &reqs) { prove_pool_run(p, L, reqs); });
   set_err(errbuf, errbuf_len, me.msg);
   return me.code;
 }
@@ -352,36 +241,18 @@ extern "C" {
 
 int bpp_prove_pool_prove(bpp_prove_pool *p, const bpp_prove_item *items, size_t n_items, uint8_t *proofs_out, size_t proof_stride,
                          size_t *proof_lens, char *errbuf, size_t errbuf_len) {
-  if (!p) return BPP_ERR_BAD_HANDLE;
-  bpp_prove_pool::Req me;
-  me.items = items;
-  me.n_items = n_items;
-  me.proofs_out = proofs_out;
-  me.proof_stride = proof_stride;
-  me.proof_lens = proof_lens;
-  return prove_pool_submit(p, me, errbuf, errbuf_len);
+  return prove_pool_submit(p, false, items, n_items, nullptr, 0, proofs_out, proof_stride, proof_lens, errbuf, errbuf_len);
 }
 
 int bpp_prove_pool_openings(bpp_prove_pool *p, const bpp_prove_item *items, size_t n_items, uint8_t *commitments_out, size_t commit_stride,
                             uint8_t *proofs_out, size_t proof_stride, size_t *proof_lens, char *errbuf, size_t errbuf_len) {
-  if (!p) return BPP_ERR_BAD_HANDLE;
-  bpp_prove_pool::Req me;
-  me.items = items;
-  me.n_items = n_items;
-  me.proofs_out = proofs_out;
-  me.proof_stride = proof_stride;
-  me.proof_lens = proof_lens;
-  me.openings = true;
-  me.commitments_out = commitments_out;
-  me.commit_stride = commit_stride;
-  return prove_pool_submit(p, me, errbuf, errbuf_len);
+  return prove_pool_submit(p, true, items, n_items, commitments_out, commit_stride, proofs_out, proof_stride, proof_lens, errbuf, errbuf_len);
 }
 
 int bpp_prove_pool_openings_stats(bpp_prove_pool *p, uint64_t *openings_calls, uint64_t *both_kinds_calls) {
   if (!p) return BPP_ERR_BAD_HANDLE;
-  std::lock_guard<std::mutex> lk(p->mu);
-  if (openings_calls) *openings_calls = p->openings_calls;
-  if (both_kinds_calls) *both_kinds_calls = p->both_kinds_calls;
+  if (openings_calls) *openings_calls = p->openings_calls.load();
+  if (both_kinds_calls) *both_kinds_calls = p->both_kinds_calls.load();
   return BPP_OK;
 }
 
