@@ -121,6 +121,21 @@ def build_lanes_harness(kind, force=False):
     return exe
 
 
+CT_SANITIZER_BIN = os.path.join(HERE, "hosttest_ct_asan")
+
+
+def build_ct_harness(force=False):
+    """hosttest_ct.cpp (ct.h: the one-lane model of the constant-time multiscalar multiplication; ct_plan.h: its chunk planner)
+    under ASan + UBSan: an executable, run by tests/test_msm_ct_host.py."""
+    src = os.path.join(CSRC, "hosttest_ct.cpp")
+    deps = [src, os.path.join(CSRC, "hosttest.cpp")] + [os.path.join(CSRC, h) for h in HEADERS]
+    if not force and not _stale(CT_SANITIZER_BIN, deps):
+        return CT_SANITIZER_BIN
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-fno-omit-frame-pointer", "-o", CT_SANITIZER_BIN, src], check=True, cwd=CSRC)
+    return CT_SANITIZER_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     build_hosttest(force="--force" in sys.argv)

@@ -90,6 +90,9 @@ SYMBOLS = [
     ("bpp_msm_vartime", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     ("bpp_msm_vartime_batched", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     ("bpp_msm_last_plan", c_int, [c_void_p, c_void_p]),
+    ("bpp_msm_ct", c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("bpp_msm_ct_batched", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    ("bpp_msm_ct_secret_bytes", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
     ("bpp_params_create", c_int, [c_void_p, c_uint32, c_uint32, c_uint32, c_void_p, c_void_p, POINTER(c_uint64)]),
     ("bpp_params_destroy", c_int, [c_void_p, c_uint64]),
     ("bpp_params_retain", c_int, [c_void_p, c_uint64]),

@@ -142,6 +142,30 @@ class Engine:
         raw = bytes(out)
         return [raw[32 * i:32 * i + 32] for i in range(g)]
 
+    def msm_ct(self, scalars, points):
+        """P::multiscalar_mul(scalars, points) -> compressed point: constant-time in the scalars (bpp_msm_ct)"""
+        assert len(scalars) == len(points)
+        out = (ctypes.c_uint8 * 32)()
+        rc = self.lib.bpp_msm_ct(self.ctx, _buf(b"".join(scalars)), _buf(b"".join(points)), len(scalars), out)
+        _check(rc, self.ctx)
+        return bytes(out)
+
+    def msm_ct_batched(self, scalars, points, group_off):
+        """bpp_msm_ct_batched: group g = terms [group_off[g], group_off[g + 1]) -> one compressed point per group"""
+        g = len(group_off) - 1
+        out = (ctypes.c_uint8 * (32 * g))()
+        go = (c_uint32 * len(group_off))(*group_off)
+        rc = self.lib.bpp_msm_ct_batched(self.ctx, _buf(b"".join(scalars)), _buf(b"".join(points)), go, g, out)
+        _check(rc, self.ctx)
+        raw = bytes(out)
+        return [raw[32 * i:32 * i + 32] for i in range(g)]
+
+    def msm_ct_secret_bytes(self):
+        """bpp_msm_ct_secret_bytes: (bytes of the constant-time MSM's secret-bearing buffers looked at, how many were not zero)"""
+        seen, cnt = c_uint64(), c_uint64()
+        _check(self.lib.bpp_msm_ct_secret_bytes(self.ctx, byref(seen), byref(cnt)), self.ctx)
+        return int(seen.value), int(cnt.value)
+
     def precomputation(self, static_points):
         return Precomputation(self, static_points)
 
@@ -152,7 +176,7 @@ class Engine:
         form = int(w[6])
         return {"c": int(w[0]), "K": int(w[1]), "K_wide": int(w[2]), "nb": int(w[3]), "G": int(w[4]), "terms": int(w[5]),
                 "quad": bool(form & 1), "reduce": ("rc_quad", "rc2", "rc", "bitsum")[(form >> 1) & 3], "final_quad": bool(form & 8),
-                "narrow_prelude": bool(form & 16), "plain": bool(form & 32), "form": form, "dig_cap": int(w[7])}
+                "narrow_prelude": bool(form & 16), "plain": bool(form & 32), "ct": bool(form & 64), "form": form, "dig_cap": int(w[7])}
 
     def profile(self, on=True):
         """bpp_profile_enable: False / 0 off, True / 1 an event at every stage boundary, 2 the roofline kernel's two events only"""

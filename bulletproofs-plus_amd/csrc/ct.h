@@ -14,10 +14,12 @@
 // BPP_CT_TOUCH in a host build and compares two scalars' traces), and so is the instruction stream.
 //
 // On the device one term runs on one QUAD (msm.h: lane q of the quad holds coordinate q of the accumulator, a doubling or an
-// addition is two rounds of four field products), a workgroup of 64 lanes sums up to 16 terms of one output.
+// addition is two rounds of four field products); k_ct_straus gives a quad K terms and one accumulator, a workgroup of 64 lanes
+// sums up to 16 K terms of one output.
 #pragma once
 #include "point.h"
 #include "scalar.h"
+#include "ct_plan.h"
 #if defined(__HIPCC__)
 #include "msm.h"  // the quad forms of the point operations
 #endif
@@ -47,8 +49,10 @@ BPP_HD void ct_recode16(int8_t d[BPP_CT_DIGITS], const sc &s) {
 
 // out[0..N) = the row that holds multiple `mag`, rows = multiples first, first + 1, .., first + E - 1 (zero when mag is none of
 // them): EVERY row is read, one is kept.  `table` = E rows of `row_stride` words.
+// Word k of a row lies `word_stride` words after word k - 1 (1: a row is contiguous).
 template <int N, int E = BPP_CT_ENTRIES>
-BPP_HD void ct_select_words(uint32_t (&out)[N], const uint32_t *table, uint32_t row_stride, uint32_t mag, uint32_t first = 0) {
+BPP_HD void ct_select_words(uint32_t (&out)[N], const uint32_t *table, uint32_t row_stride, uint32_t mag, uint32_t first = 0,
+                            uint32_t word_stride = 1) {
 #pragma unroll
   for (int k = 0; k < N; k++) out[k] = 0;
 #pragma unroll
@@ -56,7 +60,7 @@ BPP_HD void ct_select_words(uint32_t (&out)[N], const uint32_t *table, uint32_t 
     BPP_CT_TOUCH(j);
     const uint32_t keep = 0u - ((((j + first) ^ mag) - 1u) >> 31);  // all ones iff j + first == mag (the xor is < 2^31)
 #pragma unroll
-    for (int k = 0; k < N; k++) out[k] |= table[(size_t)j * row_stride + k] & keep;
+    for (int k = 0; k < N; k++) out[k] |= table[(size_t)j * row_stride + (size_t)k * word_stride] & keep;
   }
 }
 
@@ -203,6 +207,86 @@ BPP_HD void ct_var_scalarmul(ge &r, const ge &p, const sc &s) {
   r = acc;
 }
 
+// ---- MANY terms with secret scalars over the caller's own points (seam B1's MultiscalarMul::multiscalar_mul, bpp_msm_ct): Straus.
+// Per term the multiples 1 P .. 8 P (carried limbs; made by additions of a PUBLIC point), per digit position four doublings of ONE
+// accumulator shared by the terms, then one addition per term of the entry its digit names: all eight entries read, one kept
+// under a mask, a zero digit keeps none and becomes the neutral element (0, 1, 1, 0) by a mask as well, the sign is a select.
+#define BPP_CTS_ENTRIES 8  // 1 P .. 8 P
+// coordinate `coord` (0..3 = X, Y, Z, T; public) of the signed entry that `digit` names.  table = word 0 of that coordinate of entry 1 P,
+// the entries `row_stride` words apart, a coordinate's limbs `word_stride` apart.
+BPP_HD void ct_straus_coord(fe &out, const uint32_t *table, uint32_t row_stride, uint32_t word_stride, int32_t digit, uint32_t coord) {
+  uint32_t mag, neg;
+  ct_digit_parts(mag, neg, digit);
+  uint32_t w[10];
+  ct_select_words<10, BPP_CTS_ENTRIES>(w, table, row_stride, mag, 1, word_stride);
+  const uint32_t isz = (mag - 1u) >> 31;                                     // 1 iff the digit is zero
+  const uint32_t yz = (((coord ^ 1u) - 1u) | ((coord ^ 2u) - 1u)) >> 31;     // 1 iff the coordinate is Y or Z
+  w[0] |= isz & yz;
+  fe mine;
+#pragma unroll
+  for (int k = 0; k < 10; k++) mine.v[k] = w[k];
+  // -P = (-X, Y, Z, -T)
+  const uint32_t xt = (((coord ^ 0u) - 1u) | ((coord ^ 3u) - 1u)) >> 31;     // 1 iff the coordinate is X or T
+  fe_cneg_select(out, mine, neg & xt);
+}
+// one lane's model of the whole sum (host probe, and the definition k_ct_straus is held to): blocks of 16 terms, each block one
+// accumulator, the blocks' sums added in order.  n = 0: the neutral element.
+#define BPP_CTS_MODEL_BLOCK 16
+BPP_HD void ct_straus_model(ge &r, const ge *pts, const sc *scal, uint32_t n) {
+  ge total;
+  ge_identity(total);
+  uint32_t tab[BPP_CTS_MODEL_BLOCK][BPP_CTS_ENTRIES][4][10];  // [term][entry][coordinate][limb]
+  int8_t dig[BPP_CTS_MODEL_BLOCK][BPP_CT_DIGITS];
+  for (uint32_t at = 0; at < n; at += BPP_CTS_MODEL_BLOCK) {
+    const uint32_t cnt = n - at < BPP_CTS_MODEL_BLOCK ? n - at : BPP_CTS_MODEL_BLOCK;
+    for (uint32_t t = 0; t < cnt; t++) {
+      ge m = pts[at + t];
+      for (int j = 0; j < BPP_CTS_ENTRIES; j++) {
+        if (j) ge_add(m, m, pts[at + t]);
+        ge c = m;
+        fe_carry(c.X);
+        fe_carry(c.Y);
+        fe_carry(c.Z);
+        fe_carry(c.T);
+        for (int k = 0; k < 10; k++) {
+          tab[t][j][0][k] = c.X.v[k];
+          tab[t][j][1][k] = c.Y.v[k];
+          tab[t][j][2][k] = c.Z.v[k];
+          tab[t][j][3][k] = c.T.v[k];
+        }
+      }
+      ct_recode16(dig[t], scal[at + t]);
+    }
+    ge acc;
+    ge_identity(acc);
+    for (int i = BPP_CT_DIGITS - 1; i >= 0; i--) {
+      if (i != BPP_CT_DIGITS - 1)
+        for (int k = 0; k < 4; k++) ge_dbl(acc, acc);
+      for (uint32_t t = 0; t < cnt; t++) {
+        ge q;
+        ct_straus_coord(q.X, &tab[t][0][0][0], 40, 1, (int32_t)dig[t][i], 0);
+        ct_straus_coord(q.Y, &tab[t][0][1][0], 40, 1, (int32_t)dig[t][i], 1);
+        ct_straus_coord(q.Z, &tab[t][0][2][0], 40, 1, (int32_t)dig[t][i], 2);
+        ct_straus_coord(q.T, &tab[t][0][3][0], 40, 1, (int32_t)dig[t][i], 3);
+        ge_add(acc, acc, q);
+      }
+    }
+    ge_add(total, total, acc);
+  }
+  // the digits are secret-derived (volatile stores: a plain loop over a dying array is dropped)
+  for (size_t k = 0; k < sizeof(dig); k++) ((volatile int8_t *)dig)[k] = 0;
+  r = total;
+}
+
+// the canonicity of a scalar without a branch or an early exit: 1 iff s < l, by the borrow of s - l over the eight words
+BPP_HD uint32_t ct_sc_is_canonical(const sc &s) {
+  const uint32_t l[8] = {BPP_L0, BPP_L1, BPP_L2, BPP_L3, BPP_L4, BPP_L5, BPP_L6, BPP_L7};
+  uint64_t borrow = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) borrow = (((uint64_t)s.v[i] - l[i] - borrow) >> 63) & 1u;
+  return (uint32_t)borrow;
+}
+
 #if defined(__HIPCC__)
 #define CTF_MAX_TERMS 8
 struct CtFixedShared {
@@ -318,61 +402,65 @@ __global__ void __launch_bounds__(64) k_ct_sum(const ge *__restrict__ prod, uint
   acc[(size_t)acc_stride * p] = x;
 }
 
-#define CT_MAX_TERMS 16
-struct CtShared {
-  uint32_t tab[CT_MAX_TERMS][BPP_CT_ENTRIES][4][10];  // [term][entry][coordinate][limb]
-  int8_t dig[CT_MAX_TERMS][BPP_CT_DIGITS];
-  ge part[CT_MAX_TERMS];
+// ---- the constant-time multiscalar multiplication of seam B1 (bpp_msm_ct): one chunk (ct_plan.h) of one output per workgroup of
+// 64 lanes.  Quad t owns the terms t, 16 + t, .. (K of them at most: its SLOTS) of the chunk and ONE accumulator: per digit position
+// four doublings, shared by the K terms, then K additions of selected entries (ct_straus_coord) -- what ct_straus_model does for
+// the terms of a quad.  A slot beyond the chunk's count (public) runs the same instruction stream on the chunk's first scalar with
+// the neutral element for its point, and so adds nothing.
+//
+// LDS layout: the lane is the FASTEST index of the table, tab[slot][entry][limb][lane].  Every lane reads its own coordinate of
+// its own quad's term, all lanes the same (entry, limb) at a time: the 32 lanes that share an LDS cycle of a ds_read_b32 read 32
+// consecutive words, one per bank -- no conflict, for the 80 reads of every addition.  The digits lie
+// [slot][position][quad]: the 16 quads read 16 adjacent bytes, four words, each a broadcast.
+// K = 1: 20 KB of table, 24 KB in all; K = 2: 40 KB of table, 45 KB in all.
+template <int K>
+struct CtStrausShared {
+  uint32_t tab[K][BPP_CTS_ENTRIES][10][64];
+  int8_t dig[K][BPP_CT_DIGITS][BPP_CT_QUADS];
+  ge part[BPP_CT_QUADS];
 };
-
-// out[o] = sum_{i < count[o]} scal[o][i] * point(tidx[o][i]),  count[o] <= CT_MAX_TERMS; one workgroup of 64 lanes per output, one
-// quad per term.  point(idx) = dyn[idx & 0x7fffffff] when bit 31 is set (a per-call point in extended coordinates), else the
-// affine-Niels table line bases[idx] (the parameter set's generator table: Pedersen bases at n_gen + k, H at n_gen + t).
-#define BPP_CT_DYN 0x80000000u
-__global__ void __launch_bounds__(64) k_ct_msm(const sc *__restrict__ scal, const uint32_t *__restrict__ tidx,
-                                               const uint32_t *__restrict__ count, uint32_t stride, const niels *__restrict__ bases,
-                                               const ge *__restrict__ dyn, ge *__restrict__ out) {
-  const uint32_t o = blockIdx.x, lane = threadIdx.x, qi = lane & 3u, term = lane >> 2;
+// part[c] = sum over the terms i of chunk c of scal[i] * pts[i]; pts = affine Niels entries (k_decompress_plain)
+template <int K>
+__global__ void __launch_bounds__(64) k_ct_straus(const sc *__restrict__ scal, const niels *__restrict__ pts,
+                                                  const CtChunk *__restrict__ plan, ge *__restrict__ part) {
+  static_assert(K >= 1 && K <= BPP_CT_K_MAX, "kernel form");
+  static_assert(sizeof(CtStrausShared<K>) <= 64 * 1024, "static LDS of one workgroup");
+  const uint32_t lane = threadIdx.x, qi = lane & 3u, quad = lane >> 2;
   const QuadMask q = quad_mask(qi);
-  const uint32_t n = count[o] < CT_MAX_TERMS ? count[o] : CT_MAX_TERMS;
-  __shared__ CtShared sh;
-  const bool active = term < n;  // (idle quads run the same instruction stream on the output's first term and write nothing)
-  const uint32_t it = active ? term : 0u;
-  const uint32_t idx = tidx[(size_t)o * stride + it];
-  ge p;
-  if (idx & BPP_CT_DYN) {
-    p = dyn[idx & ~BPP_CT_DYN];
-  } else {
-    const niels b = bases[idx];
-    ge_from_niels(p, b);
-  }
+  const CtChunk ch = plan[blockIdx.x];
+  __shared__ CtStrausShared<K> sh;
   fe d2, one;
   fe_const(d2, FE_D2);
   fe_1(one);
-  // table 0 P .. 8 P, every entry's coordinate qi written by lane qi with carried limbs
-  auto store_entry = [&](uint32_t j, const fe &m) {
-    fe c = m;
-    fe_carry(c);
-#pragma unroll
-    for (int k = 0; k < 10; k++) sh.tab[term][j][qi][k] = c.v[k];
-  };
   fe m;
-  {
-    ge id;
-    ge_identity(id);
-    quad_load(m, q, id);
-    store_entry(0, m);
-  }
-  quad_load(m, q, p);
-  store_entry(1, m);
 #pragma unroll 1
-  for (uint32_t j = 2; j < BPP_CT_ENTRIES; j++) {
-    quad_ge_add(m, q, p, d2, one);
-    store_entry(j, m);
-  }
-  if (qi == 0) {
-    const sc s = scal[(size_t)o * stride + it];
-    ct_recode16(sh.dig[term], s);
+  for (uint32_t s = 0; s < (uint32_t)K; s++) {
+    const uint32_t idx = s * BPP_CT_QUADS + quad;
+    const bool active = idx < ch.count;  // (public)
+    const uint32_t term = ch.first + (active ? idx : 0u);
+    ge p;
+    {
+      const niels b = pts[term];
+      ge_from_niels(p, b);
+    }
+    if (!active) ge_identity(p);
+    // multiples 1 P .. 8 P by public additions, coordinate qi of every entry written by lane qi with carried limbs
+    quad_load(m, q, p);
+#pragma unroll 1
+    for (uint32_t j = 0; j < BPP_CTS_ENTRIES; j++) {
+      if (j) quad_ge_add(m, q, p, d2, one);
+      fe c = m;
+      fe_carry(c);
+#pragma unroll
+      for (int k = 0; k < 10; k++) sh.tab[s][j][k][lane] = c.v[k];
+    }
+    if (qi == 0) {
+      const sc sv = scal[term];
+      int8_t d[BPP_CT_DIGITS];
+      ct_recode16(d, sv);
+#pragma unroll
+      for (int i = 0; i < BPP_CT_DIGITS; i++) sh.dig[s][i][quad] = d[i];
+    }
   }
   __syncthreads();
   {
@@ -386,45 +474,69 @@ __global__ void __launch_bounds__(64) k_ct_msm(const sc *__restrict__ scal, cons
 #pragma unroll 1
       for (int k = 0; k < 4; k++) quad_ge_dbl(m, q);
     }
-    uint32_t mag, neg;
-    ct_digit_parts(mag, neg, (int32_t)sh.dig[term][i]);
-    uint32_t w[10];
-    ct_select_words<10>(w, &sh.tab[term][0][qi][0], 40, mag);  // this lane's coordinate of ALL nine entries
-    fe mine, flipped;
-#pragma unroll
-    for (int k = 0; k < 10; k++) mine.v[k] = w[k];
-    fe_cneg_select(flipped, mine, neg);
-    // -P = (-X, Y, Z, -T): lanes 0 and 3 take the (possibly) negated coordinate; a select on the lane's position, not a branch
-    {
-      const uint32_t xt = 0u - (uint32_t)((qi == 0u) | (qi == 3u));
-#pragma unroll
-      for (int k = 0; k < 10; k++) mine.v[k] = (flipped.v[k] & xt) | (mine.v[k] & ~xt);
-    }
-    ge other;
-    quad_gather(other, mine);
-    quad_ge_add(m, q, other, d2, one);
-  }
-  {
-    ge acc;
-    quad_gather(acc, m);
-    if (qi == 0) sh.part[term] = acc;
-  }
-  __syncthreads();
-  if (term == 0) {  // the output's terms, summed by the first quad (count is public)
-    ge first = sh.part[0];
-    quad_load(m, q, first);
 #pragma unroll 1
-    for (uint32_t j = 1; j < n; j++) {
-      const ge pj = sh.part[j];
-      quad_ge_add(m, q, pj, d2, one);
+    for (uint32_t s = 0; s < (uint32_t)K; s++) {
+      fe mine;
+      ct_straus_coord(mine, &sh.tab[s][0][0][lane], 10u * 64u, 64u, (int32_t)sh.dig[s][i][quad], qi);
+      ge other;
+      quad_gather(other, mine);
+      quad_ge_add(m, q, other, d2, one);
     }
-    ge acc;
-    quad_gather(acc, m);
-    if (qi == 0) out[o] = acc;
   }
-  // the digits and the table of multiples are secret-derived: leave nothing in LDS for the next workgroup on this CU
+  // the 16 quads' sums by a tree of four levels (every quad takes part in every chunk: an idle one holds the neutral element)
+  ge acc;
+  quad_gather(acc, m);
+  if (qi == 0) sh.part[quad] = acc;
+#pragma unroll 1
+  for (uint32_t off = BPP_CT_QUADS / 2; off >= 1; off >>= 1) {
+    __syncthreads();
+    if (quad < off) {
+      const ge y2 = sh.part[quad + off];
+      quad_ge_add(m, q, y2, d2, one);
+      quad_gather(acc, m);
+      if (qi == 0) sh.part[quad] = acc;
+    }
+  }
+  if (lane == 0) part[blockIdx.x] = acc;
+  // digits, selected multiples and partial sums are secret-derived: leave nothing in LDS for the next workgroup on this CU
   __syncthreads();
-  for (uint32_t k = lane; k < sizeof(CtShared) / 4; k += 64) ((uint32_t *)&sh)[k] = 0;
+  for (uint32_t k = lane; k < sizeof(CtStrausShared<K>) / 4; k += 64) ((uint32_t *)&sh)[k] = 0;
+}
+
+// R[g] = the sum of the partial sums of group g's chunks, part[chunk_off[g]] .. part[chunk_off[g + 1] - 1], in an order that the
+// (public) chunk count alone decides: one workgroup per group, lane l adds the chunks l, l + 64, .., then a tree over the first
+// `span` lanes, span = the power of two that covers the count (one chunk, the commitment shape: no tree at all).  A group
+// without chunks gives the neutral element.
+struct CtSumShared {
+  ge red[64];
+};
+__global__ void __launch_bounds__(64) k_ct_straus_sum(const ge *__restrict__ part, const uint32_t *__restrict__ chunk_off,
+                                                      ge *__restrict__ R) {
+  const uint32_t g = blockIdx.x, lane = threadIdx.x;
+  const uint32_t lo = chunk_off[g], n = chunk_off[g + 1] - lo;
+  uint32_t span = 1;
+  while (span < n && span < 64u) span <<= 1;
+  __shared__ CtSumShared sh;
+  ge acc;
+  ge_identity(acc);
+  if (lane < n) acc = part[lo + lane];
+  for (uint32_t c = lane + 64u; c < n; c += 64u) {
+    const ge y2 = part[lo + c];
+    ge_add(acc, acc, y2);
+  }
+  sh.red[lane] = acc;
+  __syncthreads();
+  for (uint32_t off = span >> 1; off >= 1; off >>= 1) {
+    if (lane < off) {
+      ge x = sh.red[lane], y2 = sh.red[lane + off];
+      ge_add(x, x, y2);
+      sh.red[lane] = x;
+    }
+    __syncthreads();
+  }
+  if (lane == 0) R[g] = sh.red[0];
+  __syncthreads();
+  for (uint32_t k = lane; k < sizeof(CtSumShared) / 4; k += 64) ((uint32_t *)&sh)[k] = 0;  // partial sums are secret-derived
 }
 #endif
 

@@ -586,6 +586,7 @@ enum MsmReduce : uint32_t { MSM_RC_QUAD = 0, MSM_RC2 = 1, MSM_RC = 2, MSM_BITSUM
 struct MsmForm {
   bool valid = false;       // a B1 call or a verification has run an MSM on this context
   bool plain = false;       // msm_plain.h; nothing below applies
+  bool ct = false;          // ct.h: k_ct_straus (bpp_msm_ct); only G and terms apply
   bool quad = false;        // k_msm_accumulate_quad, else k_msm_accumulate
   MsmReduce reduce = MSM_RC_QUAD;
   bool final_quad = false;  // k_msm_final_quad, else k_msm_final
@@ -594,9 +595,28 @@ struct MsmForm {
   uint32_t c = 0, K = 0, K_wide = 0, nb = 0, G = 0, terms = 0;
 };
 
+// the work buffers of bpp_msm_ct / bpp_msm_ct_batched: kept between calls (a second call of the same size allocates nothing).
+// sc, part and pin_sc hold secrets during a call and are zero between calls (bpp_msm_ct_secret_bytes reads them back)
+struct CtMsmWork {
+  bool used = false;
+  DevBuf<sc> sc_dev;         // the scalars
+  DevBuf<ge> part;           // one partial sum per chunk
+  PinnedBuf<uint8_t> pin_sc; // the one host copy of the scalars: checked here, uploaded from here
+  DevBuf<niels> pts;
+  DevBuf<uint8_t> pts_in;
+  DevBuf<uint32_t> pts_bad;
+  DevBuf<CtChunk> plan;
+  DevBuf<uint32_t> chunk_off;
+  DevBuf<ge> R;
+  DevBuf<uint8_t> out32;
+  PinnedBuf<uint32_t> pin_plan;
+  PinnedBuf<uint8_t> pin_out;
+};
+
 struct bpp_ctx {
   int device = 0;
   MsmForm msm_form;
+  CtMsmWork ct_msm;
   hipStream_t stream = nullptr;
   bool own_stream = false;
   std::string err;
@@ -651,7 +671,7 @@ struct bpp_ctx {
   struct Options {
     int transcripts_wave = -1, tables_wave = -1, side_decompress = -1, msm_c_bias = -1, msm_c_max = -1, msm_c_add = -1, msm_rc2 = -1, msm_quad = -1, msm_final_quad = -1,
         fb_threads = -1, prove_subs = -1, msm_split = -1, fused_columns = -1, prove_prio = -1, prove_fused = -1, static_gemm = -1, lazy_columns = -1, ct = -1, prove_parts = -1, prove_waves = -1, prove_fifo = -1, chain = -1, chain_test_zero = 0, wait = -1, ct_back = -1, chain_inline = -1, wide_in_lanes = -1,
-        prove_check = -1, prove_check_recovery = -1, msm_plain = -1, verify_check = -1;
+        prove_check = -1, prove_check_recovery = -1, msm_plain = -1, verify_check = -1, msm_ct_k = -1;
   } opt;
   // "verify_check" = 1 (verify_flow): what the rechecks of this context's verifications have done; the prover's self-check runs
   // its verifications with the recheck off (verify_check_off > 0) -- a rejection there is already answered by a remake
@@ -767,6 +787,9 @@ const OptionName kOptions[] = {
     // 1: a group that a verification rejects on the device (tiers PASS1, PASS2, MSM) is verified once more under the complementary
     // kernel forms with the plain MSM, and a third time when the two disagree (verify_flow); 0 / -1: off
     {"verify_check", "BPP_VERIFY_CHECK", &bpp_ctx::Options::verify_check},
+    // the kernel form of bpp_msm_ct / bpp_msm_ct_batched: 1 / 2 terms per quad (k_ct_straus<K>); 0 / -1: the engine's rule, from
+    // the call's public counts (ct_plan.h: ct_form_rule)
+    {"msm_ct_k", "BPP_MSM_CT_K", &bpp_ctx::Options::msm_ct_k},
 };
 struct TamperName {
   const char *name;
@@ -1132,9 +1155,13 @@ void msm_plain_prepare(bpp_ctx *ctx, MsmWork &w, const std::vector<uint32_t> &si
 }
 
 // decompress `n` host points into a device niels table; returns number of bad encodings
-uint32_t decompress_to_device(bpp_ctx *ctx, const uint8_t *pts32, size_t n, niels *out) {
-  DevBuf<uint8_t> d_in;
-  DevBuf<uint32_t> d_bad;
+// (keep_in / keep_bad: buffers the caller keeps between calls, instead of two allocations per call)
+uint32_t decompress_to_device(bpp_ctx *ctx, const uint8_t *pts32, size_t n, niels *out, DevBuf<uint8_t> *keep_in = nullptr,
+                              DevBuf<uint32_t> *keep_bad = nullptr) {
+  DevBuf<uint8_t> own_in;
+  DevBuf<uint32_t> own_bad;
+  DevBuf<uint8_t> &d_in = keep_in ? *keep_in : own_in;
+  DevBuf<uint32_t> &d_bad = keep_bad ? *keep_bad : own_bad;
   d_in.alloc(n * 32);
   d_bad.alloc(1);
   HIP_CHECK(hipMemcpyAsync(d_in.p, pts32, n * 32, hipMemcpyHostToDevice, ctx->stream));
@@ -1196,6 +1223,102 @@ int msm_host_entry(bpp_ctx *ctx, const niels *tab_a, uint32_t n_a, const uint8_t
   hipLaunchKernelGGL(k_compress_ge, dim3(cdiv(G, 64)), dim3(64), 0, ctx->stream, w.R.p, G, w.comp32.p);
   HIP_CHECK(hipMemcpyAsync(out32, w.comp32.p, 32 * (goff.size() - 1), hipMemcpyDeviceToHost, ctx->stream));
   HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return BPP_OK;
+}
+
+// The constant-time MSM over host scalars and host points (bpp_msm_ct, bpp_msm_ct_batched).  PUBLIC: n, the group offsets, the
+// points, which error comes back.  SECRET: the scalars -- nothing here or in the kernels (ct.h) branches on them, addresses by
+// them, or sizes a launch by them; the chunk plan and the kernel form come from the offsets alone.  The scalars' one host copy
+// (page-locked), their device buffer and the chunks' partial sums are zeroed on every way out.
+int msm_ct_entry(bpp_ctx *ctx, const uint8_t *scalars32, const uint8_t *points32, size_t n, const uint32_t *group_off_in, size_t n_groups,
+                 uint8_t *out32) {
+  CtMsmWork &w = ctx->ct_msm;
+  if (n == 0 || n_groups == 0) {  // empty sum = identity; nothing is launched
+    for (size_t g = 0; g < (n_groups ? n_groups : 1); g++) memset(out32 + 32 * g, 0, 32);
+    return BPP_OK;
+  }
+  if (!scalars32 || !points32) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+  hipStream_t s = ctx->stream;
+  // a fresh allocation is zeroed once as a whole: bpp_msm_ct_secret_bytes reads all of it, and what hipMalloc hands out is not zero
+  auto fresh_zero = [&](auto &buf, size_t count) {
+    const void *before = buf.p;
+    buf.alloc(count);
+    if (buf.p != before) HIP_CHECK(hipMemsetAsync(buf.p, 0, buf.n * sizeof(*buf.p), s));
+  };
+  ScopeExit wipe_secrets{[&] {
+    // (on the call's own stream, then waited for: the next call's upload must not overtake them, and the staging is not zeroed
+    // under an upload that is still reading it)
+    if (w.sc_dev.p) (void)hipMemsetAsync(w.sc_dev.p, 0, w.sc_dev.n * sizeof(sc), s);
+    if (w.part.p) (void)hipMemsetAsync(w.part.p, 0, w.part.n * sizeof(ge), s);
+    (void)hipStreamSynchronize(s);
+    wipe(w.pin_sc.p, w.pin_sc.n);
+  }};
+  {
+    const void *before = w.pin_sc.p;
+    w.pin_sc.resize(n * 32);
+    if (w.pin_sc.p != before) memset(w.pin_sc.p, 0, w.pin_sc.n);
+  }
+  w.used = true;
+  memcpy(w.pin_sc.p, scalars32, n * 32);
+  // every scalar is looked at, ONE decision at the end
+  uint32_t all_canonical = 1;
+  for (size_t i = 0; i < n; i++) {
+    sc a;
+    sc_load_words(a, w.pin_sc.p + 32 * i);
+    all_canonical &= ct_sc_is_canonical(a);
+    wipe(&a, sizeof a);
+  }
+  if (!all_canonical) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "scalar is not canonical");
+  const uint32_t one_group[2] = {0u, (uint32_t)n};
+  const uint32_t *goff = group_off_in ? group_off_in : one_group;
+  uint32_t largest = 0;
+  uint64_t chunks_k1 = 0;
+  for (size_t g = 0; g < n_groups; g++) {
+    const uint32_t len = goff[g + 1] - goff[g];
+    largest = std::max(largest, len);
+    chunks_k1 += (len + BPP_CT_QUADS - 1) / BPP_CT_QUADS;
+  }
+  const uint32_t K = ct_form_rule(largest, chunks_k1, ctx->opt.msm_ct_k);
+  std::vector<CtChunk> chunks;
+  std::vector<uint32_t> chunk_off;
+  if (ct_chunk_plan(goff, n_groups, n, K, chunks, chunk_off) != 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "group offsets not monotone");
+  const uint32_t G = (uint32_t)n_groups, C = (uint32_t)chunks.size();
+  w.pts.alloc(n);
+  if (decompress_to_device(ctx, points32, n, w.pts.p, &w.pts_in, &w.pts_bad))
+    return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "point is not a canonical ristretto255 encoding");
+  fresh_zero(w.sc_dev, n);
+  fresh_zero(w.part, C);
+  w.plan.alloc(C);
+  w.chunk_off.alloc(G + 1);
+  w.R.alloc(G);
+  w.out32.alloc((size_t)G * 32);
+  w.pin_plan.resize((size_t)C * 3 + G + 1);
+  w.pin_out.resize((size_t)G * 32);
+  static_assert(sizeof(CtChunk) == 12, "three words per chunk");
+  memcpy(w.pin_plan.p, chunks.data(), (size_t)C * 12);
+  memcpy(w.pin_plan.p + (size_t)C * 3, chunk_off.data(), (size_t)(G + 1) * 4);
+  HIP_CHECK(hipMemcpyAsync(w.sc_dev.p, w.pin_sc.p, n * 32, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(w.plan.p, w.pin_plan.p, (size_t)C * 12, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(w.chunk_off.p, w.pin_plan.p + (size_t)C * 3, (size_t)(G + 1) * 4, hipMemcpyHostToDevice, s));
+  if (C) {
+    if (K == 1)
+      hipLaunchKernelGGL(k_ct_straus<1>, dim3(C), dim3(64), 0, s, w.sc_dev.p, w.pts.p, w.plan.p, w.part.p);
+    else
+      hipLaunchKernelGGL(k_ct_straus<2>, dim3(C), dim3(64), 0, s, w.sc_dev.p, w.pts.p, w.plan.p, w.part.p);
+  }
+  hipLaunchKernelGGL(k_ct_straus_sum, dim3(G), dim3(64), 0, s, w.part.p, w.chunk_off.p, w.R.p);
+  hipLaunchKernelGGL(k_compress_ge, dim3(cdiv(G, 64)), dim3(64), 0, s, w.R.p, G, w.out32.p);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(w.pin_out.p, w.out32.p, (size_t)G * 32, hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  memcpy(out32, w.pin_out.p, (size_t)G * 32);
+  MsmForm f;
+  f.valid = true;
+  f.ct = true;
+  f.K = K;
+  f.G = G;
+  f.terms = (uint32_t)n;
+  ctx->msm_form = f;
   return BPP_OK;
 }
 
@@ -1449,11 +1572,66 @@ int bpp_msm_vartime_batched(bpp_ctx *ctx, const uint8_t *scalars32, const uint8_
   BPP_CATCH(ctx, nullptr, 0)
 }
 
+int bpp_msm_ct(bpp_ctx *ctx, const uint8_t *scalars32, const uint8_t *points32, size_t n, uint8_t out_point32[32]) {
+  BPP_ENTRY(ctx);
+  try {
+    return msm_ct_entry(ctx, scalars32, points32, n, nullptr, 1, out_point32);
+  }
+  BPP_CATCH(ctx, nullptr, 0)
+}
+
+int bpp_msm_ct_batched(bpp_ctx *ctx, const uint8_t *scalars32, const uint8_t *points32, const uint32_t *group_off, size_t n_groups,
+                       uint8_t *out_points32) {
+  BPP_ENTRY(ctx);
+  try {
+    if (!group_off || n_groups == 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "no groups");
+    for (size_t g = 0; g < n_groups; g++)
+      if (group_off[g + 1] < group_off[g]) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "group offsets not monotone");
+    if (group_off[0] != 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "group offsets must start at 0");
+    return msm_ct_entry(ctx, scalars32, points32, group_off[n_groups], group_off, n_groups, out_points32);
+  }
+  BPP_CATCH(ctx, nullptr, 0)
+}
+
+int bpp_msm_ct_secret_bytes(bpp_ctx *ctx, uint64_t *examined, uint64_t *nonzero) {
+  BPP_ENTRY(ctx);
+  try {
+    if (!examined || !nonzero) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+    CtMsmWork &w = ctx->ct_msm;
+    uint64_t seen = 0, cnt = 0;
+    if (w.used) {
+      HIP_CHECK(hipStreamSynchronize(ctx->stream));
+      if (w.pin_sc.p) {
+        for (size_t i = 0; i < w.pin_sc.n; i++) cnt += w.pin_sc.p[i] != 0;
+        seen += w.pin_sc.n;
+      }
+      const std::pair<const void *, size_t> dev[2] = {{w.sc_dev.p, w.sc_dev.n * sizeof(sc)}, {w.part.p, w.part.n * sizeof(ge)}};
+      for (const auto &b : dev) {
+        if (!b.first || !b.second) continue;
+        std::vector<uint8_t> h(b.second);
+        HIP_CHECK(hipMemcpy(h.data(), b.first, b.second, hipMemcpyDeviceToHost));
+        for (uint8_t v : h) cnt += v != 0;
+        seen += h.size();
+        wipe(h.data(), h.size());
+      }
+    }
+    *examined = seen;
+    *nonzero = cnt;
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, nullptr, 0)
+}
+
 int bpp_msm_last_plan(bpp_ctx *ctx, uint32_t out[8]) {
   BPP_ENTRY(ctx);
   if (!out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
   const MsmForm &f = ctx->msm_form;
   if (!f.valid) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "no MSM has run on this context");
+  if (f.ct) {  // bit 6 and the call's counts; no bucket-method word applies
+    const uint32_t v[8] = {0, 0, 0, 0, f.G, f.terms, 64u, 0};
+    memcpy(out, v, sizeof v);
+    return BPP_OK;
+  }
   const uint32_t bits = f.plain ? 32u : (f.quad ? 1u : 0u) | ((uint32_t)f.reduce << 1) | (f.final_quad ? 8u : 0u) | (f.narrow ? 16u : 0u);
   const uint32_t v[8] = {f.c, f.K, f.K_wide, f.nb, f.G, f.terms, bits, f.dig_cap};
   memcpy(out, v, sizeof v);

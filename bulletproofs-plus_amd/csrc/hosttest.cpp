@@ -69,6 +69,41 @@ int ht_ct_var_scalarmul(const uint8_t point32[32], const uint8_t scalar32[32], u
   ge r; ct_var_scalarmul(r, p, s);
   ristretto_compress(out32, r);
   return 1; }
+// sum_i scalars[i] * points[i] through ct_straus_model (the definition k_ct_straus is held to) -> compressed result; the trace as in
+// ht_ct_scalarmul: entry index (0..7 = 1 P .. 8 P) of every table read, in order.  0 if a point does not decode.
+int ht_ct_straus(const uint8_t *scalars32, const uint8_t *points32, size_t n, uint8_t out32[32], uint8_t *trace_out, size_t trace_cap,
+                 size_t *trace_len) {
+  std::vector<ge> pts(n);
+  std::vector<sc> scal(n);
+  for (size_t i = 0; i < n; i++) {
+    niels e; if (!ristretto_decompress(e, points32 + 32 * i)) return 0;
+    ge_from_niels(pts[i], e);
+    sc_load_words(scal[i], scalars32 + 32 * i);
+  }
+  std::vector<uint8_t> tr;
+  g_ct_trace = &tr;
+  ge r; ct_straus_model(r, pts.data(), scal.data(), (uint32_t)n);
+  g_ct_trace = nullptr;
+  ristretto_compress(out32, r);
+  if (trace_len) *trace_len = tr.size();
+  if (trace_out) memcpy(trace_out, tr.data(), tr.size() < trace_cap ? tr.size() : trace_cap);
+  return 1; }
+// the chunk plan of bpp_msm_ct (ct_plan.h): chunks_out = (group, first, count) triples, chunk_cap of them at most, *n_chunks their
+// number; chunk_off_out (may be null) = n_groups + 1 words.  ct_chunk_plan's code: 0, or -1 for offsets it refuses.
+int ht_ct_chunk_plan(const uint32_t *group_off, size_t n_groups, size_t n_terms, uint32_t K, uint32_t *chunks_out, size_t chunk_cap,
+                     size_t *n_chunks, uint32_t *chunk_off_out) {
+  std::vector<CtChunk> chunks;
+  std::vector<uint32_t> off;
+  const int rc = ct_chunk_plan(group_off, n_groups, n_terms, K, chunks, off);
+  if (n_chunks) *n_chunks = chunks.size();
+  if (rc != 0) return rc;
+  for (size_t c = 0; c < chunks.size() && c < chunk_cap && chunks_out; c++) {
+    chunks_out[3 * c] = chunks[c].group; chunks_out[3 * c + 1] = chunks[c].first; chunks_out[3 * c + 2] = chunks[c].count; }
+  if (chunk_off_out) memcpy(chunk_off_out, off.data(), off.size() * 4);
+  return 0; }
+// ct_form_rule and the branch-free canonicity check of bpp_msm_ct
+uint32_t ht_ct_form_rule(uint32_t largest, uint64_t chunks_k1, int forced) { return ct_form_rule(largest, chunks_k1, forced); }
+int ht_ct_sc_canonical(const uint8_t a[32]) { sc s; sc_load_words(s, a); return (int)ct_sc_is_canonical(s); }
 // the recoding alone: 64 signed radix-16 digits whose weighted sum is the scalar
 void ht_ct_recode16(const uint8_t scalar32[32], int8_t digits[64]) { sc s; sc_load_words(s, scalar32); ct_recode16(digits, s); }
 void ht_fe_mul(const uint8_t a[32], const uint8_t b[32], uint8_t out[32]) { fe x, y, z; fe_frombytes(x, a); fe_frombytes(y, b); fe_mul(z, x, y); fe_tobytes(out, z); }

@@ -153,7 +153,10 @@ int bpp_small_call_limit(bpp_ctx *ctx, int limit);
  * bpp_msm_mixed       = ::vartime_mixed_multiscalar_mul(static_scalars, dyn_scalars, dyn_points)
  *                        (src/range_proof.rs:339-345, :1050-1057); n_static <= table size, rest = zero padding
  * bpp_msm_vartime     = VartimeMultiscalarMul::vartime_multiscalar_mul          (src/range_proof.rs:482-495, :512-521)
- *                        also serves MultiscalarMul::multiscalar_mul            (src/generators/pedersen_gens.rs:120)
+ *                        VARIABLE-TIME, as the trait says: the addresses of its bucket tables are digits of its scalars.  It
+ *                        is not the constant-time trait; scalars that are secrets go to bpp_msm_ct.
+ * bpp_msm_ct          = MultiscalarMul::multiscalar_mul                         (src/generators/pedersen_gens.rs:112-122)
+ *                        dalek's constant-time Straus, see "B1: the constant-time trait" below
  * A point that does not decode makes the call return BPP_ERR_INVALID_ARGUMENT. */
 int bpp_precomp_create(bpp_ctx *ctx, const uint8_t *points32, size_t count, uint64_t *handle);
 int bpp_precomp_destroy(bpp_ctx *ctx, uint64_t handle);
@@ -172,8 +175,33 @@ int bpp_msm_vartime_batched(bpp_ctx *ctx, const uint8_t *scalars32, const uint8_
  * G (groups), terms, form, dig_cap (terms per group whose digits the prelude keeps in LDS) }.  form: bit 0 = quad accumulation
  * (else one lane per bucket); bits 1-2 = the reduction, 0 rc_quad, 1 rc2, 2 rc, 3 bitsum + window; bit 3 = final_quad (else final);
  * bit 4 = 256-lane prelude (else 1024); bit 5 = the plain kernels ("msm_plain" = 1: only G, terms and this bit are set).
+ * bit 6 = the constant-time kernels (bpp_msm_ct, bpp_msm_ct_batched: only G, terms and this bit are set).
  * BPP_ERR_INVALID_ARGUMENT before the first one (an empty sum launches nothing and records nothing). */
 int bpp_msm_last_plan(bpp_ctx *ctx, uint32_t out[8]);
+
+/* ---- B1: the constant-time trait, MultiscalarMul::multiscalar_mul ----
+ * sum_i scalars[i] * points[i] for scalars that are SECRETS over the caller's own points: commitments under bases that are no
+ * parameter set's H and G_k, blinded sums, anything written against the MultiscalarMul bound.  Arguments, group convention,
+ * return codes and messages are those of bpp_msm_vartime / bpp_msm_vartime_batched, and for the same inputs so are the output
+ * bytes (the canonical encoding of the same group element): a scalar that is not canonical or a point that does not decode
+ * gives BPP_ERR_INVALID_ARGUMENT, an empty group 32 zero bytes, a call without terms launches nothing.
+ * PUBLIC: the term counts, group_off, the points, which error is returned.  SECRET: the scalars.  No branch, no global, LDS or
+ * scratch address, no launch geometry and no choice of kernel form depends on a scalar's value (csrc/ct.h: k_ct_straus -- signed
+ * radix-16 digits, per term a table of the multiples 1 P .. 8 P of which EVERY entry is read for every digit and one is kept
+ * under an arithmetic mask; a zero scalar, a zero digit and a term whose point is the identity cost what any other costs); the
+ * canonicity check looks at every scalar of the call and decides once, at the end.  What IS data-dependent is public: the
+ * doublings and additions that build a term's table are operations on the caller's points, uniform in the scalars only.
+ * The scalars' host copy (page-locked), their device buffer, the per-chunk partial sums and the kernels' LDS are zeroed on every
+ * exit path, error returns included; the buffers stay with the context, so a second call of the same size allocates nothing.
+ * bpp_msm_ct_secret_bytes reads them back: *examined = bytes looked at (0 before the first call), *nonzero = how many were not
+ * zero (0 between calls).  "msm_plain" and the bucket-method options do not reach these entry points.  Context option
+ * "msm_ct_k" (BPP_MSM_CT_K): 1 / 2 = that many terms per quad of lanes (the K of k_ct_straus<K>: K terms share one accumulator's
+ * doublings); 0 and -1 = the engine's rule, made from the public counts.  One launch costs what a launch costs: worth calling
+ * with many outputs per call; for one commitment at a time dalek on the host is faster. */
+int bpp_msm_ct(bpp_ctx *ctx, const uint8_t *scalars32, const uint8_t *points32, size_t n, uint8_t out_point32[32]);
+int bpp_msm_ct_batched(bpp_ctx *ctx, const uint8_t *scalars32, const uint8_t *points32, const uint32_t *group_off,
+                       size_t n_groups, uint8_t *out_points32 /* n_groups x 32 */);
+int bpp_msm_ct_secret_bytes(bpp_ctx *ctx, uint64_t *examined, uint64_t *nonzero);
 
 /* ---- B2: parameters = RangeParameters::init + BulletproofGens::new + PedersenGens ----
  * (src/range_parameters.rs:32-58, src/generators/bulletproof_gens.rs:83-112, src/ristretto.rs:67-112)

@@ -213,6 +213,10 @@ extern "C" {
     pub fn bpp_msm_vartime_batched(ctx: *mut bpp_ctx, scalars32: *const u8, points32: *const u8, group_off: *const u32,
                                    n_groups: usize, out_points32: *mut u8) -> c_int;
     pub fn bpp_msm_last_plan(ctx: *mut bpp_ctx, out: *mut u32) -> c_int;
+    pub fn bpp_msm_ct(ctx: *mut bpp_ctx, scalars32: *const u8, points32: *const u8, n: usize, out_point32: *mut u8) -> c_int;
+    pub fn bpp_msm_ct_batched(ctx: *mut bpp_ctx, scalars32: *const u8, points32: *const u8, group_off: *const u32,
+                              n_groups: usize, out_points32: *mut u8) -> c_int;
+    pub fn bpp_msm_ct_secret_bytes(ctx: *mut bpp_ctx, examined: *mut u64, nonzero: *mut u64) -> c_int;
     // B2: RangeParameters::init (src/range_parameters.rs:32-58), PedersenGens::commit (src/generators/pedersen_gens.rs:112-122)
     pub fn bpp_params_create(ctx: *mut bpp_ctx, bit_length: u32, max_aggregation: u32, extension_degree: u32, h_base32: *const u8,
                              g_bases32: *const u8, params: *mut u64) -> c_int;
