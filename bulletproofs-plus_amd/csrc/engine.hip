@@ -39,6 +39,7 @@
 #include "msm.h"
 #include "msm_plain.h"
 #include "prove_job_host.h"
+#include "prove_pack_host.h"
 #include "upload_host.h"
 
 using namespace bpp;

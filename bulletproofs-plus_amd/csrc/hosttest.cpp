@@ -9,6 +9,7 @@
 #include "recode.h"
 #include "upload_host.h"
 #include "prove_job_host.h"
+#include "prove_pack_host.h"
 // the uniform-access scalar multiplication (ct.h) with its table reads RECORDED: BPP_CT_TOUCH(entry) appends the entry index
 #include <vector>
 static thread_local std::vector<uint8_t> *g_ct_trace = nullptr;
@@ -258,4 +259,31 @@ int ht_prove_job_copy(uint32_t n_bits, uint32_t m_max, uint32_t t, const bpp_pro
   c.wipe();
   for (size_t i = 0; i < c.store_bytes; i++) same = same && c.bytes()[i] == 0;
   return same ? copied : -1; }
+// the prover's witness packer (prove_pack_host.h) over the caller's items.  Returns the first finding's code (its message in msg),
+// or 0 with: desc_out 10 words per item in ProveDesc's order; sizes = {m, rounds, rounds_min, plen, bytes, states}; the packed bytes
+// and the 203-byte states up to their caps; minvals_out / minpres_out rows of m per item; roff_out; wiped_ok = 1 when every packed
+// byte reads zero after wipe()
+int ht_prove_pack(uint32_t n_bits, uint32_t m_max, uint32_t t, const uint8_t *hg32, const bpp_prove_item *items, size_t n, int mixed, int openings,
+                  uint32_t *desc_out, uint64_t *sizes, uint8_t *bytes_out, size_t bytes_cap, uint8_t *states_out, size_t states_cap,
+                  uint64_t *minvals_out, uint8_t *minpres_out, uint32_t *roff_out, int *wiped_ok, char *msg, size_t msg_len) {
+  ProvePack pk;
+  try {
+    pk.pack(ParamShape{n_bits, m_max, t}, hg32, items, n, mixed != 0, openings != 0);
+  } catch (const ProofErr &e) {
+    snprintf(msg, msg_len, "%s", e.msg.c_str());
+    return e.code;
+  }
+  static_assert(sizeof(ProveDesc) == 40, "ProveDesc is ten words");
+  memcpy(desc_out, pk.desc.data(), n * sizeof(ProveDesc));
+  const uint64_t sz[6] = {pk.m, pk.rounds, pk.rounds_min, pk.plen, pk.bytes.size(), pk.states.size()};
+  memcpy(sizes, sz, sizeof(sz));
+  memcpy(bytes_out, pk.bytes.data(), std::min(bytes_cap, pk.bytes.size()));
+  memcpy(states_out, pk.states.data(), std::min(states_cap, pk.states.size()));
+  memcpy(minvals_out, pk.minvals.data(), pk.minvals.size() * 8);
+  memcpy(minpres_out, pk.minpres.data(), pk.minpres.size());
+  memcpy(roff_out, pk.roff.data(), n * 4);
+  pk.wipe();
+  *wiped_ok = 1;
+  for (uint8_t b : pk.bytes) *wiped_ok = *wiped_ok && b == 0;
+  return 0; }
 }

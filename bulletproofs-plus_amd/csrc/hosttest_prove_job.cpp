@@ -1,5 +1,5 @@
 // Sanitizer harness (CPU test suite only): the job copy bpp_prove_submit takes of its caller's items (prove_job_host.h: the
-// per-item check, the deep copy, the wipe), built with  g++ -fsanitize=address,undefined  into an executable that
+// per-item check, the deep copy, the wipe) and the prover's witness packer (prove_pack_host.h), built with  g++ -fsanitize=address,undefined  into an executable that
 // tests/test_prove_pipeline_host.py runs.  Everything an item points to is an exact-size heap allocation, so a read past what the
 // item declares, or a look behind the pointer of an item that fails the check, is an ASan report (exit code != 0).  Prints one
 // "ok <case>" line per case.
@@ -9,7 +9,10 @@
 #include <memory>
 #include <random>
 
+#include <sanitizer/asan_interface.h>
+
 #include "prove_job_host.h"
+#include "prove_pack_host.h"
 
 using namespace bpp;
 
@@ -120,6 +123,60 @@ bool equal_item(const ParamShape &P, const bpp_prove_item &a, const bpp_prove_it
   }
   eq(a.rng_bytes, b.rng_bytes, need, ok);
   return ok;
+}
+
+// what the packer laid down for item i equals its source, field by field (offsets into pk.bytes as a whole)
+bool packed_item(const ParamShape &P, const ProvePack &pk, size_t i, const bpp_prove_item &it) {
+  const ProveDesc &d = pk.desc[i];
+  const size_t t = P.t, m = it.m, ext = 32 * (size_t)(rounds_of(P, it.m) + 3);
+  bool ok = d.m == it.m && d.mslot == pk.m && d.roff == pk.rounds - rounds_of(P, it.m) && pk.roff[i] == d.roff && d.minval_idx == i * pk.m;
+  ok = ok && d.commit_off == d.wit_off + m * (8 + 32 * t) && d.ext_off == d.commit_off + 32 * m && d.seed_off == d.ext_off + ext &&
+       d.seed_off + 32 == (i + 1 < pk.desc.size() ? pk.desc[i + 1].wit_off : pk.bytes.size());
+  ok = ok && d.flags == ((it.seed_nonce32 ? 1u : 0u) | (it.commitments32 ? 0u : PV_FLAG_MAKE_COMMITMENTS));
+  if (!ok) return false;
+  const uint8_t *b = pk.bytes.data();
+  for (size_t j = 0; j < m; j++) {
+    uint64_t v = 0;
+    for (int k = 7; k >= 0; k--) v = (v << 8) | b[d.wit_off + j * (8 + 32 * t) + k];
+    ok = ok && v == it.values[j] && memcmp(b + d.wit_off + j * (8 + 32 * t) + 8, it.blindings32 + 32 * t * j, 32 * t) == 0;
+    const bool present = it.min_present && it.min_present[j];
+    ok = ok && pk.minpres[i * pk.m + j] == (present ? 1 : 0) && pk.minvals[i * pk.m + j] == (present ? it.min_values[j] : 0);
+  }
+  const std::vector<uint8_t> zeros(32 * m + 32, 0);
+  ok = ok && memcmp(b + d.commit_off, it.commitments32 ? it.commitments32 : zeros.data(), 32 * m) == 0;
+  ok = ok && memcmp(b + d.ext_off, it.rng_bytes, ext) == 0;
+  ok = ok && memcmp(b + d.seed_off, it.seed_nonce32 ? it.seed_nonce32 : zeros.data(), 32) == 0;
+  return ok;
+}
+
+// the seven call-level appends on top of `st` (a label's Transcript::new, or the caller's state)
+void call_appends(Strobe &st, const ParamShape &P, const uint8_t *hg32, uint32_t m) {
+  merlin_append_message(st, (const uint8_t *)"dom-sep", 7, (const uint8_t *)"Bulletproofs+ Range Proof", 25);
+  merlin_append_message(st, (const uint8_t *)"H", 1, hg32, 32);
+  for (uint32_t k = 0; k < P.t; k++) merlin_append_message(st, (const uint8_t *)"G", 1, hg32 + 32 * (k + 1), 32);
+  merlin_append_u64(st, (const uint8_t *)"N", 1, P.n_bits);
+  merlin_append_u64(st, (const uint8_t *)"T", 1, P.t);
+  merlin_append_u64(st, (const uint8_t *)"M", 1, m);
+}
+bool state_is(const ProvePack &pk, size_t i, const ParamShape &P, const uint8_t *hg32, const bpp_prove_item &it) {
+  Strobe st;
+  if (it.transcript_state) strobe_from_bytes(st, it.transcript_state);
+  else merlin_new(st, it.transcript_label, (uint32_t)(it.transcript_label ? it.label_len : 0));
+  call_appends(st, P, hg32, it.m);
+  uint8_t want[203];
+  strobe_to_bytes(want, st);
+  return (size_t)pk.desc[i].state_idx * 203 + 203 <= pk.states.size() && memcmp(&pk.states[(size_t)pk.desc[i].state_idx * 203], want, 203) == 0;
+}
+
+int pack_code(const ParamShape &P, const uint8_t *hg32, const std::vector<bpp_prove_item> &v, bool mixed, bool openings, std::string *msg = nullptr) {
+  ProvePack pk;
+  try {
+    pk.pack(P, hg32, v.data(), v.size(), mixed, openings);
+  } catch (const ProofErr &e) {
+    if (msg) *msg = e.msg;
+    return e.code;
+  }
+  return BPP_OK;
 }
 
 int fails = 0;
@@ -262,6 +319,178 @@ int main() {
     for (const bpp_prove_item &it : c.items) ok = ok && it.values == nullptr && it.rng_bytes == nullptr && it.m == 0;
     ok = ok && c.code[12] == BPP_ERR_INVALID_ARGUMENT && c.code[0] == BPP_OK && c.len[0] != 0 && c.m[2] == 4;
     EXPECT("wiped_before_freed", ok);
+  }
+  std::unique_ptr<uint8_t[]> hg(new uint8_t[32 * 4]);  // H and three G bases, exact size for P
+  fill(hg.get(), 32 * 4);
+  {  // a uniform and a mixed call, every optional field in some item: descriptors, bytes, minimum-value rows
+    bool ok = true;
+    for (int mixed = 0; mixed < 2; mixed++) {
+      const uint32_t ms[2][6] = {{2, 2, 2, 2, 2, 2}, {4, 4, 2, 2, 1, 1}};
+      std::vector<Owned> own;
+      for (unsigned k = 0; k < 6; k++) own.push_back(make(P, ms[mixed][k], 1 | (k & 1 ? 2 | 4 : 0) | (k & 2 ? 2 : 0) | 8 | (k == 3 ? 64 : 0)));
+      std::vector<bpp_prove_item> v;
+      for (auto &o : own) v.push_back(o.view());
+      ProvePack pk;
+      pk.pack(P, hg.get(), v.data(), v.size(), mixed != 0, false);
+      ok = ok && pk.m == ms[mixed][0] && pk.rounds == rounds_of(P, pk.m) && pk.rounds_min == rounds_of(P, ms[mixed][5]) &&
+           pk.plen == prove_item_len_host(P, pk.m) && pk.desc.size() == 6 && pk.desc[0].wit_off == 0;
+      for (size_t i = 0; ok && i < 6; i++) ok = packed_item(P, pk, i, v[i]) && state_is(pk, i, P, hg.get(), v[i]);
+    }
+    EXPECT("pack_uniform_and_mixed", ok);
+  }
+  {  // openings items with and without commitments; without the openings flag the item that brings none is refused, unread
+    std::vector<Owned> own;
+    own.push_back(make(P, 2, 1));
+    own.push_back(make(P, 2, 0));
+    own.push_back(make(P, 1, 8));
+    own.push_back(make(P, 1, 1 | 8));
+    std::vector<bpp_prove_item> v;
+    for (auto &o : own) v.push_back(o.view());
+    ProvePack pk;
+    pk.pack(P, hg.get(), v.data(), v.size(), true, true);
+    bool ok = pk.desc[0].flags == 0 && pk.desc[1].flags == PV_FLAG_MAKE_COMMITMENTS && pk.desc[2].flags == (1u | PV_FLAG_MAKE_COMMITMENTS) &&
+              pk.desc[3].flags == 1u;
+    for (size_t i = 0; ok && i < 4; i++) ok = packed_item(P, pk, i, v[i]);
+    std::string msg;
+    v[1].values = (const uint64_t *)8;
+    v[1].blindings32 = v[1].rng_bytes = (const uint8_t *)8;
+    ok = ok && pack_code(P, hg.get(), v, true, false, &msg) == BPP_ERR_INVALID_ARGUMENT && msg == "null witness / statement field";
+    EXPECT("pack_openings", ok);
+  }
+  {  // labels and states, shared and distinct: one state per distinct (source bytes, m), each after the seven appends
+    std::vector<Owned> own;
+    own.push_back(make(P, 2, 1));       // a label
+    own.push_back(make(P, 2, 1 | 16));  // a state
+    own.push_back(make(P, 2, 1 | 32));  // no label at all
+    own.push_back(make(P, 1, 1 | 16));
+    std::vector<bpp_prove_item> v = {own[0].view(), own[0].view(), own[1].view(), own[2].view(), own[0].view(), own[3].view(), own[3].view()};
+    v[1].values = own[1].values.get();  // (another witness on the SAME label buffer)
+    v[4] = own[3].view();               // m = 1 items: the first label's bytes at ANOTHER address and under another m, a state twice
+    v[4].transcript_state = nullptr;
+    std::unique_ptr<uint8_t[]> label2(new uint8_t[own[0].label_len]);
+    memcpy(label2.get(), own[0].label.get(), own[0].label_len);
+    v[4].transcript_label = label2.get();
+    v[4].label_len = own[0].label_len;
+    std::unique_ptr<uint8_t[]> state2(new uint8_t[203]);
+    memcpy(state2.get(), own[3].state.get(), 203);
+    v[6].transcript_state = state2.get();
+    ProvePack pk;
+    pk.pack(P, hg.get(), v.data(), v.size(), true, false);
+    const uint32_t want[7] = {0, 0, 1, 2, 3, 4, 4};
+    bool ok = pk.states.size() == 5 * 203;
+    for (size_t i = 0; i < 7; i++) ok = ok && pk.desc[i].state_idx == want[i] && state_is(pk, i, P, hg.get(), v[i]);
+    EXPECT("pack_transcripts", ok);
+  }
+  {  // a failing item at every position of the check and of the call: the finding is the check's, and nothing behind a refused
+     // pointer -- the failing item's or a later item's -- is read
+    struct Bad {
+      int code;
+      const char *msg;
+    };
+    const Bad want[12] = {{BPP_ERR_INVALID_ARGUMENT, "Number of commitments must be a power of two"},
+                          {BPP_ERR_INVALID_ARGUMENT, "Number of commitments must be a power of two"},
+                          {BPP_ERR_INVALID_ARGUMENT, "Not enough generators for this statement"},
+                          {BPP_ERR_INVALID_ARGUMENT, "null witness / statement field"},
+                          {BPP_ERR_INVALID_ARGUMENT, "Mask recovery is not supported with an aggregated statement"},
+                          {BPP_ERR_INVALID_LENGTH, "not enough external randomness: need (rounds + 3) * 32 bytes"},
+                          {BPP_ERR_INVALID_LENGTH, "Value exceeds bit vector capacity!"},
+                          {BPP_ERR_INVALID_ARGUMENT, "Minimum value is larger than value"},
+                          {BPP_ERR_INVALID_ARGUMENT, "blinding factor is not canonical"},
+                          {BPP_ERR_INVALID_ARGUMENT, "seed nonce is not canonical"},
+                          {BPP_ERR_INVALID_ARGUMENT, "transcript state has pos >= rate"},
+                          {BPP_ERR_INVALID_ARGUMENT, "all items of one prove batch must share the aggregation factor"}};
+    bool ok = true;
+    for (int kind = 0; kind < 12; kind++)
+      for (size_t pos = 0; pos < 3; pos++) {
+        if (kind == 11 && pos == 0) continue;  // (the call's m IS the first item's)
+        const bool m1 = kind == 9;             // (a seed nonce needs m = 1)
+        std::vector<Owned> own;
+        for (size_t k = 0; k < 3; k++) own.push_back(make(P8, m1 ? 1 : 2, 1 | 2 | 4 | (k == pos && kind == 10 ? 16 : 0) | (m1 ? 8 : 0)));
+        Owned &o = own[pos];
+        std::vector<bpp_prove_item> v;
+        for (auto &x : own) v.push_back(x.view());
+        bpp_prove_item &b = v[pos];
+        if (kind <= 2 || kind == 11) {  // an m that says nothing about what lies behind the pointers
+          b.m = kind == 0 ? 0 : kind == 1 ? 3 : kind == 2 ? 8 : 4;
+          b.values = (const uint64_t *)8;
+          b.blindings32 = b.commitments32 = b.rng_bytes = (const uint8_t *)8;
+        } else if (kind == 3) {
+          b.rng_bytes = nullptr;
+          b.values = (const uint64_t *)8;
+        } else if (kind == 4) {
+          o.seed.reset(new uint8_t[32]);
+          canonical_scalar(o.seed.get());
+          b.seed_nonce32 = o.seed.get();
+          b.values = (const uint64_t *)8;
+        } else if (kind == 5) {
+          b.rng_len -= 1;
+          b.values = (const uint64_t *)8;
+        } else if (kind == 6) {
+          o.values[1] = 256;
+          b.blindings32 = (const uint8_t *)8;
+        } else if (kind == 7) {
+          o.values[0] = 3;  // (its promise is 7 and present)
+          b.blindings32 = (const uint8_t *)8;
+        } else if (kind == 8) {
+          memset(o.blind.get() + 32, 0xff, 32);
+        } else if (kind == 9) {
+          memset(o.seed.get(), 0xff, 32);
+        } else if (kind == 10) {
+          o.state[200] = BPP_STROBE_R;
+        }
+        for (size_t k = pos + 1; k < 3; k++) {  // whatever comes after the finding is never looked at
+          v[k].values = (const uint64_t *)8;
+          v[k].blindings32 = v[k].commitments32 = v[k].rng_bytes = (const uint8_t *)8;
+        }
+        std::string msg;
+        const int code = pack_code(P8, hg.get(), v, false, false, &msg);
+        // (an m of another kind behind the first item meets the call's own rule first, as it always did)
+        const Bad &w = kind <= 2 && pos > 0 ? want[11] : want[kind];
+        if (code != w.code || msg != w.msg) {
+          printf("  kind %d at %zu: %d %s\n", kind, pos, code, msg.c_str());
+          ok = false;
+        }
+      }
+    // the mixed call's own rule, in front of the check: an item larger than the one before it
+    std::vector<Owned> own;
+    own.push_back(make(P8, 2, 1));
+    own.push_back(make(P8, 4, 1));
+    std::vector<bpp_prove_item> v = {own[0].view(), own[1].view()};
+    v[1].values = (const uint64_t *)8;
+    std::string msg;
+    ok = ok && pack_code(P8, hg.get(), v, true, false, &msg) == BPP_ERR_INVALID_ARGUMENT &&
+         msg == "mixed prove batch: items must be sorted by aggregation factor";
+    EXPECT("pack_failing_item_at_every_position", ok);
+  }
+  {  // every packed byte reads zero after wipe(), and after the destructor (read where the freed block still lies, which the
+     // sanitizer keeps out of circulation: the destructor wipes BEFORE the vector gives its memory back)
+    std::vector<Owned> own;
+    for (unsigned k = 0; k < 8; k++) own.push_back(make(P, 2, 1 | 8));
+    std::vector<bpp_prove_item> v;
+    for (auto &o : own) v.push_back(o.view());
+    bool ok = true;
+    for (int how = 0; how < 2; how++) {
+      std::unique_ptr<ProvePack> pk(new ProvePack);
+      pk->pack(P, hg.get(), v.data(), v.size(), false, false);
+      const uint8_t *p = pk->bytes.data();
+      const size_t len = pk->bytes.size();
+      size_t nonzero = 0;
+      for (size_t i = 0; i < len; i++) nonzero += p[i] != 0;
+      ok = ok && len == 8 * (2 * (8 + 96) + 64 + 32 * (rounds_of(P, 2) + 3) + 32) && nonzero > len / 2;
+      if (how == 0) {
+        pk->wipe();
+      } else {
+        pk.reset();
+        ASAN_UNPOISON_MEMORY_REGION(p, len);
+      }
+      // (the sanitizer's allocator keeps a note of its own in the first 16 bytes of a block it has taken back)
+      for (size_t i = how ? 16 : 0; i < len; i++) ok = ok && p[i] == 0;
+      if (how == 1) ASAN_POISON_MEMORY_REGION(p, len);
+    }
+    // a call that fails half way leaves nothing either: the items packed before the finding are wiped with the rest
+    v[5].rng_bytes = nullptr;
+    ok = ok && pack_code(P, hg.get(), v, false, false) == BPP_ERR_INVALID_ARGUMENT;
+    EXPECT("pack_wiped_by_wipe_and_by_the_destructor", ok);
   }
   if (fails) {
     printf("%d case(s) failed\n", fails);

@@ -363,23 +363,7 @@ __device__ __forceinline__ void fb_reduce_one(ge *red /* LDS, this wavefront's 6
 #define KP_MAX_THREADS 256u  // the round kernel's workgroup: 1, 2 or 4 wavefronts (option "prove_waves")  // terms per row of the final round's secret-only term lists (3 + t <= 9 used)
 
 // ---------------------------------------------------------------- per-proof prover state
-struct ProveDesc {
-  uint32_t m;           // aggregation factor of this proof
-  uint32_t wit_off;     // byte offset of the witness bytes (v LE64 || r[0..t) per opening) in bytes[]
-  uint32_t commit_off;  // m compressed commitments
-  uint32_t ext_off;     // (rounds+3) x 32 bytes of external randomness
-  uint32_t minval_idx;  // m minimum values / presence flags
-  uint32_t state_idx;
-  uint32_t flags;       // bit0: seed nonce present; bit1: the commitments are to be made (kp_adopt_commitments)
-  uint32_t seed_off;    // byte offset of the 32-byte seed nonce (if any)
-  // Mixed aggregation factors (bpp_prove_batch_mixed): the call runs R = the largest proof's rounds as global steps; this proof
-  // takes part from step roff = R - its own rounds on (its local step is j - roff), so that every proof reaches the final step in
-  // the same launch.  Per-proof slots of the call's buffers (vectors, term rows) are sized for mslot, the call's largest m.
-  // A uniform call: roff = 0, mslot = m.
-  uint32_t roff;
-  uint32_t mslot;
-};
-
+// (ProveDesc, the per-proof descriptor the host packer writes: layout.h)
 struct ProveState {
   Strobe tr;   // the proof's merlin transcript
   Strobe rng;  // current TranscriptRng (src/transcripts.rs:185-194)
@@ -390,7 +374,6 @@ struct ProveState {
 
 #define PV_STATUS_COMMIT_MISMATCH 2u  // InvalidArgument: "Witness opening is invalid!" (:275-284)
 #define PV_STATUS_TRANSCRIPT 1u       // VerificationFailed: identity point / zero challenge
-#define PV_FLAG_MAKE_COMMITMENTS 2u   // ProveDesc::flags: the statement's commitments are the ones the witness check computes
 
 // build_rng (src/transcripts.rs:185-194): clone, rekey with the witness bytes, finalize with 32 external bytes
 __device__ __forceinline__ void pv_build_rng(Strobe &rng, const Strobe &tr, const uint8_t *wit, uint32_t wit_len,

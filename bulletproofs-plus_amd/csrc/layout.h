@@ -1,5 +1,5 @@
-// Plain-data descriptors shared by the host packer (upload_host.h, compiled by hipcc AND by g++ for the sanitizer
-// harness) and the device kernels (kernels_verify.h).
+// Plain-data descriptors shared by the host packers (upload_host.h, prove_pack_host.h: compiled by hipcc AND by g++ for the
+// sanitizer harnesses) and the device kernels (kernels_verify.h, kernels_prove.h).
 #pragma once
 #include <stdint.h>
 
@@ -15,6 +15,26 @@ struct ProofDesc {
   uint32_t state_idx;   // which initial transcript state
   uint32_t flags;       // bit0: seed nonce present
 };
+
+// the prover's descriptor of one proof (prove_pack_host.h writes it, kernels_prove.h reads it)
+struct ProveDesc {
+  uint32_t m;           // aggregation factor of this proof
+  uint32_t wit_off;     // byte offset of the witness bytes (v LE64 || r[0..t) per opening) in bytes[]
+  uint32_t commit_off;  // m compressed commitments
+  uint32_t ext_off;     // (rounds+3) x 32 bytes of external randomness
+  uint32_t minval_idx;  // m minimum values / presence flags
+  uint32_t state_idx;
+  uint32_t flags;       // bit0: seed nonce present; bit1: the commitments are to be made (kp_adopt_commitments)
+  uint32_t seed_off;    // byte offset of the 32-byte seed nonce (if any)
+  // Mixed aggregation factors (bpp_prove_batch_mixed): the call runs R = the largest proof's rounds as global steps; this proof
+  // takes part from step roff = R - its own rounds on (its local step is j - roff), so that every proof reaches the final step in
+  // the same launch.  Per-proof slots of the call's buffers (vectors, term rows) are sized for mslot, the call's largest m.
+  // A uniform call: roff = 0, mslot = m.
+  uint32_t roff;
+  uint32_t mslot;
+};
+
+#define PV_FLAG_MAKE_COMMITMENTS 2u   // ProveDesc::flags: the statement's commitments are the ones the witness check computes
 
 // status bits written by the kernels
 #define BPP_ST_TRANSCRIPT_FAIL 1u  // identity encoding appended or zero challenge -> VerificationFailed

@@ -14,12 +14,17 @@
 
 namespace bpp {
 
+// the rounds of the inner-product argument for an m that passes RangeStatement::init: log2(m x n_bits), rounded up
+inline uint32_t prove_rounds_host(const ParamShape &P, uint32_t m) {
+  uint32_t rounds = 0;
+  while ((1u << rounds) < m * P.n_bits) rounds++;
+  return rounds;
+}
+
 // the proof length of an item whose m passes RangeStatement::init, 0 otherwise
 inline size_t prove_item_len_host(const ParamShape &P, uint32_t m) {
   if (m == 0 || (m & (m - 1)) || P.m_max < m || m * P.n_bits < 2) return 0;
-  uint32_t rounds = 0;
-  while ((1u << rounds) < m * P.n_bits) rounds++;
-  return 1 + 32 * (size_t)(P.t + 5 + 2 * rounds);
+  return 1 + 32 * (size_t)(P.t + 5 + 2 * prove_rounds_host(P, m));
 }
 
 // the host-side checks of a one-item bpp_prove_batch on `it`, in the same order and with the same codes and messages.
@@ -30,14 +35,12 @@ inline void prove_item_check_host(const ParamShape &P, const bpp_prove_item &it,
   if (m == 0 || (m & (m - 1))) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Number of commitments must be a power of two"};
   if (P.m_max < m) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Not enough generators for this statement"};
   if (m * n < 2) throw ProofErr{BPP_ERR_INVALID_LENGTH, "bit_length * aggregation factor must be at least 2"};
-  uint32_t rounds = 0;
-  while ((1u << rounds) < m * n) rounds++;
   if (proof_stride < prove_item_len_host(P, m)) throw ProofErr{BPP_ERR_INVALID_LENGTH, "proof_stride too small"};
   if (openings && commit_stride < (size_t)32 * m) throw ProofErr{BPP_ERR_INVALID_LENGTH, "commit_stride too small"};
   if (!it.values || !it.blindings32 || (!it.commitments32 && !openings) || !it.rng_bytes || (!it.min_values && it.min_present))
     throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "null witness / statement field"};
   if (it.seed_nonce32 && m > 1) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Mask recovery is not supported with an aggregated statement"};
-  if (it.rng_len < 32 * (size_t)(rounds + 3))
+  if (it.rng_len < 32 * (size_t)(prove_rounds_host(P, m) + 3))
     throw ProofErr{BPP_ERR_INVALID_LENGTH, "not enough external randomness: need (rounds + 3) * 32 bytes"};
   for (uint32_t j = 0; j < m; j++) {
     if (n < 64 && (it.values[j] >> n) > 0) throw ProofErr{BPP_ERR_INVALID_LENGTH, "Value exceeds bit vector capacity!"};
@@ -82,11 +85,7 @@ struct ProveJobCopy {
   static size_t pad8(size_t n) { return (n + 7) & ~(size_t)7; }
 
   // the bytes prove_uniform reads of a passing item's external randomness: (rounds + 3) draws (rng_len may be longer)
-  static size_t rng_need(const ParamShape &P, uint32_t m) {
-    uint32_t rounds = 0;
-    while ((1u << rounds) < m * P.n_bits) rounds++;
-    return 32 * (size_t)(rounds + 3);
-  }
+  static size_t rng_need(const ParamShape &P, uint32_t m) { return 32 * (size_t)(prove_rounds_host(P, m) + 3); }
 
   // the same transcript source as the previous item (one label or state buffer for the whole call, the common case): the copy is
   // shared, so that the prover still sees one source

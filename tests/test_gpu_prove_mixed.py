@@ -134,6 +134,26 @@ def test_mixed_equals_one_uniform_call_per_class(bpp, engine):
     assert [g.to_bytes() for g in bpp.RangeProof.prove_batch_mixed(*args)] == [p.to_bytes() for p in bpp.RangeProof.prove_batch(*args)]
 
 
+def test_mixed_ragged_schedule_across_sub_batches(bpp, engine, opt):
+    """The ragged schedule over TWO sub-batches: the sorted call has 70 items, so under the default "prove_subs" a sub-batch holds
+    64 and the second one is six m = 1 proofs that join two steps late -- it has no active proof at steps 0 and 1, and the prefix
+    of active proofs is taken per sub-batch.  Every proof equals the oracle's bytes under every form of the round's launches."""
+    n, m_max, t = 8, 4, 1
+    params = bpp.RangeParameters.init(n, m_max, bpp.create_pedersen_gens_with_extension_degree(t), engine=engine)
+    ms = [4] * 40 + [2] * 24 + [1] * 6
+    random.Random("ragged").shuffle(ms)
+    items = _items(bpp, params, n, t, ms, b"ragged")
+    want = _oracle(n, m_max, t, items)
+    knobs = [dict(ct=c, prove_parts=p, prove_fused=f) for c in (0, 1, 2) for p in (0, -1) for f in (0, 1)]
+    for k in knobs + [dict(ct=2, ct_back=3, prove_parts=-1, prove_fused=-1)]:
+        for name, value in k.items():
+            opt(name, value)
+        got = _mixed(bpp, items)
+        for i, g in enumerate(got):
+            assert not isinstance(g, Exception), (k, i, g)
+            assert g.to_bytes() == want[i], "proof %d (m = %d) differs from the oracle under %s" % (i, items[i]["m"], k)
+
+
 def _one_call_error(bpp, it):
     with pytest.raises(bpp.ProofError) as e:
         bpp.RangeProof.prove_batch([it["tr"]], [it["st"]], [it["w"]], [it["ext"]])
