@@ -66,6 +66,11 @@ class VerifyCheckStats(Structure):
     _fields_ = [(n, c_uint64) for n in ("calls", "rechecked_groups", "confirmed", "overturned", "tie_breaks", "undecided")]
 
 
+class VerifyJointStats(Structure):
+    """struct bpp_verify_joint_stats: what the joint final checks ("verify_joint" = 1) of a context have done"""
+    _fields_ = [(n, c_uint64) for n in ("calls", "accepted", "fallbacks", "fallback_all_ok")]
+
+
 class RuntimeInfo(Structure):
     """bpp_runtime_info: what the library sees of its runtime preconditions (hardware queues, contexts, the small-call gate)"""
     _fields_ = [("device", c_int), ("contexts", c_uint32), ("contexts_peak", c_uint32), ("hw_queues", c_uint32),
@@ -175,6 +180,8 @@ SYMBOLS = [
     ("bpp_verify_check_resolve", c_int, [POINTER(ShardResult), c_int, POINTER(ShardResult), POINTER(c_int)]),
     ("bpp_verify_check_stats", c_int, [c_void_p, POINTER(VerifyCheckStats)]),
     ("bpp_batcher_verify_check_stats", c_int, [c_void_p, POINTER(VerifyCheckStats)]),
+    ("bpp_verify_joint_stats", c_int, [c_void_p, POINTER(VerifyJointStats)]),
+    ("bpp_batcher_verify_joint_stats", c_int, [c_void_p, POINTER(VerifyJointStats)]),
     ("bpp_prove_pipeline_depth", c_int, [c_void_p, c_uint32]),
     ("bpp_prove_submit", c_int, [c_void_p, c_uint64, POINTER(ProveItem), c_size_t, c_size_t, c_int, c_size_t, POINTER(c_uint64),
                                  c_void_p, c_size_t]),

@@ -176,7 +176,8 @@ class Engine:
         form = int(w[6])
         return {"c": int(w[0]), "K": int(w[1]), "K_wide": int(w[2]), "nb": int(w[3]), "G": int(w[4]), "terms": int(w[5]),
                 "quad": bool(form & 1), "reduce": ("rc_quad", "rc2", "rc", "bitsum")[(form >> 1) & 3], "final_quad": bool(form & 8),
-                "narrow_prelude": bool(form & 16), "plain": bool(form & 32), "ct": bool(form & 64), "form": form, "dig_cap": int(w[7])}
+                "narrow_prelude": bool(form & 16), "plain": bool(form & 32), "ct": bool(form & 64), "sliced_prelude": bool(form & 128),
+                "slices": (form >> 8) & 0xff, "form": form, "dig_cap": int(w[7])}
 
     def profile(self, on=True):
         """bpp_profile_enable: False / 0 off, True / 1 an event at every stage boundary, 2 the roofline kernel's two events only"""
@@ -206,6 +207,14 @@ class Engine:
         s = _lib.VerifyCheckStats()
         _check(self.lib.bpp_verify_check_stats(self.ctx, byref(s)), self.ctx)
         return {n: int(getattr(s, n)) for n, _ in _lib.VerifyCheckStats._fields_}
+
+    def verify_joint_stats(self):
+        """bpp_verify_joint_stats: what the joint final checks ("verify_joint" = 1) of this context and its pipeline lanes have done
+        -- passes that took the joint path, those it accepted, those that fell back to the per-group MSMs, and the fall-backs
+        after which every group was Ok all the same"""
+        s = _lib.VerifyJointStats()
+        _check(self.lib.bpp_verify_joint_stats(self.ctx, byref(s)), self.ctx)
+        return {n: int(getattr(s, n)) for n, _ in _lib.VerifyJointStats._fields_}
 
     def prove_check_recovery_stats(self):
         """bpp_prove_check_recovery_stats ("prove_check" = 1 and "prove_check_recovery" = 1): proofs with a seed nonce whose mask

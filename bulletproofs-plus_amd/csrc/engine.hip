@@ -155,6 +155,12 @@ inline void add_stats(struct bpp_prove_check_stats &sum, const struct bpp_prove_
   sum.remade += s.remade;
   sum.failed += s.failed;
 }
+inline void add_stats(struct bpp_verify_joint_stats &sum, const struct bpp_verify_joint_stats &s) {
+  sum.calls += s.calls;
+  sum.accepted += s.accepted;
+  sum.fallbacks += s.fallbacks;
+  sum.fallback_all_ok += s.fallback_all_ok;
+}
 inline void add_stats(struct bpp_verify_check_stats &sum, const struct bpp_verify_check_stats &s) {
   sum.calls += s.calls;
   sum.rechecked_groups += s.rechecked_groups;
@@ -425,6 +431,10 @@ struct MsmWork {
   // the plain MSM (msm_plain.h: "msm_plain" = 1, pass 2 of "verify_check"): the group offsets as the host made them, one partial
   // sum per wavefront, the ids of the groups to evaluate (mapped: the kernels read them where the host wrote them)
   std::vector<uint32_t> h_goff;
+  // the sliced prelude (msm.h: k_msm_slice_*): slices per (group, window) sort, 0 = the one-workgroup form; per-slice bucket
+  // histograms, turned into write offsets in place
+  uint32_t slices = 0;
+  DevBuf<uint32_t> slice_hist;
   DevBuf<ge> plain_part;
   PinnedBuf<uint32_t> plain_list;
 };
@@ -474,6 +484,13 @@ struct Batch {
   DevBuf<niels> dynpts;
   DevBuf<pniels> dyn_hi;  // 2^126 x dynpts as projective Niels entries (half-scalar plan only)
   MsmWork msm;
+  // "verify_joint" = 1: the one-group MSM over all reference batches of the call (kernels_verify.h: k_joint_row), planned by
+  // layout_groups beside the per-group one.  joint_G: the group count its term lists were written for (0: none);
+  // need_dyn_hi: a plan the pass may run is a half-scalar one; joint_ran: a pass took the joint path and msm_joint holds its result;
+  // joint_accepted: the last MSM this batch ran was an accepted joint check, so msm holds no results of it (bpp_batch_trace)
+  MsmWork msm_joint;
+  uint32_t joint_G = 0;
+  bool need_dyn_hi = false, joint_ran = false, joint_accepted = false;
   // layout of the last verify
   size_t last_chunk = (size_t)-1;
   uint32_t G = 0;
@@ -593,6 +610,7 @@ struct MsmForm {
   bool final_quad = false;  // k_msm_final_quad, else k_msm_final
   bool narrow = false;      // 256-lane prelude and order kernels, else 1024
   uint32_t dig_cap = 0;     // terms per group whose digits k_msm_prelude keeps in LDS
+  uint32_t slices = 0;      // the sliced prelude (k_msm_slice_*) with this many slices; 0: k_msm_prelude
   uint32_t c = 0, K = 0, K_wide = 0, nb = 0, G = 0, terms = 0;
 };
 
@@ -672,16 +690,20 @@ struct bpp_ctx {
   struct Options {
     int transcripts_wave = -1, tables_wave = -1, side_decompress = -1, msm_c_bias = -1, msm_c_max = -1, msm_c_add = -1, msm_rc2 = -1, msm_quad = -1, msm_final_quad = -1,
         fb_threads = -1, prove_subs = -1, msm_split = -1, fused_columns = -1, prove_prio = -1, prove_fused = -1, static_gemm = -1, lazy_columns = -1, ct = -1, prove_parts = -1, prove_waves = -1, prove_fifo = -1, chain = -1, chain_test_zero = 0, wait = -1, ct_back = -1, chain_inline = -1, wide_in_lanes = -1,
-        prove_check = -1, prove_check_recovery = -1, msm_plain = -1, verify_check = -1, msm_ct_k = -1;
+        prove_check = -1, prove_check_recovery = -1, msm_plain = -1, verify_check = -1, msm_ct_k = -1, verify_joint = 0, msm_prelude_slices = 0;
   } opt;
   // "verify_check" = 1 (verify_flow): what the rechecks of this context's verifications have done; the prover's self-check runs
   // its verifications with the recheck off (verify_check_off > 0) -- a rejection there is already answered by a remake
   struct bpp_verify_check_stats vcheck_stats{};
   int verify_check_off = 0;
+  // "verify_joint" = 1: passes that took the joint final check, how they ended; the remembered wait of a fall-back's second wait
+  struct bpp_verify_joint_stats vjoint_stats{};
+  WaitHint wait_hint_fallback;
   // test knobs of the recheck (bpp_ctx_set_option only, never copied to a lane): on the context's NEXT verification, in the passes
   // of the bit mask `passes` (1, 2, 4), the host copy of the results of group `group` is altered after the wait and before findings
   // are raised -- kind 1: identity flag 0; 2: identity flag 1 and the device bits of the group's status words cleared; 3 / 4:
-  // BPP_ST_TRANSCRIPT_FAIL / BPP_ST_DECOMPRESS_FAIL set in the status word of the group's first proof.  A kind above 15 holds one
+  // BPP_ST_TRANSCRIPT_FAIL / BPP_ST_DECOMPRESS_FAIL set in the status word of the group's first proof; 5: the verdict of the joint
+  // final check ("verify_joint") cleared, whatever `group` says, so that the fall-back runs on a valid input.  A kind above 15 holds one
   // kind per pass, four bits each, pass 1 in the lowest (three different outcomes need two different alterations)
   struct VerifyTamper {
     int passes = 0, group = 0, kind = 0;
@@ -791,6 +813,13 @@ const OptionName kOptions[] = {
     // the kernel form of bpp_msm_ct / bpp_msm_ct_batched: 1 / 2 terms per quad (k_ct_straus<K>); 0 / -1: the engine's rule, from
     // the call's public counts (ct_plan.h: ct_form_rule)
     {"msm_ct_k", "BPP_MSM_CT_K", &bpp_ctx::Options::msm_ct_k},
+    // 1: a verification pass with two or more groups, all of them held to the final check, runs ONE multiscalar multiplication over
+    // all of them and falls back to the per-group ones only when that joint check fails (verify_flow_once), while the joint group
+    // has at most BPP_JOINT_MAX_TERMS terms; 2: whatever its size (measurement); 0 / -1: off
+    {"verify_joint", "BPP_VERIFY_JOINT", &bpp_ctx::Options::verify_joint},
+    // the bucket MSM's prelude: S >= 2 cuts every (group, window) sort into S slices (msm.h: k_msm_slice_*), bpp_msm_vartime* included;
+    // 1: the one-workgroup form whatever the size; 0 / -1: the engine's rule (recode.h: msm_prelude_slices)
+    {"msm_prelude_slices", "BPP_MSM_PRELUDE_SLICES", &bpp_ctx::Options::msm_prelude_slices},
 };
 struct TamperName {
   const char *name;
@@ -953,23 +982,9 @@ static bool decompress_spill_enabled() {
 
 // ------------------------------------------------------------------ MSM driver
 // A call of up to this many MSM terms is "small": it has the chip to itself, its time is the length of its dependency chains
-#define BPP_SMALL_CALL_TERMS 20000u
+// (BPP_SMALL_CALL_TERMS and the rule itself: recode.h, msm_choose_window -- host-compiled by the tests as well)
 uint32_t choose_window(const bpp_ctx *ctx, uint32_t group_terms, uint32_t all_terms) {
-  // buckets per window ~ terms / 12  (bucket lists of ~12 points keep the per-lane chains short)
-  uint32_t c = 4;
-  while (c < 14 && (1u << c) * 12u <= group_terms) c++;  // nb = 2^(c-1)
-  // Above 11 bits the buckets of a window no longer fit the row / column reduction (2.1 additions per bucket, k_msm_window_rc)
-  // and go through the bit-plane one (c / 2 per bucket): 13 bits for a 4096-proof batch (61 k terms) is 20 x 61 k + 20 x 4096
-  // x 6.5 = 1.76 M additions, 11 bits 23 x 61 k + 23 x 1024 x 2.1 = 1.47 M.  The wider windows only pay from ~200 k terms on.
-  const uint32_t c_max = ctx->opt.msm_c_max >= 0 ? (uint32_t)ctx->opt.msm_c_max : (group_terms < 200000u ? 11u : 14u);
-  if (ctx->opt.msm_c_add > 0 && all_terms > BPP_SMALL_CALL_TERMS) c += (uint32_t)ctx->opt.msm_c_add;  // (A/B timing of wider windows)
-  if (c > c_max && c_max >= 4) c = c_max;
-  // A small call has the chip to itself: its time is the length of the dependency chains, not the number of additions.
-  // Wider windows shorten the bucket lists (accumulation) and the Horner step (fewer windows to add) for a longer
-  // row / column reduction: three more bits are worth 0.07-0.1 ms up to a few hundred proofs (one proof 0.79 -> 0.68 ms).
-  const int bias = ctx->opt.msm_c_bias >= 0 ? ctx->opt.msm_c_bias : 3;  // (tests run the narrow windows as well)
-  if (all_terms <= BPP_SMALL_CALL_TERMS) c = (uint32_t)std::max(4, std::min(11, (int)c + bias));
-  return c;
+  return msm_choose_window(group_terms, all_terms, ctx->opt.msm_c_max, ctx->opt.msm_c_add, ctx->opt.msm_c_bias);
 }
 
 // plan + work buffers for G groups with term offsets goff[0..G]; the term lists (term_sidx / term_pidx) are filled by
@@ -992,10 +1007,18 @@ void msm_plan_alloc(bpp_ctx *ctx, MsmWork &w, const std::vector<uint32_t> &goff,
   uint32_t maxg = 0;
   for (uint32_t g = 0; g < G; g++) maxg = std::max(maxg, goff[g + 1] - goff[g]);
   const MsmPlan plan = msm_make_plan(choose_window(ctx, maxg, split ? n / 2 : n), G, n, split ? BPP_MSM_SPLIT_BITS : 253u);
+  // which prelude (recode.h has the LDS table): refused here, before anything is allocated or launched, when neither form can hold
+  // the plan's bucket tables in a workgroup's LDS
+  const uint32_t sort_threads = BPP_SORT_THREADS;  // (the wider form's need: a plan that fits it fits the 256-lane form)
+  const uint32_t slices = msm_prelude_slices(maxg, G, plan.K, plan.nb, sort_threads, ctx->opt.msm_prelude_slices);
+  if (!msm_prelude_fits(plan.nb, sort_threads, slices ? 1u : 0u))
+    throw EngineError{BPP_ERR_ENGINE, "MSM plan: the prelude's bucket tables (" + std::to_string(plan.c) + "-bit windows) do not fit a workgroup's LDS"};
   w.plan = plan;
   w.split = split;
   w.max_group_terms = maxg;
   w.h_goff = goff;
+  w.slices = slices;
+  if (slices) w.slice_hist.alloc((size_t)G * plan.K * slices * plan.nb);
   const size_t nbk = (size_t)G * plan.K * plan.nb;
   w.counts.alloc(nbk);
   w.starts.alloc(nbk);
@@ -1044,7 +1067,8 @@ void msm_run(bpp_ctx *ctx, MsmWork &w, const sc *scalars, PointTables tabs, Stag
   f.valid = true;
   f.quad = w.split || (ctx->opt.msm_quad >= 0 ? ctx->opt.msm_quad != 0 : (size_t)plan.G * per_group <= 100000);
   f.narrow = !f.quad && w.max_group_terms <= BPP_SORT_SMALL_GROUP_TERMS;
-  f.dig_cap = f.narrow ? msm_prelude_dig_cap(plan, w.max_group_terms, BPP_SORT_THREADS_SMALL) : msm_prelude_dig_cap(plan, w.max_group_terms);
+  f.slices = w.slices;
+  f.dig_cap = f.slices ? 0u : (f.narrow ? msm_prelude_dig_cap(plan, w.max_group_terms, BPP_SORT_THREADS_SMALL) : msm_prelude_dig_cap(plan, w.max_group_terms));
   if (plan.c <= 11 && f.quad)
     f.reduce = MSM_RC_QUAD;
   else if (plan.nb <= 256 && ctx->opt.msm_rc2 != 0)  // two windows per wavefront (msm.h)
@@ -1057,7 +1081,20 @@ void msm_run(bpp_ctx *ctx, MsmWork &w, const sc *scalars, PointTables tabs, Stag
   f.c = plan.c, f.K = plan.K, f.K_wide = plan.K_wide, f.nb = plan.nb, f.G = plan.G, f.terms = plan.n_terms;
   ctx->msm_form = f;
   const uint32_t dig_cap = f.dig_cap;
-  if (f.narrow) {
+  if (f.slices) {  // large groups, or forced: histogram per slice, scan, scatter (msm.h), then the same group-level order
+    const uint32_t S = f.slices, n_wg = plan.G * plan.K * S;
+    hipLaunchKernelGGL(k_msm_slice_hist, dim3(n_wg), dim3(BPP_SLICE_THREADS), (size_t)plan.nb * 4, s, scalars, w.term_sidx.p, w.group_off.p, plan, S,
+                       w.slice_hist.p);
+    hipLaunchKernelGGL(k_msm_slice_scan, dim3(plan.G * plan.K), dim3(BPP_SLICE_SCAN_THREADS), 0, s, w.slice_hist.p, w.group_off.p, plan, S, w.counts.p,
+                       w.starts.p, w.order_win.p, w.cls_hist.p);
+    hipLaunchKernelGGL(k_msm_slice_scatter, dim3(n_wg), dim3(BPP_SLICE_THREADS), (size_t)plan.nb * 4, s, scalars, w.term_sidx.p, w.term_pidx.p,
+                       w.group_off.p, plan, S, w.slice_hist.p, w.sorted.p);
+    if (f.narrow)
+      hipLaunchKernelGGL(k_msm_order<BPP_SORT_THREADS_SMALL>, dim3(plan.G), dim3(BPP_SORT_THREADS_SMALL), 0, s, w.counts.p, w.order_win.p, w.cls_hist.p, plan,
+                         w.order.p);
+    else
+      hipLaunchKernelGGL(k_msm_order<BPP_SORT_THREADS>, dim3(plan.G), dim3(BPP_SORT_THREADS), 0, s, w.counts.p, w.order_win.p, w.cls_hist.p, plan, w.order.p);
+  } else if (f.narrow) {
     hipLaunchKernelGGL(k_msm_prelude<BPP_SORT_THREADS_SMALL>, dim3(8 * cdiv(plan.G, 8) * plan.K), dim3(BPP_SORT_THREADS_SMALL), msm_prelude_lds(plan, dig_cap), s,
                        scalars, w.term_sidx.p, w.term_pidx.p, w.group_off.p, plan, dig_cap, w.counts.p, w.starts.p, w.sorted.p, w.order_win.p, w.cls_hist.p);
     hipLaunchKernelGGL(k_msm_order<BPP_SORT_THREADS_SMALL>, dim3(plan.G), dim3(BPP_SORT_THREADS_SMALL), 0, s, w.counts.p, w.order_win.p, w.cls_hist.p, plan,
@@ -1633,7 +1670,8 @@ int bpp_msm_last_plan(bpp_ctx *ctx, uint32_t out[8]) {
     memcpy(out, v, sizeof v);
     return BPP_OK;
   }
-  const uint32_t bits = f.plain ? 32u : (f.quad ? 1u : 0u) | ((uint32_t)f.reduce << 1) | (f.final_quad ? 8u : 0u) | (f.narrow ? 16u : 0u);
+  const uint32_t bits = f.plain ? 32u : (f.quad ? 1u : 0u) | ((uint32_t)f.reduce << 1) | (f.final_quad ? 8u : 0u) | (f.narrow ? 16u : 0u) |
+                        (f.slices ? 128u | (f.slices << 8) : 0u);  // bit 7: the sliced prelude, bits 8-15: its slices
   const uint32_t v[8] = {f.c, f.K, f.K_wide, f.nb, f.G, f.terms, bits, f.dig_cap};
   memcpy(out, v, sizeof v);
   return BPP_OK;
@@ -2268,7 +2306,7 @@ void enqueue_phase1(bpp_ctx *ctx, Batch &b, StageTimer &tm, bool pass1_only, uin
     // half-scalar plan of small calls: the 2^126 multiples of every dynamic point (the statements' commitments were decoded
     // at upload), 126 doublings each, right behind the decompression and -- for small inputs -- beside PASS 1 and the scalars.
     // A point that did not decode left an arbitrary entry: its multiple is never looked at (the call fails on the status).
-    if (b.msm.split && !pass1_only)
+    if (b.need_dyn_hi && !pass1_only)  // (the per-group plan's, or the joint check's: layout_joint)
       hipLaunchKernelGGL(k_split_shift_quad, dim3(cdiv(b.total_dyn, 16)), dim3(64), 0, st, b.dynpts.p, b.total_dyn, b.dyn_hi.p);
   };
   if (side) {
@@ -2597,8 +2635,11 @@ void run_weight_chains_generic(const uint8_t *h_rng, uint8_t *h_weights, const u
 // status words (and, where asked for, the groups' identity flags and the recovered masks) -> mapped host memory, status[]
 // back to its initial value: one launch, no copy (kernels_verify.h: k_results_out).  Valid on the host once the stream has
 // been synchronised.
-void fetch_results(bpp_ctx *ctx, Batch &b, bool ident, bool masks) {
+// joint: the one identity flag of the joint final check instead of the groups' (it lands in h_ident[0])
+void fetch_results(bpp_ctx *ctx, Batch &b, bool ident, bool masks, bool joint = false) {
   if (ident) b.h_ident.resize(b.G);
+  const uint32_t *ident_src = joint ? b.msm_joint.is_identity.p : b.msm.is_identity.p;
+  const uint32_t n_ident = joint ? 1u : b.G;
   const uint32_t pieces = masks ? (uint32_t)(((size_t)b.B * b.params->t * 32) / 16) : 0u;
   if (masks) b.h_masks.resize((size_t)pieces * 16);
   const uint32_t items = std::max(b.B, ident ? b.G : 0u);
@@ -2606,7 +2647,7 @@ void fetch_results(bpp_ctx *ctx, Batch &b, bool ident, bool masks) {
   b.status_settled = false;
   hipLaunchKernelGGL(k_results_out, dim3(cdiv(items, BPP_STATUS_BLOCK)), dim3(BPP_STATUS_BLOCK), 0, ctx->stream, b.status.p, b.status0.p,
                      b.h_status.dev(), b.h_status_any.dev(), b.B,
-                     ident ? b.msm.is_identity.p : (const uint32_t *)nullptr, ident ? b.h_ident.dev() : (uint32_t *)nullptr, b.G,
+                     ident ? ident_src : (const uint32_t *)nullptr, ident ? b.h_ident.dev() : (uint32_t *)nullptr, n_ident,
                      masks ? (const uint4 *)b.masks.p : (const uint4 *)nullptr, masks ? (uint4 *)b.h_masks.dev() : (uint4 *)nullptr, pieces);
   HIP_CHECK(hipGetLastError());
   b.status_clean = true;  // (in stream order: whatever is enqueued behind this launch finds status0)
@@ -2697,13 +2738,55 @@ void plan_lanes(bpp_ctx *ctx, Batch &b, bool for_phase2) {
 // (re)build the group layout + MSM term lists for `chunk`
 // `bounds` (optional): explicit group boundaries first[0..G] (0 = first[0] < ... < first[G] = B) instead of equal chunks --
 // the reference batches of different callers pooled into one call (bpp_verify_resident_groups)
-void layout_groups(bpp_ctx *ctx, Batch &b, size_t chunk, const std::vector<uint32_t> *bounds = nullptr) {
-  if (!bounds && chunk == (size_t)-1) chunk = 0;  // ((size_t)-1 marks an explicit layout in last_chunk)
-  if (bounds) {
-    if (b.last_chunk == (size_t)-1 && b.G && b.h_group_first == *bounds) return;
-  } else if (b.last_chunk == chunk && b.G) {
+// "verify_joint" = 1 and a layout of two or more groups: plan, buffers and term lists of the joint check (one group: the `cols`
+// generator columns under the joint row, then every dynamic slot), by the rules any group of its size gets -- half-scalar split for
+// small calls included, whether or not the per-group plan is split.  Nothing happens with the option off.
+// The rule (measured, DESIGN.md 4.1 "Joint final check"): the joint form is taken while the joint group has at most
+// BPP_JOINT_MAX_TERMS terms -- pooled small calls, where it is level or ahead (8 x 2 proofs: 0.170 against 0.169 ms per call, 16 x 16:
+// 0.23 against 0.26).  Above, it loses on every shape measured (16 x 256: + 15 %, 4 x 1024 at m = 8: + 14 %, 64 x 1024: + 104 %):
+// k_msm_accumulate gives a group to ONE XCD, so a single group of any size runs its additions on an eighth of the chip.  "verify_joint"
+// = 2 takes the joint form whatever the size (measurement: tools/bench_verify_joint.py).
+#define BPP_JOINT_MAX_TERMS 14000u
+bool joint_wanted(const bpp_ctx *ctx, const Batch &b) {
+  if (b.G < 2) return false;
+  return ctx->opt.verify_joint == 2 || (ctx->opt.verify_joint == 1 && b.cols + b.total_dyn <= BPP_JOINT_MAX_TERMS);
+}
+void layout_joint(bpp_ctx *ctx, Batch &b) {
+  b.need_dyn_hi = b.msm.split;
+  if (!joint_wanted(ctx, b)) return;
+  if (b.joint_G == b.G) {  // (the plan is there: what the pass needs is said again, a pass without the joint check may lie between)
+    b.need_dyn_hi = b.msm.split || b.msm_joint.split;
     return;
   }
+  // (an earlier pass's joint point outlives a new plan: msm_joint.R is one point whatever the plan, and buffers only ever grow)
+  Params &P = *b.params;
+  const uint32_t ng = b.cols + b.total_dyn;
+  const bool split = msm_wants_split(ctx, ng);
+  b.scal.alloc((size_t)b.G * b.cols + b.total_dyn + b.cols);  // the joint row behind the dynamic scalars
+  if (split) b.dyn_hi.alloc(b.total_dyn);
+  b.need_dyn_hi = b.msm.split || split;
+  msm_plan_alloc(ctx, b.msm_joint, std::vector<uint32_t>{0u, split ? 2 * ng : ng}, split, false);
+  hipLaunchKernelGGL(k_layout_terms_joint, dim3(cdiv(ng, 256)), dim3(256), 0, ctx->stream, b.G, b.cols, b.total_dyn, b.max_mn,
+                     2 * P.n_bits * P.m_max, P.table_len, split ? 1u : 0u, b.msm_joint.term_sidx.p, b.msm_joint.term_pidx.p, b.msm_joint.group_off.p);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  b.joint_G = b.G;
+}
+
+// `joint`: the caller's pass may take the joint final check (verify_flow_once, bpp_batch_prepare); every other caller -- the sharded
+// and the phased forms, a recheck's plain pass -- gets the per-group plan alone, with no launch and no buffer of the joint one
+void layout_groups(bpp_ctx *ctx, Batch &b, size_t chunk, const std::vector<uint32_t> *bounds = nullptr, bool joint = false) {
+  if (!bounds && chunk == (size_t)-1) chunk = 0;  // ((size_t)-1 marks an explicit layout in last_chunk)
+  auto tail = [&] {
+    if (joint) layout_joint(ctx, b);
+    else b.need_dyn_hi = b.msm.split;
+  };
+  if (bounds) {
+    if (b.last_chunk == (size_t)-1 && b.G && b.h_group_first == *bounds) return tail();
+  } else if (b.last_chunk == chunk && b.G) {
+    return tail();
+  }
+  b.joint_G = 0;
   Params &P = *b.params;
   uint32_t G;
   if (bounds) {
@@ -2754,6 +2837,7 @@ void layout_groups(bpp_ctx *ctx, Batch &b, size_t chunk, const std::vector<uint3
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipStreamSynchronize(ctx->stream));  // pin_small is reused by the next plan
   b.last_chunk = bounds ? (size_t)-1 : chunk;
+  tail();
 }
 
 // Weight-dependent tail: h_weights -> device, the weighted generator rows and dynamic scalars (k_scalars_lanes), the
@@ -2765,8 +2849,9 @@ void layout_groups(bpp_ctx *ctx, Batch &b, size_t chunk, const std::vector<uint3
 // generator columns keeps k_chain_finish_bytes in front
 // plain_groups (pass 2 of "verify_check"): the final MSM of those groups alone, through the plain kernels (msm_plain.h); the layout is
 // then an unsplit one
+// joint ("verify_joint"): the joint row and ONE MSM over all groups (b.msm_joint) instead of the per-group MSMs
 void enqueue_phase2(bpp_ctx *ctx, Batch &b, StageTimer &tm, bool weights_resident = false, bool wide = false,
-                    const std::vector<uint32_t> *plain_groups = nullptr) {
+                    const std::vector<uint32_t> *plain_groups = nullptr, bool joint = false) {
   Params &P = *b.params;
   hipStream_t s = ctx->stream;
   // (weights_resident: the grouped sharded form has put them into b.weights device -> device already)
@@ -2821,7 +2906,13 @@ void enqueue_phase2(bpp_ctx *ctx, Batch &b, StageTimer &tm, bool weights_residen
     return;
   }
   PointTables tabs{P.table.p, b.dynpts.p, P.table_len, P.table_hi.p, b.dyn_hi.p};
-  msm_run(ctx, b.msm, b.scal.p, tabs, &tm);
+  if (joint) {
+    hipLaunchKernelGGL(k_joint_row, dim3(cdiv(b.cols, 64)), dim3(64), 0, s, b.scal.p, b.G, b.cols, b.scal.p + (size_t)b.G * b.cols + b.total_dyn);
+    msm_run(ctx, b.msm_joint, b.scal.p, tabs, &tm);
+  } else {
+    b.joint_accepted = false;  // (whichever entry point runs them: the per-group results are this pass's again)
+    msm_run(ctx, b.msm, b.scal.p, tabs, &tm);
+  }
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2859,7 +2950,7 @@ int bpp_batch_prepare(bpp_ctx *ctx, uint64_t batch, size_t chunk) {
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
     StageTimer tm(ctx);  // creates the profiling events when profiling is on
     ensure_ev_rng(ctx);
-    layout_groups(ctx, *it->second, chunk);  // group layout, MSM plan and every work buffer of that plan
+    layout_groups(ctx, *it->second, chunk, nullptr, true);  // group layout, both MSM plans and every work buffer of theirs
     it->second->h_ident.resize(it->second->G);
     return BPP_OK;
   }
@@ -2951,6 +3042,11 @@ int verify_flow_once(bpp_ctx *ctx, ResidentRun &run, size_t chunk, const std::ve
   const bool pass1_only = b.any_rounds_bad && b.G == 1;
   const bool want_msm = !pass1_only && any_msm;
   const bool want_masks = !pass1_only && any_masks && b.any_seed;
+  // "verify_joint": one MSM over all groups of the pass when every group is held to the final check (a RecoverOnly group is not)
+  // and the pass is no recheck's plain pass; its failure is answered by the per-group MSMs below (bpp.h, "Joint final check")
+  bool joint = want_msm && joint_wanted(ctx, b) && !run.plain_groups;
+  for (uint32_t g = 0; g < b.G && joint; g++) joint = action_of(g) != BPP_RECOVER_ONLY;
+  if (joint) layout_joint(ctx, b);  // (its plan and term lists exist from the first pass on that can take it, or from bpp_batch_prepare)
   const ChainMode cmode = want_msm ? chain_mode(ctx, b, allow_dev_chain) : CHAIN_HOST;
   enqueue_phase1(ctx, b, tm, !want_msm, nullptr, 0, 0, cmode == CHAIN_DEVICE);
 
@@ -2973,17 +3069,44 @@ int verify_flow_once(bpp_ctx *ctx, ResidentRun &run, size_t chunk, const std::ve
     run.have_masks = true;
   }
   if (want_msm) {
-    enqueue_phase2(ctx, b, tm, cmode != CHAIN_HOST, cmode == CHAIN_HOST_WIDE, run.plain_groups);
+    enqueue_phase2(ctx, b, tm, cmode != CHAIN_HOST, cmode == CHAIN_HOST_WIDE, run.plain_groups, joint);
     b.have_trace = true;
   }
-  fetch_results(ctx, b, want_msm, want_masks);
+  fetch_results(ctx, b, want_msm, want_masks, joint);
   // (the remembered wait belongs to the batch's size and group count and to what actually ran: equal work shares it)
   gpu_wait_stream(ctx, s, wait_naps(ctx, b.B), &ctx->wait_hint_end,
                   ((uint64_t)b.B << 32) | ((uint64_t)b.G << 2) | (uint64_t)((want_msm ? 1 : 0) | (want_masks ? 2 : 0)) |
-                      (run.plain_groups ? 1ull << 63 : 0ull));  // (a recheck's pass 2 is other work: it does not teach the next call how long to nap)
+                      (run.plain_groups ? 1ull << 63 : 0ull) | (joint ? 1ull << 62 : 0ull));  // (a recheck's pass 2 and a joint pass are other
+                                                                                               // work: they do not teach the next call how long to nap)
   if (want_msm && cmode != CHAIN_HOST && ctx->h_chain_zero[0]) {
     ctx->device_chain_redraws++;
     return BPP_REDRAW_ON_HOST;
+  }
+  bool joint_fell_back = false;
+  if (joint) {
+    struct bpp_verify_joint_stats &js = ctx->vjoint_stats;
+    js.calls++;
+    b.joint_ran = true;  // (stays: a recheck's passes 2 and 3, a sharded or phased call after it do not run the joint check)
+    b.joint_accepted = false;
+    bool ok = b.h_ident[0] != 0;
+    if (run.tamper && run.tamper_kind == 5) ok = false;  // test knob: the verdict as the host holds it, nothing else
+    if (ok) {
+      js.accepted++;
+      b.joint_accepted = true;
+      for (uint32_t g = 0; g < b.G; g++) b.h_ident[g] = 1;
+    } else {
+      // the per-group MSMs of today over the same scalars (nothing in front of the MSM runs again); their flags come back by
+      // k_results_out with no proof to look at: status words and masks are the first wait's
+      js.fallbacks++;
+      joint_fell_back = true;
+      PointTables tabs{P.table.p, b.dynpts.p, P.table_len, P.table_hi.p, b.dyn_hi.p};
+      msm_run(ctx, b.msm, b.scal.p, tabs, nullptr);
+      hipLaunchKernelGGL(k_results_out, dim3(cdiv(b.G, BPP_STATUS_BLOCK)), dim3(BPP_STATUS_BLOCK), 0, s, b.status.p, b.status0.p, b.h_status.dev(),
+                         b.h_status_any.dev(), 0u, b.msm.is_identity.p, b.h_ident.dev(), b.G, (const uint4 *)nullptr, (uint4 *)nullptr, 0u);
+      HIP_CHECK(hipGetLastError());
+      // (a memory of its own, keyed as joint + fall-back: a rejected call does not teach the accepted ones how long to nap)
+      gpu_wait_stream(ctx, s, wait_naps(ctx, b.B), &ctx->wait_hint_fallback, ((uint64_t)b.B << 32) | ((uint64_t)b.G << 2) | (3ull << 61));
+    }
   }
   collect_profile(ctx, b, tm, chain_ms, std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_begin).count());
   if (run.plain_groups) {  // groups whose MSM this pass did not run: nothing is claimed about them
@@ -3020,6 +3143,11 @@ int verify_flow_once(bpp_ctx *ctx, ResidentRun &run, size_t chunk, const std::ve
       if (want_msm && action_of(g) != BPP_RECOVER_ONLY && !b.h_ident[g])
         throw ProofErr{BPP_ERR_VERIFICATION_FAILED, "Range proof batch not valid", BPP_TIER_MSM, p0};
     });
+  }
+  if (joint_fell_back) {
+    bool all_ok = true;
+    for (uint32_t g = 0; g < b.G; g++) all_ok = all_ok && run.found[g].tier == BPP_TIER_NONE;
+    if (all_ok) ctx->vjoint_stats.fallback_all_ok++;
   }
   return BPP_OK;
 }
@@ -3142,7 +3270,7 @@ void verify_flow(bpp_ctx *ctx, ResidentRun &run, size_t chunk, const std::vector
     pass(3);
     p3 = run.found;
   } else {
-    layout_groups(ctx, b, chunk, bounds);
+    layout_groups(ctx, b, chunk, bounds, true);
   }
   unswap();
   run.found = p1;
@@ -3755,7 +3883,15 @@ int bpp_batch_trace(bpp_ctx *ctx, uint64_t batch, int what, uint8_t *out, size_t
         need = (size_t)b.total_dyn * 32;
         src = b.scal.p + (size_t)b.G * b.cols;
         break;
+      case BPP_TRACE_JOINT_RESULT:  // the joint final check's point, of the last pass that took it
+        if (!b.joint_ran) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "no verification pass of this batch has taken the joint final check");
+        need = 32;
+        hipLaunchKernelGGL(k_compress_ge, dim3(1), dim3(64), 0, s, b.msm_joint.R.p, 1u, b.msm_joint.comp32.p);
+        src = b.msm_joint.comp32.p;
+        break;
       case BPP_TRACE_MSM_RESULT:  // encoded on demand: verification itself only tests for the identity
+        if (b.joint_accepted)
+          return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "no per-group MSM results: the joint final check accepted and the per-group MSMs did not run");
         need = (size_t)b.G * 32;
         hipLaunchKernelGGL(k_compress_ge, dim3(cdiv(b.G, 64)), dim3(64), 0, s, b.msm.R.p, b.G, b.msm.comp32.p);
         src = b.msm.comp32.p;
@@ -3900,6 +4036,21 @@ int bpp_verify_check_stats(bpp_ctx *ctx, struct bpp_verify_check_stats *out) {
     for (auto &l : pp->lanes) {
       std::lock_guard<std::mutex> lk(l->child->mu);
       add_stats(*out, l->child->vcheck_stats);
+    }
+  return BPP_OK;
+}
+
+int bpp_verify_joint_stats(bpp_ctx *ctx, struct bpp_verify_joint_stats *out) {
+  if (!ctx || !out) return BPP_ERR_BAD_HANDLE;
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    *out = ctx->vjoint_stats;
+  }
+  // the packed pipeline's lanes: contexts of their own, made on the first submit
+  if (const std::shared_ptr<Pipeline> pp = pipeline_peek(ctx->pipe_init_mu, ctx->pipe))
+    for (auto &l : pp->lanes) {
+      std::lock_guard<std::mutex> lk(l->child->mu);
+      add_stats(*out, l->child->vjoint_stats);
     }
   return BPP_OK;
 }

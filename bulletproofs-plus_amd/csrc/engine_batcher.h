@@ -180,8 +180,12 @@ int bpp_batcher_create(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *sh
   if (lanes == 0) lanes = 2;  // (two pooled calls in flight keep the pools large; three are within run-to-run noise of two, four and six lose)
   if (lanes > 8) lanes = 8;
   std::vector<bpp_batcher::Lane> made;
-  // a lane rechecks its rejections when the context it was made from does ("verify_check", read as it is now)
-  const int rc = make_pool_lanes(ctx, params, lanes, [](bpp_ctx *c, const bpp_ctx::Options &opt) { c->opt.verify_check = opt.verify_check; }, made);
+  // a lane rechecks its rejections and takes the joint final check when the context it was made from does ("verify_check",
+  // "verify_joint", read as they are now)
+  const int rc = make_pool_lanes(ctx, params, lanes, [](bpp_ctx *c, const bpp_ctx::Options &opt) {
+    c->opt.verify_check = opt.verify_check;
+    c->opt.verify_joint = opt.verify_joint;
+  }, made);
   if (rc != BPP_OK) return rc;
   auto b = std::make_unique<bpp_batcher>(std::move(made), max_wait_us, max_calls ? max_calls : 64);
   b->params = params;
@@ -221,6 +225,17 @@ int bpp_batcher_verify_check_stats(bpp_batcher *b, struct bpp_verify_check_stats
   b->pool.for_each_lane([&](bpp_batcher::Lane &L) {  // (the first lane is the caller's context: bpp_verify_check_stats adds its pipeline's lanes)
     struct bpp_verify_check_stats one;
     if (rc == BPP_OK && (rc = bpp_verify_check_stats(L.ctx, &one)) == BPP_OK) add_stats(*out, one);
+  });
+  return rc;
+}
+
+int bpp_batcher_verify_joint_stats(bpp_batcher *b, struct bpp_verify_joint_stats *out) {
+  if (!b || !out) return BPP_ERR_BAD_HANDLE;
+  memset(out, 0, sizeof(*out));
+  int rc = BPP_OK;
+  b->pool.for_each_lane([&](bpp_batcher::Lane &L) {  // (the first lane is the caller's context: bpp_verify_joint_stats adds its pipeline's lanes)
+    struct bpp_verify_joint_stats one;
+    if (rc == BPP_OK && (rc = bpp_verify_joint_stats(L.ctx, &one)) == BPP_OK) add_stats(*out, one);
   });
   return rc;
 }

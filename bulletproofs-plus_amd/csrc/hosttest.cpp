@@ -232,6 +232,29 @@ int ht_msm_recode_split(const uint8_t a[32], uint32_t c, int16_t *out_lo, int16_
     widths[k] = k < plan.K_wide ? plan.c : plan.c - 1;
   }
   return (int)plan.K; }
+// the MSM plan's rules (recode.h): the window width of a group, whether a prelude form holds its bucket tables in a workgroup's
+// LDS (what msm_plan_alloc asks before it allocates), the least bytes such a workgroup needs, the slices of the sliced form
+uint32_t ht_msm_choose_window(uint32_t group_terms, uint32_t all_terms, int c_max, int c_add, int bias) {
+  return msm_choose_window(group_terms, all_terms, c_max, c_add, bias); }
+int ht_msm_prelude_fits(uint32_t nb, uint32_t threads, uint32_t form) { return msm_prelude_fits(nb, threads, form) ? 1 : 0; }
+uint32_t ht_msm_prelude_min_lds(uint32_t nb, uint32_t threads, uint32_t form) { return msm_prelude_min_lds(nb, threads, form); }
+uint32_t ht_msm_prelude_slices(uint32_t max_group_terms, uint32_t G, uint32_t K, uint32_t nb, uint32_t threads, int forced) {
+  return msm_prelude_slices(max_group_terms, G, K, nb, threads, forced); }
+// every group size lo .. hi under the engine's own rule: c_out[n - lo] = the window width of a group of n terms in a call of
+// n (mode 0), 64 n (mode 1) or max(n, 30 000) (mode 2) terms; returns the first n whose plan does not fit a workgroup's LDS in one
+// of the two prelude forms at 256 or 1024 lanes, 0 when all of them fit
+uint32_t ht_msm_window_sweep(uint32_t lo, uint32_t hi, int mode, uint8_t *c_out) {
+  uint32_t bad = 0;
+  for (uint32_t n = lo; n <= hi && n >= lo; n++) {
+    const uint64_t all = mode == 0 ? n : mode == 1 ? 64ull * n : (n > 30000u ? n : 30000u);
+    const uint32_t c = msm_choose_window(n, all > 0xffffffffull ? 0xffffffffu : (uint32_t)all);
+    c_out[n - lo] = (uint8_t)c;
+    const uint32_t nb = 1u << (c - 1);
+    for (uint32_t threads : {256u, 1024u})
+      for (uint32_t form : {0u, 1u})
+        if (!bad && !msm_prelude_fits(nb, threads, form)) bad = n;
+  }
+  return bad; }
 int ht_fb_recode(const uint8_t a[32], uint32_t n_gens, int16_t *digits /* 32 */, uint32_t *wbits) {
   sc x; sc_load_words(x, a);
   const FbGeom g = fb_geometry(n_gens);

@@ -1155,6 +1155,47 @@ __global__ void __launch_bounds__(256) k_layout_terms(const uint32_t *__restrict
   }
 }
 
+// ---- The joint final check ("verify_joint" = 1): ONE group over all reference batches of the call.  Its terms: the `cols`
+// generator columns under the joint row J[c] = sum_g scal[g cols + c] mod l, which k_joint_row leaves BEHIND the dynamic scalars
+// (scal[G cols + total_dyn + c]: no existing offset moves), then every dynamic slot with the scalar it already has.
+// term_pidx is what k_layout_terms gives a one-group layout.  grid = ceil((cols + total_dyn) / 256) workgroups of 256.
+__global__ void __launch_bounds__(256) k_layout_terms_joint(uint32_t G, uint32_t cols, uint32_t total_dyn, uint32_t max_mn, uint32_t n_gen,
+                                                            uint32_t table_len, uint32_t split, uint32_t *__restrict__ term_sidx,
+                                                            uint32_t *__restrict__ term_pidx, uint32_t *__restrict__ goff_dev) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, ng = cols + total_dyn;
+  if (i == 0) {
+    goff_dev[0] = 0;
+    goff_dev[1] = ng << split;
+  }
+  if (i >= ng) return;
+  uint32_t si, pi;
+  if (i < cols) {
+    si = G * cols + total_dyn + i;
+    pi = i < 2 * max_mn ? i : n_gen + (i - 2 * max_mn);
+  } else {
+    si = G * cols + (i - cols);
+    pi = table_len + (i - cols);
+  }
+  term_sidx[i] = si;
+  term_pidx[i] = pi;
+  if (split) {
+    term_sidx[ng + i] = si | BPP_TERM_HI;
+    term_pidx[ng + i] = pi | BPP_POINT_HI;
+  }
+}
+// J[c] = sum of the G canonical rows' column c, mod l: one lane per column, G - 1 modular additions.  Plain vector loads and stores.
+__global__ void __launch_bounds__(64) k_joint_row(const sc *__restrict__ rows /* [G][cols] canonical */, uint32_t G, uint32_t cols,
+                                                  sc *__restrict__ out /* [cols] */) {
+  const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= cols) return;
+  sc acc = rows[c];
+  for (uint32_t g = 1; g < G; g++) {
+    const sc v = rows[(size_t)g * cols + c];
+    sc_add(acc, acc, v);
+  }
+  out[c] = acc;
+}
+
 // Column sums per group: static[g][col] = sum_{p in g} rows[p][col], rows already weighted by k_scalars_lanes (the `+=`
 // into gi/hi/g/h_base_scalars of src/range_proof.rs:785-788,999-1020).  One wavefront per (tile of 4 columns, group):
 // lane = (proof slot, column in tile), so the four lanes of a proof slot read 4 x 32 = 128 CONTIGUOUS bytes of one proof's

@@ -239,7 +239,172 @@ inline uint32_t msm_prelude_dig_cap(const MsmPlan &plan, uint32_t max_group_term
   const uint32_t room = fixed + 1024u < 65536u ? (65536u - 1024u - fixed) / 2u : 0u;
   return max_group_terms < room ? max_group_terms : room;
 }
+// LDS bytes per workgroup for every (c, form) the window rule can produce (nb = 2^(c-1); form 0: k_msm_prelude<T>, two tables
+// + T + 768 static words, "+ cache" = cached digits up to 64 512 bytes in all; form 1: the sliced prelude below, one table in
+// k_msm_slice_hist / _scatter | the static arrays of k_msm_slice_scan).  The limit is a gfx950 workgroup's 163 840 bytes:
+//     c      nb    form 0, T = 1024    form 0, T = 256    form 1 (hist / scatter | scan)
+//   4..11  <=1024   <=15 360 + cache    <=12 288 + cache    <= 4 096 | 7 168
+//    12     2048     23 552 + cache      20 480 + cache        8 192 | 7 168
+//    13     4096     39 936 + cache      36 864 + cache       16 384 | 7 168
+//    14     8192     72 704, no cache    69 632, no cache     32 768 | 7 168
+// Both forms hold 14-bit windows: form 0 past msm_prelude_dig_cap's 64 KB budget (it caches nothing then) and inside the limit.
+// msm_prelude_fits (recode.h, host-compiled by the tests as well) is the check msm_plan_alloc makes before anything is launched.
 inline size_t msm_prelude_lds(const MsmPlan &plan, uint32_t dig_cap) { return (size_t)2 * plan.nb * 4 + (size_t)((dig_cap + 1u) & ~1u) * 2; }
+
+// ---- The prelude for LARGE groups ("sliced"; option "msm_prelude_slices", by rule from BPP_WIDE_WINDOW_TERMS terms per group):
+// the sort of one (group, window) is cut into S slices of consecutive terms, one workgroup of 256 lanes each, so that a single
+// group of a million terms fills the chip instead of ~20 CUs, and no workgroup holds more than ONE bucket table in LDS (14-bit
+// windows: 32 KB).  Three launches -- nothing waits across workgroups inside a kernel:
+//   k_msm_slice_hist     workgroup (g, k, s): histogram by |digit| of its slice in LDS, written whole to slice_hist[g][k][s][nb]
+//                        (plain vector stores, zeros included: the buffer needs no clearing)
+//   k_msm_slice_scan     workgroup (g, k): bucket totals over the slices -> counts[] / starts[] exactly as k_msm_prelude leaves
+//                        them, every slice's write offset per bucket (in place of its histogram), and the window's size ordering
+//                        (order_win[], cls_hist[])
+//   k_msm_slice_scatter  workgroup (g, k, s): its offsets into LDS, then the same scatter as k_msm_prelude's pass 2 (digits are
+//                        computed again: no cache)
+// Slice s of a group of ng terms holds terms [s L, min((s + 1) L, ng)), L = ceil(ng / S): empty when S > ng.  Inside a bucket
+// the terms of slice s precede those of slice s + 1; within a slice their order is the atomics' (as in the one-workgroup form,
+// the accumulation does not depend on it).  Everything behind the prelude reads the same arrays in the same layout.
+__device__ __forceinline__ void msm_slice_range(uint32_t ng, uint32_t S, uint32_t s, uint32_t &lo, uint32_t &hi) {
+  const uint32_t L = (ng + S - 1u) / S;
+  lo = s * L < ng ? s * L : ng;
+  hi = ng - lo > L ? lo + L : ng;
+}
+__global__ void __launch_bounds__(BPP_SLICE_THREADS) k_msm_slice_hist(const sc *__restrict__ scalars, const uint32_t *__restrict__ term_sidx,
+                                                                       const uint32_t *__restrict__ group_off, MsmPlan plan, uint32_t S,
+                                                                       uint32_t *__restrict__ slice_hist) {
+  extern __shared__ uint32_t lds[];
+  constexpr uint32_t T = BPP_SLICE_THREADS;
+  const uint32_t tid = threadIdx.x, nb = plan.nb, K = plan.K;
+  const uint32_t s = blockIdx.x % S, gk = blockIdx.x / S, g = gk / K, k = gk % K;
+  if (g >= plan.G) return;
+  const uint32_t t0 = group_off[g], ng = group_off[g + 1] - t0;
+  uint32_t lo, hi;
+  msm_slice_range(ng, S, s, lo, hi);
+  for (uint32_t q = tid; q < nb; q += T) lds[q] = 0;
+  __syncthreads();
+  for (uint32_t i0 = lo + tid; i0 < hi; i0 += 4 * T) {  // four scalars in flight per lane before the first atomic
+    uint32_t si[4];
+    int32_t d[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) si[u] = (i0 + u * T < hi) ? term_sidx[t0 + i0 + u * T] : 0xffffffffu;
+#pragma unroll
+    for (int u = 0; u < 4; u++) d[u] = si[u] != 0xffffffffu ? msm_term_digit(scalars, si[u], plan, k) : 0;
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (d[u]) atomicAdd(&lds[(uint32_t)(d[u] < 0 ? -d[u] : d[u]) - 1], 1u);
+  }
+  __syncthreads();
+  uint32_t *out = slice_hist + (size_t)blockIdx.x * nb;
+  for (uint32_t q = tid; q < nb; q += T) out[q] = lds[q];
+}
+
+__global__ void __launch_bounds__(BPP_SLICE_SCAN_THREADS) k_msm_slice_scan(uint32_t *__restrict__ slice_hist, const uint32_t *__restrict__ group_off,
+                                                                            MsmPlan plan, uint32_t S, uint32_t *counts,
+                                                                            uint32_t *__restrict__ starts, uint32_t *__restrict__ order_win,
+                                                                            uint32_t *__restrict__ cls_hist) {
+  constexpr uint32_t T = BPP_SLICE_SCAN_THREADS;
+  const uint32_t tid = threadIdx.x, nb = plan.nb, K = plan.K;
+  const uint32_t gk = blockIdx.x, g = gk / K, k = gk % K;
+  if (g >= plan.G) return;
+  __shared__ uint32_t part[T];
+  __shared__ uint32_t cls_n[256], cls_start[256], cls_cur[256];
+  const uint32_t t0 = group_off[g], ng = group_off[g + 1] - t0;
+  const uint32_t region = t0 * K + k * ng;
+  uint32_t *rows = slice_hist + (size_t)gk * S * nb;  // [S][nb]
+  const size_t bbase = (size_t)gk * nb;
+  if (tid < 256) cls_n[tid] = cls_cur[tid] = 0;
+  // thread t owns a contiguous run of `per` bins, as in k_msm_prelude
+  const uint32_t per = (nb + T - 1u) / T;
+  const uint32_t a = tid * per < nb ? tid * per : nb, b = (a + per < nb) ? a + per : nb;
+  uint32_t sum = 0;
+  for (uint32_t q = a; q < b; q++) {
+    uint32_t tot = 0;
+    for (uint32_t s = 0; s < S; s++) tot += rows[(size_t)s * nb + q];
+    counts[bbase + q] = tot;  // (read back below by the lane that wrote it)
+    sum += tot;
+  }
+  part[tid] = sum;
+  __syncthreads();
+  for (uint32_t off = 1; off < T; off <<= 1) {
+    uint32_t v = (tid >= off) ? part[tid - off] : 0;
+    __syncthreads();
+    part[tid] += v;
+    __syncthreads();
+  }
+  uint32_t run = (tid == 0) ? 0 : part[tid - 1];
+  for (uint32_t q = a; q < b; q++) {
+    const uint32_t cnt = counts[bbase + q];
+    starts[bbase + q] = region + run;
+    uint32_t at = run;  // slice s writes bucket q from here on (relative to the region)
+    for (uint32_t s = 0; s < S; s++) {
+      const uint32_t h = rows[(size_t)s * nb + q];
+      rows[(size_t)s * nb + q] = at;
+      at += h;
+    }
+    run += cnt;
+    atomicAdd(&cls_n[cnt < 255u ? cnt : 255u], 1u);  // size classes of this window's buckets
+  }
+  __syncthreads();
+  // the window's buckets by descending size class: k_msm_prelude's "order, step 1", word for word
+  uint32_t *gh = cls_hist + (size_t)g * K * 768;
+  if (tid < 256) part[tid] = cls_n[tid];
+  __syncthreads();
+  for (uint32_t off = 1; off < 256; off <<= 1) {
+    uint32_t v = (tid < 256 && tid + off < 256) ? part[tid + off] : 0;
+    __syncthreads();
+    if (tid < 256) part[tid] += v;
+    __syncthreads();
+  }
+  if (tid < 256) {
+    cls_start[tid] = part[tid] - cls_n[tid];
+    gh[k * 768 + tid] = cls_n[tid];
+    gh[k * 768 + 256 + tid] = cls_start[tid];
+  }
+  __syncthreads();
+  for (uint32_t q = a; q < b; q++) {
+    const uint32_t cnt = counts[bbase + q], cls = cnt < 255u ? cnt : 255u;
+    const uint32_t pos = cls_start[cls] + atomicAdd(&cls_cur[cls], 1u);
+    order_win[bbase + pos] = (uint32_t)(bbase + q);
+  }
+}
+
+__global__ void __launch_bounds__(BPP_SLICE_THREADS) k_msm_slice_scatter(const sc *__restrict__ scalars, const uint32_t *__restrict__ term_sidx,
+                                                                          const uint32_t *__restrict__ term_pidx,
+                                                                          const uint32_t *__restrict__ group_off, MsmPlan plan, uint32_t S,
+                                                                          const uint32_t *__restrict__ slice_offs, uint32_t *__restrict__ sorted) {
+  extern __shared__ uint32_t lds[];
+  constexpr uint32_t T = BPP_SLICE_THREADS;
+  const uint32_t tid = threadIdx.x, nb = plan.nb, K = plan.K;
+  const uint32_t s = blockIdx.x % S, gk = blockIdx.x / S, g = gk / K, k = gk % K;
+  if (g >= plan.G) return;
+  const uint32_t t0 = group_off[g], ng = group_off[g + 1] - t0;
+  const uint32_t region = t0 * K + k * ng;
+  uint32_t lo, hi;
+  msm_slice_range(ng, S, s, lo, hi);
+  if (lo >= hi) return;  // (the whole workgroup: an empty slice writes nothing)
+  const uint32_t *offs = slice_offs + (size_t)blockIdx.x * nb;
+  for (uint32_t q = tid; q < nb; q += T) lds[q] = offs[q];
+  __syncthreads();
+  for (uint32_t i0 = lo + tid; i0 < hi; i0 += 4 * T) {
+    uint32_t si[4], pi[4];
+    int32_t d[4];
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const bool in = i0 + u * T < hi;
+      si[u] = in ? term_sidx[t0 + i0 + u * T] : 0xffffffffu;
+      pi[u] = in ? term_pidx[t0 + i0 + u * T] : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; u++) d[u] = si[u] != 0xffffffffu ? msm_term_digit(scalars, si[u], plan, k) : 0;
+#pragma unroll
+    for (int u = 0; u < 4; u++)
+      if (d[u]) {
+        const uint32_t pos = atomicAdd(&lds[(uint32_t)(d[u] < 0 ? -d[u] : d[u]) - 1], 1u);
+        if (pos < ng) sorted[region + pos] = pi[u] | (d[u] < 0 ? 0x80000000u : 0u);  // point index, sign in bit 31
+      }
+  }
+}
 
 // ---- bucket sums: one lane per bucket.  XCD-aware work mapping: workgroups are dealt round-robin over the 8 XCDs
 // (blockIdx % 8), so XCD x takes the groups x, x+8, x+16, ... one after the other; a group's buckets (in size order)

@@ -101,6 +101,80 @@ inline MsmPlan msm_make_plan(uint32_t c, uint32_t G, uint32_t n_terms, uint32_t 
   plan.split = bits == 253 ? 0u : 1u;
   return plan;
 }
+// Window width of a group of `group_terms` terms in a call of `all_terms` (the engine's choose_window with the context's options
+// spelled out: c_max_opt / bias_opt < 0 and c_add <= 0 mean the engine's own rule).  Host-compiled by the tests as well.
+#define BPP_SMALL_CALL_TERMS 20000u     // a call of up to this many MSM terms has the chip to itself
+#define BPP_WIDE_WINDOW_TERMS 200000u   // groups from here on may take windows above 11 bits -- and the sliced prelude (msm.h)
+inline uint32_t msm_choose_window(uint32_t group_terms, uint32_t all_terms, int c_max_opt = -1, int c_add = 0, int bias_opt = -1) {
+  // buckets per window ~ terms / 12  (bucket lists of ~12 points keep the per-lane chains short)
+  uint32_t c = 4;
+  while (c < 14 && (1u << c) * 12u <= group_terms) c++;  // nb = 2^(c-1)
+  // Above 11 bits the buckets of a window no longer fit the row / column reduction (2.1 additions per bucket, k_msm_window_rc)
+  // and go through the bit-plane one (c / 2 per bucket): 13 bits for a 4096-proof batch (61 k terms) is 20 x 61 k + 20 x 4096
+  // x 6.5 = 1.76 M additions, 11 bits 23 x 61 k + 23 x 1024 x 2.1 = 1.47 M.  The wider windows only pay from ~200 k terms on.
+  const uint32_t c_max = c_max_opt >= 0 ? (uint32_t)c_max_opt : (group_terms < BPP_WIDE_WINDOW_TERMS ? 11u : 14u);
+  if (c_add > 0 && all_terms > BPP_SMALL_CALL_TERMS) c += (uint32_t)c_add;  // (A/B timing of wider windows)
+  if (c > c_max && c_max >= 4) c = c_max;
+  // A small call has the chip to itself: its time is the length of the dependency chains, not the number of additions.
+  // Wider windows shorten the bucket lists (accumulation) and the Horner step (fewer windows to add) for a longer
+  // row / column reduction: three more bits are worth 0.07-0.1 ms up to a few hundred proofs (one proof 0.79 -> 0.68 ms).
+  const int bias = bias_opt >= 0 ? bias_opt : 3;  // (tests run the narrow windows as well)
+  if (all_terms <= BPP_SMALL_CALL_TERMS) {
+    int cb = (int)c + bias;
+    c = (uint32_t)(cb < 4 ? 4 : (cb > 11 ? 11 : cb));
+  }
+  return c;
+}
+
+// ---- The two forms of the MSM's prelude (msm.h) and what a workgroup of each needs in LDS.
+//   form 0  k_msm_prelude<T>: one workgroup of T lanes per (group, window).  Two bucket tables of nb words (histogram, write
+//           cursors) in dynamic LDS, T + 3 x 256 words of static arrays (part[], cls_*), and as many cached digits (two bytes
+//           each) as keep the workgroup 1 KB under 64 KB -- a BUDGET (two such workgroups per CU), not the hardware's limit.
+//   form 1  the sliced prelude: k_msm_slice_hist / k_msm_slice_scatter hold ONE bucket table of nb words (256 lanes, nothing
+//           static); k_msm_slice_scan holds BPP_SLICE_SCAN_THREADS + 3 x 256 words of static arrays and no table.
+// A gfx950 workgroup may hold 160 KiB of LDS (the whole CU's), so the limit a plan is held to is 163 840 bytes.
+// Bytes per workgroup for every (c, form) the window rule can produce (nb = 2^(c-1); "+ cache" = digits, up to 64 512 in all):
+//     c      nb    form 0, T = 1024    form 0, T = 256    form 1 (hist / scatter | scan)
+//   4..11  <=1024   <=15 360 + cache    <=12 288 + cache    <= 4 096 | 7 168
+//    12     2048     23 552 + cache      20 480 + cache        8 192 | 7 168
+//    13     4096     39 936 + cache      36 864 + cache       16 384 | 7 168
+//    14     8192     72 704, no cache    69 632, no cache     32 768 | 7 168
+// 14-bit windows in form 0 are past the 64 KB budget (msm_prelude_dig_cap then caches nothing) and inside the limit: one such
+// workgroup per (group, window) runs -- tests/test_gpu_msm_structured.py has it at 25 000 terms -- with two per CU at most.  Groups
+// that get 14 bits by rule (BPP_WIDE_WINDOW_TERMS terms and more) take form 1 by rule as well: 32 KB, five workgroups per CU.
+// msm_prelude_fits is what msm_plan_alloc asks before anything is allocated or launched; forced widths above 14 bits are what
+// it refuses (c = 16, form 0: 269 312 bytes).
+#define BPP_LDS_LIMIT 163840u
+#define BPP_SLICE_THREADS 256u
+#define BPP_SLICE_SCAN_THREADS 1024u
+#define BPP_SLICES_MAX 64u
+// the least a workgroup of the form needs (form 0: without any cached digit)
+inline uint32_t msm_prelude_min_lds(uint32_t nb, uint32_t threads, uint32_t form) {
+  if (form == 0) return 2u * nb * 4u + (threads + 3u * 256u) * 4u;
+  const uint32_t table = nb * 4u, scan = (BPP_SLICE_SCAN_THREADS + 3u * 256u) * 4u;
+  return table > scan ? table : scan;
+}
+inline bool msm_prelude_fits(uint32_t nb, uint32_t threads, uint32_t form) {
+  return nb != 0 && nb <= (1u << 20) && msm_prelude_min_lds(nb, threads, form) <= BPP_LDS_LIMIT;
+}
+// How many slices the (group, window) sorts of a plan are cut into; 0: the one-workgroup form.  forced >= 2: that many, whatever
+// the size (option "msm_prelude_slices"); forced == 1: the one-workgroup form whatever the size (A/B timing of the two forms).
+// By rule a group of BPP_WIDE_WINDOW_TERMS terms and more is sliced -- with one workgroup per (group, window) such a call puts ~20 workgroups on 256 CUs, each walking its group's terms twice -- and so is a
+// plan whose tables fit form 1 only.  S aims at 640 workgroups per phase (two and a half per CU) and keeps 2048 terms per slice:
+// measured on one group of 1 048 706 terms at 14 bits (19 windows), the three launches took 1.25 / 1.10 / 1.25 / 1.32 ms with S =
+// 16 / 32 / 54 / 64 against 3.90 ms in the one-workgroup form (profiles/verify_joint.json).
+inline uint32_t msm_prelude_slices(uint32_t max_group_terms, uint32_t G, uint32_t K, uint32_t nb, uint32_t threads, int forced) {
+  if (forced >= 2) return (uint32_t)forced < BPP_SLICES_MAX ? (uint32_t)forced : BPP_SLICES_MAX;
+  if (forced == 1) return 0;
+  if (max_group_terms < BPP_WIDE_WINDOW_TERMS && msm_prelude_fits(nb, threads, 0)) return 0;
+  const uint32_t gk = G * K ? G * K : 1u;
+  uint32_t S = (640u + gk - 1u) / gk;
+  const uint32_t by_terms = (max_group_terms + 2047u) / 2048u;
+  if (S > by_terms) S = by_terms;
+  if (S > BPP_SLICES_MAX) S = BPP_SLICES_MAX;
+  return S < 2u ? 2u : S;
+}
+
 // the half of a canonical scalar a split plan's term stands for, as eight words (upper ones zero)
 BPP_HD void msm_half_words(uint32_t h[8], const uint32_t *w, bool hi) {
   constexpr uint32_t W = BPP_MSM_SPLIT_BIT >> 5, SH = BPP_MSM_SPLIT_BIT & 31u;  // 126 = 3 * 32 + 30

@@ -189,6 +189,12 @@ class Batcher:
         self.engine.lib.bpp_batcher_stats(self.handle, *[byref(x) for x in v])
         return dict(zip(("pooled_calls", "engine_calls", "solo_calls"), [x.value for x in v]))
 
+    def verify_joint_stats(self):
+        """bpp_batcher_verify_joint_stats: the joint final checks ("verify_joint" = 1) of the batcher's lanes, summed"""
+        s = _lib.VerifyJointStats()
+        api._check(self.engine.lib.bpp_batcher_verify_joint_stats(self.handle, byref(s)), None)
+        return {n: int(getattr(s, n)) for n, _ in _lib.VerifyJointStats._fields_}
+
     def close(self):
         if self.handle:
             self.engine.lib.bpp_batcher_destroy(self.handle)

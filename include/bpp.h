@@ -119,7 +119,18 @@ const char *bpp_ctx_last_error(bpp_ctx *ctx);
  * reads 0 (a false MSM rejection); 2: it reads 1 and the device bits of the group's status words are cleared (a false acceptance);
  * 3 / 4: the PASS-1 / decompression failure bit is set in the status word of the group's first proof; a value above 15 holds one
  * kind per pass, four bits each, pass 1 in the lowest.  The knobs alter bytes of
- * page-locked host memory after the wait and before findings are raised; nothing on the device is touched. */
+ * page-locked host memory after the wait and before findings are raised; nothing on the device is touched.  Kind 5 clears the
+ * verdict of the joint final check ("verify_joint"; the group knob is not looked at), so that its fall-back runs on a valid input.
+ * "verify_joint" (1: a verification pass with two or more groups, every one of them held to the final check, runs ONE multiscalar
+ * multiplication over all of them and the per-group ones only when that joint check fails -- see "Joint final check" below,
+ * bpp_verify_joint_stats; 0 and -1 = off: every call takes exactly the launches and buffers it always did.  For calls whose
+ * batches are expected to be valid.  By rule the joint form is taken while the joint group -- 2 max_mn + t + 1 generator columns
+ * and all dynamic terms of the call -- has at most 14 000 terms: pooled small calls, where it measured level or ahead; larger calls
+ * stay on the per-group path, where the joint form measured slower.  2: the joint form whatever the size, for measurement).
+ * "msm_prelude_slices" (S >= 2: every (group, window) sort of the bucket MSM's prelude is cut into S slices of terms, one
+ * workgroup each -- histograms, a scan, the scatter, as three launches -- for every MSM of the context, bpp_msm_vartime* included;
+ * at most 64.  1: the one-workgroup form for every MSM, whatever its size (A/B timing).  0 and -1 = the engine's rule: groups of
+ * 200 000 terms and more, which are also the only ones that get 14-bit windows by rule). */
 int bpp_ctx_set_option(bpp_ctx *ctx, const char *name, int value);
 /* verifications of this context whose weights were made on the device ("chain" 1 or 2), and how many of those ran once more
  * with everything on the host because a weight came out zero */
@@ -176,6 +187,7 @@ int bpp_msm_vartime_batched(bpp_ctx *ctx, const uint8_t *scalars32, const uint8_
  * (else one lane per bucket); bits 1-2 = the reduction, 0 rc_quad, 1 rc2, 2 rc, 3 bitsum + window; bit 3 = final_quad (else final);
  * bit 4 = 256-lane prelude (else 1024); bit 5 = the plain kernels ("msm_plain" = 1: only G, terms and this bit are set).
  * bit 6 = the constant-time kernels (bpp_msm_ct, bpp_msm_ct_batched: only G, terms and this bit are set).
+ * bit 7 = the sliced prelude ("msm_prelude_slices", or by rule), bits 8-15 then hold its slices and dig_cap is 0.
  * BPP_ERR_INVALID_ARGUMENT before the first one (an empty sum launches nothing and records nothing). */
 int bpp_msm_last_plan(bpp_ctx *ctx, uint32_t out[8]);
 
@@ -618,6 +630,36 @@ struct bpp_verify_check_stats {
 int bpp_verify_check_stats(bpp_ctx *ctx, struct bpp_verify_check_stats *out);
 int bpp_batcher_verify_check_stats(bpp_batcher *b, struct bpp_verify_check_stats *out);
 
+/* ---- Joint final check ("verify_joint" = 1) ----
+ * A call that carries G reference batches runs G multiscalar multiplications over the same 2 max_mn + t + 1 generator columns.
+ * With the option on, a pass of the one verification flow (bpp_verify_batch*, bpp_verify_resident with chunk > 0,
+ * bpp_verify_resident_groups(_actions), bpp_verify_resident_states, the packed pipeline's lanes, bpp_batcher) takes the joint path
+ * when it has G >= 2 groups, no group's action is RecoverOnly, it is not pass 2 of "verify_check", it got as far as PASS 2 and its
+ * joint group is within the rule's term bound (see the option's text):
+ *   1  PASS 1, the weight chains (every group keeps the weights of ITS OWN chain), masks and the scalar stage run as always;
+ *   2  the joint row J[c] = sum_g static[g][c] mod l is formed on the device and ONE MSM runs over one group: the generator columns
+ *      under J, then every dynamic term of the call with the scalar it already has;
+ *   3  the identity: every group counts as having passed the final check; findings from status bits, deferred checks and L/R
+ *      counts are raised per group in the usual order;
+ *   4  anything else: the per-group MSMs run on the same scalars (nothing in front of the MSM runs again) and the call ends
+ *      exactly as with the option off -- results, error kinds, tiers, indices, messages, masks, traces, states.
+ * Every rejection is therefore decided by the per-group MSMs; the joint check can only let through what those would, except
+ * when the sums of two or more invalid groups cancel (about 2^126 group operations, the curve's discrete-logarithm
+ * level).  A finding from status bits makes the joint sum meaningless and the fall-back runs; with "verify_check" = 1 the
+ * rejection that is rechecked is the fall-back's; a zero weight from the device chain repeats the pass as always.
+ * NOT COVERED: the sharded entry points and the phased form (bpp_verify_phase*), which run as they always did.
+ * bpp_batch_trace: BPP_TRACE_JOINT_RESULT is the joint point of the batch's last pass that took the joint path (passes 2 and 3
+ * of a recheck, a sharded or phased call, a call with the option off leave it standing); after an ACCEPTED joint pass the
+ * per-group MSMs did not run and BPP_TRACE_MSM_RESULT returns BPP_ERR_INVALID_ARGUMENT saying so, until a pass runs them again.
+ * Counters: passes that took the joint path, those it accepted, those that fell back, and the fall-backs after which every group
+ * was Ok all the same (never expected outside the test knob).  bpp_verify_joint_stats adds the context's pipeline lanes,
+ * bpp_batcher_verify_joint_stats sums a batcher's lanes. */
+struct bpp_verify_joint_stats {
+  uint64_t calls, accepted, fallbacks, fallback_all_ok;
+};
+int bpp_verify_joint_stats(bpp_ctx *ctx, struct bpp_verify_joint_stats *out);
+int bpp_batcher_verify_joint_stats(bpp_batcher *b, struct bpp_verify_joint_stats *out);
+
 /* Prove calls in flight from ONE thread and ONE context: the prover's form of bpp_verify_submit_packed / bpp_verify_collect.
  * bpp_prove_submit hands a whole prove call to one of `depth` lanes and returns a ticket; bpp_prove_collect blocks until that call
  * is done and returns EXACTLY what the blocking call over the same items returns -- bpp_prove_batch_mixed(ctx, params, items,
@@ -665,6 +707,8 @@ int bpp_prove_ticket_done(bpp_ctx *ctx, uint64_t ticket, int *done);
 #define BPP_TRACE_STATIC_SCALARS 4 /* groups x (2*max_mn + t + 1) x 32: gi0,hi0,gi1,hi1,...,g_0..g_{t-1},h */
 #define BPP_TRACE_DYNAMIC_SCALARS 5 /* total_dyn x 32, proof order: C_j.., A1, B, A, L.., R.. */
 #define BPP_TRACE_MSM_RESULT 6     /* groups x 32 compressed */
+#define BPP_TRACE_JOINT_RESULT 8   /* 32: the compressed point of the joint final check ("verify_joint"), of the last pass that took it; BPP_ERR_INVALID_ARGUMENT
+                                      if no pass of this batch has */
 #define BPP_TRACE_PLAN 7           /* four uint32: bit 0 generator columns summed in k_scalars_lanes, bit 1 taken from k_static_gemm;
                                       proofs per workgroup of k_scalars_lanes; K chunks of k_static_gemm; groups */
 int bpp_batch_trace(bpp_ctx *ctx, uint64_t batch, int what, uint8_t *out, size_t out_len, size_t *written);

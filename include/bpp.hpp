@@ -75,6 +75,15 @@ class Engine {
     return s;
   }
 
+  // "verify_joint" = 1 (bpp.h, "Joint final check"): a call with several reference batches runs one multiscalar multiplication
+  // over all of them and the per-batch ones only when that check fails; for calls whose batches are expected to be valid
+  void verify_joint(bool on) { check(bpp_ctx_set_option(ctx_, "verify_joint", on ? 1 : 0), bpp_ctx_last_error(ctx_)); }
+  struct bpp_verify_joint_stats verify_joint_stats() const {
+    struct bpp_verify_joint_stats s{};
+    check(::bpp_verify_joint_stats(ctx_, &s), bpp_ctx_last_error(ctx_));
+    return s;
+  }
+
   // Prove calls in flight from ONE thread (bpp_prove_submit / bpp_prove_collect).  prove_submit hands a whole call -- the items of
   // a bpp_prove_batch_mixed, or with openings = true of a bpp_prove_openings (an item may come without commitments) -- to a lane of
   // this engine and returns at once; the items and everything they point to are free again then.  prove_collect blocks and gives

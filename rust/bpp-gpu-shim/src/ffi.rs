@@ -191,6 +191,16 @@ pub struct bpp_verify_check_stats {
     pub undecided: u64,
 }
 
+/// `struct bpp_verify_joint_stats`: what the joint final checks ("verify_joint" = 1) of a context (or a batcher's lanes) have done
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_verify_joint_stats {
+    pub calls: u64,
+    pub accepted: u64,
+    pub fallbacks: u64,
+    pub fallback_all_ok: u64,
+}
+
 /// `int (*bpp_all_gather_fn)(void *user, const void *send, void *recv, size_t bytes_per_rank)` (include/bpp.h)
 pub type bpp_all_gather_fn = Option<unsafe extern "C" fn(user: *mut c_void, send: *const c_void, recv: *mut c_void, bytes_per_rank: usize) -> c_int>;
 
@@ -321,6 +331,8 @@ extern "C" {
     pub fn bpp_verify_check_resolve(passes: *const bpp_shard_result, n_passes: c_int, out: *mut bpp_shard_result, kind: *mut c_int) -> c_int;
     pub fn bpp_verify_check_stats(ctx: *mut bpp_ctx, out: *mut bpp_verify_check_stats) -> c_int;
     pub fn bpp_batcher_verify_check_stats(b: *mut bpp_batcher, out: *mut bpp_verify_check_stats) -> c_int;
+    pub fn bpp_verify_joint_stats(ctx: *mut bpp_ctx, out: *mut bpp_verify_joint_stats) -> c_int;
+    pub fn bpp_batcher_verify_joint_stats(b: *mut bpp_batcher, out: *mut bpp_verify_joint_stats) -> c_int;
     pub fn bpp_prove_check_stats(ctx: *mut bpp_ctx, out: *mut bpp_prove_check_stats) -> c_int;
     pub fn bpp_prove_pool_check_stats(p: *mut bpp_prove_pool, out: *mut bpp_prove_check_stats) -> c_int;
     pub fn bpp_prove_check_recovery_stats(ctx: *mut bpp_ctx, replayed: *mut u64, mismatched: *mut u64) -> c_int;
