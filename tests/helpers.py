@@ -35,22 +35,62 @@ class Case:
     pass
 
 
+class _RecordingRng:
+    """hands on another RNG's bytes and keeps them: the external RNG bytes of one oracle prove call, for the product's prover"""
+
+    def __init__(self, rng):
+        self._rng, self.taken = rng, b""
+
+    def fill_bytes(self, n):
+        out = self._rng.fill_bytes(n)
+        self.taken += out
+        return out
+
+
+def oracle_pedersen_gens(extension_degree, h_base32, g_bases32):
+    """the oracle's PedersenGens over caller-supplied bases (the reference's h_base / g_base_vec are public fields; the oracle's
+    constructor only makes the default ones, so its four attributes are set here)"""
+    assert len(g_bases32) == extension_degree
+    pc = O.PedersenGens(extension_degree)
+    pc.h_base, pc.h_base_compressed = C.decompress(h_base32), bytes(h_base32)
+    pc.g_base_vec, pc.g_base_compressed_vec = [C.decompress(g) for g in g_bases32], [bytes(g) for g in g_bases32]
+    assert pc.h_base is not None and all(g is not None for g in pc.g_base_vec)
+    return pc
+
+
+def custom_pedersen_gens(extension_degree, which="random", tag=b""):
+    """"random": from_uniform_bytes of tagged SHAKE output; "edge" (t = 2): H = enc(4), G = [enc(6), enc(p - 3)], the smallest and
+    the largest s that encode points"""
+    if which == "edge":
+        assert extension_degree == 2
+        return oracle_pedersen_gens(2, (4).to_bytes(32, "little"), [(6).to_bytes(32, "little"), (C.P - 3).to_bytes(32, "little")])
+    pts = [C.from_uniform_bytes(hashlib.shake_256(b"custom-base-%s-%d" % (tag, k)).digest(64)).compress()
+           for k in range(extension_degree + 1)]
+    return oracle_pedersen_gens(extension_degree, pts[0], pts[1:])
+
+
 def make_oracle_batch(bit_length, aggregation, extension_degree, seed=b"8675309", strategy="third", m_max=None,
-                      label=LABEL):
-    """Oracle-side batch: parameters, statements, witnesses and proofs made by the oracle prover."""
+                      label=LABEL, pc_gens=None):
+    """Oracle-side batch: parameters, statements, witnesses and proofs made by the oracle prover.  pc_gens: an oracle PedersenGens
+    of the caller's own bases (oracle_pedersen_gens); with it every generator gets a blinding of its own."""
     rng = Prng(seed)
     c = Case()
     c.bit_length, c.aggregation, c.t = bit_length, list(aggregation), extension_degree
     c.label = label
     c.m_max = m_max or max(aggregation)
-    c.o_params = O.RangeParameters(bit_length, c.m_max, O.PedersenGens(extension_degree))
+    c.pc_gens = pc_gens
+    c.o_params = O.RangeParameters(bit_length, c.m_max, pc_gens if pc_gens is not None else O.PedersenGens(extension_degree))
     c.o_statements_private, c.o_statements_public, c.o_proofs, c.o_witnesses, c.expected_masks = [], [], [], [], []
+    c.o_ext = []  # per proof: the bytes the oracle's prover drew from the external RNG, 32 per draw
     for m in aggregation:
         openings, commitments, mins = [], [], []
         for j in range(m):
             v = rng.next_u64() % (1 << (bit_length - 1))
             mins.append({"none": None, "third": v // 3, "eq": v}[strategy])
-            blind = [O.random_not_zero(rng)] * extension_degree
+            if pc_gens is None:
+                blind = [O.random_not_zero(rng)] * extension_degree
+            else:
+                blind = [O.random_not_zero(rng) for _ in range(extension_degree)]
             commitments.append(c.o_params.pc_gens.commit(v, blind))
             openings.append(O.CommitmentOpening(v, blind))
             if j == 0:
@@ -59,7 +99,9 @@ def make_oracle_batch(bit_length, aggregation, extension_degree, seed=b"8675309"
         sn = O.random_not_zero(rng) if m == 1 else None
         sp = O.RangeStatement(c.o_params, commitments, mins, sn)
         su = O.RangeStatement(c.o_params, commitments, mins, None)
-        proof = O.prove_with_rng(M.Transcript(label), sp, w, rng)
+        rec = _RecordingRng(rng)
+        proof = O.prove_with_rng(M.Transcript(label), sp, w, rec)
+        c.o_ext.append(rec.taken)
         c.o_statements_private.append(sp)
         c.o_statements_public.append(su)
         c.o_proofs.append(proof)
@@ -69,8 +111,9 @@ def make_oracle_batch(bit_length, aggregation, extension_degree, seed=b"8675309"
 
 def attach_product(c, pkg, eng):
     """Product-side view of an oracle batch: everything as bytes, bound to device parameters."""
-    c.params = pkg.RangeParameters.init(c.bit_length, c.m_max, pkg.create_pedersen_gens_with_extension_degree(c.t),
-                                        engine=eng)
+    pc = c.pc_gens
+    c.params = pkg.RangeParameters.init(c.bit_length, c.m_max, pkg.create_pedersen_gens_with_extension_degree(c.t) if pc is None
+                                        else pkg.PedersenGens(c.t, pc.h_base_compressed, list(pc.g_base_compressed_vec)), engine=eng)
     c.statements_private, c.statements_public, c.proofs = [], [], []
     for sp in c.o_statements_private:
         comp = list(sp.commitments_compressed)
@@ -84,9 +127,15 @@ def attach_product(c, pkg, eng):
 
 
 def make_batch(pkg, eng, bit_length, aggregation, extension_degree, seed=b"8675309", strategy="third", m_max=None,
-               label=LABEL):
-    return attach_product(make_oracle_batch(bit_length, aggregation, extension_degree, seed, strategy, m_max, label),
+               label=LABEL, pc_gens=None):
+    return attach_product(make_oracle_batch(bit_length, aggregation, extension_degree, seed, strategy, m_max, label, pc_gens),
                           pkg, eng)
+
+
+def restate(c, o_params, private=False):
+    """the oracle statements of batch c, bound to other parameters (same commitments, promises and nonces)"""
+    return [O.RangeStatement(o_params, s.commitments, s.minimum_value_promises, s.seed_nonce if private else None)
+            for s in c.o_statements_private]
 
 
 def oracle_verify_trace(c, action=0, private=None, statements=None, proofs=None):
