@@ -121,6 +121,20 @@ def build_lanes_harness(kind, force=False):
     return exe
 
 
+RUNTIME_BINS = {"tsan": os.path.join(HERE, "hosttest_runtime_tsan"), "asan": os.path.join(HERE, "hosttest_runtime_asan")}
+
+
+def build_runtime_harness(kind, force=False):
+    """hosttest_runtime.cpp (runtime_host.h: the small-call gate, the host worker pool, the wait schedule; chain_host.h: the chain
+    scheduler) under ThreadSanitizer (kind "tsan") or ASan + UBSan ("asan"): an executable, run by tests/test_runtime_host.py."""
+    src = os.path.join(CSRC, "hosttest_runtime.cpp")
+    exe = RUNTIME_BINS[kind]
+    if not force and not _stale(exe, [src] + [os.path.join(CSRC, h) for h in HEADERS]):
+        return exe
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-pthread"] + LANES_FLAGS[kind] + ["-o", exe, src], check=True, cwd=CSRC)
+    return exe
+
+
 CT_SANITIZER_BIN = os.path.join(HERE, "hosttest_ct_asan")
 
 

@@ -12,9 +12,15 @@
 // device / test form).  A plane-per-register AVX-512 Keccak-f for one state was measured and dropped: its five
 // cross-lane permutes per round are a 1 130-cycle dependency chain on Zen 5 (0.227 us against 0.166 us scalar).
 #pragma once
+#include <stdlib.h>
 #include <string.h>
 
+#include <functional>
+#include <utility>
+#include <vector>
+
 #include "merlin.h"
+#include "runtime_host.h"
 #include "scalar.h"
 
 namespace bpp {
@@ -532,6 +538,101 @@ static inline void weights_chain_generic(const uint8_t *rng32, size_t n, uint8_t
       host_wide_reduce(w, wide);
     } while (weight_is_zero(w));
   }
+}
+
+// weight transcript (src/range_proof.rs:811,849,853,894)
+static inline void weights_from_chain_host(const uint8_t *rng32, size_t n, uint8_t *weights32) {
+  static const bool generic = getenv("BPP_CHAIN_GENERIC") && atoi(getenv("BPP_CHAIN_GENERIC"));  // tests: merlin.h's sponge
+  if (generic) weights_chain_generic(rng32, n, weights32);
+  else weights_chain_single(rng32, n, weights32);
+}
+
+// ---- the chains of a call's groups on the host pool (runtime_host.h) -------------------------------------------------
+// Chains per bundle for G groups.  One scalar chain per worker has the lowest latency when workers are plentiful; lock-step
+// vector bundles need ~5x less CPU time per chain and keep the GPU fed when several calls / ranks share few cores
+// (measured, 64 groups x 4 calls in flight: 4 host threads 14.9 M proofs/s lock-step vs 12.5 M scalar; 32 threads
+// 15.3 M vs 15.5 M).  Used as soon as the groups outnumber half the workers -- unless the pool is idle and two rounds of
+// scalar chains cover the call: a bundle of eight takes three times as long as one scalar chain, and a lone call of 16 or
+// 32 chains (a sharded call's share of the replay) is waited for by its caller with the GPU idle (32 chains of 4096
+// proofs on 16 workers: 3.4 ms as four bundles, 2.2 ms as scalar chains).
+// simd: the chains the CPU runs in lock-step (8, 4 or 1); force: BPP_CHAIN_LOCKSTEP (0: never, other: always), negative: the rule
+static inline uint32_t chain_bundle_width(uint32_t G, uint32_t pool_size, uint32_t pool_busy, uint32_t simd, int force) {
+  if (force >= 0) return force ? simd : 1u;
+  const bool crowded = G > 2u * pool_size || pool_busy > 0;
+  return (G >= 2u * simd && 2 * G > pool_size && crowded) ? simd : 1u;
+}
+// the groups as units (first group, count) of up to W neighbours with the same number of proofs: what one worker runs
+static inline std::vector<std::pair<uint32_t, uint32_t>> chain_units(const uint32_t *group_first, uint32_t G, uint32_t W) {
+  std::vector<std::pair<uint32_t, uint32_t>> units;
+  for (uint32_t g = 0; g < G;) {
+    const uint32_t n = group_first[g + 1] - group_first[g];
+    uint32_t cnt = 1;
+    while (cnt < W && g + cnt < G && group_first[g + cnt + 1] - group_first[g + cnt] == n) cnt++;
+    units.push_back({g, cnt});
+    g += cnt;
+  }
+  return units;
+}
+// Weight chains of groups [0, G) at bundle width W (1, 4 or 8: what the CPU has), units spread over the host pool.
+// h_rng: 32 bytes per proof; h_out: 32 bytes per proof (canonical weights), wide: 64 (the sponge's bytes, not reduced)
+static inline void run_weight_chains_width(const uint8_t *h_rng, uint8_t *h_out, const uint32_t *group_first, uint32_t G, bool wide,
+                                           uint32_t W) {
+  const size_t stride = wide ? 64 : 32;  // output bytes per proof
+  const std::vector<std::pair<uint32_t, uint32_t>> units = chain_units(group_first, G, W);
+  auto scalar_chain = [&](uint32_t g) {
+    const uint32_t p0 = group_first[g], p1 = group_first[g + 1];
+    if (wide) wide_chain_single(h_rng + (size_t)p0 * 32, p1 - p0, h_out + (size_t)p0 * 64);
+    else weights_from_chain_host(h_rng + (size_t)p0 * 32, p1 - p0, h_out + (size_t)p0 * 32);
+  };
+  std::function<void(uint32_t)> run_unit = [&](uint32_t ui) {
+    uint32_t g = units[ui].first, left = units[ui].second;
+    const size_t n = group_first[g + 1] - group_first[g];
+    while (left) {
+      uint32_t w = (left >= 8 && W >= 8) ? 8 : ((left >= 4 && W >= 4) ? 4 : 1);
+      if (w == 1) {
+        scalar_chain(g);
+      } else {
+        const uint8_t *in[8];
+        uint8_t *out[8];
+        for (uint32_t k = 0; k < w; k++) {
+          in[k] = h_rng + (size_t)group_first[g + k] * 32;
+          out[k] = h_out + (size_t)group_first[g + k] * stride;
+        }
+        if (wide) {  // (zeros are the device's to find: k_chain_finish_bytes)
+          if (w == 8) wide_chain_x8(in, n, out);
+          else wide_chain_x4(in, n, out);
+          g += w;
+          left -= w;
+          continue;
+        }
+        if (w == 8) weights_chain_x8(in, n, out);
+        else weights_chain_x4(in, n, out);
+        // Scalar::random_not_zero: a zero draw (2^-252) means the lockstep result is off from there on -> redo scalar
+        for (uint32_t k = 0; k < w; k++) {
+          bool zero = false;
+          for (size_t i = 0; i < n && !zero; i++) zero = weight_is_zero(out[k] + 32 * i);
+          if (zero) scalar_chain(g + k);
+        }
+      }
+      g += w;
+      left -= w;
+    }
+  };
+  HostPool::get().parallel_for((uint32_t)units.size(), run_unit);
+}
+// lock-step chains this CPU runs: AVX-512 eight, AVX2 four
+static inline uint32_t chain_simd_width() {
+  static const uint32_t simd = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512vl") ? 8u
+                               : (__builtin_cpu_supports("avx2") ? 4u : 1u);
+  return simd;
+}
+// Weight chains of all groups (src/range_proof.rs:811,849,853,894).  Chunks are independent reference batches: groups of
+// equal size run W at a time in lockstep on vector Keccak, bundles are spread over host threads.
+static inline void run_weight_chains_generic(const uint8_t *h_rng, uint8_t *h_out, const uint32_t *group_first, uint32_t G,
+                                             bool wide = false) {
+  static const int force = getenv("BPP_CHAIN_LOCKSTEP") ? atoi(getenv("BPP_CHAIN_LOCKSTEP")) : -1;
+  HostPool &pool = HostPool::get();
+  run_weight_chains_width(h_rng, h_out, group_first, G, wide, chain_bundle_width(G, pool.size(), pool.busy(), chain_simd_width(), force));
 }
 
 }  // namespace bpp

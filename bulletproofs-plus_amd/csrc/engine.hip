@@ -8,8 +8,6 @@
 //   * SHAKE256 / SHA3-512 byte streams for generator derivation (src/generators/generators_chain.rs:23-33,
 //     src/protocols/curve_point_protocol.rs:31-35); the hash-to-group map itself runs on the device
 #include <hip/hip_runtime.h>
-#include <errno.h>
-#include <sched.h>
 #include <stdio.h>
 #include <string.h>
 #include <time.h>
@@ -40,6 +38,7 @@
 #include "msm_plain.h"
 #include "prove_job_host.h"
 #include "prove_pack_host.h"
+#include "runtime_host.h"
 #include "upload_host.h"
 
 using namespace bpp;
@@ -190,19 +189,6 @@ void set_err(char *errbuf, size_t len, const std::string &m) {
   }
 }
 
-// a whole decimal number in [lo, hi] from an environment variable; false (and *out untouched) for anything else -- a typo must
-// not silently become 0, which for a deadline means "none" and for the small-call gate "off"
-bool parse_env_long(const char *text, long lo, long hi, long *out) {
-  if (!text || !*text) return false;
-  char *end = nullptr;
-  errno = 0;
-  const long v = strtol(text, &end, 10);
-  while (end && (*end == ' ' || *end == '\t')) end++;
-  if (errno || end == text || (end && *end) || v < lo || v > hi) return false;
-  *out = v;
-  return true;
-}
-
 // ------------------------------------------------------------------ host hashing helpers (keccak from merlin.h)
 void keccak_sponge(const uint8_t *in, size_t inlen, uint8_t *out, size_t outlen, uint32_t rate, uint8_t pad) {
   uint64_t st[25];
@@ -228,18 +214,6 @@ void keccak_sponge(const uint8_t *in, size_t inlen, uint8_t *out, size_t outlen,
 }
 void shake256(const uint8_t *in, size_t inlen, uint8_t *out, size_t outlen) { keccak_sponge(in, inlen, out, outlen, 136, 0x1f); }
 void sha3_512(const uint8_t *in, size_t inlen, uint8_t out[64]) { keccak_sponge(in, inlen, out, 64, 72, 0x06); }
-
-void run_weight_chains_generic(const uint8_t *h_rng, uint8_t *h_weights, const uint32_t *group_first, uint32_t G, bool wide = false);
-void host_parallel_for(uint32_t n, const std::function<void(uint32_t)> &fn);  // on the persistent host pool
-uint32_t host_pool_size();
-uint64_t host_pool_cpu_ns();
-
-// weight transcript (src/range_proof.rs:811,849,853,894)
-void weights_from_chain_host(const uint8_t *rng32, size_t n, uint8_t *weights32) {
-  static const bool generic = getenv("BPP_CHAIN_GENERIC") && atoi(getenv("BPP_CHAIN_GENERIC"));  // tests: merlin.h's sponge
-  if (generic) weights_chain_generic(rng32, n, weights32);
-  else weights_chain_single(rng32, n, weights32);
-}
 
 // ------------------------------------------------------------------ objects
 // RangeParameters / Precomputation objects are process-wide, reference-counted and read-only once built (the reference
@@ -318,102 +292,6 @@ SharedRegistry<Precomp> &precomp_registry() {
   return *r;
 }
 
-// ------------------------------------------------------------------ per-device runtime state: admission gate, bookkeeping
-// A SMALL call (one reference batch of up to a few hundred proofs: what separate callers of RangeProof::verify_batch issue,
-// src/range_proof.rs:73-76,712-752) is a chain of about fifteen latency-bound kernels with tiny grids.  The chip runs about
-// six such chains side by side; more callers than that add nothing, and many more take it away: 8-16 callers with a context
-// each reached 5.3 k calls/s, 32 callers 2.6 k, 64 callers 1.6 k (profiles/r03_v10_calls_in_flight.jsonl) -- every context
-// brings a stream and a side stream, the runtime multiplexes them onto its hardware queues (GPU_MAX_HW_QUEUES, 4 unless the
-// host sets more) and streams that share a queue serialise behind each other's kernels.  So the library admits at most
-// `limit` small calls per device at a time (BPP_SMALL_CALLS_IN_FLIGHT, default 12; bpp_small_call_limit); the others wait
-// their turn in arrival order, on the host, holding nothing.  Large calls (they fill the chip by themselves) pass freely.
-struct DeviceState {
-  std::mutex mu;
-  struct Waiter {
-    std::condition_variable cv;
-    bool go = false;
-  };
-  std::deque<Waiter *> queue;
-  uint32_t limit = 12, in_flight = 0;
-  uint64_t small_calls = 0, small_calls_queued = 0;
-  uint32_t contexts = 0, contexts_peak = 0;
-  bool warned = false;
-  std::string env_note;  // a malformed BPP_SMALL_CALLS_IN_FLIGHT: said once, where bpp_ctx_last_error finds it
-};
-DeviceState &device_state(int dev) {
-  static std::mutex mu;
-  static std::map<int, DeviceState *> *all = new std::map<int, DeviceState *>();  // leaked: contexts may outlive static destruction
-  std::lock_guard<std::mutex> lk(mu);
-  DeviceState *&d = (*all)[dev];
-  if (!d) {
-    d = new DeviceState();
-    if (const char *e = getenv("BPP_SMALL_CALLS_IN_FLIGHT")) {  // 0: no gate
-      long v = 0;
-      if (parse_env_long(e, 0, 1 << 20, &v)) d->limit = (uint32_t)v;
-      else d->env_note = std::string("note: BPP_SMALL_CALLS_IN_FLIGHT=\"") + e + "\" is not a number: the default gate (12 calls) stands";
-    }
-  }
-  return *d;
-}
-// hardware queues the HIP runtime multiplexes this process' streams onto: read once at its start-up from GPU_MAX_HW_QUEUES
-uint32_t runtime_hw_queues() {
-  static const uint32_t q = [] {
-    const char *e = getenv("GPU_MAX_HW_QUEUES");
-    const int v = e ? atoi(e) : 0;
-    return v > 0 ? (uint32_t)v : 4u;
-  }();
-  return q;
-}
-thread_local int tl_gate_depth = 0;  // a thread that holds the gate passes it again (upload + verify of one call)
-struct GateHold {
-  DeviceState *d = nullptr;
-  GateHold(int dev, bool small) {
-    if (!small) return;
-    if (tl_gate_depth++ > 0) {
-      d = nullptr;
-      held_outer = true;
-      return;
-    }
-    DeviceState &D = device_state(dev);
-    std::unique_lock<std::mutex> lk(D.mu);
-    D.small_calls++;
-    if (D.limit == 0) {  // gate switched off: counted, never held
-      tl_gate_depth--;
-      return;
-    }
-    d = &D;
-    if (D.in_flight < D.limit && D.queue.empty()) {
-      D.in_flight++;
-      return;
-    }
-    D.small_calls_queued++;
-    DeviceState::Waiter w;
-    D.queue.push_back(&w);
-    w.cv.wait(lk, [&] { return w.go; });  // the releasing thread has already counted this call in
-  }
-  ~GateHold() {
-    if (held_outer) {
-      tl_gate_depth--;
-      return;
-    }
-    if (!d) return;
-    tl_gate_depth--;
-    std::lock_guard<std::mutex> lk(d->mu);
-    d->in_flight--;
-    while (!d->queue.empty() && d->in_flight < d->limit) {
-      DeviceState::Waiter *w = d->queue.front();
-      d->queue.pop_front();
-      d->in_flight++;
-      w->go = true;
-      w->cv.notify_one();
-    }
-  }
-  GateHold(const GateHold &) = delete;
-  GateHold &operator=(const GateHold &) = delete;
-
- private:
-  bool held_outer = false;
-};
 // calls of up to this many proofs are "small" for the gate (their MSM has at most ~20 000 terms: BPP_SMALL_CALL_TERMS)
 #define BPP_GATE_SMALL_PROOFS 1024u
 // proof + commitment bytes of an upload up to this size travel with the small arrays in k_ingest; above it by DMA
@@ -588,15 +466,6 @@ void prove_pipeline_shutdown(bpp_ctx *ctx);
 int prove_pipeline_check_stats(bpp_ctx *ctx, struct bpp_prove_check_stats *sum);
 int prove_pipeline_recovery_stats(bpp_ctx *ctx, uint64_t *replayed, uint64_t *mismatched);
 int prove_pipeline_secret_bytes(bpp_ctx *ctx, uint64_t *examined, uint64_t *nonzero);
-
-// What a waiting site remembers: how long its wait took the last times (microseconds, a running mean) and for WHICH work -- a key the
-// caller makes from the call's size.  A remembered time is only used for a call with the same key: a context that proved 8192
-// proofs per call and then proves 1024 must not sleep through the shorter call on the longer one's memory (it did, for one
-// build: 45 k proofs/s instead of 150 k in bench.py's prover leg, whose context had made the run's inputs before).
-struct WaitHint {
-  uint32_t us = 0;
-  uint64_t key = 0;
-};
 
 // The kernel forms the last bucket MSM of a context took (msm_run decides them once and launches by them; msm_plain_run
 // records the plain kernels): bpp_msm_last_plan reads this, so that a test can tell WHICH kernels gave it its bytes
@@ -893,56 +762,25 @@ inline uint32_t cdiv(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
 inline bool wait_naps(const bpp_ctx *ctx, size_t proofs) {
   return ctx->opt.wait >= 0 ? ctx->opt.wait != 0 : proofs >= BPP_WAIT_NAP_MIN_PROOFS;
 }
-// hint (optional): the caller's memory of how long THIS wait took the last times, microseconds (updated here).  A call of a
-// steady stream of calls waits about as long as the one before it: most of that is slept in ONE piece, and the looking starts
-// when the wait is nearly over -- every look is a call into the runtime and every nap two context switches, which on a busy host
-// (measured: the same build 0.3 or 1.2 cores for four waiting callers, box by box) is what a rank's idle callers cost.
-// tail_spin: after the piece slept ahead, look without napping (a call at a time then ends as promptly as under the runtime's
-// spinning wait, for ~30 % of a core instead of all of it; with nothing remembered yet the whole wait is looked through)
+// hint (optional): the caller's memory of how long THIS wait took the last times, microseconds (updated here), for the work `key`
+// names.  When and how long the caller naps between two looks is runtime_host.h's (WaitSchedule); the looking is done here.
 inline void gpu_wait_event(hipEvent_t ev, bool nap, WaitHint *wh = nullptr, uint64_t key = 0, bool tail_spin = false) {
-  if (wh && wh->key != key) {  // other work than last time: nothing is known about this wait
-    wh->us = 0;
-    wh->key = key;
-  }
-  uint32_t *hint = wh ? &wh->us : nullptr;
+  wait_hint_begin(wh, key);
   if (!nap) {
     HIP_CHECK(hipEventSynchronize(ev));
     return;
   }
-  // the first ~30 us by looking only: a wait for something that is (nearly) done must not cost a nap -- a nap is 60-100 us with
-  // the kernel's timer slack, and a prover call has six waits in a row at its end (0.6 ms of a 6.5 ms call before this)
   const auto t0 = std::chrono::steady_clock::now();
-  bool slept_ahead = false;
+  WaitSchedule sched{wh ? wh->us : 0u, tail_spin};
   for (;;) {
     const hipError_t e = hipEventQuery(ev);
     const long waited = (long)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
     if (e == hipSuccess) {
-      if (hint) *hint = *hint ? (uint32_t)((3ul * *hint + (unsigned long)waited) / 4ul) : (uint32_t)waited;
+      wait_hint_fold(wh, waited);
       return;
     }
     if (e != hipErrorNotReady) HIP_CHECK(e);
-    if (waited < 30) continue;
-    if (tail_spin && (slept_ahead || !hint || *hint <= 600)) continue;
-    long nap_us;
-    if (hint && !slept_ahead && *hint > 600 && waited < (long)*hint / 2) {
-      // the bulk of an expected wait in one piece: HALF of what the last waits took when naps follow, 70 % when the rest is looked
-      // through.  (70 % for the napping callers too overslept in short runs: between two synchronisations the steps in flight
-      // start together and stay in step, their waits spread from 6 to 13 ms around the remembered 10, a caller that sleeps past
-      // its step's end restarts its slot late and the steps in step with it all shift -- the driver's 20-step form of bench.py
-      // read 25.1 M proofs/s with 70 %, 25.6 with 60 %, 25.8-26.2 with 50 %, 26.0 with 40 %, 25.9-26.0 under the runtime's
-      // spinning wait; 256-step runs and the callers' CPU time do not change: profiles/r06_wait_ahead_ab.txt)
-      nap_us = (long)*hint * (tail_spin ? 7 : 5) / 10 - waited;
-      if (nap_us < 50) nap_us = 50;
-      slept_ahead = true;
-    } else if (slept_ahead && waited < (long)*hint * 5 / 4) {
-      nap_us = 50;  // the expected end is near: short naps (a call at a time wakes up within one of them)
-    } else {
-      // naps grow with the wait: 50 us at first (a wait of a few hundred microseconds ends within a nap of its event), an eighth of
-      // the time waited so far from 0.4 ms on, 400 us at most
-      nap_us = waited < 400 ? 50 : (waited / 8 > 400 ? 400 : waited / 8);
-    }
-    struct timespec ts = {0, nap_us * 1000};
-    nanosleep(&ts, nullptr);
+    if (const long us = sched.next_nap_us(waited)) nap_us(us);
   }
 }
 inline void gpu_wait_stream(bpp_ctx *ctx, hipStream_t s, bool nap, WaitHint *hint = nullptr, uint64_t key = 0, bool tail_spin = false);
@@ -1497,20 +1335,7 @@ int bpp_device_chain_stats(bpp_ctx *ctx, uint64_t *calls, uint64_t *redraws) {
 
 int bpp_small_call_limit(bpp_ctx *ctx, int limit) {
   if (!ctx) return BPP_ERR_BAD_HANDLE;
-  DeviceState &D = device_state(ctx->device);
-  std::lock_guard<std::mutex> lk(D.mu);
-  const int before = (int)D.limit;
-  if (limit >= 0) {
-    D.limit = (uint32_t)limit;
-    while (!D.queue.empty() && (D.limit == 0 || D.in_flight < D.limit)) {  // a wider (or removed) gate lets waiting calls in
-      DeviceState::Waiter *w = D.queue.front();
-      D.queue.pop_front();
-      D.in_flight++;
-      w->go = true;
-      w->cv.notify_one();
-    }
-  }
-  return before;
+  return device_state(ctx->device).set_limit(limit);
 }
 
 const char *bpp_ctx_last_error(bpp_ctx *ctx) { return ctx ? ctx->err.c_str() : "null ctx"; }
@@ -2405,232 +2230,6 @@ void run_weight_chains_wide(Batch &b) {
   b.h_wide.resize((size_t)b.B * 64);
   run_weight_chains_generic(b.h_rng.data(), b.h_wide.data(), b.h_group_first.data(), b.G, true);
 }
-// Persistent host workers for the weight chains (spawning threads per call costs more than a 1024-proof chain).
-class HostPool {
- public:
-  static HostPool &get() {
-    static HostPool *p = new HostPool();  // leaked on purpose: detached workers may still wait at process exit
-    return *p;
-  }
-  uint32_t size() const { return (uint32_t)workers_.size() + 1; }
-  // calls that have work queued on the pool right now (a hint for the chain scheduler, nothing is promised)
-  uint32_t busy() {
-    std::lock_guard<std::mutex> lk(mu_);
-    return (uint32_t)jobs_.size();
-  }
-  // run fn(i) for i in [0, n) on the pool + the calling thread; returns when all are done
-  void parallel_for(uint32_t n, const std::function<void(uint32_t)> &fn) {
-    if (n == 0) return;
-    if (n == 1 || workers_.empty()) {
-      CpuSpan span;
-      for (uint32_t i = 0; i < n; i++) fn(i);
-      return;
-    }
-    auto job = std::make_shared<Job>();
-    job->fn = &fn;
-    job->n = n;
-    {
-      std::lock_guard<std::mutex> lk(mu_);
-      jobs_.push_back(job);
-    }
-    cv_.notify_all();
-    work_on(*job);
-    std::unique_lock<std::mutex> lk(job->mu);
-    job->cv.wait(lk, [&] { return job->done.load() == n; });
-    std::lock_guard<std::mutex> lk2(mu_);
-    for (auto it = jobs_.begin(); it != jobs_.end(); ++it)
-      if (it->get() == job.get()) {
-        jobs_.erase(it);
-        break;
-      }
-  }
-
- private:
-  struct Job {
-    const std::function<void(uint32_t)> *fn;
-    uint32_t n;
-    std::atomic<uint32_t> next{0}, done{0};
-    std::mutex mu;
-    std::condition_variable cv;
-  };
-  // host threads this process may really run at once: the affinity mask, capped by a cgroup CPU quota when there is one (a
-  // 1-GPU box of the pool reports 256 logical CPUs and schedules 16: sized by hardware_concurrency() the pool had 32 workers
-  // there, and the chain scheduler, which compares the number of chains with the pool, took 64 chains of 4096 proofs for
-  // "few": scalar chains, 10 ms per call instead of 2 ms as eight lock-step bundles)
-  static uint32_t usable_cpus() {
-    uint32_t n = std::max(1u, std::thread::hardware_concurrency());
-    cpu_set_t set;
-    CPU_ZERO(&set);
-    if (sched_getaffinity(0, sizeof(set), &set) == 0 && CPU_COUNT(&set) > 0) n = std::min<uint32_t>(n, (uint32_t)CPU_COUNT(&set));
-    auto read2 = [](const char *path, long long &a, long long &b, bool &a_is_max) {
-      FILE *f = fopen(path, "r");
-      if (!f) return false;
-      char w[64] = {0};
-      a_is_max = false;
-      bool ok = false;
-      if (fscanf(f, "%63s %lld", w, &b) == 2) {
-        ok = true;
-        if (strcmp(w, "max") == 0) a_is_max = true;
-        else a = atoll(w);
-      }
-      fclose(f);
-      return ok;
-    };
-    long long q = 0, per = 0;
-    bool is_max = false;
-    if (read2("/sys/fs/cgroup/cpu.max", q, per, is_max)) {  // cgroup v2: "<quota|max> <period>"
-      if (!is_max && q > 0 && per > 0) n = std::min<uint32_t>(n, (uint32_t)std::max<long long>(1, (q + per / 2) / per));
-    } else {  // cgroup v1
-      FILE *fq = fopen("/sys/fs/cgroup/cpu/cpu.cfs_quota_us", "r"), *fp = fopen("/sys/fs/cgroup/cpu/cpu.cfs_period_us", "r");
-      if (fq && fp && fscanf(fq, "%lld", &q) == 1 && fscanf(fp, "%lld", &per) == 1 && q > 0 && per > 0)
-        n = std::min<uint32_t>(n, (uint32_t)std::max<long long>(1, (q + per / 2) / per));
-      if (fq) fclose(fq);
-      if (fp) fclose(fp);
-    }
-    return std::max(1u, n);
-  }
-  HostPool() {
-    uint32_t hw = usable_cpus();
-    const char *e = getenv("BPP_HOST_THREADS");
-    uint32_t want = e ? (uint32_t)atoi(e) : std::min(hw, 32u);
-    want = std::max(1u, std::min(want, 256u));
-    for (uint32_t i = 1; i < want; i++)
-      workers_.emplace_back([this] {
-        pthread_setname_np(pthread_self(), "bpp-chain");  // (who is busy: bench.py's host_cores_busy_by_thread)
-        loop();
-      });
-    for (auto &t : workers_) t.detach();
-  }
- public:
-  // CPU time spent inside jobs (thread clocks, so a thread that was not scheduled is not counted): what bpp_host_pool_cpu_ns
-  // reports -- with several ranks on one host it tells a host-bound step from a GPU-bound one
-  static uint64_t thread_cpu_ns() {
-    struct timespec ts;
-    clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts);
-    return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
-  }
-  static std::atomic<uint64_t> &cpu_ns() {
-    static std::atomic<uint64_t> v{0};
-    return v;
-  }
-  // (the thread clock is a system call, ~1 us: read once per thread and JOB, never per item -- a 256-proof call parses 256 items)
-  struct CpuSpan {
-    uint64_t t0 = thread_cpu_ns();
-    ~CpuSpan() { cpu_ns().fetch_add(thread_cpu_ns() - t0, std::memory_order_relaxed); }
-  };
-
- private:
-  static void work_on(Job &j) {
-    if (j.next.load() >= j.n) return;  // nothing left: no clock reads either
-    CpuSpan span;
-    for (;;) {
-      uint32_t i = j.next.fetch_add(1);
-      if (i >= j.n) return;
-      (*j.fn)(i);
-      if (j.done.fetch_add(1) + 1 == j.n) {
-        std::lock_guard<std::mutex> lk(j.mu);
-        j.cv.notify_all();
-      }
-    }
-  }
-  void loop() {
-    for (;;) {
-      std::shared_ptr<Job> job;
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [&] {
-          for (auto &j : jobs_)
-            if (j->next.load() < j->n) return true;
-          return false;
-        });
-        for (auto &j : jobs_)
-          if (j->next.load() < j->n) {
-            job = j;
-            break;
-          }
-      }
-      if (job) work_on(*job);
-    }
-  }
-  std::vector<std::thread> workers_;
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::deque<std::shared_ptr<Job>> jobs_;
-};
-
-void host_parallel_for(uint32_t n, const std::function<void(uint32_t)> &fn) { HostPool::get().parallel_for(n, fn); }
-uint32_t host_pool_size() { return HostPool::get().size(); }
-uint64_t host_pool_cpu_ns() { return HostPool::cpu_ns().load(std::memory_order_relaxed); }
-
-void run_weight_chains_generic(const uint8_t *h_rng, uint8_t *h_weights, const uint32_t *group_first, uint32_t G, bool wide) {
-  const size_t stride = wide ? 64 : 32;  // output bytes per proof
-  static const int simd = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512vl") ? 8
-                          : (__builtin_cpu_supports("avx2") ? 4 : 1);
-  HostPool &pool = HostPool::get();
-  // One scalar chain per worker has the lowest latency when workers are plentiful; lock-step vector bundles
-  // (chain_host.h) need ~5x less CPU time per chain and keep the GPU fed when several calls / ranks share few cores
-  // (measured, 64 groups x 4 calls in flight: 4 host threads 14.9 M proofs/s lock-step vs 12.5 M scalar; 32 threads
-  // 15.3 M vs 15.5 M).  Used as soon as the groups outnumber half the workers -- unless the pool is idle and two rounds of
-  // scalar chains cover the call: a bundle of eight takes three times as long as one scalar chain, and a lone call of 16 or
-  // 32 chains (a sharded call's share of the replay) is waited for by its caller with the GPU idle (32 chains of 4096
-  // proofs on 16 workers: 3.4 ms as four bundles, 2.2 ms as scalar chains).
-  static const int force = getenv("BPP_CHAIN_LOCKSTEP") ? atoi(getenv("BPP_CHAIN_LOCKSTEP")) : -1;
-  const bool crowded = G > 2u * pool.size() || pool.busy() > 0;
-  const uint32_t W = force >= 0 ? (force ? (uint32_t)simd : 1u)
-                                : ((G >= 2u * (uint32_t)simd && 2 * G > pool.size() && crowded) ? (uint32_t)simd : 1u);
-  struct Unit {
-    uint32_t g0, cnt;
-  };
-  std::vector<Unit> units;
-  for (uint32_t g = 0; g < G;) {
-    const uint32_t n = group_first[g + 1] - group_first[g];
-    uint32_t cnt = 1;
-    while (cnt < W && g + cnt < G && group_first[g + cnt + 1] - group_first[g + cnt] == n) cnt++;
-    units.push_back({g, cnt});
-    g += cnt;
-  }
-  auto scalar_chain = [&](uint32_t g) {
-    const uint32_t p0 = group_first[g], p1 = group_first[g + 1];
-    if (wide) wide_chain_single(h_rng + (size_t)p0 * 32, p1 - p0, h_weights + (size_t)p0 * 64);
-    else weights_from_chain_host(h_rng + (size_t)p0 * 32, p1 - p0, h_weights + (size_t)p0 * 32);
-  };
-  std::function<void(uint32_t)> run_unit = [&](uint32_t ui) {
-    const Unit &u = units[ui];
-    uint32_t g = u.g0, left = u.cnt;
-    const size_t n = group_first[g + 1] - group_first[g];
-    while (left) {
-      uint32_t w = (left >= 8 && simd >= 8) ? 8 : ((left >= 4 && simd >= 4) ? 4 : 1);
-      if (w == 1) {
-        scalar_chain(g);
-      } else {
-        const uint8_t *in[8];
-        uint8_t *out[8];
-        for (uint32_t k = 0; k < w; k++) {
-          in[k] = h_rng + (size_t)group_first[g + k] * 32;
-          out[k] = h_weights + (size_t)group_first[g + k] * stride;
-        }
-        if (wide) {  // (zeros are the device's to find: k_chain_finish_bytes)
-          if (w == 8) wide_chain_x8(in, n, out);
-          else wide_chain_x4(in, n, out);
-          g += w;
-          left -= w;
-          continue;
-        }
-        if (w == 8) weights_chain_x8(in, n, out);
-        else weights_chain_x4(in, n, out);
-        // Scalar::random_not_zero: a zero draw (2^-252) means the lockstep result is off from there on -> redo scalar
-        for (uint32_t k = 0; k < w; k++) {
-          bool zero = false;
-          for (size_t i = 0; i < n && !zero; i++) zero = weight_is_zero(out[k] + 32 * i);
-          if (zero) scalar_chain(g + k);
-        }
-      }
-      g += w;
-      left -= w;
-    }
-  };
-  pool.parallel_for((uint32_t)units.size(), run_unit);
-}
 
 // status words (and, where asked for, the groups' identity flags and the recovered masks) -> mapped host memory, status[]
 // back to its initial value: one launch, no copy (kernels_verify.h: k_results_out).  Valid on the host once the stream has
@@ -3375,7 +2974,7 @@ template <class Upload>
 int verify_uploaded(bpp_ctx *ctx, size_t n_items, Upload upload, int action, size_t chunk, uint8_t *masks_out, uint8_t *mask_present,
                     char *errbuf, size_t errbuf_len, uint8_t *states_out203 = nullptr) {
   if (!ctx) return BPP_ERR_BAD_HANDLE;
-  GateHold gate(ctx->device, n_items <= BPP_GATE_SMALL_PROOFS);  // held across upload and verification of a small call
+  GateHold gate(device_state(ctx->device), n_items <= BPP_GATE_SMALL_PROOFS);  // held across upload and verification of a small call
   uint64_t h = 0;
   int rc = upload(&h);
   if (rc != BPP_OK) return rc;
@@ -3393,7 +2992,7 @@ int bpp_verify_resident(bpp_ctx *ctx, uint64_t batch, int action, size_t chunk, 
                         char *errbuf, size_t errbuf_len) {
   if (!ctx) return BPP_ERR_BAD_HANDLE;
   const uint32_t n_peek = batch_size_peek(ctx, batch);
-  GateHold gate(ctx->device, n_peek && n_peek <= BPP_GATE_SMALL_PROOFS);  // small calls queue for the device (DeviceState)
+  GateHold gate(device_state(ctx->device), n_peek && n_peek <= BPP_GATE_SMALL_PROOFS);  // small calls queue for the device (DeviceState)
   BPP_ENTRY(ctx);
   return verify_chunked_locked(ctx, batch, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
 }
@@ -3402,7 +3001,7 @@ int bpp_verify_resident_states(bpp_ctx *ctx, uint64_t batch, int action, size_t 
                                uint8_t *states_out203, char *errbuf, size_t errbuf_len) {
   if (!ctx) return BPP_ERR_BAD_HANDLE;
   const uint32_t n_peek = batch_size_peek(ctx, batch);
-  GateHold gate(ctx->device, n_peek && n_peek <= BPP_GATE_SMALL_PROOFS);
+  GateHold gate(device_state(ctx->device), n_peek && n_peek <= BPP_GATE_SMALL_PROOFS);
   BPP_ENTRY(ctx);
   if (!states_out203) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
   return verify_chunked_locked(ctx, batch, action, chunk, masks_out, mask_present, errbuf, errbuf_len, states_out203);
@@ -3412,7 +3011,7 @@ int bpp_verify_resident_groups_actions(bpp_ctx *ctx, uint64_t batch, const uint3
                                        bpp_shard_result *results, uint8_t *masks_out, uint8_t *mask_present) {
   if (!ctx) return BPP_ERR_BAD_HANDLE;
   const uint32_t n_peek = batch_size_peek(ctx, batch);
-  GateHold gate(ctx->device, n_peek && n_peek <= BPP_GATE_SMALL_PROOFS);  // small calls queue for the device (DeviceState)
+  GateHold gate(device_state(ctx->device), n_peek && n_peek <= BPP_GATE_SMALL_PROOFS);  // small calls queue for the device (DeviceState)
   BPP_ENTRY(ctx);
   return verify_groups_locked(ctx, batch, group_first, n_groups, actions, results, masks_out, mask_present);
 }
@@ -3578,7 +3177,7 @@ void pipe_worker(bpp_ctx *owner, Pipeline *pp, PipeLane *lane) {
     err[0] = 0;
     uint64_t h = 0;
     int rc = BPP_OK;
-    GateHold gate(owner->device, job->n_items <= BPP_GATE_SMALL_PROOFS);
+    GateHold gate(device_state(owner->device), job->n_items <= BPP_GATE_SMALL_PROOFS);
     {
       std::lock_guard<std::mutex> lk(c->mu);
       try {

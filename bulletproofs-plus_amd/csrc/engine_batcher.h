@@ -114,7 +114,7 @@ void batcher_run_unchecked(bpp_batcher *b, bpp_batcher::Lane &L, std::vector<bpp
     // others are pooled again without it.
     uint64_t h = 0;
     size_t culprit = reqs.size();
-    GateHold gate(L.ctx->device, n <= BPP_GATE_SMALL_PROOFS);  // one turn at the device's gate for upload + verification
+    GateHold gate(device_state(L.ctx->device), n <= BPP_GATE_SMALL_PROOFS);  // one turn at the device's gate for upload + verification
     {
       std::lock_guard<std::mutex> lk(L.ctx->mu);
       if (hipSetDevice(L.ctx->device) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
