@@ -5,6 +5,7 @@ next_u64 % 2^(n-1), one random non-zero blinding repeated t times, seed nonce if
 "BatchedRangeProofTest".  The PRNG is SHAKE256-based (the reference's ChaCha12 stream is not reproducible here and no
 test of the reference depends on its actual bytes)."""
 import hashlib
+import types
 
 from oracle.pyref import curve as C
 from oracle.pyref import merlin as M
@@ -158,6 +159,20 @@ def trace_challenge_bytes(trace, max_rounds):
         row += [0] * (max_rounds + 3 - len(row))
         out += b"".join(sb(x) for x in row)
     return out
+
+
+def replay_verifier_state(tr, n_bits, t, pc, commitments, mins, raw):
+    """PASS 1 of the oracle's verify() (oracle/pyref/protocol.py: the loop at the head of verify) on `tr`, without the arithmetic
+    behind it: what verify() leaves in the transcript of a proof"""
+    proof = O.RangeProof.from_bytes(raw)
+    st = types.SimpleNamespace(commitments_compressed=list(commitments), minimum_value_promises=list(mins))
+    rpt = O.RangeProofTranscript(tr, pc.h_base_compressed, pc.g_base_compressed_vec, n_bits, t, len(commitments), st, None, M.NullRng())
+    rpt.challenges_y_z(proof.a)
+    for l, r in zip(proof.li, proof.ri):
+        rpt.challenge_round_e(l, r)
+    rpt.challenge_final_e(proof.a1, proof.b)
+    rpt.to_verifier_rng(proof.r1, proof.s1, proof.d1)
+    return tr.strobe.to_bytes()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

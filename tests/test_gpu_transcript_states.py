@@ -10,7 +10,6 @@ shape is therefore run a second time with context, over proofs the engine's own 
 
 Oracle work is done once per module (SHARED) and never modified."""
 import ctypes
-import types
 
 import numpy as np
 import pytest
@@ -18,7 +17,7 @@ import pytest
 from oracle import cport
 from oracle.pyref import merlin as M
 from oracle.pyref import protocol as O
-from tests.helpers import Prng, sb
+from tests.helpers import Prng, replay_verifier_state, sb
 
 pytestmark = pytest.mark.gpu
 
@@ -46,20 +45,6 @@ def p_transcripts(bpp, n, how="ops"):
             t = bpp.Transcript.from_state(o_transcript().strobe.to_bytes())
         out.append(t)
     return out
-
-
-def replay_verifier_state(tr, n_bits, t, pc, commitments, mins, raw):
-    """PASS 1 of the oracle's verify() (oracle/pyref/protocol.py: the loop at the head of verify) on `tr`, without the arithmetic
-    behind it: what verify() leaves in the transcript of a proof"""
-    proof = O.RangeProof.from_bytes(raw)
-    st = types.SimpleNamespace(commitments_compressed=list(commitments), minimum_value_promises=list(mins))
-    rpt = O.RangeProofTranscript(tr, pc.h_base_compressed, pc.g_base_compressed_vec, n_bits, t, len(commitments), st, None, M.NullRng())
-    rpt.challenges_y_z(proof.a)
-    for l, r in zip(proof.li, proof.ri):
-        rpt.challenge_round_e(l, r)
-    rpt.challenge_final_e(proof.a1, proof.b)
-    rpt.to_verifier_rng(proof.r1, proof.s1, proof.d1)
-    return tr.strobe.to_bytes()
 
 
 class Case:

@@ -7,6 +7,7 @@ import importlib
 import pytest
 
 from oracle.pyref import merlin as M
+from tests import transcript_sweep as TS
 
 LABEL, CTX_LABEL, CTX = b"outer protocol v1", b"block-context", bytes(range(7, 64))
 MSG_LENS = [0, 1, 165, 166, 167, 400]  # STROBE-128's rate is 166 bytes
@@ -62,6 +63,25 @@ def test_label_made_state_is_transcript_new():
     o.append_message(CTX_LABEL, CTX)
     assert lib.bpp_transcript_append_message(st, _buf(CTX_LABEL), len(CTX_LABEL), _buf(CTX), len(CTX)) == 0
     assert bytes(st) == o.strobe.to_bytes()
+
+
+def test_transcript_new_at_every_starting_position():
+    """bpp_transcript_new over the sweep's 166 labels (lengths 0 .. 165: every position of the block) and labels longer than a block;
+    one message and one challenge from each of those states"""
+    lib = _lib()
+    assert sorted(M.Transcript(TS.label_of(n)).strobe.pos for n in range(166)) == list(range(166))
+    for n in list(range(166)) + [166, 167, 400]:
+        label = TS.label_of(n)
+        st = (ctypes.c_uint8 * 203)()
+        assert lib.bpp_transcript_new(_buf(label), n, st) == 0
+        o = M.Transcript(label)
+        assert bytes(st) == o.strobe.to_bytes(), n
+        o.append_message(b"msg", _msg(40))
+        assert lib.bpp_transcript_append_message(st, _buf(b"msg"), 3, _buf(_msg(40)), 40) == 0
+        assert bytes(st) == o.strobe.to_bytes(), n
+        out = (ctypes.c_uint8 * 32)()
+        assert lib.bpp_transcript_challenge_bytes(st, _buf(b"chal"), 4, out, 32) == 0
+        assert bytes(out) == o.challenge_bytes(b"chal", 32) and bytes(st) == o.strobe.to_bytes(), n
 
 
 @pytest.mark.parametrize("pos", [166, 167, 255])
