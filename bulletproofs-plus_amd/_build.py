@@ -150,6 +150,21 @@ def build_ct_harness(force=False):
     return CT_SANITIZER_BIN
 
 
+INGEST_SANITIZER_BIN = os.path.join(HERE, "hosttest_ingest_asan")
+
+
+def build_ingest_harness(force=False):
+    """hosttest_ingest.cpp (ingest.h: the one-item routines of the device form of the packed upload, held to the host packer of
+    upload_host.h over a corpus) under ASan + UBSan: an executable, run by tests/test_ingest_host.py."""
+    src = os.path.join(CSRC, "hosttest_ingest.cpp")
+    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
+    if not force and not _stale(INGEST_SANITIZER_BIN, deps):
+        return INGEST_SANITIZER_BIN
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-fno-omit-frame-pointer", "-o", INGEST_SANITIZER_BIN, src], check=True, cwd=CSRC)
+    return INGEST_SANITIZER_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     build_hosttest(force="--force" in sys.argv)

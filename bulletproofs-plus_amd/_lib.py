@@ -71,6 +71,11 @@ class VerifyJointStats(Structure):
     _fields_ = [(n, c_uint64) for n in ("calls", "accepted", "fallbacks", "fallback_all_ok")]
 
 
+class IngestStats(Structure):
+    """struct bpp_ingest_stats: what the uploads from device memory of a context came to"""
+    _fields_ = [(n, c_uint64) for n in ("device_calls", "host_fallback_calls", "fallback_bytes")]
+
+
 class RuntimeInfo(Structure):
     """bpp_runtime_info: what the library sees of its runtime preconditions (hardware queues, contexts, the small-call gate)"""
     _fields_ = [("device", c_int), ("contexts", c_uint32), ("contexts_peak", c_uint32), ("hw_queues", c_uint32),
@@ -112,6 +117,11 @@ SYMBOLS = [
     ("bpp_batch_upload_packed", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), POINTER(c_uint64), c_void_p, c_size_t]),
     ("bpp_verify_batch_packed", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_int, c_size_t, c_void_p, c_void_p,
                                         c_void_p, c_size_t]),
+    ("bpp_batch_upload_packed_device", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), POINTER(c_uint64), c_void_p, c_size_t]),
+    ("bpp_verify_batch_packed_device", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_int, c_size_t, c_void_p, c_void_p,
+                                               c_void_p, c_size_t]),
+    ("bpp_device_pointer_check", c_int, [c_void_p, c_void_p, POINTER(c_int)]),
+    ("bpp_ingest_stats", c_int, [c_void_p, POINTER(IngestStats)]),
     ("bpp_ctx_pipeline_depth", c_int, [c_void_p, c_uint32]),
     ("bpp_verify_submit_packed", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_int, c_size_t, POINTER(c_uint64),
                                          c_void_p, c_size_t]),

@@ -105,6 +105,7 @@ class Engine:
     def __init__(self, device=0, stream=None):
         self.lib = _lib.load()
         self.ctx = c_void_p()
+        self.stream = int(stream) if stream else 0  # the caller's stream the context runs on (0: a stream of its own)
         if stream:
             rc = self.lib.bpp_ctx_create_on_stream(byref(self.ctx), int(device), c_void_p(int(stream)))
         else:

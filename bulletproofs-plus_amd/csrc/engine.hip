@@ -40,6 +40,7 @@
 #include "prove_pack_host.h"
 #include "runtime_host.h"
 #include "upload_host.h"
+#include "ingest.h"
 
 using namespace bpp;
 
@@ -516,6 +517,13 @@ struct bpp_ctx {
   PinnedBuf<uint8_t> pin_upload, pin_upload2;  // page-locked staging of bpp_batch_upload (bytes; descriptors etc.)
   PinnedBuf<uint32_t> pin_small;       // staging for small host->device arrays (a pageable hipMemcpyAsync of a few
                                        // hundred bytes was measured at ~10 ms on this stack)
+  // the device form of the packed upload (ingest.h): the kernel's result words and per-item info bytes, where they are fetched
+  // to, the staging of the host fall-back, and what the calls came to
+  DevBuf<uint32_t> ingest_res;
+  DevBuf<uint8_t> ingest_info;
+  PinnedBuf<uint32_t> pin_ingest;
+  PinnedBuf<uint8_t> pin_ingest_info, pin_fallback;
+  struct bpp_ingest_stats ingest_stats{};
   bool profile = false;
   bool profile_light = false;  // bpp_profile_enable(ctx, 2): events around the roofline kernel (k_msm_accumulate) only
   bpp_profile prof{};
@@ -1809,16 +1817,25 @@ void upload_host_pack(bpp_ctx *ctx, const Params &P, const bpp_verify_item *item
   else upload_pass_b(items, shape, pl, bytes, pf);
 }
 
-// ---- device half: staging -> HBM, slot lists, statement commitments decoded; consumes `pl`
+// a batch to fill: the buffers of the last destroyed one serve again
+std::unique_ptr<Batch> new_batch(bpp_ctx *ctx) {
+  auto B = std::make_unique<Batch>();
+  if (ctx->spare_batch) {
+    adopt_buffers(*B, *ctx->spare_batch);
+    ctx->spare_batch.reset();
+  }
+  return B;
+}
+
+// ---- device half: staging -> HBM, slot lists, statement commitments decoded; consumes `pl`.
+// `filled`: a batch whose proof and commitment bytes, promises and seed nonces k_ingest_packed has already written where they
+// belong (upload_packed_device); only the descriptors and the transcript state then come from the host.
 uint64_t upload_device(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t params, UploadPlan &pl,
-                       const uint8_t *const *challenges32, const uint8_t *rng_out32) {
+                       const uint8_t *const *challenges32, const uint8_t *rng_out32, std::unique_ptr<Batch> filled = nullptr) {
     Params &P = *Pp;
     const size_t n_items = pl.n_items;
-    auto B = std::make_unique<Batch>();
-    if (ctx->spare_batch) {
-      adopt_buffers(*B, *ctx->spare_batch);
-      ctx->spare_batch.reset();
-    }
+    const bool resident = filled != nullptr;
+    std::unique_ptr<Batch> B = resident ? std::move(filled) : new_batch(ctx);
     hipStream_t s = ctx->stream;
     // seed nonces pass through page-locked staging and reach the device: both are wiped on EVERY way out of here
     SmallStaging L;
@@ -1862,9 +1879,16 @@ uint64_t upload_device(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t
     // device copies (all sources page-locked: the copies are real stream-ordered DMA)
     B->bytes.alloc(bytes_len);
     B->states.alloc(states.size());
-    B->seeds.alloc(B->any_seed ? seeds.size() : 0);
+    // (a buffer that holds secrets at times starts out zero: a batch that fails before anything is written to it leaves no stale
+    // bytes of an earlier allocation there for bpp_batch_secret_bytes to count)
+    auto alloc_zeroed = [&](DevBuf<uint8_t> &buf, size_t count) {
+      const bool fresh = !(buf.p && count <= buf.n);
+      buf.alloc(count);
+      if (fresh) HIP_CHECK(hipMemsetAsync(buf.p, 0, buf.n, s));
+    };
+    if (!resident) alloc_zeroed(B->seeds, B->any_seed ? seeds.size() : 0);
     B->d_desc.alloc(n_items);
-    B->minvals.alloc(minvals.size());
+    if (!resident) B->minvals.alloc(minvals.size());
     B->src_off.alloc(dyn);
     B->owner.alloc(dyn);
     B->idx_commit.alloc(sum_m);
@@ -1886,8 +1910,13 @@ uint64_t upload_device(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t
         if (nbytes) ia.seg[ia.n_seg++] = IngestSeg{src, (uint8_t *)dst, nbytes};
       };
       const bool bytes_by_dma = bytes_len > BPP_INGEST_MAX_BYTES;
-      if (bytes_by_dma) HIP_CHECK(hipMemcpyAsync(B->bytes.p, bytes, bytes_len, hipMemcpyHostToDevice, s));
-      else seg(ctx->pin_upload.dev(), B->bytes.p, bytes_len);
+      if (resident) {
+        // (already in B->bytes / minvals / seeds: pl.minvals and pl.seeds are empty)
+      } else if (bytes_by_dma) {
+        HIP_CHECK(hipMemcpyAsync(B->bytes.p, bytes, bytes_len, hipMemcpyHostToDevice, s));
+      } else {
+        seg(ctx->pin_upload.dev(), B->bytes.p, bytes_len);
+      }
       seg(st_dev + L.o_desc, B->d_desc.p, n_items * sizeof(ProofDesc));
       seg(st_dev + L.o_min, B->minvals.p, minvals.size() * 8);
       seg(st_dev + L.o_state, B->states.p, states.size());
@@ -1916,7 +1945,7 @@ uint64_t upload_device(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t
     // (rows / parts: sized by layout_groups, which knows whether the generator columns are summed inside k_scalars_lanes)
     B->shr.alloc((size_t)n_items * SH_STRIDE);
     B->tab.alloc((size_t)n_items * lanes_tab_stride(B->lanes_nhi_max(P.n_bits)));
-    B->masks.alloc(n_items * P.t * 32);
+    alloc_zeroed(B->masks, n_items * P.t * 32);
     B->h_rng.resize(n_items * 32);
     B->h_weights.resize(n_items * 32);
     B->h_status.resize(n_items);
@@ -1995,9 +2024,167 @@ int upload_impl(bpp_ctx *ctx, uint64_t params, const bpp_verify_item *items, siz
   }
   BPP_CATCH(ctx, errbuf, errbuf_len)
 }
+
+// ---- the packed form from arrays in device memory (ingest.h)
+// one host function over hipPointerGetAttributes; a pointer the runtime does not know makes it fail, and that error must not
+// stay behind for the next hipGetLastError
+int device_pointer_kind(int device, const void *p) {
+  hipPointerAttribute_t at;
+  memset(&at, 0, sizeof(at));
+  if (!p || hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return BPP_PTR_HOST_OR_UNKNOWN;
+  }
+  if (at.isManaged || at.type == hipMemoryTypeManaged) return BPP_PTR_MANAGED;
+  if (at.type == hipMemoryTypeDevice) return at.device == device ? BPP_PTR_THIS_DEVICE : BPP_PTR_OTHER_DEVICE;
+  return BPP_PTR_HOST_OR_UNKNOWN;
+}
+
+// The fall-back: a batch the arithmetic layout does not fit (mixed first bytes, no proofs, a stride below the length) is copied to
+// page-locked staging and takes the host path, item form and all.  The staged nonces are wiped on every way out.
+uint64_t upload_packed_device_fallback(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t params, const bpp_packed_batch &in) {
+  const size_t n = in.n_items, nm = n * (size_t)in.m;
+  const bool strided = in.proofs && in.proof_len >= 1 && in.proof_stride > in.proof_len;  // staged back to back
+  const bool no_bytes = !in.proofs || in.proof_len < 1;  // (empty proofs: the item form reads none of them, whatever the stride)
+  const size_t proofs_n = no_bytes ? 0 : (strided ? n * in.proof_len : (n - 1) * in.proof_stride + in.proof_len);
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const size_t o_proofs = 0, o_commit = up16(proofs_n), o_minv = up16(o_commit + (in.commitments32 ? nm * 32 : 0)),
+               o_minp = up16(o_minv + (in.min_values ? nm * 8 : 0)), o_seedp = up16(o_minp + (in.min_present ? nm : 0)),
+               o_seed = up16(o_seedp + (in.seed_present ? n : 0)), n_seed = in.seed_nonces32 ? n * 32 : 0, total = o_seed + n_seed;
+  ctx->pin_fallback.resize(total + 16);
+  uint8_t *st = ctx->pin_fallback.data();
+  hipStream_t s = ctx->stream;
+  ScopeExit wipe_staged{[&] {
+    if (n_seed) {
+      (void)hipStreamSynchronize(s);  // the copy into the staging may still be running
+      secure_wipe(st + o_seed, n_seed);
+    }
+  }};
+  bpp_packed_batch host = in;
+  auto fetch = [&](const void *src, size_t off, size_t bytes) -> const uint8_t * {
+    if (!src) return nullptr;
+    if (bytes) HIP_CHECK(hipMemcpyAsync(st + off, src, bytes, hipMemcpyDeviceToHost, s));
+    return st + off;
+  };
+  if (strided) {
+    HIP_CHECK(hipMemcpy2DAsync(st + o_proofs, in.proof_len, in.proofs, in.proof_stride, in.proof_len, n, hipMemcpyDeviceToHost, s));
+    host.proofs = st + o_proofs;
+    host.proof_stride = in.proof_len;
+  } else {
+    host.proofs = fetch(in.proofs, o_proofs, proofs_n);
+    if (no_bytes) host.proof_stride = 0;
+  }
+  host.commitments32 = fetch(in.commitments32, o_commit, nm * 32);
+  host.min_values = (const uint64_t *)fetch(in.min_values, o_minv, nm * 8);
+  host.min_present = fetch(in.min_present, o_minp, nm);
+  host.seed_present = fetch(in.seed_present, o_seedp, n);
+  host.seed_nonces32 = fetch(in.seed_nonces32, o_seed, n_seed);
+  HIP_CHECK(hipStreamSynchronize(s));
+  ctx->ingest_stats.host_fallback_calls++;
+  ctx->ingest_stats.fallback_bytes += proofs_n + (in.commitments32 ? nm * 32 : 0) + (in.min_values ? nm * 8 : 0) + (in.min_present ? nm : 0) +
+                                      (in.seed_present ? n : 0) + n_seed;
+  UploadPlan pl;
+  PlanWipe wipe_plan{pl};
+  upload_host_pack(ctx, *Pp, nullptr, n, &host, pl);
+  return upload_device(ctx, Pp, params, pl, nullptr, nullptr);
+}
+
+int upload_packed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, uint64_t *batch, char *errbuf, size_t errbuf_len) {
+  try {
+    if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty", errbuf, errbuf_len);
+    // pointer kinds first: nothing is allocated or launched for an array this device cannot read, and no array is ever
+    // dereferenced on the host
+    const struct {
+      const char *name;
+      const void *p;
+    } arrays[] = {{"proofs", in->proofs},           {"commitments32", in->commitments32}, {"min_values", in->min_values},
+                  {"min_present", in->min_present}, {"seed_nonces32", in->seed_nonces32}, {"seed_present", in->seed_present}};
+    static const char *const kinds[] = {"", "memory of another device", "host memory or memory the runtime does not know", "managed memory"};
+    for (const auto &a : arrays) {
+      if (!a.p) continue;
+      const int kind = device_pointer_kind(ctx->device, a.p);
+      if (kind != BPP_PTR_THIS_DEVICE)
+        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + " is not device memory of this context's device (" + kinds[kind] + ")", errbuf,
+                    errbuf_len);
+    }
+    const std::shared_ptr<Params> Pp = params_registry().get(params);
+    if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
+    const size_t n_items = in->n_items;
+    if (n_items == 0 || !batch) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty", errbuf, errbuf_len);
+    if (n_items > (1u << 24)) return fail(ctx, BPP_ERR_SIZE_OVERFLOW, "batch too large", errbuf, errbuf_len);
+    const ParamShape shape{Pp->n_bits, Pp->m_max, Pp->t};
+    if (!ingest_host_prelude(*in, shape)) {
+      *batch = upload_packed_device_fallback(ctx, Pp, params, *in);
+      return BPP_OK;
+    }
+    hipStream_t s = ctx->stream;
+    std::unique_ptr<Batch> B = new_batch(ctx);
+    ScopeExit wipe_unfinished{[&] {  // B still here: an error or the fall-back.  The nonces the kernel brought in go before its buffers do
+      if (B) {
+        wipe_batch_secrets(*B, s);
+        (void)hipStreamSynchronize(s);
+      }
+    }};
+    const size_t bytes_len = n_items * in->proof_len + n_items * (size_t)in->m * 32 + BPP_BYTES_SLACK;  // (< 4 GB: the prelude)
+    B->bytes.alloc(bytes_len);
+    B->minvals.alloc(n_items * (size_t)in->m);
+    if (in->seed_nonces32) B->seeds.alloc(n_items * 32);
+    ctx->ingest_res.alloc(BPP_ING_RES_WORDS);
+    ctx->ingest_info.alloc(n_items);
+    ctx->pin_ingest.resize(BPP_ING_RES_WORDS);
+    const IngestPacked a = ingest_args(*in, shape, B->bytes.p, B->minvals.p, B->seeds.p, ctx->ingest_info.p, ctx->ingest_res.p);
+    HIP_CHECK(hipMemsetAsync(ctx->ingest_res.p, 0, BPP_ING_RES_WORDS * 4, s));
+    B->seeds_dirty = in->seed_nonces32 != nullptr;
+    hipLaunchKernelGGL(k_ingest_packed, dim3((uint32_t)cdiv((uint32_t)n_items, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, a);
+    HIP_CHECK(hipGetLastError());
+    uint32_t *res = ctx->pin_ingest.data();
+    HIP_CHECK(hipMemcpyAsync(res, ctx->ingest_res.p, BPP_ING_RES_WORDS * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (res[BPP_ING_RES_DIFFERS]) {
+      wipe_batch_secrets(*B, s);
+      (void)hipStreamSynchronize(s);
+      ctx->spare_batch = std::move(B);  // its buffers serve the host path's batch
+      *batch = upload_packed_device_fallback(ctx, Pp, params, *in);
+      return BPP_OK;
+    }
+    const uint8_t *info = nullptr;
+    if (ingest_needs_info(*in, res)) {
+      ctx->pin_ingest_info.resize(n_items);
+      HIP_CHECK(hipMemcpyAsync(ctx->pin_ingest_info.data(), ctx->ingest_info.p, n_items, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      info = ctx->pin_ingest_info.data();
+    }
+    UploadPlan pl;
+    ingest_finish_plan(*in, shape, res, info, pl);  // throws the lowest-index construction finding
+    ctx->ingest_stats.device_calls++;
+    *batch = upload_device(ctx, Pp, params, pl, nullptr, nullptr, std::move(B));
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, errbuf, errbuf_len)
+}
 }  // namespace
 
 extern "C" {
+
+int bpp_batch_upload_packed_device(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, uint64_t *batch, char *errbuf,
+                                   size_t errbuf_len) {
+  BPP_ENTRY(ctx);
+  return upload_packed_device_impl(ctx, params, in, batch, errbuf, errbuf_len);
+}
+
+int bpp_device_pointer_check(bpp_ctx *ctx, const void *p, int *kind) {
+  BPP_ENTRY(ctx);
+  if (!kind) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+  *kind = device_pointer_kind(ctx->device, p);
+  return BPP_OK;
+}
+
+int bpp_ingest_stats(bpp_ctx *ctx, struct bpp_ingest_stats *out) {
+  BPP_ENTRY(ctx);
+  if (!out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+  *out = ctx->ingest_stats;
+  return BPP_OK;
+}
 
 int bpp_batch_upload(bpp_ctx *ctx, uint64_t params, const bpp_verify_item *items, size_t n_items, uint64_t *batch,
                      char *errbuf, size_t errbuf_len) {
@@ -3040,6 +3227,12 @@ int bpp_verify_batch(bpp_ctx *ctx, uint64_t params, const bpp_verify_item *items
 int bpp_verify_batch_packed(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, int action, size_t chunk,
                             uint8_t *masks_out, uint8_t *mask_present, char *errbuf, size_t errbuf_len) {
   auto upload = [&](uint64_t *h) -> int { return bpp_batch_upload_packed(ctx, params, in, h, errbuf, errbuf_len); };
+  return verify_uploaded(ctx, in ? in->n_items : SIZE_MAX, upload, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
+}
+
+int bpp_verify_batch_packed_device(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, int action, size_t chunk,
+                                   uint8_t *masks_out, uint8_t *mask_present, char *errbuf, size_t errbuf_len) {
+  auto upload = [&](uint64_t *h) -> int { return bpp_batch_upload_packed_device(ctx, params, in, h, errbuf, errbuf_len); };
   return verify_uploaded(ctx, in ? in->n_items : SIZE_MAX, upload, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
 }
 

@@ -330,6 +330,43 @@ inline void upload_packed_as_items(const bpp_packed_batch &pk, std::vector<bpp_v
   }
 }
 
+// the arithmetic layout of a packed batch whose proofs all start with the byte `t0`: what upload_pass_a_packed fills in after it
+// has looked at the first bytes.  Reads nothing behind pk's array pointers (the device form of the upload, ingest.h, calls it
+// with arrays that lie in device memory); host_arrays = false leaves the plan's promise and nonce arrays empty (they are
+// written on the device there).
+inline void upload_plan_packed(const bpp_packed_batch &pk, uint8_t t0, UploadPlan &pl, bool host_arrays = true) {
+  const size_t n = pk.n_items;
+  const size_t nchunks = (pk.proof_len - 1) / 32;
+  uint32_t rounds = 0;
+  if (nchunks > (size_t)t0 + 5) rounds = (uint32_t)std::min<size_t>((nchunks - ((size_t)t0 + 5)) / 2, BPP_MAX_WIRE_ROUNDS);
+  const uint64_t per_dyn = (uint64_t)pk.m + 3 + 2 * (uint64_t)rounds;
+  const uint64_t proof_bytes = (uint64_t)n * pk.proof_len, sum_m = (uint64_t)n * pk.m, dyn64 = (uint64_t)n * per_dyn;
+  if (proof_bytes + sum_m * 32 >= (1ull << 32) || sum_m >= (1ull << 28) || dyn64 >= (1ull << 31))
+    throw ProofErr{BPP_ERR_SIZE_OVERFLOW, "batch too large for one call (4 GB of proof bytes)"};
+  pl.n_items = n;
+  pl.desc.assign(n, ProofDesc{});  // state_idx 0 everywhere: one transcript
+  pl.rounds_bad.assign(n, 0);
+  pl.defer.assign(n, 0);
+  pl.seeds.assign(host_arrays && pk.seed_nonces32 ? n * 32 : 0, 0);
+  pl.pre.clear();
+  pl.states.assign(203, 0);
+  pl.tr_err_index = n;
+  if (pk.transcript_state) {
+    memcpy(pl.states.data(), pk.transcript_state, 203);
+    if (pl.states[200] >= BPP_STROBE_R) pl.tr_err_index = 0;
+  } else {
+    Strobe st;
+    merlin_new(st, pk.transcript_label, (uint32_t)(pk.transcript_label ? pk.label_len : 0));
+    strobe_to_bytes(pl.states.data(), st);
+  }
+  pl.proof_bytes = (size_t)proof_bytes;
+  pl.sum_m = (size_t)sum_m;
+  pl.bytes_total = (size_t)(proof_bytes + sum_m * 32);
+  pl.total_dyn = (uint32_t)dyn64;
+  pl.minvals.assign(host_arrays ? (size_t)sum_m : 0, 0);
+  pl.packed_rounds = rounds;
+}
+
 // true: the plan's layout was filled in arithmetically (call upload_pass_b_packed next); false: use the item form
 inline bool upload_pass_a_packed(const bpp_packed_batch &pk, UploadPlan &pl, const ParallelFor &parallel_for) {
   const size_t n = pk.n_items;
@@ -346,35 +383,7 @@ inline bool upload_pass_a_packed(const bpp_packed_batch &pk, UploadPlan &pl, con
   });
   for (uint8_t d : differs)
     if (d) return false;
-  const size_t nchunks = (pk.proof_len - 1) / 32;
-  uint32_t rounds = 0;
-  if (nchunks > (size_t)t0 + 5) rounds = (uint32_t)std::min<size_t>((nchunks - ((size_t)t0 + 5)) / 2, BPP_MAX_WIRE_ROUNDS);
-  const uint64_t per_dyn = (uint64_t)pk.m + 3 + 2 * (uint64_t)rounds;
-  const uint64_t proof_bytes = (uint64_t)n * pk.proof_len, sum_m = (uint64_t)n * pk.m, dyn64 = (uint64_t)n * per_dyn;
-  if (proof_bytes + sum_m * 32 >= (1ull << 32) || sum_m >= (1ull << 28) || dyn64 >= (1ull << 31))
-    throw ProofErr{BPP_ERR_SIZE_OVERFLOW, "batch too large for one call (4 GB of proof bytes)"};
-  pl.n_items = n;
-  pl.desc.assign(n, ProofDesc{});  // state_idx 0 everywhere: one transcript
-  pl.rounds_bad.assign(n, 0);
-  pl.defer.assign(n, 0);
-  pl.seeds.assign(pk.seed_nonces32 ? n * 32 : 0, 0);
-  pl.pre.clear();
-  pl.states.assign(203, 0);
-  pl.tr_err_index = n;
-  if (pk.transcript_state) {
-    memcpy(pl.states.data(), pk.transcript_state, 203);
-    if (pl.states[200] >= BPP_STROBE_R) pl.tr_err_index = 0;
-  } else {
-    Strobe st;
-    merlin_new(st, pk.transcript_label, (uint32_t)(pk.transcript_label ? pk.label_len : 0));
-    strobe_to_bytes(pl.states.data(), st);
-  }
-  pl.proof_bytes = (size_t)proof_bytes;
-  pl.sum_m = (size_t)sum_m;
-  pl.bytes_total = (size_t)(proof_bytes + sum_m * 32);
-  pl.total_dyn = (uint32_t)dyn64;
-  pl.minvals.assign((size_t)sum_m, 0);
-  pl.packed_rounds = rounds;
+  upload_plan_packed(pk, t0, pl);
   return true;
 }
 

@@ -149,6 +149,117 @@ def verify_batch(params, inp, action=api.VerifyAction.VerifyOnly, chunk=api.MAX_
     return masks, present
 
 
+class DevicePackedInput:
+    """A homogeneous batch whose arrays already lie in DEVICE memory + the bpp_packed_batch that describes it, for the *_packed_device
+    entry points (include/bpp.h): nothing is copied to the host, one kernel checks and packs the batch where it lies.
+
+    Every array is a torch device tensor or an (address, shape) pair: uint8 tensors for bytes, any 8-byte dtype for min_values (torch's
+    uint64 is thin: int64 bit patterns are what is expected).  proofs may be a view whose rows are further apart than their length
+    (stride(0) >= proof length, or proof_stride= with an address).  Shapes, contiguity and the device index are checked here; the kind
+    of memory behind the addresses is checked by the engine (bpp_device_pointer_check) before it launches anything.
+
+    Ordering: what wrote the arrays must be ordered before the engine's stream.  order_before(engine) -- called by verify_batch_device and
+    ResidentBatch(form="device") -- synchronises torch's current stream unless the engine was created on that very stream
+    (Engine(stream=torch.cuda.current_stream().cuda_stream)); `.synchronised` says which it was.  With raw addresses the caller orders."""
+
+    def __init__(self, proofs, commitments, min_values=None, min_present=None, seed_nonces=None, label=b"", seed_present=None, state=None,
+                 proof_stride=None):
+        self._keep, self.device_index, self._torch, self.synchronised = [], None, False, False
+        addr_p, shape, stride = self._array(proofs, "proofs", 1, rows=True)
+        if len(shape) != 2:
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "proofs: an array of shape (n, proof_len) expected, got %s" % (shape,))
+        n, plen = shape
+        stride = int(proof_stride) if proof_stride is not None else (stride if stride is not None else plen)
+        addr_c, cshape, _ = self._array(commitments, "commitments", 1)
+        if len(cshape) != 3 or cshape[0] != n or cshape[2] != 32:
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "commitments: an array of shape (%d, m, 32) expected, got %s" % (n, cshape))
+        m = cshape[1]
+
+        def opt(a, name, itemsize, want):
+            if a is None:
+                return None
+            addr, got, _ = self._array(a, name, itemsize)
+            if got != want:
+                raise api.ProofError(api.ProofErrorKind.InvalidLength, "%s: array of shape %s expected, got %s" % (name, want, got))
+            return addr
+
+        self.label = np.frombuffer(bytes(label), dtype=np.uint8).copy() if len(label) else np.zeros(1, dtype=np.uint8)
+        self.state = None if state is None else np.frombuffer(bytes(state), dtype=np.uint8).copy()
+        self.n, self.m, self.proof_len = n, m, plen
+        self.struct = _lib.PackedBatch(n, addr_p, plen, stride, addr_c, m, opt(min_values, "min_values", 8, (n, m)),
+                                       opt(min_present, "min_present", 1, (n, m)), opt(seed_nonces, "seed_nonces", 1, (n, 32)),
+                                       opt(seed_present, "seed_present", 1, (n,)), None if self.state is None else self.state.ctypes.data,
+                                       self.label.ctypes.data, len(label))
+
+    def _array(self, a, name, itemsize, rows=False):
+        """-> (address, shape, row stride in bytes or None)"""
+        if isinstance(a, tuple) and len(a) == 2 and not hasattr(a[0], "data_ptr"):
+            return int(a[0]), tuple(int(d) for d in a[1]), None
+        if not hasattr(a, "data_ptr") or not getattr(a, "is_cuda", False):
+            raise api.ProofError(api.ProofErrorKind.InvalidArgument, "%s: a torch device tensor or an (address, shape) pair expected" % name)
+        import torch
+        if (itemsize == 1 and a.dtype != torch.uint8) or a.element_size() != itemsize:
+            raise api.ProofError(api.ProofErrorKind.InvalidArgument, "%s: %s expected, got %s" % (name, "uint8" if itemsize == 1 else "an 8-byte dtype", a.dtype))
+        if rows and a.dim() == 2:
+            ok = a.shape[0] <= 1 or (a.stride(1) == 1 and a.stride(0) >= a.shape[1])
+        else:
+            ok = a.is_contiguous()
+        if not ok:
+            raise api.ProofError(api.ProofErrorKind.InvalidArgument, "%s: not contiguous" % name)
+        index = a.device.index if a.device.index is not None else torch.cuda.current_device()
+        if self.device_index is None:
+            self.device_index = index
+        elif self.device_index != index:
+            raise api.ProofError(api.ProofErrorKind.InvalidArgument, "%s: on device %d, other arrays on device %d" % (name, index, self.device_index))
+        self._keep.append(a)
+        self._torch = True
+        return a.data_ptr(), tuple(a.shape), (a.stride(0) if rows and a.dim() == 2 and a.shape[0] > 1 else None)
+
+    def order_before(self, engine):
+        """make what wrote the tensors ordered before `engine`'s stream; True when that took a synchronisation"""
+        self.synchronised = False
+        if self.device_index is not None and self.device_index != int(engine.device):
+            raise api.ProofError(api.ProofErrorKind.InvalidArgument,
+                                 "arrays on device %d, engine on device %d" % (self.device_index, int(engine.device)))
+        if not self._torch:
+            return False
+        import torch
+        cur = torch.cuda.current_stream(self.device_index)
+        if engine.stream and int(cur.cuda_stream) == engine.stream:
+            return False
+        cur.synchronize()
+        self.synchronised = True
+        return True
+
+
+def verify_batch_device(params, inp, action=api.VerifyAction.VerifyOnly, chunk=api.MAX_RANGE_PROOF_BATCH_SIZE):
+    """verify_batch over a DevicePackedInput in ONE C call (bpp_verify_batch_packed_device): the results of verify_batch on the same
+    bytes in host memory.  Returns (masks uint8 [n, t, 32], present uint8 [n]) (host arrays)."""
+    eng, t = params.engine, int(params.extension_degree())
+    masks = np.zeros((inp.n, t, 32), dtype=np.uint8)
+    present = np.zeros(inp.n, dtype=np.uint8)
+    err = ctypes.create_string_buffer(256)
+    inp.order_before(eng)
+    rc = eng.lib.bpp_verify_batch_packed_device(eng.ctx, params.handle, byref(inp.struct), int(action), chunk, masks.ctypes.data,
+                                                present.ctypes.data, err, 256)
+    api._check(rc, eng.ctx, err)
+    return masks, present
+
+
+def device_pointer_kind(engine, address):
+    """bpp_device_pointer_check: 0 this engine's device memory, 1 another device's, 2 host or unknown, 3 managed (launches nothing)"""
+    kind = ctypes.c_int(-1)
+    api._check(engine.lib.bpp_device_pointer_check(engine.ctx, ctypes.c_void_p(int(address)), byref(kind)), engine.ctx)
+    return kind.value
+
+
+def ingest_stats(engine):
+    """bpp_ingest_stats -> (device_calls, host_fallback_calls, fallback_bytes) of the engine's uploads from device memory"""
+    s = _lib.IngestStats()
+    api._check(engine.lib.bpp_ingest_stats(engine.ctx, byref(s)), engine.ctx)
+    return int(s.device_calls), int(s.host_fallback_calls), int(s.fallback_bytes)
+
+
 class Batcher:
     """bpp_batcher: many host threads, each calling verify(inp) with ONE reference batch; the calls that are waiting are pooled
     into grouped engine calls (bpp_verify_resident_groups), every caller gets the outcome of a call of its own.  `shape`: a
@@ -484,15 +595,28 @@ class Pipeline:
 class ResidentBatch(api.ResidentBatch):
     """api.ResidentBatch (bpp_batch_upload / bpp_verify_resident / traces) uploaded from arrays.  form="packed": through
     bpp_batch_upload_packed (one bpp_packed_batch, no per-item structs); form="items": a bpp_verify_item array built with
-    numpy pointer arithmetic.  Both end in the same resident batch (tests/test_gpu_packed.py)."""
+    numpy pointer arithmetic.  Both end in the same resident batch (tests/test_gpu_packed.py).  form="device": the arrays are device
+    tensors or (address, shape) pairs (or `proofs` is a DevicePackedInput and the other arrays are None), uploaded through
+    bpp_batch_upload_packed_device without passing through the host; the same resident batch again (tests/test_gpu_device_inputs.py)."""
 
-    def __init__(self, params, proofs, commitments, min_values, min_present, seed_nonces, label, form="packed"):
+    def __init__(self, params, proofs, commitments, min_values, min_present, seed_nonces, label, form="packed", seed_present=None):
         self.params, self.engine, self.t = params, params.engine, int(params.extension_degree())
         self.handle = c_uint64()
         err = ctypes.create_string_buffer(256)
+        if form == "device":
+            t0 = time.perf_counter()
+            inp = proofs if isinstance(proofs, DevicePackedInput) else DevicePackedInput(proofs, commitments, min_values, min_present,
+                                                                                         seed_nonces, label, seed_present=seed_present)
+            self.n, self.input = inp.n, inp
+            inp.order_before(self.engine)
+            t1 = time.perf_counter()
+            rc = self.engine.lib.bpp_batch_upload_packed_device(self.engine.ctx, params.handle, byref(inp.struct), byref(self.handle), err, 256)
+            api._check(rc, self.engine.ctx, err)
+            self.marshal_seconds, self.upload_seconds = t1 - t0, time.perf_counter() - t1
+            return
         if form == "packed":
             t0 = time.perf_counter()
-            inp = PackedInput(proofs, commitments, min_values, min_present, seed_nonces, label)
+            inp = PackedInput(proofs, commitments, min_values, min_present, seed_nonces, label, seed_present=seed_present)
             self.n = inp.n
             t1 = time.perf_counter()
             rc = self.engine.lib.bpp_batch_upload_packed(self.engine.ctx, params.handle, byref(inp.struct), byref(self.handle), err, 256)

@@ -305,6 +305,40 @@ int bpp_batch_upload_packed(bpp_ctx *ctx, uint64_t params, const bpp_packed_batc
 int bpp_verify_batch_packed(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, int action, size_t chunk,
                             uint8_t *masks_out, uint8_t *mask_present, char *errbuf, size_t errbuf_len);
 
+/* ---- the packed form from arrays that already lie in DEVICE memory (a torch tensor, a buffer a NIC or another kernel wrote).
+ * The struct is bpp_packed_batch as it is; for these two calls six of its fields are addresses in the memory of the context's
+ * device -- proofs, commitments32, min_values, min_present, seed_nonces32, seed_present -- of the sizes given above, readable
+ * until the call returns.  transcript_state, transcript_label, masks_out, mask_present and errbuf stay host memory.  The engine
+ * never dereferences a caller array on the host: one kernel checks every item (first byte, canonical scalars, promises, nonce
+ * present) and packs the batch where it lies; no staging, no host pass over the proofs.
+ * ORDERING: whatever wrote the arrays must be complete on, or ordered before, the context's stream.  A context made with
+ * bpp_ctx_create_on_stream on the producer's stream has that by construction; any other caller synchronises first.
+ * POINTER KINDS: every non-null array goes through bpp_device_pointer_check before anything is allocated or launched; anything
+ * but BPP_PTR_THIS_DEVICE (another device's memory, host or unknown memory, managed memory) is BPP_ERR_INVALID_ARGUMENT with the
+ * field's name in errbuf.
+ * RESULTS: return codes, error kinds, message texts, their precedence, chunking and masks are those of bpp_batch_upload_packed /
+ * bpp_verify_batch_packed on the same bytes in host memory.  The batch is an ordinary resident batch.
+ * FALLBACK: a batch whose proofs disagree in their first byte (a hostile or mixed input; the host form takes its item path for
+ * it), or whose proofs / proof_len / proof_stride rule the arithmetic layout out, is copied to page-locked staging and goes
+ * through the host path: same results, counted in bpp_ingest_stats.  The staged nonces are wiped on every way out.
+ * SECRETS: the engine's copy of the seed nonces is the resident batch's buffer, wiped as ever; the caller's array is the caller's. */
+int bpp_batch_upload_packed_device(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, uint64_t *batch, char *errbuf,
+                                   size_t errbuf_len);
+int bpp_verify_batch_packed_device(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, int action, size_t chunk,
+                                   uint8_t *masks_out, uint8_t *mask_present, char *errbuf, size_t errbuf_len);
+/* what kind of memory `p` is to this context; one runtime query, launches nothing, leaves no runtime error behind */
+#define BPP_PTR_THIS_DEVICE 0     /* device memory of the context's device */
+#define BPP_PTR_OTHER_DEVICE 1    /* device memory of another device */
+#define BPP_PTR_HOST_OR_UNKNOWN 2 /* host memory (pageable, page-locked) or nothing the runtime knows */
+#define BPP_PTR_MANAGED 3         /* managed (migrating) memory */
+int bpp_device_pointer_check(bpp_ctx *ctx, const void *p, int *kind);
+struct bpp_ingest_stats {
+  uint64_t device_calls;        /* uploads whose check and packing ran on the device */
+  uint64_t host_fallback_calls; /* uploads that were staged and took the host path */
+  uint64_t fallback_bytes;      /* bytes copied to staging by those */
+};
+int bpp_ingest_stats(bpp_ctx *ctx, struct bpp_ingest_stats *out);
+
 /* Pipelined host-buffers-in verification inside ONE context.  submit parses, validates and packs `in` into page-locked
  * staging on the calling thread (construction errors are returned by submit itself, as RangeStatement::init /
  * RangeProof::from_bytes would raise them before verify_batch is entered) and returns; the caller's buffers are free again.

@@ -280,6 +280,11 @@ struct RangeWitness {
   }
 };
 
+// a bpp_packed_batch whose six array fields are addresses in DEVICE memory (bpp.h: bpp_verify_batch_packed_device)
+struct DevicePackedBatch {
+  bpp_packed_batch arrays;
+};
+
 struct ExtendedMask {
   std::vector<Bytes32> blindings;
   bool operator==(const ExtendedMask &o) const { return blindings == o.blindings; }
@@ -478,7 +483,29 @@ class RangeProof {
     return masks;
   }
 
+  // The packed form of a homogeneous batch (bpp.h: bpp_packed_batch), as an overload pair: arrays in host memory, or --
+  // DevicePackedBatch -- arrays that already lie in the memory of the engine's device (bpp_verify_batch_packed_device: checked
+  // and packed on the device, never read on the host; whatever wrote them must be ordered before the engine's stream).
+  // Same results either way.
+  static std::vector<std::optional<ExtendedMask>> verify_batch(const RangeParameters &params, const bpp_packed_batch &in, VerifyAction action,
+                                                                size_t chunk = BPP_REFERENCE_CHUNK) {
+    return verify_packed_impl(params, in, action, chunk, false);
+  }
+  static std::vector<std::optional<ExtendedMask>> verify_batch(const RangeParameters &params, const DevicePackedBatch &in, VerifyAction action,
+                                                                size_t chunk = BPP_REFERENCE_CHUNK) {
+    return verify_packed_impl(params, in.arrays, action, chunk, true);
+  }
+
  private:
+  static std::vector<std::optional<ExtendedMask>> verify_packed_impl(const RangeParameters &params, const bpp_packed_batch &in, VerifyAction action,
+                                                                      size_t chunk, bool on_device) {
+    const uint32_t t = static_cast<uint32_t>(params.extension_degree());
+    std::vector<uint8_t> masks(in.n_items * t * 32), present(in.n_items);
+    char err[256] = {0};
+    check((on_device ? bpp_verify_batch_packed_device : bpp_verify_batch_packed)(params.engine().ctx(), params.handle(), &in, static_cast<int>(action),
+                                                                                   chunk, masks.data(), present.data(), err, sizeof(err)), err);
+    return masks_of(masks, present, t);
+  }
   static std::vector<std::optional<ExtendedMask>> verify_batch_impl(const std::vector<Transcript> &transcripts,
                                                                      const std::vector<RangeStatement> &statements,
                                                                      const std::vector<RangeProof> &proofs, VerifyAction action, size_t chunk,
@@ -531,6 +558,11 @@ class RangeProof {
       check(bpp_verify_batch(params.engine().ctx(), params.handle(), items.data(), n, static_cast<int>(action), chunk, masks.data(),
                              present.data(), err, sizeof(err)), err);
     }
+    return masks_of(masks, present, t);
+  }
+
+  static std::vector<std::optional<ExtendedMask>> masks_of(const std::vector<uint8_t> &masks, const std::vector<uint8_t> &present, uint32_t t) {
+    const size_t n = present.size();
     std::vector<std::optional<ExtendedMask>> out(n);
     for (size_t i = 0; i < n; i++) {
       if (!present[i]) continue;

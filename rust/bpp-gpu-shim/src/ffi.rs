@@ -201,6 +201,15 @@ pub struct bpp_verify_joint_stats {
     pub fallback_all_ok: u64,
 }
 
+/// `struct bpp_ingest_stats`: what the uploads from device memory (`bpp_batch_upload_packed_device`) of a context came to
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_ingest_stats {
+    pub device_calls: u64,
+    pub host_fallback_calls: u64,
+    pub fallback_bytes: u64,
+}
+
 /// `int (*bpp_all_gather_fn)(void *user, const void *send, void *recv, size_t bytes_per_rank)` (include/bpp.h)
 pub type bpp_all_gather_fn = Option<unsafe extern "C" fn(user: *mut c_void, send: *const c_void, recv: *mut c_void, bytes_per_rank: usize) -> c_int>;
 
@@ -252,6 +261,13 @@ extern "C" {
                                    errbuf_len: usize) -> c_int;
     pub fn bpp_verify_batch_packed(ctx: *mut bpp_ctx, params: u64, input: *const bpp_packed_batch, action: c_int, chunk: usize,
                                    masks_out: *mut u8, mask_present: *mut u8, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    // the packed form from arrays in DEVICE memory (six array fields of `input` are device addresses; include/bpp.h)
+    pub fn bpp_batch_upload_packed_device(ctx: *mut bpp_ctx, params: u64, input: *const bpp_packed_batch, batch: *mut u64,
+                                          errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_verify_batch_packed_device(ctx: *mut bpp_ctx, params: u64, input: *const bpp_packed_batch, action: c_int, chunk: usize,
+                                          masks_out: *mut u8, mask_present: *mut u8, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_device_pointer_check(ctx: *mut bpp_ctx, p: *const c_void, kind: *mut c_int) -> c_int;
+    pub fn bpp_ingest_stats(ctx: *mut bpp_ctx, out: *mut bpp_ingest_stats) -> c_int;
     pub fn bpp_ctx_pipeline_depth(ctx: *mut bpp_ctx, depth: u32) -> c_int;
     pub fn bpp_verify_submit_packed(ctx: *mut bpp_ctx, params: u64, input: *const bpp_packed_batch, action: c_int, chunk: usize,
                                     ticket: *mut u64, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
