@@ -165,6 +165,21 @@ def build_ingest_harness(force=False):
     return INGEST_SANITIZER_BIN
 
 
+VERDICT_SANITIZER_BIN = os.path.join(HERE, "hosttest_verdict_asan")
+
+
+def build_verdict_harness(force=False):
+    """hosttest_verdict.cpp (verdict.h: the verdict resolution that bpp_verify_enqueue runs on the device, held to the throwing
+    routines of upload_host.h) under ASan + UBSan: an executable, run by tests/test_verdict_host.py."""
+    src = os.path.join(CSRC, "hosttest_verdict.cpp")
+    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
+    if not force and not _stale(VERDICT_SANITIZER_BIN, deps):
+        return VERDICT_SANITIZER_BIN
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-fno-omit-frame-pointer", "-o", VERDICT_SANITIZER_BIN, src], check=True, cwd=CSRC)
+    return VERDICT_SANITIZER_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     build_hosttest(force="--force" in sys.argv)

@@ -76,6 +76,16 @@ class IngestStats(Structure):
     _fields_ = [(n, c_uint64) for n in ("device_calls", "host_fallback_calls", "fallback_bytes")]
 
 
+class DeviceVerdict(Structure):
+    """bpp_device_verdict: one group's record of bpp_verify_enqueue, 16 bytes, as it lies in device memory"""
+    _fields_ = [("code", ctypes.c_int32), ("tier", c_uint32), ("index", c_uint32), ("flags", c_uint32)]
+
+
+class EnqueueStats(Structure):
+    """struct bpp_enqueue_stats: what the enqueued verifications of a context came to"""
+    _fields_ = [(n, c_uint64) for n in ("calls", "groups", "host_waits", "layouts_in_call")]
+
+
 class RuntimeInfo(Structure):
     """bpp_runtime_info: what the library sees of its runtime preconditions (hardware queues, contexts, the small-call gate)"""
     _fields_ = [("device", c_int), ("contexts", c_uint32), ("contexts_peak", c_uint32), ("hw_queues", c_uint32),
@@ -152,6 +162,12 @@ SYMBOLS = [
     ("bpp_verify_resident_groups", c_int, [c_void_p, c_uint64, POINTER(c_uint32), c_size_t, POINTER(ShardResult)]),
     ("bpp_verify_resident_groups_actions", c_int, [c_void_p, c_uint64, POINTER(c_uint32), c_size_t, POINTER(c_int), POINTER(ShardResult),
                                                    c_void_p, c_void_p]),
+    ("bpp_verify_enqueue", c_int, [c_void_p, c_uint64, POINTER(c_uint32), c_size_t, c_size_t, POINTER(c_int), c_int, c_void_p, c_void_p,
+                                   c_void_p, POINTER(c_uint64)]),
+    ("bpp_enqueue_done", c_int, [c_void_p, c_uint64, POINTER(c_int)]),
+    ("bpp_enqueue_wait", c_int, [c_void_p, c_uint64]),
+    ("bpp_verdict_result", c_int, [POINTER(DeviceVerdict), POINTER(ShardResult)]),
+    ("bpp_enqueue_stats", c_int, [c_void_p, POINTER(EnqueueStats)]),
     ("bpp_batcher_verify_action", c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_char_p, c_size_t]),
     ("bpp_batcher_set_limits", c_int, [c_void_p, c_uint32, c_uint32]),
     ("bpp_batcher_largest_pool", c_int, [c_void_p, POINTER(c_uint32), POINTER(c_uint32)]),

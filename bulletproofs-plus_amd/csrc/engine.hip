@@ -41,6 +41,7 @@
 #include "runtime_host.h"
 #include "upload_host.h"
 #include "ingest.h"
+#include "verdict.h"
 
 using namespace bpp;
 
@@ -393,6 +394,20 @@ struct Batch {
   bool dev_chain_pending = false;  // k_weight_chain of this call is on the chain stream: enqueue_phase2 waits for it
   bool weights_on_host = false;  // the last PASS 2 read its weights from h_weights (b.weights holds them only in the sharded forms)
   bool seeds_dirty = false, masks_dirty = false;  // device copies of seed nonces / recovered masks not yet wiped
+  // bpp_verify_enqueue (verdict.h): device copies of rounds_bad / defer, made by the batch's first enqueue and only where the host
+  // vector holds a finding (a null pointer means all clear); word 0 of enq_words holds the call's zero-weight word (low half) and
+  // the count of groups that have read it (high half), words 1 .. the groups' key words.  The whole allocation is kept as an
+  // enqueue expects it -- word 0 zero, every key all ones: k_verdict_finish leaves it so -- whatever the layout, so enqueues of the
+  // same batch follow each other on the stream with nothing in between.  enq_actions: four slots of per-group actions in mapped
+  // page-locked memory, read by k_verdict_finish where the host wrote them; a slot is rewritten only once the ticket that last
+  // used it is done.
+  DevBuf<uint8_t> d_rounds_bad, d_defer;
+  bool enq_findings_ready = false;
+  DevBuf<unsigned long long> enq_words;
+  PinnedBuf<int> enq_actions;
+  uint32_t enq_actions_G = 0, enq_actions_next = 0;
+  uint64_t enq_slot_ticket[4] = {0, 0, 0, 0};
+  uint64_t enq_last_ticket = 0;  // the batch's last enqueue (0: none): a layout change waits for it
 };
 
 // A destroyed batch leaves its device and pinned allocations to the next upload on the same context (a caller that
@@ -614,6 +629,11 @@ struct bpp_ctx {
   struct CheckTamper {
     int proof = 0, byte = 1, mask = 1, times = 1, nonce = 0;
   } tamper;
+  // bpp_verify_enqueue: a ring of events, ticket t in slot t % size (a slot that a later ticket has taken over answers for that one,
+  // which is behind t on the same stream); the counters of bpp_enqueue_stats
+  std::vector<hipEvent_t> enq_events;
+  uint64_t enq_next = 1;
+  struct bpp_enqueue_stats enq_stats{};
   std::shared_ptr<Pipeline> pipe;  // bpp_verify_submit_packed / bpp_verify_collect: lanes, tickets (built on first submit)
   std::mutex pipe_init_mu;
   uint32_t pipe_depth = 3;
@@ -735,14 +755,15 @@ enum Mark { M_START = 0, M_TRANSCRIPTS, M_DECOMPRESS, M_SCALARS, M_WEIGHTS_IN, M
 struct StageTimer {
   bpp_ctx *ctx;
   bool have[16] = {false};
-  explicit StageTimer(bpp_ctx *c) : ctx(c) {
-    if (ctx->profile && !ctx->ev_ready) {
+  bool on = true;  // false (bpp_verify_enqueue): no stage events, whatever the context's profiling says
+  explicit StageTimer(bpp_ctx *c, bool enabled = true) : ctx(c), on(enabled) {
+    if (on && ctx->profile && !ctx->ev_ready) {
       for (auto &e : ctx->ev) HIP_CHECK(hipEventCreate(&e));
       ctx->ev_ready = true;
     }
   }
   void mark(int idx) {
-    if (ctx->profile && idx < 16) {
+    if (on && ctx->profile && idx < 16) {
       // light form: the two events that bracket the roofline kernel and nothing else (every mark is a barrier packet with a
       // timestamp in the queue; thirteen per step read 0-4 % lower than two, inside the run-to-run spread: profiles/r06_stage_events_ab.txt)
       if (ctx->profile_light && idx != M_ORDER && idx != M_ACC) return;
@@ -1273,6 +1294,7 @@ void bpp_ctx_destroy(bpp_ctx *ctx) {
     for (auto &e : ctx->ev) (void)hipEventDestroy(e);
   if (ctx->ev_rng_ready) (void)hipEventDestroy(ctx->ev_rng);
   if (ctx->ev_wait_ready) (void)hipEventDestroy(ctx->ev_wait);
+  for (auto &e : ctx->enq_events) (void)hipEventDestroy(e);  // (the stream has been synchronised: every ticket is retired)
   if (ctx->side_stream) {
     (void)hipStreamSynchronize(ctx->side_stream);
     (void)hipStreamDestroy(ctx->side_stream);
@@ -2275,7 +2297,9 @@ void enqueue_finish_wide(bpp_ctx *ctx, Batch &b, hipStream_t st, bool launch = t
 }
 
 // k_weight_chain + k_chain_finish on `st`: b.rng_out -> b.weights (canonical bytes), one wavefront per group
-void enqueue_device_chain(bpp_ctx *ctx, Batch &b, hipStream_t st) {
+// zero_word != nullptr (bpp_verify_enqueue): the call's zero-weight finding goes to that device word, which belongs to the enqueue;
+// the context's host-visible word is neither reset nor written (another call may be in flight behind it)
+void enqueue_device_chain(bpp_ctx *ctx, Batch &b, hipStream_t st, uint32_t *zero_word = nullptr) {
   if (!ctx->d_chain_t0.p) {  // once per context: the weight transcript as Transcript::new leaves it (src/range_proof.rs:811)
     Strobe t0;
     const char *lbl = "Bulletproofs+ verifier weights";
@@ -2285,18 +2309,22 @@ void enqueue_device_chain(bpp_ctx *ctx, Batch &b, hipStream_t st) {
     ctx->h_chain_zero.resize(1);
   }
   b.chain_wide.alloc((size_t)b.B * 16);
-  ctx->h_chain_zero[0] = 0;
+  if (!zero_word) ctx->h_chain_zero[0] = 0;
   const uint32_t test_zero = ctx->opt.chain_test_zero > 0 ? (uint32_t)ctx->opt.chain_test_zero : 0u;
   hipLaunchKernelGGL(k_weight_chain, dim3(b.G), dim3(64), 0, st, b.rng_out.p, b.group_first.p, b.G, ctx->d_chain_t0.p, b.chain_wide.p);
-  hipLaunchKernelGGL(k_chain_finish, dim3(cdiv(b.B, 64)), dim3(64), 0, st, b.chain_wide.p, b.B, b.weights.p, ctx->h_chain_zero.dev(), test_zero);
+  hipLaunchKernelGGL(k_chain_finish, dim3(cdiv(b.B, 64)), dim3(64), 0, st, b.chain_wide.p, b.B, b.weights.p,
+                     zero_word ? zero_word : ctx->h_chain_zero.dev(), test_zero);
   ctx->device_chain_calls++;
 }
 
 // dev_chain: the weight chains follow PASS 1 as kernels (option "chain_inline" = 0: on a stream of their own beside the decompression
 // and the weight-free scalars, joined by enqueue_phase2): nothing comes to the host and the function does not wait
 void enqueue_phase1(bpp_ctx *ctx, Batch &b, StageTimer &tm, bool pass1_only, uint8_t *rng_dev_dst = nullptr, size_t rng_row_bytes = 0,
-                    size_t rng_dst_pitch = 0, bool dev_chain = false) {
-  const bool fetch_rng = rng_dev_dst == nullptr && !dev_chain;
+                    size_t rng_dst_pitch = 0, bool dev_chain = false, uint32_t *chain_zero_word = nullptr) {
+  // chain_zero_word != nullptr (bpp_verify_enqueue): the device chain, where the call runs one, runs in line on the call's stream
+  // whatever "chain_inline" says and reports a zero weight there (enqueue_device_chain); nothing comes to the host and the function
+  // does not wait, with or without a chain
+  const bool fetch_rng = rng_dev_dst == nullptr && !dev_chain && !chain_zero_word;
   b.dev_chain_pending = false;
   Params &P = *b.params;
   hipStream_t s = ctx->stream;
@@ -2361,8 +2389,8 @@ void enqueue_phase1(bpp_ctx *ctx, Batch &b, StageTimer &tm, bool pass1_only, uin
     // On the call's own stream (the rule): measured against a high-priority stream of their own beside the decompression -- the same
     // rate once one more step is in flight, and the cross-stream events of that form leave a helper thread of the runtime at 80 %
     // of a core (profiles/r06_chain_inline_ab.txt); "chain_inline" = 0 brings the side stream back
-    if (ctx->profile || ctx->opt.chain_inline != 0) {
-      enqueue_device_chain(ctx, b, s);
+    if (ctx->profile || ctx->opt.chain_inline != 0 || chain_zero_word) {
+      enqueue_device_chain(ctx, b, s, chain_zero_word);
       tm.mark(M_CHAIN);
     } else {
       if (!ctx->chain_stream) {
@@ -3171,6 +3199,197 @@ int verify_uploaded(bpp_ctx *ctx, size_t n_items, Upload upload, int action, siz
   return rc;
 }
 
+// ---- bpp_verify_enqueue: the launches of verify_flow_once with the outcome resolved on the device (verdict.h) and no wait.
+//
+// Context-level, host-written state a call in flight reads, and why a second call behind it may go ahead:
+//   h_chain_zero   not used: the zero-weight word is word 0 of the batch's enq_words, reset by k_verdict_finish in stream order.
+//   pin_small      read by k_layout_terms only; every writer (msm_plan_alloc, layout_groups) synchronises the stream before it
+//                  writes and layout_groups again before it returns, so no call in flight ever reads it.  Layouts are built by
+//                  the first enqueue of a (batch, layout) alone.
+//   ev_fork, ev_join, ev_rng   re-recorded by every call.  hipStreamWaitEvent waits for the record that was the event's latest
+//                  WHEN THE WAIT WAS ENQUEUED; a later record does not move it.  Both streams are in order, so the side stream's
+//                  decompression of call k + 1 starts behind call k's last kernel on the main stream (ev_fork) and behind call k's
+//                  decompression (same stream): the two calls may even be of the same batch.
+//   h_wide, h_weights, h_rng   the host chains' buffers: the device chain reads b.rng_out and writes b.weights, both device
+//                  memory of the batch, ordered by the stream.
+//   h_status, h_ident, h_masks   k_results_out's targets: that kernel is not launched here.
+//   the per-group actions   mapped host memory of the BATCH, four slots (Batch::enq_actions): a slot is rewritten only once the
+//                  ticket that last read it is done.
+bool enqueue_ticket_done(bpp_ctx *ctx, uint64_t ticket) {
+  if (ticket == 0 || ctx->enq_events.empty()) return true;
+  const hipError_t e = hipEventQuery(ctx->enq_events[ticket % ctx->enq_events.size()]);
+  if (e == hipSuccess) return true;
+  if (e != hipErrorNotReady) HIP_CHECK(e);
+  return false;
+}
+void enqueue_ticket_wait(bpp_ctx *ctx, uint64_t ticket) {
+  if (ticket == 0 || ctx->enq_events.empty()) return;
+  HIP_CHECK(hipEventSynchronize(ctx->enq_events[ticket % ctx->enq_events.size()]));
+}
+
+// would layout_groups(ctx, b, chunk, bounds) find its layout there?  (the same test)
+bool layout_is_current(const Batch &b, size_t chunk, const std::vector<uint32_t> *bounds) {
+  if (!b.G) return false;
+  if (bounds) return b.last_chunk == (size_t)-1 && b.h_group_first == *bounds;
+  return b.last_chunk == (chunk == (size_t)-1 ? 0 : chunk);
+}
+
+int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first, size_t n_groups, size_t chunk, const int *actions,
+                          int action_all, bpp_device_verdict *verdicts_dev, uint8_t *masks_dev, uint8_t *mask_present_dev, uint64_t *ticket) {
+  try {
+    auto it = ctx->batches.find(batch);
+    if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
+    if (!verdicts_dev || !ticket) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+    Batch &b = *it->second;
+    std::vector<uint32_t> bounds;
+    if (group_first) {
+      if (n_groups == 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+      bounds.assign(group_first, group_first + n_groups + 1);
+      if (bounds.front() != 0 || bounds.back() != b.B) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "group boundaries must run from 0 to the batch size");
+      for (size_t g = 0; g < n_groups; g++)
+        if (bounds[g] >= bounds[g + 1]) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "empty or unordered group");
+    } else {
+      const uint32_t cz = (chunk == 0 || chunk >= b.B) ? b.B : (uint32_t)chunk;
+      if (n_groups != 0 && n_groups != cdiv(b.B, cz))
+        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "n_groups is not the number of chunks (0: whatever it is)");
+      n_groups = cdiv(b.B, cz);
+    }
+    if (action_all < 0 || action_all > 2) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "unknown verify action");
+    for (size_t g = 0; actions && g < n_groups; g++)
+      if (actions[g] < 0 || actions[g] > 2) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "unknown verify action");
+    if (ctx->opt.verify_check == 1 && ctx->verify_check_off <= 0)
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "\"verify_check\" = 1: a rejection is rechecked by decisions of the host, which an enqueued call cannot make");
+    if (b.want_states) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "the batch hands out transcript states: an enqueued call cannot");
+    const struct { const void *p; const char *name; bool required; } bufs[3] = {
+        {verdicts_dev, "verdicts_dev", true}, {masks_dev, "masks_dev", false}, {mask_present_dev, "mask_present_dev", false}};
+    for (const auto &f : bufs) {
+      if (!f.p && !f.required) continue;
+      const int kind = device_pointer_kind(ctx->device, f.p);
+      if (kind != BPP_PTR_THIS_DEVICE)
+        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(f.name) + ": not device memory of the context's device (pointer kind " + std::to_string(kind) + ")");
+    }
+    if (((uintptr_t)verdicts_dev & 15u) || ((uintptr_t)masks_dev & 15u))
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "verdicts_dev / masks_dev: not 16-byte aligned");
+
+    Params &P = *b.params;
+    hipStream_t s = ctx->stream;
+    struct bpp_enqueue_stats &es = ctx->enq_stats;
+    const std::vector<uint32_t> *bp = group_first ? &bounds : nullptr;
+    // ---- the first enqueue of a (batch, layout): what bpp_batch_prepare does, and the buffers of this path
+    const bool fresh = !layout_is_current(b, chunk, bp) || !b.enq_words.p || b.enq_words.n < n_groups + 1 || !b.enq_findings_ready ||
+                       b.enq_actions_G < n_groups || ctx->enq_events.empty() || !b.chain_wide.p || !ctx->d_chain_t0.p;
+    if (fresh) {
+      if (!enqueue_ticket_done(ctx, b.enq_last_ticket)) {  // its kernels read the layout that is about to go
+        enqueue_ticket_wait(ctx, b.enq_last_ticket);
+        es.host_waits++;
+      }
+      if (ctx->enq_events.empty()) {
+        ctx->enq_events.resize(64);
+        for (auto &e : ctx->enq_events) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      }
+      ensure_ev_rng(ctx);
+      layout_groups(ctx, b, chunk, bp);
+      b.chain_wide.alloc((size_t)b.B * 16);
+      if (!ctx->d_chain_t0.p) {  // (as enqueue_device_chain makes it)
+        Strobe t0;
+        const char *lbl = "Bulletproofs+ verifier weights";
+        merlin_new(t0, (const uint8_t *)lbl, (uint32_t)strlen(lbl));
+        ctx->d_chain_t0.alloc(1);
+        HIP_CHECK(hipMemcpy(ctx->d_chain_t0.p, &t0, sizeof(t0), hipMemcpyHostToDevice));
+        ctx->h_chain_zero.resize(1);
+      }
+      if (!b.enq_words.p || b.enq_words.n < (size_t)b.G + 1) {
+        b.enq_words.alloc((size_t)b.G + 1);
+        HIP_CHECK(hipMemsetAsync(b.enq_words.p, 0xff, b.enq_words.n * 8, s));
+        HIP_CHECK(hipMemsetAsync(b.enq_words.p, 0, 8, s));
+      }
+      if (!b.enq_findings_ready) {  // uploaded once, and only where there is a finding
+        if (b.any_rounds_bad) {
+          b.d_rounds_bad.alloc(b.B);
+          HIP_CHECK(hipMemcpy(b.d_rounds_bad.p, b.rounds_bad.data(), b.B, hipMemcpyHostToDevice));
+        }
+        if (b.any_defer) {
+          b.d_defer.alloc(b.B);
+          HIP_CHECK(hipMemcpy(b.d_defer.p, b.defer.data(), b.B, hipMemcpyHostToDevice));
+        }
+        b.enq_findings_ready = true;
+      }
+      if (b.enq_actions_G < b.G) {  // (no ticket of this batch is in flight here)
+        b.enq_actions.resize(4 * (size_t)b.G);
+        b.enq_actions_G = b.G;
+        for (auto &t : b.enq_slot_ticket) t = 0;
+        b.enq_actions_next = 0;
+      }
+      HIP_CHECK(hipStreamSynchronize(s));
+      es.layouts_in_call++;
+    }
+    const uint32_t G = b.G;
+    // ---- the per-group actions where the last kernel reads them
+    const int *actions_dev = nullptr;
+    if (actions) {
+      const size_t stride = b.enq_actions_G;
+      int slot = -1;
+      for (int k = 0; k < 4 && slot < 0; k++)  // a slot that holds these very actions is shared
+        if (b.enq_slot_ticket[k] && memcmp(b.enq_actions.data() + k * stride, actions, (size_t)G * sizeof(int)) == 0) slot = k;
+      if (slot < 0) {
+        slot = (int)(b.enq_actions_next++ % 4);
+        if (!enqueue_ticket_done(ctx, b.enq_slot_ticket[slot])) {
+          enqueue_ticket_wait(ctx, b.enq_slot_ticket[slot]);
+          es.host_waits++;
+        }
+        memcpy(b.enq_actions.data() + slot * stride, actions, (size_t)G * sizeof(int));
+      }
+      b.enq_slot_ticket[slot] = ctx->enq_next;
+      actions_dev = b.enq_actions.dev() + slot * stride;
+    }
+    auto action_of = [&](uint32_t g) { return actions ? actions[g] : action_all; };
+    bool any_msm = false, any_masks = false;
+    for (uint32_t g = 0; g < G; g++) {
+      any_msm = any_msm || action_of(g) != BPP_RECOVER_ONLY;
+      any_masks = any_masks || action_of(g) != BPP_VERIFY_ONLY;
+    }
+    // the early-outs of verify_flow_once that depend on what the host knows alone
+    const bool deferred_only = b.any_defer && G == 1;  // (any_defer: some proof carries a deferred finding)
+    const bool pass1_only = b.any_rounds_bad && G == 1;
+    const bool want_msm = !deferred_only && !pass1_only && any_msm;
+    const bool want_masks = !deferred_only && !pass1_only && any_masks && b.any_seed;
+    uint32_t *zero_word = reinterpret_cast<uint32_t *>(b.enq_words.p);
+    unsigned long long *keys = b.enq_words.p + 1;
+    StageTimer tm(ctx, false);
+    if (deferred_only) {
+      if (!b.status_clean) HIP_CHECK(hipMemcpyAsync(b.status.p, b.status0.p, (size_t)b.B * 4, hipMemcpyDeviceToDevice, s));
+    } else {
+      enqueue_phase1(ctx, b, tm, !want_msm, nullptr, 0, 0, want_msm, zero_word);
+      if (want_masks) {
+        hipLaunchKernelGGL(k_masks, dim3(cdiv(b.B, 64)), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.chal.p, b.seeds.p, P.n_bits, P.t, b.cs, b.B,
+                           b.masks.p);
+        b.masks_dirty = true;
+      }
+      if (want_msm) {
+        enqueue_phase2(ctx, b, tm, true, false, nullptr, false);
+        b.have_trace = true;
+      }
+    }
+    hipLaunchKernelGGL(k_verdict_scan, dim3(cdiv(b.B, BPP_VERDICT_BLOCK)), dim3(BPP_VERDICT_BLOCK), 0, s, b.status.p, b.status0.p,
+                       b.d_rounds_bad.p ? (const uint8_t *)b.d_rounds_bad.p : (const uint8_t *)nullptr,
+                       b.d_defer.p ? (const uint8_t *)b.d_defer.p : (const uint8_t *)nullptr, b.B, b.group_first.p, G, keys);
+    b.status_clean = true;  // (in stream order, as behind k_results_out)
+    hipLaunchKernelGGL(k_verdict_finish, dim3(G), dim3(64), 0, s, keys, want_msm ? b.msm.is_identity.p : (const uint32_t *)nullptr, actions_dev,
+                       action_all, zero_word, zero_word + 1, b.group_first.p, G, b.d_desc.p,
+                       want_masks ? (const uint4 *)b.masks.p : (const uint4 *)nullptr, (uint32_t)(P.t * 2), verdicts_dev, (uint4 *)masks_dev,
+                       mask_present_dev);
+    HIP_CHECK(hipGetLastError());
+    const uint64_t t = ctx->enq_next++;
+    HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));
+    b.enq_last_ticket = t;
+    *ticket = t;
+    es.calls++;
+    es.groups += G;
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, nullptr, 0)
+}
+
 }  // namespace
 
 extern "C" {
@@ -3205,6 +3424,51 @@ int bpp_verify_resident_groups_actions(bpp_ctx *ctx, uint64_t batch, const uint3
 
 int bpp_verify_resident_groups(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first, size_t n_groups, bpp_shard_result *results) {
   return bpp_verify_resident_groups_actions(ctx, batch, group_first, n_groups, nullptr, results, nullptr, nullptr);
+}
+
+// (no gate: enqueued calls are serial on their stream, and the gate has no place to release them)
+int bpp_verify_enqueue(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first, size_t n_groups, size_t chunk, const int *actions, int action_all,
+                       bpp_device_verdict *verdicts_dev, uint8_t *masks_dev, uint8_t *mask_present_dev, uint64_t *ticket) {
+  BPP_ENTRY(ctx);
+  return verify_enqueue_locked(ctx, batch, group_first, n_groups, chunk, actions, action_all, verdicts_dev, masks_dev, mask_present_dev, ticket);
+}
+
+int bpp_enqueue_done(bpp_ctx *ctx, uint64_t ticket, int *done) {
+  BPP_ENTRY(ctx);
+  try {
+    if (!done) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+    if (ticket == 0 || ticket >= ctx->enq_next) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown ticket");
+    *done = enqueue_ticket_done(ctx, ticket) ? 1 : 0;
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, nullptr, 0)
+}
+
+int bpp_enqueue_wait(bpp_ctx *ctx, uint64_t ticket) {
+  BPP_ENTRY(ctx);
+  try {
+    if (ticket == 0 || ticket >= ctx->enq_next) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown ticket");
+    enqueue_ticket_wait(ctx, ticket);
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, nullptr, 0)
+}
+
+int bpp_verdict_result(const bpp_device_verdict *host_copy, bpp_shard_result *out) {
+  if (!host_copy || !out || !(host_copy->flags & BPP_VERDICT_WRITTEN)) return BPP_ERR_INVALID_ARGUMENT;
+  memset(out, 0, sizeof(*out));
+  if (host_copy->flags & BPP_VERDICT_REDRAW)
+    shard_result_set(*out, BPP_OK, BPP_TIER_NONE, -1, 0, "a device weight came out zero: nothing is claimed, run a blocking call");
+  else
+    shard_result_set(*out, host_copy->code, (int)host_copy->tier, -1, host_copy->index, verdict_message(host_copy->tier, host_copy->code));
+  return BPP_OK;
+}
+
+int bpp_enqueue_stats(bpp_ctx *ctx, struct bpp_enqueue_stats *out) {
+  BPP_ENTRY(ctx);
+  if (!out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+  *out = ctx->enq_stats;
+  return BPP_OK;
 }
 
 int bpp_verify_batch_with_challenges(bpp_ctx *ctx, uint64_t params, const bpp_verify_item *items, size_t n_items,

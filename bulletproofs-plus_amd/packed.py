@@ -661,3 +661,94 @@ class ResidentBatch(api.ResidentBatch):
                                                  self._present.ctypes.data, err, 256)
         api._check(rc, self.engine.ctx, err)
         return self._masks, self._present
+
+    def enqueue(self, bounds=None, chunk=0, actions=None, action=api.VerifyAction.VerifyOnly, verdicts=None, masks=None, present=None):
+        """bpp_verify_enqueue: the stream-ordered counterpart of verify_groups_actions.  Enqueues on the engine's stream and returns an
+        Enqueued at once; the per-group records and the recovered masks land in torch tensors on the engine's device -- `verdicts`
+        int32 [G, 4] (code, tier, index, flags), `masks` uint8 [n, t, 32], `present` uint8 [n]; the ones not given are allocated
+        (masks and present only when some group recovers) -- and are valid in stream order behind the call: on an engine made on
+        torch's current stream, torch work enqueued afterwards may read them with no synchronisation in between.
+        bounds: explicit group boundaries; None: equal chunks of `chunk` proofs (0: one group).  actions: one VerifyAction per
+        group; None: `action` for every group."""
+        import torch
+        dev = torch.device("cuda", int(self.engine.device))
+        if bounds is not None:
+            G = len(bounds) - 1
+            arr = (ctypes.c_uint32 * (G + 1))(*bounds)
+        else:
+            cz = self.n if (chunk == 0 or chunk >= self.n) else int(chunk)
+            G, arr = (self.n + cz - 1) // cz, None
+        act = None if actions is None else (ctypes.c_int * len(actions))(*[int(a) for a in actions])
+        if actions is not None and len(actions) != G:
+            raise api.ProofError(api.ProofErrorKind.InvalidArgument, "one action per group expected")
+        recovers = any(int(a) != 0 for a in actions) if actions is not None else int(action) != 0
+        if verdicts is None:
+            verdicts = torch.empty((max(G, 0), 4), dtype=torch.int32, device=dev)
+        if masks is None and recovers:
+            masks = torch.empty((self.n, self.t, 32), dtype=torch.uint8, device=dev)
+        if present is None and recovers:
+            present = torch.empty((self.n,), dtype=torch.uint8, device=dev)
+
+        def addr(a, name, dtype, shape):
+            if a is None:
+                return None
+            if not hasattr(a, "data_ptr"):  # (a raw address: the engine checks what lies behind it)
+                return ctypes.c_void_p(int(a))
+            if a.dtype != dtype or tuple(a.shape) != shape or not a.is_contiguous():
+                raise api.ProofError(api.ProofErrorKind.InvalidArgument, "%s: a contiguous %s tensor of shape %s expected" % (name, dtype, shape))
+            return ctypes.c_void_p(a.data_ptr())
+
+        ticket = c_uint64()
+        rc = self.engine.lib.bpp_verify_enqueue(self.engine.ctx, self.handle, arr, G, int(chunk), act, int(action),
+                                                addr(verdicts, "verdicts", torch.int32, (G, 4)),
+                                                addr(masks, "masks", torch.uint8, (self.n, self.t, 32)),
+                                                addr(present, "present", torch.uint8, (self.n,)), byref(ticket))
+        api._check(rc, self.engine.ctx)
+        return Enqueued(self.engine, ticket.value, G, verdicts, masks, present)
+
+
+VERDICT_WRITTEN, VERDICT_REDRAW = 1, 2
+
+
+class Enqueued:
+    """What ResidentBatch.enqueue returns: `.verdicts` (int32 [G, 4]: code, tier, index, flags), `.masks`, `.present` -- device
+    tensors, valid in stream order behind the call -- and the ticket: done() is one event query, wait() blocks until the call's
+    results are there, results() waits, copies the records back and returns the dicts of verify_groups_actions (a group whose
+    record carries VERDICT_REDRAW claims nothing: code 0, tier 0, and a message that says so; redraws() lists those groups)."""
+
+    def __init__(self, engine, ticket, n_groups, verdicts, masks, present):
+        self.engine, self.ticket, self.n_groups = engine, ticket, n_groups
+        self.verdicts, self.masks, self.present = verdicts, masks, present
+
+    def done(self):
+        d = ctypes.c_int()
+        api._check(self.engine.lib.bpp_enqueue_done(self.engine.ctx, self.ticket, byref(d)), self.engine.ctx)
+        return bool(d.value)
+
+    def wait(self):
+        api._check(self.engine.lib.bpp_enqueue_wait(self.engine.ctx, self.ticket), self.engine.ctx)
+
+    def _records(self):
+        self.wait()
+        host = np.ascontiguousarray(self.verdicts.cpu().numpy())
+        return host.ctypes.data_as(POINTER(_lib.DeviceVerdict)), host
+
+    def results(self):
+        recs, _keep = self._records()
+        out = []
+        for g in range(self.n_groups):
+            r = _lib.ShardResult()
+            api._check(self.engine.lib.bpp_verdict_result(byref(recs[g]), byref(r)), None)
+            out.append({"code": r.code, "tier": r.tier, "index": r.index, "msg": r.msg.decode(errors="replace")})
+        return out
+
+    def redraws(self):
+        _recs, host = self._records()
+        return [g for g in range(self.n_groups) if int(host[g, 3]) & VERDICT_REDRAW]
+
+
+def enqueue_stats(engine):
+    """bpp_enqueue_stats as a dict: calls, groups, host_waits, layouts_in_call"""
+    s = _lib.EnqueueStats()
+    api._check(engine.lib.bpp_enqueue_stats(engine.ctx, byref(s)), engine.ctx)
+    return {n: int(getattr(s, n)) for n, _ in _lib.EnqueueStats._fields_}

@@ -469,6 +469,62 @@ int bpp_verify_resident_groups(bpp_ctx *ctx, uint64_t batch, const uint32_t *gro
  * nor PASS 2 run. */
 int bpp_verify_resident_groups_actions(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first, size_t n_groups, const int *actions,
                                        bpp_shard_result *results, uint8_t *masks_out, uint8_t *mask_present);
+
+/* ---- stream-ordered calls that leave their verdicts on the device ----
+ * bpp_verify_enqueue is the stream-ordered counterpart of bpp_verify_resident_groups_actions: the same groups (explicit
+ * boundaries, or group_first == NULL: equal chunks of `chunk` proofs, 0 = one group), the same VerifyAction per group (actions ==
+ * NULL: action_all everywhere), the same outcomes -- but it ENQUEUES on the context's stream and returns.  One 16-byte record per
+ * group and the recovered masks land in DEVICE buffers the caller names; they are valid in stream order behind the call, so work
+ * the caller puts on the same stream afterwards (bpp_ctx_create_on_stream) may read them with no host round trip, and one thread
+ * can enqueue step after step, over one or several contexts, without waiting.
+ *
+ * RECORDS: verdicts_dev[g] = {code, tier, index, flags} of group g as the blocking call would report them (tier BPP_TIER_NONE and
+ * code 0: its verify() returned Ok; index counts inside the group).  flags always carries BPP_VERDICT_WRITTEN (the buffer may start
+ * out as anything).  BPP_VERDICT_REDRAW: one of the call's device weights came out zero (probability 2^-252 per proof); every group
+ * that needed weights then claims NOTHING else -- code 0, tier 0 -- and gets no masks: run a blocking call on the batch, which
+ * redraws on the host as the reference does.  bpp_verdict_result turns a host copy of a record into a bpp_shard_result with the
+ * message text of the blocking calls.
+ * MASKS: masks_dev n x extension_degree x 32 (16-byte aligned) and mask_present_dev n, either may be NULL.  A group gets the masks
+ * of its items that carry a seed nonce when its verdict is Ok and its action recovers; every other slot is zero / absent.  A
+ * RecoverOnly group is never held to the final check and keeps its masks whatever the final MSM says.  The engine's own copy is
+ * wiped by the rules of every resident batch; the caller's buffer is the caller's.
+ * LAUNCHES: those of the blocking call -- PASS 1, the weight chains (always as kernels, in line on the stream, whatever "chain"
+ * says), decompression, PASS 2, the final MSM -- then two kernels that resolve the reference's error precedence on the device.  The
+ * early-outs that depend only on what the host knows are kept: one group with a deferred finding enqueues the verdict kernels alone,
+ * one group with a bad L/R count PASS 1 and those, and a call whose groups are all RecoverOnly runs neither chains nor PASS 2.
+ * STEADY STATE: the call allocates nothing, copies nothing to the host and waits for nothing.  The FIRST enqueue of a (batch,
+ * layout) does what bpp_batch_prepare does, stream synchronisation included (layouts_in_call counts these); a layout change on a
+ * batch that has tickets in flight waits for them first (host_waits counts these, and nothing else ever does).  The same batch may
+ * be enqueued again while an earlier enqueue of the same layout is in flight: the stream orders them.
+ * REFUSED, before anything is launched (BPP_ERR_INVALID_ARGUMENT, the reason in bpp_ctx_last_error): a buffer that is not
+ * BPP_PTR_THIS_DEVICE memory by bpp_device_pointer_check (the field is named), bad boundaries, an empty group, an unknown action;
+ * "verify_check" = 1 (a promise this path cannot keep: the recheck is decided on the host); a batch whose verification hands out
+ * transcript states.  An unknown batch is BPP_ERR_BAD_HANDLE.  The joint final check ("verify_joint") and stage profiling need
+ * host decisions and are silently not taken.  Enqueued calls do not pass the small-call gate (they are serial on their stream)
+ * and teach the wait hints nothing.
+ * TICKETS: bpp_enqueue_done is one event query, bpp_enqueue_wait blocks until the call's results are there -- for callers that do
+ * want the host to know.  bpp_batch_destroy and bpp_ctx_destroy synchronise the stream and thereby retire every ticket. */
+typedef struct {
+  int32_t code;
+  uint32_t tier;
+  uint32_t index;
+  uint32_t flags;
+} bpp_device_verdict; /* 16 bytes */
+#define BPP_VERDICT_WRITTEN 1u /* set by the call: the caller's buffer may start out as anything */
+#define BPP_VERDICT_REDRAW 2u  /* a device weight came out zero (2^-252): nothing claimed, run a blocking call */
+int bpp_verify_enqueue(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first /* NULL: equal chunks */, size_t n_groups, size_t chunk,
+                       const int *actions /* NULL: action_all */, int action_all, bpp_device_verdict *verdicts_dev /* n_groups */,
+                       uint8_t *masks_dev /* n x t x 32, may be NULL */, uint8_t *mask_present_dev /* n, may be NULL */, uint64_t *ticket);
+int bpp_enqueue_done(bpp_ctx *ctx, uint64_t ticket, int *done); /* one event query */
+int bpp_enqueue_wait(bpp_ctx *ctx, uint64_t ticket);            /* for callers that do want the host to know */
+/* code, tier, index and the blocking calls' message text of a record copied to the host (rank = -1); a redraw record comes back as
+ * code 0 / tier 0 with a message that says so.  BPP_ERR_INVALID_ARGUMENT for a record the call never wrote. */
+int bpp_verdict_result(const bpp_device_verdict *host_copy, bpp_shard_result *out);
+struct bpp_enqueue_stats {
+  uint64_t calls, groups, host_waits, layouts_in_call;
+};
+int bpp_enqueue_stats(bpp_ctx *ctx, struct bpp_enqueue_stats *out);
+
 /* bpp_batcher: many host threads, each with ONE reference batch per call.  Separate small calls stop at about 5 000 calls per
  * second whatever the number of callers (a small call is a chain of latency-bound kernels and the chip runs about six of those
  * side by side); the batcher pools the calls that are waiting into grouped engine calls (bpp_verify_resident_groups) on

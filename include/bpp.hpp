@@ -135,6 +135,48 @@ class Engine {
     return r;
   }
 
+  // Stream-ordered verification of a resident batch (bpp_verify_enqueue): the call enqueues on the engine's stream and returns; one
+  // 16-byte record per group and the recovered masks land in the DEVICE buffers the caller names, valid in stream order behind the
+  // call.  The ticket is for callers that do want the host to know: done() is one event query, wait() blocks, results(host_copy)
+  // turns records the caller has copied to the host into the outcomes of the blocking call (code, tier, index, message text).
+  class EnqueueTicket {
+   public:
+    uint64_t id = 0;
+    size_t n_groups = 0;
+    bool done() const {
+      int d = 0;
+      check(bpp_enqueue_done(ctx_, id, &d), "unknown ticket");
+      return d != 0;
+    }
+    void wait() const { check(bpp_enqueue_wait(ctx_, id), bpp_ctx_last_error(ctx_)); }
+    std::vector<bpp_shard_result> results(const bpp_device_verdict *host_copy) const {
+      std::vector<bpp_shard_result> out(n_groups);
+      for (size_t g = 0; g < n_groups; g++) check(bpp_verdict_result(&host_copy[g], &out[g]), "a record the call never wrote");
+      return out;
+    }
+
+   private:
+    friend class Engine;
+    bpp_ctx *ctx_ = nullptr;
+  };
+  // group_first == nullptr: equal chunks of `chunk` proofs (0: one group) and n_groups = their number; actions == nullptr:
+  // `action` for every group
+  EnqueueTicket verify_enqueue(uint64_t batch, const uint32_t *group_first, size_t n_groups, size_t chunk, const int *actions,
+                               VerifyAction action, bpp_device_verdict *verdicts_dev, uint8_t *masks_dev = nullptr,
+                               uint8_t *mask_present_dev = nullptr) {
+    EnqueueTicket t;
+    t.ctx_ = ctx_;
+    t.n_groups = n_groups;
+    check(bpp_verify_enqueue(ctx_, batch, group_first, n_groups, chunk, actions, (int)action, verdicts_dev, masks_dev, mask_present_dev, &t.id),
+          bpp_ctx_last_error(ctx_));
+    return t;
+  }
+  struct bpp_enqueue_stats enqueue_stats() const {
+    struct bpp_enqueue_stats s{};
+    check(::bpp_enqueue_stats(ctx_, &s), bpp_ctx_last_error(ctx_));
+    return s;
+  }
+
  private:
   bpp_ctx *ctx_ = nullptr;
 };

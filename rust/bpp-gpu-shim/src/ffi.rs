@@ -210,6 +210,28 @@ pub struct bpp_ingest_stats {
     pub fallback_bytes: u64,
 }
 
+/// `bpp_device_verdict`: one group's record of `bpp_verify_enqueue`, 16 bytes, as it lies in device memory
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_device_verdict {
+    pub code: i32,
+    pub tier: u32,
+    pub index: u32,
+    pub flags: u32,
+}
+pub const BPP_VERDICT_WRITTEN: u32 = 1;
+pub const BPP_VERDICT_REDRAW: u32 = 2;
+
+/// `struct bpp_enqueue_stats`: what the enqueued verifications (`bpp_verify_enqueue`) of a context came to
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_enqueue_stats {
+    pub calls: u64,
+    pub groups: u64,
+    pub host_waits: u64,
+    pub layouts_in_call: u64,
+}
+
 /// `int (*bpp_all_gather_fn)(void *user, const void *send, void *recv, size_t bytes_per_rank)` (include/bpp.h)
 pub type bpp_all_gather_fn = Option<unsafe extern "C" fn(user: *mut c_void, send: *const c_void, recv: *mut c_void, bytes_per_rank: usize) -> c_int>;
 
@@ -300,6 +322,14 @@ extern "C" {
     pub fn bpp_batcher_verify(b: *mut bpp_batcher, input: *const bpp_packed_batch, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
     pub fn bpp_verify_resident_groups_actions(ctx: *mut bpp_ctx, batch: u64, group_first: *const u32, n_groups: usize, actions: *const c_int,
                                               results: *mut bpp_shard_result, masks_out: *mut u8, mask_present: *mut u8) -> c_int;
+    // stream-ordered calls that leave their verdicts (and masks) in device memory the caller names
+    pub fn bpp_verify_enqueue(ctx: *mut bpp_ctx, batch: u64, group_first: *const u32, n_groups: usize, chunk: usize, actions: *const c_int,
+                              action_all: c_int, verdicts_dev: *mut bpp_device_verdict, masks_dev: *mut u8, mask_present_dev: *mut u8,
+                              ticket: *mut u64) -> c_int;
+    pub fn bpp_enqueue_done(ctx: *mut bpp_ctx, ticket: u64, done: *mut c_int) -> c_int;
+    pub fn bpp_enqueue_wait(ctx: *mut bpp_ctx, ticket: u64) -> c_int;
+    pub fn bpp_verdict_result(host_copy: *const bpp_device_verdict, out: *mut bpp_shard_result) -> c_int;
+    pub fn bpp_enqueue_stats(ctx: *mut bpp_ctx, out: *mut bpp_enqueue_stats) -> c_int;
     pub fn bpp_batcher_verify_action(b: *mut bpp_batcher, input: *const bpp_packed_batch, action: c_int, masks_out: *mut u8,
                                      mask_present: *mut u8, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
     pub fn bpp_batcher_set_limits(b: *mut bpp_batcher, max_calls: u32, max_proofs: u32) -> c_int;
