@@ -180,6 +180,21 @@ def build_verdict_harness(force=False):
     return VERDICT_SANITIZER_BIN
 
 
+REFILL_SANITIZER_BIN = os.path.join(HERE, "hosttest_refill_asan")
+
+
+def build_refill_harness(force=False):
+    """hosttest_refill.cpp (refill.h: the one-lane model of the kernels of bpp_batch_refill_enqueue, held to the device upload's
+    routines of ingest.h; verdict.h with a refill state) under ASan + UBSan: an executable, run by tests/test_refill_host.py."""
+    src = os.path.join(CSRC, "hosttest_refill.cpp")
+    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
+    if not force and not _stale(REFILL_SANITIZER_BIN, deps):
+        return REFILL_SANITIZER_BIN
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-fno-omit-frame-pointer", "-o", REFILL_SANITIZER_BIN, src], check=True, cwd=CSRC)
+    return REFILL_SANITIZER_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     build_hosttest(force="--force" in sys.argv)

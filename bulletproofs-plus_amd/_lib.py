@@ -86,6 +86,16 @@ class EnqueueStats(Structure):
     _fields_ = [(n, c_uint64) for n in ("calls", "groups", "host_waits", "layouts_in_call")]
 
 
+class DeviceRefill(Structure):
+    """bpp_device_refill: the record of bpp_batch_refill_enqueue, 16 bytes, as it lies in device memory"""
+    _fields_ = [("code", ctypes.c_int32), ("msg", c_uint32), ("index", c_uint32), ("flags", c_uint32)]
+
+
+class RefillStats(Structure):
+    """struct bpp_refill_stats: what the refills of a context came to"""
+    _fields_ = [(n, c_uint64) for n in ("calls", "first_calls", "host_waits")]
+
+
 class RuntimeInfo(Structure):
     """bpp_runtime_info: what the library sees of its runtime preconditions (hardware queues, contexts, the small-call gate)"""
     _fields_ = [("device", c_int), ("contexts", c_uint32), ("contexts_peak", c_uint32), ("hw_queues", c_uint32),
@@ -168,6 +178,9 @@ SYMBOLS = [
     ("bpp_enqueue_wait", c_int, [c_void_p, c_uint64]),
     ("bpp_verdict_result", c_int, [POINTER(DeviceVerdict), POINTER(ShardResult)]),
     ("bpp_enqueue_stats", c_int, [c_void_p, POINTER(EnqueueStats)]),
+    ("bpp_batch_refill_enqueue", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_void_p, POINTER(c_uint64)]),
+    ("bpp_refill_result", c_int, [POINTER(DeviceRefill), POINTER(ShardResult)]),
+    ("bpp_refill_stats", c_int, [c_void_p, POINTER(RefillStats)]),
     ("bpp_batcher_verify_action", c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_char_p, c_size_t]),
     ("bpp_batcher_set_limits", c_int, [c_void_p, c_uint32, c_uint32]),
     ("bpp_batcher_largest_pool", c_int, [c_void_p, POINTER(c_uint32), POINTER(c_uint32)]),

@@ -42,6 +42,7 @@
 #include "upload_host.h"
 #include "ingest.h"
 #include "verdict.h"
+#include "refill.h"
 
 using namespace bpp;
 
@@ -408,7 +409,22 @@ struct Batch {
   uint32_t enq_actions_G = 0, enq_actions_next = 0;
   uint64_t enq_slot_ticket[4] = {0, 0, 0, 0};
   uint64_t enq_last_ticket = 0;  // the batch's last enqueue (0: none): a layout change waits for it
+  // bpp_batch_refill_enqueue (refill.h).  refillable: made by bpp_batch_upload_packed_device on its device path, which records the
+  // shape a refill must keep.  refilled: the contents are the stream's -- the host copies of what depends on the bytes (desc[].flags,
+  // defer, any_defer, any_seed) describe the upload's contents and are not looked at any more; d_defer is written by the refill
+  // kernel alone.  refill_red: the kernel's reduction words, zero between refills; refill_state: the word k_verdict_finish reads.
+  bool refillable = false, refilled = false;
+  struct RefillShape {
+    uint64_t n_items = 0, proof_len = 0;
+    uint32_t m = 0, t0 = 0;
+    bool nonces = false, min_values = false, min_present = false;
+  } refill_shape;
+  DevBuf<uint32_t> refill_red;
+  DevBuf<unsigned long long> refill_state;
 };
+// what the blocking verify entry points, the sharded and phased forms and the traces answer for a refilled batch: they decide by the
+// host copies above, which describe other contents
+#define BPP_REFILLED_MSG "the batch was refilled on the stream (bpp_batch_refill_enqueue) and takes enqueued calls only: upload the arrays for a blocking call"
 
 // A destroyed batch leaves its device and pinned allocations to the next upload on the same context (a caller that
 // verifies fresh host buffers call after call would otherwise pay ~30 hipMalloc/hipFree pairs, 15-25 ms, per call).
@@ -634,6 +650,7 @@ struct bpp_ctx {
   std::vector<hipEvent_t> enq_events;
   uint64_t enq_next = 1;
   struct bpp_enqueue_stats enq_stats{};
+  struct bpp_refill_stats refill_stats{};  // bpp_batch_refill_enqueue: its tickets are the enqueue tickets
   std::shared_ptr<Pipeline> pipe;  // bpp_verify_submit_packed / bpp_verify_collect: lanes, tickets (built on first submit)
   std::mutex pipe_init_mu;
   uint32_t pipe_depth = 3;
@@ -2180,6 +2197,16 @@ int upload_packed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_packed_ba
     ingest_finish_plan(*in, shape, res, info, pl);  // throws the lowest-index construction finding
     ctx->ingest_stats.device_calls++;
     *batch = upload_device(ctx, Pp, params, pl, nullptr, nullptr, std::move(B));
+    // the shape a refill of this batch must keep (bpp_batch_refill_enqueue): everything the plan above was made from but the bytes
+    Batch &made = *ctx->batches[*batch];
+    made.refillable = true;
+    made.refill_shape.n_items = n_items;
+    made.refill_shape.proof_len = in->proof_len;
+    made.refill_shape.m = in->m;
+    made.refill_shape.t0 = res[BPP_ING_RES_T0] & 255u;
+    made.refill_shape.nonces = in->seed_nonces32 != nullptr;
+    made.refill_shape.min_values = in->min_values != nullptr;
+    made.refill_shape.min_present = in->min_present != nullptr;
     return BPP_OK;
   }
   BPP_CATCH(ctx, errbuf, errbuf_len)
@@ -3132,6 +3159,7 @@ int verify_chunked_locked(bpp_ctx *ctx, uint64_t batch, int action, size_t chunk
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle", errbuf, errbuf_len);
     if (action < 0 || action > 2) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "unknown verify action", errbuf, errbuf_len);
     Batch &b = *it->second;
+    if (b.refilled) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, BPP_REFILLED_MSG, errbuf, errbuf_len);
     if (states_out203 && b.ext_challenges)
       return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "no transcript states: the caller replayed PASS 1 of this batch", errbuf, errbuf_len);
     b.want_states = states_out203 != nullptr;
@@ -3163,6 +3191,7 @@ int verify_groups_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fir
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
     if (!group_first || !results || n_groups == 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
     Batch &b = *it->second;
+    if (b.refilled) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, BPP_REFILLED_MSG);
     std::vector<uint32_t> bounds(group_first, group_first + n_groups + 1);
     if (bounds.front() != 0 || bounds.back() != b.B) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "group boundaries must run from 0 to the batch size");
     for (size_t g = 0; g < n_groups; g++)
@@ -3308,7 +3337,7 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
           b.d_rounds_bad.alloc(b.B);
           HIP_CHECK(hipMemcpy(b.d_rounds_bad.p, b.rounds_bad.data(), b.B, hipMemcpyHostToDevice));
         }
-        if (b.any_defer) {
+        if (b.any_defer && !b.refilled) {  // (a refilled batch: d_defer is the refill kernel's, the host vector is the upload's)
           b.d_defer.alloc(b.B);
           HIP_CHECK(hipMemcpy(b.d_defer.p, b.defer.data(), b.B, hipMemcpyHostToDevice));
         }
@@ -3349,10 +3378,15 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
       any_masks = any_masks || action_of(g) != BPP_VERIFY_ONLY;
     }
     // the early-outs of verify_flow_once that depend on what the host knows alone
-    const bool deferred_only = b.any_defer && G == 1;  // (any_defer: some proof carries a deferred finding)
+    // A refilled batch (bpp_batch_refill_enqueue): what the host knows of promises and nonces describes the upload's contents, so
+    // those two decisions take the general branch -- everything runs and the verdict kernels resolve the precedence, as for G > 1;
+    // masks whenever the batch has a nonce buffer.  The degree finding and rounds_bad follow from the shape and stay as they are.
+    const bool any_defer = b.refilled ? b.refill_shape.t0 != P.t : b.any_defer;
+    const bool any_seed = b.refilled ? b.refill_shape.nonces : b.any_seed;
+    const bool deferred_only = any_defer && G == 1;  // (any_defer: some proof carries a deferred finding)
     const bool pass1_only = b.any_rounds_bad && G == 1;
     const bool want_msm = !deferred_only && !pass1_only && any_msm;
-    const bool want_masks = !deferred_only && !pass1_only && any_masks && b.any_seed;
+    const bool want_masks = !deferred_only && !pass1_only && any_masks && any_seed;
     uint32_t *zero_word = reinterpret_cast<uint32_t *>(b.enq_words.p);
     unsigned long long *keys = b.enq_words.p + 1;
     StageTimer tm(ctx, false);
@@ -3377,7 +3411,7 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
     hipLaunchKernelGGL(k_verdict_finish, dim3(G), dim3(64), 0, s, keys, want_msm ? b.msm.is_identity.p : (const uint32_t *)nullptr, actions_dev,
                        action_all, zero_word, zero_word + 1, b.group_first.p, G, b.d_desc.p,
                        want_masks ? (const uint4 *)b.masks.p : (const uint4 *)nullptr, (uint32_t)(P.t * 2), verdicts_dev, (uint4 *)masks_dev,
-                       mask_present_dev);
+                       mask_present_dev, b.refill_state.p ? (const unsigned long long *)b.refill_state.p : (const unsigned long long *)nullptr);
     HIP_CHECK(hipGetLastError());
     const uint64_t t = ctx->enq_next++;
     HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));
@@ -3385,6 +3419,96 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
     *ticket = t;
     es.calls++;
     es.groups += G;
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, nullptr, 0)
+}
+
+// ---- bpp_batch_refill_enqueue (refill.h): new contents of the same shape for a resident batch, on the stream, no wait.
+//
+// The list above verify_enqueue_locked, for a refill: it writes nothing the host owns and reads nothing the host writes -- its
+// arguments travel by value, its reduction words and the state word are device memory of the batch, kept clear by k_refill_finish.
+// An enqueue in flight on the batch is in front of it on the stream, side stream included: every enqueue ends with the main stream
+// waiting for ev_join; the next enqueue's side-stream decompression waits for an ev_fork recorded behind the refill.  The action slots
+// and the layout are the shape's and stay.
+int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in, bpp_device_refill *record_dev, uint64_t *ticket) {
+  try {
+    auto it = ctx->batches.find(batch);
+    if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
+    if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+    Batch &b = *it->second;
+    if (!b.refillable || b.ext_challenges || b.want_states)
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT,
+                  "the batch cannot be refilled: only a batch that bpp_batch_upload_packed_device packed on the device records its shape (not the "
+                  "item form, the host packed form, the staged fall-back, caller-side challenges or a batch that hands out states)");
+    const Batch::RefillShape &sh = b.refill_shape;
+    const struct {
+      const char *name;
+      bool same;
+    } shape[] = {{"n_items", (uint64_t)in->n_items == sh.n_items},
+                 {"m", in->m == sh.m},
+                 {"proof_len", (uint64_t)in->proof_len == sh.proof_len},
+                 {"seed_nonces32", (in->seed_nonces32 != nullptr) == sh.nonces},
+                 {"min_values", (in->min_values != nullptr) == sh.min_values},
+                 {"min_present", (in->min_present != nullptr) == sh.min_present}};
+    for (const auto &f : shape)
+      if (!f.same) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(f.name) + " differs from the batch's shape: a refill keeps the shape of the upload");
+    if (in->proof_stride < in->proof_len) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proof_stride is below proof_len");
+    if (in->transcript_state || in->transcript_label)
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "transcript_state / transcript_label must be null: a refilled batch keeps its transcript");
+    if (!in->proofs || !in->commitments32) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proofs / commitments32: null");
+    const struct {
+      const char *name;
+      const void *p;
+    } arrays[] = {{"proofs", in->proofs},           {"commitments32", in->commitments32}, {"min_values", in->min_values},
+                  {"min_present", in->min_present}, {"seed_nonces32", in->seed_nonces32}, {"seed_present", in->seed_present},
+                  {"record_dev", record_dev}};
+    for (const auto &a : arrays) {
+      if (!a.p) continue;
+      const int kind = device_pointer_kind(ctx->device, a.p);
+      if (kind != BPP_PTR_THIS_DEVICE)
+        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + ": not device memory of the context's device (pointer kind " + std::to_string(kind) + ")");
+    }
+    if ((uintptr_t)record_dev & 3u) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "record_dev: not 4-byte aligned");
+    Params &P = *b.params;
+    const size_t n = b.B;
+    // what the kernel writes, against what the upload allocated (the shape says they fit; a kernel is not launched on less)
+    if (b.bytes.n < n * sh.proof_len + n * (size_t)sh.m * 32 + BPP_BYTES_SLACK || b.minvals.n < n * (size_t)sh.m || (sh.nonces && b.seeds.n < n * 32) ||
+        b.d_desc.n < n || b.status0.n < n || b.status.n < n || b.masks.n < n * (size_t)P.t * 32 || b.sum_m != n * sh.m)
+      throw EngineError{BPP_ERR_ENGINE, "refill: the batch's buffers do not fit its recorded shape"};
+    hipStream_t s = ctx->stream;
+    struct bpp_refill_stats &rs = ctx->refill_stats;
+    if (!b.refill_red.p) {  // the first refill of this batch: its few device words, and d_defer where no enqueue made it
+      b.refill_red.alloc(BPP_REFILL_RED_WORDS);
+      b.refill_state.alloc(1);
+      b.d_defer.alloc(n);
+      HIP_CHECK(hipMemsetAsync(b.refill_red.p, 0, BPP_REFILL_RED_WORDS * 4, s));
+      HIP_CHECK(hipMemsetAsync(b.refill_state.p, 0, 8, s));
+      rs.first_calls++;
+    }
+    if (ctx->enq_events.empty()) {  // (the context's first ticket)
+      ctx->enq_events.resize(64);
+      for (auto &e : ctx->enq_events) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    const ParamShape shape_p{P.n_bits, P.m_max, P.t};
+    const RefillPacked r = refill_args(*in, shape_p, (uint8_t)sh.t0, b.bytes.p, b.minvals.p, b.seeds.p, b.d_defer.p, b.d_desc.p, b.status0.p,
+                                       b.status.p, reinterpret_cast<uint32_t *>(b.masks.p), b.refill_red.p);
+    b.refilled = true;  // from here on the contents are the stream's, whatever becomes of the launches
+    b.seeds_dirty = sh.nonces;
+    hipLaunchKernelGGL(k_refill_packed, dim3((uint32_t)cdiv((uint32_t)n, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, r);
+    hipLaunchKernelGGL(k_refill_finish, dim3(1), dim3(64), 0, s, b.refill_red.p, b.refill_state.p, record_dev);
+    // the statements' commitments, decoded as at the end of upload_device: COMMIT_FAIL goes to status0[] and status[]
+    hipLaunchKernelGGL(k_decompress, dim3(cdiv(b.sum_m, 64)), dim3(64), 0, s, b.bytes.p, b.src_off.p, b.owner.p, b.idx_commit.p, b.sum_m,
+                       b.dynpts.p, b.status0.p, (uint32_t *)nullptr, b.status.p);
+    HIP_CHECK(hipGetLastError());
+    b.status_clean = true;
+    b.masks_dirty = false;  // (the kernel wiped every row)
+    b.have_trace = b.phase1_done = false;
+    const uint64_t t = ctx->enq_next++;
+    HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));
+    b.enq_last_ticket = t;
+    if (ticket) *ticket = t;
+    rs.calls++;
     return BPP_OK;
   }
   BPP_CATCH(ctx, nullptr, 0)
@@ -3457,10 +3581,39 @@ int bpp_enqueue_wait(bpp_ctx *ctx, uint64_t ticket) {
 int bpp_verdict_result(const bpp_device_verdict *host_copy, bpp_shard_result *out) {
   if (!host_copy || !out || !(host_copy->flags & BPP_VERDICT_WRITTEN)) return BPP_ERR_INVALID_ARGUMENT;
   memset(out, 0, sizeof(*out));
-  if (host_copy->flags & BPP_VERDICT_REDRAW)
+  if (host_copy->flags & BPP_VERDICT_REFILL)
+    shard_result_set(*out, host_copy->code, (int)host_copy->tier, -1, host_copy->index,
+                     "the batch's last refill did not take: nothing of this verification is claimed, see the refill record (bpp_refill_result)");
+  else if (host_copy->flags & BPP_VERDICT_REDRAW)
     shard_result_set(*out, BPP_OK, BPP_TIER_NONE, -1, 0, "a device weight came out zero: nothing is claimed, run a blocking call");
   else
     shard_result_set(*out, host_copy->code, (int)host_copy->tier, -1, host_copy->index, verdict_message(host_copy->tier, host_copy->code));
+  return BPP_OK;
+}
+
+// (no gate, as bpp_verify_enqueue)
+int bpp_batch_refill_enqueue(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev, bpp_device_refill *record_dev, uint64_t *ticket) {
+  BPP_ENTRY(ctx);
+  return batch_refill_locked(ctx, batch, in_dev, record_dev, ticket);
+}
+
+int bpp_refill_result(const bpp_device_refill *host_copy, bpp_shard_result *out) {
+  if (!host_copy || !out || !(host_copy->flags & BPP_REFILL_WRITTEN)) return BPP_ERR_INVALID_ARGUMENT;
+  memset(out, 0, sizeof(*out));
+  if (host_copy->flags & BPP_REFILL_FALLBACK)
+    shard_result_set(*out, BPP_OK, BPP_TIER_NONE, -1, 0,
+                     "some proof's first byte is not the batch's: nothing is claimed, upload the arrays with a blocking call");
+  else if (host_copy->flags & BPP_REFILL_FINDING)
+    shard_result_set(*out, host_copy->code, BPP_TIER_CONSTRUCTION, -1, host_copy->index, ingest_message(host_copy->msg));
+  else
+    shard_result_set(*out, BPP_OK, BPP_TIER_NONE, -1, 0, "");
+  return BPP_OK;
+}
+
+int bpp_refill_stats(bpp_ctx *ctx, struct bpp_refill_stats *out) {
+  BPP_ENTRY(ctx);
+  if (!out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+  *out = ctx->refill_stats;
   return BPP_OK;
 }
 
@@ -3821,6 +3974,7 @@ int bpp_verify_phase1(bpp_ctx *ctx, uint64_t batch, uint8_t *rng_out32, char *er
     auto it = ctx->batches.find(batch);
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle", errbuf, errbuf_len);
     Batch &b = *it->second;
+    if (b.refilled) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, BPP_REFILLED_MSG, errbuf, errbuf_len);
     StageTimer tm(ctx);
     layout_groups(ctx, b, 0);
     if (b.any_defer) check_deferred(b.defer, 0, b.B);
@@ -3843,6 +3997,7 @@ int bpp_verify_phase2(bpp_ctx *ctx, uint64_t batch, const uint8_t *weights32, ui
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle", errbuf, errbuf_len);
     if (!weights32 || !accumulator128) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
     Batch &b = *it->second;
+    if (b.refilled) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, BPP_REFILLED_MSG, errbuf, errbuf_len);
     if (!b.phase1_done) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "bpp_verify_phase1 must succeed first", errbuf, errbuf_len);
     for (uint32_t p = 0; p < b.B; p++)
       if (!sc_is_canonical(weights32 + 32 * (size_t)p))
@@ -3903,6 +4058,7 @@ int bpp_batch_trace(bpp_ctx *ctx, uint64_t batch, int what, uint8_t *out, size_t
     auto it = ctx->batches.find(batch);
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
     Batch &b = *it->second;
+    if (b.refilled) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, BPP_REFILLED_MSG);
     hipStream_t s = ctx->stream;
     size_t need = 0;
     const void *src = nullptr;

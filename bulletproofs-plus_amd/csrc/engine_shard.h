@@ -582,6 +582,7 @@ int bpp_verify_sharded_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const uint64_t
         if (it == ctxs[i]->batches.end()) throw EngineError{BPP_ERR_BAD_HANDLE, "unknown batch handle"};
         Batch &b = *it->second;
         if (b.B != counts[rank]) throw EngineError{BPP_ERR_ENGINE, "counts[rank] differs from the resident shard's size"};
+        if (b.refilled) throw EngineError{BPP_ERR_ENGINE, BPP_REFILLED_MSG};
         B[i] = &b;
         StageTimer tm(ctxs[i]);
         hipStream_t s = ctxs[i]->stream;
@@ -735,6 +736,7 @@ int bpp_verify_sharded_groups_wave(bpp_comm *comm, bpp_ctx *const *ctxs, const u
         if (it == ctx->batches.end()) throw EngineError{BPP_ERR_BAD_HANDLE, "unknown batch handle"};
         Batch &b = *it->second;
         if ((uint64_t)b.B != (uint64_t)G * c) throw EngineError{BPP_ERR_ENGINE, "the resident batch does not hold n_groups x counts[rank] proofs"};
+        if (b.refilled) throw EngineError{BPP_ERR_ENGINE, BPP_REFILLED_MSG};
         B[i] = &b;
         StageTimer tm(ctx);
         ensure_ev_rng(ctx);

@@ -1,0 +1,187 @@
+// Device side of bpp_batch_refill_enqueue: a resident batch made by bpp_batch_upload_packed_device takes new contents of the SAME
+// shape from arrays in device memory, on the stream, with no host involvement.  Everything the host decided at upload follows from
+// the shape (item count, aggregation factor, proof length, first byte t0, which optional arrays exist): layout, slots, rounds_bad,
+// the degree finding, the MSM plan.  What follows from the bytes is found here, per item, by the one-item routines of ingest.h, and
+// STAYS on the device: the construction finding of lowest index and "some first byte is not t0" are reduced into two words of the
+// batch, turned into the refill record and the batch's refill-state word by k_refill_finish, and reach the verdict records through
+// k_verdict_finish (verdict.h).
+//
+// HARD REQUIREMENT -- no verification kernel sees bytes the blocking upload would have stopped.  The host does not know what a
+// refill found, so the verification kernels run on whatever it left.  Several of them assume what the upload's checks established
+// (canonical scalars above all: a non-canonical one must never reach the MSM recode).  So an item with a construction finding, or
+// with a foreign first byte, is NOT copied: its proof slot is written as t0 followed by zero bytes, its commitments and promises
+// as zeros, its nonce as zeros with the nonce flag clear.  That is a proof which passes ingest_check_item (the harness holds it to
+// that) and which every kernel already handles as hostile input: identity encodings give a PASS-1 finding.  The decision is made by
+// the item's first lane and BROADCAST to the item's lanes before any lane moves a byte, so that copying depends on it.
+//
+// Shared by the kernels, by the engine's driver (engine.hip: batch_refill_locked) and by the sanitizer harness (hosttest_refill.cpp),
+// which runs the one-lane model refill_run_host against ingest_run_host + ingest_finish_plan.
+#pragma once
+#include "ingest.h"
+#include "verdict.h"
+
+namespace bpp {
+
+// words the kernel reduces into (device memory of the batch; zero before the run, left zero by k_refill_finish)
+#define BPP_REFILL_RED_FINDING 0  // ingest_key of the lowest-index finding under atomicMax; 0 = none
+#define BPP_REFILL_RED_DIFFERS 1  // some proof's first byte is not t0
+#define BPP_REFILL_RED_WORDS 2
+
+// bits of the per-item decision the first lane broadcasts
+#define BPP_REFILL_ITEM_TAKE 1u     // the item is copied; clear: its slot is sanitised
+#define BPP_REFILL_ITEM_FOREIGN 2u  // its first byte is not t0
+
+struct RefillPacked {
+  IngestPacked in;        // the caller's arrays and the batch's bytes / minvals / seeds (info and result are not used; tr_bad = 0)
+  uint32_t t0;            // the batch's first byte
+  uint32_t degree_bit;    // BPP_DEFER_DEGREE when t0 is not the parameters' extension degree: uniform over the batch
+  uint8_t *defer;         // n: the deferred bits k_verdict_scan reads
+  ProofDesc *desc;        // n: only flags is written (bit 0: seed nonce present)
+  uint32_t *status0, *status;  // n each: cleared here, COMMIT_FAIL is written by the decompression that follows
+  uint32_t *masks;        // n rows of mask_row_words words: the engine's recovered masks of the old contents, wiped
+  uint32_t mask_row_words;
+  uint32_t *red;          // BPP_REFILL_RED_WORDS
+};
+
+// the decision for item i, by its first lane: BPP_REFILL_ITEM_* bits, and the item's key for the reduction (0: no finding)
+BPP_HD uint32_t refill_item_check(const RefillPacked &r, size_t i, uint32_t *key_out) {
+  const IngestPacked &a = r.in;
+  const uint8_t *p = a.proofs + i * (size_t)a.proof_stride;
+  const IngestFinding f = ingest_check_item(p, (size_t)a.proof_len, a.m, ingest_seed_present(a, i), false);
+  *key_out = f.msg ? ingest_key((uint32_t)i, f.msg) : 0u;
+  const bool foreign = (uint32_t)p[0] != r.t0;  // (proof_len >= 1: the batch exists)
+  return ((f.msg == BPP_ING_OK && !foreign) ? BPP_REFILL_ITEM_TAKE : 0u) | (foreign ? BPP_REFILL_ITEM_FOREIGN : 0u);
+}
+
+// the sanitised slot of item i: t0 and zeros, zero commitments, no promises, no nonce
+BPP_HD void refill_item_sanitise(const RefillPacked &r, size_t i, uint32_t lane, uint32_t lanes) {
+  const IngestPacked &a = r.in;
+  const size_t n = a.n_items, proof_bytes = n * (size_t)a.proof_len;
+  uint8_t *slot = a.bytes + i * (size_t)a.proof_len;
+  for (size_t k = lane; k < (size_t)a.proof_len; k += lanes) slot[k] = k == 0 ? (uint8_t)r.t0 : (uint8_t)0;
+  ingest_zero(a.bytes + proof_bytes + 32 * i * (size_t)a.m, 32 * (size_t)a.m, lane, lanes);
+  for (uint32_t j = lane; j < a.m; j += lanes) a.minvals[i * (size_t)a.m + j] = 0;
+  if (a.seeds) ingest_zero(a.seeds + 32 * i, 32, lane, lanes);
+}
+
+// what `lane` of the item's lanes moves, by the broadcast decision; returns this lane's share of the item's info bits
+BPP_HD uint32_t refill_item_arrays(const RefillPacked &r, size_t i, uint32_t decision, uint32_t lane, uint32_t lanes) {
+  uint32_t bits = 0;
+  if (decision & BPP_REFILL_ITEM_TAKE) bits = ingest_item_arrays(r.in, i, lane, lanes);
+  else refill_item_sanitise(r, i, lane, lanes);
+  // nothing of the old contents outlives the refill: the status words, the engine's masks of this item
+  if (lane == 0) r.status0[i] = r.status[i] = 0;
+  uint32_t *row = r.masks + i * (size_t)r.mask_row_words;
+  for (uint32_t k = lane; k < r.mask_row_words; k += lanes) row[k] = 0;
+  return bits;
+}
+
+// the item's folded info bits to where the verification reads them, by the item's first lane
+BPP_HD void refill_item_finish(const RefillPacked &r, size_t i, uint32_t bits) {
+  r.defer[i] = (uint8_t)(r.degree_bit | (bits & BPP_ING_INFO_PROMISE));
+  r.desc[i].flags = bits & BPP_ING_INFO_SEED;
+}
+
+// the record of a refill from its two reduction words: the fall-back comes before any finding, as bpp_batch_upload_packed_device
+// decides "differs" before ingest_finish_plan throws
+BPP_HD bpp_device_refill refill_record(uint32_t finding_word, uint32_t differs) {
+  bpp_device_refill rec;
+  rec.code = BPP_OK;
+  rec.msg = BPP_ING_OK;
+  rec.index = 0;
+  rec.flags = BPP_REFILL_WRITTEN;
+  if (differs) {
+    rec.flags |= BPP_REFILL_FALLBACK;
+  } else if (finding_word) {
+    const uint32_t key = 0xffffffffu - finding_word;
+    rec.flags |= BPP_REFILL_FINDING;
+    rec.msg = key & 255u;
+    rec.index = key >> 8;
+    rec.code = ingest_finding(rec.msg).code;
+  }
+  return rec;
+}
+
+#if defined(__HIPCC__)
+// k_refill_packed: the geometry of k_ingest_packed, BPP_INGEST_LANES lanes per item and BPP_INGEST_BLOCK per workgroup.  The item's
+// first lane runs ingest_check_item and compares the first byte with t0; the decision reaches the item's lanes by a shuffle of
+// width BPP_INGEST_LANES BEFORE any lane copies (the requirement in this file's header: an item the blocking upload would have
+// stopped is never copied, so no verification kernel sees a non-canonical scalar).  No lane leaves before the shuffles: lanes
+// beyond the last item carry a zero decision and move nothing.
+__global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_refill_packed(RefillPacked r) {
+  const size_t gid = (size_t)blockIdx.x * BPP_INGEST_BLOCK + threadIdx.x;
+  const size_t i = gid / BPP_INGEST_LANES;
+  const uint32_t lane = (uint32_t)(gid % BPP_INGEST_LANES);
+  const bool live = i < r.in.n_items;
+  uint32_t decision = 0, key = 0;
+  if (live && lane == 0) decision = refill_item_check(r, i, &key);
+  decision = (uint32_t)__shfl((int)decision, 0, (int)BPP_INGEST_LANES);
+  uint32_t bits = 0;
+  if (live) bits = refill_item_arrays(r, i, decision, lane, BPP_INGEST_LANES);
+  for (uint32_t o = BPP_INGEST_LANES / 2; o; o >>= 1) bits |= (uint32_t)__shfl_xor((int)bits, (int)o, (int)BPP_INGEST_LANES);
+  if (live && lane == 0) {
+    refill_item_finish(r, i, bits);
+    if (key) atomicMax(&r.red[BPP_REFILL_RED_FINDING], key);
+  }
+  const bool d = __ballot((decision & BPP_REFILL_ITEM_FOREIGN) != 0) != 0;
+  if ((threadIdx.x & 63u) == 0 && d) atomicOr(&r.red[BPP_REFILL_RED_DIFFERS], 1u);
+}
+
+// k_refill_finish: one wavefront behind k_refill_packed.  Its first lane turns the reduction words into the record at `record`
+// (may be null) and into the batch's refill-state word, and leaves the reduction words clear for the next refill, so that no
+// memset is ever enqueued between two refills.
+__global__ void __launch_bounds__(64) k_refill_finish(uint32_t *__restrict__ red, unsigned long long *__restrict__ state,
+                                                      bpp_device_refill *__restrict__ record) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const bpp_device_refill rec = refill_record(red[BPP_REFILL_RED_FINDING], red[BPP_REFILL_RED_DIFFERS]);
+  red[BPP_REFILL_RED_FINDING] = 0;
+  red[BPP_REFILL_RED_DIFFERS] = 0;
+  *state = refill_state_make(rec.flags, rec.code, rec.msg, rec.index);
+  if (record) {
+    record->code = rec.code;
+    record->msg = rec.msg;
+    record->index = rec.index;
+    record->flags = rec.flags;
+  }
+}
+#endif
+
+// ---- host side
+// the kernel's arguments from the caller's struct and the batch's buffers (every pointer an address in device memory)
+inline RefillPacked refill_args(const bpp_packed_batch &pk, const ParamShape &P, uint8_t t0, uint8_t *bytes, uint64_t *minvals, uint8_t *seeds,
+                                uint8_t *defer, ProofDesc *desc, uint32_t *status0, uint32_t *status, uint32_t *masks, uint32_t *red) {
+  RefillPacked r;
+  memset(&r, 0, sizeof(r));
+  bpp_packed_batch in = pk;
+  in.transcript_state = nullptr;  // the batch keeps its transcript
+  r.in = ingest_args(in, P, bytes, minvals, seeds, nullptr, nullptr);
+  r.t0 = t0;
+  r.degree_bit = t0 != P.t ? BPP_DEFER_DEGREE : 0u;
+  r.defer = defer;
+  r.desc = desc;
+  r.status0 = status0;
+  r.status = status;
+  r.masks = masks;
+  r.mask_row_words = P.t * 8;
+  r.red = red;
+  return r;
+}
+
+// the two kernels on the host, one lane per item, reduced as the kernels reduce: the model hosttest_refill.cpp holds to
+// ingest_run_host + ingest_finish_plan.  `red` is expected clear and is left clear.
+inline void refill_run_host(const RefillPacked &r, uint64_t *state, bpp_device_refill *record) {
+  for (size_t i = 0; i < r.in.n_items; i++) {
+    uint32_t key;
+    const uint32_t decision = refill_item_check(r, i, &key);
+    const uint32_t bits = refill_item_arrays(r, i, decision, 0, 1);
+    refill_item_finish(r, i, bits);
+    if (key > r.red[BPP_REFILL_RED_FINDING]) r.red[BPP_REFILL_RED_FINDING] = key;
+    if (decision & BPP_REFILL_ITEM_FOREIGN) r.red[BPP_REFILL_RED_DIFFERS] |= 1u;
+  }
+  const bpp_device_refill rec = refill_record(r.red[BPP_REFILL_RED_FINDING], r.red[BPP_REFILL_RED_DIFFERS]);
+  r.red[BPP_REFILL_RED_FINDING] = r.red[BPP_REFILL_RED_DIFFERS] = 0;
+  *state = refill_state_make(rec.flags, rec.code, rec.msg, rec.index);
+  if (record) *record = rec;
+}
+
+}  // namespace bpp

@@ -86,6 +86,31 @@ BPP_HD bpp_device_verdict verdict_finish(uint64_t key, bool want_msm, int action
   return v;
 }
 
+// ---- the refill-state word of a batch (refill.h: k_refill_finish writes it, bpp_batch_refill_enqueue owns it).  Zero: the batch's
+// last refill took, or it was never refilled.  Otherwise bits 0..7 hold the BPP_REFILL_* flags of the refill record, bits 8..15 the
+// message id, bits 16..23 the code as a signed byte, bits 32..63 the index inside the batch.
+BPP_HD uint64_t refill_state_make(uint32_t flags, int32_t code, uint32_t msg, uint32_t index) {
+  if (!(flags & (BPP_REFILL_FINDING | BPP_REFILL_FALLBACK))) return 0;
+  return (uint64_t)(flags & 255u) | ((uint64_t)(msg & 255u) << 8) | ((uint64_t)((uint32_t)code & 255u) << 16) | ((uint64_t)index << 32);
+}
+
+// verdict_finish with the refill-state word: a refill that did not take answers for every group of every enqueue until the next
+// refill -- nothing of the verification is claimed, whatever it found.  A zero word gives verdict_finish as it is.
+BPP_HD bpp_device_verdict verdict_finish(uint64_t key, bool want_msm, int action, bool is_identity, bool zero_weight, uint64_t refill_state) {
+  if (!(refill_state & (BPP_REFILL_FINDING | BPP_REFILL_FALLBACK))) return verdict_finish(key, want_msm, action, is_identity, zero_weight);
+  bpp_device_verdict v;
+  v.code = BPP_OK;
+  v.tier = BPP_TIER_NONE;
+  v.index = 0;
+  v.flags = BPP_VERDICT_WRITTEN | BPP_VERDICT_REFILL;
+  if (!(refill_state & BPP_REFILL_FALLBACK)) {  // (the fall-back comes first and claims nothing)
+    v.code = (int32_t)(int8_t)(uint8_t)(refill_state >> 16);
+    v.tier = BPP_TIER_CONSTRUCTION;
+    v.index = (uint32_t)(refill_state >> 32);
+  }
+  return v;
+}
+
 // the text the blocking calls return with a (tier, code) pair ("" for Ok and for pairs no check raises)
 inline const char *verdict_message(uint32_t tier, int32_t code) {
   switch (tier) {
@@ -169,12 +194,15 @@ __global__ void __launch_bounds__(BPP_VERDICT_BLOCK) k_verdict_scan(uint32_t *__
 // brings the count to G clears both words, so the next enqueue finds them as it expects them.
 //   is_identity == nullptr: the call ran no final MSM (want_msm = 0)
 //   masks == nullptr: the call recovered no masks (no group asked, or no item carries a seed nonce)
+//   refill_state == nullptr, or a zero word: the batch's contents are what its last upload or refill made them; otherwise every
+//     group gets the refill's record (verdict_finish above) and no masks
 __global__ void __launch_bounds__(64) k_verdict_finish(unsigned long long *__restrict__ keys, const uint32_t *__restrict__ is_identity,
                                                        const int *__restrict__ actions, int action_all, uint32_t *__restrict__ zero_word,
                                                        uint32_t *__restrict__ groups_done, const uint32_t *__restrict__ group_first,
                                                        uint32_t G, const ProofDesc *__restrict__ desc, const uint4 *__restrict__ masks,
                                                        uint32_t row_pieces, bpp_device_verdict *__restrict__ verdicts,
-                                                       uint4 *__restrict__ masks_out, uint8_t *__restrict__ mask_present) {
+                                                       uint4 *__restrict__ masks_out, uint8_t *__restrict__ mask_present,
+                                                       const unsigned long long *__restrict__ refill_state = nullptr) {
   const uint32_t g = blockIdx.x, lane = threadIdx.x;
   if (g >= G) return;
   int give = 0;
@@ -183,9 +211,10 @@ __global__ void __launch_bounds__(64) k_verdict_finish(unsigned long long *__res
     keys[g] = BPP_VERDICT_KEY_NONE;
     const int action = actions ? actions[g] : action_all;
     const bool zero = *zero_word != 0;
-    const bpp_device_verdict v = verdict_finish(key, is_identity != nullptr, action, is_identity ? is_identity[g] != 0 : true, zero);
+    const bpp_device_verdict v = verdict_finish(key, is_identity != nullptr, action, is_identity ? is_identity[g] != 0 : true, zero,
+                                                refill_state ? (uint64_t)*refill_state : 0ull);
     *reinterpret_cast<uint4 *>(&verdicts[g]) = make_uint4((uint32_t)v.code, v.tier, v.index, v.flags);
-    give = (masks != nullptr && v.tier == BPP_TIER_NONE && !(v.flags & BPP_VERDICT_REDRAW) && action != BPP_VERIFY_ONLY) ? 1 : 0;
+    give = (masks != nullptr && v.tier == BPP_TIER_NONE && !(v.flags & (BPP_VERDICT_REDRAW | BPP_VERDICT_REFILL)) && action != BPP_VERIFY_ONLY) ? 1 : 0;
     // every group has read the zero-weight word once the count reaches G: the last one clears both
     __threadfence();
     if (atomicAdd(groups_done, 1u) == G - 1) {

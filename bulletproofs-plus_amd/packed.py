@@ -706,8 +706,65 @@ class ResidentBatch(api.ResidentBatch):
         api._check(rc, self.engine.ctx)
         return Enqueued(self.engine, ticket.value, G, verdicts, masks, present)
 
+    def refill(self, inp, record=None):
+        """bpp_batch_refill_enqueue: new contents of the same shape for this batch (made with form="device") from the
+        DevicePackedInput `inp`, enqueued on the engine's stream; an enqueue() afterwards gives what it would give on a fresh upload
+        of those arrays.  Nothing is synchronised here: what wrote the arrays must be ordered before the engine's stream (an engine
+        made on torch's current stream has that by construction).  The batch keeps its transcript: inp's label and state are not
+        passed on.  `record`: an int32 [4] device tensor (code, message id, index, flags) or a raw address; None: allocated.  Returns a
+        Refilled.  A refilled batch takes enqueued calls only."""
+        import torch
+        if record is None:
+            record = torch.empty((4,), dtype=torch.int32, device=torch.device("cuda", int(self.engine.device)))
+        if hasattr(record, "data_ptr"):
+            if record.dtype != torch.int32 or tuple(record.shape) != (4,) or not record.is_contiguous():
+                raise api.ProofError(api.ProofErrorKind.InvalidArgument, "record: a contiguous int32 tensor of shape (4,) expected")
+            addr = ctypes.c_void_p(record.data_ptr())
+        else:
+            addr = ctypes.c_void_p(int(record))
+        st = _lib.PackedBatch.from_buffer_copy(inp.struct)
+        st.transcript_state, st.transcript_label, st.label_len = None, None, 0
+        ticket = c_uint64()
+        rc = self.engine.lib.bpp_batch_refill_enqueue(self.engine.ctx, self.handle, byref(st), addr, byref(ticket))
+        api._check(rc, self.engine.ctx)
+        self.input = inp  # (the arrays stay alive until the refill has run)
+        return Refilled(self.engine, ticket.value, record)
 
-VERDICT_WRITTEN, VERDICT_REDRAW = 1, 2
+
+VERDICT_WRITTEN, VERDICT_REDRAW, VERDICT_REFILL = 1, 2, 4
+REFILL_WRITTEN, REFILL_FINDING, REFILL_FALLBACK = 1, 2, 4
+
+
+class Refilled:
+    """What ResidentBatch.refill returns: `.record` (int32 [4]: code, message id, index, flags -- a device tensor, valid in stream
+    order behind the call) and the ticket: done() is one event query, wait() blocks until the refill has run, result() waits,
+    copies the record back and returns {"code", "tier", "index", "msg", "flags"} (bpp_refill_result: a finding has the blocking
+    upload's code, index and text under tier 1; a fall-back record claims nothing and says so)."""
+
+    def __init__(self, engine, ticket, record):
+        self.engine, self.ticket, self.record = engine, ticket, record
+
+    def done(self):
+        d = ctypes.c_int()
+        api._check(self.engine.lib.bpp_enqueue_done(self.engine.ctx, self.ticket, byref(d)), self.engine.ctx)
+        return bool(d.value)
+
+    def wait(self):
+        api._check(self.engine.lib.bpp_enqueue_wait(self.engine.ctx, self.ticket), self.engine.ctx)
+
+    def result(self):
+        self.wait()
+        host = np.ascontiguousarray(self.record.cpu().numpy())
+        r = _lib.ShardResult()
+        api._check(self.engine.lib.bpp_refill_result(host.ctypes.data_as(POINTER(_lib.DeviceRefill)), byref(r)), None)
+        return {"code": r.code, "tier": r.tier, "index": r.index, "msg": r.msg.decode(errors="replace"), "flags": int(host[3])}
+
+
+def refill_stats(engine):
+    """bpp_refill_stats as a dict: calls, first_calls, host_waits"""
+    s = _lib.RefillStats()
+    api._check(engine.lib.bpp_refill_stats(engine.ctx, byref(s)), engine.ctx)
+    return {n: int(getattr(s, n)) for n, _ in _lib.RefillStats._fields_}
 
 
 class Enqueued:

@@ -525,6 +525,59 @@ struct bpp_enqueue_stats {
 };
 int bpp_enqueue_stats(bpp_ctx *ctx, struct bpp_enqueue_stats *out);
 
+/* ---- refill a resident batch from device arrays on the stream ----
+ * bpp_batch_refill_enqueue replaces the CONTENTS of a resident batch with the packed batch `in_dev` -- the six array fields are
+ * addresses in the memory of the context's device, as for bpp_batch_upload_packed_device -- and keeps its SHAPE: item count,
+ * aggregation factor, proof length, first byte of the proofs, whether seed_nonces32 was given, whether min_values and min_present
+ * were given.  It ENQUEUES on the context's stream and returns.  A bpp_verify_enqueue on the batch afterwards gives, group for
+ * group, exactly what it would give on a fresh bpp_batch_upload_packed_device of the same arrays: byte-identical records, masks
+ * and mask_present.  Together the two calls are a steady state with no host round trip for a producer that writes proofs into
+ * device buffers and a consumer that reads verdicts on the same stream.
+ * ORDERING: the stream's.  The arrays must be complete on, or ordered before, the context's stream and stay readable until the
+ * refill has run; an earlier enqueue of the batch still in flight is ordered before the refill.
+ * WHICH BATCHES: one made by bpp_batch_upload_packed_device that did not take the staged fall-back.  A batch of any other origin
+ * (item form, host packed form, caller-side challenges) is refused.
+ * REFUSED, before anything is launched (BPP_ERR_INVALID_ARGUMENT, the reason in bpp_ctx_last_error; an unknown batch is
+ * BPP_ERR_BAD_HANDLE): a shape field of `in_dev` that differs from the batch's (the field is named); proof_stride < proof_len; a
+ * non-null transcript_state or transcript_label (the batch keeps its transcript); a non-null array or record_dev that is not
+ * BPP_PTR_THIS_DEVICE memory (the field is named).
+ * FINDINGS STAY ON THE DEVICE: where the blocking upload fails with the lowest-index construction finding, the refill writes
+ * {code, message id, index} with BPP_REFILL_FINDING into record_dev and into a word of the batch.  Every verdict record of every
+ * later enqueue on that batch, until the next refill, then carries BPP_VERDICT_WRITTEN | BPP_VERDICT_REFILL, the refill's code,
+ * tier BPP_TIER_CONSTRUCTION, the index inside the BATCH, and no masks.  A proof whose first byte is not the batch's sets
+ * BPP_REFILL_FALLBACK (it comes before any finding, as in the blocking upload, which stages such a batch and takes the host path):
+ * the refill cannot plan again on the device, so nothing is claimed -- code 0, tier 0 under BPP_VERDICT_REFILL -- and the caller
+ * uploads those arrays with a blocking call.  An item with a finding or a foreign first byte is NOT copied: its slot holds the
+ * batch's first byte and zeros, no nonce, no promises, zero commitments, so that no verification kernel ever sees bytes the
+ * blocking upload would have stopped.
+ * STEADY STATE: the call allocates nothing, copies nothing to the host and waits for nothing (host_waits stays 0).  The first
+ * refill of a batch allocates its few device words (first_calls).  bpp_verify_enqueue behind a refill plans nothing again when its
+ * layout is the current one, and takes its general branch where it would otherwise decide by what the host knew of the old
+ * contents.
+ * A REFILLED BATCH IS STREAM-OWNED: the blocking verify entry points, the sharded and phased forms and bpp_batch_trace refuse it
+ * (upload the arrays for a blocking call); bpp_batch_destroy, bpp_batch_shape, bpp_batch_prepare and bpp_batch_secret_bytes work.
+ * SECRETS: the old nonces are overwritten by the new ones or by zeros, and the engine's mask rows of the batch are wiped.
+ * TICKETS are those of bpp_verify_enqueue: bpp_enqueue_done and bpp_enqueue_wait take them. */
+typedef struct {
+  int32_t code;   /* ProofError kind of the finding (BPP_ERR_ENGINE for an internal one), 0 without one */
+  uint32_t msg;   /* message id of the finding; bpp_refill_result gives the text */
+  uint32_t index; /* the item, counted inside the batch */
+  uint32_t flags;
+} bpp_device_refill; /* 16 bytes */
+#define BPP_REFILL_WRITTEN 1u  /* always set by the call */
+#define BPP_REFILL_FINDING 2u  /* code / msg / index: the lowest-index construction finding, as the blocking upload reports it */
+#define BPP_REFILL_FALLBACK 4u /* some proof's first byte is not the batch's: nothing claimed, upload with a blocking call */
+#define BPP_VERDICT_REFILL 4u  /* in bpp_device_verdict.flags: the batch's last refill did not take; see its refill record */
+int bpp_batch_refill_enqueue(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev, bpp_device_refill *record_dev /* may be NULL */,
+                             uint64_t *ticket /* may be NULL */);
+/* code, index and message text of a record copied to the host (tier BPP_TIER_CONSTRUCTION for a finding, rank = -1); a fall-back
+ * record comes back as code 0 / tier 0 with a message that says so.  BPP_ERR_INVALID_ARGUMENT for a record the call never wrote. */
+int bpp_refill_result(const bpp_device_refill *host_copy, bpp_shard_result *out);
+struct bpp_refill_stats {
+  uint64_t calls, first_calls, host_waits;
+};
+int bpp_refill_stats(bpp_ctx *ctx, struct bpp_refill_stats *out);
+
 /* bpp_batcher: many host threads, each with ONE reference batch per call.  Separate small calls stop at about 5 000 calls per
  * second whatever the number of callers (a small call is a chain of latency-bound kernels and the chip runs about six of those
  * side by side); the batcher pools the calls that are waiting into grouped engine calls (bpp_verify_resident_groups) on

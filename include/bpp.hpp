@@ -171,6 +171,23 @@ class Engine {
           bpp_ctx_last_error(ctx_));
     return t;
   }
+  // New contents of the same shape for a resident batch made by upload_packed_device, from arrays in device memory, enqueued on the
+  // engine's stream (bpp_batch_refill_enqueue): a verify_enqueue afterwards gives what it would give on a fresh upload of those
+  // arrays.  record_dev (may be null) receives the 16-byte refill record in stream order; the ticket is an enqueue ticket.
+  EnqueueTicket batch_refill_enqueue(uint64_t batch, const bpp_packed_batch &in_dev, bpp_device_refill *record_dev = nullptr) {
+    EnqueueTicket t;
+    t.ctx_ = ctx_;
+    // (the call first, the text afterwards: the order in which arguments are evaluated is not specified, and the call replaces the text)
+    const int rc = bpp_batch_refill_enqueue(ctx_, batch, &in_dev, record_dev, &t.id);
+    check(rc, bpp_ctx_last_error(ctx_));
+    return t;
+  }
+  struct bpp_refill_stats refill_stats() const {
+    struct bpp_refill_stats s{};
+    const int rc = ::bpp_refill_stats(ctx_, &s);
+    check(rc, bpp_ctx_last_error(ctx_));
+    return s;
+  }
   struct bpp_enqueue_stats enqueue_stats() const {
     struct bpp_enqueue_stats s{};
     check(::bpp_enqueue_stats(ctx_, &s), bpp_ctx_last_error(ctx_));

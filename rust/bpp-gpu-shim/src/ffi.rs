@@ -221,6 +221,29 @@ pub struct bpp_device_verdict {
 }
 pub const BPP_VERDICT_WRITTEN: u32 = 1;
 pub const BPP_VERDICT_REDRAW: u32 = 2;
+pub const BPP_VERDICT_REFILL: u32 = 4;
+
+/// `bpp_device_refill`: the record of `bpp_batch_refill_enqueue`, 16 bytes, as it lies in device memory
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_device_refill {
+    pub code: i32,
+    pub msg: u32,
+    pub index: u32,
+    pub flags: u32,
+}
+pub const BPP_REFILL_WRITTEN: u32 = 1;
+pub const BPP_REFILL_FINDING: u32 = 2;
+pub const BPP_REFILL_FALLBACK: u32 = 4;
+
+/// `struct bpp_refill_stats`: what the refills (`bpp_batch_refill_enqueue`) of a context came to
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_refill_stats {
+    pub calls: u64,
+    pub first_calls: u64,
+    pub host_waits: u64,
+}
 
 /// `struct bpp_enqueue_stats`: what the enqueued verifications (`bpp_verify_enqueue`) of a context came to
 #[repr(C)]
@@ -330,6 +353,11 @@ extern "C" {
     pub fn bpp_enqueue_wait(ctx: *mut bpp_ctx, ticket: u64) -> c_int;
     pub fn bpp_verdict_result(host_copy: *const bpp_device_verdict, out: *mut bpp_shard_result) -> c_int;
     pub fn bpp_enqueue_stats(ctx: *mut bpp_ctx, out: *mut bpp_enqueue_stats) -> c_int;
+    // new contents of the same shape for a resident batch, from device arrays, on the stream (tickets: those of bpp_verify_enqueue)
+    pub fn bpp_batch_refill_enqueue(ctx: *mut bpp_ctx, batch: u64, in_dev: *const bpp_packed_batch, record_dev: *mut bpp_device_refill,
+                                    ticket: *mut u64) -> c_int;
+    pub fn bpp_refill_result(host_copy: *const bpp_device_refill, out: *mut bpp_shard_result) -> c_int;
+    pub fn bpp_refill_stats(ctx: *mut bpp_ctx, out: *mut bpp_refill_stats) -> c_int;
     pub fn bpp_batcher_verify_action(b: *mut bpp_batcher, input: *const bpp_packed_batch, action: c_int, masks_out: *mut u8,
                                      mask_present: *mut u8, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
     pub fn bpp_batcher_set_limits(b: *mut bpp_batcher, max_calls: u32, max_proofs: u32) -> c_int;
