@@ -20,8 +20,12 @@
 //   * k_chain_finish: 64 bytes -> Scalar::from_bytes_mod_order_wide -> canonical 32 bytes, one lane per proof; a zero weight
 //     (probability 2^-252) cannot be redrawn without re-running the chain: it raises a flag and the call falls back to the
 //     host chain, which redraws as the reference does.
+//   * a batch refilled with a live count (refill.h) hands both kernels its count word: a group's chain then runs over the group's
+//     live proofs alone -- the reference's chain of the batch cut short, the staging loop and the one-store fast path work for
+//     any number of proofs -- and a dead slot gets weight zero, which makes every scalar of that proof zero in PASS 2.
 #pragma once
 #include "scalar.h"
+#include "verdict.h"  // the live routines
 #include "wkeccak.h"
 #include "wstrobe.h"
 
@@ -90,13 +94,19 @@ BPP_HD constexpr uint64_t chain_word_of(uint32_t w, uint32_t at, const uint8_t *
 // t0: the transcript after Transcript::new(b"Bulletproofs+ verifier weights") (25 state words, pos, pos_begin; host-made).
 // wide[p][16]: the 64 PRF bytes of proof p's draw as the interleaved halves of state words 0..7 ([word][half]).
 __global__ void __launch_bounds__(64) k_weight_chain(const uint8_t *__restrict__ rng, const uint32_t *__restrict__ group_first, uint32_t G,
-                                                     const Strobe *__restrict__ t0, uint32_t *__restrict__ wide) {
+                                                     const Strobe *__restrict__ t0, uint32_t *__restrict__ wide,
+                                                     const uint32_t *__restrict__ live = nullptr) {
   const uint32_t g = blockIdx.x, lane = threadIdx.x;
   if (g >= G) return;
+  // live (null: every proof): the batch's live count.  The group's verify() call runs over its live proofs alone, so the chain
+  // absorbs and draws n = min(p1, live) - p0 of them: the reference's chain of a batch cut short.  A group without a live proof
+  // leaves here, as one wavefront, before anything is synchronised, and never touches `wide`.
+  const uint32_t p0 = group_first[g];
+  const uint32_t n = verdict_group_live(p0, group_first[g + 1], live ? *live : BPP_VERDICT_ALL_LIVE);
+  if (n == 0) return;
   __shared__ ChainLds L;
   const WkLanes W = wk_lanes(L.img);
   const WkRc R = wk_rc(W);
-  const uint32_t p0 = group_first[g], n = group_first[g + 1] - p0;
   if (lane < 26) L.blk[lane] = 0;
   ChainSponge s;
   s.a = W.word < 25 ? wk_half(t0->st[W.word], W.half) : 0u;
@@ -167,9 +177,15 @@ __global__ void __launch_bounds__(64) k_weight_chain(const uint8_t *__restrict__
 // wide -> weights: Scalar::from_bytes_mod_order_wide of every draw, canonical bytes out; *zero_flag = 1 if any weight is zero
 // (test_zero: proof index + 1 whose weight is REPORTED as zero, for the tests of the fall-back; 0 = none)
 __global__ void __launch_bounds__(64) k_chain_finish(const uint32_t *__restrict__ wide, uint32_t B, uint8_t *__restrict__ weights,
-                                                     uint32_t *__restrict__ zero_flag, uint32_t test_zero) {
+                                                     uint32_t *__restrict__ zero_flag, uint32_t test_zero,
+                                                     const uint32_t *__restrict__ live = nullptr) {
   const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= B) return;
+  if (live && !verdict_item_live(p, *live)) {  // a dead slot: weight zero, no flag; the chain never wrote its `wide` row
+    uint4 *dead = reinterpret_cast<uint4 *>(weights + (size_t)p * 32);
+    dead[0] = dead[1] = make_uint4(0, 0, 0, 0);
+    return;
+  }
   uint32_t w[16];
   const uint4 *src = reinterpret_cast<const uint4 *>(wide + (size_t)p * 16);
 #pragma unroll

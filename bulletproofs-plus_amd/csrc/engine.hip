@@ -421,6 +421,13 @@ struct Batch {
   } refill_shape;
   DevBuf<uint32_t> refill_red;
   DevBuf<unsigned long long> refill_state;
+  // bpp_batch_refill_enqueue_count: the batch's own live count, allocated with the words above and written by k_refill_finish.
+  // has_live: some refill of the batch took a count -- from then on every refill writes the word (N without a count) and the
+  // enqueue driver hands it to the chain and verdict kernels; before that they get a null pointer and compute what they always did.
+  DevBuf<uint32_t> refill_live;
+  bool has_live = false;
+  const uint32_t *live_word() const { return has_live ? (const uint32_t *)refill_live.p : (const uint32_t *)nullptr; }
+  bool enq_weights = false;  // b.weights holds the weights of the batch's last enqueue (bpp_enqueue_weights)
 };
 // what the blocking verify entry points, the sharded and phased forms and the traces answer for a refilled batch: they decide by the
 // host copies above, which describe other contents
@@ -2338,9 +2345,10 @@ void enqueue_device_chain(bpp_ctx *ctx, Batch &b, hipStream_t st, uint32_t *zero
   b.chain_wide.alloc((size_t)b.B * 16);
   if (!zero_word) ctx->h_chain_zero[0] = 0;
   const uint32_t test_zero = ctx->opt.chain_test_zero > 0 ? (uint32_t)ctx->opt.chain_test_zero : 0u;
-  hipLaunchKernelGGL(k_weight_chain, dim3(b.G), dim3(64), 0, st, b.rng_out.p, b.group_first.p, b.G, ctx->d_chain_t0.p, b.chain_wide.p);
+  hipLaunchKernelGGL(k_weight_chain, dim3(b.G), dim3(64), 0, st, b.rng_out.p, b.group_first.p, b.G, ctx->d_chain_t0.p, b.chain_wide.p,
+                     b.live_word());  // (non-null only for a batch refilled with a count, which takes enqueued calls alone)
   hipLaunchKernelGGL(k_chain_finish, dim3(cdiv(b.B, 64)), dim3(64), 0, st, b.chain_wide.p, b.B, b.weights.p,
-                     zero_word ? zero_word : ctx->h_chain_zero.dev(), test_zero);
+                     zero_word ? zero_word : ctx->h_chain_zero.dev(), test_zero, b.live_word());
   ctx->device_chain_calls++;
 }
 
@@ -2353,6 +2361,7 @@ void enqueue_phase1(bpp_ctx *ctx, Batch &b, StageTimer &tm, bool pass1_only, uin
   // does not wait, with or without a chain
   const bool fetch_rng = rng_dev_dst == nullptr && !dev_chain && !chain_zero_word;
   b.dev_chain_pending = false;
+  b.enq_weights = false;  // (verify_enqueue_locked sets it behind its own call)
   Params &P = *b.params;
   hipStream_t s = ctx->stream;
   if (!pass1_only) plan_lanes(ctx, b);  // (an option may have changed since the layout was built: k_scalars_shared writes what PASS 2 will read)
@@ -3390,10 +3399,14 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
     uint32_t *zero_word = reinterpret_cast<uint32_t *>(b.enq_words.p);
     unsigned long long *keys = b.enq_words.p + 1;
     StageTimer tm(ctx, false);
+    // A live count (bpp_batch_refill_enqueue_count) is the device's alone: nothing here depends on it.  The chains and the two
+    // verdict kernels read the batch's word; every other kernel runs over all slots, dead ones with weight zero.
+    b.enq_weights = false;
     if (deferred_only) {
       if (!b.status_clean) HIP_CHECK(hipMemcpyAsync(b.status.p, b.status0.p, (size_t)b.B * 4, hipMemcpyDeviceToDevice, s));
     } else {
       enqueue_phase1(ctx, b, tm, !want_msm, nullptr, 0, 0, want_msm, zero_word);
+      b.enq_weights = want_msm;
       if (want_masks) {
         hipLaunchKernelGGL(k_masks, dim3(cdiv(b.B, 64)), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.chal.p, b.seeds.p, P.n_bits, P.t, b.cs, b.B,
                            b.masks.p);
@@ -3406,12 +3419,13 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
     }
     hipLaunchKernelGGL(k_verdict_scan, dim3(cdiv(b.B, BPP_VERDICT_BLOCK)), dim3(BPP_VERDICT_BLOCK), 0, s, b.status.p, b.status0.p,
                        b.d_rounds_bad.p ? (const uint8_t *)b.d_rounds_bad.p : (const uint8_t *)nullptr,
-                       b.d_defer.p ? (const uint8_t *)b.d_defer.p : (const uint8_t *)nullptr, b.B, b.group_first.p, G, keys);
+                       b.d_defer.p ? (const uint8_t *)b.d_defer.p : (const uint8_t *)nullptr, b.B, b.group_first.p, G, keys, b.live_word());
     b.status_clean = true;  // (in stream order, as behind k_results_out)
     hipLaunchKernelGGL(k_verdict_finish, dim3(G), dim3(64), 0, s, keys, want_msm ? b.msm.is_identity.p : (const uint32_t *)nullptr, actions_dev,
                        action_all, zero_word, zero_word + 1, b.group_first.p, G, b.d_desc.p,
                        want_masks ? (const uint4 *)b.masks.p : (const uint4 *)nullptr, (uint32_t)(P.t * 2), verdicts_dev, (uint4 *)masks_dev,
-                       mask_present_dev, b.refill_state.p ? (const unsigned long long *)b.refill_state.p : (const unsigned long long *)nullptr);
+                       mask_present_dev, b.refill_state.p ? (const unsigned long long *)b.refill_state.p : (const unsigned long long *)nullptr,
+                       b.live_word());
     HIP_CHECK(hipGetLastError());
     const uint64_t t = ctx->enq_next++;
     HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));
@@ -3431,7 +3445,8 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
 // An enqueue in flight on the batch is in front of it on the stream, side stream included: every enqueue ends with the main stream
 // waiting for ev_join; the next enqueue's side-stream decompression waits for an ev_fork recorded behind the refill.  The action slots
 // and the layout are the shape's and stay.
-int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in, bpp_device_refill *record_dev, uint64_t *ticket) {
+int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in, const uint32_t *count_dev, bpp_device_refill *record_dev,
+                        uint64_t *ticket) {
   try {
     auto it = ctx->batches.find(batch);
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
@@ -3462,7 +3477,7 @@ int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in
       const void *p;
     } arrays[] = {{"proofs", in->proofs},           {"commitments32", in->commitments32}, {"min_values", in->min_values},
                   {"min_present", in->min_present}, {"seed_nonces32", in->seed_nonces32}, {"seed_present", in->seed_present},
-                  {"record_dev", record_dev}};
+                  {"record_dev", record_dev},       {"count_dev", count_dev}};
     for (const auto &a : arrays) {
       if (!a.p) continue;
       const int kind = device_pointer_kind(ctx->device, a.p);
@@ -3470,6 +3485,7 @@ int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in
         return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + ": not device memory of the context's device (pointer kind " + std::to_string(kind) + ")");
     }
     if ((uintptr_t)record_dev & 3u) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "record_dev: not 4-byte aligned");
+    if ((uintptr_t)count_dev & 3u) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "count_dev: not 4-byte aligned");
     Params &P = *b.params;
     const size_t n = b.B;
     // what the kernel writes, against what the upload allocated (the shape says they fit; a kernel is not launched on less)
@@ -3481,6 +3497,7 @@ int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in
     if (!b.refill_red.p) {  // the first refill of this batch: its few device words, and d_defer where no enqueue made it
       b.refill_red.alloc(BPP_REFILL_RED_WORDS);
       b.refill_state.alloc(1);
+      b.refill_live.alloc(1);  // (written by the first refill that takes a count, read only from then on)
       b.d_defer.alloc(n);
       HIP_CHECK(hipMemsetAsync(b.refill_red.p, 0, BPP_REFILL_RED_WORDS * 4, s));
       HIP_CHECK(hipMemsetAsync(b.refill_state.p, 0, 8, s));
@@ -3492,11 +3509,14 @@ int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in
     }
     const ParamShape shape_p{P.n_bits, P.m_max, P.t};
     const RefillPacked r = refill_args(*in, shape_p, (uint8_t)sh.t0, b.bytes.p, b.minvals.p, b.seeds.p, b.d_defer.p, b.d_desc.p, b.status0.p,
-                                       b.status.p, reinterpret_cast<uint32_t *>(b.masks.p), b.refill_red.p);
+                                       b.status.p, reinterpret_cast<uint32_t *>(b.masks.p), b.refill_red.p, count_dev);
+    if (count_dev) b.has_live = true;
+    b.enq_weights = false;
     b.refilled = true;  // from here on the contents are the stream's, whatever becomes of the launches
     b.seeds_dirty = sh.nonces;
     hipLaunchKernelGGL(k_refill_packed, dim3((uint32_t)cdiv((uint32_t)n, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, r);
-    hipLaunchKernelGGL(k_refill_finish, dim3(1), dim3(64), 0, s, b.refill_red.p, b.refill_state.p, record_dev);
+    hipLaunchKernelGGL(k_refill_finish, dim3(1), dim3(64), 0, s, b.refill_red.p, b.refill_state.p, record_dev, count_dev, (uint32_t)n,
+                       b.has_live ? b.refill_live.p : (uint32_t *)nullptr);
     // the statements' commitments, decoded as at the end of upload_device: COMMIT_FAIL goes to status0[] and status[]
     hipLaunchKernelGGL(k_decompress, dim3(cdiv(b.sum_m, 64)), dim3(64), 0, s, b.bytes.p, b.src_off.p, b.owner.p, b.idx_commit.p, b.sum_m,
                        b.dynpts.p, b.status0.p, (uint32_t *)nullptr, b.status.p);
@@ -3581,7 +3601,9 @@ int bpp_enqueue_wait(bpp_ctx *ctx, uint64_t ticket) {
 int bpp_verdict_result(const bpp_device_verdict *host_copy, bpp_shard_result *out) {
   if (!host_copy || !out || !(host_copy->flags & BPP_VERDICT_WRITTEN)) return BPP_ERR_INVALID_ARGUMENT;
   memset(out, 0, sizeof(*out));
-  if (host_copy->flags & BPP_VERDICT_REFILL)
+  if (host_copy->flags & BPP_VERDICT_EMPTY)
+    shard_result_set(*out, BPP_OK, BPP_TIER_NONE, -1, 0, "the group held no live item of the batch's last refill: nothing was verified");
+  else if (host_copy->flags & BPP_VERDICT_REFILL)
     shard_result_set(*out, host_copy->code, (int)host_copy->tier, -1, host_copy->index,
                      "the batch's last refill did not take: nothing of this verification is claimed, see the refill record (bpp_refill_result)");
   else if (host_copy->flags & BPP_VERDICT_REDRAW)
@@ -3594,13 +3616,45 @@ int bpp_verdict_result(const bpp_device_verdict *host_copy, bpp_shard_result *ou
 // (no gate, as bpp_verify_enqueue)
 int bpp_batch_refill_enqueue(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev, bpp_device_refill *record_dev, uint64_t *ticket) {
   BPP_ENTRY(ctx);
-  return batch_refill_locked(ctx, batch, in_dev, record_dev, ticket);
+  return batch_refill_locked(ctx, batch, in_dev, nullptr, record_dev, ticket);
+}
+
+int bpp_batch_refill_enqueue_count(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev, const uint32_t *count_dev,
+                                   bpp_device_refill *record_dev, uint64_t *ticket) {
+  BPP_ENTRY(ctx);
+  return batch_refill_locked(ctx, batch, in_dev, count_dev, record_dev, ticket);
+}
+
+// (a diagnostic: one device-to-device copy on the stream behind the batch's last enqueue)
+int bpp_enqueue_weights(bpp_ctx *ctx, uint64_t batch, uint8_t *weights_dev, uint64_t *ticket) {
+  BPP_ENTRY(ctx);
+  try {
+    auto it = ctx->batches.find(batch);
+    if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
+    Batch &b = *it->second;
+    if (!weights_dev) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+    if (!b.enq_weights || !b.weights.p || ctx->enq_events.empty())
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "the batch's last call on the stream was not a bpp_verify_enqueue that drew weights");
+    const int kind = device_pointer_kind(ctx->device, weights_dev);
+    if (kind != BPP_PTR_THIS_DEVICE)
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "weights_dev: not device memory of the context's device (pointer kind " + std::to_string(kind) + ")");
+    HIP_CHECK(hipMemcpyAsync(weights_dev, b.weights.p, (size_t)b.B * 32, hipMemcpyDeviceToDevice, ctx->stream));
+    const uint64_t t = ctx->enq_next++;
+    HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], ctx->stream));
+    b.enq_last_ticket = t;
+    if (ticket) *ticket = t;
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, nullptr, 0)
 }
 
 int bpp_refill_result(const bpp_device_refill *host_copy, bpp_shard_result *out) {
   if (!host_copy || !out || !(host_copy->flags & BPP_REFILL_WRITTEN)) return BPP_ERR_INVALID_ARGUMENT;
   memset(out, 0, sizeof(*out));
-  if (host_copy->flags & BPP_REFILL_FALLBACK)
+  if (host_copy->flags & BPP_REFILL_COUNT)
+    shard_result_set(*out, BPP_OK, BPP_TIER_NONE, -1, 0,
+                     "the live count exceeds the batch's item count: no item was taken and nothing is claimed, refill with a count the batch holds");
+  else if (host_copy->flags & BPP_REFILL_FALLBACK)
     shard_result_set(*out, BPP_OK, BPP_TIER_NONE, -1, 0,
                      "some proof's first byte is not the batch's: nothing is claimed, upload the arrays with a blocking call");
   else if (host_copy->flags & BPP_REFILL_FINDING)

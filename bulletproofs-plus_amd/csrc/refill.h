@@ -14,6 +14,13 @@
 // that) and which every kernel already handles as hostile input: identity encodings give a PASS-1 finding.  The decision is made by
 // the item's first lane and BROADCAST to the item's lanes before any lane moves a byte, so that copying depends on it.
 //
+// THE LIVE COUNT (bpp_batch_refill_enqueue_count) -- a refill may carry fewer items than the batch holds: one word in device memory,
+// read here on the stream, says how many.  Items at and beyond it are DEAD: neither checked (what lies there is neither a finding
+// nor a fall-back) nor read; their slots take the same broadcast decision as a refused item's and are sanitised, so the requirement
+// above holds for them as well.  k_refill_finish leaves the clamped count in a word of the batch, which is what the weight chains
+// (chain_dev.h) and the verdict kernels (verdict.h) read afterwards; every other kernel runs over all slots, and a dead proof
+// contributes nothing because its weight is zero.  A count beyond the batch makes nothing live and sets BPP_REFILL_COUNT.
+//
 // Shared by the kernels, by the engine's driver (engine.hip: batch_refill_locked) and by the sanitizer harness (hosttest_refill.cpp),
 // which runs the one-lane model refill_run_host against ingest_run_host + ingest_finish_plan.
 #pragma once
@@ -41,7 +48,13 @@ struct RefillPacked {
   uint32_t *masks;        // n rows of mask_row_words words: the engine's recovered masks of the old contents, wiped
   uint32_t mask_row_words;
   uint32_t *red;          // BPP_REFILL_RED_WORDS
+  const uint32_t *count;  // one word, read when the kernel runs: the live count c; null: every item (bpp_batch_refill_enqueue_count)
 };
+
+// the live count as the batch keeps it: c clamped -- a count beyond the batch makes nothing live (BPP_REFILL_COUNT)
+BPP_HD uint32_t refill_live(uint32_t count, uint32_t n_items) { return count <= n_items ? count : 0u; }
+// is item i of the caller's arrays live: i < min(count, N) and count <= N
+BPP_HD bool refill_item_live(size_t i, uint32_t count, uint32_t n_items) { return count <= n_items && i < (size_t)count; }
 
 // the decision for item i, by its first lane: BPP_REFILL_ITEM_* bits, and the item's key for the reduction (0: no finding)
 BPP_HD uint32_t refill_item_check(const RefillPacked &r, size_t i, uint32_t *key_out) {
@@ -84,13 +97,16 @@ BPP_HD void refill_item_finish(const RefillPacked &r, size_t i, uint32_t bits) {
 
 // the record of a refill from its two reduction words: the fall-back comes before any finding, as bpp_batch_upload_packed_device
 // decides "differs" before ingest_finish_plan throws
-BPP_HD bpp_device_refill refill_record(uint32_t finding_word, uint32_t differs) {
+// A count beyond the batch (count > n_items) comes before both: no item was looked at.
+BPP_HD bpp_device_refill refill_record(uint32_t finding_word, uint32_t differs, uint32_t count = 0, uint32_t n_items = 0) {
   bpp_device_refill rec;
   rec.code = BPP_OK;
   rec.msg = BPP_ING_OK;
   rec.index = 0;
   rec.flags = BPP_REFILL_WRITTEN;
-  if (differs) {
+  if (count > n_items) {
+    rec.flags |= BPP_REFILL_COUNT;
+  } else if (differs) {
     rec.flags |= BPP_REFILL_FALLBACK;
   } else if (finding_word) {
     const uint32_t key = 0xffffffffu - finding_word;
@@ -108,13 +124,19 @@ BPP_HD bpp_device_refill refill_record(uint32_t finding_word, uint32_t differs) 
 // width BPP_INGEST_LANES BEFORE any lane copies (the requirement in this file's header: an item the blocking upload would have
 // stopped is never copied, so no verification kernel sees a non-canonical scalar).  No lane leaves before the shuffles: lanes
 // beyond the last item carry a zero decision and move nothing.
+// The live count (r.count, null: every item) is one uniform load per lane: items at and beyond it -- every item when it exceeds the
+// batch -- are DEAD: not checked, so they carry the zero decision too, and the broadcast decision sanitises their slots as it does
+// a refused item's.  Nothing of a dead item's source is read.
 __global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_refill_packed(RefillPacked r) {
   const size_t gid = (size_t)blockIdx.x * BPP_INGEST_BLOCK + threadIdx.x;
   const size_t i = gid / BPP_INGEST_LANES;
   const uint32_t lane = (uint32_t)(gid % BPP_INGEST_LANES);
-  const bool live = i < r.in.n_items;
+  const uint32_t n_items = (uint32_t)r.in.n_items;
+  const uint32_t count = r.count ? *r.count : n_items;
+  const bool live = i < n_items;  // a slot of the batch
+  const bool live_item = refill_item_live(i, count, n_items);
   uint32_t decision = 0, key = 0;
-  if (live && lane == 0) decision = refill_item_check(r, i, &key);
+  if (live_item && lane == 0) decision = refill_item_check(r, i, &key);
   decision = (uint32_t)__shfl((int)decision, 0, (int)BPP_INGEST_LANES);
   uint32_t bits = 0;
   if (live) bits = refill_item_arrays(r, i, decision, lane, BPP_INGEST_LANES);
@@ -129,11 +151,15 @@ __global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_refill_packed(RefillPacked
 
 // k_refill_finish: one wavefront behind k_refill_packed.  Its first lane turns the reduction words into the record at `record`
 // (may be null) and into the batch's refill-state word, and leaves the reduction words clear for the next refill, so that no
-// memset is ever enqueued between two refills.
+// memset is ever enqueued between two refills.  count (null: every item) is the caller's word, read here for the last time: the
+// clamped value goes to the batch's own word `live` (null: the batch never took a count), which is what later kernels read.
 __global__ void __launch_bounds__(64) k_refill_finish(uint32_t *__restrict__ red, unsigned long long *__restrict__ state,
-                                                      bpp_device_refill *__restrict__ record) {
+                                                      bpp_device_refill *__restrict__ record, const uint32_t *__restrict__ count = nullptr,
+                                                      uint32_t n_items = 0, uint32_t *__restrict__ live = nullptr) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  const bpp_device_refill rec = refill_record(red[BPP_REFILL_RED_FINDING], red[BPP_REFILL_RED_DIFFERS]);
+  const uint32_t c = count ? *count : n_items;
+  if (live) *live = refill_live(c, n_items);
+  const bpp_device_refill rec = refill_record(red[BPP_REFILL_RED_FINDING], red[BPP_REFILL_RED_DIFFERS], c, n_items);
   red[BPP_REFILL_RED_FINDING] = 0;
   red[BPP_REFILL_RED_DIFFERS] = 0;
   *state = refill_state_make(rec.flags, rec.code, rec.msg, rec.index);
@@ -149,7 +175,8 @@ __global__ void __launch_bounds__(64) k_refill_finish(uint32_t *__restrict__ red
 // ---- host side
 // the kernel's arguments from the caller's struct and the batch's buffers (every pointer an address in device memory)
 inline RefillPacked refill_args(const bpp_packed_batch &pk, const ParamShape &P, uint8_t t0, uint8_t *bytes, uint64_t *minvals, uint8_t *seeds,
-                                uint8_t *defer, ProofDesc *desc, uint32_t *status0, uint32_t *status, uint32_t *masks, uint32_t *red) {
+                                uint8_t *defer, ProofDesc *desc, uint32_t *status0, uint32_t *status, uint32_t *masks, uint32_t *red,
+                                const uint32_t *count = nullptr) {
   RefillPacked r;
   memset(&r, 0, sizeof(r));
   bpp_packed_batch in = pk;
@@ -164,21 +191,26 @@ inline RefillPacked refill_args(const bpp_packed_batch &pk, const ParamShape &P,
   r.masks = masks;
   r.mask_row_words = P.t * 8;
   r.red = red;
+  r.count = count;
   return r;
 }
 
 // the two kernels on the host, one lane per item, reduced as the kernels reduce: the model hosttest_refill.cpp holds to
-// ingest_run_host + ingest_finish_plan.  `red` is expected clear and is left clear.
-inline void refill_run_host(const RefillPacked &r, uint64_t *state, bpp_device_refill *record) {
+// ingest_run_host + ingest_finish_plan.  `red` is expected clear and is left clear.  `live` (may be null) takes the clamped count.
+inline void refill_run_host(const RefillPacked &r, uint64_t *state, bpp_device_refill *record, uint32_t *live = nullptr) {
+  const uint32_t n_items = (uint32_t)r.in.n_items;
+  const uint32_t count = r.count ? *r.count : n_items;
   for (size_t i = 0; i < r.in.n_items; i++) {
-    uint32_t key;
-    const uint32_t decision = refill_item_check(r, i, &key);
+    const bool live_item = refill_item_live(i, count, n_items);
+    uint32_t key = 0;
+    const uint32_t decision = live_item ? refill_item_check(r, i, &key) : 0u;
     const uint32_t bits = refill_item_arrays(r, i, decision, 0, 1);
     refill_item_finish(r, i, bits);
     if (key > r.red[BPP_REFILL_RED_FINDING]) r.red[BPP_REFILL_RED_FINDING] = key;
     if (decision & BPP_REFILL_ITEM_FOREIGN) r.red[BPP_REFILL_RED_DIFFERS] |= 1u;
   }
-  const bpp_device_refill rec = refill_record(r.red[BPP_REFILL_RED_FINDING], r.red[BPP_REFILL_RED_DIFFERS]);
+  if (live) *live = refill_live(count, n_items);
+  const bpp_device_refill rec = refill_record(r.red[BPP_REFILL_RED_FINDING], r.red[BPP_REFILL_RED_DIFFERS], count, n_items);
   r.red[BPP_REFILL_RED_FINDING] = r.red[BPP_REFILL_RED_DIFFERS] = 0;
   *state = refill_state_make(rec.flags, rec.code, rec.msg, rec.index);
   if (record) *record = rec;

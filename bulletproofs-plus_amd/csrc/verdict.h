@@ -86,28 +86,50 @@ BPP_HD bpp_device_verdict verdict_finish(uint64_t key, bool want_msm, int action
   return v;
 }
 
+// ---- the live count of a batch (bpp_batch_refill_enqueue_count): items at and beyond it are dead slots.  A batch without a count
+// word passes BPP_VERDICT_ALL_LIVE and everything below is what it was.
+#define BPP_VERDICT_ALL_LIVE 0xffffffffu
+// is item i live
+BPP_HD bool verdict_item_live(uint32_t i, uint32_t live) { return i < live; }
+// group [p0, p1): its live length -- the proofs its verify() call runs over; 0: an empty group
+BPP_HD uint32_t verdict_group_live(uint32_t p0, uint32_t p1, uint32_t live) { return p0 >= live ? 0u : (p1 < live ? p1 : live) - p0; }
+
 // ---- the refill-state word of a batch (refill.h: k_refill_finish writes it, bpp_batch_refill_enqueue owns it).  Zero: the batch's
 // last refill took, or it was never refilled.  Otherwise bits 0..7 hold the BPP_REFILL_* flags of the refill record, bits 8..15 the
 // message id, bits 16..23 the code as a signed byte, bits 32..63 the index inside the batch.
 BPP_HD uint64_t refill_state_make(uint32_t flags, int32_t code, uint32_t msg, uint32_t index) {
-  if (!(flags & (BPP_REFILL_FINDING | BPP_REFILL_FALLBACK))) return 0;
+  if (!(flags & (BPP_REFILL_FINDING | BPP_REFILL_FALLBACK | BPP_REFILL_COUNT))) return 0;
   return (uint64_t)(flags & 255u) | ((uint64_t)(msg & 255u) << 8) | ((uint64_t)((uint32_t)code & 255u) << 16) | ((uint64_t)index << 32);
 }
 
 // verdict_finish with the refill-state word: a refill that did not take answers for every group of every enqueue until the next
 // refill -- nothing of the verification is claimed, whatever it found.  A zero word gives verdict_finish as it is.
 BPP_HD bpp_device_verdict verdict_finish(uint64_t key, bool want_msm, int action, bool is_identity, bool zero_weight, uint64_t refill_state) {
-  if (!(refill_state & (BPP_REFILL_FINDING | BPP_REFILL_FALLBACK))) return verdict_finish(key, want_msm, action, is_identity, zero_weight);
+  if (!(refill_state & (BPP_REFILL_FINDING | BPP_REFILL_FALLBACK | BPP_REFILL_COUNT))) return verdict_finish(key, want_msm, action, is_identity, zero_weight);
   bpp_device_verdict v;
   v.code = BPP_OK;
   v.tier = BPP_TIER_NONE;
   v.index = 0;
   v.flags = BPP_VERDICT_WRITTEN | BPP_VERDICT_REFILL;
-  if (!(refill_state & BPP_REFILL_FALLBACK)) {  // (the fall-back comes first and claims nothing)
+  if (!(refill_state & (BPP_REFILL_FALLBACK | BPP_REFILL_COUNT))) {  // (a bad count and the fall-back come first and claim nothing)
     v.code = (int32_t)(int8_t)(uint8_t)(refill_state >> 16);
     v.tier = BPP_TIER_CONSTRUCTION;
     v.index = (uint32_t)(refill_state >> 32);
   }
+  return v;
+}
+
+// ... and with the group's live length (verdict_group_live): a refill that did not take still answers for every group; otherwise a
+// group without a live item claims nothing at all -- not even the redraw, which only a live item's weight can raise
+BPP_HD bpp_device_verdict verdict_finish(uint64_t key, bool want_msm, int action, bool is_identity, bool zero_weight, uint64_t refill_state,
+                                         uint32_t live_len) {
+  if (live_len != 0 || (refill_state & (BPP_REFILL_FINDING | BPP_REFILL_FALLBACK | BPP_REFILL_COUNT)))
+    return verdict_finish(key, want_msm, action, is_identity, zero_weight, refill_state);
+  bpp_device_verdict v;
+  v.code = BPP_OK;
+  v.tier = BPP_TIER_NONE;
+  v.index = 0;
+  v.flags = BPP_VERDICT_WRITTEN | BPP_VERDICT_EMPTY;
   return v;
 }
 
@@ -144,14 +166,18 @@ inline const char *verdict_message(uint32_t tier, int32_t code) {
 __global__ void __launch_bounds__(BPP_VERDICT_BLOCK) k_verdict_scan(uint32_t *__restrict__ status, const uint32_t *__restrict__ status0,
                                                                     const uint8_t *__restrict__ rounds_bad, const uint8_t *__restrict__ defer,
                                                                     uint32_t B, const uint32_t *__restrict__ group_first, uint32_t G,
-                                                                    unsigned long long *__restrict__ keys) {
+                                                                    unsigned long long *__restrict__ keys,
+                                                                    const uint32_t *__restrict__ live = nullptr) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t lv = live ? *live : BPP_VERDICT_ALL_LIVE;
   uint32_t st = 0, rb = 0, df = 0;
   if (i < B) {
     st = status[i];
     status[i] = status0[i];
     if (rounds_bad) rb = rounds_bad[i];
     if (defer) df = defer[i];
+    // a dead slot is put back like any other and contributes no key, whatever it holds (its sanitised bytes do raise PASS-1 findings)
+    if (!verdict_item_live(i, lv)) st = rb = df = 0;
   }
   uint32_t g = 0;
   uint64_t key = BPP_VERDICT_KEY_NONE;
@@ -196,15 +222,20 @@ __global__ void __launch_bounds__(BPP_VERDICT_BLOCK) k_verdict_scan(uint32_t *__
 //   masks == nullptr: the call recovered no masks (no group asked, or no item carries a seed nonce)
 //   refill_state == nullptr, or a zero word: the batch's contents are what its last upload or refill made them; otherwise every
 //     group gets the refill's record (verdict_finish above) and no masks
+//   live == nullptr: every item is live; otherwise a group that starts at or beyond *live gets the EMPTY record, and mask rows and
+//     mask_present are handed out below *live only (zeros beyond).  groups_done still reaches G.
 __global__ void __launch_bounds__(64) k_verdict_finish(unsigned long long *__restrict__ keys, const uint32_t *__restrict__ is_identity,
                                                        const int *__restrict__ actions, int action_all, uint32_t *__restrict__ zero_word,
                                                        uint32_t *__restrict__ groups_done, const uint32_t *__restrict__ group_first,
                                                        uint32_t G, const ProofDesc *__restrict__ desc, const uint4 *__restrict__ masks,
                                                        uint32_t row_pieces, bpp_device_verdict *__restrict__ verdicts,
                                                        uint4 *__restrict__ masks_out, uint8_t *__restrict__ mask_present,
-                                                       const unsigned long long *__restrict__ refill_state = nullptr) {
+                                                       const unsigned long long *__restrict__ refill_state = nullptr,
+                                                       const uint32_t *__restrict__ live = nullptr) {
   const uint32_t g = blockIdx.x, lane = threadIdx.x;
   if (g >= G) return;
+  const uint32_t lv = live ? *live : BPP_VERDICT_ALL_LIVE;
+  const uint32_t p0 = group_first[g], p1 = group_first[g + 1];
   int give = 0;
   if (lane == 0) {
     const uint64_t key = keys[g];
@@ -212,9 +243,10 @@ __global__ void __launch_bounds__(64) k_verdict_finish(unsigned long long *__res
     const int action = actions ? actions[g] : action_all;
     const bool zero = *zero_word != 0;
     const bpp_device_verdict v = verdict_finish(key, is_identity != nullptr, action, is_identity ? is_identity[g] != 0 : true, zero,
-                                                refill_state ? (uint64_t)*refill_state : 0ull);
+                                                refill_state ? (uint64_t)*refill_state : 0ull, verdict_group_live(p0, p1, lv));
     *reinterpret_cast<uint4 *>(&verdicts[g]) = make_uint4((uint32_t)v.code, v.tier, v.index, v.flags);
-    give = (masks != nullptr && v.tier == BPP_TIER_NONE && !(v.flags & (BPP_VERDICT_REDRAW | BPP_VERDICT_REFILL)) && action != BPP_VERIFY_ONLY) ? 1 : 0;
+    give = (masks != nullptr && v.tier == BPP_TIER_NONE && !(v.flags & (BPP_VERDICT_REDRAW | BPP_VERDICT_REFILL | BPP_VERDICT_EMPTY)) &&
+            action != BPP_VERIFY_ONLY) ? 1 : 0;
     // every group has read the zero-weight word once the count reaches G: the last one clears both
     __threadfence();
     if (atomicAdd(groups_done, 1u) == G - 1) {
@@ -223,14 +255,13 @@ __global__ void __launch_bounds__(64) k_verdict_finish(unsigned long long *__res
     }
   }
   give = __shfl(give, 0, 64);
-  const uint32_t p0 = group_first[g], p1 = group_first[g + 1];
   if (mask_present)
-    for (uint32_t p = p0 + lane; p < p1; p += 64) mask_present[p] = (give && (desc[p].flags & 1u)) ? 1 : 0;
+    for (uint32_t p = p0 + lane; p < p1; p += 64) mask_present[p] = (give && verdict_item_live(p, lv) && (desc[p].flags & 1u)) ? 1 : 0;
   if (masks_out) {
     const size_t q0 = (size_t)p0 * row_pieces, q1 = (size_t)p1 * row_pieces;
     for (size_t q = q0 + lane; q < q1; q += 64) {
       const uint32_t p = (uint32_t)(q / row_pieces);
-      masks_out[q] = (give && (desc[p].flags & 1u)) ? masks[q] : make_uint4(0, 0, 0, 0);
+      masks_out[q] = (give && verdict_item_live(p, lv) && (desc[p].flags & 1u)) ? masks[q] : make_uint4(0, 0, 0, 0);
     }
   }
 }

@@ -706,16 +706,44 @@ class ResidentBatch(api.ResidentBatch):
         api._check(rc, self.engine.ctx)
         return Enqueued(self.engine, ticket.value, G, verdicts, masks, present)
 
-    def refill(self, inp, record=None):
+    def refill(self, inp, record=None, count=None):
         """bpp_batch_refill_enqueue: new contents of the same shape for this batch (made with form="device") from the
         DevicePackedInput `inp`, enqueued on the engine's stream; an enqueue() afterwards gives what it would give on a fresh upload
         of those arrays.  Nothing is synchronised here: what wrote the arrays must be ordered before the engine's stream (an engine
         made on torch's current stream has that by construction).  The batch keeps its transcript: inp's label and state are not
         passed on.  `record`: an int32 [4] device tensor (code, message id, index, flags) or a raw address; None: allocated.  Returns a
-        Refilled.  A refilled batch takes enqueued calls only."""
+        Refilled.  A refilled batch takes enqueued calls only.
+        `count` (bpp_batch_refill_enqueue_count): the live count -- items at and beyond it are dead slots, not read, and an enqueue()
+        afterwards gives, for every group with a live item, what it gives on a fresh upload of the first `count` items with the
+        boundaries clipped; a group without one gets a VERDICT_EMPTY record.  An int goes into a one-word device tensor the batch
+        owns (an asynchronous copy on torch's current stream: use an engine made on that stream); a device tensor of one int32 or
+        uint32 word is passed as it is and read when the refill runs on the stream.  None: every item."""
         import torch
+        dev = torch.device("cuda", int(self.engine.device))
+        count_addr = None
+        if count is not None and hasattr(count, "data_ptr"):
+            if count.dtype not in (torch.int32, torch.uint32) or count.numel() != 1:
+                raise api.ProofError(api.ProofErrorKind.InvalidArgument, "count: an int or a tensor of one 32-bit word expected")
+            count_addr = ctypes.c_void_p(count.data_ptr())
+            self._count_arg = count  # (stays alive until the refill has run)
+        elif count is not None:
+            if not 0 <= int(count) < 2 ** 32:
+                raise api.ProofError(api.ProofErrorKind.InvalidArgument, "count: a 32-bit unsigned value expected")
+            if getattr(self, "_count_words", None) is None:
+                self._count_words, self._count_next = torch.zeros((16,), dtype=torch.int32, device=dev), 0
+            cur = torch.cuda.current_stream(int(self.engine.device))
+            shared = bool(self.engine.stream) and int(cur.cuda_stream) == self.engine.stream
+            # on the engine's own stream one word serves every refill; otherwise the write is completed here and the words take
+            # turns, so that a refill still in flight keeps the word it was given
+            slot = 0 if shared else self._count_next % 16
+            self._count_next += 1
+            word = self._count_words[slot:slot + 1]
+            word.fill_(int(count) if int(count) < 2 ** 31 else int(count) - 2 ** 32)
+            if not shared:
+                cur.synchronize()
+            count_addr = ctypes.c_void_p(word.data_ptr())
         if record is None:
-            record = torch.empty((4,), dtype=torch.int32, device=torch.device("cuda", int(self.engine.device)))
+            record = torch.empty((4,), dtype=torch.int32, device=dev)
         if hasattr(record, "data_ptr"):
             if record.dtype != torch.int32 or tuple(record.shape) != (4,) or not record.is_contiguous():
                 raise api.ProofError(api.ProofErrorKind.InvalidArgument, "record: a contiguous int32 tensor of shape (4,) expected")
@@ -725,14 +753,49 @@ class ResidentBatch(api.ResidentBatch):
         st = _lib.PackedBatch.from_buffer_copy(inp.struct)
         st.transcript_state, st.transcript_label, st.label_len = None, None, 0
         ticket = c_uint64()
-        rc = self.engine.lib.bpp_batch_refill_enqueue(self.engine.ctx, self.handle, byref(st), addr, byref(ticket))
+        if count_addr is None:
+            rc = self.engine.lib.bpp_batch_refill_enqueue(self.engine.ctx, self.handle, byref(st), addr, byref(ticket))
+        else:
+            rc = self.engine.lib.bpp_batch_refill_enqueue_count(self.engine.ctx, self.handle, byref(st), count_addr, addr, byref(ticket))
         api._check(rc, self.engine.ctx)
         self.input = inp  # (the arrays stay alive until the refill has run)
         return Refilled(self.engine, ticket.value, record)
 
+    def enqueue_weights(self, out=None):
+        """bpp_enqueue_weights, a diagnostic: the batch weights the last enqueue() of this batch used, uint8 [n, 32] on the engine's
+        device, valid in stream order behind the call (dead slots of a refill with a count: zeros).  Does not wait.  Returns an
+        EnqueuedWeights: `.weights` and the ticket."""
+        import torch
+        if out is None:
+            out = torch.empty((self.n, 32), dtype=torch.uint8, device=torch.device("cuda", int(self.engine.device)))
+        if hasattr(out, "data_ptr"):
+            if out.dtype != torch.uint8 or tuple(out.shape) != (self.n, 32) or not out.is_contiguous():
+                raise api.ProofError(api.ProofErrorKind.InvalidArgument, "out: a contiguous uint8 tensor of shape (n, 32) expected")
+            addr = ctypes.c_void_p(out.data_ptr())
+        else:
+            addr = ctypes.c_void_p(int(out))
+        ticket = c_uint64()
+        api._check(self.engine.lib.bpp_enqueue_weights(self.engine.ctx, self.handle, addr, byref(ticket)), self.engine.ctx)
+        return EnqueuedWeights(self.engine, ticket.value, out)
 
-VERDICT_WRITTEN, VERDICT_REDRAW, VERDICT_REFILL = 1, 2, 4
-REFILL_WRITTEN, REFILL_FINDING, REFILL_FALLBACK = 1, 2, 4
+
+VERDICT_WRITTEN, VERDICT_REDRAW, VERDICT_REFILL, VERDICT_EMPTY = 1, 2, 4, 8
+REFILL_WRITTEN, REFILL_FINDING, REFILL_FALLBACK, REFILL_COUNT = 1, 2, 4, 8
+
+
+class EnqueuedWeights:
+    """What ResidentBatch.enqueue_weights returns: `.weights` (uint8 [n, 32], a device tensor valid in stream order behind the call)
+    and the ticket: wait() blocks until the copy has run, numpy() waits and copies the weights to the host."""
+
+    def __init__(self, engine, ticket, weights):
+        self.engine, self.ticket, self.weights = engine, ticket, weights
+
+    def wait(self):
+        api._check(self.engine.lib.bpp_enqueue_wait(self.engine.ctx, self.ticket), self.engine.ctx)
+
+    def numpy(self):
+        self.wait()
+        return self.weights.cpu().numpy()
 
 
 class Refilled:

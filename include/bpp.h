@@ -578,6 +578,35 @@ struct bpp_refill_stats {
 };
 int bpp_refill_stats(bpp_ctx *ctx, struct bpp_refill_stats *out);
 
+/* ---- a refill with fewer items than the batch holds ----
+ * bpp_batch_refill_enqueue_count is bpp_batch_refill_enqueue with a LIVE COUNT c that is read ON THE STREAM, when the refill kernel
+ * runs: `count_dev` is one 32-bit word in BPP_PTR_THIS_DEVICE memory (anything else is refused before any launch, the field named)
+ * and the host never learns it.  `in_dev` keeps the batch's shape exactly: n_items is the batch's N and the arrays are N items
+ * long.  count_dev == NULL is bpp_batch_refill_enqueue: the same launches and the same bytes.
+ * After a refill with c (0 <= c <= N) a bpp_verify_enqueue on the batch gives, for every group that holds a live item, byte for byte
+ * what it gives on a fresh bpp_batch_upload_packed_device of the FIRST c ITEMS with the same boundaries clipped to c: the group
+ * [p0, p1) runs over [p0, min(p1, c)), its weight transcript absorbs and draws those proofs alone, `index` counts inside the group.
+ * A group with p0 >= c gets {0, BPP_TIER_NONE, 0, BPP_VERDICT_WRITTEN | BPP_VERDICT_EMPTY} and no masks.  masks_dev rows and
+ * mask_present_dev bytes of items i >= c are zero.  BPP_VERDICT_REDRAW is raised by a zero weight of a live item only and claimed
+ * by groups that hold one.
+ * ITEMS i >= c are neither checked (a non-canonical scalar, a foreign first byte, a missing nonce there is neither a finding nor a
+ * fall-back) nor copied: their slots hold the batch's first byte and zeros, zero commitments, no promises, no nonce -- what the
+ * slot of a refused item holds -- and their mask rows are wiped.  They still pass through the per-proof kernels with weight zero:
+ * a dead slot costs what a live one does.
+ * c > N sets BPP_REFILL_COUNT in the refill record (before BPP_REFILL_FALLBACK and before any finding): every slot is cleared as
+ * above, nothing is live, and every later verdict carries BPP_VERDICT_REFILL with code 0 and tier 0 until the next refill.
+ * The batch keeps the clamped count in a device word of its own, written by the refill; later enqueues read that word and never
+ * the caller's, which may be overwritten as soon as the refill has run.  STEADY STATE as for bpp_batch_refill_enqueue. */
+#define BPP_REFILL_COUNT 8u   /* in bpp_device_refill.flags: the live count exceeds the batch's item count; nothing claimed */
+#define BPP_VERDICT_EMPTY 8u  /* in bpp_device_verdict.flags: the group holds no live item of the batch's last refill */
+int bpp_batch_refill_enqueue_count(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev,
+                                   const uint32_t *count_dev /* one word in device memory; NULL: every item */,
+                                   bpp_device_refill *record_dev /* may be NULL */, uint64_t *ticket /* may be NULL */);
+/* A diagnostic: enqueues a device-to-device copy of the batch weights that the batch's last enqueued verification used, N x 32
+ * canonical bytes, into weights_dev (BPP_PTR_THIS_DEVICE memory); dead slots hold 32 zero bytes.  Allocates nothing and does not
+ * wait.  BPP_ERR_INVALID_ARGUMENT for a batch whose last call on the stream was not an enqueue that drew weights. */
+int bpp_enqueue_weights(bpp_ctx *ctx, uint64_t batch, uint8_t *weights_dev /* N x 32, device */, uint64_t *ticket /* may be NULL */);
+
 /* bpp_batcher: many host threads, each with ONE reference batch per call.  Separate small calls stop at about 5 000 calls per
  * second whatever the number of callers (a small call is a chain of latency-bound kernels and the chip runs about six of those
  * side by side); the batcher pools the calls that are waiting into grouped engine calls (bpp_verify_resident_groups) on

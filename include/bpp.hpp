@@ -182,6 +182,24 @@ class Engine {
     check(rc, bpp_ctx_last_error(ctx_));
     return t;
   }
+  // ... with a live count read on the stream (bpp_batch_refill_enqueue_count): count_dev is one word in device memory, null means
+  // every item.  Items at and beyond the count are dead slots; a group without a live item gets a BPP_VERDICT_EMPTY record.
+  EnqueueTicket batch_refill_enqueue(uint64_t batch, const bpp_packed_batch &in_dev, const uint32_t *count_dev, bpp_device_refill *record_dev) {
+    EnqueueTicket t;
+    t.ctx_ = ctx_;
+    const int rc = bpp_batch_refill_enqueue_count(ctx_, batch, &in_dev, count_dev, record_dev, &t.id);
+    check(rc, bpp_ctx_last_error(ctx_));
+    return t;
+  }
+  // A diagnostic: the weights of the batch's last enqueued verification, n x 32 bytes into device memory, in stream order
+  // (bpp_enqueue_weights); dead slots hold zeros.
+  EnqueueTicket enqueue_weights(uint64_t batch, uint8_t *weights_dev) {
+    EnqueueTicket t;
+    t.ctx_ = ctx_;
+    const int rc = bpp_enqueue_weights(ctx_, batch, weights_dev, &t.id);
+    check(rc, bpp_ctx_last_error(ctx_));
+    return t;
+  }
   struct bpp_refill_stats refill_stats() const {
     struct bpp_refill_stats s{};
     const int rc = ::bpp_refill_stats(ctx_, &s);

@@ -222,6 +222,7 @@ pub struct bpp_device_verdict {
 pub const BPP_VERDICT_WRITTEN: u32 = 1;
 pub const BPP_VERDICT_REDRAW: u32 = 2;
 pub const BPP_VERDICT_REFILL: u32 = 4;
+pub const BPP_VERDICT_EMPTY: u32 = 8;
 
 /// `bpp_device_refill`: the record of `bpp_batch_refill_enqueue`, 16 bytes, as it lies in device memory
 #[repr(C)]
@@ -235,6 +236,7 @@ pub struct bpp_device_refill {
 pub const BPP_REFILL_WRITTEN: u32 = 1;
 pub const BPP_REFILL_FINDING: u32 = 2;
 pub const BPP_REFILL_FALLBACK: u32 = 4;
+pub const BPP_REFILL_COUNT: u32 = 8;
 
 /// `struct bpp_refill_stats`: what the refills (`bpp_batch_refill_enqueue`) of a context came to
 #[repr(C)]
@@ -358,6 +360,10 @@ extern "C" {
                                     ticket: *mut u64) -> c_int;
     pub fn bpp_refill_result(host_copy: *const bpp_device_refill, out: *mut bpp_shard_result) -> c_int;
     pub fn bpp_refill_stats(ctx: *mut bpp_ctx, out: *mut bpp_refill_stats) -> c_int;
+    // ... with a live count in one word of device memory, read on the stream (null: every item); the weights of the last enqueue
+    pub fn bpp_batch_refill_enqueue_count(ctx: *mut bpp_ctx, batch: u64, in_dev: *const bpp_packed_batch, count_dev: *const u32,
+                                          record_dev: *mut bpp_device_refill, ticket: *mut u64) -> c_int;
+    pub fn bpp_enqueue_weights(ctx: *mut bpp_ctx, batch: u64, weights_dev: *mut u8, ticket: *mut u64) -> c_int;
     pub fn bpp_batcher_verify_action(b: *mut bpp_batcher, input: *const bpp_packed_batch, action: c_int, masks_out: *mut u8,
                                      mask_present: *mut u8, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
     pub fn bpp_batcher_set_limits(b: *mut bpp_batcher, max_calls: u32, max_proofs: u32) -> c_int;

@@ -7,6 +7,9 @@ warmed up, as tools/gpu_ab.py alternates its arms:
 
   upload   per step bpp_batch_upload_packed_device, bpp_verify_enqueue, bpp_batch_destroy
   refill   per step bpp_batch_refill_enqueue and bpp_verify_enqueue on one batch
+  refill_count_K   (one per --count K, any number of them) per step bpp_batch_refill_enqueue_count with the live count K in a device
+           word and bpp_verify_enqueue on a batch of its own: what a step costs when N - K of its slots are dead.  A dead slot passes
+           through the per-proof kernels with weight zero, so these arms state a cost; they are not there to meet a bar.
 
 Per (arm, repetition) one JSON line: steps/s over a window that ends in a device synchronise, process CPU seconds per step, host time
 of the step's calls (median).  In a pass of its own (not inside the timed window) every step's ingest part is bracketed by events on
@@ -40,6 +43,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--event-steps", type=int, default=40)
     ap.add_argument("--kernel-stats", default="", help="a rocprofv3 kernel_stats.csv of a run of this program")
+    ap.add_argument("--count", type=int, action="append", default=[], help="add an arm that refills with this live count (repeatable)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     import numpy as np
@@ -104,6 +108,23 @@ def main():
             enqueue(resident.handle, k)
 
         arms = {"upload": step_upload, "refill": step_refill}
+        counted = {}
+        for K in args.count:  # one batch and one count word per arm
+            rb = packed.ResidentBatch(params, ring[0], None, None, None, None, LABEL, form="device")
+            word = torch.tensor([K], dtype=torch.int32, device="cuda")
+
+            def step_count(k, mark=None, rb=rb, word=word):
+                if mark:
+                    mark[0].record(stream)
+                rc = lib.bpp_batch_refill_enqueue_count(ctx, rb.handle, ctypes.byref(bare[k]), ctypes.c_void_p(word.data_ptr()),
+                                                        ctypes.c_void_p(records[k].data_ptr()), None)
+                packed.api._check(rc, ctx)
+                if mark:
+                    mark[1].record(stream)
+                enqueue(rb.handle, k)
+
+            counted["refill_count_%d" % K] = (K, rb, word, step_count)
+        torch.cuda.synchronize()
         # ---- the refill arm's verdicts against the upload arm's, every input set (this is also the first warm-up)
         seen = {}
         for arm, step in arms.items():
@@ -113,6 +134,17 @@ def main():
             seen[arm] = [v.cpu().tolist() for v in verdicts]
         if seen["upload"] != seen["refill"] or [v[0][1] for v in seen["upload"]] != [0, 0, 7, 0]:
             raise SystemExit("verdicts differ between the arms, or are not the ones the inputs were made for: %s" % seen)
+        for arm, (K, rb, word, step) in counted.items():  # the tampered proof is item 77 of set 2: live or not
+            for k in range(RING):
+                step(k)
+            torch.cuda.synchronize()
+            got = [v.cpu().tolist()[0] for v in verdicts]
+            want = [[0, 0, 0, 1 if 0 < K <= N else (9 if K == 0 else 5)] for _ in range(RING)]
+            if 77 < K <= N:
+                want[2] = [1, 7, 0, 1]
+            if got != want:
+                raise SystemExit("%s: verdicts %s, expected %s" % (arm, got, want))
+            arms[arm] = step
 
         def timed(arm, steps):
             step, host = arms[arm], []
@@ -154,6 +186,8 @@ def main():
             emit({"arm": arm, "ingest_span_ms_median": round(statistics.median(spans), 4), "ingest_span_ms_min": round(min(spans), 4),
                   "what": "events around bpp_batch_upload_packed_device" if arm == "upload" else "events around bpp_batch_refill_enqueue"})
         resident.close()
+        for _K, rb, _word, _step in counted.values():
+            rb.close()
         params.close()
         eng.close()
     if args.kernel_stats:

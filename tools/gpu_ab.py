@@ -15,6 +15,7 @@ Legs (what is run and what the summary shows):
   prover            tools/bench_prover_leg.py (configs[4], one call at a time)  proofs/s, ms per call, MSM event time
   prover-inflight   tools/bench_prove_concurrent.py (1, 2, 4 calls in flight)   proofs/s per number of calls in flight
   latency           tools/bench_latency.py --no-cpu                             median ms per call and size
+  refill            tools/bench_refill.py (upload, refill and any --count arms)  steps/s of every repetition, per arm of that program
   cmd               the command given with --cmd                                its last line of output
 
 Examples (the A/Bs on record in HISTORY.md, as they would be run today):
@@ -88,13 +89,22 @@ def summarise(leg, out):
     if leg == "latency":
         rows = [json.loads(x) for x in out.splitlines() if x.startswith("{")]
         return "  ".join("%d: %.3f ms" % (r["batch"], r["gpu_ms_median"]) for r in rows) or "no line"
+    if leg == "refill":
+        rows = [json.loads(x) for x in out.splitlines() if x.startswith("{")]
+        arms = {}
+        for r in rows:
+            if "arm" in r and "steps_per_s" in r:
+                arms.setdefault(r["arm"], []).append(r["steps_per_s"])
+        stats = next((r["refill_arm"] for r in rows if "refill_arm" in r), {})
+        return ("  ".join("%s %s steps/s" % (k, " ".join("%.1f" % x for x in v)) for k, v in arms.items()) +
+                " | host waits: refill %s, enqueue %s" % (stats.get("refill_host_waits"), stats.get("enqueue_host_waits"))) if arms else "no line"
     lines = out.strip().splitlines()
     return lines[-1] if lines else "no output"
 
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--leg", choices=("headline", "headline-again", "prover", "prover-inflight", "latency", "cmd"), default="headline")
+    ap.add_argument("--leg", choices=("headline", "headline-again", "prover", "prover-inflight", "latency", "refill", "cmd"), default="headline")
     ap.add_argument("--reps", type=int, default=2)
     ap.add_argument("--out", default=os.path.join("gpurun_out", "ab.txt"))
     ap.add_argument("--args", default="", help="arguments every arm gets (after the leg's own)")
@@ -105,7 +115,7 @@ def main():
     base = {"headline": [sys.executable, "bench.py", "--no-extra", "--no-cpu-baseline", "--no-traffic"],
             "headline-again": [sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-traffic"],
             "prover": [sys.executable, "tools/bench_prover_leg.py"], "prover-inflight": [sys.executable, "tools/bench_prove_concurrent.py"],
-            "latency": [sys.executable, "tools/bench_latency.py", "--no-cpu"], "cmd": shlex.split(a.cmd)}[a.leg]
+            "latency": [sys.executable, "tools/bench_latency.py", "--no-cpu"], "refill": [sys.executable, "tools/bench_refill.py"], "cmd": shlex.split(a.cmd)}[a.leg]
     if not base:
         raise SystemExit("--leg cmd needs --cmd")
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
