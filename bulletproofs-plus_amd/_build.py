@@ -211,6 +211,22 @@ def build_refill_count_harness(force=False):
     return REFILL_COUNT_SANITIZER_BIN
 
 
+REFILL_LIVE_SANITIZER_BIN = os.path.join(HERE, "hosttest_refill_live_asan")
+
+
+def build_refill_live_harness(force=False):
+    """hosttest_refill_live.cpp (refill.h under a live mask: the one-lane model of the kernels of bpp_batch_refill_enqueue_live, held
+    to the device upload's routines on the live items alone; verdict.h: the live routines on compacted groups) under ASan + UBSan: an
+    executable, run by tests/test_refill_live_host.py."""
+    src = os.path.join(CSRC, "hosttest_refill_live.cpp")
+    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
+    if not force and not _stale(REFILL_LIVE_SANITIZER_BIN, deps):
+        return REFILL_LIVE_SANITIZER_BIN
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-fno-omit-frame-pointer", "-o", REFILL_LIVE_SANITIZER_BIN, src], check=True, cwd=CSRC)
+    return REFILL_LIVE_SANITIZER_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     build_hosttest(force="--force" in sys.argv)

@@ -23,6 +23,8 @@
 //   * a batch refilled with a live count (refill.h) hands both kernels its count word: a group's chain then runs over the group's
 //     live proofs alone -- the reference's chain of the batch cut short, the staging loop and the one-store fast path work for
 //     any number of proofs -- and a dead slot gets weight zero, which makes every scalar of that proof zero in PASS 2.
+//   * a batch refilled under a mask (bpp_batch_refill_enqueue_live) hands them its mask bytes instead, and the kernels'
+//     MASKED forms run: the chain skips the holes of a group and is the reference's chain of the group's live proofs in slot order.
 #pragma once
 #include "scalar.h"
 #include "verdict.h"  // the live routines
@@ -93,16 +95,23 @@ BPP_HD constexpr uint64_t chain_word_of(uint32_t w, uint32_t at, const uint8_t *
 
 // t0: the transcript after Transcript::new(b"Bulletproofs+ verifier weights") (25 state words, pos, pos_begin; host-made).
 // wide[p][16]: the 64 PRF bytes of proof p's draw as the interleaved halves of state words 0..7 ([word][half]).
+// MASKED (a batch whose last refill took a mask, live.mask: one byte per slot, 0 or 1): the group's verify() call runs over its
+// live slots in slot order, holes skipped.  The group is walked in windows of 64 slots: each lane loads its slot's byte, a ballot
+// gives the window's live lanes and a prefix popcount every live lane's rank among them; the absorbing loop stages the live slots'
+// bytes at their ranks and runs over the popcount, the draw loop walks the ballot word bit by bit, wave-uniformly, and stores draw j
+// to the row of the j-th live slot.  No rank is kept in memory; a window without a live slot costs its one load and ballot.
+template <bool MASKED = false>
 __global__ void __launch_bounds__(64) k_weight_chain(const uint8_t *__restrict__ rng, const uint32_t *__restrict__ group_first, uint32_t G,
                                                      const Strobe *__restrict__ t0, uint32_t *__restrict__ wide,
-                                                     const uint32_t *__restrict__ live = nullptr) {
+                                                     const LiveView live = LiveView{nullptr, nullptr}) {
   const uint32_t g = blockIdx.x, lane = threadIdx.x;
   if (g >= G) return;
-  // live (null: every proof): the batch's live count.  The group's verify() call runs over its live proofs alone, so the chain
+  // live.count (null: every proof): the batch's live count.  The group's verify() call runs over its live proofs alone, so the chain
   // absorbs and draws n = min(p1, live) - p0 of them: the reference's chain of a batch cut short.  A group without a live proof
   // leaves here, as one wavefront, before anything is synchronised, and never touches `wide`.
-  const uint32_t p0 = group_first[g];
-  const uint32_t n = verdict_group_live(p0, group_first[g + 1], live ? *live : BPP_VERDICT_ALL_LIVE);
+  const uint32_t p0 = group_first[g], p1 = group_first[g + 1];
+  const uint32_t n = MASKED ? verdict_group_live_wave(live.mask, p0, p1, lane)
+                            : verdict_group_live(p0, p1, live.count ? *live.count : BPP_VERDICT_ALL_LIVE);
   if (n == 0) return;
   __shared__ ChainLds L;
   const WkLanes W = wk_lanes(L.img);
@@ -121,14 +130,32 @@ __global__ void __launch_bounds__(64) k_weight_chain(const uint8_t *__restrict__
 #pragma unroll
   for (int q = 0; q < 13; q++) my_const = (q == (int)k) ? rec_const[q] : my_const;
   uint8_t *bb = (uint8_t *)L.blk;
-  for (uint32_t i0 = 0; i0 < n; i0 += BPP_CHAIN_STAGE) {
-    const uint32_t cnt = n - i0 < BPP_CHAIN_STAGE ? n - i0 : BPP_CHAIN_STAGE;
-    ws_sync();
-    if (lane < cnt) {
-      const uint4 *src = reinterpret_cast<const uint4 *>(rng + (size_t)(p0 + i0 + lane) * 32);
-      uint4 *dst = reinterpret_cast<uint4 *>(L.stage + lane * 32);
-      dst[0] = src[0];
-      dst[1] = src[1];
+  // (i0: the proof's index in the group; MASKED: the slot's offset in the group, a window of BPP_CHAIN_STAGE = 64 slots per turn)
+  for (uint32_t i0 = 0; MASKED ? i0 < p1 - p0 : i0 < n; i0 += BPP_CHAIN_STAGE) {
+    uint32_t cnt;
+    if constexpr (MASKED) {
+      const uint32_t p = p0 + i0 + lane;
+      const bool lv = p < p1 && live.mask[p] != 0;
+      const unsigned long long window = __ballot(lv);
+      cnt = (uint32_t)__popcll(window);
+      if (cnt == 0) continue;  // (uniform) nothing staged
+      ws_sync();
+      if (lv) {
+        const uint32_t rank = (uint32_t)__popcll(window & ((1ull << lane) - 1ull));
+        const uint4 *src = reinterpret_cast<const uint4 *>(rng + (size_t)p * 32);
+        uint4 *dst = reinterpret_cast<uint4 *>(L.stage + rank * 32);
+        dst[0] = src[0];
+        dst[1] = src[1];
+      }
+    } else {
+      cnt = n - i0 < BPP_CHAIN_STAGE ? n - i0 : BPP_CHAIN_STAGE;
+      ws_sync();
+      if (lane < cnt) {
+        const uint4 *src = reinterpret_cast<const uint4 *>(rng + (size_t)(p0 + i0 + lane) * 32);
+        uint4 *dst = reinterpret_cast<uint4 *>(L.stage + lane * 32);
+        dst[0] = src[0];
+        dst[1] = src[1];
+      }
     }
     ws_sync();
     for (uint32_t j = 0; j < cnt; j++) {
@@ -164,24 +191,47 @@ __global__ void __launch_bounds__(64) k_weight_chain(const uint8_t *__restrict__
   const uint32_t c_first = draw_const(32), c_next = draw_const(64);
   const bool out_lane = W.word < 8;
   uint32_t *dst = wide + (size_t)p0 * 16 + (out_lane ? W.word * 2 + W.half : 0);
-  for (uint32_t i = 0; i < n; i++) {
-    s.a ^= i == 0 ? c_first : c_next;
-    s.a = wk_keccak_f1600(s.a, W, R);
-    if (out_lane) {
-      dst[(size_t)i * 16] = s.a;
-      s.a = 0;
+  if constexpr (MASKED) {
+    // the same windows again: draw j goes to the row of the j-th live slot
+    bool first = true;
+    for (uint32_t i0 = 0; i0 < p1 - p0; i0 += BPP_CHAIN_STAGE) {
+      const uint32_t p = p0 + i0 + lane;
+      unsigned long long window = __ballot(p < p1 && live.mask[p] != 0);
+      while (window) {  // (uniform over the wavefront)
+        const uint32_t slot = i0 + (uint32_t)(__ffsll(window) - 1);
+        window &= window - 1ull;
+        s.a ^= first ? c_first : c_next;
+        first = false;
+        s.a = wk_keccak_f1600(s.a, W, R);
+        if (out_lane) {
+          dst[(size_t)slot * 16] = s.a;
+          s.a = 0;
+        }
+      }
+    }
+  } else {
+    for (uint32_t i = 0; i < n; i++) {
+      s.a ^= i == 0 ? c_first : c_next;
+      s.a = wk_keccak_f1600(s.a, W, R);
+      if (out_lane) {
+        dst[(size_t)i * 16] = s.a;
+        s.a = 0;
+      }
     }
   }
 }
 
 // wide -> weights: Scalar::from_bytes_mod_order_wide of every draw, canonical bytes out; *zero_flag = 1 if any weight is zero
 // (test_zero: proof index + 1 whose weight is REPORTED as zero, for the tests of the fall-back; 0 = none)
+// MASKED: live.mask[p] says whether slot p is live, in place of the count word.
+template <bool MASKED = false>
 __global__ void __launch_bounds__(64) k_chain_finish(const uint32_t *__restrict__ wide, uint32_t B, uint8_t *__restrict__ weights,
                                                      uint32_t *__restrict__ zero_flag, uint32_t test_zero,
-                                                     const uint32_t *__restrict__ live = nullptr) {
+                                                     const LiveView live = LiveView{nullptr, nullptr}) {
   const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= B) return;
-  if (live && !verdict_item_live(p, *live)) {  // a dead slot: weight zero, no flag; the chain never wrote its `wide` row
+  // a dead slot: weight zero, no flag; the chain never wrote its `wide` row
+  if (MASKED ? live.mask[p] == 0 : (live.count && !verdict_item_live(p, *live.count))) {
     uint4 *dead = reinterpret_cast<uint4 *>(weights + (size_t)p * 32);
     dead[0] = dead[1] = make_uint4(0, 0, 0, 0);
     return;

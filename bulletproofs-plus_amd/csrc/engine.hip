@@ -427,6 +427,15 @@ struct Batch {
   DevBuf<uint32_t> refill_live;
   bool has_live = false;
   const uint32_t *live_word() const { return has_live ? (const uint32_t *)refill_live.p : (const uint32_t *)nullptr; }
+  // bpp_batch_refill_enqueue_live: the batch's own normalised mask, N bytes, allocated by the first refill that takes a mask and
+  // written by k_refill_packed<true>.  mask_form: the batch's LAST refill took a mask -- the chain and verdict kernels then run in
+  // their MASKED forms on these bytes and get no count word; a plain or count refill afterwards drops the form (the bytes go stale
+  // and are not read).  Freed with the batch; it holds no secret.
+  DevBuf<uint8_t> refill_mask;
+  bool mask_form = false;
+  LiveView live_view() const {
+    return mask_form ? LiveView{nullptr, (const uint8_t *)refill_mask.p} : LiveView{live_word(), (const uint8_t *)nullptr};
+  }
   bool enq_weights = false;  // b.weights holds the weights of the batch's last enqueue (bpp_enqueue_weights)
 };
 // what the blocking verify entry points, the sharded and phased forms and the traces answer for a refilled batch: they decide by the
@@ -2345,10 +2354,16 @@ void enqueue_device_chain(bpp_ctx *ctx, Batch &b, hipStream_t st, uint32_t *zero
   b.chain_wide.alloc((size_t)b.B * 16);
   if (!zero_word) ctx->h_chain_zero[0] = 0;
   const uint32_t test_zero = ctx->opt.chain_test_zero > 0 ? (uint32_t)ctx->opt.chain_test_zero : 0u;
-  hipLaunchKernelGGL(k_weight_chain, dim3(b.G), dim3(64), 0, st, b.rng_out.p, b.group_first.p, b.G, ctx->d_chain_t0.p, b.chain_wide.p,
-                     b.live_word());  // (non-null only for a batch refilled with a count, which takes enqueued calls alone)
-  hipLaunchKernelGGL(k_chain_finish, dim3(cdiv(b.B, 64)), dim3(64), 0, st, b.chain_wide.p, b.B, b.weights.p,
-                     zero_word ? zero_word : ctx->h_chain_zero.dev(), test_zero, b.live_word());
+  // (the view is non-null only for a batch refilled with a count or under a mask, which takes enqueued calls alone)
+  const LiveView lv = b.live_view();
+  uint32_t *zero_dst = zero_word ? zero_word : ctx->h_chain_zero.dev();
+  if (lv.mask) {
+    hipLaunchKernelGGL(k_weight_chain<true>, dim3(b.G), dim3(64), 0, st, b.rng_out.p, b.group_first.p, b.G, ctx->d_chain_t0.p, b.chain_wide.p, lv);
+    hipLaunchKernelGGL(k_chain_finish<true>, dim3(cdiv(b.B, 64)), dim3(64), 0, st, b.chain_wide.p, b.B, b.weights.p, zero_dst, test_zero, lv);
+  } else {
+    hipLaunchKernelGGL(k_weight_chain<false>, dim3(b.G), dim3(64), 0, st, b.rng_out.p, b.group_first.p, b.G, ctx->d_chain_t0.p, b.chain_wide.p, lv);
+    hipLaunchKernelGGL(k_chain_finish<false>, dim3(cdiv(b.B, 64)), dim3(64), 0, st, b.chain_wide.p, b.B, b.weights.p, zero_dst, test_zero, lv);
+  }
   ctx->device_chain_calls++;
 }
 
@@ -3417,15 +3432,25 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
         b.have_trace = true;
       }
     }
-    hipLaunchKernelGGL(k_verdict_scan, dim3(cdiv(b.B, BPP_VERDICT_BLOCK)), dim3(BPP_VERDICT_BLOCK), 0, s, b.status.p, b.status0.p,
-                       b.d_rounds_bad.p ? (const uint8_t *)b.d_rounds_bad.p : (const uint8_t *)nullptr,
-                       b.d_defer.p ? (const uint8_t *)b.d_defer.p : (const uint8_t *)nullptr, b.B, b.group_first.p, G, keys, b.live_word());
+    const LiveView lv = b.live_view();  // the form of the batch's last refill: a count word, mask bytes (the MASKED kernels), or neither
+    const uint8_t *rounds_bad = b.d_rounds_bad.p ? (const uint8_t *)b.d_rounds_bad.p : (const uint8_t *)nullptr;
+    const uint8_t *defer = b.d_defer.p ? (const uint8_t *)b.d_defer.p : (const uint8_t *)nullptr;
+    if (lv.mask)
+      hipLaunchKernelGGL(k_verdict_scan<true>, dim3(cdiv(b.B, BPP_VERDICT_BLOCK)), dim3(BPP_VERDICT_BLOCK), 0, s, b.status.p, b.status0.p,
+                         rounds_bad, defer, b.B, b.group_first.p, G, keys, lv);
+    else
+      hipLaunchKernelGGL(k_verdict_scan<false>, dim3(cdiv(b.B, BPP_VERDICT_BLOCK)), dim3(BPP_VERDICT_BLOCK), 0, s, b.status.p, b.status0.p,
+                         rounds_bad, defer, b.B, b.group_first.p, G, keys, lv);
     b.status_clean = true;  // (in stream order, as behind k_results_out)
-    hipLaunchKernelGGL(k_verdict_finish, dim3(G), dim3(64), 0, s, keys, want_msm ? b.msm.is_identity.p : (const uint32_t *)nullptr, actions_dev,
-                       action_all, zero_word, zero_word + 1, b.group_first.p, G, b.d_desc.p,
-                       want_masks ? (const uint4 *)b.masks.p : (const uint4 *)nullptr, (uint32_t)(P.t * 2), verdicts_dev, (uint4 *)masks_dev,
-                       mask_present_dev, b.refill_state.p ? (const unsigned long long *)b.refill_state.p : (const unsigned long long *)nullptr,
-                       b.live_word());
+    const uint32_t *identity = want_msm ? b.msm.is_identity.p : (const uint32_t *)nullptr;
+    const uint4 *mask_rows = want_masks ? (const uint4 *)b.masks.p : (const uint4 *)nullptr;
+    const unsigned long long *state = b.refill_state.p ? (const unsigned long long *)b.refill_state.p : (const unsigned long long *)nullptr;
+    if (lv.mask)
+      hipLaunchKernelGGL(k_verdict_finish<true>, dim3(G), dim3(64), 0, s, keys, identity, actions_dev, action_all, zero_word, zero_word + 1,
+                         b.group_first.p, G, b.d_desc.p, mask_rows, (uint32_t)(P.t * 2), verdicts_dev, (uint4 *)masks_dev, mask_present_dev, state, lv);
+    else
+      hipLaunchKernelGGL(k_verdict_finish<false>, dim3(G), dim3(64), 0, s, keys, identity, actions_dev, action_all, zero_word, zero_word + 1,
+                         b.group_first.p, G, b.d_desc.p, mask_rows, (uint32_t)(P.t * 2), verdicts_dev, (uint4 *)masks_dev, mask_present_dev, state, lv);
     HIP_CHECK(hipGetLastError());
     const uint64_t t = ctx->enq_next++;
     HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));
@@ -3445,8 +3470,11 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
 // An enqueue in flight on the batch is in front of it on the stream, side stream included: every enqueue ends with the main stream
 // waiting for ev_join; the next enqueue's side-stream decompression waits for an ev_fork recorded behind the refill.  The action slots
 // and the layout are the shape's and stay.
-int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in, const uint32_t *count_dev, bpp_device_refill *record_dev,
-                        uint64_t *ticket) {
+// count_dev and live_dev (at most one of them): the count form and the mask form of the refill.  The batch is in the form of its last
+// refill: a mask refill switches the chain and verdict kernels to their MASKED forms on the batch's own copy of the mask, any other
+// refill switches them back.
+int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in, const uint32_t *count_dev, const uint8_t *live_dev,
+                        bpp_device_refill *record_dev, uint64_t *ticket) {
   try {
     auto it = ctx->batches.find(batch);
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
@@ -3477,7 +3505,7 @@ int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in
       const void *p;
     } arrays[] = {{"proofs", in->proofs},           {"commitments32", in->commitments32}, {"min_values", in->min_values},
                   {"min_present", in->min_present}, {"seed_nonces32", in->seed_nonces32}, {"seed_present", in->seed_present},
-                  {"record_dev", record_dev},       {"count_dev", count_dev}};
+                  {"record_dev", record_dev},       {"count_dev", count_dev},             {"live_dev", live_dev}};
     for (const auto &a : arrays) {
       if (!a.p) continue;
       const int kind = device_pointer_kind(ctx->device, a.p);
@@ -3494,6 +3522,7 @@ int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in
       throw EngineError{BPP_ERR_ENGINE, "refill: the batch's buffers do not fit its recorded shape"};
     hipStream_t s = ctx->stream;
     struct bpp_refill_stats &rs = ctx->refill_stats;
+    bool first = false;
     if (!b.refill_red.p) {  // the first refill of this batch: its few device words, and d_defer where no enqueue made it
       b.refill_red.alloc(BPP_REFILL_RED_WORDS);
       b.refill_state.alloc(1);
@@ -3501,22 +3530,32 @@ int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in
       b.d_defer.alloc(n);
       HIP_CHECK(hipMemsetAsync(b.refill_red.p, 0, BPP_REFILL_RED_WORDS * 4, s));
       HIP_CHECK(hipMemsetAsync(b.refill_state.p, 0, 8, s));
-      rs.first_calls++;
+      first = true;
     }
+    if (live_dev && !b.refill_mask.p) {  // the first refill of this batch under a mask: its N bytes, written by the kernel below
+      b.refill_mask.alloc(n);
+      first = true;
+    }
+    if (first) rs.first_calls++;
     if (ctx->enq_events.empty()) {  // (the context's first ticket)
       ctx->enq_events.resize(64);
       for (auto &e : ctx->enq_events) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     const ParamShape shape_p{P.n_bits, P.m_max, P.t};
     const RefillPacked r = refill_args(*in, shape_p, (uint8_t)sh.t0, b.bytes.p, b.minvals.p, b.seeds.p, b.d_defer.p, b.d_desc.p, b.status0.p,
-                                       b.status.p, reinterpret_cast<uint32_t *>(b.masks.p), b.refill_red.p, count_dev);
+                                       b.status.p, reinterpret_cast<uint32_t *>(b.masks.p), b.refill_red.p, count_dev, live_dev,
+                                       b.refill_mask.p);
     if (count_dev) b.has_live = true;
+    b.mask_form = live_dev != nullptr;
     b.enq_weights = false;
     b.refilled = true;  // from here on the contents are the stream's, whatever becomes of the launches
     b.seeds_dirty = sh.nonces;
-    hipLaunchKernelGGL(k_refill_packed, dim3((uint32_t)cdiv((uint32_t)n, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, r);
+    const dim3 refill_grid((uint32_t)cdiv((uint32_t)n, BPP_INGEST_BLOCK / BPP_INGEST_LANES));
+    if (b.mask_form) hipLaunchKernelGGL(k_refill_packed<true>, refill_grid, dim3(BPP_INGEST_BLOCK), 0, s, r);
+    else hipLaunchKernelGGL(k_refill_packed<false>, refill_grid, dim3(BPP_INGEST_BLOCK), 0, s, r);
+    // (under a mask nothing is clamped and the batch's count word is left alone: the later kernels do not read it in that form)
     hipLaunchKernelGGL(k_refill_finish, dim3(1), dim3(64), 0, s, b.refill_red.p, b.refill_state.p, record_dev, count_dev, (uint32_t)n,
-                       b.has_live ? b.refill_live.p : (uint32_t *)nullptr);
+                       (b.has_live && !b.mask_form) ? b.refill_live.p : (uint32_t *)nullptr);
     // the statements' commitments, decoded as at the end of upload_device: COMMIT_FAIL goes to status0[] and status[]
     hipLaunchKernelGGL(k_decompress, dim3(cdiv(b.sum_m, 64)), dim3(64), 0, s, b.bytes.p, b.src_off.p, b.owner.p, b.idx_commit.p, b.sum_m,
                        b.dynpts.p, b.status0.p, (uint32_t *)nullptr, b.status.p);
@@ -3616,13 +3655,19 @@ int bpp_verdict_result(const bpp_device_verdict *host_copy, bpp_shard_result *ou
 // (no gate, as bpp_verify_enqueue)
 int bpp_batch_refill_enqueue(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev, bpp_device_refill *record_dev, uint64_t *ticket) {
   BPP_ENTRY(ctx);
-  return batch_refill_locked(ctx, batch, in_dev, nullptr, record_dev, ticket);
+  return batch_refill_locked(ctx, batch, in_dev, nullptr, nullptr, record_dev, ticket);
 }
 
 int bpp_batch_refill_enqueue_count(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev, const uint32_t *count_dev,
                                    bpp_device_refill *record_dev, uint64_t *ticket) {
   BPP_ENTRY(ctx);
-  return batch_refill_locked(ctx, batch, in_dev, count_dev, record_dev, ticket);
+  return batch_refill_locked(ctx, batch, in_dev, count_dev, nullptr, record_dev, ticket);
+}
+
+int bpp_batch_refill_enqueue_live(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev, const uint8_t *live_dev,
+                                  bpp_device_refill *record_dev, uint64_t *ticket) {
+  BPP_ENTRY(ctx);
+  return batch_refill_locked(ctx, batch, in_dev, nullptr, live_dev, record_dev, ticket);
 }
 
 // (a diagnostic: one device-to-device copy on the stream behind the batch's last enqueue)

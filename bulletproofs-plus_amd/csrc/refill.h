@@ -21,6 +21,13 @@
 // (chain_dev.h) and the verdict kernels (verdict.h) read afterwards; every other kernel runs over all slots, and a dead proof
 // contributes nothing because its weight is zero.  A count beyond the batch makes nothing live and sets BPP_REFILL_COUNT.
 //
+// THE LIVE MASK (bpp_batch_refill_enqueue_live) -- liveness per item instead of per prefix: N bytes in device memory, read here on
+// the stream, one load per item by the item's first lane; any non-zero byte is live.  A dead item is treated exactly as the count
+// form's: not checked, not read, its slot sanitised by the same broadcast decision.  The first lane also writes the normalised byte
+// (0 or 1) to the batch's own mask, which is what the chains and the verdict kernels read afterwards (their MASKED forms); the
+// caller's array is not looked at again.  A mask refill carries no count: k_refill_finish gets null for both count pointers,
+// clamps nothing and leaves the batch's count word alone.
+//
 // Shared by the kernels, by the engine's driver (engine.hip: batch_refill_locked) and by the sanitizer harness (hosttest_refill.cpp),
 // which runs the one-lane model refill_run_host against ingest_run_host + ingest_finish_plan.
 #pragma once
@@ -49,12 +56,20 @@ struct RefillPacked {
   uint32_t mask_row_words;
   uint32_t *red;          // BPP_REFILL_RED_WORDS
   const uint32_t *count;  // one word, read when the kernel runs: the live count c; null: every item (bpp_batch_refill_enqueue_count)
+  const uint8_t *mask;    // n bytes, read when the kernel runs: item i is live when mask[i] != 0; null: no mask (bpp_batch_refill_enqueue_live)
+  uint8_t *mask_out;      // n bytes of the batch: the normalised mask, written with a mask only
 };
 
 // the live count as the batch keeps it: c clamped -- a count beyond the batch makes nothing live (BPP_REFILL_COUNT)
 BPP_HD uint32_t refill_live(uint32_t count, uint32_t n_items) { return count <= n_items ? count : 0u; }
 // is item i of the caller's arrays live: i < min(count, N) and count <= N
 BPP_HD bool refill_item_live(size_t i, uint32_t count, uint32_t n_items) { return count <= n_items && i < (size_t)count; }
+// ... under a mask, by the item's first lane: the one load of the item's byte, and the normalised byte to the batch's own mask
+BPP_HD bool refill_item_live_mask(const RefillPacked &r, size_t i) {
+  const bool lv = r.mask[i] != 0;
+  r.mask_out[i] = lv ? 1 : 0;
+  return lv;
+}
 
 // the decision for item i, by its first lane: BPP_REFILL_ITEM_* bits, and the item's key for the reduction (0: no finding)
 BPP_HD uint32_t refill_item_check(const RefillPacked &r, size_t i, uint32_t *key_out) {
@@ -127,16 +142,24 @@ BPP_HD bpp_device_refill refill_record(uint32_t finding_word, uint32_t differs, 
 // The live count (r.count, null: every item) is one uniform load per lane: items at and beyond it -- every item when it exceeds the
 // batch -- are DEAD: not checked, so they carry the zero decision too, and the broadcast decision sanitises their slots as it does
 // a refused item's.  Nothing of a dead item's source is read.
+// MASKED (r.mask and r.mask_out set, r.count null): the item's first lane loads the item's mask byte, stores the normalised byte and
+// checks the item only if it is live; liveness reaches the item's 16 lanes inside the broadcast decision, which is zero for a dead
+// item.
+template <bool MASKED = false>
 __global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_refill_packed(RefillPacked r) {
   const size_t gid = (size_t)blockIdx.x * BPP_INGEST_BLOCK + threadIdx.x;
   const size_t i = gid / BPP_INGEST_LANES;
   const uint32_t lane = (uint32_t)(gid % BPP_INGEST_LANES);
   const uint32_t n_items = (uint32_t)r.in.n_items;
-  const uint32_t count = r.count ? *r.count : n_items;
   const bool live = i < n_items;  // a slot of the batch
-  const bool live_item = refill_item_live(i, count, n_items);
   uint32_t decision = 0, key = 0;
-  if (live_item && lane == 0) decision = refill_item_check(r, i, &key);
+  if constexpr (MASKED) {
+    if (live && lane == 0 && refill_item_live_mask(r, i)) decision = refill_item_check(r, i, &key);
+  } else {
+    const uint32_t count = r.count ? *r.count : n_items;
+    const bool live_item = refill_item_live(i, count, n_items);
+    if (live_item && lane == 0) decision = refill_item_check(r, i, &key);
+  }
   decision = (uint32_t)__shfl((int)decision, 0, (int)BPP_INGEST_LANES);
   uint32_t bits = 0;
   if (live) bits = refill_item_arrays(r, i, decision, lane, BPP_INGEST_LANES);
@@ -153,6 +176,7 @@ __global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_refill_packed(RefillPacked
 // (may be null) and into the batch's refill-state word, and leaves the reduction words clear for the next refill, so that no
 // memset is ever enqueued between two refills.  count (null: every item) is the caller's word, read here for the last time: the
 // clamped value goes to the batch's own word `live` (null: the batch never took a count), which is what later kernels read.
+// A refill under a mask passes null for both: nothing is clamped and the batch's count word is left alone.
 __global__ void __launch_bounds__(64) k_refill_finish(uint32_t *__restrict__ red, unsigned long long *__restrict__ state,
                                                       bpp_device_refill *__restrict__ record, const uint32_t *__restrict__ count = nullptr,
                                                       uint32_t n_items = 0, uint32_t *__restrict__ live = nullptr) {
@@ -176,7 +200,7 @@ __global__ void __launch_bounds__(64) k_refill_finish(uint32_t *__restrict__ red
 // the kernel's arguments from the caller's struct and the batch's buffers (every pointer an address in device memory)
 inline RefillPacked refill_args(const bpp_packed_batch &pk, const ParamShape &P, uint8_t t0, uint8_t *bytes, uint64_t *minvals, uint8_t *seeds,
                                 uint8_t *defer, ProofDesc *desc, uint32_t *status0, uint32_t *status, uint32_t *masks, uint32_t *red,
-                                const uint32_t *count = nullptr) {
+                                const uint32_t *count = nullptr, const uint8_t *mask = nullptr, uint8_t *mask_out = nullptr) {
   RefillPacked r;
   memset(&r, 0, sizeof(r));
   bpp_packed_batch in = pk;
@@ -192,16 +216,19 @@ inline RefillPacked refill_args(const bpp_packed_batch &pk, const ParamShape &P,
   r.mask_row_words = P.t * 8;
   r.red = red;
   r.count = count;
+  r.mask = mask;
+  r.mask_out = mask ? mask_out : nullptr;
   return r;
 }
 
 // the two kernels on the host, one lane per item, reduced as the kernels reduce: the model hosttest_refill.cpp holds to
 // ingest_run_host + ingest_finish_plan.  `red` is expected clear and is left clear.  `live` (may be null) takes the clamped count.
+// With r.mask the items' liveness is the mask's, r.mask_out takes the normalised bytes, and no count is read or written.
 inline void refill_run_host(const RefillPacked &r, uint64_t *state, bpp_device_refill *record, uint32_t *live = nullptr) {
   const uint32_t n_items = (uint32_t)r.in.n_items;
-  const uint32_t count = r.count ? *r.count : n_items;
+  const uint32_t count = (r.count && !r.mask) ? *r.count : n_items;
   for (size_t i = 0; i < r.in.n_items; i++) {
-    const bool live_item = refill_item_live(i, count, n_items);
+    const bool live_item = r.mask ? refill_item_live_mask(r, i) : refill_item_live(i, count, n_items);
     uint32_t key = 0;
     const uint32_t decision = live_item ? refill_item_check(r, i, &key) : 0u;
     const uint32_t bits = refill_item_arrays(r, i, decision, 0, 1);
@@ -209,7 +236,7 @@ inline void refill_run_host(const RefillPacked &r, uint64_t *state, bpp_device_r
     if (key > r.red[BPP_REFILL_RED_FINDING]) r.red[BPP_REFILL_RED_FINDING] = key;
     if (decision & BPP_REFILL_ITEM_FOREIGN) r.red[BPP_REFILL_RED_DIFFERS] |= 1u;
   }
-  if (live) *live = refill_live(count, n_items);
+  if (live && !r.mask) *live = refill_live(count, n_items);
   const bpp_device_refill rec = refill_record(r.red[BPP_REFILL_RED_FINDING], r.red[BPP_REFILL_RED_DIFFERS], count, n_items);
   r.red[BPP_REFILL_RED_FINDING] = r.red[BPP_REFILL_RED_DIFFERS] = 0;
   *state = refill_state_make(rec.flags, rec.code, rec.msg, rec.index);

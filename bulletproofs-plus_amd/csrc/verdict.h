@@ -94,6 +94,27 @@ BPP_HD bool verdict_item_live(uint32_t i, uint32_t live) { return i < live; }
 // group [p0, p1): its live length -- the proofs its verify() call runs over; 0: an empty group
 BPP_HD uint32_t verdict_group_live(uint32_t p0, uint32_t p1, uint32_t live) { return p0 >= live ? 0u : (p1 < live ? p1 : live) - p0; }
 
+// ---- liveness per item (bpp_batch_refill_enqueue_live): a batch is in the form of its last refill, and the view names that form
+// alone -- `count`, the batch's count word (a prefix is live), or `mask`, the batch's own normalised copy of the refill's mask,
+// one byte per slot, 0 or 1 (any set of slots is live).  Both null: every item is live.  A live group's verify() call runs over its
+// live slots in slot order; the finding's index stays the slot offset p - p0, which is the slot of the reference's k-th live item.
+struct LiveView {
+  const uint32_t *count;
+  const uint8_t *mask;
+};
+// is item i live
+BPP_HD bool verdict_item_live(const LiveView &v, uint32_t i) {
+  return v.mask ? v.mask[i] != 0 : verdict_item_live(i, v.count ? *v.count : BPP_VERDICT_ALL_LIVE);
+}
+// group [p0, p1): how many live items it holds; 0: an empty group.  (One lane's form: k_verdict_finish and k_weight_chain count a
+// masked group with a ballot per 64 slots.)
+BPP_HD uint32_t verdict_group_live(const LiveView &v, uint32_t p0, uint32_t p1) {
+  if (!v.mask) return verdict_group_live(p0, p1, v.count ? *v.count : BPP_VERDICT_ALL_LIVE);
+  uint32_t n = 0;
+  for (uint32_t p = p0; p < p1; p++) n += v.mask[p] != 0 ? 1u : 0u;
+  return n;
+}
+
 // ---- the refill-state word of a batch (refill.h: k_refill_finish writes it, bpp_batch_refill_enqueue owns it).  Zero: the batch's
 // last refill took, or it was never refilled.  Otherwise bits 0..7 hold the BPP_REFILL_* flags of the refill record, bits 8..15 the
 // message id, bits 16..23 the code as a signed byte, bits 32..63 the index inside the batch.
@@ -162,14 +183,16 @@ inline const char *verdict_message(uint32_t tier, int32_t code) {
 // search; the keys are min-reduced per wavefront with cross-lane operations, group by group for the groups the wavefront touches,
 // and ONE 64-bit atomicMin per (wavefront, group) goes to the group's key word.  A wavefront without a finding issues no atomic and
 // stores nothing but the status reset.
+// MASKED (a batch whose last refill took a mask): live.mask is read, one byte per lane, in place of the count word.
 #define BPP_VERDICT_BLOCK 256u
+template <bool MASKED = false>
 __global__ void __launch_bounds__(BPP_VERDICT_BLOCK) k_verdict_scan(uint32_t *__restrict__ status, const uint32_t *__restrict__ status0,
                                                                     const uint8_t *__restrict__ rounds_bad, const uint8_t *__restrict__ defer,
                                                                     uint32_t B, const uint32_t *__restrict__ group_first, uint32_t G,
                                                                     unsigned long long *__restrict__ keys,
-                                                                    const uint32_t *__restrict__ live = nullptr) {
+                                                                    const LiveView live = LiveView{nullptr, nullptr}) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t lv = live ? *live : BPP_VERDICT_ALL_LIVE;
+  const uint32_t lv = (!MASKED && live.count) ? *live.count : BPP_VERDICT_ALL_LIVE;
   uint32_t st = 0, rb = 0, df = 0;
   if (i < B) {
     st = status[i];
@@ -177,7 +200,7 @@ __global__ void __launch_bounds__(BPP_VERDICT_BLOCK) k_verdict_scan(uint32_t *__
     if (rounds_bad) rb = rounds_bad[i];
     if (defer) df = defer[i];
     // a dead slot is put back like any other and contributes no key, whatever it holds (its sanitised bytes do raise PASS-1 findings)
-    if (!verdict_item_live(i, lv)) st = rb = df = 0;
+    if (MASKED ? live.mask[i] == 0 : !verdict_item_live(i, lv)) st = rb = df = 0;
   }
   uint32_t g = 0;
   uint64_t key = BPP_VERDICT_KEY_NONE;
@@ -212,6 +235,16 @@ __global__ void __launch_bounds__(BPP_VERDICT_BLOCK) k_verdict_scan(uint32_t *__
   }
 }
 
+// a masked group's live items, counted by one wavefront with a ballot per 64 mask bytes (every lane calls it; also k_weight_chain's)
+__device__ __forceinline__ uint32_t verdict_group_live_wave(const uint8_t *__restrict__ mask, uint32_t p0, uint32_t p1, uint32_t lane) {
+  uint32_t n = 0;
+  for (uint32_t w0 = p0; w0 < p1; w0 += 64) {
+    const uint32_t p = w0 + lane;
+    n += (uint32_t)__popcll(__ballot(p < p1 && mask[p] != 0));
+  }
+  return n;
+}
+
 // k_verdict_finish: one wavefront per group.  Lane 0 turns the group's key, its identity flag, its action and the call's
 // zero-weight word into the 16-byte record and puts the key word back to all ones for the next enqueue; the wavefront then
 // hands out the group's mask rows, 16 bytes per lane and turn: the engine's rows for the items that carry a seed nonce when the
@@ -222,8 +255,11 @@ __global__ void __launch_bounds__(BPP_VERDICT_BLOCK) k_verdict_scan(uint32_t *__
 //   masks == nullptr: the call recovered no masks (no group asked, or no item carries a seed nonce)
 //   refill_state == nullptr, or a zero word: the batch's contents are what its last upload or refill made them; otherwise every
 //     group gets the refill's record (verdict_finish above) and no masks
-//   live == nullptr: every item is live; otherwise a group that starts at or beyond *live gets the EMPTY record, and mask rows and
-//     mask_present are handed out below *live only (zeros beyond).  groups_done still reaches G.
+//   live.count == nullptr: every item is live; otherwise a group that starts at or beyond *live.count gets the EMPTY record, and
+//     mask rows and mask_present are handed out below it only (zeros beyond).  groups_done still reaches G.
+//   MASKED: live.mask in place of the count word.  The wavefront counts the group's live slots with a ballot per 64 mask bytes;
+//     a group without one gets the EMPTY record wherever it lies, and rows and mask_present go to live slots only.
+template <bool MASKED = false>
 __global__ void __launch_bounds__(64) k_verdict_finish(unsigned long long *__restrict__ keys, const uint32_t *__restrict__ is_identity,
                                                        const int *__restrict__ actions, int action_all, uint32_t *__restrict__ zero_word,
                                                        uint32_t *__restrict__ groups_done, const uint32_t *__restrict__ group_first,
@@ -231,11 +267,12 @@ __global__ void __launch_bounds__(64) k_verdict_finish(unsigned long long *__res
                                                        uint32_t row_pieces, bpp_device_verdict *__restrict__ verdicts,
                                                        uint4 *__restrict__ masks_out, uint8_t *__restrict__ mask_present,
                                                        const unsigned long long *__restrict__ refill_state = nullptr,
-                                                       const uint32_t *__restrict__ live = nullptr) {
+                                                       const LiveView live = LiveView{nullptr, nullptr}) {
   const uint32_t g = blockIdx.x, lane = threadIdx.x;
   if (g >= G) return;
-  const uint32_t lv = live ? *live : BPP_VERDICT_ALL_LIVE;
+  const uint32_t lv = (!MASKED && live.count) ? *live.count : BPP_VERDICT_ALL_LIVE;
   const uint32_t p0 = group_first[g], p1 = group_first[g + 1];
+  const uint32_t live_len = MASKED ? verdict_group_live_wave(live.mask, p0, p1, lane) : verdict_group_live(p0, p1, lv);
   int give = 0;
   if (lane == 0) {
     const uint64_t key = keys[g];
@@ -243,7 +280,7 @@ __global__ void __launch_bounds__(64) k_verdict_finish(unsigned long long *__res
     const int action = actions ? actions[g] : action_all;
     const bool zero = *zero_word != 0;
     const bpp_device_verdict v = verdict_finish(key, is_identity != nullptr, action, is_identity ? is_identity[g] != 0 : true, zero,
-                                                refill_state ? (uint64_t)*refill_state : 0ull, verdict_group_live(p0, p1, lv));
+                                                refill_state ? (uint64_t)*refill_state : 0ull, live_len);
     *reinterpret_cast<uint4 *>(&verdicts[g]) = make_uint4((uint32_t)v.code, v.tier, v.index, v.flags);
     give = (masks != nullptr && v.tier == BPP_TIER_NONE && !(v.flags & (BPP_VERDICT_REDRAW | BPP_VERDICT_REFILL | BPP_VERDICT_EMPTY)) &&
             action != BPP_VERIFY_ONLY) ? 1 : 0;
@@ -256,12 +293,12 @@ __global__ void __launch_bounds__(64) k_verdict_finish(unsigned long long *__res
   }
   give = __shfl(give, 0, 64);
   if (mask_present)
-    for (uint32_t p = p0 + lane; p < p1; p += 64) mask_present[p] = (give && verdict_item_live(p, lv) && (desc[p].flags & 1u)) ? 1 : 0;
+    for (uint32_t p = p0 + lane; p < p1; p += 64) mask_present[p] = (give && (MASKED ? live.mask[p] != 0 : verdict_item_live(p, lv)) && (desc[p].flags & 1u)) ? 1 : 0;
   if (masks_out) {
     const size_t q0 = (size_t)p0 * row_pieces, q1 = (size_t)p1 * row_pieces;
     for (size_t q = q0 + lane; q < q1; q += 64) {
       const uint32_t p = (uint32_t)(q / row_pieces);
-      masks_out[q] = (give && verdict_item_live(p, lv) && (desc[p].flags & 1u)) ? masks[q] : make_uint4(0, 0, 0, 0);
+      masks_out[q] = (give && (MASKED ? live.mask[p] != 0 : verdict_item_live(p, lv)) && (desc[p].flags & 1u)) ? masks[q] : make_uint4(0, 0, 0, 0);
     }
   }
 }

@@ -706,7 +706,7 @@ class ResidentBatch(api.ResidentBatch):
         api._check(rc, self.engine.ctx)
         return Enqueued(self.engine, ticket.value, G, verdicts, masks, present)
 
-    def refill(self, inp, record=None, count=None):
+    def refill(self, inp, record=None, count=None, live=None):
         """bpp_batch_refill_enqueue: new contents of the same shape for this batch (made with form="device") from the
         DevicePackedInput `inp`, enqueued on the engine's stream; an enqueue() afterwards gives what it would give on a fresh upload
         of those arrays.  Nothing is synchronised here: what wrote the arrays must be ordered before the engine's stream (an engine
@@ -717,9 +717,24 @@ class ResidentBatch(api.ResidentBatch):
         afterwards gives, for every group with a live item, what it gives on a fresh upload of the first `count` items with the
         boundaries clipped; a group without one gets a VERDICT_EMPTY record.  An int goes into a one-word device tensor the batch
         owns (an asynchronous copy on torch's current stream: use an engine made on that stream); a device tensor of one int32 or
-        uint32 word is passed as it is and read when the refill runs on the stream.  None: every item."""
+        uint32 word is passed as it is and read when the refill runs on the stream.  None: every item.
+        `live` (bpp_batch_refill_enqueue_live; not together with `count`): a per-item live mask, a contiguous uint8 device tensor of n
+        bytes (or a raw device address), read when the refill runs on the stream -- byte i non-zero: item i is live.  Dead slots
+        may lie anywhere; an enqueue() afterwards gives, for every group with a live item, what it gives on a fresh upload of the
+        group's live items alone, with `index` a slot offset inside the group, and a VERDICT_EMPTY record for a group without one.
+        The batch keeps its own copy: the tensor may be overwritten as soon as the refill has run.  None: every item."""
         import torch
+        if live is not None and count is not None:
+            raise api.ProofError(api.ProofErrorKind.InvalidArgument, "count and live: a refill takes a live count or a live mask, not both")
         dev = torch.device("cuda", int(self.engine.device))
+        live_addr = None
+        if live is not None and hasattr(live, "data_ptr"):
+            if live.dtype != torch.uint8 or live.numel() != self.n or not live.is_contiguous():
+                raise api.ProofError(api.ProofErrorKind.InvalidArgument, "live: a contiguous uint8 tensor of n bytes expected")
+            live_addr = ctypes.c_void_p(live.data_ptr())
+            self._live_arg = live  # (stays alive until the refill has run)
+        elif live is not None:
+            live_addr = ctypes.c_void_p(int(live))
         count_addr = None
         if count is not None and hasattr(count, "data_ptr"):
             if count.dtype not in (torch.int32, torch.uint32) or count.numel() != 1:
@@ -753,7 +768,9 @@ class ResidentBatch(api.ResidentBatch):
         st = _lib.PackedBatch.from_buffer_copy(inp.struct)
         st.transcript_state, st.transcript_label, st.label_len = None, None, 0
         ticket = c_uint64()
-        if count_addr is None:
+        if live_addr is not None:
+            rc = self.engine.lib.bpp_batch_refill_enqueue_live(self.engine.ctx, self.handle, byref(st), live_addr, addr, byref(ticket))
+        elif count_addr is None:
             rc = self.engine.lib.bpp_batch_refill_enqueue(self.engine.ctx, self.handle, byref(st), addr, byref(ticket))
         else:
             rc = self.engine.lib.bpp_batch_refill_enqueue_count(self.engine.ctx, self.handle, byref(st), count_addr, addr, byref(ticket))

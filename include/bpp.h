@@ -602,6 +602,34 @@ int bpp_refill_stats(bpp_ctx *ctx, struct bpp_refill_stats *out);
 int bpp_batch_refill_enqueue_count(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev,
                                    const uint32_t *count_dev /* one word in device memory; NULL: every item */,
                                    bpp_device_refill *record_dev /* may be NULL */, uint64_t *ticket /* may be NULL */);
+/* ---- a refill under a per-item live mask ----
+ * bpp_batch_refill_enqueue_live is bpp_batch_refill_enqueue with a LIVE MASK that is read ON THE STREAM, when the refill kernel runs:
+ * `live_dev` is N bytes in BPP_PTR_THIS_DEVICE memory (anything else is refused before any launch, the field named) and the host
+ * never learns it.  Byte i non-zero means item i is live; any non-zero value counts.  The refill copies the NORMALISED mask (0 / 1)
+ * into a buffer of the batch's own; later kernels read that copy and never the caller's array, which may be overwritten as soon as
+ * the refill has run.  `in_dev` keeps the batch's shape exactly, as for the count form.  live_dev == NULL is
+ * bpp_batch_refill_enqueue: the same launches and the same bytes.
+ * DEAD ITEMS (byte zero) are neither checked (a non-canonical scalar, a foreign first byte, a missing nonce there is neither a finding
+ * nor a fall-back) nor read; their slots are sanitised exactly as the count form's dead slots are: the batch's first byte and zeros,
+ * zero commitments, no promise, no nonce, mask rows wiped.  The refill record's `index` for a construction finding stays the item's
+ * index inside the batch, which is its slot.
+ * After such a refill a bpp_verify_enqueue with boundaries group_first gives, with S_g the live slots of group g in slot order:
+ *   S_g not empty: what a fresh bpp_batch_upload_packed_device of the items of S_g ALONE, in slot order, gives for them verified as
+ *     one group: code, tier and flags are equal, the weight transcript absorbs and draws those proofs alone in that order.  `index`
+ *     is a SLOT OFFSET inside the group, p - p0 of the proof that raised the finding: the slot of the fresh upload's k-th item,
+ *     so a consumer finds the proof without a prefix sum.
+ *   S_g empty: {0, BPP_TIER_NONE, 0, BPP_VERDICT_WRITTEN | BPP_VERDICT_EMPTY}, wherever the group lies -- also before live groups.
+ *   masks_dev rows and mask_present_dev bytes sit at their slots, as always: live slots carry the fresh upload's, dead slots zeros.
+ *   BPP_VERDICT_REDRAW is raised by a zero weight of a live item only.  bpp_enqueue_weights gives the fresh upload's weights at
+ *     the live slots and 32 zero bytes at dead ones.
+ * FORM: a batch is in the form of its last refill -- plain, count or mask.  A count refill after a mask refill drops the mask, and
+ * the other way round.  A batch that never took a mask allocates nothing for one; the first mask refill of a batch allocates its N
+ * bytes (counted under first_calls).  STEADY STATE, refused-before-launch rules, stream ownership, secrets and tickets are those of
+ * bpp_batch_refill_enqueue: host_waits stays 0, and a later bpp_verify_enqueue plans nothing again (layouts_in_call does not move).
+ * COST: a dead slot still passes through the per-proof kernels with weight zero and costs what a live one does. */
+int bpp_batch_refill_enqueue_live(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev,
+                                  const uint8_t *live_dev /* N bytes in device memory; NULL: every item */,
+                                  bpp_device_refill *record_dev /* may be NULL */, uint64_t *ticket /* may be NULL */);
 /* A diagnostic: enqueues a device-to-device copy of the batch weights that the batch's last enqueued verification used, N x 32
  * canonical bytes, into weights_dev (BPP_PTR_THIS_DEVICE memory); dead slots hold 32 zero bytes.  Allocates nothing and does not
  * wait.  BPP_ERR_INVALID_ARGUMENT for a batch whose last call on the stream was not an enqueue that drew weights. */

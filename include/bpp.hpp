@@ -191,6 +191,16 @@ class Engine {
     check(rc, bpp_ctx_last_error(ctx_));
     return t;
   }
+  // ... under a per-item live mask read on the stream (bpp_batch_refill_enqueue_live): live_dev is n bytes in device memory, non-zero
+  // means live, null means every item.  Dead slots may lie anywhere; a group without a live item gets a BPP_VERDICT_EMPTY record,
+  // and a finding's index is the slot offset inside its group.
+  EnqueueTicket batch_refill_enqueue_live(uint64_t batch, const bpp_packed_batch &in_dev, const uint8_t *live_dev, bpp_device_refill *record_dev) {
+    EnqueueTicket t;
+    t.ctx_ = ctx_;
+    const int rc = bpp_batch_refill_enqueue_live(ctx_, batch, &in_dev, live_dev, record_dev, &t.id);
+    check(rc, bpp_ctx_last_error(ctx_));
+    return t;
+  }
   // A diagnostic: the weights of the batch's last enqueued verification, n x 32 bytes into device memory, in stream order
   // (bpp_enqueue_weights); dead slots hold zeros.
   EnqueueTicket enqueue_weights(uint64_t batch, uint8_t *weights_dev) {

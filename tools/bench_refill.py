@@ -10,6 +10,13 @@ warmed up, as tools/gpu_ab.py alternates its arms:
   refill_count_K   (one per --count K, any number of them) per step bpp_batch_refill_enqueue_count with the live count K in a device
            word and bpp_verify_enqueue on a batch of its own: what a step costs when N - K of its slots are dead.  A dead slot passes
            through the per-proof kernels with weight zero, so these arms state a cost; they are not there to meet a bar.
+  refill_live_D    (one per --live D, a density in [0, 1]) per step bpp_batch_refill_enqueue_live under a random mask with exactly
+           L = round(D * 1024) live slots, a different mask for every input set of the ring, on a batch of its own; every --live D also
+           adds the arm refill_count_L, the count form at the same number of live items, so that the two alternate in this process.
+           Neither skips dead slots; the mask form's extra work is a byte per slot in four kernels and a ballot per 64 slots in the
+           weight chain.  The last line states, per density, both arms' time per step over the repetitions and whether the mask arm's
+           median lies inside the count arm's own spread (its lowest to its highest repetition).  Without --out the rows go to
+           profiles/refill_live.json.
 
 Per (arm, repetition) one JSON line: steps/s over a window that ends in a device synchronise, process CPU seconds per step, host time
 of the step's calls (median).  In a pass of its own (not inside the timed window) every step's ingest part is bracketed by events on
@@ -44,8 +51,17 @@ def main():
     ap.add_argument("--event-steps", type=int, default=40)
     ap.add_argument("--kernel-stats", default="", help="a rocprofv3 kernel_stats.csv of a run of this program")
     ap.add_argument("--count", type=int, action="append", default=[], help="add an arm that refills with this live count (repeatable)")
+    ap.add_argument("--live", type=float, action="append", default=[], help="add an arm that refills under a random mask of this density, and the count arm of as many live items (repeatable)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.live and not args.out:
+        args.out = os.path.join(ROOT, "profiles", "refill_live.json")
+    live_counts = {D: int(round(D * N)) for D in args.live}
+    for D, L in live_counts.items():
+        if not 0 <= L <= N:
+            raise SystemExit("--live %s: a density in [0, 1] expected" % D)
+        if L not in args.count:
+            args.count.append(L)
     import numpy as np
     import torch
     import bench
@@ -124,6 +140,28 @@ def main():
                 enqueue(rb.handle, k)
 
             counted["refill_count_%d" % K] = (K, rb, word, step_count)
+        masked = {}
+        for D, L in live_counts.items():  # one batch per arm and one mask per input set, each with exactly L live slots
+            rb = packed.ResidentBatch(params, ring[0], None, None, None, None, LABEL, form="device")
+            gen = np.random.default_rng(int(D * 1e6) + 17)
+            host_masks = []
+            for _k in range(RING):
+                mk = np.zeros(N, dtype=np.uint8)
+                mk[gen.permutation(N)[:L]] = 1
+                host_masks.append(mk)
+            dev_masks = [torch.from_numpy(mk).cuda() for mk in host_masks]
+
+            def step_live(k, mark=None, rb=rb, dev_masks=dev_masks):
+                if mark:
+                    mark[0].record(stream)
+                rc = lib.bpp_batch_refill_enqueue_live(ctx, rb.handle, ctypes.byref(bare[k]), ctypes.c_void_p(dev_masks[k].data_ptr()),
+                                                       ctypes.c_void_p(records[k].data_ptr()), None)
+                packed.api._check(rc, ctx)
+                if mark:
+                    mark[1].record(stream)
+                enqueue(rb.handle, k)
+
+            masked["refill_live_%g" % D] = (L, rb, host_masks, dev_masks, step_live)
         torch.cuda.synchronize()
         # ---- the refill arm's verdicts against the upload arm's, every input set (this is also the first warm-up)
         seen = {}
@@ -141,6 +179,17 @@ def main():
             got = [v.cpu().tolist()[0] for v in verdicts]
             want = [[0, 0, 0, 1 if 0 < K <= N else (9 if K == 0 else 5)] for _ in range(RING)]
             if 77 < K <= N:
+                want[2] = [1, 7, 0, 1]
+            if got != want:
+                raise SystemExit("%s: verdicts %s, expected %s" % (arm, got, want))
+            arms[arm] = step
+        for arm, (L, rb, host_masks, _dev_masks, step) in masked.items():  # the tampered proof is item 77 of set 2: live or not
+            for k in range(RING):
+                step(k)
+            torch.cuda.synchronize()
+            got = [v.cpu().tolist()[0] for v in verdicts]
+            want = [[0, 0, 0, 1 if L else 9] for _ in range(RING)]
+            if host_masks[2][77]:
                 want[2] = [1, 7, 0, 1]
             if got != want:
                 raise SystemExit("%s: verdicts %s, expected %s" % (arm, got, want))
@@ -185,8 +234,19 @@ def main():
                 spans.append(mark[0].elapsed_time(mark[1]))
             emit({"arm": arm, "ingest_span_ms_median": round(statistics.median(spans), 4), "ingest_span_ms_min": round(min(spans), 4),
                   "what": "events around bpp_batch_upload_packed_device" if arm == "upload" else "events around bpp_batch_refill_enqueue"})
+        # ---- the mask form against the count form at the same number of live items: is it inside the count arm's own spread
+        for arm, (L, _rb, _hm, _dm, _step) in masked.items():
+            mine = [r["ms_per_step"] for r in rows if r.get("arm") == arm and "ms_per_step" in r]
+            theirs = [r["ms_per_step"] for r in rows if r.get("arm") == "refill_count_%d" % L and "ms_per_step" in r]
+            if mine and theirs:
+                emit({"live_against_count": arm, "live_items": L, "count_arm": "refill_count_%d" % L,
+                      "live_ms_per_step": mine, "count_ms_per_step": theirs, "live_ms_per_step_median": round(statistics.median(mine), 4),
+                      "count_ms_per_step_median": round(statistics.median(theirs), 4), "count_ms_per_step_spread": [min(theirs), max(theirs)],
+                      "live_median_inside_count_spread": bool(statistics.median(mine) <= max(theirs))})
         resident.close()
         for _K, rb, _word, _step in counted.values():
+            rb.close()
+        for _L, rb, _hm, _dm, _step in masked.values():
             rb.close()
         params.close()
         eng.close()

@@ -15,7 +15,7 @@ Legs (what is run and what the summary shows):
   prover            tools/bench_prover_leg.py (configs[4], one call at a time)  proofs/s, ms per call, MSM event time
   prover-inflight   tools/bench_prove_concurrent.py (1, 2, 4 calls in flight)   proofs/s per number of calls in flight
   latency           tools/bench_latency.py --no-cpu                             median ms per call and size
-  refill            tools/bench_refill.py (upload, refill and any --count arms)  steps/s of every repetition, per arm of that program
+  refill            tools/bench_refill.py (upload, refill, any --count / --live arms)  steps/s of every repetition, per arm of that program
   cmd               the command given with --cmd                                its last line of output
 
 Examples (the A/Bs on record in HISTORY.md, as they would be run today):
