@@ -227,6 +227,22 @@ def build_refill_live_harness(force=False):
     return REFILL_LIVE_SANITIZER_BIN
 
 
+INGEST_MIXED_SANITIZER_BIN = os.path.join(HERE, "hosttest_ingest_mixed_asan")
+
+
+def build_ingest_mixed_harness(force=False):
+    """hosttest_ingest_mixed.cpp (ingest_mixed.h: the one-item routines, the host prelude and the plan of the device form of the mixed
+    upload, held to the item form of upload_host.h over a corpus) under ASan + UBSan: an executable, run by
+    tests/test_ingest_mixed_host.py."""
+    src = os.path.join(CSRC, "hosttest_ingest_mixed.cpp")
+    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
+    if not force and not _stale(INGEST_MIXED_SANITIZER_BIN, deps):
+        return INGEST_MIXED_SANITIZER_BIN
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-fno-omit-frame-pointer", "-o", INGEST_MIXED_SANITIZER_BIN, src], check=True, cwd=CSRC)
+    return INGEST_MIXED_SANITIZER_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     build_hosttest(force="--force" in sys.argv)

@@ -34,6 +34,14 @@ class PackedBatch(Structure):
                 ("transcript_label", c_void_p), ("label_len", c_size_t)]
 
 
+class MixedBatch(Structure):
+    """bpp_mixed_batch: a batch of mixed aggregation factors as arrays of rows"""
+    _fields_ = [("n_items", c_size_t), ("proofs", c_void_p), ("proof_stride", c_size_t), ("proof_lens", c_void_p), ("m", c_void_p),
+                ("m_stride", c_uint32), ("commitments32", c_void_p), ("min_values", c_void_p), ("min_present", c_void_p),
+                ("seed_nonces32", c_void_p), ("seed_present", c_void_p), ("transcript_state", c_void_p),
+                ("transcript_label", c_void_p), ("label_len", c_size_t)]
+
+
 class ShardResult(Structure):
     """bpp_shard_result: outcome of one batch of a sharded wave"""
     _fields_ = [("code", c_int), ("tier", c_int), ("rank", c_int), ("index", c_uint32), ("msg", ctypes.c_char * 160)]
@@ -140,6 +148,11 @@ SYMBOLS = [
     ("bpp_batch_upload_packed_device", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), POINTER(c_uint64), c_void_p, c_size_t]),
     ("bpp_verify_batch_packed_device", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_int, c_size_t, c_void_p, c_void_p,
                                                c_void_p, c_size_t]),
+    ("bpp_batch_upload_mixed", c_int, [c_void_p, c_uint64, POINTER(MixedBatch), POINTER(c_uint64), c_void_p, c_size_t]),
+    ("bpp_verify_batch_mixed", c_int, [c_void_p, c_uint64, POINTER(MixedBatch), c_int, c_size_t, c_void_p, c_void_p, c_void_p, c_size_t]),
+    ("bpp_batch_upload_mixed_device", c_int, [c_void_p, c_uint64, POINTER(MixedBatch), POINTER(c_uint64), c_void_p, c_size_t]),
+    ("bpp_verify_batch_mixed_device", c_int, [c_void_p, c_uint64, POINTER(MixedBatch), c_int, c_size_t, c_void_p, c_void_p, c_void_p,
+                                              c_size_t]),
     ("bpp_device_pointer_check", c_int, [c_void_p, c_void_p, POINTER(c_int)]),
     ("bpp_ingest_stats", c_int, [c_void_p, POINTER(IngestStats)]),
     ("bpp_ctx_pipeline_depth", c_int, [c_void_p, c_uint32]),

@@ -41,6 +41,7 @@
 #include "runtime_host.h"
 #include "upload_host.h"
 #include "ingest.h"
+#include "ingest_mixed.h"
 #include "verdict.h"
 #include "refill.h"
 
@@ -436,6 +437,10 @@ struct Batch {
   LiveView live_view() const {
     return mask_form ? LiveView{nullptr, (const uint8_t *)refill_mask.p} : LiveView{live_word(), (const uint8_t *)nullptr};
   }
+  // bpp_batch_upload_mixed_device on its device path: the per-item table k_ingest_mixed packed the batch by (ingest_mixed.h), kept for
+  // a refill of such a batch, which is not built (the batch is not refillable: its shape is this vector, not four numbers)
+  DevBuf<IngestMixedRow> mixed_table;
+  bool mixed = false;
   bool enq_weights = false;  // b.weights holds the weights of the batch's last enqueue (bpp_enqueue_weights)
 };
 // what the blocking verify entry points, the sharded and phased forms and the traces answer for a refilled batch: they decide by the
@@ -570,6 +575,7 @@ struct bpp_ctx {
   DevBuf<uint8_t> ingest_info;
   PinnedBuf<uint32_t> pin_ingest;
   PinnedBuf<uint8_t> pin_ingest_info, pin_fallback;
+  PinnedBuf<IngestMixedRow> pin_mixed_table;
   struct bpp_ingest_stats ingest_stats{};
   bool profile = false;
   bool profile_light = false;  // bpp_profile_enable(ctx, 2): events around the roofline kernel (k_msm_accumulate) only
@@ -2227,9 +2233,179 @@ int upload_packed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_packed_ba
   }
   BPP_CATCH(ctx, errbuf, errbuf_len)
 }
+
+// ---- the mixed form (bpp_mixed_batch): host arrays through the item form, device arrays through k_ingest_mixed (ingest_mixed.h)
+int upload_mixed_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, uint64_t *batch, char *errbuf, size_t errbuf_len) {
+  try {
+    if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty", errbuf, errbuf_len);
+    const std::shared_ptr<Params> Pp = params_registry().get(params);
+    if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
+    const size_t n_items = in->n_items;
+    if (n_items == 0 || !batch) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty", errbuf, errbuf_len);
+    if (n_items > (1u << 24)) return fail(ctx, BPP_ERR_SIZE_OVERFLOW, "batch too large", errbuf, errbuf_len);
+    upload_mixed_geometry(*in);
+    std::vector<bpp_verify_item> items;
+    upload_mixed_as_items(*in, items);
+    UploadPlan pl;
+    PlanWipe wipe_plan{pl};
+    upload_host_pack(ctx, *Pp, items.data(), n_items, nullptr, pl);
+    *batch = upload_device(ctx, Pp, params, pl, nullptr, nullptr);
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, errbuf, errbuf_len)
+}
+
+// The fall-back of the device form: the arrays are copied to page-locked staging as they lie (rows, slack and all, up to the last
+// byte the last row uses) and the batch takes the host form.  The staged nonces are wiped on every way out.
+uint64_t upload_mixed_device_fallback(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t params, const bpp_mixed_batch &in) {
+  const size_t n = in.n_items, last_m = in.m[n - 1], row_entries = (n - 1) * (size_t)in.m_stride + last_m;
+  const size_t proofs_n = in.proofs ? (n - 1) * in.proof_stride + in.proof_lens[n - 1] : 0;
+  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+  const size_t o_proofs = 0, o_commit = up16(proofs_n), o_minv = up16(o_commit + (in.commitments32 ? row_entries * 32 : 0)),
+               o_minp = up16(o_minv + (in.min_values ? row_entries * 8 : 0)), o_seedp = up16(o_minp + (in.min_present ? row_entries : 0)),
+               o_seed = up16(o_seedp + (in.seed_present ? n : 0)), n_seed = in.seed_nonces32 ? n * 32 : 0, total = o_seed + n_seed;
+  ctx->pin_fallback.resize(total + 16);
+  uint8_t *st = ctx->pin_fallback.data();
+  hipStream_t s = ctx->stream;
+  ScopeExit wipe_staged{[&] {
+    if (n_seed) {
+      (void)hipStreamSynchronize(s);  // the copy into the staging may still be running
+      secure_wipe(st + o_seed, n_seed);
+    }
+  }};
+  bpp_mixed_batch host = in;
+  auto fetch = [&](const void *src, size_t off, size_t bytes) -> const uint8_t * {
+    if (!src) return nullptr;
+    if (bytes) HIP_CHECK(hipMemcpyAsync(st + off, src, bytes, hipMemcpyDeviceToHost, s));
+    return st + off;
+  };
+  host.proofs = fetch(in.proofs, o_proofs, proofs_n);
+  host.commitments32 = fetch(in.commitments32, o_commit, row_entries * 32);
+  host.min_values = (const uint64_t *)fetch(in.min_values, o_minv, row_entries * 8);
+  host.min_present = fetch(in.min_present, o_minp, row_entries);
+  host.seed_present = fetch(in.seed_present, o_seedp, n);
+  host.seed_nonces32 = fetch(in.seed_nonces32, o_seed, n_seed);
+  HIP_CHECK(hipStreamSynchronize(s));
+  ctx->ingest_stats.host_fallback_calls++;
+  ctx->ingest_stats.fallback_bytes += proofs_n + (in.commitments32 ? row_entries * 32 : 0) + (in.min_values ? row_entries * 8 : 0) +
+                                      (in.min_present ? row_entries : 0) + (in.seed_present ? n : 0) + n_seed;
+  std::vector<bpp_verify_item> items;
+  upload_mixed_as_items(host, items);
+  UploadPlan pl;
+  PlanWipe wipe_plan{pl};
+  upload_host_pack(ctx, *Pp, items.data(), n, nullptr, pl);
+  return upload_device(ctx, Pp, params, pl, nullptr, nullptr);
+}
+
+int upload_mixed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, uint64_t *batch, char *errbuf, size_t errbuf_len) {
+  try {
+    if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty", errbuf, errbuf_len);
+    // pointer kinds first, as in upload_packed_device_impl: the six arrays are never dereferenced on the host, the two host arrays
+    // are, and so must not be memory of a device
+    const struct {
+      const char *name;
+      const void *p;
+    } arrays[] = {{"proofs", in->proofs},           {"commitments32", in->commitments32}, {"min_values", in->min_values},
+                  {"min_present", in->min_present}, {"seed_nonces32", in->seed_nonces32}, {"seed_present", in->seed_present}},
+      host_arrays[] = {{"proof_lens", in->proof_lens}, {"m", in->m}};
+    static const char *const kinds[] = {"", "memory of another device", "host memory or memory the runtime does not know", "managed memory"};
+    for (const auto &a : arrays) {
+      if (!a.p) continue;
+      const int kind = device_pointer_kind(ctx->device, a.p);
+      if (kind != BPP_PTR_THIS_DEVICE)
+        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + " is not device memory of this context's device (" + kinds[kind] + ")", errbuf,
+                    errbuf_len);
+    }
+    for (const auto &a : host_arrays) {
+      if (!a.p) continue;
+      const int kind = device_pointer_kind(ctx->device, a.p);
+      if (kind == BPP_PTR_THIS_DEVICE || kind == BPP_PTR_OTHER_DEVICE)
+        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + " is device memory: it sizes the layout and stays host memory in every form",
+                    errbuf, errbuf_len);
+    }
+    const std::shared_ptr<Params> Pp = params_registry().get(params);
+    if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
+    const size_t n_items = in->n_items;
+    if (n_items == 0 || !batch) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty", errbuf, errbuf_len);
+    if (n_items > (1u << 24)) return fail(ctx, BPP_ERR_SIZE_OVERFLOW, "batch too large", errbuf, errbuf_len);
+    const ParamShape shape{Pp->n_bits, Pp->m_max, Pp->t};
+    IngestMixedPrelude pre;
+    if (!ingest_mixed_host_prelude(*in, shape, pre)) {
+      *batch = upload_mixed_device_fallback(ctx, Pp, params, *in);
+      return BPP_OK;
+    }
+    if (pre.h == 0) ingest_mixed_throw_finding(pre, n_items, nullptr);  // item 0's, host-known: nothing to run
+    hipStream_t s = ctx->stream;
+    std::unique_ptr<Batch> B = new_batch(ctx);
+    ScopeExit wipe_unfinished{[&] {  // B still here: an error or the fall-back.  The nonces the kernel brought in go before its buffers do
+      if (B) {
+        wipe_batch_secrets(*B, s);
+        (void)hipStreamSynchronize(s);
+      }
+    }};
+    const size_t bytes_len = (size_t)(pre.proof_bytes + pre.sum_m * 32) + BPP_BYTES_SLACK;  // (< 4 GB: the prelude)
+    B->bytes.alloc(bytes_len);
+    B->minvals.alloc((size_t)pre.sum_m);
+    if (in->seed_nonces32) {
+      // (the run may stop short of the last item: a fresh allocation starts out zero, as every buffer that holds secrets at times)
+      const bool fresh = !(B->seeds.p && n_items * 32 <= B->seeds.n);
+      B->seeds.alloc(n_items * 32);
+      if (fresh) HIP_CHECK(hipMemsetAsync(B->seeds.p, 0, B->seeds.n, s));
+    }
+    B->mixed_table.alloc(n_items);
+    ctx->ingest_res.alloc(BPP_ING_RES_WORDS);
+    ctx->ingest_info.alloc(n_items);
+    ctx->pin_ingest.resize(BPP_ING_RES_WORDS);
+    ctx->pin_mixed_table.resize(n_items);
+    memcpy(ctx->pin_mixed_table.data(), pre.rows.data(), n_items * sizeof(IngestMixedRow));
+    HIP_CHECK(hipMemcpyAsync(B->mixed_table.p, ctx->pin_mixed_table.data(), n_items * sizeof(IngestMixedRow), hipMemcpyHostToDevice, s));
+    const IngestMixed a = ingest_mixed_args(*in, shape, pre, B->mixed_table.p, B->bytes.p, B->minvals.p, B->seeds.p, ctx->ingest_info.p,
+                                            ctx->ingest_res.p);
+    HIP_CHECK(hipMemsetAsync(ctx->ingest_res.p, 0, BPP_ING_RES_WORDS * 4, s));
+    B->seeds_dirty = in->seed_nonces32 != nullptr;
+    hipLaunchKernelGGL(k_ingest_mixed, dim3((uint32_t)cdiv(a.n_run, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, a);
+    HIP_CHECK(hipGetLastError());
+    uint32_t *res = ctx->pin_ingest.data();
+    HIP_CHECK(hipMemcpyAsync(res, ctx->ingest_res.p, BPP_ING_RES_WORDS * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    if (res[BPP_ING_RES_DIFFERS]) {
+      wipe_batch_secrets(*B, s);
+      (void)hipStreamSynchronize(s);
+      ctx->spare_batch = std::move(B);  // its buffers serve the host path's batch
+      *batch = upload_mixed_device_fallback(ctx, Pp, params, *in);
+      return BPP_OK;
+    }
+    ingest_mixed_throw_finding(pre, n_items, res);  // (h < n_items: the call ends here either way, nothing else is fetched)
+    const uint8_t *info = nullptr;
+    if (ingest_mixed_needs_info(*in, res)) {
+      ctx->pin_ingest_info.resize(n_items);
+      HIP_CHECK(hipMemcpyAsync(ctx->pin_ingest_info.data(), ctx->ingest_info.p, n_items, hipMemcpyDeviceToHost, s));
+      HIP_CHECK(hipStreamSynchronize(s));
+      info = ctx->pin_ingest_info.data();
+    }
+    UploadPlan pl;
+    ingest_mixed_finish_plan(*in, shape, pre, res, info, pl);
+    ctx->ingest_stats.device_calls++;
+    *batch = upload_device(ctx, Pp, params, pl, nullptr, nullptr, std::move(B));
+    ctx->batches[*batch]->mixed = true;
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, errbuf, errbuf_len)
+}
 }  // namespace
 
 extern "C" {
+
+int bpp_batch_upload_mixed(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, uint64_t *batch, char *errbuf, size_t errbuf_len) {
+  BPP_ENTRY(ctx);
+  return upload_mixed_impl(ctx, params, in, batch, errbuf, errbuf_len);
+}
+
+int bpp_batch_upload_mixed_device(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, uint64_t *batch, char *errbuf,
+                                  size_t errbuf_len) {
+  BPP_ENTRY(ctx);
+  return upload_mixed_device_impl(ctx, params, in, batch, errbuf, errbuf_len);
+}
 
 int bpp_batch_upload_packed_device(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, uint64_t *batch, char *errbuf,
                                    size_t errbuf_len) {
@@ -3749,6 +3925,18 @@ int bpp_verify_batch_packed(bpp_ctx *ctx, uint64_t params, const bpp_packed_batc
 int bpp_verify_batch_packed_device(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, int action, size_t chunk,
                                    uint8_t *masks_out, uint8_t *mask_present, char *errbuf, size_t errbuf_len) {
   auto upload = [&](uint64_t *h) -> int { return bpp_batch_upload_packed_device(ctx, params, in, h, errbuf, errbuf_len); };
+  return verify_uploaded(ctx, in ? in->n_items : SIZE_MAX, upload, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
+}
+
+int bpp_verify_batch_mixed(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, int action, size_t chunk, uint8_t *masks_out,
+                           uint8_t *mask_present, char *errbuf, size_t errbuf_len) {
+  auto upload = [&](uint64_t *h) -> int { return bpp_batch_upload_mixed(ctx, params, in, h, errbuf, errbuf_len); };
+  return verify_uploaded(ctx, in ? in->n_items : SIZE_MAX, upload, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
+}
+
+int bpp_verify_batch_mixed_device(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, int action, size_t chunk,
+                                  uint8_t *masks_out, uint8_t *mask_present, char *errbuf, size_t errbuf_len) {
+  auto upload = [&](uint64_t *h) -> int { return bpp_batch_upload_mixed_device(ctx, params, in, h, errbuf, errbuf_len); };
   return verify_uploaded(ctx, in ? in->n_items : SIZE_MAX, upload, action, chunk, masks_out, mask_present, errbuf, errbuf_len);
 }
 

@@ -204,16 +204,21 @@ struct UploadPart {  // what one worker of pass B found in its range of items
   uint32_t rmax = 0, max_mn = 0;
 };
 
+// The checks of an item that look at no byte behind its pointers: RangeStatement::init (src/range_statement.rs:36-73) as far as the
+// aggregation factor and the presence of the arrays decide it.  upload_check_item opens with it; the device form of the mixed
+// upload (ingest_mixed.h) runs it on the host over m[], where it finds the first item the kernel does not have to look at.
+inline void upload_check_statement_shape(uint32_t m, bool commitments, bool min_values, bool min_present, const ParamShape &P) {
+  if (m == 0 || (m & (m - 1))) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Number of commitments must be a power of two"};
+  if (!commitments || (!min_values && min_present))
+    throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Incorrect number of minimum value promises"};
+  if (P.m_max < m) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Not enough generators for this statement"};
+}
+
 // the per-item body of pass B, for either input form
 inline void upload_check_item(const ItemView &it, size_t i, const ParamShape &P, UploadPlan &pl, const UploadPlan::Pre &pre,
                               uint32_t rounds0, uint8_t *bytes_dst, UploadPart &pt) {
   ProofDesc &d = pl.desc[i];
-  // RangeStatement::init (src/range_statement.rs:36-73)
-  if (it.m == 0 || (it.m & (it.m - 1)))
-    throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Number of commitments must be a power of two"};
-  if (!it.commitments32 || (!it.min_values && it.min_present))
-    throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Incorrect number of minimum value promises"};
-  if (P.m_max < it.m) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Not enough generators for this statement"};
+  upload_check_statement_shape(it.m, it.commitments32 != nullptr, it.min_values != nullptr, it.min_present != nullptr, P);
   if (it.seed_nonce32 && it.m > 1)
     throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Mask recovery is not supported with an aggregated statement"};
   if (!it.proof) throw ProofErr{BPP_ERR_INVALID_LENGTH, "Serialized proof is too short"};
@@ -327,6 +332,54 @@ inline void upload_packed_as_items(const bpp_packed_batch &pk, std::vector<bpp_v
     it.transcript_state = pk.transcript_state;
     it.transcript_label = pk.transcript_label;
     it.label_len = pk.label_len;
+  }
+}
+
+// ---- the mixed form (bpp_mixed_batch): rows of proof_stride / m_stride entries, the length and the aggregation factor of every
+// item in two host arrays.  What makes no sense as rows is refused before anything is read (the refusal names the field, in the
+// host and the device form alike); everything else is the item form over views of the rows.
+inline void upload_mixed_geometry(const bpp_mixed_batch &mx) {
+  if (!mx.proof_lens) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "proof_lens is null"};
+  if (!mx.m) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "m is null"};
+  for (size_t i = 0; i < mx.n_items; i++) {
+    if (mx.proof_lens[i] > mx.proof_stride) {
+      ProofErr e{BPP_ERR_INVALID_ARGUMENT, "proof_stride is below a proof length"};
+      e.index = (uint32_t)i;
+      throw e;
+    }
+    if (mx.m[i] > mx.m_stride) {
+      ProofErr e{BPP_ERR_INVALID_ARGUMENT, "m_stride is below an aggregation factor"};
+      e.index = (uint32_t)i;
+      throw e;
+    }
+  }
+}
+inline ItemView item_view(const bpp_mixed_batch &mx, size_t i) {
+  const bool seed = mx.seed_nonces32 && (!mx.seed_present || mx.seed_present[i]);
+  const size_t row = i * (size_t)mx.m_stride;
+  return ItemView{mx.proofs ? mx.proofs + i * mx.proof_stride : nullptr,
+                  mx.proof_lens[i],
+                  mx.commitments32 ? mx.commitments32 + row * 32 : nullptr,
+                  mx.m[i],
+                  mx.min_values ? mx.min_values + row : nullptr,
+                  mx.min_present ? mx.min_present + row : nullptr,
+                  seed ? mx.seed_nonces32 + i * 32 : nullptr};
+}
+inline void upload_mixed_as_items(const bpp_mixed_batch &mx, std::vector<bpp_verify_item> &items) {
+  items.resize(mx.n_items);
+  for (size_t i = 0; i < mx.n_items; i++) {
+    const ItemView v = item_view(mx, i);
+    bpp_verify_item &it = items[i];
+    it.proof = v.proof;
+    it.proof_len = v.proof_len;
+    it.commitments32 = v.commitments32;
+    it.m = v.m;
+    it.min_values = v.min_values;
+    it.min_present = v.min_present;
+    it.seed_nonce32 = v.seed_nonce32;
+    it.transcript_state = mx.transcript_state;
+    it.transcript_label = mx.transcript_label;
+    it.label_len = mx.label_len;
   }
 }
 

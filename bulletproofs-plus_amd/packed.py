@@ -246,6 +246,122 @@ def verify_batch_device(params, inp, action=api.VerifyAction.VerifyOnly, chunk=a
     return masks, present
 
 
+def _host_array(a):
+    """a numpy array of a numpy array or a host torch tensor"""
+    if hasattr(a, "data_ptr"):
+        if getattr(a, "is_cuda", False):
+            raise api.ProofError(api.ProofErrorKind.InvalidArgument, "a host array expected, got a device tensor")
+        a = a.numpy()
+    return np.asarray(a)
+
+
+def _mixed_meta(proof_lens, m):
+    """proof_lens as size_t [n] and m as uint32 [n], host arrays in every form; -> (lens, m, n)"""
+    lens = np.ascontiguousarray(_host_array(proof_lens), dtype=np.uintp)
+    m = np.ascontiguousarray(_host_array(m), dtype=np.uint32)
+    if lens.ndim != 1 or m.shape != lens.shape:
+        raise api.ProofError(api.ProofErrorKind.InvalidLength, "proof_lens and m: two arrays of shape (n,) expected")
+    return lens, m, lens.shape[0]
+
+
+class MixedInput:
+    """A batch of MIXED aggregation factors as arrays of rows + the bpp_mixed_batch that describes it (include/bpp.h): the geometry
+    of what bpp_prove_batch_mixed / bpp_prove_openings write.  Rows are numpy arrays or host torch tensors:
+        proofs       uint8 [n, >= longest proof]   row i holds proof_lens[i] bytes (a view whose rows lie further apart is taken as it is)
+        proof_lens   [n], m [n]                    the used part of every row
+        commitments  uint8 [n, m_stride, 32]       row i holds m[i] commitments
+        min_values   uint64 [n, m_stride], min_present uint8 [n, m_stride], seed_nonces uint8 [n, 32], seed_present uint8 [n], or None
+    Row slack is never read.  Holds the arrays alive; `.struct` can be passed to the *_mixed entry points any number of times."""
+
+    def __init__(self, proofs, proof_lens, m, commitments, min_values=None, min_present=None, seed_nonces=None, label=b"", seed_present=None,
+                 state=None, proof_stride=None):
+        self.proof_lens, self.m, n = _mixed_meta(proof_lens, m)
+        p = _host_array(proofs)
+        if p.dtype != np.uint8 or p.ndim != 2 or p.shape[0] != n:
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "proofs: a uint8 array of shape (n, row) expected")
+        if not (n <= 1 or (p.strides[1] == 1 and p.strides[0] >= p.shape[1])):
+            p = np.ascontiguousarray(p)
+        self.proofs = p
+        stride = int(proof_stride) if proof_stride is not None else (p.strides[0] if n > 1 else p.shape[1])
+        commitments = np.ascontiguousarray(_host_array(commitments), dtype=np.uint8)
+        if commitments.ndim != 3 or commitments.shape[0] != n or commitments.shape[2] != 32:
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "commitments: an array of shape (n, m_stride, 32) expected")
+        ms = commitments.shape[1]
+        self.commitments = commitments
+        self.min_values = None if min_values is None else _c(_host_array(min_values), np.uint64, (n, ms))
+        self.min_present = None if min_present is None else _c(_host_array(min_present), np.uint8, (n, ms))
+        self.seed_nonces = None if seed_nonces is None else _c(_host_array(seed_nonces), np.uint8, (n, 32))
+        self.seed_present = None if seed_present is None else _c(_host_array(seed_present), np.uint8, (n,))
+        self.label = np.frombuffer(bytes(label), dtype=np.uint8).copy() if len(label) else np.zeros(1, dtype=np.uint8)
+        self.state = None if state is None else np.frombuffer(bytes(state), dtype=np.uint8).copy()
+        self.n, self.m_stride = n, ms
+        ptr = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+        self.struct = _lib.MixedBatch(n, ptr(self.proofs), stride, ptr(self.proof_lens), ptr(self.m), ms, ptr(self.commitments),
+                                      ptr(self.min_values), ptr(self.min_present), ptr(self.seed_nonces), ptr(self.seed_present),
+                                      ptr(self.state), ptr(self.label), len(label))
+
+
+class DeviceMixedInput(DevicePackedInput):
+    """MixedInput whose six row arrays already lie in DEVICE memory, for the *_mixed_device entry points: torch device tensors or
+    (address, shape) pairs of the shapes given there (proofs may be a view whose rows lie further apart than they are long, or
+    proof_stride= with an address; min_values any 8-byte dtype).  proof_lens and m are HOST arrays: they size the layout.  Ordering as
+    for DevicePackedInput: order_before(engine) is called by verify_batch_mixed_device and ResidentBatch.from_mixed."""
+
+    def __init__(self, proofs, proof_lens, m, commitments, min_values=None, min_present=None, seed_nonces=None, label=b"", seed_present=None,
+                 state=None, proof_stride=None):
+        self._keep, self.device_index, self._torch, self.synchronised = [], None, False, False
+        self.proof_lens, self.m, n = _mixed_meta(proof_lens, m)
+        addr_p, shape, stride = self._array(proofs, "proofs", 1, rows=True)
+        if len(shape) != 2 or shape[0] != n:
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "proofs: an array of shape (%d, row) expected, got %s" % (n, shape))
+        stride = int(proof_stride) if proof_stride is not None else (stride if stride is not None else shape[1])
+        addr_c, cshape, _ = self._array(commitments, "commitments", 1)
+        if len(cshape) != 3 or cshape[0] != n or cshape[2] != 32:
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "commitments: an array of shape (%d, m_stride, 32) expected, got %s" % (n, cshape))
+        ms = cshape[1]
+
+        def opt(a, name, itemsize, want):
+            if a is None:
+                return None
+            addr, got, _ = self._array(a, name, itemsize)
+            if got != want:
+                raise api.ProofError(api.ProofErrorKind.InvalidLength, "%s: array of shape %s expected, got %s" % (name, want, got))
+            return addr
+
+        self.label = np.frombuffer(bytes(label), dtype=np.uint8).copy() if len(label) else np.zeros(1, dtype=np.uint8)
+        self.state = None if state is None else np.frombuffer(bytes(state), dtype=np.uint8).copy()
+        self.n, self.m_stride = n, ms
+        self.struct = _lib.MixedBatch(n, addr_p, stride, self.proof_lens.ctypes.data, self.m.ctypes.data, ms, addr_c,
+                                      opt(min_values, "min_values", 8, (n, ms)), opt(min_present, "min_present", 1, (n, ms)),
+                                      opt(seed_nonces, "seed_nonces", 1, (n, 32)), opt(seed_present, "seed_present", 1, (n,)),
+                                      None if self.state is None else self.state.ctypes.data, self.label.ctypes.data, len(label))
+
+
+def _verify_mixed(params, inp, action, chunk, device):
+    eng, t = params.engine, int(params.extension_degree())
+    masks = np.zeros((inp.n, t, 32), dtype=np.uint8)
+    present = np.zeros(inp.n, dtype=np.uint8)
+    err = ctypes.create_string_buffer(256)
+    if device:
+        inp.order_before(eng)
+    fn = eng.lib.bpp_verify_batch_mixed_device if device else eng.lib.bpp_verify_batch_mixed
+    rc = fn(eng.ctx, params.handle, byref(inp.struct), int(action), chunk, masks.ctypes.data, present.ctypes.data, err, 256)
+    api._check(rc, eng.ctx, err)
+    return masks, present
+
+
+def verify_batch_mixed(params, inp, action=api.VerifyAction.VerifyOnly, chunk=api.MAX_RANGE_PROOF_BATCH_SIZE):
+    """RangeProof::verify_batch over a MixedInput in ONE C call (bpp_verify_batch_mixed): what the item form gives on the same rows.
+    Returns (masks uint8 [n, t, 32], present uint8 [n])."""
+    return _verify_mixed(params, inp, action, chunk, False)
+
+
+def verify_batch_mixed_device(params, inp, action=api.VerifyAction.VerifyOnly, chunk=api.MAX_RANGE_PROOF_BATCH_SIZE):
+    """verify_batch_mixed over a DeviceMixedInput (bpp_verify_batch_mixed_device): one kernel checks and packs the batch where it lies.
+    Returns (masks uint8 [n, t, 32], present uint8 [n]) (host arrays)."""
+    return _verify_mixed(params, inp, action, chunk, True)
+
+
 def device_pointer_kind(engine, address):
     """bpp_device_pointer_check: 0 this engine's device memory, 1 another device's, 2 host or unknown, 3 managed (launches nothing)"""
     kind = ctypes.c_int(-1)
@@ -650,6 +766,27 @@ class ResidentBatch(api.ResidentBatch):
                                               byref(self.handle), err, 256)
         api._check(rc, self.engine.ctx, err)
         self.marshal_seconds, self.upload_seconds = t1 - t0, time.perf_counter() - t1
+
+    @classmethod
+    def from_mixed(cls, params, inp):
+        """the resident batch of a MixedInput (bpp_batch_upload_mixed) or a DeviceMixedInput (bpp_batch_upload_mixed_device): an ordinary
+        resident batch -- verify_arrays, enqueue, the group calls and the traces work on it; refill does not (its shape is a vector)"""
+        self = cls.__new__(cls)
+        self.params, self.engine, self.t = params, params.engine, int(params.extension_degree())
+        self.handle = c_uint64()
+        self.n, self.input = inp.n, inp
+        err = ctypes.create_string_buffer(256)
+        t0 = time.perf_counter()
+        if isinstance(inp, DeviceMixedInput):
+            inp.order_before(self.engine)
+            fn = self.engine.lib.bpp_batch_upload_mixed_device
+        else:
+            fn = self.engine.lib.bpp_batch_upload_mixed
+        t1 = time.perf_counter()
+        rc = fn(self.engine.ctx, params.handle, byref(inp.struct), byref(self.handle), err, 256)
+        api._check(rc, self.engine.ctx, err)
+        self.marshal_seconds, self.upload_seconds = t1 - t0, time.perf_counter() - t1
+        return self
 
     def verify_arrays(self, action, chunk=0):
         """bpp_verify_resident with the masks as arrays (no per-item Python): (masks uint8 [n, t, 32], present uint8 [n])"""

@@ -339,6 +339,53 @@ struct bpp_ingest_stats {
 };
 int bpp_ingest_stats(bpp_ctx *ctx, struct bpp_ingest_stats *out);
 
+/* ---- the array form for batches of MIXED aggregation factors, in host or in device memory.  The struct has the geometry of what
+ * bpp_prove_batch_mixed / bpp_prove_openings write: proofs in rows of proof_stride with proof_lens[i] bytes used, commitments in
+ * rows of m_stride x 32 bytes (commit_stride = 32 x m_stride there) with m[i] entries used; the promise arrays have rows of
+ * m_stride entries as well.  ROW SLACK -- proof bytes at and beyond proof_lens[i], commitment and promise entries at and beyond
+ * m[i] -- is never read for a check and never copied.
+ * proof_lens and m are public metadata that size the layout: they are HOST memory in every form.
+ * RESULTS: for any input the four calls return what bpp_batch_upload / bpp_verify_batch return on the equivalent bpp_verify_item
+ * array (item i points into the rows, all items share the one transcript source): return code, text in errbuf, the index a finding
+ * names, masks and mask_present; the batch has the same bpp_batch_shape and gives the same bpp_batch_trace output.  One routine
+ * decides both forms.  Two refusals are the form's own, BPP_ERR_INVALID_ARGUMENT before anything is read, with the field's name in
+ * errbuf: proof_stride below a proof_lens[i], m_stride below an m[i] (and proof_lens or m null).
+ * The _device calls: six fields are addresses in the memory of the context's device, as for bpp_batch_upload_packed_device --
+ * proofs, commitments32, min_values, min_present, seed_nonces32, seed_present -- with the ORDERING, POINTER KINDS and SECRETS rules
+ * given there; proof_lens and m are refused, field named, when the runtime knows them as device memory of any device.  One kernel
+ * (k_ingest_mixed) checks every item and packs the batch where it lies; what the host can tell from m[] alone (not a power of two,
+ * above the parameters' max_aggregation, a missing promise array) it tells without the kernel looking at that item, and the
+ * lowest index of either kind is the call's finding.
+ * FALLBACK: a batch whose proofs disagree in their first byte, or that has no proofs array, is copied to page-locked staging and
+ * goes through the host form: same results, counted in bpp_ingest_stats (device uploads of this form count in the same three
+ * counters).  The staged nonces are wiped on every way out.
+ * THE BATCH is an ordinary resident batch: bpp_verify_resident*, the grouped forms, bpp_batch_prepare, bpp_batch_trace and
+ * bpp_verify_enqueue take it.  NOT BUILT: bpp_batch_refill_enqueue* refuses it as it refuses every batch the packed device upload
+ * did not make (its shape is a vector, not four numbers); there is no pipeline (bpp_verify_submit_packed) or batcher form. */
+typedef struct {
+  size_t n_items;
+  const uint8_t *proofs;           /* proof i = RangeProof::to_bytes() at proofs + i * proof_stride, proof_lens[i] bytes */
+  size_t proof_stride;             /* >= every proof_lens[i] */
+  const size_t *proof_lens;        /* n_items, ALWAYS HOST memory (what bpp_prove_batch_mixed writes to proof_lens) */
+  const uint32_t *m;               /* n_items, ALWAYS HOST memory: aggregation factor of statement i */
+  uint32_t m_stride;               /* entries per item row of the next three arrays, >= every m[i] */
+  const uint8_t *commitments32;    /* n_items rows of m_stride x 32 bytes; row i holds m[i] commitments, the rest is not read */
+  const uint64_t *min_values;      /* n_items x m_stride, or NULL */
+  const uint8_t *min_present;      /* n_items x m_stride, or NULL = all None */
+  const uint8_t *seed_nonces32;    /* n_items x 32, or NULL */
+  const uint8_t *seed_present;     /* n_items, or NULL = every item has a nonce (when seed_nonces32 != NULL) */
+  const uint8_t *transcript_state; /* as in bpp_packed_batch: one transcript serves every item */
+  const uint8_t *transcript_label;
+  size_t label_len;
+} bpp_mixed_batch;
+int bpp_batch_upload_mixed(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, uint64_t *batch, char *errbuf, size_t errbuf_len);
+int bpp_verify_batch_mixed(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, int action, size_t chunk, uint8_t *masks_out,
+                           uint8_t *mask_present, char *errbuf, size_t errbuf_len);
+int bpp_batch_upload_mixed_device(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, uint64_t *batch, char *errbuf,
+                                  size_t errbuf_len);
+int bpp_verify_batch_mixed_device(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, int action, size_t chunk,
+                                  uint8_t *masks_out, uint8_t *mask_present, char *errbuf, size_t errbuf_len);
+
 /* Pipelined host-buffers-in verification inside ONE context.  submit parses, validates and packs `in` into page-locked
  * staging on the calling thread (construction errors are returned by submit itself, as RangeStatement::init /
  * RangeProof::from_bytes would raise them before verify_batch is entered) and returns; the caller's buffers are free again.

@@ -372,6 +372,12 @@ struct DevicePackedBatch {
   bpp_packed_batch arrays;
 };
 
+// a bpp_mixed_batch whose six array fields are addresses in DEVICE memory (bpp.h: bpp_verify_batch_mixed_device); proof_lens and m
+// stay host memory
+struct DeviceMixedBatch {
+  bpp_mixed_batch arrays;
+};
+
 struct ExtendedMask {
   std::vector<Bytes32> blindings;
   bool operator==(const ExtendedMask &o) const { return blindings == o.blindings; }
@@ -583,7 +589,28 @@ class RangeProof {
     return verify_packed_impl(params, in.arrays, action, chunk, true);
   }
 
+  // The array form for batches of MIXED aggregation factors (bpp.h: bpp_mixed_batch, the geometry of the prover's mixed output), as
+  // an overload pair of the same kind: arrays in host memory, or -- DeviceMixedBatch -- arrays in the memory of the engine's device
+  // (bpp_verify_batch_mixed_device).  The results of the item form on the same rows either way.
+  static std::vector<std::optional<ExtendedMask>> verify_batch(const RangeParameters &params, const bpp_mixed_batch &in, VerifyAction action,
+                                                                size_t chunk = BPP_REFERENCE_CHUNK) {
+    return verify_mixed_impl(params, in, action, chunk, false);
+  }
+  static std::vector<std::optional<ExtendedMask>> verify_batch(const RangeParameters &params, const DeviceMixedBatch &in, VerifyAction action,
+                                                                size_t chunk = BPP_REFERENCE_CHUNK) {
+    return verify_mixed_impl(params, in.arrays, action, chunk, true);
+  }
+
  private:
+  static std::vector<std::optional<ExtendedMask>> verify_mixed_impl(const RangeParameters &params, const bpp_mixed_batch &in, VerifyAction action,
+                                                                     size_t chunk, bool on_device) {
+    const uint32_t t = static_cast<uint32_t>(params.extension_degree());
+    std::vector<uint8_t> masks(in.n_items * t * 32), present(in.n_items);
+    char err[256] = {0};
+    check((on_device ? bpp_verify_batch_mixed_device : bpp_verify_batch_mixed)(params.engine().ctx(), params.handle(), &in, static_cast<int>(action),
+                                                                                 chunk, masks.data(), present.data(), err, sizeof(err)), err);
+    return masks_of(masks, present, t);
+  }
   static std::vector<std::optional<ExtendedMask>> verify_packed_impl(const RangeParameters &params, const bpp_packed_batch &in, VerifyAction action,
                                                                       size_t chunk, bool on_device) {
     const uint32_t t = static_cast<uint32_t>(params.extension_degree());

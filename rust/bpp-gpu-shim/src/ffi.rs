@@ -81,6 +81,26 @@ pub struct bpp_packed_batch {
     pub label_len: usize,
 }
 
+/// bpp_mixed_batch: a batch of mixed aggregation factors as arrays of rows, the geometry of what `bpp_prove_batch_mixed` /
+/// `bpp_prove_openings` write; `proof_lens` and `m` are host memory in every form
+#[repr(C)]
+pub struct bpp_mixed_batch {
+    pub n_items: usize,
+    pub proofs: *const u8,
+    pub proof_stride: usize,
+    pub proof_lens: *const usize,
+    pub m: *const u32,
+    pub m_stride: u32,
+    pub commitments32: *const u8,
+    pub min_values: *const u64,
+    pub min_present: *const u8,
+    pub seed_nonces32: *const u8,
+    pub seed_present: *const u8,
+    pub transcript_state: *const u8,
+    pub transcript_label: *const u8,
+    pub label_len: usize,
+}
+
 #[repr(C)]
 pub struct bpp_comm {
     _p: [u8; 0],
@@ -313,6 +333,15 @@ extern "C" {
                                           errbuf: *mut c_char, errbuf_len: usize) -> c_int;
     pub fn bpp_verify_batch_packed_device(ctx: *mut bpp_ctx, params: u64, input: *const bpp_packed_batch, action: c_int, chunk: usize,
                                           masks_out: *mut u8, mask_present: *mut u8, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    // batches of mixed aggregation factors from arrays of rows, in host memory or (six array fields of `input`) in device memory
+    pub fn bpp_batch_upload_mixed(ctx: *mut bpp_ctx, params: u64, input: *const bpp_mixed_batch, batch: *mut u64, errbuf: *mut c_char,
+                                  errbuf_len: usize) -> c_int;
+    pub fn bpp_verify_batch_mixed(ctx: *mut bpp_ctx, params: u64, input: *const bpp_mixed_batch, action: c_int, chunk: usize,
+                                  masks_out: *mut u8, mask_present: *mut u8, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_batch_upload_mixed_device(ctx: *mut bpp_ctx, params: u64, input: *const bpp_mixed_batch, batch: *mut u64,
+                                         errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_verify_batch_mixed_device(ctx: *mut bpp_ctx, params: u64, input: *const bpp_mixed_batch, action: c_int, chunk: usize,
+                                         masks_out: *mut u8, mask_present: *mut u8, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
     pub fn bpp_device_pointer_check(ctx: *mut bpp_ctx, p: *const c_void, kind: *mut c_int) -> c_int;
     pub fn bpp_ingest_stats(ctx: *mut bpp_ctx, out: *mut bpp_ingest_stats) -> c_int;
     pub fn bpp_ctx_pipeline_depth(ctx: *mut bpp_ctx, depth: u32) -> c_int;
