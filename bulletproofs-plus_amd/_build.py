@@ -243,6 +243,22 @@ def build_ingest_mixed_harness(force=False):
     return INGEST_MIXED_SANITIZER_BIN
 
 
+REFILL_MIXED_SANITIZER_BIN = os.path.join(HERE, "hosttest_refill_mixed_asan")
+
+
+def build_refill_mixed_harness(force=False):
+    """hosttest_refill_mixed.cpp (refill_mixed.h: the one-lane model of the kernels of bpp_batch_refill_enqueue_mixed, plain, with a
+    count and under a mask, held to the device form of the mixed upload on the rows in question) under ASan + UBSan: an executable, run
+    by tests/test_refill_mixed_host.py."""
+    src = os.path.join(CSRC, "hosttest_refill_mixed.cpp")
+    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
+    if not force and not _stale(REFILL_MIXED_SANITIZER_BIN, deps):
+        return REFILL_MIXED_SANITIZER_BIN
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-fno-omit-frame-pointer", "-o", REFILL_MIXED_SANITIZER_BIN, src], check=True, cwd=CSRC)
+    return REFILL_MIXED_SANITIZER_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     build_hosttest(force="--force" in sys.argv)

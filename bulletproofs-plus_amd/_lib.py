@@ -196,6 +196,7 @@ SYMBOLS = [
     ("bpp_refill_stats", c_int, [c_void_p, POINTER(RefillStats)]),
     ("bpp_batch_refill_enqueue_count", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_void_p, c_void_p, POINTER(c_uint64)]),
     ("bpp_batch_refill_enqueue_live", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_void_p, c_void_p, POINTER(c_uint64)]),
+    ("bpp_batch_refill_enqueue_mixed", c_int, [c_void_p, c_uint64, POINTER(MixedBatch), c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
     ("bpp_enqueue_weights", c_int, [c_void_p, c_uint64, c_void_p, POINTER(c_uint64)]),
     ("bpp_batcher_verify_action", c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_char_p, c_size_t]),
     ("bpp_batcher_set_limits", c_int, [c_void_p, c_uint32, c_uint32]),

@@ -44,6 +44,7 @@
 #include "ingest_mixed.h"
 #include "verdict.h"
 #include "refill.h"
+#include "refill_mixed.h"
 
 using namespace bpp;
 
@@ -438,9 +439,20 @@ struct Batch {
     return mask_form ? LiveView{nullptr, (const uint8_t *)refill_mask.p} : LiveView{live_word(), (const uint8_t *)nullptr};
   }
   // bpp_batch_upload_mixed_device on its device path: the per-item table k_ingest_mixed packed the batch by (ingest_mixed.h), kept for
-  // a refill of such a batch, which is not built (the batch is not refillable: its shape is this vector, not four numbers)
+  // bpp_batch_refill_enqueue_mixed (refill_mixed.h), whose kernel reads it.  The shape such a refill must keep is this vector, not four
+  // numbers: mixed_shape is the host's copy of it (rows empty: not refillable by that call; `refillable` stays the packed form's).
+  // refill_shape holds n_items, t0 and the three array flags of a mixed batch as well, where verify_enqueue_locked finds them.
   DevBuf<IngestMixedRow> mixed_table;
   bool mixed = false;
+  struct MixedShape {
+    std::vector<IngestMixedRow> rows;
+    uint64_t proof_bytes = 0;
+    uint32_t max_proof_len = 0, max_m = 0;
+    bool seed_present = false;
+  } mixed_shape;
+  // the batch's last refill carried a live count or a live mask: some slots may be dead, so a host decision that follows from the
+  // per-slot shape of a mixed batch (rounds_bad) no longer holds for the call as a whole (verify_enqueue_locked)
+  bool partial_form = false;
   bool enq_weights = false;  // b.weights holds the weights of the batch's last enqueue (bpp_enqueue_weights)
 };
 // what the blocking verify entry points, the sharded and phased forms and the traces answer for a refilled batch: they decide by the
@@ -2387,7 +2399,22 @@ int upload_mixed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batc
     ingest_mixed_finish_plan(*in, shape, pre, res, info, pl);
     ctx->ingest_stats.device_calls++;
     *batch = upload_device(ctx, Pp, params, pl, nullptr, nullptr, std::move(B));
-    ctx->batches[*batch]->mixed = true;
+    Batch &made = *ctx->batches[*batch];
+    made.mixed = true;
+    // the shape a refill of this batch must keep (bpp_batch_refill_enqueue_mixed): the vector the plan above was made from, the first
+    // byte and which optional arrays exist
+    made.refill_shape.n_items = n_items;
+    made.refill_shape.t0 = res[BPP_ING_RES_T0] & 255u;
+    made.refill_shape.nonces = in->seed_nonces32 != nullptr;
+    made.refill_shape.min_values = in->min_values != nullptr;
+    made.refill_shape.min_present = in->min_present != nullptr;
+    made.mixed_shape.seed_present = in->seed_present != nullptr;
+    made.mixed_shape.proof_bytes = pre.proof_bytes;
+    for (const IngestMixedRow &r : pre.rows) {
+      made.mixed_shape.max_proof_len = std::max(made.mixed_shape.max_proof_len, r.proof_len);
+      made.mixed_shape.max_m = std::max(made.mixed_shape.max_m, r.m);
+    }
+    made.mixed_shape.rows = std::move(pre.rows);
     return BPP_OK;
   }
   BPP_CATCH(ctx, errbuf, errbuf_len)
@@ -3584,7 +3611,10 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
     const bool any_defer = b.refilled ? b.refill_shape.t0 != P.t : b.any_defer;
     const bool any_seed = b.refilled ? b.refill_shape.nonces : b.any_seed;
     const bool deferred_only = any_defer && G == 1;  // (any_defer: some proof carries a deferred finding)
-    const bool pass1_only = b.any_rounds_bad && G == 1;
+    // rounds_bad follows from the shape, which in a packed batch is uniform.  In a MIXED batch it is per slot, and under a count or a
+    // mask the offending slot may be dead: the live proofs are then held to the final check as on a fresh upload of them alone, so such
+    // a call takes the general branch as well (k_verdict_scan drops rounds_bad of dead slots).
+    const bool pass1_only = b.any_rounds_bad && G == 1 && !(b.mixed && b.refilled && b.partial_form);
     const bool want_msm = !deferred_only && !pass1_only && any_msm;
     const bool want_masks = !deferred_only && !pass1_only && any_masks && any_seed;
     uint32_t *zero_word = reinterpret_cast<uint32_t *>(b.enq_words.p);
@@ -3648,7 +3678,83 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
 // and the layout are the shape's and stay.
 // count_dev and live_dev (at most one of them): the count form and the mask form of the refill.  The batch is in the form of its last
 // refill: a mask refill switches the chain and verdict kernels to their MASKED forms on the batch's own copy of the mask, any other
-// refill switches them back.
+// refill switches them back.  batch_refill_locked is the driver of the three packed calls; batch_refill_mixed_locked (refill_mixed.h)
+// that of the mixed call; both end in refill_enqueue_tail.
+
+// what both refill drivers refuse alike, before anything else is looked at: the kind of memory behind the caller's six arrays and
+// behind record_dev / count_dev / live_dev, and the alignment of the two that are read or written as words.  Empty: nothing to refuse.
+std::string refill_pointer_refusal(bpp_ctx *ctx, const void *proofs, const void *commitments32, const void *min_values, const void *min_present,
+                                   const void *seed_nonces32, const void *seed_present, const bpp_device_refill *record_dev,
+                                   const uint32_t *count_dev, const uint8_t *live_dev) {
+  const struct {
+    const char *name;
+    const void *p;
+  } arrays[] = {{"proofs", proofs},           {"commitments32", commitments32}, {"min_values", min_values},
+                {"min_present", min_present}, {"seed_nonces32", seed_nonces32}, {"seed_present", seed_present},
+                {"record_dev", record_dev},   {"count_dev", count_dev},         {"live_dev", live_dev}};
+  for (const auto &a : arrays) {
+    if (!a.p) continue;
+    const int kind = device_pointer_kind(ctx->device, a.p);
+    if (kind != BPP_PTR_THIS_DEVICE)
+      return std::string(a.name) + ": not device memory of the context's device (pointer kind " + std::to_string(kind) + ")";
+  }
+  if ((uintptr_t)record_dev & 3u) return "record_dev: not 4-byte aligned";
+  if ((uintptr_t)count_dev & 3u) return "count_dev: not 4-byte aligned";
+  return std::string();
+}
+
+// The common tail of the two refill drivers, behind their refusals: the batch's first-call allocations, the form flags, the launches
+// and the ticket.  `launch_refill(s, masked)` makes the driver's kernel arguments -- the batch's words and mask exist by then -- and
+// launches its refill kernel in the plain/count or the masked form; k_refill_finish and the decompression of the commitments follow it.
+template <class LaunchRefill>
+void refill_enqueue_tail(bpp_ctx *ctx, Batch &b, bool nonces, const uint32_t *count_dev, const uint8_t *live_dev, bpp_device_refill *record_dev,
+                         uint64_t *ticket, LaunchRefill &&launch_refill) {
+  const size_t n = b.B;
+  hipStream_t s = ctx->stream;
+  struct bpp_refill_stats &rs = ctx->refill_stats;
+  bool first = false;
+  if (!b.refill_red.p) {  // the first refill of this batch: its few device words, and d_defer where no enqueue made it
+    b.refill_red.alloc(BPP_REFILL_RED_WORDS);
+    b.refill_state.alloc(1);
+    b.refill_live.alloc(1);  // (written by the first refill that takes a count, read only from then on)
+    b.d_defer.alloc(n);
+    HIP_CHECK(hipMemsetAsync(b.refill_red.p, 0, BPP_REFILL_RED_WORDS * 4, s));
+    HIP_CHECK(hipMemsetAsync(b.refill_state.p, 0, 8, s));
+    first = true;
+  }
+  if (live_dev && !b.refill_mask.p) {  // the first refill of this batch under a mask: its N bytes, written by the kernel below
+    b.refill_mask.alloc(n);
+    first = true;
+  }
+  if (first) rs.first_calls++;
+  if (ctx->enq_events.empty()) {  // (the context's first ticket)
+    ctx->enq_events.resize(64);
+    for (auto &e : ctx->enq_events) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  }
+  if (count_dev) b.has_live = true;
+  b.mask_form = live_dev != nullptr;
+  b.partial_form = count_dev != nullptr || live_dev != nullptr;
+  b.enq_weights = false;
+  b.refilled = true;  // from here on the contents are the stream's, whatever becomes of the launches
+  b.seeds_dirty = nonces;
+  launch_refill(s, b.mask_form);
+  // (under a mask nothing is clamped and the batch's count word is left alone: the later kernels do not read it in that form)
+  hipLaunchKernelGGL(k_refill_finish, dim3(1), dim3(64), 0, s, b.refill_red.p, b.refill_state.p, record_dev, count_dev, (uint32_t)n,
+                     (b.has_live && !b.mask_form) ? b.refill_live.p : (uint32_t *)nullptr);
+  // the statements' commitments, decoded as at the end of upload_device: COMMIT_FAIL goes to status0[] and status[]
+  hipLaunchKernelGGL(k_decompress, dim3(cdiv(b.sum_m, 64)), dim3(64), 0, s, b.bytes.p, b.src_off.p, b.owner.p, b.idx_commit.p, b.sum_m,
+                     b.dynpts.p, b.status0.p, (uint32_t *)nullptr, b.status.p);
+  HIP_CHECK(hipGetLastError());
+  b.status_clean = true;
+  b.masks_dirty = false;  // (the kernel wiped every row)
+  b.have_trace = b.phase1_done = false;
+  const uint64_t t = ctx->enq_next++;
+  HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));
+  b.enq_last_ticket = t;
+  if (ticket) *ticket = t;
+  rs.calls++;
+}
+
 int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in, const uint32_t *count_dev, const uint8_t *live_dev,
                         bpp_device_refill *record_dev, uint64_t *ticket) {
   try {
@@ -3676,74 +3782,101 @@ int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in
     if (in->transcript_state || in->transcript_label)
       return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "transcript_state / transcript_label must be null: a refilled batch keeps its transcript");
     if (!in->proofs || !in->commitments32) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proofs / commitments32: null");
-    const struct {
-      const char *name;
-      const void *p;
-    } arrays[] = {{"proofs", in->proofs},           {"commitments32", in->commitments32}, {"min_values", in->min_values},
-                  {"min_present", in->min_present}, {"seed_nonces32", in->seed_nonces32}, {"seed_present", in->seed_present},
-                  {"record_dev", record_dev},       {"count_dev", count_dev},             {"live_dev", live_dev}};
-    for (const auto &a : arrays) {
-      if (!a.p) continue;
-      const int kind = device_pointer_kind(ctx->device, a.p);
-      if (kind != BPP_PTR_THIS_DEVICE)
-        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + ": not device memory of the context's device (pointer kind " + std::to_string(kind) + ")");
-    }
-    if ((uintptr_t)record_dev & 3u) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "record_dev: not 4-byte aligned");
-    if ((uintptr_t)count_dev & 3u) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "count_dev: not 4-byte aligned");
+    const std::string refusal = refill_pointer_refusal(ctx, in->proofs, in->commitments32, in->min_values, in->min_present, in->seed_nonces32,
+                                                       in->seed_present, record_dev, count_dev, live_dev);
+    if (!refusal.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, refusal);
     Params &P = *b.params;
     const size_t n = b.B;
     // what the kernel writes, against what the upload allocated (the shape says they fit; a kernel is not launched on less)
     if (b.bytes.n < n * sh.proof_len + n * (size_t)sh.m * 32 + BPP_BYTES_SLACK || b.minvals.n < n * (size_t)sh.m || (sh.nonces && b.seeds.n < n * 32) ||
         b.d_desc.n < n || b.status0.n < n || b.status.n < n || b.masks.n < n * (size_t)P.t * 32 || b.sum_m != n * sh.m)
       throw EngineError{BPP_ERR_ENGINE, "refill: the batch's buffers do not fit its recorded shape"};
-    hipStream_t s = ctx->stream;
-    struct bpp_refill_stats &rs = ctx->refill_stats;
-    bool first = false;
-    if (!b.refill_red.p) {  // the first refill of this batch: its few device words, and d_defer where no enqueue made it
-      b.refill_red.alloc(BPP_REFILL_RED_WORDS);
-      b.refill_state.alloc(1);
-      b.refill_live.alloc(1);  // (written by the first refill that takes a count, read only from then on)
-      b.d_defer.alloc(n);
-      HIP_CHECK(hipMemsetAsync(b.refill_red.p, 0, BPP_REFILL_RED_WORDS * 4, s));
-      HIP_CHECK(hipMemsetAsync(b.refill_state.p, 0, 8, s));
-      first = true;
-    }
-    if (live_dev && !b.refill_mask.p) {  // the first refill of this batch under a mask: its N bytes, written by the kernel below
-      b.refill_mask.alloc(n);
-      first = true;
-    }
-    if (first) rs.first_calls++;
-    if (ctx->enq_events.empty()) {  // (the context's first ticket)
-      ctx->enq_events.resize(64);
-      for (auto &e : ctx->enq_events) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
     const ParamShape shape_p{P.n_bits, P.m_max, P.t};
-    const RefillPacked r = refill_args(*in, shape_p, (uint8_t)sh.t0, b.bytes.p, b.minvals.p, b.seeds.p, b.d_defer.p, b.d_desc.p, b.status0.p,
-                                       b.status.p, reinterpret_cast<uint32_t *>(b.masks.p), b.refill_red.p, count_dev, live_dev,
-                                       b.refill_mask.p);
-    if (count_dev) b.has_live = true;
-    b.mask_form = live_dev != nullptr;
-    b.enq_weights = false;
-    b.refilled = true;  // from here on the contents are the stream's, whatever becomes of the launches
-    b.seeds_dirty = sh.nonces;
-    const dim3 refill_grid((uint32_t)cdiv((uint32_t)n, BPP_INGEST_BLOCK / BPP_INGEST_LANES));
-    if (b.mask_form) hipLaunchKernelGGL(k_refill_packed<true>, refill_grid, dim3(BPP_INGEST_BLOCK), 0, s, r);
-    else hipLaunchKernelGGL(k_refill_packed<false>, refill_grid, dim3(BPP_INGEST_BLOCK), 0, s, r);
-    // (under a mask nothing is clamped and the batch's count word is left alone: the later kernels do not read it in that form)
-    hipLaunchKernelGGL(k_refill_finish, dim3(1), dim3(64), 0, s, b.refill_red.p, b.refill_state.p, record_dev, count_dev, (uint32_t)n,
-                       (b.has_live && !b.mask_form) ? b.refill_live.p : (uint32_t *)nullptr);
-    // the statements' commitments, decoded as at the end of upload_device: COMMIT_FAIL goes to status0[] and status[]
-    hipLaunchKernelGGL(k_decompress, dim3(cdiv(b.sum_m, 64)), dim3(64), 0, s, b.bytes.p, b.src_off.p, b.owner.p, b.idx_commit.p, b.sum_m,
-                       b.dynpts.p, b.status0.p, (uint32_t *)nullptr, b.status.p);
-    HIP_CHECK(hipGetLastError());
-    b.status_clean = true;
-    b.masks_dirty = false;  // (the kernel wiped every row)
-    b.have_trace = b.phase1_done = false;
-    const uint64_t t = ctx->enq_next++;
-    HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));
-    b.enq_last_ticket = t;
-    if (ticket) *ticket = t;
-    rs.calls++;
+    refill_enqueue_tail(ctx, b, sh.nonces, count_dev, live_dev, record_dev, ticket, [&](hipStream_t s, bool masked) {
+      const RefillPacked r = refill_args(*in, shape_p, (uint8_t)sh.t0, b.bytes.p, b.minvals.p, b.seeds.p, b.d_defer.p, b.d_desc.p, b.status0.p,
+                                         b.status.p, reinterpret_cast<uint32_t *>(b.masks.p), b.refill_red.p, count_dev, live_dev,
+                                         b.refill_mask.p);
+      const dim3 refill_grid((uint32_t)cdiv((uint32_t)n, BPP_INGEST_BLOCK / BPP_INGEST_LANES));
+      if (masked) hipLaunchKernelGGL(k_refill_packed<true>, refill_grid, dim3(BPP_INGEST_BLOCK), 0, s, r);
+      else hipLaunchKernelGGL(k_refill_packed<false>, refill_grid, dim3(BPP_INGEST_BLOCK), 0, s, r);
+    });
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, nullptr, 0)
+}
+
+// ---- bpp_batch_refill_enqueue_mixed (refill_mixed.h): the same for a batch of mixed aggregation factors.  Its shape is the vector
+// (proof_lens[i], m[i]) the upload recorded (Batch::mixed_shape, on the device Batch::mixed_table); in->proof_lens / in->m are host
+// arrays that must repeat it, or both null -- then nothing of size N is touched here.  The strides are the SOURCE's and need only hold
+// the batch's longest row.  Everything is refused before the tail, which is batch_refill_locked's.
+int batch_refill_mixed_locked(bpp_ctx *ctx, uint64_t batch, const bpp_mixed_batch *in, const uint32_t *count_dev, const uint8_t *live_dev,
+                              bpp_device_refill *record_dev, uint64_t *ticket) {
+  try {
+    auto it = ctx->batches.find(batch);
+    if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
+    if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+    Batch &b = *it->second;
+    const Batch::MixedShape &ms = b.mixed_shape;
+    if (!b.mixed || !b.mixed_table.p || ms.rows.empty() || b.ext_challenges || b.want_states)
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT,
+                  "the batch cannot be refilled from a mixed batch: only a batch that bpp_batch_upload_mixed_device packed on the device records "
+                  "its shape vector (not its staged fall-back, the host mixed form, a packed or item batch, caller-side challenges or a batch "
+                  "that hands out states)");
+    const Batch::RefillShape &sh = b.refill_shape;
+    if (count_dev && live_dev) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "count_dev and live_dev: a refill takes a live count or a live mask, not both");
+    const struct {
+      const char *name;
+      bool same;
+    } shape[] = {{"n_items", (uint64_t)in->n_items == sh.n_items},
+                 {"seed_nonces32", (in->seed_nonces32 != nullptr) == sh.nonces},
+                 {"seed_present", (in->seed_present != nullptr) == ms.seed_present},
+                 {"min_values", (in->min_values != nullptr) == sh.min_values},
+                 {"min_present", (in->min_present != nullptr) == sh.min_present}};
+    for (const auto &f : shape)
+      if (!f.same) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(f.name) + " differs from the batch's shape: a refill keeps the shape of the upload");
+    if ((in->proof_lens != nullptr) != (in->m != nullptr))
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proof_lens and m: give both (they must repeat the batch's vectors) or neither (the batch's own)");
+    const struct {
+      const char *name;
+      const void *p;
+    } host_arrays[] = {{"proof_lens", in->proof_lens}, {"m", in->m}};
+    for (const auto &a : host_arrays) {
+      if (!a.p) continue;
+      const int kind = device_pointer_kind(ctx->device, a.p);
+      if (kind == BPP_PTR_THIS_DEVICE || kind == BPP_PTR_OTHER_DEVICE)
+        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + " is device memory: it names the batch's shape and stays host memory in every form");
+    }
+    if (in->proof_stride < ms.max_proof_len)
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proof_stride is below the batch's largest proof_len (" + std::to_string(ms.max_proof_len) + ")");
+    if (in->m_stride < ms.max_m) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m_stride is below the batch's largest m (" + std::to_string(ms.max_m) + ")");
+    if (in->transcript_state || in->transcript_label)
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "transcript_state / transcript_label must be null: a refilled batch keeps its transcript");
+    if (!in->proofs || !in->commitments32) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proofs / commitments32: null");
+    const std::string refusal = refill_pointer_refusal(ctx, in->proofs, in->commitments32, in->min_values, in->min_present, in->seed_nonces32,
+                                                       in->seed_present, record_dev, count_dev, live_dev);
+    if (!refusal.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, refusal);
+    const size_t n = b.B;
+    for (size_t i = 0; in->proof_lens && i < n; i++) {
+      const char *field = (uint64_t)in->proof_lens[i] != ms.rows[i].proof_len ? "proof_lens" : (in->m[i] != ms.rows[i].m ? "m" : nullptr);
+      if (field)
+        return fail(ctx, BPP_ERR_INVALID_ARGUMENT,
+                    std::string(field) + "[" + std::to_string(i) + "] differs from the batch's shape: a refill keeps the shape of the upload");
+    }
+    Params &P = *b.params;
+    // what the kernel writes, against what the upload allocated (the shape says they fit; a kernel is not launched on less)
+    if (ms.rows.size() != n || b.mixed_table.n < n || b.bytes.n < ms.proof_bytes + (size_t)b.sum_m * 32 + BPP_BYTES_SLACK || b.minvals.n < b.sum_m ||
+        (sh.nonces && b.seeds.n < n * 32) || b.d_desc.n < n || b.status0.n < n || b.status.n < n || b.masks.n < n * (size_t)P.t * 32 ||
+        (uint64_t)ms.rows[n - 1].minval_idx + ms.rows[n - 1].m != b.sum_m || (uint64_t)ms.rows[n - 1].proof_off + ms.rows[n - 1].proof_len != ms.proof_bytes)
+      throw EngineError{BPP_ERR_ENGINE, "refill: the batch's buffers do not fit its recorded shape"};
+    const ParamShape shape_p{P.n_bits, P.m_max, P.t};
+    refill_enqueue_tail(ctx, b, sh.nonces, count_dev, live_dev, record_dev, ticket, [&](hipStream_t s, bool masked) {
+      const RefillMixed r = refill_mixed_args(*in, shape_p, (uint8_t)sh.t0, b.mixed_table.p, n, ms.proof_bytes, b.sum_m, b.bytes.p, b.minvals.p,
+                                              b.seeds.p, b.d_defer.p, b.d_desc.p, b.status0.p, b.status.p, reinterpret_cast<uint32_t *>(b.masks.p),
+                                              b.refill_red.p, count_dev, live_dev, b.refill_mask.p);
+      const dim3 refill_grid((uint32_t)cdiv((uint32_t)n, BPP_INGEST_BLOCK / BPP_INGEST_LANES));
+      if (masked) hipLaunchKernelGGL(k_refill_mixed<BPP_REFILL_MIXED_MASKED>, refill_grid, dim3(BPP_INGEST_BLOCK), 0, s, r);
+      else hipLaunchKernelGGL(k_refill_mixed<BPP_REFILL_MIXED_PLAIN>, refill_grid, dim3(BPP_INGEST_BLOCK), 0, s, r);
+    });
     return BPP_OK;
   }
   BPP_CATCH(ctx, nullptr, 0)
@@ -3844,6 +3977,12 @@ int bpp_batch_refill_enqueue_live(bpp_ctx *ctx, uint64_t batch, const bpp_packed
                                   bpp_device_refill *record_dev, uint64_t *ticket) {
   BPP_ENTRY(ctx);
   return batch_refill_locked(ctx, batch, in_dev, nullptr, live_dev, record_dev, ticket);
+}
+
+int bpp_batch_refill_enqueue_mixed(bpp_ctx *ctx, uint64_t batch, const bpp_mixed_batch *in_dev, const uint32_t *count_dev, const uint8_t *live_dev,
+                                   bpp_device_refill *record_dev, uint64_t *ticket) {
+  BPP_ENTRY(ctx);
+  return batch_refill_mixed_locked(ctx, batch, in_dev, count_dev, live_dev, record_dev, ticket);
 }
 
 // (a diagnostic: one device-to-device copy on the stream behind the batch's last enqueue)

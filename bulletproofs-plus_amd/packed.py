@@ -770,7 +770,8 @@ class ResidentBatch(api.ResidentBatch):
     @classmethod
     def from_mixed(cls, params, inp):
         """the resident batch of a MixedInput (bpp_batch_upload_mixed) or a DeviceMixedInput (bpp_batch_upload_mixed_device): an ordinary
-        resident batch -- verify_arrays, enqueue, the group calls and the traces work on it; refill does not (its shape is a vector)"""
+        resident batch -- verify_arrays, enqueue, the group calls and the traces work on it; refill takes a DeviceMixedInput of the
+        same shape vector when the batch came from one"""
         self = cls.__new__(cls)
         self.params, self.engine, self.t = params, params.engine, int(params.extension_degree())
         self.handle = c_uint64()
@@ -843,7 +844,7 @@ class ResidentBatch(api.ResidentBatch):
         api._check(rc, self.engine.ctx)
         return Enqueued(self.engine, ticket.value, G, verdicts, masks, present)
 
-    def refill(self, inp, record=None, count=None, live=None):
+    def refill(self, inp, record=None, count=None, live=None, shape_vectors=True):
         """bpp_batch_refill_enqueue: new contents of the same shape for this batch (made with form="device") from the
         DevicePackedInput `inp`, enqueued on the engine's stream; an enqueue() afterwards gives what it would give on a fresh upload
         of those arrays.  Nothing is synchronised here: what wrote the arrays must be ordered before the engine's stream (an engine
@@ -859,7 +860,11 @@ class ResidentBatch(api.ResidentBatch):
         bytes (or a raw device address), read when the refill runs on the stream -- byte i non-zero: item i is live.  Dead slots
         may lie anywhere; an enqueue() afterwards gives, for every group with a live item, what it gives on a fresh upload of the
         group's live items alone, with `index` a slot offset inside the group, and a VERDICT_EMPTY record for a group without one.
-        The batch keeps its own copy: the tensor may be overwritten as soon as the refill has run.  None: every item."""
+        The batch keeps its own copy: the tensor may be overwritten as soon as the refill has run.  None: every item.
+        A DeviceMixedInput `inp` (bpp_batch_refill_enqueue_mixed) refills a batch made by from_mixed from a DeviceMixedInput: its
+        proof_lens and m must repeat the batch's vectors, its strides are the source's own; `count` and `live` mean what they mean
+        above, with the fresh mixed upload of the rows in question as the reference.  shape_vectors=False passes no proof_lens / m at
+        all ("the batch's own"): the steady-state form, in which the call touches nothing of size n on the host."""
         import torch
         if live is not None and count is not None:
             raise api.ProofError(api.ProofErrorKind.InvalidArgument, "count and live: a refill takes a live count or a live mask, not both")
@@ -902,9 +907,18 @@ class ResidentBatch(api.ResidentBatch):
             addr = ctypes.c_void_p(record.data_ptr())
         else:
             addr = ctypes.c_void_p(int(record))
+        ticket = c_uint64()
+        if isinstance(inp, DeviceMixedInput):  # (first: it subclasses DevicePackedInput, whose struct goes to the packed calls below)
+            st = _lib.MixedBatch.from_buffer_copy(inp.struct)
+            st.transcript_state, st.transcript_label, st.label_len = None, None, 0
+            if not shape_vectors:
+                st.proof_lens, st.m = None, None
+            rc = self.engine.lib.bpp_batch_refill_enqueue_mixed(self.engine.ctx, self.handle, byref(st), count_addr, live_addr, addr, byref(ticket))
+            api._check(rc, self.engine.ctx)
+            self.input = inp
+            return Refilled(self.engine, ticket.value, record)
         st = _lib.PackedBatch.from_buffer_copy(inp.struct)
         st.transcript_state, st.transcript_label, st.label_len = None, None, 0
-        ticket = c_uint64()
         if live_addr is not None:
             rc = self.engine.lib.bpp_batch_refill_enqueue_live(self.engine.ctx, self.handle, byref(st), live_addr, addr, byref(ticket))
         elif count_addr is None:

@@ -360,8 +360,10 @@ int bpp_ingest_stats(bpp_ctx *ctx, struct bpp_ingest_stats *out);
  * goes through the host form: same results, counted in bpp_ingest_stats (device uploads of this form count in the same three
  * counters).  The staged nonces are wiped on every way out.
  * THE BATCH is an ordinary resident batch: bpp_verify_resident*, the grouped forms, bpp_batch_prepare, bpp_batch_trace and
- * bpp_verify_enqueue take it.  NOT BUILT: bpp_batch_refill_enqueue* refuses it as it refuses every batch the packed device upload
- * did not make (its shape is a vector, not four numbers); there is no pipeline (bpp_verify_submit_packed) or batcher form. */
+ * bpp_verify_enqueue take it.  A batch the _device upload packed on the device is refilled on the stream by
+ * bpp_batch_refill_enqueue_mixed (below, behind the packed refills); bpp_batch_refill_enqueue, _count and _live, which take a
+ * bpp_packed_batch, refuse it as they refuse every batch the packed device upload did not make (its shape is a vector, not four
+ * numbers).  NOT BUILT: a pipeline (bpp_verify_submit_packed) or batcher form. */
 typedef struct {
   size_t n_items;
   const uint8_t *proofs;           /* proof i = RangeProof::to_bytes() at proofs + i * proof_stride, proof_lens[i] bytes */
@@ -677,6 +679,30 @@ int bpp_batch_refill_enqueue_count(bpp_ctx *ctx, uint64_t batch, const bpp_packe
 int bpp_batch_refill_enqueue_live(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev,
                                   const uint8_t *live_dev /* N bytes in device memory; NULL: every item */,
                                   bpp_device_refill *record_dev /* may be NULL */, uint64_t *ticket /* may be NULL */);
+/* ---- a refill of a batch of MIXED aggregation factors ----
+ * bpp_batch_refill_enqueue_mixed is the three calls above for a batch that bpp_batch_upload_mixed_device packed on the device (not its
+ * staged fall-back, not the host mixed form, not a packed or item batch, not one with caller-side challenges or one that hands out
+ * states: refused with a text of this call's own).  The SHAPE such a refill keeps is the vector (proof_lens[i], m[i]) per slot, the
+ * item count, the first byte, and which of seed_nonces32, seed_present, min_values and min_present were given.
+ * `in_dev`: the six array fields are BPP_PTR_THIS_DEVICE addresses, as for the _device upload.  proof_stride and m_stride describe the
+ * SOURCE rows and may differ from the upload's; they must hold the batch's longest proof and largest m.  proof_lens and m are HOST
+ * memory (device memory is refused, field named) and must repeat the batch's vectors entry for entry -- the first differing index and
+ * its field are named -- or are BOTH NULL, "the batch's own vectors": the steady-state form, in which the host touches nothing of
+ * size N.  One without the other is refused.  The transcript fields must be NULL.
+ * count_dev / live_dev: at most one of them (both: refused); NULL and NULL is the plain form.  Their meaning, DEAD SLOTS, the record,
+ * the flags (a count beyond the batch before the fall-back before a finding), FORM, STEADY STATE, stream ownership, secrets and
+ * tickets are those given above, with "a fresh bpp_batch_upload_mixed_device of the same rows" (all of them / the first c / each
+ * group's live rows alone in slot order) in place of the packed upload.  A slot that is not taken -- dead, a construction finding, a
+ * foreign first byte -- is sanitised with ITS OWN lengths: the first byte and proof_lens[i] - 1 zeros, 32 x m[i] zero commitment bytes.
+ * Row slack is never read, and nothing at all of a dead row: the source arrays may end behind the last live row.
+ * Everything is refused before any launch, BPP_ERR_INVALID_ARGUMENT with the reason in bpp_ctx_last_error.
+ * SLOT CLASSES: a producer of mixed traffic sizes one batch as k1 slots of m = 1, k2 of m = 2, ... (each class with its proof
+ * length), uploads it once and refills it under a mask every step, leaving the slots it has no proof for dead.
+ * COST: a dead slot costs what a live one does. */
+int bpp_batch_refill_enqueue_mixed(bpp_ctx *ctx, uint64_t batch, const bpp_mixed_batch *in_dev,
+                                   const uint32_t *count_dev /* one device word, or NULL */,
+                                   const uint8_t *live_dev /* N device bytes, or NULL */,
+                                   bpp_device_refill *record_dev /* may be NULL */, uint64_t *ticket /* may be NULL */);
 /* A diagnostic: enqueues a device-to-device copy of the batch weights that the batch's last enqueued verification used, N x 32
  * canonical bytes, into weights_dev (BPP_PTR_THIS_DEVICE memory); dead slots hold 32 zero bytes.  Allocates nothing and does not
  * wait.  BPP_ERR_INVALID_ARGUMENT for a batch whose last call on the stream was not an enqueue that drew weights. */

@@ -201,6 +201,17 @@ class Engine {
     check(rc, bpp_ctx_last_error(ctx_));
     return t;
   }
+  // The refill of a batch of MIXED aggregation factors made by the device form of the mixed upload (bpp_batch_refill_enqueue_mixed):
+  // in_dev's six arrays are device memory, its proof_lens / m repeat the batch's vectors or are both null (the batch's own).  At most
+  // one of count_dev (one device word) and live_dev (n device bytes) is set; both null: every item.
+  EnqueueTicket batch_refill_enqueue_mixed(uint64_t batch, const bpp_mixed_batch &in_dev, const uint32_t *count_dev = nullptr,
+                                           const uint8_t *live_dev = nullptr, bpp_device_refill *record_dev = nullptr) {
+    EnqueueTicket t;
+    t.ctx_ = ctx_;
+    const int rc = bpp_batch_refill_enqueue_mixed(ctx_, batch, &in_dev, count_dev, live_dev, record_dev, &t.id);
+    check(rc, bpp_ctx_last_error(ctx_));
+    return t;
+  }
   // A diagnostic: the weights of the batch's last enqueued verification, n x 32 bytes into device memory, in stream order
   // (bpp_enqueue_weights); dead slots hold zeros.
   EnqueueTicket enqueue_weights(uint64_t batch, uint8_t *weights_dev) {

@@ -395,6 +395,10 @@ extern "C" {
     // ... under a per-item live mask, N bytes in device memory read on the stream (null: every item)
     pub fn bpp_batch_refill_enqueue_live(ctx: *mut bpp_ctx, batch: u64, in_dev: *const bpp_packed_batch, live_dev: *const u8,
                                          record_dev: *mut bpp_device_refill, ticket: *mut u64) -> c_int;
+    // ... of a batch of mixed aggregation factors: in_dev's proof_lens / m repeat the batch's vectors or are both null; at most one
+    // of count_dev and live_dev
+    pub fn bpp_batch_refill_enqueue_mixed(ctx: *mut bpp_ctx, batch: u64, in_dev: *const bpp_mixed_batch, count_dev: *const u32,
+                                          live_dev: *const u8, record_dev: *mut bpp_device_refill, ticket: *mut u64) -> c_int;
     pub fn bpp_enqueue_weights(ctx: *mut bpp_ctx, batch: u64, weights_dev: *mut u8, ticket: *mut u64) -> c_int;
     pub fn bpp_batcher_verify_action(b: *mut bpp_batcher, input: *const bpp_packed_batch, action: c_int, masks_out: *mut u8,
                                      mask_present: *mut u8, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
