@@ -259,6 +259,22 @@ def build_refill_mixed_harness(force=False):
     return REFILL_MIXED_SANITIZER_BIN
 
 
+ITEM_STATES_SANITIZER_BIN = os.path.join(HERE, "hosttest_item_states_asan")
+
+
+def build_item_states_harness(force=False):
+    """hosttest_item_states.cpp (item_states.h: the one-lane models of k_item_states -- every row, a live count, a live mask -- held to
+    the states table and tr_err_index upload_host.h makes of the equivalent item array, and the row rule of k_states_out) under
+    ASan + UBSan: an executable, run by tests/test_item_states_host.py."""
+    src = os.path.join(CSRC, "hosttest_item_states.cpp")
+    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
+    if not force and not _stale(ITEM_STATES_SANITIZER_BIN, deps):
+        return ITEM_STATES_SANITIZER_BIN
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-fno-omit-frame-pointer", "-o", ITEM_STATES_SANITIZER_BIN, src], check=True, cwd=CSRC)
+    return ITEM_STATES_SANITIZER_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     build_hosttest(force="--force" in sys.argv)

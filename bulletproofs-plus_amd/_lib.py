@@ -197,6 +197,16 @@ SYMBOLS = [
     ("bpp_batch_refill_enqueue_count", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_void_p, c_void_p, POINTER(c_uint64)]),
     ("bpp_batch_refill_enqueue_live", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_void_p, c_void_p, POINTER(c_uint64)]),
     ("bpp_batch_refill_enqueue_mixed", c_int, [c_void_p, c_uint64, POINTER(MixedBatch), c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
+    ("bpp_batch_upload_packed_device_transcripts", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_void_p, POINTER(c_uint64), c_void_p,
+                                                           c_size_t]),
+    ("bpp_batch_upload_mixed_device_transcripts", c_int, [c_void_p, c_uint64, POINTER(MixedBatch), c_void_p, POINTER(c_uint64), c_void_p,
+                                                          c_size_t]),
+    ("bpp_batch_refill_enqueue_transcripts", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_void_p, c_void_p, c_void_p, c_void_p,
+                                                     POINTER(c_uint64)]),
+    ("bpp_batch_refill_enqueue_mixed_transcripts", c_int, [c_void_p, c_uint64, POINTER(MixedBatch), c_void_p, c_void_p, c_void_p, c_void_p,
+                                                           POINTER(c_uint64)]),
+    ("bpp_verify_enqueue_states", c_int, [c_void_p, c_uint64, POINTER(c_uint32), c_size_t, c_size_t, POINTER(c_int), c_int, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, POINTER(c_uint64)]),
     ("bpp_enqueue_weights", c_int, [c_void_p, c_uint64, c_void_p, POINTER(c_uint64)]),
     ("bpp_batcher_verify_action", c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_char_p, c_size_t]),
     ("bpp_batcher_set_limits", c_int, [c_void_p, c_uint32, c_uint32]),

@@ -45,6 +45,7 @@
 #include "verdict.h"
 #include "refill.h"
 #include "refill_mixed.h"
+#include "item_states.h"
 
 using namespace bpp;
 
@@ -454,6 +455,13 @@ struct Batch {
   // per-slot shape of a mixed batch (rounds_bad) no longer holds for the call as a whole (verify_enqueue_locked)
   bool partial_form = false;
   bool enq_weights = false;  // b.weights holds the weights of the batch's last enqueue (bpp_enqueue_weights)
+  // per-item transcripts (item_states.h).  item_states: made by bpp_batch_upload_*_device_transcripts on its device path -- `states`
+  // holds one row per slot, written by k_item_states, and desc[i].state_idx = i; part of the shape the batch keeps: only the
+  // *_transcripts refills take it.  d_state_rows: the rows PASS 1 writes for bpp_verify_enqueue_states, allocated by the first such
+  // call; state_rows_dst: set for the length of that call, the destination of the kernels' STATES instantiation in place of h_states.
+  bool item_states = false;
+  DevBuf<uint32_t> d_state_rows;
+  uint32_t *state_rows_dst = nullptr;
 };
 // what the blocking verify entry points, the sharded and phased forms and the traces answer for a refilled batch: they decide by the
 // host copies above, which describe other contents
@@ -1951,7 +1959,7 @@ uint64_t upload_device(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t
     B->cols = 2 * B->max_mn + P.t + 1;
     // device copies (all sources page-locked: the copies are real stream-ordered DMA)
     B->bytes.alloc(bytes_len);
-    B->states.alloc(states.size());
+    if (!(resident && B->item_states)) B->states.alloc(states.size());  // (else: one row per item, written by k_item_states)
     // (a buffer that holds secrets at times starts out zero: a batch that fails before anything is written to it leaves no stale
     // bytes of an earlier allocation there for bpp_batch_secret_bytes to count)
     auto alloc_zeroed = [&](DevBuf<uint8_t> &buf, size_t count) {
@@ -2115,15 +2123,19 @@ int device_pointer_kind(int device, const void *p) {
 
 // The fall-back: a batch the arithmetic layout does not fit (mixed first bytes, no proofs, a stride below the length) is copied to
 // page-locked staging and takes the host path, item form and all.  The staged nonces are wiped on every way out.
-uint64_t upload_packed_device_fallback(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t params, const bpp_packed_batch &in) {
-  const size_t n = in.n_items, nm = n * (size_t)in.m;
+// item_states (the *_transcripts upload, else null): the state rows are staged with the rest and the batch goes through the item form,
+// item i under row i.
+uint64_t upload_packed_device_fallback(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t params, const bpp_packed_batch &in,
+                                       const uint8_t *item_states = nullptr) {
+  const size_t n = in.n_items, nm = n * (size_t)in.m, n_states = item_states ? n * (size_t)BPP_ITEM_STATE_BYTES : 0;
   const bool strided = in.proofs && in.proof_len >= 1 && in.proof_stride > in.proof_len;  // staged back to back
   const bool no_bytes = !in.proofs || in.proof_len < 1;  // (empty proofs: the item form reads none of them, whatever the stride)
   const size_t proofs_n = no_bytes ? 0 : (strided ? n * in.proof_len : (n - 1) * in.proof_stride + in.proof_len);
   auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
   const size_t o_proofs = 0, o_commit = up16(proofs_n), o_minv = up16(o_commit + (in.commitments32 ? nm * 32 : 0)),
                o_minp = up16(o_minv + (in.min_values ? nm * 8 : 0)), o_seedp = up16(o_minp + (in.min_present ? nm : 0)),
-               o_seed = up16(o_seedp + (in.seed_present ? n : 0)), n_seed = in.seed_nonces32 ? n * 32 : 0, total = o_seed + n_seed;
+               o_states = up16(o_seedp + (in.seed_present ? n : 0)), o_seed = up16(o_states + n_states), n_seed = in.seed_nonces32 ? n * 32 : 0,
+               total = o_seed + n_seed;
   ctx->pin_fallback.resize(total + 16);
   uint8_t *st = ctx->pin_fallback.data();
   hipStream_t s = ctx->stream;
@@ -2152,19 +2164,61 @@ uint64_t upload_packed_device_fallback(bpp_ctx *ctx, const std::shared_ptr<Param
   host.min_present = fetch(in.min_present, o_minp, nm);
   host.seed_present = fetch(in.seed_present, o_seedp, n);
   host.seed_nonces32 = fetch(in.seed_nonces32, o_seed, n_seed);
+  const uint8_t *states = fetch(item_states, o_states, n_states);
   HIP_CHECK(hipStreamSynchronize(s));
   ctx->ingest_stats.host_fallback_calls++;
   ctx->ingest_stats.fallback_bytes += proofs_n + (in.commitments32 ? nm * 32 : 0) + (in.min_values ? nm * 8 : 0) + (in.min_present ? nm : 0) +
-                                      (in.seed_present ? n : 0) + n_seed;
+                                      (in.seed_present ? n : 0) + n_seed + n_states;
   UploadPlan pl;
   PlanWipe wipe_plan{pl};
-  upload_host_pack(ctx, *Pp, nullptr, n, &host, pl);
+  if (states) {
+    std::vector<bpp_verify_item> items;
+    upload_packed_as_items(host, items);
+    for (size_t i = 0; i < n; i++) items[i].transcript_state = states + i * (size_t)BPP_ITEM_STATE_BYTES;
+    upload_host_pack(ctx, *Pp, items.data(), n, nullptr, pl);
+  } else {
+    upload_host_pack(ctx, *Pp, nullptr, n, &host, pl);
+  }
   return upload_device(ctx, Pp, params, pl, nullptr, nullptr);
 }
 
-int upload_packed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, uint64_t *batch, char *errbuf, size_t errbuf_len) {
+// what the two *_transcripts uploads refuse before anything else is looked at: the struct's own transcript fields, and a state array
+// that is null or not this device's memory.  Empty: nothing to refuse.
+std::string item_states_refusal(bpp_ctx *ctx, const uint8_t *transcript_state, const uint8_t *transcript_label, const uint8_t *item_states,
+                                const char *name) {
+  static const char *const kinds[] = {"", "memory of another device", "host memory or memory the runtime does not know", "managed memory"};
+  if (transcript_state) return std::string("transcript_state must be null: item i is verified under row i of ") + name;
+  if (transcript_label) return std::string("transcript_label must be null: item i is verified under row i of ") + name;
+  if (!item_states) return std::string(name) + " is null";
+  const int kind = device_pointer_kind(ctx->device, item_states);
+  if (kind != BPP_PTR_THIS_DEVICE) return std::string(name) + " is not device memory of this context's device (" + kinds[kind] + ")";
+  return std::string();
+}
+
+// k_item_states behind the ingest kernel of an upload: every row of the run is live; the finding goes into the ingest result word
+void launch_item_states_upload(bpp_ctx *ctx, Batch &B, const uint8_t *item_states, size_t n_items, size_t n_run) {
+  B.states.alloc(n_items * (size_t)BPP_ITEM_STATE_BYTES);
+  const ItemStates a{item_states, B.states.p, (uint32_t)n_items, (uint32_t)n_run, ctx->ingest_res.p + BPP_ING_RES_FINDING, nullptr, nullptr};
+  hipLaunchKernelGGL(k_item_states, dim3((uint32_t)cdiv((uint32_t)n_items, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0,
+                     ctx->stream, a);
+  HIP_CHECK(hipGetLastError());
+}
+
+// the plan of such a batch: no table from the host, item i under row i
+void plan_item_states(UploadPlan &pl) {
+  pl.states.clear();
+  for (size_t i = 0; i < pl.desc.size(); i++) pl.desc[i].state_idx = (uint32_t)i;
+}
+
+// with_states (bpp_batch_upload_packed_device_transcripts): item i is verified under row i of item_states (item_states.h)
+int upload_packed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, uint64_t *batch, char *errbuf, size_t errbuf_len,
+                              bool with_states = false, const uint8_t *item_states = nullptr) {
   try {
     if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty", errbuf, errbuf_len);
+    if (with_states) {
+      const std::string refusal = item_states_refusal(ctx, in->transcript_state, in->transcript_label, item_states, "item_states203");
+      if (!refusal.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, refusal, errbuf, errbuf_len);
+    }
     // pointer kinds first: nothing is allocated or launched for an array this device cannot read, and no array is ever
     // dereferenced on the host
     const struct {
@@ -2187,7 +2241,7 @@ int upload_packed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_packed_ba
     if (n_items > (1u << 24)) return fail(ctx, BPP_ERR_SIZE_OVERFLOW, "batch too large", errbuf, errbuf_len);
     const ParamShape shape{Pp->n_bits, Pp->m_max, Pp->t};
     if (!ingest_host_prelude(*in, shape)) {
-      *batch = upload_packed_device_fallback(ctx, Pp, params, *in);
+      *batch = upload_packed_device_fallback(ctx, Pp, params, *in, item_states);
       return BPP_OK;
     }
     hipStream_t s = ctx->stream;
@@ -2210,6 +2264,7 @@ int upload_packed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_packed_ba
     B->seeds_dirty = in->seed_nonces32 != nullptr;
     hipLaunchKernelGGL(k_ingest_packed, dim3((uint32_t)cdiv((uint32_t)n_items, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, a);
     HIP_CHECK(hipGetLastError());
+    if (with_states) launch_item_states_upload(ctx, *B, item_states, n_items, n_items);
     uint32_t *res = ctx->pin_ingest.data();
     HIP_CHECK(hipMemcpyAsync(res, ctx->ingest_res.p, BPP_ING_RES_WORDS * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
@@ -2217,7 +2272,7 @@ int upload_packed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_packed_ba
       wipe_batch_secrets(*B, s);
       (void)hipStreamSynchronize(s);
       ctx->spare_batch = std::move(B);  // its buffers serve the host path's batch
-      *batch = upload_packed_device_fallback(ctx, Pp, params, *in);
+      *batch = upload_packed_device_fallback(ctx, Pp, params, *in, item_states);
       return BPP_OK;
     }
     const uint8_t *info = nullptr;
@@ -2229,6 +2284,8 @@ int upload_packed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_packed_ba
     }
     UploadPlan pl;
     ingest_finish_plan(*in, shape, res, info, pl);  // throws the lowest-index construction finding
+    if (with_states) plan_item_states(pl);
+    B->item_states = with_states;
     ctx->ingest_stats.device_calls++;
     *batch = upload_device(ctx, Pp, params, pl, nullptr, nullptr, std::move(B));
     // the shape a refill of this batch must keep (bpp_batch_refill_enqueue): everything the plan above was made from but the bytes
@@ -2269,13 +2326,16 @@ int upload_mixed_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, 
 
 // The fall-back of the device form: the arrays are copied to page-locked staging as they lie (rows, slack and all, up to the last
 // byte the last row uses) and the batch takes the host form.  The staged nonces are wiped on every way out.
-uint64_t upload_mixed_device_fallback(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t params, const bpp_mixed_batch &in) {
+uint64_t upload_mixed_device_fallback(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t params, const bpp_mixed_batch &in,
+                                      const uint8_t *item_states = nullptr) {
   const size_t n = in.n_items, last_m = in.m[n - 1], row_entries = (n - 1) * (size_t)in.m_stride + last_m;
+  const size_t n_states = item_states ? n * (size_t)BPP_ITEM_STATE_BYTES : 0;
   const size_t proofs_n = in.proofs ? (n - 1) * in.proof_stride + in.proof_lens[n - 1] : 0;
   auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
   const size_t o_proofs = 0, o_commit = up16(proofs_n), o_minv = up16(o_commit + (in.commitments32 ? row_entries * 32 : 0)),
                o_minp = up16(o_minv + (in.min_values ? row_entries * 8 : 0)), o_seedp = up16(o_minp + (in.min_present ? row_entries : 0)),
-               o_seed = up16(o_seedp + (in.seed_present ? n : 0)), n_seed = in.seed_nonces32 ? n * 32 : 0, total = o_seed + n_seed;
+               o_states = up16(o_seedp + (in.seed_present ? n : 0)), o_seed = up16(o_states + n_states), n_seed = in.seed_nonces32 ? n * 32 : 0,
+               total = o_seed + n_seed;
   ctx->pin_fallback.resize(total + 16);
   uint8_t *st = ctx->pin_fallback.data();
   hipStream_t s = ctx->stream;
@@ -2297,21 +2357,29 @@ uint64_t upload_mixed_device_fallback(bpp_ctx *ctx, const std::shared_ptr<Params
   host.min_present = fetch(in.min_present, o_minp, row_entries);
   host.seed_present = fetch(in.seed_present, o_seedp, n);
   host.seed_nonces32 = fetch(in.seed_nonces32, o_seed, n_seed);
+  const uint8_t *states = fetch(item_states, o_states, n_states);
   HIP_CHECK(hipStreamSynchronize(s));
   ctx->ingest_stats.host_fallback_calls++;
   ctx->ingest_stats.fallback_bytes += proofs_n + (in.commitments32 ? row_entries * 32 : 0) + (in.min_values ? row_entries * 8 : 0) +
-                                      (in.min_present ? row_entries : 0) + (in.seed_present ? n : 0) + n_seed;
+                                      (in.min_present ? row_entries : 0) + (in.seed_present ? n : 0) + n_seed + n_states;
   std::vector<bpp_verify_item> items;
   upload_mixed_as_items(host, items);
+  for (size_t i = 0; states && i < n; i++) items[i].transcript_state = states + i * (size_t)BPP_ITEM_STATE_BYTES;
   UploadPlan pl;
   PlanWipe wipe_plan{pl};
   upload_host_pack(ctx, *Pp, items.data(), n, nullptr, pl);
   return upload_device(ctx, Pp, params, pl, nullptr, nullptr);
 }
 
-int upload_mixed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, uint64_t *batch, char *errbuf, size_t errbuf_len) {
+// with_states (bpp_batch_upload_mixed_device_transcripts): item i is verified under row i of item_states (item_states.h)
+int upload_mixed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, uint64_t *batch, char *errbuf, size_t errbuf_len,
+                             bool with_states = false, const uint8_t *item_states = nullptr) {
   try {
     if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty", errbuf, errbuf_len);
+    if (with_states) {
+      const std::string refusal = item_states_refusal(ctx, in->transcript_state, in->transcript_label, item_states, "item_states203");
+      if (!refusal.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, refusal, errbuf, errbuf_len);
+    }
     // pointer kinds first, as in upload_packed_device_impl: the six arrays are never dereferenced on the host, the two host arrays
     // are, and so must not be memory of a device
     const struct {
@@ -2343,7 +2411,7 @@ int upload_mixed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batc
     const ParamShape shape{Pp->n_bits, Pp->m_max, Pp->t};
     IngestMixedPrelude pre;
     if (!ingest_mixed_host_prelude(*in, shape, pre)) {
-      *batch = upload_mixed_device_fallback(ctx, Pp, params, *in);
+      *batch = upload_mixed_device_fallback(ctx, Pp, params, *in, item_states);
       return BPP_OK;
     }
     if (pre.h == 0) ingest_mixed_throw_finding(pre, n_items, nullptr);  // item 0's, host-known: nothing to run
@@ -2377,6 +2445,7 @@ int upload_mixed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batc
     B->seeds_dirty = in->seed_nonces32 != nullptr;
     hipLaunchKernelGGL(k_ingest_mixed, dim3((uint32_t)cdiv(a.n_run, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, a);
     HIP_CHECK(hipGetLastError());
+    if (with_states) launch_item_states_upload(ctx, *B, item_states, n_items, a.n_run);  // (rows at and beyond the host's finding: not read)
     uint32_t *res = ctx->pin_ingest.data();
     HIP_CHECK(hipMemcpyAsync(res, ctx->ingest_res.p, BPP_ING_RES_WORDS * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
@@ -2384,7 +2453,7 @@ int upload_mixed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batc
       wipe_batch_secrets(*B, s);
       (void)hipStreamSynchronize(s);
       ctx->spare_batch = std::move(B);  // its buffers serve the host path's batch
-      *batch = upload_mixed_device_fallback(ctx, Pp, params, *in);
+      *batch = upload_mixed_device_fallback(ctx, Pp, params, *in, item_states);
       return BPP_OK;
     }
     ingest_mixed_throw_finding(pre, n_items, res);  // (h < n_items: the call ends here either way, nothing else is fetched)
@@ -2397,6 +2466,8 @@ int upload_mixed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batc
     }
     UploadPlan pl;
     ingest_mixed_finish_plan(*in, shape, pre, res, info, pl);
+    if (with_states) plan_item_states(pl);
+    B->item_states = with_states;
     ctx->ingest_stats.device_calls++;
     *batch = upload_device(ctx, Pp, params, pl, nullptr, nullptr, std::move(B));
     Batch &made = *ctx->batches[*batch];
@@ -2438,6 +2509,18 @@ int bpp_batch_upload_packed_device(bpp_ctx *ctx, uint64_t params, const bpp_pack
                                    size_t errbuf_len) {
   BPP_ENTRY(ctx);
   return upload_packed_device_impl(ctx, params, in, batch, errbuf, errbuf_len);
+}
+
+int bpp_batch_upload_packed_device_transcripts(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, const uint8_t *item_states203,
+                                               uint64_t *batch, char *errbuf, size_t errbuf_len) {
+  BPP_ENTRY(ctx);
+  return upload_packed_device_impl(ctx, params, in, batch, errbuf, errbuf_len, true, item_states203);
+}
+
+int bpp_batch_upload_mixed_device_transcripts(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, const uint8_t *item_states203,
+                                              uint64_t *batch, char *errbuf, size_t errbuf_len) {
+  BPP_ENTRY(ctx);
+  return upload_mixed_device_impl(ctx, params, in, batch, errbuf, errbuf_len, true, item_states203);
 }
 
 int bpp_device_pointer_check(bpp_ctx *ctx, const void *p, int *kind) {
@@ -2623,14 +2706,18 @@ void enqueue_phase1(bpp_ctx *ctx, Batch &b, StageTimer &tm, bool pass1_only, uin
     const int force_wave = ctx->opt.transcripts_wave;  // (tests force either kernel)
     const bool wave = force_wave >= 0 ? force_wave != 0 : b.B <= BPP_TRANSCRIPTS_WAVE_MAX;
     uint8_t *rng_host = fetch_rng ? b.h_rng.dev() : nullptr;  // mapped page-locked memory: no device-to-host copy behind PASS 1
-    if (b.want_states) {  // the kernels' other instantiation: every proof's advanced transcript into b.h_states as well
-      b.h_states.resize((size_t)b.B * BPP_STATE_ROW_WORDS);
+    if (b.want_states || b.state_rows_dst) {  // the kernels' other instantiation: every proof's advanced transcript into b.h_states as well
+      uint32_t *rows_dst = b.state_rows_dst;  // (bpp_verify_enqueue_states: device memory of the batch, nothing for the host)
+      if (!rows_dst) {
+        b.h_states.resize((size_t)b.B * BPP_STATE_ROW_WORDS);
+        rows_dst = b.h_states.dev();
+      }
       if (wave)
         hipLaunchKernelGGL(k_transcripts_wave<true>, dim3(b.B), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.minvals.p, b.states.p,
-                           P.d_hg32.p, P.n_bits, P.t, b.B, b.cs, b.chal.p, b.rng_out.p, b.status.p, rng_host, b.h_states.dev());
+                           P.d_hg32.p, P.n_bits, P.t, b.B, b.cs, b.chal.p, b.rng_out.p, b.status.p, rng_host, rows_dst);
       else
         hipLaunchKernelGGL(k_transcripts<true>, dim3(cdiv(b.B, 64)), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.minvals.p, b.states.p,
-                           P.d_hg32.p, P.n_bits, P.t, b.B, b.cs, b.chal.p, b.rng_out.p, b.status.p, rng_host, b.h_states.dev());
+                           P.d_hg32.p, P.n_bits, P.t, b.B, b.cs, b.chal.p, b.rng_out.p, b.status.p, rng_host, rows_dst);
     } else if (wave)
       hipLaunchKernelGGL(k_transcripts_wave<false>, dim3(b.B), dim3(64), 0, s, b.bytes.p, b.d_desc.p, b.minvals.p, b.states.p,
                          P.d_hg32.p, P.n_bits, P.t, b.B, b.cs, b.chal.p, b.rng_out.p, b.status.p, rng_host, (uint32_t *)nullptr);
@@ -3490,13 +3577,19 @@ bool layout_is_current(const Batch &b, size_t chunk, const std::vector<uint32_t>
   return b.last_chunk == (chunk == (size_t)-1 ? 0 : chunk);
 }
 
+// with_states (bpp_verify_enqueue_states): PASS 1 runs in its STATES form into device rows of the batch, and k_states_out hands the
+// rows of Ok groups' live slots to states_out_dev behind k_verdict_finish (item_states.h); everything else is the same call.
 int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first, size_t n_groups, size_t chunk, const int *actions,
-                          int action_all, bpp_device_verdict *verdicts_dev, uint8_t *masks_dev, uint8_t *mask_present_dev, uint64_t *ticket) {
+                          int action_all, bpp_device_verdict *verdicts_dev, uint8_t *masks_dev, uint8_t *mask_present_dev, uint64_t *ticket,
+                          bool with_states = false, uint8_t *states_out_dev = nullptr) {
   try {
     auto it = ctx->batches.find(batch);
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
     if (!verdicts_dev || !ticket) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+    if (with_states && !states_out_dev) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "states_out203_dev is null");
     Batch &b = *it->second;
+    if (with_states && b.ext_challenges)
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "no transcript states: the caller replayed PASS 1 of this batch");
     std::vector<uint32_t> bounds;
     if (group_first) {
       if (n_groups == 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
@@ -3516,8 +3609,9 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
     if (ctx->opt.verify_check == 1 && ctx->verify_check_off <= 0)
       return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "\"verify_check\" = 1: a rejection is rechecked by decisions of the host, which an enqueued call cannot make");
     if (b.want_states) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "the batch hands out transcript states: an enqueued call cannot");
-    const struct { const void *p; const char *name; bool required; } bufs[3] = {
-        {verdicts_dev, "verdicts_dev", true}, {masks_dev, "masks_dev", false}, {mask_present_dev, "mask_present_dev", false}};
+    const struct { const void *p; const char *name; bool required; } bufs[4] = {
+        {verdicts_dev, "verdicts_dev", true}, {masks_dev, "masks_dev", false}, {mask_present_dev, "mask_present_dev", false},
+        {states_out_dev, "states_out203_dev", with_states}};
     for (const auto &f : bufs) {
       if (!f.p && !f.required) continue;
       const int kind = device_pointer_kind(ctx->device, f.p);
@@ -3580,6 +3674,10 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
       es.layouts_in_call++;
     }
     const uint32_t G = b.G;
+    // the rows PASS 1 writes for this call (the batch's first such call allocates them; no kernel in flight reads them)
+    if (with_states) b.d_state_rows.alloc((size_t)b.B * BPP_STATE_ROW_WORDS);
+    b.state_rows_dst = with_states ? b.d_state_rows.p : nullptr;
+    ScopeExit rows_off{[&] { b.state_rows_dst = nullptr; }};
     // ---- the per-group actions where the last kernel reads them
     const int *actions_dev = nullptr;
     if (actions) {
@@ -3657,6 +3755,10 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
     else
       hipLaunchKernelGGL(k_verdict_finish<false>, dim3(G), dim3(64), 0, s, keys, identity, actions_dev, action_all, zero_word, zero_word + 1,
                          b.group_first.p, G, b.d_desc.p, mask_rows, (uint32_t)(P.t * 2), verdicts_dev, (uint4 *)masks_dev, mask_present_dev, state, lv);
+    if (with_states) {  // (a call that ran no PASS 1 has no Ok group: every row is zero and the rows buffer is not looked at)
+      const StatesOut so{b.d_state_rows.p, BPP_STATE_ROW_WORDS, states_out_dev, verdicts_dev, b.group_first.p, G, b.B, lv};
+      hipLaunchKernelGGL(k_states_out, dim3(cdiv(b.B, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, so);
+    }
     HIP_CHECK(hipGetLastError());
     const uint64_t t = ctx->enq_next++;
     HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));
@@ -3703,12 +3805,31 @@ std::string refill_pointer_refusal(bpp_ctx *ctx, const void *proofs, const void 
   return std::string();
 }
 
+// per-item transcripts are part of the shape a batch keeps: the *_transcripts refills take only batches the *_transcripts uploads made,
+// the other refills refuse those; either text names the call to use instead.  Then the call's own state pointer.  Empty: nothing to refuse.
+std::string refill_item_states_refusal(bpp_ctx *ctx, const Batch &b, bool with_states, const uint8_t *item_states_dev, bool mixed) {
+  const std::string with = mixed ? "bpp_batch_refill_enqueue_mixed_transcripts" : "bpp_batch_refill_enqueue_transcripts";
+  const std::string without = mixed ? "bpp_batch_refill_enqueue_mixed" : "bpp_batch_refill_enqueue / _count / _live";
+  if (b.item_states && !with_states)
+    return "the batch was uploaded with per-item transcripts and every refill brings its rows: use " + with;
+  if (!b.item_states && with_states)
+    return "the batch was not uploaded with per-item transcripts (bpp_batch_upload_*_device_transcripts) and keeps its one transcript: use " + without;
+  if (!with_states) return std::string();
+  if (!item_states_dev) return "item_states203_dev is null";
+  const int kind = device_pointer_kind(ctx->device, item_states_dev);
+  if (kind != BPP_PTR_THIS_DEVICE) return "item_states203_dev: not device memory of the context's device (pointer kind " + std::to_string(kind) + ")";
+  if (b.states.n < (size_t)b.B * BPP_ITEM_STATE_BYTES) return "refill: the batch's state table does not fit its recorded shape";
+  return std::string();
+}
+
 // The common tail of the two refill drivers, behind their refusals: the batch's first-call allocations, the form flags, the launches
 // and the ticket.  `launch_refill(s, masked)` makes the driver's kernel arguments -- the batch's words and mask exist by then -- and
 // launches its refill kernel in the plain/count or the masked form; k_refill_finish and the decompression of the commitments follow it.
+// item_states_dev (a batch with per-item transcripts, else null): k_item_states follows the refill kernel -- it reads the batch's
+// normalised mask that kernel wrote -- and reduces into the same finding word in front of k_refill_finish.
 template <class LaunchRefill>
 void refill_enqueue_tail(bpp_ctx *ctx, Batch &b, bool nonces, const uint32_t *count_dev, const uint8_t *live_dev, bpp_device_refill *record_dev,
-                         uint64_t *ticket, LaunchRefill &&launch_refill) {
+                         uint64_t *ticket, const uint8_t *item_states_dev, LaunchRefill &&launch_refill) {
   const size_t n = b.B;
   hipStream_t s = ctx->stream;
   struct bpp_refill_stats &rs = ctx->refill_stats;
@@ -3738,6 +3859,11 @@ void refill_enqueue_tail(bpp_ctx *ctx, Batch &b, bool nonces, const uint32_t *co
   b.refilled = true;  // from here on the contents are the stream's, whatever becomes of the launches
   b.seeds_dirty = nonces;
   launch_refill(s, b.mask_form);
+  if (item_states_dev) {
+    const ItemStates a{item_states_dev, b.states.p, (uint32_t)n, (uint32_t)n, b.refill_red.p + BPP_REFILL_RED_FINDING, count_dev,
+                       b.mask_form ? (const uint8_t *)b.refill_mask.p : (const uint8_t *)nullptr};
+    hipLaunchKernelGGL(k_item_states, dim3((uint32_t)cdiv((uint32_t)n, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, a);
+  }
   // (under a mask nothing is clamped and the batch's count word is left alone: the later kernels do not read it in that form)
   hipLaunchKernelGGL(k_refill_finish, dim3(1), dim3(64), 0, s, b.refill_red.p, b.refill_state.p, record_dev, count_dev, (uint32_t)n,
                      (b.has_live && !b.mask_form) ? b.refill_live.p : (uint32_t *)nullptr);
@@ -3756,7 +3882,7 @@ void refill_enqueue_tail(bpp_ctx *ctx, Batch &b, bool nonces, const uint32_t *co
 }
 
 int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in, const uint32_t *count_dev, const uint8_t *live_dev,
-                        bpp_device_refill *record_dev, uint64_t *ticket) {
+                        bpp_device_refill *record_dev, uint64_t *ticket, bool with_states = false, const uint8_t *item_states_dev = nullptr) {
   try {
     auto it = ctx->batches.find(batch);
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
@@ -3766,6 +3892,9 @@ int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in
       return fail(ctx, BPP_ERR_INVALID_ARGUMENT,
                   "the batch cannot be refilled: only a batch that bpp_batch_upload_packed_device packed on the device records its shape (not the "
                   "item form, the host packed form, the staged fall-back, caller-side challenges or a batch that hands out states)");
+    if (count_dev && live_dev) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "count_dev and live_dev: a refill takes a live count or a live mask, not both");
+    const std::string states_refusal = refill_item_states_refusal(ctx, b, with_states, item_states_dev, false);
+    if (!states_refusal.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, states_refusal);
     const Batch::RefillShape &sh = b.refill_shape;
     const struct {
       const char *name;
@@ -3780,7 +3909,8 @@ int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in
       if (!f.same) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(f.name) + " differs from the batch's shape: a refill keeps the shape of the upload");
     if (in->proof_stride < in->proof_len) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proof_stride is below proof_len");
     if (in->transcript_state || in->transcript_label)
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "transcript_state / transcript_label must be null: a refilled batch keeps its transcript");
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, with_states ? "transcript_state / transcript_label must be null: item i is verified under row i of item_states203_dev"
+                                                             : "transcript_state / transcript_label must be null: a refilled batch keeps its transcript");
     if (!in->proofs || !in->commitments32) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proofs / commitments32: null");
     const std::string refusal = refill_pointer_refusal(ctx, in->proofs, in->commitments32, in->min_values, in->min_present, in->seed_nonces32,
                                                        in->seed_present, record_dev, count_dev, live_dev);
@@ -3792,7 +3922,7 @@ int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in
         b.d_desc.n < n || b.status0.n < n || b.status.n < n || b.masks.n < n * (size_t)P.t * 32 || b.sum_m != n * sh.m)
       throw EngineError{BPP_ERR_ENGINE, "refill: the batch's buffers do not fit its recorded shape"};
     const ParamShape shape_p{P.n_bits, P.m_max, P.t};
-    refill_enqueue_tail(ctx, b, sh.nonces, count_dev, live_dev, record_dev, ticket, [&](hipStream_t s, bool masked) {
+    refill_enqueue_tail(ctx, b, sh.nonces, count_dev, live_dev, record_dev, ticket, item_states_dev, [&](hipStream_t s, bool masked) {
       const RefillPacked r = refill_args(*in, shape_p, (uint8_t)sh.t0, b.bytes.p, b.minvals.p, b.seeds.p, b.d_defer.p, b.d_desc.p, b.status0.p,
                                          b.status.p, reinterpret_cast<uint32_t *>(b.masks.p), b.refill_red.p, count_dev, live_dev,
                                          b.refill_mask.p);
@@ -3810,7 +3940,7 @@ int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in
 // arrays that must repeat it, or both null -- then nothing of size N is touched here.  The strides are the SOURCE's and need only hold
 // the batch's longest row.  Everything is refused before the tail, which is batch_refill_locked's.
 int batch_refill_mixed_locked(bpp_ctx *ctx, uint64_t batch, const bpp_mixed_batch *in, const uint32_t *count_dev, const uint8_t *live_dev,
-                              bpp_device_refill *record_dev, uint64_t *ticket) {
+                              bpp_device_refill *record_dev, uint64_t *ticket, bool with_states = false, const uint8_t *item_states_dev = nullptr) {
   try {
     auto it = ctx->batches.find(batch);
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
@@ -3824,6 +3954,8 @@ int batch_refill_mixed_locked(bpp_ctx *ctx, uint64_t batch, const bpp_mixed_batc
                   "that hands out states)");
     const Batch::RefillShape &sh = b.refill_shape;
     if (count_dev && live_dev) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "count_dev and live_dev: a refill takes a live count or a live mask, not both");
+    const std::string states_refusal = refill_item_states_refusal(ctx, b, with_states, item_states_dev, true);
+    if (!states_refusal.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, states_refusal);
     const struct {
       const char *name;
       bool same;
@@ -3850,7 +3982,8 @@ int batch_refill_mixed_locked(bpp_ctx *ctx, uint64_t batch, const bpp_mixed_batc
       return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proof_stride is below the batch's largest proof_len (" + std::to_string(ms.max_proof_len) + ")");
     if (in->m_stride < ms.max_m) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m_stride is below the batch's largest m (" + std::to_string(ms.max_m) + ")");
     if (in->transcript_state || in->transcript_label)
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "transcript_state / transcript_label must be null: a refilled batch keeps its transcript");
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, with_states ? "transcript_state / transcript_label must be null: item i is verified under row i of item_states203_dev"
+                                                             : "transcript_state / transcript_label must be null: a refilled batch keeps its transcript");
     if (!in->proofs || !in->commitments32) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proofs / commitments32: null");
     const std::string refusal = refill_pointer_refusal(ctx, in->proofs, in->commitments32, in->min_values, in->min_present, in->seed_nonces32,
                                                        in->seed_present, record_dev, count_dev, live_dev);
@@ -3869,7 +4002,7 @@ int batch_refill_mixed_locked(bpp_ctx *ctx, uint64_t batch, const bpp_mixed_batc
         (uint64_t)ms.rows[n - 1].minval_idx + ms.rows[n - 1].m != b.sum_m || (uint64_t)ms.rows[n - 1].proof_off + ms.rows[n - 1].proof_len != ms.proof_bytes)
       throw EngineError{BPP_ERR_ENGINE, "refill: the batch's buffers do not fit its recorded shape"};
     const ParamShape shape_p{P.n_bits, P.m_max, P.t};
-    refill_enqueue_tail(ctx, b, sh.nonces, count_dev, live_dev, record_dev, ticket, [&](hipStream_t s, bool masked) {
+    refill_enqueue_tail(ctx, b, sh.nonces, count_dev, live_dev, record_dev, ticket, item_states_dev, [&](hipStream_t s, bool masked) {
       const RefillMixed r = refill_mixed_args(*in, shape_p, (uint8_t)sh.t0, b.mixed_table.p, n, ms.proof_bytes, b.sum_m, b.bytes.p, b.minvals.p,
                                               b.seeds.p, b.d_defer.p, b.d_desc.p, b.status0.p, b.status.p, reinterpret_cast<uint32_t *>(b.masks.p),
                                               b.refill_red.p, count_dev, live_dev, b.refill_mask.p);
@@ -3983,6 +4116,29 @@ int bpp_batch_refill_enqueue_mixed(bpp_ctx *ctx, uint64_t batch, const bpp_mixed
                                    bpp_device_refill *record_dev, uint64_t *ticket) {
   BPP_ENTRY(ctx);
   return batch_refill_mixed_locked(ctx, batch, in_dev, count_dev, live_dev, record_dev, ticket);
+}
+
+// ---- per-item transcripts (item_states.h): the refills of a batch the *_transcripts uploads made, and the enqueue that hands the
+// advanced transcripts back on the stream
+int bpp_batch_refill_enqueue_transcripts(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev, const uint8_t *item_states203_dev,
+                                         const uint32_t *count_dev, const uint8_t *live_dev, bpp_device_refill *record_dev, uint64_t *ticket) {
+  BPP_ENTRY(ctx);
+  return batch_refill_locked(ctx, batch, in_dev, count_dev, live_dev, record_dev, ticket, true, item_states203_dev);
+}
+
+int bpp_batch_refill_enqueue_mixed_transcripts(bpp_ctx *ctx, uint64_t batch, const bpp_mixed_batch *in_dev, const uint8_t *item_states203_dev,
+                                               const uint32_t *count_dev, const uint8_t *live_dev, bpp_device_refill *record_dev,
+                                               uint64_t *ticket) {
+  BPP_ENTRY(ctx);
+  return batch_refill_mixed_locked(ctx, batch, in_dev, count_dev, live_dev, record_dev, ticket, true, item_states203_dev);
+}
+
+int bpp_verify_enqueue_states(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first, size_t n_groups, size_t chunk, const int *actions,
+                              int action_all, bpp_device_verdict *verdicts_dev, uint8_t *masks_dev, uint8_t *mask_present_dev,
+                              uint8_t *states_out203_dev, uint64_t *ticket) {
+  BPP_ENTRY(ctx);
+  return verify_enqueue_locked(ctx, batch, group_first, n_groups, chunk, actions, action_all, verdicts_dev, masks_dev, mask_present_dev, ticket,
+                               true, states_out203_dev);
 }
 
 // (a diagnostic: one device-to-device copy on the stream behind the batch's last enqueue)

@@ -163,7 +163,7 @@ class DevicePackedInput:
     (Engine(stream=torch.cuda.current_stream().cuda_stream)); `.synchronised` says which it was.  With raw addresses the caller orders."""
 
     def __init__(self, proofs, commitments, min_values=None, min_present=None, seed_nonces=None, label=b"", seed_present=None, state=None,
-                 proof_stride=None):
+                 proof_stride=None, item_states=None):
         self._keep, self.device_index, self._torch, self.synchronised = [], None, False, False
         addr_p, shape, stride = self._array(proofs, "proofs", 1, rows=True)
         if len(shape) != 2:
@@ -190,6 +190,20 @@ class DevicePackedInput:
                                        opt(min_present, "min_present", 1, (n, m)), opt(seed_nonces, "seed_nonces", 1, (n, 32)),
                                        opt(seed_present, "seed_present", 1, (n,)), None if self.state is None else self.state.ctypes.data,
                                        self.label.ctypes.data, len(label))
+        self._item_states(item_states, n, opt)
+
+    def _item_states(self, item_states, n, opt):
+        """item_states= (per-item transcripts, the *_transcripts calls of include/bpp.h): a uint8 [n, 203] device tensor (any byte
+        address: a slice of a larger tensor will do) or an (address, (n, 203)) pair; row i is the STROBE state item i is verified under.
+        Such an input goes through bpp_batch_upload_*_device_transcripts / bpp_batch_refill_enqueue*_transcripts: label and state
+        are not passed on."""
+        self.item_states = None if item_states is None else ctypes.c_void_p(opt(item_states, "item_states", 1, (n, 203)))
+
+    def struct_without_transcript(self):
+        """a copy of .struct with the transcript fields null, as the refills and the *_transcripts uploads want it"""
+        st = type(self.struct).from_buffer_copy(self.struct)
+        st.transcript_state, st.transcript_label, st.label_len = None, None, 0
+        return st
 
     def _array(self, a, name, itemsize, rows=False):
         """-> (address, shape, row stride in bytes or None)"""
@@ -308,7 +322,7 @@ class DeviceMixedInput(DevicePackedInput):
     for DevicePackedInput: order_before(engine) is called by verify_batch_mixed_device and ResidentBatch.from_mixed."""
 
     def __init__(self, proofs, proof_lens, m, commitments, min_values=None, min_present=None, seed_nonces=None, label=b"", seed_present=None,
-                 state=None, proof_stride=None):
+                 state=None, proof_stride=None, item_states=None):
         self._keep, self.device_index, self._torch, self.synchronised = [], None, False, False
         self.proof_lens, self.m, n = _mixed_meta(proof_lens, m)
         addr_p, shape, stride = self._array(proofs, "proofs", 1, rows=True)
@@ -335,6 +349,7 @@ class DeviceMixedInput(DevicePackedInput):
                                       opt(min_values, "min_values", 8, (n, ms)), opt(min_present, "min_present", 1, (n, ms)),
                                       opt(seed_nonces, "seed_nonces", 1, (n, 32)), opt(seed_present, "seed_present", 1, (n,)),
                                       None if self.state is None else self.state.ctypes.data, self.label.ctypes.data, len(label))
+        self._item_states(item_states, n, opt)
 
 
 def _verify_mixed(params, inp, action, chunk, device):
@@ -726,7 +741,11 @@ class ResidentBatch(api.ResidentBatch):
             self.n, self.input = inp.n, inp
             inp.order_before(self.engine)
             t1 = time.perf_counter()
-            rc = self.engine.lib.bpp_batch_upload_packed_device(self.engine.ctx, params.handle, byref(inp.struct), byref(self.handle), err, 256)
+            if inp.item_states is not None:  # per-item transcripts: row i of inp.item_states serves item i
+                rc = self.engine.lib.bpp_batch_upload_packed_device_transcripts(self.engine.ctx, params.handle, byref(inp.struct_without_transcript()),
+                                                                                inp.item_states, byref(self.handle), err, 256)
+            else:
+                rc = self.engine.lib.bpp_batch_upload_packed_device(self.engine.ctx, params.handle, byref(inp.struct), byref(self.handle), err, 256)
             api._check(rc, self.engine.ctx, err)
             self.marshal_seconds, self.upload_seconds = t1 - t0, time.perf_counter() - t1
             return
@@ -784,7 +803,11 @@ class ResidentBatch(api.ResidentBatch):
         else:
             fn = self.engine.lib.bpp_batch_upload_mixed
         t1 = time.perf_counter()
-        rc = fn(self.engine.ctx, params.handle, byref(inp.struct), byref(self.handle), err, 256)
+        if getattr(inp, "item_states", None) is not None:  # (a DeviceMixedInput with per-item transcripts)
+            rc = self.engine.lib.bpp_batch_upload_mixed_device_transcripts(self.engine.ctx, params.handle, byref(inp.struct_without_transcript()),
+                                                                           inp.item_states, byref(self.handle), err, 256)
+        else:
+            rc = fn(self.engine.ctx, params.handle, byref(inp.struct), byref(self.handle), err, 256)
         api._check(rc, self.engine.ctx, err)
         self.marshal_seconds, self.upload_seconds = t1 - t0, time.perf_counter() - t1
         return self
@@ -800,14 +823,18 @@ class ResidentBatch(api.ResidentBatch):
         api._check(rc, self.engine.ctx, err)
         return self._masks, self._present
 
-    def enqueue(self, bounds=None, chunk=0, actions=None, action=api.VerifyAction.VerifyOnly, verdicts=None, masks=None, present=None):
+    def enqueue(self, bounds=None, chunk=0, actions=None, action=api.VerifyAction.VerifyOnly, verdicts=None, masks=None, present=None,
+                states=None):
         """bpp_verify_enqueue: the stream-ordered counterpart of verify_groups_actions.  Enqueues on the engine's stream and returns an
         Enqueued at once; the per-group records and the recovered masks land in torch tensors on the engine's device -- `verdicts`
         int32 [G, 4] (code, tier, index, flags), `masks` uint8 [n, t, 32], `present` uint8 [n]; the ones not given are allocated
         (masks and present only when some group recovers) -- and are valid in stream order behind the call: on an engine made on
         torch's current stream, torch work enqueued afterwards may read them with no synchronisation in between.
         bounds: explicit group boundaries; None: equal chunks of `chunk` proofs (0: one group).  actions: one VerifyAction per
-        group; None: `action` for every group."""
+        group; None: `action` for every group.
+        states (bpp_verify_enqueue_states): True, or a uint8 [n, 203] device tensor (or a raw device address) -- the advanced
+        transcripts come back as `.states`, valid in stream order like the records: row i is item i's transcript after the proof
+        where its group's record is Ok and the slot is live, 203 zero bytes everywhere else."""
         import torch
         dev = torch.device("cuda", int(self.engine.device))
         if bounds is not None:
@@ -837,6 +864,16 @@ class ResidentBatch(api.ResidentBatch):
             return ctypes.c_void_p(a.data_ptr())
 
         ticket = c_uint64()
+        if states is not None and states is not False:
+            if states is True:
+                states = torch.empty((self.n, 203), dtype=torch.uint8, device=dev)
+            rc = self.engine.lib.bpp_verify_enqueue_states(self.engine.ctx, self.handle, arr, G, int(chunk), act, int(action),
+                                                           addr(verdicts, "verdicts", torch.int32, (G, 4)),
+                                                           addr(masks, "masks", torch.uint8, (self.n, self.t, 32)),
+                                                           addr(present, "present", torch.uint8, (self.n,)),
+                                                           addr(states, "states", torch.uint8, (self.n, 203)), byref(ticket))
+            api._check(rc, self.engine.ctx)
+            return Enqueued(self.engine, ticket.value, G, verdicts, masks, present, states)
         rc = self.engine.lib.bpp_verify_enqueue(self.engine.ctx, self.handle, arr, G, int(chunk), act, int(action),
                                                 addr(verdicts, "verdicts", torch.int32, (G, 4)),
                                                 addr(masks, "masks", torch.uint8, (self.n, self.t, 32)),
@@ -864,7 +901,9 @@ class ResidentBatch(api.ResidentBatch):
         A DeviceMixedInput `inp` (bpp_batch_refill_enqueue_mixed) refills a batch made by from_mixed from a DeviceMixedInput: its
         proof_lens and m must repeat the batch's vectors, its strides are the source's own; `count` and `live` mean what they mean
         above, with the fresh mixed upload of the rows in question as the reference.  shape_vectors=False passes no proof_lens / m at
-        all ("the batch's own"): the steady-state form, in which the call touches nothing of size n on the host."""
+        all ("the batch's own"): the steady-state form, in which the call touches nothing of size n on the host.
+        An `inp` made with item_states= (bpp_batch_refill_enqueue_transcripts / _mixed_transcripts) refills a batch that was uploaded
+        with per-item transcripts, and only such a batch: every refill brings the rows of its items, `count` and `live` as above."""
         import torch
         if live is not None and count is not None:
             raise api.ProofError(api.ProofErrorKind.InvalidArgument, "count and live: a refill takes a live count or a live mask, not both")
@@ -913,13 +952,20 @@ class ResidentBatch(api.ResidentBatch):
             st.transcript_state, st.transcript_label, st.label_len = None, None, 0
             if not shape_vectors:
                 st.proof_lens, st.m = None, None
-            rc = self.engine.lib.bpp_batch_refill_enqueue_mixed(self.engine.ctx, self.handle, byref(st), count_addr, live_addr, addr, byref(ticket))
+            if inp.item_states is not None:
+                rc = self.engine.lib.bpp_batch_refill_enqueue_mixed_transcripts(self.engine.ctx, self.handle, byref(st), inp.item_states, count_addr,
+                                                                                live_addr, addr, byref(ticket))
+            else:
+                rc = self.engine.lib.bpp_batch_refill_enqueue_mixed(self.engine.ctx, self.handle, byref(st), count_addr, live_addr, addr, byref(ticket))
             api._check(rc, self.engine.ctx)
             self.input = inp
             return Refilled(self.engine, ticket.value, record)
         st = _lib.PackedBatch.from_buffer_copy(inp.struct)
         st.transcript_state, st.transcript_label, st.label_len = None, None, 0
-        if live_addr is not None:
+        if inp.item_states is not None:
+            rc = self.engine.lib.bpp_batch_refill_enqueue_transcripts(self.engine.ctx, self.handle, byref(st), inp.item_states, count_addr, live_addr,
+                                                                      addr, byref(ticket))
+        elif live_addr is not None:
             rc = self.engine.lib.bpp_batch_refill_enqueue_live(self.engine.ctx, self.handle, byref(st), live_addr, addr, byref(ticket))
         elif count_addr is None:
             rc = self.engine.lib.bpp_batch_refill_enqueue(self.engine.ctx, self.handle, byref(st), addr, byref(ticket))
@@ -1004,9 +1050,10 @@ class Enqueued:
     results are there, results() waits, copies the records back and returns the dicts of verify_groups_actions (a group whose
     record carries VERDICT_REDRAW claims nothing: code 0, tier 0, and a message that says so; redraws() lists those groups)."""
 
-    def __init__(self, engine, ticket, n_groups, verdicts, masks, present):
+    def __init__(self, engine, ticket, n_groups, verdicts, masks, present, states=None):
         self.engine, self.ticket, self.n_groups = engine, ticket, n_groups
         self.verdicts, self.masks, self.present = verdicts, masks, present
+        self.states = states  # (enqueue(states=...): uint8 [n, 203], the advanced transcripts; None otherwise)
 
     def done(self):
         d = ctypes.c_int()

@@ -703,6 +703,54 @@ int bpp_batch_refill_enqueue_mixed(bpp_ctx *ctx, uint64_t batch, const bpp_mixed
                                    const uint32_t *count_dev /* one device word, or NULL */,
                                    const uint8_t *live_dev /* N device bytes, or NULL */,
                                    bpp_device_refill *record_dev /* may be NULL */, uint64_t *ticket /* may be NULL */);
+/* ---- per-item transcripts on the device paths: in at upload and refill, out at enqueue ----
+ * The reference's verify_batch takes one transcript per proof and advances each in place.  The array forms above serve ONE transcript
+ * to every item; these calls give the _device forms the item form's contract (bpp_verify_item.transcript_state) with no host round
+ * trip.
+ * IN.  item_states203: n_items rows of 203 bytes in BPP_PTR_THIS_DEVICE memory, at any byte address; row i is the STROBE state
+ * (state[200] | pos | pos_begin | cur_flags, as bpp_transcript_new / _append_message leave it) item i is verified under.  The two
+ * uploads return, for any input, what bpp_batch_upload returns on the item array whose item i has transcript_state = row i: return
+ * code, text, the index a finding names, bpp_batch_shape, every bpp_batch_trace output, and the verdicts and masks of every later
+ * call.  in->transcript_state and in->transcript_label must be NULL (refused, field named); item_states203 that is NULL or not this
+ * device's memory is refused before any launch, field named.  A row with pos >= 166 (the STROBE-128 rate) is the item form's finding "transcript
+ * state has pos >= rate", raised at the lowest item that has one and, among the findings of one item, after everything the proof's
+ * parse raises; such a row is never copied, its slot holds 203 zero bytes.  A batch that takes the staged fall-back (first bytes that
+ * disagree, no proofs) stages the state rows with the rest and goes through the item form; bpp_ingest_stats counts it as ever.
+ * REFILLS.  "Uploaded with per-item transcripts" is part of the shape a batch keeps: the two refills below take only batches the two
+ * uploads below made on their device path, and bpp_batch_refill_enqueue / _count / _live / _mixed refuse such a batch; either text
+ * names the call to use instead.  count_dev / live_dev (at most one; NULL and NULL is the plain form), the record and its flags, DEAD
+ * SLOTS, FORM, STEADY STATE, stream ownership, secrets, tickets and refused-before-launch are those of the refills above, with "a
+ * fresh upload WITH TRANSCRIPTS of the rows in question" (all of them / the first c / each group's live rows alone in slot order) as
+ * the reference.  Nothing of a dead row's state is read and its slot gets 203 zero bytes; a bad state there is no finding.  A bad
+ * state at a live slot lands in the record under BPP_REFILL_FINDING with the item form's code and message id, with the precedence
+ * given above.
+ * OUT.  bpp_verify_enqueue_states is bpp_verify_enqueue plus states_out203_dev (N x 203 bytes of BPP_PTR_THIS_DEVICE memory at any
+ * byte address; NULL is refused).  It takes every batch that call takes (one transcript or one per item; not caller-side challenges,
+ * which ran no PASS 1 here).  Verdict records, masks and mask_present are byte for byte bpp_verify_enqueue's.  Row i is written on
+ * every call: where item i's group has the record {0, BPP_TIER_NONE, 0, BPP_VERDICT_WRITTEN} exactly and slot i is live, the 203
+ * bytes bpp_verify_batch_states writes for that item (the transcript after r1, s1 and every d1); everywhere else -- dead slots,
+ * rejected groups, BPP_VERDICT_EMPTY, _REDRAW and _REFILL -- 203 zero bytes, which no Merlin state is.  The first such call on a
+ * batch may allocate the engine's row buffer; after that it allocates nothing, copies nothing to the host and waits for nothing. */
+int bpp_batch_upload_packed_device_transcripts(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in,
+                                               const uint8_t *item_states203 /* n_items x 203, device */, uint64_t *batch, char *errbuf,
+                                               size_t errbuf_len);
+int bpp_batch_upload_mixed_device_transcripts(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in,
+                                              const uint8_t *item_states203 /* n_items x 203, device */, uint64_t *batch, char *errbuf,
+                                              size_t errbuf_len);
+int bpp_batch_refill_enqueue_transcripts(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev,
+                                         const uint8_t *item_states203_dev /* N x 203, device */,
+                                         const uint32_t *count_dev /* one device word, or NULL */,
+                                         const uint8_t *live_dev /* N device bytes, or NULL */,
+                                         bpp_device_refill *record_dev /* may be NULL */, uint64_t *ticket /* may be NULL */);
+int bpp_batch_refill_enqueue_mixed_transcripts(bpp_ctx *ctx, uint64_t batch, const bpp_mixed_batch *in_dev,
+                                               const uint8_t *item_states203_dev /* N x 203, device */,
+                                               const uint32_t *count_dev /* one device word, or NULL */,
+                                               const uint8_t *live_dev /* N device bytes, or NULL */,
+                                               bpp_device_refill *record_dev /* may be NULL */, uint64_t *ticket /* may be NULL */);
+int bpp_verify_enqueue_states(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first /* NULL: equal chunks */, size_t n_groups, size_t chunk,
+                              const int *actions /* NULL: action_all for every group */, int action_all, bpp_device_verdict *verdicts_dev,
+                              uint8_t *masks_dev /* may be NULL */, uint8_t *mask_present_dev /* may be NULL */,
+                              uint8_t *states_out203_dev /* N x 203, device */, uint64_t *ticket);
 /* A diagnostic: enqueues a device-to-device copy of the batch weights that the batch's last enqueued verification used, N x 32
  * canonical bytes, into weights_dev (BPP_PTR_THIS_DEVICE memory); dead slots hold 32 zero bytes.  Allocates nothing and does not
  * wait.  BPP_ERR_INVALID_ARGUMENT for a batch whose last call on the stream was not an enqueue that drew weights. */

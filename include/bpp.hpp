@@ -212,6 +212,39 @@ class Engine {
     check(rc, bpp_ctx_last_error(ctx_));
     return t;
   }
+  // Per-item transcripts (bpp.h, "per-item transcripts on the device paths").  The refills of a batch that
+  // bpp_batch_upload_packed_device_transcripts / _mixed_device_transcripts made: item_states203_dev is n rows of 203 bytes in device
+  // memory, row i the STROBE state item i is verified under; count_dev / live_dev as above, at most one of them.
+  EnqueueTicket batch_refill_enqueue(uint64_t batch, const bpp_packed_batch &in_dev, const uint8_t *item_states203_dev, const uint32_t *count_dev,
+                                     const uint8_t *live_dev, bpp_device_refill *record_dev) {
+    EnqueueTicket t;
+    t.ctx_ = ctx_;
+    const int rc = bpp_batch_refill_enqueue_transcripts(ctx_, batch, &in_dev, item_states203_dev, count_dev, live_dev, record_dev, &t.id);
+    check(rc, bpp_ctx_last_error(ctx_));
+    return t;
+  }
+  EnqueueTicket batch_refill_enqueue_mixed(uint64_t batch, const bpp_mixed_batch &in_dev, const uint8_t *item_states203_dev,
+                                           const uint32_t *count_dev, const uint8_t *live_dev, bpp_device_refill *record_dev) {
+    EnqueueTicket t;
+    t.ctx_ = ctx_;
+    const int rc = bpp_batch_refill_enqueue_mixed_transcripts(ctx_, batch, &in_dev, item_states203_dev, count_dev, live_dev, record_dev, &t.id);
+    check(rc, bpp_ctx_last_error(ctx_));
+    return t;
+  }
+  // verify_enqueue that also hands the advanced transcripts back on the stream (bpp_verify_enqueue_states): states_out203_dev is n x
+  // 203 bytes of device memory; row i is item i's transcript after the proof where its group's record is Ok and the slot is live,
+  // 203 zero bytes everywhere else.
+  EnqueueTicket verify_enqueue_states(uint64_t batch, const uint32_t *group_first, size_t n_groups, size_t chunk, const int *actions,
+                                      VerifyAction action, bpp_device_verdict *verdicts_dev, uint8_t *states_out203_dev,
+                                      uint8_t *masks_dev = nullptr, uint8_t *mask_present_dev = nullptr) {
+    EnqueueTicket t;
+    t.ctx_ = ctx_;
+    t.n_groups = n_groups;
+    const int rc = bpp_verify_enqueue_states(ctx_, batch, group_first, n_groups, chunk, actions, (int)action, verdicts_dev, masks_dev,
+                                             mask_present_dev, states_out203_dev, &t.id);
+    check(rc, bpp_ctx_last_error(ctx_));
+    return t;
+  }
   // A diagnostic: the weights of the batch's last enqueued verification, n x 32 bytes into device memory, in stream order
   // (bpp_enqueue_weights); dead slots hold zeros.
   EnqueueTicket enqueue_weights(uint64_t batch, uint8_t *weights_dev) {

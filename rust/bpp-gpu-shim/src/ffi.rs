@@ -399,6 +399,21 @@ extern "C" {
     // of count_dev and live_dev
     pub fn bpp_batch_refill_enqueue_mixed(ctx: *mut bpp_ctx, batch: u64, in_dev: *const bpp_mixed_batch, count_dev: *const u32,
                                           live_dev: *const u8, record_dev: *mut bpp_device_refill, ticket: *mut u64) -> c_int;
+    // per-item transcripts on the device paths: item_states203 = n_items rows of 203 bytes in device memory, in at upload and
+    // refill; the advanced transcripts out on the stream (states_out203_dev, n x 203)
+    pub fn bpp_batch_upload_packed_device_transcripts(ctx: *mut bpp_ctx, params: u64, input: *const bpp_packed_batch, item_states203: *const u8,
+                                                      batch: *mut u64, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_batch_upload_mixed_device_transcripts(ctx: *mut bpp_ctx, params: u64, input: *const bpp_mixed_batch, item_states203: *const u8,
+                                                     batch: *mut u64, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_batch_refill_enqueue_transcripts(ctx: *mut bpp_ctx, batch: u64, in_dev: *const bpp_packed_batch, item_states203_dev: *const u8,
+                                                count_dev: *const u32, live_dev: *const u8, record_dev: *mut bpp_device_refill,
+                                                ticket: *mut u64) -> c_int;
+    pub fn bpp_batch_refill_enqueue_mixed_transcripts(ctx: *mut bpp_ctx, batch: u64, in_dev: *const bpp_mixed_batch,
+                                                      item_states203_dev: *const u8, count_dev: *const u32, live_dev: *const u8,
+                                                      record_dev: *mut bpp_device_refill, ticket: *mut u64) -> c_int;
+    pub fn bpp_verify_enqueue_states(ctx: *mut bpp_ctx, batch: u64, group_first: *const u32, n_groups: usize, chunk: usize,
+                                     actions: *const c_int, action_all: c_int, verdicts_dev: *mut bpp_device_verdict, masks_dev: *mut u8,
+                                     mask_present_dev: *mut u8, states_out203_dev: *mut u8, ticket: *mut u64) -> c_int;
     pub fn bpp_enqueue_weights(ctx: *mut bpp_ctx, batch: u64, weights_dev: *mut u8, ticket: *mut u64) -> c_int;
     pub fn bpp_batcher_verify_action(b: *mut bpp_batcher, input: *const bpp_packed_batch, action: c_int, masks_out: *mut u8,
                                      mask_present: *mut u8, errbuf: *mut c_char, errbuf_len: usize) -> c_int;

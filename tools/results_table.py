@@ -67,6 +67,55 @@ def refill_mixed_section():
     return out + [""]
 
 
+def item_transcripts_section():
+    """profiles/item_transcripts.json: the step with per-item transcripts against the existing step (tools/bench_item_transcripts.py),
+    the two kernels alone, and the callers that do not use the feature against the parent commit's library (tools/gpu_ab.py)"""
+    fit = os.path.join(P, "item_transcripts.json")
+    out = ["## Per-item transcripts on the stream: refill with transcripts + `bpp_verify_enqueue_states` against refill + `bpp_verify_enqueue` "
+           "(`tools/bench_item_transcripts.py`, `profiles/item_transcripts.json`)", ""]
+    if not os.path.exists(fit):
+        return out + ["unmeasured", ""]
+    doc = json.load(open(fit))
+    step = doc["step"]
+    summary = [r for r in step if r.get("tool") == "bench_item_transcripts"][-1]
+    arm = lambda a, k: [r[k] for r in step if r.get("arm") == a]  # noqa: E731
+    cell = lambda v, f: (f + " (" + f + "-" + f + ")") % (statistics.median(v), min(v), max(v))  # noqa: E731
+    out += ["One thread, one context, %d slots of 64 bits, m = 1, t = 1, a ring of 4 device input sets, both arms on one tree alternating in one "
+            "process, %d repetitions of %d steps; median (lowest-highest).  The transcripts arm brings 203 bytes per proof in (`k_item_states`), "
+            "runs PASS 1 in its STATES form and writes 203 bytes per proof out (`k_states_out`).  Nothing was promised; the expectation was a "
+            "few microseconds per kernel and a PASS 1 within a per cent of the default form.  Box: recorded by the tool as \"%s\"." %
+            (summary["items"], summary["reps"], summary["steps"], summary["box"]), "",
+            "| arm | ms per step | steps/s | host ms in the step's calls | host waits (refill, enqueue), layouts planned |", "|---|---|---|---|---|"]
+    st = summary["steady_state"]
+    for a in ("plain", "transcripts"):
+        out.append("| %s | %s | %.1f | %.3f | %s |" % (a, cell(arm(a, "ms_per_step"), "%.4f"), statistics.median(arm(a, "steps_per_s")),
+                                                        statistics.median(arm(a, "host_ms_per_step_median")),
+                                                        "%d, %d; %d (both arms)" % (st["refill_host_waits"], st["enqueue_host_waits"], st["layouts_in_call"])))
+    out += ["", "Difference of the medians: %.4f ms per step (%.2f %%)." %
+            (summary["difference_ms_per_step"], 100 * summary["difference_ms_per_step"] / summary["plain_ms_per_step"]), "",
+            "| kernel (rocprofv3 kernel trace of a 40-step run) | calls | average us | lowest-highest us |", "|---|---|---|---|"]
+    for r in step:
+        if "kernel" in r:
+            out.append("| `%s` | %d | %.2f | %.2f-%.2f |" % (r["kernel"].replace("void bpp::", "").replace("bpp::", ""), r["calls"], r["avg_us"], r["min_us"], r["max_us"]))
+    ab = doc.get("callers_without_the_feature")
+    if ab:
+        out += ["", "Callers that do not use the feature, this tree against the parent commit's library, alternating (`tools/gpu_ab.py`); "
+                "median (lowest-highest) over every repetition of every run:", "",
+                "| program, arm | this tree | parent commit |", "|---|---|---|"]
+        runs = ab["bench_refill"]["runs"]
+        for name in ("refill", "refill_count_512", "refill_live_0.5", "upload"):
+            vals = {b: [v for r in runs if r["build"] == b for v in r["steps_per_s"].get(name, [])] for b in ("this", "parent")}
+            out.append("| `tools/bench_refill.py` %s, steps/s | %s | %s |" % (name, cell(vals["this"], "%.1f"), cell(vals["parent"], "%.1f")))
+        hl = ab["bench_py"]["runs"]
+        for s in sorted({r["session"] for r in hl}):
+            vals = {b: [r["M_proofs_per_s"] for r in hl if r["build"] == b and r["session"] == s] for b in ("this", "parent")}
+            clk = {b: [r["clock_GHz"] for r in hl if r["build"] == b and r["session"] == s] for b in ("this", "parent")}
+            out.append("| `bench.py`, M proofs/s, session %d (%d runs each; clocks %.2f-%.2f / %.2f-%.2f GHz) | %s | %s |" %
+                       (s, len(vals["this"]), min(clk["this"]), max(clk["this"]), min(clk["parent"]), max(clk["parent"]),
+                        cell(vals["this"], "%.2f"), cell(vals["parent"], "%.2f")))
+    return out + [""]
+
+
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r03_v1"
     out = ["# RESULTS — measured figures (generated by `tools/results_table.py %s` from `profiles/`; do not edit)" % tag, "",
@@ -357,6 +406,7 @@ def main():
                                                               span[arm]["ingest_span_ms_median"]))
         out.append("")
     out += refill_mixed_section()
+    out += item_transcripts_section()
     ks, fks = load(tag, "kernel_stats_cfg2_default.csv")
     sq, fsq = load(tag, "pmc_sq_summary.csv")
     if ks:
