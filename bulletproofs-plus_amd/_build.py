@@ -275,6 +275,22 @@ def build_item_states_harness(force=False):
     return ITEM_STATES_SANITIZER_BIN
 
 
+PROVE_INGEST_SANITIZER_BIN = os.path.join(HERE, "hosttest_prove_ingest_asan")
+
+
+def build_prove_ingest_harness(force=False):
+    """hosttest_prove_ingest.cpp (prove_ingest.h: the per-item routines of k_prove_ingest and the host plan of
+    bpp_prove_openings_device, held to ProvePack::pack and prove_item_check_host on the sorted equivalent items) under ASan + UBSan:
+    an executable, run by tests/test_prove_ingest_host.py."""
+    src = os.path.join(CSRC, "hosttest_prove_ingest.cpp")
+    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
+    if not force and not _stale(PROVE_INGEST_SANITIZER_BIN, deps):
+        return PROVE_INGEST_SANITIZER_BIN
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-fno-omit-frame-pointer", "-o", PROVE_INGEST_SANITIZER_BIN, src], check=True, cwd=CSRC)
+    return PROVE_INGEST_SANITIZER_BIN
+
+
 if __name__ == "__main__":
     build(force="--force" in sys.argv, verbose=True)
     build_hosttest(force="--force" in sys.argv)

@@ -104,6 +104,24 @@ class RefillStats(Structure):
     _fields_ = [(n, c_uint64) for n in ("calls", "first_calls", "host_waits")]
 
 
+class ProveArrays(Structure):
+    """bpp_prove_arrays: the openings of a prove call as arrays of rows in device memory (m and the transcript on the host)"""
+    _fields_ = [("n_items", c_size_t), ("m", c_void_p), ("m_stride", c_uint32), ("values", c_void_p), ("blindings32", c_void_p),
+                ("commitments32", c_void_p), ("min_values", c_void_p), ("min_present", c_void_p), ("seed_nonces32", c_void_p),
+                ("seed_present", c_void_p), ("rng_bytes", c_void_p), ("rng_stride", c_size_t), ("transcript_state", c_void_p),
+                ("transcript_label", c_void_p), ("label_len", c_size_t)]
+
+
+class DeviceProveStatus(Structure):
+    """bpp_device_prove_status: one item's record of bpp_prove_openings_device, 8 bytes, as it lies in device memory"""
+    _fields_ = [("code", ctypes.c_int32), ("msg", c_uint32)]
+
+
+class ProveDeviceStats(Structure):
+    """struct bpp_prove_device_stats: what the prove calls from device arrays of a context came to"""
+    _fields_ = [(n, c_uint64) for n in ("calls", "items", "device_findings", "host_findings")]
+
+
 class RuntimeInfo(Structure):
     """bpp_runtime_info: what the library sees of its runtime preconditions (hardware queues, contexts, the small-call gate)"""
     _fields_ = [("device", c_int), ("contexts", c_uint32), ("contexts_peak", c_uint32), ("hw_queues", c_uint32),
@@ -230,6 +248,10 @@ SYMBOLS = [
                                    POINTER(c_size_t), POINTER(c_int), c_void_p, c_size_t]),
     ("bpp_prove_openings_item_message", c_int, [c_void_p, c_uint64, POINTER(ProveItem), c_void_p, c_size_t, c_size_t, c_int, c_void_p,
                                                 c_size_t]),
+    ("bpp_prove_openings_device", c_int, [c_void_p, c_uint64, POINTER(ProveArrays), c_void_p, c_size_t, c_void_p, c_size_t,
+                                          POINTER(c_size_t), c_void_p, POINTER(c_int), c_void_p, c_size_t]),
+    ("bpp_prove_status_result", c_int, [POINTER(DeviceProveStatus), POINTER(ShardResult)]),
+    ("bpp_prove_device_stats", c_int, [c_void_p, POINTER(ProveDeviceStats)]),
     ("bpp_prove_pool_openings", c_int, [c_void_p, POINTER(ProveItem), c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
                                         POINTER(c_size_t), c_void_p, c_size_t]),
     ("bpp_prove_pool_openings_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),

@@ -46,6 +46,7 @@
 #include "refill.h"
 #include "refill_mixed.h"
 #include "item_states.h"
+#include "prove_ingest.h"
 
 using namespace bpp;
 
@@ -633,6 +634,11 @@ struct bpp_ctx {
   std::vector<hipStream_t> prove_aux_streams;
   std::vector<hipEvent_t> prove_aux_events;
   std::vector<hipEvent_t> prove_events;  // pairs around every k_fb_msm launch of the last bpp_prove_batch (profiling only)
+  // bpp_prove_openings_device: the event that orders the caller's arrays (complete on ctx->stream) before every sub-batch's ingest
+  // kernel, the table of the items the host refused (public: item, lengths, finding), what the calls came to
+  hipEvent_t prove_dev_event = nullptr;
+  DevBuf<uint8_t> prove_dev_refused;
+  struct bpp_prove_device_stats prove_dev_stats{};
   bpp_prove_profile pprof{};
   // knobs (tests, A/B timing).  -1 = the engine's own rule.  The BPP_* environment variables of the same names are read
   // ONCE, when the context is created (no getenv on any verification path: a host that calls setenv from another thread
@@ -1386,6 +1392,7 @@ void bpp_ctx_destroy(bpp_ctx *ctx) {
     (void)hipStreamDestroy(ps);
   }
   for (auto &e : ctx->prove_aux_events) (void)hipEventDestroy(e);
+  if (ctx->prove_dev_event) (void)hipEventDestroy(ctx->prove_dev_event);
   ctx->prove_arena.release();
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   {

@@ -49,6 +49,22 @@ const char *const kSelfCheckRecoveryWhy =
 // challenge_final_e leaves it; row i of states203 (203 bytes, call order) is written for every item whose status word ends as 0 --
 // after the self-check, whose remake of a proof brings its own row -- and left alone for every other item.  A call without it
 // carves, enqueues and copies exactly what it did.
+// dev != nullptr (bpp_prove_openings_device): the witness does not come from `items` but from arrays in device memory, and the
+// proofs, commitments and outcomes go to rows in device memory (ProveDeviceIO below): the call's SOURCE is the ingest kernel in
+// place of the packer, the staging and the uploads, its SINK the emit kernel in place of the copies to the host.  Everything between
+// -- plan, arena, streams, every step -- is the same.  A call without it enqueues launch for launch what it did.
+struct ProveDeviceIO {
+  const bpp_prove_arrays *in;      // the caller's struct: device addresses, the host's m[] and transcript
+  std::vector<uint32_t> m_sorted;  // the aggregation factors of the call's slots, largest first
+  std::vector<ProveDevRow> rows;   // slot k -> the caller's item, its lengths
+  uint8_t *commitments_out;
+  size_t commit_stride;
+  uint8_t *proofs_out;
+  size_t proof_stride;
+  bpp_device_prove_status *status_dev;
+  std::vector<bpp_device_prove_status> outcome;  // by slot: what came back
+};
+
 struct ProveRequest {
   uint64_t params;
   const bpp_prove_item *items;
@@ -62,6 +78,7 @@ struct ProveRequest {
   bool remake = true;
   uint8_t *made32 = nullptr;
   uint8_t *states203 = nullptr;
+  ProveDeviceIO *dev = nullptr;
 };
 
 // One prove call (the context's lock held, its device current): its packed witness, its plan, its sub-batches and its staging,
@@ -74,6 +91,10 @@ struct ProveCall {
     uint8_t *d_bytes, *d_states, *d_minpres, *d_a32, *d_lr, *d_a1b, *d_proofs, *d_commit32;
     uint32_t *d_tstates = nullptr;  // the advanced transcripts, rows of BPP_STATE_ROW_WORDS words (states203 only)
     ProveDesc *d_desc;
+    // (device arrays only) the slots' rows, the ingest kernel's finding words, the outcomes on their way to the host
+    ProveDevRow *d_rows = nullptr;
+    uint32_t *d_finding = nullptr;
+    bpp_device_prove_status *d_outcome = nullptr;
     uint64_t *d_minvals;
     ProveState *d_ps;
     sc *d_vec, *d_ts, *d_cts;
@@ -105,7 +126,8 @@ struct ProveCall {
   std::vector<Fix> fixes;
   size_t arena_need = 0;
   uint8_t *pin_bytes = nullptr, *pin_states = nullptr, *pin_minpres = nullptr, *pin_minvals = nullptr, *pin_desc = nullptr;
-  uint8_t *pin_proofs = nullptr, *pin_made = nullptr;
+  uint8_t *pin_proofs = nullptr, *pin_made = nullptr, *pin_rows = nullptr;
+  bpp_device_prove_status *pin_outcome = nullptr;
   uint32_t *pin_status = nullptr, *pin_tstates = nullptr;
   const dim3 b64{64};
   size_t ev_used = 0;
@@ -161,10 +183,20 @@ struct ProveCall {
   // ---- the witness: checked and packed by prove_pack_host.h; *proof_len is written before the stride is looked at
   void pack() {
     const ParamShape shape{P.n_bits, P.m_max, P.t};
+    if (r.dev) {  // (every slot has passed the host's part of the checks; the rest is the ingest kernel's)
+      const bpp_prove_arrays &in = *r.dev->in;
+      prove_plan_device(shape, P.hg32.data(), r.dev->m_sorted.data(), r.n_items, in.commitments32 != nullptr, in.transcript_state,
+                        in.transcript_label, in.label_len, pk);
+      set_shape();
+      return;
+    }
     const size_t len0 = prove_item_len_host(shape, r.items[0].m);  // (0: items[0] has no proof length, and the packer says why)
     if (len0 && r.proof_len) *r.proof_len = len0;
     if (len0 && r.proof_stride < len0) throw ProofErr{BPP_ERR_INVALID_LENGTH, "proof_stride too small"};
     pk.pack(shape, P.hg32.data(), r.items, r.n_items, r.mixed, r.made32 != nullptr);
+    set_shape();
+  }
+  void set_shape() {
     n = P.n_bits, t = P.t, m = pk.m, B = (uint32_t)r.n_items, mn = m * n, rounds = pk.rounds, plen = pk.plen;
     stride = 2 * mn + t + 1;
     n_gen = 2 * P.n_bits * P.m_max;
@@ -251,7 +283,7 @@ struct ProveCall {
       u.lo = q * sub_size;
       u.nb = std::min(sub_size, B - u.lo);
       u.bytes_lo = pk.desc[u.lo].wit_off;
-      u.bytes_len = (u.lo + u.nb < B ? pk.desc[u.lo + u.nb].wit_off : pk.bytes.size()) - u.bytes_lo;
+      u.bytes_len = (u.lo + u.nb < B ? pk.desc[u.lo + u.nb].wit_off : pk.bytes_len) - u.bytes_lo;
       const size_t nb = u.nb;
       arena_need = (arena_need + 255) & ~(size_t)255;
       u.arena_lo = arena_need;
@@ -287,6 +319,11 @@ struct ProveCall {
       take(u.d_pow, ct ? (size_t)ex_nt * nb * BPP_CT_DIGITS * sizeof(ge) : 16);
       take(u.d_ctprod, ct ? (size_t)ex_nt * nb * sizeof(ge) : 16);
       if (r.states203) take(u.d_tstates, nb * BPP_STATE_ROW_WORDS * 4);  // (last, and only when asked for: the arena of every other call is laid out as before)
+      if (r.dev) {  // (as above)
+        take(u.d_rows, nb * sizeof(ProveDevRow));
+        take(u.d_finding, nb * 4);
+        take(u.d_outcome, nb * sizeof(bpp_device_prove_status));
+      }
       u.arena_len = arena_need - u.arena_lo;
       u.adopts = false;
       // descriptors are relative to each sub-batch's own byte block / minimum-value rows
@@ -353,6 +390,7 @@ struct ProveCall {
 
   // ---- page-locked staging so that no copy stalls the enqueue of the next sub-batch
   void stage_in() {
+    if (r.dev) return stage_in_device();
     const size_t in_need = pk.bytes.size() + pk.states.size() + pk.minpres.size() + pk.minvals.size() * 8 + (size_t)B * sizeof(ProveDesc) + 64;
     ctx->prove_pin_in.resize(in_need);
     // (on the way out: proofs, status words and -- made32 -- the commitments the witness check computed: nothing secret)
@@ -374,8 +412,27 @@ struct ProveCall {
     pin_tstates = (uint32_t *)(pin_made + (r.made32 ? (((size_t)B * m * 32 + 15) & ~(size_t)15) : 0));  // (public data)
   }
 
-  // ---- sub-batch q's inputs, its witness check on the side stream, kp_init and kp_A
-  void enqueue_init(uint32_t q) {
+  // ---- the device-arrays form of the staging: the plan's public tables alone -- states, descriptors, rows -- on the way in (no
+  // witness byte passes through prove_pin_in), one outcome record per slot on the way out
+  void stage_in_device() {
+    auto up8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
+    ctx->prove_pin_in.resize(up8(pk.states.size()) + (size_t)B * (sizeof(ProveDesc) + sizeof(ProveDevRow)) + 64);
+    ctx->prove_pin_out.resize((size_t)B * sizeof(bpp_device_prove_status) + 64);
+    pin_states = ctx->prove_pin_in.p;
+    memcpy(pin_states, pk.states.data(), pk.states.size());
+    pin_desc = pin_states + up8(pk.states.size());
+    memcpy(pin_desc, pk.desc.data(), (size_t)B * sizeof(ProveDesc));
+    pin_rows = pin_desc + (size_t)B * sizeof(ProveDesc);
+    memcpy(pin_rows, r.dev->rows.data(), (size_t)B * sizeof(ProveDevRow));
+    pin_outcome = (bpp_device_prove_status *)ctx->prove_pin_out.p;
+    if (!ctx->prove_dev_event) HIP_CHECK(hipEventCreateWithFlags(&ctx->prove_dev_event, hipEventDisableTiming));
+    // whatever wrote the caller's arrays is complete on, or ordered before, the context's stream: every sub-batch's ingest kernel
+    // waits for this point of it
+    HIP_CHECK(hipEventRecord(ctx->prove_dev_event, ctx->stream));
+  }
+
+  // ---- sub-batch q's inputs from the page-locked staging ...
+  void upload_inputs(uint32_t q) {
     Sub &u = subs[q];
     hipStream_t s = lane_stream(q);
     const uint32_t nb = u.nb;
@@ -385,6 +442,49 @@ struct ProveCall {
     HIP_CHECK(hipMemcpyAsync(u.d_minvals, pin_minvals + (size_t)u.lo * m * 8, (size_t)nb * m * 8, hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(u.d_desc, pin_desc + (size_t)u.lo * sizeof(ProveDesc), (size_t)nb * sizeof(ProveDesc),
                              hipMemcpyHostToDevice, s));
+  }
+  // ---- ... or from the caller's arrays where they lie: k_prove_ingest writes d_bytes, d_minvals and d_minpres (the arena is zero
+  // where it writes nothing: the promise rows beyond an item's m) and sets the nonce bit of the uploaded descriptors
+  void ingest_inputs(uint32_t q) {
+    Sub &u = subs[q];
+    hipStream_t s = lane_stream(q);
+    const uint32_t nb = u.nb;
+    const bpp_prove_arrays &in = *r.dev->in;
+    HIP_CHECK(hipMemcpyAsync(u.d_states, pin_states, pk.states.size(), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(u.d_desc, pin_desc + (size_t)u.lo * sizeof(ProveDesc), (size_t)nb * sizeof(ProveDesc), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(u.d_rows, pin_rows + (size_t)u.lo * sizeof(ProveDevRow), (size_t)nb * sizeof(ProveDevRow), hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipStreamWaitEvent(s, ctx->prove_dev_event, 0));
+    ProveIngest a;
+    memset(&a, 0, sizeof(a));
+    a.values = (const uint8_t *)in.values;
+    a.blindings32 = in.blindings32;
+    a.commitments32 = in.commitments32;
+    a.min_values = (const uint8_t *)in.min_values;
+    a.min_present = in.min_present;
+    a.seed_nonces32 = in.seed_nonces32;
+    a.seed_present = in.seed_present;
+    a.rng_bytes = in.rng_bytes;
+    a.rng_stride = in.rng_stride;
+    a.m_stride = in.m_stride;
+    a.n_bits = n, a.t = t, a.nb = nb;
+    a.g0_32 = P.d_hg32.p + 32;
+    a.rows = u.d_rows;
+    a.desc = u.d_desc;
+    a.bytes = u.d_bytes;
+    a.minvals = u.d_minvals;
+    a.minpres = u.d_minpres;
+    a.finding = u.d_finding;
+    hipLaunchKernelGGL(k_prove_ingest, dim3(cdiv(nb, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, a);
+    HIP_CHECK(hipGetLastError());
+  }
+
+  // ---- sub-batch q's inputs, its witness check on the side stream, kp_init and kp_A
+  void enqueue_init(uint32_t q) {
+    Sub &u = subs[q];
+    hipStream_t s = lane_stream(q);
+    const uint32_t nb = u.nb;
+    if (r.dev) ingest_inputs(q);
+    else upload_inputs(q);
     // witness check (:275-284): commit(v_j, r_j) for every opening, compared with the statement's commitments.  Nothing of the
     // proof depends on it (a mismatch is a status bit read after the call), so its three kernels run on a stream of their own
     // beside kp_init / kp_A / the first round's small kernels (in line they were 0.2 ms of the call's first 0.75 ms, in which no
@@ -517,6 +617,17 @@ struct ProveCall {
       hipLaunchKernelGGL(kp_finish<false>, dim3(nb), b64, 0, s, u.d_desc, n, t, nb, rounds, u.d_a32, u.d_lr, u.d_a1b, u.d_vec, u.d_ps,
                          u.d_proofs, (uint32_t)plen, (uint32_t *)nullptr);
     HIP_CHECK(hipGetLastError());
+    if (r.dev) emit_out(q);
+    else copy_out(q);
+    // zeroize the device copies of witness-derived data (the reference uses Zeroizing<> for these, SURVEY 5)
+    HIP_CHECK(hipMemsetAsync(ctx->prove_arena.p + u.arena_lo, 0, u.arena_len, s));
+  }
+
+  // ---- sub-batch q's proofs, status words and made commitments to the page-locked staging ...
+  void copy_out(uint32_t q) {
+    Sub &u = subs[q];
+    hipStream_t s = lane_stream(q);
+    const uint32_t nb = u.nb;
     if (r.states203)
       HIP_CHECK(hipMemcpyAsync(pin_tstates + (size_t)u.lo * BPP_STATE_ROW_WORDS, u.d_tstates, (size_t)nb * BPP_STATE_ROW_WORDS * 4,
                                hipMemcpyDeviceToHost, s));
@@ -526,8 +637,34 @@ struct ProveCall {
                                hipMemcpyDeviceToHost, s));
     if (r.made32)
       HIP_CHECK(hipMemcpyAsync(pin_made + (size_t)u.lo * m * 32, u.d_commit32, (size_t)nb * m * 32, hipMemcpyDeviceToHost, s));
-    // zeroize the device copies of witness-derived data (the reference uses Zeroizing<> for these, SURVEY 5)
-    HIP_CHECK(hipMemsetAsync(ctx->prove_arena.p + u.arena_lo, 0, u.arena_len, s));
+  }
+  // ---- ... or scattered into the caller's rows in device memory by k_prove_emit; one outcome record per slot -- a code and a message
+  // id, public -- is all that travels to the host
+  void emit_out(uint32_t q) {
+    Sub &u = subs[q];
+    hipStream_t s = lane_stream(q);
+    const uint32_t nb = u.nb;
+    ProveEmit e;
+    memset(&e, 0, sizeof(e));
+    e.rows = u.d_rows;
+    e.n = nb;
+    e.slots = 1;
+    e.finding = u.d_finding;
+    e.status = (const uint8_t *)&u.d_ps[0].status;
+    e.status_stride = (uint32_t)sizeof(ProveState);
+    e.proofs = u.d_proofs;
+    e.plen = (uint32_t)plen;
+    e.commit32 = u.d_commit32;
+    e.mslot = m;
+    e.proofs_out = r.dev->proofs_out;
+    e.proof_stride = r.dev->proof_stride;
+    e.commitments_out = r.dev->commitments_out;
+    e.commit_stride = r.dev->commit_stride;
+    e.status_dev = r.dev->status_dev;
+    e.outcome = u.d_outcome;
+    hipLaunchKernelGGL(k_prove_emit, dim3(cdiv(nb, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, e);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(pin_outcome + u.lo, u.d_outcome, (size_t)nb * sizeof(bpp_device_prove_status), hipMemcpyDeviceToHost, s));
   }
 
   // ---- Everything is enqueued and this thread has nothing to do for the call's ~6 ms: the host copies of the witness (the packed
@@ -571,6 +708,10 @@ struct ProveCall {
 
   // ---- status words -> errors, the made commitments, the transcripts, the self-check, the proofs
   void results() {
+    if (r.dev) {  // (the proofs and commitments are where they belong; the entry point sorts the outcomes out)
+      r.dev->outcome.assign(pin_outcome, pin_outcome + B);
+      return;
+    }
     if (!r.dev_status) {
       for (uint32_t i = 0; i < B; i++) {
         if (pin_status[i] & PV_STATUS_COMMIT_MISMATCH) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Witness opening is invalid!"};
@@ -609,7 +750,7 @@ int prove_uniform(bpp_ctx *ctx, const ProveRequest &r, char *errbuf, size_t errb
   try {
     const std::shared_ptr<Params> Pp = params_registry().get(r.params);
     if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
-    if (!r.items || r.n_items == 0 || !r.proofs_out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
+    if ((!r.dev && (!r.items || !r.proofs_out)) || r.n_items == 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
     ProveCall c(ctx, *Pp, r);
     ScopeExit wipe_secrets{[&] { c.wipe_secrets(); }};
     c.pack();
@@ -1141,6 +1282,160 @@ extern "C" int bpp_prove_item_message(bpp_ctx *ctx, uint64_t params, const bpp_p
 extern "C" int bpp_prove_openings_item_message(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item, const uint8_t *first_commitment32,
                                                size_t commit_stride, size_t proof_stride, int status, char *errbuf, size_t errbuf_len) {
   return prove_item_message(ctx, params, item, proof_stride, status, errbuf, errbuf_len, true, commit_stride, first_commitment32);
+}
+
+// ================================================================= openings in device memory
+// bpp_prove_openings_device (include/bpp.h; prove_ingest.h has the split of the checks and the two kernels).  prove_mixed's shape
+// with the witness left where it is: the host checks every item from m[] and the strides, sorts the ones that pass largest m first
+// and runs them as ONE ragged call whose source is k_prove_ingest and whose sink is k_prove_emit.  The items it refuses get their
+// status record and their zeroed slots from one launch of the emit kernel over a small table, in front of the call.
+namespace {
+int prove_openings_device(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays *in, uint8_t *commitments_out, size_t commit_stride,
+                          uint8_t *proofs_out, size_t proof_stride, size_t *proof_lens, bpp_device_prove_status *status_dev, int *item_status,
+                          char *errbuf, size_t errbuf_len) {
+  try {
+    if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
+    // pointer kinds first: nothing is allocated or launched for an array this device cannot reach, and no array is ever
+    // dereferenced on the host
+    static const char *const kinds[] = {"", "memory of another device", "host memory or memory the runtime does not know", "managed memory"};
+    const struct {
+      const char *name;
+      const void *p;
+    } arrays[] = {{"values", in->values},
+                  {"blindings32", in->blindings32},
+                  {"commitments32", in->commitments32},
+                  {"min_values", in->min_values},
+                  {"min_present", in->min_present},
+                  {"seed_nonces32", in->seed_nonces32},
+                  {"seed_present", in->seed_present},
+                  {"rng_bytes", in->rng_bytes},
+                  {"commitments_out_dev", commitments_out},
+                  {"proofs_out_dev", proofs_out},
+                  {"status_dev", status_dev}};
+    if (!commitments_out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "commitments_out_dev is null", errbuf, errbuf_len);
+    if (!proofs_out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proofs_out_dev is null", errbuf, errbuf_len);
+    for (const auto &a : arrays) {
+      if (!a.p) continue;
+      const int kind = device_pointer_kind(ctx->device, a.p);
+      if (kind != BPP_PTR_THIS_DEVICE)
+        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + " is not device memory of this context's device (" + kinds[kind] + ")", errbuf,
+                    errbuf_len);
+    }
+    if (!in->m || in->n_items == 0 || !proof_lens) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
+    if (device_pointer_kind(ctx->device, in->m) != BPP_PTR_HOST_OR_UNKNOWN)
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m must be host memory: it sizes the call's layout", errbuf, errbuf_len);
+    if (in->m_stride == 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m_stride is 0", errbuf, errbuf_len);
+    if (ctx->opt.prove_check > 0)
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT,
+                  "prove_check = 1 is not supported by bpp_prove_openings_device: the self-check remakes from host items; verify the outputs "
+                  "with bpp_verify_batch_mixed_device",
+                  errbuf, errbuf_len);
+    if (in->transcript_state && in->transcript_state[200] >= BPP_STROBE_R) return fail(ctx, prove_err(BPP_PROVE_MSG_TRANSCRIPT_STATE).code,
+                                                                                      prove_msg_text(BPP_PROVE_MSG_TRANSCRIPT_STATE), errbuf, errbuf_len);
+    const std::shared_ptr<Params> Pp = params_registry().get(params);
+    if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
+    const size_t n_items = in->n_items;
+    if (n_items > (1u << 24)) return fail(ctx, BPP_ERR_SIZE_OVERFLOW, "batch too large", errbuf, errbuf_len);
+    const ParamShape shape{Pp->n_bits, Pp->m_max, Pp->t};
+
+    // the host's part of the checks, per item; the ones that pass by aggregation factor, largest first, in the caller's order
+    const bool fields_ok = in->values && in->blindings32 && in->rng_bytes && (in->min_values || !in->min_present);
+    std::vector<uint32_t> msg(n_items, BPP_PROVE_MSG_OK);
+    std::map<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> classes;
+    std::vector<ProveDevRow> refused;
+    for (size_t i = 0; i < n_items; i++) {
+      const uint32_t mi = in->m[i];
+      proof_lens[i] = prove_item_len_host(shape, mi);
+      msg[i] = prove_item_layout_finding(shape, mi, proof_stride, true, commit_stride, fields_ok);
+      if (!msg[i] && mi > in->m_stride)  // (an item the layout holds, but not a row of the arrays: the geometry is the call's)
+        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m_stride is below an aggregation factor", errbuf, errbuf_len);
+      if (!msg[i]) msg[i] = prove_item_rng_finding(shape, mi, in->rng_stride);
+      if (!msg[i]) {
+        classes[mi].push_back((uint32_t)i);
+        continue;
+      }
+      uint32_t zero = 0;  // (zeroed where the strides can hold them, as prove_mixed does)
+      if (proof_lens[i] && proof_stride >= proof_lens[i]) zero |= BPP_PROVE_ROW_ZERO_PROOF;
+      if (proof_lens[i] && commit_stride >= (size_t)32 * mi) zero |= BPP_PROVE_ROW_ZERO_COMMIT;
+      refused.push_back(ProveDevRow{(uint32_t)i, mi, (uint32_t)proof_lens[i], msg[i], zero});
+    }
+    struct bpp_prove_device_stats &stats = ctx->prove_dev_stats;
+    stats.calls++;
+    stats.items += n_items;
+    stats.host_findings += refused.size();
+    hipStream_t s = ctx->stream;
+    if (!refused.empty()) {
+      ctx->prove_dev_refused.alloc(refused.size() * sizeof(ProveDevRow));
+      HIP_CHECK(hipMemcpyAsync(ctx->prove_dev_refused.p, refused.data(), refused.size() * sizeof(ProveDevRow), hipMemcpyHostToDevice, s));
+      ProveEmit e;
+      memset(&e, 0, sizeof(e));
+      e.rows = (const ProveDevRow *)ctx->prove_dev_refused.p;
+      e.n = (uint32_t)refused.size();
+      e.proofs_out = proofs_out;
+      e.proof_stride = proof_stride;
+      e.commitments_out = commitments_out;
+      e.commit_stride = commit_stride;
+      e.status_dev = status_dev;
+      hipLaunchKernelGGL(k_prove_emit, dim3(cdiv(e.n, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, e);
+      HIP_CHECK(hipGetLastError());
+      HIP_CHECK(hipStreamSynchronize(s));  // (the table is pageable host memory of this frame)
+    }
+
+    ProveDeviceIO io{in, {}, {}, commitments_out, commit_stride, proofs_out, proof_stride, status_dev, {}};
+    for (auto &kv : classes)
+      for (uint32_t i : kv.second) {
+        io.m_sorted.push_back(kv.first);
+        io.rows.push_back(ProveDevRow{i, kv.first, (uint32_t)proof_lens[i], BPP_PROVE_MSG_OK, BPP_PROVE_ROW_ZERO_PROOF | BPP_PROVE_ROW_ZERO_COMMIT});
+      }
+    std::string engine_err;
+    int engine_rc = BPP_OK;
+    if (!io.rows.empty()) {
+      (void)take_tamper(ctx);  // (the self-check's test knobs name a call that checks: this one does not)
+      char err[256];
+      err[0] = 0;
+      ProveRequest req{params, nullptr, io.rows.size(), nullptr, 0, nullptr};
+      req.mixed = true;
+      req.dev = &io;
+      engine_rc = prove_uniform(ctx, req, err, sizeof(err));
+      engine_err = err;
+      for (size_t k = 0; k < io.rows.size(); k++) {
+        const uint32_t i = io.rows[k].item;
+        msg[i] = engine_rc != BPP_OK ? BPP_PROVE_MSG_ENGINE : io.outcome[k].msg;
+        if (engine_rc == BPP_OK && msg[i] >= BPP_PROVE_MSG_SEED_AGGREGATED && msg[i] <= BPP_PROVE_MSG_SEED_NONCE) stats.device_findings++;
+      }
+    }
+    for (size_t i = 0; item_status && i < n_items; i++) item_status[i] = msg[i] == BPP_PROVE_MSG_ENGINE ? engine_rc : prove_msg_code(msg[i]);
+    for (size_t i = 0; i < n_items; i++) {
+      if (msg[i] == BPP_PROVE_MSG_ENGINE) return fail(ctx, engine_rc, engine_err, errbuf, errbuf_len);
+      if (msg[i]) return fail(ctx, prove_msg_code(msg[i]), prove_msg_text(msg[i]), errbuf, errbuf_len);
+    }
+    set_err(errbuf, errbuf_len, "");
+    return BPP_OK;
+  }
+  BPP_CATCH(ctx, errbuf, errbuf_len)
+}
+}  // namespace
+
+extern "C" int bpp_prove_openings_device(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays *in_dev, uint8_t *commitments_out_dev,
+                                         size_t commit_stride, uint8_t *proofs_out_dev, size_t proof_stride, size_t *proof_lens,
+                                         bpp_device_prove_status *status_dev, int *item_status, char *errbuf, size_t errbuf_len) {
+  BPP_ENTRY(ctx);
+  return prove_openings_device(ctx, params, in_dev, commitments_out_dev, commit_stride, proofs_out_dev, proof_stride, proof_lens, status_dev,
+                               item_status, errbuf, errbuf_len);
+}
+
+extern "C" int bpp_prove_status_result(const bpp_device_prove_status *host_copy, bpp_shard_result *out) {
+  if (!host_copy || !out || host_copy->msg > BPP_PROVE_MSG_ENGINE) return BPP_ERR_INVALID_ARGUMENT;
+  memset(out, 0, sizeof(*out));
+  shard_result_set(*out, host_copy->code, host_copy->msg ? BPP_TIER_CONSTRUCTION : BPP_TIER_NONE, -1, 0, prove_msg_text(host_copy->msg));
+  return BPP_OK;
+}
+
+extern "C" int bpp_prove_device_stats(bpp_ctx *ctx, struct bpp_prove_device_stats *out) {
+  BPP_ENTRY(ctx);
+  if (!out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
+  *out = ctx->prove_dev_stats;
+  return BPP_OK;
 }
 
 #ifdef BPP_KP_PHASES

@@ -1,0 +1,280 @@
+// Device side of bpp_prove_openings_device: the openings of a prove call (bpp_prove_arrays: rows of m_stride entries per item, the
+// used part of every row in the host array m[]) are checked and packed where they lie in device memory, and the proofs, commitments
+// and per-item outcomes are scattered into the caller's rows in device memory.  The prover's counterpart of ingest_mixed.h: the copy
+// (ingest_copy / ingest_zero) and the launch geometry are those of ingest.h.  Shared by the kernels (k_prove_ingest, k_prove_emit), by
+// the engine's driver (engine_prove.h) and by the sanitizer harness (hosttest_prove_ingest.cpp), which runs the routines on the host,
+// lane by lane, against ProvePack::pack and prove_item_check_host on the sorted equivalent items.
+//
+// Split of the checks (prove_job_host.h states them and their order):
+//   host, no witness byte needed: prove_item_layout_finding + prove_item_rng_finding per item from m[], the strides and which arrays
+//     are given.  An item they fail never reaches the device (as in prove_mixed).
+//   device (prove_ingest_check): a nonce on an item with m > 1; per opening j in order "Value exceeds bit vector capacity!" then
+//     "Minimum value is larger than value"; per blinding factor in order "blinding factor is not canonical"; "seed nonce is not
+//     canonical".  The precedence inside an item is prove_item_check_host's.
+//   ONE precedence difference: the host routine raises "Mask recovery is not supported..." BEFORE the rng-length check, but the host
+//     cannot see seed_present; an item with both a nonce at m > 1 and an rng_stride too short for its m reports the rng-length
+//     finding here.  Reachable only with an rng_stride below what the call's largest m needs.
+//
+// The layout is the host's (prove_plan_device: ProveDesc rows, roff, mslot, offsets and transcript states from m[] alone, sorted
+// largest m first as prove_mixed sorts); the kernel writes the bytes ProvePack::pack would have written for the sorted items, so that
+// the prover's kernels read nothing new.  A FAILING item is never copied: its slot receives a fixed, public, valid substitute
+// witness (value 0, first blinding factor 1 and the others 0, no promises, no nonce; its commitment is the first blinding base, not
+// the identity), costs what a live slot costs and has its result discarded -- the launch geometry depends on nothing the host does
+// not know.
+//
+// ROW SLACK is never read and never written: every loop is bounded by the item's own m, rng length and proof length.
+#pragma once
+#include "ingest.h"
+#include "prove_pack_host.h"
+
+namespace bpp {
+
+// sorted slot k of a sub-batch (or a row of the refused items' table): the caller's item it reads and writes
+struct ProveDevRow {
+  uint32_t item;       // src[k]: the row of the caller's arrays
+  uint32_t m;
+  uint32_t proof_len;  // prove_item_len_host(m): 0 for an m no statement can have
+  uint32_t msg;        // a finding the host already has (a refused item: it has no slot), else 0
+  uint32_t zero;       // a failed item: bit 0 the proof slot, bit 1 the commitment slot may be zeroed (the strides hold them)
+};
+#define BPP_PROVE_ROW_ZERO_PROOF 1u
+#define BPP_PROVE_ROW_ZERO_COMMIT 2u
+
+// the caller's arrays as the ingest kernel sees them, and where a sub-batch's pieces go
+struct ProveIngest {
+  const uint8_t *values;  // (bytes: the array may lie at any byte address)
+  const uint8_t *blindings32, *commitments32;
+  const uint8_t *min_values;
+  const uint8_t *min_present, *seed_nonces32, *seed_present, *rng_bytes;
+  uint64_t rng_stride;
+  uint32_t m_stride, n_bits, t, nb;
+  const uint8_t *g0_32;  // the compressed first blinding base: what a substitute slot brings where the call brings commitments
+  const ProveDevRow *rows;
+  ProveDesc *desc;       // nb rows as the host planned them; bit 0 of flags is the kernel's
+  uint8_t *bytes;
+  uint64_t *minvals;
+  uint8_t *minpres;
+  uint32_t *finding;     // nb words: 0, or prove_ingest_key of the item's first finding
+};
+
+BPP_HD bool prove_seed_present(const ProveIngest &a, size_t i) { return a.seed_nonces32 && (!a.seed_present || a.seed_present[i]); }
+
+BPP_HD uint64_t prove_load_le64(const uint8_t *p) {
+  uint64_t v = 0;
+  for (int k = 0; k < 8; k++) v |= (uint64_t)p[k] << (8 * k);
+  return v;
+}
+
+// A finding's key: the larger key is the EARLIER finding in prove_item_check_host's order -- stage (nonce on an aggregated item,
+// openings, blinding factors, nonce), then the index inside the stage -- so that a maximum over the item's lanes is its first one.
+#define BPP_PROVE_STAGE_SEED_AGGREGATED 0u
+#define BPP_PROVE_STAGE_OPENINGS 1u  // index 2 j: the value, 2 j + 1: its promise
+#define BPP_PROVE_STAGE_BLINDINGS 2u
+#define BPP_PROVE_STAGE_SEED_NONCE 3u
+BPP_HD uint32_t prove_ingest_key(uint32_t stage, uint32_t index, uint32_t msg) { return 0xffffffffu - ((stage << 28) | (index << 8) | msg); }
+BPP_HD uint32_t prove_ingest_key_msg(uint32_t key) { return key ? ((0xffffffffu - key) & 255u) : 0u; }
+BPP_HD uint32_t prove_key_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
+
+// `lane`'s share of the witness checks of sorted slot k: the key of the first finding among what this lane looked at, 0 for none
+BPP_HD uint32_t prove_ingest_check(const ProveIngest &a, uint32_t k, uint32_t lane, uint32_t lanes) {
+  const size_t i = a.rows[k].item, row = i * (size_t)a.m_stride;
+  const uint32_t m = a.desc[k].m;
+  const bool seed = prove_seed_present(a, i);
+  uint32_t key = 0;
+  if (lane == 0 && seed && m > 1) key = prove_ingest_key(BPP_PROVE_STAGE_SEED_AGGREGATED, 0, BPP_PROVE_MSG_SEED_AGGREGATED);
+  for (uint32_t j = lane; j < m; j += lanes) {
+    const uint64_t v = prove_load_le64(a.values + 8 * (row + j));
+    if (a.n_bits < 64 && (v >> a.n_bits) > 0) key = prove_key_max(key, prove_ingest_key(BPP_PROVE_STAGE_OPENINGS, 2 * j, BPP_PROVE_MSG_VALUE));
+    const bool present = a.min_present ? a.min_present[row + j] != 0 : false;
+    if (present && v < prove_load_le64(a.min_values + 8 * (row + j)))
+      key = prove_key_max(key, prove_ingest_key(BPP_PROVE_STAGE_OPENINGS, 2 * j + 1, BPP_PROVE_MSG_MINIMUM));
+  }
+  for (uint32_t q = lane; q < m * a.t; q += lanes)
+    if (!sc_is_canonical(a.blindings32 + 32 * (row * a.t + q)))
+      key = prove_key_max(key, prove_ingest_key(BPP_PROVE_STAGE_BLINDINGS, q, BPP_PROVE_MSG_BLINDING));
+  if (lane == 0 && seed && !sc_is_canonical(a.seed_nonces32 + 32 * i))
+    key = prove_key_max(key, prove_ingest_key(BPP_PROVE_STAGE_SEED_NONCE, 0, BPP_PROVE_MSG_SEED_NONCE));
+  return key;
+}
+
+// `lane`'s share of what sorted slot k receives: the item's bytes, or (failed) the substitute's.  Every byte of the slot's ranges is
+// written by exactly one lane.
+BPP_HD void prove_ingest_move(const ProveIngest &a, uint32_t k, bool failed, uint32_t lane, uint32_t lanes) {
+  const ProveDesc d = a.desc[k];
+  const size_t i = a.rows[k].item, row = i * (size_t)a.m_stride;
+  const uint32_t m = d.m, wsz = 8 + 32 * a.t;
+  const size_t rng_len = (size_t)d.seed_off - d.ext_off;  // (rounds + 3) x 32: the plan's
+  uint8_t *wit = a.bytes + d.wit_off, *com = a.bytes + d.commit_off;
+  if (failed) {
+    for (uint32_t q = lane; q < m * wsz; q += lanes) wit[q] = (q % wsz) == 8 ? 1 : 0;  // v = 0, r[0] = 1, r[1..t) = 0
+    for (uint32_t q = lane; q < 32 * m; q += lanes) com[q] = a.commitments32 ? a.g0_32[q & 31u] : 0;
+    ingest_zero(a.bytes + d.ext_off, rng_len, lane, lanes);
+    ingest_zero(a.bytes + d.seed_off, 32, lane, lanes);
+    for (uint32_t j = lane; j < m; j += lanes) {
+      a.minvals[d.minval_idx + j] = 0;
+      a.minpres[d.minval_idx + j] = 0;
+    }
+    return;
+  }
+  for (uint32_t j = 0; j < m; j++) {
+    for (uint32_t q = lane; q < 8; q += lanes) wit[j * wsz + q] = a.values[8 * (row + j) + q];
+    ingest_copy(wit + j * wsz + 8, a.blindings32 + 32 * (row + j) * a.t, 32 * (size_t)a.t, lane, lanes);
+  }
+  if (a.commitments32) ingest_copy(com, a.commitments32 + 32 * row, 32 * (size_t)m, lane, lanes);
+  else ingest_zero(com, 32 * (size_t)m, lane, lanes);  // (to be made: kp_adopt_commitments writes them here)
+  ingest_copy(a.bytes + d.ext_off, a.rng_bytes + i * (size_t)a.rng_stride, rng_len, lane, lanes);
+  if (prove_seed_present(a, i)) {
+    ingest_copy(a.bytes + d.seed_off, a.seed_nonces32 + 32 * i, 32, lane, lanes);
+    if (lane == 0) a.desc[k].flags = d.flags | 1u;
+  } else {
+    ingest_zero(a.bytes + d.seed_off, 32, lane, lanes);
+  }
+  for (uint32_t j = lane; j < m; j += lanes) {
+    const bool present = a.min_present ? a.min_present[row + j] != 0 : false;
+    a.minvals[d.minval_idx + j] = present ? prove_load_le64(a.min_values + 8 * (row + j)) : 0;
+    a.minpres[d.minval_idx + j] = present ? 1 : 0;
+  }
+}
+
+// what the emit kernel reads of a sub-batch behind kp_finish (or, slots == 0, of the refused items' table) and where it writes
+struct ProveEmit {
+  const ProveDevRow *rows;
+  uint32_t n;
+  uint32_t slots;             // 1: row k is sorted slot k of the sub-batch; 0: the rows carry their finding and have no slot
+  const uint32_t *finding;    // the ingest kernel's words
+  const uint8_t *status;      // ProveState::status of slot 0 ...
+  uint32_t status_stride;     // ... and the bytes from one slot's to the next
+  const uint8_t *proofs;      // rows of plen
+  uint32_t plen;
+  const uint8_t *commit32;    // what the witness check computed, rows of 32 x mslot
+  uint32_t mslot;
+  uint8_t *proofs_out;
+  uint64_t proof_stride;
+  uint8_t *commitments_out;
+  uint64_t commit_stride;
+  bpp_device_prove_status *status_dev;  // by item; may be null
+  bpp_device_prove_status *outcome;     // by slot: what travels to the host (null without slots)
+};
+
+// the outcome of row k: the host's finding, else the ingest finding, else the proof's status bits as prove_mixed maps them
+BPP_HD uint32_t prove_emit_msg(const ProveEmit &e, uint32_t k) {
+  if (e.rows[k].msg) return e.rows[k].msg;
+  if (!e.slots) return BPP_PROVE_MSG_OK;
+  if (e.finding[k]) return prove_ingest_key_msg(e.finding[k]);
+  const uint8_t *s = e.status + (size_t)k * e.status_stride;
+  const uint32_t st = (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | ((uint32_t)s[3] << 24);
+  if (st & 2u) return BPP_PROVE_MSG_OPENING;   // PV_STATUS_COMMIT_MISMATCH
+  if (st & 1u) return BPP_PROVE_MSG_IDENTITY;  // PV_STATUS_TRANSCRIPT
+  return BPP_PROVE_MSG_OK;
+}
+
+BPP_HD void prove_emit_row(const ProveEmit &e, uint32_t k, uint32_t lane, uint32_t lanes) {
+  const ProveDevRow r = e.rows[k];
+  const uint32_t msg = prove_emit_msg(e, k);
+  uint8_t *po = e.proofs_out + (size_t)r.item * e.proof_stride, *co = e.commitments_out + (size_t)r.item * e.commit_stride;
+  if (msg == BPP_PROVE_MSG_OK) {
+    ingest_copy(po, e.proofs + (size_t)k * e.plen, r.proof_len, lane, lanes);
+    ingest_copy(co, e.commit32 + (size_t)k * 32 * e.mslot, 32 * (size_t)r.m, lane, lanes);
+  } else {
+    if (r.zero & BPP_PROVE_ROW_ZERO_PROOF) ingest_zero(po, r.proof_len, lane, lanes);
+    if (r.zero & BPP_PROVE_ROW_ZERO_COMMIT) ingest_zero(co, 32 * (size_t)r.m, lane, lanes);
+  }
+  if (lane == 0) {
+    const bpp_device_prove_status rec{prove_msg_code(msg), msg};
+    if (e.status_dev) e.status_dev[r.item] = rec;
+    if (e.outcome) e.outcome[k] = rec;
+  }
+}
+
+#if defined(__HIPCC__)
+// The geometry of k_ingest_mixed: BPP_INGEST_LANES lanes per item, 256-lane blocks, four items of different m to a wavefront.  Every
+// loop bound is the item's own and NO lane returns: all 64 reach the width-16 shuffles (a lane past nb with a zero key).  The
+// item's lanes first agree on its finding, then all of them move the item or all of them write the substitute.
+__global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_prove_ingest(ProveIngest a) {
+  const size_t gid = (size_t)blockIdx.x * BPP_INGEST_BLOCK + threadIdx.x;
+  const size_t k = gid / BPP_INGEST_LANES;
+  const uint32_t lane = (uint32_t)(gid % BPP_INGEST_LANES);
+  const bool live = k < a.nb;
+  uint32_t key = live ? prove_ingest_check(a, (uint32_t)k, lane, BPP_INGEST_LANES) : 0u;
+  for (uint32_t o = BPP_INGEST_LANES / 2; o; o >>= 1) key = prove_key_max(key, (uint32_t)__shfl_xor((int)key, (int)o, (int)BPP_INGEST_LANES));
+  if (live) {
+    prove_ingest_move(a, (uint32_t)k, key != 0, lane, BPP_INGEST_LANES);
+    if (lane == 0) a.finding[k] = key;
+  }
+}
+
+// Behind kp_finish: the same geometry, BPP_INGEST_LANES lanes per row.
+__global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_prove_emit(ProveEmit e) {
+  const size_t gid = (size_t)blockIdx.x * BPP_INGEST_BLOCK + threadIdx.x;
+  const size_t k = gid / BPP_INGEST_LANES;
+  if (k < e.n) prove_emit_row(e, (uint32_t)k, (uint32_t)(gid % BPP_INGEST_LANES), BPP_INGEST_LANES);
+}
+#endif
+
+// ---- host side: the plan in front of the run.  Pure host C++ over prove_pack_host.h.
+
+// What ProvePack::pack makes of the sorted equivalent items, as far as it follows from their aggregation factors alone: the
+// descriptors with their offsets, roff, the distinct transcript states with the call-level appends, the call's m, rounds and proof
+// length, and bytes_len.  `bytes`, `minvals` and `minpres` stay empty: the ingest kernel writes them on the device.
+// m_sorted: the aggregation factors of the items that passed the host's part of the checks, largest first.  brought: the call
+// brings a commitments array.  One transcript source for the call: a state for every distinct m, in the order they first appear.
+inline void prove_plan_device(const ParamShape &P, const uint8_t *hg32, const uint32_t *m_sorted, size_t n_items, bool brought,
+                              const uint8_t *transcript_state, const uint8_t *transcript_label, size_t label_len, ProvePack &pk) {
+  const uint32_t t = P.t, B = (uint32_t)n_items;
+  pk.m = m_sorted[0];
+  pk.plen = prove_item_len_host(P, pk.m);
+  pk.rounds = pk.rounds_min = prove_rounds_host(P, pk.m);
+  pk.desc.assign(B, ProveDesc{});
+  pk.roff.assign(B, 0);
+  std::vector<uint32_t> state_m;
+  size_t at = 0;
+  for (uint32_t i = 0; i < B; i++) {
+    const uint32_t mi = m_sorted[i], rounds_i = prove_rounds_host(P, mi);
+    ProveDesc &d = pk.desc[i];
+    d.m = mi;
+    d.mslot = pk.m;
+    d.roff = pk.roff[i] = pk.rounds - rounds_i;
+    pk.rounds_min = std::min(pk.rounds_min, rounds_i);
+    d.minval_idx = i * pk.m;
+    d.wit_off = (uint32_t)at;
+    at += (size_t)mi * (8 + 32 * t);
+    d.commit_off = (uint32_t)at;
+    at += (size_t)mi * 32;
+    d.ext_off = (uint32_t)at;
+    at += 32 * (size_t)(rounds_i + 3);
+    d.seed_off = (uint32_t)at;
+    at += 32;
+    d.flags = brought ? 0u : PV_FLAG_MAKE_COMMITMENTS;
+    if (i && m_sorted[i - 1] == mi) {
+      d.state_idx = pk.desc[i - 1].state_idx;
+      continue;
+    }
+    d.state_idx = (uint32_t)state_m.size();
+    state_m.push_back(mi);
+  }
+  pk.bytes_len = at;
+  pk.states.assign(state_m.size() * 203, 0);
+  for (size_t id = 0; id < state_m.size(); id++) {
+    if (transcript_state) {
+      memcpy(&pk.states[id * 203], transcript_state, 203);
+    } else {
+      Strobe st;
+      merlin_new(st, transcript_label, (uint32_t)(transcript_label ? label_len : 0));
+      strobe_to_bytes(&pk.states[id * 203], st);
+    }
+  }
+  pk.advance_states(P, hg32, state_m);
+}
+
+// the run of one sub-batch on the host, `lanes` lanes per item reduced as the kernel reduces: the model the harness holds to the
+// item form
+inline void prove_ingest_run_host(const ProveIngest &a, uint32_t lanes) {
+  for (uint32_t k = 0; k < a.nb; k++) {
+    uint32_t key = 0;
+    for (uint32_t lane = 0; lane < lanes; lane++) key = prove_key_max(key, prove_ingest_check(a, k, lane, lanes));
+    for (uint32_t lane = 0; lane < lanes; lane++) prove_ingest_move(a, k, key != 0, lane, lanes);
+    a.finding[k] = key;
+  }
+}
+
+}  // namespace bpp

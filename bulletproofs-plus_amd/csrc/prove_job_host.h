@@ -27,31 +27,85 @@ inline size_t prove_item_len_host(const ParamShape &P, uint32_t m) {
   return 1 + 32 * (size_t)(P.t + 5 + 2 * prove_rounds_host(P, m));
 }
 
+// The per-item findings of a prove call, by id (include/bpp.h: BPP_PROVE_MSG_*): the code and the text each one has in every
+// prove entry point.  The device form (prove_ingest.h) carries the id in its finding words and status records.
+BPP_HD int prove_msg_code(uint32_t msg) {
+  switch (msg) {
+    case BPP_PROVE_MSG_OK: return BPP_OK;
+    case BPP_PROVE_MSG_BITS:
+    case BPP_PROVE_MSG_PROOF_STRIDE:
+    case BPP_PROVE_MSG_COMMIT_STRIDE:
+    case BPP_PROVE_MSG_RNG_LEN:
+    case BPP_PROVE_MSG_VALUE: return BPP_ERR_INVALID_LENGTH;
+    case BPP_PROVE_MSG_IDENTITY: return BPP_ERR_VERIFICATION_FAILED;
+    case BPP_PROVE_MSG_ENGINE: return BPP_ERR_ENGINE;
+    default: return BPP_ERR_INVALID_ARGUMENT;
+  }
+}
+
+inline const char *prove_msg_text(uint32_t msg) {
+  static const char *const text[] = {"",
+                                     "Number of commitments must be a power of two",
+                                     "Not enough generators for this statement",
+                                     "bit_length * aggregation factor must be at least 2",
+                                     "proof_stride too small",
+                                     "commit_stride too small",
+                                     "null witness / statement field",
+                                     "Mask recovery is not supported with an aggregated statement",
+                                     "not enough external randomness: need (rounds + 3) * 32 bytes",
+                                     "Value exceeds bit vector capacity!",
+                                     "Minimum value is larger than value",
+                                     "blinding factor is not canonical",
+                                     "seed nonce is not canonical",
+                                     "transcript state has pos >= rate",
+                                     "Witness opening is invalid!",
+                                     "Identity element cannot be added to the transcript / zero challenge",
+                                     "engine fault: see bpp_ctx_last_error"};
+  return msg < sizeof(text) / sizeof(text[0]) ? text[msg] : "unknown finding";
+}
+
+inline ProofErr prove_err(uint32_t msg) { return ProofErr{prove_msg_code(msg), prove_msg_text(msg)}; }
+
+// The per-item checks come in two parts, in this order.
+// PART ONE needs no witness byte: the aggregation factor, the strides, which fields are given (fields_ok: values, blinding factors,
+// rng bytes, commitments unless they are to be made, no min_present without min_values), and the length of the external randomness.
+// Returns the first finding's id, 0 for none.  prove_item_check_host runs it on an item; bpp_prove_openings_device runs it per
+// item from m[] and the call's strides and array pointers alone, and an item it fails never reaches the device.
+inline uint32_t prove_item_layout_finding(const ParamShape &P, uint32_t m, size_t proof_stride, bool openings, size_t commit_stride,
+                                          bool fields_ok) {
+  if (m == 0 || (m & (m - 1))) return BPP_PROVE_MSG_POWER_OF_TWO;
+  if (P.m_max < m) return BPP_PROVE_MSG_GENERATORS;
+  if (m * P.n_bits < 2) return BPP_PROVE_MSG_BITS;
+  if (proof_stride < prove_item_len_host(P, m)) return BPP_PROVE_MSG_PROOF_STRIDE;
+  if (openings && commit_stride < (size_t)32 * m) return BPP_PROVE_MSG_COMMIT_STRIDE;
+  if (!fields_ok) return BPP_PROVE_MSG_NULL_FIELD;
+  return BPP_PROVE_MSG_OK;
+}
+inline uint32_t prove_item_rng_finding(const ParamShape &P, uint32_t m, size_t rng_len) {
+  return rng_len < 32 * (size_t)(prove_rounds_host(P, m) + 3) ? BPP_PROVE_MSG_RNG_LEN : BPP_PROVE_MSG_OK;
+}
+
 // the host-side checks of a one-item bpp_prove_batch on `it`, in the same order and with the same codes and messages.
 // openings: an item of bpp_prove_openings / bpp_prove_pool_openings, which may come without commitments and whose commitments go
 // to a slot of commit_stride bytes.  Nothing behind a pointer is read before the checks of m and of the pointers have passed.
+// PART TWO, what reads witness bytes (a nonce on an aggregated item, the values and promises, the blinding factors, the nonce), is
+// restated for arrays in device memory by prove_ingest.h (prove_ingest_check); hosttest_prove_ingest.cpp holds the two to each other.
+// There the "Mask recovery is not supported..." finding comes AFTER the rng length: the host cannot see which items carry a nonce.
 inline void prove_item_check_host(const ParamShape &P, const bpp_prove_item &it, size_t proof_stride, bool openings, size_t commit_stride) {
   const uint32_t n = P.n_bits, t = P.t, m = it.m;
-  if (m == 0 || (m & (m - 1))) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Number of commitments must be a power of two"};
-  if (P.m_max < m) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Not enough generators for this statement"};
-  if (m * n < 2) throw ProofErr{BPP_ERR_INVALID_LENGTH, "bit_length * aggregation factor must be at least 2"};
-  if (proof_stride < prove_item_len_host(P, m)) throw ProofErr{BPP_ERR_INVALID_LENGTH, "proof_stride too small"};
-  if (openings && commit_stride < (size_t)32 * m) throw ProofErr{BPP_ERR_INVALID_LENGTH, "commit_stride too small"};
-  if (!it.values || !it.blindings32 || (!it.commitments32 && !openings) || !it.rng_bytes || (!it.min_values && it.min_present))
-    throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "null witness / statement field"};
-  if (it.seed_nonce32 && m > 1) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Mask recovery is not supported with an aggregated statement"};
-  if (it.rng_len < 32 * (size_t)(prove_rounds_host(P, m) + 3))
-    throw ProofErr{BPP_ERR_INVALID_LENGTH, "not enough external randomness: need (rounds + 3) * 32 bytes"};
+  const bool fields_ok = it.values && it.blindings32 && (it.commitments32 || openings) && it.rng_bytes && (it.min_values || !it.min_present);
+  if (const uint32_t f = prove_item_layout_finding(P, m, proof_stride, openings, commit_stride, fields_ok)) throw prove_err(f);
+  if (it.seed_nonce32 && m > 1) throw prove_err(BPP_PROVE_MSG_SEED_AGGREGATED);
+  if (const uint32_t f = prove_item_rng_finding(P, m, it.rng_len)) throw prove_err(f);
   for (uint32_t j = 0; j < m; j++) {
-    if (n < 64 && (it.values[j] >> n) > 0) throw ProofErr{BPP_ERR_INVALID_LENGTH, "Value exceeds bit vector capacity!"};
+    if (n < 64 && (it.values[j] >> n) > 0) throw prove_err(BPP_PROVE_MSG_VALUE);
     const bool present = it.min_present ? it.min_present[j] != 0 : false;
-    if (present && it.values[j] < it.min_values[j]) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "Minimum value is larger than value"};
+    if (present && it.values[j] < it.min_values[j]) throw prove_err(BPP_PROVE_MSG_MINIMUM);
   }
   for (uint32_t q = 0; q < m * t; q++)
-    if (!sc_is_canonical(it.blindings32 + 32 * (size_t)q)) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "blinding factor is not canonical"};
-  if (it.seed_nonce32 && !sc_is_canonical(it.seed_nonce32)) throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "seed nonce is not canonical"};
-  if (it.transcript_state && it.transcript_state[200] >= BPP_STROBE_R)
-    throw ProofErr{BPP_ERR_INVALID_ARGUMENT, "transcript state has pos >= rate"};
+    if (!sc_is_canonical(it.blindings32 + 32 * (size_t)q)) throw prove_err(BPP_PROVE_MSG_BLINDING);
+  if (it.seed_nonce32 && !sc_is_canonical(it.seed_nonce32)) throw prove_err(BPP_PROVE_MSG_SEED_NONCE);
+  if (it.transcript_state && it.transcript_state[200] >= BPP_STROBE_R) throw prove_err(BPP_PROVE_MSG_TRANSCRIPT_STATE);
 }
 
 // What a ticket of the prove pipeline owns of its caller's items.  take() checks every item where the caller keeps it and copies

@@ -21,6 +21,7 @@ struct ProvePack {
   uint32_t rounds = 0;            // its rounds: the call's global steps
   uint32_t rounds_min = 0;        // the smallest class's rounds: "ct" = 2's ex_back is clamped to it
   size_t plen = 0;                // the longest proof
+  size_t bytes_len = 0;           // bytes.size(), or what the ingest kernel writes on the device where `bytes` stays empty (prove_ingest.h)
   bool packed = false;            // `bytes` may hold secrets
 
   ProvePack() = default;
@@ -121,6 +122,13 @@ struct ProvePack {
       d.state_idx = sit->second;
     }
 
+    bytes_len = bytes.size();
+    advance_states(P, hg32, state_m);
+  }
+
+  // state_m: the aggregation factor each distinct transcript state is for (its "M" append)
+  void advance_states(const ParamShape &P, const uint8_t *hg32, const std::vector<uint32_t> &state_m) {
+    const uint32_t t = P.t;
     // RangeProofTranscript::new (src/transcripts.rs:59-89) starts every proof's transcript with the same seven appends -- the
     // domain separator, H, the G bases, N, T, M: parameters of the call, not of the proof.  They are applied HERE, once per distinct
     // caller transcript; kp_init continues with the proof's own commitments and promises (two Keccak-f fewer per proof on the call's

@@ -377,6 +377,130 @@ def verify_batch_mixed_device(params, inp, action=api.VerifyAction.VerifyOnly, c
     return _verify_mixed(params, inp, action, chunk, True)
 
 
+class DeviceOpenings(DevicePackedInput):
+    """The openings of a prove call whose arrays already lie in DEVICE memory + the bpp_prove_arrays that describes them, for
+    bpp_prove_openings_device (include/bpp.h): no value, blinding factor, nonce or rng byte is copied to the host.  Torch device
+    tensors or (address, shape) pairs:
+        values       any 8-byte dtype [n, m_stride]     row i holds m[i] values
+        blindings    uint8 [n, m_stride, t, 32]
+        m            [n], a HOST array: it sizes the layout
+        commitments  uint8 [n, m_stride, 32], or None: the engine makes them (bpp_prove_openings' rule)
+        min_values   8-byte dtype [n, m_stride], min_present uint8 [n, m_stride], seed_nonces uint8 [n, 32], seed_present uint8 [n], or None
+        rng_bytes    uint8 [n, rng_stride]              row i holds (rounds_i + 3) x 32 bytes
+    Row slack is never read.  One transcript for the call: label= or state=.  Ordering as for DevicePackedInput."""
+
+    def __init__(self, values, blindings, m, commitments=None, min_values=None, min_present=None, seed_nonces=None, seed_present=None,
+                 rng_bytes=None, label=b"", state=None):
+        self._keep, self.device_index, self._torch, self.synchronised = [], None, False, False
+        self.m = np.ascontiguousarray(_host_array(m), dtype=np.uint32)
+        if self.m.ndim != 1:
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "m: an array of shape (n,) expected")
+        n = self.m.shape[0]
+        addr_v, vshape, _ = self._array(values, "values", 8)
+        if len(vshape) != 2 or vshape[0] != n:
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "values: an array of shape (%d, m_stride) expected, got %s" % (n, vshape))
+        ms = vshape[1]
+        addr_b, bshape, _ = self._array(blindings, "blindings", 1)
+        if len(bshape) != 4 or bshape[:2] != (n, ms) or bshape[3] != 32:
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "blindings: an array of shape (%d, %d, t, 32) expected, got %s" % (n, ms, bshape))
+        addr_r, rshape, _ = self._array(rng_bytes, "rng_bytes", 1)
+        if len(rshape) != 2 or rshape[0] != n:
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "rng_bytes: an array of shape (%d, rng_stride) expected, got %s" % (n, rshape))
+
+        def opt(a, name, itemsize, want):
+            if a is None:
+                return None
+            addr, got, _ = self._array(a, name, itemsize)
+            if got != want:
+                raise api.ProofError(api.ProofErrorKind.InvalidLength, "%s: array of shape %s expected, got %s" % (name, want, got))
+            return addr
+
+        self.label = np.frombuffer(bytes(label), dtype=np.uint8).copy() if len(label) else np.zeros(1, dtype=np.uint8)
+        self.label_bytes = bytes(label)
+        self.state = None if state is None else np.frombuffer(bytes(state), dtype=np.uint8).copy()
+        self.n, self.m_stride, self.t = n, ms, bshape[2]
+        self.min_values, self.min_present, self.seed_nonces, self.seed_present = min_values, min_present, seed_nonces, seed_present
+        self.struct = _lib.ProveArrays(n, self.m.ctypes.data, ms, addr_v, addr_b, opt(commitments, "commitments", 1, (n, ms, 32)),
+                                       opt(min_values, "min_values", 8, (n, ms)), opt(min_present, "min_present", 1, (n, ms)),
+                                       opt(seed_nonces, "seed_nonces", 1, (n, 32)), opt(seed_present, "seed_present", 1, (n,)), addr_r,
+                                       rshape[1], None if self.state is None else self.state.ctypes.data, self.label.ctypes.data, len(label))
+
+
+class DeviceProved:
+    """What prove_openings_device leaves: .commitments uint8 [n, 32 m_stride] and .proofs uint8 [n, longest proof] (device tensors;
+    row i holds 32 m[i] and proof_lens[i] bytes, zero for a failed item), .status int32 [n, 2] (device: code, message id), and on the
+    host .proof_lens, .m, .codes, the call's .rc and .message (the first failing item's)."""
+
+    def __init__(self, inp, commitments, proofs, proof_lens, status, codes, rc, message):
+        self.inp, self.commitments, self.proofs, self.proof_lens, self.m = inp, commitments, proofs, proof_lens, inp.m
+        self.status, self.codes, self.rc, self.message = status, codes, rc, message
+
+    def as_mixed_input(self, label=None, state=None):
+        """a DeviceMixedInput over the same tensors -- nothing is copied -- with the promises and nonces of the openings; label= / state=:
+        the verifier's transcript (default: the prove call's)"""
+        inp = self.inp
+        if label is None and state is None:
+            label, state = inp.label_bytes, (None if inp.state is None else inp.state.tobytes())
+        return DeviceMixedInput(self.proofs, self.proof_lens, self.m, self.commitments.view(self.commitments.shape[0], -1, 32),
+                                min_values=inp.min_values, min_present=inp.min_present, seed_nonces=inp.seed_nonces,
+                                label=b"" if label is None else label, seed_present=inp.seed_present, state=state)
+
+    def messages(self, engine):
+        """the message text of every item (bpp_prove_status_result over a host copy of .status)"""
+        host = np.ascontiguousarray(self.status.cpu().numpy())
+        out = []
+        for i in range(host.shape[0]):
+            r = _lib.ShardResult()
+            api._check(engine.lib.bpp_prove_status_result(host[i:i + 1].ctypes.data_as(POINTER(_lib.DeviceProveStatus)), byref(r)), None)
+            out.append((int(r.code), r.msg.decode()))
+        return out
+
+
+def prove_openings_device(params, inp, commitments_out=None, proofs_out=None, status_out=None, commit_stride=None, proof_stride=None):
+    """bpp_prove_openings over a DeviceOpenings (bpp_prove_openings_device): what bpp_prove_openings writes on host copies of the same
+    arrays, with the proofs and commitments left in device memory.  A failed item never stops the others and does not raise: look at
+    .codes / .rc / .message.  Raises when the whole call is refused or the engine faults.
+    commitments_out / proofs_out / status_out: tensors (or (address, shape) pairs, with the strides) to write into; default: fresh ones."""
+    import torch
+    eng, t, n_bits = params.engine, int(params.extension_degree()), params.bit_length()
+    n, ms = inp.n, inp.m_stride
+    dev = torch.device("cuda", inp.device_index if inp.device_index is not None else int(eng.device))
+    m_top = int(min(max(int(inp.m.max()), 1), ms)) if n else 1
+    plen = 1 + 32 * (t + 5 + 2 * max((n_bits * m_top - 1).bit_length(), 0))
+    if commitments_out is None:
+        commitments_out = torch.zeros((n, 32 * ms), dtype=torch.uint8, device=dev)
+    if proofs_out is None:
+        proofs_out = torch.zeros((n, plen), dtype=torch.uint8, device=dev)
+    if status_out is None:
+        status_out = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+
+    def out(a, stride):
+        if hasattr(a, "data_ptr"):
+            return a.data_ptr(), int(stride if stride is not None else a.stride(0) * a.element_size())
+        return int(a[0]), int(stride if stride is not None else a[1][1])
+
+    addr_c, cstride = out(commitments_out, commit_stride)
+    addr_p, pstride = out(proofs_out, proof_stride)
+    addr_s = status_out.data_ptr() if hasattr(status_out, "data_ptr") else int(status_out[0])
+    lens = np.zeros(n, dtype=np.uintp)
+    unset = -(1 << 30)
+    codes = np.full(n, unset, dtype=np.intc)
+    err = ctypes.create_string_buffer(256)
+    inp.order_before(eng)
+    rc = eng.lib.bpp_prove_openings_device(eng.ctx, params.handle, byref(inp.struct), addr_c, cstride, addr_p, pstride,
+                                           lens.ctypes.data_as(POINTER(c_size_t)), addr_s, codes.ctypes.data_as(POINTER(ctypes.c_int)), err, 256)
+    if rc < 0 or (rc != 0 and (codes == unset).all()):
+        api._check(rc, eng.ctx, err)
+    return DeviceProved(inp, commitments_out, proofs_out, lens, status_out, codes, rc, err.value.decode())
+
+
+def prove_device_stats(engine):
+    """bpp_prove_device_stats as a dict: calls, items, device_findings, host_findings"""
+    s = _lib.ProveDeviceStats()
+    api._check(engine.lib.bpp_prove_device_stats(engine.ctx, byref(s)), engine.ctx)
+    return {k: int(getattr(s, k)) for k, _ in _lib.ProveDeviceStats._fields_}
+
+
 def device_pointer_kind(engine, address):
     """bpp_device_pointer_check: 0 this engine's device memory, 1 another device's, 2 host or unknown, 3 managed (launches nothing)"""
     kind = ctypes.c_int(-1)

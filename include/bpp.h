@@ -867,6 +867,82 @@ int bpp_prove_openings(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item
  * rejection.  Looks at what ctx's LAST bpp_prove_openings or bpp_prove_batch_mixed left behind. */
 int bpp_prove_openings_item_message(bpp_ctx *ctx, uint64_t params, const bpp_prove_item *item, const uint8_t *first_commitment32,
                                     size_t commit_stride, size_t proof_stride, int status, char *errbuf, size_t errbuf_len);
+/* ---- Proving from arrays in DEVICE memory: bpp_prove_openings whose openings lie on the device and whose proofs and commitments stay
+ * there, in the row geometry bpp_mixed_batch describes (bpp_batch_upload_mixed_device and bpp_batch_refill_enqueue_mixed take the
+ * outputs as they are).  No witness byte -- value, blinding factor, nonce, rng byte -- exists in host memory in this form.
+ * THE CONTRACT: the call writes what bpp_prove_openings writes on the equivalent bpp_prove_item array (item i points into row i of
+ * host copies of the same arrays; commitments32 is its row, or NULL when the array is NULL): the return code, errbuf, item_status[i],
+ * proof_lens[i], the proof and commitment bytes, the zeroed slots of failed items.  status_dev[i] carries item i's code and a
+ * BPP_PROVE_MSG_* id, which bpp_prove_status_result turns into the host form's text.  A failed item never stops the others.  Row slack
+ * is never read and never written: not in the inputs, not in the output rows beyond proof_lens[i] / 32 * m[i] bytes.
+ * (One corner: a failed item's ranges are zeroed in EVERY call, also in one in which no item passes the host's part of the checks,
+ * where bpp_prove_openings returns before it zeroes anything.)
+ * TWO DIFFERENCES from the equivalent items, both because the transcript and the strides belong to the call and the host sees no
+ * witness byte: a transcript_state with pos (byte 200) >= 166 refuses the WHOLE call before any launch ("transcript state has pos >=
+ * rate"); and an item that has both a nonce with m > 1 and an rng_stride too short for its m reports the rng finding ("not enough
+ * external randomness..."), where the host form reports "Mask recovery is not supported...".
+ * REFUSED before anything is allocated or launched, BPP_ERR_INVALID_ARGUMENT with the field named in bpp_ctx_last_error: a non-NULL
+ * array of in_dev, proofs_out_dev, commitments_out_dev or status_dev that is not BPP_PTR_THIS_DEVICE memory; m in device memory;
+ * commitments_out_dev or proofs_out_dev NULL; m_stride == 0; "prove_check" = 1 on the context (the self-check remakes from host
+ * items and is not part of this form: the call says so instead of skipping it).
+ * ORDERING: whatever wrote the input arrays must be complete on, or ordered before, the context's stream.  The call is blocking: when
+ * it returns the outputs are complete for every stream.
+ * SECRETS: the witness is packed by a kernel into the prove arena, which is zeroed behind the call's last kernel as for every prove
+ * call; bpp_prove_secret_bytes reads 0 afterwards on every exit path. */
+typedef struct {
+  size_t n_items;
+  const uint32_t *m;              /* HOST, n_items: aggregation factor per item (it sizes the layout, like bpp_mixed_batch.m) */
+  uint32_t m_stride;              /* the per-opening arrays have rows of m_stride entries */
+  const uint64_t *values;         /* DEVICE  n x m_stride (little-endian words, at any byte address) */
+  const uint8_t *blindings32;     /* DEVICE  n x m_stride x t x 32 */
+  const uint8_t *commitments32;   /* DEVICE  n x m_stride x 32, or NULL: every item's commitments are made (bpp_prove_openings' rule) */
+  const uint64_t *min_values;     /* DEVICE  n x m_stride, or NULL */
+  const uint8_t *min_present;     /* DEVICE  n x m_stride, or NULL = all None (min_present without min_values: every item fails) */
+  const uint8_t *seed_nonces32;   /* DEVICE  n x 32, or NULL */
+  const uint8_t *seed_present;    /* DEVICE  n, or NULL = every item has one when seed_nonces32 is given */
+  const uint8_t *rng_bytes;       /* DEVICE  n x rng_stride: row i holds (rounds_i + 3) x 32 bytes of external randomness */
+  size_t rng_stride;
+  const uint8_t *transcript_state, *transcript_label; /* HOST: ONE transcript for the call, as in bpp_packed_batch */
+  size_t label_len;
+} bpp_prove_arrays;
+typedef struct {
+  int32_t code;  /* what item_status[i] holds */
+  uint32_t msg;  /* BPP_PROVE_MSG_*; bpp_prove_status_result gives the text */
+} bpp_device_prove_status; /* 8 bytes */
+#define BPP_PROVE_MSG_OK 0u
+#define BPP_PROVE_MSG_POWER_OF_TWO 1u
+#define BPP_PROVE_MSG_GENERATORS 2u
+#define BPP_PROVE_MSG_BITS 3u
+#define BPP_PROVE_MSG_PROOF_STRIDE 4u
+#define BPP_PROVE_MSG_COMMIT_STRIDE 5u
+#define BPP_PROVE_MSG_NULL_FIELD 6u
+#define BPP_PROVE_MSG_SEED_AGGREGATED 7u
+#define BPP_PROVE_MSG_RNG_LEN 8u
+#define BPP_PROVE_MSG_VALUE 9u
+#define BPP_PROVE_MSG_MINIMUM 10u
+#define BPP_PROVE_MSG_BLINDING 11u
+#define BPP_PROVE_MSG_SEED_NONCE 12u
+#define BPP_PROVE_MSG_TRANSCRIPT_STATE 13u
+#define BPP_PROVE_MSG_OPENING 14u
+#define BPP_PROVE_MSG_IDENTITY 15u
+#define BPP_PROVE_MSG_ENGINE 16u
+int bpp_prove_openings_device(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays *in_dev,
+                              uint8_t *commitments_out_dev, size_t commit_stride, /* DEVICE, row i: 32 x m[i] bytes used */
+                              uint8_t *proofs_out_dev, size_t proof_stride,       /* DEVICE, row i: proof_lens[i] bytes used */
+                              size_t *proof_lens,                                 /* HOST out, n_items */
+                              bpp_device_prove_status *status_dev,                /* DEVICE out, n_items; may be NULL */
+                              int *item_status,                                   /* HOST out, n_items; may be NULL */
+                              char *errbuf, size_t errbuf_len);
+/* code and message text of a status record copied to the host (tier BPP_TIER_CONSTRUCTION for a finding, rank = -1, index 0) */
+int bpp_prove_status_result(const bpp_device_prove_status *host_copy, bpp_shard_result *out);
+struct bpp_prove_device_stats {
+  uint64_t calls;           /* calls that passed the refusals */
+  uint64_t items;           /* their items */
+  uint64_t device_findings; /* items the ingest kernel failed (a finding that needs a witness byte) */
+  uint64_t host_findings;   /* items the host failed from m[] and the strides: they never reached the device */
+};
+int bpp_prove_device_stats(bpp_ctx *ctx, struct bpp_prove_device_stats *out);
+
 /* bpp_prove_pool: many host threads, each with a few proofs per call (one output of a wallet service, say).  A call of one proof
  * is a chain of latency-bound launches; the pool hands the calls that are waiting to ONE bpp_prove_batch_mixed on one of `lanes`
  * contexts (the first is ctx; the others are made here with ctx's options as they are now).  No thread of its own: whichever

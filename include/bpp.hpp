@@ -18,6 +18,7 @@
 #pragma once
 #include <algorithm>
 #include <array>
+#include <climits>
 #include <cstdint>
 #include <cstring>
 #include <memory>
@@ -422,6 +423,28 @@ struct DeviceMixedBatch {
   bpp_mixed_batch arrays;
 };
 
+// a bpp_prove_arrays whose array fields are addresses in DEVICE memory (bpp.h: bpp_prove_openings_device); m and the transcript
+// stay host memory
+struct DeviceProveArrays {
+  bpp_prove_arrays arrays;
+};
+
+// where RangeProof::prove_openings over a DeviceProveArrays writes, all of it DEVICE memory (status may be null), and what comes
+// back on the host
+struct DeviceProveOutputs {
+  uint8_t *commitments;
+  size_t commit_stride;
+  uint8_t *proofs;
+  size_t proof_stride;
+  bpp_device_prove_status *status;
+};
+struct DeviceProveResult {
+  int code;                       // 0, or the first failing item's code
+  std::string message;            // its message
+  std::vector<size_t> proof_lens;
+  std::vector<int> item_status;
+};
+
 struct ExtendedMask {
   std::vector<Bytes32> blindings;
   bool operator==(const ExtendedMask &o) const { return blindings == o.blindings; }
@@ -596,6 +619,26 @@ class RangeProof {
       res.first.push_back(RangeStatement::init(generators, std::move(cs), minimum_value_promises[i], seed_nonces[i]));
       res.second.push_back(from_bytes(std::vector<uint8_t>(out.begin() + i * stride, out.begin() + i * stride + lens[i])));
     }
+    return res;
+  }
+
+  // The same from openings that lie in DEVICE memory (bpp_prove_openings_device): what bpp_prove_openings writes on host copies of
+  // the same arrays, with the proofs and commitments left in device memory, in the geometry a DeviceMixedBatch describes.  A failed
+  // item never stops the others and does not throw: look at the result.  Throws when the whole call is refused or the engine faults.
+  static DeviceProveResult prove_openings(const DeviceProveArrays &openings, const DeviceProveOutputs &out,
+                                          const std::shared_ptr<RangeParameters> &generators) {
+    auto &params = *generators;
+    const size_t n = openings.arrays.n_items;
+    const int unset = INT_MIN;
+    DeviceProveResult res{0, std::string(), std::vector<size_t>(n, 0), std::vector<int>(n, unset)};
+    char err[256] = {0};
+    res.code = bpp_prove_openings_device(params.engine().ctx(), params.handle(), &openings.arrays, out.commitments, out.commit_stride,
+                                         out.proofs, out.proof_stride, res.proof_lens.data(), out.status, res.item_status.data(), err,
+                                         sizeof(err));
+    bool refused = res.code != 0;  // (a refusal writes no item's status)
+    for (int s : res.item_status) refused = refused && s == unset;
+    if (res.code < 0 || refused) check(res.code, err);
+    res.message = err;
     return res;
   }
 

@@ -101,6 +101,45 @@ pub struct bpp_mixed_batch {
     pub label_len: usize,
 }
 
+/// bpp_prove_arrays: the openings of a prove call as arrays of rows in DEVICE memory (`bpp_prove_openings_device`); `m` and the
+/// transcript are host memory
+#[repr(C)]
+pub struct bpp_prove_arrays {
+    pub n_items: usize,
+    pub m: *const u32,
+    pub m_stride: u32,
+    pub values: *const u64,
+    pub blindings32: *const u8,
+    pub commitments32: *const u8,
+    pub min_values: *const u64,
+    pub min_present: *const u8,
+    pub seed_nonces32: *const u8,
+    pub seed_present: *const u8,
+    pub rng_bytes: *const u8,
+    pub rng_stride: usize,
+    pub transcript_state: *const u8,
+    pub transcript_label: *const u8,
+    pub label_len: usize,
+}
+
+/// bpp_device_prove_status: one item's record of `bpp_prove_openings_device`, 8 bytes, as it lies in device memory
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_device_prove_status {
+    pub code: i32,
+    pub msg: u32,
+}
+
+/// `struct bpp_prove_device_stats`: what the prove calls from device arrays of a context came to
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_prove_device_stats {
+    pub calls: u64,
+    pub items: u64,
+    pub device_findings: u64,
+    pub host_findings: u64,
+}
+
 #[repr(C)]
 pub struct bpp_comm {
     _p: [u8; 0],
@@ -447,6 +486,12 @@ extern "C" {
     pub fn bpp_prove_openings_item_message(ctx: *mut bpp_ctx, params: u64, item: *const bpp_prove_item, first_commitment32: *const u8,
                                            commit_stride: usize, proof_stride: usize, status: c_int, errbuf: *mut c_char,
                                            errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_openings_device(ctx: *mut bpp_ctx, params: u64, in_dev: *const bpp_prove_arrays, commitments_out_dev: *mut u8,
+                                     commit_stride: usize, proofs_out_dev: *mut u8, proof_stride: usize, proof_lens: *mut usize,
+                                     status_dev: *mut bpp_device_prove_status, item_status: *mut c_int, errbuf: *mut c_char,
+                                     errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_status_result(host_copy: *const bpp_device_prove_status, out: *mut bpp_shard_result) -> c_int;
+    pub fn bpp_prove_device_stats(ctx: *mut bpp_ctx, out: *mut bpp_prove_device_stats) -> c_int;
     pub fn bpp_prove_pool_openings(p: *mut bpp_prove_pool, items: *const bpp_prove_item, n_items: usize, commitments_out: *mut u8,
                                    commit_stride: usize, proofs_out: *mut u8, proof_stride: usize, proof_lens: *mut usize,
                                    errbuf: *mut c_char, errbuf_len: usize) -> c_int;

@@ -1,0 +1,33 @@
+"""CPU suite: the per-item routines and the host plan of csrc/prove_ingest.h -- what bpp_prove_openings_device runs for a prove call
+whose openings lie in device memory -- on the host, lane by lane, under AddressSanitizer + UBSan, held to ProvePack::pack and
+prove_item_check_host of the item form on the sorted equivalent bpp_prove_item array.
+
+The harness (csrc/hosttest_prove_ingest.cpp, a stand-alone program; nothing is preloaded) asserts for every case that d_bytes, every
+ProveDesc field, minvals, minpres and the states equal the packer's, and that every finding's {code, message} is what
+prove_item_check_host throws for that item; an item with a finding is held to the substitute witness.  The corpus: one item; 5, 17
+and 67 items of the m pattern [1, 4, 2, 8, 1] (a sub-batch cut at 64), t = 1 and 3, commitments brought and made, a label and a
+transcript state; every finding kind at the first, a middle and the last item and opening; items with two findings; a value of
+2^n - 1 and of 2^n at n = 32; min == value and min == value + 1; a blinding factor of l - 1, of l and of all ones; a nonce on an
+m = 2 item; a nonce row with seed_present = 0; an rng_stride one byte short for the largest m only (with the one documented
+precedence difference); aggregation factors no statement can have; a call in which every item fails.  Row slack holds 0xFF in one
+pass and is poisoned in the other, and every array ends with the last byte its last row uses."""
+import importlib
+import os
+import subprocess
+
+CASES = ("one_item", "pattern_5", "pattern_17", "pattern_67", "findings_first_middle_last", "two_findings", "value_edges", "minimum_edges",
+         "blinding_edges", "nonce_on_an_m2_item", "nonce_with_seed_present_0", "rng_stride_short_for_the_largest_m", "host_findings",
+         "every_item_fails")
+
+
+def test_prove_ingest_equals_the_item_form_under_asan_ubsan():
+    pkg = importlib.import_module("bulletproofs-plus_amd")
+    exe = pkg._build.build_prove_ingest_harness()
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = r.stdout.split("\n")
+    for case in CASES:
+        assert "ok " + case in lines, (case, r.stdout[-2000:])
+    assert "all ok" in lines and not any(line.startswith("FAIL") for line in lines)
+    assert r.stderr.strip() == "", r.stderr[-4000:]

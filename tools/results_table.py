@@ -34,6 +34,33 @@ def M(x):
     return "%.2f M" % (x / 1e6)
 
 
+def prove_device_section():
+    """profiles/prove_device.json (a list of runs of tools/bench_prove_device.py): per shape, every arm over the runs"""
+    f = os.path.join(P, "prove_device.json")
+    out = ["## Proving from openings in device memory against proving from host arrays (`bpp_prove_openings_device`, "
+           "`tools/bench_prove_device.py`, `profiles/prove_device.json`)", ""]
+    if not os.path.exists(f):
+        return out + ["unmeasured", ""]
+    runs = json.load(open(f))
+    one = runs[0]
+    out += ["One thread, one context, %d items per call at %d bits; `bpp_prove_openings` over host rows against `bpp_prove_openings_device` over "
+            "the same rows resident in device memory (`csrc/prove_ingest.h`), and each followed by a mixed upload of what it wrote "
+            "(`bpp_batch_upload_mixed` / `bpp_batch_upload_mixed_device` + `bpp_batch_destroy`); the arms alternate in one process after a "
+            "warm-up, %d rounds of %d calls per run, median (lowest-highest round) over the runs.  Box: an MI355X, recorded by the tool as "
+            "\"%s\".  A record: no rate is promised -- the prover is bound by its instruction rate, the copies this form removes are a "
+            "small part of a call." % (one["items"], one["n_bits"], one["reps"], one["inner"], one["box"]), "",
+            "| shape | arm | ms per call | proofs/s |", "|---|---|---|---|"]
+    for shape in [r["shape"] for r in one["shapes"]]:
+        rows = [r for run in runs for r in run["shapes"] if r["shape"] == shape]
+        for arm in rows[0]["arms"]:
+            ms = [r["arms"][arm]["ms_per_call"] for r in rows]
+            lo, hi = min(r["arms"][arm]["ms_low"] for r in rows), max(r["arms"][arm]["ms_high"] for r in rows)
+            med = statistics.median(ms)
+            out.append("| %s (m = %d, t = %d%s) | %s | %.3f (%.3f-%.3f) | %.1f k |" % (shape, rows[0]["m"], rows[0]["t"], ", nonces" if rows[0]["nonces"] else "",
+                                                                                    arm, med, lo, hi, one["items"] / med))
+    return out + [""]
+
+
 def refill_mixed_section():
     """profiles/refill_mixed.json (a list of runs of tools/bench_refill_mixed.py): per batch size, both arms over every repetition of
     every run"""
@@ -407,6 +434,7 @@ def main():
         out.append("")
     out += refill_mixed_section()
     out += item_transcripts_section()
+    out += prove_device_section()
     ks, fks = load(tag, "kernel_stats_cfg2_default.csv")
     sq, fsq = load(tag, "pmc_sq_summary.csv")
     if ks:
