@@ -76,36 +76,6 @@ def build_hosttest(force=False):
     return HOSTTEST_LIB
 
 
-SANITIZER_BIN = os.path.join(HERE, "hosttest_upload_asan")
-
-
-def build_sanitizer_harness(force=False):
-    """hosttest_upload.cpp (host packer of bpp_batch_upload + the arithmetic probes) under ASan + UBSan: an executable,
-    run by tests/test_host_sanitizers.py.  GPU sanitizers are not available on the pool; this is the CPU build."""
-    src = os.path.join(CSRC, "hosttest_upload.cpp")
-    deps = [src, os.path.join(CSRC, "hosttest.cpp")] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and not _stale(SANITIZER_BIN, deps):
-        return SANITIZER_BIN
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-fno-omit-frame-pointer", "-DBPP_FE_BOUNDS_CHECK", "-o", SANITIZER_BIN, src], check=True, cwd=CSRC)
-    return SANITIZER_BIN
-
-
-PROVE_JOB_SANITIZER_BIN = os.path.join(HERE, "hosttest_prove_job_asan")
-
-
-def build_prove_job_harness(force=False):
-    """hosttest_prove_job.cpp (the job copy bpp_prove_submit takes of its caller's items: per-item check, deep copy, wipe) under
-    ASan + UBSan: an executable, run by tests/test_prove_pipeline_host.py."""
-    src = os.path.join(CSRC, "hosttest_prove_job.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and not _stale(PROVE_JOB_SANITIZER_BIN, deps):
-        return PROVE_JOB_SANITIZER_BIN
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-fno-omit-frame-pointer", "-o", PROVE_JOB_SANITIZER_BIN, src], check=True, cwd=CSRC)
-    return PROVE_JOB_SANITIZER_BIN
-
-
 LANES_BINS = {"tsan": os.path.join(HERE, "hosttest_lanes_tsan"), "asan": os.path.join(HERE, "hosttest_lanes_asan")}
 LANES_FLAGS = {"tsan": ["-fsanitize=thread"], "asan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]}
 
@@ -135,160 +105,68 @@ def build_runtime_harness(kind, force=False):
     return exe
 
 
-CT_SANITIZER_BIN = os.path.join(HERE, "hosttest_ct_asan")
+# The single-source harnesses under ASan + UBSan: hosttest_<name>.cpp -> the executable hosttest_<name>_asan, run by the named test.
+# GPU sanitizers are not available on the pool; these are CPU builds.  (extra dependencies, extra flags) where a harness has any.
+_ASAN_HARNESSES = {
+    "upload": ("host packer of bpp_batch_upload + the arithmetic probes; tests/test_host_sanitizers.py", ["hosttest.cpp"], ["-DBPP_FE_BOUNDS_CHECK"]),
+    "prove_job": ("the job copy bpp_prove_submit takes of its caller's items: per-item check, deep copy, wipe; "
+                  "tests/test_prove_pipeline_host.py", [], []),
+    "ct": ("ct.h: the one-lane model of the constant-time multiscalar multiplication; ct_plan.h: its chunk planner; "
+           "tests/test_msm_ct_host.py", ["hosttest.cpp"], []),
+    "ingest": ("ingest.h: the one-item routines of the device uploads in their packed form, held to the host packer of upload_host.h over "
+               "a corpus; tests/test_ingest_host.py", [], []),
+    "verdict": ("verdict.h: the verdict resolution that bpp_verify_enqueue runs on the device, held to the throwing routines of "
+                "upload_host.h; tests/test_verdict_host.py", [], []),
+    "refill": ("refill.h: the one-lane model of the kernels of bpp_batch_refill_enqueue, held to the device upload's routines of ingest.h; "
+               "verdict.h with a refill state; tests/test_refill_host.py", [], []),
+    "refill_count": ("refill.h with a live count, held to the device upload's routines on the first c items; verdict.h: the live routines on "
+                     "cut groups; tests/test_refill_count_host.py", [], []),
+    "refill_live": ("refill.h under a live mask, held to the device upload's routines on the live items alone; verdict.h: the live routines "
+                    "on compacted groups; tests/test_refill_live_host.py", [], []),
+    "ingest_mixed": ("ingest.h in its mixed form with the host prelude and the plan of ingest_mixed.h, held to the item form of upload_host.h "
+                     "over a corpus, and to the packed form on a uniform batch; tests/test_ingest_mixed_host.py", [], []),
+    "refill_mixed": ("refill.h in its mixed form, plain, with a count and under a mask, held to the device form of the mixed upload on the "
+                     "rows in question, and to the packed form on a uniform batch; tests/test_refill_mixed_host.py", [], []),
+    "item_states": ("item_states.h: the one-lane models of k_item_states -- every row, a live count, a live mask -- held to the states table "
+                    "and tr_err_index upload_host.h makes of the equivalent item array, and the row rule of k_states_out; "
+                    "tests/test_item_states_host.py", [], []),
+    "prove_ingest": ("prove_ingest.h: the per-item routines of k_prove_ingest and the host plan of bpp_prove_openings_device, held to "
+                     "ProvePack::pack and prove_item_check_host on the sorted equivalent items; tests/test_prove_ingest_host.py", [], []),
+}
 
 
-def build_ct_harness(force=False):
-    """hosttest_ct.cpp (ct.h: the one-lane model of the constant-time multiscalar multiplication; ct_plan.h: its chunk planner)
-    under ASan + UBSan: an executable, run by tests/test_msm_ct_host.py."""
-    src = os.path.join(CSRC, "hosttest_ct.cpp")
-    deps = [src, os.path.join(CSRC, "hosttest.cpp")] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and not _stale(CT_SANITIZER_BIN, deps):
-        return CT_SANITIZER_BIN
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-fno-omit-frame-pointer", "-o", CT_SANITIZER_BIN, src], check=True, cwd=CSRC)
-    return CT_SANITIZER_BIN
+def _asan_bin(name):
+    return os.path.join(HERE, "hosttest_%s_asan" % name)
 
 
-INGEST_SANITIZER_BIN = os.path.join(HERE, "hosttest_ingest_asan")
+def _asan_builder(name):
+    what, extra_deps, extra_flags = _ASAN_HARNESSES[name]
+
+    def build_harness(force=False):
+        src, exe = os.path.join(CSRC, "hosttest_%s.cpp" % name), _asan_bin(name)
+        deps = [src] + [os.path.join(CSRC, f) for f in extra_deps + HEADERS]
+        if force or _stale(exe, deps):
+            subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                            "-fno-omit-frame-pointer"] + extra_flags + ["-o", exe, src], check=True, cwd=CSRC)
+        return exe
+
+    build_harness.__doc__ = "hosttest_%s.cpp (%s) under ASan + UBSan: an executable." % (name, what)
+    return build_harness
 
 
-def build_ingest_harness(force=False):
-    """hosttest_ingest.cpp (ingest.h: the one-item routines of the device form of the packed upload, held to the host packer of
-    upload_host.h over a corpus) under ASan + UBSan: an executable, run by tests/test_ingest_host.py."""
-    src = os.path.join(CSRC, "hosttest_ingest.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and not _stale(INGEST_SANITIZER_BIN, deps):
-        return INGEST_SANITIZER_BIN
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-fno-omit-frame-pointer", "-o", INGEST_SANITIZER_BIN, src], check=True, cwd=CSRC)
-    return INGEST_SANITIZER_BIN
-
-
-VERDICT_SANITIZER_BIN = os.path.join(HERE, "hosttest_verdict_asan")
-
-
-def build_verdict_harness(force=False):
-    """hosttest_verdict.cpp (verdict.h: the verdict resolution that bpp_verify_enqueue runs on the device, held to the throwing
-    routines of upload_host.h) under ASan + UBSan: an executable, run by tests/test_verdict_host.py."""
-    src = os.path.join(CSRC, "hosttest_verdict.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and not _stale(VERDICT_SANITIZER_BIN, deps):
-        return VERDICT_SANITIZER_BIN
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-fno-omit-frame-pointer", "-o", VERDICT_SANITIZER_BIN, src], check=True, cwd=CSRC)
-    return VERDICT_SANITIZER_BIN
-
-
-REFILL_SANITIZER_BIN = os.path.join(HERE, "hosttest_refill_asan")
-
-
-def build_refill_harness(force=False):
-    """hosttest_refill.cpp (refill.h: the one-lane model of the kernels of bpp_batch_refill_enqueue, held to the device upload's
-    routines of ingest.h; verdict.h with a refill state) under ASan + UBSan: an executable, run by tests/test_refill_host.py."""
-    src = os.path.join(CSRC, "hosttest_refill.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and not _stale(REFILL_SANITIZER_BIN, deps):
-        return REFILL_SANITIZER_BIN
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-fno-omit-frame-pointer", "-o", REFILL_SANITIZER_BIN, src], check=True, cwd=CSRC)
-    return REFILL_SANITIZER_BIN
-
-
-REFILL_COUNT_SANITIZER_BIN = os.path.join(HERE, "hosttest_refill_count_asan")
-
-
-def build_refill_count_harness(force=False):
-    """hosttest_refill_count.cpp (refill.h with a live count: the one-lane model of the kernels of bpp_batch_refill_enqueue_count, held
-    to the device upload's routines on the first c items; verdict.h: the live routines on cut groups) under ASan + UBSan: an
-    executable, run by tests/test_refill_count_host.py."""
-    src = os.path.join(CSRC, "hosttest_refill_count.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and not _stale(REFILL_COUNT_SANITIZER_BIN, deps):
-        return REFILL_COUNT_SANITIZER_BIN
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-fno-omit-frame-pointer", "-o", REFILL_COUNT_SANITIZER_BIN, src], check=True, cwd=CSRC)
-    return REFILL_COUNT_SANITIZER_BIN
-
-
-REFILL_LIVE_SANITIZER_BIN = os.path.join(HERE, "hosttest_refill_live_asan")
-
-
-def build_refill_live_harness(force=False):
-    """hosttest_refill_live.cpp (refill.h under a live mask: the one-lane model of the kernels of bpp_batch_refill_enqueue_live, held
-    to the device upload's routines on the live items alone; verdict.h: the live routines on compacted groups) under ASan + UBSan: an
-    executable, run by tests/test_refill_live_host.py."""
-    src = os.path.join(CSRC, "hosttest_refill_live.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and not _stale(REFILL_LIVE_SANITIZER_BIN, deps):
-        return REFILL_LIVE_SANITIZER_BIN
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-fno-omit-frame-pointer", "-o", REFILL_LIVE_SANITIZER_BIN, src], check=True, cwd=CSRC)
-    return REFILL_LIVE_SANITIZER_BIN
-
-
-INGEST_MIXED_SANITIZER_BIN = os.path.join(HERE, "hosttest_ingest_mixed_asan")
-
-
-def build_ingest_mixed_harness(force=False):
-    """hosttest_ingest_mixed.cpp (ingest_mixed.h: the one-item routines, the host prelude and the plan of the device form of the mixed
-    upload, held to the item form of upload_host.h over a corpus) under ASan + UBSan: an executable, run by
-    tests/test_ingest_mixed_host.py."""
-    src = os.path.join(CSRC, "hosttest_ingest_mixed.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and not _stale(INGEST_MIXED_SANITIZER_BIN, deps):
-        return INGEST_MIXED_SANITIZER_BIN
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-fno-omit-frame-pointer", "-o", INGEST_MIXED_SANITIZER_BIN, src], check=True, cwd=CSRC)
-    return INGEST_MIXED_SANITIZER_BIN
-
-
-REFILL_MIXED_SANITIZER_BIN = os.path.join(HERE, "hosttest_refill_mixed_asan")
-
-
-def build_refill_mixed_harness(force=False):
-    """hosttest_refill_mixed.cpp (refill_mixed.h: the one-lane model of the kernels of bpp_batch_refill_enqueue_mixed, plain, with a
-    count and under a mask, held to the device form of the mixed upload on the rows in question) under ASan + UBSan: an executable, run
-    by tests/test_refill_mixed_host.py."""
-    src = os.path.join(CSRC, "hosttest_refill_mixed.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and not _stale(REFILL_MIXED_SANITIZER_BIN, deps):
-        return REFILL_MIXED_SANITIZER_BIN
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-fno-omit-frame-pointer", "-o", REFILL_MIXED_SANITIZER_BIN, src], check=True, cwd=CSRC)
-    return REFILL_MIXED_SANITIZER_BIN
-
-
-ITEM_STATES_SANITIZER_BIN = os.path.join(HERE, "hosttest_item_states_asan")
-
-
-def build_item_states_harness(force=False):
-    """hosttest_item_states.cpp (item_states.h: the one-lane models of k_item_states -- every row, a live count, a live mask -- held to
-    the states table and tr_err_index upload_host.h makes of the equivalent item array, and the row rule of k_states_out) under
-    ASan + UBSan: an executable, run by tests/test_item_states_host.py."""
-    src = os.path.join(CSRC, "hosttest_item_states.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and not _stale(ITEM_STATES_SANITIZER_BIN, deps):
-        return ITEM_STATES_SANITIZER_BIN
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-fno-omit-frame-pointer", "-o", ITEM_STATES_SANITIZER_BIN, src], check=True, cwd=CSRC)
-    return ITEM_STATES_SANITIZER_BIN
-
-
-PROVE_INGEST_SANITIZER_BIN = os.path.join(HERE, "hosttest_prove_ingest_asan")
-
-
-def build_prove_ingest_harness(force=False):
-    """hosttest_prove_ingest.cpp (prove_ingest.h: the per-item routines of k_prove_ingest and the host plan of
-    bpp_prove_openings_device, held to ProvePack::pack and prove_item_check_host on the sorted equivalent items) under ASan + UBSan:
-    an executable, run by tests/test_prove_ingest_host.py."""
-    src = os.path.join(CSRC, "hosttest_prove_ingest.cpp")
-    deps = [src] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and not _stale(PROVE_INGEST_SANITIZER_BIN, deps):
-        return PROVE_INGEST_SANITIZER_BIN
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                    "-fno-omit-frame-pointer", "-o", PROVE_INGEST_SANITIZER_BIN, src], check=True, cwd=CSRC)
-    return PROVE_INGEST_SANITIZER_BIN
+# the names the tests import
+SANITIZER_BIN, build_sanitizer_harness = _asan_bin("upload"), _asan_builder("upload")
+PROVE_JOB_SANITIZER_BIN, build_prove_job_harness = _asan_bin("prove_job"), _asan_builder("prove_job")
+CT_SANITIZER_BIN, build_ct_harness = _asan_bin("ct"), _asan_builder("ct")
+INGEST_SANITIZER_BIN, build_ingest_harness = _asan_bin("ingest"), _asan_builder("ingest")
+VERDICT_SANITIZER_BIN, build_verdict_harness = _asan_bin("verdict"), _asan_builder("verdict")
+REFILL_SANITIZER_BIN, build_refill_harness = _asan_bin("refill"), _asan_builder("refill")
+REFILL_COUNT_SANITIZER_BIN, build_refill_count_harness = _asan_bin("refill_count"), _asan_builder("refill_count")
+REFILL_LIVE_SANITIZER_BIN, build_refill_live_harness = _asan_bin("refill_live"), _asan_builder("refill_live")
+INGEST_MIXED_SANITIZER_BIN, build_ingest_mixed_harness = _asan_bin("ingest_mixed"), _asan_builder("ingest_mixed")
+REFILL_MIXED_SANITIZER_BIN, build_refill_mixed_harness = _asan_bin("refill_mixed"), _asan_builder("refill_mixed")
+ITEM_STATES_SANITIZER_BIN, build_item_states_harness = _asan_bin("item_states"), _asan_builder("item_states")
+PROVE_INGEST_SANITIZER_BIN, build_prove_ingest_harness = _asan_bin("prove_ingest"), _asan_builder("prove_ingest")
 
 
 if __name__ == "__main__":

@@ -44,7 +44,6 @@
 #include "ingest_mixed.h"
 #include "verdict.h"
 #include "refill.h"
-#include "refill_mixed.h"
 #include "item_states.h"
 #include "prove_ingest.h"
 
@@ -440,8 +439,8 @@ struct Batch {
   LiveView live_view() const {
     return mask_form ? LiveView{nullptr, (const uint8_t *)refill_mask.p} : LiveView{live_word(), (const uint8_t *)nullptr};
   }
-  // bpp_batch_upload_mixed_device on its device path: the per-item table k_ingest_mixed packed the batch by (ingest_mixed.h), kept for
-  // bpp_batch_refill_enqueue_mixed (refill_mixed.h), whose kernel reads it.  The shape such a refill must keep is this vector, not four
+  // bpp_batch_upload_mixed_device on its device path: the per-item table k_ingest_mixed packed the batch by (ingest.h), kept for
+  // bpp_batch_refill_enqueue_mixed (refill.h), whose kernel reads it.  The shape such a refill must keep is this vector, not four
   // numbers: mixed_shape is the host's copy of it (rows empty: not refillable by that call; `refillable` stays the packed form's).
   // refill_shape holds n_items, t0 and the three array flags of a mixed batch as well, where verify_enqueue_locked finds them.
   DevBuf<IngestMixedRow> mixed_table;
@@ -2128,19 +2127,37 @@ int device_pointer_kind(int device, const void *p) {
   return BPP_PTR_HOST_OR_UNKNOWN;
 }
 
-// The fall-back: a batch the arithmetic layout does not fit (mixed first bytes, no proofs, a stride below the length) is copied to
-// page-locked staging and takes the host path, item form and all.  The staged nonces are wiped on every way out.
-// item_states (the *_transcripts upload, else null): the state rows are staged with the rest and the batch goes through the item form,
-// item i under row i.
-uint64_t upload_packed_device_fallback(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t params, const bpp_packed_batch &in,
-                                       const uint8_t *item_states = nullptr) {
-  const size_t n = in.n_items, nm = n * (size_t)in.m, n_states = item_states ? n * (size_t)BPP_ITEM_STATE_BYTES : 0;
-  const bool strided = in.proofs && in.proof_len >= 1 && in.proof_stride > in.proof_len;  // staged back to back
-  const bool no_bytes = !in.proofs || in.proof_len < 1;  // (empty proofs: the item form reads none of them, whatever the stride)
-  const size_t proofs_n = no_bytes ? 0 : (strided ? n * in.proof_len : (n - 1) * in.proof_stride + in.proof_len);
+// the words of the upload refusals for a pointer that is not BPP_PTR_THIS_DEVICE, by kind
+const char *const upload_pointer_kinds[] = {"", "memory of another device", "host memory or memory the runtime does not know", "managed memory"};
+
+// what both device uploads refuse first: one of the caller's six arrays this device cannot read.  Nothing is allocated or launched for
+// such an array, and no array is ever dereferenced on the host.  Empty: nothing to refuse.
+template <class In>  // bpp_packed_batch or bpp_mixed_batch
+std::string upload_arrays_refusal(bpp_ctx *ctx, const In &in) {
+  const struct {
+    const char *name;
+    const void *p;
+  } arrays[] = {{"proofs", in.proofs},           {"commitments32", in.commitments32}, {"min_values", in.min_values},
+                {"min_present", in.min_present}, {"seed_nonces32", in.seed_nonces32}, {"seed_present", in.seed_present}};
+  for (const auto &a : arrays) {
+    if (!a.p) continue;
+    const int kind = device_pointer_kind(ctx->device, a.p);
+    if (kind != BPP_PTR_THIS_DEVICE)
+      return std::string(a.name) + " is not device memory of this context's device (" + upload_pointer_kinds[kind] + ")";
+  }
+  return std::string();
+}
+
+// The staging behind both fall-backs: the caller's arrays are copied to page-locked memory -- proofs_n bytes of proofs as they lie, or
+// gathered back to back, gather_len of every row, when gather_len is not 0; `entries` entries of the three per-commitment arrays; the
+// per-item arrays; the state rows of a *_transcripts upload (item_states, else null) -- and `pack(host, states)` makes the batch of the
+// staged copy `host` of `in`.  The staged nonces are wiped on every way out.
+template <class In, class Pack>
+uint64_t upload_staged(bpp_ctx *ctx, const In &in, size_t proofs_n, size_t entries, size_t gather_len, const uint8_t *item_states, Pack &&pack) {
+  const size_t n = in.n_items, n_states = item_states ? n * (size_t)BPP_ITEM_STATE_BYTES : 0;
   auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const size_t o_proofs = 0, o_commit = up16(proofs_n), o_minv = up16(o_commit + (in.commitments32 ? nm * 32 : 0)),
-               o_minp = up16(o_minv + (in.min_values ? nm * 8 : 0)), o_seedp = up16(o_minp + (in.min_present ? nm : 0)),
+  const size_t o_proofs = 0, o_commit = up16(proofs_n), o_minv = up16(o_commit + (in.commitments32 ? entries * 32 : 0)),
+               o_minp = up16(o_minv + (in.min_values ? entries * 8 : 0)), o_seedp = up16(o_minp + (in.min_present ? entries : 0)),
                o_states = up16(o_seedp + (in.seed_present ? n : 0)), o_seed = up16(o_states + n_states), n_seed = in.seed_nonces32 ? n * 32 : 0,
                total = o_seed + n_seed;
   ctx->pin_fallback.resize(total + 16);
@@ -2152,40 +2169,39 @@ uint64_t upload_packed_device_fallback(bpp_ctx *ctx, const std::shared_ptr<Param
       secure_wipe(st + o_seed, n_seed);
     }
   }};
-  bpp_packed_batch host = in;
+  In host = in;
   auto fetch = [&](const void *src, size_t off, size_t bytes) -> const uint8_t * {
     if (!src) return nullptr;
     if (bytes) HIP_CHECK(hipMemcpyAsync(st + off, src, bytes, hipMemcpyDeviceToHost, s));
     return st + off;
   };
-  if (strided) {
-    HIP_CHECK(hipMemcpy2DAsync(st + o_proofs, in.proof_len, in.proofs, in.proof_stride, in.proof_len, n, hipMemcpyDeviceToHost, s));
+  if (gather_len) {
+    HIP_CHECK(hipMemcpy2DAsync(st + o_proofs, gather_len, in.proofs, in.proof_stride, gather_len, n, hipMemcpyDeviceToHost, s));
     host.proofs = st + o_proofs;
-    host.proof_stride = in.proof_len;
+    host.proof_stride = gather_len;
   } else {
     host.proofs = fetch(in.proofs, o_proofs, proofs_n);
-    if (no_bytes) host.proof_stride = 0;
   }
-  host.commitments32 = fetch(in.commitments32, o_commit, nm * 32);
-  host.min_values = (const uint64_t *)fetch(in.min_values, o_minv, nm * 8);
-  host.min_present = fetch(in.min_present, o_minp, nm);
+  host.commitments32 = fetch(in.commitments32, o_commit, entries * 32);
+  host.min_values = (const uint64_t *)fetch(in.min_values, o_minv, entries * 8);
+  host.min_present = fetch(in.min_present, o_minp, entries);
   host.seed_present = fetch(in.seed_present, o_seedp, n);
   host.seed_nonces32 = fetch(in.seed_nonces32, o_seed, n_seed);
   const uint8_t *states = fetch(item_states, o_states, n_states);
   HIP_CHECK(hipStreamSynchronize(s));
   ctx->ingest_stats.host_fallback_calls++;
-  ctx->ingest_stats.fallback_bytes += proofs_n + (in.commitments32 ? nm * 32 : 0) + (in.min_values ? nm * 8 : 0) + (in.min_present ? nm : 0) +
-                                      (in.seed_present ? n : 0) + n_seed + n_states;
+  ctx->ingest_stats.fallback_bytes += proofs_n + (in.commitments32 ? entries * 32 : 0) + (in.min_values ? entries * 8 : 0) +
+                                      (in.min_present ? entries : 0) + (in.seed_present ? n : 0) + n_seed + n_states;
+  return pack(host, states);
+}
+
+// the staged batch through the item form, item i under row i of `states` where there are any
+uint64_t upload_staged_items(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t params, std::vector<bpp_verify_item> &items,
+                             const uint8_t *states) {
+  for (size_t i = 0; states && i < items.size(); i++) items[i].transcript_state = states + i * (size_t)BPP_ITEM_STATE_BYTES;
   UploadPlan pl;
   PlanWipe wipe_plan{pl};
-  if (states) {
-    std::vector<bpp_verify_item> items;
-    upload_packed_as_items(host, items);
-    for (size_t i = 0; i < n; i++) items[i].transcript_state = states + i * (size_t)BPP_ITEM_STATE_BYTES;
-    upload_host_pack(ctx, *Pp, items.data(), n, nullptr, pl);
-  } else {
-    upload_host_pack(ctx, *Pp, nullptr, n, &host, pl);
-  }
+  upload_host_pack(ctx, *Pp, items.data(), items.size(), nullptr, pl);
   return upload_device(ctx, Pp, params, pl, nullptr, nullptr);
 }
 
@@ -2193,12 +2209,11 @@ uint64_t upload_packed_device_fallback(bpp_ctx *ctx, const std::shared_ptr<Param
 // that is null or not this device's memory.  Empty: nothing to refuse.
 std::string item_states_refusal(bpp_ctx *ctx, const uint8_t *transcript_state, const uint8_t *transcript_label, const uint8_t *item_states,
                                 const char *name) {
-  static const char *const kinds[] = {"", "memory of another device", "host memory or memory the runtime does not know", "managed memory"};
   if (transcript_state) return std::string("transcript_state must be null: item i is verified under row i of ") + name;
   if (transcript_label) return std::string("transcript_label must be null: item i is verified under row i of ") + name;
   if (!item_states) return std::string(name) + " is null";
   const int kind = device_pointer_kind(ctx->device, item_states);
-  if (kind != BPP_PTR_THIS_DEVICE) return std::string(name) + " is not device memory of this context's device (" + kinds[kind] + ")";
+  if (kind != BPP_PTR_THIS_DEVICE) return std::string(name) + " is not device memory of this context's device (" + upload_pointer_kinds[kind] + ")";
   return std::string();
 }
 
@@ -2217,100 +2232,7 @@ void plan_item_states(UploadPlan &pl) {
   for (size_t i = 0; i < pl.desc.size(); i++) pl.desc[i].state_idx = (uint32_t)i;
 }
 
-// with_states (bpp_batch_upload_packed_device_transcripts): item i is verified under row i of item_states (item_states.h)
-int upload_packed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, uint64_t *batch, char *errbuf, size_t errbuf_len,
-                              bool with_states = false, const uint8_t *item_states = nullptr) {
-  try {
-    if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty", errbuf, errbuf_len);
-    if (with_states) {
-      const std::string refusal = item_states_refusal(ctx, in->transcript_state, in->transcript_label, item_states, "item_states203");
-      if (!refusal.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, refusal, errbuf, errbuf_len);
-    }
-    // pointer kinds first: nothing is allocated or launched for an array this device cannot read, and no array is ever
-    // dereferenced on the host
-    const struct {
-      const char *name;
-      const void *p;
-    } arrays[] = {{"proofs", in->proofs},           {"commitments32", in->commitments32}, {"min_values", in->min_values},
-                  {"min_present", in->min_present}, {"seed_nonces32", in->seed_nonces32}, {"seed_present", in->seed_present}};
-    static const char *const kinds[] = {"", "memory of another device", "host memory or memory the runtime does not know", "managed memory"};
-    for (const auto &a : arrays) {
-      if (!a.p) continue;
-      const int kind = device_pointer_kind(ctx->device, a.p);
-      if (kind != BPP_PTR_THIS_DEVICE)
-        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + " is not device memory of this context's device (" + kinds[kind] + ")", errbuf,
-                    errbuf_len);
-    }
-    const std::shared_ptr<Params> Pp = params_registry().get(params);
-    if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
-    const size_t n_items = in->n_items;
-    if (n_items == 0 || !batch) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty", errbuf, errbuf_len);
-    if (n_items > (1u << 24)) return fail(ctx, BPP_ERR_SIZE_OVERFLOW, "batch too large", errbuf, errbuf_len);
-    const ParamShape shape{Pp->n_bits, Pp->m_max, Pp->t};
-    if (!ingest_host_prelude(*in, shape)) {
-      *batch = upload_packed_device_fallback(ctx, Pp, params, *in, item_states);
-      return BPP_OK;
-    }
-    hipStream_t s = ctx->stream;
-    std::unique_ptr<Batch> B = new_batch(ctx);
-    ScopeExit wipe_unfinished{[&] {  // B still here: an error or the fall-back.  The nonces the kernel brought in go before its buffers do
-      if (B) {
-        wipe_batch_secrets(*B, s);
-        (void)hipStreamSynchronize(s);
-      }
-    }};
-    const size_t bytes_len = n_items * in->proof_len + n_items * (size_t)in->m * 32 + BPP_BYTES_SLACK;  // (< 4 GB: the prelude)
-    B->bytes.alloc(bytes_len);
-    B->minvals.alloc(n_items * (size_t)in->m);
-    if (in->seed_nonces32) B->seeds.alloc(n_items * 32);
-    ctx->ingest_res.alloc(BPP_ING_RES_WORDS);
-    ctx->ingest_info.alloc(n_items);
-    ctx->pin_ingest.resize(BPP_ING_RES_WORDS);
-    const IngestPacked a = ingest_args(*in, shape, B->bytes.p, B->minvals.p, B->seeds.p, ctx->ingest_info.p, ctx->ingest_res.p);
-    HIP_CHECK(hipMemsetAsync(ctx->ingest_res.p, 0, BPP_ING_RES_WORDS * 4, s));
-    B->seeds_dirty = in->seed_nonces32 != nullptr;
-    hipLaunchKernelGGL(k_ingest_packed, dim3((uint32_t)cdiv((uint32_t)n_items, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, a);
-    HIP_CHECK(hipGetLastError());
-    if (with_states) launch_item_states_upload(ctx, *B, item_states, n_items, n_items);
-    uint32_t *res = ctx->pin_ingest.data();
-    HIP_CHECK(hipMemcpyAsync(res, ctx->ingest_res.p, BPP_ING_RES_WORDS * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    if (res[BPP_ING_RES_DIFFERS]) {
-      wipe_batch_secrets(*B, s);
-      (void)hipStreamSynchronize(s);
-      ctx->spare_batch = std::move(B);  // its buffers serve the host path's batch
-      *batch = upload_packed_device_fallback(ctx, Pp, params, *in, item_states);
-      return BPP_OK;
-    }
-    const uint8_t *info = nullptr;
-    if (ingest_needs_info(*in, res)) {
-      ctx->pin_ingest_info.resize(n_items);
-      HIP_CHECK(hipMemcpyAsync(ctx->pin_ingest_info.data(), ctx->ingest_info.p, n_items, hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipStreamSynchronize(s));
-      info = ctx->pin_ingest_info.data();
-    }
-    UploadPlan pl;
-    ingest_finish_plan(*in, shape, res, info, pl);  // throws the lowest-index construction finding
-    if (with_states) plan_item_states(pl);
-    B->item_states = with_states;
-    ctx->ingest_stats.device_calls++;
-    *batch = upload_device(ctx, Pp, params, pl, nullptr, nullptr, std::move(B));
-    // the shape a refill of this batch must keep (bpp_batch_refill_enqueue): everything the plan above was made from but the bytes
-    Batch &made = *ctx->batches[*batch];
-    made.refillable = true;
-    made.refill_shape.n_items = n_items;
-    made.refill_shape.proof_len = in->proof_len;
-    made.refill_shape.m = in->m;
-    made.refill_shape.t0 = res[BPP_ING_RES_T0] & 255u;
-    made.refill_shape.nonces = in->seed_nonces32 != nullptr;
-    made.refill_shape.min_values = in->min_values != nullptr;
-    made.refill_shape.min_present = in->min_present != nullptr;
-    return BPP_OK;
-  }
-  BPP_CATCH(ctx, errbuf, errbuf_len)
-}
-
-// ---- the mixed form (bpp_mixed_batch): host arrays through the item form, device arrays through k_ingest_mixed (ingest_mixed.h)
+// ---- the mixed form (bpp_mixed_batch): host arrays through the item form, device arrays through upload_device_form below
 int upload_mixed_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, uint64_t *batch, char *errbuf, size_t errbuf_len) {
   try {
     if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty", errbuf, errbuf_len);
@@ -2331,97 +2253,134 @@ int upload_mixed_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, 
   BPP_CATCH(ctx, errbuf, errbuf_len)
 }
 
-// The fall-back of the device form: the arrays are copied to page-locked staging as they lie (rows, slack and all, up to the last
-// byte the last row uses) and the batch takes the host form.  The staged nonces are wiped on every way out.
-uint64_t upload_mixed_device_fallback(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t params, const bpp_mixed_batch &in,
-                                      const uint8_t *item_states = nullptr) {
-  const size_t n = in.n_items, last_m = in.m[n - 1], row_entries = (n - 1) * (size_t)in.m_stride + last_m;
-  const size_t n_states = item_states ? n * (size_t)BPP_ITEM_STATE_BYTES : 0;
-  const size_t proofs_n = in.proofs ? (n - 1) * in.proof_stride + in.proof_lens[n - 1] : 0;
-  auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-  const size_t o_proofs = 0, o_commit = up16(proofs_n), o_minv = up16(o_commit + (in.commitments32 ? row_entries * 32 : 0)),
-               o_minp = up16(o_minv + (in.min_values ? row_entries * 8 : 0)), o_seedp = up16(o_minp + (in.min_present ? row_entries : 0)),
-               o_states = up16(o_seedp + (in.seed_present ? n : 0)), o_seed = up16(o_states + n_states), n_seed = in.seed_nonces32 ? n * 32 : 0,
-               total = o_seed + n_seed;
-  ctx->pin_fallback.resize(total + 16);
-  uint8_t *st = ctx->pin_fallback.data();
-  hipStream_t s = ctx->stream;
-  ScopeExit wipe_staged{[&] {
-    if (n_seed) {
-      (void)hipStreamSynchronize(s);  // the copy into the staging may still be running
-      secure_wipe(st + o_seed, n_seed);
-    }
-  }};
-  bpp_mixed_batch host = in;
-  auto fetch = [&](const void *src, size_t off, size_t bytes) -> const uint8_t * {
-    if (!src) return nullptr;
-    if (bytes) HIP_CHECK(hipMemcpyAsync(st + off, src, bytes, hipMemcpyDeviceToHost, s));
-    return st + off;
-  };
-  host.proofs = fetch(in.proofs, o_proofs, proofs_n);
-  host.commitments32 = fetch(in.commitments32, o_commit, row_entries * 32);
-  host.min_values = (const uint64_t *)fetch(in.min_values, o_minv, row_entries * 8);
-  host.min_present = fetch(in.min_present, o_minp, row_entries);
-  host.seed_present = fetch(in.seed_present, o_seedp, n);
-  host.seed_nonces32 = fetch(in.seed_nonces32, o_seed, n_seed);
-  const uint8_t *states = fetch(item_states, o_states, n_states);
-  HIP_CHECK(hipStreamSynchronize(s));
-  ctx->ingest_stats.host_fallback_calls++;
-  ctx->ingest_stats.fallback_bytes += proofs_n + (in.commitments32 ? row_entries * 32 : 0) + (in.min_values ? row_entries * 8 : 0) +
-                                      (in.min_present ? row_entries : 0) + (in.seed_present ? n : 0) + n_seed + n_states;
-  std::vector<bpp_verify_item> items;
-  upload_mixed_as_items(host, items);
-  for (size_t i = 0; states && i < n; i++) items[i].transcript_state = states + i * (size_t)BPP_ITEM_STATE_BYTES;
-  UploadPlan pl;
-  PlanWipe wipe_plan{pl};
-  upload_host_pack(ctx, *Pp, items.data(), n, nullptr, pl);
-  return upload_device(ctx, Pp, params, pl, nullptr, nullptr);
+// ---- the two device uploads (ingest.h): one flow, upload_device_form, over what the packed and the mixed form supply -- the prelude,
+// the sizes, the kernel and its arguments, the plan, the staged fall-back and the shape a refill must keep.
+struct PackedUpload {
+  const bpp_packed_batch &in;
+  ParamShape shape{};
+
+  std::string host_arrays_refusal(bpp_ctx *) const { return std::string(); }
+  bool prelude(const ParamShape &P) {  // false: the arithmetic layout does not fit (no proofs, a stride below the length)
+    shape = P;
+    return ingest_host_prelude(in, P);
+  }
+  size_t sum_m() const { return in.n_items * (size_t)in.m; }
+  size_t bytes_total() const { return in.n_items * in.proof_len + sum_m() * 32; }
+  Ingest args(bpp_ctx *ctx, Batch &B, hipStream_t, bool) const {
+    return ingest_args(in, shape, B.bytes.p, B.minvals.p, B.seeds.p, ctx->ingest_info.p, ctx->ingest_res.p);
+  }
+  static auto kernel() { return k_ingest_packed; }
+  void plan(const uint32_t *res, const uint8_t *info, UploadPlan &pl) const { ingest_finish_plan(in, shape, res, info, pl); }
+  // a stride above the length is gathered back to back; empty proofs: the item form reads none of them, whatever the stride
+  uint64_t fallback(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t params, const uint8_t *item_states) const {
+    const size_t n = in.n_items;
+    const bool no_bytes = !in.proofs || in.proof_len < 1, strided = !no_bytes && in.proof_stride > in.proof_len;
+    const size_t proofs_n = no_bytes ? 0 : (strided ? n * in.proof_len : (n - 1) * in.proof_stride + in.proof_len);
+    return upload_staged(ctx, in, proofs_n, n * (size_t)in.m, strided ? in.proof_len : 0, item_states,
+                         [&](bpp_packed_batch &host, const uint8_t *states) {
+                           if (no_bytes) host.proof_stride = 0;
+                           if (states) {
+                             std::vector<bpp_verify_item> items;
+                             upload_packed_as_items(host, items);
+                             return upload_staged_items(ctx, Pp, params, items, states);
+                           }
+                           UploadPlan pl;
+                           PlanWipe wipe_plan{pl};
+                           upload_host_pack(ctx, *Pp, nullptr, n, &host, pl);
+                           return upload_device(ctx, Pp, params, pl, nullptr, nullptr);
+                         });
+  }
+  void record_shape(Batch &made) {  // (bpp_batch_refill_enqueue: everything the plan was made from but the bytes)
+    made.refillable = true;
+    made.refill_shape.proof_len = in.proof_len;
+    made.refill_shape.m = in.m;
+  }
+};
+
+// the two host arrays of a mixed batch are dereferenced on the host, and so must not be memory of a device.  Empty: nothing to refuse.
+std::string mixed_host_arrays_refusal(bpp_ctx *ctx, const bpp_mixed_batch &in, const char *what_it_does) {
+  const struct {
+    const char *name;
+    const void *p;
+  } host_arrays[] = {{"proof_lens", in.proof_lens}, {"m", in.m}};
+  for (const auto &a : host_arrays) {
+    const int kind = device_pointer_kind(ctx->device, a.p);
+    if (kind == BPP_PTR_THIS_DEVICE || kind == BPP_PTR_OTHER_DEVICE)
+      return std::string(a.name) + " is device memory: it " + what_it_does + " and stays host memory in every form";
+  }
+  return std::string();
 }
 
-// with_states (bpp_batch_upload_mixed_device_transcripts): item i is verified under row i of item_states (item_states.h)
-int upload_mixed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, uint64_t *batch, char *errbuf, size_t errbuf_len,
-                             bool with_states = false, const uint8_t *item_states = nullptr) {
+struct MixedUpload {
+  const bpp_mixed_batch &in;
+  ParamShape shape{};
+  IngestMixedPrelude pre{};
+
+  std::string host_arrays_refusal(bpp_ctx *ctx) const { return mixed_host_arrays_refusal(ctx, in, "sizes the layout"); }
+  bool prelude(const ParamShape &P) {  // false: no proofs array
+    shape = P;
+    if (!ingest_mixed_host_prelude(in, P, pre)) return false;
+    if (pre.h == 0) ingest_mixed_throw_finding(pre, in.n_items, nullptr);  // item 0's, host-known: nothing to run
+    return true;
+  }
+  size_t sum_m() const { return (size_t)pre.sum_m; }
+  size_t bytes_total() const { return (size_t)(pre.proof_bytes + pre.sum_m * 32); }
+  // mixed only: the table goes up in front of the run, and a fresh nonce buffer starts out zero -- the run may stop short of the last
+  // item, and every buffer that holds secrets at times starts that way
+  Ingest args(bpp_ctx *ctx, Batch &B, hipStream_t s, bool fresh_seeds) const {
+    const size_t n = in.n_items;
+    if (fresh_seeds) HIP_CHECK(hipMemsetAsync(B.seeds.p, 0, B.seeds.n, s));
+    B.mixed_table.alloc(n);
+    ctx->pin_mixed_table.resize(n);
+    memcpy(ctx->pin_mixed_table.data(), pre.rows.data(), n * sizeof(IngestMixedRow));
+    HIP_CHECK(hipMemcpyAsync(B.mixed_table.p, ctx->pin_mixed_table.data(), n * sizeof(IngestMixedRow), hipMemcpyHostToDevice, s));
+    return ingest_mixed_args(in, shape, pre, B.mixed_table.p, B.bytes.p, B.minvals.p, B.seeds.p, ctx->ingest_info.p, ctx->ingest_res.p);
+  }
+  static auto kernel() { return k_ingest_mixed; }
+  // (with h < n_items the plan throws the call's finding, the device's before the host's at h, before it looks at anything else)
+  void plan(const uint32_t *res, const uint8_t *info, UploadPlan &pl) const { ingest_mixed_finish_plan(in, shape, pre, res, info, pl); }
+  // the arrays are staged as they lie: rows, slack and all, up to the last byte the last row uses
+  uint64_t fallback(bpp_ctx *ctx, const std::shared_ptr<Params> &Pp, uint64_t params, const uint8_t *item_states) const {
+    const size_t n = in.n_items;
+    return upload_staged(ctx, in, in.proofs ? (n - 1) * in.proof_stride + in.proof_lens[n - 1] : 0, (n - 1) * (size_t)in.m_stride + in.m[n - 1], 0,
+                         item_states, [&](bpp_mixed_batch &host, const uint8_t *states) {
+                           std::vector<bpp_verify_item> items;
+                           upload_mixed_as_items(host, items);
+                           return upload_staged_items(ctx, Pp, params, items, states);
+                         });
+  }
+  void record_shape(Batch &made) {  // (bpp_batch_refill_enqueue_mixed: the vector the plan was made from)
+    made.mixed = true;
+    made.mixed_shape.seed_present = in.seed_present != nullptr;
+    made.mixed_shape.proof_bytes = pre.proof_bytes;
+    for (const IngestMixedRow &r : pre.rows) {
+      made.mixed_shape.max_proof_len = std::max(made.mixed_shape.max_proof_len, r.proof_len);
+      made.mixed_shape.max_m = std::max(made.mixed_shape.max_m, r.m);
+    }
+    made.mixed_shape.rows = std::move(pre.rows);
+  }
+};
+
+// with_states (the *_transcripts uploads): item i is verified under row i of item_states (item_states.h)
+template <class Form, class In>
+int upload_device_form(bpp_ctx *ctx, uint64_t params, const In *in, uint64_t *batch, char *errbuf, size_t errbuf_len, bool with_states = false,
+                       const uint8_t *item_states = nullptr) {
   try {
     if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty", errbuf, errbuf_len);
-    if (with_states) {
-      const std::string refusal = item_states_refusal(ctx, in->transcript_state, in->transcript_label, item_states, "item_states203");
-      if (!refusal.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, refusal, errbuf, errbuf_len);
-    }
-    // pointer kinds first, as in upload_packed_device_impl: the six arrays are never dereferenced on the host, the two host arrays
-    // are, and so must not be memory of a device
-    const struct {
-      const char *name;
-      const void *p;
-    } arrays[] = {{"proofs", in->proofs},           {"commitments32", in->commitments32}, {"min_values", in->min_values},
-                  {"min_present", in->min_present}, {"seed_nonces32", in->seed_nonces32}, {"seed_present", in->seed_present}},
-      host_arrays[] = {{"proof_lens", in->proof_lens}, {"m", in->m}};
-    static const char *const kinds[] = {"", "memory of another device", "host memory or memory the runtime does not know", "managed memory"};
-    for (const auto &a : arrays) {
-      if (!a.p) continue;
-      const int kind = device_pointer_kind(ctx->device, a.p);
-      if (kind != BPP_PTR_THIS_DEVICE)
-        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + " is not device memory of this context's device (" + kinds[kind] + ")", errbuf,
-                    errbuf_len);
-    }
-    for (const auto &a : host_arrays) {
-      if (!a.p) continue;
-      const int kind = device_pointer_kind(ctx->device, a.p);
-      if (kind == BPP_PTR_THIS_DEVICE || kind == BPP_PTR_OTHER_DEVICE)
-        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + " is device memory: it sizes the layout and stays host memory in every form",
-                    errbuf, errbuf_len);
-    }
+    Form form{*in};
+    std::string refusal = with_states ? item_states_refusal(ctx, in->transcript_state, in->transcript_label, item_states, "item_states203") : std::string();
+    if (refusal.empty()) refusal = upload_arrays_refusal(ctx, *in);  // pointer kinds before anything is allocated or launched
+    if (refusal.empty()) refusal = form.host_arrays_refusal(ctx);
+    if (!refusal.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, refusal, errbuf, errbuf_len);
     const std::shared_ptr<Params> Pp = params_registry().get(params);
     if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
     const size_t n_items = in->n_items;
     if (n_items == 0 || !batch) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "Range statements or proofs length empty", errbuf, errbuf_len);
     if (n_items > (1u << 24)) return fail(ctx, BPP_ERR_SIZE_OVERFLOW, "batch too large", errbuf, errbuf_len);
-    const ParamShape shape{Pp->n_bits, Pp->m_max, Pp->t};
-    IngestMixedPrelude pre;
-    if (!ingest_mixed_host_prelude(*in, shape, pre)) {
-      *batch = upload_mixed_device_fallback(ctx, Pp, params, *in, item_states);
+    if (!form.prelude(ParamShape{Pp->n_bits, Pp->m_max, Pp->t})) {
+      *batch = form.fallback(ctx, Pp, params, item_states);
       return BPP_OK;
     }
-    if (pre.h == 0) ingest_mixed_throw_finding(pre, n_items, nullptr);  // item 0's, host-known: nothing to run
     hipStream_t s = ctx->stream;
     std::unique_ptr<Batch> B = new_batch(ctx);
     ScopeExit wipe_unfinished{[&] {  // B still here: an error or the fall-back.  The nonces the kernel brought in go before its buffers do
@@ -2430,69 +2389,50 @@ int upload_mixed_device_impl(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batc
         (void)hipStreamSynchronize(s);
       }
     }};
-    const size_t bytes_len = (size_t)(pre.proof_bytes + pre.sum_m * 32) + BPP_BYTES_SLACK;  // (< 4 GB: the prelude)
-    B->bytes.alloc(bytes_len);
-    B->minvals.alloc((size_t)pre.sum_m);
-    if (in->seed_nonces32) {
-      // (the run may stop short of the last item: a fresh allocation starts out zero, as every buffer that holds secrets at times)
-      const bool fresh = !(B->seeds.p && n_items * 32 <= B->seeds.n);
-      B->seeds.alloc(n_items * 32);
-      if (fresh) HIP_CHECK(hipMemsetAsync(B->seeds.p, 0, B->seeds.n, s));
-    }
-    B->mixed_table.alloc(n_items);
+    B->bytes.alloc(form.bytes_total() + BPP_BYTES_SLACK);  // (< 4 GB: the prelude)
+    B->minvals.alloc(form.sum_m());
+    const bool fresh_seeds = in->seed_nonces32 && !(B->seeds.p && n_items * 32 <= B->seeds.n);
+    if (in->seed_nonces32) B->seeds.alloc(n_items * 32);
     ctx->ingest_res.alloc(BPP_ING_RES_WORDS);
     ctx->ingest_info.alloc(n_items);
     ctx->pin_ingest.resize(BPP_ING_RES_WORDS);
-    ctx->pin_mixed_table.resize(n_items);
-    memcpy(ctx->pin_mixed_table.data(), pre.rows.data(), n_items * sizeof(IngestMixedRow));
-    HIP_CHECK(hipMemcpyAsync(B->mixed_table.p, ctx->pin_mixed_table.data(), n_items * sizeof(IngestMixedRow), hipMemcpyHostToDevice, s));
-    const IngestMixed a = ingest_mixed_args(*in, shape, pre, B->mixed_table.p, B->bytes.p, B->minvals.p, B->seeds.p, ctx->ingest_info.p,
-                                            ctx->ingest_res.p);
+    const Ingest a = form.args(ctx, *B, s, fresh_seeds);
     HIP_CHECK(hipMemsetAsync(ctx->ingest_res.p, 0, BPP_ING_RES_WORDS * 4, s));
     B->seeds_dirty = in->seed_nonces32 != nullptr;
-    hipLaunchKernelGGL(k_ingest_mixed, dim3((uint32_t)cdiv(a.n_run, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, a);
+    hipLaunchKernelGGL(Form::kernel(), dim3((uint32_t)cdiv(a.n_run, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, a);
     HIP_CHECK(hipGetLastError());
-    if (with_states) launch_item_states_upload(ctx, *B, item_states, n_items, a.n_run);  // (rows at and beyond the host's finding: not read)
+    if (with_states) launch_item_states_upload(ctx, *B, item_states, n_items, a.n_run);  // (rows at and beyond a host finding: not read)
     uint32_t *res = ctx->pin_ingest.data();
     HIP_CHECK(hipMemcpyAsync(res, ctx->ingest_res.p, BPP_ING_RES_WORDS * 4, hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
-    if (res[BPP_ING_RES_DIFFERS]) {
+    if (res[BPP_ING_RES_DIFFERS]) {  // mixed first bytes: the host path, item form and all
       wipe_batch_secrets(*B, s);
       (void)hipStreamSynchronize(s);
       ctx->spare_batch = std::move(B);  // its buffers serve the host path's batch
-      *batch = upload_mixed_device_fallback(ctx, Pp, params, *in, item_states);
+      *batch = form.fallback(ctx, Pp, params, item_states);
       return BPP_OK;
     }
-    ingest_mixed_throw_finding(pre, n_items, res);  // (h < n_items: the call ends here either way, nothing else is fetched)
     const uint8_t *info = nullptr;
-    if (ingest_mixed_needs_info(*in, res)) {
+    if (!res[BPP_ING_RES_FINDING] && ingest_needs_info(*in, res)) {  // (with a finding the call ends in the plan: nothing else is fetched)
       ctx->pin_ingest_info.resize(n_items);
       HIP_CHECK(hipMemcpyAsync(ctx->pin_ingest_info.data(), ctx->ingest_info.p, n_items, hipMemcpyDeviceToHost, s));
       HIP_CHECK(hipStreamSynchronize(s));
       info = ctx->pin_ingest_info.data();
     }
     UploadPlan pl;
-    ingest_mixed_finish_plan(*in, shape, pre, res, info, pl);
+    form.plan(res, info, pl);  // throws the lowest-index construction finding
     if (with_states) plan_item_states(pl);
     B->item_states = with_states;
     ctx->ingest_stats.device_calls++;
     *batch = upload_device(ctx, Pp, params, pl, nullptr, nullptr, std::move(B));
+    // the shape a refill of this batch must keep: the form's own, the first byte and which optional arrays exist
     Batch &made = *ctx->batches[*batch];
-    made.mixed = true;
-    // the shape a refill of this batch must keep (bpp_batch_refill_enqueue_mixed): the vector the plan above was made from, the first
-    // byte and which optional arrays exist
     made.refill_shape.n_items = n_items;
     made.refill_shape.t0 = res[BPP_ING_RES_T0] & 255u;
     made.refill_shape.nonces = in->seed_nonces32 != nullptr;
     made.refill_shape.min_values = in->min_values != nullptr;
     made.refill_shape.min_present = in->min_present != nullptr;
-    made.mixed_shape.seed_present = in->seed_present != nullptr;
-    made.mixed_shape.proof_bytes = pre.proof_bytes;
-    for (const IngestMixedRow &r : pre.rows) {
-      made.mixed_shape.max_proof_len = std::max(made.mixed_shape.max_proof_len, r.proof_len);
-      made.mixed_shape.max_m = std::max(made.mixed_shape.max_m, r.m);
-    }
-    made.mixed_shape.rows = std::move(pre.rows);
+    form.record_shape(made);
     return BPP_OK;
   }
   BPP_CATCH(ctx, errbuf, errbuf_len)
@@ -2509,25 +2449,25 @@ int bpp_batch_upload_mixed(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch 
 int bpp_batch_upload_mixed_device(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, uint64_t *batch, char *errbuf,
                                   size_t errbuf_len) {
   BPP_ENTRY(ctx);
-  return upload_mixed_device_impl(ctx, params, in, batch, errbuf, errbuf_len);
+  return upload_device_form<MixedUpload>(ctx, params, in, batch, errbuf, errbuf_len);
 }
 
 int bpp_batch_upload_packed_device(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, uint64_t *batch, char *errbuf,
                                    size_t errbuf_len) {
   BPP_ENTRY(ctx);
-  return upload_packed_device_impl(ctx, params, in, batch, errbuf, errbuf_len);
+  return upload_device_form<PackedUpload>(ctx, params, in, batch, errbuf, errbuf_len);
 }
 
 int bpp_batch_upload_packed_device_transcripts(bpp_ctx *ctx, uint64_t params, const bpp_packed_batch *in, const uint8_t *item_states203,
                                                uint64_t *batch, char *errbuf, size_t errbuf_len) {
   BPP_ENTRY(ctx);
-  return upload_packed_device_impl(ctx, params, in, batch, errbuf, errbuf_len, true, item_states203);
+  return upload_device_form<PackedUpload>(ctx, params, in, batch, errbuf, errbuf_len, true, item_states203);
 }
 
 int bpp_batch_upload_mixed_device_transcripts(bpp_ctx *ctx, uint64_t params, const bpp_mixed_batch *in, const uint8_t *item_states203,
                                               uint64_t *batch, char *errbuf, size_t errbuf_len) {
   BPP_ENTRY(ctx);
-  return upload_mixed_device_impl(ctx, params, in, batch, errbuf, errbuf_len, true, item_states203);
+  return upload_device_form<MixedUpload>(ctx, params, in, batch, errbuf, errbuf_len, true, item_states203);
 }
 
 int bpp_device_pointer_check(bpp_ctx *ctx, const void *p, int *kind) {
@@ -3787,10 +3727,10 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
 // and the layout are the shape's and stay.
 // count_dev and live_dev (at most one of them): the count form and the mask form of the refill.  The batch is in the form of its last
 // refill: a mask refill switches the chain and verdict kernels to their MASKED forms on the batch's own copy of the mask, any other
-// refill switches them back.  batch_refill_locked is the driver of the three packed calls; batch_refill_mixed_locked (refill_mixed.h)
-// that of the mixed call; both end in refill_enqueue_tail.
+// refill switches them back.  batch_refill_locked is the driver of every refill call, over what PackedRefill and MixedRefill supply;
+// it ends in refill_enqueue_tail.
 
-// what both refill drivers refuse alike, before anything else is looked at: the kind of memory behind the caller's six arrays and
+// what every refill refuses alike: the kind of memory behind the caller's six arrays and
 // behind record_dev / count_dev / live_dev, and the alignment of the two that are read or written as words.  Empty: nothing to refuse.
 std::string refill_pointer_refusal(bpp_ctx *ctx, const void *proofs, const void *commitments32, const void *min_values, const void *min_present,
                                    const void *seed_nonces32, const void *seed_present, const bpp_device_refill *record_dev,
@@ -3888,134 +3828,136 @@ void refill_enqueue_tail(bpp_ctx *ctx, Batch &b, bool nonces, const uint32_t *co
   rs.calls++;
 }
 
-int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in, const uint32_t *count_dev, const uint8_t *live_dev,
-                        bpp_device_refill *record_dev, uint64_t *ticket, bool with_states = false, const uint8_t *item_states_dev = nullptr) {
-  try {
-    auto it = ctx->batches.find(batch);
-    if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
-    if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
-    Batch &b = *it->second;
-    if (!b.refillable || b.ext_challenges || b.want_states)
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT,
-                  "the batch cannot be refilled: only a batch that bpp_batch_upload_packed_device packed on the device records its shape (not the "
-                  "item form, the host packed form, the staged fall-back, caller-side challenges or a batch that hands out states)");
-    if (count_dev && live_dev) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "count_dev and live_dev: a refill takes a live count or a live mask, not both");
-    const std::string states_refusal = refill_item_states_refusal(ctx, b, with_states, item_states_dev, false);
-    if (!states_refusal.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, states_refusal);
-    const Batch::RefillShape &sh = b.refill_shape;
-    const struct {
-      const char *name;
-      bool same;
-    } shape[] = {{"n_items", (uint64_t)in->n_items == sh.n_items},
-                 {"m", in->m == sh.m},
-                 {"proof_len", (uint64_t)in->proof_len == sh.proof_len},
-                 {"seed_nonces32", (in->seed_nonces32 != nullptr) == sh.nonces},
-                 {"min_values", (in->min_values != nullptr) == sh.min_values},
-                 {"min_present", (in->min_present != nullptr) == sh.min_present}};
-    for (const auto &f : shape)
-      if (!f.same) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(f.name) + " differs from the batch's shape: a refill keeps the shape of the upload");
-    if (in->proof_stride < in->proof_len) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proof_stride is below proof_len");
-    if (in->transcript_state || in->transcript_label)
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, with_states ? "transcript_state / transcript_label must be null: item i is verified under row i of item_states203_dev"
-                                                             : "transcript_state / transcript_label must be null: a refilled batch keeps its transcript");
-    if (!in->proofs || !in->commitments32) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proofs / commitments32: null");
-    const std::string refusal = refill_pointer_refusal(ctx, in->proofs, in->commitments32, in->min_values, in->min_present, in->seed_nonces32,
-                                                       in->seed_present, record_dev, count_dev, live_dev);
-    if (!refusal.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, refusal);
-    Params &P = *b.params;
-    const size_t n = b.B;
-    // what the kernel writes, against what the upload allocated (the shape says they fit; a kernel is not launched on less)
-    if (b.bytes.n < n * sh.proof_len + n * (size_t)sh.m * 32 + BPP_BYTES_SLACK || b.minvals.n < n * (size_t)sh.m || (sh.nonces && b.seeds.n < n * 32) ||
-        b.d_desc.n < n || b.status0.n < n || b.status.n < n || b.masks.n < n * (size_t)P.t * 32 || b.sum_m != n * sh.m)
-      throw EngineError{BPP_ERR_ENGINE, "refill: the batch's buffers do not fit its recorded shape"};
-    const ParamShape shape_p{P.n_bits, P.m_max, P.t};
-    refill_enqueue_tail(ctx, b, sh.nonces, count_dev, live_dev, record_dev, ticket, item_states_dev, [&](hipStream_t s, bool masked) {
-      const RefillPacked r = refill_args(*in, shape_p, (uint8_t)sh.t0, b.bytes.p, b.minvals.p, b.seeds.p, b.d_defer.p, b.d_desc.p, b.status0.p,
-                                         b.status.p, reinterpret_cast<uint32_t *>(b.masks.p), b.refill_red.p, count_dev, live_dev,
-                                         b.refill_mask.p);
-      const dim3 refill_grid((uint32_t)cdiv((uint32_t)n, BPP_INGEST_BLOCK / BPP_INGEST_LANES));
-      if (masked) hipLaunchKernelGGL(k_refill_packed<true>, refill_grid, dim3(BPP_INGEST_BLOCK), 0, s, r);
-      else hipLaunchKernelGGL(k_refill_packed<false>, refill_grid, dim3(BPP_INGEST_BLOCK), 0, s, r);
-    });
-    return BPP_OK;
-  }
-  BPP_CATCH(ctx, nullptr, 0)
+// the fields of a refill that must repeat the batch's shape, in the order they are refused.  Empty: nothing to refuse.
+struct RefillShapeField {
+  const char *name;
+  bool same;
+};
+std::string refill_shape_refusal(std::initializer_list<RefillShapeField> fields) {
+  for (const auto &f : fields)
+    if (!f.same) return std::string(f.name) + " differs from the batch's shape: a refill keeps the shape of the upload";
+  return std::string();
 }
 
-// ---- bpp_batch_refill_enqueue_mixed (refill_mixed.h): the same for a batch of mixed aggregation factors.  Its shape is the vector
-// (proof_lens[i], m[i]) the upload recorded (Batch::mixed_shape, on the device Batch::mixed_table); in->proof_lens / in->m are host
-// arrays that must repeat it, or both null -- then nothing of size N is touched here.  The strides are the SOURCE's and need only hold
-// the batch's longest row.  Everything is refused before the tail, which is batch_refill_locked's.
-int batch_refill_mixed_locked(bpp_ctx *ctx, uint64_t batch, const bpp_mixed_batch *in, const uint32_t *count_dev, const uint8_t *live_dev,
-                              bpp_device_refill *record_dev, uint64_t *ticket, bool with_states = false, const uint8_t *item_states_dev = nullptr) {
+// What the packed and the mixed refill supply to batch_refill_locked: which batches they take, what of the caller's struct must repeat
+// the batch's shape, what the kernel writes against what the upload allocated, and the kernel with its arguments.
+struct PackedRefill {
+  const bpp_packed_batch &in;
+  static constexpr bool mixed = false;
+  static bool takes(const Batch &b) { return b.refillable; }
+  static const char *cannot() {
+    return "the batch cannot be refilled: only a batch that bpp_batch_upload_packed_device packed on the device records its shape (not the "
+           "item form, the host packed form, the staged fall-back, caller-side challenges or a batch that hands out states)";
+  }
+  std::string shape_refusal(bpp_ctx *, const Batch &b) const {
+    const Batch::RefillShape &sh = b.refill_shape;
+    const std::string refusal = refill_shape_refusal({{"n_items", (uint64_t)in.n_items == sh.n_items},
+                                                      {"m", in.m == sh.m},
+                                                      {"proof_len", (uint64_t)in.proof_len == sh.proof_len},
+                                                      {"seed_nonces32", (in.seed_nonces32 != nullptr) == sh.nonces},
+                                                      {"min_values", (in.min_values != nullptr) == sh.min_values},
+                                                      {"min_present", (in.min_present != nullptr) == sh.min_present}});
+    if (!refusal.empty()) return refusal;
+    return in.proof_stride < in.proof_len ? "proof_stride is below proof_len" : std::string();
+  }
+  std::string vector_refusal(const Batch &) const { return std::string(); }
+  bool fits(const Batch &b) const {
+    const Batch::RefillShape &sh = b.refill_shape;
+    const size_t n = b.B;
+    return b.bytes.n >= n * sh.proof_len + n * (size_t)sh.m * 32 + BPP_BYTES_SLACK && b.minvals.n >= n * (size_t)sh.m && b.sum_m == n * sh.m;
+  }
+  Refill args(Batch &b, const ParamShape &P, const uint32_t *count_dev, const uint8_t *live_dev) const {
+    return refill_args(in, P, (uint8_t)b.refill_shape.t0, b.bytes.p, b.minvals.p, b.seeds.p, b.d_defer.p, b.d_desc.p, b.status0.p, b.status.p,
+                       reinterpret_cast<uint32_t *>(b.masks.p), b.refill_red.p, count_dev, live_dev, b.refill_mask.p);
+  }
+  static auto kernel(bool masked) { return masked ? k_refill_packed<true> : k_refill_packed<false>; }
+};
+
+// The mixed batch's shape is the vector (proof_lens[i], m[i]) the upload recorded (Batch::mixed_shape, on the device Batch::mixed_table);
+// in.proof_lens / in.m are host arrays that must repeat it, or both null -- then nothing of size N is touched here.  The strides are the
+// SOURCE's and need only hold the batch's longest row.
+struct MixedRefill {
+  const bpp_mixed_batch &in;
+  static constexpr bool mixed = true;
+  static bool takes(const Batch &b) { return b.mixed && b.mixed_table.p && !b.mixed_shape.rows.empty(); }
+  static const char *cannot() {
+    return "the batch cannot be refilled from a mixed batch: only a batch that bpp_batch_upload_mixed_device packed on the device records "
+           "its shape vector (not its staged fall-back, the host mixed form, a packed or item batch, caller-side challenges or a batch "
+           "that hands out states)";
+  }
+  std::string shape_refusal(bpp_ctx *ctx, const Batch &b) const {
+    const Batch::RefillShape &sh = b.refill_shape;
+    const Batch::MixedShape &ms = b.mixed_shape;
+    std::string refusal = refill_shape_refusal({{"n_items", (uint64_t)in.n_items == sh.n_items},
+                                                {"seed_nonces32", (in.seed_nonces32 != nullptr) == sh.nonces},
+                                                {"seed_present", (in.seed_present != nullptr) == ms.seed_present},
+                                                {"min_values", (in.min_values != nullptr) == sh.min_values},
+                                                {"min_present", (in.min_present != nullptr) == sh.min_present}});
+    if (!refusal.empty()) return refusal;
+    if ((in.proof_lens != nullptr) != (in.m != nullptr))
+      return "proof_lens and m: give both (they must repeat the batch's vectors) or neither (the batch's own)";
+    refusal = mixed_host_arrays_refusal(ctx, in, "names the batch's shape");
+    if (!refusal.empty()) return refusal;
+    if (in.proof_stride < ms.max_proof_len) return "proof_stride is below the batch's largest proof_len (" + std::to_string(ms.max_proof_len) + ")";
+    if (in.m_stride < ms.max_m) return "m_stride is below the batch's largest m (" + std::to_string(ms.max_m) + ")";
+    return std::string();
+  }
+  std::string vector_refusal(const Batch &b) const {
+    for (size_t i = 0; in.proof_lens && i < b.B; i++) {
+      const IngestMixedRow &row = b.mixed_shape.rows[i];
+      const char *field = (uint64_t)in.proof_lens[i] != row.proof_len ? "proof_lens" : (in.m[i] != row.m ? "m" : nullptr);
+      if (field) return std::string(field) + "[" + std::to_string(i) + "] differs from the batch's shape: a refill keeps the shape of the upload";
+    }
+    return std::string();
+  }
+  bool fits(const Batch &b) const {
+    const Batch::MixedShape &ms = b.mixed_shape;
+    const size_t n = b.B;
+    return ms.rows.size() == n && b.mixed_table.n >= n && b.bytes.n >= ms.proof_bytes + (size_t)b.sum_m * 32 + BPP_BYTES_SLACK &&
+           b.minvals.n >= b.sum_m && (uint64_t)ms.rows[n - 1].minval_idx + ms.rows[n - 1].m == b.sum_m &&
+           (uint64_t)ms.rows[n - 1].proof_off + ms.rows[n - 1].proof_len == ms.proof_bytes;
+  }
+  Refill args(Batch &b, const ParamShape &P, const uint32_t *count_dev, const uint8_t *live_dev) const {
+    return refill_mixed_args(in, P, (uint8_t)b.refill_shape.t0, b.mixed_table.p, b.B, b.mixed_shape.proof_bytes, b.sum_m, b.bytes.p, b.minvals.p,
+                             b.seeds.p, b.d_defer.p, b.d_desc.p, b.status0.p, b.status.p, reinterpret_cast<uint32_t *>(b.masks.p), b.refill_red.p,
+                             count_dev, live_dev, b.refill_mask.p);
+  }
+  static auto kernel(bool masked) { return masked ? k_refill_mixed<true> : k_refill_mixed<false>; }
+};
+
+// the driver of every refill call.  Everything is refused before the tail.
+template <class Form, class In>
+int batch_refill_locked(bpp_ctx *ctx, uint64_t batch, const In *in, const uint32_t *count_dev, const uint8_t *live_dev, bpp_device_refill *record_dev,
+                        uint64_t *ticket, bool with_states = false, const uint8_t *item_states_dev = nullptr) {
   try {
     auto it = ctx->batches.find(batch);
     if (it == ctx->batches.end()) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown batch handle");
     if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
     Batch &b = *it->second;
-    const Batch::MixedShape &ms = b.mixed_shape;
-    if (!b.mixed || !b.mixed_table.p || ms.rows.empty() || b.ext_challenges || b.want_states)
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT,
-                  "the batch cannot be refilled from a mixed batch: only a batch that bpp_batch_upload_mixed_device packed on the device records "
-                  "its shape vector (not its staged fall-back, the host mixed form, a packed or item batch, caller-side challenges or a batch "
-                  "that hands out states)");
-    const Batch::RefillShape &sh = b.refill_shape;
+    const Form form{*in};
+    if (!Form::takes(b) || b.ext_challenges || b.want_states) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, Form::cannot());
     if (count_dev && live_dev) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "count_dev and live_dev: a refill takes a live count or a live mask, not both");
-    const std::string states_refusal = refill_item_states_refusal(ctx, b, with_states, item_states_dev, true);
-    if (!states_refusal.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, states_refusal);
-    const struct {
-      const char *name;
-      bool same;
-    } shape[] = {{"n_items", (uint64_t)in->n_items == sh.n_items},
-                 {"seed_nonces32", (in->seed_nonces32 != nullptr) == sh.nonces},
-                 {"seed_present", (in->seed_present != nullptr) == ms.seed_present},
-                 {"min_values", (in->min_values != nullptr) == sh.min_values},
-                 {"min_present", (in->min_present != nullptr) == sh.min_present}};
-    for (const auto &f : shape)
-      if (!f.same) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(f.name) + " differs from the batch's shape: a refill keeps the shape of the upload");
-    if ((in->proof_lens != nullptr) != (in->m != nullptr))
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proof_lens and m: give both (they must repeat the batch's vectors) or neither (the batch's own)");
-    const struct {
-      const char *name;
-      const void *p;
-    } host_arrays[] = {{"proof_lens", in->proof_lens}, {"m", in->m}};
-    for (const auto &a : host_arrays) {
-      if (!a.p) continue;
-      const int kind = device_pointer_kind(ctx->device, a.p);
-      if (kind == BPP_PTR_THIS_DEVICE || kind == BPP_PTR_OTHER_DEVICE)
-        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + " is device memory: it names the batch's shape and stays host memory in every form");
-    }
-    if (in->proof_stride < ms.max_proof_len)
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proof_stride is below the batch's largest proof_len (" + std::to_string(ms.max_proof_len) + ")");
-    if (in->m_stride < ms.max_m) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m_stride is below the batch's largest m (" + std::to_string(ms.max_m) + ")");
-    if (in->transcript_state || in->transcript_label)
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, with_states ? "transcript_state / transcript_label must be null: item i is verified under row i of item_states203_dev"
-                                                             : "transcript_state / transcript_label must be null: a refilled batch keeps its transcript");
-    if (!in->proofs || !in->commitments32) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proofs / commitments32: null");
-    const std::string refusal = refill_pointer_refusal(ctx, in->proofs, in->commitments32, in->min_values, in->min_present, in->seed_nonces32,
-                                                       in->seed_present, record_dev, count_dev, live_dev);
+    std::string refusal = refill_item_states_refusal(ctx, b, with_states, item_states_dev, Form::mixed);
+    if (refusal.empty()) refusal = form.shape_refusal(ctx, b);
+    if (refusal.empty() && (in->transcript_state || in->transcript_label))
+      refusal = with_states ? "transcript_state / transcript_label must be null: item i is verified under row i of item_states203_dev"
+                            : "transcript_state / transcript_label must be null: a refilled batch keeps its transcript";
+    if (refusal.empty() && (!in->proofs || !in->commitments32)) refusal = "proofs / commitments32: null";
+    if (refusal.empty())
+      refusal = refill_pointer_refusal(ctx, in->proofs, in->commitments32, in->min_values, in->min_present, in->seed_nonces32, in->seed_present,
+                                       record_dev, count_dev, live_dev);
+    if (refusal.empty()) refusal = form.vector_refusal(b);
     if (!refusal.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, refusal);
-    const size_t n = b.B;
-    for (size_t i = 0; in->proof_lens && i < n; i++) {
-      const char *field = (uint64_t)in->proof_lens[i] != ms.rows[i].proof_len ? "proof_lens" : (in->m[i] != ms.rows[i].m ? "m" : nullptr);
-      if (field)
-        return fail(ctx, BPP_ERR_INVALID_ARGUMENT,
-                    std::string(field) + "[" + std::to_string(i) + "] differs from the batch's shape: a refill keeps the shape of the upload");
-    }
     Params &P = *b.params;
+    const size_t n = b.B;
+    const bool nonces = b.refill_shape.nonces;
     // what the kernel writes, against what the upload allocated (the shape says they fit; a kernel is not launched on less)
-    if (ms.rows.size() != n || b.mixed_table.n < n || b.bytes.n < ms.proof_bytes + (size_t)b.sum_m * 32 + BPP_BYTES_SLACK || b.minvals.n < b.sum_m ||
-        (sh.nonces && b.seeds.n < n * 32) || b.d_desc.n < n || b.status0.n < n || b.status.n < n || b.masks.n < n * (size_t)P.t * 32 ||
-        (uint64_t)ms.rows[n - 1].minval_idx + ms.rows[n - 1].m != b.sum_m || (uint64_t)ms.rows[n - 1].proof_off + ms.rows[n - 1].proof_len != ms.proof_bytes)
+    if (!form.fits(b) || (nonces && b.seeds.n < n * 32) || b.d_desc.n < n || b.status0.n < n || b.status.n < n || b.masks.n < n * (size_t)P.t * 32)
       throw EngineError{BPP_ERR_ENGINE, "refill: the batch's buffers do not fit its recorded shape"};
     const ParamShape shape_p{P.n_bits, P.m_max, P.t};
-    refill_enqueue_tail(ctx, b, sh.nonces, count_dev, live_dev, record_dev, ticket, item_states_dev, [&](hipStream_t s, bool masked) {
-      const RefillMixed r = refill_mixed_args(*in, shape_p, (uint8_t)sh.t0, b.mixed_table.p, n, ms.proof_bytes, b.sum_m, b.bytes.p, b.minvals.p,
-                                              b.seeds.p, b.d_defer.p, b.d_desc.p, b.status0.p, b.status.p, reinterpret_cast<uint32_t *>(b.masks.p),
-                                              b.refill_red.p, count_dev, live_dev, b.refill_mask.p);
-      const dim3 refill_grid((uint32_t)cdiv((uint32_t)n, BPP_INGEST_BLOCK / BPP_INGEST_LANES));
-      if (masked) hipLaunchKernelGGL(k_refill_mixed<BPP_REFILL_MIXED_MASKED>, refill_grid, dim3(BPP_INGEST_BLOCK), 0, s, r);
-      else hipLaunchKernelGGL(k_refill_mixed<BPP_REFILL_MIXED_PLAIN>, refill_grid, dim3(BPP_INGEST_BLOCK), 0, s, r);
+    refill_enqueue_tail(ctx, b, nonces, count_dev, live_dev, record_dev, ticket, item_states_dev, [&](hipStream_t s, bool masked) {
+      const Refill r = form.args(b, shape_p, count_dev, live_dev);
+      hipLaunchKernelGGL(Form::kernel(masked), dim3((uint32_t)cdiv((uint32_t)n, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, r);
     });
     return BPP_OK;
   }
@@ -4104,25 +4046,25 @@ int bpp_verdict_result(const bpp_device_verdict *host_copy, bpp_shard_result *ou
 // (no gate, as bpp_verify_enqueue)
 int bpp_batch_refill_enqueue(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev, bpp_device_refill *record_dev, uint64_t *ticket) {
   BPP_ENTRY(ctx);
-  return batch_refill_locked(ctx, batch, in_dev, nullptr, nullptr, record_dev, ticket);
+  return batch_refill_locked<PackedRefill>(ctx, batch, in_dev, nullptr, nullptr, record_dev, ticket);
 }
 
 int bpp_batch_refill_enqueue_count(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev, const uint32_t *count_dev,
                                    bpp_device_refill *record_dev, uint64_t *ticket) {
   BPP_ENTRY(ctx);
-  return batch_refill_locked(ctx, batch, in_dev, count_dev, nullptr, record_dev, ticket);
+  return batch_refill_locked<PackedRefill>(ctx, batch, in_dev, count_dev, nullptr, record_dev, ticket);
 }
 
 int bpp_batch_refill_enqueue_live(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev, const uint8_t *live_dev,
                                   bpp_device_refill *record_dev, uint64_t *ticket) {
   BPP_ENTRY(ctx);
-  return batch_refill_locked(ctx, batch, in_dev, nullptr, live_dev, record_dev, ticket);
+  return batch_refill_locked<PackedRefill>(ctx, batch, in_dev, nullptr, live_dev, record_dev, ticket);
 }
 
 int bpp_batch_refill_enqueue_mixed(bpp_ctx *ctx, uint64_t batch, const bpp_mixed_batch *in_dev, const uint32_t *count_dev, const uint8_t *live_dev,
                                    bpp_device_refill *record_dev, uint64_t *ticket) {
   BPP_ENTRY(ctx);
-  return batch_refill_mixed_locked(ctx, batch, in_dev, count_dev, live_dev, record_dev, ticket);
+  return batch_refill_locked<MixedRefill>(ctx, batch, in_dev, count_dev, live_dev, record_dev, ticket);
 }
 
 // ---- per-item transcripts (item_states.h): the refills of a batch the *_transcripts uploads made, and the enqueue that hands the
@@ -4130,14 +4072,14 @@ int bpp_batch_refill_enqueue_mixed(bpp_ctx *ctx, uint64_t batch, const bpp_mixed
 int bpp_batch_refill_enqueue_transcripts(bpp_ctx *ctx, uint64_t batch, const bpp_packed_batch *in_dev, const uint8_t *item_states203_dev,
                                          const uint32_t *count_dev, const uint8_t *live_dev, bpp_device_refill *record_dev, uint64_t *ticket) {
   BPP_ENTRY(ctx);
-  return batch_refill_locked(ctx, batch, in_dev, count_dev, live_dev, record_dev, ticket, true, item_states203_dev);
+  return batch_refill_locked<PackedRefill>(ctx, batch, in_dev, count_dev, live_dev, record_dev, ticket, true, item_states203_dev);
 }
 
 int bpp_batch_refill_enqueue_mixed_transcripts(bpp_ctx *ctx, uint64_t batch, const bpp_mixed_batch *in_dev, const uint8_t *item_states203_dev,
                                                const uint32_t *count_dev, const uint8_t *live_dev, bpp_device_refill *record_dev,
                                                uint64_t *ticket) {
   BPP_ENTRY(ctx);
-  return batch_refill_mixed_locked(ctx, batch, in_dev, count_dev, live_dev, record_dev, ticket, true, item_states203_dev);
+  return batch_refill_locked<MixedRefill>(ctx, batch, in_dev, count_dev, live_dev, record_dev, ticket, true, item_states203_dev);
 }
 
 int bpp_verify_enqueue_states(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_first, size_t n_groups, size_t chunk, const int *actions,

@@ -155,8 +155,8 @@ void model(const bpp_packed_batch &pk, const ParamShape &P, Outcome &o) {
     std::unique_ptr<uint64_t[]> minvals(new uint64_t[n * pk.m]);
     memset(bytes.get(), 0xcd, bytes_total + BPP_BYTES_SLACK);
     uint32_t res[BPP_ING_RES_WORDS];
-    const IngestPacked a = ingest_args(pk, P, bytes.get(), minvals.get(), seeds.get(), info.get(), res);
-    ingest_run_host(a);
+    const Ingest a = ingest_args(pk, P, bytes.get(), minvals.get(), seeds.get(), info.get(), res);
+    ingest_run_host<false>(a);
     if (res[BPP_ING_RES_DIFFERS]) {
       o.fallback = true;
       return;

@@ -1,5 +1,6 @@
-// Sanitizer harness (CPU test suite only): the one-item routines of ingest_mixed.h -- what k_ingest_mixed runs per proof of a batch
-// of mixed aggregation factors that lies in device memory -- the host prelude and the plan, run on the host over a corpus and held
+// Sanitizer harness (CPU test suite only): the one-item routines of ingest.h in their mixed form -- what k_ingest_mixed runs per proof
+// of a batch of mixed aggregation factors that lies in device memory -- the host prelude and the plan (ingest_mixed.h), run on the
+// host over a corpus and held
 // to upload_pass_a + upload_pass_b on the equivalent item array (upload_mixed_as_items): for every case {code, message text, index}
 // are equal, and on success bytes[], minvals, seeds, every ProofDesc field, rounds_bad, defer and the plan's sums and maxima.
 // Built with  g++ -fsanitize=address,undefined  into an executable that tests/test_ingest_mixed_host.py runs.
@@ -225,13 +226,13 @@ void model(const bpp_mixed_batch &mx, const ParamShape &P, Outcome &o) {
     memset(bytes.get(), 0xcd, bytes_total + BPP_BYTES_SLACK);
     memset(seeds.get(), 0, mx.seed_nonces32 ? n * 32 : 1);
     uint32_t res[BPP_ING_RES_WORDS];
-    const IngestMixed a = ingest_mixed_args(mx, P, pre, rows.get(), bytes.get(), minvals.get(), seeds.get(), info.get(), res);
-    ingest_mixed_run_host(a);
+    const Ingest a = ingest_mixed_args(mx, P, pre, rows.get(), bytes.get(), minvals.get(), seeds.get(), info.get(), res);
+    ingest_run_host<true>(a);
     if (res[BPP_ING_RES_DIFFERS]) {
       o.fallback = true;
       return;
     }
-    ingest_mixed_finish_plan(mx, P, pre, res, ingest_mixed_needs_info(mx, res) ? info.get() : nullptr, o.pl);
+    ingest_mixed_finish_plan(mx, P, pre, res, ingest_needs_info(mx, res) ? info.get() : nullptr, o.pl);
     o.bytes.assign(bytes.get(), bytes.get() + bytes_total + BPP_BYTES_SLACK);
     o.minvals.assign(minvals.get(), minvals.get() + pre.sum_m);
     if (mx.seed_nonces32) o.seeds.assign(seeds.get(), seeds.get() + n * 32);
@@ -565,6 +566,77 @@ int main() {
       all = agree(c.mx, P);
     }
     EXPECT("mutations", all);
+  }
+  {  // packed is the mixed form whose row is arithmetic: over a uniform batch (proof_stride > proof_len, m_stride = m) the run by the
+     // table the prelude makes and the run by arithmetic leave the same bytes, promises, nonces, info, result words and plan -- with a
+     // promise above the capacity and an absent nonce, and with a non-canonical scalar, whose finding both must throw
+    bool all = true;
+    for (uint32_t m : {1u, 2u})
+      for (bool bad : {false, true}) {
+        std::vector<Item> items;
+        for (size_t i = 0; i < 7; i++) {
+          Item it = good(m, P8.n_bits, P8.t);
+          it.nonce = i != 4;
+          it.minv = {i == 2 ? 256u : 255u};
+          it.present = {1};
+          items.push_back(it);
+        }
+        if (bad) group_order(&items[3].proof[1]);
+        Case c(items, NONCE_FLAGS, true, 8, m);
+        const size_t n = c.n, bytes_len = n * c.lens[0] + n * m * 32 + BPP_BYTES_SLACK;
+        bpp_packed_batch pk;
+        memset(&pk, 0, sizeof(pk));
+        pk.n_items = n;
+        pk.proofs = c.mx.proofs;
+        pk.proof_len = c.lens[0];
+        pk.proof_stride = c.mx.proof_stride;
+        pk.m = m;
+        pk.commitments32 = c.mx.commitments32;
+        pk.min_values = c.mx.min_values;
+        pk.min_present = c.mx.min_present;
+        pk.seed_nonces32 = c.mx.seed_nonces32;
+        pk.seed_present = c.mx.seed_present;
+        pk.transcript_label = c.mx.transcript_label;
+        pk.label_len = c.mx.label_len;
+        struct Run {
+          std::vector<uint8_t> bytes, seeds, info;
+          std::vector<uint64_t> minvals;
+          uint32_t res[BPP_ING_RES_WORDS];
+          Outcome o;
+        } rows, arith;
+        for (Run *r : {&rows, &arith}) {
+          r->bytes.assign(bytes_len, 0xcd);
+          r->seeds.assign(n * 32, 0xcd);
+          r->info.assign(n, 0xcd);
+          r->minvals.assign(n * m, 0xcdcdcdcdcdcdcdcdull);
+        }
+        IngestMixedPrelude pre;
+        all = all && pk.proof_stride > pk.proof_len && ingest_mixed_host_prelude(c.mx, P8, pre) && pre.h == n && ingest_host_prelude(pk, P8);
+        if (!all) break;
+        ingest_run_host<true>(ingest_mixed_args(c.mx, P8, pre, pre.rows.data(), rows.bytes.data(), rows.minvals.data(), rows.seeds.data(),
+                                                rows.info.data(), rows.res));
+        ingest_run_host<false>(ingest_args(pk, P8, arith.bytes.data(), arith.minvals.data(), arith.seeds.data(), arith.info.data(), arith.res));
+        for (Run *r : {&rows, &arith}) {
+          const uint8_t *info = ingest_needs_info(pk, r->res) ? r->info.data() : nullptr;
+          try {
+            if (r == &rows) ingest_mixed_finish_plan(c.mx, P8, pre, r->res, info, r->o.pl);
+            else ingest_finish_plan(pk, P8, r->res, info, r->o.pl);
+          } catch (const ProofErr &e) {
+            r->o.code = e.code;
+            r->o.msg = e.msg;
+            r->o.index = e.index;
+          }
+          r->o.bytes = r->bytes;
+          r->o.seeds = r->seeds;
+          r->o.minvals = r->minvals;
+        }
+        const int want_code = (bad || m > 1) ? BPP_ERR_INVALID_ARGUMENT : 0;  // (m = 2: the nonce of item 0 is a finding of its own)
+        all = all && rows.info == arith.info && memcmp(rows.res, arith.res, sizeof(rows.res)) == 0 && rows.bytes == arith.bytes &&
+              rows.minvals == arith.minvals && rows.seeds == arith.seeds && rows.o.code == want_code && arith.o.code == want_code &&
+              rows.o.msg == arith.o.msg && rows.o.index == arith.o.index && rows.res[BPP_ING_RES_ANY_PROMISE] == 1 &&
+              (want_code || same_plan(rows.o, arith.o, n));
+      }
+    EXPECT("uniform_rows_equal_packed", all);
   }
   printf("%d comparisons\n", checked);
   if (fails) {

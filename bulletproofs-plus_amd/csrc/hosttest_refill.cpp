@@ -140,9 +140,9 @@ struct ModelBatch {
     memset(&record, fill, sizeof(record));
   }
   void refill(const bpp_packed_batch &pk, const ParamShape &P, uint8_t t0) {
-    const RefillPacked r = refill_args(pk, P, t0, bytes.get(), minvals.get(), seeds.get(), defer.get(), desc.get(), status0.get(), status.get(),
+    const Refill r = refill_args(pk, P, t0, bytes.get(), minvals.get(), seeds.get(), defer.get(), desc.get(), status0.get(), status.get(),
                                        masks.get(), red);
-    refill_run_host(r, &state, &record);
+    refill_run_host<false>(r, &state, &record);
   }
   // everything a refill writes, as one string of bytes (flags of desc only: the other fields are the shape's)
   std::vector<uint8_t> outputs(bool nonces) const {
@@ -188,8 +188,8 @@ bool hold(const bpp_packed_batch &pk, const ParamShape &P, uint8_t t0, bool shap
   bpp_packed_batch plain = pk;
   plain.transcript_label = (const uint8_t *)"harness";
   plain.label_len = 7;
-  const IngestPacked a = ingest_args(plain, P, ref.bytes.get(), ref.minvals.get(), ref.seeds.get(), info.get(), res);
-  ingest_run_host(a);
+  const Ingest a = ingest_args(plain, P, ref.bytes.get(), ref.minvals.get(), ref.seeds.get(), info.get(), res);
+  ingest_run_host<false>(a);
   bool foreign_any = false, finding_any = false;
   std::vector<uint8_t> stopped(n, 0);
   for (size_t i = 0; i < n; i++) {

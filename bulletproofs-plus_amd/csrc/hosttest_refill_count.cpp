@@ -1,6 +1,6 @@
 // Sanitizer harness (CPU test suite only): a refill with a LIVE COUNT (bpp_batch_refill_enqueue_count).
 //
-// 1. The one-lane host model of the refill kernels (refill.h: refill_run_host with RefillPacked::count) is held to what a fresh
+// 1. The one-lane host model of the refill kernels (refill.h: refill_run_host with Refill::count) is held to what a fresh
 //    device upload makes of the FIRST c ITEMS of the same arrays -- ingest_run_host + ingest_finish_plan of ingest.h -- over the
 //    corpus of hosttest_refill.cpp's kinds (edge scalars in every field, two findings, foreign first bytes, nonces at m = 1 and
 //    m = 2, promises at the capacity, a foreign degree, random mutations), for c in {0, 1, N - 1, N, N + 1}, the findings lying on
@@ -193,9 +193,9 @@ struct ModelBatch {
     memset(&record, fill, sizeof(record));
   }
   void refill(const bpp_packed_batch &pk, const ParamShape &P, uint8_t t0, const uint32_t *count) {
-    const RefillPacked r = refill_args(pk, P, t0, bytes.get(), minvals.get(), seeds.get(), defer.get(), desc.get(),
+    const Refill r = refill_args(pk, P, t0, bytes.get(), minvals.get(), seeds.get(), defer.get(), desc.get(),
                                        status0.get(), status.get(), masks.get(), red, count);
-    refill_run_host(r, &state, &record, &live);
+    refill_run_host<false>(r, &state, &record, &live);
   }
 };
 
@@ -289,8 +289,8 @@ bool hold_count(const Source &src, const ParamShape &P, uint8_t t0, uint32_t c, 
   bpp_packed_batch plain = first.pk;
   plain.transcript_label = (const uint8_t *)"harness";
   plain.label_len = 7;
-  const IngestPacked a = ingest_args(plain, P, ref.bytes.get(), ref.minvals.get(), ref.seeds.get(), info.get(), res);
-  ingest_run_host(a);
+  const Ingest a = ingest_args(plain, P, ref.bytes.get(), ref.minvals.get(), ref.seeds.get(), info.get(), res);
+  ingest_run_host<false>(a);
   bool foreign_any = false, finding_any = false;
   std::vector<uint8_t> stopped(live, 0);
   for (size_t i = 0; i < live; i++) {

@@ -1,6 +1,6 @@
 // Sanitizer harness (CPU test suite only): a refill under a per-item LIVE MASK (bpp_batch_refill_enqueue_live).
 //
-// 1. The one-lane host model of the refill kernels (refill.h: refill_run_host with RefillPacked::mask) is held to what a fresh device
+// 1. The one-lane host model of the refill kernels (refill.h: refill_run_host with Refill::mask) is held to what a fresh device
 //    upload makes of the LIVE ITEMS ALONE, in slot order -- ingest_run_host + ingest_finish_plan of ingest.h on the compacted arrays
 //    -- over the corpus of hosttest_refill_count.cpp's kinds, under the masks: all dead, all live, one live item at 0 / at N - 1,
 //    alternating (both phases), a dead run in the middle, and the byte values 2 and 255 as "live"; findings and foreign first bytes
@@ -224,9 +224,9 @@ struct ModelBatch {
   }
   // mask_bytes: exactly as many bytes as the caller's mask holds (null: no mask)
   void refill(const bpp_packed_batch &pk, const ParamShape &P, uint8_t t0, const uint8_t *mask_bytes) {
-    const RefillPacked r = refill_args(pk, P, t0, bytes.get(), minvals.get(), seeds.get(), defer.get(), desc.get(), status0.get(),
+    const Refill r = refill_args(pk, P, t0, bytes.get(), minvals.get(), seeds.get(), defer.get(), desc.get(), status0.get(),
                                        status.get(), masks.get(), red, nullptr, mask_bytes, mask.get());
-    refill_run_host(r, &state, &record, &live);
+    refill_run_host<false>(r, &state, &record, &live);
   }
 };
 
@@ -330,8 +330,8 @@ bool hold_mask(const Source &src, const ParamShape &P, uint8_t t0, const std::ve
   bpp_packed_batch plain = first.pk;
   plain.transcript_label = (const uint8_t *)"harness";
   plain.label_len = 7;
-  const IngestPacked a = ingest_args(plain, P, ref.bytes.get(), ref.minvals.get(), ref.seeds.get(), info.get(), res);
-  ingest_run_host(a);
+  const Ingest a = ingest_args(plain, P, ref.bytes.get(), ref.minvals.get(), ref.seeds.get(), info.get(), res);
+  ingest_run_host<false>(a);
   bool foreign_any = false, finding_any = false;
   std::vector<uint8_t> stopped(L, 0);
   for (size_t k = 0; k < L; k++) {

@@ -1,10 +1,10 @@
 // Sanitizer harness (CPU test suite only): a refill of a batch of MIXED aggregation factors (bpp_batch_refill_enqueue_mixed), plain,
 // with a live count and under a live mask.
 //
-// The one-lane host model of the refill kernels (refill_mixed.h: refill_mixed_run_host) runs over a batch whose shape vector
+// The one-lane host model of the refill kernels (refill.h: refill_run_host<true>) runs over a batch whose shape vector
 // (proof_lens[i], m[i]) comes from a sound corpus, and is held to what a fresh device upload makes of the rows in question -- all of
-// them, the first c, the live ones alone in slot order: ingest_mixed_host_prelude + ingest_mixed_run_host + ingest_mixed_finish_plan
-// of ingest_mixed.h over a batch of those rows:
+// them, the first c, the live ones alone in slot order: ingest_mixed_host_prelude + ingest_run_host<true> + ingest_mixed_finish_plan
+// of ingest.h / ingest_mixed.h over a batch of those rows:
 //   record and state   what the upload throws, its index k mapped to the slot of the k-th live row; FALLBACK for a foreign first byte
 //                      at a live row, before any finding; BPP_REFILL_COUNT for a count beyond the batch; clean otherwise, whatever
 //                      lies at dead rows
@@ -28,7 +28,7 @@
 #include <string>
 #include <vector>
 
-#include "refill_mixed.h"
+#include "refill.h"
 
 #if defined(__SANITIZE_ADDRESS__)
 #include <sanitizer/asan_interface.h>
@@ -245,9 +245,15 @@ struct ModelBatch {
     bpp_mixed_batch bare = mx;
     bare.proof_lens = nullptr;
     bare.m = nullptr;
-    const RefillMixed r = refill_mixed_args(bare, P, t0, rows.get(), n, proof_bytes, sum_m, bytes.get(), minvals.get(), seeds.get(), defer.get(),
+    const Refill r = refill_mixed_args(bare, P, t0, rows.get(), n, proof_bytes, sum_m, bytes.get(), minvals.get(), seeds.get(), defer.get(),
                                             desc.get(), status0.get(), status.get(), masks.get(), red, count, mask_bytes, mask.get());
-    refill_mixed_run_host(r, &state, &record, &live);
+    refill_run_host<true>(r, &state, &record, &live);
+  }
+  // ... of a batch whose rows are uniform, by arithmetic: no table
+  void refill_packed(const bpp_packed_batch &pk, const ParamShape &P, uint8_t t0, const uint32_t *count, const uint8_t *mask_bytes) {
+    const Refill r = refill_args(pk, P, t0, bytes.get(), minvals.get(), seeds.get(), defer.get(), desc.get(), status0.get(), status.get(),
+                                 masks.get(), red, count, mask_bytes, mask.get());
+    refill_run_host<false>(r, &state, &record, &live);
   }
 };
 
@@ -369,8 +375,8 @@ bool hold(const std::vector<Item> &shape, const std::vector<Item> &items, const 
   memset(ref.seeds.get(), 0, 32 * L);
   std::unique_ptr<uint8_t[]> info(new uint8_t[L]);
   uint32_t res[BPP_ING_RES_WORDS];
-  const IngestMixed a = ingest_mixed_args(fmx, P, fpre, ref.rows.get(), ref.bytes.get(), ref.minvals.get(), ref.seeds.get(), info.get(), res);
-  ingest_mixed_run_host(a);
+  const Ingest a = ingest_mixed_args(fmx, P, fpre, ref.rows.get(), ref.bytes.get(), ref.minvals.get(), ref.seeds.get(), info.get(), res);
+  ingest_run_host<true>(a);
   bool foreign_any = false, finding_any = false;
   std::vector<uint8_t> stopped(L, 0);
   for (size_t k = 0; k < L; k++) {
@@ -559,6 +565,78 @@ int main() {
       all = hold(sh, items, P, form, (uint32_t)(rng() % (n + 2)), mk);
     }
     EXPECT("mutations", all);
+  }
+  {  // packed is the mixed form whose row is arithmetic: a uniform batch (m = 2 everywhere, proof_stride > proof_len, m_stride = m)
+     // refilled by its table and by arithmetic, plain, with a count c < N and under a mask, leaves the same slot bytes, defer, flags,
+     // state word and record -- with a refused slot (a non-canonical scalar), with and without a foreign first byte, and with dead
+     // slots whose sources are unreadable
+    const size_t n = 9;
+    auto uniform = [&] {
+      std::vector<Item> v = pattern(n, 8, 1);
+      for (size_t i = 0; i < n; i++) {
+        v[i].m = 2;
+        v[i].proof = make_proof(1, 4);
+        v[i].nonce = false;
+        v[i].commits.resize(64, (uint8_t)(i + 1));
+      }
+      return v;
+    };
+    const std::vector<Item> ushape = uniform();
+    const Rows up(ushape, n, n, {}, false, 8, 2);
+    IngestMixedPrelude pre;
+    bool all = ingest_mixed_host_prelude(up.mx, P8, pre) && pre.h == n;
+    for (bool foreign : {false, true})
+      for (Form form : {PLAIN, COUNT, MASK}) {
+        std::vector<Item> items = uniform();
+        group_order(&items[4].proof[1]);
+        items[0].minv = {1, 256};  // (a promise above the capacity, taken)
+        items[0].present = {1};
+        if (foreign) items[2].proof[0] = 2;
+        const uint32_t count = 5;
+        std::vector<uint8_t> mask(n), dead(n, 0);
+        for (size_t i = 0; i < n; i++) {
+          mask[i] = i % 2 == 0 ? (uint8_t)(1 + i) : 0;
+          dead[i] = form == MASK ? !mask[i] : (form == COUNT ? i >= count : 0);
+        }
+        size_t end = n;
+        while (end && dead[end - 1]) end--;
+        const Rows src(items, end, n, dead, true, 16, 2);
+        bpp_packed_batch pk;
+        memset(&pk, 0, sizeof(pk));
+        pk.n_items = n;
+        pk.proofs = src.mx.proofs;
+        pk.proof_len = src.lens[0];
+        pk.proof_stride = src.mx.proof_stride;
+        pk.m = 2;
+        pk.commitments32 = src.mx.commitments32;
+        pk.min_values = src.mx.min_values;
+        pk.min_present = src.mx.min_present;
+        pk.seed_nonces32 = src.mx.seed_nonces32;
+        pk.seed_present = src.mx.seed_present;
+        std::unique_ptr<uint32_t> count_word(new uint32_t(count));
+        const uint32_t *cw = form == COUNT ? count_word.get() : nullptr;
+        const uint8_t *mw = form == MASK ? mask.data() : nullptr;
+        ModelBatch rows(pre, P8, 0xcd), arith(pre, P8, 0xcd);
+        rows.refill(src.mx, P8, 1, cw, mw);
+        arith.refill_packed(pk, P8, 1, cw, mw);
+        checked++;
+        bool same = pk.proof_stride > pk.proof_len && memcmp(rows.bytes.get(), arith.bytes.get(), rows.bytes_total + BPP_BYTES_SLACK) == 0 &&
+                    memcmp(rows.minvals.get(), arith.minvals.get(), (rows.sum_m + 1) * 8) == 0 && memcmp(rows.seeds.get(), arith.seeds.get(), 32 * n + 1) == 0 &&
+                    memcmp(rows.defer.get(), arith.defer.get(), n + 1) == 0 && memcmp(rows.mask.get(), arith.mask.get(), n + 1) == 0 &&
+                    memcmp(rows.status.get(), arith.status.get(), (n + 1) * 4) == 0 && memcmp(rows.status0.get(), arith.status0.get(), (n + 1) * 4) == 0 &&
+                    memcmp(rows.masks.get(), arith.masks.get(), (n * (size_t)P8.t * 8 + 1) * 4) == 0 && rows.state == arith.state && rows.live == arith.live &&
+                    memcmp(&rows.record, &arith.record, sizeof(rows.record)) == 0 && !arith.red[0] && !arith.red[1];
+        for (size_t i = 0; i < n && same; i++) same = rows.desc[i].flags == arith.desc[i].flags;
+        // and the outcome is the one the case is about: the fall-back before the finding at slot 4, slot 4 and every dead slot sanitised
+        const uint32_t want = BPP_REFILL_WRITTEN | (foreign ? BPP_REFILL_FALLBACK : BPP_REFILL_FINDING);
+        same = same && arith.record.flags == want && (foreign || (arith.record.index == 4 && arith.record.msg == BPP_ING_PARSING)) &&
+               arith.defer[0] == BPP_DEFER_PROMISE && slot_is_sanitised(arith, 4, 1, 0);
+        for (size_t i = 0; i < n && same; i++)
+          if (dead[i]) same = slot_is_sanitised(arith, i, 1, 0);
+        if (!same) printf("   form %d, foreign %d\n", (int)form, (int)foreign);
+        all = all && same;
+      }
+    EXPECT("uniform_rows_equal_packed", all);
   }
   printf("%d comparisons\n", checked);
   if (fails) {

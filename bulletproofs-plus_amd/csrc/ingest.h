@@ -1,15 +1,24 @@
-// Device side of bpp_batch_upload_packed_device: a packed (homogeneous) batch whose arrays already lie in device memory is
-// checked and packed where it lies.  The layout of such a batch is arithmetic (upload_host.h: upload_plan_packed); what depends
-// on the data is, per item, the first byte of the proof, the canonicity of t + 2 scalars, the minimum-value promises and whether
-// a seed nonce is present.  The one-item routines below restate, in the same order, what upload_check_item / parse_proof do for
-// item i of a packed batch; the host form throws, these return {code, message id}.  Shared by the kernel (k_ingest_packed), by the
-// engine's driver (engine.hip: upload_packed_device) and by the sanitizer harness (hosttest_ingest.cpp), which runs them on the
-// host against upload_pass_a_packed + upload_pass_b_packed.
+// Device side of bpp_batch_upload_packed_device and bpp_batch_upload_mixed_device: a batch whose arrays already lie in device memory
+// is checked and packed where it lies.  What depends on the data is, per item, the first byte of the proof, the canonicity of t + 2
+// scalars, the minimum-value promises and whether a seed nonce is present.  The one-item routines below restate, in the same order,
+// what upload_check_item / parse_proof do for item i; the host form throws, these return {code, message id}.
+//
+// ONE SLOT GEOMETRY, two forms.  Where item i comes from and where it goes is an IngestSlot, and every routine here works on one:
+//   packed (ROWS == false): rows of proof_stride bytes, every item proof_len bytes and m entries, so the slot is arithmetic
+//     (upload_host.h: upload_plan_packed) and no table is loaded;
+//   mixed (ROWS == true): rows of proof_stride bytes and m_stride entries, the used part of every row in the host arrays proof_lens[]
+//     and m[].  The destination is the item form's (upload_pass_a): proofs back to back in item order, then the commitments, then
+//     BPP_BYTES_SLACK zero bytes; promises at the prefix sum of m.  The host computes that and hands over one IngestMixedRow per item
+//     (ingest_mixed.h: the prelude and the plan of this form).
+// Packed is the mixed form whose row is arithmetic.  Shared by the kernels (k_ingest_packed, k_ingest_mixed), by the engine's driver
+// (engine.hip: upload_device_form) and by the sanitizer harnesses (hosttest_ingest.cpp, hosttest_ingest_mixed.cpp), which run the routines on the
+// host against the host packers of upload_host.h.
 //
 // Split of the checks (lowest-index construction finding wins, as in upload_run_parts):
-//   uniform over the batch, host, no proof byte needed: m a power of two and <= m_max, null fields, proof_len / proof_stride,
-//     the 4 GB limits (ingest_host_prelude); rounds_bad and the degree finding from t0 (ingest_finish_plan)
+//   host, no proof byte needed: m a power of two and <= m_max, null fields, lengths and strides, the 4 GB limits (ingest_host_prelude,
+//     ingest_mixed_host_prelude; the mixed form finds h, the lowest index with such a finding, and runs items [0, h) only)
 //   per item, device: a seed nonce with m > 1; the walk of parse_proof; at item 0 the unusable transcript state; the promises
+//   host, behind the run: rounds, rounds_bad and the degree finding from t0 (ingest_finish_plan, ingest_mixed_finish_plan)
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -63,24 +72,65 @@ BPP_HD IngestFinding ingest_finding(uint32_t msg) {
 
 BPP_HD uint32_t ingest_key(uint32_t index, uint32_t msg) { return 0xffffffffu - ((index << 8) | msg); }  // index < 2^24
 
-// the packed batch as the kernel sees it (every array pointer an address in device memory) and where its pieces go
-struct IngestPacked {
+// one row of the mixed form's table: the used lengths of item i and where it goes.  Also the batch's resident table (refill.h)
+struct IngestMixedRow {
+  uint32_t proof_len;   // < 2^32: the size limits
+  uint32_t proof_off;   // prefix sum of proof_len = ProofDesc::proof_off
+  uint32_t minval_idx;  // prefix sum of m = ProofDesc::minval_idx; the commitments go to proof_bytes + 32 * minval_idx
+  uint32_t m;
+};
+
+// the batch as the kernel sees it (every array pointer an address in device memory) and where its pieces go
+struct Ingest {
   const uint8_t *proofs;
-  uint64_t proof_len, proof_stride;
+  uint64_t proof_stride;
   const uint8_t *commitments32;
   const uint64_t *min_values;
   const uint8_t *min_present, *seed_nonces32, *seed_present;
-  uint32_t n_items, m, n_bits;
+  const IngestMixedRow *rows;  // mixed: one per item of the batch; packed: null, and proof_len / m below say it all
+  uint64_t proof_len;          // packed only
+  uint32_t m, m_stride;        // packed only; mixed only
+  uint32_t n_run;              // items [0, n_run) are checked and moved (packed: every item; mixed: h, the host's first finding)
+  uint32_t n_bits;
   uint32_t tr_bad;     // the call's transcript state is unusable (pos >= rate): reported at item 0, after its proof parsed
-  uint8_t *bytes;      // n * proof_len proof bytes, n * m * 32 commitment bytes, BPP_BYTES_SLACK zero bytes
-  uint64_t *minvals;   // n * m
-  uint8_t *seeds;      // n * 32, or null when seed_nonces32 is
-  uint8_t *info;       // n: BPP_ING_INFO_*
+  uint64_t proof_bytes, bytes_total;  // of the WHOLE batch: where the commitments start, where the slack starts
+  uint8_t *bytes;      // proof_bytes, then sum(m) * 32 commitment bytes, then BPP_BYTES_SLACK zero bytes
+  uint64_t *minvals;   // sum(m)
+  uint8_t *seeds;      // 32 per item, or null when seed_nonces32 is
+  uint8_t *info;       // one per item: BPP_ING_INFO_*
   uint32_t *result;    // BPP_ING_RES_WORDS words, zero before the run
 };
 
-BPP_HD bool ingest_seed_present(const IngestPacked &a, size_t i) {
+// where item i comes from and where it goes
+struct IngestSlot {
+  const uint8_t *proof;  // source: the row's first byte (formed, not dereferenced, here)
+  size_t proof_len;      // its used length
+  size_t proof_off;      // destination offset in bytes
+  size_t entry;          // source index of the item's first entry in commitments32 / min_values / min_present
+  uint32_t m;
+  size_t minval_idx;     // destination index of its first promise; its commitments go to proof_bytes + 32 * minval_idx
+};
+
+template <bool ROWS>
+BPP_HD IngestSlot ingest_slot(const Ingest &a, size_t i) {
+  const uint8_t *p = a.proofs + i * (size_t)a.proof_stride;
+  if constexpr (ROWS) {
+    const IngestMixedRow r = a.rows[i];
+    return IngestSlot{p, r.proof_len, r.proof_off, i * (size_t)a.m_stride, r.m, r.minval_idx};
+  } else {
+    return IngestSlot{p, (size_t)a.proof_len, i * (size_t)a.proof_len, i * (size_t)a.m, a.m, i * (size_t)a.m};
+  }
+}
+
+BPP_HD bool ingest_seed_present(const Ingest &a, size_t i) {
   return a.seed_nonces32 && (!a.seed_present || a.seed_present[i]);
+}
+
+// the first byte the batch's proofs are compared with: proof 0's, or 0 (no proof has it) when proof 0 is empty -- which only the
+// mixed form can see: the packed prelude declines proof_len < 1
+template <bool ROWS>
+BPP_HD uint32_t ingest_t0(const Ingest &a) {
+  return ingest_slot<ROWS>(a, 0).proof_len ? (uint32_t)a.proofs[0] : 0u;
 }
 
 // upload_check_item from its first data-dependent check to its last construction error, for item i of a packed batch (`p`:
@@ -116,6 +166,10 @@ BPP_HD IngestFinding ingest_check_item(const uint8_t *p, size_t len, uint32_t m,
 // n bytes from src to dst, shared among `lanes` lanes; neither end is aligned to anything (proof lengths are odd, the caller's
 // base may be at any byte).  On the device the middle goes as whole words of the DESTINATION, each put together from the two
 // aligned source words it straddles: those lie in the same aligned word as a byte of the source, so inside its page.
+// ROW SLACK is therefore never read: sw[w + 1] is read only for a word whose four source bytes all lie inside the n bytes asked for
+// (words = (n - head) / 4: the tail goes byte-wise), and it holds the last of those four, so it is the aligned word of a byte of the
+// row itself -- never a word that starts behind the row.  That holds for the last row of the array as for any other: the at most
+// three bytes of that word beyond the row are shifted out.
 BPP_HD void ingest_copy(uint8_t *dst, const uint8_t *src, size_t n, uint32_t lane, uint32_t lanes) {
 #if defined(__HIP_DEVICE_COMPILE__)
   size_t head = (size_t)((4u - (uint32_t)((uintptr_t)dst & 3u)) & 3u);
@@ -142,21 +196,19 @@ BPP_HD void ingest_zero(uint8_t *dst, size_t n, uint32_t lane, uint32_t lanes) {
   for (size_t k = lane; k < n; k += lanes) dst[k] = 0;
 }
 
-// What `lane` of the `lanes` lanes that share item i moves: proof and commitment bytes to their arithmetic offsets, the promises
-// (0 where not present), the nonce (zero where absent); item 0's lanes also clear the slack behind the last commitment.  Returns
-// this lane's share of the item's info bits.
-BPP_HD uint32_t ingest_item_arrays(const IngestPacked &a, size_t i, uint32_t lane, uint32_t lanes) {
-  const size_t n = a.n_items, proof_bytes = n * (size_t)a.proof_len, bytes_total = proof_bytes + n * (size_t)a.m * 32;
-  ingest_copy(a.bytes + i * (size_t)a.proof_len, a.proofs + i * (size_t)a.proof_stride, (size_t)a.proof_len, lane, lanes);
-  ingest_copy(a.bytes + proof_bytes + 32 * i * (size_t)a.m, a.commitments32 + 32 * i * (size_t)a.m, 32 * (size_t)a.m, lane, lanes);
-  if (i == 0) ingest_zero(a.bytes + bytes_total, BPP_BYTES_SLACK, lane, lanes);
+// What `lane` of the `lanes` lanes that share item i moves: proof and commitment bytes to the slot's offsets, the promises (0 where
+// not present), the nonce (zero where absent); item 0's lanes also clear the slack behind the last commitment.  Every loop is
+// bounded by the slot's own proof_len and m.  Returns this lane's share of the item's info bits.
+BPP_HD uint32_t ingest_item_arrays(const Ingest &a, const IngestSlot &sl, size_t i, uint32_t lane, uint32_t lanes) {
+  ingest_copy(a.bytes + sl.proof_off, sl.proof, sl.proof_len, lane, lanes);
+  ingest_copy(a.bytes + (size_t)a.proof_bytes + 32 * sl.minval_idx, a.commitments32 + 32 * sl.entry, 32 * (size_t)sl.m, lane, lanes);
+  if (i == 0) ingest_zero(a.bytes + (size_t)a.bytes_total, BPP_BYTES_SLACK, lane, lanes);
   uint32_t bits = 0;
-  for (uint32_t j = lane; j < a.m; j += lanes) {
-    const size_t q = i * (size_t)a.m + j;
-    const bool present = a.min_present ? a.min_present[q] != 0 : false;
-    const uint64_t v = (present && a.min_values) ? a.min_values[q] : 0;
+  for (uint32_t j = lane; j < sl.m; j += lanes) {
+    const bool present = a.min_present ? a.min_present[sl.entry + j] != 0 : false;
+    const uint64_t v = (present && a.min_values) ? a.min_values[sl.entry + j] : 0;
     if (present && a.n_bits < 64 && (v >> a.n_bits) > 0) bits |= BPP_ING_INFO_PROMISE;
-    a.minvals[q] = v;
+    a.minvals[sl.minval_idx + j] = v;
   }
   if (a.seeds) {
     if (ingest_seed_present(a, i)) {
@@ -169,33 +221,38 @@ BPP_HD uint32_t ingest_item_arrays(const IngestPacked &a, size_t i, uint32_t lan
   return bits;
 }
 
-// the check of item i and what it adds to the result words, by the item's first lane
-BPP_HD uint32_t ingest_item_check(const IngestPacked &a, size_t i, uint32_t *key_out) {
-  const uint8_t *p = a.proofs + i * (size_t)a.proof_stride;
-  const IngestFinding f = ingest_check_item(p, (size_t)a.proof_len, a.m, ingest_seed_present(a, i), a.tr_bad && i == 0);
+// the check of item i and what it adds to the result words, by the item's first lane.  An empty proof has no first byte to compare
+// (ingest_check_item reports it without reading one).
+BPP_HD uint32_t ingest_item_check(const Ingest &a, const IngestSlot &sl, size_t i, uint32_t t0, uint32_t *key_out) {
+  const IngestFinding f = ingest_check_item(sl.proof, sl.proof_len, sl.m, ingest_seed_present(a, i), a.tr_bad && i == 0);
   *key_out = f.msg ? ingest_key((uint32_t)i, f.msg) : 0u;
-  return (uint32_t)(p[0] ^ a.proofs[0]);
+  return sl.proof_len ? ((uint32_t)sl.proof[0] ^ t0) : 0u;
 }
 
 #if defined(__HIPCC__)
-// BPP_INGEST_LANES lanes per proof (the copies are 700-1100 bytes per item), the item's first lane runs the check.  No lane
-// leaves early: the info bits are folded across an item's lanes with shuffles.
+// BPP_INGEST_LANES lanes per proof (the copies are 700-1100 bytes per item), 256-lane blocks, so four items share a wavefront -- in
+// the mixed form four items of different lengths and aggregation factors.  The item's first lane runs the check.  The lanes of a
+// short item fall through their loops early, and NO lane returns: all 64 reach the width-16 shuffles that fold the info bits across
+// an item's lanes, and the ballots (a lane past n_run with zeros).
 #define BPP_INGEST_LANES 16u
 #define BPP_INGEST_BLOCK 256u
-__global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_ingest_packed(IngestPacked a) {
+template <bool ROWS>
+__device__ __forceinline__ void ingest_kernel_body(const Ingest &a) {
   const size_t gid = (size_t)blockIdx.x * BPP_INGEST_BLOCK + threadIdx.x;
   const size_t i = gid / BPP_INGEST_LANES;
   const uint32_t lane = (uint32_t)(gid % BPP_INGEST_LANES);
-  const bool live = i < a.n_items;
+  const bool live = i < a.n_run;
   uint32_t bits = 0, differs = 0;
   if (live) {
+    const IngestSlot sl = ingest_slot<ROWS>(a, i);
     if (lane == 0) {
+      const uint32_t t0 = ingest_t0<ROWS>(a);
       uint32_t key;
-      differs = ingest_item_check(a, i, &key);
+      differs = ingest_item_check(a, sl, i, t0, &key);
       if (key) atomicMax(&a.result[BPP_ING_RES_FINDING], key);
-      if (i == 0) a.result[BPP_ING_RES_T0] = a.proofs[0];
+      if (i == 0) a.result[BPP_ING_RES_T0] = t0;
     }
-    bits = ingest_item_arrays(a, i, lane, BPP_INGEST_LANES);
+    bits = ingest_item_arrays(a, sl, i, lane, BPP_INGEST_LANES);
   }
   for (uint32_t o = BPP_INGEST_LANES / 2; o; o >>= 1) bits |= (uint32_t)__shfl_xor((int)bits, (int)o, (int)BPP_INGEST_LANES);
   if (live && lane == 0) a.info[i] = (uint8_t)bits;
@@ -207,6 +264,8 @@ __global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_ingest_packed(IngestPacked
     if (pr) atomicOr(&a.result[BPP_ING_RES_ANY_PROMISE], 1u);
   }
 }
+__global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_ingest_packed(Ingest a) { ingest_kernel_body<false>(a); }
+__global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_ingest_mixed(Ingest a) { ingest_kernel_body<true>(a); }
 #endif
 
 }  // namespace bpp
@@ -245,9 +304,9 @@ inline bool ingest_host_prelude(const bpp_packed_batch &pk, const ParamShape &P)
   return true;
 }
 
-inline IngestPacked ingest_args(const bpp_packed_batch &pk, const ParamShape &P, uint8_t *bytes, uint64_t *minvals, uint8_t *seeds,
-                                uint8_t *info, uint32_t *result) {
-  IngestPacked a;
+inline Ingest ingest_args(const bpp_packed_batch &pk, const ParamShape &P, uint8_t *bytes, uint64_t *minvals, uint8_t *seeds, uint8_t *info,
+                          uint32_t *result) {
+  Ingest a;
   memset(&a, 0, sizeof(a));
   a.proofs = pk.proofs;
   a.proof_len = pk.proof_len;
@@ -257,8 +316,10 @@ inline IngestPacked ingest_args(const bpp_packed_batch &pk, const ParamShape &P,
   a.min_present = pk.min_present;
   a.seed_nonces32 = pk.seed_nonces32;
   a.seed_present = pk.seed_present;
-  a.n_items = (uint32_t)pk.n_items;
   a.m = pk.m;
+  a.n_run = (uint32_t)pk.n_items;
+  a.proof_bytes = (uint64_t)pk.n_items * pk.proof_len;
+  a.bytes_total = a.proof_bytes + (uint64_t)pk.n_items * pk.m * 32;
   a.n_bits = P.n_bits;
   a.tr_bad = (pk.transcript_state && pk.transcript_state[200] >= BPP_STROBE_R) ? 1u : 0u;
   a.bytes = bytes;
@@ -270,8 +331,18 @@ inline IngestPacked ingest_args(const bpp_packed_batch &pk, const ParamShape &P,
 }
 
 // does the per-item info have to come back?  Only for the promise findings and for nonces that only some items have
-inline bool ingest_needs_info(const bpp_packed_batch &pk, const uint32_t *res) {
-  return res[BPP_ING_RES_ANY_PROMISE] != 0 || (res[BPP_ING_RES_ANY_SEED] != 0 && pk.seed_present != nullptr);
+template <class Batch>  // bpp_packed_batch or bpp_mixed_batch
+inline bool ingest_needs_info(const Batch &in, const uint32_t *res) {
+  return res[BPP_ING_RES_ANY_PROMISE] != 0 || (res[BPP_ING_RES_ANY_SEED] != 0 && in.seed_present != nullptr);
+}
+
+// throws the run's construction finding, the one of lowest index, if its result words hold one
+inline void ingest_throw_finding(const uint32_t *res) {
+  if (!res[BPP_ING_RES_FINDING]) return;
+  const uint32_t key = 0xffffffffu - res[BPP_ING_RES_FINDING];
+  ProofErr e{ingest_finding(key & 255u).code, ingest_message(key & 255u)};
+  e.index = key >> 8;
+  throw e;
 }
 
 // Behind the run (first bytes all equal): the plan upload_pass_a_packed + upload_pass_b_packed would have made, built
@@ -280,12 +351,7 @@ inline bool ingest_needs_info(const bpp_packed_batch &pk, const uint32_t *res) {
 inline void ingest_finish_plan(const bpp_packed_batch &pk, const ParamShape &P, const uint32_t *res, const uint8_t *info, UploadPlan &pl) {
   const uint8_t t0 = (uint8_t)res[BPP_ING_RES_T0];
   upload_plan_packed(pk, t0, pl, false);  // (pass A's limits come before pass B's findings)
-  if (res[BPP_ING_RES_FINDING]) {
-    const uint32_t key = 0xffffffffu - res[BPP_ING_RES_FINDING];
-    ProofErr e{ingest_finding(key & 255u).code, ingest_message(key & 255u)};
-    e.index = key >> 8;
-    throw e;
-  }
+  ingest_throw_finding(res);
   const size_t n = pk.n_items;
   const uint32_t rounds = pl.packed_rounds, per_dyn = pk.m + 3 + 2 * rounds;
   const uint64_t mn = (uint64_t)pk.m * P.n_bits;
@@ -312,15 +378,18 @@ inline void ingest_finish_plan(const bpp_packed_batch &pk, const ParamShape &P, 
   pl.max_mn = (uint32_t)mn;
 }
 
-// the run itself on the host, one lane per item, reduced as the kernel reduces: the model hosttest_ingest.cpp holds to the host packer
-inline void ingest_run_host(const IngestPacked &a) {
+// the run itself on the host, one lane per item, reduced as the kernel reduces: the model the harnesses hold to the host packers
+template <bool ROWS>
+inline void ingest_run_host(const Ingest &a) {
   for (int w = 0; w < BPP_ING_RES_WORDS; w++) a.result[w] = 0;
-  for (size_t i = 0; i < a.n_items; i++) {
+  for (size_t i = 0; i < a.n_run; i++) {
+    const IngestSlot sl = ingest_slot<ROWS>(a, i);
+    const uint32_t t0 = ingest_t0<ROWS>(a);
     uint32_t key;
-    const uint32_t differs = ingest_item_check(a, i, &key);
+    const uint32_t differs = ingest_item_check(a, sl, i, t0, &key);
     if (key > a.result[BPP_ING_RES_FINDING]) a.result[BPP_ING_RES_FINDING] = key;
-    if (i == 0) a.result[BPP_ING_RES_T0] = a.proofs[0];
-    const uint32_t bits = ingest_item_arrays(a, i, 0, 1);
+    if (i == 0) a.result[BPP_ING_RES_T0] = t0;
+    const uint32_t bits = ingest_item_arrays(a, sl, i, 0, 1);
     a.info[i] = (uint8_t)bits;
     if (differs) a.result[BPP_ING_RES_DIFFERS] |= 1u;
     if (bits & BPP_ING_INFO_SEED) a.result[BPP_ING_RES_ANY_SEED] |= 1u;

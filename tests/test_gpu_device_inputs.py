@@ -249,7 +249,7 @@ def test_secrets_are_wiped_with_the_batch(bpp, packed, engine, batches):
 
 
 # ---- (e) pointer kinds, through bpp_device_pointer_check only: nothing is launched.  (No host address is handed to the two ingest
-# calls here; upload_packed_device_impl in csrc/engine.hip runs every non-null array through the same check before it allocates or
+# calls here; upload_device_form in csrc/engine.hip runs every non-null array through the same check before it allocates or
 # launches anything.)
 def test_pointer_kinds(packed, engine):
     t = torch.zeros(64, dtype=torch.uint8, device="cuda")

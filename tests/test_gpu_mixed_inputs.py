@@ -1,5 +1,6 @@
 """GPU tests of the array form for batches of mixed aggregation factors (bpp_batch_upload_mixed / bpp_verify_batch_mixed and their
-_device forms, csrc/ingest_mixed.h): rows of proof_stride bytes and m_stride entries, the used part of every row in two host arrays.
+_device forms, csrc/ingest.h with the host side in csrc/ingest_mixed.h): rows of proof_stride bytes and m_stride entries, the used
+part of every row in two host arrays.
 Every expectation is the ITEM form (bpp_batch_upload / bpp_verify_batch) on a bpp_verify_item array that points into the same rows:
 the batch's shape, every trace, return codes, message texts, masks and presence.  Proofs come from bpp_prove_batch_mixed
 (tests/test_gpu_prove_mixed.py holds it to the oracle); the arrays reach the device with torch.

@@ -1,5 +1,5 @@
 """GPU tests: a resident batch of MIXED aggregation factors is refilled on the stream (bpp_batch_refill_enqueue_mixed,
-csrc/refill_mixed.h), plain, with a live count and under a per-item live mask.
+csrc/refill.h in its mixed form), plain, with a live count and under a per-item live mask.
 
 The reference in every comparison is a FRESH bpp_batch_upload_mixed_device of the rows in question -- all of them, the first c, the
 live ones alone in slot order, with the group boundaries mapped to the compacted rows and empty groups dropped -- plus

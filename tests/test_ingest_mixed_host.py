@@ -1,6 +1,6 @@
-"""CPU suite: the one-item routines, the host prelude and the plan of csrc/ingest_mixed.h -- what bpp_batch_upload_mixed_device runs
-for a batch of mixed aggregation factors that lies in device memory -- on the host, under AddressSanitizer + UBSan, held to the item
-form of csrc/upload_host.h on the equivalent bpp_verify_item array.
+"""CPU suite: the one-item routines of csrc/ingest.h in their mixed form with the host prelude and the plan of csrc/ingest_mixed.h -- what
+bpp_batch_upload_mixed_device runs for a batch of mixed aggregation factors that lies in device memory -- on the host, under
+AddressSanitizer + UBSan, held to the item form of csrc/upload_host.h on the equivalent bpp_verify_item array.
 
 The harness (csrc/hosttest_ingest_mixed.cpp, a stand-alone program) runs them over a corpus and asserts for every case that {code,
 message text, index} equal those of upload_pass_a + upload_pass_b, and on success that bytes[], promises, nonces, every ProofDesc
@@ -16,7 +16,8 @@ import subprocess
 
 CASES = ("valid_shapes", "one_item", "lengths_at_index_3", "length_findings", "non_canonical_scalars", "wire_rounds_64_and_65",
          "first_byte_0_and_7", "nonce_on_an_m2_item", "host_known_findings", "null_arrays", "geometry_refusals", "size_limit",
-         "promises_at_the_capacity", "degree_and_promise", "rounds_bad", "bad_transcript_state", "mixed_first_bytes_fall_back", "mutations")
+         "promises_at_the_capacity", "degree_and_promise", "rounds_bad", "bad_transcript_state", "mixed_first_bytes_fall_back", "mutations",
+         "uniform_rows_equal_packed")
 
 
 def test_mixed_ingest_equals_the_item_form_under_asan_ubsan():

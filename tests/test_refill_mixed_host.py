@@ -2,8 +2,8 @@
 UBSan.
 
 The harness (csrc/hosttest_refill_mixed.cpp, a stand-alone program) holds the one-lane model of the refill kernels
-(csrc/refill_mixed.h: refill_mixed_run_host, plain, with a live count and under a live mask) to what a fresh device upload
-(csrc/ingest_mixed.h: prelude, run, plan) makes of the rows in question -- all, the first c, the live ones alone in slot order: the
+(csrc/refill.h: refill_run_host<true>, plain, with a live count and under a live mask) to what a fresh device upload
+(csrc/ingest.h, csrc/ingest_mixed.h: prelude, run, plan) makes of the rows in question -- all, the first c, the live ones alone in slot order: the
 record (its index the slot of the upload's k-th row, the fall-back before a finding, a count beyond the batch before both), the live
 slots byte for byte at the slots' own offsets, every dead or refused slot byte for byte the sanitised slot of ITS lengths, which
 passes the walk of the upload.  The source arrays end behind the last live row; row slack and dead rows are poisoned, so a read of
@@ -14,7 +14,7 @@ import os
 import subprocess
 
 CASES = ("clean_contents", "non_canonical_scalars", "nonce_on_aggregated_slots", "promises_above_the_capacity", "foreign_first_bytes",
-         "several_findings", "a_slot_of_unfitting_length", "mutations")
+         "several_findings", "a_slot_of_unfitting_length", "mutations", "uniform_rows_equal_packed")
 
 
 def test_mixed_refill_equals_the_mixed_upload_of_the_live_rows_under_asan_ubsan():

@@ -3,7 +3,7 @@
 
   items   bpp_batch_upload of the bpp_verify_item array over the rows in page-locked host memory (the host packer of
           csrc/upload_host.h, staging, k_ingest) -- the existing item form, the baseline, not code under test
-  device  bpp_batch_upload_mixed_device from the same rows in device memory (csrc/ingest_mixed.h: k_ingest_mixed)
+  device  bpp_batch_upload_mixed_device from the same rows in device memory (csrc/ingest.h: k_ingest_mixed)
 
 on 1024 items -- 512 x m = 1, 256 x m = 2, 256 x m = 4, interleaved -- at 64 bits, t = 1.  The arms alternate in one process as in
 tools/bench_ingest.py: both warmed up, then `--reps` rounds of `--inner` calls each (every call followed by bpp_batch_destroy, outside

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """A producer's step of MIXED aggregation factors from device memory: a fresh mixed upload per step against a refill of one resident
-batch (bpp_batch_refill_enqueue_mixed, csrc/refill_mixed.h).  The sibling of tools/bench_refill.py for the mixed form.
+batch (bpp_batch_refill_enqueue_mixed, csrc/refill.h).  The sibling of tools/bench_refill.py for the mixed form.
 
 One thread, one context (made on a torch stream), --items slots in the pattern m = 4, 1, 2, 1, 1, 4, 2 at 64 bits, t = 1, promises on
 every opening, no nonces; a ring of 4 device input sets of the SAME shape vector (the proved rows rotated inside each class of m), one

@@ -75,7 +75,7 @@ def refill_mixed_section():
     out += ["One thread, one context, a ring of %d device input sets of one shape vector (m in the pattern %s, %d bits, t = %d, promises, no "
             "nonces), one verification enqueued per step: `bpp_batch_upload_mixed_device` + `bpp_verify_enqueue` + `bpp_batch_destroy` per step "
             "against `bpp_batch_refill_enqueue_mixed` (no `proof_lens` / `m`, no count, no mask) + `bpp_verify_enqueue` on one batch "
-            "(`csrc/refill_mixed.h`); the arms alternate in one process, the sizes alternate through `tools/gpu_ab.py`; median (lowest-highest) "
+            "(`csrc/refill.h`); the arms alternate in one process, the sizes alternate through `tools/gpu_ab.py`; median (lowest-highest) "
             "over the repetitions of %d steps of every run.  The expectation was that the refill arm is not slower.  Box: an MI355X, recorded by the tool as \"%s\".  A record: no ratio "
             "is promised." % (one["ring"], ", ".join(str(m) for m in one["pattern"]), one["n_bits"], one["t"], one["steps"], one["box"]), "",
             "| slots per step | runs x repetitions | upload arm, ms per step | refill arm, ms per step | upload arm, steps/s | refill arm, steps/s | "
