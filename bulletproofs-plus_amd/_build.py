@@ -132,6 +132,9 @@ _ASAN_HARNESSES = {
                     "tests/test_item_states_host.py", [], []),
     "prove_ingest": ("prove_ingest.h: the per-item routines of k_prove_ingest and the host plan of bpp_prove_openings_device, held to "
                      "ProvePack::pack and prove_item_check_host on the sorted equivalent items; tests/test_prove_ingest_host.py", [], []),
+    "prove_states": ("prove_ingest.h: the per-item transcripts of bpp_prove_openings_device_transcripts -- the finding and its precedence, "
+                     "the plan, the model of k_prove_item_states, the out-row rule -- held to ProvePack::pack and prove_item_check_host "
+                     "on items with a transcript_state each; tests/test_prove_states_host.py", [], []),
 }
 
 
@@ -167,6 +170,7 @@ INGEST_MIXED_SANITIZER_BIN, build_ingest_mixed_harness = _asan_bin("ingest_mixed
 REFILL_MIXED_SANITIZER_BIN, build_refill_mixed_harness = _asan_bin("refill_mixed"), _asan_builder("refill_mixed")
 ITEM_STATES_SANITIZER_BIN, build_item_states_harness = _asan_bin("item_states"), _asan_builder("item_states")
 PROVE_INGEST_SANITIZER_BIN, build_prove_ingest_harness = _asan_bin("prove_ingest"), _asan_builder("prove_ingest")
+PROVE_STATES_SANITIZER_BIN, build_prove_states_harness = _asan_bin("prove_states"), _asan_builder("prove_states")
 
 
 if __name__ == "__main__":

@@ -250,6 +250,8 @@ SYMBOLS = [
                                                 c_size_t]),
     ("bpp_prove_openings_device", c_int, [c_void_p, c_uint64, POINTER(ProveArrays), c_void_p, c_size_t, c_void_p, c_size_t,
                                           POINTER(c_size_t), c_void_p, POINTER(c_int), c_void_p, c_size_t]),
+    ("bpp_prove_openings_device_transcripts", c_int, [c_void_p, c_uint64, POINTER(ProveArrays), c_void_p, c_void_p, c_size_t, c_void_p,
+                                                      c_size_t, POINTER(c_size_t), c_void_p, c_void_p, POINTER(c_int), c_void_p, c_size_t]),
     ("bpp_prove_status_result", c_int, [POINTER(DeviceProveStatus), POINTER(ShardResult)]),
     ("bpp_prove_device_stats", c_int, [c_void_p, POINTER(ProveDeviceStats)]),
     ("bpp_prove_pool_openings", c_int, [c_void_p, POINTER(ProveItem), c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,

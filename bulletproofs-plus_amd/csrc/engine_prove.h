@@ -63,6 +63,11 @@ struct ProveDeviceIO {
   size_t proof_stride;
   bpp_device_prove_status *status_dev;
   std::vector<bpp_device_prove_status> outcome;  // by slot: what came back
+  // bpp_prove_openings_device_transcripts: row i of item_states (device memory, n x 203) is the transcript item i continues -- the
+  // call-wide head runs on the device (k_prove_item_states) and no state table is uploaded; row i of states_out (device memory)
+  // receives the advanced transcript of an item that succeeds, zeros otherwise.  Either may be null.
+  const uint8_t *item_states = nullptr;
+  uint8_t *states_out = nullptr;
 };
 
 struct ProveRequest {
@@ -136,6 +141,11 @@ struct ProveCall {
 
   ProveCall(bpp_ctx *c, Params &p, const ProveRequest &req) : ctx(c), P(p), r(req) {}
 
+  // kp_finish's instantiation that leaves the advanced transcripts in the arena: for the host (states203) or for the emit kernel
+  bool wants_states() const { return r.states203 || (r.dev && r.dev->states_out); }
+  // per-item transcripts from device memory: the slots of a sub-batch (each reads its own row of the sub-batch's table), else 0
+  uint32_t per_item_sub() const { return r.dev && r.dev->item_states ? prove_sub_size((uint32_t)r.n_items, ctx->opt.prove_subs) : 0u; }
+
   // pk.bytes (values, blinding factors, seed nonces), the page-locked staging in both directions (witness bytes in,
   // ProveState out) and the device arena hold witness-derived data: wiped on EVERY exit path, including the
   // "Witness opening is invalid!" and HIP-error ones
@@ -186,7 +196,7 @@ struct ProveCall {
     if (r.dev) {  // (every slot has passed the host's part of the checks; the rest is the ingest kernel's)
       const bpp_prove_arrays &in = *r.dev->in;
       prove_plan_device(shape, P.hg32.data(), r.dev->m_sorted.data(), r.n_items, in.commitments32 != nullptr, in.transcript_state,
-                        in.transcript_label, in.label_len, pk);
+                        in.transcript_label, in.label_len, pk, per_item_sub());
       set_shape();
       return;
     }
@@ -207,9 +217,7 @@ struct ProveCall {
     // The batch runs as up to PROVE_SUBS sub-batches, each on its own stream: a round is lane step (one lane per proof,
     // Fiat-Shamir latency, a handful of wavefronts) -> wave step -> fixed-base MSM (fills the chip), so one sub-batch's
     // lane step overlaps another's MSM.  All device buffers come out of one arena allocation per call.
-    uint32_t PROVE_SUBS = 2;
-    if (ctx->opt.prove_subs > 0) PROVE_SUBS = (uint32_t)std::min(16, ctx->opt.prove_subs);
-    sub_size = std::max<uint32_t>(64, cdiv(B, PROVE_SUBS));
+    sub_size = prove_sub_size(B, ctx->opt.prove_subs);  // (2 unless "prove_subs" says otherwise, at most 16; never fewer than 64 slots)
     constexpr size_t PROVE_PART_BUDGET = (size_t)2 << 30;
     n_sub = cdiv(B, sub_size);
     // A round of a sub-batch is [point encoding, Fiat-Shamir step, vector fold] -> [fixed-base MSM]: three latency-bound
@@ -288,7 +296,7 @@ struct ProveCall {
       arena_need = (arena_need + 255) & ~(size_t)255;
       u.arena_lo = arena_need;
       take(u.d_bytes, u.bytes_len);
-      take(u.d_states, pk.states.size());
+      take(u.d_states, prove_states_table_bytes(pk, per_item_sub(), u.nb));
       take(u.d_minpres, nb * m);
       take(u.d_minvals, nb * m * 8);
       take(u.d_desc, nb * sizeof(ProveDesc));
@@ -318,7 +326,7 @@ struct ProveCall {
       take(u.d_expts, ct ? (size_t)ex_nt * nb * sizeof(ge) : 16);
       take(u.d_pow, ct ? (size_t)ex_nt * nb * BPP_CT_DIGITS * sizeof(ge) : 16);
       take(u.d_ctprod, ct ? (size_t)ex_nt * nb * sizeof(ge) : 16);
-      if (r.states203) take(u.d_tstates, nb * BPP_STATE_ROW_WORDS * 4);  // (last, and only when asked for: the arena of every other call is laid out as before)
+      if (wants_states()) take(u.d_tstates, nb * BPP_STATE_ROW_WORDS * 4);  // (last, and only when asked for: the arena of every other call is laid out as before)
       if (r.dev) {  // (as above)
         take(u.d_rows, nb * sizeof(ProveDevRow));
         take(u.d_finding, nb * 4);
@@ -450,7 +458,7 @@ struct ProveCall {
     hipStream_t s = lane_stream(q);
     const uint32_t nb = u.nb;
     const bpp_prove_arrays &in = *r.dev->in;
-    HIP_CHECK(hipMemcpyAsync(u.d_states, pin_states, pk.states.size(), hipMemcpyHostToDevice, s));
+    if (!pk.states.empty()) HIP_CHECK(hipMemcpyAsync(u.d_states, pin_states, pk.states.size(), hipMemcpyHostToDevice, s));  // (per-item transcripts: none)
     HIP_CHECK(hipMemcpyAsync(u.d_desc, pin_desc + (size_t)u.lo * sizeof(ProveDesc), (size_t)nb * sizeof(ProveDesc), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(u.d_rows, pin_rows + (size_t)u.lo * sizeof(ProveDevRow), (size_t)nb * sizeof(ProveDevRow), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipStreamWaitEvent(s, ctx->prove_dev_event, 0));
@@ -474,7 +482,25 @@ struct ProveCall {
     a.minvals = u.d_minvals;
     a.minpres = u.d_minpres;
     a.finding = u.d_finding;
+    a.item_states = r.dev->item_states;
     hipLaunchKernelGGL(k_prove_ingest, dim3(cdiv(nb, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, a);
+    HIP_CHECK(hipGetLastError());
+  }
+
+  // ---- per-item transcripts: the call-wide head of every slot's transcript, from the caller's row into row k of d_states.  Behind
+  // the ingest kernel (its finding words say which rows are read) and the point the witness check branches off at, in front of kp_init.
+  void item_states_in(uint32_t q) {
+    Sub &u = subs[q];
+    ProveItemStates a;
+    memset(&a, 0, sizeof(a));
+    a.src = r.dev->item_states;
+    a.rows = u.d_rows;
+    a.desc = u.d_desc;
+    a.finding = u.d_finding;
+    a.hg32 = P.d_hg32.p;
+    a.n_bits = n, a.t = t, a.nb = u.nb;
+    a.states = u.d_states;
+    hipLaunchKernelGGL(k_prove_item_states, dim3(u.nb), b64, 0, lane_stream(q), a);
     HIP_CHECK(hipGetLastError());
   }
 
@@ -504,6 +530,7 @@ struct ProveCall {
     }
     hipLaunchKernelGGL(k_compress_ge, dim3(cdiv(nb * m, 64)), b64, 0, sx, u.d_ge, nb * m, u.d_commit32);
     HIP_CHECK(hipEventRecord(ctx->prove_aux_events[4 * q + 1], sx));
+    if (per_item_sub()) item_states_in(q);
     if (u.adopts) {
       // bpp_prove_openings: the transcript starts with the statement's commitments, and for a flagged proof those are what the
       // check has just computed: here kp_init waits for the check instead of running beside it.  (The first round's MSM waits for
@@ -610,7 +637,7 @@ struct ProveCall {
     Sub &u = subs[q];
     hipStream_t s = lane_stream(q);
     const uint32_t nb = u.nb;
-    if (r.states203)
+    if (wants_states())
       hipLaunchKernelGGL(kp_finish<true>, dim3(nb), b64, 0, s, u.d_desc, n, t, nb, rounds, u.d_a32, u.d_lr, u.d_a1b, u.d_vec, u.d_ps,
                          u.d_proofs, (uint32_t)plen, u.d_tstates);
     else
@@ -662,6 +689,9 @@ struct ProveCall {
     e.commit_stride = r.dev->commit_stride;
     e.status_dev = r.dev->status_dev;
     e.outcome = u.d_outcome;
+    e.tstates = u.d_tstates;
+    e.tstate_words = BPP_STATE_ROW_WORDS;
+    e.states_out = r.dev->states_out;
     hipLaunchKernelGGL(k_prove_emit, dim3(cdiv(nb, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, e);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipMemcpyAsync(pin_outcome + u.lo, u.d_outcome, (size_t)nb * sizeof(bpp_device_prove_status), hipMemcpyDeviceToHost, s));
@@ -1289,10 +1319,13 @@ extern "C" int bpp_prove_openings_item_message(bpp_ctx *ctx, uint64_t params, co
 // with the witness left where it is: the host checks every item from m[] and the strides, sorts the ones that pass largest m first
 // and runs them as ONE ragged call whose source is k_prove_ingest and whose sink is k_prove_emit.  The items it refuses get their
 // status record and their zeroed slots from one launch of the emit kernel over a small table, in front of the call.
+// bpp_prove_openings_device_transcripts is the same call with one transcript per item IN (item_states: device rows of 203 bytes; the
+// pos >= rate finding is then the item's, raised by the ingest kernel, and the call-wide head of every transcript runs on the device)
+// and the advanced transcripts OUT (states_out: device rows of 203 bytes, zeros for every item that fails or is refused).
 namespace {
 int prove_openings_device(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays *in, uint8_t *commitments_out, size_t commit_stride,
                           uint8_t *proofs_out, size_t proof_stride, size_t *proof_lens, bpp_device_prove_status *status_dev, int *item_status,
-                          char *errbuf, size_t errbuf_len) {
+                          char *errbuf, size_t errbuf_len, const uint8_t *item_states = nullptr, uint8_t *states_out = nullptr) {
   try {
     if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
     // pointer kinds first: nothing is allocated or launched for an array this device cannot reach, and no array is ever
@@ -1311,7 +1344,9 @@ int prove_openings_device(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays 
                   {"rng_bytes", in->rng_bytes},
                   {"commitments_out_dev", commitments_out},
                   {"proofs_out_dev", proofs_out},
-                  {"status_dev", status_dev}};
+                  {"status_dev", status_dev},
+                  {"item_states_dev", item_states},
+                  {"states_out_dev", states_out}};
     if (!commitments_out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "commitments_out_dev is null", errbuf, errbuf_len);
     if (!proofs_out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proofs_out_dev is null", errbuf, errbuf_len);
     for (const auto &a : arrays) {
@@ -1330,6 +1365,15 @@ int prove_openings_device(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays 
                   "prove_check = 1 is not supported by bpp_prove_openings_device: the self-check remakes from host items; verify the outputs "
                   "with bpp_verify_batch_mixed_device",
                   errbuf, errbuf_len);
+    if (item_states && (in->transcript_state || in->transcript_label))
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT,
+                  "transcript_state / transcript_label must be null: item i continues row i of item_states_dev", errbuf, errbuf_len);
+    if (item_states && states_out) {  // (n_items <= 2^24 is checked below: a range is at most a few gigabytes, no overflow here)
+      const uintptr_t a = (uintptr_t)item_states, b = (uintptr_t)states_out;
+      const uintptr_t len = (uintptr_t)std::min<size_t>(in->n_items, (size_t)1 << 24) * BPP_ITEM_STATE_BYTES;
+      if (a < b + len && b < a + len)
+        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "item_states_dev and states_out_dev overlap", errbuf, errbuf_len);
+    }
     if (in->transcript_state && in->transcript_state[200] >= BPP_STROBE_R) return fail(ctx, prove_err(BPP_PROVE_MSG_TRANSCRIPT_STATE).code,
                                                                                       prove_msg_text(BPP_PROVE_MSG_TRANSCRIPT_STATE), errbuf, errbuf_len);
     const std::shared_ptr<Params> Pp = params_registry().get(params);
@@ -1376,12 +1420,15 @@ int prove_openings_device(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays 
       e.commitments_out = commitments_out;
       e.commit_stride = commit_stride;
       e.status_dev = status_dev;
+      e.states_out = states_out;  // (a refused item's row is zeroed: its rows carry their finding)
       hipLaunchKernelGGL(k_prove_emit, dim3(cdiv(e.n, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, e);
       HIP_CHECK(hipGetLastError());
       HIP_CHECK(hipStreamSynchronize(s));  // (the table is pageable host memory of this frame)
     }
 
     ProveDeviceIO io{in, {}, {}, commitments_out, commit_stride, proofs_out, proof_stride, status_dev, {}};
+    io.item_states = item_states;
+    io.states_out = states_out;
     for (auto &kv : classes)
       for (uint32_t i : kv.second) {
         io.m_sorted.push_back(kv.first);
@@ -1401,7 +1448,7 @@ int prove_openings_device(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays 
       for (size_t k = 0; k < io.rows.size(); k++) {
         const uint32_t i = io.rows[k].item;
         msg[i] = engine_rc != BPP_OK ? BPP_PROVE_MSG_ENGINE : io.outcome[k].msg;
-        if (engine_rc == BPP_OK && msg[i] >= BPP_PROVE_MSG_SEED_AGGREGATED && msg[i] <= BPP_PROVE_MSG_SEED_NONCE) stats.device_findings++;
+        if (engine_rc == BPP_OK && msg[i] >= BPP_PROVE_MSG_SEED_AGGREGATED && msg[i] <= BPP_PROVE_MSG_TRANSCRIPT_STATE) stats.device_findings++;
       }
     }
     for (size_t i = 0; item_status && i < n_items; i++) item_status[i] = msg[i] == BPP_PROVE_MSG_ENGINE ? engine_rc : prove_msg_code(msg[i]);
@@ -1422,6 +1469,15 @@ extern "C" int bpp_prove_openings_device(bpp_ctx *ctx, uint64_t params, const bp
   BPP_ENTRY(ctx);
   return prove_openings_device(ctx, params, in_dev, commitments_out_dev, commit_stride, proofs_out_dev, proof_stride, proof_lens, status_dev,
                                item_status, errbuf, errbuf_len);
+}
+
+extern "C" int bpp_prove_openings_device_transcripts(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays *in_dev, const uint8_t *item_states_dev,
+                                                     uint8_t *commitments_out_dev, size_t commit_stride, uint8_t *proofs_out_dev,
+                                                     size_t proof_stride, size_t *proof_lens, uint8_t *states_out_dev,
+                                                     bpp_device_prove_status *status_dev, int *item_status, char *errbuf, size_t errbuf_len) {
+  BPP_ENTRY(ctx);
+  return prove_openings_device(ctx, params, in_dev, commitments_out_dev, commit_stride, proofs_out_dev, proof_stride, proof_lens, status_dev,
+                               item_status, errbuf, errbuf_len, item_states_dev, states_out_dev);
 }
 
 extern "C" int bpp_prove_status_result(const bpp_device_prove_status *host_copy, bpp_shard_result *out) {

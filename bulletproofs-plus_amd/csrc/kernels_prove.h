@@ -527,7 +527,8 @@ __global__ void __launch_bounds__(64) kp_init(const uint8_t *__restrict__ bytes,
   tr.cur_flags = sb[202];
   __syncthreads();
   // (the call-wide head of RangeProofTranscript::new -- domain separator, H, G bases, N, T, M -- is already in `states`: the host
-  // applies it once per distinct caller transcript, engine_prove.h)
+  // applies it once per distinct caller transcript, engine_prove.h; with per-item transcripts from device memory
+  // k_prove_item_states applies it per slot, prove_ingest.h)
   for (uint32_t j = 0; j < d.m; j++) wm_append_message(tr, K, "Ci", 2, BytesAt{bytes + d.commit_off + 32 * j}, 32);
   for (uint32_t j = 0; j < d.m; j++) wm_append_u64(tr, K, "vi - minimum_value", 18, minvals[d.minval_idx + j]);
   const uint32_t wit_len = d.m * (8 + 32 * t);

@@ -23,8 +23,18 @@
 // not know.
 //
 // ROW SLACK is never read and never written: every loop is bounded by the item's own m, rng length and proof length.
+//
+// PER-ITEM TRANSCRIPTS (bpp_prove_openings_device_transcripts): row i of the caller's item_states (n x 203 bytes of device memory, at
+// any byte address) is the STROBE state item i's proof continues, prove_with_rng(&mut Transcript, ...) per proof.  The finding
+// "transcript state has pos >= rate" then belongs to the item and is prove_ingest_check's last stage, as it is
+// prove_item_check_host's last throw: one load of byte 200 of the row.  The call-wide head of RangeProofTranscript::new, which the
+// host applies once per distinct transcript (ProvePack::advance_states), runs on the device here, once per slot: k_prove_item_states
+// behind k_prove_ingest and in front of kp_init writes row k of the sub-batch's state table, and the plan gives slot k state_idx = k.
+// A slot with ANY finding continues a fixed public state (203 zero bytes: a sponge at position 0) and nothing of its row but byte
+// 200 is ever read.  On the way out k_prove_emit turns the row kp_finish<true> left in the arena into the caller's 203 bytes for a
+// slot whose outcome is OK, and writes 203 zero bytes for every other one, refused items included (k_states_out's rule).
 #pragma once
-#include "ingest.h"
+#include "item_states.h"
 #include "prove_pack_host.h"
 
 namespace bpp {
@@ -55,6 +65,7 @@ struct ProveIngest {
   uint64_t *minvals;
   uint8_t *minpres;
   uint32_t *finding;     // nb words: 0, or prove_ingest_key of the item's first finding
+  const uint8_t *item_states;  // the caller's n x 203 bytes, row i = item i's transcript; null: one transcript for the call
 };
 
 BPP_HD bool prove_seed_present(const ProveIngest &a, size_t i) { return a.seed_nonces32 && (!a.seed_present || a.seed_present[i]); }
@@ -66,11 +77,13 @@ BPP_HD uint64_t prove_load_le64(const uint8_t *p) {
 }
 
 // A finding's key: the larger key is the EARLIER finding in prove_item_check_host's order -- stage (nonce on an aggregated item,
-// openings, blinding factors, nonce), then the index inside the stage -- so that a maximum over the item's lanes is its first one.
+// openings, blinding factors, nonce, transcript state), then the index inside the stage -- so that a maximum over the item's lanes is
+// its first one.
 #define BPP_PROVE_STAGE_SEED_AGGREGATED 0u
 #define BPP_PROVE_STAGE_OPENINGS 1u  // index 2 j: the value, 2 j + 1: its promise
 #define BPP_PROVE_STAGE_BLINDINGS 2u
 #define BPP_PROVE_STAGE_SEED_NONCE 3u
+#define BPP_PROVE_STAGE_TRANSCRIPT 4u  // (per-item transcripts only) byte 200 of the item's row
 BPP_HD uint32_t prove_ingest_key(uint32_t stage, uint32_t index, uint32_t msg) { return 0xffffffffu - ((stage << 28) | (index << 8) | msg); }
 BPP_HD uint32_t prove_ingest_key_msg(uint32_t key) { return key ? ((0xffffffffu - key) & 255u) : 0u; }
 BPP_HD uint32_t prove_key_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
@@ -94,6 +107,8 @@ BPP_HD uint32_t prove_ingest_check(const ProveIngest &a, uint32_t k, uint32_t la
       key = prove_key_max(key, prove_ingest_key(BPP_PROVE_STAGE_BLINDINGS, q, BPP_PROVE_MSG_BLINDING));
   if (lane == 0 && seed && !sc_is_canonical(a.seed_nonces32 + 32 * i))
     key = prove_key_max(key, prove_ingest_key(BPP_PROVE_STAGE_SEED_NONCE, 0, BPP_PROVE_MSG_SEED_NONCE));
+  if (lane == 0 && a.item_states && a.item_states[i * (size_t)BPP_ITEM_STATE_BYTES + BPP_ITEM_STATE_POS] >= BPP_STROBE_R)
+    key = prove_key_max(key, prove_ingest_key(BPP_PROVE_STAGE_TRANSCRIPT, 0, BPP_PROVE_MSG_TRANSCRIPT_STATE));
   return key;
 }
 
@@ -154,6 +169,9 @@ struct ProveEmit {
   uint64_t commit_stride;
   bpp_device_prove_status *status_dev;  // by item; may be null
   bpp_device_prove_status *outcome;     // by slot: what travels to the host (null without slots)
+  const uint32_t *tstates;              // kp_finish<true>'s rows, by slot (null without slots or without states_out) ...
+  uint32_t tstate_words;                // ... of BPP_STATE_ROW_WORDS words, whose first 203 bytes are the ABI's
+  uint8_t *states_out;                  // by item: the caller's n x 203 bytes at any byte address; may be null
 };
 
 // the outcome of row k: the host's finding, else the ingest finding, else the proof's status bits as prove_mixed maps them
@@ -179,11 +197,33 @@ BPP_HD void prove_emit_row(const ProveEmit &e, uint32_t k, uint32_t lane, uint32
     if (r.zero & BPP_PROVE_ROW_ZERO_PROOF) ingest_zero(po, r.proof_len, lane, lanes);
     if (r.zero & BPP_PROVE_ROW_ZERO_COMMIT) ingest_zero(co, 32 * (size_t)r.m, lane, lanes);
   }
+  if (e.states_out) {  // (dense rows: every item has one, whatever its strides hold)
+    const bool give = msg == BPP_PROVE_MSG_OK && e.slots;
+    states_out_row(e.states_out, give ? e.tstates + (size_t)k * e.tstate_words : nullptr, r.item, give, lane, lanes);
+  }
   if (lane == 0) {
     const bpp_device_prove_status rec{prove_msg_code(msg), msg};
     if (e.status_dev) e.status_dev[r.item] = rec;
     if (e.outcome) e.outcome[k] = rec;
   }
+}
+
+// ---- per-item transcripts: what k_prove_item_states reads and writes for sorted slot k of a sub-batch
+struct ProveItemStates {
+  const uint8_t *src;       // the caller's rows, n x 203 bytes at any byte address
+  const ProveDevRow *rows;  // slot k -> the caller's item
+  const ProveDesc *desc;    // its m: the "M" append
+  const uint32_t *finding;  // the ingest kernel's words: a slot with a finding reads nothing of its row
+  const uint8_t *hg32;      // the parameters' H and G bases, (t + 1) x 32 bytes
+  uint32_t n_bits, t, nb;
+  uint8_t *states;          // the sub-batch's table, nb x 203: row k is what kp_init continues (ProveDesc::state_idx = k)
+};
+
+// byte q (< 203) of the state slot k's transcript starts from: the caller's row, or the fixed public state of a slot with a finding
+// (zeros: a sponge at position 0, which no Merlin transcript is).  Byte-wise: never outside the row.
+BPP_HD bool prove_item_state_take(const ProveItemStates &a, uint32_t k) { return a.finding[k] == 0; }
+BPP_HD uint8_t prove_item_state_byte(const ProveItemStates &a, uint32_t k, bool take, uint32_t q) {
+  return take ? a.src[(size_t)a.rows[k].item * BPP_ITEM_STATE_BYTES + q] : (uint8_t)0;
 }
 
 #if defined(__HIPCC__)
@@ -203,6 +243,41 @@ __global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_prove_ingest(ProveIngest a
   }
 }
 
+// Per-item transcripts, between k_prove_ingest and kp_init on the sub-batch's lane stream: kp_init's geometry (one wavefront per slot,
+// its ProveLds) and its cooperative sponge.  The slot's starting state -- the caller's row, or zeros for a slot with a finding: a
+// wavefront-uniform choice, and no lane returns on it -- gets the seven appends of ProvePack::advance_states (RangeProofTranscript::new,
+// src/transcripts.rs:59-89: domain separator, H, the G bases, N, T, M) and goes to row k of the table kp_init reads.  The states are
+// public; the LDS is wiped all the same, as by every prover kernel.
+__global__ void __launch_bounds__(64) k_prove_item_states(ProveItemStates a) {
+  const uint32_t k = blockIdx.x;
+  if (k >= a.nb) return;
+  __shared__ ProveLds L;
+  const KeccakLanes K = keccak_lanes(L.wk[0]);
+  const bool take = prove_item_state_take(a, k);
+  for (uint32_t q = threadIdx.x; q < 200; q += 64) ((uint8_t *)L.tr)[q] = prove_item_state_byte(a, k, take, q);
+  WStrobe tr;
+  tr.st = L.tr;
+  tr.pos = prove_item_state_byte(a, k, take, BPP_ITEM_STATE_POS);
+  tr.pos_begin = prove_item_state_byte(a, k, take, BPP_ITEM_STATE_POS + 1);
+  tr.cur_flags = prove_item_state_byte(a, k, take, BPP_ITEM_STATE_POS + 2);
+  __syncthreads();
+  wm_append_message(tr, K, "dom-sep", 7, BytesAt{(const uint8_t *)"Bulletproofs+ Range Proof"}, 25);
+  wm_append_message(tr, K, "H", 1, BytesAt{a.hg32}, 32);
+  for (uint32_t g = 0; g < a.t; g++) wm_append_message(tr, K, "G", 1, BytesAt{a.hg32 + 32 * (size_t)(g + 1)}, 32);
+  wm_append_u64(tr, K, "N", 1, a.n_bits);
+  wm_append_u64(tr, K, "T", 1, a.t);
+  wm_append_u64(tr, K, "M", 1, a.desc[k].m);
+  ws_sync();
+  uint8_t *row = a.states + (size_t)k * BPP_ITEM_STATE_BYTES;
+  for (uint32_t q = threadIdx.x; q < 200; q += 64) row[q] = ((const uint8_t *)L.tr)[q];
+  if (threadIdx.x == 0) {
+    row[BPP_ITEM_STATE_POS] = (uint8_t)tr.pos;
+    row[BPP_ITEM_STATE_POS + 1] = (uint8_t)tr.pos_begin;
+    row[BPP_ITEM_STATE_POS + 2] = (uint8_t)tr.cur_flags;
+  }
+  lds_wipe(L);
+}
+
 // Behind kp_finish: the same geometry, BPP_INGEST_LANES lanes per row.
 __global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_prove_emit(ProveEmit e) {
   const size_t gid = (size_t)blockIdx.x * BPP_INGEST_BLOCK + threadIdx.x;
@@ -213,13 +288,27 @@ __global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_prove_emit(ProveEmit e) {
 
 // ---- host side: the plan in front of the run.  Pure host C++ over prove_pack_host.h.
 
+// The slots of a sub-batch: the call is cut into "prove_subs" sub-batches (2 unless the option says otherwise, at most 16) of never
+// fewer than 64 slots.  ProveCall::plan cuts by it; with per-item transcripts the plan below needs the cut as well.
+inline uint32_t prove_sub_size(uint32_t B, int prove_subs) {
+  const uint32_t subs = prove_subs > 0 ? (uint32_t)std::min(16, prove_subs) : 2u;
+  return std::max<uint32_t>(64, (B + subs - 1) / subs);
+}
+// the bytes of a sub-batch's state table (ProveCall::carve: d_states): the call's distinct states, or a row per slot
+inline size_t prove_states_table_bytes(const ProvePack &pk, uint32_t per_item_sub, uint32_t nb) {
+  return per_item_sub ? (size_t)nb * BPP_ITEM_STATE_BYTES : pk.states.size();
+}
+
 // What ProvePack::pack makes of the sorted equivalent items, as far as it follows from their aggregation factors alone: the
 // descriptors with their offsets, roff, the distinct transcript states with the call-level appends, the call's m, rounds and proof
 // length, and bytes_len.  `bytes`, `minvals` and `minpres` stay empty: the ingest kernel writes them on the device.
 // m_sorted: the aggregation factors of the items that passed the host's part of the checks, largest first.  brought: the call
 // brings a commitments array.  One transcript source for the call: a state for every distinct m, in the order they first appear.
+// per_item_sub != 0 (per-item transcripts; the value: the slots of a sub-batch, prove_sub_size): the host sees no state.  Slot i reads
+// row i % per_item_sub of its sub-batch's table, which k_prove_item_states writes, and pk.states stays empty.
 inline void prove_plan_device(const ParamShape &P, const uint8_t *hg32, const uint32_t *m_sorted, size_t n_items, bool brought,
-                              const uint8_t *transcript_state, const uint8_t *transcript_label, size_t label_len, ProvePack &pk) {
+                              const uint8_t *transcript_state, const uint8_t *transcript_label, size_t label_len, ProvePack &pk,
+                              uint32_t per_item_sub = 0) {
   const uint32_t t = P.t, B = (uint32_t)n_items;
   pk.m = m_sorted[0];
   pk.plen = prove_item_len_host(P, pk.m);
@@ -245,6 +334,10 @@ inline void prove_plan_device(const ParamShape &P, const uint8_t *hg32, const ui
     d.seed_off = (uint32_t)at;
     at += 32;
     d.flags = brought ? 0u : PV_FLAG_MAKE_COMMITMENTS;
+    if (per_item_sub) {
+      d.state_idx = i % per_item_sub;
+      continue;
+    }
     if (i && m_sorted[i - 1] == mi) {
       d.state_idx = pk.desc[i - 1].state_idx;
       continue;
@@ -264,6 +357,24 @@ inline void prove_plan_device(const ParamShape &P, const uint8_t *hg32, const ui
     }
   }
   pk.advance_states(P, hg32, state_m);
+}
+
+// k_prove_item_states on the host: the same starting bytes, the appends on merlin.h's one-lane sponge
+inline void prove_item_states_run_host(const ProveItemStates &a) {
+  for (uint32_t k = 0; k < a.nb; k++) {
+    const bool take = prove_item_state_take(a, k);
+    uint8_t b[BPP_ITEM_STATE_BYTES];
+    for (uint32_t q = 0; q < BPP_ITEM_STATE_BYTES; q++) b[q] = prove_item_state_byte(a, k, take, q);
+    Strobe st;
+    strobe_from_bytes(st, b);
+    merlin_append_message(st, (const uint8_t *)"dom-sep", 7, (const uint8_t *)"Bulletproofs+ Range Proof", 25);
+    merlin_append_message(st, (const uint8_t *)"H", 1, a.hg32, 32);
+    for (uint32_t g = 0; g < a.t; g++) merlin_append_message(st, (const uint8_t *)"G", 1, a.hg32 + (size_t)(g + 1) * 32, 32);
+    merlin_append_u64(st, (const uint8_t *)"N", 1, a.n_bits);
+    merlin_append_u64(st, (const uint8_t *)"T", 1, a.t);
+    merlin_append_u64(st, (const uint8_t *)"M", 1, a.desc[k].m);
+    strobe_to_bytes(a.states + (size_t)k * BPP_ITEM_STATE_BYTES, st);
+  }
 }
 
 // the run of one sub-batch on the host, `lanes` lanes per item reduced as the kernel reduces: the model the harness holds to the

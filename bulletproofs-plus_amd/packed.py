@@ -357,6 +357,14 @@ def _verify_mixed(params, inp, action, chunk, device):
     masks = np.zeros((inp.n, t, 32), dtype=np.uint8)
     present = np.zeros(inp.n, dtype=np.uint8)
     err = ctypes.create_string_buffer(256)
+    if device and getattr(inp, "item_states", None) is not None:
+        # per-item transcripts have no blocking one-call form: the upload that takes them, then the resident verification
+        batch = ResidentBatch.from_mixed(params, inp)
+        try:
+            got_masks, got_present = batch.verify_arrays(action, chunk)
+            return got_masks.copy(), got_present.copy()
+        finally:
+            batch.close()
     if device:
         inp.order_before(eng)
     fn = eng.lib.bpp_verify_batch_mixed_device if device else eng.lib.bpp_verify_batch_mixed
@@ -387,10 +395,12 @@ class DeviceOpenings(DevicePackedInput):
         commitments  uint8 [n, m_stride, 32], or None: the engine makes them (bpp_prove_openings' rule)
         min_values   8-byte dtype [n, m_stride], min_present uint8 [n, m_stride], seed_nonces uint8 [n, 32], seed_present uint8 [n], or None
         rng_bytes    uint8 [n, rng_stride]              row i holds (rounds_i + 3) x 32 bytes
-    Row slack is never read.  One transcript for the call: label= or state=.  Ordering as for DevicePackedInput."""
+    Row slack is never read.  One transcript for the call: label= or state=.  Or one per item (bpp_prove_openings_device_transcripts):
+    item_states= a uint8 [n, 203] device tensor (any byte address) or an (address, (n, 203)) pair, row i the STROBE state item i's
+    proof continues; label and state are then not passed on.  Ordering as for DevicePackedInput."""
 
     def __init__(self, values, blindings, m, commitments=None, min_values=None, min_present=None, seed_nonces=None, seed_present=None,
-                 rng_bytes=None, label=b"", state=None):
+                 rng_bytes=None, label=b"", state=None, item_states=None):
         self._keep, self.device_index, self._torch, self.synchronised = [], None, False, False
         self.m = np.ascontiguousarray(_host_array(m), dtype=np.uint32)
         if self.m.ndim != 1:
@@ -424,21 +434,29 @@ class DeviceOpenings(DevicePackedInput):
                                        opt(min_values, "min_values", 8, (n, ms)), opt(min_present, "min_present", 1, (n, ms)),
                                        opt(seed_nonces, "seed_nonces", 1, (n, 32)), opt(seed_present, "seed_present", 1, (n,)), addr_r,
                                        rshape[1], None if self.state is None else self.state.ctypes.data, self.label.ctypes.data, len(label))
+        self.item_states_rows = item_states
+        self._item_states(item_states, n, opt)
 
 
 class DeviceProved:
     """What prove_openings_device leaves: .commitments uint8 [n, 32 m_stride] and .proofs uint8 [n, longest proof] (device tensors;
     row i holds 32 m[i] and proof_lens[i] bytes, zero for a failed item), .status int32 [n, 2] (device: code, message id), and on the
-    host .proof_lens, .m, .codes, the call's .rc and .message (the first failing item's)."""
+    host .proof_lens, .m, .codes, the call's .rc and .message (the first failing item's).  .states (states=): uint8 [n, 203] on the
+    device, row i the transcript item i's proof left advanced, zero for a failed item; else None."""
 
-    def __init__(self, inp, commitments, proofs, proof_lens, status, codes, rc, message):
+    def __init__(self, inp, commitments, proofs, proof_lens, status, codes, rc, message, states=None):
         self.inp, self.commitments, self.proofs, self.proof_lens, self.m = inp, commitments, proofs, proof_lens, inp.m
-        self.status, self.codes, self.rc, self.message = status, codes, rc, message
+        self.status, self.codes, self.rc, self.message, self.states = status, codes, rc, message, states
 
     def as_mixed_input(self, label=None, state=None):
         """a DeviceMixedInput over the same tensors -- nothing is copied -- with the promises and nonces of the openings; label= / state=:
-        the verifier's transcript (default: the prove call's)"""
+        the verifier's transcript (default: the prove call's -- for openings made with item_states=, the same starting rows, so that
+        every output is verified under its own transcript where it lies)"""
         inp = self.inp
+        if label is None and state is None and inp.item_states is not None:
+            return DeviceMixedInput(self.proofs, self.proof_lens, self.m, self.commitments.view(self.commitments.shape[0], -1, 32),
+                                    min_values=inp.min_values, min_present=inp.min_present, seed_nonces=inp.seed_nonces,
+                                    seed_present=inp.seed_present, item_states=inp.item_states_rows)
         if label is None and state is None:
             label, state = inp.label_bytes, (None if inp.state is None else inp.state.tobytes())
         return DeviceMixedInput(self.proofs, self.proof_lens, self.m, self.commitments.view(self.commitments.shape[0], -1, 32),
@@ -456,11 +474,14 @@ class DeviceProved:
         return out
 
 
-def prove_openings_device(params, inp, commitments_out=None, proofs_out=None, status_out=None, commit_stride=None, proof_stride=None):
+def prove_openings_device(params, inp, commitments_out=None, proofs_out=None, status_out=None, commit_stride=None, proof_stride=None,
+                          states=None):
     """bpp_prove_openings over a DeviceOpenings (bpp_prove_openings_device): what bpp_prove_openings writes on host copies of the same
     arrays, with the proofs and commitments left in device memory.  A failed item never stops the others and does not raise: look at
     .codes / .rc / .message.  Raises when the whole call is refused or the engine faults.
-    commitments_out / proofs_out / status_out: tensors (or (address, shape) pairs, with the strides) to write into; default: fresh ones."""
+    commitments_out / proofs_out / status_out: tensors (or (address, shape) pairs, with the strides) to write into; default: fresh ones.
+    states (bpp_prove_openings_device_transcripts): True, or a uint8 [n, 203] device tensor (any byte address) or a raw device address
+    -- the advanced transcripts come back as `.states`.  An `inp` made with item_states= goes through the same entry point."""
     import torch
     eng, t, n_bits = params.engine, int(params.extension_degree()), params.bit_length()
     n, ms = inp.n, inp.m_stride
@@ -487,11 +508,23 @@ def prove_openings_device(params, inp, commitments_out=None, proofs_out=None, st
     codes = np.full(n, unset, dtype=np.intc)
     err = ctypes.create_string_buffer(256)
     inp.order_before(eng)
-    rc = eng.lib.bpp_prove_openings_device(eng.ctx, params.handle, byref(inp.struct), addr_c, cstride, addr_p, pstride,
-                                           lens.ctypes.data_as(POINTER(c_size_t)), addr_s, codes.ctypes.data_as(POINTER(ctypes.c_int)), err, 256)
+    if states is False:
+        states = None
+    if states is None and inp.item_states is None:
+        rc = eng.lib.bpp_prove_openings_device(eng.ctx, params.handle, byref(inp.struct), addr_c, cstride, addr_p, pstride,
+                                               lens.ctypes.data_as(POINTER(c_size_t)), addr_s, codes.ctypes.data_as(POINTER(ctypes.c_int)), err, 256)
+    else:
+        if states is True:
+            states = torch.zeros((n, 203), dtype=torch.uint8, device=dev)
+        addr_t = None if states is None else ctypes.c_void_p(states.data_ptr() if hasattr(states, "data_ptr") else int(states))
+        # (rows in: the call's label and state are not passed on; the engine refuses the combination)
+        st = inp.struct if inp.item_states is None else inp.struct_without_transcript()
+        rc = eng.lib.bpp_prove_openings_device_transcripts(eng.ctx, params.handle, byref(st), inp.item_states, addr_c, cstride, addr_p, pstride,
+                                                           lens.ctypes.data_as(POINTER(c_size_t)), addr_t, addr_s,
+                                                           codes.ctypes.data_as(POINTER(ctypes.c_int)), err, 256)
     if rc < 0 or (rc != 0 and (codes == unset).all()):
         api._check(rc, eng.ctx, err)
-    return DeviceProved(inp, commitments_out, proofs_out, lens, status_out, codes, rc, err.value.decode())
+    return DeviceProved(inp, commitments_out, proofs_out, lens, status_out, codes, rc, err.value.decode(), states)
 
 
 def prove_device_stats(engine):

@@ -933,6 +933,29 @@ int bpp_prove_openings_device(bpp_ctx *ctx, uint64_t params, const bpp_prove_arr
                               bpp_device_prove_status *status_dev,                /* DEVICE out, n_items; may be NULL */
                               int *item_status,                                   /* HOST out, n_items; may be NULL */
                               char *errbuf, size_t errbuf_len);
+/* bpp_prove_openings_device with ONE TRANSCRIPT PER ITEM in device memory going in, and the advanced transcripts coming out: the
+ * reference's prove_with_rng(&mut Transcript, ...) per proof, the prover's counterpart of bpp_batch_upload_mixed_device_transcripts
+ * and bpp_verify_enqueue_states.  THE CONTRACT: the call writes what bpp_prove_openings_states writes on the equivalent bpp_prove_item
+ * array whose item i has transcript_state = row i of item_states_dev -- return code, errbuf, item_status, proof_lens, proof and
+ * commitment bytes, zeroed slots.  Everything bpp_prove_openings_device documents holds unchanged.
+ * item_states_dev given: in_dev->transcript_state and transcript_label must both be NULL (else BPP_ERR_INVALID_ARGUMENT before anything
+ * is allocated or launched).  A row whose byte 200 (pos) is >= 166 is THAT ITEM's finding ("transcript state has pos >= rate",
+ * BPP_PROVE_MSG_TRANSCRIPT_STATE), last in the item's precedence as in the host form; the item fails, the others go on.  Nothing of
+ * such a row but byte 200 is read, and rows of items the host refuses are never read.  The call-wide head of every transcript (domain
+ * separator, H, G bases, N, T, M) is applied on the device: the host never sees a state.
+ * item_states_dev NULL: the call's one transcript applies exactly as in bpp_prove_openings_device (whole-call refusal at pos >= 166).
+ * states_out_dev given: row i receives the 203 bytes bpp_prove_openings_states gives for an item that succeeds -- the transcript as
+ * challenge_final_e leaves it -- and 203 zero bytes for every failed or refused item, also in a call in which no item passes the
+ * host's checks.  Rows are dense (stride 203) at any byte address; no byte beyond row n_items - 1 is written.
+ * Both NULL: identical to bpp_prove_openings_device.
+ * REFUSED before any launch, in addition: either array not BPP_PTR_THIS_DEVICE memory; the two n_items x 203 ranges overlap.
+ * bpp_prove_device_stats counts a transcript finding as a device finding. */
+int bpp_prove_openings_device_transcripts(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays *in_dev,
+                                          const uint8_t *item_states_dev,             /* DEVICE n_items x 203, row i = item i's STROBE state; or NULL */
+                                          uint8_t *commitments_out_dev, size_t commit_stride, uint8_t *proofs_out_dev, size_t proof_stride,
+                                          size_t *proof_lens,
+                                          uint8_t *states_out_dev,                    /* DEVICE n_items x 203 out; or NULL */
+                                          bpp_device_prove_status *status_dev, int *item_status, char *errbuf, size_t errbuf_len);
 /* code and message text of a status record copied to the host (tier BPP_TIER_CONSTRUCTION for a finding, rank = -1, index 0) */
 int bpp_prove_status_result(const bpp_device_prove_status *host_copy, bpp_shard_result *out);
 struct bpp_prove_device_stats {

@@ -642,6 +642,27 @@ class RangeProof {
     return res;
   }
 
+  // ... with one transcript per item going in and the advanced transcripts coming out (bpp_prove_openings_device_transcripts):
+  // item_states_dev is n rows of 203 bytes in DEVICE memory, row i the STROBE state item i's proof continues (openings.arrays then
+  // names no transcript), or null: the call's one transcript; states_out_dev is n rows of 203 bytes of DEVICE memory that receive
+  // the transcripts as the proofs left them (zeros for an item that fails), or null.  A row with pos >= 166 is its item's finding.
+  static DeviceProveResult prove_openings(const DeviceProveArrays &openings, const uint8_t *item_states_dev, const DeviceProveOutputs &out,
+                                          uint8_t *states_out_dev, const std::shared_ptr<RangeParameters> &generators) {
+    auto &params = *generators;
+    const size_t n = openings.arrays.n_items;
+    const int unset = INT_MIN;
+    DeviceProveResult res{0, std::string(), std::vector<size_t>(n, 0), std::vector<int>(n, unset)};
+    char err[256] = {0};
+    res.code = bpp_prove_openings_device_transcripts(params.engine().ctx(), params.handle(), &openings.arrays, item_states_dev, out.commitments,
+                                                     out.commit_stride, out.proofs, out.proof_stride, res.proof_lens.data(), states_out_dev,
+                                                     out.status, res.item_status.data(), err, sizeof(err));
+    bool refused = res.code != 0;  // (a refusal writes no item's status)
+    for (int s : res.item_status) refused = refused && s == unset;
+    if (res.code < 0 || refused) check(res.code, err);
+    res.message = err;
+    return res;
+  }
+
   // src/range_proof.rs:712-752; every `chunk` proofs are one reference batch (all chunks are verified)
   static std::vector<std::optional<ExtendedMask>> verify_batch(const std::vector<Transcript> &transcripts,
                                                                 const std::vector<RangeStatement> &statements,

@@ -490,6 +490,11 @@ extern "C" {
                                      commit_stride: usize, proofs_out_dev: *mut u8, proof_stride: usize, proof_lens: *mut usize,
                                      status_dev: *mut bpp_device_prove_status, item_status: *mut c_int, errbuf: *mut c_char,
                                      errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_openings_device_transcripts(ctx: *mut bpp_ctx, params: u64, in_dev: *const bpp_prove_arrays,
+                                                 item_states_dev: *const u8, commitments_out_dev: *mut u8, commit_stride: usize,
+                                                 proofs_out_dev: *mut u8, proof_stride: usize, proof_lens: *mut usize,
+                                                 states_out_dev: *mut u8, status_dev: *mut bpp_device_prove_status,
+                                                 item_status: *mut c_int, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
     pub fn bpp_prove_status_result(host_copy: *const bpp_device_prove_status, out: *mut bpp_shard_result) -> c_int;
     pub fn bpp_prove_device_stats(ctx: *mut bpp_ctx, out: *mut bpp_prove_device_stats) -> c_int;
     pub fn bpp_prove_pool_openings(p: *mut bpp_prove_pool, items: *const bpp_prove_item, n_items: usize, commitments_out: *mut u8,

@@ -13,7 +13,12 @@ nonce on each.  The arms alternate in one process, both warmed up, then `--reps`
 over rounds of the round's median wall time per call with the lowest and highest round.  A record, not a gate: no ratio is asserted
 anywhere and no rate is promised -- the prover is bound by its instruction rate, and the copies the device form removes are a few
 hundred microseconds of a call of several milliseconds.  Prints one short JSON line; the full record is appended to --out
-(profiles/prove_device.json, a list of runs)."""
+(profiles/prove_device.json, a list of runs).
+
+--item-states: another pair of arms instead, configs[4]'s shape only -- bpp_prove_openings_device_transcripts with one transcript row
+per item going in and the advanced rows coming out (k_prove_item_states in front of kp_init, kp_finish<true>, the rows through
+k_prove_emit) against bpp_prove_openings_device on the same openings under one label, alternating in the same way; the record goes to
+profiles/prove_device_states.json.  The rows add about three cooperative permutations per proof in front of the call."""
 import argparse
 import ctypes
 import importlib
@@ -29,14 +34,86 @@ sys.path.insert(0, ROOT)
 SHAPES = {"configs4": dict(m=4, t=3, nonces=False), "nonces": dict(m=1, t=3, nonces=True)}
 
 
+def item_states_arms(args):
+    import numpy as np
+    import torch
+    import bench
+    bpp = importlib.import_module("bulletproofs-plus_amd")
+    packed = importlib.import_module("bulletproofs-plus_amd.packed")
+    eng = bpp.Engine(0)
+    n_bits, n, m, t = 64, args.items, SHAPES["configs4"]["m"], SHAPES["configs4"]["t"]
+    params = bpp.RangeParameters.init(n_bits, m, bpp.create_pedersen_gens_with_extension_degree(t), engine=eng)
+    rounds = (n_bits * m).bit_length() - 1
+    plen, need = 1 + 32 * (t + 5 + 2 * rounds), 32 * (rounds + 3)
+    rng = np.random.default_rng(20261021)
+    values = rng.integers(0, 1 << 63, size=(n, m), dtype=np.uint64)
+    blind = rng.integers(0, 256, size=(n, m, t, 32), dtype=np.uint8)
+    blind[..., 31] &= 0x0F
+    minv, minp = values // np.uint64(3), np.ones((n, m), dtype=np.uint8)
+    ext = rng.integers(0, 256, size=(n, need), dtype=np.uint8)
+    ms = np.full(n, m, dtype=np.uint32)
+    # one transcript per item: the label, then a context whose length differs from item to item (so do the rows' positions)
+    rows = np.zeros((n, 203), dtype=np.uint8)
+    for i in range(n):
+        tr = bpp.Transcript.new(bench.LABEL)
+        tr.append_message(b"ctx", bytes([i & 255]) * (1 + i % 167))
+        rows[i] = np.frombuffer(tr.state, dtype=np.uint8)
+    dev = lambda a: torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).cuda()  # noqa: E731
+    arrays = dict(min_values=dev(minv), min_present=dev(minp), rng_bytes=dev(ext))
+    plain = packed.DeviceOpenings(dev(values), dev(blind), ms, label=bench.LABEL, **arrays)
+    with_rows = packed.DeviceOpenings(dev(values), dev(blind), ms, item_states=dev(rows), **arrays)
+    d_proofs = torch.zeros((n, plen), dtype=torch.uint8, device="cuda")
+    d_commits = torch.zeros((n, 32 * m), dtype=torch.uint8, device="cuda")
+    d_status = torch.zeros((n, 2), dtype=torch.int32, device="cuda")
+    d_states = torch.zeros((n, 203), dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+
+    def call(inp, states):
+        res = packed.prove_openings_device(params, inp, commitments_out=d_commits, proofs_out=d_proofs, status_out=d_status, states=states)
+        assert res.rc == 0, res.message
+        return res
+
+    arms = {"device": lambda: call(plain, None), "device+item_states": lambda: call(with_rows, d_states)}
+    res = arms["device+item_states"]()
+    packed.verify_batch_mixed_device(params, res.as_mixed_input())  # (what is timed is right: the outputs verify under their own rows)
+    for fn in arms.values():
+        fn(), fn()
+    per = {k: [] for k in arms}
+    for _ in range(args.reps):
+        for k, fn in arms.items():
+            ts = []
+            for _ in range(args.inner):
+                t0 = time.perf_counter()
+                fn()
+                ts.append((time.perf_counter() - t0) * 1e3)
+            per[k].append(statistics.median(ts))
+    run = {"tool": "bench_prove_device --item-states", "items": n, "n_bits": n_bits, "m": m, "t": t, "reps": args.reps, "inner": args.inner,
+           "box": torch.cuda.get_device_name(0), "arms": {}}
+    for k, v in per.items():
+        med = statistics.median(v)
+        run["arms"][k] = {"ms_per_call": med, "ms_low": min(v), "ms_high": max(v), "proofs_per_s": n / med * 1e3}
+    run["stats"] = packed.prove_device_stats(eng)
+    runs = json.load(open(args.out)) if os.path.exists(args.out) else []
+    runs.append(run)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    json.dump(runs, open(args.out, "w"), indent=1)
+    print(json.dumps({"tool": run["tool"], "ms_per_call": {k: round(a["ms_per_call"], 3) for k, a in run["arms"].items()}}))
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--inner", type=int, default=6)
     ap.add_argument("--items", type=int, default=1024)
     ap.add_argument("--shapes", default="configs4,nonces")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "prove_device.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--item-states", action="store_true", help="time per-item transcripts in and out against the call without them")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "prove_device_states.json" if args.item_states else "prove_device.json")
+    if args.item_states:
+        return item_states_arms(args)
     import numpy as np
     import torch
     import bench
