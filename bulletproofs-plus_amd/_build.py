@@ -135,6 +135,9 @@ _ASAN_HARNESSES = {
     "prove_states": ("prove_ingest.h: the per-item transcripts of bpp_prove_openings_device_transcripts -- the finding and its precedence, "
                      "the plan, the model of k_prove_item_states, the out-row rule -- held to ProvePack::pack and prove_item_check_host "
                      "on items with a transcript_state each; tests/test_prove_states_host.py", [], []),
+    "prove_enqueue": ("prove_ingest.h as bpp_prove_enqueue uses it: the ingest routines under a live mask -- a dead row is never read -- "
+                      "held to ProvePack::pack on the live items and to the substitute on the dead ones; the summary reduction and the "
+                      "ok mask against a host loop; tests/test_prove_enqueue_host.py", [], []),
 }
 
 
@@ -171,6 +174,7 @@ REFILL_MIXED_SANITIZER_BIN, build_refill_mixed_harness = _asan_bin("refill_mixed
 ITEM_STATES_SANITIZER_BIN, build_item_states_harness = _asan_bin("item_states"), _asan_builder("item_states")
 PROVE_INGEST_SANITIZER_BIN, build_prove_ingest_harness = _asan_bin("prove_ingest"), _asan_builder("prove_ingest")
 PROVE_STATES_SANITIZER_BIN, build_prove_states_harness = _asan_bin("prove_states"), _asan_builder("prove_states")
+PROVE_ENQUEUE_SANITIZER_BIN, build_prove_enqueue_harness = _asan_bin("prove_enqueue"), _asan_builder("prove_enqueue")
 
 
 if __name__ == "__main__":

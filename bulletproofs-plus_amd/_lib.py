@@ -117,6 +117,16 @@ class DeviceProveStatus(Structure):
     _fields_ = [("code", ctypes.c_int32), ("msg", c_uint32)]
 
 
+class DeviceProveSummary(Structure):
+    """bpp_device_prove_summary: the one record of a bpp_prove_enqueue, 32 bytes, as it lies in device memory"""
+    _fields_ = [("code", ctypes.c_int32)] + [(n, c_uint32) for n in ("msg", "index", "flags", "n_ok", "n_failed", "n_empty", "reserved")]
+
+
+class ProveEnqueueStats(Structure):
+    """struct bpp_prove_enqueue_stats: what the stream-ordered prove calls of a context cost the host"""
+    _fields_ = [(n, c_uint64) for n in ("calls", "first_calls", "host_waits", "allocations")]
+
+
 class ProveDeviceStats(Structure):
     """struct bpp_prove_device_stats: what the prove calls from device arrays of a context came to"""
     _fields_ = [(n, c_uint64) for n in ("calls", "items", "device_findings", "host_findings")]
@@ -254,6 +264,14 @@ SYMBOLS = [
                                                       c_size_t, POINTER(c_size_t), c_void_p, c_void_p, POINTER(c_int), c_void_p, c_size_t]),
     ("bpp_prove_status_result", c_int, [POINTER(DeviceProveStatus), POINTER(ShardResult)]),
     ("bpp_prove_device_stats", c_int, [c_void_p, POINTER(ProveDeviceStats)]),
+    ("bpp_prove_plan_create", c_int, [c_void_p, c_uint64, POINTER(ProveArrays), c_size_t, c_size_t, c_uint32, POINTER(c_uint64), c_void_p,
+                                      c_size_t]),
+    ("bpp_prove_plan_shape", c_int, [c_void_p, c_uint64, POINTER(c_size_t), POINTER(c_int)]),
+    ("bpp_prove_plan_destroy", c_int, [c_void_p, c_uint64]),
+    ("bpp_prove_enqueue", c_int, [c_void_p, c_uint64, POINTER(ProveArrays), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, POINTER(c_uint64)]),
+    ("bpp_prove_summary_result", c_int, [POINTER(DeviceProveSummary), POINTER(ShardResult)]),
+    ("bpp_prove_enqueue_stats", c_int, [c_void_p, POINTER(ProveEnqueueStats)]),
     ("bpp_prove_pool_openings", c_int, [c_void_p, POINTER(ProveItem), c_size_t, c_void_p, c_size_t, c_void_p, c_size_t,
                                         POINTER(c_size_t), c_void_p, c_size_t]),
     ("bpp_prove_pool_openings_stats", c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),

@@ -638,6 +638,15 @@ struct bpp_ctx {
   hipEvent_t prove_dev_event = nullptr;
   DevBuf<uint8_t> prove_dev_refused;
   struct bpp_prove_device_stats prove_dev_stats{};
+  // bpp_prove_plan_create / bpp_prove_enqueue (engine_prove_plan.h): the resident plans by handle -- what the context itself needs of
+  // one is its arena, which bpp_prove_secret_bytes reads -- and the counters of bpp_prove_enqueue_stats
+  struct ProvePlanBase {
+    DevBuf<uint8_t> arena;
+    virtual ~ProvePlanBase() {}
+  };
+  std::map<uint64_t, std::unique_ptr<ProvePlanBase>> prove_plans;
+  uint64_t prove_plan_next = 1;
+  struct bpp_prove_enqueue_stats prove_enq_stats{};
   bpp_prove_profile pprof{};
   // knobs (tests, A/B timing).  -1 = the engine's own rule.  The BPP_* environment variables of the same names are read
   // ONCE, when the context is created (no getenv on any verification path: a host that calls setenv from another thread
@@ -1392,6 +1401,7 @@ void bpp_ctx_destroy(bpp_ctx *ctx) {
   }
   for (auto &e : ctx->prove_aux_events) (void)hipEventDestroy(e);
   if (ctx->prove_dev_event) (void)hipEventDestroy(ctx->prove_dev_event);
+  ctx->prove_plans.clear();  // (every stream a plan's work ran on has been synchronised above)
   ctx->prove_arena.release();
   if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   {
@@ -4714,6 +4724,8 @@ static int prove_secret_bytes_own(bpp_ctx *ctx, uint64_t *examined, uint64_t *no
     }
     HIP_CHECK(hipStreamSynchronize(ctx->stream));
     std::vector<const DevBuf<uint8_t> *> dev{&ctx->check_dev};
+    // the arenas of the resident prove plans: every stream of an enqueue is joined into the context's stream, waited for above
+    for (auto &kv : ctx->prove_plans) dev.push_back(&kv.second->arena);
     if (ctx->check_spare && ctx->check_spare->seeds.p == ctx->check_zeroed_seeds) dev.push_back(&ctx->check_spare->seeds);
     if (ctx->check_spare && ctx->check_spare->masks.p == ctx->check_zeroed_masks) dev.push_back(&ctx->check_spare->masks);
     for (const DevBuf<uint8_t> *buf : dev) {
@@ -4840,5 +4852,6 @@ int bpp_profile_get(bpp_ctx *ctx, bpp_profile *out) {
 #include "engine_batcher.h"
 
 #include "engine_prove.h"
+#include "engine_prove_plan.h"
 #include "engine_prove_pool.h"
 #include "engine_prove_pipe.h"

@@ -68,6 +68,13 @@ struct ProveDeviceIO {
   // receives the advanced transcript of an item that succeeds, zeros otherwise.  Either may be null.
   const uint8_t *item_states = nullptr;
   uint8_t *states_out = nullptr;
+  // bpp_prove_enqueue (engine_prove_plan.h): the call is one of a resident plan, whose ProveCall lives as long as the plan and is
+  // enqueued again and again.  per_item: every enqueue brings item_states (the plan is carved for them before the first rows exist);
+  // live: the caller's mask by item; ok_mask / outcome_item: what k_prove_emit writes by item beside status_dev.  All null otherwise.
+  bool per_item = false;
+  const uint8_t *live = nullptr;
+  uint8_t *ok_mask = nullptr;
+  bpp_device_prove_status *outcome_item = nullptr;
 };
 
 struct ProveRequest {
@@ -138,13 +145,19 @@ struct ProveCall {
   size_t ev_used = 0;
   std::chrono::steady_clock::time_point t_begin;
   bool arena_clean = true, staging_clean = false;
+  // where the arena and the staging on the way in live: the context's, shared by its blocking calls -- or (resident) a plan's own,
+  // carved and staged ONCE: the staging then holds the plan's public tables alone, is never rewritten and never wiped, nothing comes
+  // back to the host, and the arena holds a state row per slot whether or not an enqueue asks for the advanced transcripts
+  DevBuf<uint8_t> *arena;
+  PinnedBuf<uint8_t> *pin_in;
+  bool resident = false;
 
-  ProveCall(bpp_ctx *c, Params &p, const ProveRequest &req) : ctx(c), P(p), r(req) {}
+  ProveCall(bpp_ctx *c, Params &p, const ProveRequest &req) : ctx(c), P(p), r(req), arena(&c->prove_arena), pin_in(&c->prove_pin_in) {}
 
   // kp_finish's instantiation that leaves the advanced transcripts in the arena: for the host (states203) or for the emit kernel
   bool wants_states() const { return r.states203 || (r.dev && r.dev->states_out); }
   // per-item transcripts from device memory: the slots of a sub-batch (each reads its own row of the sub-batch's table), else 0
-  uint32_t per_item_sub() const { return r.dev && r.dev->item_states ? prove_sub_size((uint32_t)r.n_items, ctx->opt.prove_subs) : 0u; }
+  uint32_t per_item_sub() const { return r.dev && (r.dev->item_states || r.dev->per_item) ? prove_sub_size((uint32_t)r.n_items, ctx->opt.prove_subs) : 0u; }
 
   // pk.bytes (values, blinding factors, seed nonces), the page-locked staging in both directions (witness bytes in,
   // ProveState out) and the device arena hold witness-derived data: wiped on EVERY exit path, including the
@@ -154,14 +167,14 @@ struct ProveCall {
   void wipe_secrets() {
     if (!staging_clean) {
       pk.wipe();
-      wipe(ctx->prove_pin_in.p, ctx->prove_pin_in.n);
+      wipe(pin_in->p, pin_in->n);
     }
-    if (!arena_clean && ctx->prove_arena.p) {
+    if (!arena_clean && arena->p) {
       for (auto &ps : ctx->prove_aux_streams) (void)hipStreamSynchronize(ps);
       for (auto &ps : ctx->prove_streams) (void)hipStreamSynchronize(ps);
       for (auto &ps : ctx->prove_lane_streams) (void)hipStreamSynchronize(ps);
       if (ctx->prove_msm_stream) (void)hipStreamSynchronize(ctx->prove_msm_stream);
-      (void)hipMemsetAsync(ctx->prove_arena.p, 0, ctx->prove_arena.n, ctx->stream);  // (stream-ordered and waited for: the next
+      (void)hipMemsetAsync(arena->p, 0, arena->n, ctx->stream);  // (stream-ordered and waited for: the next
       (void)hipStreamSynchronize(ctx->stream);                                           // call's streams do not wait for the null stream)
     }
   }
@@ -326,7 +339,7 @@ struct ProveCall {
       take(u.d_expts, ct ? (size_t)ex_nt * nb * sizeof(ge) : 16);
       take(u.d_pow, ct ? (size_t)ex_nt * nb * BPP_CT_DIGITS * sizeof(ge) : 16);
       take(u.d_ctprod, ct ? (size_t)ex_nt * nb * sizeof(ge) : 16);
-      if (wants_states()) take(u.d_tstates, nb * BPP_STATE_ROW_WORDS * 4);  // (last, and only when asked for: the arena of every other call is laid out as before)
+      if (wants_states() || resident) take(u.d_tstates, nb * BPP_STATE_ROW_WORDS * 4);  // (last, and only when asked for -- a plan always asks: the arena of every other call is laid out as before)
       if (r.dev) {  // (as above)
         take(u.d_rows, nb * sizeof(ProveDevRow));
         take(u.d_finding, nb * 4);
@@ -349,14 +362,14 @@ struct ProveCall {
     // are written by nothing and wiped by nothing, and what hipMalloc hands out is not zero -- bpp_prove_secret_bytes (and
     // anyone reading the arena) must see zeros there, not somebody's left-overs
     // (a regrown arena may come back at the address the freed one had: the size tells, not the pointer alone)
-    const uint8_t *before = ctx->prove_arena.p;
-    const size_t before_n = ctx->prove_arena.n;
-    ctx->prove_arena.alloc(arena_need + 256);
-    if (ctx->prove_arena.p != before || ctx->prove_arena.n != before_n) {  // (on a stream of ours and waited for: the sub-batch streams do not wait for the null stream)
-      HIP_CHECK(hipMemsetAsync(ctx->prove_arena.p, 0, ctx->prove_arena.n, ctx->stream));
+    const uint8_t *before = arena->p;
+    const size_t before_n = arena->n;
+    arena->alloc(arena_need + 256);
+    if (arena->p != before || arena->n != before_n) {  // (on a stream of ours and waited for: the sub-batch streams do not wait for the null stream)
+      HIP_CHECK(hipMemsetAsync(arena->p, 0, arena->n, ctx->stream));
       HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
-    for (const Fix &f : fixes) f.set(f.field, ctx->prove_arena.p + f.off);
+    for (const Fix &f : fixes) f.set(f.field, arena->p + f.off);
   }
 
   // ---- fixed-base window tables for every generator of these parameters (one-off; contexts sharing P serialise here)
@@ -424,18 +437,22 @@ struct ProveCall {
   // witness byte passes through prove_pin_in), one outcome record per slot on the way out
   void stage_in_device() {
     auto up8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
-    ctx->prove_pin_in.resize(up8(pk.states.size()) + (size_t)B * (sizeof(ProveDesc) + sizeof(ProveDevRow)) + 64);
-    ctx->prove_pin_out.resize((size_t)B * sizeof(bpp_device_prove_status) + 64);
-    pin_states = ctx->prove_pin_in.p;
+    pin_in->resize(up8(pk.states.size()) + (size_t)B * (sizeof(ProveDesc) + sizeof(ProveDevRow)) + 64);
+    if (!resident) ctx->prove_pin_out.resize((size_t)B * sizeof(bpp_device_prove_status) + 64);
+    pin_states = pin_in->p;
     memcpy(pin_states, pk.states.data(), pk.states.size());
     pin_desc = pin_states + up8(pk.states.size());
     memcpy(pin_desc, pk.desc.data(), (size_t)B * sizeof(ProveDesc));
     pin_rows = pin_desc + (size_t)B * sizeof(ProveDesc);
     memcpy(pin_rows, r.dev->rows.data(), (size_t)B * sizeof(ProveDevRow));
+    if (resident) return;  // (a plan forks per enqueue, and nothing of it comes back to the host)
     pin_outcome = (bpp_device_prove_status *)ctx->prove_pin_out.p;
+    fork_from_ctx();
+  }
+  // whatever wrote the caller's arrays is complete on, or ordered before, the context's stream: every sub-batch's ingest kernel
+  // waits for this point of it
+  void fork_from_ctx() {
     if (!ctx->prove_dev_event) HIP_CHECK(hipEventCreateWithFlags(&ctx->prove_dev_event, hipEventDisableTiming));
-    // whatever wrote the caller's arrays is complete on, or ordered before, the context's stream: every sub-batch's ingest kernel
-    // waits for this point of it
     HIP_CHECK(hipEventRecord(ctx->prove_dev_event, ctx->stream));
   }
 
@@ -458,10 +475,13 @@ struct ProveCall {
     hipStream_t s = lane_stream(q);
     const uint32_t nb = u.nb;
     const bpp_prove_arrays &in = *r.dev->in;
+    // (a plan's enqueue: the whole sub-batch behind the fork -- the tables land in an arena range the previous enqueue's wipe, on this
+    // very stream, has left zero, and they bring back bit 0 of every descriptor's flags, which the ingest kernel sets)
+    if (resident) HIP_CHECK(hipStreamWaitEvent(s, ctx->prove_dev_event, 0));
     if (!pk.states.empty()) HIP_CHECK(hipMemcpyAsync(u.d_states, pin_states, pk.states.size(), hipMemcpyHostToDevice, s));  // (per-item transcripts: none)
     HIP_CHECK(hipMemcpyAsync(u.d_desc, pin_desc + (size_t)u.lo * sizeof(ProveDesc), (size_t)nb * sizeof(ProveDesc), hipMemcpyHostToDevice, s));
     HIP_CHECK(hipMemcpyAsync(u.d_rows, pin_rows + (size_t)u.lo * sizeof(ProveDevRow), (size_t)nb * sizeof(ProveDevRow), hipMemcpyHostToDevice, s));
-    HIP_CHECK(hipStreamWaitEvent(s, ctx->prove_dev_event, 0));
+    if (!resident) HIP_CHECK(hipStreamWaitEvent(s, ctx->prove_dev_event, 0));
     ProveIngest a;
     memset(&a, 0, sizeof(a));
     a.values = (const uint8_t *)in.values;
@@ -483,6 +503,7 @@ struct ProveCall {
     a.minpres = u.d_minpres;
     a.finding = u.d_finding;
     a.item_states = r.dev->item_states;
+    a.live = r.dev->live;
     hipLaunchKernelGGL(k_prove_ingest, dim3(cdiv(nb, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, a);
     HIP_CHECK(hipGetLastError());
   }
@@ -647,7 +668,7 @@ struct ProveCall {
     if (r.dev) emit_out(q);
     else copy_out(q);
     // zeroize the device copies of witness-derived data (the reference uses Zeroizing<> for these)
-    HIP_CHECK(hipMemsetAsync(ctx->prove_arena.p + u.arena_lo, 0, u.arena_len, s));
+    HIP_CHECK(hipMemsetAsync(arena->p + u.arena_lo, 0, u.arena_len, s));
   }
 
   // ---- sub-batch q's proofs, status words and made commitments to the page-locked staging ...
@@ -688,12 +709,15 @@ struct ProveCall {
     e.commitments_out = r.dev->commitments_out;
     e.commit_stride = r.dev->commit_stride;
     e.status_dev = r.dev->status_dev;
-    e.outcome = u.d_outcome;
+    e.outcome = resident ? nullptr : u.d_outcome;
+    e.ok_mask = r.dev->ok_mask;
+    e.outcome_item = r.dev->outcome_item;
     e.tstates = u.d_tstates;
     e.tstate_words = BPP_STATE_ROW_WORDS;
     e.states_out = r.dev->states_out;
     hipLaunchKernelGGL(k_prove_emit, dim3(cdiv(nb, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, e);
     HIP_CHECK(hipGetLastError());
+    if (resident) return;  // (the outcomes stay on the device: outcome_item, for k_prove_summary)
     HIP_CHECK(hipMemcpyAsync(pin_outcome + u.lo, u.d_outcome, (size_t)nb * sizeof(bpp_device_prove_status), hipMemcpyDeviceToHost, s));
   }
 
@@ -1481,9 +1505,11 @@ extern "C" int bpp_prove_openings_device_transcripts(bpp_ctx *ctx, uint64_t para
 }
 
 extern "C" int bpp_prove_status_result(const bpp_device_prove_status *host_copy, bpp_shard_result *out) {
-  if (!host_copy || !out || host_copy->msg > BPP_PROVE_MSG_ENGINE) return BPP_ERR_INVALID_ARGUMENT;
+  if (!host_copy || !out || host_copy->msg > BPP_PROVE_MSG_EMPTY) return BPP_ERR_INVALID_ARGUMENT;
   memset(out, 0, sizeof(*out));
-  shard_result_set(*out, host_copy->code, host_copy->msg ? BPP_TIER_CONSTRUCTION : BPP_TIER_NONE, -1, 0, prove_msg_text(host_copy->msg));
+  // (BPP_PROVE_MSG_EMPTY, a slot bpp_prove_enqueue's live mask switched off, is no finding: code 0, no tier, no text)
+  const bool finding = host_copy->msg != BPP_PROVE_MSG_OK && host_copy->msg != BPP_PROVE_MSG_EMPTY;
+  shard_result_set(*out, host_copy->code, finding ? BPP_TIER_CONSTRUCTION : BPP_TIER_NONE, -1, 0, prove_msg_text(host_copy->msg));
   return BPP_OK;
 }
 

@@ -33,6 +33,13 @@
 // A slot with ANY finding continues a fixed public state (203 zero bytes: a sponge at position 0) and nothing of its row but byte
 // 200 is ever read.  On the way out k_prove_emit turns the row kp_finish<true> left in the arena into the caller's 203 bytes for a
 // slot whose outcome is OK, and writes 203 zero bytes for every other one, refused items included (k_states_out's rule).
+//
+// THE LIVE MASK, THE OK MASK AND THE SUMMARY (bpp_prove_enqueue, engine_prove_plan.h): byte i of ProveIngest::live equal to zero makes
+// item i dead -- prove_ingest_check returns a key that carries BPP_PROVE_MSG_EMPTY before it touches any row of the item, so the slot
+// takes the failed slot's path (substitute witness, fixed public state, zeroed output ranges) with a code of 0.  k_prove_emit also
+// writes one byte per item, 1 where the outcome is OK (the live mask of the verifier's refill), and the outcome records in call
+// order; k_prove_summary reduces those to the record the blocking call's return code and message come from.  All null in the
+// blocking calls, which run as before.
 #pragma once
 #include "item_states.h"
 #include "prove_pack_host.h"
@@ -66,7 +73,11 @@ struct ProveIngest {
   uint8_t *minpres;
   uint32_t *finding;     // nb words: 0, or prove_ingest_key of the item's first finding
   const uint8_t *item_states;  // the caller's n x 203 bytes, row i = item i's transcript; null: one transcript for the call
+  const uint8_t *live;         // (bpp_prove_enqueue) n bytes by item, 0 = the item is dead: nothing of its rows is read; null: every item
 };
+
+// the live mask: a dead item's slot reads one byte of the mask and nothing else of the caller's
+BPP_HD bool prove_slot_dead(const ProveIngest &a, uint32_t k) { return a.live && a.live[a.rows[k].item] == 0; }
 
 BPP_HD bool prove_seed_present(const ProveIngest &a, size_t i) { return a.seed_nonces32 && (!a.seed_present || a.seed_present[i]); }
 
@@ -84,12 +95,16 @@ BPP_HD uint64_t prove_load_le64(const uint8_t *p) {
 #define BPP_PROVE_STAGE_BLINDINGS 2u
 #define BPP_PROVE_STAGE_SEED_NONCE 3u
 #define BPP_PROVE_STAGE_TRANSCRIPT 4u  // (per-item transcripts only) byte 200 of the item's row
+#define BPP_PROVE_STAGE_LIVE_MASK 0u   // (a live mask only) the item is dead: in front of everything, and nothing else is looked at
 BPP_HD uint32_t prove_ingest_key(uint32_t stage, uint32_t index, uint32_t msg) { return 0xffffffffu - ((stage << 28) | (index << 8) | msg); }
 BPP_HD uint32_t prove_ingest_key_msg(uint32_t key) { return key ? ((0xffffffffu - key) & 255u) : 0u; }
 BPP_HD uint32_t prove_key_max(uint32_t a, uint32_t b) { return a > b ? a : b; }
 
 // `lane`'s share of the witness checks of sorted slot k: the key of the first finding among what this lane looked at, 0 for none
 BPP_HD uint32_t prove_ingest_check(const ProveIngest &a, uint32_t k, uint32_t lane, uint32_t lanes) {
+  // a dead slot: its "finding" is BPP_PROVE_MSG_EMPTY -- the slot gets the substitute witness and the fixed public state as a
+  // failed one does, and k_prove_emit zeroes its ranges -- and no row of the item is touched, not even byte 200 of its state
+  if (prove_slot_dead(a, k)) return lane == 0 ? prove_ingest_key(BPP_PROVE_STAGE_LIVE_MASK, 0, BPP_PROVE_MSG_EMPTY) : 0u;
   const size_t i = a.rows[k].item, row = i * (size_t)a.m_stride;
   const uint32_t m = a.desc[k].m;
   const bool seed = prove_seed_present(a, i);
@@ -172,6 +187,10 @@ struct ProveEmit {
   const uint32_t *tstates;              // kp_finish<true>'s rows, by slot (null without slots or without states_out) ...
   uint32_t tstate_words;                // ... of BPP_STATE_ROW_WORDS words, whose first 203 bytes are the ABI's
   uint8_t *states_out;                  // by item: the caller's n x 203 bytes at any byte address; may be null
+  // (bpp_prove_enqueue, else null) by item, refused rows included: 1 where the outcome is OK, else 0 -- the live mask of the
+  // verifier's refill -- and the outcome records in call order, which k_prove_summary reads behind the join
+  uint8_t *ok_mask;
+  bpp_device_prove_status *outcome_item;
 };
 
 // the outcome of row k: the host's finding, else the ingest finding, else the proof's status bits as prove_mixed maps them
@@ -205,8 +224,46 @@ BPP_HD void prove_emit_row(const ProveEmit &e, uint32_t k, uint32_t lane, uint32
     const bpp_device_prove_status rec{prove_msg_code(msg), msg};
     if (e.status_dev) e.status_dev[r.item] = rec;
     if (e.outcome) e.outcome[k] = rec;
+    if (e.outcome_item) e.outcome_item[r.item] = rec;
+    if (e.ok_mask) e.ok_mask[r.item] = msg == BPP_PROVE_MSG_OK ? 1 : 0;
   }
 }
+
+// ---- the call's summary (bpp_prove_enqueue): a reduction over the outcome records in call order.  A finding is a record whose msg is
+// neither OK nor EMPTY; the summary names the first one -- the item whose code and message the blocking call returns -- and counts.
+struct ProveSummaryPart {
+  uint32_t first;  // the smallest index with a finding, 0xffffffff for none
+  uint32_t n_ok, n_failed, n_empty;
+};
+BPP_HD ProveSummaryPart prove_summary_none() { return ProveSummaryPart{0xffffffffu, 0u, 0u, 0u}; }
+BPP_HD ProveSummaryPart prove_summary_merge(const ProveSummaryPart &a, const ProveSummaryPart &b) {
+  return ProveSummaryPart{a.first < b.first ? a.first : b.first, a.n_ok + b.n_ok, a.n_failed + b.n_failed, a.n_empty + b.n_empty};
+}
+// `lane`'s share of the n records
+BPP_HD ProveSummaryPart prove_summary_scan(const bpp_device_prove_status *outcome, uint32_t n, uint32_t lane, uint32_t lanes) {
+  ProveSummaryPart p = prove_summary_none();
+  for (uint32_t i = lane; i < n; i += lanes) {
+    const uint32_t msg = outcome[i].msg;
+    if (msg == BPP_PROVE_MSG_OK) p.n_ok++;
+    else if (msg == BPP_PROVE_MSG_EMPTY) p.n_empty++;
+    else {
+      p.n_failed++;
+      if (i < p.first) p.first = i;
+    }
+  }
+  return p;
+}
+BPP_HD void prove_summary_write(bpp_device_prove_summary *out, const bpp_device_prove_status *outcome, const ProveSummaryPart &p) {
+  bpp_device_prove_summary s;
+  const bool found = p.first != 0xffffffffu;
+  s.code = found ? outcome[p.first].code : 0;
+  s.msg = found ? outcome[p.first].msg : 0u;
+  s.index = found ? p.first : 0u;
+  s.flags = BPP_PROVE_SUMMARY_WRITTEN;
+  s.n_ok = p.n_ok, s.n_failed = p.n_failed, s.n_empty = p.n_empty, s.reserved = 0;
+  *out = s;
+}
+#define BPP_PROVE_SUMMARY_BLOCK 256
 
 // ---- per-item transcripts: what k_prove_item_states reads and writes for sorted slot k of a sub-batch
 struct ProveItemStates {
@@ -283,6 +340,20 @@ __global__ void __launch_bounds__(BPP_INGEST_BLOCK) k_prove_emit(ProveEmit e) {
   const size_t gid = (size_t)blockIdx.x * BPP_INGEST_BLOCK + threadIdx.x;
   const size_t k = gid / BPP_INGEST_LANES;
   if (k < e.n) prove_emit_row(e, (uint32_t)k, (uint32_t)(gid % BPP_INGEST_LANES), BPP_INGEST_LANES);
+}
+
+// On the context's stream behind the join of every sub-batch stream: one block over the n outcome records, a tree in LDS, one
+// record out.  Public data in, public data out.
+__global__ void __launch_bounds__(BPP_PROVE_SUMMARY_BLOCK) k_prove_summary(const bpp_device_prove_status *outcome, uint32_t n,
+                                                                          bpp_device_prove_summary *out) {
+  __shared__ ProveSummaryPart part[BPP_PROVE_SUMMARY_BLOCK];
+  part[threadIdx.x] = prove_summary_scan(outcome, n, threadIdx.x, BPP_PROVE_SUMMARY_BLOCK);
+  __syncthreads();
+  for (uint32_t o = BPP_PROVE_SUMMARY_BLOCK / 2; o; o >>= 1) {
+    if (threadIdx.x < o) part[threadIdx.x] = prove_summary_merge(part[threadIdx.x], part[threadIdx.x + o]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) prove_summary_write(out, outcome, part[0]);
 }
 #endif
 
@@ -386,6 +457,15 @@ inline void prove_ingest_run_host(const ProveIngest &a, uint32_t lanes) {
     for (uint32_t lane = 0; lane < lanes; lane++) prove_ingest_move(a, k, key != 0, lane, lanes);
     a.finding[k] = key;
   }
+}
+
+// k_prove_summary on the host: the same scan per lane, merged as the tree merges
+inline void prove_summary_run_host(const bpp_device_prove_status *outcome, uint32_t n, uint32_t lanes, bpp_device_prove_summary *out) {
+  std::vector<ProveSummaryPart> part(lanes);
+  for (uint32_t lane = 0; lane < lanes; lane++) part[lane] = prove_summary_scan(outcome, n, lane, lanes);
+  for (uint32_t o = lanes / 2; o; o >>= 1)
+    for (uint32_t lane = 0; lane < o; lane++) part[lane] = prove_summary_merge(part[lane], part[lane + o]);
+  prove_summary_write(out, outcome, part[0]);
 }
 
 }  // namespace bpp

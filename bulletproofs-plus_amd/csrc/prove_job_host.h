@@ -31,7 +31,8 @@ inline size_t prove_item_len_host(const ParamShape &P, uint32_t m) {
 // prove entry point.  The device form (prove_ingest.h) carries the id in its finding words and status records.
 BPP_HD int prove_msg_code(uint32_t msg) {
   switch (msg) {
-    case BPP_PROVE_MSG_OK: return BPP_OK;
+    case BPP_PROVE_MSG_OK:
+    case BPP_PROVE_MSG_EMPTY: return BPP_OK;  // (a slot the live mask of bpp_prove_enqueue switched off: no finding)
     case BPP_PROVE_MSG_BITS:
     case BPP_PROVE_MSG_PROOF_STRIDE:
     case BPP_PROVE_MSG_COMMIT_STRIDE:
@@ -60,7 +61,8 @@ inline const char *prove_msg_text(uint32_t msg) {
                                      "transcript state has pos >= rate",
                                      "Witness opening is invalid!",
                                      "Identity element cannot be added to the transcript / zero challenge",
-                                     "engine fault: see bpp_ctx_last_error"};
+                                     "engine fault: see bpp_ctx_last_error",
+                                     ""};
   return msg < sizeof(text) / sizeof(text[0]) ? text[msg] : "unknown finding";
 }
 

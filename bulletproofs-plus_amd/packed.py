@@ -534,6 +534,136 @@ def prove_device_stats(engine):
     return {k: int(getattr(s, k)) for k, _ in _lib.ProveDeviceStats._fields_}
 
 
+PROVE_PLAN_ITEM_STATES = 1
+PROVE_SUMMARY_WRITTEN = 1
+PROVE_MSG_EMPTY = 17
+
+
+class ProvePlan:
+    """A resident prove plan (bpp_prove_plan_create): the shape of a prove call from device arrays -- m (a HOST array), the strides,
+    which optional arrays every call brings, the call's one transcript (label= / state=) or item_states=True for one transcript
+    row per item -- planned, carved and staged once.  enqueue() then proves a DeviceOpenings of that shape on the engine's stream
+    without any host work of size n and without waiting (bpp_prove_enqueue).  `.proof_lens` and `.host_status` (the code of an item
+    the host refuses from m alone, else 0) are known from here on.  close() waits for the plan's work and frees it."""
+
+    def __init__(self, engine, params, m, m_stride=None, rng_stride=None, commitments=False, min_values=False, min_present=False,
+                 seed_nonces=False, seed_present=False, label=b"", state=None, item_states=False, commit_stride=None, proof_stride=None):
+        self.engine, self.params = engine, params
+        self.m = np.ascontiguousarray(_host_array(m), dtype=np.uint32)
+        n, t, n_bits = self.m.shape[0], int(params.extension_degree()), params.bit_length()
+        m_top = max(int(self.m.max()), 1) if n else 1
+        self.m_stride = int(m_stride) if m_stride is not None else m_top
+        rounds_top = max((n_bits * min(m_top, self.m_stride) - 1).bit_length(), 0)
+        self.rng_stride = int(rng_stride) if rng_stride is not None else 32 * (rounds_top + 3)
+        self.commit_stride = int(commit_stride) if commit_stride is not None else 32 * self.m_stride
+        self.proof_stride = int(proof_stride) if proof_stride is not None else 1 + 32 * (t + 5 + 2 * rounds_top)
+        self.n, self.t, self.item_states = n, t, bool(item_states)
+        self._label = np.frombuffer(bytes(label), dtype=np.uint8).copy() if len(label) else np.zeros(1, dtype=np.uint8)
+        self._state = None if state is None else np.frombuffer(bytes(state), dtype=np.uint8).copy()
+        self.label_bytes, self.state_bytes = bytes(label), (None if state is None else bytes(state))
+        given = lambda flag: ctypes.c_void_p(1) if flag else None  # noqa: E731  (read for "will be given" alone)
+        shape = _lib.ProveArrays(n, self.m.ctypes.data, self.m_stride, given(True), given(True), given(commitments), given(min_values),
+                                 given(min_present), given(seed_nonces), given(seed_present), given(True), self.rng_stride,
+                                 None if (self._state is None or item_states) else self._state.ctypes.data,
+                                 None if item_states else self._label.ctypes.data, 0 if item_states else len(label))
+        handle = c_uint64()
+        err = ctypes.create_string_buffer(256)
+        api._check(engine.lib.bpp_prove_plan_create(engine.ctx, params.handle, byref(shape), self.commit_stride, self.proof_stride,
+                                                    PROVE_PLAN_ITEM_STATES if item_states else 0, byref(handle), err, 256), engine.ctx, err)
+        self.handle = handle.value
+        self.proof_lens = np.zeros(n, dtype=np.uintp)
+        self.host_status = np.zeros(n, dtype=np.intc)
+        api._check(engine.lib.bpp_prove_plan_shape(engine.ctx, self.handle, self.proof_lens.ctypes.data_as(POINTER(c_size_t)),
+                                                   self.host_status.ctypes.data_as(POINTER(ctypes.c_int))), engine.ctx)
+
+    def enqueue(self, openings, live=None, states=False, commitments_out=None, proofs_out=None, status_out=None, ok_mask=None,
+                summary=None, shape_vector=False):
+        """bpp_prove_enqueue over a DeviceOpenings of the plan's shape.  What wrote the arrays must be ordered before the engine's stream:
+        an engine made on torch's current stream has that by construction and nothing is synchronised; otherwise torch's current
+        stream is synchronised first (openings.order_before; with raw addresses the caller orders).  live: a contiguous uint8
+        device tensor of n bytes (0 = dead: the item's rows are never read), or None.  states: True or a uint8 [n, 203] device tensor
+        -- the advanced transcripts.  The outputs default to fresh tensors.  shape_vector=True passes the openings' m for the
+        engine to compare with the plan's; the default passes none ("the plan's own").  Returns a ProveEnqueued."""
+        import torch
+        eng, n = self.engine, self.n
+        dev = torch.device("cuda", int(eng.device))
+        if commitments_out is None:
+            commitments_out = torch.zeros((n, self.commit_stride), dtype=torch.uint8, device=dev)
+        if proofs_out is None:
+            proofs_out = torch.zeros((n, self.proof_stride), dtype=torch.uint8, device=dev)
+        if status_out is None:
+            status_out = torch.zeros((n, 2), dtype=torch.int32, device=dev)
+        if ok_mask is None:
+            ok_mask = torch.zeros((n,), dtype=torch.uint8, device=dev)
+        if summary is None:
+            summary = torch.zeros((8,), dtype=torch.int32, device=dev)
+        if states is True:
+            states = torch.zeros((n, 203), dtype=torch.uint8, device=dev)
+        elif states is False:
+            states = None
+        addr = lambda a: None if a is None else ctypes.c_void_p(a.data_ptr() if hasattr(a, "data_ptr") else int(a))  # noqa: E731
+        st = openings.struct_without_transcript()
+        if not shape_vector:
+            st.m = None
+        openings.order_before(eng)
+        ticket = c_uint64()
+        api._check(eng.lib.bpp_prove_enqueue(eng.ctx, self.handle, byref(st), openings.item_states, addr(live), addr(commitments_out),
+                                             addr(proofs_out), addr(states), addr(status_out), addr(ok_mask), addr(summary), byref(ticket)),
+                   eng.ctx)
+        return ProveEnqueued(self, openings, ticket.value, commitments_out, proofs_out, status_out, ok_mask, summary, states, live)
+
+    def close(self):
+        if self.handle:
+            self.engine.lib.bpp_prove_plan_destroy(self.engine.ctx, self.handle)
+            self.handle = 0
+
+
+class ProveEnqueued:
+    """What ProvePlan.enqueue returns: `.proofs`, `.commitments`, `.status` (int32 [n, 2]: code, message id), `.ok_mask` (uint8 [n]),
+    `.summary` (int32 [8]: code, message id, index, flags, n_ok, n_failed, n_empty, 0) and `.states` -- device tensors, valid in
+    stream order behind the call -- and the ticket: done() is one event query, wait() blocks until the call has run, result() waits
+    and returns the summary as a dict with the blocking call's code and text."""
+
+    def __init__(self, plan, inp, ticket, commitments, proofs, status, ok_mask, summary, states, live):
+        self.plan, self.inp, self.engine, self.ticket = plan, inp, plan.engine, ticket
+        self.commitments, self.proofs, self.status, self.ok_mask, self.summary, self.states = commitments, proofs, status, ok_mask, summary, states
+        self.live, self.proof_lens, self.m = live, plan.proof_lens, plan.m
+
+    def done(self):
+        d = ctypes.c_int()
+        api._check(self.engine.lib.bpp_enqueue_done(self.engine.ctx, self.ticket, byref(d)), self.engine.ctx)
+        return bool(d.value)
+
+    def wait(self):
+        api._check(self.engine.lib.bpp_enqueue_wait(self.engine.ctx, self.ticket), self.engine.ctx)
+
+    def result(self):
+        self.wait()
+        host = np.ascontiguousarray(self.summary.cpu().numpy())
+        r = _lib.ShardResult()
+        api._check(self.engine.lib.bpp_prove_summary_result(host.ctypes.data_as(POINTER(_lib.DeviceProveSummary)), byref(r)), None)
+        return {"code": r.code, "msg": r.msg.decode(errors="replace"), "msg_id": int(host[1]), "index": int(host[2]), "flags": int(host[3]),
+                "n_ok": int(host[4]), "n_failed": int(host[5]), "n_empty": int(host[6])}
+
+    def as_mixed_input(self):
+        """a DeviceMixedInput over the output tensors -- nothing is copied -- under the transcripts the proofs were made under, with
+        `.live` = the ok mask: ResidentBatch.refill takes it as the refill's live mask, so that a failed item never reaches the
+        verifier as a parse finding"""
+        if self.inp.item_states is not None:
+            inp = DeviceProved.as_mixed_input(self)
+        else:
+            inp = DeviceProved.as_mixed_input(self, label=self.plan.label_bytes, state=self.plan.state_bytes)
+        inp.live = self.ok_mask
+        return inp
+
+
+def prove_enqueue_stats(engine):
+    """bpp_prove_enqueue_stats as a dict: calls, first_calls, host_waits, allocations"""
+    s = _lib.ProveEnqueueStats()
+    api._check(engine.lib.bpp_prove_enqueue_stats(engine.ctx, byref(s)), engine.ctx)
+    return {k: int(getattr(s, k)) for k, _ in _lib.ProveEnqueueStats._fields_}
+
+
 def device_pointer_kind(engine, address):
     """bpp_device_pointer_check: 0 this engine's device memory, 1 another device's, 2 host or unknown, 3 managed (launches nothing)"""
     kind = ctypes.c_int(-1)
@@ -1062,6 +1192,8 @@ class ResidentBatch(api.ResidentBatch):
         An `inp` made with item_states= (bpp_batch_refill_enqueue_transcripts / _mixed_transcripts) refills a batch that was uploaded
         with per-item transcripts, and only such a batch: every refill brings the rows of its items, `count` and `live` as above."""
         import torch
+        if live is None and count is None:
+            live = getattr(inp, "live", None)  # (ProveEnqueued.as_mixed_input: the prover's ok mask comes with the outputs)
         if live is not None and count is not None:
             raise api.ProofError(api.ProofErrorKind.InvalidArgument, "count and live: a refill takes a live count or a live mask, not both")
         dev = torch.device("cuda", int(self.engine.device))

@@ -966,6 +966,83 @@ struct bpp_prove_device_stats {
 };
 int bpp_prove_device_stats(bpp_ctx *ctx, struct bpp_prove_device_stats *out);
 
+/* ---- Proving ON THE STREAM from a RESIDENT PLAN: bpp_prove_openings_device(_transcripts) without its host work per call.  The plan
+ * keeps the shape of a call -- n_items, m[], the strides, which optional arrays are given, the call's one transcript -- and does ONCE
+ * what the blocking call does per call from host knowledge: the per-item host checks, the sort by aggregation factor, the layout, the
+ * sub-batch cut and the arena (the plan's own, zeroed once), the fixed-base table, the streams, the refused-items table and the
+ * sorted descriptor / row / state tables, which stay in page-locked memory of the plan that no later call rewrites.
+ * bpp_prove_plan_create: `shape` is read for its geometry only; no device array of it is dereferenced or classified, a non-NULL pointer
+ * means "will be given".  m must be host memory and is copied.  The transcript (label, or 203-byte state: pos >= 166 refuses the plan
+ * as it refuses the blocking call) is copied too.  flags: BPP_PROVE_PLAN_ITEM_STATES -- every enqueue brings one transcript row per
+ * item, and shape's transcript fields must be NULL.  The plan takes the context's options as they are now ("ct", "prove_parts",
+ * "prove_subs", "prove_fused", ...), as the prove lanes do; "prove_check" = 1 refuses the plan with the blocking call's text.  An
+ * m_stride below an m[i] the layout holds refuses the plan, as it refuses the blocking call.
+ * bpp_prove_plan_shape: proof_lens[i] and (host_status, may be NULL) the code of an item the host's part of the checks refuses, else
+ * 0 -- functions of m[] and the strides: the host learns nothing per step.
+ * bpp_prove_plan_destroy waits for the plan's work in flight and frees what it owns; bpp_ctx_destroy does the same for every plan.
+ *
+ * bpp_prove_enqueue.  THE CONTRACT: for every live item the call writes what bpp_prove_openings_device_transcripts writes on the same
+ * arrays -- proof bytes, commitment bytes, the status record, the state row, zeroed slots for failed and refused items; row slack is
+ * neither read nor written; the plan's strides are the call's.  in_dev must repeat the plan's shape (n_items, m_stride, rng_stride,
+ * the same optional arrays given); m is NULL ("the plan's own": the host touches nothing of size N) or a HOST array equal to the
+ * plan's (the first differing index is named).  in_dev's transcript fields are not read (they must be NULL on an ITEM_STATES plan):
+ * the transcript is the plan's.
+ * live_dev (n device bytes, or NULL = every item): byte i == 0 makes item i DEAD.  Nothing of its rows is read -- no value, blinding
+ * factor, nonce, rng byte or state byte -- its slot runs the substitute witness (it costs what a live slot costs: the launch geometry
+ * never depends on the mask), its proof, commitment and state ranges are zeroed and its status is {0, BPP_PROVE_MSG_EMPTY}.  (An item
+ * the host refuses from m[] keeps its finding whatever the mask says.)
+ * ok_mask_dev (n device bytes, or NULL): byte i = 1 where item i's outcome is OK, else 0 (failed, refused and dead items): the mask
+ * bpp_batch_refill_enqueue_mixed(..., live_dev = ok_mask_dev, ...) takes as it is.
+ * summary_dev (or NULL): one record written behind everything else.  index = the smallest item index whose outcome is a finding, code
+ * and msg that item's -- the return code and message of the blocking call -- and the counts; without a finding {0, 0, 0, WRITTEN, ...}.
+ * bpp_prove_summary_result gives a host copy the blocking call's text (tier BPP_TIER_CONSTRUCTION, index = the item).
+ * ORDERING: the call enqueues behind everything on the context's stream and returns.  Its sub-batch streams fork from an event
+ * recorded on the context's stream and every one of them is joined back into it behind its arena wipe: the next operation on the
+ * context's stream -- a refill, a caller's kernel on a bpp_ctx_create_on_stream context, the next enqueue -- sees complete outputs.
+ * Not capturable into a HIP graph.  Blocking prove calls on the same context stay legal; the shared streams order them.
+ * STEADY STATE: after a plan's first enqueue the call allocates nothing, copies nothing to the host and waits for nothing
+ * (bpp_prove_enqueue_stats: host_waits stays 0, allocations and first_calls stay); it enqueues small host-to-device copies of the
+ * plan's constant tables from the plan's page-locked memory, which also put back what a kernel changed in them.
+ * REFUSED before any launch (BPP_ERR_INVALID_ARGUMENT, the field named in bpp_ctx_last_error): a given array, output, live_dev,
+ * ok_mask_dev or summary_dev that is not BPP_PTR_THIS_DEVICE memory; proofs_out_dev or commitments_out_dev NULL; item_states_dev given
+ * without the flag or missing with it; an optional array given or absent against the plan; a shape field that differs; overlapping
+ * state ranges.  An unknown plan is BPP_ERR_BAD_HANDLE.  A refused call leaves the counters alone.
+ * TICKETS are those of bpp_enqueue_done / bpp_enqueue_wait.
+ * SECRETS: nothing witness-derived exists in host memory; every sub-batch's arena range is zeroed on its stream behind its last
+ * kernel.  bpp_prove_secret_bytes covers the plans' arenas and reads 0 once the ticket is done.  On a HIP error inside the call the
+ * arena is wiped before the call returns (that path alone synchronises, and counts a host wait). */
+#define BPP_PROVE_PLAN_ITEM_STATES 1u
+int bpp_prove_plan_create(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays *shape, size_t commit_stride, size_t proof_stride,
+                          uint32_t flags, uint64_t *plan, char *errbuf, size_t errbuf_len);
+int bpp_prove_plan_shape(bpp_ctx *ctx, uint64_t plan, size_t *proof_lens /* HOST out, n_items */,
+                         int *host_status /* HOST out, n_items; may be NULL */);
+int bpp_prove_plan_destroy(bpp_ctx *ctx, uint64_t plan);
+typedef struct {
+  int32_t code;   /* the blocking call's return code: the first failing item's, 0 without one */
+  uint32_t msg;   /* its BPP_PROVE_MSG_* id */
+  uint32_t index; /* that item */
+  uint32_t flags; /* BPP_PROVE_SUMMARY_WRITTEN */
+  uint32_t n_ok, n_failed, n_empty, reserved;
+} bpp_device_prove_summary; /* 32 bytes */
+#define BPP_PROVE_SUMMARY_WRITTEN 1u
+#define BPP_PROVE_MSG_EMPTY 17u /* a slot the live mask switched off: code 0 */
+int bpp_prove_enqueue(bpp_ctx *ctx, uint64_t plan, const bpp_prove_arrays *in_dev,
+                      const uint8_t *item_states_dev,      /* DEVICE n x 203, iff the plan has BPP_PROVE_PLAN_ITEM_STATES */
+                      const uint8_t *live_dev,             /* DEVICE n bytes, or NULL: every item */
+                      uint8_t *commitments_out_dev, uint8_t *proofs_out_dev,
+                      uint8_t *states_out_dev,             /* DEVICE n x 203, or NULL */
+                      bpp_device_prove_status *status_dev, /* DEVICE n, or NULL */
+                      uint8_t *ok_mask_dev,                /* DEVICE n bytes, or NULL */
+                      bpp_device_prove_summary *summary_dev /* DEVICE, or NULL */, uint64_t *ticket /* or NULL */);
+int bpp_prove_summary_result(const bpp_device_prove_summary *host_copy, bpp_shard_result *out);
+struct bpp_prove_enqueue_stats {
+  uint64_t calls;       /* enqueues that passed the refusals */
+  uint64_t first_calls; /* of them, the first of their plan */
+  uint64_t host_waits;  /* times an enqueue waited for the device: 0 unless a HIP error made it wipe the arena */
+  uint64_t allocations; /* allocations made inside an enqueue (the context's ticket events, once) */
+};
+int bpp_prove_enqueue_stats(bpp_ctx *ctx, struct bpp_prove_enqueue_stats *out);
+
 /* bpp_prove_pool: many host threads, each with a few proofs per call (one output of a wallet service, say).  A call of one proof
  * is a chain of latency-bound launches; the pool hands the calls that are waiting to ONE bpp_prove_batch_mixed on one of `lanes`
  * contexts (the first is ctx; the others are made here with ctx's options as they are now).  No thread of its own: whichever

@@ -267,6 +267,80 @@ class Engine {
     return s;
   }
 
+  // Stream-ordered proving from device arrays on a resident plan (bpp_prove_plan_create / bpp_prove_enqueue).  The plan keeps the
+  // shape of a call -- `shape` is read for its geometry alone: n_items, the host array m, the strides, which arrays are non-null, the
+  // call's one transcript -- and does the blocking call's host work once.  It is destroyed with the object (bpp_prove_plan_destroy,
+  // which waits for its work in flight) and must not outlive the engine.
+  class ProvePlan {
+   public:
+    ProvePlan() = default;
+    ProvePlan(ProvePlan &&o) noexcept : ctx_(o.ctx_), handle_(o.handle_), n_(o.n_) { o.handle_ = 0; }
+    ProvePlan &operator=(ProvePlan &&o) noexcept {
+      if (this != &o) {
+        reset();
+        ctx_ = o.ctx_, handle_ = o.handle_, n_ = o.n_;
+        o.handle_ = 0;
+      }
+      return *this;
+    }
+    ProvePlan(const ProvePlan &) = delete;
+    ProvePlan &operator=(const ProvePlan &) = delete;
+    ~ProvePlan() { reset(); }
+    uint64_t handle() const { return handle_; }
+    size_t n_items() const { return n_; }
+    // proof_lens[i], and the code of an item the host refuses from m[] and the strides (0 for every other one)
+    std::vector<size_t> proof_lens(std::vector<int> *host_status = nullptr) const {
+      std::vector<size_t> lens(n_);
+      if (host_status) host_status->assign(n_, 0);
+      const int rc = bpp_prove_plan_shape(ctx_, handle_, lens.data(), host_status ? host_status->data() : nullptr);
+      check(rc, bpp_ctx_last_error(ctx_));
+      return lens;
+    }
+    void reset() {
+      if (handle_) (void)bpp_prove_plan_destroy(ctx_, handle_);
+      handle_ = 0;
+    }
+
+   private:
+    friend class Engine;
+    bpp_ctx *ctx_ = nullptr;
+    uint64_t handle_ = 0;
+    size_t n_ = 0;
+  };
+  ProvePlan prove_plan_create(uint64_t params, const bpp_prove_arrays &shape, size_t commit_stride, size_t proof_stride, uint32_t flags = 0) {
+    ProvePlan p;
+    char err[256] = {0};
+    check(bpp_prove_plan_create(ctx_, params, &shape, commit_stride, proof_stride, flags, &p.handle_, err, sizeof(err)), err);
+    p.ctx_ = ctx_;
+    p.n_ = shape.n_items;
+    return p;
+  }
+  // What an enqueue writes, all of it DEVICE memory; only the first two are required
+  struct ProveEnqueueOutputs {
+    uint8_t *commitments = nullptr, *proofs = nullptr;
+    uint8_t *states = nullptr;                   // n x 203
+    bpp_device_prove_status *status = nullptr;   // n
+    uint8_t *ok_mask = nullptr;                  // n bytes: the live mask of the verifier's refill
+    bpp_device_prove_summary *summary = nullptr;
+  };
+  // in_dev repeats the plan's shape (m may be null: the plan's own); item_states_dev iff the plan has BPP_PROVE_PLAN_ITEM_STATES;
+  // live_dev: n device bytes, 0 = dead, or null.  Enqueues behind everything on the engine's stream and returns; the ticket is an
+  // enqueue ticket (results() is not for it: bpp_prove_summary_result reads a host copy of the summary).
+  EnqueueTicket prove_enqueue(const ProvePlan &plan, const bpp_prove_arrays &in_dev, const ProveEnqueueOutputs &out,
+                              const uint8_t *item_states_dev = nullptr, const uint8_t *live_dev = nullptr) {
+    EnqueueTicket t;
+    t.ctx_ = ctx_;
+    const int rc = bpp_prove_enqueue(ctx_, plan.handle(), &in_dev, item_states_dev, live_dev, out.commitments, out.proofs, out.states, out.status,
+                                     out.ok_mask, out.summary, &t.id);
+    check(rc, bpp_ctx_last_error(ctx_));
+    return t;
+  }
+  struct bpp_prove_enqueue_stats prove_enqueue_stats() const {
+    struct bpp_prove_enqueue_stats s{};
+    check(::bpp_prove_enqueue_stats(ctx_, &s), bpp_ctx_last_error(ctx_));
+    return s;
+  }
+
  private:
   bpp_ctx *ctx_ = nullptr;
 };

@@ -140,6 +140,33 @@ pub struct bpp_prove_device_stats {
     pub host_findings: u64,
 }
 
+/// bpp_device_prove_summary: the one record of a `bpp_prove_enqueue`, 32 bytes, as it lies in device memory
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_device_prove_summary {
+    pub code: i32,
+    pub msg: u32,
+    pub index: u32,
+    pub flags: u32,
+    pub n_ok: u32,
+    pub n_failed: u32,
+    pub n_empty: u32,
+    pub reserved: u32,
+}
+pub const BPP_PROVE_PLAN_ITEM_STATES: u32 = 1;
+pub const BPP_PROVE_SUMMARY_WRITTEN: u32 = 1;
+pub const BPP_PROVE_MSG_EMPTY: u32 = 17;
+
+/// `struct bpp_prove_enqueue_stats`: what the stream-ordered prove calls of a context cost the host
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_prove_enqueue_stats {
+    pub calls: u64,
+    pub first_calls: u64,
+    pub host_waits: u64,
+    pub allocations: u64,
+}
+
 #[repr(C)]
 pub struct bpp_comm {
     _p: [u8; 0],
@@ -497,6 +524,16 @@ extern "C" {
                                                  item_status: *mut c_int, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
     pub fn bpp_prove_status_result(host_copy: *const bpp_device_prove_status, out: *mut bpp_shard_result) -> c_int;
     pub fn bpp_prove_device_stats(ctx: *mut bpp_ctx, out: *mut bpp_prove_device_stats) -> c_int;
+    pub fn bpp_prove_plan_create(ctx: *mut bpp_ctx, params: u64, shape: *const bpp_prove_arrays, commit_stride: usize,
+                                 proof_stride: usize, flags: u32, plan: *mut u64, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_prove_plan_shape(ctx: *mut bpp_ctx, plan: u64, proof_lens: *mut usize, host_status: *mut c_int) -> c_int;
+    pub fn bpp_prove_plan_destroy(ctx: *mut bpp_ctx, plan: u64) -> c_int;
+    pub fn bpp_prove_enqueue(ctx: *mut bpp_ctx, plan: u64, in_dev: *const bpp_prove_arrays, item_states_dev: *const u8,
+                             live_dev: *const u8, commitments_out_dev: *mut u8, proofs_out_dev: *mut u8, states_out_dev: *mut u8,
+                             status_dev: *mut bpp_device_prove_status, ok_mask_dev: *mut u8,
+                             summary_dev: *mut bpp_device_prove_summary, ticket: *mut u64) -> c_int;
+    pub fn bpp_prove_summary_result(host_copy: *const bpp_device_prove_summary, out: *mut bpp_shard_result) -> c_int;
+    pub fn bpp_prove_enqueue_stats(ctx: *mut bpp_ctx, out: *mut bpp_prove_enqueue_stats) -> c_int;
     pub fn bpp_prove_pool_openings(p: *mut bpp_prove_pool, items: *const bpp_prove_item, n_items: usize, commitments_out: *mut u8,
                                    commit_stride: usize, proofs_out: *mut u8, proof_stride: usize, proof_lens: *mut usize,
                                    errbuf: *mut c_char, errbuf_len: usize) -> c_int;

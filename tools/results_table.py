@@ -61,6 +61,77 @@ def prove_device_section():
     return out + [""]
 
 
+def prove_enqueue_section():
+    """profiles/prove_enqueue.json (a list of runs of tools/bench_prove_enqueue.py): per shape, every arm over the runs of this tree's
+    library; the runs of another library (BPP_LIB_PATH: the parent commit's, blocking arm only) in a table of their own"""
+    f = os.path.join(P, "prove_enqueue.json")
+    out = ["## Proving on the stream from a resident plan against the blocking call (`bpp_prove_enqueue`, `tools/bench_prove_enqueue.py`, "
+           "`profiles/prove_enqueue.json`)", ""]
+    if not os.path.exists(f):
+        return out + ["unmeasured", ""]
+    runs = json.load(open(f))
+    solo = lambda r: list(r["shapes"][0]["arms"]) == ["blocking"]  # noqa: E731  (a run of the A/B: the blocking arm alone)
+    mine = [r for r in runs if r["library"] == "this tree" and not solo(r)]
+    ab_mine = [r for r in runs if r["library"] == "this tree" and solo(r)]
+    other = [r for r in runs if r["library"] != "this tree"]
+    one = (mine or runs)[0]
+    out += ["One thread, one context on a caller's stream, %d items per step at %d bits; the arms alternate in one process after a warm-up, "
+            "%d rounds of %d steps per run, median (lowest-highest round) over the runs; host ms in the calls: wall time until the step's calls "
+            "had returned (a blocking arm: the whole step); thread CPU: the calling thread's CPU time over the whole step, the wait included "
+            "(`bpp_enqueue_wait` is the runtime's spinning event wait, the blocking call naps through most of its own).  "
+            "`enqueue`: plan.enqueue + ticket wait; `+verify`: the blocking prove, a mixed device upload and a resident verification "
+            "against enqueue, refill under the prover's ok mask, `bpp_verify_enqueue` and one wait.  Box: recorded by the tool as \"%s\".  "
+            "A record: the kernels are the same, so equal GPU time and less host time was the expectation, not a speed-up." %
+            (one["items"], one["n_bits"], one["reps"], one["inner"], one["box"]), "",
+            "| shape | arm | ms per step | proofs/s | host ms in the step's calls | thread CPU ms per step |", "|---|---|---|---|---|---|"]
+
+    def table(group):
+        lines = []
+        for shape in [r["shape"] for r in group[0]["shapes"]]:
+            rows = [r for run in group for r in run["shapes"] if r["shape"] == shape]
+            for arm in rows[0]["arms"]:
+                have = [r["arms"][arm] for r in rows if arm in r["arms"]]
+                med = statistics.median(a["ms_per_step"] for a in have)
+                lines.append("| %s (m = %d, t = %d%s) | %s | %.3f (%.3f-%.3f) | %.1f k | %.3f | %.3f |" %
+                             (shape, rows[0]["m"], rows[0]["t"], ", nonces" if rows[0]["nonces"] else "", arm, med, min(a["ms_low"] for a in have),
+                              max(a["ms_high"] for a in have), group[0]["items"] / med, statistics.median(a["host_ms_in_calls"] for a in have),
+                              statistics.median(a["host_cpu_ms_per_step"] for a in have)))
+        return lines
+
+    if mine:
+        out += table(mine)
+        med = lambda shape, arm: statistics.median(r["arms"][arm]["ms_per_step"] for run in mine for r in run["shapes"]  # noqa: E731
+                                                   if r["shape"] == shape and arm in r["arms"])
+        shapes = [r["shape"] for r in mine[0]["shapes"] if all(a in r["arms"] for a in ("blocking", "enqueue", "blocking+verify", "enqueue+verify"))]
+        if shapes:
+            out += ["", "What the verification adds to each prove arm, from the medians above: " +
+                    "; ".join("%s: %.3f ms behind the blocking prove (upload + `bpp_verify_resident`), %.3f ms behind the enqueued one (refill + "
+                              "`bpp_verify_enqueue`)" % (s, med(s, "blocking+verify") - med(s, "blocking"), med(s, "enqueue+verify") - med(s, "enqueue"))
+                              for s in shapes) +
+                    ".  The `enqueue+verify` step is SLOWER than `blocking+verify`, and the prove arms say where: not in the fork and join (the "
+                    "enqueued prove alone is no slower than the blocking one) but in the verifier's own two forms -- one enqueued verification of "
+                    "1024 proofs is a latency chain of about 3 ms whichever prover fed it (the refill section above: 3.1 ms per step for a refill "
+                    "and `bpp_verify_enqueue` of 1024 proofs from one thread), the blocking upload and resident verification of the same batch the "
+                    "smaller figure.  What the enqueue form buys is the calling thread: a third of a millisecond in its calls per step.  No kernel "
+                    "timeline of the step was taken."]
+        last =[r for r in mine[-1]["shapes"] if "stats_after" in r]
+        if last:
+            b, a = last[-1]["stats_before"], last[-1]["stats_after"]
+            out += ["", "Counters over the timed steps of the last run's last shape: `bpp_prove_enqueue_stats` calls %d -> %d, first_calls %d -> %d, "
+                    "host_waits %d -> %d, allocations %d -> %d; refill host_waits %d -> %d; `bpp_enqueue_stats` host_waits %d -> %d." %
+                    (b["prove_enqueue"]["calls"], a["prove_enqueue"]["calls"], b["prove_enqueue"]["first_calls"], a["prove_enqueue"]["first_calls"],
+                     b["prove_enqueue"]["host_waits"], a["prove_enqueue"]["host_waits"], b["prove_enqueue"]["allocations"],
+                     a["prove_enqueue"]["allocations"], b["refill"]["host_waits"], a["refill"]["host_waits"], b["enqueue"]["host_waits"],
+                     a["enqueue"]["host_waits"])]
+    if other:
+        out += ["", "The blocking call of this tree against the parent commit's library (`tools/gpu_ab.py --leg cmd`, the builds alternating on one "
+                "box, a process per run with the blocking arm alone; the parent's rows are runs with `BPP_LIB_PATH` set):", "", "| shape | arm | ms per step | proofs/s | host ms in the step's calls | "
+                "thread CPU ms per step |", "|---|---|---|---|---|---|"]
+        out += [x.replace("| blocking |", "| blocking, this tree |") for x in (table(ab_mine) if ab_mine else [])]
+        out += [x.replace("| blocking |", "| blocking, parent commit |") for x in table(other)]
+    return out + [""]
+
+
 def refill_mixed_section():
     """profiles/refill_mixed.json (a list of runs of tools/bench_refill_mixed.py): per batch size, both arms over every repetition of
     every run"""
@@ -435,6 +506,7 @@ def main():
     out += refill_mixed_section()
     out += item_transcripts_section()
     out += prove_device_section()
+    out += prove_enqueue_section()
     ks, fks = load(tag, "kernel_stats_cfg2_default.csv")
     sq, fsq = load(tag, "pmc_sq_summary.csv")
     if ks:
