@@ -138,6 +138,9 @@ _ASAN_HARNESSES = {
     "prove_enqueue": ("prove_ingest.h as bpp_prove_enqueue uses it: the ingest routines under a live mask -- a dead row is never read -- "
                       "held to ProvePack::pack on the live items and to the substitute on the dead ones; the summary reduction and the "
                       "ok mask against a host loop; tests/test_prove_enqueue_host.py", [], []),
+    "transcript_ops": ("transcript_ops.h: the per-row rules and the one-lane model of k_transcript_ops (bpp_transcripts_enqueue) -- live, "
+                       "void and dead rows, NEW / APPEND / CHALLENGE -- held to merlin.h's routines on a copy of every row, with dead rows "
+                       "and the data of void rows poisoned; the call's refusals; tests/test_transcript_ops_host.py", [], []),
 }
 
 
@@ -175,6 +178,7 @@ ITEM_STATES_SANITIZER_BIN, build_item_states_harness = _asan_bin("item_states"),
 PROVE_INGEST_SANITIZER_BIN, build_prove_ingest_harness = _asan_bin("prove_ingest"), _asan_builder("prove_ingest")
 PROVE_STATES_SANITIZER_BIN, build_prove_states_harness = _asan_bin("prove_states"), _asan_builder("prove_states")
 PROVE_ENQUEUE_SANITIZER_BIN, build_prove_enqueue_harness = _asan_bin("prove_enqueue"), _asan_builder("prove_enqueue")
+TRANSCRIPT_OPS_SANITIZER_BIN, build_transcript_ops_harness = _asan_bin("transcript_ops"), _asan_builder("transcript_ops")
 
 
 if __name__ == "__main__":

@@ -127,6 +127,22 @@ class ProveEnqueueStats(Structure):
     _fields_ = [(n, c_uint64) for n in ("calls", "first_calls", "host_waits", "allocations")]
 
 
+class TranscriptOp(Structure):
+    """bpp_transcript_op: one Merlin operation of a bpp_transcripts_enqueue (the label on the host, the rows in device memory)"""
+    _fields_ = [("kind", c_uint32), ("label", c_void_p), ("label_len", c_uint32), ("data_dev", c_void_p), ("stride", c_size_t),
+                ("len", c_uint32), ("lens_dev", c_void_p)]
+
+
+class DeviceTranscriptsRecord(Structure):
+    """bpp_device_transcripts_record: the one record of a bpp_transcripts_enqueue, 16 bytes, as it lies in device memory"""
+    _fields_ = [(n, c_uint32) for n in ("n_done", "n_void", "first_void", "flags")]
+
+
+class TranscriptsStats(Structure):
+    """struct bpp_transcripts_stats: what the bpp_transcripts_enqueue calls of a context cost the host"""
+    _fields_ = [(n, c_uint64) for n in ("calls", "first_calls", "host_waits")]
+
+
 class ProveDeviceStats(Structure):
     """struct bpp_prove_device_stats: what the prove calls from device arrays of a context came to"""
     _fields_ = [(n, c_uint64) for n in ("calls", "items", "device_findings", "host_findings")]
@@ -309,6 +325,9 @@ SYMBOLS = [
     ("bpp_transcript_new", c_int, [c_void_p, c_size_t, c_void_p]),
     ("bpp_transcript_append_message", c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
     ("bpp_transcript_challenge_bytes", c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
+    ("bpp_transcripts_enqueue", c_int, [c_void_p, c_void_p, c_size_t, POINTER(TranscriptOp), c_size_t, c_void_p, c_void_p, c_void_p,
+                                        POINTER(c_uint64)]),
+    ("bpp_transcripts_stats", c_int, [c_void_p, POINTER(TranscriptsStats)]),
     ("bpp_verify_batch_states", c_int, [c_void_p, c_uint64, POINTER(VerifyItem), c_size_t, c_int, c_size_t, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_size_t]),
     ("bpp_verify_batch_packed_states", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_int, c_size_t, c_void_p, c_void_p,

@@ -46,6 +46,7 @@
 #include "refill.h"
 #include "item_states.h"
 #include "prove_ingest.h"
+#include "transcript_ops.h"
 
 using namespace bpp;
 
@@ -647,6 +648,7 @@ struct bpp_ctx {
   std::map<uint64_t, std::unique_ptr<ProvePlanBase>> prove_plans;
   uint64_t prove_plan_next = 1;
   struct bpp_prove_enqueue_stats prove_enq_stats{};
+  struct bpp_transcripts_stats tops_stats{};  // bpp_transcripts_enqueue (engine_transcript_ops.h)
   bpp_prove_profile pprof{};
   // knobs (tests, A/B timing).  -1 = the engine's own rule.  The BPP_* environment variables of the same names are read
   // ONCE, when the context is created (no getenv on any verification path: a host that calls setenv from another thread
@@ -4855,3 +4857,4 @@ int bpp_profile_get(bpp_ctx *ctx, bpp_profile *out) {
 #include "engine_prove_plan.h"
 #include "engine_prove_pool.h"
 #include "engine_prove_pipe.h"
+#include "engine_transcript_ops.h"

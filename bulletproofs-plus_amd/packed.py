@@ -664,6 +664,141 @@ def prove_enqueue_stats(engine):
     return {k: int(getattr(s, k)) for k, _ in _lib.ProveEnqueueStats._fields_}
 
 
+TOP_NEW, TOP_APPEND, TOP_CHALLENGE = 1, 2, 3  # BPP_TOP_* of include/bpp.h
+TOP_MAX_OPS, TOP_LABEL_MAX, TOP_LEN_MAX, TOPS_WRITTEN = 8, 64, 65536, 1
+
+
+class TNew:
+    """Transcript::new(label) on every live row, whatever it held: only as the first operation of a program"""
+
+    def __init__(self, label):
+        self.label = bytes(label)
+
+
+class TAppend:
+    """append_message(label, row i of data).  data: a uint8 [n, len] device tensor (rows may be further apart than len: stride(0) >=
+    len), or an (address, (n, len)) / (address, (n, len), stride) tuple.  lens: an int32 / uint32 [n] device tensor (or an address)
+    of per-row lengths under the cap len, or None.  append_u64 is an append of eight little-endian bytes."""
+
+    def __init__(self, label, data, lens=None):
+        self.label, self.data, self.lens = bytes(label), data, lens
+
+
+class TChallenge:
+    """challenge_bytes(label, nbytes) into row i of out: a uint8 [n, nbytes] device tensor (stride(0) >= nbytes), a tuple as for
+    TAppend, or None for a fresh tensor"""
+
+    def __init__(self, label, nbytes, out=None):
+        self.label, self.nbytes, self.out = bytes(label), int(nbytes), out
+
+
+class TranscriptsEnqueued:
+    """What transcript_ops returns: `.states` (the rows, advanced in place), `.outputs` (one tensor -- or whatever was passed -- per
+    TChallenge, in program order), `.done_mask` (uint8 [n]: 1 where the row was advanced) and `.record` (int32 [4]: n_done, n_void,
+    first_void, flags) -- valid in stream order behind the call -- and the ticket: done() is one event query, wait() blocks until
+    the call has run, result() waits and returns the record as a dict (first_void None where no row was void)."""
+
+    def __init__(self, engine, ticket, states, outputs, done_mask, record, keep):
+        self.engine, self.ticket, self.states, self.outputs, self.done_mask, self.record, self._keep = engine, ticket, states, outputs, done_mask, record, keep
+
+    def done(self):
+        d = ctypes.c_int()
+        api._check(self.engine.lib.bpp_enqueue_done(self.engine.ctx, self.ticket, byref(d)), self.engine.ctx)
+        return bool(d.value)
+
+    def wait(self):
+        api._check(self.engine.lib.bpp_enqueue_wait(self.engine.ctx, self.ticket), self.engine.ctx)
+
+    def result(self):
+        self.wait()
+        host = [int(x) & 0xFFFFFFFF for x in self.record.cpu().numpy()]
+        return {"n_done": host[0], "n_void": host[1], "first_void": None if host[2] == 0xFFFFFFFF else host[2], "flags": host[3]}
+
+
+def transcript_ops(engine, states, ops, live=None, done_mask=None, record=None):
+    """bpp_transcripts_enqueue: the program `ops` (TNew / TAppend / TChallenge, at most 8) on the n rows of `states` -- a uint8 [n, 203]
+    device tensor at any byte address (a slice of a larger tensor will do) or an (address, (n, 203)) pair -- in place, on the engine's
+    stream, without waiting.  live: a uint8 [n] device tensor (0 = dead: the row is neither read nor written), or None.  done_mask and
+    record default to fresh tensors.  Ordering is DevicePackedInput.order_before's: an engine made on torch's current stream needs
+    nothing, otherwise torch's current stream is synchronised first (with raw addresses the caller orders).  Returns a
+    TranscriptsEnqueued; a refused call raises ProofError with the field named."""
+    import torch
+    dev = torch.device("cuda", int(engine.device))
+    order = DevicePackedInput.__new__(DevicePackedInput)
+    order._keep, order.device_index, order._torch, order.synchronised = [], None, False, False
+
+    def rows(a, name, width=None):
+        """-> (address, n, width, stride)"""
+        if isinstance(a, tuple) and len(a) == 3:
+            return int(a[0]), int(a[1][0]), int(a[1][1]), int(a[2])
+        addr, shape, stride = order._array(a, name, 1, rows=True)
+        if len(shape) != 2 or (width is not None and shape[1] != width):
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "%s: an array of shape (n, %s) expected, got %s" % (name, width or "len", shape))
+        return addr, shape[0], shape[1], (stride if stride is not None else shape[1])
+
+    addr_s, n, _, stride_s = rows(states, "states", 203)
+    if stride_s != 203:
+        raise api.ProofError(api.ProofErrorKind.InvalidArgument, "states: rows of 203 bytes back to back expected")
+
+    def flat(a, name, itemsize):
+        if a is None:
+            return None
+        if not hasattr(a, "data_ptr"):
+            return int(a)
+        if a.element_size() != itemsize or not a.is_contiguous() or a.numel() != n:
+            raise api.ProofError(api.ProofErrorKind.InvalidArgument, "%s: %d contiguous elements of %d bytes expected" % (name, n, itemsize))
+        order._keep.append(a)
+        order._torch = True
+        return a.data_ptr()
+
+    arr = (_lib.TranscriptOp * max(len(ops), 1))()
+    labels, outputs = [], []
+    for j, op in enumerate(ops[:len(arr)]):
+        lab = np.frombuffer(op.label, dtype=np.uint8).copy() if len(op.label) else None
+        labels.append(lab)
+        o = arr[j]
+        o.label, o.label_len = (None if lab is None else lab.ctypes.data), len(op.label)
+        if isinstance(op, TNew):
+            o.kind = TOP_NEW
+        elif isinstance(op, TAppend):
+            o.kind = TOP_APPEND
+            if op.data is not None:
+                o.data_dev, rows_n, o.len, o.stride = rows(op.data, "ops[%d].data" % j)
+                if rows_n != n:
+                    raise api.ProofError(api.ProofErrorKind.InvalidLength, "ops[%d].data: %d rows for %d states" % (j, rows_n, n))
+            o.lens_dev = flat(op.lens, "ops[%d].lens" % j, 4)
+        elif isinstance(op, TChallenge):
+            o.kind = TOP_CHALLENGE
+            out = op.out
+            if out is None and op.nbytes:
+                out = torch.zeros((n, op.nbytes), dtype=torch.uint8, device=dev)
+            if out is not None:
+                o.data_dev, rows_n, o.len, o.stride = rows(out, "ops[%d].out" % j, None if isinstance(out, tuple) else op.nbytes)
+                if rows_n != n or o.len != op.nbytes:
+                    raise api.ProofError(api.ProofErrorKind.InvalidLength, "ops[%d].out: (%d, %d) expected" % (j, n, op.nbytes))
+            outputs.append(out)
+        else:
+            raise api.ProofError(api.ProofErrorKind.InvalidArgument, "ops[%d]: TNew, TAppend or TChallenge expected" % j)
+    if done_mask is None:
+        done_mask = torch.zeros((n,), dtype=torch.uint8, device=dev)
+    if record is None:
+        record = torch.zeros((4,), dtype=torch.int32, device=dev)
+    addr_live, addr_done = flat(live, "live", 1), flat(done_mask, "done_mask", 1)
+    addr_rec = record.data_ptr() if hasattr(record, "data_ptr") else int(record)
+    order.order_before(engine)
+    ticket = c_uint64()
+    api._check(engine.lib.bpp_transcripts_enqueue(engine.ctx, ctypes.c_void_p(addr_s), n, arr, len(ops), addr_live, addr_done, addr_rec,
+                                                  byref(ticket)), engine.ctx)
+    return TranscriptsEnqueued(engine, ticket.value, states, outputs, done_mask, record, (order._keep, labels, arr))
+
+
+def transcripts_stats(engine):
+    """bpp_transcripts_stats as a dict: calls, first_calls, host_waits"""
+    s = _lib.TranscriptsStats()
+    api._check(engine.lib.bpp_transcripts_stats(engine.ctx, byref(s)), engine.ctx)
+    return {k: int(getattr(s, k)) for k, _ in _lib.TranscriptsStats._fields_}
+
+
 def device_pointer_kind(engine, address):
     """bpp_device_pointer_check: 0 this engine's device memory, 1 another device's, 2 host or unknown, 3 managed (launches nothing)"""
     kind = ctypes.c_int(-1)

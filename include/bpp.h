@@ -1276,6 +1276,79 @@ int bpp_transcript_new(const uint8_t *label, size_t label_len, uint8_t state203[
 int bpp_transcript_append_message(uint8_t state203[203], const uint8_t *label, size_t label_len, const uint8_t *msg, size_t msg_len);
 int bpp_transcript_challenge_bytes(uint8_t state203[203], const uint8_t *label, size_t label_len, uint8_t *out, size_t out_len);
 
+/* ---- Merlin on the stream: the three calls above, row-wise, on transcript rows in device memory ----
+ * bpp_transcripts_enqueue runs a short program of Merlin operations on n rows of 203 bytes in device memory (any byte address, IN
+ * PLACE), one wavefront per row on the context's stream: it MAKES the rows a *_transcripts / item_states_dev call takes (NEW, then
+ * APPEND of a row of context each) and GOES ON with the rows a *_states call hands back (CHALLENGE), without a host round trip.
+ * The call enqueues behind everything on the context's stream and returns.
+ *
+ * THE PROGRAM: n_ops (1 .. BPP_TOP_MAX_OPS) operations, applied to every live row in order.
+ *   BPP_TOP_NEW        Transcript::new(label): the row := that state, whatever it held (it is not read).  Only as op 0, without data.
+ *                      The state is public and the same for every row: the host computes it once (the routine behind
+ *                      bpp_transcript_new) and it travels in the launch arguments.  Its label may have any length.
+ *   BPP_TOP_APPEND     append_message(label, row i of data_dev).  data_dev is read: len bytes per row, or lens_dev[i] bytes (n words of
+ *                      device memory) with len as the cap.  append_u64 is an APPEND of eight little-endian bytes, as in merlin.
+ *   BPP_TOP_CHALLENGE  challenge_bytes(label, row i of data_dev).  data_dev is written: len bytes per row.
+ *   Labels are HOST memory and are copied at call time (NULL with label_len 0); row i of an op's data lies at data_dev + i * stride.
+ * THE CONTRACT, per row.  A row is LIVE where live_dev[i] != 0, or everywhere when live_dev is NULL.  A live row that is not void ends
+ * up as the 203 bytes bpp_transcript_new / bpp_transcript_append_message / bpp_transcript_challenge_bytes leave when applied to a host
+ * copy of the row in program order, and row i of every CHALLENGE holds the bytes the host call writes; its done_mask byte is 1.
+ * VOID ROWS.  A live row is void -- decided by the row's first lane before any other byte of the row or of its data is read -- if
+ *   the program does not begin with NEW and the row has pos >= 166 (byte 200) or cur_flags == 0 (byte 202), or
+ *   some APPEND has lens_dev[i] > len.
+ * A void row becomes 203 zero bytes, each of its CHALLENGE rows len zero bytes, its done_mask byte 0; it counts in n_void and
+ * competes for first_void (the lowest index wins).
+ * STRICTER THAN THE HOST HELPERS in one place: cur_flags == 0.  The host helpers look at pos alone.  No Merlin transcript has that
+ * byte zero (Transcript::new ends behind an AD operation, and every operation sets it), but the 203 zero bytes that
+ * bpp_verify_enqueue_states and bpp_prove_enqueue write for rejected, failed or dead items do: under this rule such a row stays zero
+ * through this call, with a zero challenge, instead of becoming a plausible-looking transcript.
+ * DEAD ROWS (live_dev[i] == 0): the state row is neither read nor written, nothing of its data rows or of lens_dev[i] is read, its
+ * CHALLENGE rows are zeroed, its done_mask byte is 0.  ROW SLACK (stride > len) is neither read nor written.
+ * record_dev (or NULL): {n_done, n_void, first_void (0xFFFFFFFF: none), flags = BPP_TOPS_WRITTEN}, initialised and reduced on the
+ * stream.  done_mask_dev (or NULL): n bytes.
+ * REFUSED before any launch (BPP_ERR_INVALID_ARGUMENT, the field named in bpp_ctx_last_error, the counters left alone): n == 0 (or
+ * above 2^31 - 1); n_ops 0 or above BPP_TOP_MAX_OPS; an unknown kind; NEW anywhere but at op 0, or NEW with data; an APPEND / CHALLENGE
+ * label above BPP_TOP_LABEL_MAX; len above BPP_TOP_LEN_MAX; stride < len; data_dev NULL with len > 0; lens_dev on anything but an
+ * APPEND; states203_dev, a data_dev, lens_dev, live_dev, done_mask_dev or record_dev that bpp_device_pointer_check does not class
+ * BPP_PTR_THIS_DEVICE; a written range (the states, a CHALLENGE's rows, done_mask_dev, record_dev) that overlaps any other range
+ * of the call.
+ * STEADY STATE: after a context's first call (the ticket events) the call allocates nothing, copies nothing to the host and waits
+ * for nothing: bpp_transcripts_stats' host_waits stays 0.  TICKETS are those of bpp_enqueue_done / bpp_enqueue_wait.
+ * The rows and everything appended here are the caller's public protocol data; the kernel wipes its LDS all the same. */
+#define BPP_TOP_NEW 1
+#define BPP_TOP_APPEND 2
+#define BPP_TOP_CHALLENGE 3
+#define BPP_TOP_MAX_OPS 8
+#define BPP_TOP_LABEL_MAX 64
+#define BPP_TOP_LEN_MAX 65536
+typedef struct {
+  uint32_t kind;
+  const uint8_t *label; /* HOST memory, copied at call time; NULL with label_len 0 */
+  uint32_t label_len;
+  uint8_t *data_dev;    /* DEVICE rows: row i at data_dev + i * stride; may be NULL when len == 0 */
+  size_t stride;
+  uint32_t len;             /* bytes per row (APPEND: the cap when lens_dev is given) */
+  const uint32_t *lens_dev; /* APPEND only, optional: row i's own length, n words of device memory */
+} bpp_transcript_op;
+typedef struct {
+  uint32_t n_done, n_void;
+  uint32_t first_void; /* 0xFFFFFFFF: none */
+  uint32_t flags;      /* BPP_TOPS_WRITTEN */
+} bpp_device_transcripts_record;
+#define BPP_TOPS_WRITTEN 1u
+int bpp_transcripts_enqueue(bpp_ctx *ctx, uint8_t *states203_dev /* DEVICE n x 203, any byte address, IN PLACE */, size_t n,
+                            const bpp_transcript_op *ops, size_t n_ops,
+                            const uint8_t *live_dev /* DEVICE n bytes, or NULL: every row */,
+                            uint8_t *done_mask_dev /* DEVICE n bytes, or NULL: 1 where the row was advanced */,
+                            bpp_device_transcripts_record *record_dev /* DEVICE, or NULL */,
+                            uint64_t *ticket /* or NULL; bpp_enqueue_done / bpp_enqueue_wait */);
+struct bpp_transcripts_stats {
+  uint64_t calls;       /* enqueues that passed the refusals */
+  uint64_t first_calls; /* of them, the context's first (at most 1): it makes the ticket events where no enqueue has yet */
+  uint64_t host_waits;  /* times a call waited for the device: 0 */
+};
+int bpp_transcripts_stats(bpp_ctx *ctx, struct bpp_transcripts_stats *out);
+
 /* ---- Advanced transcripts: `&mut Transcript` on the device paths ----
  * The reference's prove_with_rng and verify_batch take `&mut Transcript` (src/range_proof.rs:222-237, :712-717, :757) and leave
  * it advanced by everything the proof appended and drew, so that the caller can go on with it.  The calls below are the named

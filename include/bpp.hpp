@@ -341,6 +341,45 @@ class Engine {
     return s;
   }
 
+  // Merlin on the stream (bpp_transcripts_enqueue): a program of at most BPP_TOP_MAX_OPS operations on n transcript rows of 203 bytes
+  // in DEVICE memory, in place, one wavefront per row -- the rows a *_transcripts call takes are made here (op_new, op_append), the
+  // rows a *_states call hands back are continued here (op_challenge).  Labels are host memory and are copied by the call; data rows
+  // are device memory, row i at data_dev + i * stride (stride 0: back to back).  A row that is no transcript (pos >= 166, or
+  // cur_flags == 0: the zero rows of rejected and failed items) stays 203 zero bytes with zero challenges.
+  static bpp_transcript_op op_new(const uint8_t *label, uint32_t label_len) {
+    bpp_transcript_op o{};
+    o.kind = BPP_TOP_NEW, o.label = label, o.label_len = label_len;
+    return o;
+  }
+  static bpp_transcript_op op_append(const uint8_t *label, uint32_t label_len, const uint8_t *data_dev, uint32_t len, size_t stride = 0,
+                                     const uint32_t *lens_dev = nullptr) {
+    bpp_transcript_op o{};
+    o.kind = BPP_TOP_APPEND, o.label = label, o.label_len = label_len;
+    o.data_dev = const_cast<uint8_t *>(data_dev), o.len = len, o.stride = stride ? stride : len, o.lens_dev = lens_dev;
+    return o;
+  }
+  static bpp_transcript_op op_challenge(const uint8_t *label, uint32_t label_len, uint8_t *out_dev, uint32_t len, size_t stride = 0) {
+    bpp_transcript_op o{};
+    o.kind = BPP_TOP_CHALLENGE, o.label = label, o.label_len = label_len;
+    o.data_dev = out_dev, o.len = len, o.stride = stride ? stride : len;
+    return o;
+  }
+  // live (n device bytes, 0 = dead: the row is neither read nor written), done_mask (n device bytes) and record may be null.  Enqueues
+  // behind everything on the engine's stream and returns; the ticket is an enqueue ticket (results() is not for it).
+  EnqueueTicket transcripts_enqueue(uint8_t *states203_dev, size_t n, const std::vector<bpp_transcript_op> &ops, const uint8_t *live_dev = nullptr,
+                                    uint8_t *done_mask_dev = nullptr, bpp_device_transcripts_record *record_dev = nullptr) {
+    EnqueueTicket t;
+    t.ctx_ = ctx_;
+    const int rc = bpp_transcripts_enqueue(ctx_, states203_dev, n, ops.data(), ops.size(), live_dev, done_mask_dev, record_dev, &t.id);
+    check(rc, bpp_ctx_last_error(ctx_));  // (the message is read behind the call, not while its arguments are evaluated)
+    return t;
+  }
+  struct bpp_transcripts_stats transcripts_stats() const {
+    struct bpp_transcripts_stats s{};
+    check(::bpp_transcripts_stats(ctx_, &s), bpp_ctx_last_error(ctx_));
+    return s;
+  }
+
  private:
   bpp_ctx *ctx_ = nullptr;
 };

@@ -167,6 +167,45 @@ pub struct bpp_prove_enqueue_stats {
     pub allocations: u64,
 }
 
+/// bpp_transcript_op: one Merlin operation of a `bpp_transcripts_enqueue` (the label on the host, the rows in device memory)
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bpp_transcript_op {
+    pub kind: u32,
+    pub label: *const u8,
+    pub label_len: u32,
+    pub data_dev: *mut u8,
+    pub stride: usize,
+    pub len: u32,
+    pub lens_dev: *const u32,
+}
+pub const BPP_TOP_NEW: u32 = 1;
+pub const BPP_TOP_APPEND: u32 = 2;
+pub const BPP_TOP_CHALLENGE: u32 = 3;
+pub const BPP_TOP_MAX_OPS: usize = 8;
+pub const BPP_TOP_LABEL_MAX: u32 = 64;
+pub const BPP_TOP_LEN_MAX: u32 = 65536;
+
+/// bpp_device_transcripts_record: the one record of a `bpp_transcripts_enqueue`, 16 bytes, as it lies in device memory
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_device_transcripts_record {
+    pub n_done: u32,
+    pub n_void: u32,
+    pub first_void: u32,
+    pub flags: u32,
+}
+pub const BPP_TOPS_WRITTEN: u32 = 1;
+
+/// `struct bpp_transcripts_stats`: what the `bpp_transcripts_enqueue` calls of a context cost the host
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_transcripts_stats {
+    pub calls: u64,
+    pub first_calls: u64,
+    pub host_waits: u64,
+}
+
 #[repr(C)]
 pub struct bpp_comm {
     _p: [u8; 0],
@@ -575,6 +614,10 @@ extern "C" {
     pub fn bpp_transcript_new(label: *const u8, label_len: usize, state203: *mut u8) -> c_int;
     pub fn bpp_transcript_append_message(state203: *mut u8, label: *const u8, label_len: usize, msg: *const u8, msg_len: usize) -> c_int;
     pub fn bpp_transcript_challenge_bytes(state203: *mut u8, label: *const u8, label_len: usize, out: *mut u8, out_len: usize) -> c_int;
+    pub fn bpp_transcripts_enqueue(ctx: *mut bpp_ctx, states203_dev: *mut u8, n: usize, ops: *const bpp_transcript_op, n_ops: usize,
+                                   live_dev: *const u8, done_mask_dev: *mut u8, record_dev: *mut bpp_device_transcripts_record,
+                                   ticket: *mut u64) -> c_int;
+    pub fn bpp_transcripts_stats(ctx: *mut bpp_ctx, out: *mut bpp_transcripts_stats) -> c_int;
     pub fn bpp_verify_batch_states(ctx: *mut bpp_ctx, params: u64, items: *const bpp_verify_item, n_items: usize, action: c_int, chunk: usize,
                                    masks_out: *mut u8, mask_present: *mut u8, states_out203: *mut u8, errbuf: *mut c_char,
                                    errbuf_len: usize) -> c_int;

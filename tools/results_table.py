@@ -214,6 +214,47 @@ def item_transcripts_section():
     return out + [""]
 
 
+def transcript_ops_section():
+    """profiles/transcript_ops.json (tools/bench_transcript_ops.py): bpp_transcripts_enqueue against the host route, the call alone and
+    inside the full step; "bench_ab": bench.py's headline on this tree and on the parent commit's library, alternating (tools/gpu_ab.py)"""
+    f = os.path.join(P, "transcript_ops.json")
+    out = ["## Merlin on the stream: `bpp_transcripts_enqueue` against the host route (`tools/bench_transcript_ops.py`, "
+           "`profiles/transcript_ops.json`)", ""]
+    if not os.path.exists(f):
+        return out + ["unmeasured", ""]
+    doc = json.load(open(f))
+    out += ["One thread, an engine on torch's stream.  make = NEW + APPEND(32 bytes per row); challenge = CHALLENGE(32).  Device: calls back to "
+            "back for a window of %.1f s around one stream synchronise.  Host route: rows (or ids) copied down, the three host helpers per row, the "
+            "result copied up -- called from Python through ctypes; the last columns take the measured cost of as many empty ctypes calls off.  "
+            "Nothing was promised.  Box: \"%s\"." % (doc["window_s"], doc["box"]), "",
+            "| rows | arm | device ms per call | device M rows/s | host route ms per step (lowest-highest) | host / device | less ctypes: host ms | host / device |",
+            "|---|---|---|---|---|---|---|---|"]
+    for r in doc["sizes"]:
+        for k, a in r["arms"].items():
+            out.append("| %d | %s | %.4f | %.1f | %.3f (%.3f-%.3f) | %.1f | %.3f | %.1f |" %
+                       (r["n"], k, a["device_ms_per_call"], a["device_rows_per_s"] / 1e6, a["host_ms_per_step"], a["host_ms_low"], a["host_ms_high"],
+                        a["host_over_device"], a["host_ms_less_ctypes"], a["host_less_ctypes_over_device"]))
+    fs = doc.get("full_step")
+    if fs:
+        out += ["", "The full step (make the rows -> `bpp_prove_enqueue` -> refill -> `bpp_verify_enqueue_states` -> challenge on the rows handed back) at "
+                "%d proofs of %d bits, m = %d, t = %d, the arms alternating, %d rounds of %d steps; median of the rounds' medians (lowest-highest round):" %
+                (fs["items"], fs["n_bits"], fs["m"], fs["t"], fs["reps"], fs["inner"]), "",
+                "| arm | ms per step | proofs/s |", "|---|---|---|"]
+        for k, a in fs["arms"].items():
+            out.append("| %s | %.3f (%.3f-%.3f) | %.0f |" % (k, a["ms_per_step"], a["ms_low"], a["ms_high"], a["proofs_per_s"]))
+        st = fs["stats"]
+        out += ["", "host / device: %.3f.  Host waits inside the calls over the whole run: transcripts %d (of %d calls), prove enqueue %d, refill %d, "
+                "verify enqueue %d." % (fs["host_over_device"], st["transcripts"]["host_waits"], st["transcripts"]["calls"],
+                                        st["prove_enqueue"]["host_waits"], st["refill"]["host_waits"], st["enqueue"]["host_waits"])]
+    ab = doc.get("bench_ab")
+    if ab:
+        cell = lambda v: "%.2f (%.2f-%.2f)" % (statistics.median(v), min(v), max(v))  # noqa: E731
+        out += ["", "`bench.py`'s headline, this tree against the parent commit's library, alternating in one call (`tools/gpu_ab.py --leg headline`, "
+                "%s); M proofs/s, median (lowest-highest) of %d runs each:" % (ab["args"], len(ab["this"])), "",
+                "| this tree | parent commit |", "|---|---|", "| %s | %s |" % (cell(ab["this"]), cell(ab["parent"]))]
+    return out + [""]
+
+
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r03_v1"
     out = ["# RESULTS — measured figures (generated by `tools/results_table.py %s` from `profiles/`; do not edit)" % tag, "",
@@ -507,6 +548,7 @@ def main():
     out += item_transcripts_section()
     out += prove_device_section()
     out += prove_enqueue_section()
+    out += transcript_ops_section()
     ks, fks = load(tag, "kernel_stats_cfg2_default.csv")
     sq, fsq = load(tag, "pmc_sq_summary.csv")
     if ks:
