@@ -141,6 +141,10 @@ _ASAN_HARNESSES = {
     "transcript_ops": ("transcript_ops.h: the per-row rules and the one-lane model of k_transcript_ops (bpp_transcripts_enqueue) -- live, "
                        "void and dead rows, NEW / APPEND / CHALLENGE -- held to merlin.h's routines on a copy of every row, with dead rows "
                        "and the data of void rows poisoned; the call's refusals; tests/test_transcript_ops_host.py", [], []),
+    "transcript_rng": ("transcript_ops.h: the transcript-protocol and transcript-RNG kinds -- APPEND_POINT, CHALLENGE_SCALAR, RNG_BEGIN .. "
+                       "RNG_SCALARS -- in the one-lane model of k_transcript_ops_rng, held to merlin.h's routines and the shared scalar "
+                       "routine, with dead rows, the inputs of void rows and all slack poisoned; the void on a zero scalar; the new "
+                       "refusals; tests/test_transcript_rng_host.py", [], []),
 }
 
 
@@ -179,6 +183,7 @@ PROVE_INGEST_SANITIZER_BIN, build_prove_ingest_harness = _asan_bin("prove_ingest
 PROVE_STATES_SANITIZER_BIN, build_prove_states_harness = _asan_bin("prove_states"), _asan_builder("prove_states")
 PROVE_ENQUEUE_SANITIZER_BIN, build_prove_enqueue_harness = _asan_bin("prove_enqueue"), _asan_builder("prove_enqueue")
 TRANSCRIPT_OPS_SANITIZER_BIN, build_transcript_ops_harness = _asan_bin("transcript_ops"), _asan_builder("transcript_ops")
+TRANSCRIPT_RNG_SANITIZER_BIN, build_transcript_rng_harness = _asan_bin("transcript_rng"), _asan_builder("transcript_rng")
 
 
 if __name__ == "__main__":

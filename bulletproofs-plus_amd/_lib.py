@@ -325,6 +325,13 @@ SYMBOLS = [
     ("bpp_transcript_new", c_int, [c_void_p, c_size_t, c_void_p]),
     ("bpp_transcript_append_message", c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
     ("bpp_transcript_challenge_bytes", c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
+    ("bpp_transcript_validate_and_append_point", c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_char_p, c_size_t]),
+    ("bpp_transcript_challenge_scalar", c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_char_p, c_size_t]),
+    ("bpp_transcript_rng_begin", c_int, [c_void_p, c_void_p]),
+    ("bpp_transcript_rng_rekey", c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t]),
+    ("bpp_transcript_rng_finalize", c_int, [c_void_p, c_void_p]),
+    ("bpp_transcript_rng_fill", c_int, [c_void_p, c_void_p, c_size_t]),
+    ("bpp_transcript_rng_scalar", c_int, [c_void_p, c_void_p, c_char_p, c_size_t]),
     ("bpp_transcripts_enqueue", c_int, [c_void_p, c_void_p, c_size_t, POINTER(TranscriptOp), c_size_t, c_void_p, c_void_p, c_void_p,
                                         POINTER(c_uint64)]),
     ("bpp_transcripts_stats", c_int, [c_void_p, POINTER(TranscriptsStats)]),

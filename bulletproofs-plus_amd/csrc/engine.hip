@@ -1861,6 +1861,83 @@ int bpp_transcript_challenge_bytes(uint8_t state203[203], const uint8_t *label, 
   return BPP_OK;
 }
 
+// The reference's TranscriptProtocol and merlin's transcript RNG on 203-byte states (host only): merlin.h's routines and the scalar
+// routine the kernel of bpp_transcripts_enqueue runs (transcript_ops.h: top_scalar_from_wide).
+int bpp_transcript_validate_and_append_point(uint8_t state203[203], const uint8_t *label, size_t label_len, const uint8_t point32[32],
+                                             char *errbuf, size_t errbuf_len) {
+  if (!state203 || (!label && label_len) || !point32) return BPP_ERR_INVALID_ARGUMENT;
+  if (label_len > 0xffffffffu) return BPP_ERR_INVALID_LENGTH;
+  if (state203[200] >= BPP_STROBE_R) return BPP_ERR_INVALID_ARGUMENT;
+  uint8_t any = 0;
+  for (int k = 0; k < 32; k++) any |= point32[k];
+  if (!any) {
+    set_err(errbuf, errbuf_len, "Identity element cannot be added to the transcript");
+    return BPP_ERR_VERIFICATION_FAILED;
+  }
+  return bpp_transcript_append_message(state203, label, label_len, point32, 32);
+}
+
+int bpp_transcript_challenge_scalar(uint8_t state203[203], const uint8_t *label, size_t label_len, uint8_t out32[32], char *errbuf,
+                                    size_t errbuf_len) {
+  if (!out32) return BPP_ERR_INVALID_ARGUMENT;
+  uint8_t wide[64];
+  const int rc = bpp_transcript_challenge_bytes(state203, label, label_len, wide, 64);
+  if (rc != BPP_OK) return rc;
+  const uint32_t zero = top_scalar_from_wide(out32, wide);
+  if (zero) set_err(errbuf, errbuf_len, "Transcript challenge cannot be zero");
+  return zero ? BPP_ERR_VERIFICATION_FAILED : BPP_OK;
+}
+
+int bpp_transcript_rng_begin(const uint8_t state203[203], uint8_t rng203_out[203]) {
+  if (!state203 || !rng203_out || state203[200] >= BPP_STROBE_R) return BPP_ERR_INVALID_ARGUMENT;
+  memmove(rng203_out, state203, 203);
+  return BPP_OK;
+}
+
+int bpp_transcript_rng_rekey(uint8_t rng203[203], const uint8_t *label, size_t label_len, const uint8_t *witness, size_t witness_len) {
+  if (!rng203 || (!label && label_len) || (!witness && witness_len)) return BPP_ERR_INVALID_ARGUMENT;
+  if (label_len > 0xffffffffu || witness_len > 0xffffffffu) return BPP_ERR_INVALID_LENGTH;
+  if (rng203[200] >= BPP_STROBE_R) return BPP_ERR_INVALID_ARGUMENT;
+  Strobe s;
+  strobe_from_bytes(s, rng203);
+  merlin_rng_rekey(s, label, (uint32_t)label_len, witness, (uint32_t)witness_len);
+  strobe_to_bytes(rng203, s);
+  return BPP_OK;
+}
+
+int bpp_transcript_rng_finalize(uint8_t rng203[203], const uint8_t random32[32]) {
+  if (!rng203 || rng203[200] >= BPP_STROBE_R) return BPP_ERR_INVALID_ARGUMENT;
+  const uint8_t zeros[32] = {0};
+  Strobe s;
+  strobe_from_bytes(s, rng203);
+  merlin_rng_finalize(s, random32 ? random32 : zeros);
+  strobe_to_bytes(rng203, s);
+  return BPP_OK;
+}
+
+int bpp_transcript_rng_fill(uint8_t rng203[203], uint8_t *out, size_t out_len) {
+  if (!rng203 || (!out && out_len)) return BPP_ERR_INVALID_ARGUMENT;
+  if (out_len > 0xffffffffu) return BPP_ERR_INVALID_LENGTH;
+  if (rng203[200] >= BPP_STROBE_R) return BPP_ERR_INVALID_ARGUMENT;
+  Strobe s;
+  strobe_from_bytes(s, rng203);
+  merlin_rng_fill(s, out, (uint32_t)out_len);
+  strobe_to_bytes(rng203, s);
+  return BPP_OK;
+}
+
+int bpp_transcript_rng_scalar(uint8_t rng203[203], uint8_t out32[32], char *errbuf, size_t errbuf_len) {
+  if (!out32) return BPP_ERR_INVALID_ARGUMENT;
+  uint8_t wide[64];
+  const int rc = bpp_transcript_rng_fill(rng203, wide, 64);
+  if (rc != BPP_OK) return rc;
+  const uint32_t zero = top_scalar_from_wide(out32, wide);
+  volatile uint8_t *w = wide;
+  for (int k = 0; k < 64; k++) w[k] = 0;
+  if (zero) set_err(errbuf, errbuf_len, "Random scalar is zero");
+  return zero ? BPP_ERR_VERIFICATION_FAILED : BPP_OK;
+}
+
 int bpp_weights_from_chains(const uint8_t *rng32_all, size_t n_groups, size_t n_per_group, uint8_t *weights32_out) {
   if ((!rng32_all || !weights32_out) && n_groups * n_per_group) return BPP_ERR_INVALID_ARGUMENT;
   if (n_groups == 0 || n_per_group == 0) return BPP_OK;

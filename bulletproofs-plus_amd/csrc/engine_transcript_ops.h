@@ -1,7 +1,8 @@
 // Merlin on the stream (bpp_transcripts_enqueue, include/bpp.h): the engine's side of transcript_ops.h.  The refusals -- the
 // arguments' own (transcript_ops_refusal) and the pointer kinds -- come before anything is counted or launched; then the launch
 // arguments are made on the host (the labels copied, NEW's state computed once) and at most three launches go onto the context's
-// stream: the record's init, k_transcript_ops over n blocks of one wavefront, the record's finish.  Nothing is allocated but the
+// stream: the record's init, k_transcript_ops (or k_transcript_ops_rng, where the program holds a transcript-protocol or transcript-RNG
+// kind) over n blocks of one wavefront, the record's finish.  Nothing is allocated but the
 // context's ticket events (once, where no enqueue made them), nothing is copied, nothing is waited for.
 #pragma once
 
@@ -37,8 +38,12 @@ extern "C" int bpp_transcripts_enqueue(bpp_ctx *ctx, uint8_t *states203_dev, siz
     ts.calls++;
     if (ts.calls == 1) ts.first_calls++;
     if (record_dev) hipLaunchKernelGGL(k_transcript_record_init, dim3(1), dim3(64), 0, s, record_dev);
-    hipLaunchKernelGGL(k_transcript_ops, dim3((uint32_t)n), dim3(64), 0, s, a);
-    if (record_dev) hipLaunchKernelGGL(k_transcript_record_finish, dim3(1), dim3(64), 0, s, record_dev);
+    // (the program's kinds are public: one that holds none of the transcript-protocol / RNG kinds runs the kernel without them)
+    const bool extended = transcript_ops_extended(a);
+    if (extended) hipLaunchKernelGGL(k_transcript_ops_rng, dim3((uint32_t)n), dim3(64), 0, s, a);
+    else hipLaunchKernelGGL(k_transcript_ops, dim3((uint32_t)n), dim3(64), 0, s, a);
+    if (record_dev && extended) hipLaunchKernelGGL(k_transcript_record_finish_or, dim3(1), dim3(64), 0, s, record_dev);
+    else if (record_dev) hipLaunchKernelGGL(k_transcript_record_finish, dim3(1), dim3(64), 0, s, record_dev);
     HIP_CHECK(hipGetLastError());
     const uint64_t t = ctx->enq_next++;
     HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));

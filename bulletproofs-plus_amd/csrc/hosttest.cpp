@@ -18,8 +18,11 @@ static thread_local std::vector<uint8_t> *g_ct_trace = nullptr;
     if (g_ct_trace) g_ct_trace->push_back((uint8_t)(entry));     \
   } while (0)
 #include "ct.h"
+#include "transcript_ops.h"
 using namespace bpp;
 extern "C" {
+// the scalar routine of challenge_scalar / Scalar::random (transcript_ops.h): 64 wide bytes -> canonical bytes, 1 where zero
+uint32_t ht_top_scalar_from_wide(const uint8_t wide[64], uint8_t out32[32]) { return top_scalar_from_wide(out32, wide); }
 // scalar * P through ct_scalarmul -> compressed result; trace_out (may be null) receives the sequence of table entries read
 // (trace_cap bytes at most), *trace_len their number.  0 if P does not decode.
 int ht_ct_scalarmul(const uint8_t point32[32], const uint8_t scalar32[32], uint8_t out32[32], uint8_t *trace_out, size_t trace_cap,

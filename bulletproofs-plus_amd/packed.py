@@ -692,9 +692,74 @@ class TChallenge:
         self.label, self.nbytes, self.out = bytes(label), int(nbytes), out
 
 
+TOP_APPEND_POINT, TOP_CHALLENGE_SCALAR = 16, 17
+TOP_RNG_BEGIN, TOP_RNG_REKEY, TOP_RNG_FINALIZE, TOP_RNG_FILL, TOP_RNG_FILL32, TOP_RNG_SCALARS = 32, 33, 34, 35, 36, 37
+TOPS_IDENTITY, TOPS_ZERO_SCALAR = 2, 4
+
+
+class TAppendPoint(TAppend):
+    """validate_and_append_point(label, row i of data): data is a uint8 [n, 32] device tensor (or a tuple as for TAppend).  A row of 32
+    zero bytes -- the identity's encoding -- makes its transcript row void (record flag TOPS_IDENTITY)."""
+
+    def __init__(self, label, data):
+        TAppend.__init__(self, label, data, None)
+
+
+class TChallengeScalar(TChallenge):
+    """challenge_scalar(label): 64 challenge bytes reduced wide mod l, the 32 canonical bytes into row i of out (uint8 [n, 32], a
+    tuple, or None for a fresh tensor).  A zero scalar makes the row void (TOPS_ZERO_SCALAR)."""
+
+    def __init__(self, label, out=None):
+        TChallenge.__init__(self, label, 32, out)
+
+
+class TRngBegin:
+    """build_rng(): the program's transcript RNG becomes a clone of the row's transcript as it stands here.  The RNG lives for the
+    length of the program; the row's 203 bytes are not changed by any TRng* operation."""
+    label = b""
+
+
+class TRngRekey(TAppend):
+    """rekey_with_witness_bytes(label, row i of data): data and lens as for TAppend.  The rows are secrets."""
+
+
+class TRngFinalize:
+    """finalize(&mut rng): entropy is a uint8 [n, 32] device tensor (or tuple) -- the one draw from the caller's own RNG, per row -- or
+    None for the reference's NullRng (32 zero bytes)"""
+    label = b""
+
+    def __init__(self, entropy=None):
+        self.entropy = entropy
+
+
+class TRngFill(TChallenge):
+    """one fill_bytes(nbytes) of the finalised RNG into row i of out (as for TChallenge)"""
+
+    def __init__(self, nbytes, out=None):
+        TChallenge.__init__(self, b"", nbytes, out)
+
+
+class TRngFill32(TRngFill):
+    """nbytes / 32 successive fill_bytes(32): what a consumer drawing 32 bytes at a time sees -- the prover's rng row"""
+
+
+class TRngScalars(TChallenge):
+    """count successive Scalar::random(&mut rng), 32 canonical bytes each, into row i of out (uint8 [n, 32 * count]).  A zero scalar
+    makes the row void (TOPS_ZERO_SCALAR); the call does not redraw."""
+
+    def __init__(self, count, out=None):
+        TChallenge.__init__(self, b"", 32 * int(count), out)
+
+
+# (class, kind), the most derived first: what transcript_ops makes of an operation
+_TOP_READS = [(TAppendPoint, TOP_APPEND_POINT), (TRngRekey, TOP_RNG_REKEY), (TAppend, TOP_APPEND)]
+_TOP_WRITES = [(TChallengeScalar, TOP_CHALLENGE_SCALAR), (TRngFill32, TOP_RNG_FILL32), (TRngFill, TOP_RNG_FILL), (TRngScalars, TOP_RNG_SCALARS),
+               (TChallenge, TOP_CHALLENGE)]
+
+
 class TranscriptsEnqueued:
     """What transcript_ops returns: `.states` (the rows, advanced in place), `.outputs` (one tensor -- or whatever was passed -- per
-    TChallenge, in program order), `.done_mask` (uint8 [n]: 1 where the row was advanced) and `.record` (int32 [4]: n_done, n_void,
+    operation that writes rows: TChallenge, TChallengeScalar, TRngFill, TRngFill32, TRngScalars, in program order), `.done_mask` (uint8 [n]: 1 where the row was advanced) and `.record` (int32 [4]: n_done, n_void,
     first_void, flags) -- valid in stream order behind the call -- and the ticket: done() is one event query, wait() blocks until
     the call has run, result() waits and returns the record as a dict (first_void None where no row was void)."""
 
@@ -716,7 +781,8 @@ class TranscriptsEnqueued:
 
 
 def transcript_ops(engine, states, ops, live=None, done_mask=None, record=None):
-    """bpp_transcripts_enqueue: the program `ops` (TNew / TAppend / TChallenge, at most 8) on the n rows of `states` -- a uint8 [n, 203]
+    """bpp_transcripts_enqueue: the program `ops` (TNew / TAppend / TChallenge; TAppendPoint / TChallengeScalar; TRngBegin / TRngRekey /
+    TRngFinalize / TRngFill / TRngFill32 / TRngScalars -- at most 8) on the n rows of `states` -- a uint8 [n, 203]
     device tensor at any byte address (a slice of a larger tensor will do) or an (address, (n, 203)) pair -- in place, on the engine's
     stream, without waiting.  live: a uint8 [n] device tensor (0 = dead: the row is neither read nor written), or None.  done_mask and
     record default to fresh tensors.  Ordering is DevicePackedInput.order_before's: an engine made on torch's current stream needs
@@ -760,15 +826,23 @@ def transcript_ops(engine, states, ops, live=None, done_mask=None, record=None):
         o.label, o.label_len = (None if lab is None else lab.ctypes.data), len(op.label)
         if isinstance(op, TNew):
             o.kind = TOP_NEW
+        elif isinstance(op, TRngBegin):
+            o.kind = TOP_RNG_BEGIN
+        elif isinstance(op, TRngFinalize):
+            o.kind = TOP_RNG_FINALIZE
+            if op.entropy is not None:
+                o.data_dev, rows_n, o.len, o.stride = rows(op.entropy, "ops[%d].entropy" % j)
+                if rows_n != n:
+                    raise api.ProofError(api.ProofErrorKind.InvalidLength, "ops[%d].entropy: %d rows for %d states" % (j, rows_n, n))
         elif isinstance(op, TAppend):
-            o.kind = TOP_APPEND
+            o.kind = next(k for c, k in _TOP_READS if isinstance(op, c))
             if op.data is not None:
                 o.data_dev, rows_n, o.len, o.stride = rows(op.data, "ops[%d].data" % j)
                 if rows_n != n:
                     raise api.ProofError(api.ProofErrorKind.InvalidLength, "ops[%d].data: %d rows for %d states" % (j, rows_n, n))
             o.lens_dev = flat(op.lens, "ops[%d].lens" % j, 4)
         elif isinstance(op, TChallenge):
-            o.kind = TOP_CHALLENGE
+            o.kind = next(k for c, k in _TOP_WRITES if isinstance(op, c))
             out = op.out
             if out is None and op.nbytes:
                 out = torch.zeros((n, op.nbytes), dtype=torch.uint8, device=dev)
@@ -778,7 +852,7 @@ def transcript_ops(engine, states, ops, live=None, done_mask=None, record=None):
                     raise api.ProofError(api.ProofErrorKind.InvalidLength, "ops[%d].out: (%d, %d) expected" % (j, n, op.nbytes))
             outputs.append(out)
         else:
-            raise api.ProofError(api.ProofErrorKind.InvalidArgument, "ops[%d]: TNew, TAppend or TChallenge expected" % j)
+            raise api.ProofError(api.ProofErrorKind.InvalidArgument, "ops[%d]: a T* operation of this module expected" % j)
     if done_mask is None:
         done_mask = torch.zeros((n,), dtype=torch.uint8, device=dev)
     if record is None:

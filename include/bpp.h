@@ -1276,6 +1276,32 @@ int bpp_transcript_new(const uint8_t *label, size_t label_len, uint8_t state203[
 int bpp_transcript_append_message(uint8_t state203[203], const uint8_t *label, size_t label_len, const uint8_t *msg, size_t msg_len);
 int bpp_transcript_challenge_bytes(uint8_t state203[203], const uint8_t *label, size_t label_len, uint8_t *out, size_t out_len);
 
+/* The reference's public TranscriptProtocol (src/protocols/transcript_protocol.rs) and merlin's transcript RNG on 203-byte states in
+ * the caller's memory (host only, no device, no context): what the new kinds of bpp_transcripts_enqueue are held to.  pos >= 166 is
+ * refused as above.  errbuf (or NULL) receives the reference's message text.
+ *   _validate_and_append_point  32 zero bytes (the identity's encoding): BPP_ERR_VERIFICATION_FAILED, "Identity element cannot be added
+ *                               to the transcript", the state untouched; otherwise append_message(label, point32).
+ *   _challenge_scalar           challenge_bytes(label, 64) reduced wide mod l into out32 (canonical, little-endian).  Zero:
+ *                               BPP_ERR_VERIFICATION_FAILED, "Transcript challenge cannot be zero" (the state has advanced, as in the
+ *                               reference; out32 is 32 zero bytes).
+ *   _rng_begin                  build_rng(): rng203_out := a copy of state203.  The "RNG state" of the calls below is that copy: the
+ *                               builder until _rng_finalize, the TranscriptRng behind it.  It is keyed with the witness: wipe it.
+ *   _rng_rekey                  rekey_with_witness_bytes(label, witness).
+ *   _rng_finalize               finalize(&mut rng) with random32 the external RNG's one draw of 32 bytes; NULL: NullRng, 32 zero bytes.
+ *   _rng_fill                   one fill_bytes(out_len).
+ *   _rng_scalar                 Scalar::random: fill_bytes(64) reduced wide into out32.  Zero: BPP_ERR_VERIFICATION_FAILED, "Random
+ *                               scalar is zero" -- this library's own words: the reference has no such error, its
+ *                               ScalarProtocol::random_not_zero draws again; this call does not (the caller may). */
+int bpp_transcript_validate_and_append_point(uint8_t state203[203], const uint8_t *label, size_t label_len, const uint8_t point32[32],
+                                             char *errbuf, size_t errbuf_len);
+int bpp_transcript_challenge_scalar(uint8_t state203[203], const uint8_t *label, size_t label_len, uint8_t out32[32], char *errbuf,
+                                    size_t errbuf_len);
+int bpp_transcript_rng_begin(const uint8_t state203[203], uint8_t rng203_out[203]);
+int bpp_transcript_rng_rekey(uint8_t rng203[203], const uint8_t *label, size_t label_len, const uint8_t *witness, size_t witness_len);
+int bpp_transcript_rng_finalize(uint8_t rng203[203], const uint8_t random32[32] /* or NULL: NullRng */);
+int bpp_transcript_rng_fill(uint8_t rng203[203], uint8_t *out, size_t out_len);
+int bpp_transcript_rng_scalar(uint8_t rng203[203], uint8_t out32[32], char *errbuf, size_t errbuf_len);
+
 /* ---- Merlin on the stream: the three calls above, row-wise, on transcript rows in device memory ----
  * bpp_transcripts_enqueue runs a short program of Merlin operations on n rows of 203 bytes in device memory (any byte address, IN
  * PLACE), one wavefront per row on the context's stream: it MAKES the rows a *_transcripts / item_states_dev call takes (NEW, then
@@ -1314,10 +1340,60 @@ int bpp_transcript_challenge_bytes(uint8_t state203[203], const uint8_t *label, 
  * of the call.
  * STEADY STATE: after a context's first call (the ticket events) the call allocates nothing, copies nothing to the host and waits
  * for nothing: bpp_transcripts_stats' host_waits stays 0.  TICKETS are those of bpp_enqueue_done / bpp_enqueue_wait.
- * The rows and everything appended here are the caller's public protocol data; the kernel wipes its LDS all the same. */
+ * The rows and everything appended here are the caller's public protocol data; the kernel wipes its LDS all the same.
+ *
+ * THE TRANSCRIPT PROTOCOL AND THE TRANSCRIPT RNG (the reference's public TranscriptProtocol, src/protocols/transcript_protocol.rs, and
+ * merlin's TranscriptRngBuilder / TranscriptRng, call for call).  Eight more kinds; a program of NEW / APPEND / CHALLENGE alone runs
+ * the kernel it always ran and behaves byte for byte as above.
+ *   BPP_TOP_APPEND_POINT      validate_and_append_point(label, row i of data_dev): len must be 32, no lens_dev.  A row of 32 zero bytes
+ *                             (the identity's encoding) makes the row VOID, decided up front like the other void rules; any other row
+ *                             is an APPEND of its 32 bytes.  append_point and append_scalar are plain APPENDs of 32 bytes.
+ *   BPP_TOP_CHALLENGE_SCALAR  challenge_scalar(label): challenge_bytes(label, 64) reduced wide mod l (Scalar::from_bytes_mod_order_wide),
+ *                             the 32 canonical little-endian bytes into row i of data_dev; len must be 32.  The transcript advances
+ *                             exactly as under CHALLENGE with len 64.  A ZERO result ("Transcript challenge cannot be zero") voids the
+ *                             row in the middle of its program: it ends like every void row.
+ *   The transcript RNG lives in the kernel's LDS for the length of the row's program and is never written to memory:
+ *   BPP_TOP_RNG_BEGIN         build_rng(): the RNG := a clone of the row's transcript as it stands at this point of the program.  No
+ *                             label, no data.  A second BEGIN drops the RNG before it.
+ *   BPP_TOP_RNG_REKEY         rekey_with_witness_bytes(label, row i of data_dev): len bytes, or lens_dev[i] under the cap len
+ *                             (lens_dev[i] > len: void, as for APPEND).
+ *   BPP_TOP_RNG_FINALIZE      finalize(&mut rng): data_dev holds rows of 32 bytes, the one draw from the caller's own RNG (len must be
+ *                             32); data_dev NULL with len 0 is the reference's NullRng, 32 zero bytes.
+ *   BPP_TOP_RNG_FILL          one fill_bytes of len bytes into row i of data_dev.
+ *   BPP_TOP_RNG_FILL32        len / 32 successive fill_bytes of 32 bytes each (len a multiple of 32): what a consumer that draws 32
+ *                             bytes at a time sees, the prover's rng row under prove_with_rng(.., &mut TranscriptRng).  merlin absorbs
+ *                             the length before every draw, so these are not the bytes of one FILL of len.
+ *   BPP_TOP_RNG_SCALARS       len / 32 successive Scalar::random(&mut rng): fill_bytes(64) reduced wide, 32 canonical bytes each.  A
+ *                             zero scalar VOIDS the row; the call does not redraw as ScalarProtocol::random_not_zero does -- a redraw
+ *                             is a loop whose trip count depends on secret data, and the event has probability 2^-252.
+ *   No RNG op changes the row's 203 bytes (build_rng works on a clone); APPEND / CHALLENGE between RNG ops act on the transcript and not
+ *   on the RNG.  FINALIZE, FILL, FILL32 and SCALARS have no label in merlin and take none.
+ * THE CONTRACT for these kinds is the same: a live row that is not void ends up as, and every output row (CHALLENGE, CHALLENGE_SCALAR,
+ * RNG_FILL, RNG_FILL32, RNG_SCALARS) holds, what the host helpers below (bpp_transcript_validate_and_append_point, _challenge_scalar,
+ * _rng_begin, _rng_rekey, _rng_finalize, _rng_fill, _rng_scalar; FILL32 and SCALARS are loops of _rng_fill(.., 32) and _rng_scalar)
+ * leave on a host copy in program order.  Void and dead rows have EVERY output row of the program zeroed -- a row that goes void in the
+ * middle of its program included, which also becomes 203 zero bytes, counts in n_void and competes for first_void -- and nothing of a
+ * dead row's REKEY and FINALIZE rows is read.  Of a void row the APPEND_POINT rows alone may be read (that is how an identity is found),
+ * and only where no other rule voids the row.
+ * flags beside BPP_TOPS_WRITTEN: BPP_TOPS_IDENTITY -- some live row was voided by an APPEND_POINT; BPP_TOPS_ZERO_SCALAR -- by a zero
+ * scalar.  A program of the three kinds above reads exactly BPP_TOPS_WRITTEN.
+ * REFUSED as well: len other than 32 on APPEND_POINT, CHALLENGE_SCALAR or a FINALIZE with data; len not a multiple of 32 on FILL32 /
+ * SCALARS; lens_dev on anything but APPEND / RNG_REKEY; RNG_BEGIN with a label or data; REKEY or FINALIZE without a BEGIN in front, or
+ * behind that RNG's FINALIZE; FILL / FILL32 / SCALARS without a finalised RNG; a label on FINALIZE / FILL / FILL32 / SCALARS; the pointer
+ * kinds and the overlap rule, with REKEY's, FINALIZE's and APPEND_POINT's rows read and every output row written.
+ * SECRETS: REKEY's and FINALIZE's rows and everything FILL / FILL32 / SCALARS write.  No branch, address or launch geometry depends on
+ * them but the void on a zero scalar, which is the reference's error; the kernel's LDS is wiped on every path. */
 #define BPP_TOP_NEW 1
 #define BPP_TOP_APPEND 2
 #define BPP_TOP_CHALLENGE 3
+#define BPP_TOP_APPEND_POINT 16
+#define BPP_TOP_CHALLENGE_SCALAR 17
+#define BPP_TOP_RNG_BEGIN 32
+#define BPP_TOP_RNG_REKEY 33
+#define BPP_TOP_RNG_FINALIZE 34
+#define BPP_TOP_RNG_FILL 35
+#define BPP_TOP_RNG_FILL32 36
+#define BPP_TOP_RNG_SCALARS 37
 #define BPP_TOP_MAX_OPS 8
 #define BPP_TOP_LABEL_MAX 64
 #define BPP_TOP_LEN_MAX 65536
@@ -1333,9 +1409,11 @@ typedef struct {
 typedef struct {
   uint32_t n_done, n_void;
   uint32_t first_void; /* 0xFFFFFFFF: none */
-  uint32_t flags;      /* BPP_TOPS_WRITTEN */
+  uint32_t flags;      /* BPP_TOPS_WRITTEN | BPP_TOPS_IDENTITY | BPP_TOPS_ZERO_SCALAR */
 } bpp_device_transcripts_record;
 #define BPP_TOPS_WRITTEN 1u
+#define BPP_TOPS_IDENTITY 2u    /* some live row was voided by an APPEND_POINT of the identity's encoding */
+#define BPP_TOPS_ZERO_SCALAR 4u /* some live row was voided by a zero CHALLENGE_SCALAR or RNG_SCALARS result */
 int bpp_transcripts_enqueue(bpp_ctx *ctx, uint8_t *states203_dev /* DEVICE n x 203, any byte address, IN PLACE */, size_t n,
                             const bpp_transcript_op *ops, size_t n_ops,
                             const uint8_t *live_dev /* DEVICE n bytes, or NULL: every row */,

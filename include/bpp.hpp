@@ -364,6 +364,53 @@ class Engine {
     o.data_dev = out_dev, o.len = len, o.stride = stride ? stride : len;
     return o;
   }
+  // The reference's TranscriptProtocol and merlin's transcript RNG as operations of the same program (bpp.h: BPP_TOP_APPEND_POINT ..
+  // BPP_TOP_RNG_SCALARS).  op_append_point voids a row whose point is 32 zero bytes; op_challenge_scalar and op_rng_scalars void a row
+  // on a zero scalar.  The RNG lives for the length of the program: op_rng_begin, op_rng_rekey (any number), op_rng_finalize, then
+  // op_rng_fill / op_rng_fill32 / op_rng_scalars; none of them changes the row's 203 bytes.
+  static bpp_transcript_op op_append_point(const uint8_t *label, uint32_t label_len, const uint8_t *points_dev, size_t stride = 0) {
+    bpp_transcript_op o = op_append(label, label_len, points_dev, 32, stride);
+    o.kind = BPP_TOP_APPEND_POINT;
+    return o;
+  }
+  static bpp_transcript_op op_challenge_scalar(const uint8_t *label, uint32_t label_len, uint8_t *out_dev, size_t stride = 0) {
+    bpp_transcript_op o = op_challenge(label, label_len, out_dev, 32, stride);
+    o.kind = BPP_TOP_CHALLENGE_SCALAR;
+    return o;
+  }
+  static bpp_transcript_op op_rng_begin() {
+    bpp_transcript_op o{};
+    o.kind = BPP_TOP_RNG_BEGIN;
+    return o;
+  }
+  static bpp_transcript_op op_rng_rekey(const uint8_t *label, uint32_t label_len, const uint8_t *witness_dev, uint32_t len, size_t stride = 0,
+                                        const uint32_t *lens_dev = nullptr) {
+    bpp_transcript_op o = op_append(label, label_len, witness_dev, len, stride, lens_dev);
+    o.kind = BPP_TOP_RNG_REKEY;
+    return o;
+  }
+  // entropy_dev: n rows of 32 bytes, the one draw from the caller's own RNG; null: the reference's NullRng
+  static bpp_transcript_op op_rng_finalize(const uint8_t *entropy_dev = nullptr, size_t stride = 0) {
+    bpp_transcript_op o{};
+    o.kind = BPP_TOP_RNG_FINALIZE;
+    if (entropy_dev) o.data_dev = const_cast<uint8_t *>(entropy_dev), o.len = 32, o.stride = stride ? stride : 32;
+    return o;
+  }
+  static bpp_transcript_op op_rng_fill(uint8_t *out_dev, uint32_t len, size_t stride = 0) {
+    bpp_transcript_op o = op_challenge(nullptr, 0, out_dev, len, stride);
+    o.kind = BPP_TOP_RNG_FILL;
+    return o;
+  }
+  static bpp_transcript_op op_rng_fill32(uint8_t *out_dev, uint32_t len, size_t stride = 0) {
+    bpp_transcript_op o = op_challenge(nullptr, 0, out_dev, len, stride);
+    o.kind = BPP_TOP_RNG_FILL32;
+    return o;
+  }
+  static bpp_transcript_op op_rng_scalars(uint8_t *out_dev, uint32_t count, size_t stride = 0) {
+    bpp_transcript_op o = op_challenge(nullptr, 0, out_dev, 32 * count, stride);
+    o.kind = BPP_TOP_RNG_SCALARS;
+    return o;
+  }
   // live (n device bytes, 0 = dead: the row is neither read nor written), done_mask (n device bytes) and record may be null.  Enqueues
   // behind everything on the engine's stream and returns; the ticket is an enqueue ticket (results() is not for it).
   EnqueueTicket transcripts_enqueue(uint8_t *states203_dev, size_t n, const std::vector<bpp_transcript_op> &ops, const uint8_t *live_dev = nullptr,
@@ -423,6 +470,57 @@ class Transcript {
     check(bpp_transcript_challenge_bytes(state_.data(), reinterpret_cast<const uint8_t *>(label.data()), label.size(), out.data(), n),
           "transcript state has pos >= rate");
     return out;
+  }
+  // The reference's TranscriptProtocol (src/protocols/transcript_protocol.rs) on the state: thin wrappers of the host helpers that the
+  // device kinds BPP_TOP_APPEND_POINT / BPP_TOP_CHALLENGE_SCALAR are held to.  They throw the reference's ProofError.
+  void validate_and_append_point(const std::string &label, const Bytes32 &point) {
+    materialise();
+    char err[128] = "transcript state has pos >= rate";
+    check(bpp_transcript_validate_and_append_point(state_.data(), reinterpret_cast<const uint8_t *>(label.data()), label.size(), point.data(), err,
+                                                   sizeof(err)), err);
+  }
+  Bytes32 challenge_scalar(const std::string &label) {
+    materialise();
+    Bytes32 out{};
+    char err[128] = "transcript state has pos >= rate";
+    check(bpp_transcript_challenge_scalar(state_.data(), reinterpret_cast<const uint8_t *>(label.data()), label.size(), out.data(), err, sizeof(err)),
+          err);
+    return out;
+  }
+  // merlin's TranscriptRngBuilder / TranscriptRng on a clone of the state (bpp_transcript_rng_*): build_rng(), then rekey_with_witness_bytes
+  // any number of times, finalize (null: the reference's NullRng), then fill_bytes / scalar.  The state is keyed with the witness: it is
+  // wiped when the object goes.
+  class Rng {
+   public:
+    ~Rng() {
+      volatile uint8_t *p = st_.data();
+      for (size_t k = 0; k < st_.size(); k++) p[k] = 0;
+    }
+    Rng &rekey_with_witness_bytes(const std::string &label, const uint8_t *witness, size_t len) {
+      check(bpp_transcript_rng_rekey(st_.data(), reinterpret_cast<const uint8_t *>(label.data()), label.size(), witness, len), "bpp_transcript_rng_rekey");
+      return *this;
+    }
+    Rng &finalize(const uint8_t *random32 = nullptr) {
+      check(bpp_transcript_rng_finalize(st_.data(), random32), "bpp_transcript_rng_finalize");
+      return *this;
+    }
+    void fill_bytes(uint8_t *out, size_t len) { check(bpp_transcript_rng_fill(st_.data(), out, len), "bpp_transcript_rng_fill"); }
+    Bytes32 scalar() {
+      Bytes32 out{};
+      char err[128] = "bpp_transcript_rng_scalar";
+      check(bpp_transcript_rng_scalar(st_.data(), out.data(), err, sizeof(err)), err);
+      return out;
+    }
+
+   private:
+    friend class Transcript;
+    std::array<uint8_t, 203> st_{};
+  };
+  Rng build_rng() {
+    materialise();
+    Rng r;
+    check(bpp_transcript_rng_begin(state_.data(), r.st_.data()), "transcript state has pos >= rate");
+    return r;
   }
   // what an advancing call (RangeProof::verify_batch / prove_batch / prove_with_rng with a transcript POINTER) leaves behind
   void advance_to(const uint8_t state203[203]) {

@@ -182,6 +182,14 @@ pub struct bpp_transcript_op {
 pub const BPP_TOP_NEW: u32 = 1;
 pub const BPP_TOP_APPEND: u32 = 2;
 pub const BPP_TOP_CHALLENGE: u32 = 3;
+pub const BPP_TOP_APPEND_POINT: u32 = 16;
+pub const BPP_TOP_CHALLENGE_SCALAR: u32 = 17;
+pub const BPP_TOP_RNG_BEGIN: u32 = 32;
+pub const BPP_TOP_RNG_REKEY: u32 = 33;
+pub const BPP_TOP_RNG_FINALIZE: u32 = 34;
+pub const BPP_TOP_RNG_FILL: u32 = 35;
+pub const BPP_TOP_RNG_FILL32: u32 = 36;
+pub const BPP_TOP_RNG_SCALARS: u32 = 37;
 pub const BPP_TOP_MAX_OPS: usize = 8;
 pub const BPP_TOP_LABEL_MAX: u32 = 64;
 pub const BPP_TOP_LEN_MAX: u32 = 65536;
@@ -196,6 +204,8 @@ pub struct bpp_device_transcripts_record {
     pub flags: u32,
 }
 pub const BPP_TOPS_WRITTEN: u32 = 1;
+pub const BPP_TOPS_IDENTITY: u32 = 2;
+pub const BPP_TOPS_ZERO_SCALAR: u32 = 4;
 
 /// `struct bpp_transcripts_stats`: what the `bpp_transcripts_enqueue` calls of a context cost the host
 #[repr(C)]
@@ -614,6 +624,16 @@ extern "C" {
     pub fn bpp_transcript_new(label: *const u8, label_len: usize, state203: *mut u8) -> c_int;
     pub fn bpp_transcript_append_message(state203: *mut u8, label: *const u8, label_len: usize, msg: *const u8, msg_len: usize) -> c_int;
     pub fn bpp_transcript_challenge_bytes(state203: *mut u8, label: *const u8, label_len: usize, out: *mut u8, out_len: usize) -> c_int;
+    // the reference's TranscriptProtocol and merlin's transcript RNG on 203-byte states (host only)
+    pub fn bpp_transcript_validate_and_append_point(state203: *mut u8, label: *const u8, label_len: usize, point32: *const u8,
+                                                    errbuf: *mut c_char, errbuf_len: usize) -> c_int;
+    pub fn bpp_transcript_challenge_scalar(state203: *mut u8, label: *const u8, label_len: usize, out32: *mut u8, errbuf: *mut c_char,
+                                           errbuf_len: usize) -> c_int;
+    pub fn bpp_transcript_rng_begin(state203: *const u8, rng203_out: *mut u8) -> c_int;
+    pub fn bpp_transcript_rng_rekey(rng203: *mut u8, label: *const u8, label_len: usize, witness: *const u8, witness_len: usize) -> c_int;
+    pub fn bpp_transcript_rng_finalize(rng203: *mut u8, random32: *const u8) -> c_int;
+    pub fn bpp_transcript_rng_fill(rng203: *mut u8, out: *mut u8, out_len: usize) -> c_int;
+    pub fn bpp_transcript_rng_scalar(rng203: *mut u8, out32: *mut u8, errbuf: *mut c_char, errbuf_len: usize) -> c_int;
     pub fn bpp_transcripts_enqueue(ctx: *mut bpp_ctx, states203_dev: *mut u8, n: usize, ops: *const bpp_transcript_op, n_ops: usize,
                                    live_dev: *const u8, done_mask_dev: *mut u8, record_dev: *mut bpp_device_transcripts_record,
                                    ticket: *mut u64) -> c_int;

@@ -255,6 +255,40 @@ def transcript_ops_section():
     return out + [""]
 
 
+def transcript_rng_section():
+    """profiles/transcript_rng.json (tools/bench_transcript_rng.py): the transcript-RNG program of bpp_transcripts_enqueue against the
+    host route; "existing_program_ab": the NEW + APPEND + CHALLENGE program on this tree and on the parent commit's library"""
+    f = os.path.join(P, "transcript_rng.json")
+    out = ["## The transcript RNG on the stream: `RNG_BEGIN .. RNG_SCALARS` against the host route (`tools/bench_transcript_rng.py`, "
+           "`profiles/transcript_rng.json`)", ""]
+    if not os.path.exists(f):
+        return out + ["unmeasured", ""]
+    doc = json.load(open(f))
+    if doc.get("sizes"):
+        out += ["One thread, an engine on torch's stream.  The program: RNG_BEGIN, RNG_REKEY(32 B), RNG_FINALIZE(32 B of entropy), RNG_FILL32 of %d bytes "
+                "(a configs[4]-shaped rng row), RNG_SCALARS x %d.  Device: calls back to back for a window of %.1f s around one stream synchronise.  "
+                "Host route: the host helpers per row on one core -- called from Python through ctypes; the last columns take the measured cost of as "
+                "many empty ctypes calls off -- plus the copy to the device.  Nothing was promised.  Box: \"%s\"." %
+                (doc["rng_row_bytes"], doc["scalars"], doc["window_s"], doc["box"]), "",
+                "| rows | device ms per call | device M rows/s | host route ms per step (lowest-highest) | host / device | less ctypes: host ms | host / device |",
+                "|---|---|---|---|---|---|---|"]
+        for r in doc["sizes"]:
+            out.append("| %d | %.4f | %.2f | %.1f (%.1f-%.1f) | %.0f | %.1f | %.0f |" %
+                       (r["n"], r["device_ms_per_call"], r["device_rows_per_s"] / 1e6, r["host_ms_per_step"], r["host_ms_low"], r["host_ms_high"],
+                        r["host_over_device"], r["host_ms_less_ctypes"], r["host_less_ctypes_over_device"]))
+    ab = doc.get("existing_program_ab")
+    if ab:
+        out += ["", "The existing program (%s) on this tree against the parent commit's library, alternating in one call (`tools/gpu_ab.py --leg cmd`), "
+                "%s; the parent stands twice in every repetition, and its own lowest-highest is the spread this tree is held to:" % (ab["program"], ab["unit"]),
+                "", "| rows | parent: median (lowest-highest) | this tree: median (lowest-highest) | inside the parent's spread |", "|---|---|---|---|"]
+        for size, a in ab["sizes"].items():
+            out.append("| %s | %.4f (%.4f-%.4f) | %s | %s |" %
+                       (size, a["parent_median"], a["parent_spread"][0], a["parent_spread"][1],
+                        "%.4f (%.4f-%.4f)" % (a["this_median"], min(a["this"]), max(a["this"])) if a["this"] else "unmeasured",
+                        "yes" if a["this_inside_parent_spread"] else "no"))
+    return out + [""]
+
+
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r03_v1"
     out = ["# RESULTS — measured figures (generated by `tools/results_table.py %s` from `profiles/`; do not edit)" % tag, "",
@@ -549,6 +583,7 @@ def main():
     out += prove_device_section()
     out += prove_enqueue_section()
     out += transcript_ops_section()
+    out += transcript_rng_section()
     ks, fks = load(tag, "kernel_stats_cfg2_default.csv")
     sq, fsq = load(tag, "pmc_sq_summary.csv")
     if ks:
