@@ -3605,6 +3605,19 @@ void enqueue_ticket_wait(bpp_ctx *ctx, uint64_t ticket) {
   if (ticket == 0 || ctx->enq_events.empty()) return;
   HIP_CHECK(hipEventSynchronize(ctx->enq_events[ticket % ctx->enq_events.size()]));
 }
+// the context's 64 ticket events, made by whichever stream call comes first; true: this call made them
+bool enqueue_events_ensure(bpp_ctx *ctx) {
+  if (!ctx->enq_events.empty()) return false;
+  ctx->enq_events.resize(64);
+  for (auto &e : ctx->enq_events) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  return true;
+}
+// the next ticket, its event recorded behind what is on `s` now (the events exist: enqueue_events_ensure)
+uint64_t enqueue_ticket_issue(bpp_ctx *ctx, hipStream_t s) {
+  const uint64_t t = ctx->enq_next++;
+  HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));
+  return t;
+}
 
 // would layout_groups(ctx, b, chunk, bounds) find its layout there?  (the same test)
 bool layout_is_current(const Batch &b, size_t chunk, const std::vector<uint32_t> *bounds) {
@@ -3669,10 +3682,7 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
         enqueue_ticket_wait(ctx, b.enq_last_ticket);
         es.host_waits++;
       }
-      if (ctx->enq_events.empty()) {
-        ctx->enq_events.resize(64);
-        for (auto &e : ctx->enq_events) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      }
+      (void)enqueue_events_ensure(ctx);
       ensure_ev_rng(ctx);
       layout_groups(ctx, b, chunk, bp);
       b.chain_wide.alloc((size_t)b.B * 16);
@@ -3796,10 +3806,7 @@ int verify_enqueue_locked(bpp_ctx *ctx, uint64_t batch, const uint32_t *group_fi
       hipLaunchKernelGGL(k_states_out, dim3(cdiv(b.B, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, so);
     }
     HIP_CHECK(hipGetLastError());
-    const uint64_t t = ctx->enq_next++;
-    HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));
-    b.enq_last_ticket = t;
-    *ticket = t;
+    *ticket = b.enq_last_ticket = enqueue_ticket_issue(ctx, s);
     es.calls++;
     es.groups += G;
     return BPP_OK;
@@ -3884,10 +3891,7 @@ void refill_enqueue_tail(bpp_ctx *ctx, Batch &b, bool nonces, const uint32_t *co
     first = true;
   }
   if (first) rs.first_calls++;
-  if (ctx->enq_events.empty()) {  // (the context's first ticket)
-    ctx->enq_events.resize(64);
-    for (auto &e : ctx->enq_events) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
+  (void)enqueue_events_ensure(ctx);
   if (count_dev) b.has_live = true;
   b.mask_form = live_dev != nullptr;
   b.partial_form = count_dev != nullptr || live_dev != nullptr;
@@ -3910,10 +3914,8 @@ void refill_enqueue_tail(bpp_ctx *ctx, Batch &b, bool nonces, const uint32_t *co
   b.status_clean = true;
   b.masks_dirty = false;  // (the kernel wiped every row)
   b.have_trace = b.phase1_done = false;
-  const uint64_t t = ctx->enq_next++;
-  HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));
-  b.enq_last_ticket = t;
-  if (ticket) *ticket = t;
+  b.enq_last_ticket = enqueue_ticket_issue(ctx, s);
+  if (ticket) *ticket = b.enq_last_ticket;
   rs.calls++;
 }
 
@@ -4193,10 +4195,8 @@ int bpp_enqueue_weights(bpp_ctx *ctx, uint64_t batch, uint8_t *weights_dev, uint
     if (kind != BPP_PTR_THIS_DEVICE)
       return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "weights_dev: not device memory of the context's device (pointer kind " + std::to_string(kind) + ")");
     HIP_CHECK(hipMemcpyAsync(weights_dev, b.weights.p, (size_t)b.B * 32, hipMemcpyDeviceToDevice, ctx->stream));
-    const uint64_t t = ctx->enq_next++;
-    HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], ctx->stream));
-    b.enq_last_ticket = t;
-    if (ticket) *ticket = t;
+    b.enq_last_ticket = enqueue_ticket_issue(ctx, ctx->stream);
+    if (ticket) *ticket = b.enq_last_ticket;
     return BPP_OK;
   }
   BPP_CATCH(ctx, nullptr, 0)

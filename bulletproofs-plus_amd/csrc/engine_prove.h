@@ -55,8 +55,7 @@ const char *const kSelfCheckRecoveryWhy =
 // -- plan, arena, streams, every step -- is the same.  A call without it enqueues launch for launch what it did.
 struct ProveDeviceIO {
   const bpp_prove_arrays *in;      // the caller's struct: device addresses, the host's m[] and transcript
-  std::vector<uint32_t> m_sorted;  // the aggregation factors of the call's slots, largest first
-  std::vector<ProveDevRow> rows;   // slot k -> the caller's item, its lengths
+  ProveDeviceShape shape;          // prove_device_shape of its m[] and strides: the slots (rows, m_sorted) and the refused items
   uint8_t *commitments_out;
   size_t commit_stride;
   uint8_t *proofs_out;
@@ -208,7 +207,7 @@ struct ProveCall {
     const ParamShape shape{P.n_bits, P.m_max, P.t};
     if (r.dev) {  // (every slot has passed the host's part of the checks; the rest is the ingest kernel's)
       const bpp_prove_arrays &in = *r.dev->in;
-      prove_plan_device(shape, P.hg32.data(), r.dev->m_sorted.data(), r.n_items, in.commitments32 != nullptr, in.transcript_state,
+      prove_plan_device(shape, P.hg32.data(), r.dev->shape.m_sorted.data(), r.n_items, in.commitments32 != nullptr, in.transcript_state,
                         in.transcript_label, in.label_len, pk, per_item_sub());
       set_shape();
       return;
@@ -444,7 +443,7 @@ struct ProveCall {
     pin_desc = pin_states + up8(pk.states.size());
     memcpy(pin_desc, pk.desc.data(), (size_t)B * sizeof(ProveDesc));
     pin_rows = pin_desc + (size_t)B * sizeof(ProveDesc);
-    memcpy(pin_rows, r.dev->rows.data(), (size_t)B * sizeof(ProveDevRow));
+    memcpy(pin_rows, r.dev->shape.rows.data(), (size_t)B * sizeof(ProveDevRow));
     if (resident) return;  // (a plan forks per enqueue, and nothing of it comes back to the host)
     pin_outcome = (bpp_device_prove_status *)ctx->prove_pin_out.p;
     fork_from_ctx();
@@ -1346,7 +1345,95 @@ extern "C" int bpp_prove_openings_item_message(bpp_ctx *ctx, uint64_t params, co
 // bpp_prove_openings_device_transcripts is the same call with one transcript per item IN (item_states: device rows of 203 bytes; the
 // pos >= rate finding is then the item's, raised by the ingest kernel, and the call-wide head of every transcript runs on the device)
 // and the advanced transcripts OUT (states_out: device rows of 203 bytes, zeros for every item that fails or is refused).
+// The blocking calls and the resident plan (engine_prove_plan.h) share the shape step (prove_device_shape, prove_ingest.h) and the
+// helpers below: the pointer kinds, the whole-call refusals, the overlap of the two state ranges, the refused items' launch.
 namespace {
+// one of the call's named arrays that this device cannot reach, in the order of the list (the last three: bpp_prove_enqueue's).
+// Empty: nothing to refuse.
+std::string prove_arrays_refusal(bpp_ctx *ctx, const bpp_prove_arrays &in, const void *commitments_out, const void *proofs_out,
+                                 const void *status_dev, const void *item_states, const void *states_out, const void *live = nullptr,
+                                 const void *ok_mask = nullptr, const void *summary = nullptr) {
+  const struct {
+    const char *name;
+    const void *p;
+  } arrays[] = {{"values", in.values},
+                {"blindings32", in.blindings32},
+                {"commitments32", in.commitments32},
+                {"min_values", in.min_values},
+                {"min_present", in.min_present},
+                {"seed_nonces32", in.seed_nonces32},
+                {"seed_present", in.seed_present},
+                {"rng_bytes", in.rng_bytes},
+                {"commitments_out_dev", commitments_out},
+                {"proofs_out_dev", proofs_out},
+                {"status_dev", status_dev},
+                {"item_states_dev", item_states},
+                {"states_out_dev", states_out},
+                {"live_dev", live},
+                {"ok_mask_dev", ok_mask},
+                {"summary_dev", summary}};
+  for (const auto &a : arrays) {
+    if (!a.p) continue;
+    const int kind = device_pointer_kind(ctx->device, a.p);
+    if (kind != BPP_PTR_THIS_DEVICE)
+      return std::string(a.name) + " is not device memory of this context's device (" + upload_pointer_kinds[kind] + ")";
+  }
+  return std::string();
+}
+
+// n_rows rows of item_states_dev and of states_out_dev share a byte (either may be null: no overlap)
+bool prove_states_overlap(const uint8_t *item_states, const uint8_t *states_out, size_t n_rows) {
+  const uintptr_t a = (uintptr_t)item_states, b = (uintptr_t)states_out, len = (uintptr_t)n_rows * BPP_ITEM_STATE_BYTES;
+  return item_states && states_out && a < b + len && b < a + len;
+}
+
+// What the blocking calls and bpp_prove_plan_create refuse of a whole call behind their own null checks, in this order; BPP_OK with
+// the parameters in Pp: nothing to refuse.  per_item: one transcript per item (item_states_dev, or the plan's flag); states_out: the
+// blocking call's (a plan has no rows yet).  The overlap cannot coincide with the state's position -- it needs item_states, under
+// which a transcript_state is refused before -- but it can with the two refusals behind it.  m[] is not read here.
+int prove_device_refusals(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays &in, bool per_item, const uint8_t *item_states,
+                          const uint8_t *states_out, std::shared_ptr<Params> &Pp, char *errbuf, size_t errbuf_len) {
+  if (device_pointer_kind(ctx->device, in.m) != BPP_PTR_HOST_OR_UNKNOWN)
+    return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m must be host memory: it sizes the call's layout", errbuf, errbuf_len);
+  if (in.m_stride == 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m_stride is 0", errbuf, errbuf_len);
+  if (ctx->opt.prove_check > 0)
+    return fail(ctx, BPP_ERR_INVALID_ARGUMENT,
+                "prove_check = 1 is not supported by bpp_prove_openings_device: the self-check remakes from host items; verify the outputs "
+                "with bpp_verify_batch_mixed_device",
+                errbuf, errbuf_len);
+  if (per_item && (in.transcript_state || in.transcript_label))
+    return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "transcript_state / transcript_label must be null: item i continues row i of item_states_dev",
+                errbuf, errbuf_len);
+  if (in.transcript_state && in.transcript_state[200] >= BPP_STROBE_R)
+    return fail(ctx, prove_err(BPP_PROVE_MSG_TRANSCRIPT_STATE).code, prove_msg_text(BPP_PROVE_MSG_TRANSCRIPT_STATE), errbuf, errbuf_len);
+  // (n_items <= 2^24 is checked below: a range is at most a few gigabytes, no overflow here)
+  if (prove_states_overlap(item_states, states_out, std::min<size_t>(in.n_items, (size_t)1 << 24)))
+    return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "item_states_dev and states_out_dev overlap", errbuf, errbuf_len);
+  Pp = params_registry().get(params);
+  if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
+  if (in.n_items > (1u << 24)) return fail(ctx, BPP_ERR_SIZE_OVERFLOW, "batch too large", errbuf, errbuf_len);
+  return BPP_OK;
+}
+
+// the refused items' records and zeroed slots: one launch of the emit kernel over their table (device memory, n rows) in front of
+// the call's own launches.  A refused item's state row is zeroed: its rows carry their finding.
+void launch_prove_refused(hipStream_t s, const ProveDevRow *rows_dev, uint32_t n, const ProveDeviceIO &io) {
+  ProveEmit e;
+  memset(&e, 0, sizeof(e));
+  e.rows = rows_dev;
+  e.n = n;
+  e.proofs_out = io.proofs_out;
+  e.proof_stride = io.proof_stride;
+  e.commitments_out = io.commitments_out;
+  e.commit_stride = io.commit_stride;
+  e.status_dev = io.status_dev;
+  e.states_out = io.states_out;
+  e.ok_mask = io.ok_mask;
+  e.outcome_item = io.outcome_item;
+  hipLaunchKernelGGL(k_prove_emit, dim3(cdiv(n, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, e);
+  HIP_CHECK(hipGetLastError());
+}
+
 int prove_openings_device(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays *in, uint8_t *commitments_out, size_t commit_stride,
                           uint8_t *proofs_out, size_t proof_stride, size_t *proof_lens, bpp_device_prove_status *status_dev, int *item_status,
                           char *errbuf, size_t errbuf_len, const uint8_t *item_states = nullptr, uint8_t *states_out = nullptr) {
@@ -1354,123 +1441,51 @@ int prove_openings_device(bpp_ctx *ctx, uint64_t params, const bpp_prove_arrays 
     if (!in) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
     // pointer kinds first: nothing is allocated or launched for an array this device cannot reach, and no array is ever
     // dereferenced on the host
-    static const char *const kinds[] = {"", "memory of another device", "host memory or memory the runtime does not know", "managed memory"};
-    const struct {
-      const char *name;
-      const void *p;
-    } arrays[] = {{"values", in->values},
-                  {"blindings32", in->blindings32},
-                  {"commitments32", in->commitments32},
-                  {"min_values", in->min_values},
-                  {"min_present", in->min_present},
-                  {"seed_nonces32", in->seed_nonces32},
-                  {"seed_present", in->seed_present},
-                  {"rng_bytes", in->rng_bytes},
-                  {"commitments_out_dev", commitments_out},
-                  {"proofs_out_dev", proofs_out},
-                  {"status_dev", status_dev},
-                  {"item_states_dev", item_states},
-                  {"states_out_dev", states_out}};
     if (!commitments_out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "commitments_out_dev is null", errbuf, errbuf_len);
     if (!proofs_out) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proofs_out_dev is null", errbuf, errbuf_len);
-    for (const auto &a : arrays) {
-      if (!a.p) continue;
-      const int kind = device_pointer_kind(ctx->device, a.p);
-      if (kind != BPP_PTR_THIS_DEVICE)
-        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + " is not device memory of this context's device (" + kinds[kind] + ")", errbuf,
-                    errbuf_len);
-    }
+    const std::string why = prove_arrays_refusal(ctx, *in, commitments_out, proofs_out, status_dev, item_states, states_out);
+    if (!why.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, why, errbuf, errbuf_len);
     if (!in->m || in->n_items == 0 || !proof_lens) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
-    if (device_pointer_kind(ctx->device, in->m) != BPP_PTR_HOST_OR_UNKNOWN)
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m must be host memory: it sizes the call's layout", errbuf, errbuf_len);
-    if (in->m_stride == 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m_stride is 0", errbuf, errbuf_len);
-    if (ctx->opt.prove_check > 0)
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT,
-                  "prove_check = 1 is not supported by bpp_prove_openings_device: the self-check remakes from host items; verify the outputs "
-                  "with bpp_verify_batch_mixed_device",
-                  errbuf, errbuf_len);
-    if (item_states && (in->transcript_state || in->transcript_label))
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT,
-                  "transcript_state / transcript_label must be null: item i continues row i of item_states_dev", errbuf, errbuf_len);
-    if (item_states && states_out) {  // (n_items <= 2^24 is checked below: a range is at most a few gigabytes, no overflow here)
-      const uintptr_t a = (uintptr_t)item_states, b = (uintptr_t)states_out;
-      const uintptr_t len = (uintptr_t)std::min<size_t>(in->n_items, (size_t)1 << 24) * BPP_ITEM_STATE_BYTES;
-      if (a < b + len && b < a + len)
-        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "item_states_dev and states_out_dev overlap", errbuf, errbuf_len);
-    }
-    if (in->transcript_state && in->transcript_state[200] >= BPP_STROBE_R) return fail(ctx, prove_err(BPP_PROVE_MSG_TRANSCRIPT_STATE).code,
-                                                                                      prove_msg_text(BPP_PROVE_MSG_TRANSCRIPT_STATE), errbuf, errbuf_len);
-    const std::shared_ptr<Params> Pp = params_registry().get(params);
-    if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
+    std::shared_ptr<Params> Pp;
+    if (const int rc = prove_device_refusals(ctx, params, *in, item_states != nullptr, item_states, states_out, Pp, errbuf, errbuf_len)) return rc;
     const size_t n_items = in->n_items;
-    if (n_items > (1u << 24)) return fail(ctx, BPP_ERR_SIZE_OVERFLOW, "batch too large", errbuf, errbuf_len);
-    const ParamShape shape{Pp->n_bits, Pp->m_max, Pp->t};
 
     // the host's part of the checks, per item; the ones that pass by aggregation factor, largest first, in the caller's order
+    ProveDeviceIO io{in, {}, commitments_out, commit_stride, proofs_out, proof_stride, status_dev, {}};
+    io.item_states = item_states;
+    io.states_out = states_out;
+    ProveDeviceShape &sh = io.shape;
     const bool fields_ok = in->values && in->blindings32 && in->rng_bytes && (in->min_values || !in->min_present);
-    std::vector<uint32_t> msg(n_items, BPP_PROVE_MSG_OK);
-    std::map<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> classes;
-    std::vector<ProveDevRow> refused;
-    for (size_t i = 0; i < n_items; i++) {
-      const uint32_t mi = in->m[i];
-      proof_lens[i] = prove_item_len_host(shape, mi);
-      msg[i] = prove_item_layout_finding(shape, mi, proof_stride, true, commit_stride, fields_ok);
-      if (!msg[i] && mi > in->m_stride)  // (an item the layout holds, but not a row of the arrays: the geometry is the call's)
-        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m_stride is below an aggregation factor", errbuf, errbuf_len);
-      if (!msg[i]) msg[i] = prove_item_rng_finding(shape, mi, in->rng_stride);
-      if (!msg[i]) {
-        classes[mi].push_back((uint32_t)i);
-        continue;
-      }
-      uint32_t zero = 0;  // (zeroed where the strides can hold them, as prove_mixed does)
-      if (proof_lens[i] && proof_stride >= proof_lens[i]) zero |= BPP_PROVE_ROW_ZERO_PROOF;
-      if (proof_lens[i] && commit_stride >= (size_t)32 * mi) zero |= BPP_PROVE_ROW_ZERO_COMMIT;
-      refused.push_back(ProveDevRow{(uint32_t)i, mi, (uint32_t)proof_lens[i], msg[i], zero});
-    }
+    const bool fits = prove_device_shape(ParamShape{Pp->n_bits, Pp->m_max, Pp->t}, in->m, n_items, in->m_stride, in->rng_stride, proof_stride,
+                                         commit_stride, fields_ok, sh);
+    std::copy_n(sh.proof_lens.begin(), fits ? n_items : sh.m_stride_below + 1, proof_lens);
+    if (!fits) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m_stride is below an aggregation factor", errbuf, errbuf_len);
+    std::vector<uint32_t> &msg = sh.msg;
     struct bpp_prove_device_stats &stats = ctx->prove_dev_stats;
     stats.calls++;
     stats.items += n_items;
-    stats.host_findings += refused.size();
+    stats.host_findings += sh.refused.size();
     hipStream_t s = ctx->stream;
-    if (!refused.empty()) {
-      ctx->prove_dev_refused.alloc(refused.size() * sizeof(ProveDevRow));
-      HIP_CHECK(hipMemcpyAsync(ctx->prove_dev_refused.p, refused.data(), refused.size() * sizeof(ProveDevRow), hipMemcpyHostToDevice, s));
-      ProveEmit e;
-      memset(&e, 0, sizeof(e));
-      e.rows = (const ProveDevRow *)ctx->prove_dev_refused.p;
-      e.n = (uint32_t)refused.size();
-      e.proofs_out = proofs_out;
-      e.proof_stride = proof_stride;
-      e.commitments_out = commitments_out;
-      e.commit_stride = commit_stride;
-      e.status_dev = status_dev;
-      e.states_out = states_out;  // (a refused item's row is zeroed: its rows carry their finding)
-      hipLaunchKernelGGL(k_prove_emit, dim3(cdiv(e.n, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, e);
-      HIP_CHECK(hipGetLastError());
+    if (!sh.refused.empty()) {
+      ctx->prove_dev_refused.alloc(sh.refused.size() * sizeof(ProveDevRow));
+      HIP_CHECK(hipMemcpyAsync(ctx->prove_dev_refused.p, sh.refused.data(), sh.refused.size() * sizeof(ProveDevRow), hipMemcpyHostToDevice, s));
+      launch_prove_refused(s, (const ProveDevRow *)ctx->prove_dev_refused.p, (uint32_t)sh.refused.size(), io);
       HIP_CHECK(hipStreamSynchronize(s));  // (the table is pageable host memory of this frame)
     }
 
-    ProveDeviceIO io{in, {}, {}, commitments_out, commit_stride, proofs_out, proof_stride, status_dev, {}};
-    io.item_states = item_states;
-    io.states_out = states_out;
-    for (auto &kv : classes)
-      for (uint32_t i : kv.second) {
-        io.m_sorted.push_back(kv.first);
-        io.rows.push_back(ProveDevRow{i, kv.first, (uint32_t)proof_lens[i], BPP_PROVE_MSG_OK, BPP_PROVE_ROW_ZERO_PROOF | BPP_PROVE_ROW_ZERO_COMMIT});
-      }
     std::string engine_err;
     int engine_rc = BPP_OK;
-    if (!io.rows.empty()) {
+    if (!sh.rows.empty()) {
       (void)take_tamper(ctx);  // (the self-check's test knobs name a call that checks: this one does not)
       char err[256];
       err[0] = 0;
-      ProveRequest req{params, nullptr, io.rows.size(), nullptr, 0, nullptr};
+      ProveRequest req{params, nullptr, sh.rows.size(), nullptr, 0, nullptr};
       req.mixed = true;
       req.dev = &io;
       engine_rc = prove_uniform(ctx, req, err, sizeof(err));
       engine_err = err;
-      for (size_t k = 0; k < io.rows.size(); k++) {
-        const uint32_t i = io.rows[k].item;
+      for (size_t k = 0; k < sh.rows.size(); k++) {
+        const uint32_t i = sh.rows[k].item;
         msg[i] = engine_rc != BPP_OK ? BPP_PROVE_MSG_ENGINE : io.outcome[k].msg;
         if (engine_rc == BPP_OK && msg[i] >= BPP_PROVE_MSG_SEED_AGGREGATED && msg[i] <= BPP_PROVE_MSG_TRANSCRIPT_STATE) stats.device_findings++;
       }

@@ -1,9 +1,11 @@
 // Stream-ordered proving from device arrays on a RESIDENT PLAN (bpp_prove_plan_create / bpp_prove_enqueue, include/bpp.h).
 // bpp_prove_openings_device(_transcripts) does per call what depends on nothing but m[], the strides and which arrays are given: the
 // per-item host checks, the sort, the layout, the arena, the staging of the public tables -- and then waits for the device three
-// times over.  A plan does all of that ONCE and keeps it: a ProveCall (engine_prove.h) that lives as long as the plan, over an arena
-// and a page-locked staging of the plan's own.  An enqueue runs the SAME stages -- enqueue_init / enqueue_step / enqueue_finish, launch
-// for launch what the blocking call enqueues -- between a fork from the context's stream and a join back into it, and returns.
+// times over.  A plan does all of that ONCE and keeps it: the blocking call's whole-call refusals (prove_device_refusals,
+// engine_prove.h) and its shape step (prove_device_shape, prove_ingest.h: the result stays in ProveDeviceIO::shape), then a ProveCall
+// (engine_prove.h) that lives as long as the plan, over an arena and a page-locked staging of the plan's own.  An enqueue runs the
+// SAME stages -- enqueue_init / enqueue_step / enqueue_finish, launch for launch what the blocking call enqueues -- between a fork
+// from the context's stream and a join back into it, and returns.
 //
 // What differs from the blocking call, all of it in ProveCall behind `resident`:
 //   - the tables (descriptors, rows, states) are copied from the plan's page-locked memory per enqueue: the arena range they land in
@@ -34,13 +36,10 @@ struct ProvePlan : bpp_ctx::ProvePlanBase {
   bpp_prove_arrays arrays{};
   std::vector<uint32_t> m;
   std::vector<uint8_t> transcript;  // the 203-byte state or the label
-  std::vector<size_t> proof_lens;
-  std::vector<uint32_t> msg;        // per item: the host's finding, 0 for an item that has a slot
-  uint32_t n_refused = 0;
-  DevBuf<uint8_t> refused;          // ProveDevRow x n_refused
+  DevBuf<uint8_t> refused;          // io.shape.refused on the device
   DevBuf<bpp_device_prove_status> outcome_item;
   PinnedBuf<uint8_t> pin;
-  ProveDeviceIO io{};
+  ProveDeviceIO io{};               // (io.shape: the plan's proof lengths, host findings and tables, made once)
   ProveRequest req{};
   std::unique_ptr<ProveCall> call;  // null: the host refused every item
   std::vector<hipEvent_t> join;
@@ -95,24 +94,10 @@ extern "C" int bpp_prove_plan_create(bpp_ctx *ctx, uint64_t params, const bpp_pr
     if (flags & ~BPP_PROVE_PLAN_ITEM_STATES) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "unknown flag", errbuf, errbuf_len);
     const bool per_item = (flags & BPP_PROVE_PLAN_ITEM_STATES) != 0;
     if (!shape->m || shape->n_items == 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument", errbuf, errbuf_len);
-    if (device_pointer_kind(ctx->device, shape->m) != BPP_PTR_HOST_OR_UNKNOWN)
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m must be host memory: it sizes the call's layout", errbuf, errbuf_len);
-    if (shape->m_stride == 0) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m_stride is 0", errbuf, errbuf_len);
-    if (ctx->opt.prove_check > 0)
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT,
-                  "prove_check = 1 is not supported by bpp_prove_openings_device: the self-check remakes from host items; verify the outputs "
-                  "with bpp_verify_batch_mixed_device",
-                  errbuf, errbuf_len);
-    if (per_item && (shape->transcript_state || shape->transcript_label))
-      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "transcript_state / transcript_label must be null: item i continues row i of item_states_dev",
-                  errbuf, errbuf_len);
-    if (shape->transcript_state && shape->transcript_state[200] >= BPP_STROBE_R)
-      return fail(ctx, prove_err(BPP_PROVE_MSG_TRANSCRIPT_STATE).code, prove_msg_text(BPP_PROVE_MSG_TRANSCRIPT_STATE), errbuf, errbuf_len);
-    std::shared_ptr<Params> Pp = params_registry().get(params);
-    if (!Pp || Pp->device != ctx->device) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown params handle", errbuf, errbuf_len);
+    // (the blocking call's refusals, its text for prove_check included)
+    std::shared_ptr<Params> Pp;
+    if (const int rc = prove_device_refusals(ctx, params, *shape, per_item, nullptr, nullptr, Pp, errbuf, errbuf_len)) return rc;
     const size_t n_items = shape->n_items;
-    if (n_items > (1u << 24)) return fail(ctx, BPP_ERR_SIZE_OVERFLOW, "batch too large", errbuf, errbuf_len);
-    const ParamShape ps{Pp->n_bits, Pp->m_max, Pp->t};
 
     auto owned = std::make_unique<ProvePlan>();
     ProvePlan &pl = *owned;
@@ -135,30 +120,13 @@ extern "C" int bpp_prove_plan_create(bpp_ctx *ctx, uint64_t params, const bpp_pr
       pl.arrays.transcript_label = pl.transcript.data();
     }
 
-    // the host's part of the checks, per item, as prove_openings_device runs it per call
+    // the host's part of the checks and the two tables: the shape step (prove_ingest.h), once for the plan's life
     const bool fields_ok = shape->values && shape->blindings32 && shape->rng_bytes && (shape->min_values || !shape->min_present);
-    pl.proof_lens.assign(n_items, 0);
-    pl.msg.assign(n_items, BPP_PROVE_MSG_OK);
-    std::map<uint32_t, std::vector<uint32_t>, std::greater<uint32_t>> classes;
-    std::vector<ProveDevRow> refused;
-    for (size_t i = 0; i < n_items; i++) {
-      const uint32_t mi = pl.m[i];
-      pl.proof_lens[i] = prove_item_len_host(ps, mi);
-      pl.msg[i] = prove_item_layout_finding(ps, mi, proof_stride, true, commit_stride, fields_ok);
-      if (!pl.msg[i] && mi > shape->m_stride)
-        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m_stride is below an aggregation factor", errbuf, errbuf_len);
-      if (!pl.msg[i]) pl.msg[i] = prove_item_rng_finding(ps, mi, shape->rng_stride);
-      if (!pl.msg[i]) {
-        classes[mi].push_back((uint32_t)i);
-        continue;
-      }
-      uint32_t zero = 0;
-      if (pl.proof_lens[i] && proof_stride >= pl.proof_lens[i]) zero |= BPP_PROVE_ROW_ZERO_PROOF;
-      if (pl.proof_lens[i] && commit_stride >= (size_t)32 * mi) zero |= BPP_PROVE_ROW_ZERO_COMMIT;
-      refused.push_back(ProveDevRow{(uint32_t)i, mi, (uint32_t)pl.proof_lens[i], pl.msg[i], zero});
-    }
+    if (!prove_device_shape(ParamShape{Pp->n_bits, Pp->m_max, Pp->t}, pl.m.data(), n_items, shape->m_stride, shape->rng_stride, proof_stride,
+                            commit_stride, fields_ok, pl.io.shape))
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m_stride is below an aggregation factor", errbuf, errbuf_len);
+    const std::vector<ProveDevRow> &refused = pl.io.shape.refused;
     hipStream_t s = ctx->stream;
-    pl.n_refused = (uint32_t)refused.size();
     pl.outcome_item.alloc(n_items);
     HIP_CHECK(hipMemsetAsync(pl.outcome_item.p, 0, n_items * sizeof(bpp_device_prove_status), s));
     if (!refused.empty()) {
@@ -172,14 +140,8 @@ extern "C" int bpp_prove_plan_create(bpp_ctx *ctx, uint64_t params, const bpp_pr
     pl.io.proof_stride = proof_stride;
     pl.io.per_item = per_item;
     pl.io.outcome_item = pl.outcome_item.p;
-    for (auto &kv : classes)
-      for (uint32_t i : kv.second) {
-        pl.io.m_sorted.push_back(kv.first);
-        pl.io.rows.push_back(
-            ProveDevRow{i, kv.first, (uint32_t)pl.proof_lens[i], BPP_PROVE_MSG_OK, BPP_PROVE_ROW_ZERO_PROOF | BPP_PROVE_ROW_ZERO_COMMIT});
-      }
-    if (!pl.io.rows.empty()) {
-      pl.req = ProveRequest{params, nullptr, pl.io.rows.size(), nullptr, 0, nullptr};
+    if (!pl.io.shape.rows.empty()) {
+      pl.req = ProveRequest{params, nullptr, pl.io.shape.rows.size(), nullptr, 0, nullptr};
       pl.req.mixed = true;
       pl.req.dev = &pl.io;
       pl.call.reset(new ProveCall(ctx, *pl.P, pl.req));
@@ -214,8 +176,8 @@ extern "C" int bpp_prove_plan_shape(bpp_ctx *ctx, uint64_t plan, size_t *proof_l
   if (!pl) return fail(ctx, BPP_ERR_BAD_HANDLE, "unknown prove plan");
   if (!proof_lens) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "null argument");
   for (size_t i = 0; i < pl->m.size(); i++) {
-    proof_lens[i] = pl->proof_lens[i];
-    if (host_status) host_status[i] = prove_msg_code(pl->msg[i]);
+    proof_lens[i] = pl->io.shape.proof_lens[i];
+    if (host_status) host_status[i] = prove_msg_code(pl->io.shape.msg[i]);
   }
   return BPP_OK;
 }
@@ -241,32 +203,9 @@ extern "C" int bpp_prove_enqueue(bpp_ctx *ctx, uint64_t plan, const bpp_prove_ar
     // ---- the refusals: nothing is launched, nothing counted, no array dereferenced on the host
     if (!commitments_out_dev) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "commitments_out_dev is null");
     if (!proofs_out_dev) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "proofs_out_dev is null");
-    static const char *const kinds[] = {"", "memory of another device", "host memory or memory the runtime does not know", "managed memory"};
-    const struct {
-      const char *name;
-      const void *p;
-    } arrays[] = {{"values", in_dev->values},
-                  {"blindings32", in_dev->blindings32},
-                  {"commitments32", in_dev->commitments32},
-                  {"min_values", in_dev->min_values},
-                  {"min_present", in_dev->min_present},
-                  {"seed_nonces32", in_dev->seed_nonces32},
-                  {"seed_present", in_dev->seed_present},
-                  {"rng_bytes", in_dev->rng_bytes},
-                  {"commitments_out_dev", commitments_out_dev},
-                  {"proofs_out_dev", proofs_out_dev},
-                  {"status_dev", status_dev},
-                  {"item_states_dev", item_states_dev},
-                  {"states_out_dev", states_out_dev},
-                  {"live_dev", live_dev},
-                  {"ok_mask_dev", ok_mask_dev},
-                  {"summary_dev", summary_dev}};
-    for (const auto &a : arrays) {
-      if (!a.p) continue;
-      const int kind = device_pointer_kind(ctx->device, a.p);
-      if (kind != BPP_PTR_THIS_DEVICE)
-        return fail(ctx, BPP_ERR_INVALID_ARGUMENT, std::string(a.name) + " is not device memory of this context's device (" + kinds[kind] + ")");
-    }
+    const std::string why = prove_arrays_refusal(ctx, *in_dev, commitments_out_dev, proofs_out_dev, status_dev, item_states_dev, states_out_dev,
+                                                 live_dev, ok_mask_dev, summary_dev);
+    if (!why.empty()) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, why);
     const bool per_item = (pl.flags & BPP_PROVE_PLAN_ITEM_STATES) != 0;
     if (item_states_dev && !per_item)
       return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "item_states_dev is given, but the plan was made without BPP_PROVE_PLAN_ITEM_STATES");
@@ -304,21 +243,14 @@ extern "C" int bpp_prove_enqueue(bpp_ctx *ctx, uint64_t plan, const bpp_prove_ar
         if (in_dev->m[i] != pl.m[i])
           return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "m[" + std::to_string(i) + "] differs from the plan's (" + std::to_string(in_dev->m[i]) + " != " + std::to_string(pl.m[i]) + ")");
     }
-    if (item_states_dev && states_out_dev) {
-      const uintptr_t a = (uintptr_t)item_states_dev, b = (uintptr_t)states_out_dev;
-      const uintptr_t len = (uintptr_t)pl.m.size() * BPP_ITEM_STATE_BYTES;
-      if (a < b + len && b < a + len) return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "item_states_dev and states_out_dev overlap");
-    }
+    if (prove_states_overlap(item_states_dev, states_out_dev, pl.m.size()))
+      return fail(ctx, BPP_ERR_INVALID_ARGUMENT, "item_states_dev and states_out_dev overlap");
 
     // ---- the enqueue
     struct bpp_prove_enqueue_stats &es = ctx->prove_enq_stats;
     hipStream_t s = ctx->stream;
     const uint32_t n = (uint32_t)pl.m.size();
-    if (ctx->enq_events.empty()) {  // (the context's first ticket)
-      ctx->enq_events.resize(64);
-      for (auto &e : ctx->enq_events) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      es.allocations++;
-    }
+    if (enqueue_events_ensure(ctx)) es.allocations++;  // (the context's first ticket)
     es.calls++;
     if (!pl.enqueued) es.first_calls++;
     pl.enqueued = true;
@@ -334,22 +266,8 @@ extern "C" int bpp_prove_enqueue(bpp_ctx *ctx, uint64_t plan, const bpp_prove_ar
     pl.io.states_out = states_out_dev;
     pl.io.live = live_dev;
     pl.io.ok_mask = ok_mask_dev;
-    if (pl.n_refused) {  // the refused items' records and zeroed slots, as in front of the blocking call
-      ProveEmit e;
-      memset(&e, 0, sizeof(e));
-      e.rows = (const ProveDevRow *)pl.refused.p;
-      e.n = pl.n_refused;
-      e.proofs_out = proofs_out_dev;
-      e.proof_stride = pl.proof_stride;
-      e.commitments_out = commitments_out_dev;
-      e.commit_stride = pl.commit_stride;
-      e.status_dev = status_dev;
-      e.states_out = states_out_dev;
-      e.ok_mask = ok_mask_dev;
-      e.outcome_item = pl.outcome_item.p;
-      hipLaunchKernelGGL(k_prove_emit, dim3(cdiv(e.n, BPP_INGEST_BLOCK / BPP_INGEST_LANES)), dim3(BPP_INGEST_BLOCK), 0, s, e);
-      HIP_CHECK(hipGetLastError());
-    }
+    // the refused items' records and zeroed slots, as in front of the blocking call; the table is the plan's and stays resident
+    if (const size_t n_refused = pl.io.shape.refused.size()) launch_prove_refused(s, (const ProveDevRow *)pl.refused.p, (uint32_t)n_refused, pl.io);
     if (pl.call) {
       ProveCall &c = *pl.call;
       c.ev_used = 0;
@@ -375,8 +293,7 @@ extern "C" int bpp_prove_enqueue(bpp_ctx *ctx, uint64_t plan, const bpp_prove_ar
                          summary_dev);
       HIP_CHECK(hipGetLastError());
     }
-    const uint64_t t = ctx->enq_next++;
-    HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));
+    const uint64_t t = enqueue_ticket_issue(ctx, s);
     if (ticket) *ticket = t;
     return BPP_OK;
   }

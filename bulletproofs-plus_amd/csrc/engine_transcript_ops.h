@@ -31,10 +31,7 @@ extern "C" int bpp_transcripts_enqueue(bpp_ctx *ctx, uint8_t *states203_dev, siz
     transcript_ops_args(a, states203_dev, n, ops, n_ops, live_dev, done_mask_dev, record_dev);
     struct bpp_transcripts_stats &ts = ctx->tops_stats;
     hipStream_t s = ctx->stream;
-    if (ctx->enq_events.empty()) {  // (the context's first ticket)
-      ctx->enq_events.resize(64);
-      for (auto &e : ctx->enq_events) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
+    (void)enqueue_events_ensure(ctx);
     ts.calls++;
     if (ts.calls == 1) ts.first_calls++;
     if (record_dev) hipLaunchKernelGGL(k_transcript_record_init, dim3(1), dim3(64), 0, s, record_dev);
@@ -45,8 +42,7 @@ extern "C" int bpp_transcripts_enqueue(bpp_ctx *ctx, uint8_t *states203_dev, siz
     if (record_dev && extended) hipLaunchKernelGGL(k_transcript_record_finish_or, dim3(1), dim3(64), 0, s, record_dev);
     else if (record_dev) hipLaunchKernelGGL(k_transcript_record_finish, dim3(1), dim3(64), 0, s, record_dev);
     HIP_CHECK(hipGetLastError());
-    const uint64_t t = ctx->enq_next++;
-    HIP_CHECK(hipEventRecord(ctx->enq_events[t % ctx->enq_events.size()], s));
+    const uint64_t t = enqueue_ticket_issue(ctx, s);
     if (ticket) *ticket = t;
     return BPP_OK;
   }

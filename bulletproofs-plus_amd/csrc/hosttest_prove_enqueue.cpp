@@ -151,18 +151,13 @@ bool run(const char *name, Case &c, uint32_t lanes) {
     g_failures++;
     return false;
   };
-  // the sorted slots: every item passes the host's part (the pattern's m are all legal); largest m first, the caller's order inside
-  std::vector<uint32_t> src;
-  for (uint32_t mm = P.m_max; mm >= 1; mm >>= 1)
-    for (size_t i = 0; i < c.n; i++)
-      if (c.m[i] == mm) src.push_back((uint32_t)i);
-  const uint32_t B = (uint32_t)src.size();
-  std::vector<uint32_t> m_sorted(B);
-  std::vector<ProveDevRow> rows(B);
-  for (uint32_t k = 0; k < B; k++) {
-    m_sorted[k] = c.m[src[k]];
-    rows[k] = ProveDevRow{src[k], m_sorted[k], (uint32_t)prove_item_len_host(P, m_sorted[k]), 0, 3};
-  }
+  // the sorted slots, from the engine's shape step: every item passes the host's part (the pattern's m are all legal)
+  ProveDeviceShape sh;
+  if (!prove_device_shape(P, c.m.data(), c.n, MS, c.rngb.row, SIZE_MAX, SIZE_MAX, true, sh) || sh.rows.size() != c.n)
+    return bad("the host refused an item of the pattern", 0);
+  const std::vector<ProveDevRow> &rows = sh.rows;
+  const std::vector<uint32_t> &m_sorted = sh.m_sorted;
+  const uint32_t B = (uint32_t)rows.size();
   const uint32_t sub = 64;
   ProvePack plan;
   prove_plan_device(P, hg32.data(), m_sorted.data(), B, c.brought, nullptr, c.per_item ? nullptr : (const uint8_t *)"harness", c.per_item ? 0 : 7, plan,
@@ -207,7 +202,7 @@ bool run(const char *name, Case &c, uint32_t lanes) {
       s.n_bits = P.n_bits, s.t = t, s.nb = nb, s.states = dev_states.data() + (size_t)lo * 203;
       prove_item_states_run_host(s);
       std::vector<uint32_t> flags(nb);
-      for (uint32_t i = 0; i < nb; i++) flags[i] = c.live[src[lo + i]] ? 0u : 1u;
+      for (uint32_t i = 0; i < nb; i++) flags[i] = c.live[rows[lo + i].item] ? 0u : 1u;
       s.src = full_rows.data(), s.finding = flags.data(), s.states = ref_states.data() + (size_t)lo * 203;
       prove_item_states_run_host(s);
     }
@@ -222,10 +217,10 @@ bool run(const char *name, Case &c, uint32_t lanes) {
   }
   const uint32_t empty_key = prove_ingest_key(BPP_PROVE_STAGE_LIVE_MASK, 0, BPP_PROVE_MSG_EMPTY);
   for (uint32_t k = 0; k < B; k++) {
-    const bool live = c.live[src[k]] != 0;
+    const bool live = c.live[rows[k].item] != 0;
     if (finding[k] != (live ? 0u : empty_key) || prove_ingest_key_msg(finding[k]) != (live ? BPP_PROVE_MSG_OK : BPP_PROVE_MSG_EMPTY))
-      return bad("finding word differs", src[k]);
-    ref[k] = c.items[src[k]];
+      return bad("finding word differs", rows[k].item);
+    ref[k] = c.items[rows[k].item];
     if (!live) {
       bpp_prove_item &s = ref[k];
       memset(&s, 0, sizeof(s));

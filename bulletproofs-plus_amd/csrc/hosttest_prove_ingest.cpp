@@ -2,7 +2,8 @@
 // openings lie in device memory -- and the host plan, run on the host lane by lane (16 lanes per item as the kernel has them, and
 // one) over a corpus and held to ProvePack::pack and prove_item_check_host on the sorted equivalent items: d_bytes, every ProveDesc
 // field, minvals, minpres and the states are equal, and every finding's {code, message} is what prove_item_check_host throws for
-// that item.  An item with a finding is compared with the substitute the header describes.
+// that item.  An item with a finding is compared with the substitute the header describes.  The host's part -- findings, sort, row
+// tables -- is prove_device_shape, the function the engine runs; the case group `shape` tests it alone.
 // Built with  g++ -fsanitize=address,undefined  into an executable that tests/test_prove_ingest_host.py runs.
 // The rows of an array share one allocation; it ends with the last byte the last row uses, and the slack of every other row is
 // filled with 0xFF -- a value over the capacity, a promise above every value, a blinding factor and a nonce that are not canonical:
@@ -94,11 +95,10 @@ struct Case {
   Case(const ParamShape &P_, const std::vector<Item> &its, Nonces nonces, bool promises, bool brought, size_t rng_stride_, bool use_state)
       : P(P_), n(its.size()), ms(8), rng_stride(rng_stride_) {
     const uint32_t t = P.t;
-    for (const Item &it : its) {
-      m.push_back(it.m);
-      const bool ok = prove_item_layout_finding(P, it.m, SIZE_MAX, true, SIZE_MAX, true) == 0 && it.m <= ms && prove_item_rng_finding(P, it.m, rng_stride) == 0;
-      used.push_back(ok ? it.m : 0);
-    }
+    for (const Item &it : its) m.push_back(it.m);
+    ProveDeviceShape sh;
+    if (!prove_device_shape(P, m.data(), n, ms, rng_stride, SIZE_MAX, SIZE_MAX, true, sh)) abort();  // (no case asks for an m above the stride)
+    for (size_t i = 0; i < n; i++) used.push_back(sh.msg[i] ? 0 : m[i]);
     entries = (n - 1) * (size_t)ms + used[n - 1];
     rng_n = (n - 1) * rng_stride + (used[n - 1] ? rng_need(P, m[n - 1]) : 0);
     values = filled(entries * 8);
@@ -209,9 +209,9 @@ struct Outcome {
   bool operator==(const Outcome &o) const { return code == o.code && msg == o.msg; }
 };
 
-Outcome host_outcome(const ParamShape &P, const bpp_prove_item &it) {
+Outcome host_outcome(const ParamShape &P, const bpp_prove_item &it, size_t proof_stride = SIZE_MAX, size_t commit_stride = SIZE_MAX) {
   try {
-    prove_item_check_host(P, it, SIZE_MAX, true, SIZE_MAX);
+    prove_item_check_host(P, it, proof_stride, true, commit_stride);
   } catch (const ProofErr &e) {
     return Outcome{e.code, e.msg};
   }
@@ -230,29 +230,21 @@ bool run(const char *name, Case &c, uint32_t lanes, const std::vector<uint32_t> 
     g_failures++;
     return false;
   };
-  std::vector<uint32_t> msg(c.n, 0);
-  std::vector<uint32_t> src;
-  // the host's part per item, against the item form on the equivalent item
+  // the host's part per item -- the engine's shape step -- against the item form on the equivalent item
+  ProveDeviceShape sh;
+  if (!prove_device_shape(P, c.m.data(), c.n, c.ms, c.rng_stride, SIZE_MAX, SIZE_MAX, true, sh)) return bad("m_stride is below", sh.m_stride_below);
+  std::vector<uint32_t> msg = sh.msg;
+  const std::vector<uint32_t> &m_sorted = sh.m_sorted;
+  const std::vector<ProveDevRow> &rows = sh.rows;
   for (size_t i = 0; i < c.n; i++) {
-    msg[i] = prove_item_layout_finding(P, c.m[i], SIZE_MAX, true, SIZE_MAX, true);
-    if (!msg[i]) msg[i] = prove_item_rng_finding(P, c.m[i], c.rng_stride);
     if (!msg[i]) continue;
     const Outcome want = host_outcome(P, c.items[i]), got{prove_msg_code(msg[i]), prove_msg_text(msg[i])};
     // the one precedence difference: a nonce on an aggregated item whose rng is also short reports the rng finding here
     const bool documented = msg[i] == BPP_PROVE_MSG_RNG_LEN && want.msg == prove_msg_text(BPP_PROVE_MSG_SEED_AGGREGATED);
     if (!(want == got) && !documented) return bad("host finding differs", i);
   }
-  for (uint32_t mm = P.m_max; mm >= 1; mm >>= 1)
-    for (size_t i = 0; i < c.n; i++)
-      if (!msg[i] && c.m[i] == mm) src.push_back((uint32_t)i);
-  if (src.empty()) return true;
-  const uint32_t B = (uint32_t)src.size();
-  std::vector<uint32_t> m_sorted(B);
-  std::vector<ProveDevRow> rows(B);
-  for (uint32_t k = 0; k < B; k++) {
-    m_sorted[k] = c.m[src[k]];
-    rows[k] = ProveDevRow{src[k], m_sorted[k], (uint32_t)prove_item_len_host(P, m_sorted[k]), 0, 3};
-  }
+  if (rows.empty()) return true;
+  const uint32_t B = (uint32_t)rows.size();
   ProvePack plan;
   prove_plan_device(P, hg32.data(), m_sorted.data(), B, c.in.commitments32 != nullptr, c.in.transcript_state, c.in.transcript_label,
                     c.in.label_len, plan);
@@ -293,15 +285,15 @@ bool run(const char *name, Case &c, uint32_t lanes, const std::vector<uint32_t> 
     memcpy(&g0[32 * (size_t)j], hg32.data() + 32, 32);
   }
   for (uint32_t k = 0; k < B; k++) {
-    const bpp_prove_item &it = c.items[src[k]];
+    const bpp_prove_item &it = c.items[rows[k].item];
     const Outcome want = host_outcome(P, it);
     const uint32_t id = prove_ingest_key_msg(finding[k]);
     const Outcome got{prove_msg_code(id), prove_msg_text(id)};
     if (!(want == got)) {
       printf("  want %d '%s' got %d '%s'\n", want.code, want.msg.c_str(), got.code, got.msg.c_str());
-      return bad("device finding differs", src[k]);
+      return bad("device finding differs", rows[k].item);
     }
-    msg[src[k]] = id;
+    msg[rows[k].item] = id;
     ref[k] = it;
     if (id) {
       bpp_prove_item &s = ref[k];
@@ -495,6 +487,93 @@ void corpus() {
   }
 }
 
+// ---- the shape step itself (prove_device_shape: what the blocking calls and bpp_prove_plan_create run) over
+// m[] = {1, 4, 3, 2, 0, 2 m_max, 1, 4}.  want_msg / want_zero: per item, the finding and (for a refused item) the zero flags.
+struct ShapeCall {
+  uint32_t m_stride;
+  size_t rng_stride, proof_stride, commit_stride;
+  bool fields_ok;
+};
+
+bool shape_holds(const ParamShape &P, const std::vector<uint32_t> &m, const ShapeCall &k, const std::vector<uint32_t> &want_msg,
+                 const std::vector<uint32_t> &want_zero) {
+  auto bad = [&](const char *what, size_t i) {
+    printf("FAIL shape: %s at %zu (m_max %u, t %u, m_stride %u, rng %zu, proof %zu, commit %zu, fields %d)\n", what, i, P.m_max, P.t, k.m_stride,
+           k.rng_stride, k.proof_stride, k.commit_stride, (int)k.fields_ok);
+    g_failures++;
+    return false;
+  };
+  ProveDeviceShape sh;
+  if (!prove_device_shape(P, m.data(), m.size(), k.m_stride, k.rng_stride, k.proof_stride, k.commit_stride, k.fields_ok, sh))
+    return bad("the step stopped", sh.m_stride_below);
+  // the equivalent item: valid openings of its m (read only once every check of part one has passed), rng_stride bytes of randomness
+  const std::vector<uint64_t> values(2 * P.m_max, 0);
+  const std::vector<uint8_t> blind((size_t)2 * P.m_max * P.t * 32, 0), rngb(1, 0);
+  std::vector<uint8_t> has_slot(m.size(), 0);
+  size_t r = 0, slots = 0;
+  for (size_t i = 0; i < m.size(); i++) {
+    if (sh.proof_lens[i] != prove_item_len_host(P, m[i])) return bad("proof length differs", i);
+    bpp_prove_item it{};
+    it.m = m[i], it.values = k.fields_ok ? values.data() : nullptr, it.blindings32 = blind.data(), it.rng_bytes = rngb.data(), it.rng_len = k.rng_stride;
+    const Outcome want = host_outcome(P, it, k.proof_stride, k.commit_stride), got{prove_msg_code(sh.msg[i]), prove_msg_text(sh.msg[i])};
+    if (!(want == got)) return bad("finding differs from prove_item_check_host", i);
+    if (sh.msg[i] != want_msg[i]) return bad("not the expected finding", i);
+    if (!sh.msg[i]) {
+      has_slot[i] = 1, slots++;
+      continue;
+    }
+    if (r == sh.refused.size()) return bad("a refused item is missing from the table", i);
+    const ProveDevRow &x = sh.refused[r++];
+    if (x.item != i || x.m != m[i] || x.proof_len != sh.proof_lens[i] || x.msg != sh.msg[i]) return bad("refused row differs", i);
+    if (x.zero != want_zero[i]) return bad("zero flags differ", i);
+  }
+  if (r != sh.refused.size()) return bad("the refused table holds more than the refused items", r);
+  if (sh.rows.size() != slots || sh.m_sorted.size() != slots) return bad("the slots are not the items without a finding", slots);
+  for (size_t s = 0; s < slots; s++) {
+    const ProveDevRow &x = sh.rows[s];
+    if (x.item >= m.size() || !has_slot[x.item]) return bad("not a permutation of the items without a finding", s);
+    has_slot[x.item] = 0;
+    if (x.m != m[x.item] || sh.m_sorted[s] != x.m || x.proof_len != sh.proof_lens[x.item] || x.msg != 0 ||
+        x.zero != (BPP_PROVE_ROW_ZERO_PROOF | BPP_PROVE_ROW_ZERO_COMMIT))
+      return bad("slot row differs", s);
+    if (s && (sh.rows[s - 1].m < x.m || (sh.rows[s - 1].m == x.m && sh.rows[s - 1].item >= x.item))) return bad("not sorted", s);
+  }
+  return true;
+}
+
+void shape() {
+  const uint32_t POW2 = BPP_PROVE_MSG_POWER_OF_TWO, GEN = BPP_PROVE_MSG_GENERATORS, PS = BPP_PROVE_MSG_PROOF_STRIDE, CS = BPP_PROVE_MSG_COMMIT_STRIDE;
+  const uint32_t RNG = BPP_PROVE_MSG_RNG_LEN, ZP = BPP_PROVE_ROW_ZERO_PROOF, ZC = BPP_PROVE_ROW_ZERO_COMMIT, NUL = BPP_PROVE_MSG_NULL_FIELD;
+  bool ok = true;
+  for (const ParamShape &P : {ParamShape{64, 4, 1}, ParamShape{64, 8, 2}}) {
+    const std::vector<uint32_t> m = {1, 4, 3, 2, 0, 2 * P.m_max, 1, 4};
+    const uint32_t wide = 2 * P.m_max;
+    const size_t full = rng_need(P, P.m_max), len2 = prove_item_len_host(P, 2);
+    // every stride wide enough: 3, 0 and 2 m_max have no proof length and neither flag
+    ok = shape_holds(P, m, {wide, full, SIZE_MAX, SIZE_MAX, true}, {0, 0, POW2, 0, POW2, GEN, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}) && ok;
+    ok = prove_item_len_host(P, 3) == 0 && prove_item_len_host(P, 0) == 0 && prove_item_len_host(P, wide) == 0 && ok;
+    // a proof_stride that holds m = 2: the m = 4 items lose ZERO_PROOF, the m = 2 item -- refused for its rng -- keeps it
+    ok = shape_holds(P, m, {wide, rng_need(P, 2) - 1, len2, SIZE_MAX, true}, {0, PS, POW2, RNG, POW2, GEN, 0, PS}, {0, ZC, 0, ZP | ZC, 0, 0, 0, ZC}) && ok;
+    // the same for a commit_stride of 32 x 2 and ZERO_COMMIT
+    ok = shape_holds(P, m, {wide, rng_need(P, 2) - 1, SIZE_MAX, 64, true}, {0, CS, POW2, RNG, POW2, GEN, 0, CS}, {0, ZP, 0, ZP | ZC, 0, 0, 0, ZP}) && ok;
+    // an rng_stride one byte short of what m = 4 needs: the m = 4 items alone, with the rng finding
+    ok = shape_holds(P, m, {wide, rng_need(P, 4) - 1, SIZE_MAX, SIZE_MAX, true}, {0, RNG, POW2, 0, POW2, GEN, 0, RNG}, {0, ZP | ZC, 0, 0, 0, 0, 0, ZP | ZC}) && ok;
+    // m_stride = 2 stops at the first m = 4 item, the lengths and findings in front of it written ...
+    ProveDeviceShape sh;
+    const bool stopped = !prove_device_shape(P, m.data(), m.size(), 2, full, SIZE_MAX, SIZE_MAX, true, sh) && sh.m_stride_below == 1 &&
+                         sh.proof_lens[0] == prove_item_len_host(P, 1) && sh.proof_lens[1] == prove_item_len_host(P, 4) && sh.msg[0] == 0;
+    if (!stopped) printf("FAIL shape: m_stride = 2 did not stop at item 1 (m_max %u)\n", P.m_max), g_failures++;
+    // ... but not where the layout finding comes first: a proof_stride too short for m = 4
+    ok = shape_holds(P, m, {2, full, len2, SIZE_MAX, true}, {0, PS, POW2, 0, POW2, GEN, 0, PS}, {0, ZC, 0, 0, 0, 0, 0, ZC}) && stopped && ok;
+    // no fields: every item is refused with the layout finding it has then
+    std::vector<uint32_t> none;
+    for (uint32_t mi : m) none.push_back(prove_item_layout_finding(P, mi, SIZE_MAX, true, SIZE_MAX, false));
+    ok = none == std::vector<uint32_t>{NUL, NUL, POW2, NUL, POW2, GEN, NUL, NUL} && ok;
+    ok = shape_holds(P, m, {wide, full, SIZE_MAX, SIZE_MAX, false}, none, {ZP | ZC, ZP | ZC, 0, ZP | ZC, 0, 0, ZP | ZC, ZP | ZC}) && ok;
+  }
+  report("shape", ok);
+}
+
 }  // namespace
 
 int main() {
@@ -502,6 +581,7 @@ int main() {
     g_poison = pass == 1;
     rng.seed(20261020);
     corpus();
+    shape();
   }
   if (g_failures) {
     printf("FAILED %d\n", g_failures);

@@ -175,25 +175,18 @@ bool run(const char *name, Case &c, uint32_t lanes, const std::vector<uint32_t> 
     g_failures++;
     return false;
   };
-  std::vector<uint32_t> msg(c.n, 0), src;
-  std::vector<ProveDevRow> refused;
+  // the engine's shape step (the rows hold rng_stride = what the largest m needs: no rng finding)
+  ProveDeviceShape sh;
+  if (!prove_device_shape(P, c.m.data(), c.n, MS, c.rng_stride, SIZE_MAX, SIZE_MAX, true, sh)) return bad("m_stride is below", sh.m_stride_below);
+  std::vector<uint32_t> msg = sh.msg;
+  const std::vector<ProveDevRow> &refused = sh.refused, &rows = sh.rows;
+  const std::vector<uint32_t> &m_sorted = sh.m_sorted;
   for (size_t i = 0; i < c.n; i++) {
-    msg[i] = prove_item_layout_finding(P, c.m[i], SIZE_MAX, true, SIZE_MAX, true);
     if (!msg[i]) continue;
     const Outcome want = host_outcome(P, c.items[i]), got{prove_msg_code(msg[i]), prove_msg_text(msg[i])};
     if (!(want == got)) return bad("host finding differs", i);
-    refused.push_back(ProveDevRow{(uint32_t)i, c.m[i], 0, msg[i], 0});
   }
-  for (uint32_t mm = P.m_max; mm >= 1; mm >>= 1)
-    for (size_t i = 0; i < c.n; i++)
-      if (!msg[i] && c.m[i] == mm) src.push_back((uint32_t)i);
-  const uint32_t B = (uint32_t)src.size();
-  std::vector<uint32_t> m_sorted(B);
-  std::vector<ProveDevRow> rows(B);
-  for (uint32_t k = 0; k < B; k++) {
-    m_sorted[k] = c.m[src[k]];
-    rows[k] = ProveDevRow{src[k], m_sorted[k], (uint32_t)prove_item_len_host(P, m_sorted[k]), 0, 3};
-  }
+  const uint32_t B = (uint32_t)rows.size();
   // ---- the plan: no state table, slot k of a sub-batch reads row k of the sub-batch's own
   const uint32_t sub = prove_sub_size(B, 0);
   if (sub != 64) return bad("the sub-batch cut is not at 64", B);
@@ -248,15 +241,15 @@ bool run(const char *name, Case &c, uint32_t lanes, const std::vector<uint32_t> 
   for (uint32_t j = 0; j < P.m_max; j++) one_r[(size_t)j * t * 32] = 1;
   std::vector<bpp_prove_item> ref(B);
   for (uint32_t k = 0; k < B; k++) {
-    const bpp_prove_item &it = c.items[src[k]];
+    const bpp_prove_item &it = c.items[rows[k].item];
     const Outcome want = host_outcome(P, it);
     const uint32_t id = prove_ingest_key_msg(finding[k]);
     const Outcome got{prove_msg_code(id), prove_msg_text(id)};
     if (!(want == got)) {
       printf("  want %d '%s' got %d '%s'\n", want.code, want.msg.c_str(), got.code, got.msg.c_str());
-      return bad("device finding differs", src[k]);
+      return bad("device finding differs", rows[k].item);
     }
-    msg[src[k]] = id;
+    msg[rows[k].item] = id;
     ref[k] = it;
     if (id) {
       bpp_prove_item &s = ref[k];
@@ -296,7 +289,7 @@ bool run(const char *name, Case &c, uint32_t lanes, const std::vector<uint32_t> 
   std::vector<uint8_t> status((size_t)B * 4, 0), proofs((size_t)B * 1024, 0x11), commit32((size_t)B * P.m_max * 32, 0x22);
   if (B) emit(rows.data(), B, true, finding.data(), trows.data(), status.data(), proofs.data(), commit32.data(), P.m_max);
   std::vector<int> slot_of(c.n, -1);
-  for (uint32_t k = 0; k < B; k++) slot_of[src[k]] = (int)k;
+  for (uint32_t k = 0; k < B; k++) slot_of[rows[k].item] = (int)k;
   bool rows_ok = out_block[0] == 0xa5;
   for (size_t i = 0; i < c.n; i++) {
     const uint8_t *got = out + i * ROW;

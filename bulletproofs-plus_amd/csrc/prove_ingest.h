@@ -15,6 +15,10 @@
 //     cannot see seed_present; an item with both a nonce at m > 1 and an rng_stride too short for its m reports the rng-length
 //     finding here.  Reachable only with an rng_stride below what the call's largest m needs.
 //
+// The host's part lives HERE as well, once: prove_device_shape (the host section below) runs those two findings per item, refuses a
+// call whose m_stride is below an aggregation factor, sorts the items that pass largest m first and makes the ProveDevRow tables of
+// the slots and of the refused items.  The blocking calls, bpp_prove_plan_create and the three prover harnesses all call it.
+//
 // The layout is the host's (prove_plan_device: ProveDesc rows, roff, mslot, offsets and transcript states from m[] alone, sorted
 // largest m first as prove_mixed sorts); the kernel writes the bytes ProvePack::pack would have written for the sorted items, so that
 // the prover's kernels read nothing new.  A FAILING item is never copied: its slot receives a fixed, public, valid substitute
@@ -368,6 +372,48 @@ inline uint32_t prove_sub_size(uint32_t B, int prove_subs) {
 // the bytes of a sub-batch's state table (ProveCall::carve: d_states): the call's distinct states, or a row per slot
 inline size_t prove_states_table_bytes(const ProvePack &pk, uint32_t per_item_sub, uint32_t nb) {
   return per_item_sub ? (size_t)nb * BPP_ITEM_STATE_BYTES : pk.states.size();
+}
+
+// THE SHAPE STEP of every device form (bpp_prove_openings_device(_transcripts) per call, bpp_prove_plan_create once per plan, and
+// the sanitizer harnesses): what follows from m[], the strides and which arrays are given.  Per item the proof length and the host's
+// part of the checks -- the layout finding, then the rng length -- and from those the two tables the emit and ingest kernels read.
+struct ProveDeviceShape {
+  std::vector<size_t> proof_lens;    // per item: prove_item_len_host
+  std::vector<uint32_t> msg;         // per item: the host's finding, 0 for an item that has a slot
+  std::vector<ProveDevRow> refused;  // the items with a finding, in item order; zeroed where the strides can hold them, as prove_mixed does
+  std::vector<ProveDevRow> rows;     // the slots: largest m first, the caller's order inside a class; msg 0, both zero flags
+  std::vector<uint32_t> m_sorted;    // rows[k].m
+  size_t m_stride_below = 0;         // (a false return) the item the step stopped at
+};
+// false: item sh.m_stride_below passes the layout finding, but its m is above m_stride -- an item the layout holds, but not a row of
+// the arrays: the geometry is the call's, and the whole call is refused.  proof_lens and msg are then filled up to that item.
+inline bool prove_device_shape(const ParamShape &P, const uint32_t *m, size_t n_items, uint32_t m_stride, size_t rng_stride, size_t proof_stride,
+                               size_t commit_stride, bool fields_ok, ProveDeviceShape &sh) {
+  sh = ProveDeviceShape{};
+  sh.proof_lens.assign(n_items, 0);
+  sh.msg.assign(n_items, BPP_PROVE_MSG_OK);
+  for (size_t i = 0; i < n_items; i++) {
+    const uint32_t mi = m[i];
+    const size_t len = sh.proof_lens[i] = prove_item_len_host(P, mi);
+    uint32_t &msg = sh.msg[i];
+    msg = prove_item_layout_finding(P, mi, proof_stride, true, commit_stride, fields_ok);
+    if (!msg && mi > m_stride) {
+      sh.m_stride_below = i;
+      return false;
+    }
+    if (!msg) msg = prove_item_rng_finding(P, mi, rng_stride);
+    if (!msg) {
+      sh.rows.push_back(ProveDevRow{(uint32_t)i, mi, (uint32_t)len, BPP_PROVE_MSG_OK, BPP_PROVE_ROW_ZERO_PROOF | BPP_PROVE_ROW_ZERO_COMMIT});
+      continue;
+    }
+    uint32_t zero = 0;
+    if (len && proof_stride >= len) zero |= BPP_PROVE_ROW_ZERO_PROOF;
+    if (len && commit_stride >= (size_t)32 * mi) zero |= BPP_PROVE_ROW_ZERO_COMMIT;
+    sh.refused.push_back(ProveDevRow{(uint32_t)i, mi, (uint32_t)len, msg, zero});
+  }
+  std::stable_sort(sh.rows.begin(), sh.rows.end(), [](const ProveDevRow &a, const ProveDevRow &b) { return a.m > b.m; });
+  for (const ProveDevRow &r : sh.rows) sh.m_sorted.push_back(r.m);
+  return true;
 }
 
 // What ProvePack::pack makes of the sorted equivalent items, as far as it follows from their aggregation factors alone: the

@@ -630,3 +630,173 @@ def test_refusals_before_any_launch(bpp, engine, packed, opt):
         plan.close()
         plain.close()
     _no_secrets_left(engine)
+
+
+# ---------------------------------------------------------------- 9. the blocking call and the plan: one shape step
+def test_both_forms_one_shape(bpp, engine, packed):
+    """m = [1, 4, 3, 2, 0, 8, 1, 4] under m_max = 4, a proof_stride that holds m = 2 and a commit_stride of 128: the m = 4 items are
+    refused for the stride (their commitment slots are zeroed, their proof slots are not touched), 3, 0 and 8 have no proof length
+    (nothing of theirs is touched).  Lengths, host findings, every output row and every status record: equal between the forms."""
+    t, m_max = 1, 4
+    key = (id(engine), "m_max", m_max, t)
+    if key not in _CACHE:
+        _CACHE[key] = bpp.RangeParameters.init(N, m_max, bpp.create_pedersen_gens_with_extension_degree(t), engine=engine)
+    params = _CACHE[key]
+    ms = [1, 4, 3, 2, 0, 8, 1, 4]
+    refused, stride_refused, proved = [1, 2, 4, 5, 7], [1, 7], [0, 3, 6]
+    d = _data(t, ms, 200)
+    rows = _rows(8)
+    ps, cs = _plen(2, t), 128
+    lens = [_plen(1, t), _plen(4, t), 0, _plen(2, t), 0, 0, _plen(1, t), _plen(4, t)]
+    ref = _blocking(packed, params, _openings(packed, d, rows), 8, ps, cs)
+    assert list(ref.proof_lens) == lens
+    assert [i for i in range(8) if ref.codes[i]] == refused and ref.message == "proof_stride too small"
+    plan = _plan(packed, engine, params, d, ps, cs, rows=True)
+    try:
+        assert list(plan.proof_lens) == lens
+        assert [int(c) for c in plan.host_status] == [int(c) for c in ref.codes]  # (every finding of this call is the host's)
+        out = _enqueue(plan, _openings(packed, d, rows), 8, ps, cs)
+        res = _same(out, ref, plan)
+        assert (res["index"], res["n_ok"], res["n_failed"]) == (1, 3, 5)
+        for form in (ref, out):
+            p, c, s, st = (getattr(form, k).cpu().numpy() for k in ("proofs", "commitments", "states", "status"))
+            assert [int(x) for x in st[:, 1]] == [0, 4, 1, 0, 1, 2, 0, 4]  # proof_stride, power of two, generators
+            assert [int(x) for x in st[:, 0]] == [int(x) for x in ref.codes]
+            for i in stride_refused:  # BPP_PROVE_ROW_ZERO_COMMIT alone
+                assert (p[i] == 0xA5).all() and not c[i].any() and not s[i].any()
+            for i in (2, 4, 5):       # no flag
+                assert (p[i] == 0xA5).all() and (c[i] == 0xA5).all() and not s[i].any()
+            for i in proved:
+                assert (p[i, :lens[i]] != 0xA5).any() and (p[i, lens[i]:] == 0xA5).all()
+                assert (c[i, :32 * ms[i]] != 0xA5).any() and (c[i, 32 * ms[i]:] == 0xA5).all() and s[i].any()
+    finally:
+        plan.close()
+    _no_secrets_left(engine)
+
+
+# ---------------------------------------------------------------- 10. two faults in one call: the earlier refusal wins
+def test_refusal_precedence(bpp, engine, packed, opt):
+    t = 1
+    params = _params(bpp, engine, t)
+    d = _data(t, PATTERN, 210)
+    rows = _rows(5)
+    ps, cs = _plen(8, t), 32 * MS
+    lib = engine.lib
+    plan = _plan(packed, engine, params, d, ps, cs, rows=True)
+    try:
+        inp = _openings(packed, d, rows)
+        o = _fresh(5, ps, cs)
+        dev_m = torch.from_numpy(d["m"].view(np.int32).copy()).cuda()
+        both = torch.zeros(2 * 5 * 203, dtype=torch.uint8, device="cuda")
+        host = np.zeros(5 * 203, dtype=np.uint8)
+        bad_state = np.frombuffer(_transcript(1, 1).strobe.to_bytes(), dtype=np.uint8).copy()
+        bad_state[200] = RATE
+        label = np.frombuffer(LABEL, dtype=np.uint8).copy()
+        torch.cuda.synchronize()
+        stats = lambda: (packed.prove_device_stats(engine), packed.prove_enqueue_stats(engine))  # noqa: E731
+        before = stats()
+        p = lambda v: None if v is None else ctypes.c_void_p(int(v))  # noqa: E731
+        TOO_MANY, UNKNOWN = 2 ** 24 + 1, int(getattr(params.handle, "value", params.handle)) + 1000
+
+        def blocking(needle, rc_want=INVALID_ARGUMENT, handle=params.handle, item_states=inp.item_states, states=None, **fields):
+            st = inp.struct_without_transcript()
+            for k, v in fields.items():
+                setattr(st, k, v)
+            lens = np.zeros(5, dtype=np.uintp)
+            err = ctypes.create_string_buffer(256)
+            rc = lib.bpp_prove_openings_device_transcripts(engine.ctx, handle, ctypes.byref(st), item_states, o["commits"].data_ptr(), cs,
+                                                           o["proofs"].data_ptr(), ps, lens.ctypes.data_as(ctypes.POINTER(ctypes.c_size_t)),
+                                                           p(states), None, None, err, 256)
+            assert rc == rc_want and needle in err.value.decode(), (needle, rc, err.value.decode())
+
+        def create(needle, rc_want=INVALID_ARGUMENT, handle=params.handle, flags=1, **fields):
+            shape = packed._lib.ProveArrays(5, d["m"].ctypes.data, MS, 1, 1, None, 1, 1, 1, 1, 1, d["rng"].shape[1], None, None, 0)
+            for k, v in fields.items():
+                setattr(shape, k, v)
+            made = ctypes.c_uint64()
+            err = ctypes.create_string_buffer(256)
+            rc = lib.bpp_prove_plan_create(engine.ctx, handle, ctypes.byref(shape), cs, ps, flags, ctypes.byref(made), err, 256)
+            if rc == 0:
+                lib.bpp_prove_plan_destroy(engine.ctx, made.value)
+            assert rc == rc_want and needle in err.value.decode(), (needle, rc, err.value.decode())
+
+        # ---- the blocking call, in its order
+        blocking("values is not device memory", values=host.ctypes.data, m=None)
+        blocking("null argument", m=None, m_stride=0)
+        blocking("m must be host memory", m=dev_m.data_ptr(), m_stride=0)
+        opt("prove_check", 1)
+        blocking("m_stride is 0", m_stride=0)
+        blocking("prove_check = 1 is not supported", transcript_label=label.ctypes.data, label_len=len(LABEL))
+        create("m_stride is 0", m_stride=0)
+        create("prove_check = 1 is not supported", transcript_label=label.ctypes.data, label_len=len(LABEL))
+        opt("prove_check", -1)
+        blocking("transcript_state / transcript_label must be null", transcript_state=bad_state.ctypes.data)
+        blocking("transcript state has pos >= rate", item_states=None, transcript_state=bad_state.ctypes.data, handle=UNKNOWN)
+        blocking("overlap", item_states=p(both.data_ptr()), states=both.data_ptr() + 4 * 203, handle=UNKNOWN)
+        blocking("overlap", item_states=p(both.data_ptr()), states=both.data_ptr() + 4 * 203, n_items=TOO_MANY)
+        blocking("unknown params handle", BAD_HANDLE, handle=UNKNOWN, n_items=TOO_MANY)
+        blocking("batch too large", 5, n_items=TOO_MANY)  # (m holds five entries: the cap comes before m is read)
+        blocking("m_stride is below", m_stride=4)
+        # ---- bpp_prove_plan_create, in its order
+        create("unknown flag", flags=3, m=None)
+        create("null argument", m=None, m_stride=0)
+        create("m must be host memory", m=dev_m.data_ptr(), m_stride=0)
+        create("transcript_state / transcript_label must be null", transcript_state=bad_state.ctypes.data)
+        create("transcript state has pos >= rate", flags=0, transcript_state=bad_state.ctypes.data, handle=UNKNOWN)
+        create("unknown params handle", BAD_HANDLE, handle=UNKNOWN, n_items=TOO_MANY)
+        create("batch too large", 5, n_items=TOO_MANY)
+        create("m_stride is below", m_stride=4)
+        # ---- bpp_prove_enqueue: a pointer kind before the plan's own refusals
+        st = inp.struct_without_transcript()
+        st.m, st.n_items = None, 4
+        ticket = ctypes.c_uint64()
+        rc = lib.bpp_prove_enqueue(engine.ctx, plan.handle, ctypes.byref(st), inp.item_states, None, p(o["commits"].data_ptr()),
+                                   p(o["proofs"].data_ptr()), p(o["states"].data_ptr()), p(o["status"].data_ptr()), p(o["ok"].data_ptr()),
+                                   p(host.ctypes.data), ctypes.byref(ticket))
+        msg = (lib.bpp_ctx_last_error(engine.ctx) or b"").decode()
+        assert rc == INVALID_ARGUMENT and "summary_dev is not device memory" in msg, (rc, msg)
+        assert stats() == before  # nothing was counted: nothing was launched
+        for buf in o.values():
+            assert (buf.cpu().numpy().view(np.uint8) == 0xA5).all()
+    finally:
+        plan.close()
+
+
+# ---------------------------------------------------------------- 11. one ticket ring behind every stream call
+def test_seventy_tickets_from_three_issuers(bpp, packed):
+    t, ps, cs = 1, _plen(1, 1), 32 * MS
+    d, rows = _data(t, [1], 220), _rows(1)
+    eng = bpp.Engine(0)
+    params = bpp.RangeParameters.init(N, M_MAX, bpp.create_pedersen_gens_with_extension_degree(t), engine=eng)
+    try:
+        ref = _blocking(packed, params, _openings(packed, d, rows), 1, ps, cs)
+        assert ref.rc == 0, ref.message
+        rb = packed.ResidentBatch.from_mixed(params, ref.as_mixed_input())
+        plan = _plan(packed, eng, params, d, ps, cs, rows=True)
+        inp = _openings(packed, d, rows)
+        row, word = _dev(rows), torch.zeros((1, 4), dtype=torch.uint8, device="cuda")
+        first = rb.enqueue(bounds=[0, 1], states=True)  # (the context's first ticket; the weights bpp_enqueue_weights copies)
+        tickets = [first.ticket]
+        while len(tickets) < 70:
+            k = len(tickets) % 3
+            if k == 0:
+                tickets.append(packed.transcript_ops(eng, row, [packed.TAppend(b"ctx", word)]).ticket)
+            elif k == 1:
+                tickets.append(plan.enqueue(inp, states=True).ticket)
+            else:
+                tickets.append(rb.enqueue_weights().ticket)
+        assert tickets == list(range(tickets[0], tickets[0] + 70))
+        done = ctypes.c_int(-1)
+        lib = eng.lib
+        assert lib.bpp_enqueue_wait(eng.ctx, tickets[-1]) == 0
+        for tk in tickets[-64:]:
+            assert lib.bpp_enqueue_done(eng.ctx, tk, ctypes.byref(done)) == 0 and done.value == 1
+        for tk in (0, tickets[-1] + 1):
+            assert lib.bpp_enqueue_done(eng.ctx, tk, ctypes.byref(done)) == BAD_HANDLE
+            assert lib.bpp_enqueue_wait(eng.ctx, tk) == BAD_HANDLE
+        assert packed.prove_enqueue_stats(eng)["allocations"] == 0  # (the verifier's enqueue made the events)
+        plan.close()
+        rb.close()
+    finally:
+        params.close()
+        eng.close()

@@ -10,14 +10,18 @@ transcript state; every finding kind at the first, a middle and the last item an
 2^n - 1 and of 2^n at n = 32; min == value and min == value + 1; a blinding factor of l - 1, of l and of all ones; a nonce on an
 m = 2 item; a nonce row with seed_present = 0; an rng_stride one byte short for the largest m only (with the one documented
 precedence difference); aggregation factors no statement can have; a call in which every item fails.  Row slack holds 0xFF in one
-pass and is poisoned in the other, and every array ends with the last byte its last row uses."""
+pass and is poisoned in the other, and every array ends with the last byte its last row uses.
+
+The host's part of every case is prove_device_shape, the function the engine's two device forms run; the case group `shape` tests
+it alone over m = [1, 4, 3, 2, 0, 2 m_max, 1, 4]: findings against prove_item_check_host, lengths, the sort, the zero flags of the
+refused items under short strides, the rng finding, the m_stride refusal and its place behind the layout finding, fields_ok."""
 import importlib
 import os
 import subprocess
 
 CASES = ("one_item", "pattern_5", "pattern_17", "pattern_67", "findings_first_middle_last", "two_findings", "value_edges", "minimum_edges",
          "blinding_edges", "nonce_on_an_m2_item", "nonce_with_seed_present_0", "rng_stride_short_for_the_largest_m", "host_findings",
-         "every_item_fails")
+         "every_item_fails", "shape")
 
 
 def test_prove_ingest_equals_the_item_form_under_asan_ubsan():
