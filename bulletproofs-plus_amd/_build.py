@@ -145,6 +145,10 @@ _ASAN_HARNESSES = {
                        "RNG_SCALARS -- in the one-lane model of k_transcript_ops_rng, held to merlin.h's routines and the shared scalar "
                        "routine, with dead rows, the inputs of void rows and all slack poisoned; the void on a zero scalar; the new "
                        "refusals; tests/test_transcript_rng_host.py", [], []),
+    "rows_msm": ("rows_msm.h: the per-row rules and the one-lane models of k_rows_msm and k_rows_scalar (bpp_rows_msm_enqueue, "
+                 "bpp_rows_scalar_enqueue) -- live, void and dead rows, the padded segmented tree, the table-read trace -- held to "
+                 "ct_straus_model, ct_scalarmul and big-integer arithmetic, with dead rows and all slack poisoned; the calls' refusals; "
+                 "tests/test_rows_msm_host.py", ["hosttest.cpp"], []),
 }
 
 
@@ -184,6 +188,7 @@ PROVE_STATES_SANITIZER_BIN, build_prove_states_harness = _asan_bin("prove_states
 PROVE_ENQUEUE_SANITIZER_BIN, build_prove_enqueue_harness = _asan_bin("prove_enqueue"), _asan_builder("prove_enqueue")
 TRANSCRIPT_OPS_SANITIZER_BIN, build_transcript_ops_harness = _asan_bin("transcript_ops"), _asan_builder("transcript_ops")
 TRANSCRIPT_RNG_SANITIZER_BIN, build_transcript_rng_harness = _asan_bin("transcript_rng"), _asan_builder("transcript_rng")
+ROWS_MSM_SANITIZER_BIN, build_rows_msm_harness = _asan_bin("rows_msm"), _asan_builder("rows_msm")
 
 
 if __name__ == "__main__":

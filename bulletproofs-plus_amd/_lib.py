@@ -143,6 +143,27 @@ class TranscriptsStats(Structure):
     _fields_ = [(n, c_uint64) for n in ("calls", "first_calls", "host_waits")]
 
 
+class RowsMsm(Structure):
+    """bpp_rows_msm: n rows of K (scalar, point) terms in device memory; point_stride 0 = one row of K shared bases"""
+    _fields_ = [("n", c_size_t), ("K", c_uint32), ("scalars_dev", c_void_p), ("scalar_stride", c_size_t), ("points_dev", c_void_p),
+                ("point_stride", c_size_t)]
+
+
+class ScalarRows(Structure):
+    """bpp_scalar_rows: one operand of bpp_rows_scalar_enqueue; stride 0 = one 32-byte scalar for every row"""
+    _fields_ = [("dev", c_void_p), ("stride", c_size_t)]
+
+
+class DeviceRowsRecord(Structure):
+    """bpp_device_rows_record: the one record of a bpp_rows_*_enqueue, 16 bytes, as it lies in device memory"""
+    _fields_ = [(n, c_uint32) for n in ("n_done", "n_void", "first_void", "flags")]
+
+
+class RowsStats(Structure):
+    """struct bpp_rows_stats: what the bpp_rows_*_enqueue calls of a context cost the host"""
+    _fields_ = [(n, c_uint64) for n in ("calls", "first_calls", "host_waits")]
+
+
 class ProveDeviceStats(Structure):
     """struct bpp_prove_device_stats: what the prove calls from device arrays of a context came to"""
     _fields_ = [(n, c_uint64) for n in ("calls", "items", "device_findings", "host_findings")]
@@ -335,6 +356,10 @@ SYMBOLS = [
     ("bpp_transcripts_enqueue", c_int, [c_void_p, c_void_p, c_size_t, POINTER(TranscriptOp), c_size_t, c_void_p, c_void_p, c_void_p,
                                         POINTER(c_uint64)]),
     ("bpp_transcripts_stats", c_int, [c_void_p, POINTER(TranscriptsStats)]),
+    ("bpp_rows_msm_enqueue", c_int, [c_void_p, POINTER(RowsMsm), c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
+    ("bpp_rows_scalar_enqueue", c_int, [c_void_p, c_size_t, POINTER(ScalarRows), POINTER(ScalarRows), POINTER(ScalarRows), c_void_p, c_size_t,
+                                        c_void_p, c_void_p, c_void_p, POINTER(c_uint64)]),
+    ("bpp_rows_stats", c_int, [c_void_p, POINTER(RowsStats)]),
     ("bpp_verify_batch_states", c_int, [c_void_p, c_uint64, POINTER(VerifyItem), c_size_t, c_int, c_size_t, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_size_t]),
     ("bpp_verify_batch_packed_states", c_int, [c_void_p, c_uint64, POINTER(PackedBatch), c_int, c_size_t, c_void_p, c_void_p,

@@ -47,6 +47,7 @@
 #include "item_states.h"
 #include "prove_ingest.h"
 #include "transcript_ops.h"
+#include "rows_msm.h"
 
 using namespace bpp;
 
@@ -649,6 +650,13 @@ struct bpp_ctx {
   uint64_t prove_plan_next = 1;
   struct bpp_prove_enqueue_stats prove_enq_stats{};
   struct bpp_transcripts_stats tops_stats{};  // bpp_transcripts_enqueue (engine_transcript_ops.h)
+  // bpp_rows_msm_enqueue / bpp_rows_scalar_enqueue (engine_rows.h): the decoded points of a slab of rows or the shared bases' multiples
+  // -- public data; no scalar is ever copied here -- and the counters of bpp_rows_stats
+  struct RowsWork {
+    DevBuf<niels> pts;
+    DevBuf<uint32_t> bad, base_tab;
+    struct bpp_rows_stats stats{};
+  } rows;
   bpp_prove_profile pprof{};
   // knobs (tests, A/B timing).  -1 = the engine's own rule.  The BPP_* environment variables of the same names are read
   // ONCE, when the context is created (no getenv on any verification path: a host that calls setenv from another thread
@@ -4935,3 +4943,4 @@ int bpp_profile_get(bpp_ctx *ctx, bpp_profile *out) {
 #include "engine_prove_pool.h"
 #include "engine_prove_pipe.h"
 #include "engine_transcript_ops.h"
+#include "engine_rows.h"

@@ -1,4 +1,5 @@
 // Host-compiled probes of the shared host/device arithmetic headers (used only by tests/, CPU suite).
+#include <stdio.h>
 #include <string.h>
 #include "point.h"
 #include "scalar.h"
@@ -19,6 +20,7 @@ static thread_local std::vector<uint8_t> *g_ct_trace = nullptr;
   } while (0)
 #include "ct.h"
 #include "transcript_ops.h"
+#include "rows_msm.h"
 using namespace bpp;
 extern "C" {
 // the scalar routine of challenge_scalar / Scalar::random (transcript_ops.h): 64 wide bytes -> canonical bytes, 1 where zero
@@ -92,6 +94,48 @@ int ht_ct_straus(const uint8_t *scalars32, const uint8_t *points32, size_t n, ui
   if (trace_len) *trace_len = tr.size();
   if (trace_out) memcpy(trace_out, tr.data(), tr.size() < trace_cap ? tr.size() : trace_cap);
   return 1; }
+// rows_msm.h: the host model of k_rows_msm (bpp_rows_msm_enqueue) on host arrays laid out as the call's device arrays; record =
+// {n_done, n_void, first_void, flags}; the trace as in ht_ct_straus, over the whole call.
+void ht_rows_msm(const uint8_t *scalars, size_t scalar_stride, const uint8_t *points, size_t point_stride, size_t n, uint32_t K, uint8_t *out,
+                 size_t out_stride, const uint8_t *live, uint8_t *done_mask, uint32_t record[4], uint8_t *trace_out, size_t trace_cap,
+                 size_t *trace_len) {
+  bpp_rows_msm in{n, K, scalars, scalar_stride, points, point_stride};
+  RowsMsm a;
+  bpp_device_rows_record rec{};
+  rows_msm_args(a, in, out, out_stride, live, done_mask, &rec);
+  std::vector<uint8_t> tr;
+  g_ct_trace = &tr;
+  rows_msm_run_host(a);
+  g_ct_trace = nullptr;
+  if (record) memcpy(record, &rec, 16);
+  if (trace_len) *trace_len = tr.size();
+  if (trace_out) memcpy(trace_out, tr.data(), tr.size() < trace_cap ? tr.size() : trace_cap);
+}
+// ... and of k_rows_scalar (bpp_rows_scalar_enqueue); c may be null
+void ht_rows_scalar(const uint8_t *a, size_t a_stride, const uint8_t *b, size_t b_stride, const uint8_t *c, size_t c_stride, size_t n, uint8_t *out,
+                    size_t out_stride, const uint8_t *live, uint8_t *done_mask, uint32_t record[4]) {
+  const bpp_scalar_rows ra{a, a_stride}, rb{b, b_stride}, rc{c, c_stride};
+  RowsScalar s;
+  bpp_device_rows_record rec{};
+  rows_scalar_args(s, n, &ra, &rb, c ? &rc : nullptr, out, out_stride, live, done_mask, &rec);
+  rows_scalar_run_host(s);
+  if (record) memcpy(record, &rec, 16);
+}
+// the calls' refusals from the arguments alone: the message (empty: nothing to refuse), cut to cap - 1 characters
+void ht_rows_msm_refusal(size_t n, uint32_t K, const uint8_t *scalars, size_t scalar_stride, const uint8_t *points, size_t point_stride,
+                         const uint8_t *out, size_t out_stride, const uint8_t *live, const uint8_t *done_mask, const void *record, char *msg,
+                         size_t cap) {
+  bpp_rows_msm in{n, K, scalars, scalar_stride, points, point_stride};
+  const std::string why = rows_msm_refusal(&in, out, out_stride, live, done_mask, (const bpp_device_rows_record *)record);
+  snprintf(msg, cap, "%s", why.c_str());
+}
+void ht_rows_scalar_refusal(size_t n, const uint8_t *a, size_t a_stride, const uint8_t *b, size_t b_stride, const uint8_t *c, size_t c_stride,
+                            const uint8_t *out, size_t out_stride, const uint8_t *live, const uint8_t *done_mask, const void *record, char *msg,
+                            size_t cap) {
+  const bpp_scalar_rows ra{a, a_stride}, rb{b, b_stride}, rc{c, c_stride};
+  const std::string why = rows_scalar_refusal(n, &ra, &rb, c ? &rc : nullptr, out, out_stride, live, done_mask, (const bpp_device_rows_record *)record);
+  snprintf(msg, cap, "%s", why.c_str());
+}
 // the chunk plan of bpp_msm_ct (ct_plan.h): chunks_out = (group, first, count) triples, chunk_cap of them at most, *n_chunks their
 // number; chunk_off_out (may be null) = n_groups + 1 words.  ct_chunk_plan's code: 0, or -1 for offsets it refuses.
 int ht_ct_chunk_plan(const uint32_t *group_off, size_t n_groups, size_t n_terms, uint32_t K, uint32_t *chunks_out, size_t chunk_cap,

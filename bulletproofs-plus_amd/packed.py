@@ -873,6 +873,135 @@ def transcripts_stats(engine):
     return {k: int(getattr(s, k)) for k, _ in _lib.TranscriptsStats._fields_}
 
 
+ROWS_K_MAX, ROWS_WRITTEN, ROWS_SCALAR, ROWS_POINT = 16, 1, 2, 4  # BPP_ROWS_* of include/bpp.h
+
+
+class RowsEnqueued(TranscriptsEnqueued):
+    """What rows_msm and rows_scalar_muladd return: `.out` (uint8 [n, 32], or whatever was passed), `.done_mask` (uint8 [n]: 1 where the
+    row was written) and `.record` (int32 [4]: n_done, n_void, first_void, flags -- ROWS_WRITTEN | ROWS_SCALAR | ROWS_POINT) -- valid in
+    stream order behind the call -- and the ticket: done(), wait(), result() as for TranscriptsEnqueued."""
+
+    def __init__(self, engine, ticket, out, done_mask, record, keep):
+        TranscriptsEnqueued.__init__(self, engine, ticket, None, [out], done_mask, record, keep)
+        self.out = out
+
+
+class _RowArrays:
+    """the row arrays of one bpp_rows_*_enqueue: addresses, shapes and the ordering of DevicePackedInput"""
+
+    def __init__(self, engine):
+        import torch
+        self.engine, self.torch, self.dev = engine, torch, torch.device("cuda", int(engine.device))
+        self.order = DevicePackedInput.__new__(DevicePackedInput)
+        self.order._keep, self.order.device_index, self.order._torch, self.order.synchronised = [], None, False, False
+
+    def rows(self, a, name):
+        """a uint8 [rows, width] device tensor (stride(0) >= width) or an (address, (rows, width)[, stride]) tuple
+        -> (address, rows, width, stride)"""
+        if isinstance(a, tuple) and len(a) == 3:
+            return int(a[0]), int(a[1][0]), int(a[1][1]), int(a[2])
+        addr, shape, stride = self.order._array(a, name, 1, rows=True)
+        if len(shape) != 2:
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "%s: an array of shape (n, len) expected, got %s" % (name, shape))
+        return addr, shape[0], shape[1], (stride if stride is not None else shape[1])
+
+    def flat(self, a, name, n):
+        if a is None:
+            return None
+        if not hasattr(a, "data_ptr"):
+            return int(a)
+        if a.element_size() != 1 or not a.is_contiguous() or a.numel() != n:
+            raise api.ProofError(api.ProofErrorKind.InvalidArgument, "%s: %d contiguous bytes expected" % (name, n))
+        self.order._keep.append(a)
+        self.order._torch = True
+        return a.data_ptr()
+
+    def outputs(self, n, out, done_mask, record):
+        """-> (out, its address, its stride, done_mask, its address, record, its address), fresh tensors where None"""
+        torch = self.torch
+        if out is None:
+            out = torch.zeros((n, 32), dtype=torch.uint8, device=self.dev)
+        addr_o, rows_o, width_o, stride_o = self.rows(out, "out")
+        if rows_o != n or width_o != 32:
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "out: (%d, 32) expected" % n)
+        if done_mask is None:
+            done_mask = torch.zeros((n,), dtype=torch.uint8, device=self.dev)
+        if record is None:
+            record = torch.zeros((4,), dtype=torch.int32, device=self.dev)
+        addr_rec = record.data_ptr() if hasattr(record, "data_ptr") else int(record)
+        return out, addr_o, stride_o, done_mask, self.flat(done_mask, "done_mask", n), record, addr_rec
+
+
+def rows_msm(engine, scalars, points, K, out=None, live=None, done_mask=None, record=None):
+    """bpp_rows_msm_enqueue: out[i] = sum_{k < K} scalars[i][k] * points[i][k], constant-time in the scalars, on the engine's stream,
+    without waiting.  scalars: a uint8 [n, 32 K] device tensor at any byte address (stride(0) >= 32 K) or an (address, (n, 32 K),
+    stride) tuple -- SECRETS, read where they lie.  points: likewise [n, 32 K], or a tensor of shape [K, 32]: ONE row of K bases shared
+    by every row.  out: uint8 [n, 32] (stride(0) >= 32), a tuple, or None for a fresh tensor.  live: uint8 [n] (0 = dead: nothing of the
+    row is read, its output is zeroed), or None.  A live row with a scalar >= l or a point that does not decode is VOID: zero output,
+    done_mask 0, ROWS_SCALAR / ROWS_POINT in the record.  Ordering as for transcript_ops.  Returns a RowsEnqueued; a refused call raises
+    ProofError with the field named."""
+    ra = _RowArrays(engine)
+    K = int(K)
+    addr_s, n, width_s, stride_s = ra.rows(scalars, "scalars")
+    if width_s != 32 * K:
+        raise api.ProofError(api.ProofErrorKind.InvalidLength, "scalars: rows of 32 K = %d bytes expected, got %d" % (32 * K, width_s))
+    addr_p, rows_p, width_p, stride_p = ra.rows(points, "points")
+    if width_p == 32 and rows_p == K and (K > 1 or n != 1):
+        stride_p = 0  # shared bases
+    elif rows_p != n or width_p != 32 * K:
+        raise api.ProofError(api.ProofErrorKind.InvalidLength, "points: (%d, %d) or (%d, 32) expected, got (%d, %d)" % (n, 32 * K, K, rows_p, width_p))
+    out, addr_o, stride_o, done_mask, addr_done, record, addr_rec = ra.outputs(n, out, done_mask, record)
+    addr_live = ra.flat(live, "live", n)
+    desc = _lib.RowsMsm(n, K, addr_s, stride_s, addr_p, stride_p)
+    ra.order.order_before(engine)
+    ticket = c_uint64()
+    api._check(engine.lib.bpp_rows_msm_enqueue(engine.ctx, byref(desc), addr_o, stride_o, addr_live, addr_done, addr_rec, byref(ticket)), engine.ctx)
+    return RowsEnqueued(engine, ticket.value, out, done_mask, record, (ra.order._keep, desc))
+
+
+def rows_scalar_muladd(engine, a, b, c=None, out=None, live=None, done_mask=None, record=None):
+    """bpp_rows_scalar_enqueue: out[i] = a[i] * b[i] + c[i] mod l, 32 canonical little-endian bytes per row, on the engine's stream,
+    without waiting.  a, b, c: uint8 [n, 32] device tensors at any byte address (stride(0) >= 32), (address, (n, 32), stride) tuples,
+    or a tensor of shape [32] / [1, 32]: one scalar for every row; c None adds nothing.  At least one operand must give n (or pass
+    out).  A non-canonical operand voids the row (ROWS_SCALAR).  out, live, done_mask, record, ordering and the return value as for
+    rows_msm."""
+    ra = _RowArrays(engine)
+    ops, n = [], None
+    for name, x in (("a", a), ("b", b), ("c", c)):
+        if x is None:
+            if name != "c":
+                raise api.ProofError(api.ProofErrorKind.InvalidArgument, "%s: an operand expected" % name)
+            ops.append(None)
+            continue
+        if hasattr(x, "dim") and x.dim() == 1:
+            x = x.reshape(1, -1)
+        addr, rows_x, width, stride = ra.rows(x, name)
+        if width != 32:
+            raise api.ProofError(api.ProofErrorKind.InvalidLength, "%s: rows of 32 bytes expected, got %d" % (name, width))
+        broadcast = rows_x == 1 and not (isinstance(x, tuple) and stride)
+        if not broadcast:
+            if n is not None and rows_x != n:
+                raise api.ProofError(api.ProofErrorKind.InvalidLength, "%s: %d rows, another operand has %d" % (name, rows_x, n))
+            n = rows_x
+        ops.append(_lib.ScalarRows(addr, 0 if broadcast else stride))
+    if n is None:
+        n = 1 if out is None else ra.rows(out, "out")[1]
+    out, addr_o, stride_o, done_mask, addr_done, record, addr_rec = ra.outputs(n, out, done_mask, record)
+    addr_live = ra.flat(live, "live", n)
+    ra.order.order_before(engine)
+    ticket = c_uint64()
+    api._check(engine.lib.bpp_rows_scalar_enqueue(engine.ctx, n, byref(ops[0]), byref(ops[1]), None if ops[2] is None else byref(ops[2]), addr_o,
+                                                  stride_o, addr_live, addr_done, addr_rec, byref(ticket)), engine.ctx)
+    return RowsEnqueued(engine, ticket.value, out, done_mask, record, (ra.order._keep, ops))
+
+
+def rows_stats(engine):
+    """bpp_rows_stats as a dict: calls, first_calls, host_waits"""
+    s = _lib.RowsStats()
+    api._check(engine.lib.bpp_rows_stats(engine.ctx, byref(s)), engine.ctx)
+    return {k: int(getattr(s, k)) for k, _ in _lib.RowsStats._fields_}
+
+
 def device_pointer_kind(engine, address):
     """bpp_device_pointer_check: 0 this engine's device memory, 1 another device's, 2 host or unknown, 3 managed (launches nothing)"""
     kind = ctypes.c_int(-1)

@@ -215,6 +215,74 @@ int bpp_msm_ct_batched(bpp_ctx *ctx, const uint8_t *scalars32, const uint8_t *po
                        size_t n_groups, uint8_t *out_points32 /* n_groups x 32 */);
 int bpp_msm_ct_secret_bytes(bpp_ctx *ctx, uint64_t *examined, uint64_t *nonzero);
 
+/* ---- B1 on the stream: constant-time sums and scalar arithmetic over DEVICE rows ----
+ * What a sigma protocol around a range proof needs between the operations of bpp_transcripts_enqueue, without leaving the context's
+ * stream: the commitment to a nonce that BPP_TOP_RNG_SCALARS drew (R = r G, or r0 H + r1 G0, or a sum over the caller's own bases)
+ * and the response to a challenge that BPP_TOP_CHALLENGE_SCALAR left on the device (s = r + c x mod l).
+ *
+ * bpp_rows_msm_enqueue: out[i] = sum_{k < K} scalars[i][k] * points[i][k] for n rows, K <= BPP_ROWS_K_MAX terms each.  Rows lie at any
+ * byte address; ROW SLACK (a stride above the row length) is neither read nor written.  point_stride == 0: ONE row of K bases shared
+ * by every row of the call (decoded, with their multiples, once per call).
+ *   live row, not void: the 32 bytes bpp_msm_ct_batched writes for a group that holds host copies of the row's K terms -- the
+ *         canonical encoding of the sum, 32 zero bytes for the identity; done_mask[i] = 1; it counts in n_done.
+ *   VOID  a live row with a scalar that is not canonical (>= l: BPP_ROWS_SCALAR) or a point that does not decode (BPP_ROWS_POINT; a
+ *         shared base that does not decode voids every live row): 32 zero bytes, done_mask[i] = 0; it counts in n_void and competes
+ *         for first_void (the lowest index wins); with both causes present both flags are set.  COMPOSITION: the zero row of a void
+ *         row fed to BPP_TOP_APPEND_POINT voids that transcript row (BPP_TOPS_IDENTITY), so a void stays a void down the protocol.
+ *   DEAD  live_dev[i] == 0: nothing of the row's scalars or points is read, its output row is zeroed, done_mask[i] = 0.
+ * REFUSED before any launch (BPP_ERR_INVALID_ARGUMENT, the field named in bpp_ctx_last_error, the counters untouched): n or K out of
+ * range; a stride below the row length (but point_stride == 0) or above 2^40; a NULL scalars_dev, points_dev or out_dev; a pointer
+ * that bpp_device_pointer_check does not class BPP_PTR_THIS_DEVICE; a written range (the out rows, done_mask_dev, record_dev) that
+ * overlaps any other range of the call.  live_dev, done_mask_dev, record_dev and ticket may be NULL as for bpp_transcripts_enqueue.
+ * STEADY STATE: the call enqueues behind everything on the context's stream and returns -- no allocation, no copy to the host, no
+ * wait (bpp_rows_stats' host_waits stays 0).  The decoded points of at most 65536 rows at a time live in a buffer of the context,
+ * sized by the first call of a size; a call that grows it (or makes the ticket events) counts in first_calls.
+ * PUBLIC: n, K, the strides, the points, the live mask, which rows are void.  SECRET: the scalars.  No branch, no global, LDS or
+ * scratch address, no launch geometry and no choice of kernel form depends on a scalar's value (csrc/rows_msm.h: one quad of lanes
+ * per term, the table walk of k_ct_straus); a row's canonicity is decided once, after all K scalars have been looked at; nothing
+ * secret-derived is written to global memory but the output rows -- the row sum is reduced and compressed inside the kernel, the
+ * engine keeps no copy of the scalars -- and the kernel's LDS is wiped.
+ * NOT in this form: K > 16 (bpp_msm_ct_batched), a variable-time form, pool / pipeline / sharded forms.
+ *
+ * bpp_rows_scalar_enqueue: out[i] = a[i] * b[i] + c[i] mod l, 32 canonical little-endian bytes per row, one lane per row.  A stride of
+ * 0 is one 32-byte scalar for every row; c == NULL adds nothing.  A non-canonical operand voids the row (zero output,
+ * BPP_ROWS_SCALAR).  Live, dead, void, record, refusals, steady state as above; every operand is treated as a secret; out_dev may
+ * alias none of the inputs (the overlap rule refuses it). */
+#define BPP_ROWS_K_MAX 16
+typedef struct {
+  size_t n;                   /* rows, 1 .. 2^31 - 1 */
+  uint32_t K;                 /* terms per row, 1 .. BPP_ROWS_K_MAX */
+  const uint8_t *scalars_dev; /* DEVICE: row i = K x 32 bytes at scalars_dev + i * scalar_stride; stride >= 32 K */
+  size_t scalar_stride;
+  const uint8_t *points_dev;  /* DEVICE: row i = K x 32 bytes at points_dev + i * point_stride (>= 32 K), or */
+  size_t point_stride;        /* point_stride == 0: ONE row of K shared bases for every row of the call */
+} bpp_rows_msm;
+typedef struct {
+  uint32_t n_done, n_void;
+  uint32_t first_void; /* 0xFFFFFFFF: none */
+  uint32_t flags;      /* BPP_ROWS_WRITTEN | BPP_ROWS_SCALAR | BPP_ROWS_POINT */
+} bpp_device_rows_record;
+#define BPP_ROWS_WRITTEN 1u
+#define BPP_ROWS_SCALAR 2u /* some live row was voided by a scalar that is not canonical */
+#define BPP_ROWS_POINT 4u  /* ... by a point that does not decode */
+int bpp_rows_msm_enqueue(bpp_ctx *ctx, const bpp_rows_msm *in, uint8_t *out_dev /* DEVICE: row i = 32 bytes at out_dev + i * out_stride */,
+                         size_t out_stride, const uint8_t *live_dev /* DEVICE n bytes, or NULL: every row */,
+                         uint8_t *done_mask_dev /* DEVICE n bytes, or NULL */, bpp_device_rows_record *record_dev /* DEVICE, or NULL */,
+                         uint64_t *ticket /* or NULL; bpp_enqueue_done / bpp_enqueue_wait */);
+typedef struct {
+  const uint8_t *dev; /* DEVICE: row i = 32 bytes at dev + i * stride */
+  size_t stride;      /* >= 32, or 0: one 32-byte scalar for every row */
+} bpp_scalar_rows;
+int bpp_rows_scalar_enqueue(bpp_ctx *ctx, size_t n, const bpp_scalar_rows *a, const bpp_scalar_rows *b,
+                            const bpp_scalar_rows *c /* NULL: + 0 */, uint8_t *out_dev, size_t out_stride, const uint8_t *live_dev,
+                            uint8_t *done_mask_dev, bpp_device_rows_record *record_dev, uint64_t *ticket);
+struct bpp_rows_stats {
+  uint64_t calls;       /* enqueues (of either kind) that passed the refusals */
+  uint64_t first_calls; /* of them, those that made the ticket events or grew a work buffer of the context */
+  uint64_t host_waits;  /* times a call waited for the device: 0 */
+};
+int bpp_rows_stats(bpp_ctx *ctx, struct bpp_rows_stats *out);
+
 /* ---- B2: parameters = RangeParameters::init + BulletproofGens::new + PedersenGens ----
  * (src/range_parameters.rs:32-58, src/generators/bulletproof_gens.rs:83-112, src/ristretto.rs:67-112)
  * h_base32 / g_bases32 may be NULL: the reference's defaults (Ristretto basepoint; SHA3-512 hash-to-group of

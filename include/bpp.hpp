@@ -427,6 +427,35 @@ class Engine {
     return s;
   }
 
+  // B1 on the stream (bpp_rows_msm_enqueue, bpp_rows_scalar_enqueue): what consumes the rows transcripts_enqueue makes.
+  // rows_msm_enqueue: out[i] = sum_{k < K} scalars[i][k] * points[i][k], constant-time in the scalars, K <= BPP_ROWS_K_MAX; a
+  // point_stride of 0 in `in` is one row of K bases shared by every row.  rows_scalar_enqueue: out[i] = a[i] * b[i] + c[i] mod l (c
+  // null: + 0; a stride of 0 is one scalar for every row).  A live row with a non-canonical scalar or an undecodable point is void:
+  // zero output, done_mask 0, BPP_ROWS_SCALAR / BPP_ROWS_POINT in the record.  live, done_mask and record may be null.  Both enqueue
+  // behind everything on the engine's stream and return; the ticket is an enqueue ticket.
+  EnqueueTicket rows_msm_enqueue(const bpp_rows_msm &in, uint8_t *out_dev, size_t out_stride = 32, const uint8_t *live_dev = nullptr,
+                                 uint8_t *done_mask_dev = nullptr, bpp_device_rows_record *record_dev = nullptr) {
+    EnqueueTicket t;
+    t.ctx_ = ctx_;
+    const int rc = bpp_rows_msm_enqueue(ctx_, &in, out_dev, out_stride, live_dev, done_mask_dev, record_dev, &t.id);
+    check(rc, bpp_ctx_last_error(ctx_));
+    return t;
+  }
+  EnqueueTicket rows_scalar_enqueue(size_t n, const bpp_scalar_rows &a, const bpp_scalar_rows &b, const bpp_scalar_rows *c, uint8_t *out_dev,
+                                    size_t out_stride = 32, const uint8_t *live_dev = nullptr, uint8_t *done_mask_dev = nullptr,
+                                    bpp_device_rows_record *record_dev = nullptr) {
+    EnqueueTicket t;
+    t.ctx_ = ctx_;
+    const int rc = bpp_rows_scalar_enqueue(ctx_, n, &a, &b, c, out_dev, out_stride, live_dev, done_mask_dev, record_dev, &t.id);
+    check(rc, bpp_ctx_last_error(ctx_));
+    return t;
+  }
+  struct bpp_rows_stats rows_stats() const {
+    struct bpp_rows_stats s{};
+    check(::bpp_rows_stats(ctx_, &s), bpp_ctx_last_error(ctx_));
+    return s;
+  }
+
  private:
   bpp_ctx *ctx_ = nullptr;
 };

@@ -216,6 +216,50 @@ pub struct bpp_transcripts_stats {
     pub host_waits: u64,
 }
 
+/// bpp_rows_msm: n rows of K (scalar, point) terms in device memory for `bpp_rows_msm_enqueue`; `point_stride == 0`: one row of K shared bases
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+#[allow(non_snake_case)]
+pub struct bpp_rows_msm {
+    pub n: usize,
+    pub K: u32,
+    pub scalars_dev: *const u8,
+    pub scalar_stride: usize,
+    pub points_dev: *const u8,
+    pub point_stride: usize,
+}
+pub const BPP_ROWS_K_MAX: u32 = 16;
+
+/// bpp_scalar_rows: one operand of `bpp_rows_scalar_enqueue`; `stride == 0`: one 32-byte scalar for every row
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct bpp_scalar_rows {
+    pub dev: *const u8,
+    pub stride: usize,
+}
+
+/// bpp_device_rows_record: the one record of a `bpp_rows_*_enqueue`, 16 bytes, as it lies in device memory
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_device_rows_record {
+    pub n_done: u32,
+    pub n_void: u32,
+    pub first_void: u32,
+    pub flags: u32,
+}
+pub const BPP_ROWS_WRITTEN: u32 = 1;
+pub const BPP_ROWS_SCALAR: u32 = 2;
+pub const BPP_ROWS_POINT: u32 = 4;
+
+/// `struct bpp_rows_stats`: what the `bpp_rows_*_enqueue` calls of a context cost the host
+#[repr(C)]
+#[derive(Default, Clone, Copy, Debug)]
+pub struct bpp_rows_stats {
+    pub calls: u64,
+    pub first_calls: u64,
+    pub host_waits: u64,
+}
+
 #[repr(C)]
 pub struct bpp_comm {
     _p: [u8; 0],
@@ -638,6 +682,12 @@ extern "C" {
                                    live_dev: *const u8, done_mask_dev: *mut u8, record_dev: *mut bpp_device_transcripts_record,
                                    ticket: *mut u64) -> c_int;
     pub fn bpp_transcripts_stats(ctx: *mut bpp_ctx, out: *mut bpp_transcripts_stats) -> c_int;
+    pub fn bpp_rows_msm_enqueue(ctx: *mut bpp_ctx, input: *const bpp_rows_msm, out_dev: *mut u8, out_stride: usize, live_dev: *const u8,
+                                done_mask_dev: *mut u8, record_dev: *mut bpp_device_rows_record, ticket: *mut u64) -> c_int;
+    pub fn bpp_rows_scalar_enqueue(ctx: *mut bpp_ctx, n: usize, a: *const bpp_scalar_rows, b: *const bpp_scalar_rows, c: *const bpp_scalar_rows,
+                                   out_dev: *mut u8, out_stride: usize, live_dev: *const u8, done_mask_dev: *mut u8,
+                                   record_dev: *mut bpp_device_rows_record, ticket: *mut u64) -> c_int;
+    pub fn bpp_rows_stats(ctx: *mut bpp_ctx, out: *mut bpp_rows_stats) -> c_int;
     pub fn bpp_verify_batch_states(ctx: *mut bpp_ctx, params: u64, items: *const bpp_verify_item, n_items: usize, action: c_int, chunk: usize,
                                    masks_out: *mut u8, mask_present: *mut u8, states_out203: *mut u8, errbuf: *mut c_char,
                                    errbuf_len: usize) -> c_int;

@@ -289,6 +289,43 @@ def transcript_rng_section():
     return out + [""]
 
 
+def rows_msm_section():
+    """profiles/rows_msm.json (tools/bench_rows_msm.py): bpp_rows_msm_enqueue against the host-hop route through bpp_msm_ct_batched, the call
+    alone and inside the commit / challenge / response step; "kernels": registers, scratch and LDS from the build"""
+    f = os.path.join(P, "rows_msm.json")
+    out = ["## Constant-time sums over device rows: `bpp_rows_msm_enqueue` against the host hop (`tools/bench_rows_msm.py`, "
+           "`profiles/rows_msm.json`)", ""]
+    if not os.path.exists(f):
+        return out + ["unmeasured", ""]
+    doc = json.load(open(f))
+    out += ["One thread, an engine on torch's stream.  Device: calls back to back for a window of %.1f s around one stream synchronise.  Host hop: "
+            "the parent commit's route for the same rows -- the scalars copied down, `bpp_msm_ct_batched` (`k_ct_straus<1>`, one workgroup per "
+            "output; its own upload, wait and download), the outputs copied up.  The arms alternate, %d rounds; median (lowest-highest round).  "
+            "Both routes gave the same bytes.  Nothing was promised.  Box: \"%s\"." % (doc["window_s"], doc["reps"], doc["box"]), "",
+            "| rows | case | device ms per call | device us per output | host hop ms per step | host hop us per output | host hop / device |",
+            "|---|---|---|---|---|---|---|"]
+    for c in doc["cases"]:
+        out.append("| %d | K = %d, %s | %.4f (%.4f-%.4f) | %.4f | %.3f (%.3f-%.3f) | %.4f | %.2f |" %
+                   (c["n"], c["K"], "shared bases" if c["shared"] else "per-row points", c["device_ms_per_call"], c["device_ms_low"],
+                    c["device_ms_high"], c["device_us_per_output"], c["host_hop_ms_per_step"], c["host_hop_ms_low"], c["host_hop_ms_high"],
+                    c["host_hop_us_per_output"], c["host_hop_over_device"]))
+    st = doc.get("step")
+    if st:
+        out += ["", "The commit / challenge / response step (transcript + `RNG_SCALARS` -> r; R = r G; `APPEND_POINT` X, R, `CHALLENGE_SCALAR` -> c; "
+                "s = c x + r) at %d rows, the arms alternating, %d rounds of %d steps; median of the rounds' medians (lowest-highest round):" %
+                (st["items"], st["reps"], st["inner"]), "", "| arm | ms per step | rows/s |", "|---|---|---|"]
+        for k, a in st["arms"].items():
+            out.append("| %s | %.3f (%.3f-%.3f) | %.0f |" % (k.replace("_", " "), a["ms_per_step"], a["ms_low"], a["ms_high"], a["rows_per_s"]))
+        out += ["", "host hops / device: %.2f.  Host waits inside the calls over the whole run: rows %d (of %d calls, %d of them first calls), "
+                "transcripts %d." % (st["host_hops_over_device"], st["stats"]["rows"]["host_waits"], st["stats"]["rows"]["calls"],
+                                     st["stats"]["rows"]["first_calls"], st["stats"]["transcripts"]["host_waits"])]
+    if doc.get("kernels"):
+        out += ["", "| kernel (from the build) | VGPRs | SGPRs | scratch bytes | LDS bytes |", "|---|---|---|---|---|"]
+        for k in doc["kernels"]:
+            out.append("| `%s` | %d | %d | %d | %d |" % (k["kernel"], k["vgpr"], k["sgpr"], k["scratch"], k["lds"]))
+    return out + [""]
+
+
 def main():
     tag = sys.argv[1] if len(sys.argv) > 1 else "r03_v1"
     out = ["# RESULTS — measured figures (generated by `tools/results_table.py %s` from `profiles/`; do not edit)" % tag, "",
@@ -584,6 +621,7 @@ def main():
     out += prove_enqueue_section()
     out += transcript_ops_section()
     out += transcript_rng_section()
+    out += rows_msm_section()
     ks, fks = load(tag, "kernel_stats_cfg2_default.csv")
     sq, fsq = load(tag, "pmc_sq_summary.csv")
     if ks:
