@@ -4,6 +4,7 @@ Inputs follow the reference's own test recipe (tests/ristretto.rs:152-227, bench
 next_u64 % 2^(n-1), one random non-zero blinding repeated t times, seed nonce iff m == 1, transcript label
 "BatchedRangeProofTest".  The PRNG is SHAKE256-based (the reference's ChaCha12 stream is not reproducible here and no
 test of the reference depends on its actual bytes)."""
+import contextlib
 import hashlib
 import types
 
@@ -173,6 +174,172 @@ def replay_verifier_state(tr, n_bits, t, pc, commitments, mins, raw):
     rpt.challenge_final_e(proof.a1, proof.b)
     rpt.to_verifier_rng(proof.r1, proof.s1, proof.d1)
     return tr.strobe.to_bytes()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Chosen challenges (tests/test_verify_edges_host.py checks the families on the oracle, tests/test_gpu_verify_edges.py runs them
+# through bpp_verify_batch_with_challenges).  The protocol is complete for ANY non-zero challenges (and y != 1): an
+# honest prover run under forced challenges gives a proof that verifies under the same challenges exactly when every scalar of
+# the verifier's PASS 2 and every MSM scalar is right.
+MONT_R = 1 << 261  # csrc/scalar.h: nine 29-bit limbs
+
+
+def mont_preimage(v):
+    """the x whose Montgomery form x * 2^261 mod l is v"""
+    return v * pow(MONT_R, -1, C.L) % C.L
+
+
+# the ten values of the CPU experiment first (EDGE_SCALARS[:10]), then the limb-boundary ones
+EDGE_SCALARS = [
+    ("1", 1), ("2", 2), ("l-1", C.L - 1), ("l-2", C.L - 2), ("2^252", 1 << 252), ("(l+1)/2", (C.L + 1) // 2),
+    ("mont^-1(1)", mont_preimage(1)), ("mont^-1(l-1)", mont_preimage(C.L - 1)), ("mont^-1(2^252-1)", mont_preimage((1 << 252) - 1)),
+    ("mont^-1(2^252)", mont_preimage(1 << 252)),
+    ("(l-1)/2", (C.L - 1) // 2), ("2^29-1", (1 << 29) - 1), ("2^29", 1 << 29), ("2^58", 1 << 58), ("2^232-1", (1 << 232) - 1),
+    ("mont^-1(l-2)", mont_preimage(C.L - 2)), ("mont^-1(2^29-1)", mont_preimage((1 << 29) - 1)),
+]
+# name -> the image the entry claims under x -> x * 2^261 mod l
+EDGE_MONT_IMAGES = {"mont^-1(1)": 1, "mont^-1(l-1)": C.L - 1, "mont^-1(2^252-1)": (1 << 252) - 1, "mont^-1(2^252)": 1 << 252,
+                    "mont^-1(l-2)": C.L - 2, "mont^-1(2^29-1)": (1 << 29) - 1}
+
+
+class ForcedRecord:
+    """what the patched _challenge_scalar returned, one list per proof: [y, z, e_0.., e_final]"""
+
+    def __init__(self):
+        self.returned = []
+
+
+@contextlib.contextmanager
+def forced_challenges(rows):
+    """Inside the block O._challenge_scalar still squeezes the transcript (so every later challenge, the transcript RNG and the
+    verifier's weights stay functions of the proof) but returns rows[i][k] for challenge k of the i-th proof that passes through
+    it, where that entry is not None.  A proof starts at its `y`; proofs past the end of `rows` keep their hashed values.  Yields
+    a ForcedRecord; the original function is back on exit."""
+    rows = [list(r) if r is not None else None for r in rows]
+    assert all(v is None or 0 < v < C.L for r in rows if r is not None for v in r)
+    orig, rec = O._challenge_scalar, ForcedRecord()
+
+    def patched(t, label):
+        v = orig(t, label)
+        if label == b"y":
+            rec.returned.append([])
+        i, k = len(rec.returned) - 1, len(rec.returned[-1])
+        if i < len(rows) and rows[i] is not None:
+            assert k < len(rows[i]), "row %d is shorter than the proof's challenges" % i
+            if rows[i][k] is not None:
+                v = rows[i][k]
+        rec.returned[-1].append(v)
+        return v
+
+    O._challenge_scalar = patched
+    try:
+        yield rec
+    finally:
+        O._challenge_scalar = orig
+
+
+def oracle_verify_forced(c, row, action, private=None):
+    """the oracle's verify() of case c's proof with the challenges of `row` -> (masks as bytes | None, ProofError | None, trace)"""
+    private = (action != 0) if private is None else private
+    trace = {}
+    with forced_challenges([row]):
+        try:
+            masks = O.verify([M.Transcript(c.label)], [c.o_statement_private if private else c.o_statement_public], [c.o_proof],
+                             action, trace=trace)
+        except O.ProofError as e:
+            return None, e, trace
+    return [[sb(x) for x in m] if m is not None else None for m in masks], None, trace
+
+
+def edge_challenge_case(n, m, t, row, seed, m_max=None, name=None):
+    """One statement, witness and oracle proof made under the forced `row` ([y, z, e_0.., e_final], None = hashed), and what
+    verify_batch_with_challenges needs to check it: c.challenges (one list of 32-byte scalars: the values the oracle's verifier
+    was handed), c.rng_outputs (from the oracle's trace), c.expected_masks (the oracle's, under RecoverAndVerify for m == 1 and
+    VerifyOnly otherwise) and the oracle objects.  The oracle's own verdict under the row is c.oracle_error (None: accepted)."""
+    rounds = (n * m).bit_length() - 1
+    assert len(row) == rounds + 3
+    rng = Prng(seed)
+    c = Case()
+    c.name = name or "row"
+    c.bit_length, c.m, c.t, c.m_max, c.label, c.row = n, m, t, m_max or m, LABEL, list(row)
+    c.o_params = O.RangeParameters(n, c.m_max, O.PedersenGens(t))
+    openings, commitments, mins = [], [], []
+    for _ in range(m):
+        v = rng.next_u64() % (1 << (n - 1))
+        blind = [O.random_not_zero(rng) for _ in range(t)]
+        mins.append(v // 3)
+        commitments.append(c.o_params.pc_gens.commit(v, blind))
+        openings.append(O.CommitmentOpening(v, blind))
+    c.o_witness = O.RangeWitness(openings)
+    sn = O.random_not_zero(rng) if m == 1 else None
+    c.o_statement_private = O.RangeStatement(c.o_params, commitments, mins, sn)
+    c.o_statement_public = O.RangeStatement(c.o_params, commitments, mins, None)
+    with forced_challenges([row]) as made:
+        c.o_proof = O.prove_with_rng(M.Transcript(c.label), c.o_statement_private, c.o_witness, rng)
+    c.action = 1 if m == 1 else 0
+    with forced_challenges([row]) as seen:
+        trace = {}
+        try:
+            masks = O.verify([M.Transcript(c.label)], [c.o_statement_private if m == 1 else c.o_statement_public], [c.o_proof],
+                             c.action, trace=trace)
+            c.oracle_error = None
+            c.expected_masks = [[sb(x) for x in mk] if mk is not None else None for mk in masks]
+        except O.ProofError as e:
+            c.oracle_error, c.expected_masks = e, None
+    assert seen.returned == made.returned and len(seen.returned[0]) == len(row)
+    assert all(f is None or f == v for f, v in zip(row, seen.returned[0]))
+    c.values = list(seen.returned[0])  # every position, forced or hashed
+    c.challenges = [[sb(v) for v in c.values]]
+    c.rng_outputs = list(trace["rng_outputs"])
+    c.witness_masks = [[sb(x) for x in openings[0].r]] if m == 1 else [None]
+    return c
+
+
+EDGE_POSITION_CLASSES = ("y", "z", "e_all", "e_first", "e_last", "e_final")
+
+
+def _edge_rows(rounds):
+    """(family, case name, row) for every family of a proof with `rounds` rounds"""
+    width = rounds + 3
+    where = {"y": [0], "z": [1], "e_all": list(range(2, 2 + rounds)), "e_first": [2], "e_last": [1 + rounds], "e_final": [2 + rounds]}
+    for cls in EDGE_POSITION_CLASSES:
+        for vname, v in EDGE_SCALARS:
+            if cls == "y" and v == 1:
+                continue  # SURVEY q10: the one non-zero challenge the verifier is not complete for (edge_y_one_case)
+            row = [None] * width
+            for k in where[cls]:
+                row[k] = v
+            yield cls, "%s=%s" % (cls, vname), row
+    yield "all_edge", "all=l-1", [C.L - 1] * width
+    # y sits at an even index: it gets l-1, never the excluded 1
+    yield "all_edge", "alternating", [(C.L - 1, 1)[k & 1] for k in range(width)]
+
+
+_EDGE_CACHE = {}
+
+
+def edge_challenge_families(n, m, t, m_max=None, seed=b"edge", only=None):
+    """{family: [cases]}: one case per (position class, edge value) -- y, z, every e_j, the first e_j alone, the last e_j alone,
+    e_final -- and the family "all_edge" of two rows: every position l-1, and positions alternating l-1, 1 (its second case).
+    `only`: the families to make (the others are left out of the dict).  Proving in Python is the cost, so the cases of a
+    (shape, seed) are made once per process and shared by every test that asks; nobody changes them."""
+    key = (n, m, t, m_max, seed)
+    made = _EDGE_CACHE.setdefault(key, {})
+    rounds = (n * m).bit_length() - 1
+    out = {}
+    for i, (fam, name, row) in enumerate(_edge_rows(rounds)):
+        if only is not None and fam not in only:
+            continue
+        if name not in made:
+            made[name] = edge_challenge_case(n, m, t, row, seed + b"-%d" % i, m_max, name)
+        out.setdefault(fam, []).append(made[name])
+    return out
+
+
+def edge_y_one_case(n, m, t, seed=b"edge-y1"):
+    """a proof made under y = 1"""
+    rounds = (n * m).bit_length() - 1
+    return edge_challenge_case(n, m, t, [1] + [None] * (rounds + 2), seed, name="y=1")
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

@@ -31,6 +31,8 @@ def _buf(n=32):
 
 EDGE_FE = [0, 1, 2, P - 1, P - 2, P, P + 1, 2**255 - 1, 2**255 - 20, 2**254, 19, 2**26 - 1, 2**51]
 EDGE_SC = [0, 1, L - 1, L - 2, 2, L, L + 1, 2**256 - 1, 2**252, 2**253 - 1]
+# the chosen challenges of tests/test_gpu_verify_edges.py (limb boundaries of the nine 29-bit limbs, Montgomery-form edges)
+EDGE_SC += [v for _, v in H.EDGE_SCALARS if v not in EDGE_SC]
 
 
 def test_field(ht):
